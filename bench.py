@@ -14,7 +14,9 @@ synthetic 10 s / 16 kHz audio on the 16k-nq32ds640 architecture:
 `--workload freqcodec` is a SIDE measurement of the next scope row (BASELINE.json configs[3]: the STFT-domain FreqCodec recipe, 64 x 10 s
 on one GPU); the contract metric stays the default.
 Inputs are resident in HBM when timing starts.  The timed region runs WITHOUT the in-engine HIP-event brackets; the per-kernel
-table (and with it `roofline`) comes from a second, separate pass of the same step.  Rank 0 prints ONE JSON line.
+table (and with it `roofline`) comes from a second, separate pass of the same step.  Rank 0 prints ONE compact JSON line
+(contract_line); `--detail-json FILE` writes the full record (per-kernel tables, every roofline object) next to it.
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -22,10 +24,12 @@ import os
 import statistics
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 # utterances per engine call.  N = 1 is Config B itself (16 utterances, one call).  For N > 1 (Config C, 128 per GPU) the micro-batch
@@ -44,6 +48,8 @@ SUSTAINED_GHZ, NOMINAL_GHZ = 2.31, 2.40
 PEAK_F32_SUSTAINED = PEAK_F32_TFLOPS * SUSTAINED_GHZ / NOMINAL_GHZ
 RIDGE = PEAK_F32_TFLOPS / PEAK_HBM_TBS      # FLOP per byte above which the fp32 roof is the tighter one
 CONV_CLASSES = ("conv_", "reshead_", "gconv")   # kernel classes of the conv / transposed-conv layers (fc_engine_profile names)
+DUMP_BYTES = 60_000_000     # --dump-outputs: array bytes of all files together (64 MB with the .npy headers)
+CAT_DIMS = dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0)   # batch axis of each encode_decode output
 
 
 def physical_cores() -> int:
@@ -316,6 +322,53 @@ def kernel_rooflines(prof, prof_steps, pmc_tag: str = ""):
     out["accounting_errors"] = [k["kernel"] for k in kern if k.get("hbm_frac_invalid")]    # must be empty
     return out
 
+
+def _scalars(d, drop=()):
+    return {k: v for k, v in d.items() if not isinstance(v, (dict, list)) and k not in drop}
+
+
+def contract_line(out):
+    """The ONE line bench.py prints, reduced from the full record: its scalars and small objects (config, whole_step, transfers,
+    multi_gpu), the scalars of `roofline` (+ its conv class) and of `cpu_baseline`, and per secondary workload its scalars and roofline
+    fraction.  The line has to stay short enough for the harness that parses it (a 20 KB line was not taken, 15 KB was); the per-kernel
+    tables, the other roofline objects and the notes stay in the full record (--detail-json)."""
+    line = {k: v for k, v in out.items()
+            if not isinstance(v, (dict, list)) or k in ("config", "whole_step", "transfers", "multi_gpu", "accounting_errors")}
+    if out.get("roofline"):
+        rl = out["roofline"]
+        line["roofline"] = _scalars(rl, ("note",))
+        if rl.get("traffic_detail"):
+            line["roofline"]["traffic_from"] = "profiles/" + rl["traffic_detail"]["source"]
+        if rl.get("conv_class"):
+            line["roofline"]["conv_class"] = _scalars(rl["conv_class"])
+    if out.get("cpu_baseline"):
+        line["cpu_baseline"] = _scalars(out["cpu_baseline"])
+        line["cpu_baseline"]["port_over_reference"] = (out["cpu_baseline"].get("port_over_reference") or {}).get("ratio")
+    if out.get("secondary"):
+        line["secondary"] = {name: {**_scalars(s, ("workload",)), "frac": (s.get("roofline") or {}).get("frac")}
+                             for name, s in out["secondary"].items()}
+    return line
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays a caller of the timed path received in its last step, as <dirname>/<name>.npy.  float32 stays float32;
+    every other dtype (the int64 code indices) becomes float64, which holds it exactly.  Smallest arrays first, each one whole while it
+    fits DUMP_BYTES; an array that does not is replaced by a fixed sample of its elements (flat positions drawn without replacement by a
+    generator seeded from its name, in ascending order), so that two builds run with the same arguments compare file for file."""
+    os.makedirs(dirname, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        items.append((name, a if a.dtype == np.float32 else a.astype(np.float64)))
+    left = DUMP_BYTES
+    for name, a in sorted(items, key=lambda it: it[1].nbytes):
+        if a.nbytes > left:
+            pick = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, size=left // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def config_c_shard_side(eng, n_q: int, utts: int = 128, micro: int = 32, steps: int = 3, warmup: int = 1):
     """The per-rank work of BASELINE.json configs[2] on ONE GPU: 128 x 10 s utterances walked in micro-batches of 32 -- exactly what each
     rank of `--gpus N` (N > 1) does per step, minus the all_gather of the codes.  It is the same-shape base a future N-GPU value has to
@@ -355,7 +408,12 @@ def config_c_shard_side(eng, n_q: int, utts: int = 128, micro: int = 32, steps: 
     return out
 
 
-def freqcodec_side(config: str = "freqmpgr1", utts: int = 64, micro: int = 32, steps: int = 5, warmup: int = 2):
+def caller_outputs(results):
+    """encode_decode results of one step's engine calls -> the arrays ONE call over the whole batch returns."""
+    return {k: torch.cat([r[k] for r in results], CAT_DIMS[k]) for k, v in results[0].items() if v is not None}
+
+
+def freqcodec_side(config: str = "freqmpgr1", utts: int = 64, micro: int = 32, steps: int = 5, warmup: int = 2, dump=None):
     """Side measurement of BASELINE.json configs[3] (STFT-domain FreqCodec, batch 64 x 10 s on one GPU): the recipe net with
     conv_group_ratio = tr_conv_group_ratio = 1 (the grouped, bandwidth-bound shape of the released "gr1" model)."""
     from funcodec_amd.config import arch_from_config, recipe_config
@@ -371,9 +429,7 @@ def freqcodec_side(config: str = "freqmpgr1", utts: int = 64, micro: int = 32, s
     n_q = arch.num_quantizers
 
     def step():
-        for i in range(0, utts, micro):
-            r = eng.encode_decode(wav[i:i + micro], n_q, use_scale=True)
-        return r
+        return [eng.encode_decode(wav[i:i + micro], n_q, use_scale=True) for i in range(0, utts, micro)]
 
     eng.set_profiling(False)
     for _ in range(warmup):
@@ -381,11 +437,13 @@ def freqcodec_side(config: str = "freqmpgr1", utts: int = 64, micro: int = 32, s
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        r = step()
+        res = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     eng.check_status()
-    assert bool(torch.isfinite(r["recon"]).all())
+    assert all(bool(torch.isfinite(r["recon"]).all()) for r in res)
+    if dump:
+        dump_outputs(dump, caller_outputs(res))
     eng.set_profiling(True)
     psteps = max(1, min(3, steps))
     for _ in range(psteps):
@@ -414,7 +472,7 @@ def freqcodec_side(config: str = "freqmpgr1", utts: int = 64, micro: int = 32, s
 
 
 def laura_side(batch: int = 8, text_len: int = 100, prompt_frames: int = 75, new_frames: int = 250, steps: int = 3, warmup: int = 1,
-               cpu_sample: bool = True):
+               cpu_sample: bool = True, dump=None):
     """Side measurement of BASELINE.json configs[4]: LauraTTS zero-shot generation, batch = 8 prompts on one GPU.  One step = the
     whole Text2Audio flow for the batch with device-resident inputs: text encoder -> autoregressive decode_codec (prompt tokens +
     `new_frames` new frames per prompt, top-k 25 sampling like the recipe's --sampling 25) -> fine codec predictor -> ds640 codec
@@ -471,6 +529,8 @@ def laura_side(batch: int = 8, text_len: int = 100, prompt_frames: int = 75, new
             phases[k] += ev[k].elapsed_time(ev[k + 1])
     dt = (time.perf_counter() - t0) / steps
     assert bool(torch.isfinite(wav).all()) and all(v == prompt_frames + new_frames for v in out_lens), out_lens
+    if dump:
+        dump_outputs(dump, dict(tokens=tokens, out_lens=out_lens, wav=wav))
     hop = 640
     gen_audio_s = batch * new_frames * hop / 16000.0
     lm, d, ff, V = spec.codec_lm, spec.codec_lm.d_model, spec.codec_lm.ff, spec.lm_vocab
@@ -675,7 +735,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] side measurements of the default run")
     ap.add_argument("--dry-run-launcher", action="store_true",
                     help="exercise rank launch + sharding + gather + the JSON line over gloo without the engine (CPU test of the N > 1 path)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "<= 64 MB in all; a fixed seeded sample of an array that does not fit)")
+    ap.add_argument("--detail-json", metavar="FILE", help="also write the full record (per-kernel tables, every roofline object) to FILE")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:     # not under torchrun: spawn our own ranks
         raise SystemExit(self_launch(args.gpus))
     if args.gpus != int(os.environ.get("WORLD_SIZE", "1")):
@@ -689,8 +755,8 @@ def main():
         if not torch.cuda.is_available():
             raise SystemExit("bench.py needs an MI355X: the engine has no CPU fallback")
         torch.cuda.set_device(0)
-        res = laura_side(steps=max(1, args.steps), warmup=max(1, args.warmup), cpu_sample=not args.no_cpu_baseline) if args.workload == "laura" \
-            else freqcodec_side(steps=max(1, args.steps), warmup=max(1, args.warmup))
+        res = laura_side(steps=args.steps, warmup=max(1, args.warmup), cpu_sample=not args.no_cpu_baseline, dump=args.dump_outputs) \
+            if args.workload == "laura" else freqcodec_side(steps=args.steps, warmup=max(1, args.warmup), dump=args.dump_outputs)
         print(json.dumps(res), flush=True)
         return
     if args.workload == "freqcodec" and not is_freq():
@@ -745,16 +811,14 @@ def main():
     n_q = arch.num_quantizers
 
     def step():
-        parts, r = [], None
         if rehearsal:
             eng.new_step()
-        for i in range(0, wav.shape[0], MICRO_BATCH):      # one engine call per micro-batch; outputs as the reference returns them
-            r = eng.encode_decode(wav[i:i + MICRO_BATCH], n_q, use_scale=True)
-            parts.append(r["codes"])
-        codes = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        # one engine call per micro-batch; outputs as the reference returns them
+        res = [eng.encode_decode(wav[i:i + MICRO_BATCH], n_q, use_scale=True) for i in range(0, wav.shape[0], MICRO_BATCH)]
+        codes = res[0]["codes"] if len(res) == 1 else torch.cat([p["codes"] for p in res], 1)
         if world > 1:
             codes = gather_codes(codes, dist, shard_sizes=shard_sizes)
-        return r, codes
+        return res, codes
 
     def fence():
         if world > 1:
@@ -768,7 +832,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        r, codes = step()
+        res, codes = step()
     fence()
     dt = time.perf_counter() - t0
     eng.check_status()
@@ -805,10 +869,13 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    assert bool(torch.isfinite(r["recon"]).all())
+    assert all(bool(torch.isfinite(p["recon"]).all()) for p in res)
     assert codes.shape[1] == total_utts
     if world > 1:
         assert dist.get_world_size() == world == args.gpus, (dist.get_world_size(), world, args.gpus)     # ranks_seen
+    if rank == 0 and args.dump_outputs:
+        # N > 1: the gathered codes of every rank, rank 0's own shard of the other outputs
+        dump_outputs(args.dump_outputs, {**caller_outputs(res), "codes": codes})
 
     # ---- separate pass: per-kernel-class HIP-event durations on the engine's stream (NOT inside the timed region above)
     prof, prof_steps = [], 0
@@ -862,7 +929,7 @@ def main():
                            "traffic": (pmc_step_traffic() or {}).get("bytes_per_step") if (world == 1 and CONFIG == "ds640") else None,
                            "traffic_over_algorithmic": round(pmc_step_traffic()["bytes_per_step"] / (work["total_bytes"] * nmb), 2)
                            if (world == 1 and CONFIG == "ds640" and pmc_step_traffic()) else None},
-            "timed_region": "in-engine HIP-event brackets OFF; the per-kernel table below is a separate pass",
+            "timed_region": "in-engine HIP-event brackets OFF; the per-kernel table (--detail-json) is a separate pass",
         }
         if rehearsal:
             out["metric"] = "REHEARSAL of the control flow with a stand-in engine (FC_BENCH_REHEARSAL=1): not a measurement"
@@ -873,7 +940,7 @@ def main():
             expect = (exp_u[None, :, None] * 7 + torch.arange(n_q)[:, None, None] + torch.arange(tf)[None, None, :]) % 1024
             out["gather_ok"] = bool(torch.equal(codes, expect))
         else:
-            out["transfers"] = transfer_times(wav, r["codes"])
+            out["transfers"] = transfer_times(wav, res[-1]["codes"])
         if prof:
             out.update(kernel_rooflines(prof, prof_steps))
             if "roofline" in out:
@@ -904,7 +971,11 @@ def main():
                 except Exception as ex:      # a side measurement must never take the contract line down with it
                     sec[key] = {"error": f"{type(ex).__name__}: {ex}"}
             out["secondary"] = sec
-        print(json.dumps(out), flush=True)
+        if args.detail_json:
+            os.makedirs(os.path.dirname(os.path.abspath(args.detail_json)), exist_ok=True)
+            with open(args.detail_json, "w") as f:
+                json.dump(out, f)
+        print(json.dumps(contract_line(out)), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import torch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -87,3 +90,64 @@ def test_the_whole_n_rank_flow_of_bench_main_runs_on_cpu_with_a_stand_in_engine(
     assert r1.returncode == 0, r1.stderr[-3000:]
     o1 = _json_lines(r1.stdout)[0]
     assert o1["n_gpus"] == 1 and o1["gather_ok"] is True and o1["config"]["ranks_seen"] == 1 and "multi_gpu" not in o1
+
+
+def test_the_printed_line_stays_compact_and_keeps_the_headline():
+    """The harness parses ONE JSON line per run and did not take the 20 KB line of profiles/r06_bench.json (the full record of a default
+    run): the printed line is that record reduced by contract_line, well under 8 KB, with the headline, `roofline`, `cpu_baseline` and
+    one entry per secondary workload."""
+    sys.path.insert(0, ROOT)
+    import bench
+    with open(os.path.join(ROOT, "profiles", "r06_bench.json")) as f:
+        full = json.load(f)
+    line = json.dumps(bench.contract_line(full))
+    assert len(line) < 6144 and "\n" not in line
+    out = json.loads(line)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "dtype", "data", "config", "whole_step"):
+        assert out[k] == full[k], k
+    assert out["roofline"]["frac"] == full["roofline"]["frac"] and out["roofline"]["kernel"] == full["roofline"]["kernel"]
+    assert out["cpu_baseline"]["value"] == full["cpu_baseline"]["value"]
+    assert set(out["secondary"]) == set(full["secondary"])
+    assert all(out["secondary"][k]["value"] == full["secondary"][k]["value"] for k in full["secondary"])
+
+
+def test_dump_outputs_writes_the_last_step_reproducibly(tmp_path):
+    """--dump-outputs on the rehearsal flow: every array the step returned, as float32 / float64 .npy, identical from run to run; the full
+    record goes to --detail-json and the printed line is still the only {-line."""
+    env = {"FC_BENCH_REHEARSAL": "1", "FC_BENCH_UTTS": "5", "FC_BENCH_SAMPLES": "6400", "FC_BENCH_MICRO": "2"}
+    dirs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(d),
+                  "--detail-json", str(tmp_path / f"{run}.json")], env_extra=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len(_json_lines(r.stdout)) == 1 and json.load(open(tmp_path / f"{run}.json"))["steps"] == 2
+        dirs.append(d)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == ["codes.npy", "recon.npy"] and names == sorted(p.name for p in dirs[1].iterdir())
+    codes = np.load(dirs[0] / "codes.npy")
+    assert codes.dtype == np.float64 and codes.shape == (32, 5, 10)       # n_q x all utterances of the step x frames
+    assert np.load(dirs[0] / "recon.npy").dtype == np.float32 and np.load(dirs[0] / "recon.npy").shape == (5, 1, 6400)
+    for n in names:
+        assert np.array_equal(np.load(dirs[0] / n), np.load(dirs[1] / n))
+    r = _run(["--gpus", "1", "--steps", "0", "--no-secondary", "--no-cpu-baseline"], env_extra=env)
+    assert r.returncode != 0 and "--steps" in r.stderr and not _json_lines(r.stdout)
+
+
+def test_dump_outputs_samples_what_does_not_fit(tmp_path):
+    """Outputs above the 64 MB budget: small arrays whole, the large one a fixed sample of its elements, the same sample every time."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = dict(big=torch.from_numpy(rng.standard_normal(20_000_000, dtype=np.float32)),
+                  codes=torch.from_numpy(rng.integers(0, 1024, (32, 16, 250))), scale=torch.ones(16, 1))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sum((tmp_path / "a" / n).stat().st_size for n in files) <= 64_000_000
+    assert np.array_equal(files["codes.npy"], arrays["codes"].numpy()) and files["codes.npy"].dtype == np.float64
+    assert np.array_equal(files["scale.npy"], arrays["scale"].numpy())
+    big = files["big.npy"]
+    assert big.dtype == np.float32 and big.ndim == 1 and 10_000_000 < big.size < 20_000_000
+    for n in files:
+        assert np.array_equal(files[n], np.load(tmp_path / "b" / n))

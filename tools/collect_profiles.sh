@@ -1,6 +1,7 @@
 #!/bin/bash
 # Collects the round's evidence on the GPU box (run through gpurun from the repo root):
 #   bench.json               the official bench line (with cpu_baseline)
+#   bench_detail.json        the full record behind that line (per-kernel tables, every roofline object)
 #   bench_under_rocprof.json the same command under rocprofv3 --kernel-trace --stats
 #   kernel_stats.csv         rocprofv3 per-kernel statistics of that run
 #   last_step_per_launch.txt one line per launch of the last benchmark step (tools/trace_summary.py)
@@ -11,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python $R/bench.py --steps 20 --warmup 5 --detail-json $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats -d $OUT/rp -o out --output-format csv -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_under_rocprof.json 2> $OUT/rp.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o out --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-event-profile --no-secondary > /dev/null 2> $OUT/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o out --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-event-profile --no-secondary > /dev/null 2> $OUT/pmc_write.err

@@ -507,8 +507,9 @@ int do_codec_emb(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* te
 
 hipError_t step_gemv(const Lin& L, const float* x, int B, const float* gamma, const float* beta, float eps, int act, int mode, float* y,
                      int ldy, hipStream_t st, float* kc = nullptr, float* vc = nullptr, const int* pos = nullptr, int d = 0, int Tcap = 0,
-                     const float* apart = nullptr, int H = 0, int DK = 0, int NS = 0) {
+                     const float* apart = nullptr, int H = 0, int DK = 0, int NS = 0, int stage = 0) {
     lk::Gemv g;
+    g.stage = stage;
     g.apart = apart; g.H = H; g.DK = DK; g.NS = NS;
     g.x = x; g.wf = L.wf; g.bias = L.bias; g.gamma = gamma; g.beta = beta; g.eps = eps; g.act = act; g.mode = mode; g.y = y; g.ldy = ldy;
     g.kc = kc; g.vc = vc; g.pos = pos; g.d = d; g.Tcap = Tcap; g.B = B; g.K = L.cin; g.N = L.cout;
@@ -695,10 +696,11 @@ int check_stack(const fc_laura_stack& s, const char* name, bool step = false) {
     if (s.act != 1 && s.act != 2) return fail(std::string(name) + ": activation must be 1 (relu) or 2 (swish)");
     // limits of the kernels, refused HERE with a reason instead of a hipErrorInvalidValue at the first call: the LayerNorm kernels
     // and the sampler's fused input layer hold a row of <= 1024 channels; the step form's GEMV stages (16 + 1) x (K + 4) floats of input
-    // plus 16 KiB of partial tiles in the 160 KiB of LDS, K = ff for w_2
+    // plus 16 KiB of partial tiles in the 160 KiB of LDS, K = ff for w_2 (ff <= 2112), or stages them in windows of <= 1024 columns
+    // (launch_gemv); windows are accepted up to ff = 4 d, the ratio of both recipes
     if (s.d_model > 1024) return fail(std::string(name) + ": d_model above 1024 is not supported (LayerNorm / sampler kernels)");
-    if (step && ((size_t)17 * ((size_t)s.ff + 4) * 4 + 16 * 1024 > 160 * 1024))
-        return fail(std::string(name) + ": feed-forward width too large for the decoding step's GEMV (LDS): ff <= 2112");
+    if (step && !(s.ff <= 2112 || s.ff <= 4 * s.d_model))
+        return fail(std::string(name) + ": feed-forward width too large for the decoding step's GEMV: ff <= 2112 or ff <= 4 * d_model");
     return 0;
 }
 
@@ -942,7 +944,11 @@ int fc_laura_codec_emb(fc_laura* e, const float* text_outs, const int32_t* text_
 int fc_laura_set_persistent_step(fc_laura* e, int on) {
     if (!e) return -1;
     e->persist_on = on != 0;
-    return e->persist_on && e->persist_grid > 0 ? 1 : 0;
+    if (!e->persist_on || e->persist_grid <= 0) return 0;
+    // usable for this model at SOME batch size: B = 1 is the smallest LDS footprint (do_decode re-checks every call at its own B, NS)
+    const fc_laura_stack& s = e->codec_lm.s;
+    const int NS = std::min(8, 256 / s.heads);
+    return lk::step_persist_supported(1, s.d_model, s.ff, s.heads, s.d_model / s.heads, e->vocab(), std::max(1, NS)) ? 1 : 0;
 }
 
 int fc_laura_debug_probe(void* dev_dst, size_t cap_bytes, int stack, int layer, int what) {
@@ -961,7 +967,9 @@ int fc_laura_linear(fc_laura* e, const char* name, const float* x, int B, int T,
     if (step_form) {
         if (!L.wf) return fail(std::string(name) + " has no decoding-step form");
         if (B * T > 16) return fail("step form: at most 16 rows");
-        cx.check(step_gemv(L, x, B * T, nullptr, nullptr, 0.f, 0, 0, y, L.cout, cx.st), "GEMV");
+        if (step_form < 1 || step_form > 3) return fail("step_form must be 0 .. 3");
+        cx.check(step_gemv(L, x, B * T, nullptr, nullptr, 0.f, 0, 0, y, L.cout, cx.st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0,
+                           step_form - 1), "GEMV");
         return cx.err;
     }
     const int Tp = pad4(T);

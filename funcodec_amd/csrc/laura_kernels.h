@@ -82,6 +82,9 @@ struct Gemv {
     // x given as the key-range partials of the step attention (combined while staging): [B][H][NS][DK + 2], K = H * DK
     const float* apart = nullptr;
     int H = 0, DK = 0, NS = 0;
+    // how x is staged in LDS: 0 = one stage when (16 + 1) x (K + 4) floats fit, else windows of <= 1024 columns (x as given, modes 0 / 1);
+    // test hooks: 1 = one stage whatever the batch allows, 2 = at least two windows
+    int stage = 0;
 };
 hipError_t launch_gemv(const Gemv& g, hipStream_t st);
 // rows of x [B][C] in place: [relu](LayerNorm(x)) * post_scale

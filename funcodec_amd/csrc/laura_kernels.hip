@@ -543,6 +543,7 @@ struct GemvArgs {
     const float* apart;             // attention partials [B][H][NS][DK + 2] (x is then their combination), or null
     int H, DK, NS;
     int ablate;                     // FC_GEMV_ABLATE (tuning aid): 1 no x loads, 2 no weight loads, 4 no LayerNorm, 8 no MFMAs
+    int W, NW;                      // gemv_win_kernel: x staged in NW windows of W columns (XS = W + 4)
 };
 
 // CPW = 16-wide k chunks per wave as a compile-time constant (2 or 8 for every layer of the recipe): the weight loads are then
@@ -685,6 +686,151 @@ __global__ __launch_bounds__(64 * KS) void gemv_kernel(GemvArgs a) {
     }
 }
 
+// K beyond one LDS stage (w_2 at ff = 4096: 17 x 4100 floats would be 279 KB): x is staged in NW windows of W columns, one after the
+// other through the same LDS rows, and the MFMA chain runs over each window into the same accumulators.  Wave w owns CPW chunks of
+// EVERY window (chunks s * W/16 + w * CPW + u), so all waves have MFMA work between every pair of window barriers.  Specialised form
+// (CPW, NW compile-time; the music recipe's w_2 is <16, 4, 4>): all NW * CPW weight loads of a wave issued up front, before any
+// barrier (a plain global load survives __syncthreads), and the next window's x requested into registers (a fixed trip count with
+// clamped addresses: unconditional loads) while the current one is multiplied.  CPW = 0: generic, loads per window.
+// x as given (no LayerNorm, no attention partials: both need whole rows); modes 0 and 1.
+template <int KS, int CPW, int NW>
+__global__ __launch_bounds__(64 * KS) void gemv_win_kernel(GemvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* Xs = lds;                                   // [B + 1][XS]: the current window, row B = zeros
+    float* red = lds + (a.B + 1) * a.XS;               // [KS][64][4]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, r16 = lane & 15;
+    const int K = a.K, B = a.B, XS = a.XS, W = a.W;
+    const int nw = NW ? NW : a.NW;
+    const int tile = blockIdx.x;
+    const int nch = K / 16, cw = W / 16;               // 16-wide k chunks of the row / of a window
+    const int cpw = CPW ? CPW : cw / KS;               // chunks per wave per window
+    const float* wp = a.wf + ((size_t)tile * nch + (size_t)w * cpw) * 256 + lane * 4;
+    constexpr int NWV = CPW ? CPW * NW : 8;
+    f32x4 wv[NWV];
+    if constexpr (CPW > 0) {
+#pragma unroll
+        for (int s = 0; s < NW; ++s)
+#pragma unroll
+            for (int u = 0; u < CPW; ++u) wv[s * CPW + u] = *(const f32x4*)(wp + ((size_t)s * cw + u) * 256);
+    }
+    const int eb = r16 < B ? r16 : 0, en0 = tile * 16 + 4 * g;
+    float ebias[4], eold[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int n = en0 + r < a.N ? en0 + r : a.N - 1;
+        ebias[r] = a.bias[n];
+        eold[r] = a.mode == 1 ? a.y[(size_t)eb * a.ldy + n] : 0.f;
+    }
+    const int lim = (B + 1) * W;                       // floats of one staged window
+    // specialised: x of one window in NXT f32x4 per thread (17 rows at most)
+    constexpr int NXT = CPW ? (17 * CPW + 15) / 16 : 1;
+    f32x4 xr[NXT];
+    auto request_x = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < NXT; ++i) {
+            int e = (tid + i * 64 * KS) * 4;
+            e = e < lim ? e : lim - 4;
+            const int b = e / W, k = e - b * W;
+            xr[i] = *(const f32x4*)(a.x + (size_t)(b < B ? b : B - 1) * K + (size_t)s * W + k);
+        }
+    };
+    if constexpr (CPW > 0) request_x(0);
+    const float* xb = Xs + (r16 < B ? r16 : B) * XS + w * cpw * 16 + 4 * g;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < nw; ++s) {
+        if (s) __syncthreads();                        // every wave is done with the previous window
+        if constexpr (CPW > 0) {
+#pragma unroll
+            for (int i = 0; i < NXT; ++i) {
+                const int e = (tid + i * 64 * KS) * 4;
+                if (e < lim) *(f32x4*)(Xs + (e / W) * XS + e % W) = e / W < B ? xr[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+        } else {
+            for (int e = tid * 4; e < lim; e += 64 * KS * 4) {
+                const int b = e / W, k = e - b * W;
+                f32x4 v = *(const f32x4*)(a.x + (size_t)(b < B ? b : B - 1) * K + (size_t)s * W + k);
+                if (b >= B) v = (f32x4){0.f, 0.f, 0.f, 0.f};
+                *(f32x4*)(Xs + b * XS + k) = v;
+            }
+        }
+        __syncthreads();
+        if constexpr (CPW > 0) {
+            if (s + 1 < nw) request_x(s + 1);          // lands under this window's MFMAs
+#pragma unroll
+            for (int u = 0; u < CPW; ++u) {
+                const f32x4 xv = *(const f32x4*)(xb + u * 16);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[s * CPW + u][j], xv[j], acc, 0, 0, 0);
+            }
+        } else {
+            const float* ws = wp + (size_t)s * cw * 256;
+            for (int c0 = 0; c0 < cpw; c0 += 8) {
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (c0 + u < cpw) wv[u] = *(const f32x4*)(ws + (size_t)(c0 + u) * 256);
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (c0 + u < cpw) {
+                        const f32x4 xv = *(const f32x4*)(xb + (c0 + u) * 16);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u][j], xv[j], acc, 0, 0, 0);
+                    }
+            }
+        }
+    }
+    *(f32x4*)(red + (w * 64 + lane) * 4) = acc;
+    __syncthreads();
+    if (w != 0) return;
+    f32x4 sum = *(const f32x4*)(red + lane * 4);
+    for (int u = 1; u < KS; ++u) sum += *(const f32x4*)(red + (u * 64 + lane) * 4);
+    const int b = r16;
+    if (b >= B) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int n = tile * 16 + 4 * g + r;
+        if (n >= a.N) continue;
+        const float v = act_f(sum[r] + ebias[r], a.act);
+        a.y[(size_t)b * a.ldy + n] = a.mode == 1 ? eold[r] + v : v;
+    }
+}
+
+namespace {
+size_t gemv_lds_bytes(int B, int XS, int KS) { return ((size_t)(B + 1) * XS + (size_t)KS * 256) * sizeof(float); }
+
+hipError_t launch_gemv_windowed(const Gemv& g, GemvArgs a, int KS, dim3 grid, hipStream_t st) {
+    if (g.gamma || g.apart || g.mode == 2) return hipErrorInvalidValue;       // whole-row prologues / the cache scatter: K <= d
+    // the fewest windows of <= 1024 columns that split every wave's chunks evenly (stage 2, test hook: at least two windows)
+    const int cpw = g.K / 16 / KS, wmax = g.stage == 2 ? g.K : 1024;
+    int nw = 0;
+    for (int n = g.stage == 2 ? 2 : 1; n <= cpw && !nw; ++n)
+        if (cpw % n == 0 && g.K / n <= wmax && gemv_lds_bytes(g.B, g.K / n + 4, KS) <= 160 * 1024) nw = n;
+    if (!nw) return hipErrorInvalidValue;
+    a.W = g.K / nw; a.NW = nw; a.XS = a.W + 4;
+    const size_t lds = gemv_lds_bytes(g.B, a.XS, KS);
+    static std::atomic<unsigned long long> d_spec, d_gen[5];
+    hipError_t e;
+    if (KS == 16 && cpw / nw == 4 && nw == 4) {
+        if ((e = big_lds(gemv_win_kernel<16, 4, 4>, d_spec)) != hipSuccess) return e;
+        hipLaunchKernelGGL((gemv_win_kernel<16, 4, 4>), grid, dim3(64 * 16), lds, st, a);
+        return hipGetLastError();
+    }
+#define FC_GEMV_WIN_CASE(ks, i)                                                           \
+    if (KS == ks) {                                                                       \
+        if ((e = big_lds(gemv_win_kernel<ks, 0, 0>, d_gen[i])) != hipSuccess) return e;   \
+        hipLaunchKernelGGL((gemv_win_kernel<ks, 0, 0>), grid, dim3(64 * ks), lds, st, a); \
+        return hipGetLastError();                                                         \
+    }
+    FC_GEMV_WIN_CASE(16, 0)
+    FC_GEMV_WIN_CASE(8, 1)
+    FC_GEMV_WIN_CASE(4, 2)
+    FC_GEMV_WIN_CASE(2, 3)
+    FC_GEMV_WIN_CASE(1, 4)
+#undef FC_GEMV_WIN_CASE
+    return hipErrorInvalidValue;
+}
+}  // namespace
+
 hipError_t launch_gemv(const Gemv& g, hipStream_t st) {
     if (g.B < 1 || g.B > 16 || g.K % 16 || g.K < 16) return hipErrorInvalidValue;
     const int nch = g.K / 16;
@@ -693,13 +839,16 @@ hipError_t launch_gemv(const Gemv& g, hipStream_t st) {
     while (KS > 1 && (nch % KS || nch / KS < 2)) KS >>= 1;     // >= 2 chunks per wave, K split evenly
     if (nch % KS) KS = 1;
     GemvArgs a{g.x, g.wf, g.bias, g.gamma, g.beta, g.eps, g.act, g.mode, g.y, g.ldy, g.kc, g.vc, g.pos, g.d, g.Tcap, g.B, g.K, g.N, g.K + 4,
-               g.apart, g.H, g.DK, g.NS, 0};
+               g.apart, g.H, g.DK, g.NS, 0, 0, 0};
     static const int ablate = fc::ab_knob("FC_GEMV_ABLATE", 0);
     a.ablate = ablate;
     if (g.apart && (g.H * g.DK != g.K || g.NS < 1 || g.NS > 8 || g.B * g.H * 8 > KS * 256)) return hipErrorInvalidValue;
-    const size_t lds = ((size_t)(g.B + 1) * a.XS + (size_t)KS * 256) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid(ceil_div_h(g.N, 16));
+    // one LDS stage whenever it fits at the largest batch (every K <= 2112: the path does not depend on B), windows beyond that
+    const bool one_stage = g.stage == 1 || (g.stage == 0 && gemv_lds_bytes(16, g.K + 4, KS) <= 160 * 1024);
+    if (!one_stage) return launch_gemv_windowed(g, a, KS, grid, st);
+    const size_t lds = gemv_lds_bytes(g.B, a.XS, KS);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> d16[6], d8[6], d4[6], d2[6], d1[6];
     hipError_t e;
 #define FC_GEMV_CASE(ks, flag)                                                            \

@@ -295,7 +295,9 @@ class LauraEngine:
 
     # -- per-op entry point (tests) -----------------------------------------------------------------------------------------------
     @_on_device
-    def linear(self, name: str, x: torch.Tensor, step_form: bool = False) -> torch.Tensor:
+    def linear(self, name: str, x: torch.Tensor, step_form: bool = False, gemv_stage: str = "auto") -> torch.Tensor:
+        """One Linear of the model by name, full-sequence form or (``step_form``) the decoding step's GEMV.  ``gemv_stage`` (test
+        hook, step form): "auto" as the decoding step runs it, "single" x staged in LDS in one piece, "windowed" in >= 2 windows."""
         x = self._dev(x, torch.float32)
         B, T, cin = x.shape
         want = self.expected_tensors()
@@ -305,7 +307,8 @@ class LauraEngine:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         ws = self._ws
-        self._check(self.lib.fc_laura_linear(self._h, name.encode(), _ptr(x), B, T, int(step_form), _ptr(y), _ptr(ws), ws.numel(), self._stream()))
+        form = {"auto": 1, "single": 2, "windowed": 3}[gemv_stage] if step_form else 0
+        self._check(self.lib.fc_laura_linear(self._h, name.encode(), _ptr(x), B, T, form, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y
 
 

@@ -148,8 +148,9 @@ def laura_spec_from_config(cfg: Dict[str, Any]) -> LauraSpec:
             raise _unsupported(f"{n}: sizes", (s.idim, s.d_model, s.ff), "d_model and linear_units must be multiples of 64, the input size of 8")
         if s.d_model > 1024:
             raise _unsupported(f"{n}: d_model", s.d_model, "the LayerNorm kernels and the sampler's input layer hold rows of at most 1024 channels")
-    if lm_spec.ff > 2112:
-        raise _unsupported("codec_lm: unit", lm_spec.ff, "the decoding step's GEMV stages 17 rows of ff floats in LDS: at most 2112")
+    if not (lm_spec.ff <= 2112 or lm_spec.ff <= 4 * lm_spec.d_model):
+        raise _unsupported("codec_lm: unit", lm_spec.ff, "feed-forward width too large for the decoding step's GEMV: ff <= 2112 or "
+                           "ff <= 4 * d_model")
     return LauraSpec(input_size=input_size, vocab_size=vocab, codebook_size=K, codebook_dim=D, num_quantizers=nqs,
                      predict_nq=predict_nq, pos_emb_type=pos_emb_type, bidirectional_inputs=bool(lm.get("bidirectional_inputs", False)),
                      text_encoder=te, codec_lm=lm_spec, codec_encoder=ce, token_list=list(token_list) if token_list else None)
@@ -157,7 +158,9 @@ def laura_spec_from_config(cfg: Dict[str, Any]) -> LauraSpec:
 
 def laura_recipe_config(name: str) -> Dict[str, Any]:
     """``laura``: egs/LibriTTS/text2speech_laura/conf/text2audio_codec_lm_nq2_uni_rel_pos.yaml (84 M parameters; T5 embeddings of
-    width 1536 as text input).  ``lauraphn``: the same nets over a phoneme token list (``vocab_size`` > 0, input_size 256).
+    width 1536 as text input).  ``lauramusic``: egs/jamendo/text2music_laura/conf/text2audio_codec_lm_nq2_uni_rel_pos.yaml, the
+    recipe of the released text-to-music model (T5-base embeddings of width 768; d_model 1024, 16 heads, feed-forward 4096 in all
+    three stacks; about 330 M parameters).  ``lauraphn``: the same nets over a phoneme token list (``vocab_size`` > 0, input_size 256).
     ``tinylaura`` / ``tinylauraphn``: the same structure, small (fast parity cases)."""
     conf_big = dict(output_size=512, attention_heads=8, linear_units=2048, num_blocks=6, dropout_rate=0.1,
                     positional_dropout_rate=0.1, attention_dropout_rate=0.0, input_layer="linear", normalize_before=True,
@@ -177,6 +180,13 @@ def laura_recipe_config(name: str) -> Dict[str, Any]:
         },
     }
     if name == "laura":
+        return cfg
+    if name == "lauramusic":
+        cfg["input_size"] = 768
+        cfg["audio_max_duration"] = 30
+        for k in ("text_encoder_conf", "codec_encoder_conf"):
+            cfg[k].update(output_size=1024, attention_heads=16, linear_units=4096)
+        cfg["model_conf"]["codec_lm_conf"].update(att_unit=1024, head=16, unit=4096)
         return cfg
     if name == "lauraphn":
         cfg["input_size"] = 256

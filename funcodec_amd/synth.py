@@ -339,3 +339,19 @@ def synthetic_text(cfg: Dict[str, Any], batch: int, lengths, seed: int = 77):
     for b, n in enumerate(lengths):
         x[b, n:] = 0.0
     return x
+
+
+def synthetic_text_embedder(cfg: Dict[str, Any], seed: int = 0):
+    """A deterministic stand-in for the T5 encoder of an embedding-input LauraTTS checkpoint (``text_emb_model`` of
+    Text2Audio, bin/text2audio_inference.py:112-135): ``text -> (emb [1, n_words, input_size] float32, lens [1] int64)``, one
+    ``synthetic_text`` row per whitespace-separated word, seeded by ``seed`` and the text itself.  T5 and its weights are a
+    third-party download; this only fixes the shapes and a function of the text for parity runs."""
+    import zlib
+
+    def _embed(text: str):
+        import torch
+        n = max(1, len(text.split()))
+        x = synthetic_text(cfg, 1, [n], (seed + zlib.crc32(text.encode("utf-8"))) % (1 << 32))
+        return torch.from_numpy(x), torch.tensor([n], dtype=torch.int64)
+
+    return _embed

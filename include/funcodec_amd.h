@@ -348,7 +348,8 @@ int fc_laura_codec_emb(fc_laura* e, const float* text_outs, const int32_t* text_
 
 /* per-op entry point (tests pin each Linear against torch.nn.functional.linear): `name` = state_dict prefix of a Linear
  * ("codec_lm.encoder.encoders.3.feed_forward.w_1", "text_enc_out_layer", ...; "<block>.self_attn.linear_qkv" = the fused q/k/v).
- * x dev f32 [B][T][in], y dev f32 [B][T][out].  step_form != 0: through the decoding step's GEMV (LM layers only, B*T <= 16). */
+ * x dev f32 [B][T][in], y dev f32 [B][T][out].  step_form != 0: through the decoding step's GEMV (LM layers only, B*T <= 16);
+ * 1 = as the decoding step stages x, 2 = x in one LDS stage, 3 = x in at least two LDS windows (2 and 3 are test hooks). */
 int fc_laura_linear(fc_laura* e, const char* name, const float* x, int B, int T, int step_form, float* y,
                     void* workspace, size_t workspace_bytes, void* stream);
 
@@ -362,7 +363,8 @@ int fc_laura_debug_probe(void* dev_dst, size_t cap_bytes, int stack, int layer, 
  * funcodec/models/audio_generation/laura_model.py:501-548).  on = 1 (default; FC_LAURA_PERSIST=0 in the environment changes the default):
  * ONE persistent launch per step whose workgroups hand the token vectors to each other through arrival counters (csrc/laura_persist.hip);
  * on = 0: the chain of one kernel per Linear / attention (csrc/laura_kernels.hip).  Same arithmetic, results agree to fp32 rounding.
- * Returns 1 if the persistent form is in effect afterwards, 0 if the chain is (switched off, or the model / device cannot run it), -1 on a null handle. */
+ * Returns 1 if the persistent form is in effect afterwards, 0 if the chain is (switched off, or the model / device cannot run it at any batch
+ * size), -1 on a null handle.  Batches whose step does not fit the persistent kernel's LDS (d_model 1024: B > 2) still run on the chain. */
 int fc_laura_set_persistent_step(fc_laura* e, int on);
 /* The persistent launch needs all its workgroups resident; it is not a cooperative launch, so CUs held by another stream or process can make
  * a hand-off time out (bounded spins, no hang).  fc_laura_decode_codec then runs THAT call again on the kernel chain and succeeds with the

@@ -429,7 +429,8 @@ def fuzz_freq_recipe_config(seed: int) -> Dict[str, Any]:
 def freq_recipe_config(name: str) -> Dict[str, Any]:
     """`freqmp`: egs/LibriTTS/codec/conf/freqcodec_mag_phase_16k_n32_600k_step.yaml:1-59 (16.2 M parameters);
     `freqmp640`: ..._ds640.yaml (time ratios 2,1,2,1, 640 samples per frame);
-    `tinyfreq` / `tinyfreq640`: the same shapes with 4 base filters, 16-dim / 64-entry codebooks (small fixtures)."""
+    `tinyfreq` / `tinyfreq640`: the same shapes with 4 base filters, 16-dim / 64-entry codebooks (small fixtures);
+    suffix `f1` (e.g. `tinyfreqf1`, `tinyfreqf1wn`): one more stage of ratio [1, 1] at the bottleneck end (frequency ratio 1: F = 1 inputs)."""
     if name.startswith("freqfuzz"):
         return fuzz_freq_recipe_config(int(name[8:]))
     q0 = name.endswith("q0")                          # quantizer_conf.q0_ds_ratio = 2: first stage on the half-rate sequence
@@ -444,6 +445,8 @@ def freq_recipe_config(name: str) -> Dict[str, Any]:
     name = name[:-3] if seg else name
     angle = name.endswith("ang")                      # freqcodec_mag_angle_16k_n32_600k_step.yaml: codec_domain [mag_angle, mag_angle], 2 channels
     name = name[:-3] if angle else name
+    f1 = name.endswith("f1")                          # a first decoder stage of frequency ratio 1: 3 x 3 / strided layers on F = 1 rows, where
+    name = name[:-2] if f1 else name                  # pad2d zero-extends the frequency axis (conv.py:100-119); no recipe does this
     rel = name.endswith("rel")                        # "freqmpgr1rel": the one net of a hyper-parameter search that reproduces the README's
     name = name[:-3] if rel else name                 # 0.52 M parameters for the released gr1 model: n_filters 8, ONE LSTM layer
     gr = -1
@@ -455,6 +458,8 @@ def freq_recipe_config(name: str) -> Dict[str, Any]:
         raise KeyError(name)
     ds640 = name.endswith("640")
     ratios = [[4, 2], [4, 1], [4, 2], [4, 1]] if ds640 else [[4, 1], [4, 1], [4, 2], [4, 1]]
+    if f1:
+        ratios = [[1, 1]] + ratios
     enc = {"ratios": ratios, "norm": "time_group_norm", "norm_params": {"num_groups": 1}, "causal": False, "dilation_base": 1}
     if wn or wnc:
         enc = {"ratios": ratios, "norm": "weight_norm", "causal": bool(wnc), "dilation_base": 1}

@@ -1176,6 +1176,24 @@ Act2 run_conv2d(fc_engine* e, Ctx& cx, const ConvLayer& L, Act2 x0, const Act2* 
     const int tot_f = (kf - 1) - (sf - 1), f_after = tot_f / 2, f_before = tot_f - f_after;     // no extra padding on the frequency axis
     const int Fo = (x0.F + tot_f - kf) / sf + 1;
     const ConvGeom g = conv_geom(L, x0.T);
+    const int fpad = std::max(f_before, f_after);
+    if (x0.F <= fpad) {
+        // pad2d zero-extends an input of F <= pad rows AFTER the activation (conv.py:100-119): its halo rows are zeros of the activated image (or
+        // reflections through that extension), not the activation of raw zero rows.  Materialise the activated input with those rows.  Only
+        // nets with frequency ratio 1 (F = 1 at the bottleneck) get here; the recipes never do.
+        Act2 m;
+        m.C = C; m.F = x0.F; m.T = x0.T; m.halo = x0.halo;
+        m.buf = cx.alloc<float>((size_t)B * (m.F + 2 * m.halo) * C * m.T);
+        cx.launches += 2;
+        if (!cx.dry && !cx.err) {
+            hipError_t er = x0.halo < fpad ? hipErrorInvalidValue
+                                           : fc::launch_combine2d(x0.buf, x0.aff, x0.halo, dual ? x1.buf : nullptr, dual ? x1.aff : nullptr, x1.halo,
+                                                                  elu, e->arch.elu_alpha, B, m.F, C, m.T, m.buf, m.halo, cx.st, 0);
+            if (er == hipSuccess) er = fc::launch_halo_rows_short(m.buf, B, m.F, m.halo, fpad, C, m.T, cx.st);
+            if (er != hipSuccess) { cx.err = 1; g_err = "short-input materialisation failed (" + L.prefix + "): " + hipGetErrorString(er); }
+        }
+        x0 = m; x1 = Act2(); elu = 0; dual = false;
+    }
     // layers with several M tiles: materialise the activated input once (as run_conv does), frequency-major with the same halo
     if (L.w_group) {     // grouped conv with 2 / 4 channels per group: direct FMA kernel, prologue fused, no GEMM
         // the strided 8-row layers read every input sample from 2 output rows x ~1.25 lanes with a two-source prologue (11 VALU per read):
@@ -2007,8 +2025,109 @@ int fc_q0_source_frames(int Tf, int32_t* frames) {
 int fc_layer_out_len(const fc_engine* e, const char* prefix, int T) {
     if (!e || !prefix) return -1;
     auto it = e->by_prefix.find(prefix);
-    if (it == e->by_prefix.end()) return -1;
+    if (it == e->by_prefix.end() || it->second->c2d > 0) return -1;
     return conv_geom(*it->second, T).Tout;
+}
+
+namespace {
+// fc_layer2d_forward / fc_layer2d_out_shape: one 2-D layer through the drivers' own run_conv2d / run_convtr2d (dry: shape and workspace only)
+struct Layer2dRef { const ConvLayer* L = nullptr; int stage = -1; };      // stage >= 0: decoder convtr of that stage
+int find_layer2d(const fc_engine* e, const char* prefix, Layer2dRef* r) {
+    if (!e || !prefix) return fail("null argument");
+    if (e->arch.model_type != 1) return fail("fc_layer2d_forward: the engine is not an STFT-domain codec (model_type 1)");
+    for (size_t s = 0; s < e->dec_stages.size(); ++s)
+        if (e->dec_stages[s].resample.prefix == prefix) { r->L = &e->dec_stages[s].resample; r->stage = (int)s; return 0; }
+    auto it = e->by_prefix.find(prefix);
+    if (it == e->by_prefix.end()) return fail(std::string("unknown layer ") + prefix);
+    if (it->second->c2d == 0) return fail(std::string("layer ") + prefix + " is a 1-D layer: use fc_layer_forward");
+    r->L = it->second;
+    return 0;
+}
+
+int layer2d(fc_engine* e, Ctx& cx, const Layer2dRef& r, const float* x0, const float* aff0, const float* x1, const float* aff1, int F, int T,
+            int apply_elu, int out_halo, float* y, int64_t* shape) {
+    const ConvLayer& L = *r.L;
+    const int B = cx.B, C = L.c2d, h = e->halo2;
+    if (F <= 0 || T <= 0 || B <= 0) return fail("bad argument");
+    if (out_halo != 0 && out_halo != h) return fail("fc_layer2d_forward: out_halo must be 0 or the engine's halo (" + std::to_string(h) + ")");
+    if (r.stage >= 0 && !apply_elu) return fail("fc_layer2d_forward: a decoder convtr always follows its ELU (apply_elu = 1)");
+    if (r.stage < 0 && F + (L.kf - L.sf) < L.kf) return fail("fc_layer2d_forward: fewer frequency rows than the kernel");
+    if (r.stage < 0 && x1 && !L.dual) return fail("fc_layer2d_forward: " + L.prefix + " is planned for one source (its staging has no room for two)");
+    // the inputs, frequency-major with reflected halo rows, in buffers of this workspace (as the drivers hand them over)
+    Act2 a[2];
+    const float* xs[2] = {x0, x1};
+    const float* affs[2] = {aff0, aff1};
+    for (int i = 0; i < 2; ++i) {
+        if (i == 1 && !x1) break;
+        a[i].C = C; a[i].F = F; a[i].T = T; a[i].halo = h;
+        a[i].buf = cx.alloc<float>((size_t)B * (F + 2 * h) * C * T);
+        a[i].aff = const_cast<float*>(affs[i]);
+        a[i].normed = affs[i] != nullptr;
+        if (!cx.dry && !cx.err) {
+            hipError_t er = fc::launch_feats_relayout(a[i].buf, const_cast<float*>(xs[i]), B, C, F, T, h, 0, cx.st);
+            if (er == hipSuccess) er = fc::launch_halo_rows(a[i].buf, B, F, h, C, T, 0, cx.st);
+            if (er != hipSuccess) { cx.err = 1; g_err = std::string("input relayout failed: ") + hipGetErrorString(er); }
+        }
+    }
+    const Act2* p1 = x1 ? &a[1] : nullptr;
+    Act2 o = r.stage >= 0 ? run_convtr2d(e, cx, L, e->dec_up_phases[r.stage], a[0], p1, r.stage + 1 == (int)e->dec_stages.size(), out_halo)
+                          : run_conv2d(e, cx, L, a[0], p1, apply_elu, out_halo);
+    const int Fh = o.F + 2 * o.halo;
+    shape[0] = o.C; shape[1] = Fh; shape[2] = o.T;
+    // the pending GroupNorm affine over every row (halo rows included), then the reference's [B][C][F][T]
+    float* fin = cx.alloc<float>((size_t)B * Fh * o.C * o.T);
+    if (cx.err) return 1;
+    if (cx.dry) return 0;
+    hipError_t er = fc::launch_combine2d(o.buf, o.aff, 0, nullptr, nullptr, 0, 0, 1.f, B, Fh, o.C, o.T, fin, 0, cx.st, 0);
+    if (er == hipSuccess) er = fc::launch_feats_relayout(fin, y, B, o.C, Fh, o.T, 0, 1, cx.st);
+    if (er != hipSuccess) return fail(std::string("output relayout failed: ") + hipGetErrorString(er));
+    return 0;
+}
+}  // namespace
+
+int fc_layer2d_out_shape(const fc_engine* ce, const char* prefix, int B, int F, int T, int out_halo, int64_t* dims) {
+    fc_engine* e = const_cast<fc_engine*>(ce);
+    Layer2dRef r;
+    if (find_layer2d(e, prefix, &r)) return 1;
+    if (!dims) return fail("null argument");
+    if (out_halo == -1) { dims[0] = e->halo2; return 0; }
+    // the workspace of the largest call form: one or two sources, with or without affines, with or without ELU (a dry run of each; the
+    // pointers only mark presence, nothing is dereferenced)
+    const float* mark = reinterpret_cast<const float*>(&dims[0]);
+    size_t need = 0;
+    int ok = 0;
+    for (int form = 0; form < 8; ++form) {
+        const bool two = form & 1, aff = form & 2, elu = form & 4;
+        Ctx cx; cx.B = B; cx.dry = true;
+        int64_t shape[3];
+        const std::string keep = g_err;
+        if (layer2d(e, cx, r, mark, aff ? mark : nullptr, two ? mark : nullptr, (two && aff) ? mark : nullptr, F, T, elu, out_halo, nullptr, shape)) {
+            g_err = keep;
+            continue;
+        }
+        if (!ok++) { dims[0] = shape[0]; dims[1] = shape[1]; dims[2] = shape[2]; }
+        need = std::max(need, cx.off);
+    }
+    if (!ok) {                                        // no form is valid: report why the single-source ELU form is not
+        Ctx cx; cx.B = B; cx.dry = true;
+        int64_t shape[3];
+        layer2d(e, cx, r, mark, nullptr, nullptr, nullptr, F, T, 1, out_halo, nullptr, shape);
+        return 1;
+    }
+    dims[3] = (int64_t)(need + 4096);
+    dims[4] = r.L->c2d;
+    return 0;
+}
+
+int fc_layer2d_forward(fc_engine* e, const char* prefix, const float* x0, const float* aff0, const float* x1, const float* aff1, int B, int F,
+                       int T, int apply_elu, int out_halo, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    if (check_ready(e)) return 1;
+    if (!x0 || !y || (aff1 && !x1)) return fail("bad argument");
+    Layer2dRef r;
+    if (find_layer2d(e, prefix, &r)) return 1;
+    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    int64_t shape[3];
+    return layer2d(e, cx, r, x0, aff0, x1, aff1, F, T, apply_elu, out_halo, y, shape);
 }
 
 int fc_layer_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, int apply_elu, float* y,
@@ -2017,6 +2136,8 @@ int fc_layer_forward(fc_engine* e, const char* prefix, const float* x, int B, in
     if (!prefix || !x || !y || B <= 0 || T <= 0) return fail("bad argument");
     auto it = e->by_prefix.find(prefix);
     if (it == e->by_prefix.end()) return fail(std::string("unknown layer ") + prefix);
+    if (it->second->c2d > 0)      // a Conv2d planned over kf * C channels of frequency-major rows: the 1-D path would read kf times the input
+        return fail(std::string("layer ") + prefix + " is a 2-D layer of the STFT-domain codec: use fc_layer2d_forward");
     Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
     fc::Src s; s.ptr = x; s.used = 1;
     Act o = run_conv(e, cx, *it->second, s, fc::Src(), apply_elu, T);

@@ -111,6 +111,31 @@ hipError_t launch_halo_rows(float* buf, int B, int F, int halo, int C, int T, in
     return hipGetLastError();
 }
 
+// halo rows of an ACTIVATED buffer whose F rows are not more than the consumer's frequency padding (pad = max(before, after)): pad2d
+// (conv.py:100-119) first appends pad + 1 - F zero rows, reflects the extended image, then trims the extension.  Row -i reads extended row i,
+// row F - 1 + i reads extended row F - 1 + i, or its reflection about the last extended row; extended rows >= F are zeros.
+__global__ __launch_bounds__(256) void halo_rows_short_kernel(float* __restrict__ buf, int F, int halo, int pad, int C, int T) {
+    const int b = blockIdx.z, h = blockIdx.y;
+    const int Fp = F + 2 * halo, L = pad + 1;                 // extended length
+    const int dst = h < halo ? h : F + h;
+    const int i = h < halo ? halo - h : h - halo + 1;
+    int srcf = h < halo ? i : F - 1 + i;
+    if (srcf > L - 1) srcf = 2 * (L - 1) - srcf;              // reflected about the last extended row
+    const bool z = i > pad || srcf < 0 || srcf >= F;          // beyond the consumer's padding (never read) or a zero-extension row
+    float* d = buf + ((size_t)b * Fp + dst) * C * T;
+    const float* s = buf + ((size_t)b * Fp + halo + (z ? 0 : srcf)) * C * T;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < (size_t)C * T; e += (size_t)gridDim.x * 256) d[e] = z ? 0.f : s[e];
+}
+
+hipError_t launch_halo_rows_short(float* buf, int B, int F, int halo, int pad, int C, int T, hipStream_t st) {
+    if (halo <= 0) return hipSuccess;
+    if (F > pad || pad > halo) return hipErrorInvalidValue;
+    int gx = cdiv(C * T, 256 * 8);
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(halo_rows_short_kernel, dim3(gx, 2 * halo, B), dim3(256), 0, st, buf, F, halo, pad, C, T);
+    return hipGetLastError();
+}
+
 // dst[b][hd + f][c][t] = [elu]( a0 * s0 + (s1 ? a1 * s1 : 0) ), sources / destination frequency-major with their own halos.
 // Round 4: 16-byte accesses (a lane owns 4 consecutive samples of a row; rows of T = 1001 floats start at every alignment, hence the
 // 4-byte-aligned vector type).  These materialisation passes are 13 % of a FreqCodec gr1 call and were streaming dword by dword.
@@ -784,9 +809,6 @@ struct GConvTrArgs {
     int out_halo;            // > 0: reflected halo rows of the (trimmed) output written by the rows' own workgroups (Fout > out_halo)
 };
 
-#ifndef FC_GCONVTR_DPP
-#define FC_GCONVTR_DPP 1
-#endif
 #ifndef FC_GCONVTR_XCD
 #define FC_GCONVTR_XCD 1
 #endif
@@ -834,19 +856,18 @@ __global__ __launch_bounds__(256) void gconvtr2d_kernel(const GConvTrArgs p) {
     if (live) {
         for (int co = co_lo; co < co_hi; ++co) {
             float x[2][2][NI];                       // [ci][row q / q - 1][columns i0 - 1 .. i0 + NI - 2]
-            if (fast && TR == 1 && FC_GCONVTR_DPP) {
+            if (fast && TR == 1) {
                 // TR = 1: the lane's own 4 columns i0 .. i0 + 3 in ONE 16-byte load; column i0 - 1 is the left neighbour's last column
-                // (DPP wave_shr:1), only lane 0 of a wave loads it.
+                // (lane shuffle, ds_bpermute; a DPP wavefront shift does not give the neighbour's value on gfx950), only lane 0 of a wave
+                // loads it.
 #pragma unroll
                 for (int ci = 0; ci < 2; ++ci)
 #pragma unroll
                     for (int r = 0; r < 2; ++r) {
                         const float* row = (r ? zm : zq) + (size_t)(2 * co + ci) * p.Tin + i0;
                         const f32x4 v = *(const f32x4u*)row;
-                        float left = 0.f;
+                        float left = __shfl_up(v[3], 1, 64);
                         if (lane == 0) left = row[-1];
-                        left = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, left), __builtin_bit_cast(int, v[3]),
-                                                                                     0x138, 0xF, 0xF, false));       // wave_shr:1
                         x[ci][r][0] = left;
 #pragma unroll
                         for (int j = 1; j < NI; ++j) x[ci][r][j] = v[(j - 1) & 3];

@@ -140,6 +140,8 @@ hipError_t launch_polyphase_in(const float* wav, const float* div, int B, int T,
 hipError_t launch_stft_feats(const float* spec, int B, int F, int Tp, long long spec_sB, int halo, int C, float* feats, hipStream_t st);
 hipError_t launch_feats_relayout(float* eng, float* ref, int B, int C, int F, int Tp, int halo, int to_ref, hipStream_t st);
 hipError_t launch_halo_rows(float* buf, int B, int F, int halo, int C, int T, int zero, hipStream_t st);
+// the halo rows pad2d gives an activated input of F <= pad rows (its zero-extension, conv.py:100-119): pad = the consumer's max one-sided padding
+hipError_t launch_halo_rows_short(float* buf, int B, int F, int halo, int pad, int C, int T, hipStream_t st);
 hipError_t launch_combine2d(const float* s0, const float* aff0, int h0, const float* s1, const float* aff1, int h1, int elu, float alpha,
                             int B, int F, int C, int T, float* dst, int hd, hipStream_t st,
                             int halo_mode = 0 /* 1: also write dst's hd reflected halo rows (needs F > hd), 2: zero them */);

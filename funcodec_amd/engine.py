@@ -356,9 +356,17 @@ class CodecEngine:
         B, Cin, T = x.shape
         Tout = self.lib.fc_layer_out_len(self._h, prefix.encode(), T)
         if Tout < 0:
+            if self.arch.model_type == "freq_codec" and prefix + ".conv.bias" in self.expected_tensors():
+                raise EngineError(f"layer {prefix} is a 2-D layer of the STFT-domain codec: use layer2d_forward")
             raise EngineError(f"unknown layer {prefix}")
-        inner = ".convtr.bias" if prefix.endswith("convtr") else ".conv.bias"
-        cout = self.expected_tensors()[prefix + inner][0]
+        exp = self.expected_tensors()
+        tr = prefix.endswith("convtr")
+        inner = ".convtr" if tr else ".conv"
+        cout = exp[prefix + inner + ".bias"][0]
+        wshape = exp.get(prefix + inner + ".weight", exp.get(prefix + inner + ".weight_v"))
+        cin = wshape[0] if tr else wshape[1]
+        if Cin != cin:
+            raise EngineError(f"layer {prefix}: expected input [B, {cin}, T], got {tuple(x.shape)}")
         y = torch.empty((B, cout, Tout), dtype=torch.float32, device=self.device)
         ws = self._workspace(B, max(T, Tout) * 4 + 4096)
         need = (B * cout * (Tout + 64) * 4) * 2 + (1 << 20)
@@ -368,6 +376,52 @@ class CodecEngine:
         self._check(self.lib.fc_layer_forward(self._h, prefix.encode(), _ptr(x), B, T, int(apply_elu), _ptr(y), _ptr(ws),
                                               ws.numel(), self._stream()))
         return y
+
+    @_on_device
+    def layer2d_forward(self, prefix: str, x0: torch.Tensor, aff0: Optional[torch.Tensor] = None, x1: Optional[torch.Tensor] = None,
+                        aff1: Optional[torch.Tensor] = None, apply_elu: bool = False, out_halo: int = 0) -> torch.Tensor:
+        """One 2-D layer of the STFT-domain codec (fc_layer2d_forward): x0, x1 [B,C,F,T] and pending affines aff0, aff1 [B,C,2]
+        (scale, shift) -> the layer's output [B, Cout, Fo + 2 out_halo, Tout], GroupNorm'd (raw for weight_norm nets), halo rows included."""
+        x0 = self._dev(x0, torch.float32)
+        if x0.dim() != 4:
+            raise EngineError(f"layer2d_forward: x0 must be [B,C,F,T], got {tuple(x0.shape)}")
+        B, Cin, Fq, T = x0.shape
+        dims = (C.c_int64 * 5)()
+        self._check(self.lib.fc_layer2d_out_shape(self._h, prefix.encode(), B, Fq, T, int(out_halo), dims))
+        if Cin != int(dims[4]):
+            raise EngineError(f"layer {prefix}: expected input [B, {int(dims[4])}, F, T], got {tuple(x0.shape)}")
+        srcs = [(x0, aff0)] + ([(x1, aff1)] if x1 is not None else [])
+        if x1 is None and aff1 is not None:
+            raise EngineError("layer2d_forward: aff1 without x1")
+        conv = []
+        for x, a in srcs:
+            x = self._dev(x, torch.float32)
+            if tuple(x.shape) != (B, Cin, Fq, T):
+                raise EngineError(f"layer2d_forward: every source must be [B,C,F,T] = {(B, Cin, Fq, T)}, got {tuple(x.shape)}")
+            if a is not None:
+                a = self._dev(a, torch.float32)
+                if tuple(a.shape) != (B, Cin, 2):
+                    raise EngineError(f"layer2d_forward: an affine must be [B,C,2] = {(B, Cin, 2)}, got {tuple(a.shape)}")
+            conv.append((x, a))
+        y = torch.empty((B, int(dims[0]), int(dims[1]), int(dims[2])), dtype=torch.float32, device=self.device)
+        need = int(dims[3])
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._ws
+        (s0, a0), (s1, a1) = conv[0], (conv[1] if len(conv) > 1 else (None, None))
+        self._check(self.lib.fc_layer2d_forward(self._h, prefix.encode(), _ptr(s0), _ptr(a0), _ptr(s1), _ptr(a1), B, Fq, T, int(apply_elu),
+                                                int(out_halo), _ptr(y), _ptr(ws), ws.numel(), self._stream()))
+        return y
+
+    def freq_halo(self) -> int:
+        """Frequency halo rows of the engine's 2-D activations (the out_halo layer2d_forward accepts besides 0)."""
+        dims = (C.c_int64 * 5)()
+        for k in self.expected_tensors():
+            if k.endswith(".conv.bias") and k.startswith("encoder.model.0."):
+                self._check(self.lib.fc_layer2d_out_shape(self._h, k[:-len(".conv.bias")].encode(), 1, 1, 1, -1, dims))
+                return int(dims[0])
+        raise EngineError("freq_halo: not an STFT-domain codec")
 
     @_on_device
     def resblock_forward(self, prefix: str, x: torch.Tensor) -> torch.Tensor:

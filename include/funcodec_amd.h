@@ -193,8 +193,27 @@ int fc_q0_source_frames(int Tf, int32_t* frames /* host, Tf entries */);
  * apply_elu: apply ELU to x first (the nn.ELU that precedes the module in the Sequential). */
 int fc_layer_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, int apply_elu,
                      float* y, void* workspace, size_t workspace_bytes, void* stream);
-/* output length of that layer for input length T */
+/* output length of that layer for input length T (-1: unknown prefix, or a 2-D layer) */
 int fc_layer_out_len(const fc_engine* e, const char* prefix, int T);
+/* fc_layer_forward refuses the 2-D layers of the STFT-domain codec (model_type 1) on the host, before any launch; they go through: */
+
+/* One SConv2d / SConvTranspose2d of the 2-D nets (conv.py:342-447), addressed by its checkpoint prefix: an encoder or decoder "...conv"
+ * of SEANetEncoder2d / SEANetDecoder2d or a decoder "...convtr" (whose last_out_padding, seanet_decoder.py:279, follows from the prefix:
+ * the last decoder stage).  Runs the same run_conv2d / run_convtr2d the encode / decode drivers call, so the kernel branch is the
+ * product's own for that shape; the inputs are first copied into workspace buffers in the engine's frequency-major layout with
+ * reflected halo rows, as the drivers hand activations over.
+ *   x0, x1     dev f32 [B][C][F][T] (the reference's layout; x1 NULL = one source)
+ *   aff0, aff1 dev f32 [B][C][2] (scale, shift) pending GroupNorm affines, or NULL
+ *   the layer's input is act(aff0(x0) + aff1(x1)), act = ELU when apply_elu (a convtr always has apply_elu = 1)
+ *   y          dev f32 [B][Cout][Fo + 2 out_halo][Tout]: the GroupNorm'd output (raw for weight_norm nets) with the halo rows the
+ *              engine hands to the next layer; out_halo is 0 or the engine's frequency halo.
+ * A test hook: the drivers never call it. */
+int fc_layer2d_forward(fc_engine* e, const char* prefix, const float* x0, const float* aff0, const float* x1, const float* aff1,
+                       int B, int F, int T, int apply_elu, int out_halo, float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* dims[0] = Cout, dims[1] = Fo + 2 out_halo, dims[2] = Tout of that call for input [B][C][F][T]; dims[3] = workspace bytes it needs
+ * (tail slack included); dims[4] = C, the layer's input channels.  Host only.  out_halo = -1 returns the engine's frequency halo in
+ * dims[0] and nothing else. */
+int fc_layer2d_out_shape(const fc_engine* e, const char* prefix, int B, int F, int T, int out_halo, int64_t* dims /* [5] */);
 
 /* SEANetResnetBlock.forward (seanet_encoder.py:44-61; decoder copy seanet_decoder.py:42-59) addressed by its Sequential
  * prefix ("encoder.model.1", "decoder.model.16"): y = shortcut(x) + block(x), each conv followed by its GroupNorm (when the

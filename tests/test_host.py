@@ -187,6 +187,35 @@ def test_config_defaults_follow_the_reference_constructor():
         CodecEngine(bad)
 
 
+@pytest.mark.parametrize("name", ["tinyfreqf1", "tinyfreqf1wn"])
+def test_frequency_ratio_1_recipe_and_layer2d_shapes(name):
+    """The `f1` nets (a first decoder stage of frequency ratio 1, i.e. 2-D layers on F = 1 rows) plan like the reference, and the host
+    side of fc_layer2d_out_shape / fc_layer_out_len (no GPU): output shapes with halo rows, input channels, the refusals."""
+    import ctypes as C
+    from funcodec_amd.config import freq_recipe_config
+    cfg = freq_recipe_config(name)
+    arch = arch_from_config(cfg)
+    assert arch.ratios_f[0] == 1 and tuple(arch.ratios) == (1, 1, 1, 2, 1) and arch.norm == ("weight_norm" if name.endswith("wn") else "time_group_norm")
+    eng = CodecEngine(arch)
+    assert eng.expected_tensors() == expected_tensors(arch)
+    halo = eng.freq_halo()
+    assert halo == 3                                                      # 7 x 7 first / last convs
+    dims = (C.c_int64 * 5)()
+    # encoder.model.13: the last encoder stage (frequency ratio 1) runs its 3 x 3 block.1 on F = 1 rows
+    assert eng.lib.fc_layer2d_out_shape(eng._h, b"encoder.model.13.block.1.conv", 2, 1, 7, 0, dims) == 0
+    assert (dims[0], dims[1], dims[2], dims[4]) == (32, 1, 7, 64) and dims[3] > 0
+    assert eng.lib.fc_layer2d_out_shape(eng._h, b"encoder.model.15.conv", 2, 1, 7, halo, dims) == 0       # the 2 x 2 ratio-1 down conv
+    assert (dims[0], dims[1], dims[2], dims[4]) == (128, 1 + 2 * halo, 7, 64)
+    assert eng.lib.fc_layer2d_out_shape(eng._h, b"decoder.model.4.convtr", 1, 1, 5, halo, dims) == 0      # stage 0 convtr: F 1 -> 1
+    assert (dims[0], dims[1], dims[2], dims[4]) == (64, 1 + 2 * halo, 5, 128)
+    assert eng.lib.fc_layer2d_out_shape(eng._h, b"encoder.model.0.conv", 1, 257, 9, 1, dims) != 0
+    assert "out_halo must be 0 or the engine's halo" in eng.lib.fc_last_error().decode()
+    assert eng.lib.fc_layer2d_out_shape(eng._h, b"encoder.model.19.conv", 1, 1, 9, 0, dims) != 0
+    assert "1-D layer: use fc_layer_forward" in eng.lib.fc_last_error().decode()
+    assert eng.lib.fc_layer_out_len(eng._h, b"encoder.model.13.block.1.conv", 9) == -1                  # a 2-D layer is not a 1-D layer
+    assert eng.lib.fc_layer_out_len(eng._h, b"encoder.model.19.conv", 9) == 9
+
+
 def test_engine_sizes_and_work_accounting():
     arch = arch_from_config(recipe_config("ds640"))
     eng = CodecEngine(arch)

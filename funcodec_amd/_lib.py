@@ -7,7 +7,7 @@ import os
 from . import build as _build
 
 FC_MAX_RATIOS = 8
-FC_ABI_VERSION = 6
+FC_ABI_VERSION = 7
 
 
 class FcArch(C.Structure):
@@ -25,6 +25,7 @@ class FcArch(C.Structure):
         ("enc_conv_group_ratio", C.c_int32), ("dec_conv_group_ratio", C.c_int32), ("dec_tr_conv_group_ratio", C.c_int32),
         ("codec_dim", C.c_int32), ("codec_range", C.c_float),
         ("q0_ds_ratio", C.c_int32),
+        ("seq_model", C.c_int32), ("seq_heads", C.c_int32), ("seq_ff", C.c_int32),
     ]
 
 
@@ -80,6 +81,7 @@ SYMBOLS = {
     "fc_layer2d_forward": (C.c_int, [_P, C.c_char_p, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_layer2d_out_shape": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "fc_lstm_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "fc_seq_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_resblock_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_engine_work": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(FcWork)]),
     "fc_engine_profile": (C.c_int, [_P, C.c_int]),

@@ -33,7 +33,7 @@ class ArchSpec:
     n_residual_layers: int = 1
     dilation_base: int = 2
     compress: int = 2
-    lstm_layers: int = 2                          # seq_layer_num when seq_model == "lstm", else 0
+    lstm_layers: int = 2                          # seq_layer_num when seq_model is "lstm" or "transformer", else 0
     lstm_skip: bool = True                        # res_seq
     elu_alpha: float = 1.0
     gn_eps: float = 1e-5
@@ -68,6 +68,10 @@ class ArchSpec:
     enc_conv_group_ratio: int = -1
     dec_conv_group_ratio: int = -1
     dec_tr_conv_group_ratio: int = -1
+    # the bottleneck sequence model (seanet_encoder.py:142-151, seanet_decoder.py:116-125 and the 2-D nets): "lstm" = SLSTM with
+    # lstm_layers layers; "transformer" = TransformerEncoder (normed_modules/transformer.py:26-208) with lstm_layers blocks of
+    # SEQ_HEADS heads and SEQ_FF feed-forward units, causal when `causal` is set.  Meaningless when lstm_layers == 0.
+    seq_model: str = "lstm"
 
     @property
     def segment_length(self) -> Optional[int]:
@@ -108,6 +112,12 @@ class ArchSpec:
         return t
 
 
+# TransformerEncoder as SEANet builds it (transformer.py:52-70): the defaults are not settable from encoder_conf / decoder_conf
+SEQ_HEADS = 4
+SEQ_FF = 2048
+SEQ_WIDTHS = (64, 128, 256, 512, 1024)       # head size C / 4 in 16..256 (the attention kernel's set); LayerNorm rows <= 1024
+
+
 def _unsupported(key: str, value: Any, why: str = "") -> NotImplementedError:
     return NotImplementedError(
         f"config key {key}={value!r} is outside the MI355X hot-path scope (SURVEY.md §8){': ' + why if why else ''}")
@@ -146,7 +156,7 @@ def _check_seanet_conf(conf: Dict[str, Any], which: str) -> Dict[str, Any]:
     if conf.get("final_activation", None) is not None:
         raise _unsupported(f"{which}.final_activation", conf["final_activation"])
     seq_model = conf.get("seq_model", "lstm")
-    if seq_model not in ("lstm", None, "none", "None"):
+    if seq_model not in ("lstm", "transformer", None, "none", "None"):
         raise _unsupported(f"{which}.seq_model", seq_model)
     if not 1 <= int(conf.get("n_residual_layers", 1)) <= 8:
         raise _unsupported(f"{which}.n_residual_layers", conf["n_residual_layers"])
@@ -154,6 +164,21 @@ def _check_seanet_conf(conf: Dict[str, Any], which: str) -> Dict[str, Any]:
     if nk.get("num_groups", 1) != 1:
         raise _unsupported(f"{which}.norm_params.num_groups", nk["num_groups"])
     return conf
+
+
+def _seq_layers(seq_model: Any, layers: Any, width: int) -> int:
+    """lstm_layers of the ArchSpec for a (shared) seq_model / seq_layer_num pair; refuses transformers the engine does not build."""
+    if seq_model == "lstm":
+        return int(layers)
+    if seq_model != "transformer":
+        return 0
+    if int(layers) < 1:
+        raise _unsupported("encoder_conf.seq_layer_num", layers, "a transformer bottleneck needs at least one block")
+    if width not in SEQ_WIDTHS:
+        raise _unsupported("seq_model: transformer", width,
+                           f"bottleneck width n_filters * 2 ** len(ratios) must be one of {SEQ_WIDTHS} (head size {SEQ_WIDTHS[0] // SEQ_HEADS} .. "
+                           f"{SEQ_WIDTHS[-1] // SEQ_HEADS})")
+    return int(layers)
 
 
 def _freq_arch_from_config(cfg: Dict[str, Any]) -> ArchSpec:
@@ -236,9 +261,10 @@ def _freq_arch_from_config(cfg: Dict[str, Any]) -> ArchSpec:
     act_params = dict(shared("activation_params", {"alpha": 1.0}) or {})
     norm_params = dict(shared("norm_params", {}) or {})
     seq_model = shared("seq_model", "lstm")
-    if seq_model not in ("lstm", "none", None):
-        raise _unsupported("encoder_conf.seq_model", seq_model, "lstm or none")
-    seq_model = "lstm" if seq_model == "lstm" else "none"
+    if seq_model not in ("lstm", "transformer", "none", None):
+        raise _unsupported("encoder_conf.seq_model", seq_model, "lstm, transformer or none")
+    n_filters2 = int(shared("n_filters", 32))
+    seq_layers = _seq_layers(seq_model, shared("seq_layer_num", 2), n_filters2 * 2 ** len(ratios2))
     arch = ArchSpec(
         sample_rate=int(m.get("target_sample_hz", 24000)), input_channels=n_in,
         audio_normalize=bool(m.get("audio_normalize", False)),            # FreqCodec.__init__ default is False (codec_freq.py:141)
@@ -247,7 +273,7 @@ def _freq_arch_from_config(cfg: Dict[str, Any]) -> ArchSpec:
         kernel_size=int(shared("kernel_size", 7)), last_kernel_size=int(shared("last_kernel_size", 7)),
         residual_kernel_size=int(shared("residual_kernel_size", 3)), n_residual_layers=int(shared("n_residual_layers", 1)),
         dilation_base=int(shared("dilation_base", 2)), compress=int(shared("compress", 2)),
-        lstm_layers=int(shared("seq_layer_num", 2)) if seq_model == "lstm" else 0, lstm_skip=bool(shared("res_seq", True)),
+        lstm_layers=seq_layers, lstm_skip=bool(shared("res_seq", True)),
         elu_alpha=float(act_params.get("alpha", 1.0)), gn_eps=float(norm_params.get("eps", 1e-5)),
         codebook_size=int(q.get("codebook_size", 1024)), codebook_dim=codec_dim, num_quantizers=int(q.get("num_quantizers", 8)),
         codec_range=None if codec_range is None else float(codec_range),
@@ -258,6 +284,7 @@ def _freq_arch_from_config(cfg: Dict[str, Any]) -> ArchSpec:
         model_type="freq_codec", n_fft=int(dc.get("n_fft", 512)), stft_hop=int(dc.get("hop_length", 160)),
         enc_conv_group_ratio=int(enc.get("conv_group_ratio", -1)), dec_conv_group_ratio=int(dec.get("conv_group_ratio", -1)),
         dec_tr_conv_group_ratio=int(dec.get("tr_conv_group_ratio", -1)),
+        **({"seq_model": "transformer"} if seq_model == "transformer" else {}),
     )
     if arch.stft_hop < 1 or arch.stft_hop > arch.n_fft // 2:
         # torch.istft checks the window envelope (NOLA, > 1e-11); a periodic Hann window's squared overlap-add reaches ~0 between
@@ -332,6 +359,7 @@ def arch_from_config(cfg: Dict[str, Any]) -> ArchSpec:
     segment_dur = m["segment_dur"] if "segment_dur" in m else 1.0
     overlap_ratio = m["overlap_ratio"] if "overlap_ratio" in m else 0.01
     ratios = tuple(int(r) for r in shared("ratios", [8, 5, 4, 2]))
+    seq_layers = _seq_layers(seq_model, shared("seq_layer_num", 2), int(shared("n_filters", 32)) * 2 ** len(ratios))
     arch = ArchSpec(
         sample_rate=int(m.get("target_sample_hz", 24000)),
         input_channels=int(input_size),
@@ -345,7 +373,7 @@ def arch_from_config(cfg: Dict[str, Any]) -> ArchSpec:
         n_residual_layers=int(shared("n_residual_layers", 1)),
         dilation_base=int(shared("dilation_base", 2)),
         compress=int(shared("compress", 2)),
-        lstm_layers=int(shared("seq_layer_num", 2)) if seq_model == "lstm" else 0,
+        lstm_layers=seq_layers,
         lstm_skip=bool(shared("res_seq", True)),
         elu_alpha=float(act_params.get("alpha", 1.0)),
         gn_eps=float(norm_params.get("eps", 1e-5)),
@@ -362,6 +390,7 @@ def arch_from_config(cfg: Dict[str, Any]) -> ArchSpec:
         causal=bool(shared("causal", False)),
         segment_dur=None if segment_dur is None else float(segment_dur),
         overlap_ratio=0.01 if overlap_ratio is None else float(overlap_ratio),
+        **({"seq_model": "transformer"} if seq_model == "transformer" else {}),
     )
     if arch.stft_hop < 1 or arch.stft_hop > arch.n_fft // 2:
         # torch.istft checks the window envelope (NOLA, > 1e-11); a periodic Hann window's squared overlap-add reaches ~0 between
@@ -542,6 +571,18 @@ def fuzz_recipe_config(seed: int) -> Dict[str, Any]:
 
 
 def recipe_config(name: str) -> Dict[str, Any]:
+    if name in ("tinytf", "ds320tf", "ds640tf", "ss320tfc", "ds320tfseg", "freqmptf"):
+        # seq_model: transformer (TransformerEncoder at the bottleneck, normed_modules/transformer.py:26-208) in place of the SLSTM / no
+        # sequence model of the base recipe: "tinytf" = tiny with 16 base filters (C 64, head size 16); "ss320tfc" = the causal
+        # weight_norm SoundStream nets (causal attention), two blocks; "ds320tfseg" = segmented; "freqmptf" = the 2-D FreqCodec nets
+        base = {"tinytf": "tiny", "ds320tf": "ds320", "ds640tf": "ds640", "ss320tfc": "ss320", "ds320tfseg": "ds320seg", "freqmptf": "freqmp"}[name]
+        cfg = recipe_config(base)
+        for k in ("encoder_conf", "decoder_conf"):
+            cfg[k]["seq_model"] = "transformer"
+            cfg[k]["seq_layer_num"] = 2
+            if name == "tinytf":
+                cfg[k]["n_filters"] = 16
+        return cfg
     if name.startswith("fuzz"):
         return fuzz_recipe_config(int(name[4:]))
     if name.startswith(("freqmp", "tinyfreq", "freqfuzz")):

@@ -14,6 +14,8 @@
 
 #include "../../include/funcodec_amd.h"
 #include "kernels.h"
+#include "laura_kernels.h"
+#include "seq_kernels.h"
 
 namespace {
 
@@ -81,6 +83,21 @@ struct LstmBlock {
     std::vector<LstmLayer> layers;
 };
 
+// TransformerEncoder at the bottleneck (seq_model: transformer; normed_modules/transformer.py:26-208): pre-LayerNorm blocks, every
+// Linear a k = 1 layer of the implicit-GEMM conv kernel over feature-major [B][C][T] activations
+struct TfLayer {
+    ConvLayer qkv;          // linear_q | linear_k | linear_v as ONE GEMM of 3 C rows (weights concatenated at pack time)
+    ConvLayer out, ff1, ff2;    // linear_out, feed_forward.w_1, feed_forward.w_2
+    float *n1g = nullptr, *n1b = nullptr, *n2g = nullptr, *n2b = nullptr;   // norm1, norm2
+};
+
+struct TfBlock {
+    std::string prefix;     // "encoder.model.16"
+    int C = 0, heads = 4, ff = 2048;
+    std::vector<TfLayer> layers;
+    float *ag = nullptr, *ab = nullptr;   // after_norm
+};
+
 struct Act {               // raw tensor [B][C][T] + pending GroupNorm affine (null = already final)
     float* raw = nullptr;
     float* aff = nullptr;
@@ -97,7 +114,7 @@ struct Ctx {
     int err = 0;
     static constexpr size_t kTailSlack = 4096;
     int launches = 0, conv_launches = 0;
-    double conv_flops = 0, conv_bytes = 0, lstm_flops = 0, rvq_flops = 0, other_bytes = 0;
+    double conv_flops = 0, conv_bytes = 0, lstm_flops = 0, rvq_flops = 0, other_bytes = 0, attn_flops = 0;
     template <typename T>
     T* alloc(size_t n) {
         off = (off + 255) & ~(size_t)255;
@@ -135,6 +152,8 @@ struct fc_engine {
     struct Stage { std::vector<ResBlock> res; ConvLayer resample; };      // n_residual_layers blocks; resample = down (enc) / up (dec)
     std::vector<Stage> enc_stages, dec_stages;
     LstmBlock enc_lstm, dec_lstm;
+    TfBlock enc_tf, dec_tf;                                               // seq_model 1 (transformer) instead of the LSTMs
+    std::map<std::string, TfBlock*> tf_by_prefix;
     std::map<std::string, ConvLayer*> by_prefix;
     std::map<std::string, ResBlock*> res_by_prefix;
     // STFT-domain codec (arch.model_type == 1)
@@ -299,6 +318,39 @@ void add_quantizer_expect(fc_engine* e) {
     e->expected.push_back({"quantizer.rq.model.embed", {a.num_quantizers, a.codebook_size, e->cdim()}});
 }
 
+// TransformerEncoder's checkpoint contract, in state_dict order (EncoderLayer: self_attn, feed_forward, norm1, norm2; then after_norm)
+void add_tf_expect(fc_engine* e, TfBlock& tb) {
+    if (tb.C == 0) return;
+    const fc_arch& a = e->arch;
+    const int C = tb.C;
+    tb.heads = a.seq_heads; tb.ff = a.seq_ff;
+    tb.layers.resize(a.lstm_layers);
+    for (int l = 0; l < a.lstm_layers; ++l) {
+        const std::string p = tb.prefix + ".encoders." + std::to_string(l);
+        TfLayer& L = tb.layers[l];
+        L.qkv = mk_conv(p + ".self_attn.linear_qkv", C, 3 * C, 1, 1, false, false, true);
+        L.out = mk_conv(p + ".self_attn.linear_out", C, C, 1, 1, false, false, true);
+        L.ff1 = mk_conv(p + ".feed_forward.w_1", C, tb.ff, 1, 1, false, false, true);
+        L.ff2 = mk_conv(p + ".feed_forward.w_2", tb.ff, C, 1, 1, false, false, true);
+        for (ConvLayer* c : {&L.qkv, &L.out, &L.ff1, &L.ff2}) c->has_norm = false;
+        for (const char* n : {"linear_q", "linear_k", "linear_v", "linear_out"}) {
+            e->expected.push_back({p + ".self_attn." + n + ".weight", {C, C}});
+            e->expected.push_back({p + ".self_attn." + n + ".bias", {C}});
+        }
+        e->expected.push_back({p + ".feed_forward.w_1.weight", {tb.ff, C}});
+        e->expected.push_back({p + ".feed_forward.w_1.bias", {tb.ff}});
+        e->expected.push_back({p + ".feed_forward.w_2.weight", {C, tb.ff}});
+        e->expected.push_back({p + ".feed_forward.w_2.bias", {C}});
+        for (const char* n : {"norm1", "norm2"}) {
+            e->expected.push_back({p + "." + n + ".weight", {C}});
+            e->expected.push_back({p + "." + n + ".bias", {C}});
+        }
+    }
+    e->expected.push_back({tb.prefix + ".after_norm.weight", {C}});
+    e->expected.push_back({tb.prefix + ".after_norm.bias", {C}});
+    e->tf_by_prefix[tb.prefix] = &tb;
+}
+
 void build_plan_2d(fc_engine* e) {
     const fc_arch& a = e->arch;
     const int nf = a.n_filters, nres = a.n_residual_layers;
@@ -331,7 +383,8 @@ void build_plan_2d(fc_engine* e) {
     }
     idx++;                                                                        // ReshapeModule (squeeze the frequency axis)
     const int cb = mult * nf;
-    if (a.lstm_layers > 0) { e->enc_lstm.prefix = name("encoder", idx, ".lstm"); e->enc_lstm.H = cb; idx++; }
+    if (a.lstm_layers > 0 && a.seq_model == 1) { e->enc_tf.prefix = name("encoder", idx, ""); e->enc_tf.C = cb; idx++; }
+    else if (a.lstm_layers > 0) { e->enc_lstm.prefix = name("encoder", idx, ".lstm"); e->enc_lstm.H = cb; idx++; }
     idx++;
     const bool skip_dual = a.lstm_layers > 0 && a.lstm_skip;
     e->enc_last = mk_conv(name("encoder", idx, ".conv"), cb, a.dimension, a.last_kernel_size, 1, false, skip_dual, true);
@@ -339,7 +392,8 @@ void build_plan_2d(fc_engine* e) {
     idx = 0;
     e->dec_first = mk_conv(name("decoder", idx, ".conv"), a.dimension, cb, a.kernel_size, 1, false, false, true);
     idx++;
-    if (a.lstm_layers > 0) { e->dec_lstm.prefix = name("decoder", idx, ".lstm"); e->dec_lstm.H = cb; idx++; }
+    if (a.lstm_layers > 0 && a.seq_model == 1) { e->dec_tf.prefix = name("decoder", idx, ""); e->dec_tf.C = cb; idx++; }
+    else if (a.lstm_layers > 0) { e->dec_lstm.prefix = name("decoder", idx, ".lstm"); e->dec_lstm.H = cb; idx++; }
     idx++;                                                                        // ReshapeModule (unsqueeze)
     e->dec_stages.resize(a.n_ratios);
     e->dec_up_phases.resize(a.n_ratios);
@@ -402,9 +456,11 @@ void build_plan_2d(fc_engine* e) {
         e->lstm_by_prefix[lb.prefix] = &lb;
     };
     add_lstm(e->enc_lstm);
+    add_tf_expect(e, e->enc_tf);
     add_conv_expect(e, e->enc_last);
     add_conv_expect(e, e->dec_first);
     add_lstm(e->dec_lstm);
+    add_tf_expect(e, e->dec_tf);
     for (auto& S : e->dec_stages) {
         const int opg_t = S.resample.cout / (S.resample.groups > 0 ? S.resample.groups : 1);
         if (S.resample.wnorm) {                                               // dim 0 of a ConvTranspose2d weight = its IN channels
@@ -454,7 +510,11 @@ void build_plan(fc_engine* e) {
         mult *= 2;
     }
     const int cb = mult * nf;
-    if (a.lstm_layers > 0) {
+    if (a.lstm_layers > 0 && a.seq_model == 1) {
+        e->enc_tf.prefix = name("encoder", idx, "");
+        e->enc_tf.C = cb;
+        idx++;
+    } else if (a.lstm_layers > 0) {
         e->enc_lstm.prefix = name("encoder", idx, ".lstm");
         e->enc_lstm.H = cb;
         idx++;
@@ -466,7 +526,11 @@ void build_plan(fc_engine* e) {
     idx = 0;
     e->dec_first = mk_conv(name("decoder", idx, ".conv"), a.dimension, cb, a.kernel_size, 1, false, false, true);
     idx++;
-    if (a.lstm_layers > 0) {
+    if (a.lstm_layers > 0 && a.seq_model == 1) {
+        e->dec_tf.prefix = name("decoder", idx, "");
+        e->dec_tf.C = cb;
+        idx++;
+    } else if (a.lstm_layers > 0) {
         e->dec_lstm.prefix = name("decoder", idx, ".lstm");
         e->dec_lstm.H = cb;
         idx++;
@@ -534,9 +598,11 @@ void build_plan(fc_engine* e) {
         e->lstm_by_prefix[lb.prefix] = &lb;
     };
     add_lstm(e->enc_lstm);
+    add_tf_expect(e, e->enc_tf);
     add_conv_expect(e, e->enc_last);
     add_conv_expect(e, e->dec_first);
     add_lstm(e->dec_lstm);
+    add_tf_expect(e, e->dec_tf);
     for (auto& S : e->dec_stages) {
         add_conv_expect(e, S.resample);
         for (auto& R : S.res) { add_conv_expect(e, R.shortcut); add_conv_expect(e, R.block1); add_conv_expect(e, R.block3); }
@@ -879,6 +945,33 @@ int pack_lstm(fc_engine* e, LstmBlock& lb) {
     return 0;
 }
 
+int pack_tf(fc_engine* e, TfBlock& tb) {
+    if (tb.C == 0) return 0;
+    const int C = tb.C;
+    auto H = [&](const std::string& k) -> const std::vector<float>& { return e->host[k].data; };
+    for (int l = 0; l < (int)tb.layers.size(); ++l) {
+        const std::string p = tb.prefix + ".encoders." + std::to_string(l);
+        TfLayer& L = tb.layers[l];
+        std::vector<float> W((size_t)3 * C * C), Bv((size_t)3 * C);      // Linear weight [out][in] = the k = 1 GEMM's [M][cin][1]
+        int part = 0;
+        for (const char* n : {"linear_q", "linear_k", "linear_v"}) {
+            const auto& w = H(p + ".self_attn." + n + ".weight");
+            const auto& b = H(p + ".self_attn." + n + ".bias");
+            std::copy(w.begin(), w.end(), W.begin() + (size_t)part * C * C);
+            std::copy(b.begin(), b.end(), Bv.begin() + (size_t)part * C);
+            ++part;
+        }
+        if (pack_gemm(e, L.qkv, W, Bv)) return 1;
+        if (pack_gemm(e, L.out, H(p + ".self_attn.linear_out.weight"), H(p + ".self_attn.linear_out.bias"))) return 1;
+        if (pack_gemm(e, L.ff1, H(p + ".feed_forward.w_1.weight"), H(p + ".feed_forward.w_1.bias"))) return 1;
+        if (pack_gemm(e, L.ff2, H(p + ".feed_forward.w_2.weight"), H(p + ".feed_forward.w_2.bias"))) return 1;
+        if (upload(e, H(p + ".norm1.weight"), &L.n1g) || upload(e, H(p + ".norm1.bias"), &L.n1b)) return 1;
+        if (upload(e, H(p + ".norm2.weight"), &L.n2g) || upload(e, H(p + ".norm2.bias"), &L.n2b)) return 1;
+    }
+    if (upload(e, H(tb.prefix + ".after_norm.weight"), &tb.ag) || upload(e, H(tb.prefix + ".after_norm.bias"), &tb.ab)) return 1;
+    return 0;
+}
+
 // ---- execution ------------------------------------------------------------------------------------
 struct ConvGeom { int Tout, padL, padR, count_T; };
 
@@ -1048,6 +1141,73 @@ Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T) {
     return y;
 }
 
+// TransformerEncoder.forward (transformer.py:150-208) without the skip; returns plain y = after_norm(blocks(x)) [B][C][T].
+// Per block (EncoderLayer.forward, transformer_encoder.py:92-150, normalize_before, dropout 0), as LauraTTS's full-sequence stacks run:
+//   x += linear_out(MHA(norm1(x)));  x += w_2(relu(w_1(norm2(x))))
+// Each residual add is fused into the LayerNorm that follows it (laura_kernels.hip layernorm_fm_kernel); LayerNorm eps 1e-12
+// (layer_norm.py:21-23).  The input may carry a pending GroupNorm affine: it is materialised once.
+Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int T) {
+    const int C = tb.C, B = cx.B, ff = tb.ff, DK = C / tb.heads;
+    const long long sC = (long long)C * T;
+    float* x = cx.alloc<float>((size_t)B * C * T);        // residual stream
+    float* xn = cx.alloc<float>((size_t)B * C * T);       // LayerNorm output
+    float* dl = cx.alloc<float>((size_t)B * C * T);       // branch output (pending residual add)
+    float* qkv = cx.alloc<float>((size_t)B * 3 * C * T);
+    float* ctx = cx.alloc<float>((size_t)B * C * T);
+    float* hb = cx.alloc<float>((size_t)B * ff * T);
+    Act y;
+    y.C = C; y.T = T;
+    y.raw = cx.alloc<float>((size_t)B * C * T);
+    const double pairs = tb.layers.empty() ? 0.0 : (e->arch.causal ? 0.5 * (double)T * (T + 1) : (double)T * T);
+    const double attn_fl = 4.0 * B * pairs * C;           // q k^T and p v, every visible (query, key) pair
+    cx.attn_flops += attn_fl * tb.layers.size();
+    cx.launches += 2 + (int)tb.layers.size() * 3;
+    auto ln = [&](const float* add, const float* g, const float* b, float* out) {
+        if (cx.dry || cx.err) return;
+        ProfSpan sp(e, cx, e->profiling ? e->prof_class("layernorm_fm_kernel (transformer, residual add fused)") : 0, 0.0,
+                    4.0 * B * C * T * (add ? 4 : 2));
+        hipError_t er = fc::laura::launch_layernorm_fm(x, add, add ? x : nullptr, g, b, 1e-12f, 0, 1.f, out, B, C, T, cx.st);
+        if (er != hipSuccess) { cx.err = 1; g_err = std::string("transformer LayerNorm launch failed: ") + hipGetErrorString(er); }
+    };
+    if (!cx.dry && !cx.err) {
+        hipError_t er = fc::launch_combine(src_of(in), fc::Src(), 0, 1.f, nullptr, B, C, T, T, x, sC, T, 1, cx.st);
+        if (er != hipSuccess) { cx.err = 1; g_err = std::string("combine launch failed: ") + hipGetErrorString(er); }
+    }
+    fc::Src sxn; sxn.ptr = xn; sxn.used = 1;
+    fc::Src sctx; sctx.ptr = ctx; sctx.used = 1;
+    fc::Src shb; shb.ptr = hb; shb.used = 1;
+    const float* pending = nullptr;
+    for (const TfLayer& L : tb.layers) {
+        ln(pending, L.n1g, L.n1b, xn);
+        run_conv(e, cx, L.qkv, sxn, fc::Src(), 0, T, qkv, 3 * sC, T, 1);
+        if (!cx.dry && !cx.err) {
+            fc::SeqAttn a;
+            a.qkv = qkv; a.out = ctx; a.B = B; a.H = tb.heads; a.DK = DK; a.T = T; a.causal = e->arch.causal ? 1 : 0;
+            ProfSpan sp(e, cx, e->profiling ? e->prof_class(fc::seq_attn_kernel_name(DK)) : 0, attn_fl, 4.0 * B * 4.0 * C * T);
+            hipError_t er = fc::launch_seq_attn(a, cx.st);
+            if (er != hipSuccess) { cx.err = 1; g_err = std::string("transformer attention launch failed: ") + hipGetErrorString(er); }
+        }
+        run_conv(e, cx, L.out, sctx, fc::Src(), 0, T, dl, sC, T, 1);
+        ln(dl, L.n2g, L.n2b, xn);
+        run_conv(e, cx, L.ff1, sxn, fc::Src(), 0, T, hb, (long long)ff * T, T, 1);
+        if (!cx.dry && !cx.err) {
+            ProfSpan sp(e, cx, e->profiling ? e->prof_class("act_kernel (transformer feed-forward ReLU)") : 0, 0.0, 8.0 * B * ff * T);
+            hipError_t er = fc::laura::launch_act(hb, (size_t)B * ff * T, 1, cx.st);
+            if (er != hipSuccess) { cx.err = 1; g_err = std::string("ReLU launch failed: ") + hipGetErrorString(er); }
+        }
+        run_conv(e, cx, L.ff2, shb, fc::Src(), 0, T, dl, sC, T, 1);
+        pending = dl;
+    }
+    ln(pending, tb.ag, tb.ab, y.raw);                      // after_norm
+    return y;
+}
+
+// the bottleneck sequence model of one side: SLSTM or TransformerEncoder, output plain [B][C][T] without the skip
+bool has_seq(const LstmBlock& lb, const TfBlock& tb) { return lb.H != 0 || tb.C != 0; }
+Act run_seq(fc_engine* e, Ctx& cx, const LstmBlock& lb, const TfBlock& tb, const Act& in, int T) {
+    return tb.C ? run_transformer(e, cx, tb, in, T) : run_lstm(e, cx, lb, in, T);
+}
+
 // SEANetResnetBlock (seanet_encoder.py:16-61): returns the two raw branches whose GroupNorm'd sum is the output
 // The block's input is one tensor (first block of a stage) or the pending sum of the previous block's two branches.
 // shortcut(x) and block.1(ELU(x)) of a thin residual block from ONE staging of x (kernels.hip 1c); same outputs / statistics
@@ -1121,8 +1281,8 @@ Act run_encoder(fc_engine* e, Ctx& cx, const float* wav, int T, const float* sca
         run_resblocks(e, cx, S, src_of(x), fc::Src(), x.T, &sc, &b3);
         x = run_conv(e, cx, S.resample, src_of(sc), src_of(b3), 1, sc.T);
     }
-    if (e->enc_lstm.H) {
-        Act y = run_lstm(e, cx, e->enc_lstm, x, x.T);
+    if (has_seq(e->enc_lstm, e->enc_tf)) {
+        Act y = run_seq(e, cx, e->enc_lstm, e->enc_tf, x, x.T);
         if (e->arch.lstm_skip) return run_conv(e, cx, e->enc_last, src_of(y), src_of(x), 1, x.T);
         return run_conv(e, cx, e->enc_last, src_of(y), fc::Src(), 1, x.T);
     }
@@ -1134,8 +1294,8 @@ Act run_decoder(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf) {
     fc::Src s; s.ptr = z_bdt; s.used = 1;
     Act x = run_conv(e, cx, e->dec_first, s, fc::Src(), 0, Tf);
     fc::Src a0 = src_of(x), a1;
-    if (e->dec_lstm.H) {
-        Act y = run_lstm(e, cx, e->dec_lstm, x, x.T);
+    if (has_seq(e->dec_lstm, e->dec_tf)) {
+        Act y = run_seq(e, cx, e->dec_lstm, e->dec_tf, x, x.T);
         a0 = src_of(y);
         if (e->arch.lstm_skip) a1 = src_of(x);
     }
@@ -1485,8 +1645,8 @@ Act run_encoder_2d(fc_engine* e, Ctx& cx, const float* wav, int T, const float* 
     if (!cx.dry && !cx.err && x.F != 1) { cx.err = 1; g_err = "the 2-D encoder must reduce the frequency axis to one bin (n_fft / ratios mismatch)"; }
     Act x1;                                                                        // ReshapeModule: [B][1][C][T] is [B][C][T]
     x1.raw = x.buf; x1.aff = x.aff; x1.C = x.C; x1.T = x.T; x1.normed = x.normed;
-    if (e->enc_lstm.H) {
-        Act y = run_lstm(e, cx, e->enc_lstm, x1, x1.T);
+    if (has_seq(e->enc_lstm, e->enc_tf)) {
+        Act y = run_seq(e, cx, e->enc_lstm, e->enc_tf, x1, x1.T);
         if (a.lstm_skip) return run_conv(e, cx, e->enc_last, src_of(y), src_of(x1), 1, x1.T);
         return run_conv(e, cx, e->enc_last, src_of(y), fc::Src(), 1, x1.T);
     }
@@ -1503,8 +1663,8 @@ void run_decoder_2d(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const flo
     bool has1 = false;
     auto as2 = [](const Act& t) { Act2 r; r.buf = t.raw; r.aff = t.aff; r.C = t.C; r.F = 1; r.T = t.T; r.halo = 0; r.normed = t.normed; return r; };
     a0 = as2(x);
-    if (e->dec_lstm.H) {
-        Act y = run_lstm(e, cx, e->dec_lstm, x, x.T);
+    if (has_seq(e->dec_lstm, e->dec_tf)) {
+        Act y = run_seq(e, cx, e->dec_lstm, e->dec_tf, x, x.T);
         a0 = as2(y);
         if (a.lstm_skip) { a1 = as2(x); has1 = true; }
     }
@@ -1692,8 +1852,17 @@ int fc_engine_create(const fc_arch* arch, int device, fc_engine** out) {
     }
     if (arch->codebook_size % 64 || (arch->codebook_size > 128 && arch->codebook_size % 128))
         return fail("codebook_size must be a multiple of 64, and of 128 above 128 (8 waves x 16-code tiles)");
-    if (arch->lstm_layers > 0 && ((arch->n_filters << arch->n_ratios) % 16)) return fail("LSTM width must be a multiple of 16");
-    if (arch->lstm_layers > FC_LSTM_MAX_LAYERS) return fail("too many LSTM layers");
+    if (arch->seq_model != 0 && arch->seq_model != 1) return fail("fc_arch.seq_model must be 0 (SLSTM) or 1 (TransformerEncoder)");
+    if (arch->seq_model == 0 && arch->lstm_layers > 0 && ((arch->n_filters << arch->n_ratios) % 16)) return fail("LSTM width must be a multiple of 16");
+    if (arch->seq_model == 0 && arch->lstm_layers > FC_LSTM_MAX_LAYERS) return fail("too many LSTM layers");
+    if (arch->seq_model == 1 && arch->lstm_layers > 0) {
+        const int C = arch->n_filters << arch->n_ratios;
+        if (arch->seq_heads < 1 || C % arch->seq_heads || !fc::seq_attn_supported(C / arch->seq_heads))
+            return fail("transformer bottleneck: head size C / seq_heads must be 16, 32, 64, 128 or 256 (C = " + std::to_string(C) + ")");
+        if (C % 16 || C > 1024) return fail("transformer bottleneck: width must be a multiple of 16 and at most 1024 (LayerNorm kernel)");
+        if (arch->seq_ff < 1) return fail("transformer bottleneck: seq_ff must be >= 1");
+        if (arch->lstm_layers > 64) return fail("transformer bottleneck: at most 64 blocks");
+    }
     for (int i = 0; i < arch->n_ratios; ++i)
         if (arch->ratios[i] < 1) return fail("ratios must be >= 1");
     if (arch->model_type != 0 && arch->model_type != 1) return fail("fc_arch.model_type must be 0 (encodec) or 1 (freq_codec, mag_phase)");
@@ -1855,6 +2024,7 @@ int fc_engine_finalize(fc_engine* e) {
         if (pack_conv(e, *L)) return 1;
     if (pack_lstm(e, e->enc_lstm)) return 1;
     if (pack_lstm(e, e->dec_lstm)) return 1;
+    if (pack_tf(e, e->enc_tf) || pack_tf(e, e->dec_tf)) return 1;
     // codebooks + |e|^2 (EuclideanCodebook.quantize ddp_core_vq.py:185: embed.pow(2).sum(0)); sequential d, squares rounded
     const auto& E = e->host["quantizer.rq.model.embed"].data;
     const int nq = e->arch.num_quantizers, K = e->arch.codebook_size, D = e->cdim();
@@ -1928,7 +2098,7 @@ int fc_engine_work(const fc_engine* ce, int B, int T, int n_q, fc_work* out) {
     do_decode(e, cx, nullptr, frames_for(e, T), nullptr, T, nullptr);
     out->conv_flops = cx.conv_flops; out->conv_bytes = cx.conv_bytes;
     out->lstm_flops = cx.lstm_flops; out->rvq_flops = cx.rvq_flops;
-    out->total_flops = cx.conv_flops + cx.lstm_flops + cx.rvq_flops;
+    out->total_flops = cx.conv_flops + cx.lstm_flops + cx.rvq_flops + cx.attn_flops;     // transformer Linears are in conv_flops
     out->total_bytes = cx.conv_bytes;
     out->conv_launches = cx.conv_launches; out->total_launches = cx.launches;
     return 0;
@@ -2175,6 +2345,22 @@ int fc_lstm_forward(fc_engine* e, const char* prefix, const float* x, int B, int
     if (cx.err) return 1;
     fc::Src s1;
     if (e->arch.lstm_skip) s1 = src_of(in);
+    HIP_TRY(fc::launch_combine(src_of(o), s1, 0, 1.f, nullptr, B, o.C, T, T, y, (long long)o.C * T, T, 1, cx.st));
+    return 0;
+}
+
+int fc_seq_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, float* y, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    if (check_ready(e)) return 1;
+    if (!prefix || !x || !y || B <= 0 || T <= 0) return fail("bad argument");
+    auto it = e->tf_by_prefix.find(prefix);
+    if (it == e->tf_by_prefix.end()) return fail(std::string("unknown transformer ") + prefix);
+    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Act in; in.raw = const_cast<float*>(x); in.C = it->second->C; in.T = T;
+    Act o = run_transformer(e, cx, *it->second, in, T);
+    if (cx.err) return 1;
+    fc::Src s1;
+    if (e->arch.lstm_skip) s1 = src_of(in);           // TransformerEncoder(skip=res_seq): after_norm(x) + input
     HIP_TRY(fc::launch_combine(src_of(o), s1, 0, 1.f, nullptr, B, o.C, T, T, y, (long long)o.C * T, T, 1, cx.st));
     return 0;
 }

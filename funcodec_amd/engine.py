@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import ArchSpec
+from .config import SEQ_FF, SEQ_HEADS, ArchSpec
 
 
 class EngineError(RuntimeError):
@@ -49,7 +49,7 @@ class CodecEngine:
     def __init__(self, arch: ArchSpec, device: "torch.device | str | int" = "cuda:0"):
         self.lib = _lib.load()
         self.arch = arch
-        if arch.lstm_layers > 0 and arch.bottleneck_channels == 512:
+        if arch.lstm_layers > 0 and arch.seq_model == "lstm" and arch.bottleneck_channels == 512:
             # H = 512: the persistent LSTM advances two 16-utterance batch tiles side by side (128 workgroups each), so 32 utterances
             # per call cost the recurrence what 16 do
             self.micro_batch = 32
@@ -95,6 +95,8 @@ class CodecEngine:
         a.codec_dim = arch.codebook_dim if arch.codebook_dim != arch.dimension else 0
         a.codec_range = float(arch.codec_range or 0.0)
         a.q0_ds_ratio = int(arch.q0_ds_ratio)
+        a.seq_model = {"lstm": 0, "transformer": 1}[arch.seq_model]
+        a.seq_heads, a.seq_ff = SEQ_HEADS, SEQ_FF
         h = C.c_void_p()
         self._check(self.lib.fc_engine_create(C.byref(a), self.device.index, C.byref(h)))
         self._h = h
@@ -449,4 +451,22 @@ class CodecEngine:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         ws = self._ws
         self._check(self.lib.fc_lstm_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
+        return y
+
+    @_on_device
+    def seq_forward(self, prefix: str, x: torch.Tensor) -> torch.Tensor:
+        """TransformerEncoder.forward of the bottleneck transformer at Sequential prefix `prefix` (e.g. "encoder.model.16"): all blocks,
+        after_norm and the res_seq skip, [B,C,T] -> [B,C,T]."""
+        x = self._dev(x, torch.float32)
+        B, Cc, T = x.shape
+        want = self.expected_tensors().get(prefix + ".after_norm.weight")
+        if want is None or want[0] != Cc:
+            raise EngineError(f"transformer {prefix!r}: expected input [B, {want[0] if want else '?'}, T], got {tuple(x.shape)}")
+        y = torch.empty_like(x)
+        # residual stream, LayerNorm out, branch out, attention out, result: 5 x [B,C,T]; q|k|v [B,3C,T]; feed-forward hidden [B,ff,T]
+        need = 4 * B * T * (8 * Cc + SEQ_FF) + (1 << 20)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._ws
+        self._check(self.lib.fc_seq_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y

@@ -11,22 +11,46 @@ from __future__ import annotations
 import dataclasses
 from typing import Dict, List, Tuple
 
-from .config import ArchSpec
+from .config import SEQ_FF, ArchSpec
 
 
 @dataclasses.dataclass
 class ConvOp:
-    kind: str            # "conv" | "convtr" | "lstm"
+    kind: str            # "conv" | "convtr" | "lstm" | "transformer"
     key: str             # state_dict prefix, e.g. "encoder.model.3.conv"
     cin: int
     cout: int
     k: int = 1
     stride: int = 1
-    role: str = ""       # "first" | "shortcut" | "block1" | "block3" | "down" | "up" | "last" | "lstm"
+    role: str = ""       # "first" | "shortcut" | "block1" | "block3" | "down" | "up" | "last" | "lstm" | "transformer"
     dilation: int = 1
     kf: int = 0          # 2-D layers (freq_codec): kernel / stride along frequency; 0 = a 1-D layer
     sf: int = 1
     groups: int = 1      # grouped 2-D convs (conv_group_ratio > 0)
+
+
+def _seq_op(a: ArchSpec, key: str, c: int) -> ConvOp:
+    """The bottleneck sequence model at Sequential index `key`: SLSTM (keys under `.lstm`) or TransformerEncoder (keys directly under
+    the index: `.encoders.{l}...`, `.after_norm`)."""
+    if a.seq_model == "transformer":
+        return ConvOp("transformer", key, c, c, role="transformer")
+    return ConvOp("lstm", key + ".lstm", c, c, role="lstm")
+
+
+def transformer_tensors(key: str, c: int, blocks: int, ff: int) -> List[Tuple[str, Tuple[int, ...]]]:
+    """Checkpoint tensors of TransformerEncoder(c, output_size=c, input_layer=None) in state_dict order (transformer.py:147-164,
+    EncoderLayer / MultiHeadedAttention / PositionwiseFeedForward)."""
+    out: List[Tuple[str, Tuple[int, ...]]] = []
+    for l in range(blocks):
+        p = f"{key}.encoders.{l}"
+        for n in ("linear_q", "linear_k", "linear_v", "linear_out"):
+            out += [(f"{p}.self_attn.{n}.weight", (c, c)), (f"{p}.self_attn.{n}.bias", (c,))]
+        out += [(f"{p}.feed_forward.w_1.weight", (ff, c)), (f"{p}.feed_forward.w_1.bias", (ff,)),
+                (f"{p}.feed_forward.w_2.weight", (c, ff)), (f"{p}.feed_forward.w_2.bias", (c,))]
+        for n in ("norm1", "norm2"):
+            out += [(f"{p}.{n}.weight", (c,)), (f"{p}.{n}.bias", (c,))]
+    out += [(f"{key}.after_norm.weight", (c,)), (f"{key}.after_norm.bias", (c,))]
+    return out
 
 
 def encoder_plan(a: ArchSpec) -> List[ConvOp]:
@@ -50,7 +74,7 @@ def encoder_plan(a: ArchSpec) -> List[ConvOp]:
         mult *= 2
     c = mult * a.n_filters
     if a.lstm_layers > 0:
-        ops.append(ConvOp("lstm", f"encoder.model.{idx}.lstm", c, c, role="lstm"))
+        ops.append(_seq_op(a, f"encoder.model.{idx}", c))
         idx += 1
     idx += 1              # ELU
     ops.append(ConvOp("conv", f"encoder.model.{idx}.conv", c, a.dimension, a.last_kernel_size, 1, "last"))
@@ -65,7 +89,7 @@ def decoder_plan(a: ArchSpec) -> List[ConvOp]:
     ops.append(ConvOp("conv", f"decoder.model.{idx}.conv", a.dimension, c, a.kernel_size, 1, "first"))
     idx += 1
     if a.lstm_layers > 0:
-        ops.append(ConvOp("lstm", f"decoder.model.{idx}.lstm", c, c, role="lstm"))
+        ops.append(_seq_op(a, f"decoder.model.{idx}", c))
         idx += 1
     for ratio in a.ratios:
         c = mult * a.n_filters
@@ -112,7 +136,7 @@ def encoder_plan_2d(a: ArchSpec) -> List[ConvOp]:
     idx += 1              # ReshapeModule
     c = mult * a.n_filters
     if a.lstm_layers > 0:
-        ops.append(ConvOp("lstm", f"encoder.model.{idx}.lstm", c, c, role="lstm"))
+        ops.append(_seq_op(a, f"encoder.model.{idx}", c))
         idx += 1
     idx += 1              # ELU
     ops.append(ConvOp("conv", f"encoder.model.{idx}.conv", c, a.dimension, a.last_kernel_size, 1, "last"))
@@ -129,7 +153,7 @@ def decoder_plan_2d(a: ArchSpec) -> List[ConvOp]:
     ops.append(ConvOp("conv", f"decoder.model.{idx}.conv", a.dimension, c, a.kernel_size, 1, "first"))
     idx += 1
     if a.lstm_layers > 0:
-        ops.append(ConvOp("lstm", f"decoder.model.{idx}.lstm", c, c, role="lstm"))
+        ops.append(_seq_op(a, f"decoder.model.{idx}", c))
         idx += 1
     idx += 1              # ReshapeModule
     for fr, tr in zip(a.ratios_f, a.ratios):
@@ -174,6 +198,8 @@ def expected_tensors(a: ArchSpec) -> Dict[str, Tuple[int, ...]]:
             if gn:
                 out[f"{op.key}.norm.weight"] = (op.cout,)
                 out[f"{op.key}.norm.bias"] = (op.cout,)
+        elif op.kind == "transformer":
+            out.update(transformer_tensors(op.key, op.cin, a.lstm_layers, SEQ_FF))
         else:
             h = op.cin
             for l in range(a.lstm_layers):

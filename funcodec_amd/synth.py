@@ -14,8 +14,29 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .config import ArchSpec, arch_from_config, recipe_config
-from .plan import decoder_plan, encoder_plan
+from .config import SEQ_FF, ArchSpec, arch_from_config, recipe_config
+from .plan import decoder_plan, encoder_plan, transformer_tensors
+
+# the transformer bottleneck's weights come from a stream of their own (seed + _TF_SEED_OFFSET), drawn after everything else: the
+# checkpoints of every other configuration stay byte-identical to what they were before the transformer existed
+_TF_SEED_OFFSET = 104729
+
+
+def _transformer_weights(sd: Dict[str, np.ndarray], blocks: list, seed: int) -> None:
+    """torch-default-like TransformerEncoder weights for every (key, width, blocks) in `blocks`: Linear weight and bias
+    U(+-1/sqrt(in)); LayerNorm gamma / beta randomised around (1, 0) so that a kernel which forgot the affine part cannot pass."""
+    rng = np.random.Generator(np.random.PCG64(seed + _TF_SEED_OFFSET))
+    for key, c, n in blocks:
+        fan_in = c
+        for name, shape in transformer_tensors(key, c, n, SEQ_FF):      # every Linear's weight comes right before its bias
+            module, leaf = name.rsplit(".", 2)[-2:]
+            if module.startswith("norm") or module == "after_norm":
+                v = 1.0 + 0.1 * rng.standard_normal(shape) if leaf == "weight" else 0.1 * rng.standard_normal(shape)
+            else:
+                if leaf == "weight":
+                    fan_in = shape[1]
+                v = rng.uniform(-1.0 / np.sqrt(fan_in), 1.0 / np.sqrt(fan_in), size=shape)
+            sd[name] = v.astype(np.float32)
 
 
 def make_state_dict(arch: ArchSpec, seed: int = 0, codebook_sigma_decay: float = 1.0,
@@ -51,7 +72,7 @@ def make_state_dict(arch: ArchSpec, seed: int = 0, codebook_sigma_decay: float =
             if arch.norm == "time_group_norm":
                 sd[f"{op.key}.norm.weight"] = (1.0 + 0.1 * rng.standard_normal(op.cout)).astype(np.float32)
                 sd[f"{op.key}.norm.bias"] = (0.1 * rng.standard_normal(op.cout)).astype(np.float32)
-        else:
+        elif op.kind == "lstm":
             h = op.cin
             bound = 1.0 / np.sqrt(h)
             for l in range(arch.lstm_layers):
@@ -75,6 +96,9 @@ def make_state_dict(arch: ArchSpec, seed: int = 0, codebook_sigma_decay: float =
         # keys a real checkpoint carries and the inference engine must skip
         # (discriminator.* and mel_spec_transforms.*)
         sd["discriminator.discriminators.0.dummy.weight"] = np.zeros((4, 4), np.float32)
+    tf = [(op.key, op.cin, arch.lstm_layers) for op in encoder_plan(arch) + decoder_plan(arch) if op.kind == "transformer"]
+    if tf:
+        _transformer_weights(sd, tf, seed)
     return sd
 
 
@@ -130,8 +154,12 @@ def freq_plan(cfg: Dict[str, Any]) -> list:
     idx += 1                                          # ReshapeModule
     cb = mult * nf
     has_lstm = enc.get("seq_model", "lstm") == "lstm"
+    has_tf = enc.get("seq_model", "lstm") == "transformer"
     if has_lstm:
         ops.append(("lstm", f"encoder.model.{idx}.lstm", (cb, enc.get("seq_layer_num", 2))))
+        idx += 1
+    elif has_tf:
+        ops.append(("transformer", f"encoder.model.{idx}", (cb, enc.get("seq_layer_num", 2))))
         idx += 1
     idx += 1                                          # ELU
     ops.append(("conv", f"encoder.model.{idx}.conv", (dim, cb, lks)))
@@ -140,6 +168,9 @@ def freq_plan(cfg: Dict[str, Any]) -> list:
     idx += 1
     if has_lstm:
         ops.append(("lstm", f"decoder.model.{idx}.lstm", (cb, enc.get("seq_layer_num", 2))))
+        idx += 1
+    elif has_tf:
+        ops.append(("transformer", f"decoder.model.{idx}", (cb, enc.get("seq_layer_num", 2))))
         idx += 1
     idx += 1                                          # ReshapeModule
     for fr, tr in ratios:
@@ -168,6 +199,8 @@ def make_freq_state_dict(cfg: Dict[str, Any], seed: int = 0) -> Dict[str, np.nda
         return rng.uniform(-bound, bound, size=shape).astype(np.float32)
 
     for kind, key, shape in freq_plan(cfg):
+        if kind == "transformer":
+            continue
         if kind == "lstm":
             h = shape[0]
             b = 1.0 / np.sqrt(h)
@@ -209,6 +242,9 @@ def make_freq_state_dict(cfg: Dict[str, Any], seed: int = 0) -> Dict[str, np.nda
     sd[f"{pfx}.cluster_size"] = np.ones((nq, K), np.float32)
     sd[f"{pfx}.embed"] = embed
     sd[f"{pfx}.embed_avg"] = embed.copy()
+    tf = [(key, shape[0], shape[1]) for kind, key, shape in freq_plan(cfg) if kind == "transformer"]
+    if tf:
+        _transformer_weights(sd, tf, seed)
     return sd
 
 

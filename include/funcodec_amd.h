@@ -26,7 +26,9 @@ extern "C" {
 #endif
 
 #define FC_MAX_RATIOS 8
-#define FC_ABI_VERSION 6     /* layout of fc_arch / fc_laura_arch.  6 (round 4): fc_arch.q0_ds_ratio appended; fc_arch.input_channels = 2 with
+#define FC_ABI_VERSION 7     /* layout of fc_arch / fc_laura_arch.  7: fc_arch.seq_model / seq_heads / seq_ff appended (the transformer
+                              * bottleneck, seq_model: transformer) and fc_seq_forward added.
+                              * 6 (round 4): fc_arch.q0_ds_ratio appended; fc_arch.input_channels = 2 with
                               * model_type 0 is the stereo time-domain codec.  (Round 4 also added entry points that changed no struct:
                               * fc_laura_set_persistent_step, fc_debug_freq_features, fc_q0_source_frames.) */
 
@@ -85,6 +87,13 @@ typedef struct fc_arch {
     int32_t q0_ds_ratio;            /* quantizer_conf.q0_ds_ratio (funcodec/modules/quantization/ddp_core_vq.py:354-356,396-404): <= 1 = off;
                                        > 1: the FIRST quantiser stage sees the nearest-neighbour half-rate sequence (the reference halves
                                        whatever the value is) and its output / indices are repeated back to Tf frames */
+    /* ABI version 7: the sequence model at the bottleneck (encoder_conf / decoder_conf seq_model; seanet_encoder.py:142-151,328-337,
+     * seanet_decoder.py:116-125,297-306).  lstm_layers counts its layers / blocks and lstm_skip is its res_seq in both cases. */
+    int32_t seq_model;              /* 0 = SLSTM with lstm_layers layers; 1 = TransformerEncoder (normed_modules/transformer.py:26-208) with
+                                       lstm_layers pre-LayerNorm blocks, no positional encoding, causal when `causal` is set; the bottleneck
+                                       width C = n_filters << n_ratios must be 64, 128, 256, 512 or 1024 (head size C / seq_heads in 16..256) */
+    int32_t seq_heads;              /* attention heads of the transformer (4, the TransformerEncoder default) */
+    int32_t seq_ff;                 /* feed-forward units of the transformer (2048, linear_units default) */
 } fc_arch;
 
 /* ---- lifetime ------------------------------------------------------------------------------------ */
@@ -224,6 +233,11 @@ int fc_resblock_forward(fc_engine* e, const char* prefix, const float* x, int B,
 /* SLSTM.forward (lstm.py:22-28) addressed by prefix ("encoder.model.16.lstm"): x,y dev f32 [B,C,T]. */
 int fc_lstm_forward(fc_engine* e, const char* prefix, const float* x, int B, int T,
                     float* y, void* workspace, size_t workspace_bytes, void* stream);
+
+/* TransformerEncoder.forward (normed_modules/transformer.py:150-208: blocks, after_norm, + x when res_seq) addressed by prefix
+ * ("encoder.model.16"): x, y dev f32 [B,C,T]; the workspace of fc_engine_workspace_bytes for the same (B, T * hop) suffices. */
+int fc_seq_forward(fc_engine* e, const char* prefix, const float* x, int B, int T,
+                   float* y, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- profiling aid ------------------------------------------------------------------------------- */
 /* Algorithmic work of one fc_encode_decode call: flops and bytes, total and for the

@@ -13,10 +13,13 @@ synthetic 10 s / 16 kHz audio on the 16k-nq32ds640 architecture:
          per-utterance, results do not depend on the micro-batch), the int64 code indices all-gathered over RCCL inside the step.
 `--workload freqcodec` is a SIDE measurement of the next scope row (BASELINE.json configs[3]: the STFT-domain FreqCodec recipe, 64 x 10 s
 on one GPU); the contract metric stays the default.
-Inputs are resident in HBM when timing starts.  The timed region runs WITHOUT the in-engine HIP-event brackets; the per-kernel
-table (and with it `roofline`) comes from a second, separate pass of the same step.  Rank 0 prints ONE compact JSON line
-(contract_line); `--detail-json FILE` writes the full record (per-kernel tables, every roofline object) next to it.
-`--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy (dump_outputs).
+Inputs are resident in HBM when timing starts.  The timed region runs WITHOUT the in-engine HIP-event brackets.  A plain run does
+only what the headline needs: set up, warm up, time the steps, dump the outputs if asked, print the line.  `--full` adds everything
+else, after the timed steps: the H2D / D2H transfer times, a second, separate pass of the same step for the per-kernel table (and with
+it `roofline`), the CPU baseline, the side measurements of configs[2] - [4] (`secondary`) and, for N > 1, the per-rank / gather-only
+diagnostics (`multi_gpu`); `--no-event-profile`, `--no-cpu-baseline` and `--no-secondary` leave parts of it out.  Rank 0 prints ONE
+compact JSON line (contract_line); `--detail-json FILE` writes the full record (with --full: per-kernel tables, every roofline object)
+next to it.  `--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -726,13 +729,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-event-profile", action="store_true", help="skip the separate per-kernel HIP-event pass (no `roofline`)")
-    ap.add_argument("--profile-steps", type=int, default=5, help="steps of the separate per-kernel pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the transfers, the per-kernel pass (`roofline`), the CPU baseline, the side "
+                         "workloads (`secondary`) and, for N > 1, the per-rank / gather-only diagnostics (`multi_gpu`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of --full and the LauraTTS CPU sample")
+    ap.add_argument("--no-event-profile", action="store_true", help="with --full: skip the separate per-kernel HIP-event pass (no `roofline`)")
+    ap.add_argument("--profile-steps", type=int, default=5, help="steps of the separate per-kernel pass (--full)")
     ap.add_argument("--workload", choices=("encodec", "freqcodec", "freqcodec_gr1", "laura"), default="encodec",
                     help="encodec = the contract metric (BASELINE.json configs[1] / [2]); freqcodec / freqcodec_gr1 = side measurement of "
-                         "configs[3]; laura = side measurement of configs[4]")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] side measurements of the default run")
+                         "configs[3]; laura = side measurement of configs[4] (freqcodec_gr1 and laura print their whole record, "
+                         "--full or not)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the configs[2] - [4] side measurements")
     ap.add_argument("--dry-run-launcher", action="store_true",
                     help="exercise rank launch + sharding + gather + the JSON line over gloo without the engine (CPU test of the N > 1 path)")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -837,7 +844,7 @@ def main():
     dt = time.perf_counter() - t0
     eng.check_status()
     diag = None
-    if world > 1:
+    if world > 1 and args.full:
         # ---- self-diagnosing N > 1 line: every rank's own wall time for the K steps, and a separate gather-only loop --
         # efficiency then reads as load balance (rank spread) vs the collective (gather_ms), not as one opaque number
         mine = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -866,6 +873,7 @@ def main():
                 "gather_note": "one all_gather_into_tensor of this rank's int64 codes per step, timed alone (barrier + sync on both sides, max over "
                                "ranks); inside the timed step it runs behind the last micro-batch's kernels on the same stream",
                 "backend": dist.get_backend(), "rccl_version": ver}
+    if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
@@ -879,7 +887,7 @@ def main():
 
     # ---- separate pass: per-kernel-class HIP-event durations on the engine's stream (NOT inside the timed region above)
     prof, prof_steps = [], 0
-    if rank == 0 and not args.no_event_profile:
+    if rank == 0 and args.full and not args.no_event_profile:
         prof_steps = max(1, min(args.profile_steps, args.steps))
         eng.set_profiling(True)
         fence_local = (lambda: None) if rehearsal else torch.cuda.synchronize
@@ -929,7 +937,7 @@ def main():
                            "traffic": (pmc_step_traffic() or {}).get("bytes_per_step") if (world == 1 and CONFIG == "ds640") else None,
                            "traffic_over_algorithmic": round(pmc_step_traffic()["bytes_per_step"] / (work["total_bytes"] * nmb), 2)
                            if (world == 1 and CONFIG == "ds640" and pmc_step_traffic()) else None},
-            "timed_region": "in-engine HIP-event brackets OFF; the per-kernel table (--detail-json) is a separate pass",
+            "timed_region": "in-engine HIP-event brackets OFF; the per-kernel table (--full, --detail-json) is a separate pass",
         }
         if rehearsal:
             out["metric"] = "REHEARSAL of the control flow with a stand-in engine (FC_BENCH_REHEARSAL=1): not a measurement"
@@ -939,20 +947,21 @@ def main():
             tf = codes.shape[2]
             expect = (exp_u[None, :, None] * 7 + torch.arange(n_q)[:, None, None] + torch.arange(tf)[None, None, :]) % 1024
             out["gather_ok"] = bool(torch.equal(codes, expect))
-        else:
+        elif args.full:
             out["transfers"] = transfer_times(wav, res[-1]["codes"])
         if prof:
             out.update(kernel_rooflines(prof, prof_steps))
             if "roofline" in out:
                 out["roofline"]["whole_step"] = out["whole_step"]
-        if world > 1:
+        if diag is not None:
             out["multi_gpu"] = diag
+        if world > 1:
             out["config"]["scaling_base"] = ("efficiency is to be computed against secondary.config_c_shard_b128.value of the --gpus 1 line (same "
                                              "per-rank shape: 128 x 10 s in micro-batches of 32), NOT against the N = 1 contract value (Config B, "
                                              "16 utterances in one call)")
-        if world == 1 and not args.no_cpu_baseline and not rehearsal:
+        if world == 1 and args.full and not args.no_cpu_baseline and not rehearsal:
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and CONFIG == "ds640" and not args.no_secondary and not rehearsal:
+        if world == 1 and CONFIG == "ds640" and args.full and not args.no_secondary and not rehearsal:
             # the next scope rows, measured AFTER the headline timing so that they cannot disturb it
             sec = {}
             try:

@@ -71,7 +71,7 @@ def test_the_whole_n_rank_flow_of_bench_main_runs_on_cpu_with_a_stand_in_engine(
     loop over micro-batches (2 + 2 + 1 here), gather_codes inside the step, barrier + max-over-ranks timing, ONE JSON line from rank 0 with
     config.ranks_seen / scaling_base -- over gloo on CPU, and checks the gathered codes of all 10 utterances."""
     env = {"FC_BENCH_REHEARSAL": "1", "FC_BENCH_UTTS": "5", "FC_BENCH_SAMPLES": "6400", "FC_BENCH_MICRO": "2"}
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], env_extra=env)
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], env_extra=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout
@@ -80,7 +80,7 @@ def test_the_whole_n_rank_flow_of_bench_main_runs_on_cpu_with_a_stand_in_engine(
     assert out["config"]["ranks_seen"] == 2 and out["config"]["global_utterances"] == 10 and out["config"]["micro_batch"] == 2
     assert "config_c_shard_b128" in out["config"]["scaling_base"]
     assert out["gather_ok"] is True and "REHEARSAL" in out["metric"] and out["value"] == 0.0
-    # the self-diagnosing fields of an N > 1 line: per-rank step times, the gather timed alone, the collective library
+    # the self-diagnosing fields of an N > 1 --full line: per-rank step times, the gather timed alone, the collective library
     mg = out["multi_gpu"]
     assert len(mg["rank_ms_per_step"]) == 2 and mg["rank_ms_per_step_min"] <= mg["rank_ms_per_step_max"]
     assert abs(mg["rank_ms_per_step_max"] - max(mg["rank_ms_per_step"])) < 1e-9 and mg["rank_ms_per_step_max"] <= out["ms_per_step"] * 1.5 + 1.0
@@ -90,6 +90,22 @@ def test_the_whole_n_rank_flow_of_bench_main_runs_on_cpu_with_a_stand_in_engine(
     assert r1.returncode == 0, r1.stderr[-3000:]
     o1 = _json_lines(r1.stdout)[0]
     assert o1["n_gpus"] == 1 and o1["gather_ok"] is True and o1["config"]["ranks_seen"] == 1 and "multi_gpu" not in o1
+
+
+def test_a_plain_n_rank_run_stops_at_the_headline():
+    """Without --full the run ends with the headline: the same flow and line as above (max-over-ranks timing, the gathered codes checked),
+    but none of what --full adds after the timed steps (here: the per-rank / gather-only diagnostics)."""
+    env = {"FC_BENCH_REHEARSAL": "1", "FC_BENCH_UTTS": "5", "FC_BENCH_SAMPLES": "6400", "FC_BENCH_MICRO": "2"}
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], env_extra=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    out = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1 and out["config"]["ranks_seen"] == 2
+    assert out["gather_ok"] is True and out["ms_per_step"] > 0
+    assert not {"multi_gpu", "transfers", "roofline", "kernels", "cpu_baseline", "secondary"} & set(out)
 
 
 def test_the_printed_line_stays_compact_and_keeps_the_headline():

@@ -105,28 +105,6 @@ struct Act {               // raw tensor [B][C][T] + pending GroupNorm affine (n
     bool normed = false;   // has a pending affine (valid in dry-run planning too, where pointers are null)
 };
 
-struct Ctx {
-    int B = 0;
-    hipStream_t st = nullptr;
-    char* base = nullptr;
-    size_t cap = 0, off = 256;       // the first buffer starts 256 bytes in: the grouped 3 x 3 conv reads one float in front of a row (freq_kernels.hip, FASTEDGE)
-    bool dry = false;
-    int err = 0;
-    static constexpr size_t kTailSlack = 4096;
-    int launches = 0, conv_launches = 0;
-    double conv_flops = 0, conv_bytes = 0, lstm_flops = 0, rvq_flops = 0, other_bytes = 0, attn_flops = 0;
-    template <typename T>
-    T* alloc(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = dry ? nullptr : (T*)(base + off);
-        off += n * sizeof(T);
-        // every buffer ends at least kTailSlack bytes before the end of the workspace: kernels with unclamped row-end loads (the grouped
-        // 3 x 3 / 8 x 2 convs, freq_kernels.hip FASTEDGE) and the DMA-staged conv (over-read of the last N tile) rely on it
-        if (!dry && off + kTailSlack > cap) { err = 1; g_err = "workspace too small (sizes from fc_engine_workspace_bytes include 4 KiB of tail slack)"; return nullptr; }
-        return p;
-    }
-};
-
 int ceil_div_i(int a, int b) { return (a + b - 1) / b; }
 
 const char* kLstmPersistClass = "lstm_persist_kernel<NS> (whole recurrence of one SLSTM block, one launch)";
@@ -203,11 +181,13 @@ hipEvent_t prof_event(fc_engine* e) {
     return e->event_pool[e->events_used++];
 }
 
-struct ProfSpan {   // RAII: records start now, stop at scope exit
+// RAII: an event bracket from construction to scope exit, booked to the kernel class cls() names (called only when profiling)
+struct ProfSpan {
     fc_engine* e; hipStream_t st; int idx = -1;
-    ProfSpan(fc_engine* e_, Ctx& cx, int cls, double flops, double bytes) : e(e_), st(cx.st) {
-        if (!e->profiling || cx.dry || cx.err) return;
-        fc_engine::Span s; s.a = prof_event(e); s.b = prof_event(e); s.cls = cls; s.flops = flops; s.bytes = bytes;
+    template <typename Cls>
+    ProfSpan(fc_engine* e_, hipStream_t st_, bool live, Cls&& cls, double flops, double bytes) : e(e_), st(st_) {
+        if (!e->profiling || !live) return;
+        fc_engine::Span s; s.cls = e->prof_class(cls()); s.a = prof_event(e); s.b = prof_event(e); s.flops = flops; s.bytes = bytes;
         if (!s.a || !s.b) return;
         (void)hipEventRecord(s.a, st);
         e->spans.push_back(s);
@@ -215,6 +195,75 @@ struct ProfSpan {   // RAII: records start now, stop at scope exit
     }
     ~ProfSpan() { if (idx >= 0) (void)hipEventRecord(e->spans[idx].b, st); }
 };
+
+// One pass of the layer drivers over the plan.  A dry pass (no workspace, no stream) sizes the workspace and counts the work; a live
+// pass also enqueues.  Both run the same code, so the launch counts are the launch sequence itself.
+struct Ctx {
+    fc_engine* e = nullptr;
+    int B = 0;
+    hipStream_t st = nullptr;
+    char* base = nullptr;
+    size_t cap = 0, off = 256;       // the first buffer starts 256 bytes in: the grouped 3 x 3 conv reads one float in front of a row (freq_kernels.hip, FASTEDGE)
+    bool dry = false;
+    int err = 0;
+    static constexpr size_t kTailSlack = 4096;
+    int launches = 0, conv_launches = 0;
+    double conv_flops = 0, conv_bytes = 0, lstm_flops = 0, rvq_flops = 0, attn_flops = 0;
+    bool live() const { return !dry && !err; }
+    void fail(const std::string& msg) {      // the first failure of the pass is the one reported
+        if (!err) { err = 1; g_err = msg; }
+    }
+    template <typename T>
+    T* alloc(size_t n) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = dry ? nullptr : (T*)(base + off);
+        off += n * sizeof(T);
+        // every buffer ends at least kTailSlack bytes before the end of the workspace: kernels with unclamped row-end loads (the grouped
+        // 3 x 3 / 8 x 2 convs, freq_kernels.hip FASTEDGE) and the DMA-staged conv (over-read of the last N tile) rely on it
+        if (!dry && off + kTailSlack > cap) { fail("workspace too small (sizes from fc_engine_workspace_bytes include 4 KiB of tail slack)"); return nullptr; }
+        return p;
+    }
+    // One kernel launch: counted in both passes, enqueued only in a live one.  enqueue() returns the launch's status; a failure is
+    // reported as `what` of `layer`.
+    template <typename Enqueue>
+    void launch(const char* what, const char* layer, Enqueue&& enqueue) {
+        ++launches;
+        if (live()) check(enqueue(), what, layer);
+    }
+    // the same inside a profiler bracket that books `flops` and `bytes` to the kernel class cls() names
+    template <typename Cls, typename Enqueue>
+    void launch(const char* what, const char* layer, Cls&& cls, double flops, double bytes, Enqueue&& enqueue) {
+        ++launches;
+        if (!live()) return;
+        ProfSpan sp(e, st, true, cls, flops, bytes);
+        check(enqueue(), what, layer);
+    }
+    // a launch of a conv kernel (also counted in conv_launches)
+    template <typename Cls, typename Enqueue>
+    void conv_launch(const char* what, const char* layer, Cls&& cls, double flops, double bytes, Enqueue&& enqueue) {
+        ++conv_launches;
+        launch(what, layer, cls, flops, bytes, enqueue);
+    }
+    void check(hipError_t er, const char* what, const char* layer) {
+        if (er != hipSuccess) fail(std::string(what) + " launch failed" + (*layer ? std::string(" (") + layer + ")" : "") + ": " + hipGetErrorString(er));
+    }
+};
+
+Ctx make_ctx(fc_engine* e, int B, void* ws, size_t ws_bytes, void* stream) {
+    Ctx cx;
+    cx.e = e; cx.B = B; cx.st = (hipStream_t)stream; cx.base = (char*)ws; cx.cap = ws_bytes;
+    return cx;
+}
+
+Ctx dry_ctx(fc_engine* e, int B) {
+    Ctx cx = make_ctx(e, B, nullptr, 0, nullptr);
+    cx.dry = true;
+    return cx;
+}
+
+// a buffer position that stays null in a dry pass
+template <typename T>
+T* at(T* p, long long off) { return p ? p + off : nullptr; }
 
 // ---- plan construction (mirrors nn.Sequential indices: seanet_encoder.py:109-160, seanet_decoder.py:111-164)
 void add_conv_expect(fc_engine* e, ConvLayer& L) {
@@ -1002,6 +1051,53 @@ ConvGeom conv_geom(const ConvLayer& L, int T) {
 }
 
 static bool out_override_blocks_xq(const ConvLayer& L) { return L.kf != 1 || L.valid || L.cout <= 4; }   // 2-D / STFT GEMMs / few-output FMA layers
+
+// FreqCodec: the direct kernels and the materialisation passes write the reflected / zero halo rows of their outputs themselves (round 4;
+// FC_HALO_FUSE=0: a halo_rows launch behind every producer, as before -- A / B aid)
+static bool halo_fuse_on() {
+    static const int v = fc::ab_knob("FC_HALO_FUSE", 1);
+    return v != 0;
+}
+
+struct Act2 {              // raw [B][F + 2*halo][C][T] + pending GroupNorm affine [B][C] (null = final)
+    float* buf = nullptr;
+    float* aff = nullptr;
+    int C = 0, F = 0, T = 0, halo = 0;
+    bool normed = false;
+};
+
+// the fields of a conv launch that come from the layer's plan and its time-axis geometry (1-D convs, 2-D convs, transposed phases)
+fc::ConvLaunch conv_launch_of(const ConvLayer& L, int B, int Tin, const ConvGeom& g) {
+    fc::ConvLaunch c;
+    c.wt = L.wt; c.bias = L.bias; c.koff = L.koff; c.w_plain = L.w_plain; c.bias_host0 = L.bias0;
+    c.B = B; c.Cin = L.cin; c.Tin = Tin; c.M = L.M;
+    c.k = L.gk; c.stride = L.gstride; c.dil = L.dil; c.padL = g.padL; c.padR = g.padR;
+    c.BM = L.BM; c.BN = L.BN; c.CC = L.CC; c.nchunk = L.nchunk; c.row = L.row ? 1 : 0;
+    return c;
+}
+
+// profiler class of a conv launch: the conv_mfma_kernel instantiation launch_conv picks, or its few-output FMA kernel
+std::string conv_class(const fc::ConvLaunch& c) {
+    int mode = 0, nu = 0, row = 0;
+    fc::conv_variant(c, &mode, &nu, &row);
+    char nm[80];
+    snprintf(nm, sizeof(nm), "conv_mfma_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", c.BM, c.BN, c.BM >= 128 ? 2 : 1, c.BM >= 128 ? 2 : 4, mode, nu,
+             (row & 1) ? "true" : "false", (row & 2) ? "true" : "false");
+    if (fc::conv_cout1_ok(c)) fc::conv_fewout_name(c, nm, sizeof(nm));
+    return nm;
+}
+
+// the launches behind a conv layer's kernel: GroupNorm statistics -> affine (GroupNorm nets), then the frequency halo rows of a 2-D
+// output that the kernel did not write itself (halo_of)
+void conv_finish(fc_engine* e, Ctx& cx, const ConvLayer& L, const double* partials, int nblk, double count, float* aff, const Act2* halo_of = nullptr) {
+    if (L.has_norm)
+        cx.launch("gn_finalize", L.prefix.c_str(),
+                  [&] { return fc::launch_gn_finalize(partials, nblk, count, L.gamma, L.beta, L.cout, e->arch.gn_eps, cx.B, aff, cx.st); });
+    if (halo_of)
+        cx.launch("halo rows", L.prefix.c_str(),
+                  [&] { return fc::launch_halo_rows(halo_of->buf, cx.B, halo_of->F, halo_of->halo, halo_of->C, halo_of->T, 0, cx.st); });
+}
+
 Act run_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tin,
              float* out_override = nullptr, long long sB = 0, long long sM = 0, long long sT = 0) {
     const ConvGeom g = conv_geom(L, Tin);
@@ -1017,26 +1113,17 @@ Act run_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, fc::Src s0, fc::Src s1, 
         const int Tp = padL_x + Tin + padR_x;
         float* tmp = xq ? cx.alloc<float>(fc::conv_xq_floats(cx.B, L.cin, Tp, L.BN, L.gstride, L.gk, L.dil))
                         : cx.alloc<float>((size_t)cx.B * L.cin * Tin);
-        cx.launches++;
-        if (!cx.dry && !cx.err) {
-            hipError_t er0 = xq ? fc::launch_combine_xq(s0, s1, elu, e->arch.elu_alpha, cx.B, L.cin, Tin, padL_x, padR_x,
-                                                        (L.transposed || L.zpadL >= 0) ? 1 : 0, tmp, cx.st)
-                                : fc::launch_combine(s0, s1, elu, e->arch.elu_alpha, nullptr, cx.B, L.cin, Tin, Tin, tmp,
-                                                     (long long)L.cin * Tin, Tin, 1, cx.st);
-            if (er0 != hipSuccess) { cx.err = 1; g_err = std::string("combine launch failed: ") + hipGetErrorString(er0); }
-        }
+        cx.launch("combine", L.prefix.c_str(), [&] {
+            return xq ? fc::launch_combine_xq(s0, s1, elu, e->arch.elu_alpha, cx.B, L.cin, Tin, padL_x, padR_x, (L.transposed || L.zpadL >= 0) ? 1 : 0, tmp, cx.st)
+                      : fc::launch_combine(s0, s1, elu, e->arch.elu_alpha, nullptr, cx.B, L.cin, Tin, Tin, tmp, (long long)L.cin * Tin, Tin, 1, cx.st);
+        });
         s0 = fc::Src(); s0.ptr = tmp; s0.used = 1;
         s1 = fc::Src();
         elu = 0;
         if (xq) xq_Tp = Tp;
     }
-    fc::ConvLaunch c;
+    fc::ConvLaunch c = conv_launch_of(L, cx.B, Tin, g);
     c.s0 = s0; c.s1 = s1; c.elu = elu; c.alpha = e->arch.elu_alpha;
-    c.wt = L.wt; c.bias = L.bias; c.koff = L.koff;
-    c.B = cx.B; c.Cin = L.cin; c.Tin = Tin; c.M = L.M;
-    c.k = L.gk; c.stride = L.gstride; c.dil = L.dil; c.padL = g.padL; c.padR = g.padR;
-    c.BM = L.BM; c.BN = L.BN; c.CC = L.CC; c.nchunk = L.nchunk; c.row = L.row ? 1 : 0;
-    c.w_plain = L.w_plain; c.bias_host0 = L.bias0;
     c.xq_Tp = xq_Tp;
     Act out;
     out.C = L.cout; out.T = g.Tout;
@@ -1063,37 +1150,12 @@ Act run_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, fc::Src s0, fc::Src s1, 
         out.normed = true;
     }
     // accounting (algorithmic: real channel counts, every operand touched once)
-    cx.conv_flops += 2.0 * cx.B * (double)L.M * L.cin * L.gk * c.Tout;
-    cx.conv_bytes += 4.0 * cx.B * ((double)L.cin * Tin * (s1.used ? 2 : 1) + (double)L.cout * g.Tout);
-    cx.launches += L.has_norm ? 2 : 1;
-    cx.conv_launches += 1;
-    if (cx.dry || cx.err) return out;
     const double fl = 2.0 * cx.B * (double)L.M * L.cin * L.gk * c.Tout;
     const double by = 4.0 * cx.B * ((double)L.cin * Tin * (s1.used ? 2 : 1) + (double)L.cout * g.Tout);
-    hipError_t er;
-    {
-        int cls = 0;
-        if (e->profiling) {
-            int mode = 0, nu = 0;
-            int row = 0;
-            fc::conv_variant(c, &mode, &nu, &row);
-            char nm[80];
-            snprintf(nm, sizeof(nm), "conv_mfma_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", L.BM, L.BN, L.BM >= 128 ? 2 : 1,
-                     L.BM >= 128 ? 2 : 4, mode, nu, (row & 1) ? "true" : "false", (row & 2) ? "true" : "false");
-            if (fc::conv_cout1_ok(c))
-                fc::conv_fewout_name(c, nm, sizeof(nm));
-            cls = e->prof_class(nm);
-        }
-        ProfSpan sp(e, cx, cls, fl, by);
-        er = fc::launch_conv(c, cx.st);
-    }
-    if (er != hipSuccess) { cx.err = 1; g_err = "conv launch failed (" + L.prefix + "): " + hipGetErrorString(er) +
-                " (invalid value = tiling / LDS limits, or an utterance longer than 2^32 / (4 * channels per chunk) samples)"; return out; }
-    if (L.has_norm) {
-        er = fc::launch_gn_finalize(c.partials, nblk, (double)L.cout * g.count_T, L.gamma, L.beta, L.cout, e->arch.gn_eps,
-                                    cx.B, out.aff, cx.st);
-        if (er != hipSuccess) { cx.err = 1; g_err = std::string("gn_finalize launch failed: ") + hipGetErrorString(er); }
-    }
+    cx.conv_flops += fl; cx.conv_bytes += by;
+    // an invalid-value failure: tiling / LDS limits, or an utterance longer than 2^32 / (4 * channels per chunk) samples
+    cx.conv_launch("conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
+    conv_finish(e, cx, L, c.partials, nblk, (double)L.cout * g.count_T, out.aff);
     return out;
 }
 
@@ -1118,25 +1180,23 @@ Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T) {
     Act y;
     y.C = H; y.T = T;
     y.raw = cx.alloc<float>((size_t)B * H * T);
-    cx.lstm_flops += 2.0 * B * (double)T * 4 * H * H * (2 * L - 1);
-    cx.launches += persist ? 2 : T + L;
-    if (!cx.dry && !cx.err) {
-        // algorithmic bytes per SURVEY.md 8d: the recurrent weights read ONCE (they stay resident in registers) + the x-projection in + y out;
-        // the per-step launches re-stream the weights, which is traffic, not algorithm
-        const double lstm_bytes = 4.0 * (4.0 * H * H * (2 * L - 1) + (double)T * B * 4.0 * H + (double)B * H * T);
-        ProfSpan sp(e, cx, e->profiling ? e->prof_class(persist ? kLstmPersistClass : kLstmWaveClass) : 0, 2.0 * B * (double)T * 4 * H * H * (2 * L - 1), lstm_bytes);
-        hipError_t er = fc::launch_zero_fill(state, persist ? fc::lstm_persist_clear_floats(B, H) : (size_t)3 * L * B * H, cx.st);
-        const float* w[FC_LSTM_MAX_LAYERS] = {nullptr};
-        const float* bias[FC_LSTM_MAX_LAYERS] = {nullptr};
-        for (int l = 0; l < L; ++l) { w[l] = l == 0 ? lb.layers[0].whh : lb.layers[l].wcat; bias[l] = lb.layers[l].bperm; }
-        if (persist) {
-            if (er == hipSuccess) er = fc::launch_lstm_persist(w[0], w[1], bias[1], xproj, state, y.raw, B, H, T, e->status_dev, cx.st);
-        } else {
-            float *h = state, *c = state + (size_t)2 * L * B * H;
-            for (int s = 0; s < T + L - 1 && er == hipSuccess; ++s)
-                er = fc::launch_lstm_wave(w, bias, xproj, h, c, y.raw, B, H, T, L, s, cx.st);
-        }
-        if (er != hipSuccess) { cx.err = 1; g_err = std::string("lstm step failed: ") + hipGetErrorString(er); }
+    const double fl = 2.0 * B * (double)T * 4 * H * H * (2 * L - 1);
+    cx.lstm_flops += fl;
+    // algorithmic bytes per SURVEY.md 8d: the recurrent weights read ONCE (they stay resident in registers) + the x-projection in + y out;
+    // the per-step launches re-stream the weights, which is traffic, not algorithm
+    const double by = 4.0 * (4.0 * H * H * (2 * L - 1) + (double)T * B * 4.0 * H + (double)B * H * T);
+    const float* w[FC_LSTM_MAX_LAYERS] = {nullptr};
+    const float* bias[FC_LSTM_MAX_LAYERS] = {nullptr};
+    for (int l = 0; l < L; ++l) { w[l] = l == 0 ? lb.layers[0].whh : lb.layers[l].wcat; bias[l] = lb.layers[l].bperm; }
+    const char* pre = lb.prefix.c_str();
+    ProfSpan sp(e, cx.st, cx.live(), [&] { return persist ? kLstmPersistClass : kLstmWaveClass; }, fl, by);
+    cx.launch("lstm state clear", pre,
+              [&] { return fc::launch_zero_fill(state, persist ? fc::lstm_persist_clear_floats(B, H) : (size_t)3 * L * B * H, cx.st); });
+    if (persist) {
+        cx.launch("lstm", pre, [&] { return fc::launch_lstm_persist(w[0], w[1], bias[1], xproj, state, y.raw, B, H, T, e->status_dev, cx.st); });
+    } else {
+        for (int s = 0; s < T + L - 1; ++s)
+            cx.launch("lstm step", pre, [&] { return fc::launch_lstm_wave(w, bias, xproj, state, state + (size_t)2 * L * B * H, y.raw, B, H, T, L, s, cx.st); });
     }
     return y;
 }
@@ -1161,18 +1221,12 @@ Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int
     const double pairs = tb.layers.empty() ? 0.0 : (e->arch.causal ? 0.5 * (double)T * (T + 1) : (double)T * T);
     const double attn_fl = 4.0 * B * pairs * C;           // q k^T and p v, every visible (query, key) pair
     cx.attn_flops += attn_fl * tb.layers.size();
-    cx.launches += 2 + (int)tb.layers.size() * 3;
+    const char* pre = tb.prefix.c_str();
     auto ln = [&](const float* add, const float* g, const float* b, float* out) {
-        if (cx.dry || cx.err) return;
-        ProfSpan sp(e, cx, e->profiling ? e->prof_class("layernorm_fm_kernel (transformer, residual add fused)") : 0, 0.0,
-                    4.0 * B * C * T * (add ? 4 : 2));
-        hipError_t er = fc::laura::launch_layernorm_fm(x, add, add ? x : nullptr, g, b, 1e-12f, 0, 1.f, out, B, C, T, cx.st);
-        if (er != hipSuccess) { cx.err = 1; g_err = std::string("transformer LayerNorm launch failed: ") + hipGetErrorString(er); }
+        cx.launch("transformer LayerNorm", pre, [] { return "layernorm_fm_kernel (transformer, residual add fused)"; }, 0.0, 4.0 * B * C * T * (add ? 4 : 2),
+                  [&] { return fc::laura::launch_layernorm_fm(x, add, add ? x : nullptr, g, b, 1e-12f, 0, 1.f, out, B, C, T, cx.st); });
     };
-    if (!cx.dry && !cx.err) {
-        hipError_t er = fc::launch_combine(src_of(in), fc::Src(), 0, 1.f, nullptr, B, C, T, T, x, sC, T, 1, cx.st);
-        if (er != hipSuccess) { cx.err = 1; g_err = std::string("combine launch failed: ") + hipGetErrorString(er); }
-    }
+    cx.launch("combine", pre, [&] { return fc::launch_combine(src_of(in), fc::Src(), 0, 1.f, nullptr, B, C, T, T, x, sC, T, 1, cx.st); });
     fc::Src sxn; sxn.ptr = xn; sxn.used = 1;
     fc::Src sctx; sctx.ptr = ctx; sctx.used = 1;
     fc::Src shb; shb.ptr = hb; shb.used = 1;
@@ -1180,21 +1234,15 @@ Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int
     for (const TfLayer& L : tb.layers) {
         ln(pending, L.n1g, L.n1b, xn);
         run_conv(e, cx, L.qkv, sxn, fc::Src(), 0, T, qkv, 3 * sC, T, 1);
-        if (!cx.dry && !cx.err) {
-            fc::SeqAttn a;
-            a.qkv = qkv; a.out = ctx; a.B = B; a.H = tb.heads; a.DK = DK; a.T = T; a.causal = e->arch.causal ? 1 : 0;
-            ProfSpan sp(e, cx, e->profiling ? e->prof_class(fc::seq_attn_kernel_name(DK)) : 0, attn_fl, 4.0 * B * 4.0 * C * T);
-            hipError_t er = fc::launch_seq_attn(a, cx.st);
-            if (er != hipSuccess) { cx.err = 1; g_err = std::string("transformer attention launch failed: ") + hipGetErrorString(er); }
-        }
+        fc::SeqAttn a;
+        a.qkv = qkv; a.out = ctx; a.B = B; a.H = tb.heads; a.DK = DK; a.T = T; a.causal = e->arch.causal ? 1 : 0;
+        cx.launch("transformer attention", pre, [&] { return fc::seq_attn_kernel_name(DK); }, attn_fl, 4.0 * B * 4.0 * C * T,
+                  [&] { return fc::launch_seq_attn(a, cx.st); });
         run_conv(e, cx, L.out, sctx, fc::Src(), 0, T, dl, sC, T, 1);
         ln(dl, L.n2g, L.n2b, xn);
         run_conv(e, cx, L.ff1, sxn, fc::Src(), 0, T, hb, (long long)ff * T, T, 1);
-        if (!cx.dry && !cx.err) {
-            ProfSpan sp(e, cx, e->profiling ? e->prof_class("act_kernel (transformer feed-forward ReLU)") : 0, 0.0, 8.0 * B * ff * T);
-            hipError_t er = fc::laura::launch_act(hb, (size_t)B * ff * T, 1, cx.st);
-            if (er != hipSuccess) { cx.err = 1; g_err = std::string("ReLU launch failed: ") + hipGetErrorString(er); }
-        }
+        cx.launch("ReLU", pre, [] { return "act_kernel (transformer feed-forward ReLU)"; }, 0.0, 8.0 * B * ff * T,
+                  [&] { return fc::laura::launch_act(hb, (size_t)B * ff * T, 1, cx.st); });
         run_conv(e, cx, L.ff2, shb, fc::Src(), 0, T, dl, sC, T, 1);
         pending = dl;
     }
@@ -1233,27 +1281,14 @@ void run_reshead(fc_engine* e, Ctx& cx, const fc_engine::ResBlock& R, fc::Src a0
     const double fl = 2.0 * cx.B * (double)T * ((double)C * C + (double)hid * C * R.block1.k);
     const double by = 4.0 * cx.B * (double)T * ((double)C * (a1.used ? 2 : 1) + C + hid);      // x read ONCE, both outputs written
     cx.conv_flops += fl; cx.conv_bytes += by;
-    cx.launches += R.shortcut.has_norm ? 3 : 1;
-    cx.conv_launches += 1;
-    if (cx.dry || cx.err) return;
-    hipError_t er;
-    {
-        int cls = 0;
-        if (e->profiling) {
-            char nm[64];
-            snprintf(nm, sizeof(nm), "reshead_kernel<%d, %d, %s>", C, R.block1.k, a1.ptr ? "true" : "false");
-            cls = e->prof_class(nm);
-        }
-        ProfSpan sp(e, cx, cls, fl, by);
-        er = fc::launch_reshead(c, cx.st);
-    }
-    if (er != hipSuccess) { cx.err = 1; g_err = "fused res-block head launch failed (" + R.shortcut.prefix + "): " + hipGetErrorString(er); return; }
-    if (R.shortcut.has_norm) {
-        er = fc::launch_gn_finalize(c.part_sc, nblk, (double)C * T, R.shortcut.gamma, R.shortcut.beta, C, e->arch.gn_eps, cx.B, sc->aff, cx.st);
-        if (er == hipSuccess)
-            er = fc::launch_gn_finalize(c.part_b1, nblk, (double)hid * T, R.block1.gamma, R.block1.beta, hid, e->arch.gn_eps, cx.B, b1->aff, cx.st);
-        if (er != hipSuccess) { cx.err = 1; g_err = std::string("gn_finalize launch failed: ") + hipGetErrorString(er); }
-    }
+    auto cls = [&] {
+        char nm[64];
+        snprintf(nm, sizeof(nm), "reshead_kernel<%d, %d, %s>", C, R.block1.k, a1.used ? "true" : "false");
+        return std::string(nm);
+    };
+    cx.conv_launch("fused res-block head", R.shortcut.prefix.c_str(), cls, fl, by, [&] { return fc::launch_reshead(c, cx.st); });
+    conv_finish(e, cx, R.shortcut, c.part_sc, nblk, (double)C * T, sc->aff);
+    conv_finish(e, cx, R.block1, c.part_b1, nblk, (double)hid * T, b1->aff);
 }
 
 // SEANetResnetBlock (seanet_encoder.py:16-61): returns the two raw branches whose GroupNorm'd sum is the output
@@ -1311,80 +1346,68 @@ Act run_decoder(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf) {
 }
 
 
-// FreqCodec: the direct kernels and the materialisation passes write the reflected / zero halo rows of their outputs themselves (round 4;
-// FC_HALO_FUSE=0: a halo_rows launch behind every producer, as before -- A / B aid)
-static bool halo_fuse_on() {
-    static const int v = fc::ab_knob("FC_HALO_FUSE", 1);
-    return v != 0;
-}
-
 // ---- STFT-domain codec: execution over frequency-major activations --------------------------------------------------------------
-struct Act2 {              // raw [B][F + 2*halo][C][T] + pending GroupNorm affine [B][C] (null = final)
-    float* buf = nullptr;
-    float* aff = nullptr;
-    int C = 0, F = 0, T = 0, halo = 0;
-    bool normed = false;
-};
 // fc_engine::halo2 (set by build_plan_2d): frequency halo rows of every 2-D activation that a kf > 1 conv may read = the largest one-sided
 // frequency padding of the net's convs (7x7: 3, 3x3: 1, strided 2 fr rows with stride fr: ceil(fr / 2))
 
+// The activated input of a 2-D conv (pending affines, second source, ELU) materialised once, frequency-major with x0's halo rows, which the
+// pass writes itself where it can (else a halo_rows launch).  pad > 0: an input of F <= pad rows; pad2d zero-extends it AFTER the activation
+// (conv.py:100-119), so its halo rows are zeros of the activated image (or reflections through that extension), not the activation of raw
+// zero rows.  Only nets with frequency ratio 1 (F = 1 at the bottleneck) get there; the recipes never do.
+Act2 materialise2d(fc_engine* e, Ctx& cx, const ConvLayer& L, const Act2& x0, const Act2* x1, int elu, int pad) {
+    const int B = cx.B, C = L.c2d;
+    Act2 m;
+    m.C = C; m.F = x0.F; m.T = x0.T; m.halo = x0.halo;
+    m.buf = cx.alloc<float>((size_t)B * (m.F + 2 * m.halo) * C * m.T);
+    const bool fuse_halo = !pad && halo_fuse_on() && m.F > m.halo;
+    cx.launch("combine2d", L.prefix.c_str(), [&] {
+        if (x0.halo < pad) return hipErrorInvalidValue;
+        return fc::launch_combine2d(x0.buf, x0.aff, x0.halo, x1 ? x1->buf : nullptr, x1 ? x1->aff : nullptr, x1 ? x1->halo : 0, elu, e->arch.elu_alpha,
+                                    B, m.F, C, m.T, m.buf, m.halo, cx.st, fuse_halo ? 1 : 0);
+    });
+    if (pad) cx.launch("halo rows", L.prefix.c_str(), [&] { return fc::launch_halo_rows_short(m.buf, B, m.F, m.halo, pad, C, m.T, cx.st); });
+    else if (!fuse_halo) cx.launch("halo rows", L.prefix.c_str(), [&] { return fc::launch_halo_rows(m.buf, B, m.F, m.halo, C, m.T, 0, cx.st); });
+    return m;
+}
+
 // SConv2d.forward (conv.py:342-381) as ONE launch of the 1-D implicit-GEMM kernel over B * Fo virtual utterances
-Act2 run_conv2d(fc_engine* e, Ctx& cx, const ConvLayer& L, Act2 x0, const Act2* x1p, int elu, int out_halo) {
+Act2 run_conv2d(fc_engine* e, Ctx& cx, const ConvLayer& L, Act2 x0, const Act2* x1, int elu, int out_halo) {
     const int B = cx.B, C = L.c2d, kf = L.kf, sf = L.sf;
-    Act2 x1 = x1p ? *x1p : Act2();
-    bool dual = x1p != nullptr;
     const int tot_f = (kf - 1) - (sf - 1), f_after = tot_f / 2, f_before = tot_f - f_after;     // no extra padding on the frequency axis
     const int Fo = (x0.F + tot_f - kf) / sf + 1;
     const ConvGeom g = conv_geom(L, x0.T);
     const int fpad = std::max(f_before, f_after);
-    if (x0.F <= fpad) {
-        // pad2d zero-extends an input of F <= pad rows AFTER the activation (conv.py:100-119): its halo rows are zeros of the activated image (or
-        // reflections through that extension), not the activation of raw zero rows.  Materialise the activated input with those rows.  Only
-        // nets with frequency ratio 1 (F = 1 at the bottleneck) get here; the recipes never do.
-        Act2 m;
-        m.C = C; m.F = x0.F; m.T = x0.T; m.halo = x0.halo;
-        m.buf = cx.alloc<float>((size_t)B * (m.F + 2 * m.halo) * C * m.T);
-        cx.launches += 2;
-        if (!cx.dry && !cx.err) {
-            hipError_t er = x0.halo < fpad ? hipErrorInvalidValue
-                                           : fc::launch_combine2d(x0.buf, x0.aff, x0.halo, dual ? x1.buf : nullptr, dual ? x1.aff : nullptr, x1.halo,
-                                                                  elu, e->arch.elu_alpha, B, m.F, C, m.T, m.buf, m.halo, cx.st, 0);
-            if (er == hipSuccess) er = fc::launch_halo_rows_short(m.buf, B, m.F, m.halo, fpad, C, m.T, cx.st);
-            if (er != hipSuccess) { cx.err = 1; g_err = "short-input materialisation failed (" + L.prefix + "): " + hipGetErrorString(er); }
-        }
-        x0 = m; x1 = Act2(); elu = 0; dual = false;
-    }
-    // layers with several M tiles: materialise the activated input once (as run_conv does), frequency-major with the same halo
-    if (L.w_group) {     // grouped conv with 2 / 4 channels per group: direct FMA kernel, prologue fused, no GEMM
-        // the strided 8-row layers read every input sample from 2 output rows x ~1.25 lanes with a two-source prologue (11 VALU per read):
-        // activate once instead (FC_GCONV_MAT=0: in-kernel prologue)
+    if (x0.F <= fpad) { x0 = materialise2d(e, cx, L, x0, x1, elu, fpad); x1 = nullptr; elu = 0; }
+    bool mat;
+    if (L.w_group) {
+        // the grouped direct kernel's strided 8-row layers read every input sample from 2 output rows x ~1.25 lanes with a two-source
+        // prologue (11 VALU per read): activate once instead (FC_GCONV_MAT=0: in-kernel prologue)
         static const int gmat = fc::ab_knob("FC_GCONV_MAT", 1);
-        if (gmat && kf >= 4 && dual) {
-            Act2 m;
-            m.C = C; m.F = x0.F; m.T = x0.T; m.halo = x0.halo;
-            m.buf = cx.alloc<float>((size_t)B * (m.F + 2 * m.halo) * C * m.T);
-            const bool fuse_halo = halo_fuse_on() && m.F > m.halo;      // the pass writes its own reflected halo rows
-            cx.launches += fuse_halo ? 1 : 2;
-            if (!cx.dry && !cx.err) {
-                hipError_t er = fc::launch_combine2d(x0.buf, x0.aff, x0.halo, x1.buf, x1.aff, x1.halo, elu, e->arch.elu_alpha, B, m.F, C, m.T, m.buf,
-                                                     m.halo, cx.st, fuse_halo ? 1 : 0);
-                if (er == hipSuccess && !fuse_halo) er = fc::launch_halo_rows(m.buf, B, m.F, m.halo, C, m.T, 0, cx.st);
-                if (er != hipSuccess) { cx.err = 1; g_err = std::string("combine2d launch failed: ") + hipGetErrorString(er); }
-            }
-            x0 = m; x1 = Act2(); elu = 0; dual = false;
-        }
-        Act2 o;
-        o.C = L.cout; o.F = Fo; o.T = g.Tout; o.halo = out_halo;
-        o.buf = cx.alloc<float>((size_t)B * (Fo + 2 * out_halo) * L.cout * g.Tout);
-        if (!cx.dry && (x0.halo < f_before || x0.halo < f_after || (x1.buf && x1.halo != x0.halo))) {
-            cx.err = 1; g_err = "internal: frequency halo too small for " + L.prefix; return o;
-        }
-        const long long rowsz = (long long)C * x0.T, orow = (long long)L.cout * g.Tout;
+        mat = gmat && kf >= 4 && x1;
+    } else {
+        // layers with several M tiles: materialise the activated input once (as run_conv does); the few-output FMA kernel re-stages every
+        // input row for each of the kf output rows that read it: activate once instead
+        static const int few_mat = fc::ab_knob("FC_FEWOUT_MAT", 1);
+        const bool few_out = few_mat && L.cout <= 4 && L.stride == 1 && sf == 1 && (L.k == 3 || L.k == 5 || L.k == 7) && kf > 1;   // = pack_conv2d's w_plain rule
+        mat = (L.Mpad / L.BM >= 3 || few_out || L.force_plain) && (x0.normed || x1 || elu);
+    }
+    if (mat) { x0 = materialise2d(e, cx, L, x0, x1, elu, 0); x1 = nullptr; elu = 0; }
+    Act2 o;
+    o.C = L.cout; o.F = Fo; o.T = g.Tout; o.halo = out_halo;
+    o.buf = cx.alloc<float>((size_t)B * (Fo + 2 * out_halo) * L.cout * g.Tout);
+    if (!cx.dry && (x0.halo < f_before || x0.halo < f_after || (x1 && x1->halo != x0.halo))) {
+        cx.fail("internal: frequency halo too small for " + L.prefix);
+        return o;
+    }
+    const long long rowsz = (long long)C * x0.T, orow = (long long)L.cout * g.Tout;
+    const double by = 4.0 * B * ((double)C * x0.F * x0.T * (x1 ? 2 : 1) + (double)L.cout * Fo * g.Tout);
+    o.normed = L.has_norm;                  // weight_norm nets: no statistics, no affine
+    if (L.w_group) {     // grouped conv with 2 / 4 channels per group: direct FMA kernel, prologue fused, no GEMM
         fc::GConvLaunch c;
-        c.src0 = cx.dry ? nullptr : x0.buf + (long long)(x0.halo - f_before) * rowsz; c.aff0 = x0.aff;
-        if (dual) { c.src1 = cx.dry ? nullptr : x1.buf + (long long)(x1.halo - f_before) * rowsz; c.aff1 = x1.aff; }
+        c.src0 = at(x0.buf, (x0.halo - f_before) * rowsz); c.aff0 = x0.aff;
+        if (x1) { c.src1 = at(x1->buf, (x1->halo - f_before) * rowsz); c.aff1 = x1->aff; }
         c.w = L.w_group; c.bias = L.bias;
-        c.out = cx.dry ? nullptr : o.buf + (long long)out_halo * orow;
+        c.out = at(o.buf, out_halo * orow);
         c.B = B; c.C = C; c.M = L.cout; c.G = L.groups; c.Tin = x0.T; c.Tout = g.Tout; c.Fo = Fo; c.kf = kf; c.kt = L.k; c.sf = sf; c.st = L.stride;
         c.padL = g.padL; c.padR = g.padR; c.elu = elu; c.alpha = e->arch.elu_alpha;
         c.guard_lo = cx.base; c.guard_hi = cx.base ? cx.base + cx.cap : nullptr;      // both sources are buffers of THIS workspace (Ctx::alloc)
@@ -1393,99 +1416,34 @@ Act2 run_conv2d(fc_engine* e, Ctx& cx, const ConvLayer& L, Act2 x0, const Act2* 
         const bool fuse_halo = halo_fuse_on() && fc::gconv2d_fuses_halo(kf, L.k, L.stride, Fo, out_halo);
         c.out_halo = fuse_halo ? out_halo : 0;
         const int nblk = fc::gconv2d_nblk(g.Tout, Fo, L.groups, kf);
-        c.partials = L.has_norm ? cx.alloc<double>((size_t)B * nblk * 2) : nullptr;       // weight_norm nets: no statistics, no affine
+        c.partials = L.has_norm ? cx.alloc<double>((size_t)B * nblk * 2) : nullptr;
         o.aff = L.has_norm ? cx.alloc<float>((size_t)B * L.cout * 2) : nullptr;
-        o.normed = L.has_norm;
         const double fl = 2.0 * B * Fo * (double)L.cout * (C / L.groups) * kf * L.k * g.Tout;
-        const double by = 4.0 * B * ((double)C * x0.F * x0.T * (dual ? 2 : 1) + (double)L.cout * Fo * g.Tout);
         cx.conv_flops += fl; cx.conv_bytes += by;
-        cx.launches += (out_halo && !fuse_halo) ? 3 : 2; cx.conv_launches += 1;
-        if (cx.dry || cx.err) return o;
-        hipError_t er;
-        {
-            int cls = 0;
-            if (e->profiling) {
-                char nm[64];
-                snprintf(nm, sizeof(nm), "gconv2d_kernel<%d, %d, %d, %d, %d, %s>", C / L.groups, L.cout / L.groups, kf, L.k, L.stride, dual ? "true" : "false");
-                cls = e->prof_class(nm);
-            }
-            ProfSpan sp(e, cx, cls, fl, by);
-            er = fc::launch_gconv2d(c, cx.st);
-        }
-        if (er == hipSuccess && L.has_norm)
-            er = fc::launch_gn_finalize(c.partials, nblk, (double)L.cout * Fo * g.count_T, L.gamma, L.beta, L.cout, e->arch.gn_eps, B, o.aff, cx.st);
-        if (er == hipSuccess && out_halo && !fuse_halo) er = fc::launch_halo_rows(o.buf, B, Fo, out_halo, L.cout, g.Tout, 0, cx.st);
-        if (er != hipSuccess) { cx.err = 1; g_err = "grouped 2-D conv launch failed (" + L.prefix + "): " + hipGetErrorString(er); }
+        auto cls = [&] {
+            char nm[64];
+            snprintf(nm, sizeof(nm), "gconv2d_kernel<%d, %d, %d, %d, %d, %s>", C / L.groups, L.cout / L.groups, kf, L.k, L.stride, x1 ? "true" : "false");
+            return std::string(nm);
+        };
+        cx.conv_launch("grouped 2-D conv", L.prefix.c_str(), cls, fl, by, [&] { return fc::launch_gconv2d(c, cx.st); });
+        conv_finish(e, cx, L, c.partials, nblk, (double)L.cout * Fo * g.count_T, o.aff, out_halo && !fuse_halo ? &o : nullptr);
         return o;
     }
-    // the few-output FMA kernel re-stages every input row for each of the kf output rows that read it: activate once instead
-    static const int few_mat = fc::ab_knob("FC_FEWOUT_MAT", 1);
-    const bool few_out = few_mat && L.cout <= 4 && L.stride == 1 && sf == 1 && (L.k == 3 || L.k == 5 || L.k == 7) && kf > 1;   // = pack_conv2d's w_plain rule
-    if ((L.Mpad / L.BM >= 3 || few_out || L.force_plain) && (x0.normed || dual || elu)) {
-        Act2 m;
-        m.C = C; m.F = x0.F; m.T = x0.T; m.halo = x0.halo;
-        m.buf = cx.alloc<float>((size_t)B * (m.F + 2 * m.halo) * C * m.T);
-        const bool fuse_halo = halo_fuse_on() && m.F > m.halo;
-        cx.launches += fuse_halo ? 1 : 2;
-        if (!cx.dry && !cx.err) {
-            hipError_t er = fc::launch_combine2d(x0.buf, x0.aff, x0.halo, dual ? x1.buf : nullptr, dual ? x1.aff : nullptr, x1.halo, elu,
-                                                 e->arch.elu_alpha, B, m.F, C, m.T, m.buf, m.halo, cx.st, fuse_halo ? 1 : 0);
-            if (er == hipSuccess && !fuse_halo) er = fc::launch_halo_rows(m.buf, B, m.F, m.halo, C, m.T, 0, cx.st);
-            if (er != hipSuccess) { cx.err = 1; g_err = std::string("combine2d launch failed: ") + hipGetErrorString(er); }
-        }
-        x0 = m; x1 = Act2(); elu = 0; dual = false;
-    }
-    const bool dual_eff = dual;
-    Act2 o;
-    o.C = L.cout; o.F = Fo; o.T = g.Tout; o.halo = out_halo;
-    o.buf = cx.alloc<float>((size_t)B * (Fo + 2 * out_halo) * L.cout * g.Tout);
-    if (!cx.dry && (x0.halo < f_before || x0.halo < f_after || (x1.buf && x1.halo != x0.halo))) {
-        cx.err = 1; g_err = "internal: frequency halo too small for " + L.prefix; return o;
-    }
-    fc::ConvLaunch c;
-    const long long rowsz = (long long)C * x0.T;
-    c.s0.ptr = cx.dry ? nullptr : x0.buf + (long long)(x0.halo - f_before) * rowsz;
-    c.s0.aff = x0.aff; c.s0.used = x0.normed ? 3 : 1;
-    if (dual_eff) { c.s1.ptr = cx.dry ? nullptr : x1.buf + (long long)(x1.halo - f_before) * rowsz; c.s1.aff = x1.aff; c.s1.used = x1.normed ? 3 : 1; }
+    fc::ConvLaunch c = conv_launch_of(L, B * Fo, x0.T, g);
+    c.s0.ptr = at(x0.buf, (x0.halo - f_before) * rowsz); c.s0.aff = x0.aff; c.s0.used = x0.normed ? 3 : 1;
+    if (x1) { c.s1.ptr = at(x1->buf, (x1->halo - f_before) * rowsz); c.s1.aff = x1->aff; c.s1.used = x1->normed ? 3 : 1; }
     c.elu = elu; c.alpha = e->arch.elu_alpha;
-    c.wt = L.wt; c.bias = L.bias; c.koff = L.koff;
-    c.B = B * Fo; c.Cin = L.cin; c.Tin = x0.T; c.M = L.M; c.Tout = g.Tout;
-    c.k = L.gk; c.stride = L.gstride; c.dil = L.dil; c.padL = g.padL; c.padR = g.padR;
-    c.BM = L.BM; c.BN = L.BN; c.CC = L.CC; c.nchunk = L.nchunk; c.row = L.row ? 1 : 0;
-    c.Fo = Fo; c.affC = C; c.w_plain = L.w_plain;
+    c.Tout = g.Tout; c.Fo = Fo; c.affC = C;
     c.in_sB0 = (long long)(x0.F + 2 * x0.halo) * rowsz; c.in_sB1 = (long long)sf * rowsz;
-    const long long orow = (long long)L.cout * g.Tout;
-    c.out = cx.dry ? nullptr : o.buf + (long long)out_halo * orow;
+    c.out = at(o.buf, out_halo * orow);
     c.out_sB = (long long)(Fo + 2 * out_halo) * orow; c.out_sF = orow; c.out_sM = g.Tout; c.out_sT = 1;
     const int nblk = fc::conv_nblk(c);
     c.partials = L.has_norm ? cx.alloc<double>((size_t)B * Fo * nblk * 2) : nullptr;
     o.aff = L.has_norm ? cx.alloc<float>((size_t)B * L.cout * 2) : nullptr;
-    o.normed = L.has_norm;
     const double fl = 2.0 * B * Fo * (double)L.M * L.cin * L.gk * g.Tout;
-    const double by = 4.0 * B * ((double)C * x0.F * x0.T * (dual_eff ? 2 : 1) + (double)L.cout * Fo * g.Tout);
     cx.conv_flops += fl; cx.conv_bytes += by;
-    cx.launches += out_halo ? 3 : 2; cx.conv_launches += 1;
-    if (cx.dry || cx.err) return o;
-    hipError_t er;
-    {
-        int cls = 0;
-        if (e->profiling) {
-            int mode = 0, nu = 0, row = 0;
-            fc::conv_variant(c, &mode, &nu, &row);
-            char nm[80];
-            snprintf(nm, sizeof(nm), "conv_mfma_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", L.BM, L.BN, L.BM >= 128 ? 2 : 1, L.BM >= 128 ? 2 : 4, mode, nu,
-                     (row & 1) ? "true" : "false", (row & 2) ? "true" : "false");
-            if (fc::conv_cout1_ok(c))
-                fc::conv_fewout_name(c, nm, sizeof(nm));
-            cls = e->prof_class(nm);
-        }
-        ProfSpan sp(e, cx, cls, fl, by);
-        er = fc::launch_conv(c, cx.st);
-    }
-    if (er == hipSuccess && L.has_norm)
-        er = fc::launch_gn_finalize(c.partials, nblk * Fo, (double)L.cout * Fo * g.count_T, L.gamma, L.beta, L.cout, e->arch.gn_eps, B, o.aff, cx.st);
-    if (er == hipSuccess && out_halo) er = fc::launch_halo_rows(o.buf, B, Fo, out_halo, L.cout, g.Tout, 0, cx.st);
-    if (er != hipSuccess) { cx.err = 1; g_err = "2-D conv launch failed (" + L.prefix + "): " + hipGetErrorString(er); }
+    cx.conv_launch("2-D conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
+    conv_finish(e, cx, L, c.partials, nblk * Fo, (double)L.cout * Fo * g.count_T, o.aff, out_halo ? &o : nullptr);
     return o;
 }
 
@@ -1530,73 +1488,44 @@ Act2 run_convtr2d(fc_engine* e, Ctx& cx, const ConvLayer& S, const std::vector<C
     const double fl = 2.0 * B * (Fin + 1) * (double)phases[0].M * 2 * C * 2 * (T + 1) * sf;
     const double by = 4.0 * B * ((double)C * Fin * T * (x1 ? 2 : 1) + (double)cout * Fout * g.Tout);
     cx.conv_flops += fl; cx.conv_bytes += by;
-    cx.launches += sf + 3 + (out_halo ? 1 : 0) - (halo_fuse_on() ? 1 : 0) - ((phases[0].w_group && halo_fuse_on() && out_halo && Fout > out_halo) ? 1 : 0);
-    cx.conv_launches += sf;
-    if (cx.dry || cx.err) return o;
-    hipError_t er = fc::launch_combine2d(x0.buf, x0.aff, x0.halo, x1 ? x1->buf : nullptr, x1 ? x1->aff : nullptr, x1 ? x1->halo : 0, 1,
-                                         e->arch.elu_alpha, B, Fin, C, T, z.buf, 1, cx.st, halo_fuse_on() ? 2 : 0);      // 2: its zero rows too
-    if (er == hipSuccess && !halo_fuse_on()) er = fc::launch_halo_rows(z.buf, B, Fin, 1, C, T, 1, cx.st);
+    const char* pre = S.prefix.c_str();
+    const double gn_count = (double)cout * (Fin + 1) * sf * g.count_T;
+    cx.launch("combine2d", pre, [&] {
+        return fc::launch_combine2d(x0.buf, x0.aff, x0.halo, x1 ? x1->buf : nullptr, x1 ? x1->aff : nullptr, x1 ? x1->halo : 0, 1, e->arch.elu_alpha,
+                                    B, Fin, C, T, z.buf, 1, cx.st, halo_fuse_on() ? 2 : 0);      // 2: its zero rows too
+    });
+    if (!halo_fuse_on()) cx.launch("halo rows", pre, [&] { return fc::launch_halo_rows(z.buf, B, Fin, 1, C, T, 1, cx.st); });
     if (phases[0].w_group) {          // grouped (2 in / 1 out channel per group): one direct launch over the untrimmed output
-        double* gpart = partials;
-        if (er == hipSuccess) {
-            int cls = 0;
-            if (e->profiling) {
-                char nm[64];
-                snprintf(nm, sizeof(nm), "gconvtr2d_kernel<%d>", st);
-                cls = e->prof_class(nm);
-            }
-            ProfSpan sp(e, cx, cls, 2.0 * B * (double)cout * 8 * (Fin + 1) * sf * (T + 1) * st, by);
-            er = fc::launch_gconvtr2d(z.buf, phases[0].w_group, phases[0].w_plain, o.buf + (long long)out_halo * orow, gpart, B, C, cout, Fin, T, sf, st,
-                                      f_l, Fout, t_trimL, g.Tout, (long long)(Fout + 2 * out_halo) * orow, cx.st,
-                                      (halo_fuse_on() && Fout > out_halo) ? out_halo : 0);
-        }
-        if (er == hipSuccess && has_norm)
-            er = fc::launch_gn_finalize(gpart, gnblk, (double)cout * (Fin + 1) * sf * g.count_T, phases[0].gamma, phases[0].beta, cout, e->arch.gn_eps,
-                                        B, o.aff, cx.st);
-        if (er == hipSuccess && out_halo && !(halo_fuse_on() && Fout > out_halo)) er = fc::launch_halo_rows(o.buf, B, Fout, out_halo, cout, g.Tout, 0, cx.st);
-        if (er != hipSuccess) { cx.err = 1; g_err = "grouped 2-D transposed conv launch failed (" + S.prefix + "): " + hipGetErrorString(er); }
+        const bool fuse_halo = halo_fuse_on() && Fout > out_halo;
+        cx.conv_launch("grouped 2-D transposed conv", pre, [&] { return "gconvtr2d_kernel<" + std::to_string(st) + ">"; },
+                       2.0 * B * (double)cout * 8 * (Fin + 1) * sf * (T + 1) * st, by, [&] {
+                           return fc::launch_gconvtr2d(z.buf, phases[0].w_group, phases[0].w_plain, o.buf + (long long)out_halo * orow, partials, B, C, cout,
+                                                       Fin, T, sf, st, f_l, Fout, t_trimL, g.Tout, (long long)(Fout + 2 * out_halo) * orow, cx.st,
+                                                       fuse_halo ? out_halo : 0);
+                       });
+        conv_finish(e, cx, phases[0], partials, gnblk, gn_count, o.aff, out_halo && !fuse_halo ? &o : nullptr);
         return o;
     }
-    for (int p = 0; p < sf && er == hipSuccess; ++p) {
+    for (int p = 0; p < sf; ++p) {
         const ConvLayer& L = phases[p];
-        fc::ConvLaunch c;
+        fc::ConvLaunch c = conv_launch_of(L, B * (Fin + 1), T, g);
         c.s0.ptr = z.buf; c.s0.used = 1;
-        c.wt = L.wt; c.bias = L.bias; c.koff = L.koff;
-        c.B = B * (Fin + 1); c.Cin = L.cin; c.Tin = T; c.M = L.M;
-        c.k = L.gk; c.stride = L.gstride; c.dil = 1; c.padL = g.padL; c.padR = g.padR; c.pad_zero = 1;
-        c.BM = L.BM; c.BN = L.BN; c.CC = L.CC; c.nchunk = L.nchunk; c.row = L.row ? 1 : 0;
+        c.pad_zero = 1;
         c.Tout = T + 1; c.up_r = st; c.trimL = t_trimL; c.Tfinal = g.Tout;
         c.Fo = Fin + 1; c.affC = C;
         c.in_sB0 = (long long)(Fin + 2) * C * T; c.in_sB1 = (long long)C * T;
-        c.out = o.buf + ((long long)out_halo + p - f_l) * orow;      // rows outside [0, Fout) are never stored (store range below)
+        c.out = at(o.buf, (out_halo + p - f_l) * orow);                  // rows outside [0, Fout) are never stored (store range below)
         c.out_sB = (long long)(Fout + 2 * out_halo) * orow; c.out_sF = (long long)sf * orow; c.out_sM = g.Tout; c.out_sT = 1;
         int lo = f_l - p;                                            // q * sf + p - f_l >= 0
         lo = lo <= 0 ? 0 : (lo + sf - 1) / sf;
         int hi = (Fout - 1 + f_l - p) >= 0 ? (Fout - 1 + f_l - p) / sf + 1 : 0;   // q * sf + p - f_l <= Fout - 1
         if (hi > Fin + 1) hi = Fin + 1;
         c.store_lo = lo; c.store_hi = hi;
-        c.partials = has_norm ? partials + (long long)p * part_row * 2 : nullptr;
+        c.partials = has_norm ? at(partials, p * part_row * 2) : nullptr;
         c.part_sB0 = (long long)sf * part_row;
-        int cls = 0;
-        if (e->profiling) {
-            int mode = 0, nu = 0, row = 0;
-            fc::conv_variant(c, &mode, &nu, &row);
-            char nm[80];
-            snprintf(nm, sizeof(nm), "conv_mfma_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", L.BM, L.BN, L.BM >= 128 ? 2 : 1, L.BM >= 128 ? 2 : 4, mode, nu,
-                     (row & 1) ? "true" : "false", (row & 2) ? "true" : "false");
-            if (fc::conv_cout1_ok(c))
-                fc::conv_fewout_name(c, nm, sizeof(nm));
-            cls = e->prof_class(nm);
-        }
-        ProfSpan sp(e, cx, cls, fl / sf, by / sf);
-        er = fc::launch_conv(c, cx.st);
+        cx.conv_launch("2-D transposed conv", pre, [&] { return conv_class(c); }, fl / sf, by / sf, [&] { return fc::launch_conv(c, cx.st); });
     }
-    const ConvLayer& L0 = phases[0];
-    if (er == hipSuccess && has_norm)
-        er = fc::launch_gn_finalize(partials, (int)(sf * part_row), (double)cout * (Fin + 1) * sf * g.count_T, L0.gamma, L0.beta, cout, e->arch.gn_eps,
-                                    B, o.aff, cx.st);
-    if (er == hipSuccess && out_halo) er = fc::launch_halo_rows(o.buf, B, Fout, out_halo, cout, g.Tout, 0, cx.st);
-    if (er != hipSuccess) { cx.err = 1; g_err = "2-D transposed conv launch failed (" + S.prefix + "): " + hipGetErrorString(er); }
+    conv_finish(e, cx, phases[0], partials, (int)(sf * part_row), gn_count, o.aff, out_halo ? &o : nullptr);
     return o;
 }
 
@@ -1611,30 +1540,21 @@ Act run_encoder_2d(fc_engine* e, Ctx& cx, const float* wav, int T, const float* 
     const fc_arch& a = e->arch;
     const int B = cx.B, hop = a.stft_hop, F = a.n_fft / 2 + 1, Tp = stft_frames(e, T), taps = ceil_div_i(a.n_fft, hop), Mp = Tp + taps - 1;
     float* xp = cx.alloc<float>((size_t)B * hop * Mp);
-    cx.launches += 3;
-    if (!cx.dry && !cx.err) {
-        if (T <= a.n_fft / 2) { cx.err = 1; g_err = "utterance shorter than n_fft/2 + 1 samples (torch.stft reflect padding needs more)"; }
-        else if (fc::launch_polyphase_in(wav, a.audio_normalize ? scale : nullptr, B, T, hop, a.n_fft, Mp, xp, cx.st) != hipSuccess) {
-            cx.err = 1; g_err = "polyphase launch failed";
-        }
-    }
+    if (!cx.dry && T <= a.n_fft / 2) cx.fail("utterance shorter than n_fft/2 + 1 samples (torch.stft reflect padding needs more)");
+    cx.launch("polyphase", "", [&] { return fc::launch_polyphase_in(wav, a.audio_normalize ? scale : nullptr, B, T, hop, a.n_fft, Mp, xp, cx.st); });
     fc::Src sx; sx.ptr = xp; sx.used = 1;
     Act spec = run_conv(e, cx, e->stft, sx, fc::Src(), 0, Mp);                     // [B][2F][Tp]: re rows, then im rows
     Act2 feats;
     feats.C = a.input_channels; feats.F = F; feats.T = Tp; feats.halo = e->halo2;
     feats.buf = cx.alloc<float>((size_t)B * (F + 2 * e->halo2) * feats.C * Tp);
-    if (!cx.dry && !cx.err) {
-        hipError_t er = fc::launch_stft_feats(spec.raw, B, F, Tp, (long long)2 * F * Tp, e->halo2, feats.C, feats.buf, cx.st);
-        // test hooks (fc_debug_freq_features): hand the features out / take them from the caller, in the reference's [B][C][F][Tp]
-        if (er == hipSuccess && g_feat_hook.buf && g_feat_hook.mode != 0) {
-            const size_t need = (size_t)B * feats.C * F * Tp * sizeof(float);
-            if (need > g_feat_hook.cap) { cx.err = 1; g_err = "fc_debug_freq_features: buffer too small"; }
-            else er = fc::launch_feats_relayout(feats.buf, g_feat_hook.buf, B, feats.C, F, Tp, e->halo2, g_feat_hook.mode == 1, cx.st);
-            g_feat_hook.mode = 0;            // one shot
-        }
-        if (er == hipSuccess) er = fc::launch_halo_rows(feats.buf, B, F, e->halo2, feats.C, Tp, 0, cx.st);
-        if (er != hipSuccess) { cx.err = 1; g_err = std::string("stft feature launch failed: ") + hipGetErrorString(er); }
+    cx.launch("stft feature", "", [&] { return fc::launch_stft_feats(spec.raw, B, F, Tp, (long long)2 * F * Tp, e->halo2, feats.C, feats.buf, cx.st); });
+    // test hooks (fc_debug_freq_features): hand the features out / take them from the caller, in the reference's [B][C][F][Tp]
+    if (g_feat_hook.mode != 0) {
+        if (!cx.dry && (size_t)B * feats.C * F * Tp * sizeof(float) > g_feat_hook.cap) cx.fail("fc_debug_freq_features: buffer too small");
+        cx.launch("feature hook", "", [&] { return fc::launch_feats_relayout(feats.buf, g_feat_hook.buf, B, feats.C, F, Tp, e->halo2, g_feat_hook.mode == 1, cx.st); });
+        if (!cx.dry) g_feat_hook.mode = 0;            // one shot
     }
+    cx.launch("halo rows", "", [&] { return fc::launch_halo_rows(feats.buf, B, F, e->halo2, feats.C, Tp, 0, cx.st); });
     Act2 x = run_conv2d(e, cx, e->enc2_first, feats, nullptr, 0, e->halo2);
     for (size_t si = 0; si < e->enc_stages.size(); ++si) {
         auto& S = e->enc_stages[si];
@@ -1642,7 +1562,7 @@ Act run_encoder_2d(fc_engine* e, Ctx& cx, const float* wav, int T, const float* 
         run_resblocks2d(e, cx, S, x, nullptr, &sc, &b3);
         x = run_conv2d(e, cx, S.resample, sc, &b3, 1, si + 1 == e->enc_stages.size() ? 0 : e->halo2);
     }
-    if (!cx.dry && !cx.err && x.F != 1) { cx.err = 1; g_err = "the 2-D encoder must reduce the frequency axis to one bin (n_fft / ratios mismatch)"; }
+    if (!cx.dry && x.F != 1) cx.fail("the 2-D encoder must reduce the frequency axis to one bin (n_fft / ratios mismatch)");
     Act x1;                                                                        // ReshapeModule: [B][1][C][T] is [B][C][T]
     x1.raw = x.buf; x1.aff = x.aff; x1.C = x.C; x1.T = x.T; x1.normed = x.normed;
     if (has_seq(e->enc_lstm, e->enc_tf)) {
@@ -1678,20 +1598,13 @@ void run_decoder_2d(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const flo
     Act2 last = run_conv2d(e, cx, e->dec2_last, a0, &a1, 1, 0);                     // [B][F][3][Tp2] raw + GroupNorm(1, 3) affine
     const int Tp2 = last.T, Mp2 = Tp2 + taps - 1;
     float* spec = cx.alloc<float>((size_t)B * 2 * F * Tp2);
-    cx.launches += 2;
-    if (!cx.dry && !cx.err) {
-        if (last.F != F) { cx.err = 1; g_err = "internal: decoder frequency rows != n_fft / 2 + 1"; }
-        else if (out_len > hop * (Tp2 - 1)) { cx.err = 1; g_err = "out_len exceeds the inverse STFT's length stft_hop * (frames - 1)"; }
-        else if (fc::launch_spec_from_dec(last.buf, last.aff, B, F, Tp2, 0, a.input_channels, spec, cx.st) != hipSuccess) { cx.err = 1; g_err = "spectrum launch failed"; }
-    }
+    if (!cx.dry && last.F != F) cx.fail("internal: decoder frequency rows != n_fft / 2 + 1");
+    if (!cx.dry && out_len > hop * (Tp2 - 1)) cx.fail("out_len exceeds the inverse STFT's length stft_hop * (frames - 1)");
+    cx.launch("spectrum", "", [&] { return fc::launch_spec_from_dec(last.buf, last.aff, B, F, Tp2, 0, a.input_channels, spec, cx.st); });
     fc::Src ss; ss.ptr = spec; ss.used = 1;
     Act yp = run_conv(e, cx, e->istft, ss, fc::Src(), 0, Tp2);                      // [B][hop][Mp2]
-    if (!cx.dry && !cx.err) {
-        if (yp.T != Mp2) { cx.err = 1; g_err = "internal: inverse-STFT GEMM length"; }
-        else if (fc::launch_istft_finish(yp.raw, e->win2, B, hop, a.n_fft, Mp2, Tp2, scale, out_len, wav, cx.st) != hipSuccess) {
-            cx.err = 1; g_err = "istft finish launch failed";
-        }
-    }
+    if (!cx.dry && yp.T != Mp2) cx.fail("internal: inverse-STFT GEMM length");
+    cx.launch("istft finish", "", [&] { return fc::launch_istft_finish(yp.raw, e->win2, B, hop, a.n_fft, Mp2, Tp2, scale, out_len, wav, cx.st); });
 }
 
 int total_hop(const fc_engine* e) {
@@ -1720,15 +1633,14 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
     float* sc = nullptr;
     if (e->arch.audio_normalize) {
         sc = scale ? scale : cx.alloc<float>(B);
-        cx.launches++;
-        if (!cx.dry && !cx.err) {
-            if (fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st) != hipSuccess) return fail("volume kernel launch failed");
-        }
+        cx.launch("volume", "", [&] { return fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st); });
     }
     Act last = e->arch.model_type == 1 ? run_encoder_2d(e, cx, wav, T, sc) : run_encoder(e, cx, wav, T, sc);
     const int Dc = e->cdim();
     const bool ranged = e->arch.codec_range > 0.f;
-    float* emb = enc_out ? enc_out : ((e->q_proj || ranged) && !enc_out ? nullptr : cx.alloc<float>((size_t)B * Tf * D));
+    // encoder output rows [B][Tf][D] (seanet_encoder.py:175) with the last GroupNorm applied: the quantiser's input, or asked for
+    const bool emb_rows = enc_out || !(e->q_proj || ranged);
+    float* emb = enc_out ? enc_out : emb_rows ? cx.alloc<float>((size_t)B * Tf * D) : nullptr;
     // quantiser input rows [B*Tf][Dc]: the encoder output itself, or input_proj(...) / tanh(...) * range of it (costume_quantizer.py:84-87)
     Act pj;
     if (e->q_proj) pj = run_conv(e, cx, e->q_in, src_of(last), fc::Src(), 0, Tf);
@@ -1738,39 +1650,30 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
     // quantizer_conf.q0_ds_ratio > 1 (ddp_core_vq.py:396-404): stage 0 of frame t quantises frame q0_source_frame(t, Tf) (kernels.h)
     const bool q0 = e->arch.q0_ds_ratio > 1;
     int* q0map = q0 ? cx.alloc<int>((size_t)B * Tf) : nullptr;
-    cx.launches += 2 + (ranged ? 1 : 0) + (q0 ? 1 : 0);
-    cx.rvq_flops += 2.0 * B * Tf * (double)n_q * e->arch.codebook_size * Dc;
-    if (!cx.dry && !cx.err) {
-        if (last.T != Tf) return fail("internal: frame count mismatch");
-        // encoder output permuted to [B,Tf,D] (seanet_encoder.py:175) with the last GroupNorm applied
-        if (emb && fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, emb, (long long)Tf * D, 1, D, cx.st) != hipSuccess)
-            return fail("combine launch failed");
-        if (e->q_proj) {
-            if (fc::launch_combine(src_of(pj), fc::Src(), 0, 1.f, nullptr, B, Dc, Tf, Tf, xq, (long long)Tf * Dc, 1, Dc, cx.st) != hipSuccess)
-                return fail("combine launch failed");
-        } else if (ranged) {
-            if (fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, xq, (long long)Tf * D, 1, D, cx.st) != hipSuccess)
-                return fail("combine launch failed");
-        }
-        if (ranged && fc::launch_tanh_range(xq, (size_t)B * Tf * Dc, e->arch.codec_range, cx.st) != hipSuccess) return fail("tanh launch failed");
-        if (q0) {
-            if (Tf < 2) return fail("quantizer_conf.q0_ds_ratio > 1 needs at least 2 frames (the reference's F.interpolate(size=[Tf // 2]) raises on 0)");
-            if (fc::launch_q0_map(q0map, B, Tf, cx.st) != hipSuccess) return fail("q0 map launch failed");
-        }
-        ProfSpan sp(e, cx, e->profiling ? e->prof_class(kRvqClass) : 0, 2.0 * B * Tf * (double)n_q * e->arch.codebook_size * Dc, 0.0);
-        if (fc::launch_rvq_encode(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, e->cb_frag, e->enorm, codes, quant_c, qbdt_c,
-                                  sub_quants, Tf, cx.st, q0map) != hipSuccess)
-            return fail("rvq launch failed (codebook size must be a multiple of 64, dim in {16,32,64,128,256,512})");
+    const double rvq_fl = 2.0 * B * Tf * (double)n_q * e->arch.codebook_size * Dc;
+    cx.rvq_flops += rvq_fl;
+    if (!cx.dry && last.T != Tf) cx.fail("internal: frame count mismatch");
+    if (emb_rows)
+        cx.launch("combine", "", [&] { return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, emb, (long long)Tf * D, 1, D, cx.st); });
+    if (e->q_proj)
+        cx.launch("combine", "", [&] { return fc::launch_combine(src_of(pj), fc::Src(), 0, 1.f, nullptr, B, Dc, Tf, Tf, xq, (long long)Tf * Dc, 1, Dc, cx.st); });
+    else if (ranged)
+        cx.launch("combine", "", [&] { return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, xq, (long long)Tf * D, 1, D, cx.st); });
+    if (ranged) cx.launch("tanh", "", [&] { return fc::launch_tanh_range(xq, (size_t)B * Tf * Dc, e->arch.codec_range, cx.st); });
+    if (q0) {
+        if (!cx.dry && Tf < 2) cx.fail("quantizer_conf.q0_ds_ratio > 1 needs at least 2 frames (the reference's F.interpolate(size=[Tf // 2]) raises on 0)");
+        cx.launch("q0 map", "", [&] { return fc::launch_q0_map(q0map, B, Tf, cx.st); });
     }
+    cx.launch("rvq", "", [] { return kRvqClass; }, rvq_fl, 0.0, [&] {
+        return fc::launch_rvq_encode(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, e->cb_frag, e->enorm, codes, quant_c, qbdt_c, sub_quants, Tf, cx.st, q0map);
+    });
     float* qbdt = qbdt_c;
     if (e->q_proj) {       // output_proj (costume_quantizer.py:92-94): decoder input [B][D][Tf] and the returned embeddings [B][Tf][D]
         fc::Src qs; qs.ptr = qbdt_c; qs.used = 1;
         Act qo = run_conv(e, cx, e->q_out, qs, fc::Src(), 0, Tf);
         qbdt = qo.raw;
-        cx.launches++;
-        if (!cx.dry && !cx.err && quantized &&
-            fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, quantized, (long long)Tf * D, 1, D, cx.st) != hipSuccess)
-            return fail("combine launch failed");
+        if (quantized)
+            cx.launch("combine", "", [&] { return fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, quantized, (long long)Tf * D, 1, D, cx.st); });
     }
     if (quant_bdt_out) *quant_bdt_out = qbdt;
     return cx.err;
@@ -1782,14 +1685,12 @@ int do_decode(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* sc
         return cx.err;
     }
     Act last = run_decoder(e, cx, z_bdt, Tf);
-    cx.launches++;
-    if (!cx.dry && !cx.err) {
-        if (out_len > last.T) return fail("out_len exceeds Tf*hop");
-        // final GroupNorm apply (decoder.model.N.conv.norm has C = audio channels), x scale (codec_basic.py:406-407), trim (:711)
-        const int C = e->audio_ch();
-        if (fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, scale, cx.B, C, last.T, out_len, wav, (long long)C * out_len, out_len, 1, cx.st) != hipSuccess)
-            return fail("combine launch failed");
-    }
+    if (!cx.dry && out_len > last.T) cx.fail("out_len exceeds Tf*hop");
+    // final GroupNorm apply (decoder.model.N.conv.norm has C = audio channels), x scale (codec_basic.py:406-407), trim (:711)
+    const int C = e->audio_ch();
+    cx.launch("combine", "", [&] {
+        return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, scale, cx.B, C, last.T, out_len, wav, (long long)C * out_len, out_len, 1, cx.st);
+    });
     return cx.err;
 }
 
@@ -1815,12 +1716,6 @@ int check_ready(fc_engine* e) {
     if (!e) return fail("null engine");
     if (!e->finalized) return fail("engine not finalized");
     return consume_status(e);
-}
-
-Ctx make_ctx(int B, void* ws, size_t ws_bytes, void* stream) {
-    Ctx cx;
-    cx.B = B; cx.st = (hipStream_t)stream; cx.base = (char*)ws; cx.cap = ws_bytes;
-    return cx;
 }
 
 }  // namespace
@@ -2079,7 +1974,7 @@ size_t fc_engine_workspace_bytes(const fc_engine* ce, int B, int T) {
     if (!e || B <= 0 || T <= 0) return 0;
     // tiling is only known after finalize(); plan with the same rule here
     const int Tf = frames_for(e, T), D = e->arch.dimension;
-    Ctx cx; cx.B = B; cx.dry = true;
+    Ctx cx = dry_ctx(e, B);
     float* q = nullptr;
     do_encode(e, cx, nullptr, T, e->arch.num_quantizers, nullptr, nullptr, nullptr, nullptr, nullptr, &q);
     cx.alloc<float>((size_t)B * Tf * D);           // quantized when the caller does not want it
@@ -2092,9 +1987,11 @@ size_t fc_engine_workspace_bytes(const fc_engine* ce, int B, int T) {
 int fc_engine_work(const fc_engine* ce, int B, int T, int n_q, fc_work* out) {
     fc_engine* e = const_cast<fc_engine*>(ce);
     if (!e || !out) return fail("null argument");
-    Ctx cx; cx.B = B; cx.dry = true;
+    Ctx cx = dry_ctx(e, B);
     float* q = nullptr;
-    do_encode(e, cx, nullptr, T, n_q, nullptr, nullptr, nullptr, nullptr, nullptr, &q);
+    // the call counted is fc_encode_decode as the Python wrapper makes it: with the quantised embeddings (the pointer only marks presence)
+    float quantized_mark;
+    do_encode(e, cx, nullptr, T, n_q, nullptr, &quantized_mark, nullptr, nullptr, nullptr, &q);
     do_decode(e, cx, nullptr, frames_for(e, T), nullptr, T, nullptr);
     out->conv_flops = cx.conv_flops; out->conv_bytes = cx.conv_bytes;
     out->lstm_flops = cx.lstm_flops; out->rvq_flops = cx.rvq_flops;
@@ -2116,7 +2013,7 @@ int fc_encode(fc_engine* e, const float* wav, int B, int T, int n_q, int64_t* co
     if (check_ready(e)) return 1;
     if (!wav || !codes || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return do_encode(e, cx, wav, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr);
 }
 
@@ -2124,7 +2021,7 @@ int fc_decode_emb(fc_engine* e, const float* emb, const float* scale, int B, int
                   void* workspace, size_t workspace_bytes, void* stream) {
     if (check_ready(e)) return 1;
     if (!emb || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     const int D = e->arch.dimension;
     float* z = cx.alloc<float>((size_t)B * D * Tf);
     if (cx.err) return 1;
@@ -2137,7 +2034,7 @@ int fc_decode_codes(fc_engine* e, const int64_t* codes, int B, int Tf, int n_q, 
     if (check_ready(e)) return 1;
     if (!codes || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     const int D = e->arch.dimension, Dc = e->cdim();
     float* z = cx.alloc<float>((size_t)B * Dc * Tf);
     if (cx.err) return 1;
@@ -2158,7 +2055,7 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
     if (check_ready(e)) return 1;
     if (!wav || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     float* sc = scale;
     if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
     float* qbdt = nullptr;
@@ -2233,11 +2130,8 @@ int layer2d(fc_engine* e, Ctx& cx, const Layer2dRef& r, const float* x0, const f
         a[i].buf = cx.alloc<float>((size_t)B * (F + 2 * h) * C * T);
         a[i].aff = const_cast<float*>(affs[i]);
         a[i].normed = affs[i] != nullptr;
-        if (!cx.dry && !cx.err) {
-            hipError_t er = fc::launch_feats_relayout(a[i].buf, const_cast<float*>(xs[i]), B, C, F, T, h, 0, cx.st);
-            if (er == hipSuccess) er = fc::launch_halo_rows(a[i].buf, B, F, h, C, T, 0, cx.st);
-            if (er != hipSuccess) { cx.err = 1; g_err = std::string("input relayout failed: ") + hipGetErrorString(er); }
-        }
+        cx.launch("input relayout", L.prefix.c_str(), [&] { return fc::launch_feats_relayout(a[i].buf, const_cast<float*>(xs[i]), B, C, F, T, h, 0, cx.st); });
+        cx.launch("halo rows", L.prefix.c_str(), [&] { return fc::launch_halo_rows(a[i].buf, B, F, h, C, T, 0, cx.st); });
     }
     const Act2* p1 = x1 ? &a[1] : nullptr;
     Act2 o = r.stage >= 0 ? run_convtr2d(e, cx, L, e->dec_up_phases[r.stage], a[0], p1, r.stage + 1 == (int)e->dec_stages.size(), out_halo)
@@ -2246,12 +2140,9 @@ int layer2d(fc_engine* e, Ctx& cx, const Layer2dRef& r, const float* x0, const f
     shape[0] = o.C; shape[1] = Fh; shape[2] = o.T;
     // the pending GroupNorm affine over every row (halo rows included), then the reference's [B][C][F][T]
     float* fin = cx.alloc<float>((size_t)B * Fh * o.C * o.T);
-    if (cx.err) return 1;
-    if (cx.dry) return 0;
-    hipError_t er = fc::launch_combine2d(o.buf, o.aff, 0, nullptr, nullptr, 0, 0, 1.f, B, Fh, o.C, o.T, fin, 0, cx.st, 0);
-    if (er == hipSuccess) er = fc::launch_feats_relayout(fin, y, B, o.C, Fh, o.T, 0, 1, cx.st);
-    if (er != hipSuccess) return fail(std::string("output relayout failed: ") + hipGetErrorString(er));
-    return 0;
+    cx.launch("output affine", L.prefix.c_str(), [&] { return fc::launch_combine2d(o.buf, o.aff, 0, nullptr, nullptr, 0, 0, 1.f, B, Fh, o.C, o.T, fin, 0, cx.st, 0); });
+    cx.launch("output relayout", L.prefix.c_str(), [&] { return fc::launch_feats_relayout(fin, y, B, o.C, Fh, o.T, 0, 1, cx.st); });
+    return cx.err;
 }
 }  // namespace
 
@@ -2268,7 +2159,7 @@ int fc_layer2d_out_shape(const fc_engine* ce, const char* prefix, int B, int F, 
     int ok = 0;
     for (int form = 0; form < 8; ++form) {
         const bool two = form & 1, aff = form & 2, elu = form & 4;
-        Ctx cx; cx.B = B; cx.dry = true;
+        Ctx cx = dry_ctx(e, B);
         int64_t shape[3];
         const std::string keep = g_err;
         if (layer2d(e, cx, r, mark, aff ? mark : nullptr, two ? mark : nullptr, (two && aff) ? mark : nullptr, F, T, elu, out_halo, nullptr, shape)) {
@@ -2279,7 +2170,7 @@ int fc_layer2d_out_shape(const fc_engine* ce, const char* prefix, int B, int F, 
         need = std::max(need, cx.off);
     }
     if (!ok) {                                        // no form is valid: report why the single-source ELU form is not
-        Ctx cx; cx.B = B; cx.dry = true;
+        Ctx cx = dry_ctx(e, B);
         int64_t shape[3];
         layer2d(e, cx, r, mark, nullptr, nullptr, nullptr, F, T, 1, out_halo, nullptr, shape);
         return 1;
@@ -2295,7 +2186,7 @@ int fc_layer2d_forward(fc_engine* e, const char* prefix, const float* x0, const 
     if (!x0 || !y || (aff1 && !x1)) return fail("bad argument");
     Layer2dRef r;
     if (find_layer2d(e, prefix, &r)) return 1;
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     int64_t shape[3];
     return layer2d(e, cx, r, x0, aff0, x1, aff1, F, T, apply_elu, out_halo, y, shape);
 }
@@ -2308,7 +2199,7 @@ int fc_layer_forward(fc_engine* e, const char* prefix, const float* x, int B, in
     if (it == e->by_prefix.end()) return fail(std::string("unknown layer ") + prefix);
     if (it->second->c2d > 0)      // a Conv2d planned over kf * C channels of frequency-major rows: the 1-D path would read kf times the input
         return fail(std::string("layer ") + prefix + " is a 2-D layer of the STFT-domain codec: use fc_layer2d_forward");
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     fc::Src s; s.ptr = x; s.used = 1;
     Act o = run_conv(e, cx, *it->second, s, fc::Src(), apply_elu, T);
     if (cx.err) return 1;
@@ -2322,7 +2213,7 @@ int fc_resblock_forward(fc_engine* e, const char* prefix, const float* x, int B,
     if (!prefix || !x || !y || B <= 0 || T <= 0) return fail("bad argument");
     auto it = e->res_by_prefix.find(prefix);
     if (it == e->res_by_prefix.end()) return fail(std::string("unknown residual block ") + prefix);
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     fc_engine::Stage one;
     one.res.push_back(*it->second);
     fc::Src s; s.ptr = x; s.used = 1;
@@ -2339,7 +2230,7 @@ int fc_lstm_forward(fc_engine* e, const char* prefix, const float* x, int B, int
     if (!prefix || !x || !y || B <= 0 || T <= 0) return fail("bad argument");
     auto it = e->lstm_by_prefix.find(prefix);
     if (it == e->lstm_by_prefix.end()) return fail(std::string("unknown lstm ") + prefix);
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     Act in; in.raw = const_cast<float*>(x); in.C = it->second->H; in.T = T;
     Act o = run_lstm(e, cx, *it->second, in, T);
     if (cx.err) return 1;
@@ -2355,7 +2246,7 @@ int fc_seq_forward(fc_engine* e, const char* prefix, const float* x, int B, int 
     if (!prefix || !x || !y || B <= 0 || T <= 0) return fail("bad argument");
     auto it = e->tf_by_prefix.find(prefix);
     if (it == e->tf_by_prefix.end()) return fail(std::string("unknown transformer ") + prefix);
-    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     Act in; in.raw = const_cast<float*>(x); in.C = it->second->C; in.T = T;
     Act o = run_transformer(e, cx, *it->second, in, T);
     if (cx.err) return 1;

@@ -1040,6 +1040,11 @@ def test_freq_codec_against_oracle_fresh_inputs(cfg_name, seed, B, T, kind, bw, 
     o = orc.inference(wav, bit_width=bw, use_scale=use_scale)
     ret = m.inference(wav.cuda().unsqueeze(1), bit_width=bw, use_scale=use_scale)
     m.engine.check_status()
+    if cfg_name == "tinyfreqgr1wnc":
+        # the work accounting = the kernel dispatches of one fc_encode_decode with these arguments in a rocprofv3 kernel trace: no
+        # GroupNorm launches (weight_norm), one gconvtr2d_kernel launch per grouped ConvTranspose2d, the SLSTMs on their per-step launches
+        w = m.engine.work(B, T, m.arch.num_quantizers_for_bandwidth(bw))
+        assert (w["total_launches"], w["conv_launches"]) == (78, 40), w
     rep = index_report(ret["code_indices"][0], o["code_indices"][0])
     assert ret["recon_speech"].shape == o["recon_speech"].shape
     assert (ret["code_embeddings"][0][1] is None) == (not use_scale)

@@ -113,6 +113,10 @@ def test_causal_attention_does_not_see_later_frames():
     x2[:, :, 400:] = torch.randn(2, 256, 377, generator=torch.Generator().manual_seed(6)) * 3
     y, y2 = m.engine.seq_forward(prefix, x.cuda()).cpu(), m.engine.seq_forward(prefix, x2.cuda()).cpu()
     assert torch.equal(y[:, :, :400], y2[:, :, :400]) and not torch.equal(y[:, :, 400:], y2[:, :, 400:])
+    # the work accounting of this engine = the kernel dispatches of one fc_encode_decode(B 2, T 4000) in a rocprofv3 kernel trace (per
+    # transformer block: two LayerNorms, the attention, the ReLU and four GEMMs)
+    w = m.engine.work(2, 4000, arch.num_quantizers)
+    assert (w["total_launches"], w["conv_launches"]) == (60, 34), w
 
 
 # ---- 2. end to end against the real reference ----------------------------------------------------------------------------------

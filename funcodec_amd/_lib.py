@@ -77,12 +77,14 @@ SYMBOLS = {
     "fc_rvq_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_q0_source_frames": (C.c_int, [C.c_int, _P]),
     "fc_layer_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "fc_layer_forward_src": (C.c_int, [_P, C.c_char_p, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_layer_out_len": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "fc_layer2d_forward": (C.c_int, [_P, C.c_char_p, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_layer2d_out_shape": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "fc_lstm_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_seq_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_resblock_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "fc_resblock_forward_src": (C.c_int, [_P, C.c_char_p, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_engine_work": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(FcWork)]),
     "fc_engine_profile": (C.c_int, [_P, C.c_int]),
     "fc_engine_profile_read": (C.c_int, [_P, C.POINTER(FcProf)]),

@@ -2191,37 +2191,70 @@ int fc_layer2d_forward(fc_engine* e, const char* prefix, const float* x0, const 
     return layer2d(e, cx, r, x0, aff0, x1, aff1, F, T, apply_elu, out_halo, y, shape);
 }
 
-int fc_layer_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, int apply_elu, float* y,
-                     void* workspace, size_t workspace_bytes, void* stream) {
-    if (check_ready(e)) return 1;
-    if (!prefix || !x || !y || B <= 0 || T <= 0) return fail("bad argument");
+namespace {
+fc::Src hook_src(const float* x, const float* aff, const float* div) {
+    fc::Src s;
+    s.ptr = x; s.aff = aff; s.div = div;
+    s.used = x ? ((aff || div) ? 3 : 1) : 0;
+    return s;
+}
+}  // namespace
+
+// the host-side refusals of fc_layer_forward_src (they need the plan only, no weights)
+static int layer_src_check(const fc_engine* e, const char* prefix, const float* x0, const float* aff0, const float* div0, const float* x1,
+                           const float* aff1, int B, int T, const ConvLayer** out) {
+    if (!e || !prefix || !x0 || B <= 0 || T <= 0 || (aff1 && !x1) || (aff0 && div0)) return fail("bad argument");
     auto it = e->by_prefix.find(prefix);
     if (it == e->by_prefix.end()) return fail(std::string("unknown layer ") + prefix);
-    if (it->second->c2d > 0)      // a Conv2d planned over kf * C channels of frequency-major rows: the 1-D path would read kf times the input
+    const ConvLayer& L = *it->second;
+    if (L.c2d > 0)      // a Conv2d planned over kf * C channels of frequency-major rows: the 1-D path would read kf times the input
         return fail(std::string("layer ") + prefix + " is a 2-D layer of the STFT-domain codec: use fc_layer2d_forward");
+    if (x1 && !L.dual) return fail("fc_layer_forward_src: " + L.prefix + " is planned for one source (its staging has no room for two)");
+    if (div0 && &L != &e->enc_first) return fail("fc_layer_forward_src: div0 is the encoder's first conv's volume scale (" + e->enc_first.prefix + ")");
+    *out = &L;
+    return 0;
+}
+
+int fc_layer_forward_src(fc_engine* e, const char* prefix, const float* x0, const float* aff0, const float* div0, const float* x1,
+                         const float* aff1, int B, int T, int apply_elu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    const ConvLayer* L = nullptr;
+    if (layer_src_check(e, prefix, x0, aff0, div0, x1, aff1, B, T, &L)) return 1;
+    if (!y) return fail("bad argument");
+    if (check_ready(e)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    fc::Src s; s.ptr = x; s.used = 1;
-    Act o = run_conv(e, cx, *it->second, s, fc::Src(), apply_elu, T);
+    Act o = run_conv(e, cx, *L, hook_src(x0, aff0, div0), hook_src(x1, aff1, nullptr), apply_elu, T);
     if (cx.err) return 1;
     HIP_TRY(fc::launch_combine(src_of(o), fc::Src(), 0, 1.f, nullptr, B, o.C, o.T, o.T, y, (long long)o.C * o.T, o.T, 1, cx.st));
     return 0;
 }
 
-int fc_resblock_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, float* y, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-    if (check_ready(e)) return 1;
-    if (!prefix || !x || !y || B <= 0 || T <= 0) return fail("bad argument");
+int fc_layer_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, int apply_elu, float* y,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    return fc_layer_forward_src(e, prefix, x, nullptr, nullptr, nullptr, nullptr, B, T, apply_elu, y, workspace, workspace_bytes, stream);
+}
+
+int fc_resblock_forward_src(fc_engine* e, const char* prefix, const float* x0, const float* aff0, const float* x1, const float* aff1, int B,
+                            int T, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!e || !prefix || !x0 || !y || B <= 0 || T <= 0 || (aff1 && !x1)) return fail("bad argument");
     auto it = e->res_by_prefix.find(prefix);
     if (it == e->res_by_prefix.end()) return fail(std::string("unknown residual block ") + prefix);
+    const fc_engine::ResBlock& R = *it->second;
+    if (x1 && !R.shortcut.dual)
+        return fail(std::string("fc_resblock_forward_src: block ") + prefix + " is planned for one source (its staging has no room for two)");
+    if (check_ready(e)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     fc_engine::Stage one;
-    one.res.push_back(*it->second);
-    fc::Src s; s.ptr = x; s.used = 1;
+    one.res.push_back(R);
     Act sc, b3;
-    run_resblocks(e, cx, one, s, fc::Src(), T, &sc, &b3);
+    run_resblocks(e, cx, one, hook_src(x0, aff0, nullptr), hook_src(x1, aff1, nullptr), T, &sc, &b3);
     if (cx.err) return 1;
     HIP_TRY(fc::launch_combine(src_of(sc), src_of(b3), 0, 1.f, nullptr, B, sc.C, T, T, y, (long long)sc.C * T, T, 1, cx.st));
     return 0;
+}
+
+int fc_resblock_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, float* y, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    return fc_resblock_forward_src(e, prefix, x, nullptr, nullptr, nullptr, B, T, y, workspace, workspace_bytes, stream);
 }
 
 int fc_lstm_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, float* y, void* workspace,

@@ -352,8 +352,30 @@ class CodecEngine:
                                            0 if ws is None else 4 * N, self._stream()))
         return codes, quant
 
+    def _sources(self, what: str, shape, aff0, x1, aff1):
+        """(x1, aff0, aff1) of a per-layer call on the device, checked against the layer's input shape [B, C, T]."""
+        B, Cin = shape[0], shape[1]
+        if x1 is None and aff1 is not None:
+            raise EngineError(f"{what}: aff1 without x1")
+        if x1 is not None:
+            x1 = self._dev(x1, torch.float32)
+            if tuple(x1.shape) != tuple(shape):
+                raise EngineError(f"{what}: x1 must be [B,C,T] = {tuple(shape)}, got {tuple(x1.shape)}")
+        affs = []
+        for a in (aff0, aff1):
+            if a is not None:
+                a = self._dev(a, torch.float32)
+                if tuple(a.shape) != (B, Cin, 2):
+                    raise EngineError(f"{what}: an affine must be [B,C,2] = {(B, Cin, 2)}, got {tuple(a.shape)}")
+            affs.append(a)
+        return x1, affs[0], affs[1]
+
     @_on_device
-    def layer_forward(self, prefix: str, x: torch.Tensor, apply_elu: bool = False) -> torch.Tensor:
+    def layer_forward(self, prefix: str, x: torch.Tensor, apply_elu: bool = False, *, aff0: Optional[torch.Tensor] = None,
+                      div: Optional[torch.Tensor] = None, x1: Optional[torch.Tensor] = None, aff1: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One 1-D layer (fc_layer_forward / fc_layer_forward_src) on act(aff0(x / div) + aff1(x1)): x, x1 [B,C,T], pending GroupNorm
+        affines aff0, aff1 [B,C,2] (scale, shift), div [B] (the encoder's first conv only), act = ELU when apply_elu -> the layer's output
+        [B, Cout, Tout], GroupNorm'd (raw for weight_norm nets)."""
         x = self._dev(x, torch.float32)
         B, Cin, T = x.shape
         Tout = self.lib.fc_layer_out_len(self._h, prefix.encode(), T)
@@ -369,14 +391,24 @@ class CodecEngine:
         cin = wshape[0] if tr else wshape[1]
         if Cin != cin:
             raise EngineError(f"layer {prefix}: expected input [B, {cin}, T], got {tuple(x.shape)}")
+        x1, aff0, aff1 = self._sources(f"layer {prefix}", x.shape, aff0, x1, aff1)
+        if div is not None:
+            div = self._dev(div.reshape(-1), torch.float32)
+            if div.numel() != B:
+                raise EngineError(f"layer {prefix}: div must hold one scale per utterance ({B}), got {div.numel()}")
         y = torch.empty((B, cout, Tout), dtype=torch.float32, device=self.device)
         ws = self._workspace(B, max(T, Tout) * 4 + 4096)
-        need = (B * cout * (Tout + 64) * 4) * 2 + (1 << 20)
+        # the layer's output + statistics, and a materialised (activated, summed) input for layers with >= 3 row tiles
+        need = (B * cout * (Tout + 64) * 4) * 2 + B * cin * (T + 2048) * 4 + (1 << 20)
         if ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             ws = self._ws
-        self._check(self.lib.fc_layer_forward(self._h, prefix.encode(), _ptr(x), B, T, int(apply_elu), _ptr(y), _ptr(ws),
-                                              ws.numel(), self._stream()))
+        if aff0 is None and div is None and x1 is None:
+            rc = self.lib.fc_layer_forward(self._h, prefix.encode(), _ptr(x), B, T, int(apply_elu), _ptr(y), _ptr(ws), ws.numel(), self._stream())
+        else:
+            rc = self.lib.fc_layer_forward_src(self._h, prefix.encode(), _ptr(x), _ptr(aff0), _ptr(div), _ptr(x1), _ptr(aff1), B, T,
+                                               int(apply_elu), _ptr(y), _ptr(ws), ws.numel(), self._stream())
+        self._check(rc)
         return y
 
     @_on_device
@@ -426,16 +458,24 @@ class CodecEngine:
         raise EngineError("freq_halo: not an STFT-domain codec")
 
     @_on_device
-    def resblock_forward(self, prefix: str, x: torch.Tensor) -> torch.Tensor:
-        """SEANetResnetBlock.forward of the block at Sequential prefix `prefix` (e.g. "encoder.model.1"): [B,C,T] -> [B,C,T]."""
+    def resblock_forward(self, prefix: str, x: torch.Tensor, *, aff0: Optional[torch.Tensor] = None, x1: Optional[torch.Tensor] = None,
+                         aff1: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """SEANetResnetBlock.forward of the block at Sequential prefix `prefix` (e.g. "encoder.model.1") on aff0(x) + aff1(x1)
+        (fc_resblock_forward / fc_resblock_forward_src; affines [B,C,2] (scale, shift)): [B,C,T] -> [B,C,T]."""
         x = self._dev(x, torch.float32)
         B, Cc, T = x.shape
+        x1, aff0, aff1 = self._sources(f"block {prefix}", x.shape, aff0, x1, aff1)
         y = torch.empty_like(x)
-        need = B * Cc * (T + 64) * 4 * 4 + (4 << 20)
+        need = B * Cc * (T + 64) * 4 * 6 + (4 << 20)      # both branches, the hidden one, and up to two materialised inputs
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         ws = self._ws
-        self._check(self.lib.fc_resblock_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
+        if aff0 is None and x1 is None:
+            rc = self.lib.fc_resblock_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream())
+        else:
+            rc = self.lib.fc_resblock_forward_src(self._h, prefix.encode(), _ptr(x), _ptr(aff0), _ptr(x1), _ptr(aff1), B, T, _ptr(y), _ptr(ws),
+                                                  ws.numel(), self._stream())
+        self._check(rc)
         return y
 
     @_on_device

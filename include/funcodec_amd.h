@@ -202,6 +202,16 @@ int fc_q0_source_frames(int Tf, int32_t* frames /* host, Tf entries */);
  * apply_elu: apply ELU to x first (the nn.ELU that precedes the module in the Sequential). */
 int fc_layer_forward(fc_engine* e, const char* prefix, const float* x, int B, int T, int apply_elu,
                      float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The same layer in any call form the encode / decode drivers use (run_encoder / run_resblocks / run_decoder): the drivers' own run_conv
+ * with the sources they hand over, so the kernel is the one the product picks for that layer, form and shape.
+ *   x0, x1     dev f32 [B][Cin][T] (x1 NULL = one source)
+ *   aff0, aff1 dev f32 [B][Cin][2] (scale, shift) pending GroupNorm affines, or NULL
+ *   div0       dev f32 [B]: x0 is divided by div0[b] (the volume scale of the encoder's first conv), or NULL
+ *   the layer's input is act(aff0(x0 / div0) + aff1(x1)), act = ELU when apply_elu; y as fc_layer_forward.
+ * Refused on the host: a second source for a layer the plan gives one (its staging has no room for two), div0 on any layer but the
+ * encoder's first conv, div0 together with aff0, a 2-D layer.  fc_layer_forward is this call with x0 alone.  A test hook. */
+int fc_layer_forward_src(fc_engine* e, const char* prefix, const float* x0, const float* aff0, const float* div0, const float* x1,
+                         const float* aff1, int B, int T, int apply_elu, float* y, void* workspace, size_t workspace_bytes, void* stream);
 /* output length of that layer for input length T (-1: unknown prefix, or a 2-D layer) */
 int fc_layer_out_len(const fc_engine* e, const char* prefix, int T);
 /* fc_layer_forward refuses the 2-D layers of the STFT-domain codec (model_type 1) on the host, before any launch; they go through: */
@@ -229,6 +239,11 @@ int fc_layer2d_out_shape(const fc_engine* e, const char* prefix, int B, int F, i
  * recipe has one); x, y dev f32 [B,C,T].  Exercises the fused shortcut + block.1 launch of the thin (C <= 64) blocks. */
 int fc_resblock_forward(fc_engine* e, const char* prefix, const float* x, int B, int T,
                         float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The same block on the input the drivers hand it: aff0(x0) + aff1(x1) (x1, aff1 NULL: one source; affines [B][C][2] as above), through
+ * run_resblocks, so the thin blocks run reshead_kernel<C, k, DUAL> with one or two sources.  A second source is refused on the host for
+ * a block the plan gives one (block 0 of a stage).  fc_resblock_forward is this call with x0 alone. */
+int fc_resblock_forward_src(fc_engine* e, const char* prefix, const float* x0, const float* aff0, const float* x1, const float* aff1,
+                            int B, int T, float* y, void* workspace, size_t workspace_bytes, void* stream);
 
 /* SLSTM.forward (lstm.py:22-28) addressed by prefix ("encoder.model.16.lstm"): x,y dev f32 [B,C,T]. */
 int fc_lstm_forward(fc_engine* e, const char* prefix, const float* x, int B, int T,

@@ -216,6 +216,32 @@ def test_frequency_ratio_1_recipe_and_layer2d_shapes(name):
     assert eng.lib.fc_layer_out_len(eng._h, b"encoder.model.19.conv", 9) == 9
 
 
+def test_layer_call_form_hooks_refuse_on_the_host():
+    """fc_layer_forward_src / fc_resblock_forward_src refuse before any launch (no GPU, no weights): a second source for a layer or block
+    the plan gives one, a divisor anywhere but the encoder's first conv, a 2-D layer.  The pointers are never dereferenced."""
+    import ctypes as C
+    from funcodec_amd.config import freq_recipe_config
+    eng = CodecEngine(arch_from_config(recipe_config("tiny")))
+    lib, h, p = eng.lib, eng._h, C.c_void_p(256)
+
+    def layer(prefix, x1=None, div=None):
+        return lib.fc_layer_forward_src(h, prefix, p, None, div, x1, None, 1, 9, 1, p, p, 1 << 20, None)
+
+    assert layer(b"encoder.model.1.block.3.conv", x1=p) != 0
+    assert "is planned for one source" in lib.fc_last_error().decode()
+    assert layer(b"encoder.model.1.shortcut.conv", div=p) != 0
+    assert "div0 is the encoder's first conv's volume scale" in lib.fc_last_error().decode()
+    assert lib.fc_resblock_forward_src(h, b"encoder.model.1", p, None, p, None, 1, 9, p, p, 1 << 20, None) != 0
+    assert "is planned for one source" in lib.fc_last_error().decode()
+    # the forms the drivers use pass the checks and stop at the missing weights
+    for prefix, x1, div in ((b"encoder.model.0.conv", None, p), (b"encoder.model.3.conv", p, None), (b"decoder.model.9.conv", p, None)):
+        assert layer(prefix, x1=x1, div=div) != 0
+        assert "not finalized" in lib.fc_last_error().decode(), prefix
+    feng = CodecEngine(arch_from_config(freq_recipe_config("tinyfreq")))
+    assert feng.lib.fc_layer_forward_src(feng._h, b"encoder.model.1.block.1.conv", p, None, None, None, None, 1, 9, 0, p, p, 1 << 20, None) != 0
+    assert "use fc_layer2d_forward" in feng.lib.fc_last_error().decode()
+
+
 def test_engine_sizes_and_work_accounting():
     arch = arch_from_config(recipe_config("ds640"))
     eng = CodecEngine(arch)

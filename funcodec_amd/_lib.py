@@ -96,6 +96,17 @@ SYMBOLS = {
     "fc_write_wav_pcm16": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int, C.c_int]),
     "fc_overlap_add": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "fc_engine_status": (C.c_int, [_P, C.POINTER(C.c_uint)]),
+    # streaming session of a causal time-domain engine
+    "fc_stream_state_bytes": (C.c_size_t, [_P, C.c_int]),
+    "fc_stream_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    "fc_stream_destroy": (None, [_P]),
+    "fc_stream_min_first": (C.c_int, [_P, C.c_int]),
+    "fc_stream_workspace_bytes": (C.c_size_t, [_P]),
+    "fc_stream_reset": (C.c_int, [_P, _P, _P]),
+    "fc_stream_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int), _P, C.c_size_t, _P]),
+    "fc_stream_decode_codes": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "fc_stream_decode_emb": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "fc_stream_lstm_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     # LauraTTS generation (ABI version 5)
     "fc_laura_create": (C.c_int, [C.POINTER(FcLauraArch), C.c_int, C.POINTER(_P)]),
     "fc_laura_destroy": (None, [_P]),

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "laura_kernels.h"
 #include "seq_kernels.h"
+#include "stream_kernels.h"
 
 namespace {
 
@@ -168,6 +169,23 @@ struct fc_engine {
         prof_names.push_back(name);
         return (int)prof_names.size() - 1;
     }
+};
+
+// One streaming session of a causal time-domain engine (fc_stream_*).  Everything that survives a push lives in `state`, ONE device
+// allocation of the caller (fc_stream_state_bytes): [scale B] [per conv with a left context: carry [2][B][cin][pt], ping-pong on the parity
+// of the side's push count] [encoder LSTM h [L][2][B][H] | c [L][B][H]] [decoder LSTM the same].  The host side keeps only push counters.
+struct fc_stream {
+    fc_engine* e = nullptr;
+    int B = 0, max_chunk = 0, n_q = 0;
+    float* state = nullptr;
+    size_t state_floats = 0;
+    std::map<const ConvLayer*, size_t> carry;       // float offset of the layer's carry pair inside state
+    size_t enc_lstm_off = 0, dec_lstm_off = 0;
+    int enc_pushes = 0, dec_pushes = 0;
+    bool enc_done = false;                          // the final push has been taken
+    bool broken = false;                            // a push failed half-way: carries are a mix of old and new until the next reset
+    int enc_min_first = 0, dec_min_first = 0;       // shortest first push: samples (a hop multiple) / frames
+    std::vector<float> ones;
 };
 
 namespace {
@@ -1627,6 +1645,8 @@ int frames_for(const fc_engine* e, int T) {
 }
 
 // ---- composite paths (each usable in dry mode for workspace sizing / work accounting) ---------------
+int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
+                float** quant_bdt_out);
 int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* codes, float* quantized,
               float* sub_quants, float* scale, float* enc_out, float** quant_bdt_out) {
     const int B = cx.B, D = e->arch.dimension, Tf = frames_for(e, T);
@@ -1636,6 +1656,13 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
         cx.launch("volume", "", [&] { return fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st); });
     }
     Act last = e->arch.model_type == 1 ? run_encoder_2d(e, cx, wav, T, sc) : run_encoder(e, cx, wav, T, sc);
+    return do_quantize(e, cx, last, Tf, n_q, codes, quantized, sub_quants, enc_out, quant_bdt_out);
+}
+
+// the quantiser behind the encoder's last conv (per frame: the offline call and a streaming push share it)
+int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
+                float** quant_bdt_out) {
+    const int B = cx.B, D = e->arch.dimension;
     const int Dc = e->cdim();
     const bool ranged = e->arch.codec_range > 0.f;
     // encoder output rows [B][Tf][D] (seanet_encoder.py:175) with the last GroupNorm applied: the quantiser's input, or asked for
@@ -1716,6 +1743,229 @@ int check_ready(fc_engine* e) {
     if (!e) return fail("null engine");
     if (!e->finalized) return fail("engine not finalized");
     return consume_status(e);
+}
+
+
+// ---- streaming session ---------------------------------------------------------------------------------------------------------
+// The reference has no streaming code; what a session must reproduce is the OFFLINE callable on the concatenation of its pushes:
+// Encodec.inference_encoding (codec_basic.py:720-764) for fc_stream_encode, Encodec.inference_decoding / inference_decoding_emb
+// (:766-836) for the two decode calls.  A causal SConv1d (conv.py:243-261) looks at padding_total columns to its left and at nothing to
+// its right except the last call's extra_padding, so a chunk is a plain conv without padding over [carry | chunk] where the carry is the
+// last padding_total columns of the layer's input so far.  The one place the offline call is NOT causal is the very start: pad1d reflects
+// (pad_mode "reflect", the only mode the configs use), i.e. the left padding of EVERY layer is columns 1..padding_total of its own input.
+// A session therefore takes a first push long enough to hold that reflection at every layer (fc_stream_min_first; the Python session
+// gathers short pushes until it has that much) and stages the reflection instead of a carry there.
+inline int stream_pt(const ConvLayer& L) { return L.transposed ? 1 : (L.k - 1) * L.dil - (L.stride - 1); }
+
+// every conv of the 1-D nets that carries a left context, with the columns of its input per encoder input sample (1 / div) or per
+// decoder frame (mul): f(layer, is_decoder, div_or_mul)
+template <typename F>
+void for_each_stream_conv(fc_engine* e, F&& f) {
+    int div = 1;
+    f(e->enc_first, false, div);
+    for (int s = 0; s < (int)e->enc_stages.size(); ++s) {
+        for (auto& R : e->enc_stages[s].res) f(R.block1, false, div);
+        f(e->enc_stages[s].resample, false, div);
+        div *= e->enc_stages[s].resample.stride;
+    }
+    f(e->enc_last, false, div);
+    int mul = 1;
+    f(e->dec_first, true, mul);
+    for (auto& S : e->dec_stages) {
+        f(S.resample, true, mul);
+        mul *= S.resample.stride;
+        for (auto& R : S.res) f(R.block1, true, mul);
+    }
+    f(e->dec_last, true, mul);
+}
+
+// why this engine cannot stream, or null.  Each reason names the configuration key.
+const char* stream_refusal(const fc_engine* e) {
+    const fc_arch& a = e->arch;
+    if (a.model_type != 0) return "streaming is not available for model: freq_codec (the STFT frames overlap; time-domain codec only)";
+    if (!a.causal) return "streaming needs encoder_conf.causal / decoder_conf.causal: true (a non-causal net looks ahead at every layer)";
+    if (a.lstm_layers > 0 && a.seq_model == 1) return "streaming is not available for seq_model: transformer (it needs a key / value cache across pushes)";
+    if (a.q0_ds_ratio > 1) return "streaming is not available for quantizer_conf.q0_ds_ratio > 1 (the half-rate first stage looks across frame pairs)";
+    return nullptr;
+}
+
+void stream_layout(fc_engine* e, int B, fc_stream* S) {
+    size_t off = ((size_t)B + 63) & ~(size_t)63;      // scale [B]
+    const int hop = total_hop(e);
+    int enc_min = hop, dec_min = 1;
+    for_each_stream_conv(e, [&](const ConvLayer& L, bool dec, int rate) {
+        const int pt = stream_pt(L);
+        if (pt <= 0) return;
+        S->carry[&L] = off;
+        off += ((size_t)2 * B * L.cin * pt + 63) & ~(size_t)63;
+        if (L.transposed) return;                      // zero left context at the start: no reflection to hold
+        if (!dec) enc_min = std::max(enc_min, (pt + 1) * rate);
+        else dec_min = std::max(dec_min, ceil_div_i(pt + 1, rate));
+    });
+    const size_t L = (size_t)e->arch.lstm_layers;
+    S->enc_lstm_off = off; off += 3 * L * B * e->enc_lstm.H;
+    S->dec_lstm_off = off; off += 3 * L * B * e->dec_lstm.H;
+    S->state_floats = off;
+    S->enc_min_first = ceil_div_i(enc_min, hop) * hop;
+    S->dec_min_first = dec_min;
+}
+
+// One causal SConv1d / SConvTranspose1d of a push: the staging pass (prologue + left context + new carry), then the layer's own GEMM
+// kernel as a conv without padding over what was staged.  side_pushes: pushes this side (encoder / decoder) has taken before this one.
+Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc, int side_pushes, bool final) {
+    const int B = cx.B, pt = stream_pt(L);
+    // the last push takes the reference's extra_padding (conv.py:57-64): earlier pushes are multiples of the stride, so the figure for the
+    // whole utterance is the one conv_geom gives the last chunk
+    const int extra = (!L.transposed && final) ? conv_geom(L, Tc).padR : 0;
+    const int Tp = pt + Tc + extra;
+    float* buf = cx.alloc<float>((size_t)B * L.cin * Tp);
+    if (!cx.dry && !L.transposed && !final && Tc % L.stride != 0) cx.fail("internal: a chunk that is not a multiple of the stride (" + L.prefix + ")");
+    if (!cx.dry && extra > pt + Tc - 1) cx.fail("internal: extra padding longer than the staged columns (" + L.prefix + ")");
+    fc::StreamStage g;
+    g.s0 = s0; g.s1 = s1; g.elu = elu; g.alpha = e->arch.elu_alpha;
+    g.B = B; g.C = L.cin; g.Tc = Tc; g.pt = pt; g.padR = extra; g.buf = buf;
+    g.left = side_pushes > 0 ? 0 : (L.transposed ? 2 : 1);
+    if (pt > 0) {
+        float* pair = S->state + S->carry.at(&L);
+        const size_t n = (size_t)B * L.cin * pt;
+        g.carry_in = pair + (size_t)(side_pushes & 1) * n;
+        g.carry_out = pair + (size_t)((side_pushes + 1) & 1) * n;
+    }
+    cx.launch("stream stage", L.prefix.c_str(), [] { return "stream_stage_kernel (streaming: prologue, left context and carry of a conv)"; }, 0.0,
+              4.0 * B * L.cin * ((double)Tc * (s1.used ? 2 : 1) + Tp + 2.0 * pt), [&] { return fc::launch_stream_stage(g, cx.st); });
+    ConvGeom geo;
+    geo.padL = 0; geo.padR = 0;
+    geo.Tout = L.transposed ? Tc * L.stride : (Tp - ((L.k - 1) * L.dil + 1)) / L.stride + 1;
+    geo.count_T = geo.Tout;
+    fc::ConvLaunch c = conv_launch_of(L, B, Tp, geo);
+    c.s0.ptr = buf; c.s0.used = 1;
+    c.alpha = e->arch.elu_alpha;
+    c.pad_zero = 1;                                   // nothing is padded; columns past the row end of the last tile read as zero
+    Act out;
+    out.C = L.cout; out.T = geo.Tout;
+    if (L.transposed) {                               // group j = taps (x[j-1], x[j]) = staged columns (j, j + 1): Tc groups, all kept
+        c.Tout = Tc; c.up_r = L.stride; c.trimL = 0; c.Tfinal = geo.Tout;
+    } else {
+        c.Tout = geo.Tout;
+    }
+    out.raw = cx.alloc<float>((size_t)B * L.cout * geo.Tout);
+    c.out = out.raw; c.out_sB = (long long)L.cout * geo.Tout; c.out_sM = geo.Tout; c.out_sT = 1;
+    const double fl = 2.0 * B * (double)L.M * L.cin * L.gk * c.Tout;
+    const double by = 4.0 * B * ((double)L.cin * Tp + (double)L.cout * geo.Tout);
+    cx.conv_flops += fl; cx.conv_bytes += by;
+    cx.conv_launch("conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
+    return out;
+}
+
+// SLSTM.forward (lstm.py:22-28) over a chunk, continuing the recurrence of the earlier pushes: the per-step kernel with its (h, c)
+// buffers inside the session state instead of a cleared workspace buffer.  h_l(t) sits at parity t & 1 and step 0 reads parity 1, so
+// after an odd number of steps the last hidden state is copied to where the next push looks for it.
+Act run_lstm_stream(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, float* st) {
+    const int H = lb.H, B = cx.B, L = (int)lb.layers.size();
+    float* xproj = cx.alloc<float>((size_t)T * B * 4 * H);
+    run_conv(e, cx, lb.layers[0].inproj, src_of(in), fc::Src(), 0, T, xproj, (long long)4 * H, 1, (long long)B * 4 * H);
+    Act y;
+    y.C = H; y.T = T;
+    y.raw = cx.alloc<float>((size_t)B * H * T);
+    const double fl = 2.0 * B * (double)T * 4 * H * H * (2 * L - 1);
+    cx.lstm_flops += fl;
+    const float* w[FC_LSTM_MAX_LAYERS] = {nullptr};
+    const float* bias[FC_LSTM_MAX_LAYERS] = {nullptr};
+    for (int l = 0; l < L; ++l) { w[l] = l == 0 ? lb.layers[0].whh : lb.layers[l].wcat; bias[l] = lb.layers[l].bperm; }
+    const char* pre = lb.prefix.c_str();
+    const size_t BH = (size_t)B * H;
+    ProfSpan sp(e, cx.st, cx.live(), [&] { return kLstmWaveClass; }, fl, 0.0);
+    for (int s = 0; s < T + L - 1; ++s)
+        cx.launch("lstm step", pre, [&] { return fc::launch_lstm_wave(w, bias, xproj, st, st + 2 * L * BH, y.raw, B, H, T, L, s, cx.st); });
+    if (T & 1)
+        for (int l = 0; l < L; ++l)
+            cx.launch("lstm carry", pre, [&] {
+                return hipMemcpyAsync(st + (size_t)(2 * l + 1) * BH, st + (size_t)(2 * l) * BH, BH * sizeof(float), hipMemcpyDeviceToDevice, cx.st);
+            });
+    return y;
+}
+
+// SEANetResnetBlock chain of a stage on a chunk: the k = 1 convs (shortcut, block.3) are pointwise and run as offline; block.1 carries
+void stream_resblocks(fc_engine* e, Ctx& cx, const fc_stream* S, const fc_engine::Stage& St, fc::Src* a0, fc::Src* a1, int T, int pushes, Act* sc, Act* b3) {
+    for (const auto& R : St.res) {
+        *sc = run_conv(e, cx, R.shortcut, *a0, *a1, 0, T);
+        Act b1 = stream_conv(e, cx, S, R.block1, *a0, *a1, 1, T, pushes, false);
+        *b3 = run_conv(e, cx, R.block3, src_of(b1), fc::Src(), 1, b1.T);
+        *a0 = src_of(*sc); *a1 = src_of(*b3);
+    }
+}
+
+// SEANetEncoder.forward on the chunk wav [B][C][Tc] of an utterance whose n earlier chunks the session has seen
+Act run_encoder_stream(fc_engine* e, Ctx& cx, const fc_stream* S, int n, const float* wav, int Tc, bool final) {
+    fc::Src s; s.ptr = wav; s.div = S->state; s.used = 3;
+    Act x = stream_conv(e, cx, S, e->enc_first, s, fc::Src(), 0, Tc, n, final);
+    for (auto& St : e->enc_stages) {
+        Act sc, b3;
+        fc::Src a0 = src_of(x), a1;
+        stream_resblocks(e, cx, S, St, &a0, &a1, x.T, n, &sc, &b3);
+        x = stream_conv(e, cx, S, St.resample, a0, a1, 1, x.T, n, final);
+    }
+    if (e->enc_lstm.H) {
+        Act y = run_lstm_stream(e, cx, e->enc_lstm, x, x.T, S->state + S->enc_lstm_off);
+        return stream_conv(e, cx, S, e->enc_last, src_of(y), e->arch.lstm_skip ? src_of(x) : fc::Src(), 1, x.T, n, final);
+    }
+    return stream_conv(e, cx, S, e->enc_last, src_of(x), fc::Src(), 1, x.T, n, final);
+}
+
+// SEANetDecoder.forward on the chunk z [B][D][Tfc]: Tfc * hop samples, no look-ahead (causal unpad1d trims on the right only)
+Act run_decoder_stream(fc_engine* e, Ctx& cx, const fc_stream* S, int n, const float* z_bdt, int Tfc) {
+    fc::Src s; s.ptr = z_bdt; s.used = 1;
+    Act x = stream_conv(e, cx, S, e->dec_first, s, fc::Src(), 0, Tfc, n, false);
+    fc::Src a0 = src_of(x), a1;
+    if (e->dec_lstm.H) {
+        Act y = run_lstm_stream(e, cx, e->dec_lstm, x, x.T, S->state + S->dec_lstm_off);
+        a0 = src_of(y);
+        if (e->arch.lstm_skip) a1 = src_of(x);
+    }
+    int T = Tfc;
+    for (auto& St : e->dec_stages) {
+        Act up = stream_conv(e, cx, S, St.resample, a0, a1, 1, T, n, false);
+        Act sc, b3;
+        a0 = src_of(up); a1 = fc::Src();
+        stream_resblocks(e, cx, S, St, &a0, &a1, up.T, n, &sc, &b3);
+        T = up.T;
+    }
+    return stream_conv(e, cx, S, e->dec_last, a0, a1, 1, T, n, false);
+}
+
+// n: pushes this side of the session has taken before this one (0 = the first push of an utterance)
+int stream_encode_pass(const fc_stream* S, Ctx& cx, int n, const float* wav, int Tc, bool final, int64_t* codes, float* quantized, float* enc_out) {
+    fc_engine* e = S->e;
+    Act last = run_encoder_stream(e, cx, S, n, wav, Tc, final);
+    const int Tfc = final ? frames_for(e, Tc) : Tc / total_hop(e);
+    if (!cx.dry && last.T != Tfc) cx.fail("internal: frame count of a streaming push");
+    return do_quantize(e, cx, last, Tfc, S->n_q, codes, quantized, nullptr, enc_out, nullptr);
+}
+
+int stream_decode_pass(const fc_stream* S, Ctx& cx, int n, const float* z_bdt, int Tfc, int use_scale, float* wav) {
+    fc_engine* e = S->e;
+    Act last = run_decoder_stream(e, cx, S, n, z_bdt, Tfc);
+    const int C = e->audio_ch();
+    cx.launch("combine", "", [&] {
+        return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, use_scale ? S->state : nullptr, cx.B, C, last.T, last.T, wav, (long long)C * last.T,
+                                  last.T, 1, cx.st);
+    });
+    return cx.err;
+}
+
+int stream_ready(fc_stream* S) {
+    if (!S) return fail("null stream");
+    if (S->broken)
+        return fail("a push of this session failed after it had begun to write carries: the utterance's state is invalid until fc_stream_reset");
+    return check_ready(S->e);
+}
+
+int stream_decode_check(fc_stream* S, int Tfc) {
+    if (Tfc <= 0 || Tfc > ceil_div_i(S->max_chunk, total_hop(S->e))) return fail("streaming decode: a push holds 1 .. max_chunk_samples / hop frames");
+    if (S->dec_pushes == 0 && Tfc < S->dec_min_first)
+        return fail("streaming decode: the first push of an utterance must hold at least " + std::to_string(S->dec_min_first) +
+                    " frames (the offline call's reflected left padding spans them); shorter utterances go through the offline call");
+    return 0;
 }
 
 }  // namespace
@@ -2397,6 +2647,153 @@ int fc_debug_conv_layout(int k, int stride, int dil, int CC, int BM, int BN, int
 int fc_debug_timeline(unsigned long long* dst) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(fc::debug_timeline(dst));
+    return 0;
+}
+
+// ---- streaming session (include/funcodec_amd.h) ---------------------------------------------------------------------------------
+size_t fc_stream_state_bytes(const fc_engine* ce, int B) {
+    fc_engine* e = const_cast<fc_engine*>(ce);
+    if (!e || B <= 0 || stream_refusal(e)) return 0;
+    fc_stream tmp;
+    stream_layout(e, B, &tmp);
+    return tmp.state_floats * sizeof(float);
+}
+
+int fc_stream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_stream** out) {
+    if (!e || !out) return fail("null argument");
+    if (!e->finalized) return fail("engine not finalized");
+    if (const char* why = stream_refusal(e)) return fail(why);
+    if (B <= 0) return fail("bad batch size");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    std::unique_ptr<fc_stream> S(new fc_stream);
+    S->e = e; S->B = B; S->n_q = n_q; S->max_chunk = max_chunk_samples;
+    stream_layout(e, B, S.get());
+    const int hop = total_hop(e);
+    if (max_chunk_samples < S->enc_min_first || max_chunk_samples < S->dec_min_first * hop)
+        return fail("max_chunk_samples must hold the first push of an utterance: at least " +
+                    std::to_string(std::max(S->enc_min_first, S->dec_min_first * hop)) + " samples for this net");
+    if (!state || ((uintptr_t)state & 15) || state_bytes < S->state_floats * sizeof(float))
+        return fail("stream state: a 16-byte aligned device buffer of fc_stream_state_bytes() bytes");
+    S->state = (float*)state;
+    S->ones.assign(B, 1.f);
+    S->enc_done = true; S->enc_pushes = -1; S->dec_pushes = -1;     // unusable until the first fc_stream_reset
+    *out = S.release();
+    return 0;
+}
+
+void fc_stream_destroy(fc_stream* s) { delete s; }
+
+int fc_stream_min_first(const fc_stream* s, int decode) { return s ? (decode ? s->dec_min_first : s->enc_min_first) : 0; }
+
+size_t fc_stream_workspace_bytes(const fc_stream* S) {
+    if (!S) return 0;
+    fc_engine* e = S->e;
+    const int hop = total_hop(e), D = e->arch.dimension, Tf = ceil_div_i(S->max_chunk, hop);
+    // a first push and a later one stage the same columns: sized as push 0, a final one (the extra padding)
+    Ctx ce = dry_ctx(e, S->B);
+    stream_encode_pass(S, ce, 0, nullptr, S->max_chunk, true, nullptr, nullptr, nullptr);
+    Ctx cd = dry_ctx(e, S->B);
+    cd.alloc<float>((size_t)S->B * std::max(D, e->cdim()) * Tf);
+    if (e->q_proj) { fc::Src qs; qs.used = 1; run_conv(e, cd, e->q_out, qs, fc::Src(), 0, Tf); }
+    stream_decode_pass(S, cd, 0, nullptr, Tf, 1, nullptr);
+    return std::max(ce.off, cd.off) + 4096;
+}
+
+int fc_stream_reset(fc_stream* S, const float* scale, void* stream) {
+    if (!S) return fail("null stream");
+    if (check_ready(S->e)) return 1;                  // a session broken by a failed push is what reset repairs
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(fc::launch_zero_fill(S->state, S->state_floats, st));
+    if (scale) HIP_TRY(hipMemcpyAsync(S->state, scale, (size_t)S->B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(hipMemcpyAsync(S->state, S->ones.data(), (size_t)S->B * sizeof(float), hipMemcpyHostToDevice, st));
+    S->enc_pushes = 0; S->dec_pushes = 0; S->enc_done = false; S->broken = false;
+    return 0;
+}
+
+int fc_stream_encode(fc_stream* S, const float* wav, int Tc, int final, int64_t* codes, float* quantized, float* enc_out, int* n_frames,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (stream_ready(S)) return 1;
+    fc_engine* e = S->e;
+    const int hop = total_hop(e);
+    if (!wav || !codes || !n_frames) return fail("bad argument");
+    if (S->enc_pushes < 0) return fail("streaming encode: fc_stream_reset first");
+    if (S->enc_done) return fail("streaming encode: the utterance took its final push; fc_stream_reset starts the next one");
+    if (Tc < 1 || Tc > S->max_chunk) return fail("streaming encode: a push holds 1 .. max_chunk_samples samples, got " + std::to_string(Tc));
+    if (!final && Tc % hop != 0)
+        return fail("streaming encode: every push but the final one must be a multiple of the hop (" + std::to_string(hop) + " samples), got " +
+                    std::to_string(Tc) + "; it is not padded silently");
+    if (S->enc_pushes == 0 && Tc < S->enc_min_first)
+        return fail("streaming encode: the first push of an utterance must hold at least " + std::to_string(S->enc_min_first) +
+                    " samples (the offline call's reflected left padding spans them); shorter utterances go through the offline call");
+    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
+    S->broken = true;                                   // until the whole push is enqueued: a failure in between leaves mixed carries
+    if (stream_encode_pass(S, cx, S->enc_pushes, wav, Tc, final != 0, codes, quantized, enc_out)) return 1;
+    S->broken = false;
+    *n_frames = final ? frames_for(e, Tc) : Tc / hop;
+    S->enc_pushes++;
+    if (final) S->enc_done = true;
+    return 0;
+}
+
+int fc_stream_decode_emb(fc_stream* S, const float* emb, int Tfc, int use_scale, float* wav, void* workspace, size_t workspace_bytes, void* stream) {
+    if (stream_ready(S)) return 1;
+    fc_engine* e = S->e;
+    if (!emb || !wav) return fail("bad argument");
+    if (S->dec_pushes < 0) return fail("streaming decode: fc_stream_reset first");
+    if (stream_decode_check(S, Tfc)) return 1;
+    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
+    float* z = cx.alloc<float>((size_t)S->B * e->arch.dimension * Tfc);
+    if (cx.err) return 1;
+    HIP_TRY(fc::launch_transpose_btd(emb, S->B, Tfc, e->arch.dimension, z, cx.st));
+    S->broken = true;
+    if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
+    S->broken = false;
+    S->dec_pushes++;
+    return 0;
+}
+
+int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_scale, float* wav, float* emb_out, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (stream_ready(S)) return 1;
+    fc_engine* e = S->e;
+    if (!codes || !wav) return fail("bad argument");
+    if (S->dec_pushes < 0) return fail("streaming decode: fc_stream_reset first");
+    if (stream_decode_check(S, Tfc)) return 1;
+    const int B = S->B, D = e->arch.dimension, Dc = e->cdim();
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
+    float* z = cx.alloc<float>((size_t)B * Dc * Tfc);
+    if (cx.err) return 1;
+    HIP_TRY(fc::launch_rvq_decode(codes, B, Tfc, S->n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st));
+    if (e->q_proj) {       // CostumeQuantizer.decode (costume_quantizer.py:114-119), per frame as in fc_decode_codes
+        fc::Src qs; qs.ptr = z; qs.used = 1;
+        Act qo = run_conv(e, cx, e->q_out, qs, fc::Src(), 0, Tfc);
+        if (cx.err) return 1;
+        if (emb_out) HIP_TRY(fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tfc, Tfc, emb_out, (long long)Tfc * D, 1, D, cx.st));
+        z = qo.raw;
+    }
+    S->broken = true;
+    if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
+    S->broken = false;
+    S->dec_pushes++;
+    return 0;
+}
+
+// Test hook: the SLSTM stage of a push alone (lstm.py:22-28 without the skip), continuing the recurrence the session's encoder
+// (decoder = 0) or decoder (decoder = 1) LSTM state holds, exactly as a push runs it (run_lstm_stream).  x, y dev f32 [B][H][T].
+int fc_stream_lstm_forward(fc_stream* S, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    if (stream_ready(S)) return 1;
+    fc_engine* e = S->e;
+    const LstmBlock& lb = decoder ? e->dec_lstm : e->enc_lstm;
+    if (!x || !y || T <= 0) return fail("bad argument");
+    if (!lb.H) return fail("this net has no LSTM");
+    if (S->enc_pushes < 0) return fail("streaming: fc_stream_reset first");
+    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
+    Act in; in.raw = const_cast<float*>(x); in.C = lb.H; in.T = T;
+    S->broken = true;
+    Act out = run_lstm_stream(e, cx, lb, in, T, S->state + (decoder ? S->dec_lstm_off : S->enc_lstm_off));
+    if (cx.err) return 1;
+    HIP_TRY(hipMemcpyAsync(y, out.raw, (size_t)S->B * lb.H * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st));
+    S->broken = false;
     return 0;
 }
 

@@ -42,6 +42,12 @@ class EncodecMI355X:
     def load_state_dict(self, state, strict: bool = False):
         self.engine.load_state_dict(state)
 
+    def open_stream(self, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None, max_chunk: Optional[int] = None):
+        """A streaming encode / decode session for `batch` utterances of a causal checkpoint (funcodec_amd/stream.py CodecStream):
+        n_q quantisers (default: all), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call."""
+        from .stream import CodecStream
+        return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk)
+
     # -- helpers -------------------------------------------------------------------------------
     def _as_bct(self, speech: torch.Tensor) -> torch.Tensor:
         if speech.dim() == 2:

@@ -1,0 +1,291 @@
+"""Streaming encode / decode for causal checkpoints (``norm: weight_norm, causal: true``) on top of the fc_stream_* calls.
+
+The reference has no streaming implementation (``streaming=`` of ``funcodec/bin/codec_inference.py`` selects a data
+iterator), so the specification is causality itself: pushing an utterance through in chunks gives what the offline call
+(``Encodec.inference_encoding`` / ``inference_decoding``, codec_basic.py:720-836) gives for the whole utterance.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+
+from .engine import EngineError, _on_device, _ptr
+
+
+def stream_refusal(arch) -> Optional[str]:
+    """Why a model of this architecture cannot stream (the configuration key is named), or None."""
+    if arch.model_type != "encodec":
+        return "streaming is not available for model: freq_codec (the STFT frames overlap; time-domain codec only)"
+    if not arch.causal:
+        return "streaming needs encoder_conf.causal / decoder_conf.causal: true (a non-causal net looks ahead at every layer)"
+    if arch.lstm_layers > 0 and arch.seq_model == "transformer":
+        return "streaming is not available for seq_model: transformer (it needs a key / value cache across pushes)"
+    if arch.segment_length is not None:
+        return "streaming is not available with model_conf.segment_dur (segments are normalised and decoded as whole utterances)"
+    if arch.q0_ds_ratio > 1:
+        return "streaming is not available for quantizer_conf.q0_ds_ratio > 1 (the half-rate first stage looks across frame pairs)"
+    return None
+
+
+class CodecStream:
+    """One utterance batch pushed through a causal codec chunk by chunk; obtained from ``EncodecMI355X.open_stream``.
+
+    * ``encode(wav, final=False) -> (codes [n_q,B,Tf], quantized [B,Tf,D])``: every push but the final one is a positive
+      multiple of ``hop`` samples; the final one has any length >= 1.  A push that breaks the rule raises, it is never padded.
+    * ``decode(codes [B,Tf,n_q])`` / ``decode_emb(emb [B,Tf,D]) -> wav [B,C,Tf*hop]``.
+    * ``reset(scale=None)`` starts the next utterance.
+
+    Start-up.  The offline call pads every causal conv on the left by *reflection* (``pad_mode: reflect``, conv.py:82-99,
+    251-253), i.e. with the columns that follow: only there does a frame depend on later input.  The session therefore
+    holds back the first ``min_first_samples`` (encode) / ``min_first_frames`` (decode) of an utterance: pushes shorter than
+    that return empty tensors until enough has arrived, then everything held back comes out at once.  From then on a push
+    of n frames returns n frames that depend on nothing later.  An utterance shorter than the start-up goes through the
+    offline call: ``encode(..., final=True)`` raises for it, and so does ``decode(..., final=True)``; without ``final`` a decode
+    session cannot know that the utterance has ended and keeps returning empty tensors while it gathers.  A push that fails
+    half-way (an error from the library) invalidates the utterance: every later call raises until ``reset``.
+
+    Volume scale.  ``audio_normalize`` derives its scale from the whole utterance (codec_basic.py:366-371), which no
+    stream can know: the session takes one scale per utterance (``scale`` [B], default 1); encode divides by it and decode
+    multiplies by it when ``use_scale`` is set, as the offline ``use_scale`` does.  Feeding the offline call's scale
+    reproduces the offline result; a running volume estimate is not implemented.
+    """
+
+    def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
+                 max_chunk: Optional[int] = None):
+        why = stream_refusal(model.arch)
+        if why:
+            raise EngineError(why)
+        self.model, self.engine, self.arch = model, model.engine, model.arch
+        eng = self.engine
+        self.lib, self.device = eng.lib, eng.device
+        self.batch = int(batch)
+        self.n_q = int(n_q) if n_q is not None else self.arch.num_quantizers
+        self.hop = eng.hop_length
+        self._h = None
+        self._open(max_chunk)
+        self.reset(scale)
+
+    @_on_device
+    def _open(self, max_chunk):
+        eng = self.engine
+        nbytes = int(self.lib.fc_stream_state_bytes(eng._h, self.batch))
+        if nbytes == 0:
+            raise EngineError("this engine cannot stream")
+        #: everything the session carries between pushes (fc_stream_state_bytes): one allocation, nothing else is kept on the device
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.max_chunk = int(max_chunk) if max_chunk is not None else 100 * self.hop
+        h = C.c_void_p()
+        eng._check(self.lib.fc_stream_create(eng._h, self.batch, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
+        self._h = h
+        self.min_first_samples = int(self.lib.fc_stream_min_first(h, 0))
+        self.min_first_frames = int(self.lib.fc_stream_min_first(h, 1))
+        self._ws_bytes = int(self.lib.fc_stream_workspace_bytes(h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self.lib.fc_stream_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _ws(self) -> torch.Tensor:
+        # the engine's own scratch buffer: sessions and offline calls keep nothing in it between calls
+        eng = self.engine
+        if eng._ws is None or eng._ws.numel() < self._ws_bytes:
+            eng._ws = None
+            eng._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+        return eng._ws
+
+    @_on_device
+    def reset(self, scale: Optional[torch.Tensor] = None) -> None:
+        sc = None
+        if scale is not None:
+            sc = self.engine._dev(torch.as_tensor(scale).reshape(-1), torch.float32)
+            if sc.numel() != self.batch:
+                raise EngineError(f"scale must hold one value per utterance ({self.batch}), got {sc.numel()}")
+        self.engine._check(self.lib.fc_stream_reset(self._h, _ptr(sc), self.engine._stream()))
+        self._enc_head, self._dec_head = [], []       # pushes held back until the start-up length has arrived
+        self._enc_started = self._dec_started = False
+
+    # -- encode --------------------------------------------------------------------------------
+    def _encode_call(self, wav: torch.Tensor, final: bool, want_enc_out: bool = False):
+        B, T = wav.shape[0], wav.shape[-1]
+        Tf, D = self.engine.frames(T), self.arch.dimension
+        codes = torch.empty((self.n_q, B, Tf), dtype=torch.int64, device=self.device)
+        quant = torch.empty((B, Tf, D), dtype=torch.float32, device=self.device)
+        enc = torch.empty((B, Tf, D), dtype=torch.float32, device=self.device) if (self.arch.bypass_quantizer or want_enc_out) else None
+        n = C.c_int(0)
+        ws = self._ws()
+        self.engine._check(self.lib.fc_stream_encode(self._h, _ptr(wav), T, int(final), _ptr(codes), _ptr(quant), _ptr(enc), C.byref(n),
+                                                     _ptr(ws), ws.numel(), self.engine._stream()))
+        assert n.value == Tf
+        if self.arch.bypass_quantizer:         # codec_basic.py:700-701: the encoder output in place of the quantised embeddings
+            return torch.zeros((B, Tf), dtype=torch.long, device=self.device), enc, enc
+        return codes, quant, enc
+
+    @_on_device
+    def encode(self, wav: torch.Tensor, final: bool = False, want_enc_out: bool = False) -> Tuple[torch.Tensor, ...]:
+        """wav [B,T] or [B,C,T] -> (codes [n_q,B,Tf], quantized [B,Tf,D]), plus the encoder output [B,Tf,D] when want_enc_out"""
+        wav = self.engine._wav_in(wav)
+        if wav.dim() == 2:
+            wav = wav.unsqueeze(1)
+        if wav.shape[0] != self.batch:
+            raise EngineError(f"this session streams {self.batch} utterances, got {wav.shape[0]}")
+        T = wav.shape[-1]
+        if T < 1 or (not final and T % self.hop != 0):
+            raise EngineError(f"streaming encode: every push but the final one must be a positive multiple of the hop ({self.hop} samples), "
+                              f"got {T}; it is not padded silently")
+        if not self._enc_started:
+            self._enc_head.append(wav)
+            have = sum(w.shape[-1] for w in self._enc_head)
+            if have < self.min_first_samples and not final:
+                D = self.arch.dimension
+                empty = (self.n_q, self.batch, 0) if not self.arch.bypass_quantizer else (self.batch, 0)
+                none = torch.empty((self.batch, 0, D), device=self.device)
+                return (torch.empty(empty, dtype=torch.int64, device=self.device), none) + ((none,) if want_enc_out else ())
+            wav = torch.cat(self._enc_head, -1).contiguous() if len(self._enc_head) > 1 else wav
+            self._enc_head, self._enc_started = [], True
+            T = wav.shape[-1]
+        # longer than a call takes: whole-hop pieces, the rest (with the final flag) last
+        step = self.max_chunk // self.hop * self.hop
+        outs, pos = [], 0
+        while pos < T:
+            n = T - pos if T - pos <= self.max_chunk else step
+            outs.append(self._encode_call(wav[..., pos:pos + n].contiguous(), final and pos + n == T, want_enc_out))
+            pos += n
+        res = (torch.cat([o[0] for o in outs], -1), torch.cat([o[1] for o in outs], 1))
+        return res + ((torch.cat([o[2] for o in outs], 1),) if want_enc_out else ())
+
+    # -- decode --------------------------------------------------------------------------------
+    def _decode_pushes(self, x: torch.Tensor, final: bool, call) -> torch.Tensor:
+        if x.shape[0] != self.batch:
+            raise EngineError(f"this session streams {self.batch} utterances, got {x.shape[0]}")
+        if not self._dec_started:
+            self._dec_head.append(x)
+            have = sum(t.shape[1] for t in self._dec_head)
+            if have < self.min_first_frames:
+                if final:
+                    raise EngineError(f"streaming decode: the utterance ends after {have} frames, fewer than the {self.min_first_frames} the "
+                                      "first push must hold (the offline call's reflected left padding spans them); decode it with the offline call")
+                return torch.empty((self.batch, self.engine.channels, 0), dtype=torch.float32, device=self.device)
+            x = torch.cat(self._dec_head, 1).contiguous() if len(self._dec_head) > 1 else x
+            self._dec_head, self._dec_started = [], True
+        step = self.max_chunk // self.hop
+        outs = []
+        for pos in range(0, x.shape[1], step):
+            part = x[:, pos:pos + step].contiguous()
+            wav = torch.empty((self.batch, self.engine.channels, part.shape[1] * self.hop), dtype=torch.float32, device=self.device)
+            ws = self._ws()
+            self.engine._check(call(part, wav, ws))
+            outs.append(wav)
+        return outs[0] if len(outs) == 1 else torch.cat(outs, -1)
+
+    @_on_device
+    def decode(self, codes: torch.Tensor, use_scale: bool = True, final: bool = False) -> torch.Tensor:
+        """codes [B,Tf,n_q] (the reference's token layout) -> wav [B,C,Tf*hop].  final=True says the utterance ends here: it changes no
+        sample (the decoder has no right padding) but raises if frames are still held back, instead of returning nothing for ever."""
+        codes = self.engine._dev(codes, torch.int64)
+        if codes.dim() != 3 or codes.shape[2] != self.n_q:
+            raise EngineError(f"codes must be [B,Tf,{self.n_q}], got {tuple(codes.shape)}")
+        return self._decode_pushes(codes, final, lambda part, wav, ws: self.lib.fc_stream_decode_codes(
+            self._h, _ptr(part), part.shape[1], int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(), self.engine._stream()))
+
+    @_on_device
+    def decode_emb(self, emb: torch.Tensor, use_scale: bool = True, final: bool = False) -> torch.Tensor:
+        """emb [B,Tf,D] -> wav [B,C,Tf*hop]; final as in decode"""
+        emb = self.engine._dev(emb, torch.float32)
+        if emb.dim() != 3 or emb.shape[2] != self.arch.dimension:
+            raise EngineError(f"emb must be [B,Tf,{self.arch.dimension}], got {tuple(emb.shape)}")
+        return self._decode_pushes(emb, final, lambda part, wav, ws: self.lib.fc_stream_decode_emb(
+            self._h, _ptr(part), part.shape[1], int(use_scale), _ptr(wav), _ptr(ws), ws.numel(), self.engine._stream()))
+
+    @_on_device
+    def lstm_forward(self, x: torch.Tensor, decoder: bool = False) -> torch.Tensor:
+        """Test hook (fc_stream_lstm_forward): the SLSTM stage of a push alone, without the res_seq skip, on the session's encoder /
+        decoder LSTM state: x [B,H,T] -> [B,H,T]; consecutive calls continue one recurrence."""
+        x = self.engine._dev(x, torch.float32)
+        B, H, T = x.shape
+        if B != self.batch or H != self.arch.bottleneck_channels:
+            raise EngineError(f"lstm_forward: x must be [{self.batch},{self.arch.bottleneck_channels},T], got {tuple(x.shape)}")
+        y = torch.empty_like(x)
+        need = 4 * (T * B * 4 * H + 2 * B * H * T) + (1 << 20)
+        eng = self.engine
+        if eng._ws is None or eng._ws.numel() < need:
+            eng._ws = None
+            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = eng._ws
+        eng._check(self.lib.fc_stream_lstm_forward(self._h, int(decoder), _ptr(x), T, _ptr(y), _ptr(ws), ws.numel(), eng._stream()))
+        return y
+
+
+# ---- the per-layer geometry of a push, restated in Python (tests/test_stream_host.py checks it against torch) ------------------
+def conv_layers(arch):
+    """Every conv of the 1-D encoder and decoder that carries a left context, in execution order:
+    dicts(side, kind 'conv' | 'convtr', cin, cout, k, stride, dil, carry = columns carried,
+    columns of its input per codec frame = cols_per_frame).  Mirrors the engine's plan (SEANetEncoder / SEANetDecoder, seanet_encoder.py:109-160,
+    seanet_decoder.py:111-164)."""
+    nf, out = arch.n_filters, []
+    hop = 1
+    for r in arch.ratios:
+        hop *= r
+    cpf = {"encoder": hop, "decoder": 1}          # columns of the next layer's input per codec frame
+
+    def conv(side, cin, cout, k, stride=1, dil=1, tr=False):
+        carry = 1 if tr else (k - 1) * dil - (stride - 1)
+        out.append(dict(side=side, kind="convtr" if tr else "conv", cin=cin, cout=cout, k=k, stride=stride, dil=dil, carry=carry,
+                        cols_per_frame=cpf[side]))
+        cpf[side] = cpf[side] * stride if tr else cpf[side] // stride
+
+    ch = arch.input_channels if arch.input_channels == 2 else 1
+    mult = 1
+    conv("encoder", ch, nf, arch.kernel_size)
+    for ratio in reversed(list(arch.ratios)):
+        c = mult * nf
+        for j in range(arch.n_residual_layers):
+            conv("encoder", c, c // arch.compress, arch.residual_kernel_size, 1, arch.dilation_base ** j)
+        conv("encoder", c, 2 * c, 2 * ratio, ratio)
+        mult *= 2
+    conv("encoder", mult * nf, arch.dimension, arch.last_kernel_size)
+    conv("decoder", arch.dimension, mult * nf, arch.kernel_size)
+    for ratio in arch.ratios:
+        c = mult * nf
+        conv("decoder", c, c // 2, 2 * ratio, ratio, tr=True)
+        for j in range(arch.n_residual_layers):
+            conv("decoder", c // 2, c // 2 // arch.compress, arch.residual_kernel_size, 1, arch.dilation_base ** j)
+        mult //= 2
+    conv("decoder", nf, ch, arch.last_kernel_size)
+    return out
+
+
+def extra_padding(length: int, k: int, stride: int, padding_total: int) -> int:
+    """get_extra_padding_for_conv1d (conv.py:57-64) in integers"""
+    num = length - k + padding_total
+    n_frames_ceil = -((-num) // stride) + 1
+    return (n_frames_ceil - 1) * stride + (k - padding_total) - length
+
+
+def chunk_geometry(layer, tc: int, final: bool):
+    """(staged columns, output columns) of one push of tc input columns through `layer`: the conv runs without padding over
+    [carry | chunk | extra], extra only at the final push."""
+    if layer["kind"] == "convtr":
+        return 1 + tc, tc * layer["stride"]
+    pt = layer["carry"]
+    extra = extra_padding(tc, layer["k"], layer["stride"], pt) if final else 0
+    tp = pt + tc + extra
+    return tp, (tp - ((layer["k"] - 1) * layer["dil"] + 1)) // layer["stride"] + 1
+
+
+def min_first(arch):
+    """(samples, frames): the shortest first push of an utterance for encode / decode (every layer's chunk must hold the reflected
+    left padding of the offline call, carry + 1 columns); what fc_stream_min_first returns."""
+    hop = 1
+    for r in arch.ratios:
+        hop *= r
+    frames = {"encoder": 1, "decoder": 1}
+    for L in conv_layers(arch):
+        if L["kind"] == "conv":                   # a transposed conv starts from a zero column: nothing to hold
+            frames[L["side"]] = max(frames[L["side"]], -(-(L["carry"] + 1) // L["cols_per_frame"]))
+    return frames["encoder"] * hop, frames["decoder"]

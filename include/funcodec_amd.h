@@ -173,6 +173,53 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
 int fc_overlap_add(const float* const* frames, const int* lens, int n_frames, int B, int frame0_len, int stride,
                    int out_len, float* out, void* stream);
 
+/* ---- streaming session (causal time-domain nets: norm weight_norm, causal true) ----------------------------------------
+ * The reference has no streaming implementation (`streaming=` of bin/codec_inference.py selects a data iterator), so the
+ * specification is the offline callable itself: the pushes of one utterance add up to Encodec.inference_encoding
+ * (codec_basic.py:720-764) of their concatenation for fc_stream_encode, and to Encodec.inference_decoding /
+ * inference_decoding_emb (:766-836) of the concatenated codes / embeddings for the two decode calls.
+ *   - every push but the final one is a positive multiple of the hop; the final one (final = 1) has any length >= 1 and takes
+ *     the reference's extra_padding (conv.py:57-64) at every layer; a push that breaks the rule fails, it is never padded;
+ *   - the offline call pads every causal conv on the left by REFLECTION (pad1d, conv.py:82-99,251-253), i.e. with columns
+ *     1..padding_total of the layer's own input: the first push of an utterance must therefore hold fc_stream_min_first
+ *     samples (encode) / frames (decode); from then on a frame's codes and samples depend on nothing that comes later;
+ *   - the volume scale of audio_normalize (codec_basic.py:366-371) is a function of the whole utterance, which no stream
+ *     knows: the session takes one scale per utterance at reset (NULL = 1), encode divides by it, decode multiplies by it
+ *     when use_scale is set (:406-407);
+ *   - everything carried between pushes (per conv the last padding_total input columns, one input column per transposed
+ *     conv, the LSTMs' (h, c), the scale) lives in ONE caller-owned device buffer of fc_stream_state_bytes bytes, 16-byte
+ *     aligned; nothing is allocated per push; encoder and decoder state are separate, so one session may do both;
+ *   - refused at create, the key named in the message: non-causal nets, seq_model transformer, model freq_codec,
+ *     quantizer_conf.q0_ds_ratio > 1.  Segmented mode (model_conf.segment_dur) is not a property of the engine -- fc_arch has no
+ *     such field, the segments are a host-side loop over offline calls -- so only the host session can refuse it, and does.
+ * Calls on one engine, its sessions included, are serialised by the caller; sessions do not disturb each other or the
+ * offline calls. */
+typedef struct fc_stream fc_stream;
+size_t fc_stream_state_bytes(const fc_engine* e, int B);       /* 0: this engine cannot stream */
+int  fc_stream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, void* state /* dev */, size_t state_bytes, fc_stream** out);
+void fc_stream_destroy(fc_stream* s);
+/* shortest first push of an utterance: samples, a multiple of the hop (decode = 0) or frames (decode = 1) */
+int  fc_stream_min_first(const fc_stream* s, int decode);
+/* device scratch of any push of this session (tail slack included, as fc_engine_workspace_bytes) */
+size_t fc_stream_workspace_bytes(const fc_stream* s);
+/* starts an utterance: clears the state; scale dev f32 [B] or NULL.  Required before the first push. */
+int  fc_stream_reset(fc_stream* s, const float* scale, void* stream);
+/*   wav dev f32 [B][C][Tc];  codes dev i64 [n_q][B][*n_frames];  quantized, enc_out dev f32 [B][*n_frames][D] or NULL
+ *   *n_frames (host) = Tc / hop, or ceil at every encoder stride for the final push (= fc_engine_frames(Tc)) */
+int  fc_stream_encode(fc_stream* s, const float* wav, int Tc, int final, int64_t* codes, float* quantized, float* enc_out, int* n_frames,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/*   codes dev i64 [B][Tfc][n_q] (n_q of create);  emb dev f32 [B][Tfc][D];  wav dev f32 [B][C][Tfc * hop];  emb_out as fc_decode_codes */
+int  fc_stream_decode_codes(fc_stream* s, const int64_t* codes, int Tfc, int use_scale, float* wav, float* emb_out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int  fc_stream_decode_emb(fc_stream* s, const float* emb, int Tfc, int use_scale, float* wav,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* A push that fails after it has begun (workspace too small, a launch error) leaves carries half written: every later call of
+ * the session fails with a message until fc_stream_reset.  Size the workspace with fc_stream_workspace_bytes to rule the first out.
+ * Test hook: the SLSTM stage of a push alone (lstm.py:22-28 without the res_seq skip) on the session's encoder (decoder = 0) or
+ * decoder (decoder = 1) LSTM state: x, y dev f32 [B][H][T]; consecutive calls continue one recurrence, as consecutive pushes do. */
+int  fc_stream_lstm_forward(fc_stream* s, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Deferred device-side failures.  Kernels cannot return a status, so two conditions are recorded in host-visible
  * status words and reported by the NEXT fc_* compute call on the engine (non-zero return, message in fc_last_error(),
  * condition cleared) or by this call.  *flags (may be NULL) receives the conditions pending at entry:

@@ -283,6 +283,49 @@ Ctx dry_ctx(fc_engine* e, int B) {
 template <typename T>
 T* at(T* p, long long off) { return p ? p + off : nullptr; }
 
+// ---- the time-domain SEANet's layer order, stated once (nn.Sequential order: seanet_encoder.py:109-160, seanet_decoder.py:111-164).
+// The plan's contract, the weight packing, the streaming state layout and the forward walk (run_encoder / run_decoder) all follow it.
+enum class Role { First, Shortcut, Block1, Block3, Resample, Last };
+// a causal conv with k > 1 looks at columns to its left, which a streaming push must carry; the k = 1 convs of a block are pointwise
+inline bool carries_context(Role r) { return r != Role::Shortcut && r != Role::Block3; }
+
+struct ConvVisit {
+    ConvLayer& L;
+    bool dec;                     // decoder side
+    Role role;
+    int rate;                     // columns of L's input: one per `rate` encoder input samples / `rate` per decoder frame
+    fc_engine::ResBlock* block;   // the residual block of a Shortcut / Block1 / Block3 layer, else null
+};
+
+// every conv of the 1-D nets in execution order.  The bottleneck sequence model sits in front of the encoder's Last and behind the
+// decoder's First.
+template <typename F>
+void for_each_conv(fc_engine* e, F&& f) {
+    auto blocks = [&](fc_engine::Stage& S, bool dec, int rate) {
+        for (auto& R : S.res) {
+            f(ConvVisit{R.shortcut, dec, Role::Shortcut, rate, &R});
+            f(ConvVisit{R.block1, dec, Role::Block1, rate, &R});
+            f(ConvVisit{R.block3, dec, Role::Block3, rate, &R});
+        }
+    };
+    int div = 1;
+    f(ConvVisit{e->enc_first, false, Role::First, div, nullptr});
+    for (auto& S : e->enc_stages) {
+        blocks(S, false, div);
+        f(ConvVisit{S.resample, false, Role::Resample, div, nullptr});
+        div *= S.resample.stride;
+    }
+    f(ConvVisit{e->enc_last, false, Role::Last, div, nullptr});
+    int mul = 1;
+    f(ConvVisit{e->dec_first, true, Role::First, mul, nullptr});
+    for (auto& S : e->dec_stages) {
+        f(ConvVisit{S.resample, true, Role::Resample, mul, nullptr});
+        mul *= S.resample.stride;
+        blocks(S, true, mul);
+    }
+    f(ConvVisit{e->dec_last, true, Role::Last, mul, nullptr});
+}
+
 // ---- plan construction (mirrors nn.Sequential indices: seanet_encoder.py:109-160, seanet_decoder.py:111-164)
 void add_conv_expect(fc_engine* e, ConvLayer& L) {
     const std::string inner = L.transposed ? ".convtr" : ".conv";
@@ -418,6 +461,22 @@ void add_tf_expect(fc_engine* e, TfBlock& tb) {
     e->tf_by_prefix[tb.prefix] = &tb;
 }
 
+// SLSTM's checkpoint contract (torch.nn.LSTM names), and the input projection of every layer as a k = 1 GEMM
+void add_lstm_expect(fc_engine* e, LstmBlock& lb) {
+    if (lb.H == 0) return;
+    lb.layers.resize(e->arch.lstm_layers);
+    for (int l = 0; l < e->arch.lstm_layers; ++l) {
+        const std::string sfx = "_l" + std::to_string(l);
+        lb.layers[l].inproj = mk_conv(lb.prefix + ".inproj" + sfx, lb.H, 4 * lb.H, 1, 1, false, false, true);
+        lb.layers[l].inproj.has_norm = false;
+        e->expected.push_back({lb.prefix + ".weight_ih" + sfx, {4 * lb.H, lb.H}});
+        e->expected.push_back({lb.prefix + ".weight_hh" + sfx, {4 * lb.H, lb.H}});
+        e->expected.push_back({lb.prefix + ".bias_ih" + sfx, {4 * lb.H}});
+        e->expected.push_back({lb.prefix + ".bias_hh" + sfx, {4 * lb.H}});
+    }
+    e->lstm_by_prefix[lb.prefix] = &lb;
+}
+
 void build_plan_2d(fc_engine* e) {
     const fc_arch& a = e->arch;
     const int nf = a.n_filters, nres = a.n_residual_layers;
@@ -508,25 +567,11 @@ void build_plan_2d(fc_engine* e) {
         for (auto& R : S.res) { add_conv2d_expect(e, R.block1); add_conv2d_expect(e, R.block3); add_conv2d_expect(e, R.shortcut); }
         add_conv2d_expect(e, S.resample);
     }
-    auto add_lstm = [&](LstmBlock& lb) {
-        if (lb.H == 0) return;
-        lb.layers.resize(a.lstm_layers);
-        for (int l = 0; l < a.lstm_layers; ++l) {
-            const std::string sfx = "_l" + std::to_string(l);
-            lb.layers[l].inproj = mk_conv(lb.prefix + ".inproj" + sfx, lb.H, 4 * lb.H, 1, 1, false, false, true);
-            lb.layers[l].inproj.has_norm = false;
-            e->expected.push_back({lb.prefix + ".weight_ih" + sfx, {4 * lb.H, lb.H}});
-            e->expected.push_back({lb.prefix + ".weight_hh" + sfx, {4 * lb.H, lb.H}});
-            e->expected.push_back({lb.prefix + ".bias_ih" + sfx, {4 * lb.H}});
-            e->expected.push_back({lb.prefix + ".bias_hh" + sfx, {4 * lb.H}});
-        }
-        e->lstm_by_prefix[lb.prefix] = &lb;
-    };
-    add_lstm(e->enc_lstm);
+    add_lstm_expect(e, e->enc_lstm);
     add_tf_expect(e, e->enc_tf);
     add_conv_expect(e, e->enc_last);
     add_conv_expect(e, e->dec_first);
-    add_lstm(e->dec_lstm);
+    add_lstm_expect(e, e->dec_lstm);
     add_tf_expect(e, e->dec_tf);
     for (auto& S : e->dec_stages) {
         const int opg_t = S.resample.cout / (S.resample.groups > 0 ? S.resample.groups : 1);
@@ -624,57 +669,20 @@ void build_plan(fc_engine* e) {
     idx++;
     e->dec_last = mk_conv(name("decoder", idx, ".conv"), nf, e->audio_ch(), a.last_kernel_size, 1, false, true);
 
-    // ---- conv wrapper flavour of every SConv1d / SConvTranspose1d of the nets (conv.py:20-56)
-    {
-        std::vector<ConvLayer*> all = {&e->enc_first, &e->enc_last, &e->dec_first, &e->dec_last};
-        for (auto* st : {&e->enc_stages, &e->dec_stages})
-            for (auto& S : *st) {
-                for (auto& R : S.res) { all.push_back(&R.shortcut); all.push_back(&R.block1); all.push_back(&R.block3); }
-                all.push_back(&S.resample);
-            }
-        for (ConvLayer* L : all) {
-            L->has_norm = a.norm_type == 0;
-            L->wnorm = a.norm_type == 1;
-            L->causal = a.causal != 0;
+    // ---- per layer: the conv wrapper flavour of its SConv1d / SConvTranspose1d (conv.py:20-56) and its part of the checkpoint
+    // contract, in execution order, the sequence models' tensors where they sit between the convs
+    for_each_conv(e, [&](const ConvVisit& v) {
+        v.L.has_norm = a.norm_type == 0;
+        v.L.wnorm = a.norm_type == 1;
+        v.L.causal = a.causal != 0;
+        if (v.role == Role::Shortcut) {
+            const std::string& sp = v.L.prefix;                          // "<side>.model.<i>.shortcut.conv"
+            e->res_by_prefix[sp.substr(0, sp.size() - std::string(".shortcut.conv").size())] = v.block;
         }
-    }
-    for (auto* stg : {&e->enc_stages, &e->dec_stages})
-        for (auto& S : *stg)
-            for (auto& R : S.res) {
-                const std::string& sp = R.shortcut.prefix;               // "<side>.model.<i>.shortcut.conv"
-                e->res_by_prefix[sp.substr(0, sp.size() - std::string(".shortcut.conv").size())] = &R;
-            }
-    // ---- checkpoint contract, in execution order
-    add_conv_expect(e, e->enc_first);
-    for (auto& S : e->enc_stages) {
-        for (auto& R : S.res) { add_conv_expect(e, R.shortcut); add_conv_expect(e, R.block1); add_conv_expect(e, R.block3); }
-        add_conv_expect(e, S.resample);
-    }
-    auto add_lstm = [&](LstmBlock& lb) {
-        if (lb.H == 0) return;
-        lb.layers.resize(a.lstm_layers);
-        for (int l = 0; l < a.lstm_layers; ++l) {
-            const std::string sfx = "_l" + std::to_string(l);
-            lb.layers[l].inproj = mk_conv(lb.prefix + ".inproj" + sfx, lb.H, 4 * lb.H, 1, 1, false, false, true);
-            lb.layers[l].inproj.has_norm = false;
-            e->expected.push_back({lb.prefix + ".weight_ih" + sfx, {4 * lb.H, lb.H}});
-            e->expected.push_back({lb.prefix + ".weight_hh" + sfx, {4 * lb.H, lb.H}});
-            e->expected.push_back({lb.prefix + ".bias_ih" + sfx, {4 * lb.H}});
-            e->expected.push_back({lb.prefix + ".bias_hh" + sfx, {4 * lb.H}});
-        }
-        e->lstm_by_prefix[lb.prefix] = &lb;
-    };
-    add_lstm(e->enc_lstm);
-    add_tf_expect(e, e->enc_tf);
-    add_conv_expect(e, e->enc_last);
-    add_conv_expect(e, e->dec_first);
-    add_lstm(e->dec_lstm);
-    add_tf_expect(e, e->dec_tf);
-    for (auto& S : e->dec_stages) {
-        add_conv_expect(e, S.resample);
-        for (auto& R : S.res) { add_conv_expect(e, R.shortcut); add_conv_expect(e, R.block1); add_conv_expect(e, R.block3); }
-    }
-    add_conv_expect(e, e->dec_last);
+        if (!v.dec && v.role == Role::Last) { add_lstm_expect(e, e->enc_lstm); add_tf_expect(e, e->enc_tf); }
+        add_conv_expect(e, v.L);
+        if (v.dec && v.role == Role::First) { add_lstm_expect(e, e->dec_lstm); add_tf_expect(e, e->dec_tf); }
+    });
     add_quantizer_expect(e);
 }
 
@@ -1182,19 +1190,23 @@ inline fc::Src src_of(const Act& a) { fc::Src s; s.ptr = a.raw; s.aff = a.aff; s
 
 // SLSTM.forward (lstm.py:22-28) without the skip; returns plain y [B][H][T].
 // Layer wavefront: one launch per "diagonal" s advances every layer l by its timestep s - l.
-Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T) {
+// `carried` (a streaming push; null offline): the per-step kernel's (h, c) buffers inside the session state, which continue the recurrence
+// of the earlier pushes instead of starting from a cleared workspace buffer.  h_l(t) sits at parity t & 1 and step 0 reads parity 1, so
+// after an odd number of steps the last hidden state is copied to where the next push looks for it.
+Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, float* carried = nullptr) {
     const int H = lb.H, B = cx.B, L = (int)lb.layers.size();
     float* xproj = cx.alloc<float>((size_t)T * B * 4 * H);
     run_conv(e, cx, lb.layers[0].inproj, src_of(in), fc::Src(), 0, T, xproj, (long long)4 * H, 1, (long long)B * 4 * H);
     static const int persist_env = fc::deploy_switch("FC_LSTM_PERSIST", 1);
     bool persist = false;
-    if (persist_env && e->lstm_persist_ok) {
+    if (!carried && persist_env && e->lstm_persist_ok) {      // the persistent kernel keeps its state to itself: offline only
         const int key = B * 4096 + H;            // the occupancy query is cached per (B, H)
         if (e->persist_checked_B != key) { e->persist_checked_val = fc::lstm_persist_supported(B, H, L, e->device); e->persist_checked_B = key; }
         persist = e->persist_checked_val;
     }
     // persistent kernel: barrier words + hidden-state history; per-step launches: h [L][2][B][H], c [L][B][H]
-    float* state = cx.alloc<float>(persist ? fc::lstm_persist_state_floats(B, H, T) : (size_t)3 * L * B * H);
+    const size_t BH = (size_t)B * H;
+    float* state = carried ? carried : cx.alloc<float>(persist ? fc::lstm_persist_state_floats(B, H, T) : 3 * L * BH);
     Act y;
     y.C = H; y.T = T;
     y.raw = cx.alloc<float>((size_t)B * H * T);
@@ -1208,14 +1220,20 @@ Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T) {
     for (int l = 0; l < L; ++l) { w[l] = l == 0 ? lb.layers[0].whh : lb.layers[l].wcat; bias[l] = lb.layers[l].bperm; }
     const char* pre = lb.prefix.c_str();
     ProfSpan sp(e, cx.st, cx.live(), [&] { return persist ? kLstmPersistClass : kLstmWaveClass; }, fl, by);
-    cx.launch("lstm state clear", pre,
-              [&] { return fc::launch_zero_fill(state, persist ? fc::lstm_persist_clear_floats(B, H) : (size_t)3 * L * B * H, cx.st); });
+    if (!carried)
+        cx.launch("lstm state clear", pre,
+                  [&] { return fc::launch_zero_fill(state, persist ? fc::lstm_persist_clear_floats(B, H) : 3 * L * BH, cx.st); });
     if (persist) {
         cx.launch("lstm", pre, [&] { return fc::launch_lstm_persist(w[0], w[1], bias[1], xproj, state, y.raw, B, H, T, e->status_dev, cx.st); });
     } else {
         for (int s = 0; s < T + L - 1; ++s)
-            cx.launch("lstm step", pre, [&] { return fc::launch_lstm_wave(w, bias, xproj, state, state + (size_t)2 * L * B * H, y.raw, B, H, T, L, s, cx.st); });
+            cx.launch("lstm step", pre, [&] { return fc::launch_lstm_wave(w, bias, xproj, state, state + 2 * L * BH, y.raw, B, H, T, L, s, cx.st); });
     }
+    if (carried && (T & 1))
+        for (int l = 0; l < L; ++l)
+            cx.launch("lstm carry", pre, [&] {
+                return hipMemcpyAsync(state + (size_t)(2 * l + 1) * BH, state + (size_t)(2 * l) * BH, BH * sizeof(float), hipMemcpyDeviceToDevice, cx.st);
+            });
     return y;
 }
 
@@ -1309,58 +1327,80 @@ void run_reshead(fc_engine* e, Ctx& cx, const fc_engine::ResBlock& R, fc::Src a0
     conv_finish(e, cx, R.block1, c.part_b1, nblk, (double)hid * T, b1->aff);
 }
 
-// SEANetResnetBlock (seanet_encoder.py:16-61): returns the two raw branches whose GroupNorm'd sum is the output
+// ---- the forward walk of the time-domain nets: ONE walk for an offline call and for a push of a streaming session.  The two kinds of
+// pass differ in three places and nowhere else: the conv step (walk_conv), the head of a residual block (run_resblocks) and the
+// bottleneck (run_bottleneck).
+struct Pass {
+    const fc_stream* S = nullptr;   // the session of a push; null: an offline call over the whole utterance
+    int n = 0;                      // pushes this side (encoder / decoder) of the session has taken before this one
+    bool final = false;             // the utterance's last encoder push (a decoder push never is)
+};
+
+Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc, int side_pushes, bool final);
+
+// the conv step: in a push, the layers that carry a left context run over [carry | chunk] (stream_conv); the pointwise ones as offline
+Act walk_conv(fc_engine* e, Ctx& cx, const Pass& p, Role role, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T) {
+    if (p.S && carries_context(role)) return stream_conv(e, cx, p.S, L, s0, s1, elu, T, p.n, p.final);
+    return run_conv(e, cx, L, s0, s1, elu, T);
+}
+
+// the bottleneck of one side: the sources of the conv behind it = the sequence model's output (plus its input with lstm_skip), or x itself
+// in a net without one.  A push continues the per-step LSTM on the session's state (stream_refusal: no transformer in a stream).
+void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x, fc::Src* a0, fc::Src* a1) {
+    const LstmBlock& lb = dec ? e->dec_lstm : e->enc_lstm;
+    const TfBlock& tb = dec ? e->dec_tf : e->enc_tf;
+    *a0 = src_of(x); *a1 = fc::Src();
+    if (!has_seq(lb, tb)) return;
+    Act y = p.S ? run_lstm(e, cx, lb, x, x.T, p.S->state + (dec ? p.S->dec_lstm_off : p.S->enc_lstm_off)) : run_seq(e, cx, lb, tb, x, x.T);
+    *a0 = src_of(y);
+    if (e->arch.lstm_skip) *a1 = src_of(x);
+}
+
+// SEANetResnetBlock (seanet_encoder.py:16-61) over the blocks of a stage: returns the two raw branches whose GroupNorm'd sum is the output
 // The block's input is one tensor (first block of a stage) or the pending sum of the previous block's two branches.
-void run_resblocks(fc_engine* e, Ctx& cx, const fc_engine::Stage& S, fc::Src a0, fc::Src a1, int T, Act* sc, Act* b3) {
+void run_resblocks(fc_engine* e, Ctx& cx, const Pass& p, const fc_engine::Stage& S, fc::Src a0, fc::Src a1, int T, Act* sc, Act* b3) {
     for (const auto& R : S.res) {
         Act b1;
-        if (R.fused_head && !a0.div) {
+        if (!p.S && R.fused_head && !a0.div) {      // the fused head has no form that stages a carry
             run_reshead(e, cx, R, a0, a1, T, sc, &b1);
         } else {
-            *sc = run_conv(e, cx, R.shortcut, a0, a1, 0, T);
-            b1 = run_conv(e, cx, R.block1, a0, a1, 1, T);
+            *sc = walk_conv(e, cx, p, Role::Shortcut, R.shortcut, a0, a1, 0, T);
+            b1 = walk_conv(e, cx, p, Role::Block1, R.block1, a0, a1, 1, T);
         }
-        *b3 = run_conv(e, cx, R.block3, src_of(b1), fc::Src(), 1, b1.T);
+        *b3 = walk_conv(e, cx, p, Role::Block3, R.block3, src_of(b1), fc::Src(), 1, b1.T);
         a0 = src_of(*sc); a1 = src_of(*b3);
     }
 }
 
-// SEANetEncoder.forward: wav [B][T] (optionally divided by scale[b]) -> last conv (raw + affine), T -> Tf
-Act run_encoder(fc_engine* e, Ctx& cx, const float* wav, int T, const float* scale) {
-    fc::Src s; s.ptr = wav; s.div = scale; s.used = e->arch.audio_normalize ? 3 : 1;
-    Act x = run_conv(e, cx, e->enc_first, s, fc::Src(), 0, T);
+// SEANetEncoder.forward: wav [B][C][T] (a chunk of it in a push; with the caller's divisor) -> last conv (raw + affine), T -> Tf
+Act run_encoder(fc_engine* e, Ctx& cx, const Pass& p, fc::Src wav, int T) {
+    Act x = walk_conv(e, cx, p, Role::First, e->enc_first, wav, fc::Src(), 0, T);
     for (auto& S : e->enc_stages) {
         Act sc, b3;
-        run_resblocks(e, cx, S, src_of(x), fc::Src(), x.T, &sc, &b3);
-        x = run_conv(e, cx, S.resample, src_of(sc), src_of(b3), 1, sc.T);
+        run_resblocks(e, cx, p, S, src_of(x), fc::Src(), x.T, &sc, &b3);
+        x = walk_conv(e, cx, p, Role::Resample, S.resample, src_of(sc), src_of(b3), 1, sc.T);
     }
-    if (has_seq(e->enc_lstm, e->enc_tf)) {
-        Act y = run_seq(e, cx, e->enc_lstm, e->enc_tf, x, x.T);
-        if (e->arch.lstm_skip) return run_conv(e, cx, e->enc_last, src_of(y), src_of(x), 1, x.T);
-        return run_conv(e, cx, e->enc_last, src_of(y), fc::Src(), 1, x.T);
-    }
-    return run_conv(e, cx, e->enc_last, src_of(x), fc::Src(), 1, x.T);
+    fc::Src a0, a1;
+    run_bottleneck(e, cx, p, false, x, &a0, &a1);
+    return walk_conv(e, cx, p, Role::Last, e->enc_last, a0, a1, 1, x.T);
 }
 
-// SEANetDecoder.forward: z [B][D][Tf] plain -> last conv (raw [B][1][Tf*hop] + affine)
-Act run_decoder(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf) {
+// SEANetDecoder.forward: z [B][D][Tf] plain -> last conv (raw [B][C][Tf*hop] + affine).  A push of Tf frames gives Tf * hop samples
+// without look-ahead (causal unpad1d trims on the right only).
+Act run_decoder(fc_engine* e, Ctx& cx, const Pass& p, const float* z_bdt, int Tf) {
     fc::Src s; s.ptr = z_bdt; s.used = 1;
-    Act x = run_conv(e, cx, e->dec_first, s, fc::Src(), 0, Tf);
-    fc::Src a0 = src_of(x), a1;
-    if (has_seq(e->dec_lstm, e->dec_tf)) {
-        Act y = run_seq(e, cx, e->dec_lstm, e->dec_tf, x, x.T);
-        a0 = src_of(y);
-        if (e->arch.lstm_skip) a1 = src_of(x);
-    }
+    Act x = walk_conv(e, cx, p, Role::First, e->dec_first, s, fc::Src(), 0, Tf);
+    fc::Src a0, a1;
+    run_bottleneck(e, cx, p, true, x, &a0, &a1);
     int T = Tf;
     for (auto& S : e->dec_stages) {
-        Act up = run_conv(e, cx, S.resample, a0, a1, 1, T);
+        Act up = walk_conv(e, cx, p, Role::Resample, S.resample, a0, a1, 1, T);
         Act sc, b3;
-        run_resblocks(e, cx, S, src_of(up), fc::Src(), up.T, &sc, &b3);
+        run_resblocks(e, cx, p, S, src_of(up), fc::Src(), up.T, &sc, &b3);
         a0 = src_of(sc); a1 = src_of(b3);
         T = up.T;
     }
-    return run_conv(e, cx, e->dec_last, a0, a1, 1, T);
+    return walk_conv(e, cx, p, Role::Last, e->dec_last, a0, a1, 1, T);
 }
 
 
@@ -1583,12 +1623,9 @@ Act run_encoder_2d(fc_engine* e, Ctx& cx, const float* wav, int T, const float* 
     if (!cx.dry && x.F != 1) cx.fail("the 2-D encoder must reduce the frequency axis to one bin (n_fft / ratios mismatch)");
     Act x1;                                                                        // ReshapeModule: [B][1][C][T] is [B][C][T]
     x1.raw = x.buf; x1.aff = x.aff; x1.C = x.C; x1.T = x.T; x1.normed = x.normed;
-    if (has_seq(e->enc_lstm, e->enc_tf)) {
-        Act y = run_seq(e, cx, e->enc_lstm, e->enc_tf, x1, x1.T);
-        if (a.lstm_skip) return run_conv(e, cx, e->enc_last, src_of(y), src_of(x1), 1, x1.T);
-        return run_conv(e, cx, e->enc_last, src_of(y), fc::Src(), 1, x1.T);
-    }
-    return run_conv(e, cx, e->enc_last, src_of(x1), fc::Src(), 1, x1.T);
+    fc::Src a0, a1;
+    run_bottleneck(e, cx, Pass(), false, x1, &a0, &a1);
+    return run_conv(e, cx, e->enc_last, a0, a1, 1, x1.T);
 }
 
 // SEANetDecoder2d.forward + FreqCodec._decode_frame (codec_freq.py:409-448, mag_phase): z [B][D][Tf] -> wav [B][out_len]
@@ -1655,7 +1692,8 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
         sc = scale ? scale : cx.alloc<float>(B);
         cx.launch("volume", "", [&] { return fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st); });
     }
-    Act last = e->arch.model_type == 1 ? run_encoder_2d(e, cx, wav, T, sc) : run_encoder(e, cx, wav, T, sc);
+    fc::Src s; s.ptr = wav; s.div = sc; s.used = e->arch.audio_normalize ? 3 : 1;
+    Act last = e->arch.model_type == 1 ? run_encoder_2d(e, cx, wav, T, sc) : run_encoder(e, cx, Pass(), s, T);
     return do_quantize(e, cx, last, Tf, n_q, codes, quantized, sub_quants, enc_out, quant_bdt_out);
 }
 
@@ -1711,7 +1749,7 @@ int do_decode(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* sc
         run_decoder_2d(e, cx, z_bdt, Tf, scale, out_len, wav);
         return cx.err;
     }
-    Act last = run_decoder(e, cx, z_bdt, Tf);
+    Act last = run_decoder(e, cx, Pass(), z_bdt, Tf);
     if (!cx.dry && out_len > last.T) cx.fail("out_len exceeds Tf*hop");
     // final GroupNorm apply (decoder.model.N.conv.norm has C = audio channels), x scale (codec_basic.py:406-407), trim (:711)
     const int C = e->audio_ch();
@@ -1719,6 +1757,23 @@ int do_decode(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* sc
         return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, scale, cx.B, C, last.T, out_len, wav, (long long)C * out_len, out_len, 1, cx.st);
     });
     return cx.err;
+}
+
+// Codes to decoder input (fc_decode_codes, fc_stream_decode_codes): the summed code vectors of `codes` [n_q][B][Tf] into *z [B][Dc][Tf],
+// then CostumeQuantizer.decode's output_proj on them (costume_quantizer.py:114-119).  On return *z is the decoder's input [B][D][Tf];
+// emb_out (optional) gets the embeddings [B][Tf][D].
+int codes_to_decoder_input(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, int n_q, float* emb_out, float** z) {
+    const int B = cx.B, D = e->arch.dimension;
+    if (cx.err) return 1;
+    if (cx.live())
+        HIP_TRY(fc::launch_rvq_decode(codes, B, Tf, n_q, e->cdim(), e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, *z, e->status_dev, cx.st));
+    if (!e->q_proj) return 0;
+    fc::Src qs; qs.ptr = *z; qs.used = 1;
+    Act qo = run_conv(e, cx, e->q_out, qs, fc::Src(), 0, Tf);
+    if (cx.err) return 1;
+    if (emb_out && cx.live()) HIP_TRY(fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, emb_out, (long long)Tf * D, 1, D, cx.st));
+    *z = qo.raw;
+    return 0;
 }
 
 // Deferred device-side failures of EARLIER calls (kernels cannot return a status): reported once, then cleared.
@@ -1757,28 +1812,6 @@ int check_ready(fc_engine* e) {
 // gathers short pushes until it has that much) and stages the reflection instead of a carry there.
 inline int stream_pt(const ConvLayer& L) { return L.transposed ? 1 : (L.k - 1) * L.dil - (L.stride - 1); }
 
-// every conv of the 1-D nets that carries a left context, with the columns of its input per encoder input sample (1 / div) or per
-// decoder frame (mul): f(layer, is_decoder, div_or_mul)
-template <typename F>
-void for_each_stream_conv(fc_engine* e, F&& f) {
-    int div = 1;
-    f(e->enc_first, false, div);
-    for (int s = 0; s < (int)e->enc_stages.size(); ++s) {
-        for (auto& R : e->enc_stages[s].res) f(R.block1, false, div);
-        f(e->enc_stages[s].resample, false, div);
-        div *= e->enc_stages[s].resample.stride;
-    }
-    f(e->enc_last, false, div);
-    int mul = 1;
-    f(e->dec_first, true, mul);
-    for (auto& S : e->dec_stages) {
-        f(S.resample, true, mul);
-        mul *= S.resample.stride;
-        for (auto& R : S.res) f(R.block1, true, mul);
-    }
-    f(e->dec_last, true, mul);
-}
-
 // why this engine cannot stream, or null.  Each reason names the configuration key.
 const char* stream_refusal(const fc_engine* e) {
     const fc_arch& a = e->arch;
@@ -1793,14 +1826,15 @@ void stream_layout(fc_engine* e, int B, fc_stream* S) {
     size_t off = ((size_t)B + 63) & ~(size_t)63;      // scale [B]
     const int hop = total_hop(e);
     int enc_min = hop, dec_min = 1;
-    for_each_stream_conv(e, [&](const ConvLayer& L, bool dec, int rate) {
+    for_each_conv(e, [&](const ConvVisit& v) {
+        const ConvLayer& L = v.L;
         const int pt = stream_pt(L);
-        if (pt <= 0) return;
+        if (!carries_context(v.role) || pt <= 0) return;
         S->carry[&L] = off;
         off += ((size_t)2 * B * L.cin * pt + 63) & ~(size_t)63;
         if (L.transposed) return;                      // zero left context at the start: no reflection to hold
-        if (!dec) enc_min = std::max(enc_min, (pt + 1) * rate);
-        else dec_min = std::max(dec_min, ceil_div_i(pt + 1, rate));
+        if (!v.dec) enc_min = std::max(enc_min, (pt + 1) * v.rate);
+        else dec_min = std::max(dec_min, ceil_div_i(pt + 1, v.rate));
     });
     const size_t L = (size_t)e->arch.lstm_layers;
     S->enc_lstm_off = off; off += 3 * L * B * e->enc_lstm.H;
@@ -1857,86 +1891,11 @@ Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, f
     return out;
 }
 
-// SLSTM.forward (lstm.py:22-28) over a chunk, continuing the recurrence of the earlier pushes: the per-step kernel with its (h, c)
-// buffers inside the session state instead of a cleared workspace buffer.  h_l(t) sits at parity t & 1 and step 0 reads parity 1, so
-// after an odd number of steps the last hidden state is copied to where the next push looks for it.
-Act run_lstm_stream(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, float* st) {
-    const int H = lb.H, B = cx.B, L = (int)lb.layers.size();
-    float* xproj = cx.alloc<float>((size_t)T * B * 4 * H);
-    run_conv(e, cx, lb.layers[0].inproj, src_of(in), fc::Src(), 0, T, xproj, (long long)4 * H, 1, (long long)B * 4 * H);
-    Act y;
-    y.C = H; y.T = T;
-    y.raw = cx.alloc<float>((size_t)B * H * T);
-    const double fl = 2.0 * B * (double)T * 4 * H * H * (2 * L - 1);
-    cx.lstm_flops += fl;
-    const float* w[FC_LSTM_MAX_LAYERS] = {nullptr};
-    const float* bias[FC_LSTM_MAX_LAYERS] = {nullptr};
-    for (int l = 0; l < L; ++l) { w[l] = l == 0 ? lb.layers[0].whh : lb.layers[l].wcat; bias[l] = lb.layers[l].bperm; }
-    const char* pre = lb.prefix.c_str();
-    const size_t BH = (size_t)B * H;
-    ProfSpan sp(e, cx.st, cx.live(), [&] { return kLstmWaveClass; }, fl, 0.0);
-    for (int s = 0; s < T + L - 1; ++s)
-        cx.launch("lstm step", pre, [&] { return fc::launch_lstm_wave(w, bias, xproj, st, st + 2 * L * BH, y.raw, B, H, T, L, s, cx.st); });
-    if (T & 1)
-        for (int l = 0; l < L; ++l)
-            cx.launch("lstm carry", pre, [&] {
-                return hipMemcpyAsync(st + (size_t)(2 * l + 1) * BH, st + (size_t)(2 * l) * BH, BH * sizeof(float), hipMemcpyDeviceToDevice, cx.st);
-            });
-    return y;
-}
-
-// SEANetResnetBlock chain of a stage on a chunk: the k = 1 convs (shortcut, block.3) are pointwise and run as offline; block.1 carries
-void stream_resblocks(fc_engine* e, Ctx& cx, const fc_stream* S, const fc_engine::Stage& St, fc::Src* a0, fc::Src* a1, int T, int pushes, Act* sc, Act* b3) {
-    for (const auto& R : St.res) {
-        *sc = run_conv(e, cx, R.shortcut, *a0, *a1, 0, T);
-        Act b1 = stream_conv(e, cx, S, R.block1, *a0, *a1, 1, T, pushes, false);
-        *b3 = run_conv(e, cx, R.block3, src_of(b1), fc::Src(), 1, b1.T);
-        *a0 = src_of(*sc); *a1 = src_of(*b3);
-    }
-}
-
-// SEANetEncoder.forward on the chunk wav [B][C][Tc] of an utterance whose n earlier chunks the session has seen
-Act run_encoder_stream(fc_engine* e, Ctx& cx, const fc_stream* S, int n, const float* wav, int Tc, bool final) {
-    fc::Src s; s.ptr = wav; s.div = S->state; s.used = 3;
-    Act x = stream_conv(e, cx, S, e->enc_first, s, fc::Src(), 0, Tc, n, final);
-    for (auto& St : e->enc_stages) {
-        Act sc, b3;
-        fc::Src a0 = src_of(x), a1;
-        stream_resblocks(e, cx, S, St, &a0, &a1, x.T, n, &sc, &b3);
-        x = stream_conv(e, cx, S, St.resample, a0, a1, 1, x.T, n, final);
-    }
-    if (e->enc_lstm.H) {
-        Act y = run_lstm_stream(e, cx, e->enc_lstm, x, x.T, S->state + S->enc_lstm_off);
-        return stream_conv(e, cx, S, e->enc_last, src_of(y), e->arch.lstm_skip ? src_of(x) : fc::Src(), 1, x.T, n, final);
-    }
-    return stream_conv(e, cx, S, e->enc_last, src_of(x), fc::Src(), 1, x.T, n, final);
-}
-
-// SEANetDecoder.forward on the chunk z [B][D][Tfc]: Tfc * hop samples, no look-ahead (causal unpad1d trims on the right only)
-Act run_decoder_stream(fc_engine* e, Ctx& cx, const fc_stream* S, int n, const float* z_bdt, int Tfc) {
-    fc::Src s; s.ptr = z_bdt; s.used = 1;
-    Act x = stream_conv(e, cx, S, e->dec_first, s, fc::Src(), 0, Tfc, n, false);
-    fc::Src a0 = src_of(x), a1;
-    if (e->dec_lstm.H) {
-        Act y = run_lstm_stream(e, cx, e->dec_lstm, x, x.T, S->state + S->dec_lstm_off);
-        a0 = src_of(y);
-        if (e->arch.lstm_skip) a1 = src_of(x);
-    }
-    int T = Tfc;
-    for (auto& St : e->dec_stages) {
-        Act up = stream_conv(e, cx, S, St.resample, a0, a1, 1, T, n, false);
-        Act sc, b3;
-        a0 = src_of(up); a1 = fc::Src();
-        stream_resblocks(e, cx, S, St, &a0, &a1, up.T, n, &sc, &b3);
-        T = up.T;
-    }
-    return stream_conv(e, cx, S, e->dec_last, a0, a1, 1, T, n, false);
-}
-
 // n: pushes this side of the session has taken before this one (0 = the first push of an utterance)
 int stream_encode_pass(const fc_stream* S, Ctx& cx, int n, const float* wav, int Tc, bool final, int64_t* codes, float* quantized, float* enc_out) {
     fc_engine* e = S->e;
-    Act last = run_encoder_stream(e, cx, S, n, wav, Tc, final);
+    fc::Src s; s.ptr = wav; s.div = S->state; s.used = 3;       // the session's scale [B] (ones when reset gave none)
+    Act last = run_encoder(e, cx, Pass{S, n, final}, s, Tc);
     const int Tfc = final ? frames_for(e, Tc) : Tc / total_hop(e);
     if (!cx.dry && last.T != Tfc) cx.fail("internal: frame count of a streaming push");
     return do_quantize(e, cx, last, Tfc, S->n_q, codes, quantized, nullptr, enc_out, nullptr);
@@ -1944,7 +1903,7 @@ int stream_encode_pass(const fc_stream* S, Ctx& cx, int n, const float* wav, int
 
 int stream_decode_pass(const fc_stream* S, Ctx& cx, int n, const float* z_bdt, int Tfc, int use_scale, float* wav) {
     fc_engine* e = S->e;
-    Act last = run_decoder_stream(e, cx, S, n, z_bdt, Tfc);
+    Act last = run_decoder(e, cx, Pass{S, n, false}, z_bdt, Tfc);
     const int C = e->audio_ch();
     cx.launch("combine", "", [&] {
         return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, use_scale ? S->state : nullptr, cx.B, C, last.T, last.T, wav, (long long)C * last.T,
@@ -2150,23 +2109,14 @@ int fc_engine_finalize(fc_engine* e) {
         }
         if (pack_conv(e, e->enc_last) || pack_conv(e, e->dec_first)) return 1;
         if (pack_dft(e)) return 1;
+    } else {
+        // all fused res-block heads, then all convs: the heads read the host copies of their two convs' weights (the host map is still
+        // alive here)
+        int err = 0;
+        for_each_conv(e, [&](const ConvVisit& v) { if (!err && v.role == Role::Shortcut) err = pack_reshead(e, *v.block); });
+        for_each_conv(e, [&](const ConvVisit& v) { if (!err) err = pack_conv(e, v.L); });
+        if (err) return 1;
     }
-    std::vector<ConvLayer*> convs = {&e->enc_first, &e->enc_last, &e->dec_first, &e->dec_last};
-    if (e->arch.model_type == 1) convs.clear();
-    for (auto* st : {&e->enc_stages, &e->dec_stages})
-        for (auto& S : *st) {
-            if (e->arch.model_type == 1) break;
-            for (auto& R : S.res) { convs.push_back(&R.shortcut); convs.push_back(&R.block1); convs.push_back(&R.block3); }
-            convs.push_back(&S.resample);
-        }
-    // fused res-block heads read the host copies of the two convs' weights: pack them before pack_conv drops nothing (host map is
-    // still alive here)
-    for (auto* stg : {&e->enc_stages, &e->dec_stages})
-        for (auto& S : *stg)
-            for (auto& R : S.res)
-                if (e->arch.model_type == 0 && pack_reshead(e, R)) return 1;
-    for (ConvLayer* L : convs)
-        if (pack_conv(e, *L)) return 1;
     if (pack_lstm(e, e->enc_lstm)) return 1;
     if (pack_lstm(e, e->dec_lstm)) return 1;
     if (pack_tf(e, e->enc_tf) || pack_tf(e, e->dec_tf)) return 1;
@@ -2285,17 +2235,8 @@ int fc_decode_codes(fc_engine* e, const int64_t* codes, int B, int Tf, int n_q, 
     if (!codes || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    const int D = e->arch.dimension, Dc = e->cdim();
-    float* z = cx.alloc<float>((size_t)B * Dc * Tf);
-    if (cx.err) return 1;
-    HIP_TRY(fc::launch_rvq_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st));
-    if (e->q_proj) {       // CostumeQuantizer.decode (costume_quantizer.py:114-119): output_proj on the summed code vectors
-        fc::Src qs; qs.ptr = z; qs.used = 1;
-        Act qo = run_conv(e, cx, e->q_out, qs, fc::Src(), 0, Tf);
-        if (cx.err) return 1;
-        if (emb_out) HIP_TRY(fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, emb_out, (long long)Tf * D, 1, D, cx.st));
-        z = qo.raw;
-    }
+    float* z = cx.alloc<float>((size_t)B * e->cdim() * Tf);
+    if (codes_to_decoder_input(e, cx, codes, Tf, n_q, emb_out, &z)) return 1;
     return do_decode(e, cx, z, Tf, nullptr, out_len, wav);
 }
 
@@ -2496,7 +2437,7 @@ int fc_resblock_forward_src(fc_engine* e, const char* prefix, const float* x0, c
     fc_engine::Stage one;
     one.res.push_back(R);
     Act sc, b3;
-    run_resblocks(e, cx, one, hook_src(x0, aff0, nullptr), hook_src(x1, aff1, nullptr), T, &sc, &b3);
+    run_resblocks(e, cx, Pass(), one, hook_src(x0, aff0, nullptr), hook_src(x1, aff1, nullptr), T, &sc, &b3);
     if (cx.err) return 1;
     HIP_TRY(fc::launch_combine(src_of(sc), src_of(b3), 0, 1.f, nullptr, B, sc.C, T, T, y, (long long)sc.C * T, T, 1, cx.st));
     return 0;
@@ -2693,9 +2634,9 @@ size_t fc_stream_workspace_bytes(const fc_stream* S) {
     Ctx ce = dry_ctx(e, S->B);
     stream_encode_pass(S, ce, 0, nullptr, S->max_chunk, true, nullptr, nullptr, nullptr);
     Ctx cd = dry_ctx(e, S->B);
-    cd.alloc<float>((size_t)S->B * std::max(D, e->cdim()) * Tf);
-    if (e->q_proj) { fc::Src qs; qs.used = 1; run_conv(e, cd, e->q_out, qs, fc::Src(), 0, Tf); }
-    stream_decode_pass(S, cd, 0, nullptr, Tf, 1, nullptr);
+    float* z = cd.alloc<float>((size_t)S->B * std::max(D, e->cdim()) * Tf);       // the first buffer of either decode call
+    codes_to_decoder_input(e, cd, nullptr, Tf, S->n_q, nullptr, &z);
+    stream_decode_pass(S, cd, 0, z, Tf, 1, nullptr);
     return std::max(ce.off, cd.off) + 4096;
 }
 
@@ -2759,18 +2700,9 @@ int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_
     if (!codes || !wav) return fail("bad argument");
     if (S->dec_pushes < 0) return fail("streaming decode: fc_stream_reset first");
     if (stream_decode_check(S, Tfc)) return 1;
-    const int B = S->B, D = e->arch.dimension, Dc = e->cdim();
-    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    float* z = cx.alloc<float>((size_t)B * Dc * Tfc);
-    if (cx.err) return 1;
-    HIP_TRY(fc::launch_rvq_decode(codes, B, Tfc, S->n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st));
-    if (e->q_proj) {       // CostumeQuantizer.decode (costume_quantizer.py:114-119), per frame as in fc_decode_codes
-        fc::Src qs; qs.ptr = z; qs.used = 1;
-        Act qo = run_conv(e, cx, e->q_out, qs, fc::Src(), 0, Tfc);
-        if (cx.err) return 1;
-        if (emb_out) HIP_TRY(fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tfc, Tfc, emb_out, (long long)Tfc * D, 1, D, cx.st));
-        z = qo.raw;
-    }
+    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
+    float* z = cx.alloc<float>((size_t)S->B * e->cdim() * Tfc);
+    if (codes_to_decoder_input(e, cx, codes, Tfc, S->n_q, emb_out, &z)) return 1;      // per frame: nothing to carry
     S->broken = true;
     if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
     S->broken = false;
@@ -2779,7 +2711,7 @@ int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_
 }
 
 // Test hook: the SLSTM stage of a push alone (lstm.py:22-28 without the skip), continuing the recurrence the session's encoder
-// (decoder = 0) or decoder (decoder = 1) LSTM state holds, exactly as a push runs it (run_lstm_stream).  x, y dev f32 [B][H][T].
+// (decoder = 0) or decoder (decoder = 1) LSTM state holds, exactly as a push runs it (run_lstm on the carried state).  x, y dev f32 [B][H][T].
 int fc_stream_lstm_forward(fc_stream* S, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream) {
     if (stream_ready(S)) return 1;
     fc_engine* e = S->e;
@@ -2790,7 +2722,7 @@ int fc_stream_lstm_forward(fc_stream* S, int decoder, const float* x, int T, flo
     Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
     Act in; in.raw = const_cast<float*>(x); in.C = lb.H; in.T = T;
     S->broken = true;
-    Act out = run_lstm_stream(e, cx, lb, in, T, S->state + (decoder ? S->dec_lstm_off : S->enc_lstm_off));
+    Act out = run_lstm(e, cx, lb, in, T, S->state + (decoder ? S->dec_lstm_off : S->enc_lstm_off));
     if (cx.err) return 1;
     HIP_TRY(hipMemcpyAsync(y, out.raw, (size_t)S->B * lb.H * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st));
     S->broken = false;

@@ -74,6 +74,12 @@ SYMBOLS = {
     "fc_decode_emb": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_decode_codes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_encode_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    # length-aware (ragged) batches: the offline signatures plus the device lengths
+    "fc_ragged_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int]),
+    "fc_encode_ragged": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "fc_decode_emb_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "fc_decode_codes_ragged": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "fc_encode_decode_ragged": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "fc_rvq_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_q0_source_frames": (C.c_int, [C.c_int, _P]),
     "fc_layer_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

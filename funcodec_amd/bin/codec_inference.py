@@ -80,19 +80,24 @@ class Speech2Token:
             bit_width: int = None,
             use_scale: bool = True,
             run_mod: str = "inference",
+            speech_lengths: Optional[Union[torch.Tensor, np.ndarray]] = None,
     ):
-        """Returns (code_indices, code_embeddings, recon_speech, sub_quants) like the reference (:86-134)."""
+        """Returns (code_indices, code_embeddings, recon_speech, sub_quants) like the reference (:86-134).
+
+        speech_lengths [B] (not in the reference; default None = the reference's behaviour): samples per row (frames per row for the
+        two decode modes).  With it every row is computed as if it were alone in the batch, cut at its own length, zeros behind
+        (EncodecMI355X.inference)."""
         if ppg is not None:
             raise NotImplementedError("ppg conditioning (codec_semantic_aug) is outside the hot-path scope")
         if isinstance(speech, np.ndarray):
             speech = torch.from_numpy(speech)
         speech = speech.to(self.model.device)
         if run_mod == "inference":
-            ret = self.model.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale)
+            ret = self.model.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, speech_lengths=speech_lengths)
         elif run_mod == "encode":
-            ret = self.model.inference_encoding(speech, need_recon=False, bit_width=bit_width)
+            ret = self.model.inference_encoding(speech, need_recon=False, bit_width=bit_width, speech_lengths=speech_lengths)
         elif run_mod == "decode_emb":
-            ret = self.model.inference_decoding_emb(speech)
+            ret = self.model.inference_decoding_emb(speech, token_lengths=speech_lengths)
         else:
             q = self.model.quantizer
             bit_per_quant = (q.sampling_rate // q.encoder_hop_length) * int(math.log2(q.codebook_size))
@@ -101,7 +106,7 @@ class Speech2Token:
                 nq = int(max(bit_width // bit_per_quant, 1))
             speech = speech[:, :, :nq]
             logging.info("use %d quantizers.", speech.shape[-1])
-            ret = self.model.inference_decoding(speech)
+            ret = self.model.inference_decoding(speech, token_lengths=speech_lengths)
         if self.check_status:
             self.model.engine.check_status(sync=True)
         if self.dtype != "float32":
@@ -305,6 +310,10 @@ def inference_modelscope(
                 if should_resample:                                                 # reference :318-322 (lengths stay in file samples)
                     batch["speech"] = fio.resample(batch["speech"], file_sr, sampling_rate)
                 speech_length = batch.pop("speech_lengths")
+                if _str2bool(kwargs.get("length_aware", False)):        # opt-in: the lengths go to the model instead of being dropped
+                    if should_resample:
+                        raise NotImplementedError("length_aware with file_sampling_rate != sampling_rate (the lengths count file samples)")
+                    batch["speech_lengths"] = speech_length
                 bw = param_dict["bit_width"] if param_dict is not None and "bit_width" in param_dict else bit_width
                 token_id, token_emb, recon_speech, sub_quants = my_model(**batch, need_recon=True, bit_width=bw,
                                                                          use_scale=use_scale, run_mod=run_mod)
@@ -381,6 +390,9 @@ def get_parser():
     g.add_argument("--need_sub_quants", type=_str2bool)
     g.add_argument("--run_mod", type=str, choices=["inference", "encode", "decode", "decode_emb"], default="inference")
     g.add_argument("--stat_flops", type=_str2bool, default=False)
+    # not in the reference: every utterance of a batch is coded as if it were alone (its own volume scale, normalisation statistics and
+    # end padding), so that --batch_size N writes what --batch_size 1 writes
+    g.add_argument("--length_aware", type=_str2bool, default=False)
     return p
 
 

@@ -15,6 +15,7 @@
 #include "../../include/funcodec_amd.h"
 #include "kernels.h"
 #include "laura_kernels.h"
+#include "ragged_kernels.h"
 #include "seq_kernels.h"
 #include "stream_kernels.h"
 
@@ -104,6 +105,7 @@ struct Act {               // raw tensor [B][C][T] + pending GroupNorm affine (n
     float* aff = nullptr;
     int C = 0, T = 0;
     bool normed = false;   // has a pending affine (valid in dry-run planning too, where pointers are null)
+    int ld = 0;            // row pitch when it is not T (ragged pass: the untrimmed output of a transposed conv)
 };
 
 int ceil_div_i(int a, int b) { return (a + b - 1) / b; }
@@ -224,6 +226,10 @@ struct Ctx {
     size_t cap = 0, off = 256;       // the first buffer starts 256 bytes in: the grouped 3 x 3 conv reads one float in front of a row (freq_kernels.hip, FASTEDGE)
     bool dry = false;
     int err = 0;
+    // where the walk of a ragged pass stands (run_encoder / run_decoder keep them): the side, and the columns of the layer's input per
+    // encoder input sample / decoder frame (ConvVisit::rate); no_xq: the DMA-staged materialisation (MODE 5) is not used in a ragged pass
+    bool dec_side = false, no_xq = false;
+    int rate = 1;
     static constexpr size_t kTailSlack = 4096;
     int launches = 0, conv_launches = 0;
     double conv_flops = 0, conv_bytes = 0, lstm_flops = 0, rvq_flops = 0, attn_flops = 0;
@@ -1051,16 +1057,15 @@ int pack_tf(fc_engine* e, TfBlock& tb) {
 struct ConvGeom { int Tout, padL, padR, count_T; };
 
 // SConv1d.forward padding arithmetic (conv.py:243-258, get_extra_padding_for_conv1d :57-64)
+// (In a length-aware pass every ROW has its own T here; the per-layer row-length rule -- ceil at every stride -- and the
+// extra-padding arithmetic, which this function uses too, are stated once in ragged_kernels.h: RagLen / ragged_cols / ragged_extra.)
 ConvGeom conv_geom(const ConvLayer& L, int T) {
     ConvGeom g;
     if (L.valid) { g.padL = 0; g.padR = 0; g.Tout = T - L.k + 1; g.count_T = g.Tout; return g; }
     if (L.zpadL >= 0) { g.padL = L.zpadL; g.padR = L.zpadR; g.Tout = T + g.padL + g.padR - L.k + 1; g.count_T = g.Tout; return g; }
     if (!L.transposed) {
         const int pt = (L.k - 1) * L.dil - (L.stride - 1);      // padding_total (conv.py:247)
-        const int num = T - L.k + pt;
-        const int nfr = num >= 0 ? ceil_div_i(num, L.stride) : -((-num) / L.stride);   // ceil(n_frames) - 1
-        const int ideal = nfr * L.stride + (L.k - pt);
-        const int extra = ideal - T;
+        const int extra = fc::ragged_extra(T, L.k, pt, L.stride);   // get_extra_padding_for_conv1d: stated once, for a batch and for a row
         if (L.causal) { g.padL = pt; g.padR = extra; }          // all fixed padding on the left (conv.py:249-251)
         else if (L.extra_left) { g.padR = pt / 2; g.padL = pt - pt / 2 + extra; }   // SConv2d, time axis (conv.py:376-377)
         else { g.padR = pt / 2 + extra; g.padL = pt - pt / 2; }
@@ -1134,7 +1139,7 @@ Act run_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, fc::Src s0, fc::Src s1, 
     if ((L.Mpad / L.BM >= 3 || L.force_plain) && has_prologue) {
         // the conv kernel's quad layout stages such an input by DMA when it is materialised with 4 channels interleaved and its padding in
         // place (kernels.hip combine_xq_kernel / conv_kernel.h MODE 5); else the plain [B][C][T] tensor and the register-staged PLAIN form
-        const bool xq = !s0.div && !out_override_blocks_xq(L) && fc::conv_xq_ok(L.cin, L.CC, L.gk, L.gstride, L.dil, L.BM, L.BN, L.row ? 1 : 0);
+        const bool xq = !cx.no_xq && !s0.div && !out_override_blocks_xq(L) && fc::conv_xq_ok(L.cin, L.CC, L.gk, L.gstride, L.dil, L.BM, L.BN, L.row ? 1 : 0);
         const int padL_x = L.transposed ? 1 : g.padL, padR_x = L.transposed ? 1 : g.padR;
         const int Tp = padL_x + Tin + padR_x;
         float* tmp = xq ? cx.alloc<float>(fc::conv_xq_floats(cx.B, L.cin, Tp, L.BN, L.gstride, L.gk, L.dil))
@@ -1186,7 +1191,7 @@ Act run_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, fc::Src s0, fc::Src s1, 
 }
 
 // Src.used: bit 0 = present, bit 1 = carries an affine / divisor (planning flags, valid when pointers are null)
-inline fc::Src src_of(const Act& a) { fc::Src s; s.ptr = a.raw; s.aff = a.aff; s.used = a.normed ? 3 : 1; return s; }
+inline fc::Src src_of(const Act& a) { fc::Src s; s.ptr = a.raw; s.aff = a.aff; s.used = a.normed ? 3 : 1; s.ld = a.ld; return s; }
 
 // SLSTM.forward (lstm.py:22-28) without the skip; returns plain y [B][H][T].
 // Layer wavefront: one launch per "diagonal" s advances every layer l by its timestep s - l.
@@ -1334,12 +1339,30 @@ struct Pass {
     const fc_stream* S = nullptr;   // the session of a push; null: an offline call over the whole utterance
     int n = 0;                      // pushes this side (encoder / decoder) of the session has taken before this one
     bool final = false;             // the utterance's last encoder push (a decoder push never is)
+    // a length-aware (ragged) call: every row ends at its own length.  lengths: device [B], clamped (null in a dry pass); they count
+    // encoder input samples, or, on the decoder side, what frame_div of them make a frame (the hop behind an encoder, 1 for token_lengths)
+    bool ragged = false;
+    const int* lengths = nullptr;
+    int frame_div = 1;
 };
 
+// the columns of every row at the input of the layer the walk of a ragged pass stands at (the rule: ragged_kernels.h)
+inline fc::RagLen ragged_len(const Ctx& cx, const Pass& p) {
+    fc::RagLen r;
+    r.lens = p.lengths;
+    if (cx.dec_side) { r.div = p.frame_div; r.mul = cx.rate; }
+    else r.div = cx.rate;
+    return r;
+}
+
+Act ragged_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T);
 Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc, int side_pushes, bool final);
 
-// the conv step: in a push, the layers that carry a left context run over [carry | chunk] (stream_conv); the pointwise ones as offline
+// the conv step: in a push, the layers that carry a left context run over [carry | chunk] (stream_conv); the pointwise ones as offline.
+// In a ragged pass every conv that looks beyond its own column (k > 1) or normalises over the row runs behind a per-row staging pass
+// (ragged_conv); a pointwise weight_norm conv maps column to column and runs as offline, garbage columns included.
 Act walk_conv(fc_engine* e, Ctx& cx, const Pass& p, Role role, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T) {
+    if (p.ragged && (L.k > 1 || L.has_norm)) return ragged_conv(e, cx, p, L, s0, s1, elu, T);
     if (p.S && carries_context(role)) return stream_conv(e, cx, p.S, L, s0, s1, elu, T, p.n, p.final);
     return run_conv(e, cx, L, s0, s1, elu, T);
 }
@@ -1361,7 +1384,7 @@ void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x
 void run_resblocks(fc_engine* e, Ctx& cx, const Pass& p, const fc_engine::Stage& S, fc::Src a0, fc::Src a1, int T, Act* sc, Act* b3) {
     for (const auto& R : S.res) {
         Act b1;
-        if (!p.S && R.fused_head && !a0.div) {      // the fused head has no form that stages a carry
+        if (!p.S && !p.ragged && R.fused_head && !a0.div) {      // the fused head has no form that stages a carry or a row end
             run_reshead(e, cx, R, a0, a1, T, sc, &b1);
         } else {
             *sc = walk_conv(e, cx, p, Role::Shortcut, R.shortcut, a0, a1, 0, T);
@@ -1374,11 +1397,13 @@ void run_resblocks(fc_engine* e, Ctx& cx, const Pass& p, const fc_engine::Stage&
 
 // SEANetEncoder.forward: wav [B][C][T] (a chunk of it in a push; with the caller's divisor) -> last conv (raw + affine), T -> Tf
 Act run_encoder(fc_engine* e, Ctx& cx, const Pass& p, fc::Src wav, int T) {
+    cx.dec_side = false; cx.rate = 1; cx.no_xq = p.ragged;
     Act x = walk_conv(e, cx, p, Role::First, e->enc_first, wav, fc::Src(), 0, T);
     for (auto& S : e->enc_stages) {
         Act sc, b3;
         run_resblocks(e, cx, p, S, src_of(x), fc::Src(), x.T, &sc, &b3);
         x = walk_conv(e, cx, p, Role::Resample, S.resample, src_of(sc), src_of(b3), 1, sc.T);
+        cx.rate *= S.resample.stride;
     }
     fc::Src a0, a1;
     run_bottleneck(e, cx, p, false, x, &a0, &a1);
@@ -1389,12 +1414,14 @@ Act run_encoder(fc_engine* e, Ctx& cx, const Pass& p, fc::Src wav, int T) {
 // without look-ahead (causal unpad1d trims on the right only).
 Act run_decoder(fc_engine* e, Ctx& cx, const Pass& p, const float* z_bdt, int Tf) {
     fc::Src s; s.ptr = z_bdt; s.used = 1;
+    cx.dec_side = true; cx.rate = 1; cx.no_xq = p.ragged;
     Act x = walk_conv(e, cx, p, Role::First, e->dec_first, s, fc::Src(), 0, Tf);
     fc::Src a0, a1;
     run_bottleneck(e, cx, p, true, x, &a0, &a1);
     int T = Tf;
     for (auto& S : e->dec_stages) {
         Act up = walk_conv(e, cx, p, Role::Resample, S.resample, a0, a1, 1, T);
+        cx.rate *= S.resample.stride;
         Act sc, b3;
         run_resblocks(e, cx, p, S, src_of(up), fc::Src(), up.T, &sc, &b3);
         a0 = src_of(sc); a1 = src_of(b3);
@@ -1685,15 +1712,17 @@ int frames_for(const fc_engine* e, int T) {
 int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
                 float** quant_bdt_out);
 int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* codes, float* quantized,
-              float* sub_quants, float* scale, float* enc_out, float** quant_bdt_out) {
+              float* sub_quants, float* scale, float* enc_out, float** quant_bdt_out, const Pass& p = Pass()) {
     const int B = cx.B, D = e->arch.dimension, Tf = frames_for(e, T);
     float* sc = nullptr;
     if (e->arch.audio_normalize) {
         sc = scale ? scale : cx.alloc<float>(B);
-        cx.launch("volume", "", [&] { return fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st); });
+        cx.launch("volume", "", [&] {
+            return p.ragged ? fc::launch_ragged_volume(wav, B, e->audio_ch(), T, p.lengths, sc, cx.st) : fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st);
+        });
     }
     fc::Src s; s.ptr = wav; s.div = sc; s.used = e->arch.audio_normalize ? 3 : 1;
-    Act last = e->arch.model_type == 1 ? run_encoder_2d(e, cx, wav, T, sc) : run_encoder(e, cx, Pass(), s, T);
+    Act last = e->arch.model_type == 1 ? run_encoder_2d(e, cx, wav, T, sc) : run_encoder(e, cx, p, s, T);
     return do_quantize(e, cx, last, Tf, n_q, codes, quantized, sub_quants, enc_out, quant_bdt_out);
 }
 
@@ -1744,12 +1773,12 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
     return cx.err;
 }
 
-int do_decode(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* scale, int out_len, float* wav) {
+int do_decode(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* scale, int out_len, float* wav, const Pass& p = Pass()) {
     if (e->arch.model_type == 1) {
         run_decoder_2d(e, cx, z_bdt, Tf, scale, out_len, wav);
         return cx.err;
     }
-    Act last = run_decoder(e, cx, Pass(), z_bdt, Tf);
+    Act last = run_decoder(e, cx, p, z_bdt, Tf);
     if (!cx.dry && out_len > last.T) cx.fail("out_len exceeds Tf*hop");
     // final GroupNorm apply (decoder.model.N.conv.norm has C = audio channels), x scale (codec_basic.py:406-407), trim (:711)
     const int C = e->audio_ch();
@@ -1790,6 +1819,11 @@ int consume_status(fc_engine* e) {
         e->status_host[FC_STATUS_BAD_CODE] = 0;
         return fail("a previous decode call was given code indices outside [0, codebook_size) (the reference's F.embedding raises, "
                     "ddp_core_vq.py:191); they were clamped, the decoded audio of that call is not meaningful");
+    }
+    if (e->status_host[FC_STATUS_BAD_LENGTH]) {
+        e->status_host[FC_STATUS_BAD_LENGTH] = 0;
+        return fail("a previous length-aware call was given a row length outside [1, Tmax] (speech_lengths / token_lengths); it was clamped, "
+                    "that row's outputs of that call are not meaningful");
     }
     return 0;
 }
@@ -1909,6 +1943,126 @@ int stream_decode_pass(const fc_stream* S, Ctx& cx, int n, const float* z_bdt, i
         return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, use_scale ? S->state : nullptr, cx.B, C, last.T, last.T, wav, (long long)C * last.T,
                                   last.T, 1, cx.st);
     });
+    return cx.err;
+}
+
+// ---- length-aware (ragged) pass -------------------------------------------------------------------------------------------------
+// What a ragged call must reproduce is the OFFLINE callable on every row alone, cut at the row's own length.  The pass differs from the
+// offline one in three places: the volume scale (the row's own samples), the conv step (ragged_conv: a staging pass that pads every row at
+// its own end, then the layer's GEMM kernel without padding over the common width) and the GroupNorm statistics (the row's valid columns
+// only).  Columns behind a row's end hold finite garbage from then on (the staging pass writes zeros there and never reads there), which
+// the LSTM (forward in time, rows independent) and the quantiser (per frame) compute and the final masking stores zero.
+
+// why this engine has no length-aware calls, or null.  Each reason names the configuration key.
+const char* ragged_refusal(const fc_engine* e) {
+    const fc_arch& a = e->arch;
+    if (a.model_type != 0) return "length-aware batches are not available for model: freq_codec (time-domain codec only)";
+    if (a.lstm_layers > 0 && a.seq_model == 1) return "length-aware batches are not available for seq_model: transformer (it needs a key mask per row)";
+    if (a.q0_ds_ratio > 1) return "length-aware batches are not available for quantizer_conf.q0_ds_ratio > 1 (the half-rate first stage is laid out per batch width)";
+    return nullptr;
+}
+
+// One SConv1d / SConvTranspose1d (+ GroupNorm) of a ragged pass
+Act ragged_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T) {
+    const int B = cx.B, pt = stream_pt(L);
+    const fc::RagLen in = ragged_len(cx, p);
+    const int Tp = L.transposed ? T + 2 : pt + T + fc::ragged_extra(T, L.k, pt, L.stride);
+    float* buf = cx.alloc<float>((size_t)B * L.cin * Tp);
+    fc::RaggedStage g;
+    g.s0 = s0; g.s1 = s1; g.elu = elu; g.alpha = e->arch.elu_alpha;
+    g.B = B; g.C = L.cin; g.Tin = T; g.Tp = Tp; g.k = L.k; g.pt = pt; g.stride = L.stride;
+    g.causal = L.causal ? 1 : 0; g.transposed = L.transposed ? 1 : 0; g.len = in; g.buf = buf;
+    cx.launch("ragged stage", L.prefix.c_str(), [] { return "ragged_stage_kernel (length-aware: prologue and per-row padding of a conv)"; }, 0.0,
+              4.0 * B * L.cin * ((double)T * (s1.used ? 2 : 1) + Tp), [&] { return fc::launch_ragged_stage(g, cx.st); });
+    ConvGeom geo;
+    geo.padL = 0; geo.padR = 0;
+    geo.Tout = L.transposed ? T * L.stride : (Tp - ((L.k - 1) * L.dil + 1)) / L.stride + 1;
+    geo.count_T = geo.Tout;
+    if (!cx.dry && geo.Tout != conv_geom(L, T).Tout) cx.fail("internal: staged width of a ragged conv (" + L.prefix + ")");
+    fc::ConvLaunch c = conv_launch_of(L, B, Tp, geo);
+    c.s0.ptr = buf; c.s0.used = 1;
+    c.alpha = e->arch.elu_alpha;
+    c.pad_zero = 1;                                   // nothing is padded; columns past the row end of the last tile read as zero
+    Act out;
+    out.C = L.cout; out.T = geo.Tout;
+    fc::RagLen valid = in;                            // the row's columns of what GroupNorm sees
+    int pitch = geo.Tout;
+    if (L.transposed) {                               // group j = taps (x[j-1], x[j]) = staged columns (j, j + 1): T + 1 groups
+        const int trimL = L.causal ? 0 : L.stride - L.stride / 2;
+        c.Tout = T + 1; c.up_r = L.stride;
+        valid.mul *= L.stride;
+        if (L.has_norm) {                             // GroupNorm sees the UNTRIMMED output (conv.py:287-303): store all of it, hand on the trimmed window
+            pitch = (T + 1) * L.stride;
+            c.trimL = 0; c.Tfinal = pitch;
+            valid.add = L.stride;
+            out.ld = pitch;
+        } else {
+            c.trimL = trimL; c.Tfinal = geo.Tout;
+        }
+        float* full = cx.alloc<float>((size_t)B * L.cout * pitch);
+        c.out = full;
+        out.raw = L.has_norm ? at(full, trimL) : full;
+    } else {
+        c.Tout = geo.Tout;
+        valid.div *= L.stride;                        // strided convs sit on the encoder side only (mul == 1 there)
+        out.raw = cx.alloc<float>((size_t)B * L.cout * geo.Tout);
+        c.out = out.raw;
+    }
+    c.out_sB = (long long)L.cout * pitch; c.out_sM = pitch; c.out_sT = 1;
+    const double fl = 2.0 * B * (double)L.M * L.cin * L.gk * c.Tout;
+    const double by = 4.0 * B * ((double)L.cin * Tp + (double)L.cout * pitch);
+    cx.conv_flops += fl; cx.conv_bytes += by;
+    cx.conv_launch("conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
+    if (L.has_norm) {
+        double* partials = cx.alloc<double>((size_t)B * L.cout * fc::ragged_gn_segments(pitch) * 2);
+        out.aff = cx.alloc<float>((size_t)B * L.cout * 2);
+        out.normed = true;
+        cx.launch("ragged GroupNorm statistics", L.prefix.c_str(),
+                  [] { return "ragged_gn_partials_kernel (length-aware: GroupNorm sums over a row's valid columns)"; }, 0.0, 4.0 * B * L.cout * (double)pitch,
+                  [&] { return fc::launch_ragged_gn_partials(c.out, B, L.cout, pitch, valid, partials, cx.st); });
+        cx.launch("ragged gn_finalize", L.prefix.c_str(),
+                  [&] { return fc::launch_ragged_gn_finalize(partials, B, L.cout, pitch, valid, L.gamma, L.beta, e->arch.gn_eps, out.aff, cx.st); });
+    }
+    return out;
+}
+
+// the clamped device lengths of a ragged call, in the workspace
+int* ragged_lengths(fc_engine* e, Ctx& cx, const int32_t* lengths, int Tmax) {
+    int* lens = cx.alloc<int>(cx.B);
+    cx.launch("ragged lengths", "", [&] { return fc::launch_ragged_lengths(lengths, cx.B, Tmax, lens, e->status_dev, cx.st); });
+    return lens;
+}
+
+// zero behind every row's frames in the encoder-side outputs
+void ragged_mask_encoded(fc_engine* e, Ctx& cx, const Pass& p, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out) {
+    const int B = cx.B, D = e->arch.dimension;
+    fc::RagLen f; f.lens = p.lengths; f.div = total_hop(e);
+    cx.launch("ragged mask", "codes", [&] { return fc::launch_ragged_mask_i64(codes, n_q, B, 1, Tf, 1, f, cx.st); });
+    if (quantized) cx.launch("ragged mask", "quantized", [&] { return fc::launch_ragged_mask_f32(quantized, 1, B, 1, Tf, D, f, cx.st); });
+    if (sub_quants) cx.launch("ragged mask", "sub_quants", [&] { return fc::launch_ragged_mask_f32(sub_quants, n_q, B, e->cdim(), Tf, 1, f, cx.st); });
+    if (enc_out) cx.launch("ragged mask", "enc_out", [&] { return fc::launch_ragged_mask_f32(enc_out, 1, B, 1, Tf, D, f, cx.st); });
+}
+
+int ragged_ready(fc_engine* e) {
+    if (check_ready(e)) return 1;
+    if (const char* why = ragged_refusal(e)) return fail(why);
+    return 0;
+}
+
+// the four calls over one context (dry: workspace sizing)
+int ragged_encode(fc_engine* e, Ctx& cx, const float* wav, const int32_t* lengths, int T, int n_q, int64_t* codes, float* quantized,
+                  float* sub_quants, float* scale, float* enc_out, float** qbdt, Pass* pass) {
+    Pass p;
+    p.ragged = true; p.lengths = ragged_lengths(e, cx, lengths, T); p.frame_div = total_hop(e);
+    if (do_encode(e, cx, wav, T, n_q, codes, quantized, sub_quants, scale, enc_out, qbdt, p)) return 1;
+    ragged_mask_encoded(e, cx, p, frames_for(e, T), n_q, codes, quantized, sub_quants, enc_out);
+    if (pass) *pass = p;
+    return cx.err;
+}
+
+int ragged_decode(fc_engine* e, Ctx& cx, const Pass& p, const float* z_bdt, int Tf, const float* scale, int out_len, const fc::RagLen& valid, float* wav) {
+    if (do_decode(e, cx, z_bdt, Tf, scale, out_len, wav, p)) return 1;
+    cx.launch("ragged mask", "wav", [&] { return fc::launch_ragged_mask_f32(wav, 1, cx.B, e->audio_ch(), out_len, 1, valid, cx.st); });
     return cx.err;
 }
 
@@ -2256,6 +2410,82 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
     return do_decode(e, cx, qbdt, Tf, (use_scale && e->arch.audio_normalize) ? sc : nullptr, T < dec_len ? T : dec_len, recon);
 }
 
+// ---- length-aware (ragged) calls: the offline siblings' signatures plus `lengths`
+size_t fc_ragged_workspace_bytes(const fc_engine* ce, int B, int Tmax) {
+    fc_engine* e = const_cast<fc_engine*>(ce);
+    if (!e || B <= 0 || Tmax <= 0 || ragged_refusal(e)) return 0;
+    const int Tf = frames_for(e, Tmax), D = e->arch.dimension;
+    Ctx cx = dry_ctx(e, B);
+    float* q = nullptr;
+    Pass p;
+    float mark;                                    // optional outputs: the pointer only marks presence in a dry pass
+    ragged_encode(e, cx, nullptr, nullptr, Tmax, e->arch.num_quantizers, nullptr, &mark, &mark, nullptr, &mark, &q, &p);
+    cx.alloc<float>((size_t)B * Tf * D);           // transposed copy for decode_emb / code vectors for decode_codes
+    cx.alloc<int64_t>((size_t)B * Tf * e->arch.num_quantizers);     // masked copy of the tokens
+    fc::RagLen v;
+    ragged_decode(e, cx, p, nullptr, Tf, nullptr, decoded_samples(e, Tf), v, nullptr);
+    return cx.off + 4096;
+}
+
+int fc_encode_ragged(fc_engine* e, const float* wav, const int32_t* lengths, int B, int T, int n_q, int64_t* codes, float* quantized,
+                     float* sub_quants, float* scale, float* enc_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (ragged_ready(e)) return 1;
+    if (!wav || !lengths || !codes || B <= 0 || T <= 0) return fail("bad argument");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
+    return ragged_encode(e, cx, wav, lengths, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr, nullptr);
+}
+
+int fc_decode_emb_ragged(fc_engine* e, const float* emb, const float* scale, const int32_t* lengths, int B, int Tf, int out_len, float* wav,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (ragged_ready(e)) return 1;
+    if (!emb || !lengths || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
+    Pass p;
+    p.ragged = true; p.lengths = ragged_lengths(e, cx, lengths, Tf); p.frame_div = 1;
+    const int D = e->arch.dimension;
+    float* z = cx.alloc<float>((size_t)B * D * Tf);
+    // what lies behind a row's frames is never read (dec_first is staged)
+    cx.launch("transpose", "emb", [&] { return fc::launch_transpose_btd(emb, B, Tf, D, z, cx.st); });
+    fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(e);
+    return ragged_decode(e, cx, p, z, Tf, scale, out_len, v, wav);
+}
+
+int fc_decode_codes_ragged(fc_engine* e, const int64_t* codes, const int32_t* lengths, int B, int Tf, int n_q, int out_len, float* wav,
+                           float* emb_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (ragged_ready(e)) return 1;
+    if (!codes || !lengths || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
+    Pass p;
+    p.ragged = true; p.lengths = ragged_lengths(e, cx, lengths, Tf); p.frame_div = 1;
+    fc::RagLen f; f.lens = p.lengths;
+    // the tokens behind a row's frames are the caller's garbage: a masked copy, so that none of them is looked up (or reported as out of range)
+    int64_t* masked = cx.alloc<int64_t>((size_t)B * Tf * n_q);
+    float* z = cx.alloc<float>((size_t)B * e->cdim() * Tf);
+    cx.launch("copy", "tokens", [&] { return hipMemcpyAsync(masked, codes, (size_t)B * Tf * n_q * sizeof(int64_t), hipMemcpyDeviceToDevice, cx.st); });
+    cx.launch("ragged mask", "tokens", [&] { return fc::launch_ragged_mask_i64(masked, 1, B, 1, Tf, n_q, f, cx.st); });
+    if (codes_to_decoder_input(e, cx, masked, Tf, n_q, emb_out, &z)) return 1;
+    if (emb_out) cx.launch("ragged mask", "emb_out", [&] { return fc::launch_ragged_mask_f32(emb_out, 1, B, 1, Tf, e->arch.dimension, f, cx.st); });
+    fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(e);
+    return ragged_decode(e, cx, p, z, Tf, nullptr, out_len, v, wav);
+}
+
+int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengths, int B, int T, int n_q, int use_scale, int64_t* codes,
+                            float* quantized, float* sub_quants, float* scale, float* recon, void* workspace, size_t workspace_bytes, void* stream) {
+    if (ragged_ready(e)) return 1;
+    if (!wav || !lengths || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
+    float* sc = scale;
+    if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
+    float* qbdt = nullptr;
+    Pass p;
+    if (ragged_encode(e, cx, wav, lengths, T, n_q, codes, quantized, sub_quants, sc, nullptr, &qbdt, &p)) return 1;
+    fc::RagLen v; v.lens = p.lengths;              // a row's reconstruction is cut at its own samples (the reference's recon[:, :, :T])
+    return ragged_decode(e, cx, p, qbdt, frames_for(e, T), (use_scale && e->arch.audio_normalize) ? sc : nullptr, T, v, recon);
+}
+
 int fc_rvq_encode(fc_engine* e, const float* x, int N, int n_q, int64_t* codes, float* quantized, void* workspace,
                   size_t workspace_bytes, void* stream) {
     if (check_ready(e)) return 1;
@@ -2486,6 +2716,7 @@ int fc_engine_status(fc_engine* e, unsigned* flags) {
     if (e->status_host) {
         if (e->status_host[FC_STATUS_LSTM_TIMEOUT]) f |= FC_STATUS_FLAG_LSTM_TIMEOUT;
         if (e->status_host[FC_STATUS_BAD_CODE]) f |= FC_STATUS_FLAG_BAD_CODE;
+        if (e->status_host[FC_STATUS_BAD_LENGTH]) f |= FC_STATUS_FLAG_BAD_LENGTH;
     }
     if (flags) *flags = f;
     if (!e->finalized) return 0;

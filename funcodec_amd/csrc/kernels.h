@@ -45,6 +45,8 @@ struct Src {
     const float* aff = nullptr;   // [B][C][2] or null
     const float* div = nullptr;   // [B] or null
     int used = 0;                 // host-side bookkeeping only (dry-run planning has null pointers)
+    int ld = 0;                   // host-side: row pitch when it is not T (ragged pass: the untrimmed output of a transposed conv); only
+                                  // launch_ragged_stage reads it
 };
 
 struct ConvLaunch {
@@ -213,6 +215,7 @@ hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D,
 // engine status words (host-pinned, device-mapped): written by kernels with plain stores, read by the host without a sync
 #define FC_STATUS_LSTM_TIMEOUT 0   // persistent LSTM: the grid barrier timed out (workgroups not co-resident); outputs poisoned
 #define FC_STATUS_BAD_CODE 1       // decode: a code index outside [0, codebook_size) was clamped
+#define FC_STATUS_BAD_LENGTH 2     // ragged pass: a row length outside [1, Tmax] was clamped
 #define FC_STATUS_WORDS 16
 
 #define FC_LSTM_MAX_LAYERS 4

@@ -37,6 +37,20 @@ def _on_device(fn):
     return wrapper
 
 
+def ragged_refusal(arch) -> Optional[str]:
+    """Why a model of this architecture has no length-aware (``speech_lengths`` / ``token_lengths``) calls, or None.  The
+    configuration key is named, as ``stream_refusal`` does."""
+    if arch.model_type != "encodec":
+        return "length-aware batches are not available for model: freq_codec (time-domain codec only)"
+    if arch.lstm_layers > 0 and arch.seq_model == "transformer":
+        return "length-aware batches are not available for seq_model: transformer (it needs a key mask per row)"
+    if arch.q0_ds_ratio > 1:
+        return "length-aware batches are not available for quantizer_conf.q0_ds_ratio > 1 (the half-rate first stage is laid out per batch width)"
+    if arch.segment_length is not None:
+        return "length-aware batches are not available with model_conf.segment_dur (segments are a host loop over whole utterances)"
+    return None
+
+
 class CodecEngine:
     """One engine per (device, checkpoint).  Calls on one engine are serialised by the caller,
     like a torch module's forward."""
@@ -174,11 +188,14 @@ class CodecEngine:
         """Samples the decoder emits for n_frames frames (n_frames * hop; stft_hop * (2-D time frames - 1) for freq_codec)."""
         return self.lib.fc_engine_decoded_samples(self._h, n_frames)
 
-    def _workspace(self, B: int, T: int) -> torch.Tensor:
-        key = (B, T)
+    def _workspace(self, B: int, T: int, ragged: bool = False) -> torch.Tensor:
+        key = (B, T, "ragged") if ragged else (B, T)
         need = self._ws_need.get(key)
         if need is None:
-            need = self._ws_need[key] = int(self.lib.fc_engine_workspace_bytes(self._h, B, T))
+            size = self.lib.fc_ragged_workspace_bytes if ragged else self.lib.fc_engine_workspace_bytes
+            need = self._ws_need[key] = int(size(self._h, B, T))
+            if ragged and need == 0:
+                raise EngineError(ragged_refusal(self.arch) or "this engine has no length-aware calls")
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -215,7 +232,20 @@ class CodecEngine:
             raise EngineError(f"wav must be [B,{self.channels},T]" + (" or [B,T]" if self.channels == 1 else "") + f", got {tuple(wav.shape)}")
         return wav
 
+    def _lengths_in(self, lengths, B: int) -> torch.Tensor:
+        """speech_lengths / token_lengths [B] of a length-aware call as device int32.  The range [1, Tmax] is checked on the device
+        (clamped and reported through check_status), so no host round trip is made here."""
+        why = ragged_refusal(self.arch)
+        if why:
+            raise EngineError(why)
+        lengths = torch.as_tensor(lengths).reshape(-1)
+        if lengths.numel() != B:
+            raise EngineError(f"lengths must hold one entry per row ({B}), got {lengths.numel()}")
+        return self._dev(lengths, torch.int32)
+
     # -- hot path ------------------------------------------------------------------------------
+    # Every call below takes an optional `lengths` [B]: without it the offline call over the whole batch width, as ever; with it the
+    # length-aware (ragged) sibling, whose row b is what the call gives row b alone cut at lengths[b], zeros behind (fc_*_ragged).
     @staticmethod
     def _cat(parts, dims):
         """Concatenate per-micro-batch result dicts along each tensor's batch dimension."""
@@ -226,12 +256,15 @@ class CodecEngine:
         return out
 
     @_on_device
-    def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False):
+    def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False, lengths=None):
         """wav [B,T] (or [B,C,T]) -> dict(codes [n_q,B,Tf] i64, quantized [B,Tf,D], sub_quants [n_q,B,D,Tf], scale [B,1]|None)."""
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
+        if lengths is not None:
+            lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
-            parts = [self.encode(wav[i:i + self.micro_batch], n_q, want_sub_quants, want_enc_out)
+            parts = [self.encode(wav[i:i + self.micro_batch], n_q, want_sub_quants, want_enc_out,
+                                 None if lengths is None else lengths[i:i + self.micro_batch])
                      for i in range(0, B, self.micro_batch)]
             return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, enc_out=0))
         Tf, D = self.frames(T), self.arch.dimension
@@ -241,18 +274,25 @@ class CodecEngine:
         subq = torch.empty((n_q, B, self.arch.codebook_dim, Tf), dtype=torch.float32, device=dev) if want_sub_quants else None
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         enc = torch.empty((B, Tf, D), dtype=torch.float32, device=dev) if want_enc_out else None
-        ws = self._workspace(B, T)
-        self._check(self.lib.fc_encode(self._h, _ptr(wav), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq), _ptr(scale),
-                                       _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
+        ws = self._workspace(B, T, lengths is not None)
+        if lengths is not None:
+            self._check(self.lib.fc_encode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq),
+                                                  _ptr(scale), _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
+        else:
+            self._check(self.lib.fc_encode(self._h, _ptr(wav), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq), _ptr(scale),
+                                           _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
         return dict(codes=codes, quantized=quant, sub_quants=subq,
                     scale=None if scale is None else scale.view(B, 1), enc_out=enc)
 
     @_on_device
-    def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True):
+    def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True, lengths=None):
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
+        if lengths is not None:
+            lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
-            parts = [self.encode_decode(wav[i:i + self.micro_batch], n_q, use_scale, want_sub_quants)
+            parts = [self.encode_decode(wav[i:i + self.micro_batch], n_q, use_scale, want_sub_quants,
+                                        None if lengths is None else lengths[i:i + self.micro_batch])
                      for i in range(0, B, self.micro_batch)]
             return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0))
         Tf, D = self.frames(T), self.arch.dimension
@@ -262,46 +302,64 @@ class CodecEngine:
         subq = torch.empty((n_q, B, self.arch.codebook_dim, Tf), dtype=torch.float32, device=dev) if want_sub_quants else None
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         recon = torch.empty((B, self.channels, min(T, self.decoded_samples(Tf))), dtype=torch.float32, device=dev)   # like recon[:, :, :T] of the reference
-        ws = self._workspace(B, T)
-        self._check(self.lib.fc_encode_decode(self._h, _ptr(wav), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
-                                              _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
+        ws = self._workspace(B, T, lengths is not None)
+        if lengths is not None:
+            self._check(self.lib.fc_encode_decode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
+                                                         _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
+        else:
+            self._check(self.lib.fc_encode_decode(self._h, _ptr(wav), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
+                                                  _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
         return dict(codes=codes, quantized=quant, sub_quants=subq,
                     scale=None if scale is None else scale.view(B, 1), recon=recon)
 
     @_on_device
-    def decode_codes(self, tokens: torch.Tensor):
-        """tokens [B,Tf,n_q] i64 -> (wav [B,1,Tf*hop], emb [B,Tf,D])."""
+    def decode_codes(self, tokens: torch.Tensor, lengths=None):
+        """tokens [B,Tf,n_q] i64 -> (wav [B,1,Tf*hop], emb [B,Tf,D]).  lengths: frames per row."""
         tokens = self._dev(tokens, torch.int64)
         B, Tf, n_q = tokens.shape
+        if lengths is not None:
+            lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
-            parts = [self.decode_codes(tokens[i:i + self.micro_batch]) for i in range(0, B, self.micro_batch)]
+            parts = [self.decode_codes(tokens[i:i + self.micro_batch], None if lengths is None else lengths[i:i + self.micro_batch])
+                     for i in range(0, B, self.micro_batch)]
             return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
         L = self.decoded_samples(Tf)
         wav = torch.empty((B, self.channels, L), dtype=torch.float32, device=self.device)
         emb = torch.empty((B, Tf, self.arch.dimension), dtype=torch.float32, device=self.device)
-        ws = self._workspace(B, Tf * self.hop_length)
-        self._check(self.lib.fc_decode_codes(self._h, _ptr(tokens), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws), ws.numel(),
-                                             self._stream()))
+        ws = self._workspace(B, Tf * self.hop_length, lengths is not None)
+        if lengths is not None:
+            self._check(self.lib.fc_decode_codes_ragged(self._h, _ptr(tokens), _ptr(lengths), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws),
+                                                        ws.numel(), self._stream()))
+        else:
+            self._check(self.lib.fc_decode_codes(self._h, _ptr(tokens), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws), ws.numel(),
+                                                 self._stream()))
         return wav, emb
 
     @_on_device
-    def decode_emb(self, emb: torch.Tensor, scale: Optional[torch.Tensor] = None, out_len: Optional[int] = None):
-        """emb [B,Tf,D] -> wav [B,1,out_len or Tf*hop]."""
+    def decode_emb(self, emb: torch.Tensor, scale: Optional[torch.Tensor] = None, out_len: Optional[int] = None, lengths=None):
+        """emb [B,Tf,D] -> wav [B,1,out_len or Tf*hop].  lengths: frames per row."""
         emb = self._dev(emb, torch.float32)
         B, Tf, D = emb.shape
         if D != self.arch.dimension:
             raise EngineError(f"embedding dim {D} != {self.arch.dimension}")
+        if lengths is not None:
+            lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
             return torch.cat([self.decode_emb(emb[i:i + self.micro_batch],
-                                              None if scale is None else scale.reshape(-1)[i:i + self.micro_batch], out_len)
+                                              None if scale is None else scale.reshape(-1)[i:i + self.micro_batch], out_len,
+                                              None if lengths is None else lengths[i:i + self.micro_batch])
                               for i in range(0, B, self.micro_batch)], 0)
         L = self.decoded_samples(Tf)
         out_len = L if out_len is None else int(out_len)
         sc = None if scale is None else self._dev(scale.reshape(-1), torch.float32)
         wav = torch.empty((B, self.channels, out_len), dtype=torch.float32, device=self.device)
-        ws = self._workspace(B, Tf * self.hop_length)
-        self._check(self.lib.fc_decode_emb(self._h, _ptr(emb), _ptr(sc), B, Tf, out_len, _ptr(wav), _ptr(ws), ws.numel(),
-                                           self._stream()))
+        ws = self._workspace(B, Tf * self.hop_length, lengths is not None)
+        if lengths is not None:
+            self._check(self.lib.fc_decode_emb_ragged(self._h, _ptr(emb), _ptr(sc), _ptr(lengths), B, Tf, out_len, _ptr(wav), _ptr(ws),
+                                                      ws.numel(), self._stream()))
+        else:
+            self._check(self.lib.fc_decode_emb(self._h, _ptr(emb), _ptr(sc), B, Tf, out_len, _ptr(wav), _ptr(ws), ws.numel(),
+                                               self._stream()))
         return wav
 
     @_on_device

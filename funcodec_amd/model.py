@@ -13,7 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ArchSpec
-from .engine import CodecEngine
+from .engine import CodecEngine, EngineError, ragged_refusal
 
 
 class EncodecMI355X:
@@ -105,11 +105,25 @@ class EncodecMI355X:
     # -- Encodec.inference (codec_basic.py:670-718) ------------------------------------------
     @torch.no_grad()
     def inference(self, speech: torch.Tensor, need_recon: bool = True, bit_width: int = None,
-                  use_scale: bool = True, _quantise_always: bool = False) -> Dict[str, torch.Tensor]:
+                  use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None) -> Dict[str, torch.Tensor]:
+        """speech_lengths [B] (optional): samples per row.  With it, row b of every output is what this call returns for
+        ``speech[b, ..., :speech_lengths[b]]`` alone (its own volume scale, GroupNorm statistics, end padding), zeros behind its
+        ``engine.frames(len)`` frames / ``len`` samples; without it, the call over the whole batch width, as the reference runs it."""
         speech = self._as_bct(speech)
         bypass = self.arch.bypass_quantizer and not _quantise_always
         n_q = self.arch.num_quantizers_for_bandwidth(bit_width)
         wav = speech[:, 0, :] if self.engine.channels == 1 else speech
+        if speech_lengths is not None:
+            why = ragged_refusal(self.arch)
+            if why:
+                raise EngineError(why)
+            if bypass:     # inference() alone: inference_encoding quantises whatever the flag says, the decode calls never see it
+                raise EngineError("Encodec.inference with speech_lengths is not built for model_conf.bypass_quantizer (it would decode the "
+                                  "encoder output of every row by its own frames); inference_encoding and the decode calls take lengths")
+            r = (self.engine.encode_decode(wav, n_q, use_scale=use_scale, lengths=speech_lengths) if need_recon
+                 else self.engine.encode(wav, n_q, lengths=speech_lengths))
+            return dict(recon_speech=r.get("recon"), code_indices=[r["codes"]],
+                        code_embeddings=[(r["quantized"], r["scale"] if use_scale else None)], sub_quants=[r["sub_quants"]])
         if self.arch.segment_length is not None:
             wav = wav.to(self.device, torch.float32)
             return self._inference_segmented(wav, n_q, need_recon, use_scale, bypass)
@@ -133,15 +147,17 @@ class EncodecMI355X:
     # -- Encodec.inference_encoding (codec_basic.py:720-764) ---------------------------------
     @torch.no_grad()
     def inference_encoding(self, speech: torch.Tensor, need_recon: bool = False, bit_width: int = None,
-                           use_scale: bool = True) -> Dict[str, torch.Tensor]:
+                           use_scale: bool = True, speech_lengths=None) -> Dict[str, torch.Tensor]:
         # (model_conf.bypass_quantizer does not reach this entry point in the reference: it quantises, :748-750)
-        return self.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, _quantise_always=True)
+        return self.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, _quantise_always=True,
+                              speech_lengths=speech_lengths)
 
     # -- Encodec.inference_decoding (codec_basic.py:766-802) ---------------------------------
     @torch.no_grad()
     def inference_decoding(self, token_idx: torch.Tensor, need_recon: bool = True, bit_width: int = None,
-                           use_scale: bool = True) -> Dict[str, torch.Tensor]:
-        recon, emb = self.engine.decode_codes(token_idx)
+                           use_scale: bool = True, token_lengths=None) -> Dict[str, torch.Tensor]:
+        """token_lengths [B] (optional): frames per row; row b is then decoded from its own frames alone, zeros behind frames * hop."""
+        recon, emb = self.engine.decode_codes(token_idx, lengths=token_lengths)
         if self.arch.segment_length is not None and need_recon:      # _decode: one frame through the overlap-add (codec_basic.py:396)
             recon = self.engine.overlap_add([recon], self.arch.segment_stride or 1)
         return dict(recon_speech=recon if need_recon else None, code_indices=None,
@@ -150,8 +166,10 @@ class EncodecMI355X:
     # -- Encodec.inference_decoding_emb (codec_basic.py:804-836) -----------------------------
     @torch.no_grad()
     def inference_decoding_emb(self, token_idx: torch.Tensor, need_recon: bool = True, bit_width: int = None,
-                               use_scale: bool = True) -> Dict[str, torch.Tensor]:
-        recon = self.engine.decode_emb(token_idx) if need_recon else None
+                               use_scale: bool = True, token_lengths=None) -> Dict[str, torch.Tensor]:
+        if token_lengths is not None and not need_recon:
+            self.engine._lengths_in(token_lengths, token_idx.shape[0])      # a refused architecture raises whatever is asked for
+        recon = self.engine.decode_emb(token_idx, lengths=token_lengths) if need_recon else None
         if self.arch.segment_length is not None and recon is not None:
             recon = self.engine.overlap_add([recon], self.arch.segment_stride or 1)
         return dict(recon_speech=recon, code_indices=None, code_embeddings=[(token_idx, None)], sub_quants=None)

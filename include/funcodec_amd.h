@@ -163,6 +163,36 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
                      int64_t* codes, float* quantized, float* sub_quants, float* scale, float* recon,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- length-aware (ragged) batches ----------------------------------------------------------------
+ * (entry points added without a struct change: FC_ABI_VERSION stays 7)
+ * A batch [B,Tmax] whose rows have lengths of their own.  `lengths` dev i32 [B], 1 <= lengths[b] <= Tmax (samples for the encode calls,
+ * frames for the decode calls).  Row b of every output equals what the offline callable named below returns for row b ALONE cut at its
+ * length: its volume scale, the GroupNorm statistics of every conv, the reflection padding at its end and the extra_padding of every
+ * strided conv are the row's own.  Row b has fc_engine_frames(lengths[b]) valid frames and lengths[b] (decode: frames * hop) valid samples;
+ * everything behind a row's valid part is written as zero.  A row's valid outputs depend on nothing outside that row: not on the other rows,
+ * not on Tmax, not on what lies behind lengths[b] in the caller's buffers (it is never read).  The output shapes are those of the offline
+ * sibling for (B, Tmax).
+ * Time-domain codec only; refused with the configuration key named: model freq_codec, seq_model: transformer,
+ * quantizer_conf.q0_ds_ratio > 1 (fc_ragged_workspace_bytes returns 0 for these).  A length outside [1, Tmax] is clamped on the device and
+ * reported like an out-of-range code: by the next compute call or fc_engine_status (FC_STATUS_FLAG_BAD_LENGTH). */
+/* workspace of any ragged call with batch B and Tmax samples (or frames * hop); includes the 4 KiB tail slack like fc_engine_workspace_bytes */
+size_t fc_ragged_workspace_bytes(const fc_engine* e, int B, int Tmax);
+/* Encodec.inference_encoding (codec_basic.py:720-764) on wav[b, ..., :lengths[b]], per row; arguments as fc_encode */
+int fc_encode_ragged(fc_engine* e, const float* wav, const int32_t* lengths /* dev [B] */, int B, int T, int n_q,
+                     int64_t* codes, float* quantized, float* sub_quants, float* scale, float* enc_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* Encodec.inference_decoding_emb (codec_basic.py:804-836) on emb[b, :lengths[b]], per row; arguments as fc_decode_emb */
+int fc_decode_emb_ragged(fc_engine* e, const float* emb, const float* scale, const int32_t* lengths /* dev [B], frames */, int B, int Tf,
+                         int out_len, float* wav, void* workspace, size_t workspace_bytes, void* stream);
+/* Encodec.inference_decoding (codec_basic.py:766-802) on codes[b, :lengths[b]], per row; arguments as fc_decode_codes.  Tokens behind a
+ * row's frames are not looked up (and never reported as out of range) */
+int fc_decode_codes_ragged(fc_engine* e, const int64_t* codes, const int32_t* lengths /* dev [B], frames */, int B, int Tf, int n_q,
+                           int out_len, float* wav, float* emb_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Encodec.inference (codec_basic.py:670-718) on wav[b, ..., :lengths[b]], per row; arguments as fc_encode_decode; recon [B,T] */
+int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengths /* dev [B] */, int B, int T, int n_q, int use_scale,
+                            int64_t* codes, float* quantized, float* sub_quants, float* scale, float* recon,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* _linear_overlap_add (funcodec/models/codec_basic.py:77-116), the tail of Encodec._decode (:382-396) when
  * model_conf.segment_dur is set: triangle-weighted overlap-add of the decoded segments, products accumulated in
  * frame order and divided once by the summed weights, exactly as the reference orders it.
@@ -229,6 +259,7 @@ int  fc_stream_lstm_forward(fc_stream* s, int decoder, const float* x, int T, fl
  * Call it after synchronising the stream to learn about the calls enqueued so far. */
 #define FC_STATUS_FLAG_LSTM_TIMEOUT 1u
 #define FC_STATUS_FLAG_BAD_CODE 2u
+#define FC_STATUS_FLAG_BAD_LENGTH 4u   /* a length-aware call saw a row length outside [1, Tmax] (clamped) */
 int fc_engine_status(fc_engine* e, unsigned* flags);
 
 /* ---- per-op entry points (so tests can pin each kernel against torch.nn.functional) -------------- */

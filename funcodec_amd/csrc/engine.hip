@@ -1655,10 +1655,27 @@ Act run_encoder_2d(fc_engine* e, Ctx& cx, const float* wav, int T, const float* 
     return run_conv(e, cx, e->enc_last, a0, a1, 1, x1.T);
 }
 
+// FreqCodec._decode_frame behind the 2-D decoder (codec_freq.py:419-448): the decoder's last conv (raw, frequency-major, its GroupNorm
+// pending as last.aff) -> spectrum rows [B][2F][Tp] -> inverse-DFT GEMM -> envelope division, centre trim, x scale[b], out_len samples.
+// spec_out (fc_freq_synthesis): where the spectrum rows lie in the workspace.
+void run_synthesis_2d(fc_engine* e, Ctx& cx, const Act2& last, const float* scale, int out_len, float* wav, float** spec_out = nullptr) {
+    const fc_arch& a = e->arch;
+    const int B = cx.B, hop = a.stft_hop, F = a.n_fft / 2 + 1, taps = ceil_div_i(a.n_fft, hop);
+    const int Tp2 = last.T, Mp2 = Tp2 + taps - 1;
+    float* spec = cx.alloc<float>((size_t)B * 2 * F * Tp2);
+    if (spec_out) *spec_out = spec;
+    if (!cx.dry && last.F != F) cx.fail("internal: decoder frequency rows != n_fft / 2 + 1");
+    if (!cx.dry && out_len > hop * (Tp2 - 1)) cx.fail("out_len exceeds the inverse STFT's length stft_hop * (frames - 1)");
+    cx.launch("spectrum", "", [&] { return fc::launch_spec_from_dec(last.buf, last.aff, B, F, Tp2, last.halo, a.input_channels, spec, cx.st); });
+    fc::Src ss; ss.ptr = spec; ss.used = 1;
+    Act yp = run_conv(e, cx, e->istft, ss, fc::Src(), 0, Tp2);                      // [B][hop][Mp2]
+    if (!cx.dry && yp.T != Mp2) cx.fail("internal: inverse-STFT GEMM length");
+    cx.launch("istft finish", "", [&] { return fc::launch_istft_finish(yp.raw, e->win2, B, hop, a.n_fft, Mp2, Tp2, scale, out_len, wav, cx.st); });
+}
+
 // SEANetDecoder2d.forward + FreqCodec._decode_frame (codec_freq.py:409-448, mag_phase): z [B][D][Tf] -> wav [B][out_len]
 void run_decoder_2d(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* scale, int out_len, float* wav) {
     const fc_arch& a = e->arch;
-    const int B = cx.B, hop = a.stft_hop, F = a.n_fft / 2 + 1, taps = ceil_div_i(a.n_fft, hop);
     fc::Src s; s.ptr = z_bdt; s.used = 1;
     Act x = run_conv(e, cx, e->dec_first, s, fc::Src(), 0, Tf);
     Act2 a0, a1;
@@ -1678,15 +1695,7 @@ void run_decoder_2d(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const flo
         a0 = sc; a1 = b3; has1 = true;
     }
     Act2 last = run_conv2d(e, cx, e->dec2_last, a0, &a1, 1, 0);                     // [B][F][3][Tp2] raw + GroupNorm(1, 3) affine
-    const int Tp2 = last.T, Mp2 = Tp2 + taps - 1;
-    float* spec = cx.alloc<float>((size_t)B * 2 * F * Tp2);
-    if (!cx.dry && last.F != F) cx.fail("internal: decoder frequency rows != n_fft / 2 + 1");
-    if (!cx.dry && out_len > hop * (Tp2 - 1)) cx.fail("out_len exceeds the inverse STFT's length stft_hop * (frames - 1)");
-    cx.launch("spectrum", "", [&] { return fc::launch_spec_from_dec(last.buf, last.aff, B, F, Tp2, 0, a.input_channels, spec, cx.st); });
-    fc::Src ss; ss.ptr = spec; ss.used = 1;
-    Act yp = run_conv(e, cx, e->istft, ss, fc::Src(), 0, Tp2);                      // [B][hop][Mp2]
-    if (!cx.dry && yp.T != Mp2) cx.fail("internal: inverse-STFT GEMM length");
-    cx.launch("istft finish", "", [&] { return fc::launch_istft_finish(yp.raw, e->win2, B, hop, a.n_fft, Mp2, Tp2, scale, out_len, wav, cx.st); });
+    run_synthesis_2d(e, cx, last, scale, out_len, wav);
 }
 
 int total_hop(const fc_engine* e) {
@@ -2610,6 +2619,61 @@ int fc_layer2d_forward(fc_engine* e, const char* prefix, const float* x0, const 
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     int64_t shape[3];
     return layer2d(e, cx, r, x0, aff0, x1, aff1, F, T, apply_elu, out_halo, y, shape);
+}
+
+namespace {
+// fc_freq_synthesis / fc_freq_synthesis_size: the host-side refusals (they need the architecture only)
+int freq_synthesis_check(const fc_engine* e, int B, int C, int F, int Tp, int out_len) {
+    if (!e) return fail("null argument");
+    const fc_arch& a = e->arch;
+    if (a.model_type != 1) return fail("fc_freq_synthesis: the engine is not an STFT-domain codec (model_type 1)");
+    if (B <= 0) return fail("bad argument");
+    if (C != a.input_channels)
+        return fail("fc_freq_synthesis: dec has " + std::to_string(C) + " channels, the decoder's output has " + std::to_string(a.input_channels));
+    if (F != a.n_fft / 2 + 1)
+        return fail("fc_freq_synthesis: dec has " + std::to_string(F) + " frequency rows, n_fft / 2 + 1 is " + std::to_string(a.n_fft / 2 + 1));
+    if (Tp < 2) return fail("fc_freq_synthesis: the inverse STFT needs at least 2 frames, got " + std::to_string(Tp));
+    const long long full = (long long)a.stft_hop * (Tp - 1);
+    if (out_len < 1 || out_len > full)
+        return fail("fc_freq_synthesis: out_len " + std::to_string(out_len) + " is outside [1, stft_hop * (frames - 1)] = [1, " + std::to_string(full) + "]");
+    return 0;
+}
+
+// dec [B][C][F][Tp] -> the engine's frequency-major rows (halo 0, as run_decoder_2d's last conv leaves them) -> run_synthesis_2d
+int freq_synthesis(fc_engine* e, Ctx& cx, const float* dec, const float* aff, const float* scale, int Tp, int out_len, float* wav, float* spec_out) {
+    const fc_arch& a = e->arch;
+    const int B = cx.B, C = a.input_channels, F = a.n_fft / 2 + 1;
+    Act2 last;
+    last.C = C; last.F = F; last.T = Tp; last.halo = 0;
+    last.buf = cx.alloc<float>((size_t)B * F * C * Tp);
+    last.aff = const_cast<float*>(aff);
+    last.normed = aff != nullptr;
+    cx.launch("input relayout", "", [&] { return fc::launch_feats_relayout(last.buf, const_cast<float*>(dec), B, C, F, Tp, 0, 0, cx.st); });
+    float* spec = nullptr;
+    run_synthesis_2d(e, cx, last, scale, out_len, wav, &spec);
+    if (spec_out)
+        cx.launch("copy", "spectrum", [&] { return hipMemcpyAsync(spec_out, spec, (size_t)B * 2 * F * Tp * sizeof(float), hipMemcpyDeviceToDevice, cx.st); });
+    return cx.err;
+}
+}  // namespace
+
+int fc_freq_synthesis_size(const fc_engine* ce, int B, int C, int F, int Tp, int out_len, size_t* workspace_bytes) {
+    fc_engine* e = const_cast<fc_engine*>(ce);
+    if (freq_synthesis_check(e, B, C, F, Tp, out_len)) return 1;
+    if (!workspace_bytes) return fail("null argument");
+    Ctx cx = dry_ctx(e, B);
+    if (freq_synthesis(e, cx, nullptr, nullptr, nullptr, Tp, out_len, nullptr, nullptr)) return 1;
+    *workspace_bytes = cx.off + 4096;
+    return 0;
+}
+
+int fc_freq_synthesis(fc_engine* e, const float* dec, const float* aff, const float* scale, int B, int C, int F, int Tp, int out_len, float* wav,
+                      float* spec, void* workspace, size_t workspace_bytes, void* stream) {
+    if (freq_synthesis_check(e, B, C, F, Tp, out_len)) return 1;
+    if (!dec || !wav) return fail("bad argument");
+    if (check_ready(e)) return 1;
+    Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
+    return freq_synthesis(e, cx, dec, aff, scale, Tp, out_len, wav, spec);
 }
 
 namespace {

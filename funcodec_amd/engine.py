@@ -506,6 +506,38 @@ class CodecEngine:
                                                 int(out_halo), _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y
 
+    @_on_device
+    def freq_synthesis(self, dec: torch.Tensor, aff: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                       out_len: Optional[int] = None, want_spec: bool = False):
+        """The back end of the STFT-domain codec behind the 2-D decoder (fc_freq_synthesis): dec [B,C,F,Tp] (the decoder's last conv, raw),
+        its pending GroupNorm affine aff [B,C,2] (scale, shift), scale [B] -> wav [B, out_len] (default stft_hop * (Tp - 1)); with
+        want_spec also the spectrum rows [B, 2 F, Tp] (real rows, then imaginary rows) the inverse-DFT GEMM reads."""
+        dec = self._dev(dec, torch.float32)
+        if dec.dim() != 4:
+            raise EngineError(f"freq_synthesis: dec must be [B,C,F,Tp], got {tuple(dec.shape)}")
+        B, Cc, Fq, Tp = dec.shape
+        if out_len is None:
+            out_len = self.arch.stft_hop * (Tp - 1)
+        need = C.c_size_t()
+        self._check(self.lib.fc_freq_synthesis_size(self._h, B, Cc, Fq, Tp, int(out_len), C.byref(need)))
+        if aff is not None:
+            aff = self._dev(aff, torch.float32)
+            if tuple(aff.shape) != (B, Cc, 2):
+                raise EngineError(f"freq_synthesis: the affine must be [B,C,2] = {(B, Cc, 2)}, got {tuple(aff.shape)}")
+        if scale is not None:
+            scale = self._dev(scale.reshape(-1), torch.float32)
+            if scale.numel() != B:
+                raise EngineError(f"freq_synthesis: scale must hold one value per utterance ({B}), got {scale.numel()}")
+        wav = torch.empty((B, int(out_len)), dtype=torch.float32, device=self.device)
+        spec = torch.empty((B, 2 * Fq, Tp), dtype=torch.float32, device=self.device) if want_spec else None
+        if self._ws is None or self._ws.numel() < need.value:
+            self._ws = None
+            self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        ws = self._ws
+        self._check(self.lib.fc_freq_synthesis(self._h, _ptr(dec), _ptr(aff), _ptr(scale), B, Cc, Fq, Tp, int(out_len), _ptr(wav), _ptr(spec),
+                                               _ptr(ws), ws.numel(), self._stream()))
+        return (wav, spec) if want_spec else wav
+
     def freq_halo(self) -> int:
         """Frequency halo rows of the engine's 2-D activations (the out_halo layer2d_forward accepts besides 0)."""
         dims = (C.c_int64 * 5)()

@@ -312,6 +312,22 @@ int fc_layer2d_forward(fc_engine* e, const char* prefix, const float* x0, const 
  * dims[0] and nothing else. */
 int fc_layer2d_out_shape(const fc_engine* e, const char* prefix, int B, int F, int T, int out_halo, int64_t* dims /* [5] */);
 
+/* The back end of the STFT-domain codec behind the 2-D decoder (FreqCodec._decode_frame, codec_freq.py:419-448), through the very function
+ * the decode driver calls after its last conv: softplus(magnitude) x phase (mag_phase, C = 3) or x (cos, sin)(sin(o1) pi) (mag_angle,
+ * C = 2) -> inverse-DFT GEMM -> window-envelope division, centre trim, x scale[b], the first out_len samples.
+ *   dec      dev f32 [B][C][F][Tp] (the reference's layout), C = input_channels, F = n_fft / 2 + 1; copied into a workspace buffer in the
+ *            engine's frequency-major layout without halo rows, as the decoder's last conv leaves its output
+ *   aff      dev f32 [B][C][2] (scale, shift): that conv's pending GroupNorm affine, or NULL (weight_norm nets)
+ *   scale    dev f32 [B] or NULL
+ *   wav      dev f32 [B][out_len], 1 <= out_len <= stft_hop * (Tp - 1)
+ *   spec     dev f32 [B][2 F][Tp] or NULL: the spectrum rows the inverse-DFT GEMM reads (real rows, then imaginary rows)
+ * Refused on the host, before any launch: a time-domain engine, C or F other than the engine's, Tp < 2, out_len outside its range.
+ * A test hook: the drivers never call it. */
+int fc_freq_synthesis(fc_engine* e, const float* dec, const float* aff, const float* scale, int B, int C, int F, int Tp, int out_len,
+                      float* wav, float* spec, void* workspace, size_t workspace_bytes, void* stream);
+/* the same refusals, and the workspace bytes of that call (tail slack included).  Host only. */
+int fc_freq_synthesis_size(const fc_engine* e, int B, int C, int F, int Tp, int out_len, size_t* workspace_bytes);
+
 /* SEANetResnetBlock.forward (seanet_encoder.py:44-61; decoder copy seanet_decoder.py:42-59) addressed by its Sequential
  * prefix ("encoder.model.1", "decoder.model.16"): y = shortcut(x) + block(x), each conv followed by its GroupNorm (when the
  * recipe has one); x, y dev f32 [B,C,T].  Exercises the fused shortcut + block.1 launch of the thin (C <= 64) blocks. */

@@ -242,6 +242,31 @@ def test_layer_call_form_hooks_refuse_on_the_host():
     assert "use fc_layer2d_forward" in feng.lib.fc_last_error().decode()
 
 
+def test_freq_synthesis_refuses_on_the_host():
+    """fc_freq_synthesis_size / fc_freq_synthesis refuse before any launch (no GPU, no weights): a time-domain engine, a wrong channel or
+    row count, fewer than 2 frames, out_len outside [1, stft_hop (frames - 1)]; an accepted shape reports its workspace."""
+    import ctypes as C
+    from funcodec_amd.config import freq_recipe_config
+    need = C.c_size_t(0)
+    p = C.c_void_p(256)
+    teng = CodecEngine(arch_from_config(recipe_config("tiny")))
+    assert teng.lib.fc_freq_synthesis_size(teng._h, 1, 3, 257, 4, 480, C.byref(need)) != 0
+    assert "not an STFT-domain codec" in teng.lib.fc_last_error().decode()
+    for name, ch in (("tinyfreq", 3), ("tinyfreqang", 2)):
+        eng = CodecEngine(arch_from_config(freq_recipe_config(name)))
+        lib, h = eng.lib, eng._h
+        for args, why in (((1, 5 - ch, 257, 4, 480), "channels"), ((1, ch, 256, 4, 480), "frequency rows"), ((1, ch, 257, 1, 1), "at least 2 frames"),
+                          ((1, ch, 257, 4, 0), "out_len 0 is outside"), ((1, ch, 257, 4, 481), "out_len 481 is outside [1, stft_hop * (frames - 1)] = [1, 480]")):
+            assert lib.fc_freq_synthesis_size(h, *args, C.byref(need)) != 0
+            assert why in lib.fc_last_error().decode(), (args, lib.fc_last_error())
+            assert lib.fc_freq_synthesis(h, p, None, None, *args, p, None, p, 1 << 20, None) != 0
+            assert why in lib.fc_last_error().decode(), (args, lib.fc_last_error())
+        assert lib.fc_freq_synthesis_size(h, 3, ch, 257, 4, 480, C.byref(need)) == 0
+        assert need.value > 3 * (ch * 257 * 4 + 2 * 257 * 4) * 4                      # the relayouted input and the spectrum rows at least
+        assert lib.fc_freq_synthesis(h, p, None, None, 3, ch, 257, 4, 480, p, None, p, 1 << 20, None) != 0
+        assert "not finalized" in lib.fc_last_error().decode()
+
+
 def test_engine_sizes_and_work_accounting():
     arch = arch_from_config(recipe_config("ds640"))
     eng = CodecEngine(arch)

@@ -115,6 +115,16 @@ SYMBOLS = {
     "fc_stream_decode_codes": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_stream_decode_emb": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_stream_lstm_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    # slot session: S slots that start, push and end independently in one batch (counts and flags: host int32 [S])
+    "fc_slots_state_bytes": (C.c_size_t, [_P, C.c_int]),
+    "fc_slots_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    "fc_slots_destroy": (None, [_P]),
+    "fc_slots_min_first": (C.c_int, [_P, C.c_int]),
+    "fc_slots_workspace_bytes": (C.c_size_t, [_P]),
+    "fc_slots_encode": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "fc_slots_decode_codes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "fc_slots_decode_emb": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "fc_slots_lstm_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     # LauraTTS generation (ABI version 5)
     "fc_laura_create": (C.c_int, [C.POINTER(FcLauraArch), C.c_int, C.POINTER(_P)]),
     "fc_laura_destroy": (None, [_P]),

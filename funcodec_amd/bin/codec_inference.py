@@ -123,6 +123,10 @@ class Speech2Token:
         `streaming=` keyword selects a data iterator; that keyword keeps its meaning here (accepted, unused)."""
         return self.model.open_stream(batch, n_q=n_q, scale=scale, max_chunk=max_chunk)
 
+    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
+        """A slot session of the loaded (causal) model: funcodec_amd.stream.StreamSlots, independent utterances sharing every push."""
+        return self.model.open_slots(slots, n_q=n_q, max_chunk=max_chunk)
+
     @staticmethod
     def from_pretrained(model_tag: Optional[str] = None, **kwargs: Optional[Any]):
         """Like the reference (codec_inference.py:136-150: "model_tag ... Currently, not used"): the instance is built from **kwargs

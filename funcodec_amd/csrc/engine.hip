@@ -17,6 +17,7 @@
 #include "laura_kernels.h"
 #include "ragged_kernels.h"
 #include "seq_kernels.h"
+#include "slots_kernels.h"
 #include "stream_kernels.h"
 
 namespace {
@@ -188,6 +189,16 @@ struct fc_stream {
     bool broken = false;                            // a push failed half-way: carries are a mix of old and new until the next reset
     int enc_min_first = 0, dec_min_first = 0;       // shortest first push: samples (a hop multiple) / frames
     std::vector<float> ones;
+};
+
+// One slot session (fc_slots_*): S rows that start, continue, end and idle independently in one push.  The state is fc_stream's layout
+// for B = S (stream_layout: scale, carries, LSTM state), ONE caller-owned device allocation; the host keeps each slot's phase per side.
+struct fc_slots {
+    enum Phase : char { Idle, Running, Ended, Poisoned };
+    fc_stream lay;                                  // e, B = S, max_chunk, n_q, state and its layout; the push counters are not used
+    std::vector<char> enc_phase, dec_phase;         // [S]
+    int enc_pushes = 0, dec_pushes = 0;             // the carries' ping-pong parity per side: idle rows copy theirs, so one number serves all
+    std::vector<int32_t> push;                      // [2 S]: counts, then flags, of the push being enqueued (the source of its one copy)
 };
 
 namespace {
@@ -1198,7 +1209,9 @@ inline fc::Src src_of(const Act& a) { fc::Src s; s.ptr = a.raw; s.aff = a.aff; s
 // `carried` (a streaming push; null offline): the per-step kernel's (h, c) buffers inside the session state, which continue the recurrence
 // of the earlier pushes instead of starting from a cleared workspace buffer.  h_l(t) sits at parity t & 1 and step 0 reads parity 1, so
 // after an odd number of steps the last hidden state is copied to where the next push looks for it.
-Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, float* carried = nullptr) {
+// `steps` (a push of a slot session, with `carried`): row b takes ragged_cols(steps) of the T steps; the masked steps keep every row's
+// hidden state at the common parity (kernels.hip lstm_wave_kernel, MASKED), so the copy after an odd T serves all rows.
+Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, float* carried = nullptr, const fc::RagLen* steps = nullptr) {
     const int H = lb.H, B = cx.B, L = (int)lb.layers.size();
     float* xproj = cx.alloc<float>((size_t)T * B * 4 * H);
     run_conv(e, cx, lb.layers[0].inproj, src_of(in), fc::Src(), 0, T, xproj, (long long)4 * H, 1, (long long)B * 4 * H);
@@ -1232,7 +1245,10 @@ Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, f
         cx.launch("lstm", pre, [&] { return fc::launch_lstm_persist(w[0], w[1], bias[1], xproj, state, y.raw, B, H, T, e->status_dev, cx.st); });
     } else {
         for (int s = 0; s < T + L - 1; ++s)
-            cx.launch("lstm step", pre, [&] { return fc::launch_lstm_wave(w, bias, xproj, state, state + 2 * L * BH, y.raw, B, H, T, L, s, cx.st); });
+            cx.launch("lstm step", pre, [&] {
+                return steps ? fc::launch_lstm_wave(w, bias, xproj, state, state + 2 * L * BH, y.raw, B, H, T, L, s, cx.st, steps->lens, steps->div, steps->mul)
+                             : fc::launch_lstm_wave(w, bias, xproj, state, state + 2 * L * BH, y.raw, B, H, T, L, s, cx.st);
+            });
     }
     if (carried && (T & 1))
         for (int l = 0; l < L; ++l)
@@ -1344,6 +1360,11 @@ struct Pass {
     bool ragged = false;
     const int* lengths = nullptr;
     int frame_div = 1;
+    // a push of a slot session: `lengths` (device [S], 0 = idle) and `flags` (device [S], kSlotStart | kSlotFinal) per row, counted as in a
+    // ragged call; n = pushes this side has taken before; host_push = the same counts and flags on the host ([2 S]; null in a dry pass)
+    const fc_slots* Q = nullptr;
+    const int* flags = nullptr;
+    const int32_t* host_push = nullptr;
 };
 
 // the columns of every row at the input of the layer the walk of a ragged pass stands at (the rule: ragged_kernels.h)
@@ -1357,11 +1378,14 @@ inline fc::RagLen ragged_len(const Ctx& cx, const Pass& p) {
 
 Act ragged_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T);
 Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc, int side_pushes, bool final);
+Act slots_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T);
 
 // the conv step: in a push, the layers that carry a left context run over [carry | chunk] (stream_conv); the pointwise ones as offline.
 // In a ragged pass every conv that looks beyond its own column (k > 1) or normalises over the row runs behind a per-row staging pass
 // (ragged_conv); a pointwise weight_norm conv maps column to column and runs as offline, garbage columns included.
+// A push of a slot session is both at once: the layers with a context run behind slots_conv's per-row staging, the pointwise ones as offline.
 Act walk_conv(fc_engine* e, Ctx& cx, const Pass& p, Role role, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T) {
+    if (p.Q) return carries_context(role) ? slots_conv(e, cx, p, L, s0, s1, elu, T) : run_conv(e, cx, L, s0, s1, elu, T);
     if (p.ragged && (L.k > 1 || L.has_norm)) return ragged_conv(e, cx, p, L, s0, s1, elu, T);
     if (p.S && carries_context(role)) return stream_conv(e, cx, p.S, L, s0, s1, elu, T, p.n, p.final);
     return run_conv(e, cx, L, s0, s1, elu, T);
@@ -1374,7 +1398,13 @@ void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x
     const TfBlock& tb = dec ? e->dec_tf : e->enc_tf;
     *a0 = src_of(x); *a1 = fc::Src();
     if (!has_seq(lb, tb)) return;
-    Act y = p.S ? run_lstm(e, cx, lb, x, x.T, p.S->state + (dec ? p.S->dec_lstm_off : p.S->enc_lstm_off)) : run_seq(e, cx, lb, tb, x, x.T);
+    Act y;
+    if (p.Q) {                                        // a slot push: every row takes its own frames of the LSTM's steps
+        const fc::RagLen steps = ragged_len(cx, p);
+        y = run_lstm(e, cx, lb, x, x.T, p.Q->lay.state + (dec ? p.Q->lay.dec_lstm_off : p.Q->lay.enc_lstm_off), &steps);
+    } else {
+        y = p.S ? run_lstm(e, cx, lb, x, x.T, p.S->state + (dec ? p.S->dec_lstm_off : p.S->enc_lstm_off)) : run_seq(e, cx, lb, tb, x, x.T);
+    }
     *a0 = src_of(y);
     if (e->arch.lstm_skip) *a1 = src_of(x);
 }
@@ -1384,7 +1414,7 @@ void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x
 void run_resblocks(fc_engine* e, Ctx& cx, const Pass& p, const fc_engine::Stage& S, fc::Src a0, fc::Src a1, int T, Act* sc, Act* b3) {
     for (const auto& R : S.res) {
         Act b1;
-        if (!p.S && !p.ragged && R.fused_head && !a0.div) {      // the fused head has no form that stages a carry or a row end
+        if (!p.S && !p.Q && !p.ragged && R.fused_head && !a0.div) {      // the fused head has no form that stages a carry or a row end
             run_reshead(e, cx, R, a0, a1, T, sc, &b1);
         } else {
             *sc = walk_conv(e, cx, p, Role::Shortcut, R.shortcut, a0, a1, 0, T);
@@ -1887,6 +1917,35 @@ void stream_layout(fc_engine* e, int B, fc_stream* S) {
     S->dec_min_first = dec_min;
 }
 
+// The GEMM behind the staging pass of a push (stream_conv, slots_conv): the layer's own kernel as a conv without padding over the staged
+// buf [B][cin][Tp], which holds Tc new columns per row behind the left context.
+Act staged_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, const float* buf, int Tp, int Tc) {
+    const int B = cx.B;
+    ConvGeom geo;
+    geo.padL = 0; geo.padR = 0;
+    geo.Tout = L.transposed ? Tc * L.stride : (Tp - ((L.k - 1) * L.dil + 1)) / L.stride + 1;
+    geo.count_T = geo.Tout;
+    fc::ConvLaunch c = conv_launch_of(L, B, Tp, geo);
+    c.s0.ptr = buf; c.s0.used = 1;
+    c.alpha = e->arch.elu_alpha;
+    c.pad_zero = 1;                                   // nothing is padded; columns past the row end of the last tile read as zero
+    Act out;
+    out.C = L.cout; out.T = geo.Tout;
+    if (L.transposed) {                               // group j = taps (x[j-1], x[j]) = staged columns (j, j + 1): Tc groups, all kept
+        c.Tout = Tc; c.up_r = L.stride; c.trimL = 0; c.Tfinal = geo.Tout;
+    } else {
+        c.Tout = geo.Tout;
+    }
+    out.raw = cx.alloc<float>((size_t)B * L.cout * geo.Tout);
+    c.out = out.raw; c.out_sB = (long long)L.cout * geo.Tout; c.out_sM = geo.Tout; c.out_sT = 1;
+    const double fl = 2.0 * B * (double)L.M * L.cin * L.gk * c.Tout;
+    const double by = 4.0 * B * ((double)L.cin * Tp + (double)L.cout * geo.Tout);
+    cx.conv_flops += fl; cx.conv_bytes += by;
+    cx.conv_launch("conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
+    return out;
+}
+
+
 // One causal SConv1d / SConvTranspose1d of a push: the staging pass (prologue + left context + new carry), then the layer's own GEMM
 // kernel as a conv without padding over what was staged.  side_pushes: pushes this side (encoder / decoder) has taken before this one.
 Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc, int side_pushes, bool final) {
@@ -1910,28 +1969,37 @@ Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, f
     }
     cx.launch("stream stage", L.prefix.c_str(), [] { return "stream_stage_kernel (streaming: prologue, left context and carry of a conv)"; }, 0.0,
               4.0 * B * L.cin * ((double)Tc * (s1.used ? 2 : 1) + Tp + 2.0 * pt), [&] { return fc::launch_stream_stage(g, cx.st); });
-    ConvGeom geo;
-    geo.padL = 0; geo.padR = 0;
-    geo.Tout = L.transposed ? Tc * L.stride : (Tp - ((L.k - 1) * L.dil + 1)) / L.stride + 1;
-    geo.count_T = geo.Tout;
-    fc::ConvLaunch c = conv_launch_of(L, B, Tp, geo);
-    c.s0.ptr = buf; c.s0.used = 1;
-    c.alpha = e->arch.elu_alpha;
-    c.pad_zero = 1;                                   // nothing is padded; columns past the row end of the last tile read as zero
-    Act out;
-    out.C = L.cout; out.T = geo.Tout;
-    if (L.transposed) {                               // group j = taps (x[j-1], x[j]) = staged columns (j, j + 1): Tc groups, all kept
-        c.Tout = Tc; c.up_r = L.stride; c.trimL = 0; c.Tfinal = geo.Tout;
-    } else {
-        c.Tout = geo.Tout;
+    return staged_conv(e, cx, L, buf, Tp, Tc);
+}
+
+// One causal SConv1d / SConvTranspose1d of a push of a slot session: stream_conv with every row at its own place in its own utterance.
+// The common staged width holds the widest row with the extra_padding of a last push, whether a row of this push ends or not.
+Act slots_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T) {
+    const fc_stream* S = &p.Q->lay;
+    const int B = cx.B, pt = stream_pt(L);
+    const int Tp = L.transposed ? 1 + T : pt + T + fc::ragged_extra(T, L.k, pt, L.stride);
+    float* buf = cx.alloc<float>((size_t)B * L.cin * Tp);
+    fc::SlotsStage g;
+    g.s0 = s0; g.s1 = s1; g.elu = elu; g.alpha = e->arch.elu_alpha;
+    g.S = B; g.C = L.cin; g.T = T; g.Tp = Tp; g.k = L.k; g.pt = pt; g.stride = L.stride; g.transposed = L.transposed ? 1 : 0;
+    g.len = ragged_len(cx, p); g.flags = p.flags; g.buf = buf;
+    if (!cx.dry && p.host_push)
+        for (int b = 0; b < B; ++b) {                 // what the kernel relies on, per row
+            const int len = p.host_push[b];
+            if (len <= 0) continue;
+            const int n = fc::ragged_cols(len, g.len.div, g.len.mul, 0);
+            const int extra = (!L.transposed && (p.host_push[B + b] & fc::kSlotFinal)) ? fc::ragged_extra(n, L.k, pt, L.stride) : 0;
+            if (n > T || extra > pt + n - 1 || pt + n + extra > Tp) cx.fail("internal: a row of a slot push does not fit its staging (" + L.prefix + ")");
+        }
+    if (pt > 0) {
+        float* pair = S->state + S->carry.at(&L);
+        const size_t n = (size_t)B * L.cin * pt;
+        g.carry_in = pair + (size_t)(p.n & 1) * n;
+        g.carry_out = pair + (size_t)((p.n + 1) & 1) * n;
     }
-    out.raw = cx.alloc<float>((size_t)B * L.cout * geo.Tout);
-    c.out = out.raw; c.out_sB = (long long)L.cout * geo.Tout; c.out_sM = geo.Tout; c.out_sT = 1;
-    const double fl = 2.0 * B * (double)L.M * L.cin * L.gk * c.Tout;
-    const double by = 4.0 * B * ((double)L.cin * Tp + (double)L.cout * geo.Tout);
-    cx.conv_flops += fl; cx.conv_bytes += by;
-    cx.conv_launch("conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
-    return out;
+    cx.launch("slots stage", L.prefix.c_str(), [] { return "slots_stage_kernel (slot session: prologue, per-row context, end and carry of a conv)"; }, 0.0,
+              4.0 * B * L.cin * ((double)T * (s1.used ? 2 : 1) + Tp + 2.0 * pt), [&] { return fc::launch_slots_stage(g, cx.st); });
+    return staged_conv(e, cx, L, buf, Tp, T);
 }
 
 // n: pushes this side of the session has taken before this one (0 = the first push of an utterance)
@@ -2088,6 +2156,129 @@ int stream_decode_check(fc_stream* S, int Tfc) {
         return fail("streaming decode: the first push of an utterance must hold at least " + std::to_string(S->dec_min_first) +
                     " frames (the offline call's reflected left padding spans them); shorter utterances go through the offline call");
     return 0;
+}
+
+
+// ---- slot session ---------------------------------------------------------------------------------------------------------------
+// What a slot must reproduce is what a streaming session reproduces: the OFFLINE callable on the concatenation of the slot's pushes of
+// one utterance, whatever the other slots of the push do.  A push is a pass of the fourth kind (Pass::Q): the staging pass of every conv
+// with a context treats each row by its own count and flags (slots_conv), the LSTM masks the steps a row does not take, the quantiser runs
+// per frame over the common width, and what lies behind a row's valid part of every output is zeroed last (the ragged pass's masking).
+
+int slots_ready(fc_slots* Q) {
+    if (!Q) return fail("null slot session");
+    return check_ready(Q->lay.e);
+}
+
+// The rules of a push (include/funcodec_amd.h), checked for every slot BEFORE anything is enqueued or changed.  `unit`: what a count
+// counts; whole: non-final counts are multiples of it (the hop on the encoder side, 1 frame on the decoder side).
+int slots_check(const fc_slots* Q, bool decode, const int32_t* counts, const int32_t* flags, int width, int max_width) {
+    const int S = Q->lay.B, hop = total_hop(Q->lay.e);
+    const char* side = decode ? "slot decode" : "slot encode";
+    const char* unit = decode ? "frames" : "samples";
+    const std::vector<char>& phase = decode ? Q->dec_phase : Q->enc_phase;
+    const int min_first = decode ? Q->lay.dec_min_first : Q->lay.enc_min_first, whole = decode ? 1 : hop;
+    auto bad = [&](int b, const std::string& what) { return fail(std::string(side) + ": slot " + std::to_string(b) + ": " + what); };
+    if (width < 1 || width > max_width)
+        return fail(std::string(side) + ": a push is 1 .. " + std::to_string(max_width) + " " + unit + " wide (max_chunk_samples), got " + std::to_string(width));
+    int active = 0;
+    for (int b = 0; b < S; ++b) {
+        const int n = counts[b], f = flags[b];
+        if (n < 0 || n > width) return bad(b, "a count lies in [0, the push's width " + std::to_string(width) + "], got " + std::to_string(n));
+        if (f & ~(FC_SLOT_START | FC_SLOT_FINAL)) return bad(b, "unknown flag bits");
+        if (n == 0) {
+            if (f) return bad(b, "an idle slot (count 0) takes no START or FINAL: a push that starts or ends an utterance holds at least one of its " + std::string(unit));
+            continue;
+        }
+        ++active;
+        if (!(f & FC_SLOT_START) && phase[b] != fc_slots::Running)
+            return bad(b, phase[b] == fc_slots::Poisoned
+                              ? "a push of this session failed after it had begun to write carries: the slot's state is invalid until it is restarted with START"
+                              : phase[b] == fc_slots::Ended ? "the utterance took its FINAL push; the next push of this slot needs START"
+                                                            : "no utterance is running: a push without START continues one");
+        if (!(f & FC_SLOT_FINAL) && n % whole != 0)
+            return bad(b, "every push but the FINAL one must be a positive multiple of the hop (" + std::to_string(hop) + " samples), got " + std::to_string(n) +
+                              "; it is not padded silently");
+        if ((f & FC_SLOT_START) && n < min_first)
+            return bad(b, "the START push of an utterance must hold at least " + std::to_string(min_first) + " " + unit +
+                              " (fc_slots_min_first: the offline call's reflected left padding spans them), got " + std::to_string(n));
+    }
+    if (!active) return fail(std::string(side) + ": no slot is active in this push (every count is 0)");
+    return 0;
+}
+
+// the counts and flags of a push on the device, in the workspace: ONE copy out of the session's own host buffer.
+// Q->push is pageable memory that the next push overwrites.  That is correct because the runtime stages a pageable host-to-device copy
+// before hipMemcpyAsync returns (the call is synchronous with respect to the host buffer, as for fc_stream_reset's ones); the price is
+// that the host waits there instead of queueing the next push behind this one.  A push is synchronised by its caller anyway (the wrapper
+// slices its outputs per slot), so a pinned ring that lets pushes queue is left to the HIP-graph work.
+Pass slots_pass(fc_slots* Q, Ctx& cx, bool decode, const int32_t* counts, const int32_t* flags) {
+    const int S = cx.B;
+    Pass p;
+    p.Q = Q; p.n = decode ? Q->dec_pushes : Q->enc_pushes; p.frame_div = 1;
+    int32_t* dev = cx.alloc<int32_t>((size_t)2 * S);
+    p.lengths = dev; p.flags = at(dev, S);
+    if (!cx.dry) {
+        std::copy(counts, counts + S, Q->push.begin());
+        std::copy(flags, flags + S, Q->push.begin() + S);
+        p.host_push = Q->push.data();
+    }
+    cx.launch("copy", "slot counts", [&] { return hipMemcpyAsync(dev, Q->push.data(), (size_t)2 * S * sizeof(int32_t), hipMemcpyHostToDevice, cx.st); });
+    return p;
+}
+
+// the rows that START: LSTM state of the side cleared, and on the encoder side the slot's scale set
+void slots_start(fc_slots* Q, Ctx& cx, const Pass& p, bool decode, const float* scale) {
+    fc_engine* e = Q->lay.e;
+    const LstmBlock& lb = decode ? e->dec_lstm : e->enc_lstm;
+    float* lstm = lb.H ? Q->lay.state + (decode ? Q->lay.dec_lstm_off : Q->lay.enc_lstm_off) : nullptr;
+    if (!lstm && decode) return;
+    cx.launch("slots start", "", [&] {
+        return fc::launch_slots_start(p.flags, cx.B, lstm, (int)lb.layers.size(), lb.H, scale, decode ? nullptr : Q->lay.state, cx.st);
+    });
+}
+
+int slots_encode_pass(fc_slots* Q, Ctx& cx, const float* wav, int Tc, const int32_t* counts, const int32_t* flags, const float* scale, int64_t* codes,
+                      float* quantized, float* enc_out) {
+    fc_engine* e = Q->lay.e;
+    const Pass p = slots_pass(Q, cx, false, counts, flags);
+    slots_start(Q, cx, p, false, scale);
+    fc::Src s; s.ptr = wav; s.div = Q->lay.state; s.used = 3;       // the slots' scale [S]
+    Act last = run_encoder(e, cx, p, s, Tc);
+    const int Tf = frames_for(e, Tc);
+    if (!cx.dry && last.T != Tf) cx.fail("internal: frame count of a slot push");
+    if (do_quantize(e, cx, last, Tf, Q->lay.n_q, codes, quantized, nullptr, enc_out, nullptr)) return 1;
+    Pass m = p; m.frame_div = total_hop(e);                          // ragged_mask_encoded counts samples
+    ragged_mask_encoded(e, cx, m, Tf, Q->lay.n_q, codes, quantized, nullptr, enc_out);
+    return cx.err;
+}
+
+// z: the decoder input [S][D][Tf] of either decode call; what lies behind a row's frames in it is never read (dec_first is staged)
+int slots_decode_pass(fc_slots* Q, Ctx& cx, const Pass& p, const float* z_bdt, int Tf, int use_scale, float* wav) {
+    fc_engine* e = Q->lay.e;
+    slots_start(Q, cx, p, true, nullptr);
+    Act last = run_decoder(e, cx, p, z_bdt, Tf);
+    const int C = e->audio_ch();
+    cx.launch("combine", "", [&] {
+        return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, use_scale ? Q->lay.state : nullptr, cx.B, C, last.T, last.T, wav, (long long)C * last.T,
+                                  last.T, 1, cx.st);
+    });
+    fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(e);
+    cx.launch("ragged mask", "wav", [&] { return fc::launch_ragged_mask_f32(wav, 1, cx.B, C, last.T, 1, v, cx.st); });
+    return cx.err;
+}
+
+// a push has been enqueued (ok) or failed after its first launch: the slots' phases and the side's parity
+void slots_commit(fc_slots* Q, bool decode, const int32_t* counts, const int32_t* flags, bool ok) {
+    std::vector<char>& phase = decode ? Q->dec_phase : Q->enc_phase;
+    if (!ok) {      // carries and LSTM state are a mix of old and new, on both parities: every slot restarts, on either side
+        std::fill(Q->enc_phase.begin(), Q->enc_phase.end(), (char)fc_slots::Poisoned);
+        std::fill(Q->dec_phase.begin(), Q->dec_phase.end(), (char)fc_slots::Poisoned);
+        return;
+    }
+    for (int b = 0; b < Q->lay.B; ++b)
+        if (counts[b] > 0) phase[b] = (flags[b] & FC_SLOT_FINAL) ? fc_slots::Ended : fc_slots::Running;
+    ++(decode ? Q->dec_pushes : Q->enc_pushes);
 }
 
 }  // namespace
@@ -3022,6 +3213,132 @@ int fc_stream_lstm_forward(fc_stream* S, int decoder, const float* x, int T, flo
     HIP_TRY(hipMemcpyAsync(y, out.raw, (size_t)S->B * lb.H * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st));
     S->broken = false;
     return 0;
+}
+
+// ---- slot session (include/funcodec_amd.h) --------------------------------------------------------------------------------------
+size_t fc_slots_state_bytes(const fc_engine* e, int S) { return fc_stream_state_bytes(e, S); }
+
+int fc_slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_slots** out) {
+    if (!e || !out) return fail("null argument");
+    if (!e->finalized) return fail("engine not finalized");
+    if (const char* why = stream_refusal(e)) return fail(why);
+    if (S <= 0 || S > 65535) return fail("bad slot count (1 .. 65535)");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    std::unique_ptr<fc_slots> Q(new fc_slots);
+    fc_stream& lay = Q->lay;
+    lay.e = e; lay.B = S; lay.n_q = n_q; lay.max_chunk = max_chunk_samples;
+    stream_layout(e, S, &lay);
+    const int hop = total_hop(e);
+    if (max_chunk_samples < lay.enc_min_first || max_chunk_samples < lay.dec_min_first * hop)
+        return fail("max_chunk_samples must hold the START push of an utterance: at least " +
+                    std::to_string(std::max(lay.enc_min_first, lay.dec_min_first * hop)) + " samples for this net");
+    if (!state || ((uintptr_t)state & 15) || state_bytes < lay.state_floats * sizeof(float))
+        return fail("slot state: a 16-byte aligned device buffer of fc_slots_state_bytes() bytes");
+    lay.state = (float*)state;
+    // the scale of a slot whose encoder has not started an utterance is 1: decode multiplies by it from the first push on
+    lay.ones.assign(S, 1.f);
+    HIP_TRY(hipMemcpy(state, lay.ones.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice));
+    Q->enc_phase.assign(S, (char)fc_slots::Idle); Q->dec_phase.assign(S, (char)fc_slots::Idle);
+    Q->push.assign((size_t)2 * S, 0);
+    *out = Q.release();
+    return 0;
+}
+
+void fc_slots_destroy(fc_slots* s) { delete s; }
+
+int fc_slots_min_first(const fc_slots* s, int decode) { return s ? (decode ? s->lay.dec_min_first : s->lay.enc_min_first) : 0; }
+
+size_t fc_slots_workspace_bytes(const fc_slots* cq) {
+    fc_slots* Q = const_cast<fc_slots*>(cq);
+    if (!Q) return 0;
+    fc_engine* e = Q->lay.e;
+    const int S = Q->lay.B, hop = total_hop(e), D = e->arch.dimension, Tf = ceil_div_i(Q->lay.max_chunk, hop);
+    float mark;                                    // optional outputs: the pointer only marks presence in a dry pass
+    Ctx ce = dry_ctx(e, S);
+    slots_encode_pass(Q, ce, nullptr, Q->lay.max_chunk, nullptr, nullptr, nullptr, nullptr, &mark, nullptr);   // no enc_out: its rows are then a buffer of the pass
+    Ctx cd = dry_ctx(e, S);
+    const Pass p = slots_pass(Q, cd, true, nullptr, nullptr);
+    cd.alloc<int64_t>((size_t)S * Tf * Q->lay.n_q);                               // masked copy of the tokens
+    float* z = cd.alloc<float>((size_t)S * std::max(D, e->cdim()) * Tf);          // the first buffer of either decode call
+    codes_to_decoder_input(e, cd, nullptr, Tf, Q->lay.n_q, nullptr, &z);
+    slots_decode_pass(Q, cd, p, z, Tf, 1, nullptr);
+    return std::max(ce.off, cd.off) + 4096;
+}
+
+int fc_slots_encode(fc_slots* Q, const float* wav, int Tc, const int32_t* samples, const int32_t* flags, const float* scale, int64_t* codes,
+                    float* quantized, float* enc_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (slots_ready(Q)) return 1;
+    if (!wav || !samples || !flags || !codes) return fail("bad argument");
+    if (slots_check(Q, false, samples, flags, Tc, Q->lay.max_chunk)) return 1;
+    Ctx cx = make_ctx(Q->lay.e, Q->lay.B, workspace, workspace_bytes, stream);
+    const int err = slots_encode_pass(Q, cx, wav, Tc, samples, flags, scale, codes, quantized, enc_out);
+    slots_commit(Q, false, samples, flags, !err);
+    return err;
+}
+
+int fc_slots_decode_emb(fc_slots* Q, const float* emb, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (slots_ready(Q)) return 1;
+    fc_engine* e = Q->lay.e;
+    if (!emb || !frames || !flags || !wav) return fail("bad argument");
+    if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->lay.max_chunk, total_hop(e)))) return 1;
+    Ctx cx = make_ctx(e, Q->lay.B, workspace, workspace_bytes, stream);
+    const Pass p = slots_pass(Q, cx, true, frames, flags);
+    float* z = cx.alloc<float>((size_t)cx.B * e->arch.dimension * Tfc);
+    cx.launch("transpose", "emb", [&] { return fc::launch_transpose_btd(emb, cx.B, Tfc, e->arch.dimension, z, cx.st); });
+    const int err = slots_decode_pass(Q, cx, p, z, Tfc, use_scale, wav);
+    slots_commit(Q, true, frames, flags, !err);
+    return err;
+}
+
+int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
+                          float* emb_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (slots_ready(Q)) return 1;
+    fc_engine* e = Q->lay.e;
+    if (!codes || !frames || !flags || !wav) return fail("bad argument");
+    if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->lay.max_chunk, total_hop(e)))) return 1;
+    const int S = Q->lay.B, n_q = Q->lay.n_q;
+    Ctx cx = make_ctx(e, S, workspace, workspace_bytes, stream);
+    const Pass p = slots_pass(Q, cx, true, frames, flags);
+    fc::RagLen f; f.lens = p.lengths;
+    // the tokens behind a row's frames are the caller's garbage: a masked copy, so that none of them is looked up (or reported as out of range)
+    int64_t* masked = cx.alloc<int64_t>((size_t)S * Tfc * n_q);
+    float* z = cx.alloc<float>((size_t)S * e->cdim() * Tfc);
+    cx.launch("copy", "tokens", [&] { return hipMemcpyAsync(masked, codes, (size_t)S * Tfc * n_q * sizeof(int64_t), hipMemcpyDeviceToDevice, cx.st); });
+    cx.launch("ragged mask", "tokens", [&] { return fc::launch_ragged_mask_i64(masked, 1, S, 1, Tfc, n_q, f, cx.st); });
+    int err = codes_to_decoder_input(e, cx, masked, Tfc, n_q, emb_out, &z);
+    if (!err && emb_out) cx.launch("ragged mask", "emb_out", [&] { return fc::launch_ragged_mask_f32(emb_out, 1, S, 1, Tfc, e->arch.dimension, f, cx.st); });
+    if (!err) err = slots_decode_pass(Q, cx, p, z, Tfc, use_scale, wav);
+    slots_commit(Q, true, frames, flags, !err);
+    return err;
+}
+
+// Test hook: the SLSTM stage of a slot push alone, on the session's encoder (decoder = 0) or decoder (decoder = 1) LSTM state, exactly as a
+// push runs it: the rows with start[b] != 0 begin from zeros, row b takes steps[b] <= T steps.  x, y dev f32 [S][H][T]; steps, start host [S].
+// It does not look at the slots' phases and does not change them.
+int fc_slots_lstm_forward(fc_slots* Q, int decoder, const float* x, int T, const int32_t* steps, const int32_t* start, float* y, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    if (slots_ready(Q)) return 1;
+    fc_engine* e = Q->lay.e;
+    const int S = Q->lay.B;
+    const LstmBlock& lb = decoder ? e->dec_lstm : e->enc_lstm;
+    if (!x || !y || !steps || !start || T <= 0) return fail("bad argument");
+    if (!lb.H) return fail("this net has no LSTM");
+    std::vector<int32_t> fl(S);
+    for (int b = 0; b < S; ++b) {
+        if (steps[b] < 0 || steps[b] > T) return fail("fc_slots_lstm_forward: slot " + std::to_string(b) + ": steps lie in [0, T]");
+        fl[b] = start[b] ? FC_SLOT_START : 0;
+    }
+    Ctx cx = make_ctx(e, S, workspace, workspace_bytes, stream);
+    const Pass p = slots_pass(Q, cx, decoder != 0, steps, fl.data());
+    float* lstm = Q->lay.state + (decoder ? Q->lay.dec_lstm_off : Q->lay.enc_lstm_off);
+    cx.launch("slots start", "", [&] { return fc::launch_slots_start(p.flags, S, lstm, (int)lb.layers.size(), lb.H, nullptr, nullptr, cx.st); });
+    Act in; in.raw = const_cast<float*>(x); in.C = lb.H; in.T = T;
+    fc::RagLen st; st.lens = p.lengths;
+    Act out = run_lstm(e, cx, lb, in, T, lstm, &st);
+    cx.launch("copy", "y", [&] { return hipMemcpyAsync(y, out.raw, (size_t)S * lb.H * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st); });
+    if (cx.err) slots_commit(Q, decoder != 0, steps, fl.data(), false);
+    return cx.err;
 }
 
 }  // extern "C"

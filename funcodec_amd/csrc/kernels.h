@@ -221,8 +221,10 @@ hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D,
 #define FC_LSTM_MAX_LAYERS 4
 // Layer-wavefront step s (see kernels.hip): w[0] = W_hh0 perm [4H][H]; w[l>=1] = [W_ih_l | W_hh_l] perm [4H][2H];
 // bias[l>=1] = perm(b_ih + b_hh); h [L][2][B][H] and c [L][B][H] zero-initialised by the caller.
+// steps (a push of a slot session; null: every row takes all T steps): device [B], row b takes ceil(steps[b] / sdiv) * smul <= T steps;
+// a step beyond that carries the row's h across the parity, leaves its c alone and writes y = 0.
 hipError_t launch_lstm_wave(const float* const* w, const float* const* bias, const float* xproj, float* h, float* c,
-                            float* y, int B, int H, int T, int L, int s, hipStream_t st);
+                            float* y, int B, int H, int T, int L, int s, hipStream_t st, const int* steps = nullptr, int sdiv = 1, int smul = 1);
 
 // Persistent 2-layer recurrence (one launch); sync = 2 zeroed words; h [2][2][B][H] zeroed by the caller.
 hipError_t launch_lstm_persist(const float* w0, const float* w1, const float* bias1, const float* xproj, float* state, float* y,

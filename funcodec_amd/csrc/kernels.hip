@@ -1966,9 +1966,15 @@ struct LstmWaveArgs {
     float* c;
     float* y;
     int B, H, T, L, s, KS;
+    // MASKED form only (a push of a slot session): row b takes ceil(steps[b] / sdiv) * smul of the T steps
+    const int* steps;
+    int sdiv, smul;
 };
 
-template <int NS>
+// MASKED: a step beyond a row's own count carries h_l across the parity and leaves c alone (y = 0 there), so that after the launch
+// sequence every row's last hidden state sits at the same parity whatever its count.  A live step of a row is computed exactly as in the
+// plain form (rows are independent columns of the MFMA).
+template <int NS, bool MASKED = false>
 __global__ __launch_bounds__(256) void lstm_wave_kernel(const LstmWaveArgs p) {
     __shared__ f32x4 red[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -2041,7 +2047,12 @@ __global__ __launch_bounds__(256) void lstm_wave_kernel(const LstmWaveArgs p) {
         if (wid == 0) {
             f32x4 sgate = red[0][lane];
             for (int w = 1; w < p.KS; ++w) sgate = sgate + red[w][lane];
-            if (bvalid) {
+            bool masked = false;
+            if (MASKED) masked = bvalid && t >= (p.steps[brow] + p.sdiv - 1) / p.sdiv * p.smul;
+            if (masked) {
+                h_out[ci] = h_own_prev[ci];
+                if (layer == p.L - 1) p.y[ci * p.T + t] = 0.f;
+            } else if (bvalid) {
                 const float gi = sigmoid_f(sgate[0] + xp[0]);
                 const float gf = sigmoid_f(sgate[1] + xp[1]);
                 const float gg = tanh_f(sgate[2] + xp[2]);
@@ -2058,16 +2069,28 @@ __global__ __launch_bounds__(256) void lstm_wave_kernel(const LstmWaveArgs p) {
 }
 
 hipError_t launch_lstm_wave(const float* const* w, const float* const* bias, const float* xproj, float* h, float* c,
-                            float* y, int B, int H, int T, int L, int s, hipStream_t st) {
-    if (H % 16 != 0 || L < 1 || L > FC_LSTM_MAX_LAYERS) return hipErrorInvalidValue;
+                            float* y, int B, int H, int T, int L, int s, hipStream_t st, const int* steps, int sdiv, int smul) {
+    if (H % 16 != 0 || L < 1 || L > FC_LSTM_MAX_LAYERS || (steps && (sdiv < 1 || smul < 1))) return hipErrorInvalidValue;
     LstmWaveArgs a;
     for (int l = 0; l < FC_LSTM_MAX_LAYERS; ++l) { a.w[l] = l < L ? w[l] : nullptr; a.bias[l] = l < L ? bias[l] : nullptr; }
     a.xproj = xproj; a.h = h; a.c = c; a.y = y; a.B = B; a.H = H; a.T = T; a.L = L; a.s = s;
+    a.steps = steps; a.sdiv = sdiv; a.smul = smul;
     int KS = 4;
     while (KS > 1 && (H % (16 * KS)) != 0) KS >>= 1;
     a.KS = KS;
     const int ns = H / (16 * KS);
     dim3 grid(L * (H / 4)), block(256);
+    if (steps) {
+        switch (ns) {
+            case 1: hipLaunchKernelGGL((lstm_wave_kernel<1, true>), grid, block, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((lstm_wave_kernel<2, true>), grid, block, 0, st, a); break;
+            case 4: hipLaunchKernelGGL((lstm_wave_kernel<4, true>), grid, block, 0, st, a); break;
+            case 8: hipLaunchKernelGGL((lstm_wave_kernel<8, true>), grid, block, 0, st, a); break;
+            case 16: hipLaunchKernelGGL((lstm_wave_kernel<16, true>), grid, block, 0, st, a); break;
+            default: hipLaunchKernelGGL((lstm_wave_kernel<0, true>), grid, block, 0, st, a); break;
+        }
+        return hipGetLastError();
+    }
     switch (ns) {
         case 1: hipLaunchKernelGGL(lstm_wave_kernel<1>, grid, block, 0, st, a); break;
         case 2: hipLaunchKernelGGL(lstm_wave_kernel<2>, grid, block, 0, st, a); break;

@@ -48,6 +48,12 @@ class EncodecMI355X:
         from .stream import CodecStream
         return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk)
 
+    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
+        """A slot session of a causal checkpoint (funcodec_amd/stream.py StreamSlots): `slots` independent utterances that start, push
+        and end at their own times and share every push of the batch; n_q quantisers (default: all), at most max_chunk samples per call."""
+        from .stream import StreamSlots
+        return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk)
+
     # -- helpers -------------------------------------------------------------------------------
     def _as_bct(self, speech: torch.Tensor) -> torch.Tensor:
         if speech.dim() == 2:

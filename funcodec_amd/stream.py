@@ -1,4 +1,5 @@
-"""Streaming encode / decode for causal checkpoints (``norm: weight_norm, causal: true``) on top of the fc_stream_* calls.
+"""Streaming encode / decode for causal checkpoints (``norm: weight_norm, causal: true``) on top of the fc_stream_* calls
+(``CodecStream``: one batch in lock-step) and the fc_slots_* calls (``StreamSlots``: slots that start, push and end independently).
 
 The reference has no streaming implementation (``streaming=`` of ``funcodec/bin/codec_inference.py`` selects a data
 iterator), so the specification is causality itself: pushing an utterance through in chunks gives what the offline call
@@ -7,7 +8,7 @@ iterator), so the specification is causality itself: pushing an utterance throug
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -221,6 +222,299 @@ class CodecStream:
         return y
 
 
+FC_SLOT_START, FC_SLOT_FINAL = 1, 2
+
+
+class _Side:
+    """what the wrapper keeps per slot and side (encode / decode)"""
+    __slots__ = ("head", "started", "ended")
+
+    def __init__(self):
+        self.head, self.started, self.ended = [], False, False
+
+
+class StreamSlots:
+    """``slots`` independent utterances streamed through ONE batch; obtained from ``EncodecMI355X.open_slots``.
+
+    A push is bound by its launches, so 32 callers in one push cost about what one costs.  Each slot holds one utterance at a
+    time and does, per slot, what ``CodecStream`` does for its batch: the pushes of one utterance add up to the offline call on that
+    utterance alone, whatever the other slots do in the meantime.
+
+    * ``encode({slot: (wav, final)}) -> {slot: (codes [n_q,Tf], quantized [Tf,D])}`` (plus the encoder output [Tf,D] with
+      ``want_enc_out``); ``wav`` is [C,T] or [T]; a bare tensor means ``final=False``.  Every push of a slot but its final one is a
+      positive multiple of ``hop`` samples.  Slots that are not named sit idle; slots that emitted nothing are not in the result.
+    * ``decode({slot: (codes [Tf,n_q], final)})`` / ``decode_emb({slot: (emb [Tf,D], final)}) -> {slot: wav [C,Tf*hop]}``.
+    * ``start(slot, scale=None)`` begins the next utterance of a slot (a fresh session has every slot started, scale 1); on a slot whose
+      utterance is still running it abandons that utterance.  There is no ``end``: the final push ends an utterance.
+
+    Per slot: pushes are held back until ``min_first_samples`` / ``min_first_frames`` have arrived, then everything held comes
+    out at once; an utterance that ends shorter than that raises (the offline call's job); what is longer than ``max_chunk`` is split.
+    A call is checked as a whole before anything is pushed: a refused call changes nothing, and neither does a call whose first push
+    the library refuses by one of its rules (it refuses before its first launch).  Any other error from the library -- a push that
+    fails after it has begun, or a refusal after part of the call has been pushed -- invalidates every slot until it is restarted with
+    ``start``, as the library itself then demands.
+
+    Volume scale: one per utterance, set at ``start`` (default 1; a slot that was never started has scale 1).  It reaches the library
+    with the utterance's first encode push and with its first decode push, so ``decode(use_scale=True)`` multiplies by it in a slot
+    that only decodes as well.
+    """
+
+    def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
+        why = stream_refusal(model.arch)
+        if why:
+            raise EngineError(why)
+        self.model, self.engine, self.arch = model, model.engine, model.arch
+        eng = self.engine
+        self.lib, self.device = eng.lib, eng.device
+        self.slots = int(slots)
+        self.n_q = int(n_q) if n_q is not None else self.arch.num_quantizers
+        self.hop = eng.hop_length
+        self.pad_value = 0.0          # what the assembled batch holds behind a row's count and in idle rows (never read; a test aid)
+        self._h = None
+        self._open(max_chunk)
+        self._enc = [_Side() for _ in range(self.slots)]
+        self._dec = [_Side() for _ in range(self.slots)]
+        self._scale = [1.0] * self.slots
+        self._poisoned = [False] * self.slots
+
+    @_on_device
+    def _open(self, max_chunk):
+        eng = self.engine
+        nbytes = int(self.lib.fc_slots_state_bytes(eng._h, self.slots))
+        if nbytes == 0:
+            raise EngineError("this engine cannot stream")
+        #: everything the session carries between pushes (fc_slots_state_bytes): one allocation; fc_slots_create writes the scales (1)
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        if self.state.is_cuda:
+            torch.cuda.current_stream(self.device).synchronize()      # the library's copy is synchronous and not ordered with this stream
+        self.max_chunk = int(max_chunk) if max_chunk is not None else 100 * self.hop
+        h = C.c_void_p()
+        eng._check(self.lib.fc_slots_create(eng._h, self.slots, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
+        self._h = h
+        self.min_first_samples = int(self.lib.fc_slots_min_first(h, 0))
+        self.min_first_frames = int(self.lib.fc_slots_min_first(h, 1))
+        self._ws_bytes = int(self.lib.fc_slots_workspace_bytes(h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self.lib.fc_slots_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _ws(self) -> torch.Tensor:
+        eng = self.engine
+        if eng._ws is None or eng._ws.numel() < self._ws_bytes:
+            eng._ws = None
+            eng._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+        return eng._ws
+
+    def _slot(self, slot) -> int:
+        if not isinstance(slot, int) or not 0 <= slot < self.slots:
+            raise EngineError(f"this session has slots 0 .. {self.slots - 1}, got {slot!r}")
+        return slot
+
+    def start(self, slot: int, scale=None) -> None:
+        slot = self._slot(slot)
+        self._enc[slot], self._dec[slot] = _Side(), _Side()
+        self._scale[slot] = 1.0 if scale is None else float(torch.as_tensor(scale).reshape(()))
+        self._poisoned[slot] = False
+
+    # -- what CodecStream does for its batch, per slot ------------------------------------------------
+    def _plan(self, sides, pushes, tdim, unit, min_first, what):
+        """Per named slot: the pieces [(tensor, flags)] this call pushes for it (none while it gathers its start-up) and the slot's
+        state afterwards.  Raises before anything is changed."""
+        plan = {}
+        for slot, item in pushes.items():
+            slot = self._slot(slot)
+            x, final = item if isinstance(item, tuple) else (item, False)
+            sd = sides[slot]
+            length = lambda t: t.shape[tdim]
+            n = length(x)
+            if self._poisoned[slot]:
+                raise EngineError(f"slot {slot}: a push of this session failed inside the library; start({slot}) begins the next utterance")
+            if sd.ended:
+                raise EngineError(f"slot {slot}: the utterance took its final push; start({slot}) begins the next one")
+            if n < 1 or (unit > 1 and not final and n % unit != 0):
+                raise EngineError(f"slot {slot}: every push but the final one must be a positive multiple of the hop ({self.hop} samples), "
+                                  f"got {n}; it is not padded silently")
+            head, flags = sd.head + [x], 0
+            if not sd.started:
+                have = sum(length(t) for t in head)
+                if have < min_first:
+                    if final:
+                        raise EngineError(f"slot {slot}: the utterance ends after {have} {what}, fewer than the {min_first} the first push must hold "
+                                          "(the offline call's reflected left padding spans them); it goes through the offline call")
+                    plan[slot] = ([], head, False, False)
+                    continue
+                flags = FC_SLOT_START
+            plan[slot] = (self._pieces(head, flags, bool(final), tdim, unit), [], True, bool(final))
+        return plan
+
+    def _pieces(self, head, flags, final, tdim, unit):
+        """what is longer than a call takes: whole-hop pieces, the rest (with the final flag) last"""
+        x = torch.cat(head, tdim) if len(head) > 1 else head[0]
+        n, cap = x.shape[tdim], self.max_chunk // (self.hop // unit)      # samples (unit = hop) or frames (unit = 1) per call
+        step = cap // unit * unit
+        out, pos = [], 0
+        while pos < n:
+            m = n - pos if n - pos <= cap else step
+            part = x.narrow(tdim, pos, m)
+            out.append((part, flags | (FC_SLOT_FINAL if final and pos + m == n else 0)))
+            flags, pos = 0, pos + m
+        return out
+
+    def _run(self, sides, plan, call) -> Dict[int, List]:
+        """commit the plan and push its pieces round by round: round r holds piece r of every slot that has one"""
+        before = {slot: (sides[slot].head, sides[slot].started, sides[slot].ended) for slot in plan}
+        for slot, (pieces, head, started, ended) in plan.items():
+            sides[slot].head, sides[slot].started, sides[slot].ended = head, started, ended
+        outs: Dict[int, List] = {}
+        rounds = max((len(v[0]) for v in plan.values()), default=0)
+        r = 0
+        try:
+            for r in range(rounds):
+                rows = {slot: v[0][r] for slot, v in plan.items() if r < len(v[0])}
+                for slot, res in call(rows).items():
+                    outs.setdefault(slot, []).append(res)
+        except EngineError as err:
+            # the library's rule refusals ("slot encode: ..." / "slot decode: ...", slots_check) come before its first launch and change
+            # nothing there: if nothing of this call has been pushed either, the call is undone here too
+            if r == 0 and str(err).startswith(("slot encode:", "slot decode:")):
+                for slot, (head, started, ended) in before.items():
+                    sides[slot].head, sides[slot].started, sides[slot].ended = head, started, ended
+            else:
+                self._poisoned = [True] * self.slots
+            raise
+        return outs
+
+    def _counts(self, rows, length):
+        counts, flags = (C.c_int32 * self.slots)(), (C.c_int32 * self.slots)()
+        for slot, (x, f) in rows.items():
+            counts[slot], flags[slot] = length(x), f
+        return counts, flags
+
+    # -- encode --------------------------------------------------------------------------------------
+    def _encode_call(self, rows, want_enc_out):
+        S, D, ch = self.slots, self.arch.dimension, self.engine.channels
+        counts, flags = self._counts(rows, lambda w: w.shape[-1])
+        Tc = max(counts)
+        Tf = self.engine.frames(Tc)
+        wav = torch.full((S, ch, Tc), self.pad_value, dtype=torch.float32, device=self.device)
+        scale = None
+        for slot, (w, f) in rows.items():
+            wav[slot, :, :w.shape[-1]] = w
+            if f & FC_SLOT_START and scale is None:
+                scale = torch.ones(S, dtype=torch.float32)
+        if scale is not None:
+            for slot, (w, f) in rows.items():
+                if f & FC_SLOT_START:
+                    scale[slot] = self._scale[slot]
+            scale = scale.to(self.device)
+        codes = torch.empty((self.n_q, S, Tf), dtype=torch.int64, device=self.device)
+        quant = torch.empty((S, Tf, D), dtype=torch.float32, device=self.device)
+        enc = torch.empty((S, Tf, D), dtype=torch.float32, device=self.device) if (self.arch.bypass_quantizer or want_enc_out) else None
+        ws = self._ws()
+        self.engine._check(self.lib.fc_slots_encode(self._h, _ptr(wav), Tc, counts, flags, _ptr(scale), _ptr(codes), _ptr(quant), _ptr(enc),
+                                                    _ptr(ws), ws.numel(), self.engine._stream()))
+        out = {}
+        for slot, (w, f) in rows.items():
+            n = self.engine.frames(w.shape[-1]) if f & FC_SLOT_FINAL else w.shape[-1] // self.hop
+            if self.arch.bypass_quantizer:     # codec_basic.py:700-701: the encoder output in place of the quantised embeddings
+                out[slot] = (torch.zeros((n,), dtype=torch.long, device=self.device), enc[slot, :n], enc[slot, :n])
+            else:
+                out[slot] = (codes[:, slot, :n], quant[slot, :n], enc[slot, :n] if enc is not None else None)
+        return out
+
+    @_on_device
+    def encode(self, pushes, want_enc_out: bool = False) -> Dict[int, Tuple[torch.Tensor, ...]]:
+        ch = self.engine.channels
+
+        def as_ct(item):
+            w, final = item if isinstance(item, tuple) else (item, False)
+            w = self.engine._dev(torch.as_tensor(w), torch.float32)
+            if w.dim() == 1:
+                w = w.unsqueeze(0)
+            if w.dim() != 2 or w.shape[0] != ch:
+                raise EngineError(f"a slot's wav must be [{ch},T]" + (" or [T]" if ch == 1 else "") + f", got {tuple(w.shape)}")
+            return w, final
+        pushes = {slot: as_ct(item) for slot, item in pushes.items()}
+        plan = self._plan(self._enc, pushes, -1, self.hop, self.min_first_samples, "samples")
+        outs = self._run(self._enc, plan, lambda rows: self._encode_call(rows, want_enc_out))
+        cat = lambda parts, i, dim: torch.cat([p[i] for p in parts], dim) if len(parts) > 1 else parts[0][i]
+        return {slot: (cat(parts, 0, -1), cat(parts, 1, 0)) + ((cat(parts, 2, 0),) if want_enc_out else ()) for slot, parts in outs.items()}
+
+    # -- decode --------------------------------------------------------------------------------------
+    def _decode_call(self, rows, use_scale, emb):
+        S, ch, inner = self.slots, self.engine.channels, (self.arch.dimension if emb else self.n_q)
+        counts, flags = self._counts(rows, lambda t: t.shape[0])
+        Tf = max(counts)
+        if emb:
+            x = torch.full((S, Tf, inner), self.pad_value, dtype=torch.float32, device=self.device)
+        else:
+            x = torch.zeros((S, Tf, inner), dtype=torch.int64, device=self.device)
+        for slot, (t, f) in rows.items():
+            x[slot, :t.shape[0]] = t
+        starts = [slot for slot, (t, f) in rows.items() if f & FC_SLOT_START]
+        if starts:      # the utterance's scale, for a slot whose encoder has not set it: the first S floats of the state (funcodec_amd.h)
+            vals = torch.tensor([self._scale[slot] for slot in starts], dtype=torch.float32).to(self.device)
+            self.state[:4 * S].view(torch.float32)[torch.tensor(starts, device=self.device)] = vals
+        wav = torch.empty((S, ch, Tf * self.hop), dtype=torch.float32, device=self.device)
+        ws = self._ws()
+        if emb:
+            rc = self.lib.fc_slots_decode_emb(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), _ptr(ws), ws.numel(), self.engine._stream())
+        else:
+            rc = self.lib.fc_slots_decode_codes(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(),
+                                                self.engine._stream())
+        self.engine._check(rc)
+        return {slot: (wav[slot, :, :t.shape[0] * self.hop],) for slot, (t, f) in rows.items()}
+
+    def _decode(self, pushes, use_scale, emb):
+        inner, dtype = (self.arch.dimension, torch.float32) if emb else (self.n_q, torch.int64)
+
+        def as_tn(item):
+            t, final = item if isinstance(item, tuple) else (item, False)
+            t = self.engine._dev(torch.as_tensor(t), dtype)
+            if t.dim() != 2 or t.shape[1] != inner:
+                raise EngineError(f"a slot's {'emb' if emb else 'codes'} must be [Tf,{inner}], got {tuple(t.shape)}")
+            return t, final
+        pushes = {slot: as_tn(item) for slot, item in pushes.items()}
+        plan = self._plan(self._dec, pushes, 0, 1, self.min_first_frames, "frames")
+        outs = self._run(self._dec, plan, lambda rows: self._decode_call(rows, use_scale, emb))
+        return {slot: torch.cat([p[0] for p in parts], -1) if len(parts) > 1 else parts[0][0] for slot, parts in outs.items()}
+
+    @_on_device
+    def decode(self, pushes, use_scale: bool = True) -> Dict[int, torch.Tensor]:
+        """{slot: (codes [Tf,n_q], final)} -> {slot: wav [C,Tf*hop]}.  final=True says the slot's utterance ends here: it changes no sample
+        but raises if frames are still held back, and the slot then needs ``start``."""
+        return self._decode(pushes, use_scale, False)
+
+    @_on_device
+    def decode_emb(self, pushes, use_scale: bool = True) -> Dict[int, torch.Tensor]:
+        """{slot: (emb [Tf,D], final)} -> {slot: wav [C,Tf*hop]}; final as in decode"""
+        return self._decode(pushes, use_scale, True)
+
+    @_on_device
+    def lstm_forward(self, x: torch.Tensor, steps, start, decoder: bool = False) -> torch.Tensor:
+        """Test hook (fc_slots_lstm_forward): the SLSTM stage of a slot push alone on the session's encoder / decoder LSTM state:
+        x [S,H,T] -> [S,H,T]; slot b takes steps[b] <= T steps (zeros behind) and begins from zeros where start[b]."""
+        x = self.engine._dev(x, torch.float32)
+        S, H, T = x.shape
+        if S != self.slots or H != self.arch.bottleneck_channels or len(steps) != S or len(start) != S:
+            raise EngineError(f"lstm_forward: x must be [{self.slots},{self.arch.bottleneck_channels},T] with one step count and start flag per slot")
+        y = torch.empty_like(x)
+        need = 4 * (T * S * 4 * H + 2 * S * H * T) + (1 << 20)
+        eng = self.engine
+        if eng._ws is None or eng._ws.numel() < need:
+            eng._ws = None
+            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = eng._ws
+        st, fl = (C.c_int32 * S)(*[int(v) for v in steps]), (C.c_int32 * S)(*[int(bool(v)) for v in start])
+        eng._check(self.lib.fc_slots_lstm_forward(self._h, int(decoder), _ptr(x), T, st, fl, _ptr(y), _ptr(ws), ws.numel(), eng._stream()))
+        return y
+
+
 # ---- the per-layer geometry of a push, restated in Python (tests/test_stream_host.py checks it against torch) ------------------
 def conv_layers(arch):
     """Every conv of the 1-D encoder and decoder that carries a left context, in execution order:
@@ -289,3 +583,38 @@ def min_first(arch):
         if L["kind"] == "conv":                   # a transposed conv starts from a zero column: nothing to hold
             frames[L["side"]] = max(frames[L["side"]], -(-(L["carry"] + 1) // L["cols_per_frame"]))
     return frames["encoder"] * hop, frames["decoder"]
+
+
+# ---- the per-row staging rule of a slot push, restated in Python (tests/test_slots_host.py checks it against torch) -----------------
+def slot_staged_width(layer, t: int) -> int:
+    """columns of the staged buffer of a slot push whose common width at `layer` is t: it holds the widest row with the extra padding of
+    a last push, whether a row of this push ends or not"""
+    if layer["kind"] == "convtr":
+        return 1 + t
+    pt = layer["carry"]
+    return pt + t + extra_padding(t, layer["k"], layer["stride"], pt)
+
+
+def stage_slot_row(layer, carry, row, start: bool, final: bool, tp: int):
+    """What slots_stage_kernel writes for one row of a push: (staged [cin, tp], new carry [cin, carry columns]).
+    row [cin, n] is the activated input of the row's own n columns (n = 0: an idle row).  [left | row | extra if final | zeros] with
+    left = the reflection of the row's own columns 1..pt at START (zeros in front of a transposed conv), else the carry; the new carry is
+    the last pt columns of [left | row]; an idle row stages zeros and keeps its carry."""
+    import torch.nn.functional as F
+    pt, tr, n = layer["carry"], layer["kind"] == "convtr", row.shape[-1]
+    if n == 0:
+        return row.new_zeros(row.shape[0], tp), carry
+    if start:
+        if tr:
+            left = row.new_zeros(row.shape[0], pt)
+        else:                                          # pad1d zero-extends a row not longer than the padding before it reflects
+            ext = torch.cat([row, row.new_zeros(row.shape[0], max(0, pt + 1 - n))], -1)
+            left = ext[:, 1:pt + 1].flip(-1)
+    else:
+        left = carry
+    buf = torch.cat([left, row], -1)
+    new_carry = buf[:, buf.shape[-1] - pt:]
+    extra = extra_padding(n, layer["k"], layer["stride"], pt) if (final and not tr) else 0
+    if extra:
+        buf = F.pad(buf[None], (0, extra), "reflect")[0]
+    return torch.cat([buf, row.new_zeros(row.shape[0], tp - buf.shape[-1])], -1), new_carry

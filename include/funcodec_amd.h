@@ -250,6 +250,55 @@ int  fc_stream_decode_emb(fc_stream* s, const float* emb, int Tfc, int use_scale
  * decoder (decoder = 1) LSTM state: x, y dev f32 [B][H][T]; consecutive calls continue one recurrence, as consecutive pushes do. */
 int  fc_stream_lstm_forward(fc_stream* s, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- slot session: S slots that start, push and end independently in ONE batch ------------------------------------------
+ * A streaming push is bound by its launches, so S independent callers cost about what one costs when they share a push.  A slot
+ * session has S slots, each one utterance at a time; the specification is the streaming session's: the pushes of one utterance
+ * add up to the offline call on that utterance alone, whatever the other slots do (they may hold NaN: nothing behind a row's
+ * count is read).  The state is the streaming session's for B = S (one caller-owned buffer, nothing allocated per push), the
+ * refusals at create are the same, and so is the start-up rule (fc_slots_min_first).
+ *
+ * A push is [S][..][width] with, per slot, a count (samples for encode, frames for decode) and flags, both HOST int32 [S]:
+ *   count 0                 the slot sits idle in this push (flags must be 0); its state is carried over untouched
+ *   FC_SLOT_START           the push begins an utterance: left context by reflection, LSTM state cleared, and (encode) the slot's
+ *                           volume scale set from scale[slot] (dev f32 [S]; NULL = 1).  scale is read for START rows only;
+ *                           decode multiplies by the slot's current scale when use_scale is set.  START on a slot whose utterance
+ *                           is still running abandons that utterance (allowed)
+ * The slots' scales are the first S floats of the state buffer.  fc_slots_create writes 1 into them (a synchronous copy: the
+ * buffer must be allocated and not in use by then), so a slot whose encoder never started decodes with scale 1; a caller that
+ * only decodes may write a slot's scale there itself, on the stream of its pushes, before the slot's decode START.
+ *   FC_SLOT_FINAL           the push ends the utterance (with START: a whole utterance in one push): an encode row takes the
+ *                           reference's extra_padding at every layer and may have any count >= 1; a decode row changes no sample
+ * The rules, checked for every slot BEFORE the first launch -- a refused push changes nothing, the message names the slot and the rule:
+ *   - 1 <= width <= max_chunk_samples (decode: / hop, rounded up); every count in [0, width]; at least one slot active;
+ *   - a push without START needs a running utterance in that slot (one that has STARTed and not taken its FINAL push);
+ *   - a push without FINAL is a positive multiple of the hop (encode); it is never padded silently;
+ *   - a START push holds at least fc_slots_min_first samples / frames.
+ * Encoder and decoder phases of a slot are separate.  Outputs are laid out as in the streaming calls over the common width; behind
+ * a row's valid part (ceil(count / hop) frames, count * hop samples) every output is zero.
+ * A push that fails after its first launch (workspace too small, a launch error) leaves carries half written: every slot then
+ * refuses to continue until it is restarted with START, on either side.
+ * Calls on one engine, its sessions included, are serialised by the caller. */
+#define FC_SLOT_START 1
+#define FC_SLOT_FINAL 2
+typedef struct fc_slots fc_slots;
+size_t fc_slots_state_bytes(const fc_engine* e, int S);        /* 0: this engine cannot stream */
+int  fc_slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, void* state /* dev */, size_t state_bytes, fc_slots** out);
+void fc_slots_destroy(fc_slots* s);
+int  fc_slots_min_first(const fc_slots* s, int decode);
+size_t fc_slots_workspace_bytes(const fc_slots* s);
+/*   wav dev f32 [S][C][Tc];  codes dev i64 [n_q][S][fc_engine_frames(Tc)];  quantized, enc_out dev f32 [S][frames][D] or NULL */
+int  fc_slots_encode(fc_slots* s, const float* wav, int Tc, const int32_t* samples, const int32_t* flags, const float* scale, int64_t* codes,
+                     float* quantized, float* enc_out, void* workspace, size_t workspace_bytes, void* stream);
+/*   codes dev i64 [S][Tfc][n_q];  emb dev f32 [S][Tfc][D];  wav dev f32 [S][C][Tfc * hop];  emb_out as fc_decode_codes */
+int  fc_slots_decode_codes(fc_slots* s, const int64_t* codes, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
+                           float* emb_out, void* workspace, size_t workspace_bytes, void* stream);
+int  fc_slots_decode_emb(fc_slots* s, const float* emb, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* Test hook: the SLSTM stage of a slot push alone on the session's encoder / decoder LSTM state: x, y dev f32 [S][H][T]; row b takes
+ * steps[b] <= T steps (a step beyond leaves its (h, c) as they were, y = 0 there) and begins from zeros where start[b] != 0; both host [S]. */
+int  fc_slots_lstm_forward(fc_slots* s, int decoder, const float* x, int T, const int32_t* steps, const int32_t* start, float* y,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Deferred device-side failures.  Kernels cannot return a status, so two conditions are recorded in host-visible
  * status words and reported by the NEXT fc_* compute call on the engine (non-zero return, message in fc_last_error(),
  * condition cleared) or by this call.  *flags (may be NULL) receives the conditions pending at entry:

@@ -174,28 +174,31 @@ struct fc_engine {
     }
 };
 
-// One streaming session of a causal time-domain engine (fc_stream_*).  Everything that survives a push lives in `state`, ONE device
-// allocation of the caller (fc_stream_state_bytes): [scale B] [per conv with a left context: carry [2][B][cin][pt], ping-pong on the parity
-// of the side's push count] [encoder LSTM h [L][2][B][H] | c [L][B][H]] [decoder LSTM the same].  The host side keeps only push counters.
-struct fc_stream {
+// What both kinds of session of a causal time-domain engine keep.  Everything that survives a push lives in `state`, ONE device allocation
+// of the caller (fc_stream_state_bytes; stream_layout): [scale B] [per conv with a left context: carry [2][B][cin][pt], ping-pong on the
+// parity of the side's push count] [encoder LSTM h [L][2][B][H] | c [L][B][H]] [decoder LSTM the same].
+struct Session {
     fc_engine* e = nullptr;
-    int B = 0, max_chunk = 0, n_q = 0;
+    int B = 0, max_chunk = 0, n_q = 0;              // B: the rows of a push (utterances in lock-step / slots)
     float* state = nullptr;
     size_t state_floats = 0;
     std::map<const ConvLayer*, size_t> carry;       // float offset of the layer's carry pair inside state
     size_t enc_lstm_off = 0, dec_lstm_off = 0;
-    int enc_pushes = 0, dec_pushes = 0;
-    bool enc_done = false;                          // the final push has been taken
-    bool broken = false;                            // a push failed half-way: carries are a mix of old and new until the next reset
     int enc_min_first = 0, dec_min_first = 0;       // shortest first push: samples (a hop multiple) / frames
     std::vector<float> ones;
 };
 
-// One slot session (fc_slots_*): S rows that start, continue, end and idle independently in one push.  The state is fc_stream's layout
-// for B = S (stream_layout: scale, carries, LSTM state), ONE caller-owned device allocation; the host keeps each slot's phase per side.
-struct fc_slots {
+// One streaming session (fc_stream_*): B utterances in lock-step.  The host side keeps only push counters.
+struct fc_stream : Session {
+    int enc_pushes = 0, dec_pushes = 0;
+    bool enc_done = false;                          // the final push has been taken
+    bool broken = false;                            // a push failed half-way: carries are a mix of old and new until the next reset
+};
+
+// One slot session (fc_slots_*): B = S rows that start, continue, end and idle independently in one push; the host keeps each slot's
+// phase per side.
+struct fc_slots : Session {
     enum Phase : char { Idle, Running, Ended, Poisoned };
-    fc_stream lay;                                  // e, B = S, max_chunk, n_q, state and its layout; the push counters are not used
     std::vector<char> enc_phase, dec_phase;         // [S]
     int enc_pushes = 0, dec_pushes = 0;             // the carries' ping-pong parity per side: idle rows copy theirs, so one number serves all
     std::vector<int32_t> push;                      // [2 S]: counts, then flags, of the push being enqueued (the source of its one copy)
@@ -1348,21 +1351,21 @@ void run_reshead(fc_engine* e, Ctx& cx, const fc_engine::ResBlock& R, fc::Src a0
     conv_finish(e, cx, R.block1, c.part_b1, nblk, (double)hid * T, b1->aff);
 }
 
-// ---- the forward walk of the time-domain nets: ONE walk for an offline call and for a push of a streaming session.  The two kinds of
-// pass differ in three places and nowhere else: the conv step (walk_conv), the head of a residual block (run_resblocks) and the
-// bottleneck (run_bottleneck).
+// ---- the forward walk of the time-domain nets: ONE walk for an offline call, a ragged call and a push of either kind of session.  The
+// four kinds of pass differ in three places and nowhere else: the conv step (walk_conv), the head of a residual block (run_resblocks) and
+// the bottleneck (run_bottleneck).
 struct Pass {
-    const fc_stream* S = nullptr;   // the session of a push; null: an offline call over the whole utterance
-    int n = 0;                      // pushes this side (encoder / decoder) of the session has taken before this one
-    bool final = false;             // the utterance's last encoder push (a decoder push never is)
-    // a length-aware (ragged) call: every row ends at its own length.  lengths: device [B], clamped (null in a dry pass); they count
+    enum Kind { Offline, Stream, Ragged, Slots } kind = Offline;     // Offline: one call over the whole utterance, nothing below is read
+    // Stream, Slots (a push): the session, and the pushes this side (encoder / decoder) of it has taken before this one
+    const Session* sess = nullptr;
+    int n = 0;
+    // Stream: the utterance's last encoder push (a decoder push never is)
+    bool final = false;
+    // Ragged, Slots: every row ends at its own length.  lengths: device [B], clamped (null in a dry pass; 0 = an idle slot); they count
     // encoder input samples, or, on the decoder side, what frame_div of them make a frame (the hop behind an encoder, 1 for token_lengths)
-    bool ragged = false;
     const int* lengths = nullptr;
     int frame_div = 1;
-    // a push of a slot session: `lengths` (device [S], 0 = idle) and `flags` (device [S], kSlotStart | kSlotFinal) per row, counted as in a
-    // ragged call; n = pushes this side has taken before; host_push = the same counts and flags on the host ([2 S]; null in a dry pass)
-    const fc_slots* Q = nullptr;
+    // Slots: `flags` (device [S], kSlotStart | kSlotFinal) per row; host_push = the counts and flags on the host ([2 S]; null in a dry pass)
     const int* flags = nullptr;
     const int32_t* host_push = nullptr;
 };
@@ -1377,33 +1380,41 @@ inline fc::RagLen ragged_len(const Ctx& cx, const Pass& p) {
 }
 
 Act ragged_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T);
-Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc, int side_pushes, bool final);
+Act stream_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc);
 Act slots_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T);
+float* lstm_state(const Session& s, bool dec);
 
-// the conv step: in a push, the layers that carry a left context run over [carry | chunk] (stream_conv); the pointwise ones as offline.
-// In a ragged pass every conv that looks beyond its own column (k > 1) or normalises over the row runs behind a per-row staging pass
-// (ragged_conv); a pointwise weight_norm conv maps column to column and runs as offline, garbage columns included.
-// A push of a slot session is both at once: the layers with a context run behind slots_conv's per-row staging, the pointwise ones as offline.
+// the conv step.  A push stages the layers that carry a left context and runs them over [carry | chunk] (stream_conv; slots_conv with
+// every row at its own place); its pointwise layers run as offline.  A ragged pass stages every conv that looks beyond its own column
+// (k > 1) or normalises over the row (ragged_conv); a pointwise weight_norm conv maps column to column and runs as offline, garbage
+// columns included.
 Act walk_conv(fc_engine* e, Ctx& cx, const Pass& p, Role role, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T) {
-    if (p.Q) return carries_context(role) ? slots_conv(e, cx, p, L, s0, s1, elu, T) : run_conv(e, cx, L, s0, s1, elu, T);
-    if (p.ragged && (L.k > 1 || L.has_norm)) return ragged_conv(e, cx, p, L, s0, s1, elu, T);
-    if (p.S && carries_context(role)) return stream_conv(e, cx, p.S, L, s0, s1, elu, T, p.n, p.final);
+    switch (p.kind) {
+        case Pass::Stream: if (carries_context(role)) return stream_conv(e, cx, p, L, s0, s1, elu, T); break;
+        case Pass::Slots: if (carries_context(role)) return slots_conv(e, cx, p, L, s0, s1, elu, T); break;
+        case Pass::Ragged: if (L.k > 1 || L.has_norm) return ragged_conv(e, cx, p, L, s0, s1, elu, T); break;
+        case Pass::Offline: break;
+    }
     return run_conv(e, cx, L, s0, s1, elu, T);
 }
 
 // the bottleneck of one side: the sources of the conv behind it = the sequence model's output (plus its input with lstm_skip), or x itself
-// in a net without one.  A push continues the per-step LSTM on the session's state (stream_refusal: no transformer in a stream).
+// in a net without one.  A push continues the per-step LSTM on the session's state (stream_refusal: no transformer in a session).
 void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x, fc::Src* a0, fc::Src* a1) {
     const LstmBlock& lb = dec ? e->dec_lstm : e->enc_lstm;
     const TfBlock& tb = dec ? e->dec_tf : e->enc_tf;
     *a0 = src_of(x); *a1 = fc::Src();
     if (!has_seq(lb, tb)) return;
     Act y;
-    if (p.Q) {                                        // a slot push: every row takes its own frames of the LSTM's steps
-        const fc::RagLen steps = ragged_len(cx, p);
-        y = run_lstm(e, cx, lb, x, x.T, p.Q->lay.state + (dec ? p.Q->lay.dec_lstm_off : p.Q->lay.enc_lstm_off), &steps);
-    } else {
-        y = p.S ? run_lstm(e, cx, lb, x, x.T, p.S->state + (dec ? p.S->dec_lstm_off : p.S->enc_lstm_off)) : run_seq(e, cx, lb, tb, x, x.T);
+    switch (p.kind) {
+        case Pass::Stream: y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec)); break;
+        case Pass::Slots: {                               // every row takes its own frames of the LSTM's steps
+            const fc::RagLen steps = ragged_len(cx, p);
+            y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec), &steps);
+            break;
+        }
+        case Pass::Ragged:                                // forward in time, rows independent: as offline, garbage columns included
+        case Pass::Offline: y = run_seq(e, cx, lb, tb, x, x.T); break;
     }
     *a0 = src_of(y);
     if (e->arch.lstm_skip) *a1 = src_of(x);
@@ -1414,7 +1425,7 @@ void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x
 void run_resblocks(fc_engine* e, Ctx& cx, const Pass& p, const fc_engine::Stage& S, fc::Src a0, fc::Src a1, int T, Act* sc, Act* b3) {
     for (const auto& R : S.res) {
         Act b1;
-        if (!p.S && !p.Q && !p.ragged && R.fused_head && !a0.div) {      // the fused head has no form that stages a carry or a row end
+        if (p.kind == Pass::Offline && R.fused_head && !a0.div) {      // the fused head has no form that stages a carry or a row end
             run_reshead(e, cx, R, a0, a1, T, sc, &b1);
         } else {
             *sc = walk_conv(e, cx, p, Role::Shortcut, R.shortcut, a0, a1, 0, T);
@@ -1427,7 +1438,7 @@ void run_resblocks(fc_engine* e, Ctx& cx, const Pass& p, const fc_engine::Stage&
 
 // SEANetEncoder.forward: wav [B][C][T] (a chunk of it in a push; with the caller's divisor) -> last conv (raw + affine), T -> Tf
 Act run_encoder(fc_engine* e, Ctx& cx, const Pass& p, fc::Src wav, int T) {
-    cx.dec_side = false; cx.rate = 1; cx.no_xq = p.ragged;
+    cx.dec_side = false; cx.rate = 1; cx.no_xq = p.kind == Pass::Ragged;
     Act x = walk_conv(e, cx, p, Role::First, e->enc_first, wav, fc::Src(), 0, T);
     for (auto& S : e->enc_stages) {
         Act sc, b3;
@@ -1444,7 +1455,7 @@ Act run_encoder(fc_engine* e, Ctx& cx, const Pass& p, fc::Src wav, int T) {
 // without look-ahead (causal unpad1d trims on the right only).
 Act run_decoder(fc_engine* e, Ctx& cx, const Pass& p, const float* z_bdt, int Tf) {
     fc::Src s; s.ptr = z_bdt; s.used = 1;
-    cx.dec_side = true; cx.rate = 1; cx.no_xq = p.ragged;
+    cx.dec_side = true; cx.rate = 1; cx.no_xq = p.kind == Pass::Ragged;
     Act x = walk_conv(e, cx, p, Role::First, e->dec_first, s, fc::Src(), 0, Tf);
     fc::Src a0, a1;
     run_bottleneck(e, cx, p, true, x, &a0, &a1);
@@ -1757,7 +1768,7 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
     if (e->arch.audio_normalize) {
         sc = scale ? scale : cx.alloc<float>(B);
         cx.launch("volume", "", [&] {
-            return p.ragged ? fc::launch_ragged_volume(wav, B, e->audio_ch(), T, p.lengths, sc, cx.st) : fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st);
+            return p.kind == Pass::Ragged ? fc::launch_ragged_volume(wav, B, e->audio_ch(), T, p.lengths, sc, cx.st) : fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st);
         });
     }
     fc::Src s; s.ptr = wav; s.div = sc; s.used = e->arch.audio_normalize ? 3 : 1;
@@ -1812,36 +1823,63 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
     return cx.err;
 }
 
-int do_decode(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* scale, int out_len, float* wav, const Pass& p = Pass()) {
+// The tail of every decode pass, into the caller's wav [B][C][out_len]: the final GroupNorm apply (decoder.model.N.conv.norm has C = audio
+// channels), x scale (codec_basic.py:406-407), trim (:711); `valid` (rows that end at their own length): zeros behind every row's samples
+int finish_decode(fc_engine* e, Ctx& cx, const Act& last, const float* scale, int out_len, float* wav, const fc::RagLen* valid) {
+    const int C = e->audio_ch();
+    cx.launch("combine", "", [&] {
+        return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, scale, cx.B, C, last.T, out_len, wav, (long long)C * out_len, out_len, 1, cx.st);
+    });
+    if (valid) cx.launch("ragged mask", "wav", [&] { return fc::launch_ragged_mask_f32(wav, 1, cx.B, C, out_len, 1, *valid, cx.st); });
+    return cx.err;
+}
+
+int do_decode(fc_engine* e, Ctx& cx, const float* z_bdt, int Tf, const float* scale, int out_len, float* wav, const Pass& p = Pass(),
+              const fc::RagLen* valid = nullptr) {
     if (e->arch.model_type == 1) {
         run_decoder_2d(e, cx, z_bdt, Tf, scale, out_len, wav);
         return cx.err;
     }
     Act last = run_decoder(e, cx, p, z_bdt, Tf);
     if (!cx.dry && out_len > last.T) cx.fail("out_len exceeds Tf*hop");
-    // final GroupNorm apply (decoder.model.N.conv.norm has C = audio channels), x scale (codec_basic.py:406-407), trim (:711)
-    const int C = e->audio_ch();
-    cx.launch("combine", "", [&] {
-        return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, scale, cx.B, C, last.T, out_len, wav, (long long)C * out_len, out_len, 1, cx.st);
-    });
-    return cx.err;
+    return finish_decode(e, cx, last, scale, out_len, wav, valid);
 }
 
-// Codes to decoder input (fc_decode_codes, fc_stream_decode_codes): the summed code vectors of `codes` [n_q][B][Tf] into *z [B][Dc][Tf],
-// then CostumeQuantizer.decode's output_proj on them (costume_quantizer.py:114-119).  On return *z is the decoder's input [B][D][Tf];
-// emb_out (optional) gets the embeddings [B][Tf][D].
-int codes_to_decoder_input(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, int n_q, float* emb_out, float** z) {
-    const int B = cx.B, D = e->arch.dimension;
-    if (cx.err) return 1;
-    if (cx.live())
-        HIP_TRY(fc::launch_rvq_decode(codes, B, Tf, n_q, e->cdim(), e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, *z, e->status_dev, cx.st));
-    if (!e->q_proj) return 0;
-    fc::Src qs; qs.ptr = *z; qs.used = 1;
-    Act qo = run_conv(e, cx, e->q_out, qs, fc::Src(), 0, Tf);
-    if (cx.err) return 1;
-    if (emb_out && cx.live()) HIP_TRY(fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, emb_out, (long long)Tf * D, 1, D, cx.st));
-    *z = qo.raw;
-    return 0;
+// Embeddings to decoder input (the decode_emb calls): emb [B][Tf][D] into z [B][D][Tf].  What lies behind a row's frames in a ragged
+// call or a slot push is never read (dec_first is staged).
+float* decoder_input_emb(fc_engine* e, Ctx& cx, const float* emb, int Tf) {
+    const int D = e->arch.dimension;
+    float* z = cx.alloc<float>((size_t)cx.B * D * Tf);
+    cx.launch("transpose", "emb", [&] { return fc::launch_transpose_btd(emb, cx.B, Tf, D, z, cx.st); });
+    return z;
+}
+
+// Codes to decoder input (the decode_codes calls): the summed code vectors of `codes` [B][Tf][n_q] into [B][Dc][Tf], then
+// CostumeQuantizer.decode's output_proj on them (costume_quantizer.py:114-119).  Returns the decoder's input [B][D][Tf]; emb_out
+// (optional) gets the embeddings [B][Tf][D].  `rows` (null, or the frames of every row of a ragged call / slot push): the tokens behind a
+// row's frames are the caller's garbage, so a masked copy is looked up (none of them is read, or reported as out of range) and emb_out is
+// masked too.  `either` (workspace sizing): the first buffer as wide as the wider of the two decode calls needs it.
+float* decoder_input_codes(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, int n_q, float* emb_out, const fc::RagLen* rows, bool either = false) {
+    const int B = cx.B, D = e->arch.dimension, Dc = e->cdim();
+    if (rows) {
+        int64_t* masked = cx.alloc<int64_t>((size_t)B * Tf * n_q);
+        cx.launch("copy", "tokens", [&] { return hipMemcpyAsync(masked, codes, (size_t)B * Tf * n_q * sizeof(int64_t), hipMemcpyDeviceToDevice, cx.st); });
+        cx.launch("ragged mask", "tokens", [&] { return fc::launch_ragged_mask_i64(masked, 1, B, 1, Tf, n_q, *rows, cx.st); });
+        codes = masked;
+    }
+    float* z = cx.alloc<float>((size_t)B * (either ? std::max(D, Dc) : Dc) * Tf);
+    cx.launch("rvq decode", "", [&] {
+        return fc::launch_rvq_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st);
+    });
+    if (e->q_proj) {
+        fc::Src qs; qs.ptr = z; qs.used = 1;
+        Act qo = run_conv(e, cx, e->q_out, qs, fc::Src(), 0, Tf);
+        if (emb_out)
+            cx.launch("combine", "", [&] { return fc::launch_combine(src_of(qo), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, emb_out, (long long)Tf * D, 1, D, cx.st); });
+        z = qo.raw;
+    }
+    if (rows && emb_out) cx.launch("ragged mask", "emb_out", [&] { return fc::launch_ragged_mask_f32(emb_out, 1, B, 1, Tf, D, *rows, cx.st); });
+    return z;
 }
 
 // Deferred device-side failures of EARLIER calls (kernels cannot return a status): reported once, then cleared.
@@ -1895,7 +1933,7 @@ const char* stream_refusal(const fc_engine* e) {
     return nullptr;
 }
 
-void stream_layout(fc_engine* e, int B, fc_stream* S) {
+void stream_layout(fc_engine* e, int B, Session* S) {
     size_t off = ((size_t)B + 63) & ~(size_t)63;      // scale [B]
     const int hop = total_hop(e);
     int enc_min = hop, dec_min = 1;
@@ -1917,72 +1955,97 @@ void stream_layout(fc_engine* e, int B, fc_stream* S) {
     S->dec_min_first = dec_min;
 }
 
-// The GEMM behind the staging pass of a push (stream_conv, slots_conv): the layer's own kernel as a conv without padding over the staged
-// buf [B][cin][Tp], which holds Tc new columns per row behind the left context.
-Act staged_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, const float* buf, int Tp, int Tc) {
+// the carry of layer L inside the session state: a push reads the one at the parity of the n pushes its side has taken and writes the other
+struct CarryPair { const float* in = nullptr; float* out = nullptr; };
+CarryPair carry_pair(const Session& s, const ConvLayer& L, int n) {
+    CarryPair c;
+    const int pt = stream_pt(L);
+    if (pt <= 0) return c;
+    float* pair = s.state + s.carry.at(&L);
+    const size_t half = (size_t)s.B * L.cin * pt;
+    c.in = pair + (size_t)(n & 1) * half;
+    c.out = pair + (size_t)(~n & 1) * half;
+    return c;
+}
+
+// the session's LSTM state of one side (run_lstm's `carried`)
+float* lstm_state(const Session& s, bool dec) { return s.state + (dec ? s.dec_lstm_off : s.enc_lstm_off); }
+
+// The GEMM behind every staging pass (stream_conv, slots_conv, ragged_conv): the layer's own kernel as a conv without padding over the
+// staged buf [B][cin][Tp], which holds T new columns per row behind the left context.  A transposed layer computes `groups` tap pairs
+// (group j = taps (x[j-1], x[j]) = staged columns (j, j + 1)) and drops trimL columns on the left.  With a GroupNorm behind it, which sees
+// the UNTRIMMED output (conv.py:287-303), all groups * stride columns are `stored` at pitch `pitch` and `out` is the trimmed window into them.
+struct Staged { Act out; float* stored = nullptr; int pitch = 0; };
+Staged staged_conv(fc_engine* e, Ctx& cx, const ConvLayer& L, const float* buf, int Tp, int T, int groups, int trimL) {
     const int B = cx.B;
     ConvGeom geo;
     geo.padL = 0; geo.padR = 0;
-    geo.Tout = L.transposed ? Tc * L.stride : (Tp - ((L.k - 1) * L.dil + 1)) / L.stride + 1;
+    geo.Tout = L.transposed ? T * L.stride : (Tp - ((L.k - 1) * L.dil + 1)) / L.stride + 1;
     geo.count_T = geo.Tout;
     fc::ConvLaunch c = conv_launch_of(L, B, Tp, geo);
     c.s0.ptr = buf; c.s0.used = 1;
     c.alpha = e->arch.elu_alpha;
     c.pad_zero = 1;                                   // nothing is padded; columns past the row end of the last tile read as zero
-    Act out;
-    out.C = L.cout; out.T = geo.Tout;
-    if (L.transposed) {                               // group j = taps (x[j-1], x[j]) = staged columns (j, j + 1): Tc groups, all kept
-        c.Tout = Tc; c.up_r = L.stride; c.trimL = 0; c.Tfinal = geo.Tout;
+    Staged r;
+    r.out.C = L.cout; r.out.T = geo.Tout;
+    r.pitch = geo.Tout;
+    const bool untrimmed = L.transposed && L.has_norm;
+    if (L.transposed) {
+        c.Tout = groups; c.up_r = L.stride;
+        if (untrimmed) {
+            r.pitch = groups * L.stride;
+            c.trimL = 0; c.Tfinal = r.pitch;
+            r.out.ld = r.pitch;
+        } else {
+            c.trimL = trimL; c.Tfinal = geo.Tout;
+        }
     } else {
         c.Tout = geo.Tout;
     }
-    out.raw = cx.alloc<float>((size_t)B * L.cout * geo.Tout);
-    c.out = out.raw; c.out_sB = (long long)L.cout * geo.Tout; c.out_sM = geo.Tout; c.out_sT = 1;
+    r.stored = cx.alloc<float>((size_t)B * L.cout * r.pitch);
+    r.out.raw = untrimmed ? at(r.stored, trimL) : r.stored;
+    c.out = r.stored; c.out_sB = (long long)L.cout * r.pitch; c.out_sM = r.pitch; c.out_sT = 1;
     const double fl = 2.0 * B * (double)L.M * L.cin * L.gk * c.Tout;
-    const double by = 4.0 * B * ((double)L.cin * Tp + (double)L.cout * geo.Tout);
+    const double by = 4.0 * B * ((double)L.cin * Tp + (double)L.cout * r.pitch);
     cx.conv_flops += fl; cx.conv_bytes += by;
     cx.conv_launch("conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
-    return out;
+    return r;
 }
 
-
 // One causal SConv1d / SConvTranspose1d of a push: the staging pass (prologue + left context + new carry), then the layer's own GEMM
-// kernel as a conv without padding over what was staged.  side_pushes: pushes this side (encoder / decoder) has taken before this one.
-Act stream_conv(fc_engine* e, Ctx& cx, const fc_stream* S, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc, int side_pushes, bool final) {
+// kernel as a conv without padding over what was staged.
+Act stream_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc) {
     const int B = cx.B, pt = stream_pt(L);
     // the last push takes the reference's extra_padding (conv.py:57-64): earlier pushes are multiples of the stride, so the figure for the
     // whole utterance is the one conv_geom gives the last chunk
-    const int extra = (!L.transposed && final) ? conv_geom(L, Tc).padR : 0;
+    const int extra = (!L.transposed && p.final) ? conv_geom(L, Tc).padR : 0;
     const int Tp = pt + Tc + extra;
     float* buf = cx.alloc<float>((size_t)B * L.cin * Tp);
-    if (!cx.dry && !L.transposed && !final && Tc % L.stride != 0) cx.fail("internal: a chunk that is not a multiple of the stride (" + L.prefix + ")");
+    if (!cx.dry && !L.transposed && !p.final && Tc % L.stride != 0) cx.fail("internal: a chunk that is not a multiple of the stride (" + L.prefix + ")");
     if (!cx.dry && extra > pt + Tc - 1) cx.fail("internal: extra padding longer than the staged columns (" + L.prefix + ")");
+    const CarryPair carry = carry_pair(*p.sess, L, p.n);
     fc::StreamStage g;
     g.s0 = s0; g.s1 = s1; g.elu = elu; g.alpha = e->arch.elu_alpha;
     g.B = B; g.C = L.cin; g.Tc = Tc; g.pt = pt; g.padR = extra; g.buf = buf;
-    g.left = side_pushes > 0 ? 0 : (L.transposed ? 2 : 1);
-    if (pt > 0) {
-        float* pair = S->state + S->carry.at(&L);
-        const size_t n = (size_t)B * L.cin * pt;
-        g.carry_in = pair + (size_t)(side_pushes & 1) * n;
-        g.carry_out = pair + (size_t)((side_pushes + 1) & 1) * n;
-    }
+    g.left = p.n > 0 ? 0 : (L.transposed ? 2 : 1);
+    g.carry_in = carry.in; g.carry_out = carry.out;
     cx.launch("stream stage", L.prefix.c_str(), [] { return "stream_stage_kernel (streaming: prologue, left context and carry of a conv)"; }, 0.0,
               4.0 * B * L.cin * ((double)Tc * (s1.used ? 2 : 1) + Tp + 2.0 * pt), [&] { return fc::launch_stream_stage(g, cx.st); });
-    return staged_conv(e, cx, L, buf, Tp, Tc);
+    return staged_conv(e, cx, L, buf, Tp, Tc, Tc, 0).out;
 }
 
 // One causal SConv1d / SConvTranspose1d of a push of a slot session: stream_conv with every row at its own place in its own utterance.
 // The common staged width holds the widest row with the extra_padding of a last push, whether a row of this push ends or not.
 Act slots_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T) {
-    const fc_stream* S = &p.Q->lay;
     const int B = cx.B, pt = stream_pt(L);
     const int Tp = L.transposed ? 1 + T : pt + T + fc::ragged_extra(T, L.k, pt, L.stride);
     float* buf = cx.alloc<float>((size_t)B * L.cin * Tp);
+    const CarryPair carry = carry_pair(*p.sess, L, p.n);
     fc::SlotsStage g;
     g.s0 = s0; g.s1 = s1; g.elu = elu; g.alpha = e->arch.elu_alpha;
     g.S = B; g.C = L.cin; g.T = T; g.Tp = Tp; g.k = L.k; g.pt = pt; g.stride = L.stride; g.transposed = L.transposed ? 1 : 0;
     g.len = ragged_len(cx, p); g.flags = p.flags; g.buf = buf;
+    g.carry_in = carry.in; g.carry_out = carry.out;
     if (!cx.dry && p.host_push)
         for (int b = 0; b < B; ++b) {                 // what the kernel relies on, per row
             const int len = p.host_push[b];
@@ -1991,36 +2054,30 @@ Act slots_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src
             const int extra = (!L.transposed && (p.host_push[B + b] & fc::kSlotFinal)) ? fc::ragged_extra(n, L.k, pt, L.stride) : 0;
             if (n > T || extra > pt + n - 1 || pt + n + extra > Tp) cx.fail("internal: a row of a slot push does not fit its staging (" + L.prefix + ")");
         }
-    if (pt > 0) {
-        float* pair = S->state + S->carry.at(&L);
-        const size_t n = (size_t)B * L.cin * pt;
-        g.carry_in = pair + (size_t)(p.n & 1) * n;
-        g.carry_out = pair + (size_t)((p.n + 1) & 1) * n;
-    }
     cx.launch("slots stage", L.prefix.c_str(), [] { return "slots_stage_kernel (slot session: prologue, per-row context, end and carry of a conv)"; }, 0.0,
               4.0 * B * L.cin * ((double)T * (s1.used ? 2 : 1) + Tp + 2.0 * pt), [&] { return fc::launch_slots_stage(g, cx.st); });
-    return staged_conv(e, cx, L, buf, Tp, T);
+    return staged_conv(e, cx, L, buf, Tp, T, T, 0).out;
 }
 
-// n: pushes this side of the session has taken before this one (0 = the first push of an utterance)
+// a push of a streaming session; n: pushes this side has taken before this one (0 = the first push of an utterance)
+Pass stream_pass(const fc_stream* S, int n, bool final) {
+    Pass p;
+    p.kind = Pass::Stream; p.sess = S; p.n = n; p.final = final;
+    return p;
+}
+
 int stream_encode_pass(const fc_stream* S, Ctx& cx, int n, const float* wav, int Tc, bool final, int64_t* codes, float* quantized, float* enc_out) {
     fc_engine* e = S->e;
     fc::Src s; s.ptr = wav; s.div = S->state; s.used = 3;       // the session's scale [B] (ones when reset gave none)
-    Act last = run_encoder(e, cx, Pass{S, n, final}, s, Tc);
+    Act last = run_encoder(e, cx, stream_pass(S, n, final), s, Tc);
     const int Tfc = final ? frames_for(e, Tc) : Tc / total_hop(e);
     if (!cx.dry && last.T != Tfc) cx.fail("internal: frame count of a streaming push");
     return do_quantize(e, cx, last, Tfc, S->n_q, codes, quantized, nullptr, enc_out, nullptr);
 }
 
 int stream_decode_pass(const fc_stream* S, Ctx& cx, int n, const float* z_bdt, int Tfc, int use_scale, float* wav) {
-    fc_engine* e = S->e;
-    Act last = run_decoder(e, cx, Pass{S, n, false}, z_bdt, Tfc);
-    const int C = e->audio_ch();
-    cx.launch("combine", "", [&] {
-        return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, use_scale ? S->state : nullptr, cx.B, C, last.T, last.T, wav, (long long)C * last.T,
-                                  last.T, 1, cx.st);
-    });
-    return cx.err;
+    Act last = run_decoder(S->e, cx, stream_pass(S, n, false), z_bdt, Tfc);
+    return finish_decode(S->e, cx, last, use_scale ? S->state : nullptr, last.T, wav, nullptr);
 }
 
 // ---- length-aware (ragged) pass -------------------------------------------------------------------------------------------------
@@ -2051,63 +2108,33 @@ Act ragged_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Sr
     g.causal = L.causal ? 1 : 0; g.transposed = L.transposed ? 1 : 0; g.len = in; g.buf = buf;
     cx.launch("ragged stage", L.prefix.c_str(), [] { return "ragged_stage_kernel (length-aware: prologue and per-row padding of a conv)"; }, 0.0,
               4.0 * B * L.cin * ((double)T * (s1.used ? 2 : 1) + Tp), [&] { return fc::launch_ragged_stage(g, cx.st); });
-    ConvGeom geo;
-    geo.padL = 0; geo.padR = 0;
-    geo.Tout = L.transposed ? T * L.stride : (Tp - ((L.k - 1) * L.dil + 1)) / L.stride + 1;
-    geo.count_T = geo.Tout;
-    if (!cx.dry && geo.Tout != conv_geom(L, T).Tout) cx.fail("internal: staged width of a ragged conv (" + L.prefix + ")");
-    fc::ConvLaunch c = conv_launch_of(L, B, Tp, geo);
-    c.s0.ptr = buf; c.s0.used = 1;
-    c.alpha = e->arch.elu_alpha;
-    c.pad_zero = 1;                                   // nothing is padded; columns past the row end of the last tile read as zero
-    Act out;
-    out.C = L.cout; out.T = geo.Tout;
-    fc::RagLen valid = in;                            // the row's columns of what GroupNorm sees
-    int pitch = geo.Tout;
-    if (L.transposed) {                               // group j = taps (x[j-1], x[j]) = staged columns (j, j + 1): T + 1 groups
-        const int trimL = L.causal ? 0 : L.stride - L.stride / 2;
-        c.Tout = T + 1; c.up_r = L.stride;
-        valid.mul *= L.stride;
-        if (L.has_norm) {                             // GroupNorm sees the UNTRIMMED output (conv.py:287-303): store all of it, hand on the trimmed window
-            pitch = (T + 1) * L.stride;
-            c.trimL = 0; c.Tfinal = pitch;
-            valid.add = L.stride;
-            out.ld = pitch;
-        } else {
-            c.trimL = trimL; c.Tfinal = geo.Tout;
-        }
-        float* full = cx.alloc<float>((size_t)B * L.cout * pitch);
-        c.out = full;
-        out.raw = L.has_norm ? at(full, trimL) : full;
-    } else {
-        c.Tout = geo.Tout;
-        valid.div *= L.stride;                        // strided convs sit on the encoder side only (mul == 1 there)
-        out.raw = cx.alloc<float>((size_t)B * L.cout * geo.Tout);
-        c.out = out.raw;
-    }
-    c.out_sB = (long long)L.cout * pitch; c.out_sM = pitch; c.out_sT = 1;
-    const double fl = 2.0 * B * (double)L.M * L.cin * L.gk * c.Tout;
-    const double by = 4.0 * B * ((double)L.cin * Tp + (double)L.cout * pitch);
-    cx.conv_flops += fl; cx.conv_bytes += by;
-    cx.conv_launch("conv", L.prefix.c_str(), [&] { return conv_class(c); }, fl, by, [&] { return fc::launch_conv(c, cx.st); });
+    // a transposed layer computes T + 1 tap pairs; unpad1d trims left = r - r/2 of them when the net is not causal
+    const Staged r = staged_conv(e, cx, L, buf, Tp, T, T + 1, L.causal ? 0 : L.stride - L.stride / 2);
+    Act out = r.out;
+    if (!cx.dry && out.T != conv_geom(L, T).Tout) cx.fail("internal: staged width of a ragged conv (" + L.prefix + ")");
     if (L.has_norm) {
-        double* partials = cx.alloc<double>((size_t)B * L.cout * fc::ragged_gn_segments(pitch) * 2);
+        fc::RagLen valid = in;                        // the row's columns of what GroupNorm sees
+        if (L.transposed) { valid.mul *= L.stride; valid.add = L.stride; }
+        else valid.div *= L.stride;                   // strided convs sit on the encoder side only (mul == 1 there)
+        double* partials = cx.alloc<double>((size_t)B * L.cout * fc::ragged_gn_segments(r.pitch) * 2);
         out.aff = cx.alloc<float>((size_t)B * L.cout * 2);
         out.normed = true;
         cx.launch("ragged GroupNorm statistics", L.prefix.c_str(),
-                  [] { return "ragged_gn_partials_kernel (length-aware: GroupNorm sums over a row's valid columns)"; }, 0.0, 4.0 * B * L.cout * (double)pitch,
-                  [&] { return fc::launch_ragged_gn_partials(c.out, B, L.cout, pitch, valid, partials, cx.st); });
+                  [] { return "ragged_gn_partials_kernel (length-aware: GroupNorm sums over a row's valid columns)"; }, 0.0, 4.0 * B * L.cout * (double)r.pitch,
+                  [&] { return fc::launch_ragged_gn_partials(r.stored, B, L.cout, r.pitch, valid, partials, cx.st); });
         cx.launch("ragged gn_finalize", L.prefix.c_str(),
-                  [&] { return fc::launch_ragged_gn_finalize(partials, B, L.cout, pitch, valid, L.gamma, L.beta, e->arch.gn_eps, out.aff, cx.st); });
+                  [&] { return fc::launch_ragged_gn_finalize(partials, B, L.cout, r.pitch, valid, L.gamma, L.beta, e->arch.gn_eps, out.aff, cx.st); });
     }
     return out;
 }
 
-// the clamped device lengths of a ragged call, in the workspace
-int* ragged_lengths(fc_engine* e, Ctx& cx, const int32_t* lengths, int Tmax) {
+// a ragged call: the clamped device lengths in the workspace; frame_div of them make a frame
+Pass ragged_pass(fc_engine* e, Ctx& cx, const int32_t* lengths, int Tmax, int frame_div) {
     int* lens = cx.alloc<int>(cx.B);
     cx.launch("ragged lengths", "", [&] { return fc::launch_ragged_lengths(lengths, cx.B, Tmax, lens, e->status_dev, cx.st); });
-    return lens;
+    Pass p;
+    p.kind = Pass::Ragged; p.lengths = lens; p.frame_div = frame_div;
+    return p;
 }
 
 // zero behind every row's frames in the encoder-side outputs
@@ -2126,20 +2153,13 @@ int ragged_ready(fc_engine* e) {
     return 0;
 }
 
-// the four calls over one context (dry: workspace sizing)
+// the encoder side of the four calls over one context (dry: workspace sizing)
 int ragged_encode(fc_engine* e, Ctx& cx, const float* wav, const int32_t* lengths, int T, int n_q, int64_t* codes, float* quantized,
                   float* sub_quants, float* scale, float* enc_out, float** qbdt, Pass* pass) {
-    Pass p;
-    p.ragged = true; p.lengths = ragged_lengths(e, cx, lengths, T); p.frame_div = total_hop(e);
+    const Pass p = ragged_pass(e, cx, lengths, T, total_hop(e));
     if (do_encode(e, cx, wav, T, n_q, codes, quantized, sub_quants, scale, enc_out, qbdt, p)) return 1;
     ragged_mask_encoded(e, cx, p, frames_for(e, T), n_q, codes, quantized, sub_quants, enc_out);
     if (pass) *pass = p;
-    return cx.err;
-}
-
-int ragged_decode(fc_engine* e, Ctx& cx, const Pass& p, const float* z_bdt, int Tf, const float* scale, int out_len, const fc::RagLen& valid, float* wav) {
-    if (do_decode(e, cx, z_bdt, Tf, scale, out_len, wav, p)) return 1;
-    cx.launch("ragged mask", "wav", [&] { return fc::launch_ragged_mask_f32(wav, 1, cx.B, e->audio_ch(), out_len, 1, valid, cx.st); });
     return cx.err;
 }
 
@@ -2151,6 +2171,7 @@ int stream_ready(fc_stream* S) {
 }
 
 int stream_decode_check(fc_stream* S, int Tfc) {
+    if (S->dec_pushes < 0) return fail("streaming decode: fc_stream_reset first");
     if (Tfc <= 0 || Tfc > ceil_div_i(S->max_chunk, total_hop(S->e))) return fail("streaming decode: a push holds 1 .. max_chunk_samples / hop frames");
     if (S->dec_pushes == 0 && Tfc < S->dec_min_first)
         return fail("streaming decode: the first push of an utterance must hold at least " + std::to_string(S->dec_min_first) +
@@ -2158,26 +2179,36 @@ int stream_decode_check(fc_stream* S, int Tfc) {
     return 0;
 }
 
+// a decode push from its decoder input z on: enqueued whole, or the session is broken
+int stream_decode_push(fc_stream* S, Ctx& cx, const float* z, int Tfc, int use_scale, float* wav) {
+    if (cx.err) return 1;                               // nothing of the state has been written yet
+    S->broken = true;
+    if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
+    S->broken = false;
+    S->dec_pushes++;
+    return 0;
+}
+
 
 // ---- slot session ---------------------------------------------------------------------------------------------------------------
 // What a slot must reproduce is what a streaming session reproduces: the OFFLINE callable on the concatenation of the slot's pushes of
-// one utterance, whatever the other slots of the push do.  A push is a pass of the fourth kind (Pass::Q): the staging pass of every conv
+// one utterance, whatever the other slots of the push do.  A push is a pass of the fourth kind (Pass::Slots): the staging pass of every conv
 // with a context treats each row by its own count and flags (slots_conv), the LSTM masks the steps a row does not take, the quantiser runs
 // per frame over the common width, and what lies behind a row's valid part of every output is zeroed last (the ragged pass's masking).
 
 int slots_ready(fc_slots* Q) {
     if (!Q) return fail("null slot session");
-    return check_ready(Q->lay.e);
+    return check_ready(Q->e);
 }
 
 // The rules of a push (include/funcodec_amd.h), checked for every slot BEFORE anything is enqueued or changed.  `unit`: what a count
 // counts; whole: non-final counts are multiples of it (the hop on the encoder side, 1 frame on the decoder side).
 int slots_check(const fc_slots* Q, bool decode, const int32_t* counts, const int32_t* flags, int width, int max_width) {
-    const int S = Q->lay.B, hop = total_hop(Q->lay.e);
+    const int S = Q->B, hop = total_hop(Q->e);
     const char* side = decode ? "slot decode" : "slot encode";
     const char* unit = decode ? "frames" : "samples";
     const std::vector<char>& phase = decode ? Q->dec_phase : Q->enc_phase;
-    const int min_first = decode ? Q->lay.dec_min_first : Q->lay.enc_min_first, whole = decode ? 1 : hop;
+    const int min_first = decode ? Q->dec_min_first : Q->enc_min_first, whole = decode ? 1 : hop;
     auto bad = [&](int b, const std::string& what) { return fail(std::string(side) + ": slot " + std::to_string(b) + ": " + what); };
     if (width < 1 || width > max_width)
         return fail(std::string(side) + ": a push is 1 .. " + std::to_string(max_width) + " " + unit + " wide (max_chunk_samples), got " + std::to_string(width));
@@ -2215,7 +2246,7 @@ int slots_check(const fc_slots* Q, bool decode, const int32_t* counts, const int
 Pass slots_pass(fc_slots* Q, Ctx& cx, bool decode, const int32_t* counts, const int32_t* flags) {
     const int S = cx.B;
     Pass p;
-    p.Q = Q; p.n = decode ? Q->dec_pushes : Q->enc_pushes; p.frame_div = 1;
+    p.kind = Pass::Slots; p.sess = Q; p.n = decode ? Q->dec_pushes : Q->enc_pushes; p.frame_div = 1;
     int32_t* dev = cx.alloc<int32_t>((size_t)2 * S);
     p.lengths = dev; p.flags = at(dev, S);
     if (!cx.dry) {
@@ -2229,43 +2260,35 @@ Pass slots_pass(fc_slots* Q, Ctx& cx, bool decode, const int32_t* counts, const 
 
 // the rows that START: LSTM state of the side cleared, and on the encoder side the slot's scale set
 void slots_start(fc_slots* Q, Ctx& cx, const Pass& p, bool decode, const float* scale) {
-    fc_engine* e = Q->lay.e;
-    const LstmBlock& lb = decode ? e->dec_lstm : e->enc_lstm;
-    float* lstm = lb.H ? Q->lay.state + (decode ? Q->lay.dec_lstm_off : Q->lay.enc_lstm_off) : nullptr;
+    const LstmBlock& lb = decode ? Q->e->dec_lstm : Q->e->enc_lstm;
+    float* lstm = lb.H ? lstm_state(*Q, decode) : nullptr;
     if (!lstm && decode) return;
     cx.launch("slots start", "", [&] {
-        return fc::launch_slots_start(p.flags, cx.B, lstm, (int)lb.layers.size(), lb.H, scale, decode ? nullptr : Q->lay.state, cx.st);
+        return fc::launch_slots_start(p.flags, cx.B, lstm, (int)lb.layers.size(), lb.H, scale, decode ? nullptr : Q->state, cx.st);
     });
 }
 
 int slots_encode_pass(fc_slots* Q, Ctx& cx, const float* wav, int Tc, const int32_t* counts, const int32_t* flags, const float* scale, int64_t* codes,
                       float* quantized, float* enc_out) {
-    fc_engine* e = Q->lay.e;
+    fc_engine* e = Q->e;
     const Pass p = slots_pass(Q, cx, false, counts, flags);
     slots_start(Q, cx, p, false, scale);
-    fc::Src s; s.ptr = wav; s.div = Q->lay.state; s.used = 3;       // the slots' scale [S]
+    fc::Src s; s.ptr = wav; s.div = Q->state; s.used = 3;       // the slots' scale [S]
     Act last = run_encoder(e, cx, p, s, Tc);
     const int Tf = frames_for(e, Tc);
     if (!cx.dry && last.T != Tf) cx.fail("internal: frame count of a slot push");
-    if (do_quantize(e, cx, last, Tf, Q->lay.n_q, codes, quantized, nullptr, enc_out, nullptr)) return 1;
+    if (do_quantize(e, cx, last, Tf, Q->n_q, codes, quantized, nullptr, enc_out, nullptr)) return 1;
     Pass m = p; m.frame_div = total_hop(e);                          // ragged_mask_encoded counts samples
-    ragged_mask_encoded(e, cx, m, Tf, Q->lay.n_q, codes, quantized, nullptr, enc_out);
+    ragged_mask_encoded(e, cx, m, Tf, Q->n_q, codes, quantized, nullptr, enc_out);
     return cx.err;
 }
 
 // z: the decoder input [S][D][Tf] of either decode call; what lies behind a row's frames in it is never read (dec_first is staged)
 int slots_decode_pass(fc_slots* Q, Ctx& cx, const Pass& p, const float* z_bdt, int Tf, int use_scale, float* wav) {
-    fc_engine* e = Q->lay.e;
     slots_start(Q, cx, p, true, nullptr);
-    Act last = run_decoder(e, cx, p, z_bdt, Tf);
-    const int C = e->audio_ch();
-    cx.launch("combine", "", [&] {
-        return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, use_scale ? Q->lay.state : nullptr, cx.B, C, last.T, last.T, wav, (long long)C * last.T,
-                                  last.T, 1, cx.st);
-    });
-    fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(e);
-    cx.launch("ragged mask", "wav", [&] { return fc::launch_ragged_mask_f32(wav, 1, cx.B, C, last.T, 1, v, cx.st); });
-    return cx.err;
+    Act last = run_decoder(Q->e, cx, p, z_bdt, Tf);
+    fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(Q->e);
+    return finish_decode(Q->e, cx, last, use_scale ? Q->state : nullptr, last.T, wav, &v);
 }
 
 // a push has been enqueued (ok) or failed after its first launch: the slots' phases and the side's parity
@@ -2276,7 +2299,7 @@ void slots_commit(fc_slots* Q, bool decode, const int32_t* counts, const int32_t
         std::fill(Q->dec_phase.begin(), Q->dec_phase.end(), (char)fc_slots::Poisoned);
         return;
     }
-    for (int b = 0; b < Q->lay.B; ++b)
+    for (int b = 0; b < Q->B; ++b)
         if (counts[b] > 0) phase[b] = (flags[b] & FC_SLOT_FINAL) ? fc_slots::Ended : fc_slots::Running;
     ++(decode ? Q->dec_pushes : Q->enc_pushes);
 }
@@ -2533,7 +2556,7 @@ size_t fc_engine_workspace_bytes(const fc_engine* ce, int B, int T) {
     do_encode(e, cx, nullptr, T, e->arch.num_quantizers, nullptr, nullptr, nullptr, nullptr, nullptr, &q);
     cx.alloc<float>((size_t)B * Tf * D);           // quantized when the caller does not want it
     cx.alloc<float>((size_t)B * Tf * D);           // emb for decode_codes
-    cx.alloc<float>((size_t)B * Tf * D);           // transposed copy for decode_emb
+    decoder_input_emb(e, cx, nullptr, Tf);
     do_decode(e, cx, nullptr, Tf, nullptr, decoded_samples(e, Tf), nullptr);
     return cx.off + 4096;
 }
@@ -2576,11 +2599,7 @@ int fc_decode_emb(fc_engine* e, const float* emb, const float* scale, int B, int
     if (check_ready(e)) return 1;
     if (!emb || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    const int D = e->arch.dimension;
-    float* z = cx.alloc<float>((size_t)B * D * Tf);
-    if (cx.err) return 1;
-    HIP_TRY(fc::launch_transpose_btd(emb, B, Tf, D, z, cx.st));
-    return do_decode(e, cx, z, Tf, scale, out_len, wav);
+    return do_decode(e, cx, decoder_input_emb(e, cx, emb, Tf), Tf, scale, out_len, wav);
 }
 
 int fc_decode_codes(fc_engine* e, const int64_t* codes, int B, int Tf, int n_q, int out_len, float* wav, float* emb_out,
@@ -2589,9 +2608,7 @@ int fc_decode_codes(fc_engine* e, const int64_t* codes, int B, int Tf, int n_q, 
     if (!codes || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    float* z = cx.alloc<float>((size_t)B * e->cdim() * Tf);
-    if (codes_to_decoder_input(e, cx, codes, Tf, n_q, emb_out, &z)) return 1;
-    return do_decode(e, cx, z, Tf, nullptr, out_len, wav);
+    return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, nullptr), Tf, nullptr, out_len, wav);
 }
 
 int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int use_scale, int64_t* codes, float* quantized,
@@ -2614,16 +2631,16 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
 size_t fc_ragged_workspace_bytes(const fc_engine* ce, int B, int Tmax) {
     fc_engine* e = const_cast<fc_engine*>(ce);
     if (!e || B <= 0 || Tmax <= 0 || ragged_refusal(e)) return 0;
-    const int Tf = frames_for(e, Tmax), D = e->arch.dimension;
+    const int Tf = frames_for(e, Tmax);
     Ctx cx = dry_ctx(e, B);
     float* q = nullptr;
     Pass p;
     float mark;                                    // optional outputs: the pointer only marks presence in a dry pass
     ragged_encode(e, cx, nullptr, nullptr, Tmax, e->arch.num_quantizers, nullptr, &mark, &mark, nullptr, &mark, &q, &p);
-    cx.alloc<float>((size_t)B * Tf * D);           // transposed copy for decode_emb / code vectors for decode_codes
+    decoder_input_emb(e, cx, nullptr, Tf);         // as wide as the code vectors of decode_codes
     cx.alloc<int64_t>((size_t)B * Tf * e->arch.num_quantizers);     // masked copy of the tokens
     fc::RagLen v;
-    ragged_decode(e, cx, p, nullptr, Tf, nullptr, decoded_samples(e, Tf), v, nullptr);
+    do_decode(e, cx, nullptr, Tf, nullptr, decoded_samples(e, Tf), nullptr, p, &v);
     return cx.off + 4096;
 }
 
@@ -2641,14 +2658,9 @@ int fc_decode_emb_ragged(fc_engine* e, const float* emb, const float* scale, con
     if (ragged_ready(e)) return 1;
     if (!emb || !lengths || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    Pass p;
-    p.ragged = true; p.lengths = ragged_lengths(e, cx, lengths, Tf); p.frame_div = 1;
-    const int D = e->arch.dimension;
-    float* z = cx.alloc<float>((size_t)B * D * Tf);
-    // what lies behind a row's frames is never read (dec_first is staged)
-    cx.launch("transpose", "emb", [&] { return fc::launch_transpose_btd(emb, B, Tf, D, z, cx.st); });
+    const Pass p = ragged_pass(e, cx, lengths, Tf, 1);
     fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(e);
-    return ragged_decode(e, cx, p, z, Tf, scale, out_len, v, wav);
+    return do_decode(e, cx, decoder_input_emb(e, cx, emb, Tf), Tf, scale, out_len, wav, p, &v);
 }
 
 int fc_decode_codes_ragged(fc_engine* e, const int64_t* codes, const int32_t* lengths, int B, int Tf, int n_q, int out_len, float* wav,
@@ -2657,18 +2669,10 @@ int fc_decode_codes_ragged(fc_engine* e, const int64_t* codes, const int32_t* le
     if (!codes || !lengths || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    Pass p;
-    p.ragged = true; p.lengths = ragged_lengths(e, cx, lengths, Tf); p.frame_div = 1;
+    const Pass p = ragged_pass(e, cx, lengths, Tf, 1);
     fc::RagLen f; f.lens = p.lengths;
-    // the tokens behind a row's frames are the caller's garbage: a masked copy, so that none of them is looked up (or reported as out of range)
-    int64_t* masked = cx.alloc<int64_t>((size_t)B * Tf * n_q);
-    float* z = cx.alloc<float>((size_t)B * e->cdim() * Tf);
-    cx.launch("copy", "tokens", [&] { return hipMemcpyAsync(masked, codes, (size_t)B * Tf * n_q * sizeof(int64_t), hipMemcpyDeviceToDevice, cx.st); });
-    cx.launch("ragged mask", "tokens", [&] { return fc::launch_ragged_mask_i64(masked, 1, B, 1, Tf, n_q, f, cx.st); });
-    if (codes_to_decoder_input(e, cx, masked, Tf, n_q, emb_out, &z)) return 1;
-    if (emb_out) cx.launch("ragged mask", "emb_out", [&] { return fc::launch_ragged_mask_f32(emb_out, 1, B, 1, Tf, e->arch.dimension, f, cx.st); });
     fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(e);
-    return ragged_decode(e, cx, p, z, Tf, nullptr, out_len, v, wav);
+    return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, &f), Tf, nullptr, out_len, wav, p, &v);
 }
 
 int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengths, int B, int T, int n_q, int use_scale, int64_t* codes,
@@ -2683,7 +2687,7 @@ int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengt
     Pass p;
     if (ragged_encode(e, cx, wav, lengths, T, n_q, codes, quantized, sub_quants, sc, nullptr, &qbdt, &p)) return 1;
     fc::RagLen v; v.lens = p.lengths;              // a row's reconstruction is cut at its own samples (the reference's recon[:, :, :T])
-    return ragged_decode(e, cx, p, qbdt, frames_for(e, T), (use_scale && e->arch.audio_normalize) ? sc : nullptr, T, v, recon);
+    return do_decode(e, cx, qbdt, frames_for(e, T), (use_scale && e->arch.audio_normalize) ? sc : nullptr, T, recon, p, &v);
 }
 
 int fc_rvq_encode(fc_engine* e, const float* x, int N, int n_q, int64_t* codes, float* quantized, void* workspace,
@@ -3081,28 +3085,59 @@ int fc_debug_timeline(unsigned long long* dst) {
 size_t fc_stream_state_bytes(const fc_engine* ce, int B) {
     fc_engine* e = const_cast<fc_engine*>(ce);
     if (!e || B <= 0 || stream_refusal(e)) return 0;
-    fc_stream tmp;
+    Session tmp;
     stream_layout(e, B, &tmp);
     return tmp.state_floats * sizeof(float);
 }
 
-int fc_stream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_stream** out) {
+}  // extern "C"
+
+namespace {
+
+// What fc_stream_create and fc_slots_create share: the argument checks and the layout of the caller's state.  rows_error: why the row
+// count is refused, or null; `first`: what the kind calls the first push of an utterance; state_rule: its wording of the state rule.
+int session_create(Session* s, fc_engine* e, const void* out, int rows, const char* rows_error, int max_chunk_samples, int n_q, void* state,
+                   size_t state_bytes, const char* first, const char* state_rule) {
     if (!e || !out) return fail("null argument");
     if (!e->finalized) return fail("engine not finalized");
     if (const char* why = stream_refusal(e)) return fail(why);
-    if (B <= 0) return fail("bad batch size");
+    if (rows_error) return fail(rows_error);
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    s->e = e; s->B = rows; s->n_q = n_q; s->max_chunk = max_chunk_samples;
+    stream_layout(e, rows, s);
+    const int need = std::max(s->enc_min_first, s->dec_min_first * total_hop(e));
+    if (max_chunk_samples < need)
+        return fail(std::string("max_chunk_samples must hold the ") + first + " push of an utterance: at least " + std::to_string(need) + " samples for this net");
+    if (!state || ((uintptr_t)state & 15) || state_bytes < s->state_floats * sizeof(float)) return fail(state_rule);
+    s->state = (float*)state;
+    s->ones.assign(rows, 1.f);
+    return 0;
+}
+
+// The two fc_*_lstm_forward hooks: the SLSTM stage of a push alone (lstm.py:22-28 without the skip) on the session's LSTM state of one
+// side, exactly as a push runs it (run_lstm on the carried state; `steps`: a slot push).  x, y dev f32 [B][H][T].
+const LstmBlock* lstm_hook_block(const Session& s, int decoder, bool args_ok) {
+    const LstmBlock& lb = decoder ? s.e->dec_lstm : s.e->enc_lstm;
+    if (!args_ok) { fail("bad argument"); return nullptr; }
+    if (!lb.H) { fail("this net has no LSTM"); return nullptr; }
+    return &lb;
+}
+int lstm_hook_run(const Session& s, Ctx& cx, const LstmBlock& lb, int decoder, const float* x, int T, const fc::RagLen* steps, float* y) {
+    Act in; in.raw = const_cast<float*>(x); in.C = lb.H; in.T = T;
+    Act out = run_lstm(s.e, cx, lb, in, T, lstm_state(s, decoder != 0), steps);
+    cx.launch("copy", "y", [&] { return hipMemcpyAsync(y, out.raw, (size_t)s.B * lb.H * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st); });
+    return cx.err;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fc_stream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_stream** out) {
     std::unique_ptr<fc_stream> S(new fc_stream);
-    S->e = e; S->B = B; S->n_q = n_q; S->max_chunk = max_chunk_samples;
-    stream_layout(e, B, S.get());
-    const int hop = total_hop(e);
-    if (max_chunk_samples < S->enc_min_first || max_chunk_samples < S->dec_min_first * hop)
-        return fail("max_chunk_samples must hold the first push of an utterance: at least " +
-                    std::to_string(std::max(S->enc_min_first, S->dec_min_first * hop)) + " samples for this net");
-    if (!state || ((uintptr_t)state & 15) || state_bytes < S->state_floats * sizeof(float))
-        return fail("stream state: a 16-byte aligned device buffer of fc_stream_state_bytes() bytes");
-    S->state = (float*)state;
-    S->ones.assign(B, 1.f);
+    if (session_create(S.get(), e, out, B, B <= 0 ? "bad batch size" : nullptr, max_chunk_samples, n_q, state, state_bytes, "first",
+                       "stream state: a 16-byte aligned device buffer of fc_stream_state_bytes() bytes"))
+        return 1;
     S->enc_done = true; S->enc_pushes = -1; S->dec_pushes = -1;     // unusable until the first fc_stream_reset
     *out = S.release();
     return 0;
@@ -3114,15 +3149,13 @@ int fc_stream_min_first(const fc_stream* s, int decode) { return s ? (decode ? s
 
 size_t fc_stream_workspace_bytes(const fc_stream* S) {
     if (!S) return 0;
-    fc_engine* e = S->e;
-    const int hop = total_hop(e), D = e->arch.dimension, Tf = ceil_div_i(S->max_chunk, hop);
-    // a first push and a later one stage the same columns: sized as push 0, a final one (the extra padding)
-    Ctx ce = dry_ctx(e, S->B);
+    const int Tf = ceil_div_i(S->max_chunk, total_hop(S->e));
+    // the largest encode push.  A first push and a later one stage the same columns: sized as push 0, a final one (the extra padding)
+    Ctx ce = dry_ctx(S->e, S->B);
     stream_encode_pass(S, ce, 0, nullptr, S->max_chunk, true, nullptr, nullptr, nullptr);
-    Ctx cd = dry_ctx(e, S->B);
-    float* z = cd.alloc<float>((size_t)S->B * std::max(D, e->cdim()) * Tf);       // the first buffer of either decode call
-    codes_to_decoder_input(e, cd, nullptr, Tf, S->n_q, nullptr, &z);
-    stream_decode_pass(S, cd, 0, z, Tf, 1, nullptr);
+    // the largest decode push: decode_codes, with the first buffer as wide as decode_emb's
+    Ctx cd = dry_ctx(S->e, S->B);
+    stream_decode_pass(S, cd, 0, decoder_input_codes(S->e, cd, nullptr, Tf, S->n_q, nullptr, nullptr, true), Tf, 1, nullptr);
     return std::max(ce.off, cd.off) + 4096;
 }
 
@@ -3164,53 +3197,32 @@ int fc_stream_encode(fc_stream* S, const float* wav, int Tc, int final, int64_t*
 
 int fc_stream_decode_emb(fc_stream* S, const float* emb, int Tfc, int use_scale, float* wav, void* workspace, size_t workspace_bytes, void* stream) {
     if (stream_ready(S)) return 1;
-    fc_engine* e = S->e;
     if (!emb || !wav) return fail("bad argument");
-    if (S->dec_pushes < 0) return fail("streaming decode: fc_stream_reset first");
     if (stream_decode_check(S, Tfc)) return 1;
-    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
-    float* z = cx.alloc<float>((size_t)S->B * e->arch.dimension * Tfc);
-    if (cx.err) return 1;
-    HIP_TRY(fc::launch_transpose_btd(emb, S->B, Tfc, e->arch.dimension, z, cx.st));
-    S->broken = true;
-    if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
-    S->broken = false;
-    S->dec_pushes++;
-    return 0;
+    Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
+    return stream_decode_push(S, cx, decoder_input_emb(S->e, cx, emb, Tfc), Tfc, use_scale, wav);
 }
 
 int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_scale, float* wav, float* emb_out, void* workspace,
                            size_t workspace_bytes, void* stream) {
     if (stream_ready(S)) return 1;
-    fc_engine* e = S->e;
     if (!codes || !wav) return fail("bad argument");
-    if (S->dec_pushes < 0) return fail("streaming decode: fc_stream_reset first");
     if (stream_decode_check(S, Tfc)) return 1;
-    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
-    float* z = cx.alloc<float>((size_t)S->B * e->cdim() * Tfc);
-    if (codes_to_decoder_input(e, cx, codes, Tfc, S->n_q, emb_out, &z)) return 1;      // per frame: nothing to carry
-    S->broken = true;
-    if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
-    S->broken = false;
-    S->dec_pushes++;
-    return 0;
+    Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
+    // the lookup is per frame: nothing to carry
+    return stream_decode_push(S, cx, decoder_input_codes(S->e, cx, codes, Tfc, S->n_q, emb_out, nullptr), Tfc, use_scale, wav);
 }
 
-// Test hook: the SLSTM stage of a push alone (lstm.py:22-28 without the skip), continuing the recurrence the session's encoder
-// (decoder = 0) or decoder (decoder = 1) LSTM state holds, exactly as a push runs it (run_lstm on the carried state).  x, y dev f32 [B][H][T].
+// Test hook: the SLSTM stage of a push alone, continuing the recurrence the session's encoder (decoder = 0) or decoder (decoder = 1)
+// LSTM state holds.
 int fc_stream_lstm_forward(fc_stream* S, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream) {
     if (stream_ready(S)) return 1;
-    fc_engine* e = S->e;
-    const LstmBlock& lb = decoder ? e->dec_lstm : e->enc_lstm;
-    if (!x || !y || T <= 0) return fail("bad argument");
-    if (!lb.H) return fail("this net has no LSTM");
+    const LstmBlock* lb = lstm_hook_block(*S, decoder, x && y && T > 0);
+    if (!lb) return 1;
     if (S->enc_pushes < 0) return fail("streaming: fc_stream_reset first");
-    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
-    Act in; in.raw = const_cast<float*>(x); in.C = lb.H; in.T = T;
+    Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
     S->broken = true;
-    Act out = run_lstm(e, cx, lb, in, T, S->state + (decoder ? S->dec_lstm_off : S->enc_lstm_off));
-    if (cx.err) return 1;
-    HIP_TRY(hipMemcpyAsync(y, out.raw, (size_t)S->B * lb.H * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st));
+    if (lstm_hook_run(*S, cx, *lb, decoder, x, T, nullptr, y)) return 1;
     S->broken = false;
     return 0;
 }
@@ -3219,25 +3231,12 @@ int fc_stream_lstm_forward(fc_stream* S, int decoder, const float* x, int T, flo
 size_t fc_slots_state_bytes(const fc_engine* e, int S) { return fc_stream_state_bytes(e, S); }
 
 int fc_slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_slots** out) {
-    if (!e || !out) return fail("null argument");
-    if (!e->finalized) return fail("engine not finalized");
-    if (const char* why = stream_refusal(e)) return fail(why);
-    if (S <= 0 || S > 65535) return fail("bad slot count (1 .. 65535)");
-    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     std::unique_ptr<fc_slots> Q(new fc_slots);
-    fc_stream& lay = Q->lay;
-    lay.e = e; lay.B = S; lay.n_q = n_q; lay.max_chunk = max_chunk_samples;
-    stream_layout(e, S, &lay);
-    const int hop = total_hop(e);
-    if (max_chunk_samples < lay.enc_min_first || max_chunk_samples < lay.dec_min_first * hop)
-        return fail("max_chunk_samples must hold the START push of an utterance: at least " +
-                    std::to_string(std::max(lay.enc_min_first, lay.dec_min_first * hop)) + " samples for this net");
-    if (!state || ((uintptr_t)state & 15) || state_bytes < lay.state_floats * sizeof(float))
-        return fail("slot state: a 16-byte aligned device buffer of fc_slots_state_bytes() bytes");
-    lay.state = (float*)state;
+    if (session_create(Q.get(), e, out, S, (S <= 0 || S > 65535) ? "bad slot count (1 .. 65535)" : nullptr, max_chunk_samples, n_q, state, state_bytes,
+                       "START", "slot state: a 16-byte aligned device buffer of fc_slots_state_bytes() bytes"))
+        return 1;
     // the scale of a slot whose encoder has not started an utterance is 1: decode multiplies by it from the first push on
-    lay.ones.assign(S, 1.f);
-    HIP_TRY(hipMemcpy(state, lay.ones.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(state, Q->ones.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice));
     Q->enc_phase.assign(S, (char)fc_slots::Idle); Q->dec_phase.assign(S, (char)fc_slots::Idle);
     Q->push.assign((size_t)2 * S, 0);
     *out = Q.release();
@@ -3246,22 +3245,21 @@ int fc_slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, void* s
 
 void fc_slots_destroy(fc_slots* s) { delete s; }
 
-int fc_slots_min_first(const fc_slots* s, int decode) { return s ? (decode ? s->lay.dec_min_first : s->lay.enc_min_first) : 0; }
+int fc_slots_min_first(const fc_slots* s, int decode) { return s ? (decode ? s->dec_min_first : s->enc_min_first) : 0; }
 
 size_t fc_slots_workspace_bytes(const fc_slots* cq) {
     fc_slots* Q = const_cast<fc_slots*>(cq);
     if (!Q) return 0;
-    fc_engine* e = Q->lay.e;
-    const int S = Q->lay.B, hop = total_hop(e), D = e->arch.dimension, Tf = ceil_div_i(Q->lay.max_chunk, hop);
+    const int Tf = ceil_div_i(Q->max_chunk, total_hop(Q->e));
     float mark;                                    // optional outputs: the pointer only marks presence in a dry pass
-    Ctx ce = dry_ctx(e, S);
-    slots_encode_pass(Q, ce, nullptr, Q->lay.max_chunk, nullptr, nullptr, nullptr, nullptr, &mark, nullptr);   // no enc_out: its rows are then a buffer of the pass
-    Ctx cd = dry_ctx(e, S);
+    // the largest encode push (no enc_out: its rows are then a buffer of the pass)
+    Ctx ce = dry_ctx(Q->e, Q->B);
+    slots_encode_pass(Q, ce, nullptr, Q->max_chunk, nullptr, nullptr, nullptr, nullptr, &mark, nullptr);
+    // the largest decode push: decode_codes, with the first buffer as wide as decode_emb's
+    Ctx cd = dry_ctx(Q->e, Q->B);
     const Pass p = slots_pass(Q, cd, true, nullptr, nullptr);
-    cd.alloc<int64_t>((size_t)S * Tf * Q->lay.n_q);                               // masked copy of the tokens
-    float* z = cd.alloc<float>((size_t)S * std::max(D, e->cdim()) * Tf);          // the first buffer of either decode call
-    codes_to_decoder_input(e, cd, nullptr, Tf, Q->lay.n_q, nullptr, &z);
-    slots_decode_pass(Q, cd, p, z, Tf, 1, nullptr);
+    const fc::RagLen rows;
+    slots_decode_pass(Q, cd, p, decoder_input_codes(Q->e, cd, nullptr, Tf, Q->n_q, nullptr, &rows, true), Tf, 1, nullptr);
     return std::max(ce.off, cd.off) + 4096;
 }
 
@@ -3269,8 +3267,8 @@ int fc_slots_encode(fc_slots* Q, const float* wav, int Tc, const int32_t* sample
                     float* quantized, float* enc_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (slots_ready(Q)) return 1;
     if (!wav || !samples || !flags || !codes) return fail("bad argument");
-    if (slots_check(Q, false, samples, flags, Tc, Q->lay.max_chunk)) return 1;
-    Ctx cx = make_ctx(Q->lay.e, Q->lay.B, workspace, workspace_bytes, stream);
+    if (slots_check(Q, false, samples, flags, Tc, Q->max_chunk)) return 1;
+    Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
     const int err = slots_encode_pass(Q, cx, wav, Tc, samples, flags, scale, codes, quantized, enc_out);
     slots_commit(Q, false, samples, flags, !err);
     return err;
@@ -3279,14 +3277,11 @@ int fc_slots_encode(fc_slots* Q, const float* wav, int Tc, const int32_t* sample
 int fc_slots_decode_emb(fc_slots* Q, const float* emb, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (slots_ready(Q)) return 1;
-    fc_engine* e = Q->lay.e;
     if (!emb || !frames || !flags || !wav) return fail("bad argument");
-    if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->lay.max_chunk, total_hop(e)))) return 1;
-    Ctx cx = make_ctx(e, Q->lay.B, workspace, workspace_bytes, stream);
+    if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->max_chunk, total_hop(Q->e)))) return 1;
+    Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
     const Pass p = slots_pass(Q, cx, true, frames, flags);
-    float* z = cx.alloc<float>((size_t)cx.B * e->arch.dimension * Tfc);
-    cx.launch("transpose", "emb", [&] { return fc::launch_transpose_btd(emb, cx.B, Tfc, e->arch.dimension, z, cx.st); });
-    const int err = slots_decode_pass(Q, cx, p, z, Tfc, use_scale, wav);
+    const int err = slots_decode_pass(Q, cx, p, decoder_input_emb(Q->e, cx, emb, Tfc), Tfc, use_scale, wav);
     slots_commit(Q, true, frames, flags, !err);
     return err;
 }
@@ -3294,50 +3289,36 @@ int fc_slots_decode_emb(fc_slots* Q, const float* emb, int Tfc, const int32_t* f
 int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
                           float* emb_out, void* workspace, size_t workspace_bytes, void* stream) {
     if (slots_ready(Q)) return 1;
-    fc_engine* e = Q->lay.e;
     if (!codes || !frames || !flags || !wav) return fail("bad argument");
-    if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->lay.max_chunk, total_hop(e)))) return 1;
-    const int S = Q->lay.B, n_q = Q->lay.n_q;
-    Ctx cx = make_ctx(e, S, workspace, workspace_bytes, stream);
+    if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->max_chunk, total_hop(Q->e)))) return 1;
+    Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
     const Pass p = slots_pass(Q, cx, true, frames, flags);
-    fc::RagLen f; f.lens = p.lengths;
-    // the tokens behind a row's frames are the caller's garbage: a masked copy, so that none of them is looked up (or reported as out of range)
-    int64_t* masked = cx.alloc<int64_t>((size_t)S * Tfc * n_q);
-    float* z = cx.alloc<float>((size_t)S * e->cdim() * Tfc);
-    cx.launch("copy", "tokens", [&] { return hipMemcpyAsync(masked, codes, (size_t)S * Tfc * n_q * sizeof(int64_t), hipMemcpyDeviceToDevice, cx.st); });
-    cx.launch("ragged mask", "tokens", [&] { return fc::launch_ragged_mask_i64(masked, 1, S, 1, Tfc, n_q, f, cx.st); });
-    int err = codes_to_decoder_input(e, cx, masked, Tfc, n_q, emb_out, &z);
-    if (!err && emb_out) cx.launch("ragged mask", "emb_out", [&] { return fc::launch_ragged_mask_f32(emb_out, 1, S, 1, Tfc, e->arch.dimension, f, cx.st); });
-    if (!err) err = slots_decode_pass(Q, cx, p, z, Tfc, use_scale, wav);
+    fc::RagLen rows; rows.lens = p.lengths;
+    const int err = slots_decode_pass(Q, cx, p, decoder_input_codes(Q->e, cx, codes, Tfc, Q->n_q, emb_out, &rows), Tfc, use_scale, wav);
     slots_commit(Q, true, frames, flags, !err);
     return err;
 }
 
-// Test hook: the SLSTM stage of a slot push alone, on the session's encoder (decoder = 0) or decoder (decoder = 1) LSTM state, exactly as a
-// push runs it: the rows with start[b] != 0 begin from zeros, row b takes steps[b] <= T steps.  x, y dev f32 [S][H][T]; steps, start host [S].
-// It does not look at the slots' phases and does not change them.
+// Test hook: the SLSTM stage of a slot push alone: the rows with start[b] != 0 begin from zeros, row b takes steps[b] <= T steps.
+// steps, start host [S].  It does not look at the slots' phases and does not change them.
 int fc_slots_lstm_forward(fc_slots* Q, int decoder, const float* x, int T, const int32_t* steps, const int32_t* start, float* y, void* workspace,
                           size_t workspace_bytes, void* stream) {
     if (slots_ready(Q)) return 1;
-    fc_engine* e = Q->lay.e;
-    const int S = Q->lay.B;
-    const LstmBlock& lb = decoder ? e->dec_lstm : e->enc_lstm;
-    if (!x || !y || !steps || !start || T <= 0) return fail("bad argument");
-    if (!lb.H) return fail("this net has no LSTM");
+    const int S = Q->B;
+    const LstmBlock* lb = lstm_hook_block(*Q, decoder, x && y && steps && start && T > 0);
+    if (!lb) return 1;
     std::vector<int32_t> fl(S);
     for (int b = 0; b < S; ++b) {
         if (steps[b] < 0 || steps[b] > T) return fail("fc_slots_lstm_forward: slot " + std::to_string(b) + ": steps lie in [0, T]");
         fl[b] = start[b] ? FC_SLOT_START : 0;
     }
-    Ctx cx = make_ctx(e, S, workspace, workspace_bytes, stream);
+    Ctx cx = make_ctx(Q->e, S, workspace, workspace_bytes, stream);
     const Pass p = slots_pass(Q, cx, decoder != 0, steps, fl.data());
-    float* lstm = Q->lay.state + (decoder ? Q->lay.dec_lstm_off : Q->lay.enc_lstm_off);
-    cx.launch("slots start", "", [&] { return fc::launch_slots_start(p.flags, S, lstm, (int)lb.layers.size(), lb.H, nullptr, nullptr, cx.st); });
-    Act in; in.raw = const_cast<float*>(x); in.C = lb.H; in.T = T;
+    cx.launch("slots start", "", [&] {      // the LSTM state alone: the slots' scales stay
+        return fc::launch_slots_start(p.flags, S, lstm_state(*Q, decoder != 0), (int)lb->layers.size(), lb->H, nullptr, nullptr, cx.st);
+    });
     fc::RagLen st; st.lens = p.lengths;
-    Act out = run_lstm(e, cx, lb, in, T, lstm, &st);
-    cx.launch("copy", "y", [&] { return hipMemcpyAsync(y, out.raw, (size_t)S * lb.H * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st); });
-    if (cx.err) slots_commit(Q, decoder != 0, steps, fl.data(), false);
+    if (lstm_hook_run(*Q, cx, *lb, decoder, x, T, &st, y)) slots_commit(Q, decoder != 0, steps, fl.data(), false);
     return cx.err;
 }
 

@@ -196,9 +196,13 @@ class CodecEngine:
             need = self._ws_need[key] = int(size(self._h, B, T))
             if ragged and need == 0:
                 raise EngineError(ragged_refusal(self.arch) or "this engine has no length-aware calls")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._scratch(need)
+
+    def _scratch(self, nbytes: int) -> torch.Tensor:
+        """the engine's one scratch buffer, grown to nbytes: calls and sessions keep nothing in it between calls"""
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None                   # the old buffer goes before the new one comes
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
     def _stream(self):
@@ -455,12 +459,9 @@ class CodecEngine:
             if div.numel() != B:
                 raise EngineError(f"layer {prefix}: div must hold one scale per utterance ({B}), got {div.numel()}")
         y = torch.empty((B, cout, Tout), dtype=torch.float32, device=self.device)
-        ws = self._workspace(B, max(T, Tout) * 4 + 4096)
+        self._workspace(B, max(T, Tout) * 4 + 4096)
         # the layer's output + statistics, and a materialised (activated, summed) input for layers with >= 3 row tiles
-        need = (B * cout * (Tout + 64) * 4) * 2 + B * cin * (T + 2048) * 4 + (1 << 20)
-        if ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            ws = self._ws
+        ws = self._scratch((B * cout * (Tout + 64) * 4) * 2 + B * cin * (T + 2048) * 4 + (1 << 20))
         if aff0 is None and div is None and x1 is None:
             rc = self.lib.fc_layer_forward(self._h, prefix.encode(), _ptr(x), B, T, int(apply_elu), _ptr(y), _ptr(ws), ws.numel(), self._stream())
         else:
@@ -497,10 +498,7 @@ class CodecEngine:
             conv.append((x, a))
         y = torch.empty((B, int(dims[0]), int(dims[1]), int(dims[2])), dtype=torch.float32, device=self.device)
         need = int(dims[3])
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._scratch(need)
         (s0, a0), (s1, a1) = conv[0], (conv[1] if len(conv) > 1 else (None, None))
         self._check(self.lib.fc_layer2d_forward(self._h, prefix.encode(), _ptr(s0), _ptr(a0), _ptr(s1), _ptr(a1), B, Fq, T, int(apply_elu),
                                                 int(out_halo), _ptr(y), _ptr(ws), ws.numel(), self._stream()))
@@ -530,10 +528,7 @@ class CodecEngine:
                 raise EngineError(f"freq_synthesis: scale must hold one value per utterance ({B}), got {scale.numel()}")
         wav = torch.empty((B, int(out_len)), dtype=torch.float32, device=self.device)
         spec = torch.empty((B, 2 * Fq, Tp), dtype=torch.float32, device=self.device) if want_spec else None
-        if self._ws is None or self._ws.numel() < need.value:
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._scratch(need.value)
         self._check(self.lib.fc_freq_synthesis(self._h, _ptr(dec), _ptr(aff), _ptr(scale), B, Cc, Fq, Tp, int(out_len), _ptr(wav), _ptr(spec),
                                                _ptr(ws), ws.numel(), self._stream()))
         return (wav, spec) if want_spec else wav
@@ -557,9 +552,7 @@ class CodecEngine:
         x1, aff0, aff1 = self._sources(f"block {prefix}", x.shape, aff0, x1, aff1)
         y = torch.empty_like(x)
         need = B * Cc * (T + 64) * 4 * 6 + (4 << 20)      # both branches, the hidden one, and up to two materialised inputs
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._scratch(need)
         if aff0 is None and x1 is None:
             rc = self.lib.fc_resblock_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream())
         else:
@@ -577,9 +570,7 @@ class CodecEngine:
             raise EngineError(f"lstm {prefix!r}: expected input [B, {want[1] if want else '?'}, T], got {tuple(x.shape)}")
         y = torch.empty_like(x)
         need = (T * B * 4 * H + 3 * B * H + B * H * T + (2 * T + 1) * 16 * ((B + 15) // 16) * H) * 4 * self.arch.lstm_layers + (1 << 20)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._scratch(need)
         self._check(self.lib.fc_lstm_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y
 
@@ -595,8 +586,6 @@ class CodecEngine:
         y = torch.empty_like(x)
         # residual stream, LayerNorm out, branch out, attention out, result: 5 x [B,C,T]; q|k|v [B,3C,T]; feed-forward hidden [B,ff,T]
         need = 4 * B * T * (8 * Cc + SEQ_FF) + (1 << 20)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._scratch(need)
         self._check(self.lib.fc_seq_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y

@@ -12,7 +12,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .engine import EngineError, _on_device, _ptr
+from .engine import CodecEngine, EngineError, _on_device, _ptr
 
 
 def stream_refusal(arch) -> Optional[str]:
@@ -30,7 +30,100 @@ def stream_refusal(arch) -> Optional[str]:
     return None
 
 
-class CodecStream:
+FC_SLOT_START, FC_SLOT_FINAL = 1, 2
+
+
+class _Side:
+    """what a wrapper keeps per utterance and side (encode / decode)"""
+    __slots__ = ("head", "started", "ended")
+
+    def __init__(self):
+        self.head, self.started, self.ended = [], False, False
+
+
+class _Session:
+    """What CodecStream and StreamSlots share: the library's session over `rows` rows (the fc_stream_* or the fc_slots_* calls, `_family`),
+    its state and sizes, and the start-up and splitting rule of an utterance."""
+    _family = ""
+
+    def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int]):
+        why = stream_refusal(model.arch)
+        if why:
+            raise EngineError(why)
+        self.model, self.engine, self.arch = model, model.engine, model.arch
+        eng = self.engine
+        self.lib, self.device = eng.lib, eng.device
+        self.n_q = int(n_q) if n_q is not None else self.arch.num_quantizers
+        self.hop = eng.hop_length
+        self._h = None
+        self._open(rows, max_chunk)
+
+    def _fn(self, name: str):
+        return getattr(self.lib, f"{self._family}_{name}")
+
+    @_on_device
+    def _open(self, rows, max_chunk):
+        eng = self.engine
+        nbytes = int(self._fn("state_bytes")(eng._h, rows))
+        if nbytes == 0:
+            raise EngineError("this engine cannot stream")
+        #: everything the session carries between pushes (fc_stream_state_bytes): one allocation, nothing else is kept on the device
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        if self.state.is_cuda:
+            torch.cuda.current_stream(self.device).synchronize()      # fc_slots_create writes the scales (1) with a copy that is not ordered with this stream
+        self.max_chunk = int(max_chunk) if max_chunk is not None else 100 * self.hop
+        h = C.c_void_p()
+        eng._check(self._fn("create")(eng._h, rows, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
+        self._h = h
+        self.min_first_samples = int(self._fn("min_first")(h, 0))
+        self.min_first_frames = int(self._fn("min_first")(h, 1))
+        self._ws_bytes = int(self._fn("workspace_bytes")(h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._fn("destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _scratch(self, nbytes: int) -> torch.Tensor:
+        # the engine's own scratch buffer, by the engine's own rule; called on the class because all it needs of the engine is `_ws` and `device`
+        return CodecEngine._scratch(self.engine, nbytes)
+
+    def _ws(self) -> torch.Tensor:
+        return self._scratch(self._ws_bytes)
+
+    def _take(self, sd: _Side, x: torch.Tensor, final: bool, tdim: int, unit: int, min_first: int, short):
+        """The start-up and splitting rule of one side `sd` of one utterance.  What arrives along `tdim` (samples: unit = hop; frames:
+        unit = 1) is held back until min_first of it is there; an utterance that ends (final) before that raises short(have).  Then
+        everything held comes out at once, cut into pieces no longer than a call takes, all but the last whole hops:
+        [(part, flags)] with START on the utterance's first piece and FINAL on its last.  Returns (pieces, what stays held back) and
+        changes nothing."""
+        head, flags = sd.head + [x], 0
+        if not sd.started:
+            have = sum(t.shape[tdim] for t in head)
+            if have < min_first:
+                if final:
+                    raise short(have)
+                return [], head
+            flags = FC_SLOT_START
+        x = torch.cat(head, tdim) if len(head) > 1 else head[0]
+        n, cap = x.shape[tdim], self.max_chunk // (self.hop // unit)      # samples (unit = hop) or frames (unit = 1) per call
+        step = cap // unit * unit
+        out, pos = [], 0
+        while pos < n:
+            m = n - pos if n - pos <= cap else step
+            out.append((x.narrow(tdim, pos, m), flags | (FC_SLOT_FINAL if final and pos + m == n else 0)))
+            flags, pos = 0, pos + m
+        return out, []
+
+    def _lstm_scratch(self, x: torch.Tensor) -> torch.Tensor:
+        B, H, T = x.shape
+        return self._scratch(4 * (T * B * 4 * H + 2 * B * H * T) + (1 << 20))
+
+
+class CodecStream(_Session):
     """One utterance batch pushed through a causal codec chunk by chunk; obtained from ``EncodecMI355X.open_stream``.
 
     * ``encode(wav, final=False) -> (codes [n_q,B,Tf], quantized [B,Tf,D])``: every push but the final one is a positive
@@ -53,52 +146,13 @@ class CodecStream:
     reproduces the offline result; a running volume estimate is not implemented.
     """
 
+    _family = "fc_stream"
+
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
                  max_chunk: Optional[int] = None):
-        why = stream_refusal(model.arch)
-        if why:
-            raise EngineError(why)
-        self.model, self.engine, self.arch = model, model.engine, model.arch
-        eng = self.engine
-        self.lib, self.device = eng.lib, eng.device
         self.batch = int(batch)
-        self.n_q = int(n_q) if n_q is not None else self.arch.num_quantizers
-        self.hop = eng.hop_length
-        self._h = None
-        self._open(max_chunk)
+        super().__init__(model, self.batch, n_q, max_chunk)
         self.reset(scale)
-
-    @_on_device
-    def _open(self, max_chunk):
-        eng = self.engine
-        nbytes = int(self.lib.fc_stream_state_bytes(eng._h, self.batch))
-        if nbytes == 0:
-            raise EngineError("this engine cannot stream")
-        #: everything the session carries between pushes (fc_stream_state_bytes): one allocation, nothing else is kept on the device
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self.max_chunk = int(max_chunk) if max_chunk is not None else 100 * self.hop
-        h = C.c_void_p()
-        eng._check(self.lib.fc_stream_create(eng._h, self.batch, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
-        self._h = h
-        self.min_first_samples = int(self.lib.fc_stream_min_first(h, 0))
-        self.min_first_frames = int(self.lib.fc_stream_min_first(h, 1))
-        self._ws_bytes = int(self.lib.fc_stream_workspace_bytes(h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.fc_stream_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def _ws(self) -> torch.Tensor:
-        # the engine's own scratch buffer: sessions and offline calls keep nothing in it between calls
-        eng = self.engine
-        if eng._ws is None or eng._ws.numel() < self._ws_bytes:
-            eng._ws = None
-            eng._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
-        return eng._ws
 
     @_on_device
     def reset(self, scale: Optional[torch.Tensor] = None) -> None:
@@ -108,8 +162,7 @@ class CodecStream:
             if sc.numel() != self.batch:
                 raise EngineError(f"scale must hold one value per utterance ({self.batch}), got {sc.numel()}")
         self.engine._check(self.lib.fc_stream_reset(self._h, _ptr(sc), self.engine._stream()))
-        self._enc_head, self._dec_head = [], []       # pushes held back until the start-up length has arrived
-        self._enc_started = self._dec_started = False
+        self._enc, self._dec = _Side(), _Side()       # pushes held back until the start-up length has arrived
 
     # -- encode --------------------------------------------------------------------------------
     def _encode_call(self, wav: torch.Tensor, final: bool, want_enc_out: bool = False):
@@ -139,24 +192,16 @@ class CodecStream:
         if T < 1 or (not final and T % self.hop != 0):
             raise EngineError(f"streaming encode: every push but the final one must be a positive multiple of the hop ({self.hop} samples), "
                               f"got {T}; it is not padded silently")
-        if not self._enc_started:
-            self._enc_head.append(wav)
-            have = sum(w.shape[-1] for w in self._enc_head)
-            if have < self.min_first_samples and not final:
-                D = self.arch.dimension
-                empty = (self.n_q, self.batch, 0) if not self.arch.bypass_quantizer else (self.batch, 0)
-                none = torch.empty((self.batch, 0, D), device=self.device)
-                return (torch.empty(empty, dtype=torch.int64, device=self.device), none) + ((none,) if want_enc_out else ())
-            wav = torch.cat(self._enc_head, -1).contiguous() if len(self._enc_head) > 1 else wav
-            self._enc_head, self._enc_started = [], True
-            T = wav.shape[-1]
-        # longer than a call takes: whole-hop pieces, the rest (with the final flag) last
-        step = self.max_chunk // self.hop * self.hop
-        outs, pos = [], 0
-        while pos < T:
-            n = T - pos if T - pos <= self.max_chunk else step
-            outs.append(self._encode_call(wav[..., pos:pos + n].contiguous(), final and pos + n == T, want_enc_out))
-            pos += n
+        pieces, self._enc.head = self._take(self._enc, wav, final, -1, self.hop, self.min_first_samples, lambda have: EngineError(
+            f"streaming encode: the first push of an utterance must hold at least {self.min_first_samples} samples (the offline call's "
+            "reflected left padding spans them); shorter utterances go through the offline call"))
+        if not pieces:
+            D = self.arch.dimension
+            empty = (self.n_q, self.batch, 0) if not self.arch.bypass_quantizer else (self.batch, 0)
+            none = torch.empty((self.batch, 0, D), device=self.device)
+            return (torch.empty(empty, dtype=torch.int64, device=self.device), none) + ((none,) if want_enc_out else ())
+        self._enc.started = True
+        outs = [self._encode_call(part.contiguous(), bool(f & FC_SLOT_FINAL), want_enc_out) for part, f in pieces]
         res = (torch.cat([o[0] for o in outs], -1), torch.cat([o[1] for o in outs], 1))
         return res + ((torch.cat([o[2] for o in outs], 1),) if want_enc_out else ())
 
@@ -164,20 +209,15 @@ class CodecStream:
     def _decode_pushes(self, x: torch.Tensor, final: bool, call) -> torch.Tensor:
         if x.shape[0] != self.batch:
             raise EngineError(f"this session streams {self.batch} utterances, got {x.shape[0]}")
-        if not self._dec_started:
-            self._dec_head.append(x)
-            have = sum(t.shape[1] for t in self._dec_head)
-            if have < self.min_first_frames:
-                if final:
-                    raise EngineError(f"streaming decode: the utterance ends after {have} frames, fewer than the {self.min_first_frames} the "
-                                      "first push must hold (the offline call's reflected left padding spans them); decode it with the offline call")
-                return torch.empty((self.batch, self.engine.channels, 0), dtype=torch.float32, device=self.device)
-            x = torch.cat(self._dec_head, 1).contiguous() if len(self._dec_head) > 1 else x
-            self._dec_head, self._dec_started = [], True
-        step = self.max_chunk // self.hop
+        pieces, self._dec.head = self._take(self._dec, x, final, 1, 1, self.min_first_frames, lambda have: EngineError(
+            f"streaming decode: the utterance ends after {have} frames, fewer than the {self.min_first_frames} the "
+            "first push must hold (the offline call's reflected left padding spans them); decode it with the offline call"))
+        if not pieces:
+            return torch.empty((self.batch, self.engine.channels, 0), dtype=torch.float32, device=self.device)
+        self._dec.started = True
         outs = []
-        for pos in range(0, x.shape[1], step):
-            part = x[:, pos:pos + step].contiguous()
+        for part, _ in pieces:
+            part = part.contiguous()
             wav = torch.empty((self.batch, self.engine.channels, part.shape[1] * self.hop), dtype=torch.float32, device=self.device)
             ws = self._ws()
             self.engine._check(call(part, wav, ws))
@@ -211,29 +251,12 @@ class CodecStream:
         B, H, T = x.shape
         if B != self.batch or H != self.arch.bottleneck_channels:
             raise EngineError(f"lstm_forward: x must be [{self.batch},{self.arch.bottleneck_channels},T], got {tuple(x.shape)}")
-        y = torch.empty_like(x)
-        need = 4 * (T * B * 4 * H + 2 * B * H * T) + (1 << 20)
-        eng = self.engine
-        if eng._ws is None or eng._ws.numel() < need:
-            eng._ws = None
-            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = eng._ws
+        y, ws, eng = torch.empty_like(x), self._lstm_scratch(x), self.engine
         eng._check(self.lib.fc_stream_lstm_forward(self._h, int(decoder), _ptr(x), T, _ptr(y), _ptr(ws), ws.numel(), eng._stream()))
         return y
 
 
-FC_SLOT_START, FC_SLOT_FINAL = 1, 2
-
-
-class _Side:
-    """what the wrapper keeps per slot and side (encode / decode)"""
-    __slots__ = ("head", "started", "ended")
-
-    def __init__(self):
-        self.head, self.started, self.ended = [], False, False
-
-
-class StreamSlots:
+class StreamSlots(_Session):
     """``slots`` independent utterances streamed through ONE batch; obtained from ``EncodecMI355X.open_slots``.
 
     A push is bound by its launches, so 32 callers in one push cost about what one costs.  Each slot holds one utterance at a
@@ -259,56 +282,16 @@ class StreamSlots:
     that only decodes as well.
     """
 
+    _family = "fc_slots"
+
     def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
-        why = stream_refusal(model.arch)
-        if why:
-            raise EngineError(why)
-        self.model, self.engine, self.arch = model, model.engine, model.arch
-        eng = self.engine
-        self.lib, self.device = eng.lib, eng.device
         self.slots = int(slots)
-        self.n_q = int(n_q) if n_q is not None else self.arch.num_quantizers
-        self.hop = eng.hop_length
         self.pad_value = 0.0          # what the assembled batch holds behind a row's count and in idle rows (never read; a test aid)
-        self._h = None
-        self._open(max_chunk)
+        super().__init__(model, self.slots, n_q, max_chunk)
         self._enc = [_Side() for _ in range(self.slots)]
         self._dec = [_Side() for _ in range(self.slots)]
         self._scale = [1.0] * self.slots
         self._poisoned = [False] * self.slots
-
-    @_on_device
-    def _open(self, max_chunk):
-        eng = self.engine
-        nbytes = int(self.lib.fc_slots_state_bytes(eng._h, self.slots))
-        if nbytes == 0:
-            raise EngineError("this engine cannot stream")
-        #: everything the session carries between pushes (fc_slots_state_bytes): one allocation; fc_slots_create writes the scales (1)
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        if self.state.is_cuda:
-            torch.cuda.current_stream(self.device).synchronize()      # the library's copy is synchronous and not ordered with this stream
-        self.max_chunk = int(max_chunk) if max_chunk is not None else 100 * self.hop
-        h = C.c_void_p()
-        eng._check(self.lib.fc_slots_create(eng._h, self.slots, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
-        self._h = h
-        self.min_first_samples = int(self.lib.fc_slots_min_first(h, 0))
-        self.min_first_frames = int(self.lib.fc_slots_min_first(h, 1))
-        self._ws_bytes = int(self.lib.fc_slots_workspace_bytes(h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.fc_slots_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def _ws(self) -> torch.Tensor:
-        eng = self.engine
-        if eng._ws is None or eng._ws.numel() < self._ws_bytes:
-            eng._ws = None
-            eng._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
-        return eng._ws
 
     def _slot(self, slot) -> int:
         if not isinstance(slot, int) or not 0 <= slot < self.slots:
@@ -330,8 +313,7 @@ class StreamSlots:
             slot = self._slot(slot)
             x, final = item if isinstance(item, tuple) else (item, False)
             sd = sides[slot]
-            length = lambda t: t.shape[tdim]
-            n = length(x)
+            n = x.shape[tdim]
             if self._poisoned[slot]:
                 raise EngineError(f"slot {slot}: a push of this session failed inside the library; start({slot}) begins the next utterance")
             if sd.ended:
@@ -339,31 +321,11 @@ class StreamSlots:
             if n < 1 or (unit > 1 and not final and n % unit != 0):
                 raise EngineError(f"slot {slot}: every push but the final one must be a positive multiple of the hop ({self.hop} samples), "
                                   f"got {n}; it is not padded silently")
-            head, flags = sd.head + [x], 0
-            if not sd.started:
-                have = sum(length(t) for t in head)
-                if have < min_first:
-                    if final:
-                        raise EngineError(f"slot {slot}: the utterance ends after {have} {what}, fewer than the {min_first} the first push must hold "
-                                          "(the offline call's reflected left padding spans them); it goes through the offline call")
-                    plan[slot] = ([], head, False, False)
-                    continue
-                flags = FC_SLOT_START
-            plan[slot] = (self._pieces(head, flags, bool(final), tdim, unit), [], True, bool(final))
+            pieces, head = self._take(sd, x, bool(final), tdim, unit, min_first, lambda have: EngineError(
+                f"slot {slot}: the utterance ends after {have} {what}, fewer than the {min_first} the first push must hold "
+                "(the offline call's reflected left padding spans them); it goes through the offline call"))
+            plan[slot] = (pieces, head, bool(pieces), bool(pieces) and bool(final))
         return plan
-
-    def _pieces(self, head, flags, final, tdim, unit):
-        """what is longer than a call takes: whole-hop pieces, the rest (with the final flag) last"""
-        x = torch.cat(head, tdim) if len(head) > 1 else head[0]
-        n, cap = x.shape[tdim], self.max_chunk // (self.hop // unit)      # samples (unit = hop) or frames (unit = 1) per call
-        step = cap // unit * unit
-        out, pos = [], 0
-        while pos < n:
-            m = n - pos if n - pos <= cap else step
-            part = x.narrow(tdim, pos, m)
-            out.append((part, flags | (FC_SLOT_FINAL if final and pos + m == n else 0)))
-            flags, pos = 0, pos + m
-        return out
 
     def _run(self, sides, plan, call) -> Dict[int, List]:
         """commit the plan and push its pieces round by round: round r holds piece r of every slot that has one"""
@@ -503,13 +465,7 @@ class StreamSlots:
         S, H, T = x.shape
         if S != self.slots or H != self.arch.bottleneck_channels or len(steps) != S or len(start) != S:
             raise EngineError(f"lstm_forward: x must be [{self.slots},{self.arch.bottleneck_channels},T] with one step count and start flag per slot")
-        y = torch.empty_like(x)
-        need = 4 * (T * S * 4 * H + 2 * S * H * T) + (1 << 20)
-        eng = self.engine
-        if eng._ws is None or eng._ws.numel() < need:
-            eng._ws = None
-            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = eng._ws
+        y, ws, eng = torch.empty_like(x), self._lstm_scratch(x), self.engine
         st, fl = (C.c_int32 * S)(*[int(v) for v in steps]), (C.c_int32 * S)(*[int(bool(v)) for v in start])
         eng._check(self.lib.fc_slots_lstm_forward(self._h, int(decoder), _ptr(x), T, st, fl, _ptr(y), _ptr(ws), ws.numel(), eng._stream()))
         return y

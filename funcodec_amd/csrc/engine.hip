@@ -156,6 +156,11 @@ struct fc_engine {
     // status words written by kernels (host-pinned, device-mapped; kernels.h FC_STATUS_*), read at the next call without a sync
     volatile unsigned* status_host = nullptr;
     unsigned* status_dev = nullptr;
+    // per-row stage counts of the calls that follow (fc_engine_set_row_nq): the host copy (empty = none set) and the device table the
+    // quantiser kernels index by batch row; the table only grows, so a launch still in flight never loses it
+    std::vector<int32_t> row_nq;
+    int* row_nq_dev = nullptr;
+    size_t row_nq_cap = 0;
     bool lstm_persist_ok = true;             // cleared after a grid-barrier timeout: later calls take the per-step launch path
     int persist_checked_B = -1; bool persist_checked_val = false;
     // optional event timing
@@ -1758,6 +1763,24 @@ int frames_for(const fc_engine* e, int T) {
     return T;
 }
 
+// ---- per-row stage counts (fc_engine_set_row_nq) ----------------------------------------------------
+// the device table of the calls that quantise or look up codes, or null when none is set
+const int* row_nq_table(const fc_engine* e) { return e->row_nq.empty() ? nullptr : e->row_nq_dev; }
+
+// The rule of a call made while a table is set, checked BEFORE its first launch: as many rows as the table has, and n_q (the first
+// dimension of the codes) no smaller than any entry.
+int row_nq_check(const fc_engine* e, int rows, int n_q) {
+    if (e->row_nq.empty()) return 0;
+    if ((int)e->row_nq.size() != rows)
+        return fail("per-row stage counts are set for " + std::to_string(e->row_nq.size()) + " rows (fc_engine_set_row_nq); this call has " +
+                    std::to_string(rows) + " (clear them with a NULL table)");
+    for (size_t b = 0; b < e->row_nq.size(); ++b)
+        if (e->row_nq[b] > n_q)
+            return fail("n_q is the cap of the per-row stage counts (fc_engine_set_row_nq): row " + std::to_string(b) + " asks for " +
+                        std::to_string(e->row_nq[b]) + " stages, n_q is " + std::to_string(n_q));
+    return 0;
+}
+
 // ---- composite paths (each usable in dry mode for workspace sizing / work accounting) ---------------
 int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
                 float** quant_bdt_out);
@@ -1797,6 +1820,8 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
     const double rvq_fl = 2.0 * B * Tf * (double)n_q * e->arch.codebook_size * Dc;
     cx.rvq_flops += rvq_fl;
     if (!cx.dry && last.T != Tf) cx.fail("internal: frame count mismatch");
+    const int* nq_rows = row_nq_table(e);              // indexed by batch row (a slot push: by slot)
+    if (!cx.dry && nq_rows && (int)e->row_nq.size() != B) cx.fail("internal: per-row stage counts of another batch width");
     if (emb_rows)
         cx.launch("combine", "", [&] { return fc::launch_combine(src_of(last), fc::Src(), 0, 1.f, nullptr, B, D, Tf, Tf, emb, (long long)Tf * D, 1, D, cx.st); });
     if (e->q_proj)
@@ -1809,7 +1834,8 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
         cx.launch("q0 map", "", [&] { return fc::launch_q0_map(q0map, B, Tf, cx.st); });
     }
     cx.launch("rvq", "", [] { return kRvqClass; }, rvq_fl, 0.0, [&] {
-        return fc::launch_rvq_encode(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, e->cb_frag, e->enorm, codes, quant_c, qbdt_c, sub_quants, Tf, cx.st, q0map);
+        return fc::launch_rvq_encode(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, e->cb_frag, e->enorm, codes, quant_c, qbdt_c, sub_quants, Tf, cx.st, q0map,
+                                     nq_rows);
     });
     float* qbdt = qbdt_c;
     if (e->q_proj) {       // output_proj (costume_quantizer.py:92-94): decoder input [B][D][Tf] and the returned embeddings [B][Tf][D]
@@ -1868,8 +1894,11 @@ float* decoder_input_codes(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, 
         codes = masked;
     }
     float* z = cx.alloc<float>((size_t)B * (either ? std::max(D, Dc) : Dc) * Tf);
+    const int* nq_rows = row_nq_table(e);              // a row's codes behind its count are not read
+    if (!cx.dry && nq_rows && (int)e->row_nq.size() != B) cx.fail("internal: per-row stage counts of another batch width");
     cx.launch("rvq decode", "", [&] {
-        return fc::launch_rvq_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st);
+        return fc::launch_rvq_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st,
+                                     nq_rows);
     });
     if (e->q_proj) {
         fc::Src qs; qs.ptr = z; qs.used = 1;
@@ -2590,6 +2619,7 @@ int fc_encode(fc_engine* e, const float* wav, int B, int T, int n_q, int64_t* co
     if (check_ready(e)) return 1;
     if (!wav || !codes || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (row_nq_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return do_encode(e, cx, wav, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr);
 }
@@ -2607,6 +2637,7 @@ int fc_decode_codes(fc_engine* e, const int64_t* codes, int B, int Tf, int n_q, 
     if (check_ready(e)) return 1;
     if (!codes || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (row_nq_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, nullptr), Tf, nullptr, out_len, wav);
 }
@@ -2617,6 +2648,7 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
     if (check_ready(e)) return 1;
     if (!wav || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (row_nq_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     float* sc = scale;
     if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
@@ -2649,6 +2681,7 @@ int fc_encode_ragged(fc_engine* e, const float* wav, const int32_t* lengths, int
     if (ragged_ready(e)) return 1;
     if (!wav || !lengths || !codes || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (row_nq_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return ragged_encode(e, cx, wav, lengths, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr, nullptr);
 }
@@ -2668,6 +2701,7 @@ int fc_decode_codes_ragged(fc_engine* e, const int64_t* codes, const int32_t* le
     if (ragged_ready(e)) return 1;
     if (!codes || !lengths || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (row_nq_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     const Pass p = ragged_pass(e, cx, lengths, Tf, 1);
     fc::RagLen f; f.lens = p.lengths;
@@ -2680,6 +2714,7 @@ int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengt
     if (ragged_ready(e)) return 1;
     if (!wav || !lengths || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (row_nq_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     float* sc = scale;
     if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
@@ -2690,21 +2725,51 @@ int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengt
     return do_decode(e, cx, qbdt, frames_for(e, T), (use_scale && e->arch.audio_normalize) ? sc : nullptr, T, recon, p, &v);
 }
 
+int fc_engine_set_row_nq(fc_engine* e, const int32_t* n_q_rows, int B, void* stream) {
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!n_q_rows) { e->row_nq.clear(); return 0; }
+    if (B <= 0) return fail("fc_engine_set_row_nq: a table holds at least one row");
+    for (int b = 0; b < B; ++b)
+        if (n_q_rows[b] < 1 || n_q_rows[b] > e->arch.num_quantizers)
+            return fail("fc_engine_set_row_nq: row " + std::to_string(b) + ": a stage count lies in [1, num_quantizers = " +
+                        std::to_string(e->arch.num_quantizers) + "], got " + std::to_string(n_q_rows[b]));
+    if ((size_t)B > e->row_nq_cap) {    // a larger table; the old one stays allocated for the launches that may still read it
+        const size_t cap = std::max<size_t>(64, 2 * (size_t)B);
+        void* p = nullptr;
+        HIP_TRY(hipMalloc(&p, cap * sizeof(int32_t)));
+        e->dev_allocs.push_back(p);
+        e->row_nq_dev = (int*)p; e->row_nq_cap = cap;
+    }
+    // the source of the copy is the engine's own host copy, which lives as long as the engine: the caller's table may go at once
+    e->row_nq.assign(n_q_rows, n_q_rows + B);
+    if (hipError_t er = hipMemcpyAsync(e->row_nq_dev, e->row_nq.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream);
+        er != hipSuccess) {
+        e->row_nq.clear();
+        return fail(std::string("fc_engine_set_row_nq: copy of the table: ") + hipGetErrorString(er));
+    }
+    return 0;
+}
+
 int fc_rvq_encode(fc_engine* e, const float* x, int N, int n_q, int64_t* codes, float* quantized, void* workspace,
                   size_t workspace_bytes, void* stream) {
     if (check_ready(e)) return 1;
     (void)workspace; (void)workspace_bytes;
     if (!x || !codes || N <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    // with per-row stage counts for B rows (fc_engine_set_row_nq) the N rows are B utterances of N / B frames each
+    const int B = e->row_nq.empty() ? 1 : (int)e->row_nq.size(), Tf = N / B;
+    if (N % B != 0) return fail("fc_rvq_encode: with per-row stage counts for " + std::to_string(B) + " rows, N must be a multiple of that");
+    if (row_nq_check(e, B, n_q)) return 1;
     int* q0map = nullptr;
     if (e->arch.q0_ds_ratio > 1) {      // the rows are ONE utterance of N frames; the stage-0 source-row table lives in the caller's workspace
-        if (N < 2) return fail("quantizer_conf.q0_ds_ratio > 1 needs at least 2 frames");
+        if (Tf < 2) return fail("quantizer_conf.q0_ds_ratio > 1 needs at least 2 frames");
         if (!workspace || workspace_bytes < (size_t)N * sizeof(int)) return fail("fc_rvq_encode with q0_ds_ratio > 1 needs a workspace of N * 4 bytes");
         q0map = (int*)workspace;
-        HIP_TRY(fc::launch_q0_map(q0map, 1, N, (hipStream_t)stream));
+        HIP_TRY(fc::launch_q0_map(q0map, B, Tf, (hipStream_t)stream));
     }
     HIP_TRY(fc::launch_rvq_encode(x, N, e->cdim(), e->arch.codebook_size, n_q, e->cb, e->cb_frag, e->enorm, codes, quantized,
-                                  nullptr, nullptr, N, (hipStream_t)stream, q0map));
+                                  nullptr, nullptr, Tf, (hipStream_t)stream, q0map, row_nq_table(e)));
     return 0;
 }
 
@@ -3185,6 +3250,7 @@ int fc_stream_encode(fc_stream* S, const float* wav, int Tc, int final, int64_t*
     if (S->enc_pushes == 0 && Tc < S->enc_min_first)
         return fail("streaming encode: the first push of an utterance must hold at least " + std::to_string(S->enc_min_first) +
                     " samples (the offline call's reflected left padding spans them); shorter utterances go through the offline call");
+    if (row_nq_check(e, S->B, S->n_q)) return 1;
     Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
     S->broken = true;                                   // until the whole push is enqueued: a failure in between leaves mixed carries
     if (stream_encode_pass(S, cx, S->enc_pushes, wav, Tc, final != 0, codes, quantized, enc_out)) return 1;
@@ -3208,6 +3274,7 @@ int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_
     if (stream_ready(S)) return 1;
     if (!codes || !wav) return fail("bad argument");
     if (stream_decode_check(S, Tfc)) return 1;
+    if (row_nq_check(S->e, S->B, S->n_q)) return 1;
     Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
     // the lookup is per frame: nothing to carry
     return stream_decode_push(S, cx, decoder_input_codes(S->e, cx, codes, Tfc, S->n_q, emb_out, nullptr), Tfc, use_scale, wav);
@@ -3268,6 +3335,7 @@ int fc_slots_encode(fc_slots* Q, const float* wav, int Tc, const int32_t* sample
     if (slots_ready(Q)) return 1;
     if (!wav || !samples || !flags || !codes) return fail("bad argument");
     if (slots_check(Q, false, samples, flags, Tc, Q->max_chunk)) return 1;
+    if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
     Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
     const int err = slots_encode_pass(Q, cx, wav, Tc, samples, flags, scale, codes, quantized, enc_out);
     slots_commit(Q, false, samples, flags, !err);
@@ -3291,6 +3359,7 @@ int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int3
     if (slots_ready(Q)) return 1;
     if (!codes || !frames || !flags || !wav) return fail("bad argument");
     if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->max_chunk, total_hop(Q->e)))) return 1;
+    if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
     Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
     const Pass p = slots_pass(Q, cx, true, frames, flags);
     fc::RagLen rows; rows.lens = p.lengths;

@@ -184,7 +184,10 @@ hipError_t launch_rvq_encode(const float* x, int N, int D, int K, int nq, const 
                              const float* enorm,
                              int64_t* codes /*[nq][N]*/, float* quant /*[N][D] or null*/,
                              float* quant_bdt /*[B][D][Tf] or null*/, float* subq /*[nq][B][D][Tf] or null*/,
-                             int Tf, hipStream_t st, const int* src0 /* [N] stage-0 source rows (q0_ds_ratio > 1) or null */ = nullptr);
+                             int Tf, hipStream_t st, const int* src0 /* [N] stage-0 source rows (q0_ds_ratio > 1) or null */ = nullptr,
+                             // per-batch-row stage counts [N / Tf] (device, each in [1, nq]) or null: row n runs the first nq_rows[n / Tf]
+                             // stages exactly as a call with that nq would; codes and subq of its later stages are 0 (N % Tf == 0)
+                             const int* nq_rows = nullptr);
 
 // quantizer_conf.q0_ds_ratio > 1 (DistributedResidualVectorQuantization.forward, ddp_core_vq.py:396-404): the first stage quantises
 // F.interpolate(residual, size=[Tf // 2]) and its output (and indices) go back through F.interpolate(size=[Tf]), both mode "nearest"
@@ -209,8 +212,9 @@ __host__ __device__ inline int q0_source_frame(int t, int Tf) {
 hipError_t launch_q0_map(int* map /* [B][Tf] */, int B, int Tf, hipStream_t st);
 // codes [B][Tf][nq] (i64) -> emb [B][Tf][D] and/or emb_bdt [B][D][Tf]
 // status: host-visible engine status words (FC_STATUS_*), or null; an index outside [0, K) sets FC_STATUS_BAD_CODE
+// nq_rows: per-batch-row stage counts [B] (device) or null; the codes behind a row's count are not read (and never reported)
 hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb,
-                             float* emb, float* emb_bdt, unsigned* status, hipStream_t st);
+                             float* emb, float* emb_bdt, unsigned* status, hipStream_t st, const int* nq_rows = nullptr);
 
 // engine status words (host-pinned, device-mapped): written by kernels with plain stores, read by the host without a sync
 #define FC_STATUS_LSTM_TIMEOUT 0   // persistent LSTM: the grid barrier timed out (workgroups not co-resident); outputs poisoned

@@ -1477,13 +1477,19 @@ hipError_t launch_transpose_btd(const float* in, int B, int T, int D, float* out
 // with RS = 2 the same registers feed two independent 16-row MFMA accumulators (same arithmetic per row).
 // Q0: the stage-0 source-row table `src0` is honoured (quantizer_conf.q0_ds_ratio > 1); a template parameter so that the benchmark's
 // instantiations keep their register allocation (183 registers, no spill).
-template <int D, int RS, bool Q0 = false>
+// RQ: the per-batch-row stage counts `nq_rows` [N / Tf] are honoured (frame row n belongs to batch row n / Tf), a template parameter for
+// the same reason.  A residual quantiser is a prefix code, so row r with count k_r runs its stages i < k_r exactly as without the table; for
+// i >= k_r nothing is added to its quantised sum, its code and its sub_quant of that stage are 0, and what the row still computes while
+// its neighbours go on stays in the row (every row has its own residual, MFMA output row and arg-max).  The workgroup ends after the
+// largest count of its rows -- the same for all its threads, so the barriers of a stage stay uniform -- and writes the zeros of the
+// stages it did not run.  nq is the cap: the first dimension of codes / subq, >= every count.
+template <int D, int RS, bool Q0 = false, bool RQ = false>
 __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict__ x, int N, int K, int nq,
                                                          const float* __restrict__ cb, const float* __restrict__ cbf,
                                                          const float* __restrict__ enorm,
                                                          int64_t* __restrict__ codes, float* __restrict__ quant,
                                                          float* __restrict__ quant_bdt, float* __restrict__ subq, int Tf,
-                                                         int ablate, const int* __restrict__ src0) {
+                                                         int ablate, const int* __restrict__ src0, const int* __restrict__ nq_rows) {
     constexpr int NQ4 = D / 16;
     constexpr int ROWS = 16 * RS;
     // residual rows, padded by 4 floats: the |x|^2 chains read R[r][32 j + i] from 64 lanes (r, j) at once -- with a row stride of
@@ -1495,10 +1501,25 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
     __shared__ float bestv[8][ROWS];
     __shared__ int besti[8][ROWS];
     __shared__ int sel[ROWS];
+    __shared__ int krow[RQ ? ROWS : 1];                 // RQ: stages of the workgroup's rows (0 behind row N)
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, r16 = lane & 15;
     const int row0 = blockIdx.x * ROWS;
+    int nqw = nq;                                       // stages this workgroup runs
+    if constexpr (RQ) {
+        // the rows of a workgroup are consecutive frames, so their batch rows are consecutive too: every thread takes the same maximum
+        const int last = (row0 + ROWS <= N ? row0 + ROWS : N) - 1;
+        nqw = 0;
+        for (int b = row0 / Tf; b <= last / Tf; ++b) {
+            const int k = nq_rows[b] < nq ? nq_rows[b] : nq;
+            nqw = k > nqw ? k : nqw;
+        }
+        if (tid < ROWS) {
+            const int n = row0 + tid;
+            krow[tid] = n < N ? (nq_rows[n / Tf] < nq ? nq_rows[n / Tf] : nq) : 0;      // read behind the first barrier of stage 0
+        }
+    }
 
     for (int e = tid; e < ROWS * D; e += 512) {
         const int r = e / D, d = e - r * D;
@@ -1515,7 +1536,7 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
     constexpr bool DEEP = RS == 1;                                // one row set: codebook tiles two ahead (the two-row-set form has twice the MFMAs per tile)
     f32x4 b0[NQ4];                                               // first codebook fragment of the stage (requested one stage ahead)
     f32x4 b1p[DEEP ? NQ4 : 1];                                   // DEEP: the second one
-    for (int i = 0; i < nq; ++i) {
+    for (int i = 0; i < nqw; ++i) {
         __syncthreads();
         if (tid < 4 * ROWS) {   // |x|^2
             const int r = tid >> 2, j = tid & 3;
@@ -1604,7 +1625,7 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
                 if (t + 1 < ntile) do_tile(t + 1, b1p);
                 // the next stage's first fragments do not depend on this stage's result: requested now, the arg-max / residual-update tail
                 // of this stage hides their latency
-                if (i + 1 < nq) { load_tile(i + 1, 0, b0); if (ntile > 1) load_tile(i + 1, 1, b1p); }
+                if (i + 1 < nqw) { load_tile(i + 1, 0, b0); if (ntile > 1) load_tile(i + 1, 1, b1p); }
             } else {
                 f32x4 b1[NQ4];
                 if (i == 0) load_tile(0, 0, b0);
@@ -1618,7 +1639,7 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
                 if (t < ntile) do_tile(t, b0);
                 // the next stage's first fragment does not depend on this stage's result: request it now, the arg-max /
                 // residual-update tail of this stage hides its latency
-                if (i + 1 < nq) load_tile(i + 1, 0, b0);
+                if (i + 1 < nqw) load_tile(i + 1, 0, b0);
             }
         }
 #pragma unroll
@@ -1645,6 +1666,7 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
             }
             if (bi < 0 || bi >= K) bi = 0;   // all-NaN row: torch would return an index too; stay in range
             sel[tid] = bi;
+            if constexpr (RQ) { if (i >= krow[tid]) bi = 0; }       // a stage the row does not take: code 0 (sel stays in range for the gather)
             if (row0 + tid < N) codes[(size_t)i * N + row0 + tid] = (int64_t)bi;
         }
         __syncthreads();
@@ -1664,13 +1686,30 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
             float res = R[r][d];
             if (Q0 && i == 0 && n < N) res = x[(size_t)n * D + d];
             R[r][d] = res - qv[it];
-            qreg[it] = qreg[it] + qv[it];
+            bool keep = true;
+            if constexpr (RQ) keep = i < krow[r];
+            if (keep) qreg[it] = qreg[it] + qv[it];
             if (subq && n < N && !FC_ABL(ablate, 4)) {
                 const int bb = n / Tf, t = n - bb * Tf;
                 const int Bn = N / Tf;
-                subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = qv[it];
+                subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = keep ? qv[it] : 0.f;
             }
         }
+    }
+    if constexpr (RQ) {       // the stages behind the workgroup's last one: codes and sub_quants 0
+        if (tid < ROWS && row0 + tid < N)
+            for (int i = nqw; i < nq; ++i) codes[(size_t)i * N + row0 + tid] = 0;
+        if (subq)
+            for (int i = nqw; i < nq; ++i)
+#pragma unroll
+                for (int it = 0; it < NEL; ++it) {
+                    const int e = tid + 512 * it, r = e / D, d = e - r * D;
+                    const int n = row0 + r;
+                    if (n >= N || (ROWS * D % 512 != 0 && e >= ROWS * D)) continue;
+                    const int bb = n / Tf, t = n - bb * Tf;
+                    const int Bn = N / Tf;
+                    subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = 0.f;
+                }
     }
 #pragma unroll
     for (int it = 0; it < NEL; ++it) {
@@ -1689,13 +1728,14 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
 // Wide codebooks (D = 512, the SoundStream recipe): same arithmetic and the same argmax / update flow as rvq_encode_kernel,
 // but a (row, code) chain is fed in chunks of 256 dims -- the 2x fragment of the row (re-read from LDS per chunk) and the two
 // in-flight codebook fragments then fit the register file -- and the running quantised sum lives in registers instead of LDS.
-template <int D, bool Q0 = false>
+// RQ: per-batch-row stage counts, as in rvq_encode_kernel.
+template <int D, bool Q0 = false, bool RQ = false>
 __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __restrict__ x, int N, int K, int nq,
                                                               const float* __restrict__ cb, const float* __restrict__ cbf,
                                                               const float* __restrict__ enorm,
                                                               int64_t* __restrict__ codes, float* __restrict__ quant,
                                                               float* __restrict__ quant_bdt, float* __restrict__ subq, int Tf,
-                                                              const int* __restrict__ src0) {
+                                                              const int* __restrict__ src0, const int* __restrict__ nq_rows) {
     static_assert(D % 256 == 0, "chunks of 256 dims");
     constexpr int NC = D / 256, CQ = 16, NEL = 16 * D / 512;
     __shared__ __attribute__((aligned(16))) float R[16][D];
@@ -1703,9 +1743,23 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
     __shared__ float bestv[8][16];
     __shared__ int besti[8][16];
     __shared__ int sel[16];
+    __shared__ int krow[RQ ? 16 : 1];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, r16 = lane & 15;
     const int row0 = blockIdx.x * 16;
+    int nqw = nq;
+    if constexpr (RQ) {
+        const int last = (row0 + 16 <= N ? row0 + 16 : N) - 1;
+        nqw = 0;
+        for (int b = row0 / Tf; b <= last / Tf; ++b) {
+            const int k = nq_rows[b] < nq ? nq_rows[b] : nq;
+            nqw = k > nqw ? k : nqw;
+        }
+        if (tid < 16) {
+            const int n = row0 + tid;
+            krow[tid] = n < N ? (nq_rows[n / Tf] < nq ? nq_rows[n / Tf] : nq) : 0;
+        }
+    }
     float qreg[NEL];                                     // running sum of the selected code rows, element e = tid + 512*i
 #pragma unroll
     for (int i2 = 0; i2 < NEL; ++i2) {
@@ -1717,7 +1771,7 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
     const bool wactive = wid * codes_per_wave < K;
     const int ntile = wactive ? codes_per_wave >> 4 : 0, nunit = ntile * NC;
     const int code0 = wid * codes_per_wave;
-    for (int i = 0; i < nq; ++i) {
+    for (int i = 0; i < nqw; ++i) {
         __syncthreads();
         if (tid < 64) {   // |x|^2, same chains as the narrow kernel
             const int r = tid >> 2, j = tid & 3;
@@ -1798,6 +1852,7 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
             }
             if (bi < 0 || bi >= K) bi = 0;
             sel[tid] = bi;
+            if constexpr (RQ) { if (i >= krow[tid]) bi = 0; }
             if (row0 + tid < N) codes[(size_t)i * N + row0 + tid] = (int64_t)bi;
         }
         __syncthreads();
@@ -1808,12 +1863,27 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
             float res = R[r][d];
             if (Q0 && i == 0 && n < N) res = x[(size_t)n * D + d];
             R[r][d] = res - qv;
-            qreg[i2] = qreg[i2] + qv;
+            bool keep = true;
+            if constexpr (RQ) keep = i < krow[r];
+            if (keep) qreg[i2] = qreg[i2] + qv;
             if (subq && n < N) {
                 const int bb = n / Tf, t = n - bb * Tf, Bn = N / Tf;
-                subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = qv;
+                subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = keep ? qv : 0.f;
             }
         }
+    }
+    if constexpr (RQ) {
+        if (tid < 16 && row0 + tid < N)
+            for (int i = nqw; i < nq; ++i) codes[(size_t)i * N + row0 + tid] = 0;
+        if (subq)
+            for (int i = nqw; i < nq; ++i)
+#pragma unroll
+                for (int i2 = 0; i2 < NEL; ++i2) {
+                    const int e = tid + 512 * i2, r = e / D, d = e - r * D, n = row0 + r;
+                    if (n >= N) continue;
+                    const int bb = n / Tf, t = n - bb * Tf, Bn = N / Tf;
+                    subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = 0.f;
+                }
     }
 #pragma unroll
     for (int i2 = 0; i2 < NEL; ++i2) {
@@ -1841,14 +1911,18 @@ hipError_t launch_q0_map(int* map, int B, int Tf, hipStream_t st) {
 
 hipError_t launch_rvq_encode(const float* x, int N, int D, int K, int nq, const float* cb, const float* cb_frag,
                              const float* enorm, int64_t* codes, float* quant, float* quant_bdt, float* subq, int Tf, hipStream_t st,
-                             const int* src0) {
+                             const int* src0, const int* nq_rows) {
     if (N <= 0) return hipSuccess;
     if (K % 16 != 0 || (K > 128 && K % 128 != 0)) return hipErrorInvalidValue;
+    if (nq_rows && (Tf <= 0 || N % Tf != 0)) return hipErrorInvalidValue;      // the table is indexed by n / Tf
     if (D == 512) {
-        if (src0) hipLaunchKernelGGL((rvq_encode_wide_kernel<512, true>), dim3(ceil_div(N, 16)), dim3(512), 0, st, x, N, K, nq, cb, cb_frag, enorm,
-                                     codes, quant, quant_bdt, subq, Tf, src0);
-        else hipLaunchKernelGGL((rvq_encode_wide_kernel<512>), dim3(ceil_div(N, 16)), dim3(512), 0, st, x, N, K, nq, cb, cb_frag, enorm, codes,
-                           quant, quant_bdt, subq, Tf, src0);
+#define FC_RVQ_WIDE(Q0_, RQ_)                                                                                                     \
+    hipLaunchKernelGGL((rvq_encode_wide_kernel<512, Q0_, RQ_>), dim3(ceil_div(N, 16)), dim3(512), 0, st, x, N, K, nq, cb, cb_frag, enorm, \
+                       codes, quant, quant_bdt, subq, Tf, src0, nq_rows)
+        if (nq_rows) { if (src0) FC_RVQ_WIDE(true, true); else FC_RVQ_WIDE(false, true); }
+        else if (src0) FC_RVQ_WIDE(true, false);
+        else FC_RVQ_WIDE(false, false);
+#undef FC_RVQ_WIDE
         return hipGetLastError();
     }
     // two row sets per workgroup once there are enough rows to keep ~half the CUs busy that way (L2 traffic halves)
@@ -1877,14 +1951,18 @@ hipError_t launch_rvq_encode(const float* x, int N, int D, int K, int nq, const 
     const int n_cus = cu_table.n[cur_dev & 63];
     const bool two = !src0 && D <= 128 && (two_env >= 0 ? (two_env != 0 && N >= 2048) : N > 16 * n_cus);
     dim3 grid(ceil_div(N, two ? 32 : 16)), block(512);
+#define FC_RVQ_FORM(DD, RS_, Q0_, RQ_)                                                                             \
+    hipLaunchKernelGGL((rvq_encode_kernel<DD, RS_, Q0_, RQ_>), grid, block, 0, st, x, N, K, nq, cb, cb_frag, enorm, codes, quant, quant_bdt, \
+                       subq, Tf, ablate, src0, nq_rows)
 #define FC_RVQ_CASE(DD)                                                                                            \
     case DD:                                                                                                       \
-        if (two) hipLaunchKernelGGL((rvq_encode_kernel<(DD <= 128 ? DD : 16), 2>), grid, block, 0, st, x, N, K, nq, cb, cb_frag, enorm, codes, quant, \
-                                    quant_bdt, subq, Tf, ablate, src0);                                            \
-        else if (src0) hipLaunchKernelGGL((rvq_encode_kernel<DD, 1, true>), grid, block, 0, st, x, N, K, nq, cb, cb_frag, enorm, codes, quant, quant_bdt, \
-                                subq, Tf, ablate, src0);                                                           \
-        else hipLaunchKernelGGL((rvq_encode_kernel<DD, 1>), grid, block, 0, st, x, N, K, nq, cb, cb_frag, enorm, codes, quant, quant_bdt, \
-                                subq, Tf, ablate, src0);                                                           \
+        if (nq_rows) {                                     /* the same choice of form, with the per-row stage counts */ \
+            if (two) FC_RVQ_FORM((DD <= 128 ? DD : 16), 2, false, true);                                           \
+            else if (src0) FC_RVQ_FORM(DD, 1, true, true);                                                         \
+            else FC_RVQ_FORM(DD, 1, false, true);                                                                  \
+        } else if (two) FC_RVQ_FORM((DD <= 128 ? DD : 16), 2, false, false);                                       \
+        else if (src0) FC_RVQ_FORM(DD, 1, true, false);                                                            \
+        else FC_RVQ_FORM(DD, 1, false, false);                                                                     \
         break;
     switch (D) {
         FC_RVQ_CASE(16)
@@ -1895,18 +1973,22 @@ hipError_t launch_rvq_encode(const float* x, int N, int D, int K, int nq, const 
         default: return hipErrorInvalidValue;
     }
 #undef FC_RVQ_CASE
+#undef FC_RVQ_FORM
     return hipGetLastError();
 }
 
 // DRVQ.decode (ddp_core_vq.py:442-453): out = ((0 + E_0[i0]) + E_1[i1]) + ...
+// nq_rows (per-batch-row stage counts [B], or null): row n sums its first nq_rows[n / Tf] stages; the codes behind them are not read
 __global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restrict__ codes, int Tf, int nq, int D, int K,
                                                          const float* __restrict__ cb, float* __restrict__ emb,
-                                                         float* __restrict__ emb_bdt, unsigned* __restrict__ status) {
+                                                         float* __restrict__ emb_bdt, unsigned* __restrict__ status,
+                                                         const int* __restrict__ nq_rows) {
     const int n = blockIdx.x;   // row = b*Tf + t
     const int b = n / Tf, t = n - b * Tf;
+    const int k = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         float s = 0.f;
-        for (int i = 0; i < nq; ++i) {
+        for (int i = 0; i < k; ++i) {
             long long idx = codes[(size_t)n * nq + i];
             // F.embedding raises on an index outside [0, K) (ddp_core_vq.py:191): never read out of bounds, but make the
             // corrupt token loud -- the engine status word reports it (fc_engine_status)
@@ -1922,10 +2004,10 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restri
 }
 
 hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb, float* emb,
-                             float* emb_bdt, unsigned* status, hipStream_t st) {
+                             float* emb_bdt, unsigned* status, hipStream_t st, const int* nq_rows) {
     if (B * Tf <= 0) return hipSuccess;
     const int threads = D >= 256 ? 256 : (D >= 128 ? 128 : 64);
-    hipLaunchKernelGGL(rvq_decode_kernel, dim3(B * Tf), dim3(threads), 0, st, codes, Tf, nq, D, K, cb, emb, emb_bdt, status);
+    hipLaunchKernelGGL(rvq_decode_kernel, dim3(B * Tf), dim3(threads), 0, st, codes, Tf, nq, D, K, cb, emb, emb_bdt, status, nq_rows);
     return hipGetLastError();
 }
 

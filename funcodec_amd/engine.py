@@ -4,6 +4,7 @@ operation of the hot path happens inside libfuncodec_amd.so (HIP, gfx950).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import logging
 from typing import Dict, Optional
@@ -49,6 +50,38 @@ def ragged_refusal(arch) -> Optional[str]:
     if arch.segment_length is not None:
         return "length-aware batches are not available with model_conf.segment_dur (segments are a host loop over whole utterances)"
     return None
+
+
+def row_nq_refusal(arch) -> Optional[str]:
+    """Why a model of this architecture takes no per-row stage counts (a ``bit_width`` / ``n_q`` per row), or None.  The configuration
+    key is named, as ``ragged_refusal`` does."""
+    if arch.segment_length is not None:
+        return "a bit rate per row is not available with model_conf.segment_dur (segments are extra batch rows of the engine call)"
+    if arch.bypass_quantizer:
+        return "a bit rate per row is not available with model_conf.bypass_quantizer (the quantiser's result is dropped)"
+    return None
+
+
+def row_nq_list(arch, rows, B: int, cap: Optional[int] = None) -> list:
+    """The per-row stage counts of a call as a list of B ints in [1, cap] (cap: ``num_quantizers`` unless given); raises before any
+    engine call -- a bad count or a list of the wrong length refuses the call as a whole."""
+    why = row_nq_refusal(arch)
+    if why:
+        raise EngineError(why)
+    cap = arch.num_quantizers if cap is None else int(cap)
+    if hasattr(rows, "ndim"):                          # a tensor or an array
+        if rows.ndim != 1:
+            raise EngineError(f"per-row stage counts must be a sequence or 1-D tensor, got shape {tuple(rows.shape)}")
+        rows = rows.tolist()
+    rows = list(rows)
+    if len(rows) != B:
+        raise EngineError(f"per-row stage counts must hold one entry per row ({B}), got {len(rows)}")
+    out = []
+    for b, v in enumerate(rows):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
+            raise EngineError(f"row {b}: a stage count lies in [1, {cap}], got {v!r}")
+        out.append(int(v))
+    return out
 
 
 class CodecEngine:
@@ -247,7 +280,23 @@ class CodecEngine:
             raise EngineError(f"lengths must hold one entry per row ({B}), got {lengths.numel()}")
         return self._dev(lengths, torch.int32)
 
+    @contextlib.contextmanager
+    def _row_nq(self, rows):
+        """The engine's per-row stage counts (fc_engine_set_row_nq) for the calls made inside; cleared on the way out, whatever
+        happened, so a later plain call on this engine is untouched.  rows: None (nothing is set) or a checked list (row_nq_list)."""
+        if rows is None:
+            yield
+            return
+        self._check(self.lib.fc_engine_set_row_nq(self._h, (C.c_int32 * len(rows))(*rows), len(rows), self._stream()))
+        try:
+            yield
+        finally:
+            self.lib.fc_engine_set_row_nq(self._h, None, 0, None)
+
     # -- hot path ------------------------------------------------------------------------------
+    # n_q_rows (encode, encode_decode, decode_codes; optional): a stage count per row, each <= n_q (decode_codes: the tokens' last
+    # dimension).  Row b is then what the call with n_q = n_q_rows[b] gives it; codes and sub_quants of its later stages are 0, and a
+    # decode does not read them.
     # Every call below takes an optional `lengths` [B]: without it the offline call over the whole batch width, as ever; with it the
     # length-aware (ragged) sibling, whose row b is what the call gives row b alone cut at lengths[b], zeros behind (fc_*_ragged).
     @staticmethod
@@ -260,15 +309,18 @@ class CodecEngine:
         return out
 
     @_on_device
-    def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False, lengths=None):
+    def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False, lengths=None, n_q_rows=None):
         """wav [B,T] (or [B,C,T]) -> dict(codes [n_q,B,Tf] i64, quantized [B,Tf,D], sub_quants [n_q,B,D,Tf], scale [B,1]|None)."""
+        if n_q_rows is not None:                       # refused as a whole before anything reaches the device
+            n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
         if lengths is not None:
             lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
             parts = [self.encode(wav[i:i + self.micro_batch], n_q, want_sub_quants, want_enc_out,
-                                 None if lengths is None else lengths[i:i + self.micro_batch])
+                                 None if lengths is None else lengths[i:i + self.micro_batch],
+                                 None if n_q_rows is None else n_q_rows[i:i + self.micro_batch])
                      for i in range(0, B, self.micro_batch)]
             return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, enc_out=0))
         Tf, D = self.frames(T), self.arch.dimension
@@ -279,24 +331,28 @@ class CodecEngine:
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         enc = torch.empty((B, Tf, D), dtype=torch.float32, device=dev) if want_enc_out else None
         ws = self._workspace(B, T, lengths is not None)
-        if lengths is not None:
-            self._check(self.lib.fc_encode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq),
-                                                  _ptr(scale), _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
-        else:
-            self._check(self.lib.fc_encode(self._h, _ptr(wav), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq), _ptr(scale),
-                                           _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
+        with self._row_nq(n_q_rows):
+            if lengths is not None:
+                self._check(self.lib.fc_encode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq),
+                                                      _ptr(scale), _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
+            else:
+                self._check(self.lib.fc_encode(self._h, _ptr(wav), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq), _ptr(scale),
+                                               _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
         return dict(codes=codes, quantized=quant, sub_quants=subq,
                     scale=None if scale is None else scale.view(B, 1), enc_out=enc)
 
     @_on_device
-    def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True, lengths=None):
+    def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True, lengths=None, n_q_rows=None):
+        if n_q_rows is not None:                       # refused as a whole before anything reaches the device
+            n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
         if lengths is not None:
             lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
             parts = [self.encode_decode(wav[i:i + self.micro_batch], n_q, use_scale, want_sub_quants,
-                                        None if lengths is None else lengths[i:i + self.micro_batch])
+                                        None if lengths is None else lengths[i:i + self.micro_batch],
+                                        None if n_q_rows is None else n_q_rows[i:i + self.micro_batch])
                      for i in range(0, B, self.micro_batch)]
             return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0))
         Tf, D = self.frames(T), self.arch.dimension
@@ -307,36 +363,41 @@ class CodecEngine:
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         recon = torch.empty((B, self.channels, min(T, self.decoded_samples(Tf))), dtype=torch.float32, device=dev)   # like recon[:, :, :T] of the reference
         ws = self._workspace(B, T, lengths is not None)
-        if lengths is not None:
-            self._check(self.lib.fc_encode_decode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
-                                                         _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
-        else:
-            self._check(self.lib.fc_encode_decode(self._h, _ptr(wav), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
-                                                  _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
+        with self._row_nq(n_q_rows):
+            if lengths is not None:
+                self._check(self.lib.fc_encode_decode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
+                                                             _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
+            else:
+                self._check(self.lib.fc_encode_decode(self._h, _ptr(wav), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
+                                                      _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
         return dict(codes=codes, quantized=quant, sub_quants=subq,
                     scale=None if scale is None else scale.view(B, 1), recon=recon)
 
     @_on_device
-    def decode_codes(self, tokens: torch.Tensor, lengths=None):
+    def decode_codes(self, tokens: torch.Tensor, lengths=None, n_q_rows=None):
         """tokens [B,Tf,n_q] i64 -> (wav [B,1,Tf*hop], emb [B,Tf,D]).  lengths: frames per row."""
+        if n_q_rows is not None:                       # refused as a whole before anything reaches the device
+            n_q_rows = row_nq_list(self.arch, n_q_rows, tokens.shape[0], tokens.shape[-1])
         tokens = self._dev(tokens, torch.int64)
         B, Tf, n_q = tokens.shape
         if lengths is not None:
             lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
-            parts = [self.decode_codes(tokens[i:i + self.micro_batch], None if lengths is None else lengths[i:i + self.micro_batch])
+            parts = [self.decode_codes(tokens[i:i + self.micro_batch], None if lengths is None else lengths[i:i + self.micro_batch],
+                                       None if n_q_rows is None else n_q_rows[i:i + self.micro_batch])
                      for i in range(0, B, self.micro_batch)]
             return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
         L = self.decoded_samples(Tf)
         wav = torch.empty((B, self.channels, L), dtype=torch.float32, device=self.device)
         emb = torch.empty((B, Tf, self.arch.dimension), dtype=torch.float32, device=self.device)
         ws = self._workspace(B, Tf * self.hop_length, lengths is not None)
-        if lengths is not None:
-            self._check(self.lib.fc_decode_codes_ragged(self._h, _ptr(tokens), _ptr(lengths), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws),
-                                                        ws.numel(), self._stream()))
-        else:
-            self._check(self.lib.fc_decode_codes(self._h, _ptr(tokens), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws), ws.numel(),
-                                                 self._stream()))
+        with self._row_nq(n_q_rows):
+            if lengths is not None:
+                self._check(self.lib.fc_decode_codes_ragged(self._h, _ptr(tokens), _ptr(lengths), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws),
+                                                            ws.numel(), self._stream()))
+            else:
+                self._check(self.lib.fc_decode_codes(self._h, _ptr(tokens), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws), ws.numel(),
+                                                     self._stream()))
         return wav, emb
 
     @_on_device
@@ -402,7 +463,13 @@ class CodecEngine:
 
     # -- per-op entry points (tests) -----------------------------------------------------------
     @_on_device
-    def rvq_encode(self, x: torch.Tensor, n_q: int):
+    def rvq_encode(self, x: torch.Tensor, n_q: int, n_q_rows=None):
+        """x [N,D] -> (codes [n_q,N], quantized [N,D]).  n_q_rows (B entries): the N rows are B utterances of N / B frames each, utterance b
+        with n_q_rows[b] stages."""
+        if n_q_rows is not None:
+            n_q_rows = row_nq_list(self.arch, n_q_rows, len(n_q_rows), n_q)
+            if x.shape[0] % len(n_q_rows) != 0:
+                raise EngineError(f"rvq_encode: {x.shape[0]} rows are not {len(n_q_rows)} utterances of equal length")
         x = self._dev(x, torch.float32)
         N, D = x.shape
         if D != self.arch.codebook_dim:
@@ -410,8 +477,9 @@ class CodecEngine:
         codes = torch.empty((n_q, N), dtype=torch.int64, device=self.device)
         quant = torch.empty((N, D), dtype=torch.float32, device=self.device)
         ws = torch.empty(N, dtype=torch.int32, device=self.device) if self.arch.q0_ds_ratio > 1 else None     # stage-0 source-row table
-        self._check(self.lib.fc_rvq_encode(self._h, _ptr(x), N, n_q, _ptr(codes), _ptr(quant), _ptr(ws) if ws is not None else None,
-                                           0 if ws is None else 4 * N, self._stream()))
+        with self._row_nq(n_q_rows):
+            self._check(self.lib.fc_rvq_encode(self._h, _ptr(x), N, n_q, _ptr(codes), _ptr(quant), _ptr(ws) if ws is not None else None,
+                                               0 if ws is None else 4 * N, self._stream()))
         return codes, quant
 
     def _sources(self, what: str, shape, aff0, x1, aff1):

@@ -7,13 +7,14 @@ can switch without touching call sites.
 """
 from __future__ import annotations
 
+import numbers
 import types
 from typing import Dict, Optional
 
 import torch
 
 from .config import ArchSpec
-from .engine import CodecEngine, EngineError, ragged_refusal
+from .engine import CodecEngine, EngineError, ragged_refusal, row_nq_list
 
 
 class EncodecMI355X:
@@ -44,13 +45,15 @@ class EncodecMI355X:
 
     def open_stream(self, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None, max_chunk: Optional[int] = None):
         """A streaming encode / decode session for `batch` utterances of a causal checkpoint (funcodec_amd/stream.py CodecStream):
-        n_q quantisers (default: all), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call."""
+        n_q quantisers (default: all; a list of `batch` counts gives every utterance its own, and ``set_n_q`` changes them between
+        pushes), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call."""
         from .stream import CodecStream
         return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk)
 
     def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
         """A slot session of a causal checkpoint (funcodec_amd/stream.py StreamSlots): `slots` independent utterances that start, push
-        and end at their own times and share every push of the batch; n_q quantisers (default: all), at most max_chunk samples per call."""
+        and end at their own times and share every push of the batch; n_q quantisers at the most (default: all; ``start(slot, n_q=)`` and
+        ``set_n_q(slot, n_q)`` give a slot fewer, at any time between pushes), at most max_chunk samples per call."""
         from .stream import StreamSlots
         return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk)
 
@@ -108,16 +111,35 @@ class EncodecMI355X:
         return dict(codes=torch.zeros(emb.shape[0], emb.shape[1], dtype=torch.long, device=emb.device), quantized=emb,
                     sub_quants=torch.zeros_like(emb), scale=r["scale"])
 
+    @staticmethod
+    def _one_bit_width(bit_width) -> bool:
+        """one value for the whole batch (None, a Python or numpy number, a 0-dim tensor or array), as the reference takes it"""
+        return bit_width is None or isinstance(bit_width, numbers.Real) or (hasattr(bit_width, "ndim") and bit_width.ndim == 0)
+
+    def _bit_widths(self, bit_width, B: int):
+        """(n_q of the call, per-row stage counts or None) of a ``bit_width`` that is one value for the batch, as in the reference, or a
+        sequence / 1-D tensor of B of them: every entry goes through num_quantizers_for_bandwidth, the call's n_q is the largest."""
+        if self._one_bit_width(bit_width):
+            return self.arch.num_quantizers_for_bandwidth(float(bit_width) if hasattr(bit_width, "ndim") else bit_width), None
+        if hasattr(bit_width, "ndim"):                 # a tensor or an array
+            if bit_width.ndim != 1:
+                raise EngineError(f"bit_width must be one value or a sequence / 1-D tensor of one per row, got shape {tuple(bit_width.shape)}")
+            bit_width = bit_width.tolist()
+        rows = row_nq_list(self.arch, [self.arch.num_quantizers_for_bandwidth(bw) for bw in bit_width], B)
+        return max(rows), rows
+
     # -- Encodec.inference (codec_basic.py:670-718) ------------------------------------------
     @torch.no_grad()
     def inference(self, speech: torch.Tensor, need_recon: bool = True, bit_width: int = None,
                   use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None) -> Dict[str, torch.Tensor]:
-        """speech_lengths [B] (optional): samples per row.  With it, row b of every output is what this call returns for
+        """bit_width: one value for the batch, as in the reference, or a sequence / 1-D tensor of B: row b is then what this call returns
+        for it with ``bit_width[b]``; ``code_indices`` is [max n_q, B, Tf] with zeros at the stages a row does not take (``sub_quants`` too).
+        speech_lengths [B] (optional): samples per row.  With it, row b of every output is what this call returns for
         ``speech[b, ..., :speech_lengths[b]]`` alone (its own volume scale, GroupNorm statistics, end padding), zeros behind its
         ``engine.frames(len)`` frames / ``len`` samples; without it, the call over the whole batch width, as the reference runs it."""
         speech = self._as_bct(speech)
         bypass = self.arch.bypass_quantizer and not _quantise_always
-        n_q = self.arch.num_quantizers_for_bandwidth(bit_width)
+        n_q, rows = self._bit_widths(bit_width, speech.shape[0])
         wav = speech[:, 0, :] if self.engine.channels == 1 else speech
         if speech_lengths is not None:
             why = ragged_refusal(self.arch)
@@ -126,8 +148,8 @@ class EncodecMI355X:
             if bypass:     # inference() alone: inference_encoding quantises whatever the flag says, the decode calls never see it
                 raise EngineError("Encodec.inference with speech_lengths is not built for model_conf.bypass_quantizer (it would decode the "
                                   "encoder output of every row by its own frames); inference_encoding and the decode calls take lengths")
-            r = (self.engine.encode_decode(wav, n_q, use_scale=use_scale, lengths=speech_lengths) if need_recon
-                 else self.engine.encode(wav, n_q, lengths=speech_lengths))
+            r = (self.engine.encode_decode(wav, n_q, use_scale=use_scale, lengths=speech_lengths, n_q_rows=rows) if need_recon
+                 else self.engine.encode(wav, n_q, lengths=speech_lengths, n_q_rows=rows))
             return dict(recon_speech=r.get("recon"), code_indices=[r["codes"]],
                         code_embeddings=[(r["quantized"], r["scale"] if use_scale else None)], sub_quants=[r["sub_quants"]])
         if self.arch.segment_length is not None:
@@ -141,10 +163,10 @@ class EncodecMI355X:
                 recon = self.engine.decode_emb(r["quantized"], r["scale"] if use_scale else None,
                                                out_len=min(T, self.engine.decoded_samples(r["quantized"].shape[1])))
         elif need_recon:
-            r = self.engine.encode_decode(wav, n_q, use_scale=use_scale)
+            r = self.engine.encode_decode(wav, n_q, use_scale=use_scale, n_q_rows=rows)
             recon = r["recon"]
         else:
-            r = self.engine.encode(wav, n_q)
+            r = self.engine.encode(wav, n_q, n_q_rows=rows)
             recon = None
         scale = r["scale"] if use_scale else None
         return dict(recon_speech=recon, code_indices=[r["codes"]], code_embeddings=[(r["quantized"], scale)],
@@ -162,8 +184,13 @@ class EncodecMI355X:
     @torch.no_grad()
     def inference_decoding(self, token_idx: torch.Tensor, need_recon: bool = True, bit_width: int = None,
                            use_scale: bool = True, token_lengths=None) -> Dict[str, torch.Tensor]:
-        """token_lengths [B] (optional): frames per row; row b is then decoded from its own frames alone, zeros behind frames * hop."""
-        recon, emb = self.engine.decode_codes(token_idx, lengths=token_lengths)
+        """token_lengths [B] (optional): frames per row; row b is then decoded from its own frames alone, zeros behind frames * hop.
+        bit_width: ignored when it is one value, as in the reference (the tokens' last dimension says how many stages there are); a
+        sequence / 1-D tensor of B gives row b its own count: its tokens behind that are not read."""
+        rows = None
+        if not self._one_bit_width(bit_width):
+            rows = self._bit_widths(bit_width, token_idx.shape[0])[1]
+        recon, emb = self.engine.decode_codes(token_idx, lengths=token_lengths, n_q_rows=rows)
         if self.arch.segment_length is not None and need_recon:      # _decode: one frame through the overlap-add (codec_basic.py:396)
             recon = self.engine.overlap_add([recon], self.arch.segment_stride or 1)
         return dict(recon_speech=recon if need_recon else None, code_indices=None,

@@ -7,12 +7,14 @@ iterator), so the specification is causality itself: pushing an utterance throug
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import numbers
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .engine import CodecEngine, EngineError, _on_device, _ptr
+from .engine import CodecEngine, EngineError, _on_device, _ptr, row_nq_list
 
 
 def stream_refusal(arch) -> Optional[str]:
@@ -53,7 +55,10 @@ class _Session:
         self.model, self.engine, self.arch = model, model.engine, model.arch
         eng = self.engine
         self.lib, self.device = eng.lib, eng.device
+        #: the session's n_q: the first dimension of its codes, and the most any row may use (the cap of the per-row stage counts)
         self.n_q = int(n_q) if n_q is not None else self.arch.num_quantizers
+        #: the rows' own stage counts; None while every row runs all n_q stages (nothing is set on the engine then)
+        self._row_nq: Optional[List[int]] = None
         self.hop = eng.hop_length
         self._h = None
         self._open(rows, max_chunk)
@@ -118,6 +123,21 @@ class _Session:
             flags, pos = 0, pos + m
         return out, []
 
+    def _checked_row_nq(self, rows, n: int) -> List[int]:
+        """n stage counts in [1, the session's n_q], or an EngineError before anything is changed"""
+        if not 1 <= self.n_q <= self.arch.num_quantizers:
+            raise EngineError(f"n_q lies in [1, {self.arch.num_quantizers}], got {self.n_q}")
+        return row_nq_list(self.arch, rows, n, self.n_q)
+
+    def _engine_row_nq(self, rows):
+        """the engine's table around one push; with no counts of its own a push does not touch the engine's table at all"""
+        return contextlib.nullcontext() if rows is None else self.engine._row_nq(rows)
+
+    def _push_row_nq(self):
+        """what a push sets on the engine: the rows' counts, or None when every row runs all n_q stages (the plain kernels)"""
+        rows = self._row_nq
+        return None if rows is None or all(v == self.n_q for v in rows) else rows
+
     def _lstm_scratch(self, x: torch.Tensor) -> torch.Tensor:
         B, H, T = x.shape
         return self._scratch(4 * (T * B * 4 * H + 2 * B * H * T) + (1 << 20))
@@ -130,6 +150,10 @@ class CodecStream(_Session):
       multiple of ``hop`` samples; the final one has any length >= 1.  A push that breaks the rule raises, it is never padded.
     * ``decode(codes [B,Tf,n_q])`` / ``decode_emb(emb [B,Tf,D]) -> wav [B,C,Tf*hop]``.
     * ``reset(scale=None)`` starts the next utterance.
+    * ``set_n_q(rows)``: a stage count per utterance, each in [1, n_q], for the pushes that follow -- in the middle of an utterance
+      too (a residual quantiser is a prefix code and carries nothing from frame to frame).  ``open_stream(batch, n_q=[...])`` sets them
+      from the start; the session's ``n_q``, the first dimension of its codes, is then the largest of the list.  Row b of a push is what
+      a session with ``n_q = rows[b]`` gives it; its codes at later stages are 0, and ``decode`` does not read them.
 
     Start-up.  The offline call pads every causal conv on the left by *reflection* (``pad_mode: reflect``, conv.py:82-99,
     251-253), i.e. with the columns that follow: only there does a frame depend on later input.  The session therefore
@@ -151,8 +175,17 @@ class CodecStream(_Session):
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
                  max_chunk: Optional[int] = None):
         self.batch = int(batch)
+        rows = None
+        if n_q is not None and not isinstance(n_q, numbers.Integral):       # a count per utterance: refused before anything is opened
+            rows = row_nq_list(model.arch, n_q, self.batch)
+            n_q = max(rows)
         super().__init__(model, self.batch, n_q, max_chunk)
+        self._row_nq = rows
         self.reset(scale)
+
+    def set_n_q(self, rows) -> None:
+        """stage counts [batch], each in [1, n_q], of the pushes that follow; a refused call changes nothing"""
+        self._row_nq = self._checked_row_nq(rows, self.batch)
 
     @_on_device
     def reset(self, scale: Optional[torch.Tensor] = None) -> None:
@@ -173,8 +206,9 @@ class CodecStream(_Session):
         enc = torch.empty((B, Tf, D), dtype=torch.float32, device=self.device) if (self.arch.bypass_quantizer or want_enc_out) else None
         n = C.c_int(0)
         ws = self._ws()
-        self.engine._check(self.lib.fc_stream_encode(self._h, _ptr(wav), T, int(final), _ptr(codes), _ptr(quant), _ptr(enc), C.byref(n),
-                                                     _ptr(ws), ws.numel(), self.engine._stream()))
+        with self._engine_row_nq(self._push_row_nq()):
+            self.engine._check(self.lib.fc_stream_encode(self._h, _ptr(wav), T, int(final), _ptr(codes), _ptr(quant), _ptr(enc), C.byref(n),
+                                                         _ptr(ws), ws.numel(), self.engine._stream()))
         assert n.value == Tf
         if self.arch.bypass_quantizer:         # codec_basic.py:700-701: the encoder output in place of the quantised embeddings
             return torch.zeros((B, Tf), dtype=torch.long, device=self.device), enc, enc
@@ -206,7 +240,7 @@ class CodecStream(_Session):
         return res + ((torch.cat([o[2] for o in outs], 1),) if want_enc_out else ())
 
     # -- decode --------------------------------------------------------------------------------
-    def _decode_pushes(self, x: torch.Tensor, final: bool, call) -> torch.Tensor:
+    def _decode_pushes(self, x: torch.Tensor, final: bool, call, rows_apply: bool = False) -> torch.Tensor:
         if x.shape[0] != self.batch:
             raise EngineError(f"this session streams {self.batch} utterances, got {x.shape[0]}")
         pieces, self._dec.head = self._take(self._dec, x, final, 1, 1, self.min_first_frames, lambda have: EngineError(
@@ -220,7 +254,8 @@ class CodecStream(_Session):
             part = part.contiguous()
             wav = torch.empty((self.batch, self.engine.channels, part.shape[1] * self.hop), dtype=torch.float32, device=self.device)
             ws = self._ws()
-            self.engine._check(call(part, wav, ws))
+            with self._engine_row_nq(self._push_row_nq() if rows_apply else None):
+                self.engine._check(call(part, wav, ws))
             outs.append(wav)
         return outs[0] if len(outs) == 1 else torch.cat(outs, -1)
 
@@ -232,7 +267,7 @@ class CodecStream(_Session):
         if codes.dim() != 3 or codes.shape[2] != self.n_q:
             raise EngineError(f"codes must be [B,Tf,{self.n_q}], got {tuple(codes.shape)}")
         return self._decode_pushes(codes, final, lambda part, wav, ws: self.lib.fc_stream_decode_codes(
-            self._h, _ptr(part), part.shape[1], int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(), self.engine._stream()))
+            self._h, _ptr(part), part.shape[1], int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(), self.engine._stream()), rows_apply=True)
 
     @_on_device
     def decode_emb(self, emb: torch.Tensor, use_scale: bool = True, final: bool = False) -> torch.Tensor:
@@ -267,8 +302,12 @@ class StreamSlots(_Session):
       ``want_enc_out``); ``wav`` is [C,T] or [T]; a bare tensor means ``final=False``.  Every push of a slot but its final one is a
       positive multiple of ``hop`` samples.  Slots that are not named sit idle; slots that emitted nothing are not in the result.
     * ``decode({slot: (codes [Tf,n_q], final)})`` / ``decode_emb({slot: (emb [Tf,D], final)}) -> {slot: wav [C,Tf*hop]}``.
-    * ``start(slot, scale=None)`` begins the next utterance of a slot (a fresh session has every slot started, scale 1); on a slot whose
-      utterance is still running it abandons that utterance.  There is no ``end``: the final push ends an utterance.
+    * ``start(slot, scale=None, n_q=None)`` begins the next utterance of a slot (a fresh session has every slot started, scale 1); on a
+      slot whose utterance is still running it abandons that utterance.  There is no ``end``: the final push ends an utterance.
+    * ``set_n_q(slot, n_q)``: the slot's stage count, in [1, the session's n_q], for the pushes that follow -- at any time between
+      pushes, in the middle of an utterance too; ``start`` sets it as well (``None``: all n_q of the session).  The session's ``n_q`` is
+      the most any slot may use and the first dimension of every slot's codes: a slot with fewer stages gets zeros at the later ones,
+      everything else is what a session with that ``n_q`` gives it, and ``decode`` does not read its codes behind its count.
 
     Per slot: pushes are held back until ``min_first_samples`` / ``min_first_frames`` have arrived, then everything held comes
     out at once; an utterance that ends shorter than that raises (the offline call's job); what is longer than ``max_chunk`` is split.
@@ -292,14 +331,22 @@ class StreamSlots(_Session):
         self._dec = [_Side() for _ in range(self.slots)]
         self._scale = [1.0] * self.slots
         self._poisoned = [False] * self.slots
+        self._row_nq = [self.n_q] * self.slots
 
     def _slot(self, slot) -> int:
         if not isinstance(slot, int) or not 0 <= slot < self.slots:
             raise EngineError(f"this session has slots 0 .. {self.slots - 1}, got {slot!r}")
         return slot
 
-    def start(self, slot: int, scale=None) -> None:
+    def set_n_q(self, slot: int, n_q: int) -> None:
+        """the slot's stage count for the pushes that follow; a refused call changes nothing"""
         slot = self._slot(slot)
+        self._row_nq[slot] = self._checked_row_nq([n_q], 1)[0]
+
+    def start(self, slot: int, scale=None, n_q=None) -> None:
+        slot = self._slot(slot)
+        n_q = self.n_q if n_q is None else self._checked_row_nq([n_q], 1)[0]      # refused before the slot is touched
+        self._row_nq[slot] = n_q
         self._enc[slot], self._dec[slot] = _Side(), _Side()
         self._scale[slot] = 1.0 if scale is None else float(torch.as_tensor(scale).reshape(()))
         self._poisoned[slot] = False
@@ -378,8 +425,9 @@ class StreamSlots(_Session):
         quant = torch.empty((S, Tf, D), dtype=torch.float32, device=self.device)
         enc = torch.empty((S, Tf, D), dtype=torch.float32, device=self.device) if (self.arch.bypass_quantizer or want_enc_out) else None
         ws = self._ws()
-        self.engine._check(self.lib.fc_slots_encode(self._h, _ptr(wav), Tc, counts, flags, _ptr(scale), _ptr(codes), _ptr(quant), _ptr(enc),
-                                                    _ptr(ws), ws.numel(), self.engine._stream()))
+        with self._engine_row_nq(self._push_row_nq()):
+            self.engine._check(self.lib.fc_slots_encode(self._h, _ptr(wav), Tc, counts, flags, _ptr(scale), _ptr(codes), _ptr(quant), _ptr(enc),
+                                                        _ptr(ws), ws.numel(), self.engine._stream()))
         out = {}
         for slot, (w, f) in rows.items():
             n = self.engine.frames(w.shape[-1]) if f & FC_SLOT_FINAL else w.shape[-1] // self.hop
@@ -427,8 +475,9 @@ class StreamSlots(_Session):
         if emb:
             rc = self.lib.fc_slots_decode_emb(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), _ptr(ws), ws.numel(), self.engine._stream())
         else:
-            rc = self.lib.fc_slots_decode_codes(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(),
-                                                self.engine._stream())
+            with self._engine_row_nq(self._push_row_nq()):
+                rc = self.lib.fc_slots_decode_codes(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(),
+                                                    self.engine._stream())
         self.engine._check(rc)
         return {slot: (wav[slot, :, :t.shape[0] * self.hop],) for slot, (t, f) in rows.items()}
 

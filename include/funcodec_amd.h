@@ -193,6 +193,28 @@ int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengt
                             int64_t* codes, float* quantized, float* sub_quants, float* scale, float* recon,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- a bit rate per row ----------------------------------------------------------------------------
+ * (an entry point added without a struct change: FC_ABI_VERSION stays 7)
+ * A residual quantiser is a prefix code: stage i depends on the stages before it only, and nothing is carried from frame to frame.  So
+ * every row of a batch, a streaming session or a slot session may run its own number of stages, and change it from one call to the next.
+ *   n_q_rows   HOST i32 [B], each in [1, num_quantizers]: the stage counts of the calls that FOLLOW on this engine; NULL clears them
+ *              (B is then ignored).  The engine keeps them in a small device table of its own; the copy is ordered on `stream`, the
+ *              caller's array may go when the call returns.
+ * While a table is set, every call that quantises or looks up codes -- fc_encode, fc_encode_decode, fc_decode_codes, their _ragged
+ * siblings, the encode and decode_codes pushes of both session kinds, and the per-op hook for the quantiser -- must have batch width (or
+ * slot count) B, and its n_q argument (a session's: the n_q of create) is the CAP: the first dimension of its codes, >= every entry.  A call
+ * that breaks either rule is refused before its first launch and changes nothing.  The table is indexed by batch row (in a slot push: by
+ * slot; the count of an idle slot is ignored).  Row b with count k:
+ *   - codes[:k], and the quantised embeddings, their decoder input and the reconstruction, are bit for bit what the same call with
+ *     n_q = k gives that row; codes[k:] and sub_quants[k:] of the row are 0 (behind a row's length of a ragged call: as ever);
+ *   - a decode call sums the row's first k code vectors and does not read its codes[.., k:]: whatever they hold changes nothing and is
+ *     never reported as out of range.
+ * In the per-op hook the N rows are B utterances of N / B frames each (N a multiple of B).
+ * The calls that take embeddings are not concerned.  With no table set every call launches exactly what it launched before.
+ * Segmented mode (model_conf.segment_dur: segments are extra batch rows) and model_conf.bypass_quantizer are host-side matters -- fc_arch
+ * has neither field -- so only the host wrappers can refuse them, and do. */
+int fc_engine_set_row_nq(fc_engine* e, const int32_t* n_q_rows /* host [B] or NULL */, int B, void* stream);
+
 /* _linear_overlap_add (funcodec/models/codec_basic.py:77-116), the tail of Encodec._decode (:382-396) when
  * model_conf.segment_dur is set: triangle-weighted overlap-add of the decoded segments, products accumulated in
  * frame order and divided once by the summed weights, exactly as the reference orders it.

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libfuncodec_amd.so")
 OBJ_DIR = os.path.join(CSRC, "_obj")
-HEADERS = ["kernels.h", "conv_kernel.h", "laura_kernels.h", "seq_kernels.h", "stream_kernels.h", "ragged_kernels.h", "slots_kernels.h", os.path.join("..", "..", "include", "funcodec_amd.h")]
+HEADERS = ["kernels.h", "device_common.h", "conv_kernel.h", "laura_kernels.h", "seq_kernels.h", "stream_kernels.h", "ragged_kernels.h", "slots_kernels.h", os.path.join("..", "..", "include", "funcodec_amd.h")]
 
 
 def sources():

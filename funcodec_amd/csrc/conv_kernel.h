@@ -2,6 +2,7 @@
 // DECLARES the per-tile launchers) and by one conv_tile_*.hip per tile shape (which instantiates them): the ~180 instantiations
 // then compile as five parallel translation units instead of one 4-minute one.
 #pragma once
+#include "device_common.h"
 #include "kernels.h"
 
 #include <atomic>
@@ -12,8 +13,6 @@
 namespace fc {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));     // 4-byte aligned vector stores (global memory takes them)
 typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
 
 static inline __host__ __device__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -102,15 +101,6 @@ struct ConvArgs {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-// ELU(alpha) on the hardware exp2: exp(v) = 2^(v*log2 e).  For v <= 0 the rounding of the product contributes
-// |v|*log2(e)*2^-24 relative error to e^v, i.e. at most 3e-8 absolute on the ELU output (below one fp32 ulp of the
-// result), so no compensated product is needed.  fp32 MFMA and fp32 VALU share the SIMD's FMA lanes on gfx950
-// (tests/micro/mfma_valu_overlap.hip: the two do not overlap), so every VALU instruction here is paid in full.
-__device__ __forceinline__ float elu_f(float v, float alpha) {
-    const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f);
-    return v > 0.f ? v : fmaf(e, alpha, -alpha);
-}
 
 // Buffer loads for the register-staged quad paths (round 5): `buffer_load_dword v, v_off, s[rsrc], s_off offen` forms its address from a scalar
 // descriptor, a scalar offset and ONE 32-bit lane offset -- no vector instruction.  The global_load form hipcc picks for `base + lane offset`
@@ -383,7 +373,6 @@ __global__ __launch_bounds__(512, 4) void conv_mfma_kernel(const ConvArgs p) {
             // instructions are issued in the gaps of the co-resident matrix wave's MFMA stream, the item lasts as long as the busiest one.
             // Tail columns ((k - 1) * dilation per row): one (channel quad, column) unit per thread.
             // ---------------------------------------------------------------------------------------------
-            typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
             typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
             // NU 14 / 13 (round 6): ONE full round of 256 (4 channels x 4 columns) units re-cut as 4 rounds of 1-column units / 2 rounds of 2-column
             // units.  Why: a `ds_write_b128` is serviced in groups of 8 consecutive lanes over 32 banks (MI355X_MICROARCH.md), and with 4 columns
@@ -595,7 +584,6 @@ __global__ __launch_bounds__(512, 4) void conv_mfma_kernel(const ConvArgs p) {
             // Edge tiles (reflect / zero padding inside the slab) load the 4 columns of a lane with 4 dword loads
             // from per-tile column offsets instead.
             // ---------------------------------------------------------------------------------------------
-            typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
             constexpr int LPR = BN / 4, RPI = 64 / LPR, RPR = 4 * RPI;     // lanes per row, rows per instruction / round
             // rounds per item: a compile-time constant in the specialised instantiations (NU = 2 / 4 / 8 here) so that the loads
             // of an item are straight-line code.  With a run-time count every load sat behind its own scalar branch, the loaded
@@ -1226,7 +1214,7 @@ __global__ __launch_bounds__(512, 4) void conv_mfma_kernel(const ConvArgs p) {
                             const float v0 = acc[i][j][4 * rq], v1 = acc[i][j][4 * rq + 1], v2 = acc[i][j][4 * rq + 2], v3 = acc[i][j][4 * rq + 3];
                             const int t = n * p.up_r + phs - p.trimL;
                             if (t >= 0 && t + 3 < p.Tfinal) {
-                                *(f32x4_u*)(rowp + t) = (f32x4_u){v0, v1, v2, v3};
+                                *(f32x4u*)(rowp + t) = (f32x4u){v0, v1, v2, v3};
                             } else {
                                 if (t >= 0 && t < p.Tfinal) rowp[t] = v0;
                                 if (t + 1 >= 0 && t + 1 < p.Tfinal) rowp[t + 1] = v1;

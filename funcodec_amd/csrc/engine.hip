@@ -391,8 +391,6 @@ ConvLayer mk_conv_(const std::string& prefix, int cin, int cout, int k, int stri
     return L;
 }
 
-void choose_tiling(ConvLayer& L);
-
 // ---- STFT-domain codec: SEANetEncoder2d / SEANetDecoder2d (seanet_encoder.py:252-363, seanet_decoder.py:244-360) ---------------
 // Same Sequential indexing as the reference; every Conv2d is planned as a 1-D GEMM over kf * C channels (frequency-major layout).
 // `groups` > 1 (conv_group_ratio > 0): the layer still runs as the dense GEMM over a block-diagonal weight built at finalize (the
@@ -1791,7 +1789,7 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
     if (e->arch.audio_normalize) {
         sc = scale ? scale : cx.alloc<float>(B);
         cx.launch("volume", "", [&] {
-            return p.kind == Pass::Ragged ? fc::launch_ragged_volume(wav, B, e->audio_ch(), T, p.lengths, sc, cx.st) : fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st);
+            return fc::launch_volume(wav, B, e->audio_ch(), T, sc, cx.st, p.kind == Pass::Ragged ? p.lengths : nullptr);
         });
     }
     fc::Src s; s.ptr = wav; s.div = sc; s.used = e->arch.audio_normalize ? 3 : 1;

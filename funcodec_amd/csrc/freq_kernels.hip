@@ -6,12 +6,12 @@
 // fo*sf (conv_kernel.h, two-level batch addressing); the frequency padding (pad2d reflect, conv.py:100-119) is materialised as
 // halo rows by halo_rows_kernel.  The STFT and its inverse are GEMMs on the same conv kernel (DFT matrix as conv weights over the
 // hop-phase ("polyphase") view of the signal); what is left for this file is layout changes and pointwise math.
+#include "device_common.h"
 #include "kernels.h"
 
 namespace fc {
 
 static inline __host__ __device__ int cdiv(int a, int b) { return (a + b - 1) / b; }
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // xp[b][j][m] = xpad[m*hop + j], xpad = reflect-padded (n_fft/2 each side, torch.stft center=True) utterance, zero beyond it.
 // (optionally / div[b]: the volume normalisation of _encode_frame, codec_freq.py:334-341)
@@ -142,7 +142,6 @@ hipError_t launch_halo_rows_short(float* buf, int B, int F, int halo, int pad, i
 __global__ __launch_bounds__(256) void combine2d_kernel(const float* __restrict__ s0, const float* __restrict__ aff0, int h0,
                                                         const float* __restrict__ s1, const float* __restrict__ aff1, int h1,
                                                         int elu, float alpha, int F, int C, int T, float* __restrict__ dst, int hd, int halo_mode) {
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     const int b = blockIdx.z, fc = blockIdx.y, f = fc / C, c = fc - f * C;
     // halo rows of dst written here instead of by a halo_rows launch (round 4): mode 1 = reflect (row -i = row i, row F-1+i = row F-1-i; the
     // row's own workgroup stores it a second time), mode 2 = zeros (the edge rows' workgroups clear them).  Offsets in rows relative to row f.
@@ -308,13 +307,12 @@ template <int CPG, int OPG, int KF, int KT, int ST, bool DUAL, int FO, bool NEED
 __global__ __launch_bounds__(256) FC_GCONV_ATTR void gconv2d_kernel(const GConvArgs p) {
     // FO = output frequency rows per lane (rows fo0, fo0 + 1): the KF + (FO - 1) SF input rows they read are loaded and activated once
     // instead of FO x KF times (3x3: 4 rows instead of 6; 8-row stride-4 layers: 12 instead of 16)
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     constexpr int NE = 3 * ST + KT;              // input columns behind 4 outputs
     constexpr int NV = (NE + 3) / 4;             // 16-byte pieces
     constexpr int NW = OPG * CPG * KF * KT;
     __shared__ float wsh[NW];
     __shared__ double red[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     const int tile = blockIdx.x, g = blockIdx.y, z = blockIdx.z;
     const int FoP = (p.Fo + FO - 1) / FO;        // row groups per utterance
     const int b = z / FoP, fo0 = (z - b * FoP) * FO;
@@ -495,18 +493,11 @@ __global__ __launch_bounds__(256) FC_GCONV_ATTR void gconv2d_kernel(const GConvA
         }
     }
     if (p.partials) {
-        double d1 = (double)s1v, d2 = (double)s2v;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            d1 += __shfl_xor(d1, off, 64);
-            d2 += __shfl_xor(d2, off, 64);
-        }
-        if (lane == 0) { red[0][wid] = d1; red[1][wid] = d2; }
-        __syncthreads();
-        if (tid == 0) {
+        double t1, t2;
+        if (gn_partial_reduce(s1v, s2v, red, t1, t2)) {
             const size_t slot = ((((size_t)b * FoP + (fo0 / FO)) * p.G + g) * gridDim.x + tile) * 2;
-            p.partials[slot] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-            p.partials[slot + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+            p.partials[slot] = t1;
+            p.partials[slot + 1] = t2;
         }
     }
 }
@@ -526,7 +517,6 @@ constexpr int G3_RF = 8, G3_TN = 256, G3_PW = 264;       // output rows / column
 
 template <int CPG, int OPG, bool DUAL>
 __global__ __launch_bounds__(256) void gconv2d_3x3_lds_kernel(const GConvArgs p) {
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     constexpr int PR = G3_RF + 2;                        // patch rows
     constexpr int NPC = (G3_TN + 2 + 3) / 4;             // 16-byte pieces per patch row (65: columns 0 .. 259)
@@ -655,18 +645,11 @@ __global__ __launch_bounds__(256) void gconv2d_3x3_lds_kernel(const GConvArgs p)
         }
     }
     if (p.partials) {
-        double d1 = (double)s1v, d2 = (double)s2v;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            d1 += __shfl_xor(d1, off, 64);
-            d2 += __shfl_xor(d2, off, 64);
-        }
-        if (lane == 0) { red[0][wid] = d1; red[1][wid] = d2; }
-        __syncthreads();
-        if (tid == 0) {
+        double t1, t2;
+        if (gn_partial_reduce(s1v, s2v, red, t1, t2)) {
             const size_t slot = ((((size_t)b * FoT + (fo0 / G3_RF)) * p.G + g) * gridDim.x + tile) * 2;
-            p.partials[slot] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-            p.partials[slot + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+            p.partials[slot] = t1;
+            p.partials[slot + 1] = t2;
         }
     }
 }
@@ -817,10 +800,9 @@ struct GConvTrArgs {
 #endif
 template <int TR>
 __global__ __launch_bounds__(256) void gconvtr2d_kernel(const GConvTrArgs p) {
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     constexpr int NI = 4 / TR + 1;                   // input columns behind 4 untrimmed output columns
     __shared__ double red[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     // XCD-aware order (round 4).  Neighbouring input-row pairs share a row (row q is read again for pair q + 1): in dispatch order
     // (workgroup w -> XCD w % 8, observed) they sat on different XCDs and every XCD's L2 fetched the input again.  1-D grid of 8 * per
     // workgroups; XCD x walks the contiguous range [x * per, (x + 1) * per) of the (tile, row, utterance) order.
@@ -950,23 +932,16 @@ __global__ __launch_bounds__(256) void gconvtr2d_kernel(const GConvTrArgs p) {
             }
         }
     }
-    double d1 = (double)s1v, d2 = (double)s2v;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        d1 += __shfl_xor(d1, off, 64);
-        d2 += __shfl_xor(d2, off, 64);
-    }
-    if (lane == 0) { red[0][wid] = d1; red[1][wid] = d2; }
-    __syncthreads();
-    if (tid == 0 && p.partials) {                        // weight_norm nets: no GroupNorm statistics
+    double t1, t2;
+    if (gn_partial_reduce(s1v, s2v, red, t1, t2) && p.partials) {        // weight_norm nets: no GroupNorm statistics
         // partial slots stay one per (utterance, untrimmed output row, tile): the cs workgroups of an input-row pair share its fr slots --
         // chunk c fills slot c and zeroes slots c + cs, c + 2 cs, ...
         const int nrows = (p.Fin + 1) * p.fr;
         const int step = FC_GCONVTR_ROWS ? p.cs : 1, first = FC_GCONVTR_ROWS ? chunk : ph_lo;
         for (int ph_f = first; ph_f < ph_hi; ph_f += step) {
             const size_t slot = (((size_t)b * nrows + (q * p.fr + ph_f)) * p.nx + tile) * 2;
-            p.partials[slot] = ph_f == first ? ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3] : 0.0;
-            p.partials[slot + 1] = ph_f == first ? ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3] : 0.0;
+            p.partials[slot] = ph_f == first ? t1 : 0.0;
+            p.partials[slot + 1] = ph_f == first ? t2 : 0.0;
         }
     }
 }

@@ -173,8 +173,10 @@ hipError_t launch_combine(const Src& s0, const Src& s1, int elu, float alpha, co
 // x = tanh(x) * range in place over n floats (CostumeQuantizer.input_act, costume_quantizer.py:32-35,66-67)
 hipError_t launch_tanh_range(float* x, size_t n, float range, hipStream_t st);
 
-// scale[b] = 1e-8 + sqrt(mean_t x[b][t]^2)
-hipError_t launch_volume(const float* wav /* [B][C][T], C = 1 | 2 */, int B, int C, int T, float* scale, hipStream_t st);
+// scale[b] = 1e-8 + sqrt(mean_t x[b][t]^2) of the channel mean (codec_basic.py:366-371); lens (device, [B]) or null: over the row's own
+// first lens[b] samples instead of all T (length-aware batches)
+hipError_t launch_volume(const float* wav /* [B][C][T], C = 1 | 2 */, int B, int C, int T, float* scale, hipStream_t st,
+                         const int* lens = nullptr);
 
 // [B][T][D] -> [B][D][T]
 hipError_t launch_transpose_btd(const float* in, int B, int T, int D, float* out, hipStream_t st);

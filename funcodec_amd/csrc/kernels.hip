@@ -301,12 +301,56 @@ struct Cout1Args {
 // streaming form below, which wins on the long 1-D rows: 187 vs 225 us.)
 constexpr int C1L_TN = 1024, C1L_CH = 8, C1L_ROW = 1032;
 
+// Padded-coordinate column g (g = 0 is the row's first sample) -> source index under reflect padding (pad1d, conv.py:82-99: a row not
+// longer than the padding is zero-extended to Leff before it reflects), or -1 where the staged value is a zero: left of the padding, or
+// a reflection that lands in the zero extension.  The one index map of the three few-output kernels.
+__device__ __forceinline__ int fewout_reflect_src(int g, int padL, int Leff, int T) {
+    int src = g < 0 ? -g : g;
+    src = src >= Leff ? 2 * (Leff - 1) - src : src;
+    return (g >= -padL && src >= 0 && src < T) ? src : -1;
+}
+
+// Epilogue of the two LDS forms (every lane holds outputs): a lane's 4 consecutive outputs n0 .. n0 + 3 of every output channel get their
+// bias and are stored (one 16-byte store, or the row's last 1 .. 3 values singly); the valid ones enter the lane's fp32 (sum, sum of
+// squares), which go to fewout_partial.  conv_cout1_kernel states the same steps itself (lanes without outputs, the tuning builds' store
+// switch): through this function every one of its instantiations allocated other registers.
+template <int MO>
+__device__ __forceinline__ float2 fewout_epilogue(const Cout1Args& p, const float (&acc)[MO][4], int n0, int breal, int fo) {
+    float s1v = 0.f, s2v = 0.f;
+#pragma unroll
+    for (int m = 0; m < MO; ++m) {
+        float o[4];
+        const float bm = p.bias[m];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o[j] = acc[m][j] + bm;
+            if (n0 + j < p.T) { s1v += o[j]; s2v = fmaf(o[j], o[j], s2v); }
+        }
+        float* orow = p.out + (size_t)breal * p.out_sB + (size_t)fo * p.out_sF + (size_t)m * p.out_sM + n0;
+        if (n0 + 3 < p.T) *(f32x4u*)orow = (f32x4){o[0], o[1], o[2], o[3]};
+        else
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (n0 + j < p.T) orow[j] = o[j];
+    }
+    return make_float2(s1v, s2v);
+}
+
+// ... and where the statistics of all three kernels go: reduced over the workgroup into its one (sum, sum of squares) slot
+__device__ __forceinline__ void fewout_partial(const Cout1Args& p, float2 sv, double (&red)[2][4], int breal, int fo, int tile) {
+    if (!p.partials) return;
+    double t1, t2;
+    if (gn_partial_reduce(sv.x, sv.y, red, t1, t2)) {
+        const size_t slot = ((size_t)breal * p.part_sB0 + (size_t)fo * gridDim.x + tile) * 2;
+        p.partials[slot] = t1;
+        p.partials[slot + 1] = t2;
+    }
+}
+
 template <int K, bool DUAL, int MO>
 __global__ __launch_bounds__(256) void conv_fewout_rows_kernel(const Cout1Args p) {
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     __shared__ __attribute__((aligned(16))) float Xs[C1L_CH][C1L_ROW];
     __shared__ double red[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     const int tile = blockIdx.x, b = blockIdx.y;
     const int breal = p.Fo > 1 ? b / p.Fo : b, fo = p.Fo > 1 ? b - breal * p.Fo : 0;
     const int t0 = tile * C1L_TN, tbase = t0 - p.padL;
@@ -321,18 +365,13 @@ __global__ __launch_bounds__(256) void conv_fewout_rows_kernel(const Cout1Args p
     const int g0 = tbase + 4 * tid;
     const bool vec_ok = g0 >= 0 && g0 + 3 < p.T;
     int esrc[5]; unsigned emask = 0;
-    {
-        const int refl = 2 * (p.Leff - 1);
 #pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const int col = j < 4 ? 4 * tid + j : 1024 + tid;
-            const int g = tbase + col;
-            int src = g < 0 ? -g : g;
-            src = src >= p.Leff ? refl - src : src;
-            const bool ok = (j < 4 || tid < 8) && g >= -p.padL && src >= 0 && src < p.T;
-            esrc[j] = ok ? src : 0;
-            emask |= (ok ? 1u : 0u) << j;
-        }
+    for (int j = 0; j < 5; ++j) {
+        const int col = j < 4 ? 4 * tid + j : 1024 + tid;
+        const int src = (j < 4 || tid < 8) ? fewout_reflect_src(tbase + col, p.padL, p.Leff, p.T) : -1;
+        const bool ok = src >= 0;
+        esrc[j] = ok ? src : 0;
+        emask |= (ok ? 1u : 0u) << j;
     }
     auto act = [&](float v, float w, float2 A, float2 A1) __attribute__((always_inline)) {
         if FC_ABL(p.ablate, 8) return v;
@@ -414,38 +453,7 @@ __global__ __launch_bounds__(256) void conv_fewout_rows_kernel(const Cout1Args p
         __syncthreads();
     }
     // ---- epilogue: bias, store, statistics of the valid outputs
-    float s1v = 0.f, s2v = 0.f;
-#pragma unroll
-    for (int m = 0; m < MO; ++m) {
-        float o[4];
-        const float bm = p.bias[m];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            o[j] = acc[m][j] + bm;
-            const int n = t0 + 4 * tid + j;
-            if (n < p.T) { s1v += o[j]; s2v = fmaf(o[j], o[j], s2v); }
-        }
-        float* orow = p.out + (size_t)breal * p.out_sB + (size_t)fo * p.out_sF + (size_t)m * p.out_sM + t0 + 4 * tid;
-        if (t0 + 4 * tid + 3 < p.T) *(f32x4u*)orow = (f32x4){o[0], o[1], o[2], o[3]};
-        else
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (t0 + 4 * tid + j < p.T) orow[j] = o[j];
-    }
-    if (p.partials) {
-        double d1 = (double)s1v, d2 = (double)s2v;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            d1 += __shfl_xor(d1, off, 64);
-            d2 += __shfl_xor(d2, off, 64);
-        }
-        if (lane == 0) { red[0][wid] = d1; red[1][wid] = d2; }
-        __syncthreads();
-        if (tid == 0) {
-            const size_t slot = ((size_t)breal * p.part_sB0 + (size_t)fo * gridDim.x + tile) * 2;
-            p.partials[slot] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-            p.partials[slot + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-        }
-    }
+    fewout_partial(p, fewout_epilogue<MO>(p, acc, t0 + 4 * tid, breal, fo), red, breal, fo, tile);
 }
 
 // PLAIN-input form of the rows kernel (round 4): the source is one already materialised tensor (no affine, no ELU, one source -- the 2-D
@@ -481,15 +489,11 @@ __global__ __launch_bounds__(256) void conv_fewout_rows_plain_kernel(const Cout1
     int first_bad = (p.T - gbase) >> 2;                               // smallest tid with gbase + 4 tid + 3 >= T
     first_bad = first_bad < (cl >> 2) ? (cl >> 2) : (first_bad > 256 ? 256 : first_bad);
     const int cr = 4 * first_bad;
-    const int refl = 2 * (p.Leff - 1);
     // this wave's edge columns (it serves row `wid` of every stage): column -> reflected source index, or -1 (a zero for every channel)
     constexpr int NE = (C1L_ROW + 63) / 64 + 1;                       // 64-column pieces: [0, cl) is one, [cr, C1L_ROW) at most 17
     int esrc[2];                                                      // common case: two pieces (left + right); longer ranges loop below
     auto edge_src = [&](int col) __attribute__((always_inline)) {
-        const int g = gbase + col;
-        int src = g < 0 ? -g : g;
-        src = src >= p.Leff ? refl - src : src;
-        return (col < C1L_ROW && g >= -p.padL && src >= 0 && src < p.T) ? src : -1;
+        return col < C1L_ROW ? fewout_reflect_src(gbase + col, p.padL, p.Leff, p.T) : -1;
     };
     (void)NE;
     esrc[0] = lane < cl ? edge_src(lane) : -1;
@@ -563,40 +567,8 @@ __global__ __launch_bounds__(256) void conv_fewout_rows_plain_kernel(const Cout1
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
-    // ---- epilogue: bias, store, statistics of the valid outputs (as above)
-    float s1v = 0.f, s2v = 0.f;
-#pragma unroll
-    for (int m = 0; m < MO; ++m) {
-        float o[4];
-        const float bm = p.bias[m];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            o[j] = acc[m][j] + bm;
-            const int n = t0 + 4 * tid + j;
-            if (n < p.T) { s1v += o[j]; s2v = fmaf(o[j], o[j], s2v); }
-        }
-        typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-        float* orow = p.out + (size_t)breal * p.out_sB + (size_t)fo * p.out_sF + (size_t)m * p.out_sM + t0 + 4 * tid;
-        if (t0 + 4 * tid + 3 < p.T) *(f32x4u*)orow = (f32x4){o[0], o[1], o[2], o[3]};
-        else
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (t0 + 4 * tid + j < p.T) orow[j] = o[j];
-    }
-    if (p.partials) {
-        double d1 = (double)s1v, d2 = (double)s2v;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            d1 += __shfl_xor(d1, off, 64);
-            d2 += __shfl_xor(d2, off, 64);
-        }
-        if (lane == 0) { red[0][wid] = d1; red[1][wid] = d2; }
-        __syncthreads();
-        if (tid == 0) {
-            const size_t slot = ((size_t)breal * p.part_sB0 + (size_t)fo * gridDim.x + tile) * 2;
-            p.partials[slot] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-            p.partials[slot + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-        }
-    }
+    // ---- epilogue: bias, store, statistics of the valid outputs
+    fewout_partial(p, fewout_epilogue<MO>(p, acc, t0 + 4 * tid, breal, fo), red, breal, fo, tile);
 }
 
 constexpr int C1_WOUT = 248, C1_TN = 4 * C1_WOUT, C1_UN = 4;    // outputs per wave / per workgroup; channels per load group
@@ -612,7 +584,6 @@ __device__ __forceinline__ float wave_shl1(float v) {
 // current 4 are multiplied.  Lanes at a padded edge (reflect, conv.py:82-99) gather their 4 samples by index instead.
 template <int K, bool DUAL, int MO>
 __global__ __launch_bounds__(256) void conv_cout1_kernel(const Cout1Args p) {
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     __shared__ double red[2][4];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int tile = blockIdx.x, b = blockIdx.y;
@@ -628,17 +599,11 @@ __global__ __launch_bounds__(256) void conv_cout1_kernel(const Cout1Args p) {
     const int g0 = t0 - p.padL + 4 * lane;                      // padded-coordinate index of this lane's first sample
     const bool vec_ok = g0 >= 0 && g0 + 3 < p.T;
     int esrc[4]; unsigned emask = 0;
-    {
-        const int refl = 2 * (p.Leff - 1);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int g = g0 + j;
-            int src = g < 0 ? -g : g;
-            src = src >= p.Leff ? refl - src : src;
-            const bool ok = g >= -p.padL && src >= 0 && src < p.T;
-            esrc[j] = ok ? src : 0;
-            emask |= (ok ? 1u : 0u) << j;
-        }
+    for (int j = 0; j < 4; ++j) {
+        const int src = fewout_reflect_src(g0 + j, p.padL, p.Leff, p.T);
+        esrc[j] = src >= 0 ? src : 0;
+        emask |= (src >= 0 ? 1u : 0u) << j;
     }
     const unsigned vmask = vec_ok ? 0xFu : emask;
     float acc[MO][4];
@@ -732,26 +697,27 @@ __global__ __launch_bounds__(256) void conv_cout1_kernel(const Cout1Args p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (n0 + j < p.T) orow[j] = o[j];
     }
-    if (p.partials) {
-        double d1 = (double)s1v, d2 = (double)s2v;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            d1 += __shfl_xor(d1, off, 64);
-            d2 += __shfl_xor(d2, off, 64);
-        }
-        if (lane == 0) { red[0][wid] = d1; red[1][wid] = d2; }
-        __syncthreads();
-        if (tid == 0) {
-            const size_t slot = ((size_t)breal * p.part_sB0 + (size_t)fo * gridDim.x + tile) * 2;
-            p.partials[slot] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-            p.partials[slot + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-        }
-    }
+    fewout_partial(p, make_float2(s1v, s2v), red, breal, fo, tile);
 }
 
 bool conv_cout1_ok(const ConvLaunch& c) {
     return c.w_plain && c.M >= 1 && c.M <= 4 && c.store_lo <= 0 && c.store_hi >= c.Fo && c.stride == 1 && c.dil == 1 && !c.up_r && !c.pad_zero && !c.s0.div && c.out_sT == 1 && c.Tout == c.Tin &&
            (c.k == 7 || c.k == 3 || c.k == 5) && c.padL + c.padR == c.k - 1;
+}
+
+// one (k, M): the all-DMA plain form, the LDS rows form or the streaming form, the latter two with one or two sources
+template <int K, int MO>
+static hipError_t launch_fewout(const ConvLaunch& c, const Cout1Args& a, dim3 grid, hipStream_t st) {
+    const dim3 block(256);
+    if (conv_fewout_plain(c)) hipLaunchKernelGGL((conv_fewout_rows_plain_kernel<K, MO>), grid, block, 0, st, a);
+    else if (conv_fewout_rows(c)) {
+        if (c.s1.ptr) hipLaunchKernelGGL((conv_fewout_rows_kernel<K, true, MO>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((conv_fewout_rows_kernel<K, false, MO>), grid, block, 0, st, a);
+    } else {
+        if (c.s1.ptr) hipLaunchKernelGGL((conv_cout1_kernel<K, true, MO>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((conv_cout1_kernel<K, false, MO>), grid, block, 0, st, a);
+    }
+    return hipGetLastError();
 }
 
 static hipError_t launch_conv_cout1(const ConvLaunch& c, hipStream_t st) {
@@ -770,38 +736,22 @@ static hipError_t launch_conv_cout1(const ConvLaunch& c, hipStream_t st) {
     a.Leff = c.Tin > maxpad ? c.Tin : maxpad + 1;
     a.elu = c.elu; a.alpha = c.alpha;
     if (c.B > 65535) return hipErrorInvalidValue;
-    dim3 grid(ceil_div(c.Tout, tile_n), c.B), block(256);
-    const bool rows = tile_n == C1L_TN;
-    // one materialised source, no prologue arithmetic: the all-DMA staging form
-    if (conv_fewout_plain(c)) {
-#define FC_C1P(KK, MM) if (c.k == KK && c.M == MM) { hipLaunchKernelGGL((conv_fewout_rows_plain_kernel<KK, MM>), grid, block, 0, st, a); return hipGetLastError(); }
-        FC_C1P(3, 1) FC_C1P(3, 2) FC_C1P(3, 3) FC_C1P(3, 4) FC_C1P(5, 1) FC_C1P(5, 2) FC_C1P(5, 3) FC_C1P(5, 4)
-        FC_C1P(7, 1) FC_C1P(7, 2) FC_C1P(7, 3) FC_C1P(7, 4)
-#undef FC_C1P
-    }
-#define FC_C1M(KK, MM)                                                                                  \
-    case MM:                                                                                            \
-        if (rows) {                                                                                     \
-            if (c.s1.ptr) hipLaunchKernelGGL((conv_fewout_rows_kernel<KK, true, MM>), grid, block, 0, st, a);  \
-            else hipLaunchKernelGGL((conv_fewout_rows_kernel<KK, false, MM>), grid, block, 0, st, a);   \
-        } else {                                                                                        \
-            if (c.s1.ptr) hipLaunchKernelGGL((conv_cout1_kernel<KK, true, MM>), grid, block, 0, st, a); \
-            else hipLaunchKernelGGL((conv_cout1_kernel<KK, false, MM>), grid, block, 0, st, a);         \
-        }                                                                                               \
-        break;
-#define FC_C1(KK)                                                                                       \
-    case KK:                                                                                            \
-        switch (c.M) { FC_C1M(KK, 1) FC_C1M(KK, 2) FC_C1M(KK, 3) FC_C1M(KK, 4) default: return hipErrorInvalidValue; } \
-        break;
-    switch (c.k) {
-        FC_C1(3)
-        FC_C1(5)
-        FC_C1(7)
+    const dim3 grid(ceil_div(c.Tout, tile_n), c.B);
+    switch (10 * c.k + c.M) {       // case "kM": k in {3, 5, 7}, M in 1 .. 4 (conv_cout1_ok)
+        case 31: return launch_fewout<3, 1>(c, a, grid, st);
+        case 32: return launch_fewout<3, 2>(c, a, grid, st);
+        case 33: return launch_fewout<3, 3>(c, a, grid, st);
+        case 34: return launch_fewout<3, 4>(c, a, grid, st);
+        case 51: return launch_fewout<5, 1>(c, a, grid, st);
+        case 52: return launch_fewout<5, 2>(c, a, grid, st);
+        case 53: return launch_fewout<5, 3>(c, a, grid, st);
+        case 54: return launch_fewout<5, 4>(c, a, grid, st);
+        case 71: return launch_fewout<7, 1>(c, a, grid, st);
+        case 72: return launch_fewout<7, 2>(c, a, grid, st);
+        case 73: return launch_fewout<7, 3>(c, a, grid, st);
+        case 74: return launch_fewout<7, 4>(c, a, grid, st);
         default: return hipErrorInvalidValue;
     }
-#undef FC_C1
-#undef FC_C1M
-    return hipGetLastError();
 }
 
 // =================================================================================================
@@ -848,7 +798,6 @@ template <int C, int K3, bool DUAL>
 __global__ __launch_bounds__(256, C == 32 ? 3 : 2) void reshead_kernel(const ResHeadArgs p) {
     constexpr int HID = C / 2, NCH = C / RH_CH, MT = C / 32;
     constexpr bool B16 = HID == 16;                         // block.1 on 16x16x4 tiles
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Wsc = smem;                                      // [C][C]
     float* Wb1 = Wsc + C * C;                               // [K3*C][HID]
@@ -1245,7 +1194,6 @@ __global__ __launch_bounds__(256) void combine_kernel(Src s0, Src s1, int elu, f
     if (o_sT == 1 && !s0.div) {
         // contiguous output rows (every materialisation inside the engine): 4 samples per thread, 16-byte loads / stores
         // (dword alignment only: rows start at row * Tsrc floats)
-        typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
         float* orow = out + (size_t)b * o_sB + (size_t)c * o_sC;
         const float* r0 = s0.ptr + row * Tsrc;
         const float* r1 = s1.ptr ? s1.ptr + row * Tsrc : r0;
@@ -1313,7 +1261,6 @@ hipError_t launch_combine(const Src& s0, const Src& s1, int elu, float alpha, co
 // contiguous bytes.
 __global__ __launch_bounds__(256) void combine_xq_kernel(Src s0, Src s1, int elu, float alpha, int C, int Tin, int padL, int padR, int pad_zero,
                                                          int Leff, float* __restrict__ xq) {
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     const int b = blockIdx.z, g4 = blockIdx.y, Tp = padL + Tin + padR;
     const size_t row0 = (size_t)b * C + 4 * g4;
     float2 a0[4], a1[4];
@@ -1399,39 +1346,40 @@ hipError_t launch_combine_xq(const Src& s0, const Src& s1, int elu, float alpha,
 
 // volume = sqrt(mean(mono^2)); scale = 1e-8 + volume, mono = the channel mean        (Encodec._encode_frame codec_basic.py:366-371)
 // wav [B][C][T], C = 1 or 2 (stereo: mono = (left + right) / 2, the fp32 sum torch's x.mean(dim=1) forms, halved exactly)
+// lens (device, [B], or null): row b is its first lens[b] samples -- the same kernel with n in place of T, so a row of a length-aware
+// batch gets the scale of the one-utterance call of that length by construction
 template <int C>
-__global__ __launch_bounds__(1024) void volume_kernel(const float* __restrict__ wav, int T, float* __restrict__ scale) {
+__global__ __launch_bounds__(1024) void volume_kernel(const float* __restrict__ wav, int T, const int* __restrict__ lens,
+                                                      float* __restrict__ scale) {
     __shared__ double sh[1024];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x, tid = threadIdx.x, n = lens ? lens[b] : T;
     const float* x = wav + (size_t)b * C * T;
     // 16-byte loads (dword alignment only: T need not be a multiple of 4) and four independent fp64 chains per thread:
     // one dependent add chain per element kept this 10 MB reduction at 70 us
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    const int T4 = T >> 2;
-    for (int q = tid; q < T4; q += 1024) {
+    const int n4 = n >> 2;
+    for (int q = tid; q < n4; q += 1024) {
         f32x4 v = *(const f32x4u*)(x + 4 * q);
         if (C == 2) v = (v + (f32x4)(*(const f32x4u*)(x + T + 4 * q))) * 0.5f;
         s0 += (double)(v[0] * v[0]); s1 += (double)(v[1] * v[1]); s2 += (double)(v[2] * v[2]); s3 += (double)(v[3] * v[3]);
     }
-    for (int t = 4 * T4 + tid; t < T; t += 1024) {
+    for (int t = 4 * n4 + tid; t < n; t += 1024) {
         float v = x[t];
         if (C == 2) v = (v + x[T + t]) * 0.5f;
         s0 += (double)(v * v);
     }
-    const double s = (s0 + s1) + (s2 + s3);
-    sh[tid] = s;
+    sh[tid] = (s0 + s1) + (s2 + s3);
     __syncthreads();
     for (int o = 512; o >= 1; o >>= 1) {
         if (tid < o) sh[tid] += sh[tid + o];
         __syncthreads();
     }
-    if (tid == 0) scale[b] = 1e-8f + sqrtf((float)(sh[0] / (double)T));
+    if (tid == 0) scale[b] = 1e-8f + sqrtf((float)(sh[0] / (double)n));
 }
 
-hipError_t launch_volume(const float* wav, int B, int C, int T, float* scale, hipStream_t st) {
-    if (C == 1) hipLaunchKernelGGL(volume_kernel<1>, dim3(B), dim3(1024), 0, st, wav, T, scale);
-    else if (C == 2) hipLaunchKernelGGL(volume_kernel<2>, dim3(B), dim3(1024), 0, st, wav, T, scale);
+hipError_t launch_volume(const float* wav, int B, int C, int T, float* scale, hipStream_t st, const int* lens) {
+    if (C == 1) hipLaunchKernelGGL(volume_kernel<1>, dim3(B), dim3(1024), 0, st, wav, T, lens, scale);
+    else if (C == 2) hipLaunchKernelGGL(volume_kernel<2>, dim3(B), dim3(1024), 0, st, wav, T, lens, scale);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1472,6 +1420,85 @@ hipError_t launch_transpose_btd(const float* in, int B, int T, int D, float* out
 //                d = 16q + 4g + j  for q = 0..D/16-1, j = 0..3, g = 0..3 (innermost);
 //      |e|^2   : precomputed at load time (engine.hip), sequential d = 0..D-1, squares rounded separately.
 // =================================================================================================
+// ---- the steps rvq_encode_kernel and rvq_encode_wide_kernel share, stated once (ROWS = rows of the workgroup).  The two tails (the RQ
+//      zeros behind the last stage, the quant / quant_bdt store) are the same lines in both kernels too, but stay in the kernels: as
+//      functions they changed the register allocation of most RQ instantiations (ROCm 7.2 hipcc, kernel-resource-usage remarks).
+
+// RQ: the stages this workgroup runs (the largest count among its rows) and, in krow, every row's own count (0 behind row N; read behind
+// the first barrier of stage 0).  The rows of a workgroup are consecutive frames, so their batch rows are consecutive too: every thread
+// takes the same maximum.  Without RQ: nq, krow untouched.
+template <int ROWS, bool RQ>
+__device__ __forceinline__ int rvq_stage_counts(int row0, int N, int nq, int Tf, const int* nq_rows, int* krow) {
+    if constexpr (!RQ) return nq;
+    else {
+        const int tid = threadIdx.x;
+        const int last = (row0 + ROWS <= N ? row0 + ROWS : N) - 1;
+        int nqw = 0;
+        for (int b = row0 / Tf; b <= last / Tf; ++b) {
+            const int k = nq_rows[b] < nq ? nq_rows[b] : nq;
+            nqw = k > nqw ? k : nqw;
+        }
+        if (tid < ROWS) {
+            const int n = row0 + tid;
+            krow[tid] = n < N ? (nq_rows[n / Tf] < nq ? nq_rows[n / Tf] : nq) : 0;
+        }
+        return nqw;
+    }
+}
+
+// |x|^2 of one residual row by four lanes j = 0 .. 3 (consecutive lanes): chain j over d in [j D/4, (j + 1) D/4) with the square rounded
+// separately, the chains combined (p0 + p1) + (p2 + p3); lane j = 0 writes the result
+template <int D>
+__device__ __forceinline__ void rvq_row_norm(const float* row, int j, float* xn_row) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int d = j * (D / 4); d < (j + 1) * (D / 4); ++d) {
+        const float v = row[d];
+        s = __fadd_rn(s, __fmul_rn(v, v));
+    }
+    const float s_pair = __fadd_rn(s, __shfl_xor(s, 1, 64));          // p0+p1 | p2+p3
+    const float s_all = __fadd_rn(s_pair, __shfl_xor(s_pair, 2, 64));  // (p0+p1)+(p2+p3)
+    if (j == 0) *xn_row = s_all;
+}
+
+// arg-max of a stage, FIRST max wins: every wave's (best, index) registers (row 16 s2 + 4 g + r, the wave's codes spread over the 16 lanes
+// r16) meet by a 16-lane butterfly, the 8 waves' results through LDS; thread `row` then clamps the index into range (all-NaN row: torch
+// would return an index too), leaves it in sel for the gather and stores the row's code -- 0 for a stage the row does not take (RQ; sel
+// keeps the real index).  Holds one barrier; the caller's next barrier publishes sel.  tid, wid, g, r16: the caller's thread coordinates
+// (taken as arguments: recomputed here they cost rvq_encode_kernel<128, 1> two registers).
+template <int RS, bool RQ>
+__device__ __forceinline__ void rvq_argmax_merge(float (&best)[RS][4], int (&bidx)[RS][4], float (*bestv)[16 * RS], int (*besti)[16 * RS],
+                                                 int* sel, const int* krow, int i, int K, int N, int row0, int64_t* codes, int tid, int wid,
+                                                 int g, int r16) {
+#pragma unroll
+    for (int s2 = 0; s2 < RS; ++s2) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                const float ov = __shfl_xor(best[s2][r], o, 64);
+                const int oi = __shfl_xor(bidx[s2][r], o, 64);
+                if (ov > best[s2][r] || (ov == best[s2][r] && oi < bidx[s2][r])) { best[s2][r] = ov; bidx[s2][r] = oi; }
+            }
+            if (r16 == 0) { bestv[wid][16 * s2 + 4 * g + r] = best[s2][r]; besti[wid][16 * s2 + 4 * g + r] = bidx[s2][r]; }
+        }
+    }
+    __syncthreads();
+    if (tid < 16 * RS) {
+        float bv = bestv[0][tid];
+        int bi = besti[0][tid];
+        for (int w = 1; w < 8; ++w) {
+            const float ov = bestv[w][tid];
+            const int oi = besti[w][tid];
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (bi < 0 || bi >= K) bi = 0;   // all-NaN row: torch would return an index too; stay in range
+        sel[tid] = bi;
+        if constexpr (RQ) { if (i >= krow[tid]) bi = 0; }       // a stage the row does not take: code 0 (sel stays in range for the gather)
+        if (row0 + tid < N) codes[(size_t)i * N + row0 + tid] = (int64_t)bi;
+    }
+}
+
 // RS = row sets of 16 rows per workgroup.  The stage is L2-bandwidth bound when one codebook load feeds only 16 rows
 // (every workgroup streams the whole 512 KiB stage codebook: 250 workgroups x 512 KiB = 128 MiB per stage at config B);
 // with RS = 2 the same registers feed two independent 16-row MFMA accumulators (same arithmetic per row).
@@ -1506,20 +1533,7 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, r16 = lane & 15;
     const int row0 = blockIdx.x * ROWS;
-    int nqw = nq;                                       // stages this workgroup runs
-    if constexpr (RQ) {
-        // the rows of a workgroup are consecutive frames, so their batch rows are consecutive too: every thread takes the same maximum
-        const int last = (row0 + ROWS <= N ? row0 + ROWS : N) - 1;
-        nqw = 0;
-        for (int b = row0 / Tf; b <= last / Tf; ++b) {
-            const int k = nq_rows[b] < nq ? nq_rows[b] : nq;
-            nqw = k > nqw ? k : nqw;
-        }
-        if (tid < ROWS) {
-            const int n = row0 + tid;
-            krow[tid] = n < N ? (nq_rows[n / Tf] < nq ? nq_rows[n / Tf] : nq) : 0;      // read behind the first barrier of stage 0
-        }
-    }
+    const int nqw = rvq_stage_counts<ROWS, RQ>(row0, N, nq, Tf, nq_rows, krow);      // stages this workgroup runs
 
     for (int e = tid; e < ROWS * D; e += 512) {
         const int r = e / D, d = e - r * D;
@@ -1538,18 +1552,7 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
     f32x4 b1p[DEEP ? NQ4 : 1];                                   // DEEP: the second one
     for (int i = 0; i < nqw; ++i) {
         __syncthreads();
-        if (tid < 4 * ROWS) {   // |x|^2
-            const int r = tid >> 2, j = tid & 3;
-            float s = 0.f;
-#pragma unroll 8
-            for (int d = j * (D / 4); d < (j + 1) * (D / 4); ++d) {
-                const float v = R[r][d];
-                s = __fadd_rn(s, __fmul_rn(v, v));
-            }
-            const float s_pair = __fadd_rn(s, __shfl_xor(s, 1, 64));          // p0+p1 | p2+p3
-            const float s_all = __fadd_rn(s_pair, __shfl_xor(s_pair, 2, 64));  // (p0+p1)+(p2+p3)
-            if (j == 0) xn[r] = s_all;
-        }
+        if (tid < 4 * ROWS) rvq_row_norm<D>(R[tid >> 2], tid & 3, &xn[tid >> 2]);   // |x|^2
         f32x4 a4[RS][NQ4];
 #pragma unroll
         for (int s2 = 0; s2 < RS; ++s2)
@@ -1642,33 +1645,7 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
                 if (i + 1 < nqw) load_tile(i + 1, 0, b0);
             }
         }
-#pragma unroll
-        for (int s2 = 0; s2 < RS; ++s2) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) {
-                    const float ov = __shfl_xor(best[s2][r], o, 64);
-                    const int oi = __shfl_xor(bidx[s2][r], o, 64);
-                    if (ov > best[s2][r] || (ov == best[s2][r] && oi < bidx[s2][r])) { best[s2][r] = ov; bidx[s2][r] = oi; }
-                }
-                if (r16 == 0) { bestv[wid][16 * s2 + 4 * g + r] = best[s2][r]; besti[wid][16 * s2 + 4 * g + r] = bidx[s2][r]; }
-            }
-        }
-        __syncthreads();
-        if (tid < ROWS) {
-            float bv = bestv[0][tid];
-            int bi = besti[0][tid];
-            for (int w = 1; w < 8; ++w) {
-                const float ov = bestv[w][tid];
-                const int oi = besti[w][tid];
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
-            if (bi < 0 || bi >= K) bi = 0;   // all-NaN row: torch would return an index too; stay in range
-            sel[tid] = bi;
-            if constexpr (RQ) { if (i >= krow[tid]) bi = 0; }       // a stage the row does not take: code 0 (sel stays in range for the gather)
-            if (row0 + tid < N) codes[(size_t)i * N + row0 + tid] = (int64_t)bi;
-        }
+        rvq_argmax_merge<RS, RQ>(best, bidx, bestv, besti, sel, krow, i, K, N, row0, codes, tid, wid, g, r16);
         __syncthreads();
         // gather the selected code rows: all loads first (they are independent), then the LDS / register updates
         float qv[NEL];
@@ -1696,6 +1673,8 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
             }
         }
     }
+    // The two tails; rvq_encode_wide_kernel repeats them line for line (why they are not one function: the note above
+    // rvq_stage_counts).  An edit here is an edit there.
     if constexpr (RQ) {       // the stages behind the workgroup's last one: codes and sub_quants 0
         if (tid < ROWS && row0 + tid < N)
             for (int i = nqw; i < nq; ++i) codes[(size_t)i * N + row0 + tid] = 0;
@@ -1725,10 +1704,9 @@ __global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict
     }
 }
 
-// Wide codebooks (D = 512, the SoundStream recipe): same arithmetic and the same argmax / update flow as rvq_encode_kernel,
-// but a (row, code) chain is fed in chunks of 256 dims -- the 2x fragment of the row (re-read from LDS per chunk) and the two
-// in-flight codebook fragments then fit the register file -- and the running quantised sum lives in registers instead of LDS.
-// RQ: per-batch-row stage counts, as in rvq_encode_kernel.
+// Wide codebooks (D = 512, the SoundStream recipe): the shared steps above around its own matrix loop.  A (row, code) chain is fed in
+// chunks of 256 dims -- the 2x fragment of the row (re-read from LDS per chunk) and the two in-flight codebook fragments then fit the
+// register file -- and the residual update fuses each gather with its use.  Q0, RQ: see rvq_encode_kernel.
 template <int D, bool Q0 = false, bool RQ = false>
 __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __restrict__ x, int N, int K, int nq,
                                                               const float* __restrict__ cb, const float* __restrict__ cbf,
@@ -1747,19 +1725,7 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, r16 = lane & 15;
     const int row0 = blockIdx.x * 16;
-    int nqw = nq;
-    if constexpr (RQ) {
-        const int last = (row0 + 16 <= N ? row0 + 16 : N) - 1;
-        nqw = 0;
-        for (int b = row0 / Tf; b <= last / Tf; ++b) {
-            const int k = nq_rows[b] < nq ? nq_rows[b] : nq;
-            nqw = k > nqw ? k : nqw;
-        }
-        if (tid < 16) {
-            const int n = row0 + tid;
-            krow[tid] = n < N ? (nq_rows[n / Tf] < nq ? nq_rows[n / Tf] : nq) : 0;
-        }
-    }
+    const int nqw = rvq_stage_counts<16, RQ>(row0, N, nq, Tf, nq_rows, krow);
     float qreg[NEL];                                     // running sum of the selected code rows, element e = tid + 512*i
 #pragma unroll
     for (int i2 = 0; i2 < NEL; ++i2) {
@@ -1773,23 +1739,12 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
     const int code0 = wid * codes_per_wave;
     for (int i = 0; i < nqw; ++i) {
         __syncthreads();
-        if (tid < 64) {   // |x|^2, same chains as the narrow kernel
-            const int r = tid >> 2, j = tid & 3;
-            float s = 0.f;
-#pragma unroll 8
-            for (int d = j * (D / 4); d < (j + 1) * (D / 4); ++d) {
-                const float v = R[r][d];
-                s = __fadd_rn(s, __fmul_rn(v, v));
-            }
-            const float s_pair = __fadd_rn(s, __shfl_xor(s, 1, 64));
-            const float s_all = __fadd_rn(s_pair, __shfl_xor(s_pair, 2, 64));
-            if (j == 0) xn[r] = s_all;
-        }
+        if (tid < 64) rvq_row_norm<D>(R[tid >> 2], tid & 3, &xn[tid >> 2]);   // |x|^2
         __syncthreads();
-        float best[4], xr[4];
-        int bidx[4];
+        float best[1][4], xr[4];
+        int bidx[1][4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { best[r] = -INFINITY; bidx[r] = 0x7fffffff; xr[r] = xn[4 * g + r]; }
+        for (int r = 0; r < 4; ++r) { best[0][r] = -INFINITY; bidx[0][r] = 0x7fffffff; xr[r] = xn[4 * g + r]; }
         const float* cbi = cb + (size_t)i * K * D;
         auto load_unit = [&](int u, f32x4 (&bq)[CQ]) __attribute__((always_inline)) {
             const int t = u / NC, c = u - t * NC, code = code0 + 16 * t;
@@ -1815,7 +1770,7 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float dist = -__fadd_rn(__fsub_rn(xr[r], acc[r]), en);
-                    if (dist > best[r]) { best[r] = dist; bidx[r] = code; }
+                    if (dist > best[0][r]) { best[0][r] = dist; bidx[0][r] = code; }
                 }
             }
         };
@@ -1831,30 +1786,7 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
             }
             if (u < nunit) do_unit(u, b0);
         }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const float ov = __shfl_xor(best[r], o, 64);
-                const int oi = __shfl_xor(bidx[r], o, 64);
-                if (ov > best[r] || (ov == best[r] && oi < bidx[r])) { best[r] = ov; bidx[r] = oi; }
-            }
-            if (r16 == 0) { bestv[wid][4 * g + r] = best[r]; besti[wid][4 * g + r] = bidx[r]; }
-        }
-        __syncthreads();
-        if (tid < 16) {
-            float bv = bestv[0][tid];
-            int bi = besti[0][tid];
-            for (int w = 1; w < 8; ++w) {
-                const float ov = bestv[w][tid];
-                const int oi = besti[w][tid];
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
-            if (bi < 0 || bi >= K) bi = 0;
-            sel[tid] = bi;
-            if constexpr (RQ) { if (i >= krow[tid]) bi = 0; }
-            if (row0 + tid < N) codes[(size_t)i * N + row0 + tid] = (int64_t)bi;
-        }
+        rvq_argmax_merge<1, RQ>(best, bidx, bestv, besti, sel, krow, i, K, N, row0, codes, tid, wid, g, r16);
         __syncthreads();
 #pragma unroll
         for (int i2 = 0; i2 < NEL; ++i2) {
@@ -1872,6 +1804,8 @@ __global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __res
             }
         }
     }
+    // The two tails, line for line those of rvq_encode_kernel (why they are not one function: the note above rvq_stage_counts).  An edit
+    // here is an edit there.
     if constexpr (RQ) {
         if (tid < 16 && row0 + tid < N)
             for (int i = nqw; i < nq; ++i) codes[(size_t)i * N + row0 + tid] = 0;

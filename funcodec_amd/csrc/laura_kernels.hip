@@ -5,15 +5,13 @@
 // B operand = B[k g][col r];  accumulator register v = D[row 4 g + v][col r].
 #include "laura_kernels.h"
 #include "kernels.h"
+#include "device_common.h"
 
 #include <atomic>
 #include <cstdlib>
 
 namespace fc {
 namespace laura {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 namespace {
 

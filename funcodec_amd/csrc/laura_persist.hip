@@ -31,6 +31,7 @@
 //   softmax with the flash-decoding split), same formulas as gemv_kernel / attn_step_kernel; the split of K and of the key ranges differs,
 //   so results agree with the chain to fp32 rounding, not bit for bit.
 #include "laura_kernels.h"
+#include "device_common.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -38,8 +39,6 @@
 namespace fc {
 namespace laura {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 // Pointers that reach the kernel through a table in memory (StepLayer) are generic to the compiler: it would emit flat_load (LDS
 // aperture check, counted in lgkmcnt as well).  Everything here lives in global memory: say so.
 typedef const __attribute__((address_space(1))) float* gfp;

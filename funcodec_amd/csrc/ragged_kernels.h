@@ -29,9 +29,6 @@ __host__ __device__ inline int ragged_extra(int n, int k, int pt, int stride) {
 // lens[b] = clamp(in[b], 1, Tmax); a length outside that range raises FC_STATUS_BAD_LENGTH
 hipError_t launch_ragged_lengths(const int32_t* in, int B, int Tmax, int* lens, unsigned* status, hipStream_t st);
 
-// scale[b] = 1e-8 + rms over the row's own len samples of the channel mean (codec_basic.py:366-371); wav [B][C][T]
-hipError_t launch_ragged_volume(const float* wav, int B, int C, int T, const int* lens, float* scale, hipStream_t st);
-
 // The staging pass in front of a conv of a ragged pass, sibling of stream_stage_kernel: applies the consumer's prologue
 // act(aff0(s0 / div) + aff1(s1)) and writes, per row, [left padding | the row's n columns | right padding incl. the row's own extra_padding
 // | zeros] into buf [B][C][Tp]: reflection, or the zero-extended reflection of pad1d for rows not longer than the padding (conv.py:82-99),

@@ -2,19 +2,11 @@
 // All of them are LDS-free streaming kernels (the reductions keep a few doubles in LDS), vector stores only, no atomics: every element
 // has exactly one writer, and every summation order depends on the row's own length alone, never on the batch around it.
 #include "ragged_kernels.h"
+#include "device_common.h"
 
 namespace fc {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // 16-byte accesses at dword alignment (rows start at any column)
-
-// ELU exactly as the conv kernels' fused prologue computes it (conv_kernel.h elu_f)
-__device__ __forceinline__ float ragged_elu(float v, float alpha) {
-    const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f);
-    return v > 0.f ? v : fmaf(e, alpha, -alpha);
-}
 
 __global__ __launch_bounds__(256) void ragged_lengths_kernel(const int32_t* __restrict__ in, int B, int Tmax, int* __restrict__ lens,
                                                              unsigned* status) {
@@ -24,33 +16,6 @@ __global__ __launch_bounds__(256) void ragged_lengths_kernel(const int32_t* __re
     const int c = v < 1 ? 1 : (v > Tmax ? Tmax : v);
     lens[b] = c;
     if (c != v && status) status[FC_STATUS_BAD_LENGTH] = 1u;
-}
-
-template <int C>
-__global__ __launch_bounds__(1024) void ragged_volume_kernel(const float* __restrict__ wav, int T, const int* __restrict__ lens,
-                                                             float* __restrict__ scale) {
-    __shared__ double sh[1024];
-    const int b = blockIdx.x, tid = threadIdx.x, n = lens[b];
-    const float* x = wav + (size_t)b * C * T;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    const int n4 = n >> 2;
-    for (int q = tid; q < n4; q += 1024) {
-        f32x4 v = *(const f32x4u*)(x + 4 * q);
-        if (C == 2) v = (v + (f32x4)(*(const f32x4u*)(x + T + 4 * q))) * 0.5f;
-        s0 += (double)(v[0] * v[0]); s1 += (double)(v[1] * v[1]); s2 += (double)(v[2] * v[2]); s3 += (double)(v[3] * v[3]);
-    }
-    for (int t = 4 * n4 + tid; t < n; t += 1024) {
-        float v = x[t];
-        if (C == 2) v = (v + x[T + t]) * 0.5f;
-        s0 += (double)(v * v);
-    }
-    sh[tid] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    for (int o = 512; o >= 1; o >>= 1) {
-        if (tid < o) sh[tid] += sh[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) scale[b] = 1e-8f + sqrtf((float)(sh[0] / (double)n));
 }
 
 struct StageArgs {
@@ -90,7 +55,7 @@ __global__ __launch_bounds__(256) void ragged_stage_kernel(const StageArgs p) {
         if (p.a0) v = fmaf(v, A0.x, A0.y);
         if (p.div) v = v / dv;
         if (x1) v = v + (p.a1 ? fmaf(w, A1.x, A1.y) : w);
-        if (p.elu) v = ragged_elu(v, p.alpha);
+        if (p.elu) v = elu_f(v, p.alpha);
         return v;
     };
     auto col = [&](int q) __attribute__((always_inline)) {      // staged column q
@@ -199,13 +164,6 @@ hipError_t launch_mask(T* p, int O, int B, int M, int Tn, int Dn, const RagLen& 
 hipError_t launch_ragged_lengths(const int32_t* in, int B, int Tmax, int* lens, unsigned* status, hipStream_t st) {
     if (B <= 0 || Tmax <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ragged_lengths_kernel, dim3((B + 255) / 256), dim3(256), 0, st, in, B, Tmax, lens, status);
-    return hipGetLastError();
-}
-
-hipError_t launch_ragged_volume(const float* wav, int B, int C, int T, const int* lens, float* scale, hipStream_t st) {
-    if (C == 1) hipLaunchKernelGGL(ragged_volume_kernel<1>, dim3(B), dim3(1024), 0, st, wav, T, lens, scale);
-    else if (C == 2) hipLaunchKernelGGL(ragged_volume_kernel<2>, dim3(B), dim3(1024), 0, st, wav, T, lens, scale);
-    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -15,13 +15,11 @@
 // Masking (causal, tail keys past T): a masked entry gets probability exactly 0 and is left out of the running maximum, so it adds
 // exactly nothing (0 * v) and a query's result does not depend on keys it cannot see.  Key tiles wholly above the diagonal are skipped.
 #include "seq_kernels.h"
+#include "device_common.h"
 
 namespace fc {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 template <int DK>
 __global__ __launch_bounds__(256) void seq_attn_kernel(const float* __restrict__ qkv, float* __restrict__ out, int H, int T, int causal,

@@ -2,19 +2,11 @@
 // independently, and the per-row start of an utterance.  See slots_kernels.h for the contract.
 // LDS-free streaming kernels, vector stores only, no atomics: every element has exactly one writer.
 #include "slots_kernels.h"
+#include "device_common.h"
 
 namespace fc {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // 16-byte accesses at dword alignment (rows start at any column)
-
-// ELU exactly as the conv kernels' fused prologue computes it (conv_kernel.h elu_f): a layer sees the same activation in every kind of pass
-__device__ __forceinline__ float slots_elu(float v, float alpha) {
-    const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f);
-    return v > 0.f ? v : fmaf(e, alpha, -alpha);
-}
 
 struct StageArgs {
     const float *s0, *s1, *div, *carry_in;
@@ -48,7 +40,7 @@ __global__ __launch_bounds__(256) void slots_stage_kernel(const StageArgs p) {
     auto act = [&](float v, float w) __attribute__((always_inline)) {
         if (p.div) v = v / dv;
         if (x1) v = v + w;
-        if (p.elu) v = slots_elu(v, p.alpha);
+        if (p.elu) v = elu_f(v, p.alpha);
         return v;
     };
     auto chunk_at = [&](int t) __attribute__((always_inline)) { return act(x0[t], x1 ? x1[t] : 0.f); };

@@ -1,18 +1,10 @@
 // Streaming session (fc_stream_*): the staging pass in front of every causal conv of a push.  See stream_kernels.h for the contract.
 #include "stream_kernels.h"
+#include "device_common.h"
 
 namespace fc {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // 16-byte accesses at dword alignment (rows start at any column)
-
-// ELU exactly as the conv kernels' fused prologue computes it (conv_kernel.h elu_f): a layer sees the same activation streamed or not
-__device__ __forceinline__ float stream_elu(float v, float alpha) {
-    const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f);
-    return v > 0.f ? v : fmaf(e, alpha, -alpha);
-}
 
 struct StageArgs {
     const float *s0, *s1, *div, *carry_in;
@@ -39,7 +31,7 @@ __global__ __launch_bounds__(256) void stream_stage_kernel(const StageArgs p) {
     auto act = [&](float v, float w) __attribute__((always_inline)) {
         if (p.div) v = v / dv;
         if (x1) v = v + w;
-        if (p.elu) v = stream_elu(v, p.alpha);
+        if (p.elu) v = elu_f(v, p.alpha);
         return v;
     };
     auto chunk_at = [&](int t) __attribute__((always_inline)) { return act(x0[t], x1 ? x1[t] : 0.f); };

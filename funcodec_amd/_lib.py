@@ -117,6 +117,10 @@ SYMBOLS = {
     "fc_stream_decode_codes": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_stream_decode_emb": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_stream_lstm_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    # a streaming session of a causal transformer net: an fc_stream with a key / value cache of max_frames frames per side
+    "fc_seqstream_state_bytes": (C.c_size_t, [_P, C.c_int, C.c_int]),
+    "fc_seqstream_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    "fc_seqstream_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     # slot session: S slots that start, push and end independently in one batch (counts and flags: host int32 [S])
     "fc_slots_state_bytes": (C.c_size_t, [_P, C.c_int]),
     "fc_slots_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),

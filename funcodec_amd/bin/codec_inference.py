@@ -118,10 +118,11 @@ class Speech2Token:
                        sub_quants=None if ret["sub_quants"] is None else [cast(x) for x in ret["sub_quants"]])
         return (ret["code_indices"], ret["code_embeddings"], ret["recon_speech"], ret["sub_quants"])
 
-    def open_stream(self, batch: int = 1, n_q: Optional[int] = None, scale=None, max_chunk: Optional[int] = None):
+    def open_stream(self, batch: int = 1, n_q: Optional[int] = None, scale=None, max_chunk: Optional[int] = None,
+                    max_frames: Optional[int] = None):
         """A streaming session of the loaded (causal) model: funcodec_amd.stream.CodecStream.  Not in the reference, whose
         `streaming=` keyword selects a data iterator; that keyword keeps its meaning here (accepted, unused)."""
-        return self.model.open_stream(batch, n_q=n_q, scale=scale, max_chunk=max_chunk)
+        return self.model.open_stream(batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames)
 
     def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
         """A slot session of the loaded (causal) model: funcodec_amd.stream.StreamSlots, independent utterances sharing every push."""

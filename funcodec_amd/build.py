@@ -23,7 +23,7 @@ def sources():
     tiles = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "conv_tile*_*.hip")))
     heavy = [t for t in tiles if t.startswith("conv_tileq_") and "_m" not in t] + [t for t in tiles if t.endswith("_m01.hip")]
     rest = [t for t in tiles if t not in heavy]
-    return heavy + ["kernels.hip", "laura_persist.hip", "laura_kernels.hip", "freq_kernels.hip", "seq_kernels.hip", "stream_kernels.hip", "ragged_kernels.hip", "slots_kernels.hip", "engine.hip", "laura.hip"] + rest
+    return heavy + ["kernels.hip", "laura_persist.hip", "laura_kernels.hip", "freq_kernels.hip", "seq_kernels.hip", "seqstream_kernels.hip", "stream_kernels.hip", "ragged_kernels.hip", "slots_kernels.hip", "engine.hip", "laura.hip"] + rest
 
 
 def _hipcc() -> str:

@@ -181,7 +181,9 @@ struct fc_engine {
 
 // What both kinds of session of a causal time-domain engine keep.  Everything that survives a push lives in `state`, ONE device allocation
 // of the caller (fc_stream_state_bytes; stream_layout): [scale B] [per conv with a left context: carry [2][B][cin][pt], ping-pong on the
-// parity of the side's push count] [encoder LSTM h [L][2][B][H] | c [L][B][H]] [decoder LSTM the same].
+// parity of the side's push count] [encoder LSTM h [L][2][B][H] | c [L][B][H]] [decoder LSTM the same], and behind them, in a session
+// opened with max_frames for a transformer bottleneck (fc_seqstream_create), the key / value caches: per side, per block, K [B][C][F]
+// then V [B][C][F], F = seq_cache_pitch(max_frames).
 struct Session {
     fc_engine* e = nullptr;
     int B = 0, max_chunk = 0, n_q = 0;              // B: the rows of a push (utterances in lock-step / slots)
@@ -189,6 +191,9 @@ struct Session {
     size_t state_floats = 0;
     std::map<const ConvLayer*, size_t> carry;       // float offset of the layer's carry pair inside state
     size_t enc_lstm_off = 0, dec_lstm_off = 0;
+    int max_frames = 0;                             // the bound of an utterance's frames per side; 0: no transformer in this session
+    size_t enc_kv_off = 0, dec_kv_off = 0;          // float offsets of the two sides' key / value caches; carried_floats: what lies in front
+    size_t carried_floats = 0;                      // of them and is cleared at reset (the caches are written before they are read)
     int enc_min_first = 0, dec_min_first = 0;       // shortest first push: samples (a hop multiple) / frames
     std::vector<float> ones;
 };
@@ -196,6 +201,7 @@ struct Session {
 // One streaming session (fc_stream_*): B utterances in lock-step.  The host side keeps only push counters.
 struct fc_stream : Session {
     int enc_pushes = 0, dec_pushes = 0;
+    int enc_frames = 0, dec_frames = 0;             // frames each side's transformer has taken since reset (the `pos` of its next push)
     bool enc_done = false;                          // the final push has been taken
     bool broken = false;                            // a push failed half-way: carries are a mix of old and new until the next reset
 };
@@ -1269,7 +1275,11 @@ Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, f
 //   x += linear_out(MHA(norm1(x)));  x += w_2(relu(w_1(norm2(x))))
 // Each residual add is fused into the LayerNorm that follows it (laura_kernels.hip layernorm_fm_kernel); LayerNorm eps 1e-12
 // (layer_norm.py:21-23).  The input may carry a pending GroupNorm affine: it is materialised once.
-Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int T) {
+// `kv` (a streaming push; null offline): the side's key / value cache inside the session state and the frames it holds.  The T frames
+// of the push run through the same launches; K and V of every block are appended at [pos, pos + T) (seq_cache_append_kernel) and the
+// attention reads them from there (seq_attn_cached_kernel: query i sees keys 0 .. pos + i).
+struct TfCache { float* base = nullptr; int pos = 0, F = 0; };
+Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int T, const TfCache* kv = nullptr) {
     const int C = tb.C, B = cx.B, ff = tb.ff, DK = C / tb.heads;
     const long long sC = (long long)C * T;
     float* x = cx.alloc<float>((size_t)B * C * T);        // residual stream
@@ -1281,7 +1291,10 @@ Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int
     Act y;
     y.C = C; y.T = T;
     y.raw = cx.alloc<float>((size_t)B * C * T);
-    const double pairs = tb.layers.empty() ? 0.0 : (e->arch.causal ? 0.5 * (double)T * (T + 1) : (double)T * T);
+    float* part = kv ? cx.alloc<float>(fc::seq_attn_cached_part_floats(B, tb.heads, DK)) : nullptr;     // of every push: no size depends on pos
+    const double pairs = tb.layers.empty() ? 0.0
+                         : kv ? (double)T * kv->pos + 0.5 * (double)T * (T + 1)
+                              : (e->arch.causal ? 0.5 * (double)T * (T + 1) : (double)T * T);
     const double attn_fl = 4.0 * B * pairs * C;           // q k^T and p v, every visible (query, key) pair
     cx.attn_flops += attn_fl * tb.layers.size();
     const char* pre = tb.prefix.c_str();
@@ -1294,13 +1307,28 @@ Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int
     fc::Src sctx; sctx.ptr = ctx; sctx.used = 1;
     fc::Src shb; shb.ptr = hb; shb.used = 1;
     const float* pending = nullptr;
+    size_t block = 0;
     for (const TfLayer& L : tb.layers) {
         ln(pending, L.n1g, L.n1b, xn);
         run_conv(e, cx, L.qkv, sxn, fc::Src(), 0, T, qkv, 3 * sC, T, 1);
-        fc::SeqAttn a;
-        a.qkv = qkv; a.out = ctx; a.B = B; a.H = tb.heads; a.DK = DK; a.T = T; a.causal = e->arch.causal ? 1 : 0;
-        cx.launch("transformer attention", pre, [&] { return fc::seq_attn_kernel_name(DK); }, attn_fl, 4.0 * B * 4.0 * C * T,
-                  [&] { return fc::launch_seq_attn(a, cx.st); });
+        if (kv) {
+            const size_t plane = (size_t)B * C * kv->F;
+            float* kc = kv->base ? kv->base + 2 * plane * block : nullptr;
+            fc::SeqCacheAppend ap;
+            ap.qkv = qkv; ap.kc = kc; ap.vc = kc ? kc + plane : nullptr; ap.B = B; ap.C = C; ap.n = T; ap.pos = kv->pos; ap.F = kv->F;
+            cx.launch("transformer cache append", pre, [] { return "seq_cache_append_kernel (streaming: K and V of a push into the cache)"; }, 0.0,
+                      4.0 * B * 4.0 * C * T, [&] { return fc::launch_seq_cache_append(ap, cx.st); });
+            fc::SeqAttnCached a;
+            a.qkv = qkv; a.kc = ap.kc; a.vc = ap.vc; a.out = ctx; a.part = part; a.B = B; a.H = tb.heads; a.DK = DK; a.n = T; a.pos = kv->pos; a.F = kv->F;
+            cx.launch("transformer cached attention", pre, [&] { return fc::seq_attn_cached_kernel_name(DK); }, attn_fl,
+                      4.0 * B * C * (2.0 * T + 2.0 * (kv->pos + T)), [&] { return fc::launch_seq_attn_cached(a, cx.st); });
+        } else {
+            fc::SeqAttn a;
+            a.qkv = qkv; a.out = ctx; a.B = B; a.H = tb.heads; a.DK = DK; a.T = T; a.causal = e->arch.causal ? 1 : 0;
+            cx.launch("transformer attention", pre, [&] { return fc::seq_attn_kernel_name(DK); }, attn_fl, 4.0 * B * 4.0 * C * T,
+                      [&] { return fc::launch_seq_attn(a, cx.st); });
+        }
+        ++block;
         run_conv(e, cx, L.out, sctx, fc::Src(), 0, T, dl, sC, T, 1);
         ln(dl, L.n2g, L.n2b, xn);
         run_conv(e, cx, L.ff1, sxn, fc::Src(), 0, T, hb, (long long)ff * T, T, 1);
@@ -1386,6 +1414,7 @@ Act ragged_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Sr
 Act stream_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc);
 Act slots_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T);
 float* lstm_state(const Session& s, bool dec);
+TfCache tf_cache(const Session& s, bool dec);
 
 // the conv step.  A push stages the layers that carry a left context and runs them over [carry | chunk] (stream_conv; slots_conv with
 // every row at its own place); its pointwise layers run as offline.  A ragged pass stages every conv that looks beyond its own column
@@ -1402,7 +1431,8 @@ Act walk_conv(fc_engine* e, Ctx& cx, const Pass& p, Role role, const ConvLayer& 
 }
 
 // the bottleneck of one side: the sources of the conv behind it = the sequence model's output (plus its input with lstm_skip), or x itself
-// in a net without one.  A push continues the per-step LSTM on the session's state (stream_refusal: no transformer in a session).
+// in a net without one.  A push continues the per-step LSTM on the session's state, or the transformer on the session's key / value
+// cache (a session opened with max_frames; the slot pass has no transformer: stream_refusal).
 void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x, fc::Src* a0, fc::Src* a1) {
     const LstmBlock& lb = dec ? e->dec_lstm : e->enc_lstm;
     const TfBlock& tb = dec ? e->dec_tf : e->enc_tf;
@@ -1410,7 +1440,15 @@ void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x
     if (!has_seq(lb, tb)) return;
     Act y;
     switch (p.kind) {
-        case Pass::Stream: y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec)); break;
+        case Pass::Stream:
+            if (tb.C) {
+                const TfCache kv = tf_cache(*p.sess, dec);
+                if (!cx.dry && kv.pos + x.T > p.sess->max_frames) { cx.fail("internal: a push past max_frames reached the transformer"); return; }
+                y = run_transformer(e, cx, tb, x, x.T, &kv);
+            } else {
+                y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec));
+            }
+            break;
         case Pass::Slots: {                               // every row takes its own frames of the LSTM's steps
             const fc::RagLen steps = ragged_len(cx, p);
             y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec), &steps);
@@ -1951,12 +1989,15 @@ int check_ready(fc_engine* e) {
 inline int stream_pt(const ConvLayer& L) { return L.transposed ? 1 : (L.k - 1) * L.dil - (L.stride - 1); }
 
 // why this engine cannot stream, or null.  Each reason names the configuration key.
-const char* stream_refusal(const fc_engine* e) {
+const char* stream_refusal(const fc_engine* e, int max_frames = 0) {
     const fc_arch& a = e->arch;
     if (a.model_type != 0) return "streaming is not available for model: freq_codec (the STFT frames overlap; time-domain codec only)";
     if (!a.causal) return "streaming needs encoder_conf.causal / decoder_conf.causal: true (a non-causal net looks ahead at every layer)";
-    if (a.lstm_layers > 0 && a.seq_model == 1) return "streaming is not available for seq_model: transformer (it needs a key / value cache across pushes)";
+    if (a.lstm_layers > 0 && a.seq_model == 1 && max_frames <= 0)
+        return "streaming is not available for seq_model: transformer (it needs a key / value cache across pushes: fc_seqstream_create takes its bound, max_frames)";
     if (a.q0_ds_ratio > 1) return "streaming is not available for quantizer_conf.q0_ds_ratio > 1 (the half-rate first stage looks across frame pairs)";
+    if (max_frames > 0 && !(a.lstm_layers > 0 && a.seq_model == 1))
+        return "max_frames bounds the key / value cache of seq_model: transformer; this net has no transformer bottleneck (fc_stream_create opens its session)";
     return nullptr;
 }
 
@@ -1977,6 +2018,13 @@ void stream_layout(fc_engine* e, int B, Session* S) {
     const size_t L = (size_t)e->arch.lstm_layers;
     S->enc_lstm_off = off; off += 3 * L * B * e->enc_lstm.H;
     S->dec_lstm_off = off; off += 3 * L * B * e->dec_lstm.H;
+    S->carried_floats = off;
+    if (S->max_frames > 0) {                          // the key / value caches: per block K then V, [B][C][F] each
+        const size_t F = (size_t)fc::seq_cache_pitch(S->max_frames);
+        off = (off + 63) & ~(size_t)63;
+        S->enc_kv_off = off; off += e->enc_tf.layers.size() * 2 * B * e->enc_tf.C * F;
+        S->dec_kv_off = off; off += e->dec_tf.layers.size() * 2 * B * e->dec_tf.C * F;
+    }
     S->state_floats = off;
     S->enc_min_first = ceil_div_i(enc_min, hop) * hop;
     S->dec_min_first = dec_min;
@@ -1997,6 +2045,17 @@ CarryPair carry_pair(const Session& s, const ConvLayer& L, int n) {
 
 // the session's LSTM state of one side (run_lstm's `carried`)
 float* lstm_state(const Session& s, bool dec) { return s.state + (dec ? s.dec_lstm_off : s.enc_lstm_off); }
+
+// the session's key / value cache of one side and the frames it holds (run_transformer's `kv`).  Only an fc_stream has one
+// (stream_refusal), and the sizing pass (no state yet) runs at pos 0: no size of a push depends on pos.
+TfCache tf_cache(const Session& s, bool dec) {
+    const fc_stream& st = static_cast<const fc_stream&>(s);
+    TfCache c;
+    c.base = s.state ? s.state + (dec ? s.dec_kv_off : s.enc_kv_off) : nullptr;
+    c.pos = dec ? st.dec_frames : st.enc_frames;
+    c.F = fc::seq_cache_pitch(s.max_frames);
+    return c;
+}
 
 // The GEMM behind every staging pass (stream_conv, slots_conv, ragged_conv): the layer's own kernel as a conv without padding over the
 // staged buf [B][cin][Tp], which holds T new columns per row behind the left context.  A transposed layer computes `groups` tap pairs
@@ -2197,13 +2256,23 @@ int stream_ready(fc_stream* S) {
     return check_ready(S->e);
 }
 
+// the bound of a session with a key / value cache: a push that would take a side past max_frames is refused before its first launch
+int frames_fit(const fc_stream* S, bool dec, int frames) {
+    const int have = dec ? S->dec_frames : S->enc_frames;
+    if (S->max_frames > 0 && have + frames > S->max_frames)
+        return fail(std::string(dec ? "streaming decode" : "streaming encode") + ": this push of " + std::to_string(frames) + " frames would take the utterance to " +
+                    std::to_string(have + frames) + " frames, past the session's max_frames = " + std::to_string(S->max_frames) +
+                    " (the size of its key / value cache); nothing was changed, fc_stream_reset starts the next utterance");
+    return 0;
+}
+
 int stream_decode_check(fc_stream* S, int Tfc) {
     if (S->dec_pushes < 0) return fail("streaming decode: fc_stream_reset first");
     if (Tfc <= 0 || Tfc > ceil_div_i(S->max_chunk, total_hop(S->e))) return fail("streaming decode: a push holds 1 .. max_chunk_samples / hop frames");
     if (S->dec_pushes == 0 && Tfc < S->dec_min_first)
         return fail("streaming decode: the first push of an utterance must hold at least " + std::to_string(S->dec_min_first) +
                     " frames (the offline call's reflected left padding spans them); shorter utterances go through the offline call");
-    return 0;
+    return frames_fit(S, true, Tfc);
 }
 
 // a decode push from its decoder input z on: enqueued whole, or the session is broken
@@ -2213,6 +2282,7 @@ int stream_decode_push(fc_stream* S, Ctx& cx, const float* z, int Tfc, int use_s
     if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
     S->broken = false;
     S->dec_pushes++;
+    S->dec_frames += Tfc;
     return 0;
 }
 
@@ -3153,6 +3223,15 @@ size_t fc_stream_state_bytes(const fc_engine* ce, int B) {
     return tmp.state_floats * sizeof(float);
 }
 
+size_t fc_seqstream_state_bytes(const fc_engine* ce, int B, int max_frames) {
+    fc_engine* e = const_cast<fc_engine*>(ce);
+    if (!e || B <= 0 || max_frames <= 0 || stream_refusal(e, max_frames)) return 0;
+    Session tmp;
+    tmp.max_frames = max_frames;
+    stream_layout(e, B, &tmp);
+    return tmp.state_floats * sizeof(float);
+}
+
 }  // extern "C"
 
 namespace {
@@ -3160,14 +3239,17 @@ namespace {
 // What fc_stream_create and fc_slots_create share: the argument checks and the layout of the caller's state.  rows_error: why the row
 // count is refused, or null; `first`: what the kind calls the first push of an utterance; state_rule: its wording of the state rule.
 int session_create(Session* s, fc_engine* e, const void* out, int rows, const char* rows_error, int max_chunk_samples, int n_q, void* state,
-                   size_t state_bytes, const char* first, const char* state_rule) {
+                   size_t state_bytes, const char* first, const char* state_rule, int max_frames = 0) {
     if (!e || !out) return fail("null argument");
     if (!e->finalized) return fail("engine not finalized");
-    if (const char* why = stream_refusal(e)) return fail(why);
+    if (const char* why = stream_refusal(e, max_frames)) return fail(why);
     if (rows_error) return fail(rows_error);
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    s->e = e; s->B = rows; s->n_q = n_q; s->max_chunk = max_chunk_samples;
+    s->e = e; s->B = rows; s->n_q = n_q; s->max_chunk = max_chunk_samples; s->max_frames = max_frames;
     stream_layout(e, rows, s);
+    if (max_frames > 0 && max_frames < std::max(s->enc_min_first / total_hop(e), s->dec_min_first))
+        return fail("max_frames must hold the first push of an utterance: at least " + std::to_string(std::max(s->enc_min_first / total_hop(e), s->dec_min_first)) +
+                    " frames for this net");
     const int need = std::max(s->enc_min_first, s->dec_min_first * total_hop(e));
     if (max_chunk_samples < need)
         return fail(std::string("max_chunk_samples must hold the ") + first + " push of an utterance: at least " + std::to_string(need) + " samples for this net");
@@ -3206,6 +3288,17 @@ int fc_stream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, void* 
     return 0;
 }
 
+int fc_seqstream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, int max_frames, void* state, size_t state_bytes, fc_stream** out) {
+    if (max_frames <= 0) return fail("max_frames must be positive: the most frames an utterance of this session may hold per side");
+    std::unique_ptr<fc_stream> S(new fc_stream);
+    if (session_create(S.get(), e, out, B, B <= 0 ? "bad batch size" : nullptr, max_chunk_samples, n_q, state, state_bytes, "first",
+                       "stream state: a 16-byte aligned device buffer of fc_seqstream_state_bytes() bytes", max_frames))
+        return 1;
+    S->enc_done = true; S->enc_pushes = -1; S->dec_pushes = -1;     // unusable until the first fc_stream_reset
+    *out = S.release();
+    return 0;
+}
+
 void fc_stream_destroy(fc_stream* s) { delete s; }
 
 int fc_stream_min_first(const fc_stream* s, int decode) { return s ? (decode ? s->dec_min_first : s->enc_min_first) : 0; }
@@ -3226,10 +3319,10 @@ int fc_stream_reset(fc_stream* S, const float* scale, void* stream) {
     if (!S) return fail("null stream");
     if (check_ready(S->e)) return 1;                  // a session broken by a failed push is what reset repairs
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(fc::launch_zero_fill(S->state, S->state_floats, st));
+    HIP_TRY(fc::launch_zero_fill(S->state, S->carried_floats, st));      // not the key / value caches: they are written before they are read
     if (scale) HIP_TRY(hipMemcpyAsync(S->state, scale, (size_t)S->B * sizeof(float), hipMemcpyDeviceToDevice, st));
     else HIP_TRY(hipMemcpyAsync(S->state, S->ones.data(), (size_t)S->B * sizeof(float), hipMemcpyHostToDevice, st));
-    S->enc_pushes = 0; S->dec_pushes = 0; S->enc_done = false; S->broken = false;
+    S->enc_pushes = 0; S->dec_pushes = 0; S->enc_frames = 0; S->dec_frames = 0; S->enc_done = false; S->broken = false;
     return 0;
 }
 
@@ -3248,13 +3341,16 @@ int fc_stream_encode(fc_stream* S, const float* wav, int Tc, int final, int64_t*
     if (S->enc_pushes == 0 && Tc < S->enc_min_first)
         return fail("streaming encode: the first push of an utterance must hold at least " + std::to_string(S->enc_min_first) +
                     " samples (the offline call's reflected left padding spans them); shorter utterances go through the offline call");
+    const int Tfc = final ? frames_for(e, Tc) : Tc / hop;
+    if (frames_fit(S, false, Tfc)) return 1;
     if (row_nq_check(e, S->B, S->n_q)) return 1;
     Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
     S->broken = true;                                   // until the whole push is enqueued: a failure in between leaves mixed carries
     if (stream_encode_pass(S, cx, S->enc_pushes, wav, Tc, final != 0, codes, quantized, enc_out)) return 1;
     S->broken = false;
-    *n_frames = final ? frames_for(e, Tc) : Tc / hop;
+    *n_frames = Tfc;
     S->enc_pushes++;
+    S->enc_frames += Tfc;
     if (final) S->enc_done = true;
     return 0;
 }
@@ -3289,6 +3385,27 @@ int fc_stream_lstm_forward(fc_stream* S, int decoder, const float* x, int T, flo
     S->broken = true;
     if (lstm_hook_run(*S, cx, *lb, decoder, x, T, nullptr, y)) return 1;
     S->broken = false;
+    return 0;
+}
+
+// Test hook: the transformer stage of a push alone (TransformerEncoder.forward without the res_seq skip) on the session's key / value
+// cache of one side; it advances that side's frame count as a push does.  x, y dev f32 [B][C][T].
+int fc_seqstream_forward(fc_stream* S, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    if (stream_ready(S)) return 1;
+    if (!x || !y || T <= 0) return fail("bad argument");
+    const TfBlock& tb = decoder ? S->e->dec_tf : S->e->enc_tf;
+    if (!tb.C || S->max_frames <= 0) return fail("this session has no transformer bottleneck (fc_seqstream_create opens one)");
+    if (S->enc_pushes < 0) return fail("streaming: fc_stream_reset first");
+    if (frames_fit(S, decoder != 0, T)) return 1;
+    Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
+    const TfCache kv = tf_cache(*S, decoder != 0);
+    Act in; in.raw = const_cast<float*>(x); in.C = tb.C; in.T = T;
+    S->broken = true;
+    Act out = run_transformer(S->e, cx, tb, in, T, &kv);
+    cx.launch("copy", "y", [&] { return hipMemcpyAsync(y, out.raw, (size_t)S->B * tb.C * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st); });
+    if (cx.err) return 1;
+    S->broken = false;
+    (decoder ? S->dec_frames : S->enc_frames) += T;
     return 0;
 }
 

@@ -19,4 +19,41 @@ bool seq_attn_supported(int DK);
 hipError_t launch_seq_attn(const SeqAttn& a, hipStream_t st);
 const char* seq_attn_kernel_name(int DK);
 
+// ---- the attention of a streaming push (seqstream_kernels.hip): few queries against the session's key / value cache ----
+// The cache of one block is channel-major like the operands above, [B][C][F] for K and the same for V, with the frame pitch F a
+// multiple of 16 (seq_cache_pitch): the fragment loads are those of seq_attn_kernel, a push appends n contiguous floats per channel,
+// and a 16-key vector load of V is aligned and never leaves a row.
+struct SeqAttnCached {
+    const float* qkv = nullptr;     // the chunk's [B][3 C][n]; only its q rows are read
+    const float* kc = nullptr;      // [B][C][F]: frames [0, pos + n) hold the utterance's keys, this push's included (SeqCacheAppend)
+    const float* vc = nullptr;      // [B][C][F]: the values
+    float* out = nullptr;           // [B][C][n]; query i sees keys 0 .. pos + i
+    float* part = nullptr;          // seq_attn_cached_part_floats() floats of scratch: the partial (m, l, O) of the key split
+    int B = 0, H = 0, DK = 0, n = 0, pos = 0, F = 0;
+};
+// The thresholds between the forms.  A push of at most kSeqCachedSplitMaxQueries frames is one 16-query tile per (row, head): its keys
+// are split over `units` waves, kSeqCachedTilesPerUnit 16-key tiles each until kSeqCachedMaxUnits waves are reached, and the partials
+// are merged in unit order by a second launch.  A longer push runs one wave per 16 queries over the whole cache (units = 1, no merge).
+constexpr int kSeqCachedSplitMaxQueries = 16;
+constexpr int kSeqCachedTilesPerUnit = 2;
+constexpr int kSeqCachedMaxUnits = 16;
+inline int seq_cache_pitch(int max_frames) { return (max_frames + 15) & ~15; }
+inline int seq_attn_cached_units(int n, int pos) {
+    if (n > kSeqCachedSplitMaxQueries) return 1;
+    const int tiles = (pos + n + 15) / 16, u = (tiles + kSeqCachedTilesPerUnit - 1) / kSeqCachedTilesPerUnit;
+    return u < 1 ? 1 : (u > kSeqCachedMaxUnits ? kSeqCachedMaxUnits : u);
+}
+inline size_t seq_attn_cached_part_floats(int B, int H, int DK) { return (size_t)B * H * kSeqCachedMaxUnits * (DK + 2) * 16; }
+hipError_t launch_seq_attn_cached(const SeqAttnCached& a, hipStream_t st);
+const char* seq_attn_cached_kernel_name(int DK);
+
+// K and V of a push into the cache: rows [C, 3 C) of the chunk's qkv [B][3 C][n] to frames [pos, pos + n) of kc / vc [B][C][F]
+struct SeqCacheAppend {
+    const float* qkv = nullptr;
+    float* kc = nullptr;
+    float* vc = nullptr;
+    int B = 0, C = 0, n = 0, pos = 0, F = 0;
+};
+hipError_t launch_seq_cache_append(const SeqCacheAppend& a, hipStream_t st);
+
 }  // namespace fc

@@ -657,3 +657,19 @@ class CodecEngine:
         ws = self._scratch(need)
         self._check(self.lib.fc_seq_forward(self._h, prefix.encode(), _ptr(x), B, T, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y
+
+    @_on_device
+    def stream_seq_forward(self, session, x: torch.Tensor, decoder: bool = False) -> torch.Tensor:
+        """Test hook (fc_seqstream_forward): the transformer stage of a push alone, without the res_seq skip, on the key / value cache
+        of the encoder / decoder side of `session` (a CodecStream opened with max_frames): x [B,C,T] -> [B,C,T].  It advances that
+        side's frame count, so consecutive calls continue one utterance."""
+        x = self._dev(x, torch.float32)
+        B, Cc, T = x.shape
+        if B != session.batch or Cc != self.arch.bottleneck_channels:
+            raise EngineError(f"stream_seq_forward: x must be [{session.batch},{self.arch.bottleneck_channels},T], got {tuple(x.shape)}")
+        y = torch.empty_like(x)
+        # fc_seq_forward's buffers for the chunk, and the partials of the cached attention's key split: 16 units x 16 queries x (DK + 2) per head
+        need = 4 * B * T * (8 * Cc + SEQ_FF) + 4 * B * 256 * (Cc + 2 * SEQ_HEADS) + (1 << 20)
+        ws = self._scratch(need)
+        self._check(self.lib.fc_seqstream_forward(session._h, int(decoder), _ptr(x), T, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
+        return y

@@ -43,12 +43,15 @@ class EncodecMI355X:
     def load_state_dict(self, state, strict: bool = False):
         self.engine.load_state_dict(state)
 
-    def open_stream(self, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None, max_chunk: Optional[int] = None):
+    def open_stream(self, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None, max_chunk: Optional[int] = None,
+                    max_frames: Optional[int] = None):
         """A streaming encode / decode session for `batch` utterances of a causal checkpoint (funcodec_amd/stream.py CodecStream):
         n_q quantisers (default: all; a list of `batch` counts gives every utterance its own, and ``set_n_q`` changes them between
-        pushes), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call."""
+        pushes), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call.  A causal net whose bottleneck is
+        a transformer (seq_model: transformer) needs max_frames, the most frames one utterance may hold per side: the size of the
+        session's key / value cache.  Any other net is refused with it."""
         from .stream import CodecStream
-        return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk)
+        return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames)
 
     def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
         """A slot session of a causal checkpoint (funcodec_amd/stream.py StreamSlots): `slots` independent utterances that start, push

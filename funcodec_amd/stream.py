@@ -17,18 +17,32 @@ import torch
 from .engine import CodecEngine, EngineError, _on_device, _ptr, row_nq_list
 
 
-def stream_refusal(arch) -> Optional[str]:
-    """Why a model of this architecture cannot stream (the configuration key is named), or None."""
+def stream_refusal(arch, max_frames: Optional[int] = None) -> Optional[str]:
+    """Why a model of this architecture cannot stream (the configuration key is named), or None.  max_frames: the bound of an
+    utterance's frames that a session of a causal transformer net is opened with (the size of its key / value cache); without it such
+    a net is refused, and with it a net that has no transformer bottleneck is: nothing is silently ignored."""
     if arch.model_type != "encodec":
         return "streaming is not available for model: freq_codec (the STFT frames overlap; time-domain codec only)"
     if not arch.causal:
         return "streaming needs encoder_conf.causal / decoder_conf.causal: true (a non-causal net looks ahead at every layer)"
     if arch.lstm_layers > 0 and arch.seq_model == "transformer":
-        return "streaming is not available for seq_model: transformer (it needs a key / value cache across pushes)"
+        if max_frames is None:
+            return ("streaming is not available for seq_model: transformer (it needs a key / value cache across pushes: "
+                    "open_stream(..., max_frames=N) gives it a size)")
     if arch.segment_length is not None:
         return "streaming is not available with model_conf.segment_dur (segments are normalised and decoded as whole utterances)"
     if arch.q0_ds_ratio > 1:
         return "streaming is not available for quantizer_conf.q0_ds_ratio > 1 (the half-rate first stage looks across frame pairs)"
+    if max_frames is not None:
+        if not (arch.lstm_layers > 0 and arch.seq_model == "transformer"):
+            return "max_frames bounds the key / value cache of seq_model: transformer; this net has no transformer bottleneck, open it without max_frames"
+        samples, frames = min_first(arch)
+        hop = 1
+        for r in arch.ratios:
+            hop *= r
+        need = max(samples // hop, frames)
+        if int(max_frames) < need:
+            return f"max_frames must hold the first push of an utterance: at least {need} frames for this net, got {max_frames}"
     return None
 
 
@@ -37,10 +51,10 @@ FC_SLOT_START, FC_SLOT_FINAL = 1, 2
 
 class _Side:
     """what a wrapper keeps per utterance and side (encode / decode)"""
-    __slots__ = ("head", "started", "ended")
+    __slots__ = ("head", "started", "ended", "frames")
 
     def __init__(self):
-        self.head, self.started, self.ended = [], False, False
+        self.head, self.started, self.ended, self.frames = [], False, False, 0      # frames: pushed so far (read where max_frames bounds them)
 
 
 class _Session:
@@ -48,8 +62,8 @@ class _Session:
     its state and sizes, and the start-up and splitting rule of an utterance."""
     _family = ""
 
-    def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int]):
-        why = stream_refusal(model.arch)
+    def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None):
+        why = stream_refusal(model.arch, max_frames)
         if why:
             raise EngineError(why)
         self.model, self.engine, self.arch = model, model.engine, model.arch
@@ -61,6 +75,8 @@ class _Session:
         self._row_nq: Optional[List[int]] = None
         self.hop = eng.hop_length
         self._h = None
+        #: the most frames an utterance may hold per side (a causal transformer net: the size of its key / value cache), or None
+        self.max_frames = int(max_frames) if max_frames is not None else None
         self._open(rows, max_chunk)
 
     def _fn(self, name: str):
@@ -69,7 +85,8 @@ class _Session:
     @_on_device
     def _open(self, rows, max_chunk):
         eng = self.engine
-        nbytes = int(self._fn("state_bytes")(eng._h, rows))
+        cached = self.max_frames is not None            # an fc_stream with a key / value cache: sized and created by the fc_seqstream_* pair
+        nbytes = int(self.lib.fc_seqstream_state_bytes(eng._h, rows, self.max_frames) if cached else self._fn("state_bytes")(eng._h, rows))
         if nbytes == 0:
             raise EngineError("this engine cannot stream")
         #: everything the session carries between pushes (fc_stream_state_bytes): one allocation, nothing else is kept on the device
@@ -78,7 +95,10 @@ class _Session:
             torch.cuda.current_stream(self.device).synchronize()      # fc_slots_create writes the scales (1) with a copy that is not ordered with this stream
         self.max_chunk = int(max_chunk) if max_chunk is not None else 100 * self.hop
         h = C.c_void_p()
-        eng._check(self._fn("create")(eng._h, rows, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
+        if cached:
+            eng._check(self.lib.fc_seqstream_create(eng._h, rows, self.max_chunk, self.n_q, self.max_frames, _ptr(self.state), nbytes, C.byref(h)))
+        else:
+            eng._check(self._fn("create")(eng._h, rows, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
         self._h = h
         self.min_first_samples = int(self._fn("min_first")(h, 0))
         self.min_first_frames = int(self._fn("min_first")(h, 1))
@@ -138,6 +158,13 @@ class _Session:
         rows = self._row_nq
         return None if rows is None or all(v == self.n_q for v in rows) else rows
 
+    def _fits(self, sd: _Side, frames: int, what: str) -> None:
+        """the bound of a session with a key / value cache: a call whose frames would pass max_frames is refused before anything is pushed"""
+        if self.max_frames is not None and sd.frames + frames > self.max_frames:
+            raise EngineError(f"streaming {what}: this call's {frames} frames would take the utterance to {sd.frames + frames} frames, past the "
+                              f"session's max_frames = {self.max_frames} (the size of its key / value cache); nothing was changed, reset() "
+                              "starts the next utterance")
+
     def _lstm_scratch(self, x: torch.Tensor) -> torch.Tensor:
         B, H, T = x.shape
         return self._scratch(4 * (T * B * 4 * H + 2 * B * H * T) + (1 << 20))
@@ -168,18 +195,23 @@ class CodecStream(_Session):
     stream can know: the session takes one scale per utterance (``scale`` [B], default 1); encode divides by it and decode
     multiplies by it when ``use_scale`` is set, as the offline ``use_scale`` does.  Feeding the offline call's scale
     reproduces the offline result; a running volume estimate is not implemented.
+
+    Transformer bottleneck.  A causal net with ``seq_model: transformer`` attends over every earlier frame, so its session keeps the keys
+    and values of every block (fc_seqstream_create) and needs their size: ``max_frames``, the most frames one utterance may hold per side.
+    A call whose frames would pass it raises before anything is pushed and changes nothing; ``reset`` starts the next utterance.  Without
+    ``max_frames`` such a net is refused, with it any other net is.
     """
 
     _family = "fc_stream"
 
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
-                 max_chunk: Optional[int] = None):
+                 max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
         self.batch = int(batch)
         rows = None
         if n_q is not None and not isinstance(n_q, numbers.Integral):       # a count per utterance: refused before anything is opened
             rows = row_nq_list(model.arch, n_q, self.batch)
             n_q = max(rows)
-        super().__init__(model, self.batch, n_q, max_chunk)
+        super().__init__(model, self.batch, n_q, max_chunk, max_frames)
         self._row_nq = rows
         self.reset(scale)
 
@@ -226,15 +258,19 @@ class CodecStream(_Session):
         if T < 1 or (not final and T % self.hop != 0):
             raise EngineError(f"streaming encode: every push but the final one must be a positive multiple of the hop ({self.hop} samples), "
                               f"got {T}; it is not padded silently")
-        pieces, self._enc.head = self._take(self._enc, wav, final, -1, self.hop, self.min_first_samples, lambda have: EngineError(
+        pieces, head = self._take(self._enc, wav, final, -1, self.hop, self.min_first_samples, lambda have: EngineError(
             f"streaming encode: the first push of an utterance must hold at least {self.min_first_samples} samples (the offline call's "
             "reflected left padding spans them); shorter utterances go through the offline call"))
+        frames = sum(self.engine.frames(p.shape[-1]) if f & FC_SLOT_FINAL else p.shape[-1] // self.hop for p, f in pieces)
+        self._fits(self._enc, frames, "encode")
+        self._enc.head = head
         if not pieces:
             D = self.arch.dimension
             empty = (self.n_q, self.batch, 0) if not self.arch.bypass_quantizer else (self.batch, 0)
             none = torch.empty((self.batch, 0, D), device=self.device)
             return (torch.empty(empty, dtype=torch.int64, device=self.device), none) + ((none,) if want_enc_out else ())
         self._enc.started = True
+        self._enc.frames += frames
         outs = [self._encode_call(part.contiguous(), bool(f & FC_SLOT_FINAL), want_enc_out) for part, f in pieces]
         res = (torch.cat([o[0] for o in outs], -1), torch.cat([o[1] for o in outs], 1))
         return res + ((torch.cat([o[2] for o in outs], 1),) if want_enc_out else ())
@@ -243,12 +279,16 @@ class CodecStream(_Session):
     def _decode_pushes(self, x: torch.Tensor, final: bool, call, rows_apply: bool = False) -> torch.Tensor:
         if x.shape[0] != self.batch:
             raise EngineError(f"this session streams {self.batch} utterances, got {x.shape[0]}")
-        pieces, self._dec.head = self._take(self._dec, x, final, 1, 1, self.min_first_frames, lambda have: EngineError(
+        pieces, head = self._take(self._dec, x, final, 1, 1, self.min_first_frames, lambda have: EngineError(
             f"streaming decode: the utterance ends after {have} frames, fewer than the {self.min_first_frames} the "
             "first push must hold (the offline call's reflected left padding spans them); decode it with the offline call"))
+        frames = sum(p.shape[1] for p, _ in pieces)
+        self._fits(self._dec, frames, "decode")
+        self._dec.head = head
         if not pieces:
             return torch.empty((self.batch, self.engine.channels, 0), dtype=torch.float32, device=self.device)
         self._dec.started = True
+        self._dec.frames += frames
         outs = []
         for part, _ in pieces:
             part = part.contiguous()
@@ -289,6 +329,11 @@ class CodecStream(_Session):
         y, ws, eng = torch.empty_like(x), self._lstm_scratch(x), self.engine
         eng._check(self.lib.fc_stream_lstm_forward(self._h, int(decoder), _ptr(x), T, _ptr(y), _ptr(ws), ws.numel(), eng._stream()))
         return y
+
+    def seq_forward(self, x: torch.Tensor, decoder: bool = False) -> torch.Tensor:
+        """Test hook (fc_seqstream_forward; CodecEngine.stream_seq_forward): the transformer stage of a push alone, without the res_seq
+        skip, on the session's encoder / decoder key / value cache: x [B,C,T] -> [B,C,T]; consecutive calls continue one utterance."""
+        return self.engine.stream_seq_forward(self, x, decoder=decoder)
 
 
 class StreamSlots(_Session):

@@ -241,8 +241,8 @@ int fc_overlap_add(const float* const* frames, const int* lens, int n_frames, in
  *   - everything carried between pushes (per conv the last padding_total input columns, one input column per transposed
  *     conv, the LSTMs' (h, c), the scale) lives in ONE caller-owned device buffer of fc_stream_state_bytes bytes, 16-byte
  *     aligned; nothing is allocated per push; encoder and decoder state are separate, so one session may do both;
- *   - refused at create, the key named in the message: non-causal nets, seq_model transformer, model freq_codec,
- *     quantizer_conf.q0_ds_ratio > 1.  Segmented mode (model_conf.segment_dur) is not a property of the engine -- fc_arch has no
+ *   - refused at create, the key named in the message: non-causal nets, seq_model transformer (fc_stream_create has no bound for
+ *     its key / value cache: fc_seqstream_create below opens such a net), model freq_codec, quantizer_conf.q0_ds_ratio > 1.  Segmented mode (model_conf.segment_dur) is not a property of the engine -- fc_arch has no
  *     such field, the segments are a host-side loop over offline calls -- so only the host session can refuse it, and does.
  * Calls on one engine, its sessions included, are serialised by the caller; sessions do not disturb each other or the
  * offline calls. */
@@ -271,6 +271,29 @@ int  fc_stream_decode_emb(fc_stream* s, const float* emb, int Tfc, int use_scale
  * Test hook: the SLSTM stage of a push alone (lstm.py:22-28 without the res_seq skip) on the session's encoder (decoder = 0) or
  * decoder (decoder = 1) LSTM state: x, y dev f32 [B][H][T]; consecutive calls continue one recurrence, as consecutive pushes do. */
 int  fc_stream_lstm_forward(fc_stream* s, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- streaming a causal net whose bottleneck is the TransformerEncoder (seq_model: transformer, causal: true) -------------
+ * (entry points added without a struct change: FC_ABI_VERSION stays 7)
+ * Causal attention sees every earlier frame, so a session keeps the keys and values of every block of both bottlenecks, and a cache
+ * needs a size: max_frames, the most frames one utterance may hold per side (encoder / decoder), given at create.  The session is an
+ * ordinary fc_stream: every fc_stream_* call works on it and the semantics are those above.  At the bottleneck of either side, with
+ * pos the frames the side has taken since fc_stream_reset: a push of n frames appends its K and V to every block's cache at
+ * [pos, pos + n), and query i of the push sees keys 0 .. pos + i (transformer.py:172-177), inside the first push too; LayerNorm, the
+ * Linears and the feed-forward are per frame.  The caches lie behind what fc_stream_state_bytes lays out: per side, per block,
+ * K [B][C][F] then V [B][C][F] floats, F = max_frames rounded up to 16, the first cache at a multiple of 256 bytes.
+ *   - a push that would take a side past max_frames is refused before its first launch and changes nothing (the message names
+ *     max_frames); the session goes on, fc_stream_reset starts the next utterance.  reset does not clear the caches: a frame is
+ *     written before it is read, and no key behind pos + n reaches a result;
+ *   - refused at create: max_frames < 1 or below the first push (fc_stream_min_first), a net without a transformer bottleneck
+ *     (the message names max_frames), and whatever fc_stream_create refuses for other reasons;
+ *   - slot sessions go on refusing these nets (they need a position per slot). */
+size_t fc_seqstream_state_bytes(const fc_engine* e, int B, int max_frames);       /* 0: this engine cannot stream this way */
+int  fc_seqstream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, int max_frames, void* state /* dev */, size_t state_bytes,
+                         fc_stream** out);
+/* Test hook, the sibling of fc_stream_lstm_forward: the transformer stage of a push alone (all blocks and after_norm, without the
+ * res_seq skip) on the session's encoder (decoder = 0) or decoder (decoder = 1) cache: x, y dev f32 [B][C][T]; it advances that
+ * side's frame count, so consecutive calls continue one utterance, as consecutive pushes do. */
+int  fc_seqstream_forward(fc_stream* s, int decoder, const float* x, int T, float* y, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- slot session: S slots that start, push and end independently in ONE batch ------------------------------------------
  * A streaming push is bound by its launches, so S independent callers cost about what one costs when they share a push.  A slot

@@ -131,6 +131,10 @@ SYMBOLS = {
     "fc_slots_decode_codes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_slots_decode_emb": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_slots_lstm_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    # a slot session of a causal transformer net: an fc_slots with a key / value cache and a position per slot
+    "fc_seqslots_state_bytes": (C.c_size_t, [_P, C.c_int, C.c_int]),
+    "fc_seqslots_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    "fc_seqslots_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     # LauraTTS generation (ABI version 5)
     "fc_laura_create": (C.c_int, [C.POINTER(FcLauraArch), C.c_int, C.POINTER(_P)]),
     "fc_laura_destroy": (None, [_P]),

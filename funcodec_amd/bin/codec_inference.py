@@ -124,9 +124,10 @@ class Speech2Token:
         `streaming=` keyword selects a data iterator; that keyword keeps its meaning here (accepted, unused)."""
         return self.model.open_stream(batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames)
 
-    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
-        """A slot session of the loaded (causal) model: funcodec_amd.stream.StreamSlots, independent utterances sharing every push."""
-        return self.model.open_slots(slots, n_q=n_q, max_chunk=max_chunk)
+    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
+        """A slot session of the loaded (causal) model: funcodec_amd.stream.StreamSlots, independent utterances sharing every push
+        (max_frames: the bound a transformer bottleneck needs, as for open_stream)."""
+        return self.model.open_slots(slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames)
 
     @staticmethod
     def from_pretrained(model_tag: Optional[str] = None, **kwargs: Optional[Any]):

@@ -212,7 +212,9 @@ struct fc_slots : Session {
     enum Phase : char { Idle, Running, Ended, Poisoned };
     std::vector<char> enc_phase, dec_phase;         // [S]
     int enc_pushes = 0, dec_pushes = 0;             // the carries' ping-pong parity per side: idle rows copy theirs, so one number serves all
-    std::vector<int32_t> push;                      // [2 S]: counts, then flags, of the push being enqueued (the source of its one copy)
+    std::vector<int32_t> push;                      // [3 S]: counts, flags, then the cache positions of the push being enqueued (the source of its one copy)
+    // a session with a key / value cache (fc_seqslots_create): the frames each slot's utterance has cached per side, the `pos` of its next push
+    std::vector<int32_t> enc_frames, dec_frames;    // [S]; empty without max_frames
 };
 
 namespace {
@@ -1278,7 +1280,17 @@ Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, f
 // `kv` (a streaming push; null offline): the side's key / value cache inside the session state and the frames it holds.  The T frames
 // of the push run through the same launches; K and V of every block are appended at [pos, pos + T) (seq_cache_append_kernel) and the
 // attention reads them from there (seq_attn_cached_kernel: query i sees keys 0 .. pos + i).
-struct TfCache { float* base = nullptr; int pos = 0, F = 0; };
+// A slot push (`rows`): every row has its own frame count and position (seq_kernels.h, SeqRows); the device reads both from the push's
+// table, host_n / host_pos are the same numbers on the host (null in a dry pass) and only size the attention's grid.
+struct TfCache {
+    float* base = nullptr;
+    int pos = 0, F = 0;
+    bool rows = false;
+    fc::RagLen len;
+    const int* pos_dev = nullptr;
+    const int32_t* host_len = nullptr;
+    const int32_t* host_pos = nullptr;
+};
 Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int T, const TfCache* kv = nullptr) {
     const int C = tb.C, B = cx.B, ff = tb.ff, DK = C / tb.heads;
     const long long sC = (long long)C * T;
@@ -1292,7 +1304,21 @@ Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int
     y.C = C; y.T = T;
     y.raw = cx.alloc<float>((size_t)B * C * T);
     float* part = kv ? cx.alloc<float>(fc::seq_attn_cached_part_floats(B, tb.heads, DK)) : nullptr;     // of every push: no size depends on pos
+    fc::SeqRows rows;                                      // a slot push: the rows' own (n_b, pos_b)
+    double row_pairs = 0.0, row_keys = 0.0;                // its visible (query, key) pairs and the keys it reads, summed over the rows
+    if (kv && kv->rows) {
+        rows.len = kv->len; rows.pos = kv->pos_dev; rows.S = B; rows.T = T; rows.F = kv->F;
+        for (int b = 0; b < B && kv->host_len; ++b) {
+            const int len = kv->host_len[b], n = len > 0 ? fc::ragged_cols(len, rows.len.div, rows.len.mul, rows.len.add) : 0, pos = kv->host_pos[b];
+            if (n < 1) continue;
+            if (n > T || pos < 0 || pos + n > kv->F) { cx.fail("internal: a slot's frames leave the chunk or the key / value cache"); return y; }
+            rows.max_waves = std::max(rows.max_waves, fc::seq_attn_rows_waves(n, pos));
+            row_pairs += (double)n * pos + 0.5 * (double)n * (n + 1);
+            row_keys += pos + n;
+        }
+    }
     const double pairs = tb.layers.empty() ? 0.0
+                         : kv && kv->rows ? row_pairs / B
                          : kv ? (double)T * kv->pos + 0.5 * (double)T * (T + 1)
                               : (e->arch.causal ? 0.5 * (double)T * (T + 1) : (double)T * T);
     const double attn_fl = 4.0 * B * pairs * C;           // q k^T and p v, every visible (query, key) pair
@@ -1311,7 +1337,18 @@ Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int
     for (const TfLayer& L : tb.layers) {
         ln(pending, L.n1g, L.n1b, xn);
         run_conv(e, cx, L.qkv, sxn, fc::Src(), 0, T, qkv, 3 * sC, T, 1);
-        if (kv) {
+        if (kv && kv->rows) {
+            const size_t plane = (size_t)B * C * kv->F;
+            float* kc = kv->base ? kv->base + 2 * plane * block : nullptr;
+            fc::SeqCacheAppendRows ap;
+            ap.qkv = qkv; ap.kc = kc; ap.vc = kc ? kc + plane : nullptr; ap.C = C; ap.rows = rows;
+            cx.launch("transformer cache append", pre, [] { return "seq_cache_append_rows_kernel (slot push: K and V of every row into its cache)"; }, 0.0,
+                      4.0 * B * 4.0 * C * T, [&] { return fc::launch_seq_cache_append_rows(ap, cx.st); });
+            fc::SeqAttnRows a;
+            a.qkv = qkv; a.kc = ap.kc; a.vc = ap.vc; a.out = ctx; a.part = part; a.H = tb.heads; a.DK = DK; a.rows = rows;
+            cx.launch("transformer cached attention", pre, [&] { return fc::seq_attn_rows_kernel_name(DK); }, attn_fl,
+                      4.0 * C * (2.0 * B * T + 2.0 * row_keys), [&] { return fc::launch_seq_attn_rows(a, cx.st); });
+        } else if (kv) {
             const size_t plane = (size_t)B * C * kv->F;
             float* kc = kv->base ? kv->base + 2 * plane * block : nullptr;
             fc::SeqCacheAppend ap;
@@ -1399,6 +1436,9 @@ struct Pass {
     // Slots: `flags` (device [S], kSlotStart | kSlotFinal) per row; host_push = the counts and flags on the host ([2 S]; null in a dry pass)
     const int* flags = nullptr;
     const int32_t* host_push = nullptr;
+    // Slots of a session with a key / value cache: the frames every row's utterance has cached on this side (device [S], behind the flags
+    // in the same copy; a START row's is 0); host_push is then [3 S]
+    const int* pos = nullptr;
 };
 
 // the columns of every row at the input of the layer the walk of a ragged pass stands at (the rule: ragged_kernels.h)
@@ -1414,7 +1454,7 @@ Act ragged_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Sr
 Act stream_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int Tc);
 Act slots_conv(fc_engine* e, Ctx& cx, const Pass& p, const ConvLayer& L, fc::Src s0, fc::Src s1, int elu, int T);
 float* lstm_state(const Session& s, bool dec);
-TfCache tf_cache(const Session& s, bool dec);
+TfCache tf_cache(const Session& s, bool dec, int pos);
 
 // the conv step.  A push stages the layers that carry a left context and runs them over [carry | chunk] (stream_conv; slots_conv with
 // every row at its own place); its pointwise layers run as offline.  A ragged pass stages every conv that looks beyond its own column
@@ -1432,7 +1472,7 @@ Act walk_conv(fc_engine* e, Ctx& cx, const Pass& p, Role role, const ConvLayer& 
 
 // the bottleneck of one side: the sources of the conv behind it = the sequence model's output (plus its input with lstm_skip), or x itself
 // in a net without one.  A push continues the per-step LSTM on the session's state, or the transformer on the session's key / value
-// cache (a session opened with max_frames; the slot pass has no transformer: stream_refusal).
+// cache (a session opened with max_frames); a slot push does either with every row at its own place.
 void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x, fc::Src* a0, fc::Src* a1) {
     const LstmBlock& lb = dec ? e->dec_lstm : e->enc_lstm;
     const TfBlock& tb = dec ? e->dec_tf : e->enc_tf;
@@ -1442,16 +1482,23 @@ void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x
     switch (p.kind) {
         case Pass::Stream:
             if (tb.C) {
-                const TfCache kv = tf_cache(*p.sess, dec);
+                const TfCache kv = tf_cache(*p.sess, dec, dec ? static_cast<const fc_stream*>(p.sess)->dec_frames : static_cast<const fc_stream*>(p.sess)->enc_frames);
                 if (!cx.dry && kv.pos + x.T > p.sess->max_frames) { cx.fail("internal: a push past max_frames reached the transformer"); return; }
                 y = run_transformer(e, cx, tb, x, x.T, &kv);
             } else {
                 y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec));
             }
             break;
-        case Pass::Slots: {                               // every row takes its own frames of the LSTM's steps
+        case Pass::Slots: {                               // every row takes its own frames: of the LSTM's steps, or of the cache and the attention
             const fc::RagLen steps = ragged_len(cx, p);
-            y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec), &steps);
+            if (tb.C) {
+                TfCache kv = tf_cache(*p.sess, dec, 0);
+                kv.rows = true; kv.len = steps; kv.pos_dev = p.pos;
+                if (p.host_push) { kv.host_len = p.host_push; kv.host_pos = p.host_push + 2 * cx.B; }
+                y = run_transformer(e, cx, tb, x, x.T, &kv);
+            } else {
+                y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec), &steps);
+            }
             break;
         }
         case Pass::Ragged:                                // forward in time, rows independent: as offline, garbage columns included
@@ -2046,13 +2093,12 @@ CarryPair carry_pair(const Session& s, const ConvLayer& L, int n) {
 // the session's LSTM state of one side (run_lstm's `carried`)
 float* lstm_state(const Session& s, bool dec) { return s.state + (dec ? s.dec_lstm_off : s.enc_lstm_off); }
 
-// the session's key / value cache of one side and the frames it holds (run_transformer's `kv`).  Only an fc_stream has one
-// (stream_refusal), and the sizing pass (no state yet) runs at pos 0: no size of a push depends on pos.
-TfCache tf_cache(const Session& s, bool dec) {
-    const fc_stream& st = static_cast<const fc_stream&>(s);
+// the session's key / value cache of one side and the frames it holds (run_transformer's `kv`; a slot session's rows have their own
+// positions, which the caller adds).  The sizing pass (no state yet) runs at pos 0: no size of a push depends on pos.
+TfCache tf_cache(const Session& s, bool dec, int pos) {
     TfCache c;
     c.base = s.state ? s.state + (dec ? s.dec_kv_off : s.enc_kv_off) : nullptr;
-    c.pos = dec ? st.dec_frames : st.enc_frames;
+    c.pos = pos;
     c.F = fc::seq_cache_pitch(s.max_frames);
     return c;
 }
@@ -2330,6 +2376,13 @@ int slots_check(const fc_slots* Q, bool decode, const int32_t* counts, const int
         if ((f & FC_SLOT_START) && n < min_first)
             return bad(b, "the START push of an utterance must hold at least " + std::to_string(min_first) + " " + unit +
                               " (fc_slots_min_first: the offline call's reflected left padding spans them), got " + std::to_string(n));
+        if (Q->max_frames > 0) {                          // the bound of the slot's key / value cache
+            const int have = (f & FC_SLOT_START) ? 0 : (decode ? Q->dec_frames : Q->enc_frames)[b], add = ceil_div_i(n, whole);
+            if (have + add > Q->max_frames)
+                return bad(b, "this push of " + std::to_string(add) + " frames would take the utterance to " + std::to_string(have + add) +
+                                  " frames, past the session's max_frames = " + std::to_string(Q->max_frames) +
+                                  " (the size of its key / value cache); nothing was changed, a push with START begins the slot's next utterance");
+        }
     }
     if (!active) return fail(std::string(side) + ": no slot is active in this push (every count is 0)");
     return 0;
@@ -2344,14 +2397,19 @@ Pass slots_pass(fc_slots* Q, Ctx& cx, bool decode, const int32_t* counts, const 
     const int S = cx.B;
     Pass p;
     p.kind = Pass::Slots; p.sess = Q; p.n = decode ? Q->dec_pushes : Q->enc_pushes; p.frame_div = 1;
-    int32_t* dev = cx.alloc<int32_t>((size_t)2 * S);
+    const bool cached = Q->max_frames > 0;               // then the rows' cache positions travel behind the flags
+    const size_t words = (size_t)(cached ? 3 : 2) * S;
+    int32_t* dev = cx.alloc<int32_t>(words);
     p.lengths = dev; p.flags = at(dev, S);
+    if (cached) p.pos = at(dev, 2 * S);
     if (!cx.dry) {
         std::copy(counts, counts + S, Q->push.begin());
         std::copy(flags, flags + S, Q->push.begin() + S);
+        const std::vector<int32_t>& frames = decode ? Q->dec_frames : Q->enc_frames;
+        for (int b = 0; cached && b < S; ++b) Q->push[2 * S + b] = (flags[b] & FC_SLOT_START) ? 0 : frames[b];
         p.host_push = Q->push.data();
     }
-    cx.launch("copy", "slot counts", [&] { return hipMemcpyAsync(dev, Q->push.data(), (size_t)2 * S * sizeof(int32_t), hipMemcpyHostToDevice, cx.st); });
+    cx.launch("copy", "slot counts", [&] { return hipMemcpyAsync(dev, Q->push.data(), words * sizeof(int32_t), hipMemcpyHostToDevice, cx.st); });
     return p;
 }
 
@@ -2388,6 +2446,14 @@ int slots_decode_pass(fc_slots* Q, Ctx& cx, const Pass& p, const float* z_bdt, i
     return finish_decode(Q->e, cx, last, use_scale ? Q->state : nullptr, last.T, wav, &v);
 }
 
+// the frames the rows of an enqueued push have added to their key / value caches (a START row begins at 0); `whole`: counts per frame
+void slots_advance(fc_slots* Q, bool decode, const int32_t* counts, const int32_t* flags, int whole) {
+    if (Q->max_frames <= 0) return;
+    std::vector<int32_t>& frames = decode ? Q->dec_frames : Q->enc_frames;
+    for (int b = 0; b < Q->B; ++b)
+        if (counts[b] > 0) frames[b] = ((flags[b] & FC_SLOT_START) ? 0 : frames[b]) + ceil_div_i(counts[b], whole);
+}
+
 // a push has been enqueued (ok) or failed after its first launch: the slots' phases and the side's parity
 void slots_commit(fc_slots* Q, bool decode, const int32_t* counts, const int32_t* flags, bool ok) {
     std::vector<char>& phase = decode ? Q->dec_phase : Q->enc_phase;
@@ -2398,6 +2464,7 @@ void slots_commit(fc_slots* Q, bool decode, const int32_t* counts, const int32_t
     }
     for (int b = 0; b < Q->B; ++b)
         if (counts[b] > 0) phase[b] = (flags[b] & FC_SLOT_FINAL) ? fc_slots::Ended : fc_slots::Running;
+    slots_advance(Q, decode, counts, flags, decode ? 1 : total_hop(Q->e));
     ++(decode ? Q->dec_pushes : Q->enc_pushes);
 }
 
@@ -3398,7 +3465,7 @@ int fc_seqstream_forward(fc_stream* S, int decoder, const float* x, int T, float
     if (S->enc_pushes < 0) return fail("streaming: fc_stream_reset first");
     if (frames_fit(S, decoder != 0, T)) return 1;
     Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
-    const TfCache kv = tf_cache(*S, decoder != 0);
+    const TfCache kv = tf_cache(*S, decoder != 0, decoder ? S->dec_frames : S->enc_frames);
     Act in; in.raw = const_cast<float*>(x); in.C = tb.C; in.T = T;
     S->broken = true;
     Act out = run_transformer(S->e, cx, tb, in, T, &kv);
@@ -3411,18 +3478,38 @@ int fc_seqstream_forward(fc_stream* S, int decoder, const float* x, int T, float
 
 // ---- slot session (include/funcodec_amd.h) --------------------------------------------------------------------------------------
 size_t fc_slots_state_bytes(const fc_engine* e, int S) { return fc_stream_state_bytes(e, S); }
+size_t fc_seqslots_state_bytes(const fc_engine* e, int S, int max_frames) { return fc_seqstream_state_bytes(e, S, max_frames); }
 
-int fc_slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_slots** out) {
+}  // extern "C"
+
+namespace {
+// fc_slots_create (max_frames = 0) and fc_seqslots_create: one slot session, with or without a key / value cache
+int slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, int max_frames, void* state, size_t state_bytes, const char* state_rule,
+                 fc_slots** out) {
     std::unique_ptr<fc_slots> Q(new fc_slots);
     if (session_create(Q.get(), e, out, S, (S <= 0 || S > 65535) ? "bad slot count (1 .. 65535)" : nullptr, max_chunk_samples, n_q, state, state_bytes,
-                       "START", "slot state: a 16-byte aligned device buffer of fc_slots_state_bytes() bytes"))
+                       "START", state_rule, max_frames))
         return 1;
     // the scale of a slot whose encoder has not started an utterance is 1: decode multiplies by it from the first push on
     HIP_TRY(hipMemcpy(state, Q->ones.data(), (size_t)S * sizeof(float), hipMemcpyHostToDevice));
     Q->enc_phase.assign(S, (char)fc_slots::Idle); Q->dec_phase.assign(S, (char)fc_slots::Idle);
-    Q->push.assign((size_t)2 * S, 0);
+    Q->push.assign((size_t)(max_frames > 0 ? 3 : 2) * S, 0);
+    if (max_frames > 0) { Q->enc_frames.assign(S, 0); Q->dec_frames.assign(S, 0); }
     *out = Q.release();
     return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int fc_slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_slots** out) {
+    return slots_create(e, S, max_chunk_samples, n_q, 0, state, state_bytes, "slot state: a 16-byte aligned device buffer of fc_slots_state_bytes() bytes", out);
+}
+
+int fc_seqslots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, int max_frames, void* state, size_t state_bytes, fc_slots** out) {
+    if (max_frames <= 0) return fail("max_frames must be positive: the most frames a slot's utterance may hold per side");
+    return slots_create(e, S, max_chunk_samples, n_q, max_frames, state, state_bytes,
+                        "slot state: a 16-byte aligned device buffer of fc_seqslots_state_bytes() bytes", out);
 }
 
 void fc_slots_destroy(fc_slots* s) { delete s; }
@@ -3503,6 +3590,40 @@ int fc_slots_lstm_forward(fc_slots* Q, int decoder, const float* x, int T, const
     });
     fc::RagLen st; st.lens = p.lengths;
     if (lstm_hook_run(*Q, cx, *lb, decoder, x, T, &st, y)) slots_commit(Q, decoder != 0, steps, fl.data(), false);
+    return cx.err;
+}
+
+// Test hook: the transformer stage of a slot push alone (TransformerEncoder.forward without the res_seq skip) on the session's key / value
+// cache of one side: the rows with start[b] != 0 begin at position 0, row b takes frames[b] <= T frames (zeros behind).  frames, start
+// host [S].  It advances the side's per-slot frame counts as a push does, refuses a row past max_frames before anything is enqueued, and
+// does not look at the slots' phases.  x, y dev f32 [S][C][T].
+int fc_seqslots_forward(fc_slots* Q, int decoder, const float* x, int T, const int32_t* frames, const int32_t* start, float* y, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (slots_ready(Q)) return 1;
+    const int S = Q->B;
+    if (!x || !y || !frames || !start || T <= 0) return fail("bad argument");
+    const TfBlock& tb = decoder ? Q->e->dec_tf : Q->e->enc_tf;
+    if (!tb.C || Q->max_frames <= 0) return fail("this session has no transformer bottleneck (fc_seqslots_create opens one)");
+    const std::vector<int32_t>& have = decoder ? Q->dec_frames : Q->enc_frames;
+    std::vector<int32_t> fl(S);
+    for (int b = 0; b < S; ++b) {
+        if (frames[b] < 0 || frames[b] > T) return fail("fc_seqslots_forward: slot " + std::to_string(b) + ": frames lie in [0, T]");
+        fl[b] = start[b] ? FC_SLOT_START : 0;
+        const int to = (start[b] ? 0 : have[b]) + frames[b];
+        if (frames[b] > 0 && to > Q->max_frames)
+            return fail("fc_seqslots_forward: slot " + std::to_string(b) + ": these " + std::to_string(frames[b]) + " frames would take the utterance to " +
+                        std::to_string(to) + " frames, past the session's max_frames = " + std::to_string(Q->max_frames) + "; nothing was changed");
+    }
+    Ctx cx = make_ctx(Q->e, S, workspace, workspace_bytes, stream);
+    const Pass p = slots_pass(Q, cx, decoder != 0, frames, fl.data());
+    TfCache kv = tf_cache(*Q, decoder != 0, 0);
+    kv.rows = true; kv.len.lens = p.lengths; kv.pos_dev = p.pos; kv.host_len = p.host_push; kv.host_pos = p.host_push + 2 * S;
+    Act in; in.raw = const_cast<float*>(x); in.C = tb.C; in.T = T;
+    Act out = run_transformer(Q->e, cx, tb, in, T, &kv);
+    cx.launch("copy", "y", [&] { return hipMemcpyAsync(y, out.raw, (size_t)S * tb.C * T * sizeof(float), hipMemcpyDeviceToDevice, cx.st); });
+    cx.launch("ragged mask", "y", [&] { return fc::launch_ragged_mask_f32(y, 1, S, tb.C, T, 1, kv.len, cx.st); });      // as a push masks its outputs
+    if (cx.err) slots_commit(Q, decoder != 0, frames, fl.data(), false);
+    else slots_advance(Q, decoder != 0, frames, fl.data(), 1);
     return cx.err;
 }
 

@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ragged_kernels.h"
+
 namespace fc {
 
 struct SeqAttn {
@@ -38,7 +40,7 @@ constexpr int kSeqCachedSplitMaxQueries = 16;
 constexpr int kSeqCachedTilesPerUnit = 2;
 constexpr int kSeqCachedMaxUnits = 16;
 inline int seq_cache_pitch(int max_frames) { return (max_frames + 15) & ~15; }
-inline int seq_attn_cached_units(int n, int pos) {
+__host__ __device__ inline int seq_attn_cached_units(int n, int pos) {
     if (n > kSeqCachedSplitMaxQueries) return 1;
     const int tiles = (pos + n + 15) / 16, u = (tiles + kSeqCachedTilesPerUnit - 1) / kSeqCachedTilesPerUnit;
     return u < 1 ? 1 : (u > kSeqCachedMaxUnits ? kSeqCachedMaxUnits : u);
@@ -55,5 +57,40 @@ struct SeqCacheAppend {
     int B = 0, C = 0, n = 0, pos = 0, F = 0;
 };
 hipError_t launch_seq_cache_append(const SeqCacheAppend& a, hipStream_t st);
+
+// ---- the row-wise forms (a slot push): every row b of the chunk [S][3 C][T] has its own frame count n_b = ragged_cols(len_b) in [0, T]
+// (RagLen's rule; 0: an idle row) and its own position pos_b, the frames its utterance has cached.  Row b is computed exactly as the
+// lock-step launches compute a one-row push (n_b, pos_b): the same tile loop, the same split (seq_attn_cached_units(n_b, pos_b) waves for
+// a row of at most kSeqCachedSplitMaxQueries frames, merged in unit order; one wave per 16 queries above), so its result depends on its
+// own inputs and (n_b, pos_b) alone -- not on S, on T or on the other rows.  The pitch of the chunk and of `out` is T; columns [n_b, T)
+// of `out` are written as zeros.  The device reads n_b and pos_b once per wave; the host passes what only sizes the grid.
+struct SeqRows {
+    RagLen len;                     // lens: device [S]; n_b = ragged_cols(lens[b], div, mul, add)
+    const int* pos = nullptr;       // device [S]
+    int S = 0, T = 0, F = 0;
+    int max_waves = 0;              // host: the largest seq_attn_rows_waves(n_b, pos_b) of the push (0: every row is idle)
+};
+inline int seq_attn_rows_waves(int n, int pos) { return (n + 15) / 16 * seq_attn_cached_units(n, pos); }
+struct SeqAttnRows {
+    const float* qkv = nullptr;     // [S][3 C][T]
+    const float* kc = nullptr;      // [S][C][F]
+    const float* vc = nullptr;
+    float* out = nullptr;           // [S][C][T]
+    float* part = nullptr;          // seq_attn_cached_part_floats(S, H, DK) floats: row b, head h, unit u at ((b H + h) kSeqCachedMaxUnits + u)
+    int H = 0, DK = 0;
+    SeqRows rows;
+};
+// two launches: the attention of every row, then the merge of the split rows together with the zeros behind every row's count
+hipError_t launch_seq_attn_rows(const SeqAttnRows& a, hipStream_t st);
+const char* seq_attn_rows_kernel_name(int DK);
+
+struct SeqCacheAppendRows {
+    const float* qkv = nullptr;
+    float* kc = nullptr;
+    float* vc = nullptr;
+    int C = 0;
+    SeqRows rows;
+};
+hipError_t launch_seq_cache_append_rows(const SeqCacheAppendRows& a, hipStream_t st);
 
 }  // namespace fc

@@ -53,12 +53,14 @@ class EncodecMI355X:
         from .stream import CodecStream
         return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames)
 
-    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
+    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
         """A slot session of a causal checkpoint (funcodec_amd/stream.py StreamSlots): `slots` independent utterances that start, push
         and end at their own times and share every push of the batch; n_q quantisers at the most (default: all; ``start(slot, n_q=)`` and
-        ``set_n_q(slot, n_q)`` give a slot fewer, at any time between pushes), at most max_chunk samples per call."""
+        ``set_n_q(slot, n_q)`` give a slot fewer, at any time between pushes), at most max_chunk samples per call.  As for
+        ``open_stream``, a net whose bottleneck is a transformer needs max_frames, the most frames one slot's utterance may hold per
+        side (every slot has its own key / value cache and its own position in it); any other net is refused with it."""
         from .stream import StreamSlots
-        return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk)
+        return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames)
 
     # -- helpers -------------------------------------------------------------------------------
     def _as_bct(self, speech: torch.Tensor) -> torch.Tensor:

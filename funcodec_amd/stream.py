@@ -14,6 +14,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from .config import SEQ_FF, SEQ_HEADS
 from .engine import CodecEngine, EngineError, _on_device, _ptr, row_nq_list
 
 
@@ -61,6 +62,7 @@ class _Session:
     """What CodecStream and StreamSlots share: the library's session over `rows` rows (the fc_stream_* or the fc_slots_* calls, `_family`),
     its state and sizes, and the start-up and splitting rule of an utterance."""
     _family = ""
+    _cached_family = ""       # the pair that sizes and creates the kind's session with a key / value cache (max_frames)
 
     def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None):
         why = stream_refusal(model.arch, max_frames)
@@ -85,8 +87,9 @@ class _Session:
     @_on_device
     def _open(self, rows, max_chunk):
         eng = self.engine
-        cached = self.max_frames is not None            # an fc_stream with a key / value cache: sized and created by the fc_seqstream_* pair
-        nbytes = int(self.lib.fc_seqstream_state_bytes(eng._h, rows, self.max_frames) if cached else self._fn("state_bytes")(eng._h, rows))
+        cached = self.max_frames is not None            # a session with a key / value cache: sized and created by the fc_seq*_ pair of its kind
+        seq = lambda name: getattr(self.lib, f"{self._cached_family}_{name}")
+        nbytes = int(seq("state_bytes")(eng._h, rows, self.max_frames) if cached else self._fn("state_bytes")(eng._h, rows))
         if nbytes == 0:
             raise EngineError("this engine cannot stream")
         #: everything the session carries between pushes (fc_stream_state_bytes): one allocation, nothing else is kept on the device
@@ -96,7 +99,7 @@ class _Session:
         self.max_chunk = int(max_chunk) if max_chunk is not None else 100 * self.hop
         h = C.c_void_p()
         if cached:
-            eng._check(self.lib.fc_seqstream_create(eng._h, rows, self.max_chunk, self.n_q, self.max_frames, _ptr(self.state), nbytes, C.byref(h)))
+            eng._check(seq("create")(eng._h, rows, self.max_chunk, self.n_q, self.max_frames, _ptr(self.state), nbytes, C.byref(h)))
         else:
             eng._check(self._fn("create")(eng._h, rows, self.max_chunk, self.n_q, _ptr(self.state), nbytes, C.byref(h)))
         self._h = h
@@ -203,6 +206,7 @@ class CodecStream(_Session):
     """
 
     _family = "fc_stream"
+    _cached_family = "fc_seqstream"
 
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
                  max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
@@ -364,14 +368,20 @@ class StreamSlots(_Session):
     Volume scale: one per utterance, set at ``start`` (default 1; a slot that was never started has scale 1).  It reaches the library
     with the utterance's first encode push and with its first decode push, so ``decode(use_scale=True)`` multiplies by it in a slot
     that only decodes as well.
+
+    Transformer bottleneck.  As for ``CodecStream``, a causal net with ``seq_model: transformer`` needs ``max_frames``, the most frames
+    one slot's utterance may hold per side (fc_seqslots_create): every slot has its own key / value cache and its own position in it,
+    which ``start`` puts back to 0.  A call that would take a slot past the bound raises before anything is pushed, names the slot and
+    changes nothing; ``start(slot)`` begins its next utterance.  Without ``max_frames`` such a net is refused, with it any other net is.
     """
 
     _family = "fc_slots"
+    _cached_family = "fc_seqslots"
 
-    def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None):
+    def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
         self.slots = int(slots)
         self.pad_value = 0.0          # what the assembled batch holds behind a row's count and in idle rows (never read; a test aid)
-        super().__init__(model, self.slots, n_q, max_chunk)
+        super().__init__(model, self.slots, n_q, max_chunk, max_frames)
         self._enc = [_Side() for _ in range(self.slots)]
         self._dec = [_Side() for _ in range(self.slots)]
         self._scale = [1.0] * self.slots
@@ -416,14 +426,19 @@ class StreamSlots(_Session):
             pieces, head = self._take(sd, x, bool(final), tdim, unit, min_first, lambda have: EngineError(
                 f"slot {slot}: the utterance ends after {have} {what}, fewer than the {min_first} the first push must hold "
                 "(the offline call's reflected left padding spans them); it goes through the offline call"))
-            plan[slot] = (pieces, head, bool(pieces), bool(pieces) and bool(final))
+            frames = sum(self.engine.frames(p.shape[tdim]) if unit > 1 and f & FC_SLOT_FINAL else p.shape[tdim] // unit for p, f in pieces)
+            if self.max_frames is not None and sd.frames + frames > self.max_frames:      # _fits, per slot
+                raise EngineError(f"slot {slot}: this call's {frames} frames would take the utterance to {sd.frames + frames} frames, past the "
+                                  f"session's max_frames = {self.max_frames} (the size of its key / value cache); nothing was changed, "
+                                  f"start({slot}) begins the next utterance")
+            plan[slot] = (pieces, head, bool(pieces), bool(pieces) and bool(final), sd.frames + frames)
         return plan
 
     def _run(self, sides, plan, call) -> Dict[int, List]:
         """commit the plan and push its pieces round by round: round r holds piece r of every slot that has one"""
-        before = {slot: (sides[slot].head, sides[slot].started, sides[slot].ended) for slot in plan}
-        for slot, (pieces, head, started, ended) in plan.items():
-            sides[slot].head, sides[slot].started, sides[slot].ended = head, started, ended
+        before = {slot: (sides[slot].head, sides[slot].started, sides[slot].ended, sides[slot].frames) for slot in plan}
+        for slot, (pieces, head, started, ended, frames) in plan.items():
+            sides[slot].head, sides[slot].started, sides[slot].ended, sides[slot].frames = head, started, ended, frames
         outs: Dict[int, List] = {}
         rounds = max((len(v[0]) for v in plan.values()), default=0)
         r = 0
@@ -436,8 +451,8 @@ class StreamSlots(_Session):
             # the library's rule refusals ("slot encode: ..." / "slot decode: ...", slots_check) come before its first launch and change
             # nothing there: if nothing of this call has been pushed either, the call is undone here too
             if r == 0 and str(err).startswith(("slot encode:", "slot decode:")):
-                for slot, (head, started, ended) in before.items():
-                    sides[slot].head, sides[slot].started, sides[slot].ended = head, started, ended
+                for slot, (head, started, ended, frames) in before.items():
+                    sides[slot].head, sides[slot].started, sides[slot].ended, sides[slot].frames = head, started, ended, frames
             else:
                 self._poisoned = [True] * self.slots
             raise
@@ -562,6 +577,22 @@ class StreamSlots(_Session):
         y, ws, eng = torch.empty_like(x), self._lstm_scratch(x), self.engine
         st, fl = (C.c_int32 * S)(*[int(v) for v in steps]), (C.c_int32 * S)(*[int(bool(v)) for v in start])
         eng._check(self.lib.fc_slots_lstm_forward(self._h, int(decoder), _ptr(x), T, st, fl, _ptr(y), _ptr(ws), ws.numel(), eng._stream()))
+        return y
+
+    @_on_device
+    def seq_forward(self, x: torch.Tensor, frames, start, decoder: bool = False) -> torch.Tensor:
+        """Test hook (fc_seqslots_forward): the transformer stage of a slot push alone, without the res_seq skip, on the session's
+        encoder / decoder key / value cache: x [S,C,T] -> [S,C,T]; slot b takes frames[b] <= T frames (zeros behind) at its own
+        position, which begins at 0 where start[b]; consecutive calls continue every slot's own utterance."""
+        x = self.engine._dev(x, torch.float32)
+        S, Cc, T = x.shape
+        if S != self.slots or Cc != self.arch.bottleneck_channels or len(frames) != S or len(start) != S:
+            raise EngineError(f"seq_forward: x must be [{self.slots},{self.arch.bottleneck_channels},T] with one frame count and start flag per slot")
+        y, eng = torch.empty_like(x), self.engine
+        # the chunk's buffers and the partials of the attention's key split, as CodecEngine.stream_seq_forward sizes them, and the push's table
+        ws = self._scratch(4 * S * T * (8 * Cc + SEQ_FF) + 4 * S * 256 * (Cc + 2 * SEQ_HEADS) + 12 * S + (1 << 20))
+        fr, fl = (C.c_int32 * S)(*[int(v) for v in frames]), (C.c_int32 * S)(*[int(bool(v)) for v in start])
+        eng._check(self.lib.fc_seqslots_forward(self._h, int(decoder), _ptr(x), T, fr, fl, _ptr(y), _ptr(ws), ws.numel(), eng._stream()))
         return y
 
 

@@ -286,7 +286,7 @@ int  fc_stream_lstm_forward(fc_stream* s, int decoder, const float* x, int T, fl
  *     written before it is read, and no key behind pos + n reaches a result;
  *   - refused at create: max_frames < 1 or below the first push (fc_stream_min_first), a net without a transformer bottleneck
  *     (the message names max_frames), and whatever fc_stream_create refuses for other reasons;
- *   - slot sessions go on refusing these nets (they need a position per slot). */
+ *   - fc_slots_create refuses these nets as fc_stream_create does; fc_seqslots_create below opens their slot session. */
 size_t fc_seqstream_state_bytes(const fc_engine* e, int B, int max_frames);       /* 0: this engine cannot stream this way */
 int  fc_seqstream_create(fc_engine* e, int B, int max_chunk_samples, int n_q, int max_frames, void* state /* dev */, size_t state_bytes,
                          fc_stream** out);
@@ -343,6 +343,30 @@ int  fc_slots_decode_emb(fc_slots* s, const float* emb, int Tfc, const int32_t* 
  * steps[b] <= T steps (a step beyond leaves its (h, c) as they were, y = 0 there) and begins from zeros where start[b] != 0; both host [S]. */
 int  fc_slots_lstm_forward(fc_slots* s, int decoder, const float* x, int T, const int32_t* steps, const int32_t* start, float* y,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- slot session of a causal transformer net (seq_model: transformer, causal: true) ----------------------------------------
+ * (entry points added without a struct change: FC_ABI_VERSION stays 7)
+ * The slot session with the key / value cache of fc_seqstream_create: size and layout of the state are fc_seqstream_state_bytes(e, S,
+ * max_frames)'s, and the session is an ordinary fc_slots for every fc_slots_* call above.  What a lock-step session keeps once, the
+ * frames a side has taken since reset, a slot session keeps per slot and side, on the host: a START push sets the slot's count to 0
+ * (the caches are not cleared: a frame is written before it is read), every enqueued push adds the row's frames.  At the bottleneck
+ * row b of a push takes its own n_b frames (ceil(count / hop) of an encode push) at its own position pos_b: K and V go to
+ * [pos_b, pos_b + n_b) of the slot's own cache rows and query i sees keys 0 .. pos_b + i, by the arithmetic and the split of the work
+ * of a one-row lock-step push (n_b, pos_b); the positions travel to the device in the push's one copy of counts and flags.  A slot's
+ * results therefore do not depend on S, on the push's width or on what the other slots do.
+ *   - a push that would take ANY slot past max_frames is refused before its first launch, by the rules above: the message names the
+ *     slot and max_frames, nothing changes for any slot, and a push with START begins the refused slot's next utterance;
+ *   - refused at create: max_frames < 1 or below the START push (fc_slots_min_first), a net without a transformer bottleneck (the
+ *     message names max_frames), and whatever fc_slots_create refuses for other reasons. */
+size_t fc_seqslots_state_bytes(const fc_engine* e, int S, int max_frames);        /* 0: this engine cannot stream this way */
+int  fc_seqslots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, int max_frames, void* state /* dev */, size_t state_bytes,
+                        fc_slots** out);
+/* Test hook, the sibling of fc_seqstream_forward and fc_slots_lstm_forward: the transformer stage of a slot push alone on the
+ * session's encoder / decoder cache: x, y dev f32 [S][C][T]; row b takes frames[b] <= T frames (y = 0 behind them) and begins at
+ * position 0 where start[b] != 0; both host [S].  It advances the side's per-slot frame counts, refuses a row past max_frames before
+ * anything is enqueued, and neither reads nor changes the slots' phases. */
+int  fc_seqslots_forward(fc_slots* s, int decoder, const float* x, int T, const int32_t* frames, const int32_t* start, float* y,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* Deferred device-side failures.  Kernels cannot return a status, so two conditions are recorded in host-visible
  * status words and reported by the NEXT fc_* compute call on the engine (non-zero return, message in fc_last_error(),

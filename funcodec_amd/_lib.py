@@ -152,6 +152,15 @@ SYMBOLS = {
     "fc_laura_debug_probe": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "fc_laura_set_persistent_step": (C.c_int, [_P, C.c_int]),
     "fc_laura_persistent_step_fallbacks": (C.c_int, [_P]),
+    # decoding session: S slots of decode_codec that start and end independently in one running batch
+    "fc_laura_slots_state_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
+    "fc_laura_slots_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    "fc_laura_slots_destroy": (None, [_P]),
+    "fc_laura_slots_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int]),
+    "fc_laura_slots_start": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _P,
+                                       _P, C.c_size_t, _P]),
+    "fc_laura_slots_step": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "fc_laura_slots_take": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
 }
 
 _lib = None

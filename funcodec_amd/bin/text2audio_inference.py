@@ -6,7 +6,8 @@ funcodec/bin/text2audio_inference.py:30-198 (LauraTTS zero-shot generation), run
                      sampling=25, continual=True, codec_config_file="codec/config.yaml", codec_model_file="codec/model.pth")
     ret_val, decoded_codec = t2a(text, prompt_text, prompt_audio)          # ret_val = {"gen": wav, "gen_only_lm": wav}
 
-plus ``generate_batch`` (up to 16 prompts per engine call: the reference is batch-1 with one host round trip per token).
+plus ``generate_batch`` (up to 16 prompts per engine call: the reference is batch-1 with one host round trip per token) and
+``generate_many`` (any number of prompts through a decoding session whose slots are refilled as utterances end).
 """
 from __future__ import annotations
 
@@ -125,28 +126,19 @@ class Text2Audio:
                                           None if prompt_audio is None else [prompt_audio])
         return ret[0], codecs[0]
 
-    # -- up to 16 prompts per engine call -----------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def generate_batch(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
-                       prompt_audios: Optional[Sequence[np.ndarray]] = None, seed: Optional[int] = None):
-        """Returns (list of {"gen": wav [1, 1, T], "gen_only_lm": wav}, list of decoded_codec [1, T, predict_nq]) like calling the
-        reference once per utterance; utterances of one call share the engine passes."""
-        m, nq = self.model, self.model.predict_nq
-        n = len(texts)
-        continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
-        cont, cont_lens = None, None
-        if continual_mode:
-            texts = [" ".join([p, t]).strip() for p, t in zip(prompt_texts, texts)]
-            per = []
-            for a in prompt_audios:       # prompt recordings differ in length: one codec call each (no padding inside an utterance)
-                a = torch.as_tensor(a, dtype=torch.float32)
-                codec = self.codec_model(a, run_mod="encode")[0][0].squeeze(1).transpose(0, 1)      # [T, n_q]
-                per.append(codec[:, :nq])
-            cont_lens = [int(c.shape[0]) for c in per]
-            cont = torch.zeros((n, max(cont_lens), nq), dtype=torch.int64, device=m.device)
-            for i, c in enumerate(per):
-                cont[i, : c.shape[0]] = c
-        # 0. text embeddings, 1. text encoder
+    # -- the parts generate_batch and generate_many share ---------------------------------------------------------------------------
+    def _prompt_codecs(self, prompt_audios):
+        """First predict_nq code groups of every prompt recording: [T, nq] each (one codec call each: no padding inside an utterance)."""
+        per = []
+        for a in prompt_audios:
+            a = torch.as_tensor(a, dtype=torch.float32)
+            codec = self.codec_model(a, run_mod="encode")[0][0].squeeze(1).transpose(0, 1)      # [T, n_q]
+            per.append(codec[:, : self.model.predict_nq])
+        return per
+
+    def _encode_texts(self, texts):
+        """0. text embeddings, 1. text encoder: (text_outs [n, L, D], lengths)."""
+        m, n = self.model, len(texts)
         embs, lens = [], []
         for t in texts:
             e, l = self.text_emb_model(t)
@@ -160,19 +152,87 @@ class Text2Audio:
         for i, e in enumerate(embs):
             text_in[i, : lens[i]] = e[: lens[i]].to(m.device)
         text_outs, _ = m.encode(text_in, torch.tensor(lens))
-        # 2. first codec groups, autoregressively
-        tokens, out_lens = m.decode_codec_batch(text_outs, lens, self.max_length, self.sampling, cont, cont_lens, seed)
-        excl = [(cl if self.exclude_prompt else 0) for cl in (cont_lens or [0] * n)] if continual_mode else [None] * n
-        # 3. dense embeddings of all codec groups, then the codec decoder (utterances of equal length share a decoder call)
-        emb = m.cal_codec_emb_batch(text_outs, lens, tokens, out_lens)
+        return text_outs, lens
+
+    def _synthesise(self, text_outs, lens, tokens, out_lens, excl):
+        """3. dense embeddings of all codec groups, then the codec decoder, for one batch of finished utterances."""
+        emb = self.model.cal_codec_emb_batch(text_outs, lens, tokens, out_lens)
         rets, codecs = [], []
-        for i in range(n):
+        for i in range(len(lens)):
             dec = tokens[i: i + 1, : out_lens[i]]
             lo = excl[i]
             _, _, gen_only_lm, _ = self.codec_model(dec[:, lo:], bit_width=None, run_mod="decode")
             _, _, gen, _ = self.codec_model(emb[i: i + 1, : out_lens[i]][:, lo:], run_mod="decode_emb")
             rets.append(dict(gen=gen, gen_only_lm=gen_only_lm))
             codecs.append(dec)
+        return rets, codecs
+
+    # -- up to 16 prompts per engine call -----------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def generate_batch(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
+                       prompt_audios: Optional[Sequence[np.ndarray]] = None, seed: Optional[int] = None):
+        """Returns (list of {"gen": wav [1, 1, T], "gen_only_lm": wav}, list of decoded_codec [1, T, predict_nq]) like calling the
+        reference once per utterance; utterances of one call share the engine passes."""
+        m, nq = self.model, self.model.predict_nq
+        n = len(texts)
+        continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
+        cont, cont_lens = None, None
+        if continual_mode:
+            texts = [" ".join([p, t]).strip() for p, t in zip(prompt_texts, texts)]
+            per = self._prompt_codecs(prompt_audios)
+            cont_lens = [int(c.shape[0]) for c in per]
+            cont = torch.zeros((n, max(cont_lens), nq), dtype=torch.int64, device=m.device)
+            for i, c in enumerate(per):
+                cont[i, : c.shape[0]] = c
+        text_outs, lens = self._encode_texts(texts)
+        # 2. first codec groups, autoregressively
+        tokens, out_lens = m.decode_codec_batch(text_outs, lens, self.max_length, self.sampling, cont, cont_lens, seed)
+        excl = [(cl if self.exclude_prompt else 0) for cl in (cont_lens or [0] * n)] if continual_mode else [None] * n
+        return self._synthesise(text_outs, lens, tokens, out_lens, excl)
+
+    # -- any number of prompts through a decoding session ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
+                      prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
+                      step_n: int = 1):
+        """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
+        starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
+        request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed."""
+        from ..laura import drive_slots
+        m, nq = self.model, self.model.predict_nq
+        n = len(texts)
+        continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
+        per = None
+        if continual_mode:
+            texts = [" ".join([p, t]).strip() for p, t in zip(prompt_texts, texts)]
+            per = self._prompt_codecs(prompt_audios)
+        seeds = [m._next_seed() for _ in range(n)] if seeds is None else [int(v) for v in seeds]
+        if len(seeds) != n:
+            raise ValueError(f"generate_many: {len(seeds)} seeds for {n} requests")
+        groups = [list(range(i, min(i + 16, n))) for i in range(0, n, 16)]         # the batch forms take 16 utterances at a time
+        outs, lens = [None] * n, [0] * n
+        session = m.open_decode(slots, logp=False)
+        try:
+            def start(slot, i):
+                # a request's text is encoded when its slot is free, alone: its text_outs are those of a one-utterance call
+                to, ln = self._encode_texts([texts[i]])
+                outs[i], lens[i] = to[0, : ln[0]], ln[0]
+                session.start(slot, outs[i], lens[i], self.max_length, self.sampling, seeds[i], None if per is None else per[i])
+            taken = drive_slots(session, slots, n, start, step_n)
+        finally:
+            session.free()
+        rets, codecs = [], []
+        for g in groups:                               # finished utterances, 16 at a time, through the batch forms
+            L, C = max(lens[i] for i in g), max(max(taken[i][1] for i in g), 1)
+            text_outs = torch.zeros((len(g), L, outs[g[0]].shape[-1]), dtype=torch.float32, device=m.device)
+            tokens = torch.zeros((len(g), C, nq), dtype=torch.int64, device=m.device)
+            for j, i in enumerate(g):
+                text_outs[j, : lens[i]] = outs[i]
+                tokens[j, : taken[i][1]] = taken[i][0]
+            excl = [((int(per[i].shape[0]) if self.exclude_prompt else 0) if continual_mode else None) for i in g]
+            r, c = self._synthesise(text_outs, [lens[i] for i in g], tokens, [taken[i][1] for i in g], excl)
+            rets += r
+            codecs += c
         return rets, codecs
 
     @staticmethod

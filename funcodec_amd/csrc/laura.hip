@@ -337,9 +337,11 @@ int pack_stack(fc_laura* e, Stack& S, const float* pe_dev, void* ws, size_t ws_b
 
 // ---- execution ---------------------------------------------------------------------------------------------------------------
 struct KvOut {            // LM prefix pass: K / V rows of every block go to the decoding step's caches
-    float* kc = nullptr;  // [layers][B][d][Tcap]
-    float* vc = nullptr;  // [layers][B][Tcap][d]
+    float* kc = nullptr;  // [layers][rows][d][Tcap]
+    float* vc = nullptr;  // [layers][rows][Tcap][d]
     int Tcap = 0;
+    size_t layer_stride = 0;   // floats from one block's cache to the next: rows * d * Tcap
+    size_t row_base = 0;       // where the pass's row 0 lies inside a block's cache (a decoding session's slot: slot * d * Tcap)
 };
 
 // debugging aid (fc_laura_debug_probe): copy one intermediate tensor of the next full-sequence stack run to a caller buffer
@@ -375,8 +377,8 @@ float* run_stack_full(fc_laura* e, Ctx& cx, const Stack& S, const float* in, int
         probe(cx, S, 1, i, xn, (size_t)B * d * T);
         cx.check(launch_lin_full(b.qkv, xn, B, T, qkv, cx.st), "QKV GEMM");
         probe(cx, S, 2, i, qkv, (size_t)B * 3 * d * T);
-        if (kv) cx.check(lk::launch_kv_store(qkv, lens, B, d, T, kv->Tcap, kv->kc + (size_t)i * B * d * kv->Tcap,
-                                             kv->vc + (size_t)i * B * d * kv->Tcap, cx.st), "kv store");
+        if (kv) cx.check(lk::launch_kv_store(qkv, lens, B, d, T, kv->Tcap, kv->kc + (size_t)i * kv->layer_stride + kv->row_base,
+                                             kv->vc + (size_t)i * kv->layer_stride + kv->row_base, cx.st), "kv store");
         lk::AttnFull a;
         a.qkv = qkv; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.lens = lens; a.bidir = bidir; a.causal = causal; a.ctx = ctx;
         a.B = B; a.H = S.s.heads; a.DK = d / S.s.heads; a.T = T; a.R = e->R; a.PR = e->PR;
@@ -522,11 +524,140 @@ __global__ void copy_prompt_kernel(const int64_t* src, const int* lens, int Cmax
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[(size_t)b * stride * nq + i] = src[(size_t)b * Cmax * nq + i];
 }
 
+// Everything a decoding step of B rows keeps between two samples: the caches, the positions and counters, the token vectors of the kernel
+// chain, the persistent step's edge buffers and arrival counters.  A decode_codec call lays it out in its workspace, a decoding session
+// in its state.
+struct StepMem {
+    int B = 0, Tcap = 0, NS = 1, KS2 = 1;
+    int* pos = nullptr;                 // [B] = sequence length after the prefix pass: the cache fill
+    int* ctr = nullptr;                 // n_gen[B], done[B], step[B], n_done
+    float *kc = nullptr, *vc = nullptr; // [layers][B][d][Tcap], [layers][B][Tcap][d]
+    float *xs = nullptr, *qb = nullptr, *apart = nullptr, *hb = nullptr, *lg = nullptr, *nemb = nullptr, *edge = nullptr;
+    unsigned *psync = nullptr, *pseq = nullptr;
+    size_t edge_stride = 0, sync_words = 0, o_q = 0, o_ap = 0, o_xm = 0, o_hb = 0, o_xo = 0;
+    int* n_gen() const { return ctr; }
+    int* done() const { return ctr + B; }
+    int* step() const { return ctr + 2 * B; }
+    int* n_done() const { return ctr + 3 * B; }
+    unsigned* error_word() const { return psync + sync_words - 64; }
+};
+
+StepMem alloc_step_mem(fc_laura* e, Ctx& cx, int B, int Tcap) {
+    const Stack& S = e->codec_lm;
+    const int D = e->arch.codebook_dim, V = e->vocab(), d = S.s.d_model, ff = S.s.ff, NL = S.s.layers;
+    const int heads = S.s.heads, dkh = d / S.s.heads;
+    StepMem m;
+    m.B = B; m.Tcap = Tcap;
+    m.pos = cx.alloc<int>(B);
+    m.ctr = cx.alloc<int>(3 * B + 4);
+    m.kc = cx.alloc<float>((size_t)NL * B * d * Tcap);
+    m.vc = cx.alloc<float>((size_t)NL * B * d * Tcap);
+    m.xs = cx.alloc<float>((size_t)16 * d);
+    m.qb = cx.alloc<float>((size_t)16 * d);
+    m.NS = 256 / (B * heads);                   // key ranges per (utterance, head): fill the chip's 256 CUs
+    m.NS = m.NS < 1 ? 1 : (m.NS > 8 ? 8 : m.NS);
+    m.apart = cx.alloc<float>((size_t)16 * heads * 8 * (dkh + 2));
+    m.hb = cx.alloc<float>((size_t)16 * ff);
+    m.lg = cx.alloc<float>((size_t)16 * V);
+    m.nemb = cx.alloc<float>((size_t)16 * D);
+    // the decoding step as ONE persistent launch (laura_persist.hip): per-block edge buffers, arrival counters, the launch counter
+    m.KS2 = lk::step_persist_ksplit(d, ff);
+    auto pad32 = [](size_t n) { return (n + 31) & ~(size_t)31; };
+    m.o_q = 0; m.o_ap = m.o_q + pad32((size_t)16 * d); m.o_xm = m.o_ap + pad32((size_t)16 * heads * 8 * (dkh + 4));
+    m.o_hb = m.o_xm + pad32((size_t)16 * d); m.o_xo = m.o_hb + pad32((size_t)16 * ff);
+    m.edge_stride = m.o_xo + pad32((size_t)m.KS2 * 16 * d);
+    m.edge = cx.alloc<float>(m.edge_stride * NL);
+    m.sync_words = lk::step_persist_sync_words(NL);
+    m.psync = cx.alloc<unsigned>(m.sync_words + 32);
+    m.pseq = m.psync ? m.psync + m.sync_words : nullptr;            // one word behind the counters
+    return m;
+}
+
+bool step_persist_ok(const fc_laura* e, const StepMem& m) {
+    const fc_laura_stack& s = e->codec_lm.s;
+    return e->persist_on && e->persist_grid > 0 &&
+           lk::step_persist_supported(m.B, s.d_model, s.ff, s.heads, s.d_model / s.heads, e->vocab(), m.NS);
+}
+
+// the sampler of a step over m's rows; the caller adds what is its own (the call's or the rows' parameters, the token buffers)
+lk::Sample step_sampler(const fc_laura* e, const StepMem& m) {
+    const Stack& S = e->codec_lm;
+    lk::Sample sm;
+    sm.logits = m.lg; sm.B = m.B; sm.K = e->arch.codebook_size; sm.nq = e->arch.predict_nq;
+    sm.n_gen = m.n_gen(); sm.done = m.done(); sm.n_done = m.n_done(); sm.pos = m.pos; sm.step = m.step();
+    sm.cb = e->cb; sm.D = e->arch.codebook_dim; sm.next_emb = m.nemb;
+    // the sampler also runs the LM's input layer on the new token (Linear + LayerNorm + ReLU + x * sqrt(d)): xs is ready for block 0
+    sm.emb_wt = e->lm_embed_wt; sm.emb_bias = S.embed.bias; sm.emb_g = S.eg; sm.emb_b = S.eb; sm.dm = S.s.d_model; sm.emb_relu = S.s.embed_relu;
+    sm.xscale = sqrtf((float)S.s.d_model); sm.xs = m.xs;
+    sm.launch_seq = m.pseq;                // every sampler launch numbers the persistent step launch that follows it (1, 2, ...)
+    return sm;
+}
+
+lk::StepPersistArgs step_persist_args(const fc_laura* e, const StepMem& m, unsigned long long* ptrace) {
+    const Stack& S = e->codec_lm;
+    lk::StepPersistArgs pa{};
+    pa.layers = e->step_layers; pa.wdec = e->lm_decoder.wf; pa.bdec = e->lm_decoder.bias; pa.ag = S.ag; pa.ab = S.ab;
+    pa.xs = m.xs; pa.logits = m.lg; pa.edge = m.edge; pa.kc = m.kc; pa.vc = m.vc; pa.pos = m.pos; pa.sync = m.psync; pa.seq = m.pseq;
+    pa.edge_stride = m.edge_stride; pa.o_q = (int)m.o_q; pa.o_ap = (int)m.o_ap; pa.o_xm = (int)m.o_xm; pa.o_hb = (int)m.o_hb; pa.o_xo = (int)m.o_xo;
+    pa.B = m.B; pa.d = S.s.d_model; pa.ff = S.s.ff; pa.H = S.s.heads; pa.DK = S.s.d_model / S.s.heads; pa.NL = S.s.layers; pa.V = e->vocab();
+    pa.Tcap = m.Tcap; pa.R = e->R; pa.PR = e->PR; pa.NS = m.NS;
+    pa.act = S.s.act; pa.G = e->persist_grid; pa.KS2 = m.KS2; pa.trace = ptrace;
+    { const char* t = getenv("FC_LAURA_PERSIST_TEST"); pa.test_timeout = t && std::string(t) == "timeout"; }
+    return pa;
+}
+
+// One decoding step: the newest token of every row through the LM against its KV cache, then the sampler.  Every kernel reads its
+// positions from device memory, so the launch sequence is identical from step to step.  pa null: the kernel chain.
+void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st) {
+    const Stack& S = e->codec_lm;
+    const int B = m.B, d = S.s.d_model, ff = S.s.ff, NL = S.s.layers, V = e->vocab(), Tcap = m.Tcap, heads = S.s.heads, dkh = d / S.s.heads;
+    if (pa) {
+        cx.check(lk::launch_step_persist(*pa, st), "persistent decoding step");
+        cx.check(lk::launch_sample(sm, st), "sampling");
+        return;
+    }
+    for (int i = 0; i < NL; ++i) {
+        const Block& b = S.blocks[i];
+        float* kc = m.kc + (size_t)i * B * d * Tcap;
+        float* vc = m.vc + (size_t)i * B * d * Tcap;
+        cx.check(step_gemv(b.qkv, m.xs, B, b.n1g, b.n1b, 1e-12f, 0, 2, m.qb, d, st, kc, vc, m.pos, d, Tcap), "QKV GEMV");
+        lk::AttnStep a;
+        a.q = m.qb; a.kc = kc; a.vc = vc; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.pos = m.pos; a.part = m.apart; a.NS = m.NS;
+        a.B = B; a.H = heads; a.DK = dkh; a.Tcap = Tcap; a.R = e->R; a.PR = e->PR;
+        cx.check(lk::launch_attn_step(a, st), "step attention");
+        // linear_out reads the key-range partials and combines them while staging its input
+        cx.check(step_gemv(b.out, nullptr, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, m.apart, heads, dkh, m.NS), "out GEMV");
+        cx.check(step_gemv(b.ff1, m.xs, B, b.n2g, b.n2b, 1e-12f, S.s.act, 0, m.hb, ff, st), "FFN GEMV 1");
+        cx.check(step_gemv(b.ff2, m.hb, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st), "FFN GEMV 2");
+    }
+    cx.check(step_gemv(e->lm_decoder, m.xs, B, S.ag, S.ab, 1e-12f, 0, 0, m.lg, V, st), "decoder GEMV");
+    cx.check(lk::launch_sample(sm, st), "sampling");
+}
+
+bool graph_enabled() {
+    static const bool on = !(getenv("FC_LAURA_GRAPH") && atoi(getenv("FC_LAURA_GRAPH")) == 0);
+    return on;
+}
+
+// one step captured on st as an executable graph (62 small launches on the chain: the loop is launch-bound otherwise); null if the
+// stream cannot be captured.  A launch that fails while capturing sets cx.err.
+hipGraphExec_t capture_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st) {
+    hipGraphExec_t gexec = nullptr;
+    hipGraph_t graph = nullptr;
+    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    run_step(e, cx, m, pa, sm, st);
+    const hipError_t ec = hipStreamEndCapture(st, &graph);
+    if (ec != hipSuccess || cx.err || hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) gexec = nullptr;
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!cx.err) (void)hipGetLastError();
+    return gexec;
+}
+
 int do_decode(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* text_lens, int L, const int64_t* continual,
               const int32_t* cont_lens, int Cmax, int max_length, int mode, int ki, float pf, uint64_t seed, const int64_t* forced,
               int64_t* tokens, int32_t* out_lens, float* step_logp, int max_prefix) {
     const Stack& S = e->codec_lm;
-    const int B = cx.B, D = e->arch.codebook_dim, V = e->vocab(), d = S.s.d_model, ff = S.s.ff, NL = S.s.layers;
+    const int B = cx.B, D = e->arch.codebook_dim, V = e->vocab(), d = S.s.d_model;
     const int nq = e->arch.predict_nq, K = e->arch.codebook_size;
     const int T = pad4(max_prefix);
     const int Tcap = pad4(max_prefix + max_length);
@@ -535,93 +666,37 @@ int do_decode(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* text_
     int Tt = 0;
     float* tfm = text_to_fm(e, cx, text_outs, tl, L, &Tt);
     float* seq = cx.alloc<float>((size_t)B * D * T);
-    int* pos = cx.alloc<int>(B);            // = sequence length after the prefix pass: the cache fill
     int* bidir = cx.alloc<int>(B);
-    int* ctr = cx.alloc<int>(3 * B + 4);    // n_gen[B], done[B], step[B], n_done
+    const StepMem m = alloc_step_mem(e, cx, B, Tcap);
+    int* pos = m.pos;
     KvOut kv;
-    kv.Tcap = Tcap;
-    kv.kc = cx.alloc<float>((size_t)NL * B * d * Tcap);
-    kv.vc = cx.alloc<float>((size_t)NL * B * d * Tcap);
-    float* xs = cx.alloc<float>((size_t)16 * d);
-    float* qb = cx.alloc<float>((size_t)16 * d);
-    const int heads = S.s.heads, dkh = d / S.s.heads;
-    int NS = 256 / (B * heads);                 // key ranges per (utterance, head): fill the chip's 256 CUs
-    NS = NS < 1 ? 1 : (NS > 8 ? 8 : NS);
-    float* apart = cx.alloc<float>((size_t)16 * heads * 8 * (dkh + 2));
-    float* hb = cx.alloc<float>((size_t)16 * ff);
-    float* lg = cx.alloc<float>((size_t)16 * V);
-    float* nemb = cx.alloc<float>((size_t)16 * D);
-    // the decoding step as ONE persistent launch (laura_persist.hip): per-block edge buffers, arrival counters, the launch counter
-    const int KS2 = lk::step_persist_ksplit(d, ff);
-    auto pad32 = [](size_t n) { return (n + 31) & ~(size_t)31; };
-    const size_t o_q = 0, o_ap = o_q + pad32((size_t)16 * d), o_xm = o_ap + pad32((size_t)16 * heads * 8 * (dkh + 4)),
-                 o_hb = o_xm + pad32((size_t)16 * d), o_xo = o_hb + pad32((size_t)16 * ff), edge_stride = o_xo + pad32((size_t)KS2 * 16 * d);
-    float* edge = cx.alloc<float>(edge_stride * NL);
-    const size_t sync_words = lk::step_persist_sync_words(NL);
-    unsigned* psync = cx.alloc<unsigned>(sync_words + 32);
-    unsigned* pseq = psync ? psync + sync_words : nullptr;          // one word behind the counters
+    kv.Tcap = Tcap; kv.kc = m.kc; kv.vc = m.vc; kv.layer_stride = (size_t)B * d * Tcap;
     static const char* trace_path = getenv("FC_LAURA_TRACE");        // tuning aid: s_memtime stamps of the LAST persistent step -> file
     unsigned long long* ptrace = trace_path ? cx.alloc<unsigned long long>((size_t)256 * 64 * 8) : nullptr;
-    const bool persist = e->persist_on && e->persist_grid > 0 && lk::step_persist_supported(B, d, ff, heads, dkh, V, NS);
+    const bool persist = step_persist_ok(e, m);
     if (cx.live()) {
         cx.check(lk::launch_lm_assemble(tfm, Tt, tl, e->lm_emb, e->cb, K, nq, continual, cl, Cmax, B, D, T, seq, pos, bidir, cx.st), "LM input");
-        cx.check(lk::launch_fill_i32(ctr, 0, 3 * B + 4, cx.st), "counters");
-        cx.check(lk::launch_fill_i32((int*)psync, 0, (int)sync_words + 32, cx.st), "arrival counters");
+        cx.check(lk::launch_fill_i32(m.ctr, 0, 3 * B + 4, cx.st), "counters");
+        cx.check(lk::launch_fill_i32((int*)m.psync, 0, (int)m.sync_words + 32, cx.st), "arrival counters");
         if (continual) hipLaunchKernelGGL(copy_prompt_kernel, dim3(B), dim3(256), 0, cx.st, continual, cl, Cmax, nq, tokens, Cmax + max_length);
     }
     float* h = run_stack_full(e, cx, S, seq, T, pos, e->arch.bidirectional_inputs ? bidir : nullptr, 1, &kv);
     if (cx.dry || cx.err) return cx.err;
-    int *n_gen = ctr, *done = ctr + B, *step = ctr + 2 * B, *n_done = ctr + 3 * B;
-    cx.check(lk::launch_gather_last(h, pos, B, d, T, xs, cx.st), "last position");
-    cx.check(step_gemv(e->lm_decoder, xs, B, nullptr, nullptr, 0.f, 0, 0, lg, V, cx.st), "decoder GEMV");
-    lk::Sample sm;
-    sm.logits = lg; sm.B = B; sm.K = K; sm.nq = nq; sm.mode = mode; sm.ki = ki; sm.pf = pf; sm.seed = seed; sm.forced = forced;
-    sm.max_steps = max_length; sm.tokens = tokens; sm.tok_stride = Cmax + max_length; sm.tok_off = cl; sm.n_gen = n_gen; sm.done = done;
-    sm.n_done = n_done; sm.pos = pos; sm.step = step; sm.logp_out = step_logp; sm.cb = e->cb; sm.D = D; sm.next_emb = nemb;
-    // the sampler also runs the LM's input layer on the new token (Linear + LayerNorm + ReLU + x * sqrt(d)): xs is ready for block 0
-    sm.emb_wt = e->lm_embed_wt; sm.emb_bias = S.embed.bias; sm.emb_g = S.eg; sm.emb_b = S.eb; sm.dm = d; sm.emb_relu = S.s.embed_relu;
-    sm.xscale = sqrtf((float)d); sm.xs = xs;
-    sm.launch_seq = pseq;                  // every sampler launch numbers the persistent step launch that follows it (1, 2, ...)
+    cx.check(lk::launch_gather_last(h, pos, B, d, T, m.xs, cx.st), "last position");
+    cx.check(step_gemv(e->lm_decoder, m.xs, B, nullptr, nullptr, 0.f, 0, 0, m.lg, V, cx.st), "decoder GEMV");
+    lk::Sample sm = step_sampler(e, m);
+    sm.mode = mode; sm.ki = ki; sm.pf = pf; sm.seed = seed; sm.forced = forced; sm.max_steps = max_length;
+    sm.tokens = tokens; sm.tok_stride = Cmax + max_length; sm.tok_off = cl; sm.logp_out = step_logp;
     cx.check(lk::launch_sample(sm, cx.st), "sampling");
     int host_done = 0;
-    lk::StepPersistArgs pa{};
-    pa.layers = e->step_layers; pa.wdec = e->lm_decoder.wf; pa.bdec = e->lm_decoder.bias; pa.ag = S.ag; pa.ab = S.ab;
-    pa.xs = xs; pa.logits = lg; pa.edge = edge; pa.kc = kv.kc; pa.vc = kv.vc; pa.pos = pos; pa.sync = psync; pa.seq = pseq;
-    pa.edge_stride = edge_stride; pa.o_q = (int)o_q; pa.o_ap = (int)o_ap; pa.o_xm = (int)o_xm; pa.o_hb = (int)o_hb; pa.o_xo = (int)o_xo;
-    pa.B = B; pa.d = d; pa.ff = ff; pa.H = heads; pa.DK = dkh; pa.NL = NL; pa.V = V; pa.Tcap = Tcap; pa.R = e->R; pa.PR = e->PR; pa.NS = NS;
-    pa.act = S.s.act; pa.G = e->persist_grid; pa.KS2 = KS2; pa.trace = ptrace;
-    { const char* t = getenv("FC_LAURA_PERSIST_TEST"); pa.test_timeout = t && std::string(t) == "timeout"; }
+    const lk::StepPersistArgs pa = step_persist_args(e, m, ptrace);
     if (ptrace && cx.live()) cx.check(hipMemsetAsync(ptrace, 0, (size_t)256 * 64 * 8 * sizeof(unsigned long long), cx.st), "trace");
-    // one decoding step: the newest token of every utterance through the LM against its KV cache.  Every kernel reads its
-    // positions from device memory, so the launch sequence is identical from step to step.
-    auto run_step = [&](hipStream_t st) {
-        if (persist) {
-            cx.check(lk::launch_step_persist(pa, st), "persistent decoding step");
-            cx.check(lk::launch_sample(sm, st), "sampling");
-            return;
-        }
-        for (int i = 0; i < NL; ++i) {
-            const Block& b = S.blocks[i];
-            float* kc = kv.kc + (size_t)i * B * d * Tcap;
-            float* vc = kv.vc + (size_t)i * B * d * Tcap;
-            cx.check(step_gemv(b.qkv, xs, B, b.n1g, b.n1b, 1e-12f, 0, 2, qb, d, st, kc, vc, pos, d, Tcap), "QKV GEMV");
-            lk::AttnStep a;
-            a.q = qb; a.kc = kc; a.vc = vc; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.pos = pos; a.part = apart; a.NS = NS;
-            a.B = B; a.H = heads; a.DK = dkh; a.Tcap = Tcap; a.R = e->R; a.PR = e->PR;
-            cx.check(lk::launch_attn_step(a, st), "step attention");
-            // linear_out reads the key-range partials and combines them while staging its input
-            cx.check(step_gemv(b.out, nullptr, B, nullptr, nullptr, 0.f, 0, 1, xs, d, st, nullptr, nullptr, nullptr, 0, 0, apart, heads, dkh, NS), "out GEMV");
-            cx.check(step_gemv(b.ff1, xs, B, b.n2g, b.n2b, 1e-12f, S.s.act, 0, hb, ff, st), "FFN GEMV 1");
-            cx.check(step_gemv(b.ff2, hb, B, nullptr, nullptr, 0.f, 0, 1, xs, d, st), "FFN GEMV 2");
-        }
-        cx.check(step_gemv(e->lm_decoder, xs, B, S.ag, S.ab, 1e-12f, 0, 0, lg, V, st), "decoder GEMV");
-        cx.check(lk::launch_sample(sm, st), "sampling");
-    };
+    auto step = [&](hipStream_t st) { run_step(e, cx, m, persist ? &pa : nullptr, sm, st); };
     bool timed_out = false;
     auto all_done = [&]() -> bool {       // all utterances finished? (one small read-back)
         unsigned perr = 0;             // both words in the same stream-ordered read-back: one synchronisation, no null-stream copy
-        hipError_t ea = hipMemcpyAsync(&host_done, n_done, sizeof(int), hipMemcpyDeviceToHost, cx.st);
-        if (ea == hipSuccess && persist) ea = hipMemcpyAsync(&perr, psync + sync_words - 64, sizeof(unsigned), hipMemcpyDeviceToHost, cx.st);
+        hipError_t ea = hipMemcpyAsync(&host_done, m.n_done(), sizeof(int), hipMemcpyDeviceToHost, cx.st);
+        if (ea == hipSuccess && persist) ea = hipMemcpyAsync(&perr, m.error_word(), sizeof(unsigned), hipMemcpyDeviceToHost, cx.st);
         if (ea != hipSuccess || hipStreamSynchronize(cx.st) != hipSuccess) { cx.err = 1; fail("decode_codec: status read-back failed"); return true; }
         if (perr) {                    // stop replaying steps once a hand-off has timed out; the caller re-runs the call on the kernel chain
             cx.err = 1;
@@ -631,24 +706,16 @@ int do_decode(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* text_
         return host_done >= B;
     };
     int s = 1;
-    if (s < max_length && !cx.err) { run_step(cx.st); ++s; }          // first step eagerly (also sets the kernels' LDS attributes)
-    // the remaining steps replay ONE captured HIP graph of the step (62 small launches): the loop is launch-bound otherwise
-    static const bool graph_env = !(getenv("FC_LAURA_GRAPH") && atoi(getenv("FC_LAURA_GRAPH")) == 0);
+    if (s < max_length && !cx.err) { step(cx.st); ++s; }              // first step eagerly (also sets the kernels' LDS attributes)
+    // the remaining steps replay ONE captured HIP graph of the step
     hipGraphExec_t gexec = nullptr;
-    if (graph_env && cx.st != nullptr && max_length - s >= 4 && !cx.err) {
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(cx.st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            run_step(cx.st);
-            const hipError_t ec = hipStreamEndCapture(cx.st, &graph);
-            if (ec != hipSuccess || cx.err || hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) gexec = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (cx.err) return 1;                                       // a launch failed while capturing
-            (void)hipGetLastError();
-        }
+    if (graph_enabled() && cx.st != nullptr && max_length - s >= 4 && !cx.err) {
+        gexec = capture_step(e, cx, m, persist ? &pa : nullptr, sm, cx.st);
+        if (cx.err) return 1;                                           // a launch failed while capturing
     }
     for (; s < max_length && !cx.err; ++s) {
         if (gexec) cx.check(hipGraphLaunch(gexec, cx.st), "graph launch");
-        else run_step(cx.st);
+        else step(cx.st);
         if ((s & 15) == 15 && s + 1 < max_length && all_done()) break;
     }
     if (gexec) (void)hipGraphExecDestroy(gexec);
@@ -666,7 +733,7 @@ int do_decode(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* text_
     }
     if (persist) {      // a hand-off of the persistent step timed out (a workgroup not resident, a lost store): never a silent result
         unsigned perr = 0;
-        HIP_TRY(hipMemcpyAsync(&perr, psync + sync_words - 64, sizeof(unsigned), hipMemcpyDeviceToHost, cx.st));
+        HIP_TRY(hipMemcpyAsync(&perr, m.error_word(), sizeof(unsigned), hipMemcpyDeviceToHost, cx.st));
         HIP_TRY(hipStreamSynchronize(cx.st));
         if (perr) {
             e->persist_on = false;         // never a silent result: the caller (fc_laura_decode_codec) re-runs this call on the kernel chain
@@ -674,10 +741,114 @@ int do_decode(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* text_
         }
     }
     std::vector<int> gen(B);
-    HIP_TRY(hipMemcpyAsync(gen.data(), n_gen, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, cx.st));
+    HIP_TRY(hipMemcpyAsync(gen.data(), m.n_gen(), (size_t)B * sizeof(int), hipMemcpyDeviceToHost, cx.st));
     HIP_TRY(hipStreamSynchronize(cx.st));
     for (int b = 0; b < B; ++b) out_lens[b] = (continual ? cont_lens[b] : 0) + gen[b];
     return 0;
+}
+
+// ---- decoding session ----------------------------------------------------------------------------------------------------
+enum SlotState { SLOT_FREE = 0, SLOT_RUNNING = 1, SLOT_DONE = 2, SLOT_FAILED = 3 };
+
+}  // namespace
+
+// S slots over ONE StepMem of S rows: a slot is a row of the step.  Everything that survives a call lies in the caller's state allocation,
+// so every pointer of a step is fixed and the step is captured once.
+struct fc_laura_slots {
+    fc_laura* e = nullptr;
+    int S = 0, R = 0;                       // slots; positions per slot (the pitch of the caches, token and log-probability rows)
+    bool with_logp = false;
+    StepMem m;
+    lk::SampleRow* rows = nullptr;          // device [S]
+    int* tok_off = nullptr;                 // device [S]: the slot's continual prompt length
+    int64_t *tokens = nullptr, *forced = nullptr;     // [S][R][nq]
+    float* logp = nullptr;                  // [S][R][V] or null
+    std::vector<int> state, cont_len, max_len, n_gen;
+    hipGraphExec_t gexec = nullptr;         // the captured step, and the form it holds
+    bool g_persist = false, g_timeout = false;
+    bool warmed[2] = {false, false};        // one eager step run per form (sets the kernels' LDS attributes, which a capture cannot)
+    bool chain_only = false;                // after a hand-off timeout
+    unsigned long long persist_steps = 0;   // persistent launches since the arrival counters were zeroed
+    hipStream_t last = nullptr;
+    int* status = nullptr;                  // pinned host [2 S + 1]: the read-back of a step (n_gen, done, error word)
+};
+
+namespace {
+
+void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, fc_laura_slots& s) {
+    const int nq = e->arch.predict_nq, V = e->vocab();
+    s.m = alloc_step_mem(e, cx, S, R);
+    s.rows = cx.alloc<lk::SampleRow>(S);
+    s.tok_off = cx.alloc<int>(S);
+    s.tokens = cx.alloc<int64_t>((size_t)S * R * nq);
+    s.forced = cx.alloc<int64_t>((size_t)S * R * nq);
+    s.logp = with_logp ? cx.alloc<float>((size_t)S * R * V) : nullptr;
+}
+
+lk::Sample slots_sampler(const fc_laura_slots* s) {
+    lk::Sample sm = step_sampler(s->e, s->m);
+    sm.rows = s->rows; sm.row_stride = s->R; sm.forced = s->forced;
+    sm.tokens = s->tokens; sm.tok_stride = s->R; sm.tok_off = s->tok_off; sm.logp_out = s->logp;
+    return sm;
+}
+
+// arrival counters to zero, launch number to 1: the first persistent launch after this is launch 1 again
+void slots_reset_sync(fc_laura_slots* s, Ctx& cx) {
+    cx.check(lk::launch_fill_i32((int*)s->m.psync, 0, (int)s->m.sync_words + 32, cx.st), "arrival counters");
+    cx.check(lk::launch_fill_i32((int*)s->m.pseq, 1, 1, cx.st), "launch counter");
+    s->persist_steps = 0;
+}
+
+// the prefix pass of ONE prompt (B = 1) into row `slot`, and the slot's first sample
+int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, int text_len, const int64_t* continual, int cont_len,
+                 const lk::SampleRow& row, const int64_t* forced) {
+    fc_laura* e = s->e;
+    const Stack& S = e->codec_lm;
+    const int D = e->arch.codebook_dim, V = e->vocab(), d = S.s.d_model, nq = e->arch.predict_nq, K = e->arch.codebook_size;
+    const int T = pad4(text_len + 2 + cont_len);
+    const int32_t tl_h = text_len, cl_h = cont_len;
+    int* tl = upload_lens(cx, &tl_h, 1);
+    int* cl = upload_lens(cx, &cl_h, 1);
+    int Tt = 0;
+    float* tfm = text_to_fm(e, cx, text_outs, tl, text_len, &Tt);
+    float* seq = cx.alloc<float>((size_t)D * T);
+    int* bidir = cx.alloc<int>(1);
+    const StepMem& m = s->m;
+    int* pos = m.pos ? m.pos + slot : nullptr;
+    if (cx.live()) {
+        lk::SlotReset r;
+        r.slot = slot; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
+        r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
+        r.continual = continual; r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
+        cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+        cx.check(lk::launch_lm_assemble(tfm, Tt, tl, e->lm_emb, e->cb, K, nq, continual, cl, cont_len, 1, D, T, seq, pos, bidir, cx.st), "LM input");
+    }
+    KvOut kv;
+    kv.Tcap = m.Tcap; kv.kc = m.kc; kv.vc = m.vc;
+    kv.layer_stride = (size_t)s->S * d * m.Tcap; kv.row_base = (size_t)slot * d * m.Tcap;
+    float* h = run_stack_full(e, cx, S, seq, T, pos, e->arch.bidirectional_inputs ? bidir : nullptr, 1, &kv);
+    if (cx.dry || cx.err) return cx.err;
+    cx.check(lk::launch_gather_last(h, pos, 1, d, T, m.xs + (size_t)slot * d, cx.st), "last position");
+    cx.check(step_gemv(e->lm_decoder, m.xs + (size_t)slot * d, 1, nullptr, nullptr, 0.f, 0, 0, m.lg + (size_t)slot * V, V, cx.st), "decoder GEMV");
+    lk::Sample sm = slots_sampler(s);
+    sm.row0 = slot; sm.nrows = 1;
+    sm.launch_seq = nullptr;               // only the full-width launch that precedes a persistent step numbers it
+    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    return cx.err;
+}
+
+int check_sampling(int mode, int k, float p) {
+    if (mode < 0 || mode > 3) return fail("sampling_mode must be 0..3");
+    if (mode == 2 && k < 1) return fail("top-k sampling needs sampling_k >= 1");
+    if (mode == 3 && !(p > 0.f)) return fail("nucleus sampling needs sampling_p > 0");
+    return 0;
+}
+
+void slots_report(const fc_laura_slots* s, int32_t* done_out, int32_t* n_gen_out) {
+    for (int i = 0; i < s->S; ++i) {
+        if (done_out) done_out[i] = s->state[i];
+        if (n_gen_out) n_gen_out[i] = s->n_gen[i];
+    }
 }
 
 int check_ready(fc_laura* e) {
@@ -901,9 +1072,7 @@ int fc_laura_decode_codec(fc_laura* e, const float* text_outs, const int32_t* te
     if (check_ready(e)) return 1;
     if (!text_outs || !text_lens || !tokens || !out_lens || !workspace || B < 1 || B > 16 || L < 1 || max_length < 1)
         return fail("bad argument (1 <= B <= 16 utterances per call)");
-    if (sampling_mode < 0 || sampling_mode > 3) return fail("sampling_mode must be 0..3");
-    if (sampling_mode == 2 && sampling_k < 1) return fail("top-k sampling needs sampling_k >= 1");
-    if (sampling_mode == 3 && !(sampling_p > 0.f)) return fail("nucleus sampling needs sampling_p > 0");
+    if (check_sampling(sampling_mode, sampling_k, sampling_p)) return 1;
     if (check_lens(text_lens, B, 1, L, "text_lens")) return 1;
     if (continual && (!cont_lens || check_lens(cont_lens, B, 0, Cmax, "cont_lens"))) return fail("bad cont_lens");
     int prefix = 0;
@@ -927,6 +1096,192 @@ int fc_laura_decode_codec(fc_laura* e, const float* text_outs, const int32_t* te
 }
 
 int fc_laura_persistent_step_fallbacks(const fc_laura* e) { return e ? e->persist_fallbacks : -1; }
+
+/* ---- decoding session: S slots that start and end independently in one running batch ---- */
+size_t fc_laura_slots_state_bytes(const fc_laura* ce, int slots, int max_positions, int with_logp) {
+    fc_laura* e = const_cast<fc_laura*>(ce);
+    if (!e || slots < 1 || slots > 16 || max_positions < 16 || max_positions > e->R || max_positions % 4) return 0;
+    Ctx cx = make_ctx(slots, nullptr, 0, nullptr);
+    fc_laura_slots s;
+    slots_layout(e, cx, slots, max_positions, with_logp != 0, s);
+    return cx.off + 4096;
+}
+
+int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_logp, void* state, size_t state_bytes, fc_laura_slots** out) {
+    if (check_ready(e)) return 1;
+    if (slots < 1 || slots > 16) return fail("a decoding session has 1 .. 16 slots (the step form's 16 MFMA columns), got " + std::to_string(slots));
+    if (max_positions < 16 || max_positions % 4 || max_positions > e->R)
+        return fail("a decoding session's max_positions must be a multiple of 4 in [16, " + std::to_string(e->R) + "] (the engine's), got " +
+                    std::to_string(max_positions));
+    if (!state || !out) return fail("null argument");
+    auto s = std::make_unique<fc_laura_slots>();
+    s->e = e; s->S = slots; s->R = max_positions; s->with_logp = with_logp != 0;
+    Ctx cx = make_ctx(slots, state, state_bytes, nullptr);
+    slots_layout(e, cx, slots, max_positions, s->with_logp, *s);
+    if (cx.err) return fail("decoding session: state allocation too small (fc_laura_slots_state_bytes)");
+    s->state.assign(slots, SLOT_FREE); s->cont_len.assign(slots, 0); s->max_len.assign(slots, 0); s->n_gen.assign(slots, 0);
+    // a never-started slot: done = 1, pos = 0, a zero xs row -- it goes through every step with finite values and the sampler skips it
+    const StepMem& m = s->m;
+    const Stack& S = e->codec_lm;
+    const int d = S.s.d_model, heads = S.s.heads, dkh = d / heads;
+    HIP_TRY(hipMemset(m.pos, 0, (size_t)slots * sizeof(int)));
+    HIP_TRY(hipMemset(m.ctr, 0, (size_t)(3 * slots + 4) * sizeof(int)));
+    HIP_TRY(hipMemset(m.xs, 0, (size_t)16 * d * sizeof(float)));
+    HIP_TRY(hipMemset(m.qb, 0, (size_t)16 * d * sizeof(float)));
+    HIP_TRY(hipMemset(m.apart, 0, (size_t)16 * heads * 8 * (dkh + 2) * sizeof(float)));
+    HIP_TRY(hipMemset(m.hb, 0, (size_t)16 * S.s.ff * sizeof(float)));
+    HIP_TRY(hipMemset(m.lg, 0, (size_t)16 * e->vocab() * sizeof(float)));
+    HIP_TRY(hipMemset(m.nemb, 0, (size_t)16 * e->arch.codebook_dim * sizeof(float)));
+    HIP_TRY(hipMemset(m.edge, 0, m.edge_stride * S.s.layers * sizeof(float)));
+    HIP_TRY(hipMemset(m.psync, 0, (m.sync_words + 32) * sizeof(unsigned)));
+    HIP_TRY(hipMemset(s->rows, 0, (size_t)slots * sizeof(lk::SampleRow)));
+    HIP_TRY(hipMemset(s->tok_off, 0, (size_t)slots * sizeof(int)));
+    std::vector<int> ones(slots, 1);
+    const unsigned one = 1u;
+    HIP_TRY(hipMemcpy(m.done(), ones.data(), (size_t)slots * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m.pseq, &one, sizeof(unsigned), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipHostMalloc((void**)&s->status, (size_t)(2 * slots + 1) * sizeof(int), hipHostMallocDefault));
+    *out = s.release();
+    return 0;
+}
+
+void fc_laura_slots_destroy(fc_laura_slots* s) {
+    if (!s) return;
+    if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
+    if (s->status) (void)hipHostFree(s->status);
+    delete s;
+}
+
+size_t fc_laura_slots_workspace_bytes(const fc_laura_slots* cs, int L, int Cmax) {
+    fc_laura_slots* s = const_cast<fc_laura_slots*>(cs);
+    if (!s || L < 1 || Cmax < 0) return 0;
+    Ctx cx = make_ctx(1, nullptr, 0, nullptr);
+    slots_prefix(s, cx, 0, nullptr, L, nullptr, Cmax, lk::SampleRow{}, nullptr);
+    return cx.off + 4096;
+}
+
+int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, int text_len, const int64_t* continual, int cont_len,
+                         int max_length, int sampling_mode, int sampling_k, float sampling_p, uint64_t seed, const int64_t* forced,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
+    if (!text_outs || !workspace || text_len < 1 || max_length < 1 || cont_len < 0 || (cont_len > 0 && !continual))
+        return fail("decoding session: bad argument for slot " + std::to_string(slot));
+    if (check_sampling(sampling_mode, sampling_k, sampling_p)) return 1;
+    const int need = text_len + 2 + cont_len + max_length;
+    if (need > s->R)
+        return fail("decoding session: slot " + std::to_string(slot) + ": text_len + 2 + cont_len + max_length = " + std::to_string(need) +
+                    " exceeds the session's max_positions " + std::to_string(s->R));
+    lk::SampleRow row{};
+    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
+    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;      // the slot index is NOT in the Philox counter: a slot's draws are its own
+    {
+        Ctx dry = make_ctx(1, nullptr, 0, nullptr);
+        slots_prefix(s, dry, slot, nullptr, text_len, nullptr, cont_len, row, nullptr);
+        if (dry.off > workspace_bytes) return fail("workspace too small");
+    }
+    // from here on the slot's previous utterance is gone (a start on a running slot abandons it)
+    s->state[slot] = SLOT_FAILED; s->n_gen[slot] = 0; s->cont_len[slot] = cont_len; s->max_len[slot] = max_length;
+    s->last = (hipStream_t)stream;
+    Ctx cx = make_ctx(1, workspace, workspace_bytes, stream);
+    if (slots_prefix(s, cx, slot, text_outs, text_len, cont_len ? continual : nullptr, cont_len, row, forced)) return 1;
+    s->state[slot] = SLOT_RUNNING;
+    return 0;
+}
+
+int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32_t* n_gen_out, void* stream) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (n_steps < 1) return fail("decoding session: n_steps must be >= 1");
+    bool any = false;
+    for (int i = 0; i < s->S; ++i) any = any || s->state[i] == SLOT_RUNNING;
+    if (!any) { slots_report(s, done_out, n_gen_out); return 0; }
+    fc_laura* e = s->e;
+    const StepMem& m = s->m;
+    Ctx cx = make_ctx(s->S, (void*)m.pos, 0, stream);       // launches only: nothing is allocated
+    s->last = cx.st;
+    const bool persist = !s->chain_only && step_persist_ok(e, m);
+    const lk::StepPersistArgs pa = step_persist_args(e, m, nullptr);
+    lk::Sample sm = slots_sampler(s);
+    if (!persist) sm.launch_seq = nullptr;                  // the launch number counts persistent launches only: the forms may alternate
+    const lk::StepPersistArgs* pap = persist ? &pa : nullptr;
+    // the arrival counters grow by a fixed amount per launch: back to zero long before 32 bits are used up
+    if (persist && s->persist_steps + (unsigned long long)n_steps > (1ull << 20)) slots_reset_sync(s, cx);
+    if (s->gexec && (s->g_persist != persist || s->g_timeout != (pa.test_timeout != 0))) {
+        (void)hipGraphExecDestroy(s->gexec);
+        s->gexec = nullptr;
+    }
+    for (int i = 0; i < n_steps && !cx.err; ++i) {
+        if (!s->warmed[persist]) {                          // the form's first step runs eagerly
+            run_step(e, cx, m, pap, sm, cx.st);
+            s->warmed[persist] = true;
+            continue;
+        }
+        if (!s->gexec && graph_enabled() && cx.st != nullptr) {
+            s->gexec = capture_step(e, cx, m, pap, sm, cx.st);
+            s->g_persist = persist; s->g_timeout = pa.test_timeout != 0;
+            if (cx.err) break;
+        }
+        if (s->gexec) cx.check(hipGraphLaunch(s->gexec, cx.st), "graph launch");
+        else run_step(e, cx, m, pap, sm, cx.st);
+    }
+    if (persist) s->persist_steps += (unsigned long long)n_steps;
+    // one stream-ordered read-back: n_gen [S], done [S] (adjacent) and the persistent step's error word
+    int* host = s->status;
+    host[2 * s->S] = 0;
+    hipError_t ea = cx.err ? hipErrorUnknown : hipMemcpyAsync(host, m.ctr, (size_t)2 * s->S * sizeof(int), hipMemcpyDeviceToHost, cx.st);
+    if (ea == hipSuccess && persist) ea = hipMemcpyAsync(host + 2 * s->S, m.error_word(), sizeof(unsigned), hipMemcpyDeviceToHost, cx.st);
+    if (ea == hipSuccess) ea = hipStreamSynchronize(cx.st);
+    const unsigned perr = (unsigned)host[2 * s->S];
+    if (ea != hipSuccess) {
+        for (int i = 0; i < s->S; ++i)
+            if (s->state[i] == SLOT_RUNNING) s->state[i] = SLOT_FAILED;
+        if (!cx.err) fail(std::string("decoding session: status read-back failed: ") + hipGetErrorString(ea));
+        return 1;
+    }
+    if (perr) {
+        // A hand-off of the persistent step timed out.  The residual rows are updated in place, so the step cannot be run again: every slot
+        // that was running is failed (start revives it), the session stays on the kernel chain, the event is counted.  Never a silent result.
+        for (int i = 0; i < s->S; ++i)
+            if (s->state[i] == SLOT_RUNNING) s->state[i] = SLOT_FAILED;
+        s->chain_only = true;
+        e->persist_fallbacks++;
+        if (s->gexec) { (void)hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
+        cx.check(lk::launch_fill_i32(m.done(), 1, s->S, cx.st), "done flags");
+        slots_reset_sync(s, cx);
+        if (hipStreamSynchronize(cx.st) != hipSuccess || cx.err) return fail("decoding session: reset after a timed-out step failed");
+    } else {
+        for (int i = 0; i < s->S; ++i) {
+            if (s->state[i] != SLOT_RUNNING) continue;
+            s->n_gen[i] = host[i];
+            if (host[s->S + i]) s->state[i] = SLOT_DONE;
+        }
+    }
+    slots_report(s, done_out, n_gen_out);
+    return 0;
+}
+
+int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, int32_t* len_out, float* logp_out) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
+    if (s->state[slot] == SLOT_FAILED) return fail("decoding session: slot " + std::to_string(slot) + " failed (a hand-off of the persistent step timed out); start it again");
+    if (s->state[slot] != SLOT_DONE) return fail("decoding session: slot " + std::to_string(slot) + " has not ended");
+    if (!tokens || !len_out) return fail("null argument");
+    const int nq = s->e->arch.predict_nq, V = s->e->vocab();
+    const int n = s->cont_len[slot] + s->n_gen[slot];
+    if (cap < n) return fail("decoding session: slot " + std::to_string(slot) + " holds " + std::to_string(n) + " tokens, room for " + std::to_string(cap));
+    if (logp_out && !s->logp) return fail("decoding session: opened without per-step log-probabilities");
+    if (n > 0) HIP_TRY(hipMemcpyAsync(tokens, s->tokens + (size_t)slot * s->R * nq, (size_t)n * nq * sizeof(int64_t), hipMemcpyDeviceToDevice, s->last));
+    if (logp_out)
+        HIP_TRY(hipMemcpyAsync(logp_out, s->logp + (size_t)slot * s->R * V, (size_t)s->max_len[slot] * V * sizeof(float), hipMemcpyDeviceToDevice, s->last));
+    HIP_TRY(hipStreamSynchronize(s->last));
+    *len_out = n;
+    s->state[slot] = SLOT_FREE;
+    return 0;
+}
 
 int fc_laura_codec_emb(fc_laura* e, const float* text_outs, const int32_t* text_lens, int B, int L, const int64_t* codec, int nq_cols,
                        const int32_t* codec_lens, int Cmax, float* emb, void* workspace, size_t workspace_bytes, void* stream) {

@@ -102,6 +102,16 @@ struct AttnStep {
 };
 hipError_t launch_attn_step(const AttnStep& a, hipStream_t st);
 
+// per-row sampling parameters of a decoding session (device table [B]): what a decode_codec call fixes for all its rows
+struct SampleRow {
+    int mode, ki;
+    float pf;
+    int max_steps;
+    unsigned long long seed;
+    int forced_on;                  // 0: this row samples even when the launch has a forced-token buffer
+    unsigned rng_row;               // second word of the row's Philox counter (decode_codec: the batch row)
+};
+
 struct Sample {
     const float* logits = nullptr;  // [B][V], V = nq * (K + 1)
     int B = 0, K = 0, nq = 0;
@@ -128,8 +138,30 @@ struct Sample {
     float xscale = 1.f;
     float* xs = nullptr;            // [B][dm]
     unsigned* launch_seq = nullptr; // device word incremented once per launch (the persistent step kernel's launch number), or null
+    // decoding session: mode / ki / pf / seed / max_steps / forced on-off / Philox row word per row instead of the fields above; forced and
+    // logp_out then have row_stride steps per row.  null: exactly the launch a decode_codec call makes
+    const SampleRow* rows = nullptr;
+    int row_stride = 0;
+    int row0 = 0, nrows = 0;        // rows row0 .. row0 + nrows - 1 only (nrows 0: all B)
 };
 hipError_t launch_sample(const Sample& s, hipStream_t st);
+
+struct SlotReset {                  // see slot_reset_kernel
+    int slot = 0, free_slot = 0;    // free_slot: leave the slot ended (done = 1), as a never-started one is
+    int *n_gen = nullptr, *done = nullptr, *step = nullptr, *pos = nullptr, *tok_off = nullptr;
+    SampleRow* rows = nullptr;
+    SampleRow row{};
+    float* xs = nullptr;
+    int dm = 0;
+    int64_t* tokens = nullptr;      // [S][tok_stride][nq]
+    int tok_stride = 0, nq = 0, cont_len = 0;
+    const int64_t* continual = nullptr;   // [cont_len][nq]
+    int64_t* forced = nullptr;      // [S][tok_stride][nq]
+    const int64_t* forced_src = nullptr;  // [row.max_steps][nq] or null
+    float* logp = nullptr;          // [S][tok_stride][V] or null
+    int V = 0;
+};
+hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st);
 
 hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t st);
 

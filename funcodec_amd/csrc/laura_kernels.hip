@@ -1082,6 +1082,9 @@ struct SampleArgs {
     float xscale;
     float* xs;
     unsigned* launch_seq;
+    // decoding session: per-row parameters (null: the call's own, above), the row stride of forced / logp_out, the first row of this launch
+    const SampleRow* rows;
+    int stride, row0;
 };
 
 #define FC_SAMPLE_MAXV 2048      // candidates per group, padded to a power of two for the bitonic sort (K + 1 <= 2048)
@@ -1100,14 +1103,21 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __shared__ int cidx[256];
     __shared__ int ccount;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int b = blockIdx.x;
+    const int b = a.row0 + blockIdx.x;
     const int G = a.K + 1, V = a.nq * G;
+    // the call's parameters, or the row's own (a decoding session: the table is device memory, so a captured step never changes)
+    const SampleRow* row = a.rows ? a.rows + b : nullptr;
+    const int mode = row ? row->mode : a.mode, ki = row ? row->ki : a.ki, max_steps = row ? row->max_steps : a.max_steps;
+    const float pf = row ? row->pf : a.pf;
+    const unsigned long long seed = row ? row->seed : a.seed;
+    const int64_t* forced = (row && !row->forced_on) ? nullptr : a.forced;
+    const unsigned rng_row = row ? row->rng_row : (unsigned)b;      // second word of the Philox counter
     const int step = a.step[b];          // per-utterance sample counter (RNG stream position)
     const int gen = a.n_gen[b];
     const bool was_done = a.done[b] != 0;
     const float* lg = a.logits + (size_t)b * V;
     // log-softmax over the whole vocabulary of the step (TransformerEmbedLM.score, transformer_lm.py:309-311), when asked for
-    if (a.logp_out && !was_done && gen < a.max_steps) {
+    if (a.logp_out && !was_done && gen < max_steps) {
         float m = -INFINITY;
         for (int v = tid; v < V; v += 256) m = fmaxf(m, lg[v]);
         m = wave_max(m);
@@ -1121,7 +1131,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         if (lane == 0) wred[w] = s;
         __syncthreads();
         const float ls = logf(wred[0] + wred[1] + wred[2] + wred[3]);
-        float* o = a.logp_out + ((size_t)b * a.max_steps + gen) * V;
+        float* o = a.logp_out + ((size_t)b * a.stride + gen) * V;
         for (int v = tid; v < V; v += 256) o[v] = (lg[v] - m) - ls;
         __syncthreads();
     }
@@ -1154,7 +1164,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             if (wred[u] > m || (wred[u] == m && wredi[u] < mi)) { m = wred[u]; mi = wredi[u]; }
         __syncthreads();
         int pick = mi;
-        if (a.mode != 0) {
+        if (mode != 0) {
             // unnormalised probabilities exp(x - max) (the normaliser cancels in every mode except the nucleus threshold)
             float s = 0.f;
 #pragma unroll
@@ -1171,11 +1181,11 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             const float total = wred[0] + wred[1] + wred[2] + wred[3];
             int ncand = G;
             bool selected = false;                   // top-k candidates already in val[] / idx[] order
-            if (a.mode == 2 && a.ki <= 64) {
+            if (mode == 2 && ki <= 64) {
                 // top-k with a small k (the recipe samples with --sampling 25): radix-select the k-th largest logit (4 passes over
                 // 8-bit digits of the order-preserving integer image of the float), collect everything >= it, order those few by
                 // (probability descending, index ascending) with a counting rank -- no full sort of the 1025 logits
-                const int kk = a.ki < 1 ? 1 : a.ki;
+                const int kk = ki < 1 ? 1 : ki;
                 unsigned lk[XPT];
                 int nl = 0;
 #pragma unroll
@@ -1253,7 +1263,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                     selected = true;
                 }
             }
-            if (!selected && a.mode >= 2) {
+            if (!selected && mode >= 2) {
                 // descending by probability, ties by index (topk / a stable descending sort): bitonic sort of 2048 pairs
                 for (int kk = 2; kk <= FC_SAMPLE_MAXV; kk <<= 1)
                     for (int j = kk >> 1; j > 0; j >>= 1) {
@@ -1270,13 +1280,13 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                         }
                     }
                 __syncthreads();
-                if (a.mode == 2) ncand = a.ki < G ? (a.ki < 1 ? 1 : a.ki) : G;
+                if (mode == 2) ncand = ki < G ? (ki < 1 ? 1 : ki) : G;
                 else {
                     // nucleus: take entries while the running probability mass is < pf (the entry that crosses is kept)
                     if (tid == 0) {
                         float cum = 0.f;
                         int n = 0;
-                        const float thr = a.pf * total;
+                        const float thr = pf * total;
                         while (n < G && cum < thr) { cum += val[n]; ++n; }
                         sh_i[0] = n < 1 ? 1 : n;
                     }
@@ -1300,7 +1310,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                     if (lane >= o) incl += t;
                 }
                 const float tot = __shfl(incl, 63, 64);
-                const float u = philox_uniform(a.seed, (unsigned)step, (unsigned)b, (unsigned)k);
+                const float u = philox_uniform(seed, (unsigned)step, rng_row, (unsigned)k);
                 const float target = u * tot;
                 const float below = incl - mine;
                 // the lane whose range [below, incl) holds the target; rounding at the very top goes to the last non-empty lane
@@ -1325,7 +1335,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             __syncthreads();
         }
         if (tid == 0) {
-            if (a.forced && gen < a.max_steps) pick = (int)a.forced[((size_t)b * a.max_steps + gen) * a.nq + k];
+            if (forced && gen < max_steps) pick = (int)forced[((size_t)b * a.stride + gen) * a.nq + k];
             chosen[k] = pick;
         }
         __syncthreads();
@@ -1333,7 +1343,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     // ---- bookkeeping of decode_codec (laura_model.py:519-546): a step whose ids contain <eos> ends the utterance and is dropped
     bool eos = false;
     for (int k = 0; k < a.nq; ++k) eos = eos || chosen[k] == a.K;
-    const bool active = !was_done && gen < a.max_steps;
+    const bool active = !was_done && gen < max_steps;
     if (active && !eos) {
         if (tid < a.nq) a.tokens[((size_t)b * a.tok_stride + a.tok_off[b] + gen) * a.nq + tid] = (int64_t)chosen[tid];
         // next LM input: sum of the groups' codebook rows (build_llm_io -> calc_dense_vector)
@@ -1425,11 +1435,11 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             else {
                 a.n_gen[b] = gen + 1;
                 if (step > 0) a.pos[b] += 1;      // step 0 samples from the prefix; later steps appended one token to the cache
-                if (gen + 1 >= a.max_steps) { a.done[b] = 1; atomicAdd(a.n_done, 1); }
+                if (gen + 1 >= max_steps) { a.done[b] = 1; atomicAdd(a.n_done, 1); }
             }
         }
         a.step[b] = step + 1;
-        if (b == 0 && a.launch_seq) *a.launch_seq += 1u;
+        if (blockIdx.x == 0 && a.launch_seq) *a.launch_seq += 1u;
     }
 }
 
@@ -1438,8 +1448,41 @@ hipError_t launch_sample(const Sample& s, hipStream_t st) {
     if (s.emb_wt && (s.dm > 1024 || s.dm % 4 || s.D > FC_SAMPLE_MAXV)) return hipErrorInvalidValue;
     SampleArgs a{s.logits, s.K, s.nq, s.mode, s.ki, s.pf, s.seed, s.forced, s.max_steps, s.tokens, s.tok_stride, s.tok_off, s.n_gen,
                  s.done, s.n_done, s.pos, s.step, s.logp_out, s.cb, s.D, s.next_emb, s.B,
-                 s.emb_wt, s.emb_bias, s.emb_g, s.emb_b, s.dm, s.emb_relu, s.xscale, s.xs, s.launch_seq};
-    hipLaunchKernelGGL(sample_kernel, dim3(s.B), dim3(256), 0, st, a);
+                 s.emb_wt, s.emb_bias, s.emb_g, s.emb_b, s.dm, s.emb_relu, s.xscale, s.xs, s.launch_seq,
+                 s.rows, s.rows ? s.row_stride : s.max_steps, s.row0};
+    const int n = s.nrows > 0 ? s.nrows : s.B;
+    if (s.row0 < 0 || s.row0 + n > s.B) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_kernel, dim3(n), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// One slot of a decoding session back to "nothing generated": its counters and position, its row of the sampling table, a zero LM
+// input row, its token row = the continual prompt (what copy_prompt_kernel does per call) followed by zeros, its forced tokens, zero
+// log-probability rows.  The other slots' rows are not touched.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void slot_reset_kernel(SlotReset r) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
+    const int b = r.slot;
+    if (tid == 0) {
+        r.n_gen[b] = 0; r.done[b] = r.free_slot ? 1 : 0; r.step[b] = 0; r.pos[b] = 0; r.tok_off[b] = r.cont_len;
+        r.rows[b] = r.row;
+    }
+    for (size_t i = tid; i < (size_t)r.dm; i += nth) r.xs[(size_t)b * r.dm + i] = 0.f;
+    const size_t nprompt = (size_t)r.cont_len * r.nq, ntok = (size_t)r.tok_stride * r.nq;
+    for (size_t i = tid; i < ntok; i += nth) r.tokens[(size_t)b * ntok + i] = i < nprompt ? r.continual[i] : 0;
+    if (r.forced_src) {
+        const size_t nf = (size_t)r.row.max_steps * r.nq;
+        for (size_t i = tid; i < nf; i += nth) r.forced[(size_t)b * ntok + i] = r.forced_src[i];
+    }
+    if (r.logp) {
+        const size_t nl = (size_t)r.row.max_steps * r.V;
+        for (size_t i = tid; i < nl; i += nth) r.logp[(size_t)b * r.tok_stride * r.V + i] = 0.f;
+    }
+}
+hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st) {
+    if (r.slot < 0 || r.cont_len < 0 || r.row.max_steps < 0 || r.cont_len + r.row.max_steps > r.tok_stride) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slot_reset_kernel, dim3(64), dim3(256), 0, st, r);
     return hipGetLastError();
 }
 

@@ -272,6 +272,12 @@ class LauraEngine:
         lens = [int(v) for v in out_lens]
         return (tokens, lens, logp) if return_logp else (tokens, lens)
 
+    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True) -> "DecodeSlots":
+        """A decoding session of `slots` slots (1 .. 16): prompts join and leave a running batch.  max_positions (default: the engine's)
+        bounds text_len + 2 + prompt tokens + max_length of a slot and sizes the session's state; logp=False leaves out the per-step
+        log-probabilities [slots, max_positions, vocab], the largest part of it."""
+        return DecodeSlots(self, slots, max_positions, logp)
+
     # -- LauraGenModel.cal_codec_emb on one-hot probabilities (syn_audio) ---------------------------------------------------
     @_on_device
     def codec_emb(self, text_outs: torch.Tensor, text_lengths: Sequence[int], codec: torch.Tensor, codec_lengths: Sequence[int]) -> torch.Tensor:
@@ -310,6 +316,203 @@ class LauraEngine:
         form = {"auto": 1, "single": 2, "windowed": 3}[gemv_stage] if step_form else 0
         self._check(self.lib.fc_laura_linear(self._h, name.encode(), _ptr(x), B, T, form, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y
+
+
+SLOT_STATES = {1: "running", 2: "done", 3: "failed"}       # fc_laura_slots_step's done_out; 0 = free (not reported)
+
+
+class DecodeSlots:
+    """A decoding session (``LauraEngine.open_decode``): S slots of ``decode_codec``, each holding one utterance at a time.  ``start``
+    puts a prompt into a slot while the others are in the middle of theirs, ``step`` advances every running slot by the same number of
+    decoding steps, ``take`` returns what an ended slot generated and frees it.  A slot depends on nothing but its own prompt and
+    parameters; a session of one slot is ``decode_codec`` on the prompt alone, bit for bit."""
+
+    def __init__(self, engine: "LauraEngine", slots: int, max_positions: Optional[int] = None, logp: bool = True):
+        self.engine, self.lib, self.device = engine, engine.lib, engine.device
+        self.slots = int(slots)
+        self.max_positions = int(engine.max_positions if max_positions is None else max_positions)
+        self.with_logp = bool(logp)
+        self._h = None
+        self._max_length = [0] * max(self.slots, 0)
+        self._status = (C.c_int32 * max(self.slots, 1))()
+        self._n_gen = (C.c_int32 * max(self.slots, 1))()
+        self._open()
+
+    @_on_device
+    def _open(self):
+        eng = self.engine
+        nbytes = int(self.lib.fc_laura_slots_state_bytes(eng._h, self.slots, self.max_positions, int(self.with_logp)))
+        #: everything the session carries between calls (fc_laura_slots_state_bytes): one allocation
+        self.state = torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=self.device) if nbytes else None
+        if self.state is not None:
+            torch.cuda.current_stream(self.device).synchronize()      # fc_laura_slots_create writes with copies that this stream does not order
+        h = C.c_void_p()
+        eng._check(self.lib.fc_laura_slots_create(eng._h, self.slots, self.max_positions, int(self.with_logp), _ptr(self.state), nbytes,
+                                                  C.byref(h)))
+        self._h = h
+
+    def free(self) -> None:
+        """End the session and release its state."""
+        if getattr(self, "_h", None):
+            self.lib.fc_laura_slots_destroy(self._h)
+            self._h = None
+        self.state = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise EngineError("decoding session: used after free()")
+        return self._h
+
+    def _run_stream(self):
+        # the step is a captured HIP graph; the legacy default stream cannot be captured (see LauraEngine.decode_codec)
+        eng = self.engine
+        cur = torch.cuda.current_stream(self.device)
+        run = cur
+        if cur.cuda_stream == 0:
+            if eng._side is None:
+                eng._side = torch.cuda.Stream(self.device)
+            run = eng._side
+            run.wait_stream(cur)
+        return cur, run
+
+    @_on_device
+    def start(self, slot: int, text_outs: torch.Tensor, text_len: int, max_length: int = 30 * 25, sampling: Union[bool, int, float] = True,
+              seed: int = 0, continual: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None) -> None:
+        """One prompt into `slot`: text_outs [L, D] or [1, L, D] (rows < text_len are used), continual int64 [C, nq] prompt tokens, forced
+        int64 [max_length, nq].  A running slot's utterance is abandoned.  A refused call changes nothing for any slot."""
+        eng, nq = self.engine, self.engine.spec.predict_nq
+        h = self._handle()
+        text_outs = eng._dev(text_outs, torch.float32)
+        if text_outs.dim() == 2:
+            text_outs = text_outs.unsqueeze(0)
+        eng._check_text_outs("decode session start", text_outs)
+        text_len, max_length = int(text_len), int(max_length)
+        if text_outs.shape[0] != 1 or not 1 <= text_len <= text_outs.shape[1]:
+            raise EngineError(f"decode session start: slot {slot}: one prompt [L, D] with 1 <= text_len <= L, got {tuple(text_outs.shape)}, text_len {text_len}")
+        if max_length < 1:
+            raise EngineError(f"decode session start: slot {slot}: max_length {max_length} < 1")
+        text = text_outs[0, :text_len].contiguous()
+        cont_len = 0
+        if continual is not None:
+            continual = eng._dev(continual, torch.int64)
+            if continual.dim() == 3 and continual.shape[0] == 1:
+                continual = continual[0]
+            if continual.dim() != 2 or continual.shape[1] != nq:
+                raise EngineError(f"decode session start: slot {slot}: continual must be int64 [C, {nq}], got {tuple(continual.shape)}")
+            cont_len = continual.shape[0]
+            continual = continual.contiguous() if cont_len else None
+        if forced is not None:
+            forced = eng._dev(forced, torch.int64)
+            if forced.dim() == 3 and forced.shape[0] == 1:
+                forced = forced[0]
+            if tuple(forced.shape) != (max_length, nq):
+                raise EngineError(f"decode session start: slot {slot}: forced must be int64 [{max_length}, {nq}], got {tuple(forced.shape)}")
+        mode, k, p = sampling_args(sampling)
+        need = int(self.lib.fc_laura_slots_workspace_bytes(h, text_len, cont_len))
+        if eng._ws is None or eng._ws.numel() < need:
+            eng._ws = None
+            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = eng._ws
+        cur, run = self._run_stream()
+        try:
+            eng._check(self.lib.fc_laura_slots_start(h, int(slot), _ptr(text), text_len, _ptr(continual), cont_len, max_length, mode, k, p,
+                                                     int(seed) & (2 ** 64 - 1), _ptr(forced), _ptr(ws), ws.numel(),
+                                                     C.c_void_p(run.cuda_stream)))
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+        self._max_length[int(slot)] = max_length
+
+    @_on_device
+    def step(self, n: int = 16) -> Dict[int, str]:
+        """n decoding steps for every running slot; {slot: "running" | "done" | "failed"} for every slot that holds an utterance."""
+        h = self._handle()
+        cur, run = self._run_stream()
+        before = self.engine.persistent_step_fallbacks
+        try:
+            self.engine._check(self.lib.fc_laura_slots_step(h, int(n), self._status, self._n_gen, C.c_void_p(run.cuda_stream)))
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+        if self.engine.persistent_step_fallbacks != before:
+            self.engine._fallbacks_seen = self.engine.persistent_step_fallbacks
+            import warnings
+            warnings.warn("decoding session: the persistent decoding step timed out at a hand-off (CUs held by another stream / process?); the "
+                          "running slots are failed (start them again) and the session stays on the kernel chain", RuntimeWarning)
+        return {i: SLOT_STATES[int(self._status[i])] for i in range(self.slots) if int(self._status[i]) in SLOT_STATES}
+
+    @_on_device
+    def take(self, slot: int, return_logp: bool = False):
+        """What an ended slot generated: (tokens [len, nq] int64 = prompt tokens + generated ones, len) and, with return_logp, the
+        per-step log-probabilities [max_length, vocab].  The slot is free afterwards.  Refused for a slot that has not ended."""
+        h = self._handle()
+        slot = int(slot)
+        if not 0 <= slot < self.slots:
+            raise EngineError(f"decoding session: slot {slot} outside 0 .. {self.slots - 1}")
+        nq = self.engine.spec.predict_nq
+        cap = self.max_positions
+        tokens = torch.zeros((cap, nq), dtype=torch.int64, device=self.device)
+        logp = None
+        if return_logp:
+            logp = torch.zeros((max(self._max_length[slot], 1), self.engine.spec.lm_vocab), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()          # the copies run on the session's stream
+        n = C.c_int32(0)
+        self.engine._check(self.lib.fc_laura_slots_take(h, slot, _ptr(tokens), cap, C.byref(n), _ptr(logp)))
+        tokens = tokens[: n.value].clone()
+        return (tokens, int(n.value), logp) if return_logp else (tokens, int(n.value))
+
+
+def refill(pending: Sequence[int], free_slots: Sequence[int]) -> List[tuple]:
+    """The refill policy of a decoding session, a plain function of (arrival order, which slots are free): the waiting requests, in
+    arrival order, go to the free slots in ascending order.  Returns [(slot, request)]."""
+    return list(zip(sorted(free_slots), pending))
+
+
+def drive_slots(session, slots: int, n_requests: int, start, step_n: int = 1) -> list:
+    """Run n_requests through a session of `slots` slots kept full in arrival order: ``start(slot, request)`` puts request number
+    `request` into a slot; ``session.step(step_n)`` and ``session.take(slot)`` are a DecodeSlots' (or a stand-in's).  A slot that ended
+    is taken and refilled at the next step boundary; a failed slot's request goes back to the head of the queue.  Returns the takes in
+    request order.
+
+    step_n = 1 looks after every step.  Then no request starts later than it would in ANY schedule that starts requests in arrival
+    order on `slots` rows -- lock-step decode_codec calls of `slots` rows among them -- so the session never runs more steps than
+    those (by induction over the requests: when the other schedule starts request j, fewer than `slots` of the earlier requests
+    are still running in it, and here each of them started no later, so a slot is free here too).  A larger step_n saves a status
+    read-back per step and ends slots up to step_n - 1 steps late."""
+    pending = list(range(n_requests))
+    owner: Dict[int, int] = {}
+    free = list(range(slots))
+    results = [None] * n_requests
+    retries = 0
+    while pending or owner:
+        for slot, req in refill(pending, free):
+            start(slot, req)
+            owner[slot] = req
+            pending.remove(req)
+            free.remove(slot)
+        status = session.step(step_n)
+        failed = []
+        for slot in sorted(owner):
+            st = status.get(slot)
+            if st == "running":
+                continue
+            req = owner.pop(slot)
+            free.append(slot)
+            if st == "done":
+                results[req] = session.take(slot)
+            else:                                   # failed: start revives the slot; the session is on the kernel chain from here on
+                retries += 1
+                if retries > n_requests:
+                    raise EngineError(f"decoding session: request {req} failed again after the session fell back to the kernel chain")
+                failed.append(req)
+        pending[:0] = sorted(failed)
+    return results
 
 
 class LauraGenMI355X:
@@ -372,6 +575,9 @@ class LauraGenMI355X:
                            continual_lengths: Optional[Sequence[int]] = None, seed: Optional[int] = None):
         return self.engine.decode_codec(text, text_lengths, max_length, sampling, self._next_seed() if seed is None else seed, continual,
                                         continual_lengths)
+
+    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True) -> DecodeSlots:
+        return self.engine.open_decode(slots, max_positions, logp)
 
     @torch.no_grad()
     def cal_codec_emb_batch(self, text, text_lengths, codec, codec_lengths):

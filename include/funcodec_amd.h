@@ -632,6 +632,43 @@ int fc_laura_set_persistent_step(fc_laura* e, int on);
  * This counter says how many calls of this engine went that way (0 normally; -1 on a null handle): a fallback is reported, never silent. */
 int fc_laura_persistent_step_fallbacks(const fc_laura* e);
 
+/* ---- decoding session: prompts join and leave a running batch (continuous batching of LauraGenModel.decode_codec,
+ * laura_model.py:501-548, which the reference runs for one utterance at a time) ------------------------------------------
+ * S slots (1 .. 16), each holding one utterance at a time.  One step call advances every running slot by the same number of
+ * decoding steps; a slot can be started while the others are in the middle of theirs, and a slot that ended (<eos>, or its own
+ * max_length) is free for the next prompt.  A slot depends on nothing but its own prompt and parameters: its tokens, length and
+ * per-step log-probabilities are the same bits alone or in a full session, in any slot, whatever starts and ends around it (its
+ * Philox counter is (seed, step, 0, group): the slot index is not in it).  A session of one slot is fc_laura_decode_codec on that
+ * prompt alone, bit for bit; a session of S slots computes a row as an S-row call does (same key ranges per head).
+ * Everything that survives a call lies in ONE device allocation of the caller (`state`, zero-filled or not): the key / value caches
+ * [layers][S][d][max_positions] and [layers][S][max_positions][d], positions, counters and the per-slot sampling table, the step's
+ * token vectors and hand-off buffers, tokens and forced tokens [S][max_positions][predict_nq] and, with_logp != 0, the per-step
+ * log-probabilities [S][max_positions][vocab].  max_positions: a multiple of 4 in [16, the engine's]. */
+typedef struct fc_laura_slots fc_laura_slots;
+size_t fc_laura_slots_state_bytes(const fc_laura* e, int slots, int max_positions, int with_logp);   /* 0: refused (see create) */
+int  fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_logp, void* state, size_t state_bytes, fc_laura_slots** out);
+void fc_laura_slots_destroy(fc_laura_slots* s);
+/* device scratch of fc_laura_slots_start for a text of <= L tokens and <= Cmax prompt tokens */
+size_t fc_laura_slots_workspace_bytes(const fc_laura_slots* s, int L, int Cmax);
+/* The head of decode_codec for ONE prompt into slot `slot`: prefix pass (B = 1) into the slot's cache rows and the first sample.
+ *   text_outs dev f32 [text_len][codebook_dim];  continual dev i64 [cont_len][predict_nq] or NULL (cont_len 0)
+ *   sampling_mode / sampling_k / sampling_p / seed / forced (dev i64 [max_length][predict_nq] or NULL, copied): as fc_laura_decode_codec
+ * Refused before any launch, changing nothing for any slot: a slot outside 0 .. S - 1, bad sampling arguments,
+ * text_len + 2 + cont_len + max_length > max_positions.  A running slot's utterance is abandoned.  Revives a failed slot. */
+int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, int text_len, const int64_t* continual, int cont_len,
+                         int max_length, int sampling_mode, int sampling_k, float sampling_p, uint64_t seed, const int64_t* forced,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* The loop body of decode_codec, n_steps times for every running slot (one captured graph of the step, replayed), then ONE
+ * stream-ordered read-back.  Returns at once when no slot is running.
+ *   done_out  host i32 [S] or NULL: 0 free, 1 running, 2 ended (take it), 3 failed;   n_gen_out host i32 [S] or NULL: tokens generated
+ * A hand-off of the persistent step that times out fails every slot that was running (the step updates its rows in place and
+ * cannot be repeated); the session then stays on the kernel chain and fc_laura_persistent_step_fallbacks counts the event. */
+int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32_t* n_gen_out, void* stream);
+/* The tail of decode_codec for an ended slot, which is free afterwards (refused for a slot that has not ended):
+ *   tokens dev i64 [cap][predict_nq]: prompt tokens followed by the generated ones;  len_out host: their number
+ *   logp_out dev f32 [max_length][vocab] or NULL: what every step sampled from (zero rows past the last step) */
+int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, int32_t* len_out, float* logp_out);
+
 #ifdef __cplusplus
 }
 #endif

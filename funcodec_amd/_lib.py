@@ -135,6 +135,13 @@ SYMBOLS = {
     "fc_seqslots_state_bytes": (C.c_size_t, [_P, C.c_int, C.c_int]),
     "fc_seqslots_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
     "fc_seqslots_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    # graph replay of a session's pushes (opt-in per session; counts: int64 [4] = replays, captures, evictions, fallbacks)
+    "fc_graphstream_set": (C.c_int, [_P, C.c_int]),
+    "fc_graphstream_enabled": (C.c_int, [_P]),
+    "fc_graphstream_counts": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "fc_graphslots_set": (C.c_int, [_P, C.c_int]),
+    "fc_graphslots_enabled": (C.c_int, [_P]),
+    "fc_graphslots_counts": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     # LauraTTS generation (ABI version 5)
     "fc_laura_create": (C.c_int, [C.POINTER(FcLauraArch), C.c_int, C.POINTER(_P)]),
     "fc_laura_destroy": (None, [_P]),

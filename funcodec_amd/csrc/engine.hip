@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -196,6 +197,36 @@ struct Session {
     size_t carried_floats = 0;                      // of them and is cleared at reset (the caches are written before they are read)
     int enc_min_first = 0, dec_min_first = 0;       // shortest first push: samples (a hop multiple) / frames
     std::vector<float> ones;
+
+    // Graph replay of the session's pushes (fc_graphstream_set, fc_graphslots_set; include/funcodec_amd.h).  The key of a captured push holds every host value
+    // its enqueued work depends on (DESIGN.md section 8 lists the walk's host values and where each one lives); everything else the
+    // launches read lies in device memory and is read at replay.
+    struct GraphKey {
+        int form = 0;                               // 0 encode, 1 decode_codes, 2 decode_emb (which also names the side)
+        int width = 0, parity = 0, n_q = 0, use_scale = 0;
+        std::array<const void*, 5> ptr{};           // inputs, outputs (null: absent) and the slot push's scale
+        const void* ws = nullptr; size_t ws_bytes = 0;
+        const void* stream = nullptr;
+        const void* nq_table = nullptr; int nq_rows = 0;      // per-row stage counts: null / 0 when none are set
+        bool operator==(const GraphKey& o) const {
+            return form == o.form && width == o.width && parity == o.parity && n_q == o.n_q && use_scale == o.use_scale && ptr == o.ptr && ws == o.ws &&
+                   ws_bytes == o.ws_bytes && stream == o.stream && nq_table == o.nq_table && nq_rows == o.nq_rows;
+        }
+    };
+    struct Graph { GraphKey key; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
+    static constexpr size_t kMaxGraphs = 16;
+    bool graph_on = false;
+    std::vector<Graph> graphs;                      // at most kMaxGraphs; the least recently used one is evicted
+    unsigned long long graph_tick = 0;
+    int64_t graph_counts[4] = {0, 0, 0, 0};         // replays, captures, evictions, fallbacks since create
+    void drop_graphs() {
+        for (Graph& g : graphs) (void)hipGraphExecDestroy(g.exec);
+        graphs.clear();
+    }
+    Session() = default;
+    Session(const Session&) = delete;
+    Session& operator=(const Session&) = delete;
+    ~Session() { drop_graphs(); }
 };
 
 // One streaming session (fc_stream_*): B utterances in lock-step.  The host side keeps only push counters.
@@ -1290,6 +1321,8 @@ struct TfCache {
     const int* pos_dev = nullptr;
     const int32_t* host_len = nullptr;
     const int32_t* host_pos = nullptr;
+    bool grid_bound = false;        // a captured slot push: the attention's grid by the bound that depends on T alone (the rows' own counts and
+                                    // positions are read on the device, a wave beyond a row's units returns at once: the same bits)
 };
 Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int T, const TfCache* kv = nullptr) {
     const int C = tb.C, B = cx.B, ff = tb.ff, DK = C / tb.heads;
@@ -1316,6 +1349,7 @@ Act run_transformer(fc_engine* e, Ctx& cx, const TfBlock& tb, const Act& in, int
             row_pairs += (double)n * pos + 0.5 * (double)n * (n + 1);
             row_keys += pos + n;
         }
+        if (kv->grid_bound) rows.max_waves = (T + 15) / 16 * fc::kSeqCachedMaxUnits;
     }
     const double pairs = tb.layers.empty() ? 0.0
                          : kv && kv->rows ? row_pairs / B
@@ -1439,6 +1473,8 @@ struct Pass {
     // Slots of a session with a key / value cache: the frames every row's utterance has cached on this side (device [S], behind the flags
     // in the same copy; a START row's is 0); host_push is then [3 S]
     const int* pos = nullptr;
+    // Slots: the pass is being captured into a graph that later pushes replay, so nothing it enqueues may depend on the rows' host values
+    bool graphed = false;
 };
 
 // the columns of every row at the input of the layer the walk of a ragged pass stands at (the rule: ragged_kernels.h)
@@ -1495,6 +1531,7 @@ void run_bottleneck(fc_engine* e, Ctx& cx, const Pass& p, bool dec, const Act& x
                 TfCache kv = tf_cache(*p.sess, dec, 0);
                 kv.rows = true; kv.len = steps; kv.pos_dev = p.pos;
                 if (p.host_push) { kv.host_len = p.host_push; kv.host_pos = p.host_push + 2 * cx.B; }
+                kv.grid_bound = p.graphed;
                 y = run_transformer(e, cx, tb, x, x.T, &kv);
             } else {
                 y = run_lstm(e, cx, lb, x, x.T, lstm_state(*p.sess, dec), &steps);
@@ -2321,12 +2358,112 @@ int stream_decode_check(fc_stream* S, int Tfc) {
     return frames_fit(S, true, Tfc);
 }
 
-// a decode push from its decoder input z on: enqueued whole, or the session is broken
-int stream_decode_push(fc_stream* S, Ctx& cx, const float* z, int Tfc, int use_scale, float* wav) {
-    if (cx.err) return 1;                               // nothing of the state has been written yet
-    S->broken = true;
-    if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
-    S->broken = false;
+// ---- graph replay of a push (include/funcodec_amd.h) ----------------------------------------------------------
+// FC_SESSION_GRAPH=0: the process switch that keeps every session eager, whatever fc_graph*_set is asked
+bool session_graph_allowed() {
+    static const int on = fc::deploy_switch("FC_SESSION_GRAPH", 1);
+    return on != 0;
+}
+
+enum GraphForm { kFormEncode = 0, kFormDecodeCodes = 1, kFormDecodeEmb = 2 };
+
+Session::GraphKey graph_key(const Session& s, int form, int width, int parity, int use_scale, std::array<const void*, 5> ptr, void* ws, size_t ws_bytes,
+                            void* stream) {
+    Session::GraphKey k;
+    k.form = form; k.width = width; k.parity = parity & 1; k.n_q = s.n_q; k.use_scale = use_scale ? 1 : 0;
+    k.ptr = ptr; k.ws = ws; k.ws_bytes = ws_bytes; k.stream = stream;
+    k.nq_table = row_nq_table(s.e); k.nq_rows = (int)s.e->row_nq.size();
+    return k;
+}
+
+// One push of a session, after every check of it has passed.  body(cx, captured) walks the whole pass over a fresh context and returns
+// its error; `eager(st)` enqueues what must not sit inside a graph (the slot push's copy from host memory) and is called in front of a
+// graph launch only: an eager pass enqueues that copy itself.  key: null for a push that is not to be cached (a one-off).
+// Returns 0, 1 (the pass failed: its message is set) or 2 (the graph's launch failed: what it has written is unknown).
+//   hit:  eager part, hipGraphLaunch.
+//   miss: the pass is captured on the caller's stream (thread-local mode: one stream, a linear chain, nothing executes), instantiated,
+//         launched and stored; the least recently used of kMaxGraphs graphs goes.  A launch that fails while capturing fails the push.
+//   If the stream cannot be captured or the graph not instantiated, the sticky error is cleared and the push runs eagerly (fallbacks).
+template <typename Eager, typename Body>
+int session_push(Session* s, const Session::GraphKey* key, void* ws, size_t ws_bytes, void* stream, Eager&& eager, Body&& body) {
+    auto run = [&](bool captured) {
+        Ctx cx = make_ctx(s->e, s->B, ws, ws_bytes, stream);
+        return body(cx, captured) ? 1 : 0;
+    };
+    if (!key || !s->graph_on || s->e->profiling) return run(false);
+    hipStream_t st = (hipStream_t)stream;
+    auto launch = [&](hipGraphExec_t exec) {
+        hipError_t er = eager(st);
+        if (er == hipSuccess) er = hipGraphLaunch(exec, st);
+        if (er != hipSuccess) { fail(std::string("the graph launch of a push failed: ") + hipGetErrorString(er)); return 2; }
+        return 0;
+    };
+    const unsigned long long tick = ++s->graph_tick;
+    for (Session::Graph& g : s->graphs)
+        if (g.key == *key) {
+            g.used = tick;
+            if (const int rc = launch(g.exec)) return rc;
+            ++s->graph_counts[0];
+            return 0;
+        }
+    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+        (void)hipGetLastError();
+        ++s->graph_counts[3];
+        return run(false);
+    }
+    const int err = run(true);
+    hipGraph_t graph = nullptr;
+    const hipError_t ec = hipStreamEndCapture(st, &graph);
+    hipGraphExec_t exec = nullptr;
+    if (!err && ec == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
+    if (graph) (void)hipGraphDestroy(graph);
+    if (err) return 1;                                  // a launch failed while capturing: a failed push, nothing is stored
+    if (!exec) {
+        (void)hipGetLastError();
+        ++s->graph_counts[3];
+        return run(false);
+    }
+    if (const int rc = launch(exec)) { (void)hipGraphExecDestroy(exec); return rc; }
+    if (s->graphs.size() >= Session::kMaxGraphs) {
+        auto lru = std::min_element(s->graphs.begin(), s->graphs.end(), [](const Session::Graph& a, const Session::Graph& b) { return a.used < b.used; });
+        (void)hipGraphExecDestroy(lru->exec);
+        s->graphs.erase(lru);
+        ++s->graph_counts[2];
+    }
+    Session::Graph g;
+    g.key = *key; g.exec = exec; g.used = tick;
+    s->graphs.push_back(g);
+    ++s->graph_counts[1];
+    return 0;
+}
+const auto no_eager_part = [](hipStream_t) { return hipSuccess; };
+
+int session_set_graph(Session* s, int on) {
+    s->graph_on = on && session_graph_allowed();
+    if (!s->graph_on) s->drop_graphs();
+    return 0;
+}
+int session_graph_counts(const Session* s, int64_t* out) {
+    if (!s || !out) return fail("null argument");
+    std::copy(s->graph_counts, s->graph_counts + 4, out);
+    return 0;
+}
+
+// A decode push of either form (`in`: codes or embeddings): enqueued whole, or the session is broken.  The first push of an utterance
+// stages reflections and is a one-off; every later one is a steady push that a session with graph replay captures and replays.
+int stream_decode_push(fc_stream* S, int form, const void* in, int Tfc, int use_scale, float* wav, float* emb_out, void* ws, size_t ws_bytes, void* stream) {
+    const Session::GraphKey key = graph_key(*S, form, Tfc, S->dec_pushes, use_scale, {in, wav, emb_out}, ws, ws_bytes, stream);
+    const int rc = session_push(S, S->dec_pushes > 0 ? &key : nullptr, ws, ws_bytes, stream, no_eager_part, [&](Ctx& cx, bool) {
+        const float* z = form == kFormDecodeCodes ? decoder_input_codes(S->e, cx, (const int64_t*)in, Tfc, S->n_q, emb_out, nullptr)      // the lookup is per frame: nothing to carry
+                                                  : decoder_input_emb(S->e, cx, (const float*)in, Tfc);
+        if (cx.err) return 1;                           // nothing of the state has been written yet
+        S->broken = true;
+        if (stream_decode_pass(S, cx, S->dec_pushes, z, Tfc, use_scale, wav)) return 1;
+        S->broken = false;
+        return 0;
+    });
+    if (rc == 2) S->broken = true;
+    if (rc) return 1;
     S->dec_pushes++;
     S->dec_frames += Tfc;
     return 0;
@@ -2388,28 +2525,49 @@ int slots_check(const fc_slots* Q, bool decode, const int32_t* counts, const int
     return 0;
 }
 
-// the counts and flags of a push on the device, in the workspace: ONE copy out of the session's own host buffer.
+// The counts and flags of a push on the device: ONE copy out of the session's own host buffer to the HEAD of the workspace.  The table
+// is the place a fresh context's first allocation gets (slots_table), so its address depends on the workspace pointer alone: a captured
+// push reads it where the copy in front of every replay writes it (slots_upload), and slots_pass refuses any other order of allocation.
 // Q->push is pageable memory that the next push overwrites.  That is correct because the runtime stages a pageable host-to-device copy
 // before hipMemcpyAsync returns (the call is synchronous with respect to the host buffer, as for fc_stream_reset's ones); the price is
 // that the host waits there instead of queueing the next push behind this one.  A push is synchronised by its caller anyway (the wrapper
-// slices its outputs per slot), so a pinned ring that lets pushes queue is left to the HIP-graph work.
-Pass slots_pass(fc_slots* Q, Ctx& cx, bool decode, const int32_t* counts, const int32_t* flags) {
+// slices its outputs per slot).  The copy is never part of a captured graph: a capture takes no copy from pageable host memory.
+size_t slots_table_words(const fc_slots* Q) { return (size_t)(Q->max_frames > 0 ? 3 : 2) * Q->B; }      // with a cache the rows' positions travel behind the flags
+int32_t* slots_table(void* workspace) { return (int32_t*)((char*)workspace + Ctx().off); }
+
+// the host side of the copy: counts, flags and, with a cache, the positions of the push (a START row's is 0) in Q->push
+void slots_fill(fc_slots* Q, bool decode, const int32_t* counts, const int32_t* flags) {
+    const int S = Q->B;
+    std::copy(counts, counts + S, Q->push.begin());
+    std::copy(flags, flags + S, Q->push.begin() + S);
+    const std::vector<int32_t>& frames = decode ? Q->dec_frames : Q->enc_frames;
+    for (int b = 0; Q->max_frames > 0 && b < S; ++b) Q->push[2 * S + b] = (flags[b] & FC_SLOT_START) ? 0 : frames[b];
+}
+
+// the copy in front of a captured or replayed push.  A workspace too small for the table takes no copy: the pass fails at its first allocation.
+hipError_t slots_upload(fc_slots* Q, bool decode, const int32_t* counts, const int32_t* flags, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const size_t bytes = slots_table_words(Q) * sizeof(int32_t);
+    if (!workspace || Ctx().off + bytes + Ctx::kTailSlack > workspace_bytes) return hipSuccess;
+    slots_fill(Q, decode, counts, flags);
+    return hipMemcpyAsync(slots_table(workspace), Q->push.data(), bytes, hipMemcpyHostToDevice, st);
+}
+
+// upload: the pass enqueues the copy itself (an eager push); a captured pass leaves it to slots_upload
+Pass slots_pass(fc_slots* Q, Ctx& cx, bool decode, const int32_t* counts, const int32_t* flags, bool upload = true) {
     const int S = cx.B;
     Pass p;
-    p.kind = Pass::Slots; p.sess = Q; p.n = decode ? Q->dec_pushes : Q->enc_pushes; p.frame_div = 1;
-    const bool cached = Q->max_frames > 0;               // then the rows' cache positions travel behind the flags
-    const size_t words = (size_t)(cached ? 3 : 2) * S;
+    p.kind = Pass::Slots; p.sess = Q; p.n = decode ? Q->dec_pushes : Q->enc_pushes; p.frame_div = 1; p.graphed = !upload;
+    const bool cached = Q->max_frames > 0;
+    const size_t words = slots_table_words(Q);
     int32_t* dev = cx.alloc<int32_t>(words);
+    if (!cx.dry && dev && dev != slots_table(cx.base)) cx.fail("internal: the table of a slot push is not the first allocation of its pass");
     p.lengths = dev; p.flags = at(dev, S);
     if (cached) p.pos = at(dev, 2 * S);
     if (!cx.dry) {
-        std::copy(counts, counts + S, Q->push.begin());
-        std::copy(flags, flags + S, Q->push.begin() + S);
-        const std::vector<int32_t>& frames = decode ? Q->dec_frames : Q->enc_frames;
-        for (int b = 0; cached && b < S; ++b) Q->push[2 * S + b] = (flags[b] & FC_SLOT_START) ? 0 : frames[b];
+        slots_fill(Q, decode, counts, flags);
         p.host_push = Q->push.data();
     }
-    cx.launch("copy", "slot counts", [&] { return hipMemcpyAsync(dev, Q->push.data(), words * sizeof(int32_t), hipMemcpyHostToDevice, cx.st); });
+    if (upload) cx.launch("copy", "slot counts", [&] { return hipMemcpyAsync(dev, Q->push.data(), words * sizeof(int32_t), hipMemcpyHostToDevice, cx.st); });
     return p;
 }
 
@@ -2424,9 +2582,9 @@ void slots_start(fc_slots* Q, Ctx& cx, const Pass& p, bool decode, const float* 
 }
 
 int slots_encode_pass(fc_slots* Q, Ctx& cx, const float* wav, int Tc, const int32_t* counts, const int32_t* flags, const float* scale, int64_t* codes,
-                      float* quantized, float* enc_out) {
+                      float* quantized, float* enc_out, bool captured = false) {
     fc_engine* e = Q->e;
-    const Pass p = slots_pass(Q, cx, false, counts, flags);
+    const Pass p = slots_pass(Q, cx, false, counts, flags, !captured);
     slots_start(Q, cx, p, false, scale);
     fc::Src s; s.ptr = wav; s.div = Q->state; s.used = 3;       // the slots' scale [S]
     Act last = run_encoder(e, cx, p, s, Tc);
@@ -3370,6 +3528,16 @@ void fc_stream_destroy(fc_stream* s) { delete s; }
 
 int fc_stream_min_first(const fc_stream* s, int decode) { return s ? (decode ? s->dec_min_first : s->enc_min_first) : 0; }
 
+int fc_graphstream_set(fc_stream* S, int on) {
+    if (!S) return fail("null stream");
+    if (on && S->max_frames > 0)
+        return fail("graph replay is not available for a lock-step session opened with max_frames: its key / value cache position is a launch argument that "
+                    "changes with every push; a slot session opened with max_frames reads every row's position from device memory and replays");
+    return session_set_graph(S, on);
+}
+int fc_graphstream_enabled(const fc_stream* S) { return S && S->graph_on ? 1 : 0; }
+int fc_graphstream_counts(const fc_stream* S, int64_t counts[4]) { return session_graph_counts(S, counts); }
+
 size_t fc_stream_workspace_bytes(const fc_stream* S) {
     if (!S) return 0;
     const int Tf = ceil_div_i(S->max_chunk, total_hop(S->e));
@@ -3411,9 +3579,12 @@ int fc_stream_encode(fc_stream* S, const float* wav, int Tc, int final, int64_t*
     const int Tfc = final ? frames_for(e, Tc) : Tc / hop;
     if (frames_fit(S, false, Tfc)) return 1;
     if (row_nq_check(e, S->B, S->n_q)) return 1;
-    Ctx cx = make_ctx(e, S->B, workspace, workspace_bytes, stream);
+    // the first push of an utterance (reflection staging) and the final one (extra padding) are one-offs: never cached
+    const Session::GraphKey key = graph_key(*S, kFormEncode, Tc, S->enc_pushes, 0, {wav, codes, quantized, enc_out}, workspace, workspace_bytes, stream);
     S->broken = true;                                   // until the whole push is enqueued: a failure in between leaves mixed carries
-    if (stream_encode_pass(S, cx, S->enc_pushes, wav, Tc, final != 0, codes, quantized, enc_out)) return 1;
+    if (session_push(S, S->enc_pushes > 0 && !final ? &key : nullptr, workspace, workspace_bytes, stream, no_eager_part,
+                     [&](Ctx& cx, bool) { return stream_encode_pass(S, cx, S->enc_pushes, wav, Tc, final != 0, codes, quantized, enc_out); }))
+        return 1;
     S->broken = false;
     *n_frames = Tfc;
     S->enc_pushes++;
@@ -3426,8 +3597,7 @@ int fc_stream_decode_emb(fc_stream* S, const float* emb, int Tfc, int use_scale,
     if (stream_ready(S)) return 1;
     if (!emb || !wav) return fail("bad argument");
     if (stream_decode_check(S, Tfc)) return 1;
-    Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
-    return stream_decode_push(S, cx, decoder_input_emb(S->e, cx, emb, Tfc), Tfc, use_scale, wav);
+    return stream_decode_push(S, kFormDecodeEmb, emb, Tfc, use_scale, wav, nullptr, workspace, workspace_bytes, stream);
 }
 
 int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_scale, float* wav, float* emb_out, void* workspace,
@@ -3436,9 +3606,7 @@ int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_
     if (!codes || !wav) return fail("bad argument");
     if (stream_decode_check(S, Tfc)) return 1;
     if (row_nq_check(S->e, S->B, S->n_q)) return 1;
-    Ctx cx = make_ctx(S->e, S->B, workspace, workspace_bytes, stream);
-    // the lookup is per frame: nothing to carry
-    return stream_decode_push(S, cx, decoder_input_codes(S->e, cx, codes, Tfc, S->n_q, emb_out, nullptr), Tfc, use_scale, wav);
+    return stream_decode_push(S, kFormDecodeCodes, codes, Tfc, use_scale, wav, emb_out, workspace, workspace_bytes, stream);
 }
 
 // Test hook: the SLSTM stage of a push alone, continuing the recurrence the session's encoder (decoder = 0) or decoder (decoder = 1)
@@ -3516,6 +3684,10 @@ void fc_slots_destroy(fc_slots* s) { delete s; }
 
 int fc_slots_min_first(const fc_slots* s, int decode) { return s ? (decode ? s->dec_min_first : s->enc_min_first) : 0; }
 
+int fc_graphslots_set(fc_slots* Q, int on) { return Q ? session_set_graph(Q, on) : fail("null slot session"); }
+int fc_graphslots_enabled(const fc_slots* Q) { return Q && Q->graph_on ? 1 : 0; }
+int fc_graphslots_counts(const fc_slots* Q, int64_t counts[4]) { return session_graph_counts(Q, counts); }
+
 size_t fc_slots_workspace_bytes(const fc_slots* cq) {
     fc_slots* Q = const_cast<fc_slots*>(cq);
     if (!Q) return 0;
@@ -3538,10 +3710,12 @@ int fc_slots_encode(fc_slots* Q, const float* wav, int Tc, const int32_t* sample
     if (!wav || !samples || !flags || !codes) return fail("bad argument");
     if (slots_check(Q, false, samples, flags, Tc, Q->max_chunk)) return 1;
     if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
-    Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
-    const int err = slots_encode_pass(Q, cx, wav, Tc, samples, flags, scale, codes, quantized, enc_out);
+    const Session::GraphKey key = graph_key(*Q, kFormEncode, Tc, Q->enc_pushes, 0, {wav, codes, quantized, enc_out, scale}, workspace, workspace_bytes, stream);
+    const int err = session_push(
+        Q, &key, workspace, workspace_bytes, stream, [&](hipStream_t st) { return slots_upload(Q, false, samples, flags, workspace, workspace_bytes, st); },
+        [&](Ctx& cx, bool captured) { return slots_encode_pass(Q, cx, wav, Tc, samples, flags, scale, codes, quantized, enc_out, captured); });
     slots_commit(Q, false, samples, flags, !err);
-    return err;
+    return err ? 1 : 0;
 }
 
 int fc_slots_decode_emb(fc_slots* Q, const float* emb, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
@@ -3549,11 +3723,15 @@ int fc_slots_decode_emb(fc_slots* Q, const float* emb, int Tfc, const int32_t* f
     if (slots_ready(Q)) return 1;
     if (!emb || !frames || !flags || !wav) return fail("bad argument");
     if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->max_chunk, total_hop(Q->e)))) return 1;
-    Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
-    const Pass p = slots_pass(Q, cx, true, frames, flags);
-    const int err = slots_decode_pass(Q, cx, p, decoder_input_emb(Q->e, cx, emb, Tfc), Tfc, use_scale, wav);
+    const Session::GraphKey key = graph_key(*Q, kFormDecodeEmb, Tfc, Q->dec_pushes, use_scale, {emb, wav}, workspace, workspace_bytes, stream);
+    const int err = session_push(
+        Q, &key, workspace, workspace_bytes, stream, [&](hipStream_t st) { return slots_upload(Q, true, frames, flags, workspace, workspace_bytes, st); },
+        [&](Ctx& cx, bool captured) {
+            const Pass p = slots_pass(Q, cx, true, frames, flags, !captured);
+            return slots_decode_pass(Q, cx, p, decoder_input_emb(Q->e, cx, emb, Tfc), Tfc, use_scale, wav);
+        });
     slots_commit(Q, true, frames, flags, !err);
-    return err;
+    return err ? 1 : 0;
 }
 
 int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int32_t* frames, const int32_t* flags, int use_scale, float* wav,
@@ -3562,12 +3740,16 @@ int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int3
     if (!codes || !frames || !flags || !wav) return fail("bad argument");
     if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->max_chunk, total_hop(Q->e)))) return 1;
     if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
-    Ctx cx = make_ctx(Q->e, Q->B, workspace, workspace_bytes, stream);
-    const Pass p = slots_pass(Q, cx, true, frames, flags);
-    fc::RagLen rows; rows.lens = p.lengths;
-    const int err = slots_decode_pass(Q, cx, p, decoder_input_codes(Q->e, cx, codes, Tfc, Q->n_q, emb_out, &rows), Tfc, use_scale, wav);
+    const Session::GraphKey key = graph_key(*Q, kFormDecodeCodes, Tfc, Q->dec_pushes, use_scale, {codes, wav, emb_out}, workspace, workspace_bytes, stream);
+    const int err = session_push(
+        Q, &key, workspace, workspace_bytes, stream, [&](hipStream_t st) { return slots_upload(Q, true, frames, flags, workspace, workspace_bytes, st); },
+        [&](Ctx& cx, bool captured) {
+            const Pass p = slots_pass(Q, cx, true, frames, flags, !captured);
+            fc::RagLen rows; rows.lens = p.lengths;
+            return slots_decode_pass(Q, cx, p, decoder_input_codes(Q->e, cx, codes, Tfc, Q->n_q, emb_out, &rows), Tfc, use_scale, wav);
+        });
     slots_commit(Q, true, frames, flags, !err);
-    return err;
+    return err ? 1 : 0;
 }
 
 // Test hook: the SLSTM stage of a slot push alone: the rows with start[b] != 0 begin from zeros, row b takes steps[b] <= T steps.

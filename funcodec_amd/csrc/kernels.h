@@ -31,6 +31,7 @@ inline int ab_knob(const char* name, int dflt) {
 //   FC_ROW=0            element staging for the stride-1 conv layers too
 //   FC_TARGET_WGS=<n>   workgroups a conv launch aims for (default 2 per CU)
 //   FC_LAURA_PERSIST=0 / FC_LAURA_GRAPH=0   LauraTTS decoding step as the kernel chain / without the HIP graph (laura.hip)
+//   FC_SESSION_GRAPH=0  sessions asked to replay their pushes as HIP graphs stay eager (engine.hip session_push; tests/test_session_graph_gpu.py)
 // Test hooks (change behaviour on purpose, documented where they are read): FC_ABLATE_LSTM=64, FC_LAURA_PERSIST_TEST=timeout.
 // Diagnostics (print / dump only): FC_DUMP_PLAN, FC_LAURA_TRACE.
 inline int deploy_switch(const char* name, int dflt) {

@@ -44,23 +44,26 @@ class EncodecMI355X:
         self.engine.load_state_dict(state)
 
     def open_stream(self, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None, max_chunk: Optional[int] = None,
-                    max_frames: Optional[int] = None):
+                    max_frames: Optional[int] = None, graph: bool = False):
         """A streaming encode / decode session for `batch` utterances of a causal checkpoint (funcodec_amd/stream.py CodecStream):
         n_q quantisers (default: all; a list of `batch` counts gives every utterance its own, and ``set_n_q`` changes them between
         pushes), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call.  A causal net whose bottleneck is
         a transformer (seq_model: transformer) needs max_frames, the most frames one utterance may hold per side: the size of the
-        session's key / value cache.  Any other net is refused with it."""
+        session's key / value cache.  Any other net is refused with it.  graph=True: steady pushes are replayed as captured HIP graphs
+        from fixed buffers of the session, and what a push returns are copies (CodecStream, "Graph replay"); refused with max_frames."""
         from .stream import CodecStream
-        return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames)
+        return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames, graph=graph)
 
-    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
+    def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
+                   graph: bool = False):
         """A slot session of a causal checkpoint (funcodec_amd/stream.py StreamSlots): `slots` independent utterances that start, push
         and end at their own times and share every push of the batch; n_q quantisers at the most (default: all; ``start(slot, n_q=)`` and
         ``set_n_q(slot, n_q)`` give a slot fewer, at any time between pushes), at most max_chunk samples per call.  As for
         ``open_stream``, a net whose bottleneck is a transformer needs max_frames, the most frames one slot's utterance may hold per
-        side (every slot has its own key / value cache and its own position in it); any other net is refused with it."""
+        side (every slot has its own key / value cache and its own position in it); any other net is refused with it.  graph=True: pushes
+        are replayed as captured HIP graphs from fixed buffers of the session, and what a push returns are copies (StreamSlots)."""
         from .stream import StreamSlots
-        return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames)
+        return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames, graph=graph)
 
     # -- helpers -------------------------------------------------------------------------------
     def _as_bct(self, speech: torch.Tensor) -> torch.Tensor:

@@ -49,6 +49,49 @@ def stream_refusal(arch, max_frames: Optional[int] = None) -> Optional[str]:
 
 FC_SLOT_START, FC_SLOT_FINAL = 1, 2
 
+#: fc_graphstream_set's own wording for a lock-step session with a key / value cache (raised here before anything is opened)
+GRAPH_MAX_FRAMES_REFUSAL = ("graph replay is not available for a lock-step session opened with max_frames: its key / value cache position is a "
+                            "launch argument that changes with every push; a slot session opened with max_frames reads every row's position "
+                            "from device memory and replays")
+
+
+class _GraphBuffers:
+    """What a session opened with ``graph=True`` owns so that the pointers of its pushes, which are part of the key of a captured push,
+    repeat from push to push: one flat device buffer per argument, sized once for ``max_chunk`` and viewed from its base in the shape
+    of the push (the pointer does not move with the push's width), its own workspace, and its own stream (the default stream cannot
+    be captured).  The caching allocator gives no such promise for tensors allocated per push."""
+
+    def __init__(self, sess, rows: int):
+        eng, arch, dev = sess.engine, sess.arch, sess.device
+        ch, D, n_q = eng.channels, arch.dimension, sess.n_q
+        tf_enc = eng.frames(sess.max_chunk)                 # a FINAL encode push rounds up at every stride
+        tf_dec = -(-sess.max_chunk // sess.hop)
+        f32, i64 = torch.float32, torch.int64
+        sizes = {"wav_in": (rows * ch * sess.max_chunk, f32), "codes": (n_q * rows * tf_enc, i64), "quantized": (rows * tf_enc * D, f32),
+                 "enc_out": (rows * tf_enc * D, f32), "tokens": (rows * tf_dec * n_q, i64), "emb": (rows * tf_dec * D, f32),
+                 "wav_out": (rows * ch * tf_dec * sess.hop, f32), "scale": (rows, f32)}
+        self._flat = {k: torch.zeros(n, dtype=dt, device=dev) for k, (n, dt) in sizes.items()}
+        self.ws = torch.empty(sess._ws_bytes, dtype=torch.uint8, device=dev)
+        self.stream = torch.cuda.Stream(device=dev)
+        self.device = dev
+
+    def view(self, name: str, shape) -> torch.Tensor:
+        n = 1
+        for v in shape:
+            n *= int(v)
+        return self._flat[name][:n].view(*shape)
+
+    @contextlib.contextmanager
+    def on_stream(self):
+        """the push itself runs on the session's stream, ordered behind and in front of the caller's current stream"""
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        try:
+            with torch.cuda.stream(self.stream):
+                yield
+        finally:
+            cur.wait_stream(self.stream)
+
 
 class _Side:
     """what a wrapper keeps per utterance and side (encode / decode)"""
@@ -63,11 +106,14 @@ class _Session:
     its state and sizes, and the start-up and splitting rule of an utterance."""
     _family = ""
     _cached_family = ""       # the pair that sizes and creates the kind's session with a key / value cache (max_frames)
+    _graph_family = ""        # the three calls of the kind's graph replay (set, enabled, counts)
 
-    def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None):
+    def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None, graph: bool = False):
         why = stream_refusal(model.arch, max_frames)
         if why:
             raise EngineError(why)
+        if graph and max_frames is not None and self._family == "fc_stream":
+            raise EngineError(GRAPH_MAX_FRAMES_REFUSAL)
         self.model, self.engine, self.arch = model, model.engine, model.arch
         eng = self.engine
         self.lib, self.device = eng.lib, eng.device
@@ -79,10 +125,18 @@ class _Session:
         self._h = None
         #: the most frames an utterance may hold per side (a causal transformer net: the size of its key / value cache), or None
         self.max_frames = int(max_frames) if max_frames is not None else None
+        #: True while the library replays this session's steady pushes as captured HIP graphs (False with FC_SESSION_GRAPH=0)
+        self.graph = False
+        self._g: Optional[_GraphBuffers] = None         # the fixed buffers of a session opened with graph=True; None: nothing of it exists
         self._open(rows, max_chunk)
+        if graph:
+            self._graph_open(rows)
 
     def _fn(self, name: str):
         return getattr(self.lib, f"{self._family}_{name}")
+
+    def _graph_fn(self, name: str):
+        return getattr(self.lib, f"{self._graph_family}_{name}")
 
     @_on_device
     def _open(self, rows, max_chunk):
@@ -106,6 +160,41 @@ class _Session:
         self.min_first_samples = int(self._fn("min_first")(h, 0))
         self.min_first_frames = int(self._fn("min_first")(h, 1))
         self._ws_bytes = int(self._fn("workspace_bytes")(h))
+
+    @_on_device
+    def _graph_open(self, rows):
+        self.engine._check(self._graph_fn("set")(self._h, 1))
+        self.graph = bool(self._graph_fn("enabled")(self._h))
+        self._g = _GraphBuffers(self, rows)
+
+    def graph_stats(self) -> Dict[str, int]:
+        """{replays, captures, evictions, fallbacks} of this session's pushes since it was opened (all 0 without ``graph=True``):
+        pushes replayed from a cached graph, pushes captured (a new key), cached graphs evicted (16 are kept), and pushes that ran
+        eagerly because their capture could not be made."""
+        out = (C.c_int64 * 4)()
+        self._graph_fn("counts")(self._h, out)
+        return dict(zip(("replays", "captures", "evictions", "fallbacks"), (int(v) for v in out)))
+
+    # A push's tensors.  Without graph=True: allocated per push and returned as they are.  With it: views of the session's fixed
+    # buffers, the push on the session's own stream and workspace, and what is returned are copies (the next push overwrites the buffers).
+    def _buf(self, name: str, shape, dtype) -> torch.Tensor:
+        return torch.empty(shape, dtype=dtype, device=self.device) if self._g is None else self._g.view(name, shape)
+
+    def _given(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        if self._g is None:
+            return x
+        buf = self._g.view(name, x.shape)
+        buf.copy_(x)
+        return buf
+
+    def _out(self, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        return t if self._g is None or t is None else t.clone()
+
+    def _push_ws(self) -> torch.Tensor:
+        return self._ws() if self._g is None else self._g.ws
+
+    def _push_stream(self):
+        return contextlib.nullcontext() if self._g is None else self._g.on_stream()
 
     def __del__(self):
         try:
@@ -203,19 +292,28 @@ class CodecStream(_Session):
     and values of every block (fc_seqstream_create) and needs their size: ``max_frames``, the most frames one utterance may hold per side.
     A call whose frames would pass it raises before anything is pushed and changes nothing; ``reset`` starts the next utterance.  Without
     ``max_frames`` such a net is refused, with it any other net is.
+
+    Graph replay (``graph=True``, off by default).  The library captures a steady push (neither the first of an utterance nor the
+    final one) as a HIP graph and replays it for every later push with the same key: call form, width, parity of the side's push
+    count, n_q, use_scale and every pointer.  The session therefore owns fixed device buffers sized for ``max_chunk``, a workspace and a
+    stream of its own, copies what it is given into them, and RETURNS COPIES of the results, because the next push overwrites the
+    buffers.  The results are the eager session's bits.  ``graph_stats()`` counts replays, captures, evictions and fallbacks;
+    ``FC_SESSION_GRAPH=0`` in the environment keeps such a session eager.  Not available together with ``max_frames`` (the cache position
+    of a lock-step session is a launch argument): ``open_slots(..., max_frames=N, graph=True)`` is.
     """
 
     _family = "fc_stream"
     _cached_family = "fc_seqstream"
+    _graph_family = "fc_graphstream"
 
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
-                 max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
+                 max_chunk: Optional[int] = None, max_frames: Optional[int] = None, graph: bool = False):
         self.batch = int(batch)
         rows = None
         if n_q is not None and not isinstance(n_q, numbers.Integral):       # a count per utterance: refused before anything is opened
             rows = row_nq_list(model.arch, n_q, self.batch)
             n_q = max(rows)
-        super().__init__(model, self.batch, n_q, max_chunk, max_frames)
+        super().__init__(model, self.batch, n_q, max_chunk, max_frames, graph)
         self._row_nq = rows
         self.reset(scale)
 
@@ -237,15 +335,17 @@ class CodecStream(_Session):
     def _encode_call(self, wav: torch.Tensor, final: bool, want_enc_out: bool = False):
         B, T = wav.shape[0], wav.shape[-1]
         Tf, D = self.engine.frames(T), self.arch.dimension
-        codes = torch.empty((self.n_q, B, Tf), dtype=torch.int64, device=self.device)
-        quant = torch.empty((B, Tf, D), dtype=torch.float32, device=self.device)
-        enc = torch.empty((B, Tf, D), dtype=torch.float32, device=self.device) if (self.arch.bypass_quantizer or want_enc_out) else None
+        wav = self._given("wav_in", wav)
+        codes = self._buf("codes", (self.n_q, B, Tf), torch.int64)
+        quant = self._buf("quantized", (B, Tf, D), torch.float32)
+        enc = self._buf("enc_out", (B, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
         n = C.c_int(0)
-        ws = self._ws()
-        with self._engine_row_nq(self._push_row_nq()):
+        ws = self._push_ws()
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()):
             self.engine._check(self.lib.fc_stream_encode(self._h, _ptr(wav), T, int(final), _ptr(codes), _ptr(quant), _ptr(enc), C.byref(n),
                                                          _ptr(ws), ws.numel(), self.engine._stream()))
         assert n.value == Tf
+        codes, quant, enc = self._out(codes), self._out(quant), self._out(enc)
         if self.arch.bypass_quantizer:         # codec_basic.py:700-701: the encoder output in place of the quantised embeddings
             return torch.zeros((B, Tf), dtype=torch.long, device=self.device), enc, enc
         return codes, quant, enc
@@ -281,6 +381,7 @@ class CodecStream(_Session):
 
     # -- decode --------------------------------------------------------------------------------
     def _decode_pushes(self, x: torch.Tensor, final: bool, call, rows_apply: bool = False) -> torch.Tensor:
+        name = "tokens" if x.dtype == torch.int64 else "emb"
         if x.shape[0] != self.batch:
             raise EngineError(f"this session streams {self.batch} utterances, got {x.shape[0]}")
         pieces, head = self._take(self._dec, x, final, 1, 1, self.min_first_frames, lambda have: EngineError(
@@ -295,12 +396,12 @@ class CodecStream(_Session):
         self._dec.frames += frames
         outs = []
         for part, _ in pieces:
-            part = part.contiguous()
-            wav = torch.empty((self.batch, self.engine.channels, part.shape[1] * self.hop), dtype=torch.float32, device=self.device)
-            ws = self._ws()
-            with self._engine_row_nq(self._push_row_nq() if rows_apply else None):
+            part = self._given(name, part.contiguous())
+            wav = self._buf("wav_out", (self.batch, self.engine.channels, part.shape[1] * self.hop), torch.float32)
+            ws = self._push_ws()
+            with self._push_stream(), self._engine_row_nq(self._push_row_nq() if rows_apply else None):
                 self.engine._check(call(part, wav, ws))
-            outs.append(wav)
+            outs.append(self._out(wav))
         return outs[0] if len(outs) == 1 else torch.cat(outs, -1)
 
     @_on_device
@@ -373,15 +474,22 @@ class StreamSlots(_Session):
     one slot's utterance may hold per side (fc_seqslots_create): every slot has its own key / value cache and its own position in it,
     which ``start`` puts back to 0.  A call that would take a slot past the bound raises before anything is pushed, names the slot and
     changes nothing; ``start(slot)`` begins its next utterance.  Without ``max_frames`` such a net is refused, with it any other net is.
+
+    Graph replay (``graph=True``, off by default).  As for ``CodecStream``: every push of a slot session is a steady one (START, FINAL and
+    idle rows are data in device memory, copied in front of the replay), so every push replays once its key -- form, width, parity, n_q,
+    use_scale, pointers -- has been captured.  The session owns fixed buffers, a workspace and a stream, and what ``encode`` / ``decode``
+    RETURN ARE COPIES: the next push overwrites the buffers.  With ``max_frames`` too (every row's cache position is read on the device).
     """
 
     _family = "fc_slots"
     _cached_family = "fc_seqslots"
+    _graph_family = "fc_graphslots"
 
-    def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None):
+    def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
+                 graph: bool = False):
         self.slots = int(slots)
         self.pad_value = 0.0          # what the assembled batch holds behind a row's count and in idle rows (never read; a test aid)
-        super().__init__(model, self.slots, n_q, max_chunk, max_frames)
+        super().__init__(model, self.slots, n_q, max_chunk, max_frames, graph)
         self._enc = [_Side() for _ in range(self.slots)]
         self._dec = [_Side() for _ in range(self.slots)]
         self._scale = [1.0] * self.slots
@@ -470,31 +578,34 @@ class StreamSlots(_Session):
         counts, flags = self._counts(rows, lambda w: w.shape[-1])
         Tc = max(counts)
         Tf = self.engine.frames(Tc)
-        wav = torch.full((S, ch, Tc), self.pad_value, dtype=torch.float32, device=self.device)
+        wav = self._buf("wav_in", (S, ch, Tc), torch.float32).fill_(self.pad_value)
         scale = None
         for slot, (w, f) in rows.items():
             wav[slot, :, :w.shape[-1]] = w
             if f & FC_SLOT_START and scale is None:
                 scale = torch.ones(S, dtype=torch.float32)
+        if scale is None and self._g is not None:
+            scale = torch.ones(S, dtype=torch.float32)         # one pointer whether a row STARTs or not (it is read for START rows only): one key
         if scale is not None:
             for slot, (w, f) in rows.items():
                 if f & FC_SLOT_START:
                     scale[slot] = self._scale[slot]
-            scale = scale.to(self.device)
-        codes = torch.empty((self.n_q, S, Tf), dtype=torch.int64, device=self.device)
-        quant = torch.empty((S, Tf, D), dtype=torch.float32, device=self.device)
-        enc = torch.empty((S, Tf, D), dtype=torch.float32, device=self.device) if (self.arch.bypass_quantizer or want_enc_out) else None
-        ws = self._ws()
-        with self._engine_row_nq(self._push_row_nq()):
+            scale = self._given("scale", scale.to(self.device))
+        codes = self._buf("codes", (self.n_q, S, Tf), torch.int64)
+        quant = self._buf("quantized", (S, Tf, D), torch.float32)
+        enc = self._buf("enc_out", (S, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
+        ws = self._push_ws()
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()):
             self.engine._check(self.lib.fc_slots_encode(self._h, _ptr(wav), Tc, counts, flags, _ptr(scale), _ptr(codes), _ptr(quant), _ptr(enc),
                                                         _ptr(ws), ws.numel(), self.engine._stream()))
         out = {}
         for slot, (w, f) in rows.items():
             n = self.engine.frames(w.shape[-1]) if f & FC_SLOT_FINAL else w.shape[-1] // self.hop
             if self.arch.bypass_quantizer:     # codec_basic.py:700-701: the encoder output in place of the quantised embeddings
-                out[slot] = (torch.zeros((n,), dtype=torch.long, device=self.device), enc[slot, :n], enc[slot, :n])
+                e = self._out(enc[slot, :n])
+                out[slot] = (torch.zeros((n,), dtype=torch.long, device=self.device), e, e)
             else:
-                out[slot] = (codes[:, slot, :n], quant[slot, :n], enc[slot, :n] if enc is not None else None)
+                out[slot] = (self._out(codes[:, slot, :n]), self._out(quant[slot, :n]), self._out(enc[slot, :n]) if enc is not None else None)
         return out
 
     @_on_device
@@ -521,25 +632,27 @@ class StreamSlots(_Session):
         counts, flags = self._counts(rows, lambda t: t.shape[0])
         Tf = max(counts)
         if emb:
-            x = torch.full((S, Tf, inner), self.pad_value, dtype=torch.float32, device=self.device)
+            x = self._buf("emb", (S, Tf, inner), torch.float32).fill_(self.pad_value)
         else:
-            x = torch.zeros((S, Tf, inner), dtype=torch.int64, device=self.device)
+            x = self._buf("tokens", (S, Tf, inner), torch.int64).zero_()
         for slot, (t, f) in rows.items():
             x[slot, :t.shape[0]] = t
         starts = [slot for slot, (t, f) in rows.items() if f & FC_SLOT_START]
         if starts:      # the utterance's scale, for a slot whose encoder has not set it: the first S floats of the state (funcodec_amd.h)
             vals = torch.tensor([self._scale[slot] for slot in starts], dtype=torch.float32).to(self.device)
             self.state[:4 * S].view(torch.float32)[torch.tensor(starts, device=self.device)] = vals
-        wav = torch.empty((S, ch, Tf * self.hop), dtype=torch.float32, device=self.device)
-        ws = self._ws()
-        if emb:
-            rc = self.lib.fc_slots_decode_emb(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), _ptr(ws), ws.numel(), self.engine._stream())
-        else:
-            with self._engine_row_nq(self._push_row_nq()):
-                rc = self.lib.fc_slots_decode_codes(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(),
-                                                    self.engine._stream())
+        wav = self._buf("wav_out", (S, ch, Tf * self.hop), torch.float32)
+        ws = self._push_ws()
+        with self._push_stream():
+            if emb:
+                rc = self.lib.fc_slots_decode_emb(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), _ptr(ws), ws.numel(),
+                                                  self.engine._stream())
+            else:
+                with self._engine_row_nq(self._push_row_nq()):
+                    rc = self.lib.fc_slots_decode_codes(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(),
+                                                        self.engine._stream())
         self.engine._check(rc)
-        return {slot: (wav[slot, :, :t.shape[0] * self.hop],) for slot, (t, f) in rows.items()}
+        return {slot: (self._out(wav[slot, :, :t.shape[0] * self.hop]),) for slot, (t, f) in rows.items()}
 
     def _decode(self, pushes, use_scale, emb):
         inner, dtype = (self.arch.dimension, torch.float32) if emb else (self.n_q, torch.int64)

@@ -368,6 +368,40 @@ int  fc_seqslots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, int
 int  fc_seqslots_forward(fc_slots* s, int decoder, const float* x, int T, const int32_t* frames, const int32_t* start, float* y,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- graph replay of a session's pushes (opt-in per session, off by default) ------------------------------------------------
+ * (entry points added without a struct change: FC_ABI_VERSION stays 7; fc_graphstream_* take an fc_stream, fc_graphslots_* an fc_slots)
+ * A push is some 60 small launches.  With graph replay on, a push is enqueued as ONE hipGraphLaunch of a graph captured from the very
+ * launches the push makes without it (one stream, a linear chain); what is computed does not change.  Measured, replay saves the host's
+ * time to enqueue (about 0.16 of 0.2 ms per push) and nothing else: the device runs the same kernels one after the other.
+ * Every check of a push runs first, as ever: a refused push changes nothing.  Then the push's KEY is looked up among the session's
+ * graphs.  The key holds every host value the enqueued work depends on: the call form (encode, decode_codes, decode_emb), the width
+ * (Tc / Tfc), the parity of the side's push count, n_q, use_scale, EVERY POINTER ARGUMENT (inputs, outputs -- NULL for an absent one --,
+ * scale, workspace and its size, the stream) and whether per-row stage counts are set (fc_engine_set_row_nq), with the table's
+ * device address and width.  A hit replays; a miss captures (hipStreamCaptureModeThreadLocal on the caller's stream, which must
+ * not be the null stream), instantiates, launches and stores the graph.  So a caller whose pointers repeat from push to push -- fixed
+ * input, output and workspace buffers -- replays, two graphs per (side, form, width) in the steady state, one per parity; a caller
+ * whose pointers move captures every time, which costs more than the eager push.
+ *   - fc_stream: the first push of an utterance (reflection staging) and the final push are one-offs and run eagerly;
+ *   - fc_slots: every push qualifies.  Its one copy of counts, flags and cache positions from host memory is issued in front of
+ *     the replay, to the head of the workspace, where the captured kernels read it; with a key / value cache the attention's grid is
+ *     sized by the bound that depends on the width alone, the rows' counts and positions are read on the device;
+ *   - a session of fc_seqstream_create is REFUSED (its cache position is a launch argument that changes with every push; the message
+ *     names max_frames and points to the slot session);
+ *   - while engine profiling is live (fc_engine_profile) pushes run eagerly;
+ *   - at most 16 graphs per session, the least recently used one is evicted; all go with the session or with fc_graph*_set(s, 0);
+ *     fc_stream_reset and START keep them;
+ *   - if the stream cannot be captured or the graph not instantiated, that push runs eagerly and `fallbacks` counts it.  A launch that
+ *     fails while capturing, or a failing hipGraphLaunch, is a failed push as above (fc_stream_reset / START), and no graph is stored;
+ *   - FC_SESSION_GRAPH=0 in the environment makes fc_graph*_set(s, 1) a no-op that returns 0 and leaves the session eager
+ *     (fc_graph*_enabled then reports 0).
+ * fc_graph*_set returns non-zero with fc_last_error set when refused.  counts: {replays, captures, evictions, fallbacks} since create. */
+int  fc_graphstream_set(fc_stream* s, int on);
+int  fc_graphstream_enabled(const fc_stream* s);
+int  fc_graphstream_counts(const fc_stream* s, int64_t counts[4]);
+int  fc_graphslots_set(fc_slots* s, int on);
+int  fc_graphslots_enabled(const fc_slots* s);
+int  fc_graphslots_counts(const fc_slots* s, int64_t counts[4]);
+
 /* Deferred device-side failures.  Kernels cannot return a status, so two conditions are recorded in host-visible
  * status words and reported by the NEXT fc_* compute call on the engine (non-zero return, message in fc_last_error(),
  * condition cleared) or by this call.  *flags (may be NULL) receives the conditions pending at entry:

@@ -194,46 +194,68 @@ class Text2Audio:
     @torch.no_grad()
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
-                      step_n: int = 1):
+                      step_n: int = 1, samples: int = 1):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
-        request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed."""
-        from ..laura import drive_slots
+        request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.
+
+        samples = N > 1 draws N candidates per request (consecutive entries in arrival order; seeds [n][N], or drawn per candidate)
+        and returns one list of N per request in both return values.  A candidate whose request has another candidate running in
+        some slot is started from that slot (DecodeSlots.start_from: a copy of the prefix instead of a prefix pass); the two ways
+        give the same bits, so every candidate is what its request listed N times as N requests with the same seeds gives, and
+        which way a candidate started is purely a matter of cost."""
+        from ..laura import drive_samples
         m, nq = self.model, self.model.predict_nq
-        n = len(texts)
+        n, N = len(texts), int(samples)
+        if N < 1:
+            raise ValueError(f"generate_many: samples must be >= 1, got {samples}")
         continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
         per = None
         if continual_mode:
             texts = [" ".join([p, t]).strip() for p, t in zip(prompt_texts, texts)]
             per = self._prompt_codecs(prompt_audios)
-        seeds = [m._next_seed() for _ in range(n)] if seeds is None else [int(v) for v in seeds]
-        if len(seeds) != n:
+        if seeds is None:
+            seeds = [m._next_seed() for _ in range(n * N)]
+        elif N == 1:
+            seeds = [int(v) for v in seeds]
+        else:
+            if len(seeds) != n or any(len(row) != N for row in seeds):
+                raise ValueError(f"generate_many: seeds must be [{n}][{N}]")
+            seeds = [int(v) for row in seeds for v in row]
+        if len(seeds) != n * N:
             raise ValueError(f"generate_many: {len(seeds)} seeds for {n} requests")
-        groups = [list(range(i, min(i + 16, n))) for i in range(0, n, 16)]         # the batch forms take 16 utterances at a time
         outs, lens = [None] * n, [0] * n
         session = m.open_decode(slots, logp=False)
         try:
-            def start(slot, i):
+            def start(slot, c):
                 # a request's text is encoded when its slot is free, alone: its text_outs are those of a one-utterance call
-                to, ln = self._encode_texts([texts[i]])
-                outs[i], lens[i] = to[0, : ln[0]], ln[0]
-                session.start(slot, outs[i], lens[i], self.max_length, self.sampling, seeds[i], None if per is None else per[i])
-            taken = drive_slots(session, slots, n, start, step_n)
+                i = c // N
+                if N == 1 or outs[i] is None:
+                    to, ln = self._encode_texts([texts[i]])
+                    outs[i], lens[i] = to[0, : ln[0]], ln[0]
+                session.start(slot, outs[i], lens[i], self.max_length, self.sampling, seeds[c], None if per is None else per[i])
+
+            def start_from(slot, src, c):
+                session.start_from(slot, src, self.max_length, self.sampling, seeds[c])
+            taken = [t for row in drive_samples(session, slots, n, N, start, start_from, step_n) for t in row]
         finally:
             session.free()
         rets, codecs = [], []
-        for g in groups:                               # finished utterances, 16 at a time, through the batch forms
-            L, C = max(lens[i] for i in g), max(max(taken[i][1] for i in g), 1)
-            text_outs = torch.zeros((len(g), L, outs[g[0]].shape[-1]), dtype=torch.float32, device=m.device)
+        cands = list(range(n * N))
+        for g in (cands[i: i + 16] for i in range(0, n * N, 16)):      # finished utterances, 16 at a time, through the batch forms
+            L, C = max(lens[c // N] for c in g), max(max(taken[c][1] for c in g), 1)
+            text_outs = torch.zeros((len(g), L, outs[g[0] // N].shape[-1]), dtype=torch.float32, device=m.device)
             tokens = torch.zeros((len(g), C, nq), dtype=torch.int64, device=m.device)
-            for j, i in enumerate(g):
-                text_outs[j, : lens[i]] = outs[i]
-                tokens[j, : taken[i][1]] = taken[i][0]
-            excl = [((int(per[i].shape[0]) if self.exclude_prompt else 0) if continual_mode else None) for i in g]
-            r, c = self._synthesise(text_outs, [lens[i] for i in g], tokens, [taken[i][1] for i in g], excl)
+            for j, c in enumerate(g):
+                text_outs[j, : lens[c // N]] = outs[c // N]
+                tokens[j, : taken[c][1]] = taken[c][0]
+            excl = [((int(per[c // N].shape[0]) if self.exclude_prompt else 0) if continual_mode else None) for c in g]
+            r, cd = self._synthesise(text_outs, [lens[c // N] for c in g], tokens, [taken[c][1] for c in g], excl)
             rets += r
-            codecs += c
-        return rets, codecs
+            codecs += cd
+        if N == 1:
+            return rets, codecs
+        return [rets[i * N: (i + 1) * N] for i in range(n)], [codecs[i * N: (i + 1) * N] for i in range(n)]
 
     @staticmethod
     def from_pretrained(model_tag: Optional[str] = None, **kwargs: Optional[Any]):

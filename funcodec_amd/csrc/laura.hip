@@ -763,7 +763,9 @@ struct fc_laura_slots {
     int* tok_off = nullptr;                 // device [S]: the slot's continual prompt length
     int64_t *tokens = nullptr, *forced = nullptr;     // [S][R][nq]
     float* logp = nullptr;                  // [S][R][V] or null
+    float* lg0 = nullptr;                   // [S][V]: the logits every slot's prefix pass ended with (the step overwrites m.lg)
     std::vector<int> state, cont_len, max_len, n_gen;
+    std::vector<int> text_len, prefix;      // of the prompt a slot holds: text tokens, prefix positions P = text_len + 2 + cont_len
     hipGraphExec_t gexec = nullptr;         // the captured step, and the form it holds
     bool g_persist = false, g_timeout = false;
     bool warmed[2] = {false, false};        // one eager step run per form (sets the kernels' LDS attributes, which a capture cannot)
@@ -783,6 +785,7 @@ void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, fc_laura_s
     s.tokens = cx.alloc<int64_t>((size_t)S * R * nq);
     s.forced = cx.alloc<int64_t>((size_t)S * R * nq);
     s.logp = with_logp ? cx.alloc<float>((size_t)S * R * V) : nullptr;
+    s.lg0 = cx.alloc<float>((size_t)S * V);
 }
 
 lk::Sample slots_sampler(const fc_laura_slots* s) {
@@ -830,6 +833,9 @@ int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, i
     if (cx.dry || cx.err) return cx.err;
     cx.check(lk::launch_gather_last(h, pos, 1, d, T, m.xs + (size_t)slot * d, cx.st), "last position");
     cx.check(step_gemv(e->lm_decoder, m.xs + (size_t)slot * d, 1, nullptr, nullptr, 0.f, 0, 0, m.lg + (size_t)slot * V, V, cx.st), "decoder GEMV");
+    // kept for fc_laura_slots_start_from: the step overwrites the slot's row of m.lg
+    cx.check(hipMemcpyAsync(s->lg0 + (size_t)slot * V, m.lg + (size_t)slot * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, cx.st),
+             "prefix logits");
     lk::Sample sm = slots_sampler(s);
     sm.row0 = slot; sm.nrows = 1;
     sm.launch_seq = nullptr;               // only the full-width launch that precedes a persistent step numbers it
@@ -1120,6 +1126,7 @@ int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_lo
     slots_layout(e, cx, slots, max_positions, s->with_logp, *s);
     if (cx.err) return fail("decoding session: state allocation too small (fc_laura_slots_state_bytes)");
     s->state.assign(slots, SLOT_FREE); s->cont_len.assign(slots, 0); s->max_len.assign(slots, 0); s->n_gen.assign(slots, 0);
+    s->text_len.assign(slots, 0); s->prefix.assign(slots, 0);
     // a never-started slot: done = 1, pos = 0, a zero xs row -- it goes through every step with finite values and the sampler skips it
     const StepMem& m = s->m;
     const Stack& S = e->codec_lm;
@@ -1184,10 +1191,58 @@ int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, in
     }
     // from here on the slot's previous utterance is gone (a start on a running slot abandons it)
     s->state[slot] = SLOT_FAILED; s->n_gen[slot] = 0; s->cont_len[slot] = cont_len; s->max_len[slot] = max_length;
+    s->text_len[slot] = text_len; s->prefix[slot] = text_len + 2 + cont_len;
     s->last = (hipStream_t)stream;
     Ctx cx = make_ctx(1, workspace, workspace_bytes, stream);
     if (slots_prefix(s, cx, slot, text_outs, text_len, cont_len ? continual : nullptr, cont_len, row, forced)) return 1;
     s->state[slot] = SLOT_RUNNING;
+    return 0;
+}
+
+int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_length, int sampling_mode, int sampling_k, float sampling_p,
+                              uint64_t seed, const int64_t* forced, void* stream) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    const std::string range = " outside 0 .. " + std::to_string(s->S - 1);
+    if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + range);
+    if (src < 0 || src >= s->S) return fail("decoding session: source slot " + std::to_string(src) + range);
+    if (dst == src) return fail("decoding session: slot " + std::to_string(dst) + " cannot be started from itself");
+    if (s->state[src] != SLOT_RUNNING && s->state[src] != SLOT_DONE)
+        return fail("decoding session: source slot " + std::to_string(src) + " holds no utterance (" +
+                    (s->state[src] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+    if (max_length < 1) return fail("decoding session: bad argument for slot " + std::to_string(dst));
+    if (check_sampling(sampling_mode, sampling_k, sampling_p)) return 1;
+    const int P = s->prefix[src], cont_len = s->cont_len[src];
+    if (P + max_length > s->R)
+        return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
+                    " exceeds the session's max_positions " + std::to_string(s->R));
+    fc_laura* e = s->e;
+    const StepMem& m = s->m;
+    const int d = e->codec_lm.s.d_model, V = e->vocab(), nq = e->arch.predict_nq;
+    lk::SampleRow row{};
+    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
+    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;
+    // from here on the destination's previous utterance is gone (as a start on a running slot abandons it)
+    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = 0; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
+    s->text_len[dst] = s->text_len[src]; s->prefix[dst] = P;
+    Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
+    s->last = cx.st;
+    lk::SlotReset r;
+    r.slot = dst; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
+    r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
+    r.continual = s->tokens + (size_t)src * s->R * nq;      // the source's prompt tokens: generation never changes rows [0, cont_len)
+    r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
+    cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+    lk::PrefixCopy c;
+    c.kc = m.kc; c.vc = m.vc; c.lg = m.lg; c.lg0 = s->lg0; c.pos = m.pos;
+    c.NL = e->codec_lm.s.layers; c.S = s->S; c.d = d; c.Tcap = m.Tcap; c.V = V; c.P = P; c.src = src; c.n = 1; c.dst[0] = dst;
+    cx.check(lk::launch_prefix_copy(c, cx.st), "prefix copy");
+    lk::Sample sm = slots_sampler(s);
+    sm.row0 = dst; sm.nrows = 1;
+    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
+    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    if (cx.err) return 1;
+    s->state[dst] = SLOT_RUNNING;
     return 0;
 }
 

@@ -163,6 +163,18 @@ struct SlotReset {                  // see slot_reset_kernel
 };
 hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st);
 
+struct PrefixCopy {                 // see prefix_copy_kernel
+    float *kc = nullptr, *vc = nullptr;   // the session's caches [NL][S][d][Tcap], [NL][S][Tcap][d]
+    float* lg = nullptr;            // [S][V] logits of the step
+    float* lg0 = nullptr;           // [S][V] logits every slot's prefix ended with
+    int* pos = nullptr;             // device [S]
+    int NL = 0, S = 0, d = 0, Tcap = 0, V = 0;
+    int P = 0;                      // prefix positions (text_len + 2 + cont_len), known to the host
+    int src = 0, n = 0;             // source slot; destinations dst[0 .. n), 1 <= n <= S - 1, none of them src
+    int dst[15] = {};
+};
+hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st);
+
 hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t st);
 
 // ---- step form as ONE persistent launch (laura_persist.hip) ------------------------------------------------------------------------

@@ -1486,5 +1486,74 @@ hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The prefix of slot `src` (its first P cache positions and the logits its prefix pass ended with) into n other slots: what a prefix
+// pass of the same prompt would leave there, bit for bit, for the price of a copy.  grid.y = layer; along x a layer's K vectors, then
+// its V vectors, then one block (layer 0 only) for the logits and the positions.  Every 16-byte source vector is loaded once and stored
+// n times; a block takes FC_PREFIX_VPT x 256 consecutive vectors, its loads in flight together.
+//   K [d][Tcap]: rows of pad4(P) floats (Tcap % 4 == 0: every row start is 16-byte aligned).  Columns [P, pad4(P)) carry whatever the
+//   source holds there (its own later positions).  A destination never reads a column it did not write itself: a step writes K and V at
+//   pos before its attention reads keys 0 .. pos -- on the kernel chain the QKV GEMV's scatter is the launch ahead of attn_step_kernel, in
+//   the persistent step an attention unit waits for the whole QKV phase (wait_phase(ph - 1)) -- and the first step of a destination runs
+//   at pos = P.  (A slot reused by `start` has its previous utterance's columns there in the same way.)
+//   V [Tcap][d]: the first P * d floats, contiguous (d % 4 == 0).
+// ---------------------------------------------------------------------------------------------------------------------
+#define FC_PREFIX_VPT 4
+__global__ __launch_bounds__(256) void prefix_copy_kernel(PrefixCopy c) {
+    const int l = blockIdx.y, tid = threadIdx.x;
+    const int kq = (c.P + 3) >> 2;                                    // vectors per K row: pad4(P) / 4
+    const int nK = c.d * kq, nV = (c.P * c.d) >> 2;
+    const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
+    int blk = blockIdx.x;
+    if (blk >= bK + bV) {                                             // the logits, the saved logits, the position
+        if (l != 0) return;
+        const float* s = c.lg0 + (size_t)c.src * c.V;
+        for (int v = tid; v < c.V; v += 256) {
+            const float x = s[v];
+            for (int i = 0; i < c.n; ++i) {
+                c.lg[(size_t)c.dst[i] * c.V + v] = x;
+                c.lg0[(size_t)c.dst[i] * c.V + v] = x;
+            }
+        }
+        for (int i = 0; i < c.n; ++i)
+            if (tid == i) c.pos[c.dst[i]] = c.P;
+        return;
+    }
+    const bool isK = blk < bK;
+    if (!isK) blk -= bK;
+    const size_t row = (size_t)c.d * c.Tcap;                         // floats of one slot's row of a layer, K and V alike
+    float* base = (isK ? c.kc : c.vc) + (size_t)l * c.S * row;
+    const int nvec = isK ? nK : nV;
+    const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
+    size_t off[FC_PREFIX_VPT];
+    f32x4 v[FC_PREFIX_VPT];
+#pragma unroll
+    for (int u = 0; u < FC_PREFIX_VPT; ++u) {
+        int i = i0 + 256 * u;
+        i = i < nvec ? i : nvec - 1;                                  // clamped: unconditional loads, predicated stores
+        off[u] = isK ? (size_t)(i / kq) * c.Tcap + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+        v[u] = *(const f32x4*)(base + c.src * row + off[u]);
+    }
+    for (int k = 0; k < c.n; ++k) {
+        float* o = base + c.dst[k] * row;
+#pragma unroll
+        for (int u = 0; u < FC_PREFIX_VPT; ++u)
+            if (i0 + 256 * u < nvec) *(f32x4*)(o + off[u]) = v[u];
+    }
+}
+hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st) {
+    if (c.NL < 1 || c.S < 2 || c.n < 1 || c.n > c.S - 1 || c.n > 15 || c.src < 0 || c.src >= c.S) return hipErrorInvalidValue;
+    if (c.d < 4 || c.d % 4 || c.Tcap % 4 || c.P < 1 || ((c.P + 3) & ~3) > c.Tcap || c.V < 1) return hipErrorInvalidValue;
+    for (int i = 0; i < c.n; ++i)
+        if (c.dst[i] < 0 || c.dst[i] >= c.S || c.dst[i] == c.src) return hipErrorInvalidValue;
+    const int per = 256 * FC_PREFIX_VPT;
+    const int kq = ((c.P + 3) & ~3) >> 2;
+    const long long nK = (long long)c.d * kq, nV = ((long long)c.P * c.d) >> 2;
+    if (nK > 0x7fffffff || nV > 0x7fffffff) return hipErrorInvalidValue;
+    const int bK = (int)((nK + per - 1) / per), bV = (int)((nV + per - 1) / per);
+    hipLaunchKernelGGL(prefix_copy_kernel, dim3(bK + bV + 1, c.NL), dim3(256), 0, st, c);
+    return hipGetLastError();
+}
+
 }  // namespace laura
 }  // namespace fc

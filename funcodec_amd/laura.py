@@ -430,6 +430,37 @@ class DecodeSlots:
         self._max_length[int(slot)] = max_length
 
     @_on_device
+    def start_from(self, dst: int, src: int, max_length: Optional[int] = None, sampling: Union[bool, int, float] = True, seed: int = 0,
+                   forced: Optional[torch.Tensor] = None) -> None:
+        """The prompt that slot `src` holds (text and continual tokens) into slot `dst` with `dst`'s own max_length (default: the
+        source's), sampling, seed and forced tokens: a device copy of the source's prefix instead of a prefix pass.  `dst` is, bit for
+        bit, the slot that ``start`` gives for the same prompt and parameters; `src` is not disturbed, may be running or ended (not yet
+        taken), and may itself come from a start_from.  A running `dst` is abandoned.  A refused call changes nothing for any slot."""
+        eng, nq = self.engine, self.engine.spec.predict_nq
+        h = self._handle()
+        dst, src = int(dst), int(src)
+        if max_length is None:
+            if not 0 <= src < self.slots:
+                raise EngineError(f"decode session start_from: source slot {src} outside 0 .. {self.slots - 1}")
+            max_length = self._max_length[src]
+        max_length = int(max_length)
+        if forced is not None:
+            forced = eng._dev(forced, torch.int64)
+            if forced.dim() == 3 and forced.shape[0] == 1:
+                forced = forced[0]
+            if tuple(forced.shape) != (max_length, nq):
+                raise EngineError(f"decode session start_from: slot {dst}: forced must be int64 [{max_length}, {nq}], got {tuple(forced.shape)}")
+        mode, k, p = sampling_args(sampling)
+        cur, run = self._run_stream()
+        try:
+            eng._check(self.lib.fc_laura_slots_start_from(h, dst, src, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), _ptr(forced),
+                                                          C.c_void_p(run.cuda_stream)))
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+        self._max_length[dst] = max_length
+
+    @_on_device
     def step(self, n: int = 16) -> Dict[int, str]:
         """n decoding steps for every running slot; {slot: "running" | "done" | "failed"} for every slot that holds an utterance."""
         h = self._handle()
@@ -513,6 +544,39 @@ def drive_slots(session, slots: int, n_requests: int, start, step_n: int = 1) ->
                 failed.append(req)
         pending[:0] = sorted(failed)
     return results
+
+
+def drive_samples(session, slots: int, n_requests: int, samples: int, start, start_from, step_n: int = 1) -> list:
+    """`samples` candidates of each of n_requests requests through a session of `slots` slots: candidate number c = request * samples
+    + k, in that (arrival) order through ``drive_slots``, whose policy is unchanged.  A candidate whose request already has a candidate
+    running in some slot is started from that slot, ``start_from(slot, source_slot, c)``; otherwise ``start(slot, c)`` runs the prefix
+    pass.  The two ways give the same bits (DecodeSlots.start_from), so which one a candidate gets is purely a matter of cost, never
+    of result: a request whose candidates never overlap in time simply pays a prefix pass each.  Returns the takes, one list of
+    `samples` per request."""
+    held: Dict[int, int] = {}               # slot -> the candidate running in it (drive_slots' own `owner`, seen from the callbacks)
+
+    class _Watched:                         # the session as drive_slots uses it: a slot that stopped running holds nothing any more
+        def step(self, n):
+            status = session.step(n)
+            for slot in list(held):
+                if status.get(slot) != "running":
+                    del held[slot]
+            return status
+
+        def take(self, slot):
+            return session.take(slot)
+
+    def begin(slot, c):
+        held.pop(slot, None)
+        src = next((s for s in sorted(held) if held[s] // samples == c // samples), None)
+        if src is None:
+            start(slot, c)
+        else:
+            start_from(slot, src, c)
+        held[slot] = c
+
+    taken = drive_slots(_Watched(), slots, n_requests * samples, begin, step_n)
+    return [taken[i * samples: (i + 1) * samples] for i in range(n_requests)]
 
 
 class LauraGenMI355X:

@@ -702,6 +702,18 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
  *   tokens dev i64 [cap][predict_nq]: prompt tokens followed by the generated ones;  len_out host: their number
  *   logp_out dev f32 [max_length][vocab] or NULL: what every step sampled from (zero rows past the last step) */
 int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, int32_t* len_out, float* logp_out);
+/* The head of decode_codec (laura_model.py:501-548) for the prompt that slot `src` already holds, into slot `dst`: no prefix pass.  One
+ * device copy of the source's prefix -- its first text_len + 2 + cont_len key / value positions in every layer and the logits its own
+ * prefix pass ended with, which the session keeps per slot -- then the first sample with `dst`'s own parameters.  The result is, bit
+ * for bit, the slot that fc_laura_slots_start gives for the same text, prompt tokens and parameters; the source is not disturbed, may
+ * be in the middle of its utterance or ended (not yet taken), and may itself have been started this way.  Several candidates of one
+ * prompt thus cost one prefix pass.
+ *   max_length / sampling_mode / sampling_k / sampling_p / seed / forced: `dst`'s own, as fc_laura_slots_start
+ * Refused before any launch, changing nothing for any slot: `dst` or `src` outside 0 .. S - 1, dst == src, a source that holds no
+ * utterance (free, never started, failed), bad sampling arguments, max_length < 1, the source's text_len + 2 + cont_len + max_length >
+ * max_positions.  A running `dst`'s utterance is abandoned. */
+int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_length, int sampling_mode, int sampling_k, float sampling_p,
+                              uint64_t seed, const int64_t* forced, void* stream);
 
 #ifdef __cplusplus
 }

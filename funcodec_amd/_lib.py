@@ -169,6 +169,7 @@ SYMBOLS = {
     "fc_laura_slots_step": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "fc_laura_slots_take": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
     "fc_laura_slots_start_from": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _P, _P]),
+    "fc_laura_slots_fork": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _P]),
 }
 
 _lib = None

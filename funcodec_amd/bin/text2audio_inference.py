@@ -194,7 +194,7 @@ class Text2Audio:
     @torch.no_grad()
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
-                      step_n: int = 1, samples: int = 1):
+                      step_n: int = 1, samples: int = 1, retries: int = 0):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
         request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.
@@ -203,12 +203,18 @@ class Text2Audio:
         and returns one list of N per request in both return values.  A candidate whose request has another candidate running in
         some slot is started from that slot (DecodeSlots.start_from: a copy of the prefix instead of a prefix pass); the two ways
         give the same bits, so every candidate is what its request listed N times as N requests with the same seeds gives, and
-        which way a candidate started is purely a matter of cost."""
-        from ..laura import drive_samples
+        which way a candidate started is purely a matter of cost.
+
+        retries = R > 0 gives a candidate that reaches max_length without <eos> up to R second tries (laura.drive_retries): its slot
+        is rewound in place to the first half of its tokens (DecodeSlots.rewind, keep = n_gen // 2: no prefix pass, no copy) and
+        goes on with seed laura.retry_seed(seed, attempt); the last attempt is kept.  retries = 0 is the call without it."""
+        from ..laura import drive_retries, drive_samples, retry_seed
         m, nq = self.model, self.model.predict_nq
-        n, N = len(texts), int(samples)
+        n, N, R = len(texts), int(samples), int(retries)
         if N < 1:
             raise ValueError(f"generate_many: samples must be >= 1, got {samples}")
+        if R < 0:
+            raise ValueError(f"generate_many: retries must be >= 0, got {retries}")
         continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
         per = None
         if continual_mode:
@@ -237,7 +243,14 @@ class Text2Audio:
 
             def start_from(slot, src, c):
                 session.start_from(slot, src, self.max_length, self.sampling, seeds[c])
-            taken = [t for row in drive_samples(session, slots, n, N, start, start_from, step_n) for t in row]
+
+            def rewind(slot, c, keep, attempt):
+                session.rewind(slot, keep, self.max_length, self.sampling, retry_seed(seeds[c], attempt))
+            if R == 0:
+                rows = drive_samples(session, slots, n, N, start, start_from, step_n)
+            else:
+                rows = drive_retries(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
+            taken = [t for row in rows for t in row]
         finally:
             session.free()
         rets, codecs = [], []

@@ -766,6 +766,7 @@ struct fc_laura_slots {
     float* lg0 = nullptr;                   // [S][V]: the logits every slot's prefix pass ended with (the step overwrites m.lg)
     std::vector<int> state, cont_len, max_len, n_gen;
     std::vector<int> text_len, prefix;      // of the prompt a slot holds: text tokens, prefix positions P = text_len + 2 + cont_len
+    std::vector<int> forced_on;             // the slot's utterance follows forced tokens (rows [0, max_len) of its forced row)
     hipGraphExec_t gexec = nullptr;         // the captured step, and the form it holds
     bool g_persist = false, g_timeout = false;
     bool warmed[2] = {false, false};        // one eager step run per form (sets the kernels' LDS attributes, which a capture cannot)
@@ -847,6 +848,47 @@ int check_sampling(int mode, int k, float p) {
     if (mode < 0 || mode > 3) return fail("sampling_mode must be 0..3");
     if (mode == 2 && k < 1) return fail("top-k sampling needs sampling_k >= 1");
     if (mode == 3 && !(p > 0.f)) return fail("nucleus sampling needs sampling_p > 0");
+    return 0;
+}
+
+// Slot `dst` from the prompt slot `src` holds: the reset, the copy of the source's prefix, the first sample from the prefix logits.  The
+// caller has checked everything.  dst == src (a rewind to nothing generated) keeps the slot's own prefix and needs no copy.
+int slots_from_prefix(fc_laura_slots* s, int dst, int src, int max_length, int sampling_mode, int sampling_k, float sampling_p, uint64_t seed,
+                      const int64_t* forced, void* stream) {
+    const int P = s->prefix[src], cont_len = s->cont_len[src];
+    fc_laura* e = s->e;
+    const StepMem& m = s->m;
+    const int d = e->codec_lm.s.d_model, V = e->vocab(), nq = e->arch.predict_nq;
+    lk::SampleRow row{};
+    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
+    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;
+    // from here on the destination's previous utterance is gone (as a start on a running slot abandons it)
+    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = 0; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
+    s->text_len[dst] = s->text_len[src]; s->prefix[dst] = P; s->forced_on[dst] = forced ? 1 : 0;
+    Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
+    s->last = cx.st;
+    lk::SlotReset r;
+    r.slot = dst; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
+    r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
+    r.continual = s->tokens + (size_t)src * s->R * nq;      // the source's prompt tokens: generation never changes rows [0, cont_len)
+    r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
+    cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+    if (dst != src) {
+        lk::PrefixCopy c;
+        c.kc = m.kc; c.vc = m.vc; c.lg = m.lg; c.lg0 = s->lg0; c.pos = m.pos;
+        c.NL = e->codec_lm.s.layers; c.S = s->S; c.d = d; c.Tcap = m.Tcap; c.V = V; c.P = P; c.src = src; c.n = 1; c.dst[0] = dst;
+        cx.check(lk::launch_prefix_copy(c, cx.st), "prefix copy");
+    } else {
+        cx.check(hipMemcpyAsync(m.lg + (size_t)dst * V, s->lg0 + (size_t)dst * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, cx.st),
+                 "prefix logits");
+        cx.check(lk::launch_fill_i32(m.pos + dst, P, 1, cx.st), "position");
+    }
+    lk::Sample sm = slots_sampler(s);
+    sm.row0 = dst; sm.nrows = 1;
+    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
+    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    if (cx.err) return 1;
+    s->state[dst] = SLOT_RUNNING;
     return 0;
 }
 
@@ -1126,7 +1168,7 @@ int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_lo
     slots_layout(e, cx, slots, max_positions, s->with_logp, *s);
     if (cx.err) return fail("decoding session: state allocation too small (fc_laura_slots_state_bytes)");
     s->state.assign(slots, SLOT_FREE); s->cont_len.assign(slots, 0); s->max_len.assign(slots, 0); s->n_gen.assign(slots, 0);
-    s->text_len.assign(slots, 0); s->prefix.assign(slots, 0);
+    s->text_len.assign(slots, 0); s->prefix.assign(slots, 0); s->forced_on.assign(slots, 0);
     // a never-started slot: done = 1, pos = 0, a zero xs row -- it goes through every step with finite values and the sampler skips it
     const StepMem& m = s->m;
     const Stack& S = e->codec_lm;
@@ -1191,7 +1233,7 @@ int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, in
     }
     // from here on the slot's previous utterance is gone (a start on a running slot abandons it)
     s->state[slot] = SLOT_FAILED; s->n_gen[slot] = 0; s->cont_len[slot] = cont_len; s->max_len[slot] = max_length;
-    s->text_len[slot] = text_len; s->prefix[slot] = text_len + 2 + cont_len;
+    s->text_len[slot] = text_len; s->prefix[slot] = text_len + 2 + cont_len; s->forced_on[slot] = forced ? 1 : 0;
     s->last = (hipStream_t)stream;
     Ctx cx = make_ctx(1, workspace, workspace_bytes, stream);
     if (slots_prefix(s, cx, slot, text_outs, text_len, cont_len ? continual : nullptr, cont_len, row, forced)) return 1;
@@ -1216,31 +1258,64 @@ int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_lengt
     if (P + max_length > s->R)
         return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
                     " exceeds the session's max_positions " + std::to_string(s->R));
+    return slots_from_prefix(s, dst, src, max_length, sampling_mode, sampling_k, sampling_p, seed, forced, stream);
+}
+
+int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_length, int sampling_mode, int sampling_k, float sampling_p,
+                        uint64_t seed, void* stream) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    const std::string range = " outside 0 .. " + std::to_string(s->S - 1);
+    if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + range);
+    if (src < 0 || src >= s->S) return fail("decoding session: source slot " + std::to_string(src) + range);
+    if (s->state[src] != SLOT_RUNNING && s->state[src] != SLOT_DONE)
+        return fail("decoding session: source slot " + std::to_string(src) + " holds no utterance (" +
+                    (s->state[src] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+    const int g = s->n_gen[src];
+    if (keep < 0) keep = g;
+    if (keep > g)
+        return fail("decoding session: slot " + std::to_string(dst) + ": keep " + std::to_string(keep) + " outside 0 .. " + std::to_string(g) +
+                    ", the tokens source slot " + std::to_string(src) + " has generated as last reported");
+    if (max_length < 1) max_length = s->max_len[src];
+    if (max_length <= keep)
+        return fail("decoding session: slot " + std::to_string(dst) + ": max_length " + std::to_string(max_length) + " leaves nothing to generate after keep " +
+                    std::to_string(keep));
+    if (check_sampling(sampling_mode, sampling_k, sampling_p)) return 1;
+    const int P = s->prefix[src], cont_len = s->cont_len[src];
+    if (P + max_length > s->R)
+        return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
+                    " exceeds the session's max_positions " + std::to_string(s->R));
+    if (keep == 0) return slots_from_prefix(s, dst, src, max_length, sampling_mode, sampling_k, sampling_p, seed, nullptr, stream);
+    const int forced_on = s->forced_on[src], forced_rows = s->max_len[src];
+    if (forced_on && max_length > forced_rows)
+        return fail("decoding session: slot " + std::to_string(dst) + ": source slot " + std::to_string(src) + " follows " + std::to_string(forced_rows) +
+                    " forced tokens, max_length " + std::to_string(max_length) + " goes past them");
     fc_laura* e = s->e;
     const StepMem& m = s->m;
     const int d = e->codec_lm.s.d_model, V = e->vocab(), nq = e->arch.predict_nq;
-    lk::SampleRow row{};
-    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
-    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;
-    // from here on the destination's previous utterance is gone (as a start on a running slot abandons it)
-    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = 0; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
-    s->text_len[dst] = s->text_len[src]; s->prefix[dst] = P;
+    // from here on the destination's previous utterance is gone; in place the slot's own utterance is kept up to token `keep`
+    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = keep; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
+    s->text_len[dst] = s->text_len[src]; s->prefix[dst] = P; s->forced_on[dst] = forced_on;
     Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
     s->last = cx.st;
-    lk::SlotReset r;
-    r.slot = dst; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
-    r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
-    r.continual = s->tokens + (size_t)src * s->R * nq;      // the source's prompt tokens: generation never changes rows [0, cont_len)
-    r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
-    cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
-    lk::PrefixCopy c;
-    c.kc = m.kc; c.vc = m.vc; c.lg = m.lg; c.lg0 = s->lg0; c.pos = m.pos;
-    c.NL = e->codec_lm.s.layers; c.S = s->S; c.d = d; c.Tcap = m.Tcap; c.V = V; c.P = P; c.src = src; c.n = 1; c.dst[0] = dst;
-    cx.check(lk::launch_prefix_copy(c, cx.st), "prefix copy");
-    lk::Sample sm = slots_sampler(s);
-    sm.row0 = dst; sm.nrows = 1;
-    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
-    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    if (dst != src) {
+        // positions [0, P + keep - 1): the prefix and kept tokens 0 .. keep - 2; token keep - 1 is the next step's input.  Sets pos[dst].
+        lk::PrefixCopy c;
+        c.kc = m.kc; c.vc = m.vc; c.lg = m.lg; c.lg0 = s->lg0; c.pos = m.pos;
+        c.NL = e->codec_lm.s.layers; c.S = s->S; c.d = d; c.Tcap = m.Tcap; c.V = V; c.P = P + keep - 1; c.src = src; c.n = 1; c.dst[0] = dst;
+        cx.check(lk::launch_prefix_copy(c, cx.st), "cache copy");
+    }
+    const lk::Sample sm = slots_sampler(s);
+    lk::SlotBranch r;
+    r.S = s->S; r.dst = dst; r.src = src; r.keep = keep; r.P = P;
+    r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off; r.rows = s->rows;
+    r.row.mode = sampling_mode; r.row.ki = sampling_k; r.row.pf = sampling_p; r.row.max_steps = max_length; r.row.seed = seed;
+    r.row.forced_on = forced_on; r.row.rng_row = 0u;
+    r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len; r.forced = s->forced; r.forced_rows = forced_rows;
+    r.logp = s->logp; r.V = V;
+    r.cb = sm.cb; r.K = sm.K; r.D = sm.D; r.next_emb = sm.next_emb; r.emb_wt = sm.emb_wt; r.emb_bias = sm.emb_bias; r.emb_g = sm.emb_g;
+    r.emb_b = sm.emb_b; r.dm = sm.dm; r.emb_relu = sm.emb_relu; r.xscale = sm.xscale; r.xs = sm.xs;
+    cx.check(lk::launch_slot_branch(r, cx.st), "slot branch");
     if (cx.err) return 1;
     s->state[dst] = SLOT_RUNNING;
     return 0;

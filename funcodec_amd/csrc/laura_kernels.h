@@ -175,6 +175,30 @@ struct PrefixCopy {                 // see prefix_copy_kernel
 };
 hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st);
 
+struct SlotBranch {                 // see slot_branch_kernel
+    int S = 0, dst = 0, src = 0;    // dst == src: in place
+    int keep = 0;                   // generated tokens of the source that stay, >= 1
+    int P = 0;                      // prefix positions of the prompt (text_len + 2 + cont_len)
+    int *n_gen = nullptr, *done = nullptr, *step = nullptr, *pos = nullptr, *tok_off = nullptr;
+    SampleRow* rows = nullptr;
+    SampleRow row{};                // dst's own; forced_on is the source's
+    int64_t* tokens = nullptr;      // [S][tok_stride][nq]
+    int tok_stride = 0, nq = 0, cont_len = 0;
+    int64_t* forced = nullptr;      // [S][tok_stride][nq]
+    int forced_rows = 0;            // rows of the source's forced tokens (its max_length)
+    float* logp = nullptr;          // [S][tok_stride][V] or null
+    int V = 0;
+    // the LM's next input from kept token keep - 1: the fields of Sample of the same names
+    const float* cb = nullptr;
+    int K = 0, D = 0;
+    float* next_emb = nullptr;
+    const float *emb_wt = nullptr, *emb_bias = nullptr, *emb_g = nullptr, *emb_b = nullptr;
+    int dm = 0, emb_relu = 0;
+    float xscale = 1.f;
+    float* xs = nullptr;
+};
+hipError_t launch_slot_branch(const SlotBranch& r, hipStream_t st);
+
 hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t st);
 
 // ---- step form as ONE persistent launch (laura_persist.hip) ------------------------------------------------------------------------

@@ -1089,6 +1089,107 @@ struct SampleArgs {
 
 #define FC_SAMPLE_MAXV 2048      // candidates per group, padded to a power of two for the bitonic sort (K + 1 <= 2048)
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The tail of a sample: the LM's next input row of utterance b from the nq chosen ids.  next_emb[b] = sum_k cb[k][chosen[k]], then (emb_wt
+// given) the LM's fused input layer into xs[b].  One 256-thread workgroup; val[] / idx[] (FC_SAMPLE_MAXV words each) and wred[4] are the
+// caller's LDS, free at this point; chosen[] is visible to every thread.  sample_kernel and slot_branch_kernel both call this and nothing
+// else, so a slot that is re-embedded from a kept token gets the sampler's own bits.
+// ---------------------------------------------------------------------------------------------------------------------
+struct EmbedNext {
+    const float* cb;
+    int K, nq, D;
+    float* next_emb;
+    const float *emb_wt, *emb_bias, *emb_g, *emb_b;
+    int dm, emb_relu;
+    float xscale;
+    float* xs;
+};
+
+__device__ __forceinline__ void embed_next(const EmbedNext& e, int b, const int* chosen, float* val, int* idx, float* wred) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // next LM input: sum of the groups' codebook rows (build_llm_io -> calc_dense_vector)
+    for (int dd = tid; dd < e.D; dd += 256) {
+        float s = 0.f;
+        for (int k = 0; k < e.nq; ++k) {
+            const float v = e.cb[((size_t)k * e.K + chosen[k]) * e.D + dd];
+            s = k == 0 ? v : s + v;
+        }
+        e.next_emb[(size_t)b * e.D + dd] = s;
+        val[dd] = s;                                   // val[] is free now: the embedding for the fused input layer
+    }
+    if (e.emb_wt) {
+        __syncthreads();
+        // y[n] = bias[n] + sum_k W^T[k][n] e[k]: thread (output quad nq4, k part kp) takes 4 consecutive outputs over its share of
+        // the k range with independent 16-byte loads; the parts meet in LDS (idx[] reinterpreted, free now)
+        float* ysum = (float*)idx;                      // [dm] after the reduction
+        const int nquads = e.dm >> 2;                   // dm % 4 == 0
+        const int kparts = 256 / nquads > 0 ? 256 / nquads : 1;
+        const int nq4 = tid % nquads, kp = tid / nquads;
+        const int kper = (e.D + kparts - 1) / kparts;
+        f32x4 accq = {0.f, 0.f, 0.f, 0.f};
+        if (kp < kparts && tid < nquads * kparts) {
+            const int kb0 = kp * kper, kb1 = kb0 + kper < e.D ? kb0 + kper : e.D;
+            const float* wq = e.emb_wt + 4 * nq4;
+            int kk = kb0;
+            for (; kk + 16 <= kb1; kk += 16) {          // 16 independent 16-byte loads in flight (the table is cold in L2 every step)
+                f32x4 wv16[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) wv16[u] = *(const f32x4*)(wq + (size_t)(kk + u) * e.dm);
+#pragma unroll
+                for (int u = 0; u < 16; ++u) accq += val[kk + u] * wv16[u];
+            }
+            for (; kk + 4 <= kb1; kk += 4) {
+                f32x4 wv4[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) wv4[u] = *(const f32x4*)(wq + (size_t)(kk + u) * e.dm);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) accq += val[kk + u] * wv4[u];
+            }
+            for (; kk < kb1; ++kk) accq += val[kk] * *(const f32x4*)(wq + (size_t)kk * e.dm);
+        }
+        __syncthreads();                                // everybody is done with idx[] (the sampler's candidate ids)
+        float* ypart = (float*)idx;                     // [kparts][dm], kparts * dm <= 2048 floats
+        if (tid < nquads * kparts) *(f32x4*)(ypart + kp * e.dm + 4 * nq4) = accq;
+        __syncthreads();
+        float yv[4];
+        float ps = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int n = tid + 256 * i;
+            yv[i] = 0.f;
+            if (n < e.dm) {
+                float acc = e.emb_bias[n];
+                for (int q = 0; q < kparts; ++q) acc += ypart[q * e.dm + n];
+                yv[i] = acc;
+                ps += acc;
+            }
+        }
+        (void)ysum;
+        ps = wave_sum(ps);
+        if (lane == 0) wred[w] = ps;
+        __syncthreads();
+        const float mean = (wred[0] + wred[1] + wred[2] + wred[3]) / (float)e.dm;
+        __syncthreads();
+        float pq = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (tid + 256 * i < e.dm) { const float dv = yv[i] - mean; pq += dv * dv; }
+        pq = wave_sum(pq);
+        if (lane == 0) wred[w] = pq;
+        __syncthreads();
+        const float rstd = 1.f / sqrtf((wred[0] + wred[1] + wred[2] + wred[3]) / (float)e.dm + 1e-5f);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int n = tid + 256 * i;
+            if (n < e.dm) {
+                float o = (yv[i] - mean) * rstd * e.emb_g[n] + e.emb_b[n];
+                if (e.emb_relu) o = o > 0.f ? o : 0.f;
+                e.xs[(size_t)b * e.dm + n] = o * e.xscale;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __shared__ __attribute__((aligned(16))) float val[FC_SAMPLE_MAXV];
     __shared__ __attribute__((aligned(16))) int idx[FC_SAMPLE_MAXV];
@@ -1346,87 +1447,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const bool active = !was_done && gen < max_steps;
     if (active && !eos) {
         if (tid < a.nq) a.tokens[((size_t)b * a.tok_stride + a.tok_off[b] + gen) * a.nq + tid] = (int64_t)chosen[tid];
-        // next LM input: sum of the groups' codebook rows (build_llm_io -> calc_dense_vector)
-        for (int dd = tid; dd < a.D; dd += 256) {
-            float s = 0.f;
-            for (int k = 0; k < a.nq; ++k) {
-                const float v = a.cb[((size_t)k * a.K + chosen[k]) * a.D + dd];
-                s = k == 0 ? v : s + v;
-            }
-            a.next_emb[(size_t)b * a.D + dd] = s;
-            val[dd] = s;                                   // val[] is free now: the embedding for the fused input layer
-        }
-        if (a.emb_wt) {
-            __syncthreads();
-            // y[n] = bias[n] + sum_k W^T[k][n] e[k]: thread (output quad nq4, k part kp) takes 4 consecutive outputs over its share of
-            // the k range with independent 16-byte loads; the parts meet in LDS (idx[] reinterpreted, free now)
-            float* ysum = (float*)idx;                      // [dm] after the reduction
-            const int nquads = a.dm >> 2;                   // dm % 4 == 0
-            const int kparts = 256 / nquads > 0 ? 256 / nquads : 1;
-            const int nq4 = tid % nquads, kp = tid / nquads;
-            const int kper = (a.D + kparts - 1) / kparts;
-            f32x4 accq = {0.f, 0.f, 0.f, 0.f};
-            if (kp < kparts && tid < nquads * kparts) {
-                const int kb0 = kp * kper, kb1 = kb0 + kper < a.D ? kb0 + kper : a.D;
-                const float* wq = a.emb_wt + 4 * nq4;
-                int kk = kb0;
-                for (; kk + 16 <= kb1; kk += 16) {          // 16 independent 16-byte loads in flight (the table is cold in L2 every step)
-                    f32x4 wv16[16];
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) wv16[u] = *(const f32x4*)(wq + (size_t)(kk + u) * a.dm);
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) accq += val[kk + u] * wv16[u];
-                }
-                for (; kk + 4 <= kb1; kk += 4) {
-                    f32x4 wv4[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) wv4[u] = *(const f32x4*)(wq + (size_t)(kk + u) * a.dm);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) accq += val[kk + u] * wv4[u];
-                }
-                for (; kk < kb1; ++kk) accq += val[kk] * *(const f32x4*)(wq + (size_t)kk * a.dm);
-            }
-            __syncthreads();                                // everybody is done with idx[] (the sampler's candidate ids)
-            float* ypart = (float*)idx;                     // [kparts][dm], kparts * dm <= 2048 floats
-            if (tid < nquads * kparts) *(f32x4*)(ypart + kp * a.dm + 4 * nq4) = accq;
-            __syncthreads();
-            float yv[4];
-            float ps = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = tid + 256 * i;
-                yv[i] = 0.f;
-                if (n < a.dm) {
-                    float acc = a.emb_bias[n];
-                    for (int q = 0; q < kparts; ++q) acc += ypart[q * a.dm + n];
-                    yv[i] = acc;
-                    ps += acc;
-                }
-            }
-            (void)ysum;
-            ps = wave_sum(ps);
-            if (lane == 0) wred[w] = ps;
-            __syncthreads();
-            const float mean = (wred[0] + wred[1] + wred[2] + wred[3]) / (float)a.dm;
-            __syncthreads();
-            float pq = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (tid + 256 * i < a.dm) { const float dv = yv[i] - mean; pq += dv * dv; }
-            pq = wave_sum(pq);
-            if (lane == 0) wred[w] = pq;
-            __syncthreads();
-            const float rstd = 1.f / sqrtf((wred[0] + wred[1] + wred[2] + wred[3]) / (float)a.dm + 1e-5f);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = tid + 256 * i;
-                if (n < a.dm) {
-                    float o = (yv[i] - mean) * rstd * a.emb_g[n] + a.emb_b[n];
-                    if (a.emb_relu) o = o > 0.f ? o : 0.f;
-                    a.xs[(size_t)b * a.dm + n] = o * a.xscale;
-                }
-            }
-        }
+        embed_next(EmbedNext{a.cb, a.K, a.nq, a.D, a.next_emb, a.emb_wt, a.emb_bias, a.emb_g, a.emb_b, a.dm, a.emb_relu, a.xscale, a.xs},
+                   b, chosen, val, idx, wred);
     }
     __syncthreads();
     if (tid == 0) {
@@ -1552,6 +1574,90 @@ hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st) {
     if (nK > 0x7fffffff || nV > 0x7fffffff) return hipErrorInvalidValue;
     const int bK = (int)((nK + per - 1) / per), bV = (int)((nV + per - 1) / per);
     hipLaunchKernelGGL(prefix_copy_kernel, dim3(bK + bV + 1, c.NL), dim3(256), 0, st, c);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Slot `dst` takes up slot `src`'s utterance as it stood after its first `keep` >= 1 generated tokens (dst == src: the slot goes back
+// there in place).  What the next step and the sampler's bookkeeping read, and nothing else:
+//   block 0: the LM's next input, next_emb[dst] and xs[dst], from kept token keep - 1 through embed_next -- the sampler's own tail, the
+//   same block shape and LDS -- and, one thread, the counters (n_gen = step = keep, done = 0, tok_off), dst's row of the sampling table.
+//   pos is the copy's (prefix_copy_kernel with P + keep - 1 positions) or, in place, set here.
+//   blocks 1 ..: grid-stride over 16-byte vectors of the token row ([0, cont_len + keep) kept, zeros behind), the forced row (the
+//   source's) and the log-probability rows ([0, keep) kept, zeros up to max_steps: take(return_logp) relies on rows never run being
+//   zero).  In place the kept parts are not touched, only the zeros behind them are written.  Every vector lies inside the slot's own
+//   row: tok_stride % 4 == 0, so a row's length is a whole number of vectors and its start is 16-byte aligned.
+// A source that is running may be stepped again behind this launch: rows [0, keep) of its tables never change once written.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(256) void slot_branch_kernel(SlotBranch r) {
+    __shared__ __attribute__((aligned(16))) float val[FC_SAMPLE_MAXV];
+    __shared__ __attribute__((aligned(16))) int idx[FC_SAMPLE_MAXV];
+    __shared__ float wred[4];
+    __shared__ int chosen[8];
+    const int tid = threadIdx.x;
+    const int d = r.dst, s = r.src;
+    const bool same = d == s;
+    const size_t ntok = (size_t)r.tok_stride * r.nq;                  // int64 per token / forced row, even
+    if (blockIdx.x == 0) {
+        if (tid < r.nq) chosen[tid] = (int)r.tokens[(size_t)s * ntok + (size_t)(r.cont_len + r.keep - 1) * r.nq + tid];
+        __syncthreads();
+        embed_next(EmbedNext{r.cb, r.K, r.nq, r.D, r.next_emb, r.emb_wt, r.emb_bias, r.emb_g, r.emb_b, r.dm, r.emb_relu, r.xscale, r.xs},
+                   d, chosen, val, idx, wred);
+        if (tid == 0) {
+            r.n_gen[d] = r.keep; r.step[d] = r.keep; r.done[d] = 0; r.tok_off[d] = r.cont_len;
+            if (same) r.pos[d] = r.P + r.keep - 1;
+            r.rows[d] = r.row;
+        }
+        return;
+    }
+    const size_t t0 = (size_t)(blockIdx.x - 1) * 256 + tid, nth = (size_t)(gridDim.x - 1) * 256;
+    {   // the token row
+        const size_t ncopy = (size_t)(r.cont_len + r.keep) * r.nq;
+        const i64x2* sv = (const i64x2*)(r.tokens + (size_t)s * ntok);
+        i64x2* dv = (i64x2*)(r.tokens + (size_t)d * ntok);
+        // in place: whole vectors behind the kept part, the odd element ahead of them on its own (kept data is never rewritten)
+        if (same && (ncopy & 1) && t0 == 0) r.tokens[(size_t)d * ntok + ncopy] = 0;
+        for (size_t i = (same ? (ncopy + 1) >> 1 : 0) + t0; i < ntok >> 1; i += nth) {
+            i64x2 v = {0, 0};
+            if (2 * i < ncopy) v = sv[i];
+            if (2 * i + 1 >= ncopy) v.y = 0;
+            dv[i] = v;
+        }
+    }
+    if (!same && r.row.forced_on) {   // the forced row, as far as the source's reaches
+        const size_t nf = ((size_t)r.forced_rows * r.nq + 1) >> 1;
+        const i64x2* sv = (const i64x2*)(r.forced + (size_t)s * ntok);
+        i64x2* dv = (i64x2*)(r.forced + (size_t)d * ntok);
+        for (size_t i = t0; i < nf; i += nth) dv[i] = sv[i];
+    }
+    if (r.logp) {
+        const size_t ncopy = (size_t)r.keep * r.V, nl = ((size_t)r.row.max_steps * r.V + 3) >> 2;
+        const f32x4* sv = (const f32x4*)(r.logp + (size_t)s * r.tok_stride * r.V);
+        f32x4* dv = (f32x4*)(r.logp + (size_t)d * r.tok_stride * r.V);
+        if (same && t0 < 4 && ncopy + t0 < ((ncopy + 3) & ~(size_t)3)) r.logp[(size_t)d * r.tok_stride * r.V + ncopy + t0] = 0.f;
+        for (size_t i = (same ? (ncopy + 3) >> 2 : 0) + t0; i < nl; i += nth) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (4 * i < ncopy) v = sv[i];
+            if (4 * i + 3 >= ncopy) {                                 // the vector the kept part ends in, or one behind it
+                if (4 * i >= ncopy) v.x = 0.f;
+                if (4 * i + 1 >= ncopy) v.y = 0.f;
+                if (4 * i + 2 >= ncopy) v.z = 0.f;
+                v.w = 0.f;
+            }
+            dv[i] = v;
+        }
+    }
+}
+hipError_t launch_slot_branch(const SlotBranch& r, hipStream_t st) {
+    if (r.S < 1 || r.dst < 0 || r.dst >= r.S || r.src < 0 || r.src >= r.S || r.keep < 1 || r.cont_len < 0 || r.P < 1) return hipErrorInvalidValue;
+    if (r.tok_stride % 4 || r.row.max_steps <= r.keep || r.cont_len + r.row.max_steps > r.tok_stride || r.P + r.row.max_steps > r.tok_stride)
+        return hipErrorInvalidValue;
+    if (r.forced_rows < 0 || r.forced_rows > r.tok_stride) return hipErrorInvalidValue;
+    if (r.K + 1 > FC_SAMPLE_MAXV || r.nq > 8 || r.nq < 1 || !r.cb || !r.next_emb) return hipErrorInvalidValue;
+    if (r.emb_wt && (r.dm > 1024 || r.dm % 4 || r.D > FC_SAMPLE_MAXV)) return hipErrorInvalidValue;      // as launch_sample
+    hipLaunchKernelGGL(slot_branch_kernel, dim3(65), dim3(256), 0, st, r);
     return hipGetLastError();
 }
 

@@ -461,6 +461,50 @@ class DecodeSlots:
         self._max_length[dst] = max_length
 
     @_on_device
+    def fork(self, dst: int, src: int, keep: Optional[int] = None, max_length: Optional[int] = None,
+             sampling: Union[bool, int, float] = True, seed: int = 0) -> None:
+        """Slot `dst` holds slot `src`'s utterance as it stood after its first `keep` generated tokens (default: all that the last
+        ``step`` reported, ``n_gen(src)``) and goes on from there with its own sampling, seed and max_length (default: the source's):
+        a device copy of the source's cache positions, tokens and log-probability rows, no prefix pass and no decoding step.  With the
+        source's own sampling and seed `dst` ends exactly as the source does; with any other, its per-step log-probabilities are those
+        of ``start`` with its final tokens forced.  `src` is not disturbed, may be running or ended (by <eos> or by length, not yet
+        taken) and may itself come from a fork or a start_from; keep = 0 is ``start_from``.  A running `dst` is abandoned.  A refused
+        call changes nothing for any slot."""
+        h = self._handle()
+        dst, src = int(dst), int(src)
+        if not 0 <= src < self.slots:
+            raise EngineError(f"decode session fork: source slot {src} outside 0 .. {self.slots - 1}")
+        keep = -1 if keep is None else int(keep)
+        if keep < -1:
+            raise EngineError(f"decode session fork: slot {dst}: keep {keep} < 0")
+        if max_length is not None and int(max_length) < 1:
+            raise EngineError(f"decode session fork: slot {dst}: max_length {int(max_length)} < 1")
+        max_length = 0 if max_length is None else int(max_length)         # 0: the source's, which the library knows
+        mode, k, p = sampling_args(sampling)
+        cur, run = self._run_stream()
+        try:
+            self.engine._check(self.lib.fc_laura_slots_fork(h, dst, src, keep, max_length, mode, k, p, int(seed) & (2 ** 64 - 1),
+                                                            C.c_void_p(run.cuda_stream)))
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+        self._max_length[dst] = max_length or self._max_length[src]
+        self._n_gen[dst] = self._n_gen[src] if keep < 0 else keep
+
+    def rewind(self, slot: int, keep: int, max_length: Optional[int] = None, sampling: Union[bool, int, float] = True, seed: int = 0) -> None:
+        """``fork(slot, slot, keep, ...)``: the slot goes back to its first `keep` generated tokens in place and goes on from there
+        with the given sampling, seed and max_length (default: its own).  An ended slot (not yet taken) runs again; one that ended on
+        <eos>, rewound to keep = n_gen, draws its ending again."""
+        self.fork(slot, slot, keep, max_length, sampling, seed)
+
+    def n_gen(self, slot: int) -> int:
+        """Tokens slot `slot` has generated, as the last ``step`` reported it (after a fork or rewind: the tokens kept)."""
+        slot = int(slot)
+        if not 0 <= slot < self.slots:
+            raise EngineError(f"decoding session: slot {slot} outside 0 .. {self.slots - 1}")
+        return int(self._n_gen[slot])
+
+    @_on_device
     def step(self, n: int = 16) -> Dict[int, str]:
         """n decoding steps for every running slot; {slot: "running" | "done" | "failed"} for every slot that holds an utterance."""
         h = self._handle()
@@ -577,6 +621,58 @@ def drive_samples(session, slots: int, n_requests: int, samples: int, start, sta
 
     taken = drive_slots(_Watched(), slots, n_requests * samples, begin, step_n)
     return [taken[i * samples: (i + 1) * samples] for i in range(n_requests)]
+
+
+RETRY_SEED_STRIDE = 0x9E3779B97F4A7C15
+
+
+def retry_seed(seed: int, attempt: int) -> int:
+    """The seed of attempt number `attempt` (0 = the candidate's own) of a candidate that is rewound after ending by length."""
+    return (int(seed) + int(attempt) * RETRY_SEED_STRIDE) % (2 ** 64)
+
+
+def drive_retries(session, slots: int, n_requests: int, samples: int, retries: int, max_length: int, start, start_from, rewind,
+                  step_n: int = 1) -> list:
+    """``drive_samples`` with second tries.  A candidate whose slot ends by length -- ``session.n_gen(slot) >= max_length``, so no
+    <eos> -- is not taken: ``rewind(slot, c, keep, attempt)`` sends it back to its first keep = n_gen // 2 tokens to go on with
+    ``retry_seed(seed, attempt)``, attempt = 1, 2, ... up to `retries` times per candidate; the last attempt is kept however it ends.
+    A slot that ends on <eos> is never rewound.  ``drive_slots`` sees a rewound slot as still running, so its policy, the arrival
+    order and ``drive_samples``' choice between start and start_from are unchanged; retries = 0 rewinds nothing.  Returns what
+    ``drive_samples`` returns."""
+    cand: Dict[int, int] = {}               # slot -> the candidate it holds
+    tries: Dict[int, int] = {}              # slot -> rewinds of that candidate so far
+
+    class _Retrying:
+        def step(self, n):
+            status = dict(session.step(n))
+            for slot in sorted(cand):
+                if status.get(slot) != "done" or tries[slot] >= retries:
+                    continue
+                g = session.n_gen(slot)
+                if g < max_length:          # ended on <eos>
+                    continue
+                tries[slot] += 1
+                rewind(slot, cand[slot], g // 2, tries[slot])
+                status[slot] = "running"
+            return status
+
+        def take(self, slot):
+            cand.pop(slot, None)
+            tries.pop(slot, None)
+            return session.take(slot)
+
+    def begin(slot, c):
+        cand[slot], tries[slot] = c, 0
+
+    def start_(slot, c):
+        start(slot, c)
+        begin(slot, c)
+
+    def start_from_(slot, src, c):
+        start_from(slot, src, c)
+        begin(slot, c)
+
+    return drive_samples(_Retrying(), slots, n_requests, samples, start_, start_from_, step_n)
 
 
 class LauraGenMI355X:

@@ -714,6 +714,24 @@ int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, i
  * max_positions.  A running `dst`'s utterance is abandoned. */
 int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_length, int sampling_mode, int sampling_k, float sampling_p,
                               uint64_t seed, const int64_t* forced, void* stream);
+/* decode_codec (laura_model.py:501-548) taken up in the middle of its loop :519-546: slot `dst` holds the utterance of slot `src` as it
+ * stood after its first `keep` generated tokens -- the prompt, those tokens, their log-probability rows and the forced tokens are the
+ * source's -- and goes on from there with its OWN sampling mode, seed and max_length.  No prefix pass and no decoding step is run: one
+ * device copy of the source's key / value positions [0, text_len + 2 + cont_len + keep - 1) and one launch that copies the token and
+ * log-probability rows, sets the counters and runs the LM's input layer on token keep - 1, exactly as the sampler did.  dst == src rewinds
+ * a slot in place (no copy at all); an ended slot runs again.  Sample j of an utterance depends on the logits of step j and (seed, j)
+ * only, so with the source's own mode and seed the destination ends as the source does, bit for bit, and with any other its per-step
+ * log-probabilities are those of fc_laura_slots_start with its final tokens forced.  The source is not disturbed; it may be running or
+ * ended (by <eos> or by length, not yet taken) and may itself be the product of a fork or of fc_laura_slots_start_from.
+ *   keep        0 .. the source's n_gen as fc_laura_slots_step last reported it; < 0: all of them.  keep = 0 is
+ *               fc_laura_slots_start_from without forced tokens, through the same code
+ *   max_length  `dst`'s own, > keep; < 1: the source's
+ *   sampling_mode / sampling_k / sampling_p / seed: `dst`'s own, as fc_laura_slots_start
+ * Refused before any launch, changing nothing for any slot: `dst` or `src` outside 0 .. S - 1, a source that holds no utterance (free,
+ * never started, failed), keep above the source's n_gen, max_length <= keep, text_len + 2 + cont_len + max_length > max_positions, bad
+ * sampling arguments, a source that follows forced tokens with a max_length beyond them.  A running `dst` != `src` is abandoned. */
+int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_length, int sampling_mode, int sampling_k, float sampling_p,
+                        uint64_t seed, void* stream);
 
 #ifdef __cplusplus
 }

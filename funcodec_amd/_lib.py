@@ -170,6 +170,10 @@ SYMBOLS = {
     "fc_laura_slots_take": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
     "fc_laura_slots_start_from": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _P, _P]),
     "fc_laura_slots_fork": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _P]),
+    # a session that keeps the log-probability of every step's picks: one float per slot and step (terms: HOST float32 [cap])
+    "fc_laura_slots_state_bytes_scored": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fc_laura_slots_create_scored": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    "fc_laura_slots_score": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 _lib = None

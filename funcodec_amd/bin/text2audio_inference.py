@@ -194,7 +194,7 @@ class Text2Audio:
     @torch.no_grad()
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
-                      step_n: int = 1, samples: int = 1, retries: int = 0):
+                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all"):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
         request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.
@@ -207,14 +207,24 @@ class Text2Audio:
 
         retries = R > 0 gives a candidate that reaches max_length without <eos> up to R second tries (laura.drive_retries): its slot
         is rewound in place to the first half of its tokens (DecodeSlots.rewind, keep = n_gen // 2: no prefix pass, no copy) and
-        goes on with seed laura.retry_seed(seed, attempt); the last attempt is kept.  retries = 0 is the call without it."""
-        from ..laura import drive_retries, drive_samples, retry_seed
+        goes on with seed laura.retry_seed(seed, attempt); the last attempt is kept.  retries = 0 is the call without it.
+
+        keep = "best" keeps one candidate per request: the session scores every step on the device (open_decode(score=True): the
+        log-probability the LM gave its own picks), laura.pick_best ranks a request's N candidates -- <eos>-ended above run-aways,
+        then the higher mean log-probability per step, ties to the lower index; with retries, a candidate's last attempt by the score
+        of its whole final path -- and only the winners reach the fine predictor and the codec decoder.  Returns (rets, codecs,
+        choice): rets[i], codecs[i] in the shape of samples = 1, choice[i] = (k, mean) of the candidate kept.  The candidates are,
+        token for token, those of keep = "all" (the default: today's call, a session without scores) with the same seeds."""
+        from ..laura import drive_best, drive_retries, drive_samples, retry_seed
         m, nq = self.model, self.model.predict_nq
         n, N, R = len(texts), int(samples), int(retries)
         if N < 1:
             raise ValueError(f"generate_many: samples must be >= 1, got {samples}")
         if R < 0:
             raise ValueError(f"generate_many: retries must be >= 0, got {retries}")
+        if keep not in ("all", "best"):
+            raise ValueError(f"generate_many: keep must be \"all\" or \"best\", got {keep!r}")
+        best = keep == "best"
         continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
         per = None
         if continual_mode:
@@ -231,7 +241,7 @@ class Text2Audio:
         if len(seeds) != n * N:
             raise ValueError(f"generate_many: {len(seeds)} seeds for {n} requests")
         outs, lens = [None] * n, [0] * n
-        session = m.open_decode(slots, logp=False)
+        session = m.open_decode(slots, logp=False, score=True) if best else m.open_decode(slots, logp=False)
         try:
             def start(slot, c):
                 # a request's text is encoded when its slot is free, alone: its text_outs are those of a one-utterance call
@@ -246,16 +256,22 @@ class Text2Audio:
 
             def rewind(slot, c, keep, attempt):
                 session.rewind(slot, keep, self.max_length, self.sampling, retry_seed(seeds[c], attempt))
-            if R == 0:
-                rows = drive_samples(session, slots, n, N, start, start_from, step_n)
+            choice = None
+            if best:
+                kept = drive_best(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
+                taken = {i * N + k: t for i, (k, t) in enumerate(kept)}
+                choice = [(k, t[-1][0] / t[-1][1]) for k, t in kept]
             else:
-                rows = drive_retries(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
-            taken = [t for row in rows for t in row]
+                if R == 0:
+                    rows = drive_samples(session, slots, n, N, start, start_from, step_n)
+                else:
+                    rows = drive_retries(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
+                taken = [t for row in rows for t in row]
         finally:
             session.free()
         rets, codecs = [], []
-        cands = list(range(n * N))
-        for g in (cands[i: i + 16] for i in range(0, n * N, 16)):      # finished utterances, 16 at a time, through the batch forms
+        cands = sorted(taken) if best else list(range(n * N))          # keep = "best": the winners only
+        for g in (cands[i: i + 16] for i in range(0, len(cands), 16)):      # finished utterances, 16 at a time, through the batch forms
             L, C = max(lens[c // N] for c in g), max(max(taken[c][1] for c in g), 1)
             text_outs = torch.zeros((len(g), L, outs[g[0] // N].shape[-1]), dtype=torch.float32, device=m.device)
             tokens = torch.zeros((len(g), C, nq), dtype=torch.int64, device=m.device)
@@ -266,6 +282,8 @@ class Text2Audio:
             r, cd = self._synthesise(text_outs, [lens[c // N] for c in g], tokens, [taken[c][1] for c in g], excl)
             rets += r
             codecs += cd
+        if best:
+            return rets, codecs, choice
         if N == 1:
             return rets, codecs
         return [rets[i * N: (i + 1) * N] for i in range(n)], [codecs[i * N: (i + 1) * N] for i in range(n)]

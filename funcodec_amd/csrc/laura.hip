@@ -757,12 +757,13 @@ enum SlotState { SLOT_FREE = 0, SLOT_RUNNING = 1, SLOT_DONE = 2, SLOT_FAILED = 3
 struct fc_laura_slots {
     fc_laura* e = nullptr;
     int S = 0, R = 0;                       // slots; positions per slot (the pitch of the caches, token and log-probability rows)
-    bool with_logp = false;
+    bool with_logp = false, with_score = false;
     StepMem m;
     lk::SampleRow* rows = nullptr;          // device [S]
     int* tok_off = nullptr;                 // device [S]: the slot's continual prompt length
     int64_t *tokens = nullptr, *forced = nullptr;     // [S][R][nq]
     float* logp = nullptr;                  // [S][R][V] or null
+    float* score = nullptr;                 // [S][R] or null: the log-probability of every step's picks (sample_kernel)
     float* lg0 = nullptr;                   // [S][V]: the logits every slot's prefix pass ended with (the step overwrites m.lg)
     std::vector<int> state, cont_len, max_len, n_gen;
     std::vector<int> text_len, prefix;      // of the prompt a slot holds: text tokens, prefix positions P = text_len + 2 + cont_len
@@ -778,7 +779,7 @@ struct fc_laura_slots {
 
 namespace {
 
-void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, fc_laura_slots& s) {
+void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, bool with_score, fc_laura_slots& s) {
     const int nq = e->arch.predict_nq, V = e->vocab();
     s.m = alloc_step_mem(e, cx, S, R);
     s.rows = cx.alloc<lk::SampleRow>(S);
@@ -787,12 +788,14 @@ void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, fc_laura_s
     s.forced = cx.alloc<int64_t>((size_t)S * R * nq);
     s.logp = with_logp ? cx.alloc<float>((size_t)S * R * V) : nullptr;
     s.lg0 = cx.alloc<float>((size_t)S * V);
+    s.score = with_score ? cx.alloc<float>((size_t)S * R) : nullptr;       // behind everything a session without scores has
 }
 
 lk::Sample slots_sampler(const fc_laura_slots* s) {
     lk::Sample sm = step_sampler(s->e, s->m);
     sm.rows = s->rows; sm.row_stride = s->R; sm.forced = s->forced;
     sm.tokens = s->tokens; sm.tok_stride = s->R; sm.tok_off = s->tok_off; sm.logp_out = s->logp;
+    sm.score_out = s->score;
     return sm;
 }
 
@@ -824,6 +827,7 @@ int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, i
         r.slot = slot; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
         r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
         r.continual = continual; r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
+        r.score = s->score;
         cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
         cx.check(lk::launch_lm_assemble(tfm, Tt, tl, e->lm_emb, e->cb, K, nq, continual, cl, cont_len, 1, D, T, seq, pos, bidir, cx.st), "LM input");
     }
@@ -872,6 +876,7 @@ int slots_from_prefix(fc_laura_slots* s, int dst, int src, int max_length, int s
     r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
     r.continual = s->tokens + (size_t)src * s->R * nq;      // the source's prompt tokens: generation never changes rows [0, cont_len)
     r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
+    r.score = s->score;
     cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
     if (dst != src) {
         lk::PrefixCopy c;
@@ -1146,16 +1151,25 @@ int fc_laura_decode_codec(fc_laura* e, const float* text_outs, const int32_t* te
 int fc_laura_persistent_step_fallbacks(const fc_laura* e) { return e ? e->persist_fallbacks : -1; }
 
 /* ---- decoding session: S slots that start and end independently in one running batch ---- */
-size_t fc_laura_slots_state_bytes(const fc_laura* ce, int slots, int max_positions, int with_logp) {
+size_t fc_laura_slots_state_bytes(const fc_laura* e, int slots, int max_positions, int with_logp) {
+    return fc_laura_slots_state_bytes_scored(e, slots, max_positions, with_logp, 0);
+}
+
+size_t fc_laura_slots_state_bytes_scored(const fc_laura* ce, int slots, int max_positions, int with_logp, int with_score) {
     fc_laura* e = const_cast<fc_laura*>(ce);
     if (!e || slots < 1 || slots > 16 || max_positions < 16 || max_positions > e->R || max_positions % 4) return 0;
     Ctx cx = make_ctx(slots, nullptr, 0, nullptr);
     fc_laura_slots s;
-    slots_layout(e, cx, slots, max_positions, with_logp != 0, s);
+    slots_layout(e, cx, slots, max_positions, with_logp != 0, with_score != 0, s);
     return cx.off + 4096;
 }
 
 int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_logp, void* state, size_t state_bytes, fc_laura_slots** out) {
+    return fc_laura_slots_create_scored(e, slots, max_positions, with_logp, 0, state, state_bytes, out);
+}
+
+int fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
+                                 fc_laura_slots** out) {
     if (check_ready(e)) return 1;
     if (slots < 1 || slots > 16) return fail("a decoding session has 1 .. 16 slots (the step form's 16 MFMA columns), got " + std::to_string(slots));
     if (max_positions < 16 || max_positions % 4 || max_positions > e->R)
@@ -1163,9 +1177,9 @@ int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_lo
                     std::to_string(max_positions));
     if (!state || !out) return fail("null argument");
     auto s = std::make_unique<fc_laura_slots>();
-    s->e = e; s->S = slots; s->R = max_positions; s->with_logp = with_logp != 0;
+    s->e = e; s->S = slots; s->R = max_positions; s->with_logp = with_logp != 0; s->with_score = with_score != 0;
     Ctx cx = make_ctx(slots, state, state_bytes, nullptr);
-    slots_layout(e, cx, slots, max_positions, s->with_logp, *s);
+    slots_layout(e, cx, slots, max_positions, s->with_logp, s->with_score, *s);
     if (cx.err) return fail("decoding session: state allocation too small (fc_laura_slots_state_bytes)");
     s->state.assign(slots, SLOT_FREE); s->cont_len.assign(slots, 0); s->max_len.assign(slots, 0); s->n_gen.assign(slots, 0);
     s->text_len.assign(slots, 0); s->prefix.assign(slots, 0); s->forced_on.assign(slots, 0);
@@ -1185,6 +1199,7 @@ int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_lo
     HIP_TRY(hipMemset(m.psync, 0, (m.sync_words + 32) * sizeof(unsigned)));
     HIP_TRY(hipMemset(s->rows, 0, (size_t)slots * sizeof(lk::SampleRow)));
     HIP_TRY(hipMemset(s->tok_off, 0, (size_t)slots * sizeof(int)));
+    if (s->score) HIP_TRY(hipMemset(s->score, 0, (size_t)slots * max_positions * sizeof(float)));
     std::vector<int> ones(slots, 1);
     const unsigned one = 1u;
     HIP_TRY(hipMemcpy(m.done(), ones.data(), (size_t)slots * sizeof(int), hipMemcpyHostToDevice));
@@ -1312,7 +1327,7 @@ int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_l
     r.row.mode = sampling_mode; r.row.ki = sampling_k; r.row.pf = sampling_p; r.row.max_steps = max_length; r.row.seed = seed;
     r.row.forced_on = forced_on; r.row.rng_row = 0u;
     r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len; r.forced = s->forced; r.forced_rows = forced_rows;
-    r.logp = s->logp; r.V = V;
+    r.logp = s->logp; r.V = V; r.score = s->score;
     r.cb = sm.cb; r.K = sm.K; r.D = sm.D; r.next_emb = sm.next_emb; r.emb_wt = sm.emb_wt; r.emb_bias = sm.emb_bias; r.emb_g = sm.emb_g;
     r.emb_b = sm.emb_b; r.dm = sm.dm; r.emb_relu = sm.emb_relu; r.xscale = sm.xscale; r.xs = sm.xs;
     cx.check(lk::launch_slot_branch(r, cx.st), "slot branch");
@@ -1410,6 +1425,24 @@ int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, i
     HIP_TRY(hipStreamSynchronize(s->last));
     *len_out = n;
     s->state[slot] = SLOT_FREE;
+    return 0;
+}
+
+int fc_laura_slots_score(fc_laura_slots* s, int slot, float* terms, int cap, int32_t* count_out, int32_t* end_out) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
+    if (!s->score) return fail("decoding session: slot " + std::to_string(slot) + ": the session was opened without scores");
+    if (s->state[slot] == SLOT_FAILED) return fail("decoding session: slot " + std::to_string(slot) + " failed (a hand-off of the persistent step timed out); start it again");
+    if (s->state[slot] != SLOT_DONE && s->state[slot] != SLOT_RUNNING) return fail("decoding session: slot " + std::to_string(slot) + " holds no utterance");
+    if (!terms || !count_out || !end_out) return fail("null argument");
+    if (cap < s->R) return fail("decoding session: slot " + std::to_string(slot) + ": a score row has " + std::to_string(s->R) + " terms, room for " + std::to_string(cap));
+    HIP_TRY(hipMemcpyAsync(terms, s->score + (size_t)slot * s->R, (size_t)s->R * sizeof(float), hipMemcpyDeviceToHost, s->last));
+    HIP_TRY(hipStreamSynchronize(s->last));
+    // a slot that ended below its max_length ended on <eos>: that step ran and has a term, but no token
+    const bool ended = s->state[slot] == SLOT_DONE, eos = ended && s->n_gen[slot] < s->max_len[slot];
+    *count_out = s->n_gen[slot] + (eos ? 1 : 0);
+    *end_out = eos ? 2 : (ended ? 1 : 0);
     return 0;
 }
 

@@ -129,6 +129,7 @@ struct Sample {
     int* pos = nullptr;             // device [B]: cache fill, incremented for utterances still running
     int* step = nullptr;            // device [B]: samples drawn so far per utterance (RNG stream position), incremented
     float* logp_out = nullptr;      // [B][max_steps][V] or null: log-softmax the step sampled from
+    float* score_out = nullptr;     // [B][max_steps] or null: the log-probability of the step's final picks (see sample_kernel)
     const float* cb = nullptr;      // [nq_all][K][D] codebook table: next LM input = sum_k cb[k][tok_k]
     int D = 0;
     float* next_emb = nullptr;      // [B][D]
@@ -138,8 +139,8 @@ struct Sample {
     float xscale = 1.f;
     float* xs = nullptr;            // [B][dm]
     unsigned* launch_seq = nullptr; // device word incremented once per launch (the persistent step kernel's launch number), or null
-    // decoding session: mode / ki / pf / seed / max_steps / forced on-off / Philox row word per row instead of the fields above; forced and
-    // logp_out then have row_stride steps per row.  null: exactly the launch a decode_codec call makes
+    // decoding session: mode / ki / pf / seed / max_steps / forced on-off / Philox row word per row instead of the fields above; forced,
+    // logp_out and score_out then have row_stride steps per row.  null: exactly the launch a decode_codec call makes
     const SampleRow* rows = nullptr;
     int row_stride = 0;
     int row0 = 0, nrows = 0;        // rows row0 .. row0 + nrows - 1 only (nrows 0: all B)
@@ -160,6 +161,7 @@ struct SlotReset {                  // see slot_reset_kernel
     const int64_t* forced_src = nullptr;  // [row.max_steps][nq] or null
     float* logp = nullptr;          // [S][tok_stride][V] or null
     int V = 0;
+    float* score = nullptr;         // [S][tok_stride] or null
 };
 hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st);
 
@@ -188,6 +190,7 @@ struct SlotBranch {                 // see slot_branch_kernel
     int forced_rows = 0;            // rows of the source's forced tokens (its max_length)
     float* logp = nullptr;          // [S][tok_stride][V] or null
     int V = 0;
+    float* score = nullptr;         // [S][tok_stride] or null
     // the LM's next input from kept token keep - 1: the fields of Sample of the same names
     const float* cb = nullptr;
     int K = 0, D = 0;

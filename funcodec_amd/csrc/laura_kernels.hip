@@ -1071,6 +1071,7 @@ struct SampleArgs {
     const int* tok_off;
     int *n_gen, *done, *n_done, *pos, *step;
     float* logp_out;
+    float* score_out;
     const float* cb;
     int D;
     float* next_emb;
@@ -1082,7 +1083,7 @@ struct SampleArgs {
     float xscale;
     float* xs;
     unsigned* launch_seq;
-    // decoding session: per-row parameters (null: the call's own, above), the row stride of forced / logp_out, the first row of this launch
+    // decoding session: per-row parameters (null: the call's own, above), the row stride of forced / logp_out / score_out, the first row of this launch
     const SampleRow* rows;
     int stride, row0;
 };
@@ -1190,6 +1191,40 @@ __device__ __forceinline__ void embed_next(const EmbedNext& e, int b, const int*
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// sum over a group of exp(x - m), m the group's maximum: the normaliser of softmax(logits[group]), by all 256 threads.  xr[] holds the
+// thread's logits (entry i = logit tid + 256 i, clamped past G).  One statement of the sum, so that the sampling modes, which draw from
+// it, and the step's score (SampleArgs::score_out), which greedy mode forms without drawing, get the same bits: per thread in i order,
+// wave_sum, the four waves in wave order.  STORE: the unnormalised probabilities and their indices into val[] / idx[] for the draw
+// (padding -1: sorts last).  Ends behind a barrier; wred[] is read by every thread and free again at the caller's next barrier.
+// ---------------------------------------------------------------------------------------------------------------------
+template <bool STORE>
+__device__ __forceinline__ float group_exp_total(const float (&xr)[FC_SAMPLE_MAXV / 256], float m, int G, float* val, int* idx, float* wred) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < FC_SAMPLE_MAXV / 256; ++i) {
+        const int v = tid + 256 * i;
+        const float e = v < G ? expf(xr[i] - m) : -1.f;
+        if (STORE) {
+            val[v] = e;
+            idx[v] = v;
+        }
+        if (v < G) s += e;
+    }
+    s = wave_sum(s);
+    if (lane == 0) wred[w] = s;
+    __syncthreads();
+    return wred[0] + wred[1] + wred[2] + wred[3];
+}
+
+// The score of a step (score_out, a decoding session opened with scores): for utterance b at generated step gen, with the FINAL picks t[k]
+// of the groups (a forced token replaces the draw first),
+//     term[gen] = sum over k < nq, in k order, of ( (x_k[t[k]] - m_k) - logf(sum_v exp(x_k[v] - m_k)) ),
+// the log of the probability LauraGenModel.sampling_ids gives the picks before any top-k / nucleus truncation (laura_model.py:466-499:
+// softmax over the group's own G = K + 1 logits; step_logp's rows are the whole-vocabulary log-softmax instead).  A function of the step's
+// logits and the final picks only: the same bits in every sampling mode and for forced tokens (greedy mode, which draws nothing, runs
+// group_exp_total for it).  Thread 0 forms and writes it, for every step the sampler runs for the row, the ending <eos> step included.
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __shared__ __attribute__((aligned(16))) float val[FC_SAMPLE_MAXV];
     __shared__ __attribute__((aligned(16))) int idx[FC_SAMPLE_MAXV];
@@ -1236,6 +1271,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         for (int v = tid; v < V; v += 256) o[v] = (lg[v] - m) - ls;
         __syncthreads();
     }
+    float term = 0.f;                                // thread 0: the step's score
     for (int k = 0; k < a.nq; ++k) {
         const float* x = lg + k * G;
         // ---- group maximum and its FIRST index (greedy: weighted_scores.topk(1))
@@ -1265,21 +1301,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             if (wred[u] > m || (wred[u] == m && wredi[u] < mi)) { m = wred[u]; mi = wredi[u]; }
         __syncthreads();
         int pick = mi;
+        float norm = 0.f;                            // the group's sum of exp(x - max), where the step's score needs it
+        if (mode == 0 && a.score_out) norm = group_exp_total<false>(xr, m, G, val, idx, wred);
         if (mode != 0) {
             // unnormalised probabilities exp(x - max) (the normaliser cancels in every mode except the nucleus threshold)
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < XPT; ++i) {
-                const int v = tid + 256 * i;
-                const float e = v < G ? expf(xr[i] - m) : -1.f;      // padding sorts last
-                val[v] = e;
-                idx[v] = v;
-                if (v < G) s += e;
-            }
-            s = wave_sum(s);
-            if (lane == 0) wred[w] = s;
-            __syncthreads();
-            const float total = wred[0] + wred[1] + wred[2] + wred[3];
+            const float total = group_exp_total<true>(xr, m, G, val, idx, wred);
+            norm = total;
             int ncand = G;
             bool selected = false;                   // top-k candidates already in val[] / idx[] order
             if (mode == 2 && ki <= 64) {
@@ -1438,9 +1465,16 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         if (tid == 0) {
             if (forced && gen < max_steps) pick = (int)forced[((size_t)b * a.stride + gen) * a.nq + k];
             chosen[k] = pick;
+            if (a.score_out) {                       // from the logits row: val[] is sorted by now
+                const float t = (x[pick < 0 ? 0 : (pick < G ? pick : G - 1)] - m) - logf(norm);
+                term = k == 0 ? t : term + t;
+            }
         }
         __syncthreads();
     }
+    // the step's score, for a step that runs for the row (`active` below).  Written here, not in the bookkeeping at the end: the pointer
+    // live across embed_next cost the kernel a private segment (68 bytes per lane reserved, no access to it) even when it is null
+    if (tid == 0 && a.score_out && !was_done && gen < max_steps) a.score_out[(size_t)b * a.stride + gen] = term;
     // ---- bookkeeping of decode_codec (laura_model.py:519-546): a step whose ids contain <eos> ends the utterance and is dropped
     bool eos = false;
     for (int k = 0; k < a.nq; ++k) eos = eos || chosen[k] == a.K;
@@ -1469,7 +1503,7 @@ hipError_t launch_sample(const Sample& s, hipStream_t st) {
     if (s.K + 1 > FC_SAMPLE_MAXV || s.nq > 8 || s.nq < 1) return hipErrorInvalidValue;
     if (s.emb_wt && (s.dm > 1024 || s.dm % 4 || s.D > FC_SAMPLE_MAXV)) return hipErrorInvalidValue;
     SampleArgs a{s.logits, s.K, s.nq, s.mode, s.ki, s.pf, s.seed, s.forced, s.max_steps, s.tokens, s.tok_stride, s.tok_off, s.n_gen,
-                 s.done, s.n_done, s.pos, s.step, s.logp_out, s.cb, s.D, s.next_emb, s.B,
+                 s.done, s.n_done, s.pos, s.step, s.logp_out, s.score_out, s.cb, s.D, s.next_emb, s.B,
                  s.emb_wt, s.emb_bias, s.emb_g, s.emb_b, s.dm, s.emb_relu, s.xscale, s.xs, s.launch_seq,
                  s.rows, s.rows ? s.row_stride : s.max_steps, s.row0};
     const int n = s.nrows > 0 ? s.nrows : s.B;
@@ -1481,7 +1515,7 @@ hipError_t launch_sample(const Sample& s, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------------------
 // One slot of a decoding session back to "nothing generated": its counters and position, its row of the sampling table, a zero LM
 // input row, its token row = the continual prompt (what copy_prompt_kernel does per call) followed by zeros, its forced tokens, zero
-// log-probability rows.  The other slots' rows are not touched.
+// log-probability rows, a zero score row.  The other slots' rows are not touched.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void slot_reset_kernel(SlotReset r) {
     const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
@@ -1501,6 +1535,8 @@ __global__ __launch_bounds__(256) void slot_reset_kernel(SlotReset r) {
         const size_t nl = (size_t)r.row.max_steps * r.V;
         for (size_t i = tid; i < nl; i += nth) r.logp[(size_t)b * r.tok_stride * r.V + i] = 0.f;
     }
+    if (r.score)
+        for (size_t i = tid; i < (size_t)r.tok_stride; i += nth) r.score[(size_t)b * r.tok_stride + i] = 0.f;
 }
 hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st) {
     if (r.slot < 0 || r.cont_len < 0 || r.row.max_steps < 0 || r.cont_len + r.row.max_steps > r.tok_stride) return hipErrorInvalidValue;
@@ -1585,11 +1621,32 @@ hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st) {
 //   pos is the copy's (prefix_copy_kernel with P + keep - 1 positions) or, in place, set here.
 //   blocks 1 ..: grid-stride over 16-byte vectors of the token row ([0, cont_len + keep) kept, zeros behind), the forced row (the
 //   source's) and the log-probability rows ([0, keep) kept, zeros up to max_steps: take(return_logp) relies on rows never run being
-//   zero).  In place the kept parts are not touched, only the zeros behind them are written.  Every vector lies inside the slot's own
+//   zero) and, in a session with scores, the score row ([0, keep) kept, zeros behind to the row's end, so a branched utterance carries
+//   the score of its whole path and holds no term of the steps it left).  In place the kept parts are not touched, only the zeros behind them are written.  Every vector lies inside the slot's own
 //   row: tok_stride % 4 == 0, so a row's length is a whole number of vectors and its start is 16-byte aligned.
 // A source that is running may be stepped again behind this launch: rows [0, keep) of its tables never change once written.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+// A float row of the branch: floats [0, ncopy) of `src` kept, zeros behind them up to vector nvec (16-byte vectors; both rows start
+// 16-byte aligned).  In place (same) the kept floats are not touched: the floats up to the next vector boundary one by one, whole
+// vectors behind.  Thread t0 of nth.
+__device__ __forceinline__ void branch_f32_row(const float* src, float* dst, size_t ncopy, size_t nvec, bool same, size_t t0, size_t nth) {
+    const f32x4* sv = (const f32x4*)src;
+    f32x4* dv = (f32x4*)dst;
+    if (same && t0 < 4 && ncopy + t0 < ((ncopy + 3) & ~(size_t)3)) dst[ncopy + t0] = 0.f;
+    for (size_t i = (same ? (ncopy + 3) >> 2 : 0) + t0; i < nvec; i += nth) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (4 * i < ncopy) v = sv[i];
+        if (4 * i + 3 >= ncopy) {                                     // the vector the kept part ends in, or one behind it
+            if (4 * i >= ncopy) v.x = 0.f;
+            if (4 * i + 1 >= ncopy) v.y = 0.f;
+            if (4 * i + 2 >= ncopy) v.z = 0.f;
+            v.w = 0.f;
+        }
+        dv[i] = v;
+    }
+}
 
 __global__ __launch_bounds__(256) void slot_branch_kernel(SlotBranch r) {
     __shared__ __attribute__((aligned(16))) float val[FC_SAMPLE_MAXV];
@@ -1632,23 +1689,13 @@ __global__ __launch_bounds__(256) void slot_branch_kernel(SlotBranch r) {
         i64x2* dv = (i64x2*)(r.forced + (size_t)d * ntok);
         for (size_t i = t0; i < nf; i += nth) dv[i] = sv[i];
     }
-    if (r.logp) {
-        const size_t ncopy = (size_t)r.keep * r.V, nl = ((size_t)r.row.max_steps * r.V + 3) >> 2;
-        const f32x4* sv = (const f32x4*)(r.logp + (size_t)s * r.tok_stride * r.V);
-        f32x4* dv = (f32x4*)(r.logp + (size_t)d * r.tok_stride * r.V);
-        if (same && t0 < 4 && ncopy + t0 < ((ncopy + 3) & ~(size_t)3)) r.logp[(size_t)d * r.tok_stride * r.V + ncopy + t0] = 0.f;
-        for (size_t i = (same ? (ncopy + 3) >> 2 : 0) + t0; i < nl; i += nth) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (4 * i < ncopy) v = sv[i];
-            if (4 * i + 3 >= ncopy) {                                 // the vector the kept part ends in, or one behind it
-                if (4 * i >= ncopy) v.x = 0.f;
-                if (4 * i + 1 >= ncopy) v.y = 0.f;
-                if (4 * i + 2 >= ncopy) v.z = 0.f;
-                v.w = 0.f;
-            }
-            dv[i] = v;
-        }
-    }
+    // the log-probability rows up to max_steps, the score row to its end (as the token row: a term is one float per step)
+    if (r.logp)
+        branch_f32_row(r.logp + (size_t)s * r.tok_stride * r.V, r.logp + (size_t)d * r.tok_stride * r.V, (size_t)r.keep * r.V,
+                       ((size_t)r.row.max_steps * r.V + 3) >> 2, same, t0, nth);
+    if (r.score)
+        branch_f32_row(r.score + (size_t)s * r.tok_stride, r.score + (size_t)d * r.tok_stride, (size_t)r.keep, (size_t)r.tok_stride >> 2, same,
+                       t0, nth);
 }
 hipError_t launch_slot_branch(const SlotBranch& r, hipStream_t st) {
     if (r.S < 1 || r.dst < 0 || r.dst >= r.S || r.src < 0 || r.src >= r.S || r.keep < 1 || r.cont_len < 0 || r.P < 1) return hipErrorInvalidValue;

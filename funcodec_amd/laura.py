@@ -272,11 +272,12 @@ class LauraEngine:
         lens = [int(v) for v in out_lens]
         return (tokens, lens, logp) if return_logp else (tokens, lens)
 
-    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True) -> "DecodeSlots":
+    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False) -> "DecodeSlots":
         """A decoding session of `slots` slots (1 .. 16): prompts join and leave a running batch.  max_positions (default: the engine's)
         bounds text_len + 2 + prompt tokens + max_length of a slot and sizes the session's state; logp=False leaves out the per-step
-        log-probabilities [slots, max_positions, vocab], the largest part of it."""
-        return DecodeSlots(self, slots, max_positions, logp)
+        log-probabilities [slots, max_positions, vocab], the largest part of it.  score=True keeps one number per slot and step, the
+        log-probability of the step's picks (DecodeSlots.score): [slots, max_positions] floats."""
+        return DecodeSlots(self, slots, max_positions, logp, score)
 
     # -- LauraGenModel.cal_codec_emb on one-hot probabilities (syn_audio) ---------------------------------------------------
     @_on_device
@@ -327,11 +328,12 @@ class DecodeSlots:
     decoding steps, ``take`` returns what an ended slot generated and frees it.  A slot depends on nothing but its own prompt and
     parameters; a session of one slot is ``decode_codec`` on the prompt alone, bit for bit."""
 
-    def __init__(self, engine: "LauraEngine", slots: int, max_positions: Optional[int] = None, logp: bool = True):
+    def __init__(self, engine: "LauraEngine", slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False):
         self.engine, self.lib, self.device = engine, engine.lib, engine.device
         self.slots = int(slots)
         self.max_positions = int(engine.max_positions if max_positions is None else max_positions)
         self.with_logp = bool(logp)
+        self.with_score = bool(score)
         self._h = None
         self._max_length = [0] * max(self.slots, 0)
         self._status = (C.c_int32 * max(self.slots, 1))()
@@ -341,14 +343,21 @@ class DecodeSlots:
     @_on_device
     def _open(self):
         eng = self.engine
-        nbytes = int(self.lib.fc_laura_slots_state_bytes(eng._h, self.slots, self.max_positions, int(self.with_logp)))
+        if self.with_score:
+            nbytes = int(self.lib.fc_laura_slots_state_bytes_scored(eng._h, self.slots, self.max_positions, int(self.with_logp), 1))
+        else:                                                            # the session without scores: the call it always was
+            nbytes = int(self.lib.fc_laura_slots_state_bytes(eng._h, self.slots, self.max_positions, int(self.with_logp)))
         #: everything the session carries between calls (fc_laura_slots_state_bytes): one allocation
         self.state = torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=self.device) if nbytes else None
         if self.state is not None:
             torch.cuda.current_stream(self.device).synchronize()      # fc_laura_slots_create writes with copies that this stream does not order
         h = C.c_void_p()
-        eng._check(self.lib.fc_laura_slots_create(eng._h, self.slots, self.max_positions, int(self.with_logp), _ptr(self.state), nbytes,
-                                                  C.byref(h)))
+        if self.with_score:
+            eng._check(self.lib.fc_laura_slots_create_scored(eng._h, self.slots, self.max_positions, int(self.with_logp), 1, _ptr(self.state),
+                                                             nbytes, C.byref(h)))
+        else:
+            eng._check(self.lib.fc_laura_slots_create(eng._h, self.slots, self.max_positions, int(self.with_logp), _ptr(self.state), nbytes,
+                                                      C.byref(h)))
         self._h = h
 
     def free(self) -> None:
@@ -523,13 +532,45 @@ class DecodeSlots:
         return {i: SLOT_STATES[int(self._status[i])] for i in range(self.slots) if int(self._status[i]) in SLOT_STATES}
 
     @_on_device
-    def take(self, slot: int, return_logp: bool = False):
-        """What an ended slot generated: (tokens [len, nq] int64 = prompt tokens + generated ones, len) and, with return_logp, the
-        per-step log-probabilities [max_length, vocab].  The slot is free afterwards.  Refused for a slot that has not ended."""
+    def score_row(self, slot: int):
+        """The score row of a slot that holds an utterance, running or ended: (row float32 [max_positions] on the host, count, end).
+        row[j] is the log-probability of generated step j's picks: the sum over the groups of log softmax(logits[group])[pick], the
+        probability the reference's ``sampling_ids`` gives the pick before any top-k / nucleus truncation, a forced token counting as
+        the pick.  It is a function of the step's logits and picks only: the same bits in every sampling mode.  count = the terms
+        written: the tokens generated as the last ``step`` reported (after a fork or rewind: the tokens kept), plus the ending step of
+        a slot that ended on <eos>; the row is zero behind them.  end: 0 running, 1 ended by length, 2 ended on <eos>.  Refused, with
+        the slot named, for a session opened without score=True."""
         h = self._handle()
         slot = int(slot)
         if not 0 <= slot < self.slots:
             raise EngineError(f"decoding session: slot {slot} outside 0 .. {self.slots - 1}")
+        if not self.with_score:
+            raise EngineError(f"decoding session: slot {slot}: the session was opened without scores (open_decode(score=True))")
+        row = torch.zeros(self.max_positions, dtype=torch.float32)
+        torch.cuda.current_stream(self.device).synchronize()          # the copy runs on the session's stream
+        count, end = C.c_int32(0), C.c_int32(0)
+        self.engine._check(self.lib.fc_laura_slots_score(h, slot, C.c_void_p(row.data_ptr()), row.numel(), C.byref(count), C.byref(end)))
+        return row, int(count.value), int(end.value)
+
+    def score(self, slot: int):
+        """(sum, count, ended_on_eos) of an ended slot, which stays as it is: the float64 sum, on the host, of the fp32 terms
+        [0, count) of ``score_row``.  ``pick_best`` ranks these.  Refused for a slot that has not ended, and for a session without
+        scores."""
+        row, count, end = self.score_row(slot)
+        if end == 0:
+            raise EngineError(f"decoding session: slot {int(slot)} has not ended")
+        return float(row[:count].double().sum()), count, end == 2
+
+    @_on_device
+    def take(self, slot: int, return_logp: bool = False, return_score: bool = False):
+        """What an ended slot generated: (tokens [len, nq] int64 = prompt tokens + generated ones, len) and, with return_logp, the
+        per-step log-probabilities [max_length, vocab]; with return_score, (sum, count, ended_on_eos) as ``score`` gives it is appended.
+        The slot is free afterwards.  Refused for a slot that has not ended."""
+        h = self._handle()
+        slot = int(slot)
+        if not 0 <= slot < self.slots:
+            raise EngineError(f"decoding session: slot {slot} outside 0 .. {self.slots - 1}")
+        scored = self.score(slot) if return_score else None            # ahead of the take, which frees the slot
         nq = self.engine.spec.predict_nq
         cap = self.max_positions
         tokens = torch.zeros((cap, nq), dtype=torch.int64, device=self.device)
@@ -540,7 +581,8 @@ class DecodeSlots:
         n = C.c_int32(0)
         self.engine._check(self.lib.fc_laura_slots_take(h, slot, _ptr(tokens), cap, C.byref(n), _ptr(logp)))
         tokens = tokens[: n.value].clone()
-        return (tokens, int(n.value), logp) if return_logp else (tokens, int(n.value))
+        out = (tokens, int(n.value), logp) if return_logp else (tokens, int(n.value))
+        return out + (scored,) if return_score else out
 
 
 def refill(pending: Sequence[int], free_slots: Sequence[int]) -> List[tuple]:
@@ -675,6 +717,51 @@ def drive_retries(session, slots: int, n_requests: int, samples: int, retries: i
     return drive_samples(_Retrying(), slots, n_requests, samples, start_, start_from_, step_n)
 
 
+def pick_best(scores: Sequence[tuple]) -> int:
+    """The ranking rule of ``generate_many(keep="best")``, a plain function of the candidates' (sum, count, ended_on_eos) as
+    ``DecodeSlots.score`` gives them: the index of the candidate kept.  A candidate that ended on <eos> ranks above every candidate
+    that ran to max_length (a run-away is what `retries` exists to get rid of); within a class the higher mean log-probability per
+    step, sum / count, wins; ties go to the lower index.  count == 0 cannot occur for an ended slot and is refused."""
+    if len(scores) < 1:
+        raise ValueError("pick_best: no candidates")
+    best, best_key = -1, None
+    for i, (total, count, eos) in enumerate(scores):
+        if int(count) < 1:
+            raise ValueError(f"pick_best: candidate {i} has count {count}: an ended slot has at least one scored step")
+        key = (1 if eos else 0, float(total) / int(count))
+        if best_key is None or key > best_key:
+            best, best_key = i, key
+    return best
+
+
+def drive_best(session, slots: int, n_requests: int, samples: int, retries: int, max_length: int, start, start_from, rewind,
+               step_n: int = 1) -> list:
+    """``drive_samples`` (retries = 0) or ``drive_retries`` on a session opened with score=True, every candidate taken with its score
+    (``session.take(slot, return_score=True)``: the last element of the take), then ``pick_best`` per request.  The drivers, their
+    arrival order and which candidates start from a sibling are unchanged; a rewound candidate is ranked by its last attempt, whose
+    score is that of its whole final path.  Returns [(k, take of candidate k)], one per request."""
+
+    class _Scored:
+        def step(self, n):
+            return session.step(n)
+
+        def n_gen(self, slot):
+            return session.n_gen(slot)
+
+        def take(self, slot):
+            return session.take(slot, return_score=True)
+
+    if retries == 0:
+        rows = drive_samples(_Scored(), slots, n_requests, samples, start, start_from, step_n)
+    else:
+        rows = drive_retries(_Scored(), slots, n_requests, samples, retries, max_length, start, start_from, rewind, step_n)
+    kept = []
+    for row in rows:
+        k = pick_best([t[-1] for t in row])
+        kept.append((k, row[k]))
+    return kept
+
+
 class LauraGenMI355X:
     """Drop-in for the inference surface of ``LauraGenModel``: same method names, argument meaning and return values
     (batch-1 tensors in, tensors out) as funcodec/models/audio_generation/laura_model.py, plus ``*_batch`` forms."""
@@ -736,8 +823,8 @@ class LauraGenMI355X:
         return self.engine.decode_codec(text, text_lengths, max_length, sampling, self._next_seed() if seed is None else seed, continual,
                                         continual_lengths)
 
-    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True) -> DecodeSlots:
-        return self.engine.open_decode(slots, max_positions, logp)
+    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False) -> DecodeSlots:
+        return self.engine.open_decode(slots, max_positions, logp, score)
 
     @torch.no_grad()
     def cal_codec_emb_batch(self, text, text_lengths, codec, codec_lengths):

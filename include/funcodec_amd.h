@@ -732,6 +732,24 @@ int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_lengt
  * sampling arguments, a source that follows forced tokens with a max_length beyond them.  A running `dst` != `src` is abandoned. */
 int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_length, int sampling_mode, int sampling_k, float sampling_p,
                         uint64_t seed, void* stream);
+/* A session that scores its candidates (with_score != 0; 0 is fc_laura_slots_state_bytes / fc_laura_slots_create, bit for bit and launch
+ * for launch): one fp32 term per slot and generated step, [S][max_positions] floats behind everything else in `state`,
+ *     term[j] = sum over the predict_nq groups k, in k order, of  x_k[t_k] - max(x_k) - log(sum_v exp(x_k[v] - max(x_k)))
+ * with x_k the group's codebook_size + 1 logits of step j and t_k the step's FINAL pick (a forced token counts as the pick): the log of
+ * the probability LauraGenModel.sampling_ids (laura_model.py:466-499) gives the picks before any top-k / nucleus truncation.  It is a
+ * function of the step's logits and picks only -- the same bits in every sampling mode and for forced tokens -- and is written for every
+ * step the slot's sampler runs, the ending <eos> step included.  start / start_from zero the slot's row; fork copies terms [0, keep) from
+ * the source and zeroes the rest of the row (in place: only the zeros), so a branched utterance has the score of its whole path.  Nothing
+ * is summed on the device. */
+size_t fc_laura_slots_state_bytes_scored(const fc_laura* e, int slots, int max_positions, int with_logp, int with_score);
+int  fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
+                                  fc_laura_slots** out);
+/* The score row of a slot that holds an utterance (running or ended; the slot keeps it: call this ahead of fc_laura_slots_take):
+ *   terms      HOST f32 [cap], cap >= max_positions: the slot's whole row, zeros behind the terms written
+ *   count_out  host: terms written as fc_laura_slots_step last reported -- n_gen, plus 1 for a slot that ended on <eos>
+ *   end_out    host: 0 the slot is running, 1 it ended by length, 2 it ended on <eos> (ended with n_gen < max_length)
+ * Refused, with the slot named: a session created without scores, a slot outside 0 .. S - 1, a free, never-started or failed slot. */
+int fc_laura_slots_score(fc_laura_slots* s, int slot, float* terms, int cap, int32_t* count_out, int32_t* end_out);
 
 #ifdef __cplusplus
 }

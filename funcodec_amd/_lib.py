@@ -174,6 +174,8 @@ SYMBOLS = {
     "fc_laura_slots_state_bytes_scored": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "fc_laura_slots_create_scored": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
     "fc_laura_slots_score": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # a slot's sampling rules (temperature, min_length, top_p, repeat_window, repeat_count): written by the next start / start_from / fork
+    "fc_laura_slots_set_rules": (C.c_int, [_P, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int]),
 }
 
 _lib = None

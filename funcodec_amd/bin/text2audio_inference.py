@@ -194,7 +194,7 @@ class Text2Audio:
     @torch.no_grad()
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
-                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all"):
+                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all", rules=None):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
         request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.
@@ -214,7 +214,10 @@ class Text2Audio:
         then the higher mean log-probability per step, ties to the lower index; with retries, a candidate's last attempt by the score
         of its whole final path -- and only the winners reach the fine predictor and the codec decoder.  Returns (rets, codecs,
         choice): rets[i], codecs[i] in the shape of samples = 1, choice[i] = (k, mean) of the candidate kept.  The candidates are,
-        token for token, those of keep = "all" (the default: today's call, a session without scores) with the same seeds."""
+        token for token, those of keep = "all" (the default: today's call, a session without scores) with the same seeds.
+
+        rules = a ``laura.SamplingRules`` (temperature, min_length, top_p with an integer ``sampling``, the repeat rule) for every
+        candidate: every start, start_from and rewind of the call carries it.  None is the call without rules."""
         from ..laura import drive_best, drive_retries, drive_samples, retry_seed
         m, nq = self.model, self.model.predict_nq
         n, N, R = len(texts), int(samples), int(retries)
@@ -249,13 +252,13 @@ class Text2Audio:
                 if N == 1 or outs[i] is None:
                     to, ln = self._encode_texts([texts[i]])
                     outs[i], lens[i] = to[0, : ln[0]], ln[0]
-                session.start(slot, outs[i], lens[i], self.max_length, self.sampling, seeds[c], None if per is None else per[i])
+                session.start(slot, outs[i], lens[i], self.max_length, self.sampling, seeds[c], None if per is None else per[i], rules=rules)
 
             def start_from(slot, src, c):
-                session.start_from(slot, src, self.max_length, self.sampling, seeds[c])
+                session.start_from(slot, src, self.max_length, self.sampling, seeds[c], rules=rules)
 
             def rewind(slot, c, keep, attempt):
-                session.rewind(slot, keep, self.max_length, self.sampling, retry_seed(seeds[c], attempt))
+                session.rewind(slot, keep, self.max_length, self.sampling, retry_seed(seeds[c], attempt), rules=rules)
             choice = None
             if best:
                 kept = drive_best(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)

@@ -768,6 +768,7 @@ struct fc_laura_slots {
     std::vector<int> state, cont_len, max_len, n_gen;
     std::vector<int> text_len, prefix;      // of the prompt a slot holds: text tokens, prefix positions P = text_len + 2 + cont_len
     std::vector<int> forced_on;             // the slot's utterance follows forced tokens (rows [0, max_len) of its forced row)
+    std::vector<lk::SampleRow> rules;       // per slot, the rule fields only (fc_laura_slots_set_rules): into the slot's row at every start / fork
     hipGraphExec_t gexec = nullptr;         // the captured step, and the form it holds
     bool g_persist = false, g_timeout = false;
     bool warmed[2] = {false, false};        // one eager step run per form (sets the kernels' LDS attributes, which a capture cannot)
@@ -848,6 +849,23 @@ int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, i
     return cx.err;
 }
 
+// the slot's rules against the sampling mode of the start / start_from / fork that is about to write them
+int check_rules_mode(const fc_laura_slots* s, int slot, int mode) {
+    const lk::SampleRow& r = s->rules[slot];
+    if (r.top_p > 0.f && mode != 2)
+        return fail("decoding session: slot " + std::to_string(slot) + ": top_p applies with top-k sampling (an integer `sampling`) only");
+    if (r.repeat_window > 0 && mode == 0)
+        return fail("decoding session: slot " + std::to_string(slot) + ": the repeat rule needs a drawing mode, not greedy");
+    return 0;
+}
+
+// the slot's rules into a row of the sampling table
+void put_rules(const fc_laura_slots* s, int slot, lk::SampleRow& row) {
+    const lk::SampleRow& r = s->rules[slot];
+    row.temperature = r.temperature; row.min_length = r.min_length; row.top_p = r.top_p;
+    row.repeat_window = r.repeat_window; row.repeat_count = r.repeat_count;
+}
+
 int check_sampling(int mode, int k, float p) {
     if (mode < 0 || mode > 3) return fail("sampling_mode must be 0..3");
     if (mode == 2 && k < 1) return fail("top-k sampling needs sampling_k >= 1");
@@ -866,6 +884,7 @@ int slots_from_prefix(fc_laura_slots* s, int dst, int src, int max_length, int s
     lk::SampleRow row{};
     row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
     row.forced_on = forced ? 1 : 0; row.rng_row = 0u;
+    put_rules(s, dst, row);
     // from here on the destination's previous utterance is gone (as a start on a running slot abandons it)
     s->state[dst] = SLOT_FAILED; s->n_gen[dst] = 0; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
     s->text_len[dst] = s->text_len[src]; s->prefix[dst] = P; s->forced_on[dst] = forced ? 1 : 0;
@@ -1197,7 +1216,8 @@ int fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int 
     HIP_TRY(hipMemset(m.nemb, 0, (size_t)16 * e->arch.codebook_dim * sizeof(float)));
     HIP_TRY(hipMemset(m.edge, 0, m.edge_stride * S.s.layers * sizeof(float)));
     HIP_TRY(hipMemset(m.psync, 0, (m.sync_words + 32) * sizeof(unsigned)));
-    HIP_TRY(hipMemset(s->rows, 0, (size_t)slots * sizeof(lk::SampleRow)));
+    s->rules.assign(slots, lk::SampleRow{});                // the neutral rules
+    HIP_TRY(hipMemcpy(s->rows, s->rules.data(), (size_t)slots * sizeof(lk::SampleRow), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(s->tok_off, 0, (size_t)slots * sizeof(int)));
     if (s->score) HIP_TRY(hipMemset(s->score, 0, (size_t)slots * max_positions * sizeof(float)));
     std::vector<int> ones(slots, 1);
@@ -1233,7 +1253,7 @@ int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, in
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
     if (!text_outs || !workspace || text_len < 1 || max_length < 1 || cont_len < 0 || (cont_len > 0 && !continual))
         return fail("decoding session: bad argument for slot " + std::to_string(slot));
-    if (check_sampling(sampling_mode, sampling_k, sampling_p)) return 1;
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, slot, sampling_mode)) return 1;
     const int need = text_len + 2 + cont_len + max_length;
     if (need > s->R)
         return fail("decoding session: slot " + std::to_string(slot) + ": text_len + 2 + cont_len + max_length = " + std::to_string(need) +
@@ -1241,6 +1261,7 @@ int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, in
     lk::SampleRow row{};
     row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
     row.forced_on = forced ? 1 : 0; row.rng_row = 0u;      // the slot index is NOT in the Philox counter: a slot's draws are its own
+    put_rules(s, slot, row);
     {
         Ctx dry = make_ctx(1, nullptr, 0, nullptr);
         slots_prefix(s, dry, slot, nullptr, text_len, nullptr, cont_len, row, nullptr);
@@ -1268,7 +1289,7 @@ int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_lengt
         return fail("decoding session: source slot " + std::to_string(src) + " holds no utterance (" +
                     (s->state[src] == SLOT_FAILED ? "failed" : "free or never started") + ")");
     if (max_length < 1) return fail("decoding session: bad argument for slot " + std::to_string(dst));
-    if (check_sampling(sampling_mode, sampling_k, sampling_p)) return 1;
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, dst, sampling_mode)) return 1;
     const int P = s->prefix[src], cont_len = s->cont_len[src];
     if (P + max_length > s->R)
         return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
@@ -1295,7 +1316,7 @@ int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_l
     if (max_length <= keep)
         return fail("decoding session: slot " + std::to_string(dst) + ": max_length " + std::to_string(max_length) + " leaves nothing to generate after keep " +
                     std::to_string(keep));
-    if (check_sampling(sampling_mode, sampling_k, sampling_p)) return 1;
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, dst, sampling_mode)) return 1;
     const int P = s->prefix[src], cont_len = s->cont_len[src];
     if (P + max_length > s->R)
         return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
@@ -1326,6 +1347,7 @@ int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_l
     r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off; r.rows = s->rows;
     r.row.mode = sampling_mode; r.row.ki = sampling_k; r.row.pf = sampling_p; r.row.max_steps = max_length; r.row.seed = seed;
     r.row.forced_on = forced_on; r.row.rng_row = 0u;
+    put_rules(s, dst, r.row);
     r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len; r.forced = s->forced; r.forced_rows = forced_rows;
     r.logp = s->logp; r.V = V; r.score = s->score;
     r.cb = sm.cb; r.K = sm.K; r.D = sm.D; r.next_emb = sm.next_emb; r.emb_wt = sm.emb_wt; r.emb_bias = sm.emb_bias; r.emb_g = sm.emb_g;
@@ -1333,6 +1355,22 @@ int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_l
     cx.check(lk::launch_slot_branch(r, cx.st), "slot branch");
     if (cx.err) return 1;
     s->state[dst] = SLOT_RUNNING;
+    return 0;
+}
+
+int fc_laura_slots_set_rules(fc_laura_slots* s, int slot, float temperature, int min_length, float top_p, int repeat_window, int repeat_count) {
+    if (!s) return fail("null session");
+    if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
+    const std::string who = "decoding session: slot " + std::to_string(slot) + ": ";
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) return fail(who + "temperature must be finite and > 0");
+    if (min_length < 0) return fail(who + "min_length " + std::to_string(min_length) + " < 0");
+    if (!(top_p >= 0.f && top_p <= 1.f)) return fail(who + "top_p must lie in (0, 1], or be 0 for none");
+    if (repeat_window < 0 || repeat_window > 256) return fail(who + "repeat_window " + std::to_string(repeat_window) + " outside 0 .. 256");
+    if (repeat_window > 0 && (repeat_count < 1 || repeat_count > repeat_window))
+        return fail(who + "repeat_count " + std::to_string(repeat_count) + " outside 1 .. repeat_window " + std::to_string(repeat_window));
+    lk::SampleRow& r = s->rules[slot];
+    r.temperature = temperature; r.min_length = min_length; r.top_p = top_p;
+    r.repeat_window = repeat_window; r.repeat_count = repeat_window > 0 ? repeat_count : 1;
     return 0;
 }
 

@@ -110,6 +110,12 @@ struct SampleRow {
     unsigned long long seed;
     int forced_on;                  // 0: this row samples even when the launch has a forced-token buffer
     unsigned rng_row;               // second word of the row's Philox counter (decode_codec: the batch row)
+    // the slot's sampling rules (fc_laura_slots_set_rules; the defaults are the neutral rules: the sampler without them, bit for bit)
+    float temperature = 1.f;        // logits are divided by it, finite and > 0
+    int min_length = 0;             // <eos> is -inf in every group while fewer tokens than this are generated
+    float top_p = 0.f;              // mode 2 only, 0 = none: the top-k candidates cut to the nucleus of top_p
+    int repeat_window = 0;          // 0 = off, <= 256: a drawn id that fills the last repeat_window generated tokens of its group ...
+    int repeat_count = 1;           // ... at least repeat_count times is drawn again from the whole group
 };
 
 struct Sample {

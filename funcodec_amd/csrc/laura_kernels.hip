@@ -1218,6 +1218,61 @@ __device__ __forceinline__ float group_exp_total(const float (&xr)[FC_SAMPLE_MAX
     return wred[0] + wred[1] + wred[2] + wred[3];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// One draw by inverse CDF over the first ncand candidates of val[] / idx[] in their order: chunk sums, then an exact walk inside the
+// chunk.  The uniform number is Philox of (seed, step, rng_row, word).  All 256 threads call it; returns the drawn candidate's id to
+// every thread.  csum[256] and sh_pick are the caller's LDS.  The sampler's first draw of a group (word = the group) and the repeat
+// rule's second draw (word = 8 + the group) both go through here and nowhere else.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int draw_inverse_cdf(const float* val, const int* idx, int ncand, float* csum, int* sh_pick,
+                                                unsigned long long seed, unsigned step, unsigned rng_row, unsigned word) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int CH = (ncand + 255) / 256;
+    float cs = 0.f;
+    for (int i = tid * CH; i < (tid + 1) * CH && i < ncand; ++i) cs += val[i];
+    csum[tid] = cs;
+    __syncthreads();
+    if (w == 0) {        // wave 0: lane l owns chunks 4l .. 4l+3; prefix sums by shuffles, then one lane walks its chunks / elements
+        const float c0 = csum[4 * lane], c1 = csum[4 * lane + 1], c2 = csum[4 * lane + 2], c3 = csum[4 * lane + 3];
+        const float mine = (c0 + c1) + (c2 + c3);
+        float incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float t = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += t;
+        }
+        const float tot = __shfl(incl, 63, 64);
+        const float u = philox_uniform(seed, step, rng_row, word);
+        const float target = u * tot;
+        const float below = incl - mine;
+        // the lane whose range [below, incl) holds the target; rounding at the very top goes to the last non-empty lane
+        const unsigned long long nonempty = __ballot(mine > 0.f);
+        const unsigned long long ballot = __ballot(mine > 0.f && target >= below && target < incl);
+        const int owner = ballot ? (int)__ffsll((long long)ballot) - 1 : (nonempty ? 63 - __clzll((long long)nonempty) : 0);
+        if (lane == owner) {
+            float run = below;
+            int c = 0;                                  // the first of the lane's chunks 0 .. 2 that the target falls in, else chunk 3
+            if (run + c0 <= target) {
+                run += c0; c = 1;
+                if (run + c1 <= target) {
+                    run += c1; c = 2;
+                    if (run + c2 <= target) { run += c2; c = 3; }
+                }
+            }
+            int i = (4 * lane + c) * CH;
+            const int iend = (4 * lane + c + 1) * CH < ncand ? (4 * lane + c + 1) * CH : ncand;
+            while (i + 1 < iend && run + val[i] <= target) { run += val[i]; ++i; }
+            if (i >= ncand) i = ncand - 1;
+            if (i < 0) i = 0;
+            *sh_pick = idx[i];
+        }
+    }
+    __syncthreads();
+    const int pick = *sh_pick;
+    __syncthreads();
+    return pick;
+}
+
 // The score of a step (score_out, a decoding session opened with scores): for utterance b at generated step gen, with the FINAL picks t[k]
 // of the groups (a forced token replaces the draw first),
 //     term[gen] = sum over k < nq, in k order, of ( (x_k[t[k]] - m_k) - logf(sum_v exp(x_k[v] - m_k)) ),
@@ -1225,6 +1280,13 @@ __device__ __forceinline__ float group_exp_total(const float (&xr)[FC_SAMPLE_MAX
 // softmax over the group's own G = K + 1 logits; step_logp's rows are the whole-vocabulary log-softmax instead).  A function of the step's
 // logits and the final picks only: the same bits in every sampling mode and for forced tokens (greedy mode, which draws nothing, runs
 // group_exp_total for it).  Thread 0 forms and writes it, for every step the sampler runs for the row, the ending <eos> step included.
+//
+// A row's sampling rules (SampleRow, stated in full at fc_laura_slots_set_rules): x above is the group's logits AFTER the temperature
+// (x / T, an fp32 division) and the minimum length (<eos> = -inf while gen < min_length), so the arg-max, the softmax total, the top-k
+// select, the nucleus walk and the score all see that vector; logp_out stays the log-softmax of the raw logits.  top_p cuts the top-k
+// candidates to their nucleus; the repeat rule draws a second time, from the whole group in index order, when the first draw fills the
+// window.  While <eos> is masked it is the last candidate in every order (probability 0, the highest index) and is left out of the
+// candidates, so no rounding of the draw can return it.  The neutral rules skip every one of these statements.
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __shared__ __attribute__((aligned(16))) float val[FC_SAMPLE_MAXV];
     __shared__ __attribute__((aligned(16))) int idx[FC_SAMPLE_MAXV];
@@ -1251,6 +1313,15 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const int step = a.step[b];          // per-utterance sample counter (RNG stream position)
     const int gen = a.n_gen[b];
     const bool was_done = a.done[b] != 0;
+    // the row's rules (a call without a table has the neutral ones), through LDS: as five more scalars, or read through `row` where
+    // they are used, they cost the kernel a private segment (68 / 100 bytes per lane reserved, no access to it)
+    __shared__ float sh_rf[2];                       // temperature, top_p
+    __shared__ int sh_ri[3];                         // min_length, repeat_window, repeat_count
+    if (tid == 0) {
+        sh_rf[0] = row ? row->temperature : 1.f; sh_rf[1] = row ? row->top_p : 0.f;
+        sh_ri[0] = row ? row->min_length : 0; sh_ri[1] = row ? row->repeat_window : 0; sh_ri[2] = row ? row->repeat_count : 1;
+    }
+    __syncthreads();
     const float* lg = a.logits + (size_t)b * V;
     // log-softmax over the whole vocabulary of the step (TransformerEmbedLM.score, transformer_lm.py:309-311), when asked for
     if (a.logp_out && !was_done && gen < max_steps) {
@@ -1281,6 +1352,18 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         float xr[XPT];
 #pragma unroll
         for (int i = 0; i < XPT; ++i) { const int v = tid + 256 * i; xr[i] = x[v < G ? v : G - 1]; }
+        // rules 1 and 2: everything below sees x / T with <eos> masked
+        const float temp = sh_rf[0];
+        const bool no_eos = gen < sh_ri[0];           // <eos> masked at this step
+        if (temp != 1.f) {
+#pragma unroll
+            for (int i = 0; i < XPT; ++i) xr[i] = __fdiv_rn(xr[i], temp);
+        }
+        if (no_eos) {
+#pragma unroll
+            for (int i = 0; i < XPT; ++i)
+                if (tid + 256 * i >= G - 1) xr[i] = -INFINITY;          // <eos>, and the clamped copies of it behind the group
+        }
         float m = -INFINITY;
         int mi = 0x7fffffff;
 #pragma unroll
@@ -1422,51 +1505,50 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                     ncand = sh_i[0];
                 }
             }
-            // inverse CDF over the first ncand candidates in their order: chunk sums, then an exact walk inside the chunk
-            const int CH = (ncand + 255) / 256;
-            float cs = 0.f;
-            for (int i = tid * CH; i < (tid + 1) * CH && i < ncand; ++i) cs += val[i];
-            csum[tid] = cs;
-            __syncthreads();
-            if (w == 0) {        // wave 0: lane l owns chunks 4l .. 4l+3; prefix sums by shuffles, then one lane walks its chunks / elements
-                const float c0 = csum[4 * lane], c1 = csum[4 * lane + 1], c2 = csum[4 * lane + 2], c3 = csum[4 * lane + 3];
-                const float mine = (c0 + c1) + (c2 + c3);
-                float incl = mine;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const float t = __shfl_up(incl, o, 64);
-                    if (lane >= o) incl += t;
+            const float top_p = sh_rf[1];
+            const int rep_w = sh_ri[1];
+            if (mode == 2 && top_p > 0.f) {
+                // top-k with top-p: mode 3's walk over the top-k candidates, stopped at k
+                if (tid == 0) {
+                    float cum = 0.f;
+                    int n = 0;
+                    const float thr = top_p * total;
+                    while (n < ncand && cum < thr) { cum += val[n]; ++n; }
+                    sh_i[0] = n < 1 ? 1 : n;
                 }
-                const float tot = __shfl(incl, 63, 64);
-                const float u = philox_uniform(seed, (unsigned)step, rng_row, (unsigned)k);
-                const float target = u * tot;
-                const float below = incl - mine;
-                // the lane whose range [below, incl) holds the target; rounding at the very top goes to the last non-empty lane
-                const unsigned long long nonempty = __ballot(mine > 0.f);
-                const unsigned long long ballot = __ballot(mine > 0.f && target >= below && target < incl);
-                const int owner = ballot ? (int)__ffsll((long long)ballot) - 1 : (nonempty ? 63 - __clzll((long long)nonempty) : 0);
-                if (lane == owner) {
-                    const float cc[4] = {c0, c1, c2, c3};
-                    float run = below;
-                    int c = 0;
-                    while (c < 3 && run + cc[c] <= target) { run += cc[c]; ++c; }
-                    int i = (4 * lane + c) * CH;
-                    const int iend = (4 * lane + c + 1) * CH < ncand ? (4 * lane + c + 1) * CH : ncand;
-                    while (i + 1 < iend && run + val[i] <= target) { run += val[i]; ++i; }
-                    if (i >= ncand) i = ncand - 1;
-                    if (i < 0) i = 0;
-                    sh_i[1] = idx[i];
-                }
+                __syncthreads();
+                ncand = sh_i[0];
             }
-            __syncthreads();
-            pick = sh_i[1];
-            __syncthreads();
+            if (no_eos && ncand > G - 1) ncand = G - 1;
+            // the draw, and under the repeat rule at most one more (one statement of the draw for both: every condition is uniform)
+            for (unsigned word = (unsigned)k;; word += 8u) {
+                pick = draw_inverse_cdf(val, idx, ncand, csum, &sh_i[1], seed, (unsigned)step, rng_row, word);
+                if (rep_w <= 0 || word >= 8u) break;
+                // the repeat rule: how often the drawn id stands in the group's last rep_w generated tokens, one token per thread
+                const int j = gen - 1 - tid;
+                bool hit = false;
+                if (tid < rep_w && j >= 0) hit = a.tokens[((size_t)b * a.tok_stride + a.tok_off[b] + j) * a.nq + k] == (int64_t)pick;
+                const unsigned long long hits = __ballot(hit);
+                if (lane == 0) wredi[w] = __popcll(hits);
+                __syncthreads();
+                const int count = wredi[0] + wredi[1] + wredi[2] + wredi[3];
+                __syncthreads();
+                if (count < sh_ri[2]) break;
+                // drawn again from softmax over the whole group in index order: val[] / idx[] rebuilt from the registers (the select
+                // overwrote their head), the same sum as the first time
+                group_exp_total<true>(xr, m, G, val, idx, wred);
+                ncand = no_eos ? G - 1 : G;
+            }
         }
         if (tid == 0) {
             if (forced && gen < max_steps) pick = (int)forced[((size_t)b * a.stride + gen) * a.nq + k];
             chosen[k] = pick;
             if (a.score_out) {                       // from the logits row: val[] is sorted by now
-                const float t = (x[pick < 0 ? 0 : (pick < G ? pick : G - 1)] - m) - logf(norm);
+                const int pc = pick < 0 ? 0 : (pick < G ? pick : G - 1);
+                float xp = x[pc];
+                if (temp != 1.f) xp = __fdiv_rn(xp, temp);         // as xr[] above
+                if (no_eos && pc == G - 1) xp = -INFINITY;         // a forced <eos> below the minimum length
+                const float t = (xp - m) - logf(norm);
                 term = k == 0 ? t : term + t;
             }
         }
@@ -1648,6 +1730,7 @@ __device__ __forceinline__ void branch_f32_row(const float* src, float* dst, siz
     }
 }
 
+static_assert(sizeof(SampleRow) == 56, "slot_branch_kernel stores the row field by field: a new field goes there too");
 __global__ __launch_bounds__(256) void slot_branch_kernel(SlotBranch r) {
     __shared__ __attribute__((aligned(16))) float val[FC_SAMPLE_MAXV];
     __shared__ __attribute__((aligned(16))) int idx[FC_SAMPLE_MAXV];
@@ -1665,7 +1748,11 @@ __global__ __launch_bounds__(256) void slot_branch_kernel(SlotBranch r) {
         if (tid == 0) {
             r.n_gen[d] = r.keep; r.step[d] = r.keep; r.done[d] = 0; r.tok_off[d] = r.cont_len;
             if (same) r.pos[d] = r.P + r.keep - 1;
-            r.rows[d] = r.row;
+            // field by field: as one aggregate copy the row went through a private segment here (32 bytes per lane, 77 VGPRs)
+            SampleRow* o = r.rows + d;
+            o->mode = r.row.mode; o->ki = r.row.ki; o->pf = r.row.pf; o->max_steps = r.row.max_steps; o->seed = r.row.seed;
+            o->forced_on = r.row.forced_on; o->rng_row = r.row.rng_row; o->temperature = r.row.temperature; o->min_length = r.row.min_length;
+            o->top_p = r.row.top_p; o->repeat_window = r.row.repeat_window; o->repeat_count = r.row.repeat_count;
         }
         return;
     }

@@ -35,6 +35,46 @@ def sampling_args(sampling: Union[bool, int, float]):
     raise NotImplementedError(f"Not implemented for {type(sampling)} sampling")
 
 
+class SamplingRules:
+    """What shapes a decoding slot's draw beside ``sampling`` and ``seed`` (fc_laura_slots_set_rules states the semantics): the logits
+    are divided by `temperature`; <eos> cannot be picked while the slot has generated fewer than `min_length` tokens; `top_p` cuts the
+    top-k candidates of an integer ``sampling`` to their nucleus; with `repeat_window` W > 0, a drawn id that already stands at least
+    `repeat_count` times among the group's last W generated tokens is drawn again from the whole distribution (drawing modes only).
+    The defaults are the neutral rules: the session without rules, bit for bit."""
+
+    __slots__ = ("temperature", "min_length", "top_p", "repeat_window", "repeat_count")
+
+    def __init__(self, temperature: float = 1.0, min_length: int = 0, top_p: Optional[float] = None, repeat_window: int = 0,
+                 repeat_count: int = 1):
+        t = float(temperature)
+        if not (0.0 < t <= float(np.finfo(np.float32).max) and float(np.float32(t)) > 0.0):
+            raise ValueError(f"SamplingRules: temperature must be finite and > 0 (in float32), got {temperature!r}")
+        for name, v in (("min_length", min_length), ("repeat_window", repeat_window), ("repeat_count", repeat_count)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"SamplingRules: {name} must be an integer, got {v!r}")
+        if min_length < 0:
+            raise ValueError(f"SamplingRules: min_length must be >= 0, got {min_length}")
+        if top_p is not None and not 0.0 < float(np.float32(top_p)) <= 1.0:       # as the library sees it: 0 there means none
+            raise ValueError(f"SamplingRules: top_p must lie in (0, 1] (None: no nucleus cut), got {top_p!r}")
+        if not 0 <= repeat_window <= 256:
+            raise ValueError(f"SamplingRules: repeat_window must lie in 0 .. 256 (0: off), got {repeat_window}")
+        if repeat_window > 0 and not 1 <= repeat_count <= repeat_window:
+            raise ValueError(f"SamplingRules: repeat_count must lie in 1 .. repeat_window = {repeat_window}, got {repeat_count}")
+        if repeat_window == 0 and repeat_count < 1:
+            raise ValueError(f"SamplingRules: repeat_count must be >= 1, got {repeat_count}")
+        self.temperature, self.min_length = t, int(min_length)
+        self.top_p = None if top_p is None else float(top_p)
+        self.repeat_window, self.repeat_count = int(repeat_window), int(repeat_count)
+
+    def args(self):
+        """(temperature, min_length, top_p, repeat_window, repeat_count) of fc_laura_slots_set_rules; top_p 0 = none"""
+        return self.temperature, self.min_length, 0.0 if self.top_p is None else self.top_p, self.repeat_window, self.repeat_count
+
+    def __repr__(self):
+        return (f"SamplingRules(temperature={self.temperature}, min_length={self.min_length}, top_p={self.top_p}, "
+                f"repeat_window={self.repeat_window}, repeat_count={self.repeat_count})")
+
+
 class LauraEngine:
     """One engine per (device, checkpoint); calls are serialised by the caller like a torch module's forward."""
 
@@ -390,11 +430,21 @@ class DecodeSlots:
             run.wait_stream(cur)
         return cur, run
 
+    def _set_rules(self, slot: int, rules: Optional[SamplingRules]) -> None:
+        """`rules` (None: the neutral ones) as the rules the next start / start_from / fork into `slot` writes: per call, like sampling
+        and seed.  Nothing on the device changes here."""
+        if rules is not None and not isinstance(rules, SamplingRules):
+            raise ValueError(f"decode session: slot {slot}: rules must be a SamplingRules or None, got {type(rules).__name__}")
+        t, n, p, w, r = (rules or SamplingRules()).args()
+        self.engine._check(self.lib.fc_laura_slots_set_rules(self._handle(), int(slot), t, n, p, w, r))
+
     @_on_device
     def start(self, slot: int, text_outs: torch.Tensor, text_len: int, max_length: int = 30 * 25, sampling: Union[bool, int, float] = True,
-              seed: int = 0, continual: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None) -> None:
+              seed: int = 0, continual: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None,
+              rules: Optional[SamplingRules] = None) -> None:
         """One prompt into `slot`: text_outs [L, D] or [1, L, D] (rows < text_len are used), continual int64 [C, nq] prompt tokens, forced
-        int64 [max_length, nq].  A running slot's utterance is abandoned.  A refused call changes nothing for any slot."""
+        int64 [max_length, nq], rules a ``SamplingRules`` (None: neutral).  A running slot's utterance is abandoned.  A refused call
+        changes nothing for any slot."""
         eng, nq = self.engine, self.engine.spec.predict_nq
         h = self._handle()
         text_outs = eng._dev(text_outs, torch.float32)
@@ -423,6 +473,7 @@ class DecodeSlots:
             if tuple(forced.shape) != (max_length, nq):
                 raise EngineError(f"decode session start: slot {slot}: forced must be int64 [{max_length}, {nq}], got {tuple(forced.shape)}")
         mode, k, p = sampling_args(sampling)
+        self._set_rules(slot, rules)
         need = int(self.lib.fc_laura_slots_workspace_bytes(h, text_len, cont_len))
         if eng._ws is None or eng._ws.numel() < need:
             eng._ws = None
@@ -440,9 +491,9 @@ class DecodeSlots:
 
     @_on_device
     def start_from(self, dst: int, src: int, max_length: Optional[int] = None, sampling: Union[bool, int, float] = True, seed: int = 0,
-                   forced: Optional[torch.Tensor] = None) -> None:
+                   forced: Optional[torch.Tensor] = None, rules: Optional[SamplingRules] = None) -> None:
         """The prompt that slot `src` holds (text and continual tokens) into slot `dst` with `dst`'s own max_length (default: the
-        source's), sampling, seed and forced tokens: a device copy of the source's prefix instead of a prefix pass.  `dst` is, bit for
+        source's), sampling, seed, rules and forced tokens: a device copy of the source's prefix instead of a prefix pass.  `dst` is, bit for
         bit, the slot that ``start`` gives for the same prompt and parameters; `src` is not disturbed, may be running or ended (not yet
         taken), and may itself come from a start_from.  A running `dst` is abandoned.  A refused call changes nothing for any slot."""
         eng, nq = self.engine, self.engine.spec.predict_nq
@@ -460,6 +511,7 @@ class DecodeSlots:
             if tuple(forced.shape) != (max_length, nq):
                 raise EngineError(f"decode session start_from: slot {dst}: forced must be int64 [{max_length}, {nq}], got {tuple(forced.shape)}")
         mode, k, p = sampling_args(sampling)
+        self._set_rules(dst, rules)
         cur, run = self._run_stream()
         try:
             eng._check(self.lib.fc_laura_slots_start_from(h, dst, src, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), _ptr(forced),
@@ -471,9 +523,10 @@ class DecodeSlots:
 
     @_on_device
     def fork(self, dst: int, src: int, keep: Optional[int] = None, max_length: Optional[int] = None,
-             sampling: Union[bool, int, float] = True, seed: int = 0) -> None:
+             sampling: Union[bool, int, float] = True, seed: int = 0, rules: Optional[SamplingRules] = None) -> None:
         """Slot `dst` holds slot `src`'s utterance as it stood after its first `keep` generated tokens (default: all that the last
-        ``step`` reported, ``n_gen(src)``) and goes on from there with its own sampling, seed and max_length (default: the source's):
+        ``step`` reported, ``n_gen(src)``) and goes on from there with its own sampling, seed, rules (None: neutral, whatever the
+        source's) and max_length (default: the source's):
         a device copy of the source's cache positions, tokens and log-probability rows, no prefix pass and no decoding step.  With the
         source's own sampling and seed `dst` ends exactly as the source does; with any other, its per-step log-probabilities are those
         of ``start`` with its final tokens forced.  `src` is not disturbed, may be running or ended (by <eos> or by length, not yet
@@ -490,6 +543,7 @@ class DecodeSlots:
             raise EngineError(f"decode session fork: slot {dst}: max_length {int(max_length)} < 1")
         max_length = 0 if max_length is None else int(max_length)         # 0: the source's, which the library knows
         mode, k, p = sampling_args(sampling)
+        self._set_rules(dst, rules)
         cur, run = self._run_stream()
         try:
             self.engine._check(self.lib.fc_laura_slots_fork(h, dst, src, keep, max_length, mode, k, p, int(seed) & (2 ** 64 - 1),
@@ -500,11 +554,12 @@ class DecodeSlots:
         self._max_length[dst] = max_length or self._max_length[src]
         self._n_gen[dst] = self._n_gen[src] if keep < 0 else keep
 
-    def rewind(self, slot: int, keep: int, max_length: Optional[int] = None, sampling: Union[bool, int, float] = True, seed: int = 0) -> None:
+    def rewind(self, slot: int, keep: int, max_length: Optional[int] = None, sampling: Union[bool, int, float] = True, seed: int = 0,
+               rules: Optional[SamplingRules] = None) -> None:
         """``fork(slot, slot, keep, ...)``: the slot goes back to its first `keep` generated tokens in place and goes on from there
-        with the given sampling, seed and max_length (default: its own).  An ended slot (not yet taken) runs again; one that ended on
+        with the given sampling, seed, rules and max_length (default: its own).  An ended slot (not yet taken) runs again; one that ended on
         <eos>, rewound to keep = n_gen, draws its ending again."""
-        self.fork(slot, slot, keep, max_length, sampling, seed)
+        self.fork(slot, slot, keep, max_length, sampling, seed, rules)
 
     def n_gen(self, slot: int) -> int:
         """Tokens slot `slot` has generated, as the last ``step`` reported it (after a fork or rewind: the tokens kept)."""

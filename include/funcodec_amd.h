@@ -750,6 +750,34 @@ int  fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int
  *   end_out    host: 0 the slot is running, 1 it ended by length, 2 it ended on <eos> (ended with n_gen < max_length)
  * Refused, with the slot named: a session created without scores, a slot outside 0 .. S - 1, a free, never-started or failed slot. */
 int fc_laura_slots_score(fc_laura_slots* s, int slot, float* terms, int cap, int32_t* count_out, int32_t* end_out);
+/* The sampling rules of slot `slot`, kept on the host side of the session: every later fc_laura_slots_start, _start_from or _fork with
+ * that slot as the DESTINATION (dst == src, a rewind, included) writes them into the slot's row of the device sampling table, beside the
+ * mode, seed and max_length of that call.  They hold until set again; a session that never calls this has the neutral rules.  The step
+ * is not captured again and nothing else in it changes.
+ * For a running slot the sampler visits every group k of G = codebook_size + 1 logits x, <eos> at index G - 1; gen = the tokens the slot
+ * has generated so far.
+ *   1. temperature T (finite, > 0):  y[v] = x[v] / T, an IEEE fp32 division; T = 1 gives y = x bit for bit.
+ *   2. min_length n (>= 0):  while gen < n, y[G - 1] = -inf in every group: the utterance cannot end before it has n generated
+ *      tokens (a forced token still can); max_length still ends it.
+ *   3. Everything behind these two sees y: the greedy arg-max (lowest index on ties), the softmax total, the top-k select, the nucleus
+ *      walk, and the step's score term, which becomes sum over k of log softmax(y_k)[pick_k] -- the distribution the pick is drawn from
+ *      before truncation.  The log-probability rows (fc_laura_slots_take's logp_out) stay the whole-vocabulary log-softmax of the raw
+ *      logits.
+ *   4. top_p p (0 < p <= 1; 0 = none), with top-k sampling (sampling_mode 2) only: the top-k candidates in their order (probability
+ *      descending, index ascending) are cut to the shortest prefix whose mass reaches p x the sum over the whole group; the entry that
+ *      crosses is kept and at least one entry stays -- mode 3's walk, stopped at k.
+ *   5. repeat_window W (0 .. 256, 0 = off) and repeat_count r (1 .. W), in the drawing modes (1, 2, 3) only: after the draw of t in group
+ *      k let c be the number of generated tokens j in [max(0, gen - W), gen) whose group-k id equals t (prompt tokens are not in the
+ *      window).  If c >= r, t is drawn again, once, from softmax(y) over all G entries in index order, by the same inverse-CDF routine
+ *      as the first draw; its uniform number is Philox of the step's counter with the group word 8 + k (first draws use k < 8), so it is
+ *      a function of (seed, step, group) and not of the slot index.  A forced token replaces the pick after all of this.
+ *   6. The neutral rules -- T = 1, min_length 0, top_p 0, W = 0 -- are the session without rules bit for bit: tokens, log-probability
+ *      rows, scores and random-number stream.
+ * Refused before anything changes, with the slot named: a slot outside 0 .. S - 1, a non-finite or non-positive temperature, a
+ * negative min_length, top_p outside [0, 1], repeat_window outside 0 .. 256, repeat_count outside 1 .. repeat_window when the window is
+ * on.  top_p without top-k sampling and a window with greedy are refused by the start / start_from / fork that follows, together with
+ * its "bad sampling arguments", before it changes anything.  fc_laura_decode_codec has no rules. */
+int fc_laura_slots_set_rules(fc_laura_slots* s, int slot, float temperature, int min_length, float top_p, int repeat_window, int repeat_count);
 
 #ifdef __cplusplus
 }

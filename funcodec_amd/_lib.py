@@ -176,6 +176,11 @@ SYMBOLS = {
     "fc_laura_slots_score": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     # a slot's sampling rules (temperature, min_length, top_p, repeat_window, repeat_count): written by the next start / start_from / fork
     "fc_laura_slots_set_rules": (C.c_int, [_P, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int]),
+    # n different prompts into n slots with one prefix pass (host arrays [n]: slots, lengths, per-row parameters)
+    "fc_laura_slots_start_many_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
+    "fc_laura_slots_start_many": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    # start_from across two sessions of one engine (both driven on one stream)
+    "fc_laura_slots_start_from_session": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _P, _P]),
 }
 
 _lib = None

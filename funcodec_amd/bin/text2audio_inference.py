@@ -194,7 +194,7 @@ class Text2Audio:
     @torch.no_grad()
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
-                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all", rules=None):
+                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all", rules=None, prefill: int = 0):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
         request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.
@@ -217,8 +217,18 @@ class Text2Audio:
         token for token, those of keep = "all" (the default: today's call, a session without scores) with the same seeds.
 
         rules = a ``laura.SamplingRules`` (temperature, min_length, top_p with an integer ``sampling``, the repeat rule) for every
-        candidate: every start, start_from and rewind of the call carries it.  None is the call without rules."""
-        from ..laura import drive_best, drive_retries, drive_samples, retry_seed
+        candidate: every start, start_from and rewind of the call carries it.  None is the call without rules.
+
+        prefill = P in 1 .. 16 runs the prefix passes ahead of need, P different prompts per pass: a second, holding session of P
+        rows (never stepped, no log-probabilities, the main session's max_positions) is filled through DecodeSlots.start_many
+        whenever a slot needs a request that is not held -- that request and the next ones in arrival order (laura.prefill states the
+        rule) -- and EVERY candidate starts by a device copy from its request's row (DecodeSlots.start_from(source=held)); a row is
+        released once all `samples` candidates of its request have started.  Held rows are started greedy with max_length 1; what
+        they sample is never used.  Texts are still encoded one request at a time.  A slot started by the copy is, bit for bit, the
+        slot its own prefix pass gives, so the results are token for token and sample for sample those of prefill = 0 (the default:
+        today's call) with the same seeds, whatever samples, retries, keep and rules; n requests cost ceil(n / P) prefix passes
+        instead of n.  ``self.last_prefix_passes`` = {"main", "held"} says how many each session of the last call ran."""
+        from ..laura import HeldPrompts, drive_best, drive_retries, drive_samples, retry_seed
         m, nq = self.model, self.model.predict_nq
         n, N, R = len(texts), int(samples), int(retries)
         if N < 1:
@@ -227,6 +237,9 @@ class Text2Audio:
             raise ValueError(f"generate_many: retries must be >= 0, got {retries}")
         if keep not in ("all", "best"):
             raise ValueError(f"generate_many: keep must be \"all\" or \"best\", got {keep!r}")
+        P = int(prefill)
+        if not 0 <= P <= 16:
+            raise ValueError(f"generate_many: prefill must be 0 (off) or 1 .. 16 rows, got {prefill}")
         best = keep == "best"
         continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
         per = None
@@ -245,8 +258,30 @@ class Text2Audio:
             raise ValueError(f"generate_many: {len(seeds)} seeds for {n} requests")
         outs, lens = [None] * n, [0] * n
         session = m.open_decode(slots, logp=False, score=True) if best else m.open_decode(slots, logp=False)
+        held, plan = None, None
         try:
+            if P:
+                held, plan = m.open_decode(P, logp=False), HeldPrompts(P, n, N)
+
+            def encoded(i):
+                if outs[i] is None:
+                    to, ln = self._encode_texts([texts[i]])
+                    outs[i], lens[i] = to[0, : ln[0]], ln[0]
+
+            def from_held(slot, c):
+                # every candidate, first or sibling, is a copy from its request's row of the holding session
+                i = c // N
+                todo = plan.need(i)
+                if todo:
+                    for _, q in todo:
+                        encoded(q)
+                    held.start_many({row: dict(text_outs=outs[q], text_len=lens[q], max_length=1, sampling=False,
+                                               continual=None if per is None else per[q]) for row, q in todo})
+                session.start_from(slot, plan.start(i), self.max_length, self.sampling, seeds[c], rules=rules, source=held)
+
             def start(slot, c):
+                if P:
+                    return from_held(slot, c)
                 # a request's text is encoded when its slot is free, alone: its text_outs are those of a one-utterance call
                 i = c // N
                 if N == 1 or outs[i] is None:
@@ -255,6 +290,8 @@ class Text2Audio:
                 session.start(slot, outs[i], lens[i], self.max_length, self.sampling, seeds[c], None if per is None else per[i], rules=rules)
 
             def start_from(slot, src, c):
+                if P:
+                    return from_held(slot, c)
                 session.start_from(slot, src, self.max_length, self.sampling, seeds[c], rules=rules)
 
             def rewind(slot, c, keep, attempt):
@@ -271,7 +308,10 @@ class Text2Audio:
                     rows = drive_retries(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
                 taken = [t for row in rows for t in row]
         finally:
+            self.last_prefix_passes = {"main": session.prefix_passes, "held": held.prefix_passes if held is not None else 0}
             session.free()
+            if held is not None:
+                held.free()
         rets, codecs = [], []
         cands = sorted(taken) if best else list(range(n * N))          # keep = "best": the winners only
         for g in (cands[i: i + 16] for i in range(0, len(cands), 16)):      # finished utterances, 16 at a time, through the batch forms

@@ -342,6 +342,8 @@ struct KvOut {            // LM prefix pass: K / V rows of every block go to the
     int Tcap = 0;
     size_t layer_stride = 0;   // floats from one block's cache to the next: rows * d * Tcap
     size_t row_base = 0;       // where the pass's row 0 lies inside a block's cache (a decoding session's slot: slot * d * Tcap)
+    const lk::RowSlots* slots = nullptr;   // a session slot per batch row instead (fc_laura_slots_start_many), S slots in the session
+    int S = 0;
 };
 
 // debugging aid (fc_laura_debug_probe): copy one intermediate tensor of the next full-sequence stack run to a caller buffer
@@ -377,7 +379,10 @@ float* run_stack_full(fc_laura* e, Ctx& cx, const Stack& S, const float* in, int
         probe(cx, S, 1, i, xn, (size_t)B * d * T);
         cx.check(launch_lin_full(b.qkv, xn, B, T, qkv, cx.st), "QKV GEMM");
         probe(cx, S, 2, i, qkv, (size_t)B * 3 * d * T);
-        if (kv) cx.check(lk::launch_kv_store(qkv, lens, B, d, T, kv->Tcap, kv->kc + (size_t)i * kv->layer_stride + kv->row_base,
+        if (kv && kv->slots)
+            cx.check(lk::launch_kv_store_slots(qkv, lens, *kv->slots, kv->S, d, T, kv->Tcap, kv->kc + (size_t)i * kv->layer_stride,
+                                               kv->vc + (size_t)i * kv->layer_stride, cx.st), "kv store");
+        else if (kv) cx.check(lk::launch_kv_store(qkv, lens, B, d, T, kv->Tcap, kv->kc + (size_t)i * kv->layer_stride + kv->row_base,
                                              kv->vc + (size_t)i * kv->layer_stride + kv->row_base, cx.st), "kv store");
         lk::AttnFull a;
         a.qkv = qkv; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.lens = lens; a.bidir = bidir; a.causal = causal; a.ctx = ctx;
@@ -849,6 +854,57 @@ int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, i
     return cx.err;
 }
 
+// ONE prefix pass of n different prompts (B = n, T = pad4(Tmax), Tmax >= every row's prefix length) into the rows rs names, and each
+// slot's first sample.  Only the stack, the text transpose and the input assembly run at B = n: a column of the stack depends on its own
+// row's columns alone, so every slot holds the bits slots_prefix gives it.  What surrounds the stack stays one
+// launch per slot, exactly the launches of slots_prefix: the reset, the decoder GEMV on one row, the copy of the prefix logits, the
+// one-row sampler.  text_outs [n][L][D], continual [n][Cmax][nq] or null; the lengths are host arrays (null in a dry run).
+int slots_prefix_many(fc_laura_slots* s, Ctx& cx, const lk::RowSlots& rs, const float* text_outs, const int32_t* text_lens, int L,
+                      const int64_t* continual, const int32_t* cont_lens, int Cmax, const lk::SampleRow* rows, int Tmax) {
+    fc_laura* e = s->e;
+    const Stack& S = e->codec_lm;
+    const int D = e->arch.codebook_dim, V = e->vocab(), d = S.s.d_model, nq = e->arch.predict_nq, K = e->arch.codebook_size;
+    const int n = rs.n, T = pad4(Tmax);
+    int* tl = upload_lens(cx, text_lens, n);
+    int* cl = upload_lens(cx, continual ? cont_lens : nullptr, n, 0);
+    int Tt = 0;
+    float* tfm = text_to_fm(e, cx, text_outs, tl, L, &Tt);
+    float* seq = cx.alloc<float>((size_t)n * D * T);
+    int* seq_len = cx.alloc<int>(n);
+    int* bidir = cx.alloc<int>(n);
+    const StepMem& m = s->m;
+    if (cx.live()) {
+        for (int b = 0; b < n; ++b) {
+            const int cont_len = continual ? cont_lens[b] : 0;
+            lk::SlotReset r;
+            r.slot = rs.slot[b]; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
+            r.rows = s->rows; r.row = rows[b]; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
+            r.continual = cont_len ? continual + (size_t)b * Cmax * nq : nullptr; r.forced = s->forced; r.forced_src = nullptr;
+            r.logp = s->logp; r.V = V; r.score = s->score;
+            cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+        }
+        cx.check(lk::launch_lm_assemble(tfm, Tt, tl, e->lm_emb, e->cb, K, nq, continual, cl, Cmax, n, D, T, seq, seq_len, bidir, cx.st), "LM input");
+    }
+    KvOut kv;
+    kv.Tcap = m.Tcap; kv.kc = m.kc; kv.vc = m.vc;
+    kv.layer_stride = (size_t)s->S * d * m.Tcap; kv.slots = &rs; kv.S = s->S;
+    float* h = run_stack_full(e, cx, S, seq, T, seq_len, e->arch.bidirectional_inputs ? bidir : nullptr, 1, &kv);
+    if (cx.dry || cx.err) return cx.err;
+    cx.check(lk::launch_gather_last_slots(h, seq_len, rs, s->S, d, T, m.xs, m.pos, cx.st), "last position");
+    lk::Sample sm = slots_sampler(s);
+    sm.nrows = 1;
+    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
+    for (int b = 0; b < n && !cx.err; ++b) {
+        const int slot = rs.slot[b];
+        cx.check(step_gemv(e->lm_decoder, m.xs + (size_t)slot * d, 1, nullptr, nullptr, 0.f, 0, 0, m.lg + (size_t)slot * V, V, cx.st), "decoder GEMV");
+        cx.check(hipMemcpyAsync(s->lg0 + (size_t)slot * V, m.lg + (size_t)slot * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, cx.st),
+                 "prefix logits");
+        sm.row0 = slot;
+        cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    }
+    return cx.err;
+}
+
 // the slot's rules against the sampling mode of the start / start_from / fork that is about to write them
 int check_rules_mode(const fc_laura_slots* s, int slot, int mode) {
     const lk::SampleRow& r = s->rules[slot];
@@ -866,11 +922,16 @@ void put_rules(const fc_laura_slots* s, int slot, lk::SampleRow& row) {
     row.repeat_window = r.repeat_window; row.repeat_count = r.repeat_count;
 }
 
+const char* sampling_problem(int mode, int k, float p) {
+    if (mode < 0 || mode > 3) return "sampling_mode must be 0..3";
+    if (mode == 2 && k < 1) return "top-k sampling needs sampling_k >= 1";
+    if (mode == 3 && !(p > 0.f)) return "nucleus sampling needs sampling_p > 0";
+    return nullptr;
+}
+
 int check_sampling(int mode, int k, float p) {
-    if (mode < 0 || mode > 3) return fail("sampling_mode must be 0..3");
-    if (mode == 2 && k < 1) return fail("top-k sampling needs sampling_k >= 1");
-    if (mode == 3 && !(p > 0.f)) return fail("nucleus sampling needs sampling_p > 0");
-    return 0;
+    const char* why = sampling_problem(mode, k, p);
+    return why ? fail(why) : 0;
 }
 
 // Slot `dst` from the prompt slot `src` holds: the reset, the copy of the source's prefix, the first sample from the prefix logits.  The
@@ -1295,6 +1356,129 @@ int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_lengt
         return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
                     " exceeds the session's max_positions " + std::to_string(s->R));
     return slots_from_prefix(s, dst, src, max_length, sampling_mode, sampling_k, sampling_p, seed, forced, stream);
+}
+
+size_t fc_laura_slots_start_many_workspace_bytes(const fc_laura_slots* cs, int n, int L, int Cmax) {
+    fc_laura_slots* s = const_cast<fc_laura_slots*>(cs);
+    if (!s || n < 1 || n > 16 || n > s->S || L < 1 || Cmax < 0) return 0;
+    Ctx cx = make_ctx(n, nullptr, 0, nullptr);
+    lk::RowSlots rs;
+    rs.n = n;
+    slots_prefix_many(s, cx, rs, nullptr, nullptr, L, nullptr, nullptr, Cmax, nullptr, L + 2 + Cmax);
+    return cx.off + 4096;
+}
+
+int fc_laura_slots_start_many(fc_laura_slots* s, int n, const int32_t* slots, const float* text_outs, const int32_t* text_lens, int L,
+                              const int64_t* continual, const int32_t* cont_lens, int Cmax, const int32_t* max_lengths,
+                              const int32_t* sampling_modes, const int32_t* sampling_ks, const float* sampling_ps, const uint64_t* seeds,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (!slots || !text_outs || !text_lens || !max_lengths || !sampling_modes || !sampling_ks || !sampling_ps || !seeds || !workspace ||
+        n < 1 || L < 1 || Cmax < 0 || (continual && !cont_lens))
+        return fail("decoding session: start_many: bad argument");
+    // every rule for every row before the first launch: a refused call changes nothing for any slot
+    const int nmax = std::min(16, s->S);
+    if (n > nmax)
+        return fail("decoding session: slot " + std::to_string(slots[nmax]) + ": start_many takes at most min(16, slots) = " +
+                    std::to_string(nmax) + " prompts per call, got " + std::to_string(n));
+    lk::RowSlots rs;
+    rs.n = n;
+    lk::SampleRow rows[16];
+    int Tmax = 0;
+    for (int b = 0; b < n; ++b) {
+        const int slot = slots[b];
+        const std::string who = "decoding session: slot " + std::to_string(slot);
+        if (slot < 0 || slot >= s->S) return fail(who + " outside 0 .. " + std::to_string(s->S - 1));
+        for (int j = 0; j < b; ++j)
+            if (slots[j] == slot) return fail(who + " is named twice in one start_many");
+        const int cont_len = continual ? cont_lens[b] : 0;
+        if (text_lens[b] < 1 || text_lens[b] > L || max_lengths[b] < 1 || cont_len < 0 || cont_len > Cmax)
+            return fail("decoding session: bad argument for slot " + std::to_string(slot));
+        if (const char* why = sampling_problem(sampling_modes[b], sampling_ks[b], sampling_ps[b])) return fail(who + ": " + why);
+        if (check_rules_mode(s, slot, sampling_modes[b])) return 1;
+        const int P = text_lens[b] + 2 + cont_len, need = P + max_lengths[b];
+        if (need > s->R)
+            return fail(who + ": text_len + 2 + cont_len + max_length = " + std::to_string(need) + " exceeds the session's max_positions " +
+                        std::to_string(s->R));
+        Tmax = std::max(Tmax, P);
+        rs.slot[b] = slot;
+        lk::SampleRow& row = rows[b];
+        row = lk::SampleRow{};
+        row.mode = sampling_modes[b]; row.ki = sampling_ks[b]; row.pf = sampling_ps[b]; row.max_steps = max_lengths[b]; row.seed = seeds[b];
+        row.forced_on = 0; row.rng_row = 0u;
+        put_rules(s, slot, row);
+    }
+    {
+        Ctx dry = make_ctx(n, nullptr, 0, nullptr);
+        slots_prefix_many(s, dry, rs, nullptr, nullptr, L, nullptr, nullptr, Cmax, nullptr, Tmax);
+        if (dry.off > workspace_bytes) return fail("workspace too small");
+    }
+    // from here on the named slots' previous utterances are gone (a start on a running slot abandons it)
+    for (int b = 0; b < n; ++b) {
+        const int slot = slots[b], cont_len = continual ? cont_lens[b] : 0;
+        s->state[slot] = SLOT_FAILED; s->n_gen[slot] = 0; s->cont_len[slot] = cont_len; s->max_len[slot] = max_lengths[b];
+        s->text_len[slot] = text_lens[b]; s->prefix[slot] = text_lens[b] + 2 + cont_len; s->forced_on[slot] = 0;
+    }
+    s->last = (hipStream_t)stream;
+    Ctx cx = make_ctx(n, workspace, workspace_bytes, stream);
+    if (slots_prefix_many(s, cx, rs, text_outs, text_lens, L, continual, cont_lens, Cmax, rows, Tmax)) return 1;
+    for (int b = 0; b < n; ++b) s->state[slots[b]] = SLOT_RUNNING;
+    return 0;
+}
+
+int fc_laura_slots_start_from_session(fc_laura_slots* s, int dst, const fc_laura_slots* from, int src, int max_length, int sampling_mode,
+                                      int sampling_k, float sampling_p, uint64_t seed, const int64_t* forced, void* stream) {
+    if (!s || !from) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + " outside 0 .. " + std::to_string(s->S - 1));
+    if (from->e != s->e)
+        return fail("decoding session: slot " + std::to_string(dst) + ": the source session belongs to another engine (other weights: its prefix is not this engine's)");
+    if (from == s)
+        return fail("decoding session: slot " + std::to_string(dst) + ": the source session is this session (fc_laura_slots_start_from copies inside one)");
+    if (src < 0 || src >= from->S)
+        return fail("decoding session: source slot " + std::to_string(src) + " outside 0 .. " + std::to_string(from->S - 1) + " of the source session");
+    if (from->state[src] != SLOT_RUNNING && from->state[src] != SLOT_DONE)
+        return fail("decoding session: source slot " + std::to_string(src) + " of the source session holds no utterance (" +
+                    (from->state[src] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+    if (max_length < 1) return fail("decoding session: bad argument for slot " + std::to_string(dst));
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, dst, sampling_mode)) return 1;
+    const int P = from->prefix[src], cont_len = from->cont_len[src];
+    if (P + max_length > s->R)
+        return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
+                    " exceeds the session's max_positions " + std::to_string(s->R));
+    fc_laura* e = s->e;
+    const StepMem& m = s->m;
+    const int d = e->codec_lm.s.d_model, V = e->vocab(), nq = e->arch.predict_nq;
+    lk::SampleRow row{};
+    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
+    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;
+    put_rules(s, dst, row);
+    // from here on the destination's previous utterance is gone (as a start on a running slot abandons it)
+    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = 0; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
+    s->text_len[dst] = from->text_len[src]; s->prefix[dst] = P; s->forced_on[dst] = forced ? 1 : 0;
+    Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
+    s->last = cx.st;
+    lk::SlotReset r;
+    r.slot = dst; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
+    r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
+    r.continual = from->tokens + (size_t)src * from->R * nq;   // the source's prompt tokens, in the source session's token row
+    r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
+    r.score = s->score;
+    cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+    lk::PrefixImport c;
+    c.kc_src = from->m.kc; c.vc_src = from->m.vc; c.kc_dst = m.kc; c.vc_dst = m.vc;
+    c.lg0_src = from->lg0; c.lg_dst = m.lg; c.lg0_dst = s->lg0; c.pos_dst = m.pos;
+    c.NL = e->codec_lm.s.layers; c.d = d; c.V = V; c.S_src = from->S; c.Tcap_src = from->m.Tcap; c.S_dst = s->S; c.Tcap_dst = m.Tcap;
+    c.P = P; c.src = src; c.dst = dst;
+    cx.check(lk::launch_prefix_import(c, cx.st), "prefix import");
+    lk::Sample sm = slots_sampler(s);
+    sm.row0 = dst; sm.nrows = 1;
+    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
+    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    if (cx.err) return 1;
+    s->state[dst] = SLOT_RUNNING;
+    return 0;
 }
 
 int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_length, int sampling_mode, int sampling_k, float sampling_p,

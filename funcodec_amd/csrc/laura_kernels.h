@@ -63,6 +63,19 @@ hipError_t launch_kv_store(const float* qkv, const int* lens, int B, int d, int 
 // x_last[b][c] = x[b][c][lens[b] - 1]   ([16][C] token-major, rows >= B untouched)
 hipError_t launch_gather_last(const float* x, const int* lens, int B, int C, int T, float* out, hipStream_t st);
 
+// A prefix pass of n DIFFERENT prompts for a decoding session (fc_laura_slots_start_many): batch row b belongs to session slot
+// slot[b].  By value in the kernel arguments, like the lengths.
+struct RowSlots {
+    int n = 0;
+    int slot[16] = {};
+};
+// launch_kv_store with a destination slot per batch row: kc [S][d][Tcap], vc [S][Tcap][d] are one layer's caches of the session
+hipError_t launch_kv_store_slots(const float* qkv, const int* lens, const RowSlots& rs, int S, int d, int T, int Tcap, float* kc, float* vc,
+                                 hipStream_t st);
+// xs[slot[b]][c] = x[b][c][lens[b] - 1] and pos[slot[b]] = lens[b]   (xs [S][C] token-major, pos [S]; other slots untouched)
+hipError_t launch_gather_last_slots(const float* x, const int* lens, const RowSlots& rs, int S, int C, int T, float* xs, int* pos,
+                                    hipStream_t st);
+
 // ---- step form ------------------------------------------------------------------------------------------------------------
 struct Gemv {
     const float* x = nullptr;       // [B][K] token-major
@@ -182,6 +195,19 @@ struct PrefixCopy {                 // see prefix_copy_kernel
     int dst[15] = {};
 };
 hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st);
+
+struct PrefixImport {               // see prefix_import_kernel: prefix_copy_kernel between two sessions of one engine
+    const float *kc_src = nullptr, *vc_src = nullptr;   // the source session's caches [NL][S_src][d][Tcap_src], [NL][S_src][Tcap_src][d]
+    float *kc_dst = nullptr, *vc_dst = nullptr;         // the destination session's, with S_dst and Tcap_dst
+    const float* lg0_src = nullptr; // [S_src][V] logits every source slot's prefix ended with
+    float *lg_dst = nullptr, *lg0_dst = nullptr;        // [S_dst][V]
+    int* pos_dst = nullptr;         // device [S_dst]
+    int NL = 0, d = 0, V = 0;
+    int S_src = 0, Tcap_src = 0, S_dst = 0, Tcap_dst = 0;
+    int P = 0;                      // prefix positions of the source's prompt
+    int src = 0, dst = 0;
+};
+hipError_t launch_prefix_import(const PrefixImport& c, hipStream_t st);
 
 struct SlotBranch {                 // see slot_branch_kernel
     int S = 0, dst = 0, src = 0;    // dst == src: in place

@@ -513,6 +513,63 @@ hipError_t launch_gather_last(const float* x, const int* lens, int B, int C, int
     return hipGetLastError();
 }
 
+// kv_store_kernel for a prefix pass of several prompts of a decoding session: batch row b goes to the session's slot rs.slot[b].  The
+// values are copied, so a slot's cache positions are those of the one-row pass whatever the other rows hold.
+__global__ __launch_bounds__(256) void kv_store_slots_kernel(const float* __restrict__ qkv, const int* __restrict__ lens, RowSlots rs, int d,
+                                                             int T, int Tcap, float* __restrict__ kc, float* __restrict__ vc) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, t0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int len = lens[b] < Tcap ? lens[b] : Tcap;
+    const size_t slot = (size_t)rs.slot[b];
+    const float* kb = qkv + ((size_t)b * 3 + 1) * d * T;
+    const float* vb = qkv + ((size_t)b * 3 + 2) * d * T;
+    for (int r = ty; r < 32; r += 8) {
+        const int n = n0 + r, t = t0 + tx;
+        const bool ok = n < d && t < len && t < T;
+        if (ok) kc[(slot * d + n) * Tcap + t] = kb[(size_t)n * T + t];
+        tile[r][tx] = ok ? vb[(size_t)n * T + t] : 0.f;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int t = t0 + r, n = n0 + tx;
+        if (t < len && t < T && n < d) vc[(slot * Tcap + t) * d + n] = tile[tx][r];
+    }
+}
+static bool row_slots_ok(const RowSlots& rs, int S) {
+    if (rs.n < 1 || rs.n > 16 || S < 1) return false;
+    for (int i = 0; i < rs.n; ++i) {
+        if (rs.slot[i] < 0 || rs.slot[i] >= S) return false;
+        for (int j = 0; j < i; ++j)
+            if (rs.slot[j] == rs.slot[i]) return false;
+    }
+    return true;
+}
+hipError_t launch_kv_store_slots(const float* qkv, const int* lens, const RowSlots& rs, int S, int d, int T, int Tcap, float* kc, float* vc,
+                                 hipStream_t st) {
+    if (!row_slots_ok(rs, S) || d < 1 || T < 1 || Tcap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kv_store_slots_kernel, dim3(ceil_div_h(T, 32), ceil_div_h(d, 32), rs.n), dim3(256), 0, st, qkv, lens, rs, d, T, Tcap,
+                       kc, vc);
+    return hipGetLastError();
+}
+
+// gather_last_kernel with a destination slot per batch row, and the row's length as the slot's cache fill
+__global__ __launch_bounds__(256) void gather_last_slots_kernel(const float* __restrict__ x, const int* __restrict__ lens, RowSlots rs, int C,
+                                                                int T, float* __restrict__ xs, int* __restrict__ pos) {
+    const int b = blockIdx.x;
+    const size_t slot = (size_t)rs.slot[b];
+    int t = lens[b] - 1;
+    t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+    for (int c = threadIdx.x; c < C; c += 256) xs[slot * C + c] = x[((size_t)b * C + c) * T + t];
+    if (threadIdx.x == 0) pos[slot] = lens[b];
+}
+hipError_t launch_gather_last_slots(const float* x, const int* lens, const RowSlots& rs, int S, int C, int T, float* xs, int* pos,
+                                    hipStream_t st) {
+    if (!row_slots_ok(rs, S) || C < 1 || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_last_slots_kernel, dim3(rs.n), dim3(256), 0, st, x, lens, rs, C, T, xs, pos);
+    return hipGetLastError();
+}
+
 __global__ void fill_i32_kernel(int* p, int v, int n) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < n) p[i] = v;
@@ -1692,6 +1749,67 @@ hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st) {
     if (nK > 0x7fffffff || nV > 0x7fffffff) return hipErrorInvalidValue;
     const int bK = (int)((nK + per - 1) / per), bV = (int)((nV + per - 1) / per);
     hipLaunchKernelGGL(prefix_copy_kernel, dim3(bK + bV + 1, c.NL), dim3(256), 0, st, c);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// prefix_copy_kernel between two sessions of one engine: the prefix of slot `src` of the source session into slot `dst` of the
+// destination session, whose slot count and cache pitch may differ.  The same grid (grid.y = layer; along x a layer's K vectors, its V
+// vectors, one block for the logits and the position), the same FC_PREFIX_VPT x 256 16-byte vectors per block with their loads in flight
+// together; one destination.
+//   K: rows of pad4(P) floats from pitch Tcap_src to pitch Tcap_dst (both % 4 == 0).  Columns [P, pad4(P)) carry what the source holds
+//   there; the destination never reads them before it has written them (see prefix_copy_kernel).
+//   V: the first P * d floats of the slot's row, contiguous in both sessions.
+//   lg0_src[src] into lg_dst[dst] and lg0_dst[dst]; pos_dst[dst] = P.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void prefix_import_kernel(PrefixImport c) {
+    const int l = blockIdx.y, tid = threadIdx.x;
+    const int kq = (c.P + 3) >> 2;
+    const int nK = c.d * kq, nV = (c.P * c.d) >> 2;
+    const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
+    int blk = blockIdx.x;
+    if (blk >= bK + bV) {
+        if (l != 0) return;
+        const float* s = c.lg0_src + (size_t)c.src * c.V;
+        for (int v = tid; v < c.V; v += 256) {
+            const float x = s[v];
+            c.lg_dst[(size_t)c.dst * c.V + v] = x;
+            c.lg0_dst[(size_t)c.dst * c.V + v] = x;
+        }
+        if (tid == 0) c.pos_dst[c.dst] = c.P;
+        return;
+    }
+    const bool isK = blk < bK;
+    if (!isK) blk -= bK;
+    const size_t row_s = (size_t)c.d * c.Tcap_src, row_d = (size_t)c.d * c.Tcap_dst;
+    const float* sb = (isK ? c.kc_src : c.vc_src) + ((size_t)l * c.S_src + c.src) * row_s;
+    float* db = (isK ? c.kc_dst : c.vc_dst) + ((size_t)l * c.S_dst + c.dst) * row_d;
+    const int nvec = isK ? nK : nV;
+    const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
+    size_t od[FC_PREFIX_VPT];
+    f32x4 v[FC_PREFIX_VPT];
+#pragma unroll
+    for (int u = 0; u < FC_PREFIX_VPT; ++u) {
+        int i = i0 + 256 * u;
+        i = i < nvec ? i : nvec - 1;                                  // clamped: unconditional loads, predicated stores
+        const size_t os = isK ? (size_t)(i / kq) * c.Tcap_src + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+        od[u] = isK ? (size_t)(i / kq) * c.Tcap_dst + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+        v[u] = *(const f32x4*)(sb + os);
+    }
+#pragma unroll
+    for (int u = 0; u < FC_PREFIX_VPT; ++u)
+        if (i0 + 256 * u < nvec) *(f32x4*)(db + od[u]) = v[u];
+}
+hipError_t launch_prefix_import(const PrefixImport& c, hipStream_t st) {
+    if (c.NL < 1 || c.S_src < 1 || c.S_dst < 1 || c.src < 0 || c.src >= c.S_src || c.dst < 0 || c.dst >= c.S_dst) return hipErrorInvalidValue;
+    if (c.d < 4 || c.d % 4 || c.Tcap_src % 4 || c.Tcap_dst % 4 || c.P < 1 || c.V < 1) return hipErrorInvalidValue;
+    if (((c.P + 3) & ~3) > c.Tcap_src || ((c.P + 3) & ~3) > c.Tcap_dst) return hipErrorInvalidValue;
+    const int per = 256 * FC_PREFIX_VPT;
+    const int kq = ((c.P + 3) & ~3) >> 2;
+    const long long nK = (long long)c.d * kq, nV = ((long long)c.P * c.d) >> 2;
+    if (nK > 0x7fffffff || nV > 0x7fffffff) return hipErrorInvalidValue;
+    const int bK = (int)((nK + per - 1) / per), bV = (int)((nV + per - 1) / per);
+    hipLaunchKernelGGL(prefix_import_kernel, dim3(bK + bV + 1, c.NL), dim3(256), 0, st, c);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
+from collections.abc import Mapping
 from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -378,6 +379,8 @@ class DecodeSlots:
         self._max_length = [0] * max(self.slots, 0)
         self._status = (C.c_int32 * max(self.slots, 1))()
         self._n_gen = (C.c_int32 * max(self.slots, 1))()
+        #: prefix passes this session has run: one per ``start``, one per ``start_many`` whatever its n, none for start_from / fork
+        self.prefix_passes = 0
         self._open()
 
     @_on_device
@@ -488,10 +491,109 @@ class DecodeSlots:
             if run is not cur:
                 cur.wait_stream(run)
         self._max_length[int(slot)] = max_length
+        self.prefix_passes += 1
+
+    START_MANY_KEYS = ("text_outs", "text_len", "max_length", "sampling", "seed", "continual", "rules")
+
+    def _many_rows(self, requests) -> List[tuple]:
+        """The argument checks of ``start_many`` that need no device: [(slot, request dict with ``start``'s defaults filled in)]."""
+        what = "decode session start_many"
+        items = list(requests.items()) if isinstance(requests, Mapping) else [tuple(r) for r in requests]
+        if not items:
+            raise EngineError(f"{what}: no requests")
+        rows, seen = [], set()
+        for slot, req in items:
+            slot = int(slot)
+            if not 0 <= slot < self.slots:
+                raise EngineError(f"{what}: slot {slot} outside 0 .. {self.slots - 1}")
+            if slot in seen:
+                raise EngineError(f"{what}: slot {slot} is named twice")
+            seen.add(slot)
+            if not isinstance(req, Mapping):
+                raise EngineError(f"{what}: slot {slot}: a request is a dict of {', '.join(self.START_MANY_KEYS)}")
+            unknown = sorted(set(req) - set(self.START_MANY_KEYS))
+            if unknown:
+                hint = " (start_many takes no forced tokens: start forces)" if "forced" in unknown else ""
+                raise EngineError(f"{what}: slot {slot}: unknown key(s) {unknown}{hint}")
+            if "text_outs" not in req or "text_len" not in req:
+                raise EngineError(f"{what}: slot {slot}: text_outs and text_len are required")
+            r = dict(max_length=30 * 25, sampling=True, seed=0, continual=None, rules=None)
+            r.update(req)
+            if int(r["max_length"]) < 1:
+                raise EngineError(f"{what}: slot {slot}: max_length {int(r['max_length'])} < 1")
+            rows.append((slot, r))
+        if len(rows) > min(16, self.slots):
+            raise EngineError(f"{what}: slot {rows[min(16, self.slots)][0]}: at most min(16, slots) = {min(16, self.slots)} prompts per call, "
+                              f"got {len(rows)}")
+        return rows
+
+    @_on_device
+    def start_many(self, requests) -> None:
+        """n different prompts into n slots with ONE prefix pass: `requests` maps slot -> dict(text_outs, text_len, max_length, sampling,
+        seed, continual, rules) with ``start``'s meanings and defaults (or is a sequence of such (slot, dict) pairs); 1 <= n <=
+        min(16, slots), the slots distinct, in any order.  Every named slot is, bit for bit, the slot ``start`` gives for its prompt and
+        parameters -- how a slot was started changes its cost, never its result.  No forced tokens here: ``start`` forces.  A running
+        slot's utterance is abandoned.  A refused call names the slot and changes nothing for any slot."""
+        eng, nq = self.engine, self.engine.spec.predict_nq
+        h = self._handle()
+        rows = self._many_rows(requests)
+        n = len(rows)
+        texts, conts = [], []
+        for slot, r in rows:
+            t = eng._dev(r["text_outs"], torch.float32)
+            if t.dim() == 3 and t.shape[0] == 1:
+                t = t[0]
+            text_len = int(r["text_len"])
+            if t.dim() != 2 or t.shape[1] != eng.spec.codebook_dim or not 1 <= text_len <= t.shape[0]:
+                raise EngineError(f"decode session start_many: slot {slot}: one prompt [L, {eng.spec.codebook_dim}] with 1 <= text_len <= L, "
+                                  f"got {tuple(t.shape)}, text_len {text_len}")
+            texts.append(t[:text_len])
+            c = r["continual"]
+            if c is not None:
+                c = eng._dev(c, torch.int64)
+                if c.dim() == 3 and c.shape[0] == 1:
+                    c = c[0]
+                if c.dim() != 2 or c.shape[1] != nq:
+                    raise EngineError(f"decode session start_many: slot {slot}: continual must be int64 [C, {nq}], got {tuple(c.shape)}")
+            conts.append(c)
+        L = max(t.shape[0] for t in texts)
+        Cmax = max((c.shape[0] for c in conts if c is not None), default=0)
+        text = torch.zeros((n, L, eng.spec.codebook_dim), dtype=torch.float32, device=self.device)
+        cont = torch.zeros((n, Cmax, nq), dtype=torch.int64, device=self.device) if Cmax else None
+        for b, (t, c) in enumerate(zip(texts, conts)):
+            text[b, : t.shape[0]] = t
+            if c is not None and c.shape[0]:
+                cont[b, : c.shape[0]] = c
+        modes = [sampling_args(r["sampling"]) for _, r in rows]
+        for slot, r in rows:
+            self._set_rules(slot, r["rules"])
+        need = int(self.lib.fc_laura_slots_start_many_workspace_bytes(h, n, L, Cmax))
+        if eng._ws is None or eng._ws.numel() < need:
+            eng._ws = None
+            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = eng._ws
+        slots_a = _i32([slot for slot, _ in rows])
+        tl_a = _i32([t.shape[0] for t in texts])
+        cl_a = _i32([0 if c is None else c.shape[0] for c in conts]) if cont is not None else None
+        ml_a = _i32([int(r["max_length"]) for _, r in rows])
+        mode_a, k_a = _i32([m[0] for m in modes]), _i32([m[1] for m in modes])
+        p_a = (C.c_float * n)(*[m[2] for m in modes])
+        seed_a = (C.c_uint64 * n)(*[int(r["seed"]) & (2 ** 64 - 1) for _, r in rows])
+        cur, run = self._run_stream()
+        try:
+            eng._check(self.lib.fc_laura_slots_start_many(h, n, slots_a, _ptr(text), tl_a, L, _ptr(cont), cl_a, Cmax, ml_a, mode_a, k_a, p_a,
+                                                          seed_a, _ptr(ws), ws.numel(), C.c_void_p(run.cuda_stream)))
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+        for slot, r in rows:
+            self._max_length[slot] = int(r["max_length"])
+        self.prefix_passes += 1
 
     @_on_device
     def start_from(self, dst: int, src: int, max_length: Optional[int] = None, sampling: Union[bool, int, float] = True, seed: int = 0,
-                   forced: Optional[torch.Tensor] = None, rules: Optional[SamplingRules] = None) -> None:
+                   forced: Optional[torch.Tensor] = None, rules: Optional[SamplingRules] = None,
+                   source: Optional["DecodeSlots"] = None) -> None:
         """The prompt that slot `src` holds (text and continual tokens) into slot `dst` with `dst`'s own max_length (default: the
         source's), sampling, seed, rules and forced tokens: a device copy of the source's prefix instead of a prefix pass.  `dst` is, bit for
         bit, the slot that ``start`` gives for the same prompt and parameters; `src` is not disturbed, may be running or ended (not yet
@@ -499,10 +601,15 @@ class DecodeSlots:
         eng, nq = self.engine, self.engine.spec.predict_nq
         h = self._handle()
         dst, src = int(dst), int(src)
+        if source is self:
+            source = None
+        if source is not None and not isinstance(source, DecodeSlots):
+            raise EngineError(f"decode session start_from: slot {dst}: source must be a DecodeSlots or None, got {type(source).__name__}")
+        held = self if source is None else source
         if max_length is None:
-            if not 0 <= src < self.slots:
-                raise EngineError(f"decode session start_from: source slot {src} outside 0 .. {self.slots - 1}")
-            max_length = self._max_length[src]
+            if not 0 <= src < held.slots:
+                raise EngineError(f"decode session start_from: source slot {src} outside 0 .. {held.slots - 1}")
+            max_length = held._max_length[src]
         max_length = int(max_length)
         if forced is not None:
             forced = eng._dev(forced, torch.int64)
@@ -514,8 +621,12 @@ class DecodeSlots:
         self._set_rules(dst, rules)
         cur, run = self._run_stream()
         try:
-            eng._check(self.lib.fc_laura_slots_start_from(h, dst, src, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), _ptr(forced),
-                                                          C.c_void_p(run.cuda_stream)))
+            if source is None:
+                eng._check(self.lib.fc_laura_slots_start_from(h, dst, src, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), _ptr(forced),
+                                                              C.c_void_p(run.cuda_stream)))
+            else:                           # the prompt lies in another session of this engine; both sessions run on this stream
+                eng._check(self.lib.fc_laura_slots_start_from_session(h, dst, source._handle(), src, max_length, mode, k, p,
+                                                                      int(seed) & (2 ** 64 - 1), _ptr(forced), C.c_void_p(run.cuda_stream)))
         finally:
             if run is not cur:
                 cur.wait_stream(run)
@@ -644,6 +755,66 @@ def refill(pending: Sequence[int], free_slots: Sequence[int]) -> List[tuple]:
     """The refill policy of a decoding session, a plain function of (arrival order, which slots are free): the waiting requests, in
     arrival order, go to the free slots in ascending order.  Returns [(slot, request)]."""
     return list(zip(sorted(free_slots), pending))
+
+
+def prefill(need: int, held: Dict[int, int], rows: int, n_requests: int, fresh: int) -> List[tuple]:
+    """Which requests a holding session of `rows` rows prefills, in ONE prefix pass, when a slot needs request `need`: a plain function
+    of (the request needed, `held` = row -> the request it holds and has not released, `fresh` = the lowest request never prefilled).
+    Nothing, if `need` is held.  Otherwise `need` itself, then the requests from max(need + 1, fresh) on in arrival order that are not
+    held, as many as rows are free, into the free rows in ascending order; if no row is free the row holding the request needed last
+    (the highest number) gives way -- it is prefilled again when its turn comes.  Returns [(row, request)], `need` first.
+
+    In arrival order (the drivers' order without failures) need == fresh at every miss and all rows are free then, so request i is
+    prefilled by pass i // rows and n requests cost ceil(n / rows) passes.  A request that comes back after its row was released (a
+    failed slot's) is prefilled once more, with fresh requests beside it."""
+    if not 0 <= need < n_requests:
+        raise ValueError(f"prefill: request {need} outside 0 .. {n_requests - 1}")
+    if rows < 1:
+        raise ValueError(f"prefill: a holding session has at least one row, got {rows}")
+    if need in held.values():
+        return []
+    free = sorted(r for r in range(rows) if r not in held)
+    if not free:
+        free = [max(held, key=lambda r: held[r])]
+    want = [need] + [q for q in range(max(need + 1, fresh), n_requests) if q not in held.values()]
+    return list(zip(free, want))
+
+
+class HeldPrompts:
+    """The bookkeeping of ``generate_many(prefill=P)`` around ``prefill``, no device in it: which row of the holding session holds
+    which request, and when a row is released -- once all `samples` candidates of its request have started."""
+
+    def __init__(self, rows: int, n_requests: int, samples: int = 1):
+        self.rows, self.n_requests, self.samples = int(rows), int(n_requests), int(samples)
+        self.held: Dict[int, int] = {}          # row -> request
+        self.started: Dict[int, int] = {}       # request -> candidates started from its row so far
+        self.fresh = 0
+        self.passes = 0
+
+    def need(self, request: int) -> List[tuple]:
+        """[(row, request)] to prefill in one pass before `request` can be started ([]: it is held); the rows are taken here."""
+        plan = prefill(request, self.held, self.rows, self.n_requests, self.fresh)
+        for row, q in plan:
+            self.held[row] = q
+            self.started[q] = 0
+            self.fresh = max(self.fresh, q + 1)
+        if plan:
+            self.passes += 1
+        return plan
+
+    def row_of(self, request: int) -> int:
+        for row, q in self.held.items():
+            if q == request:
+                return row
+        raise KeyError(f"request {request} is not held")
+
+    def start(self, request: int) -> int:
+        """A candidate of `request` starts from its row (returned); the row is released behind the last one."""
+        row = self.row_of(request)
+        self.started[request] += 1
+        if self.started[request] >= self.samples:
+            del self.held[row]
+        return row
 
 
 def drive_slots(session, slots: int, n_requests: int, start, step_n: int = 1) -> list:

@@ -778,6 +778,40 @@ int fc_laura_slots_score(fc_laura_slots* s, int slot, float* terms, int cap, int
  * on.  top_p without top-k sampling and a window with greedy are refused by the start / start_from / fork that follows, together with
  * its "bad sampling arguments", before it changes anything.  fc_laura_decode_codec has no rules. */
 int fc_laura_slots_set_rules(fc_laura_slots* s, int slot, float temperature, int min_length, float top_p, int repeat_window, int repeat_count);
+/* (entry points added without a struct change: FC_ABI_VERSION stays 7)
+ * The head of decode_codec (laura_model.py:501-548) for n DIFFERENT prompts into n slots with ONE prefix pass: the LM stack runs once at
+ * B = n over time axes padded to the longest prompt; the reset, the output layer on the last position, and the first sample stay one
+ * launch per slot, exactly those of fc_laura_slots_start.  After the call every named slot holds what fc_laura_slots_start would have
+ * left there for its prompt and parameters, BIT FOR BIT -- cache positions [0, P), logits, position, token / forced / log-probability /
+ * score rows, its row of the sampling table, the first sample: a column of the full-sequence stack depends on its own row's columns
+ * only, never on the batch size, the padded length or a neighbour (DESIGN.md section 9 gives the argument per kernel).  No other slot
+ * changes; the persistent step's launch number and arrival counters are not touched and the captured step is not captured again.
+ *   n           1 .. min(16, S);  slots host i32 [n]: distinct, any order
+ *   text_outs   dev f32 [n][L][codebook_dim], rows >= text_lens[b] ignored;  text_lens host i32 [n], 1 .. L
+ *   continual   dev i64 [n][Cmax][predict_nq] or NULL, rows >= cont_lens[b] ignored;  cont_lens host i32 [n] (NULL with continual NULL)
+ *   max_lengths / sampling_modes / sampling_ks host i32 [n], sampling_ps host f32 [n], seeds host u64 [n]: per row, as fc_laura_slots_start
+ * Forced tokens are not taken (fc_laura_slots_start forces).  A slot's rules are those of fc_laura_slots_set_rules.
+ * Every rule is checked for every row before the first launch; a refused call changes nothing for any slot and names the slot: a slot
+ * outside 0 .. S - 1 or named twice, n outside 1 .. min(16, S), text_len + 2 + cont_len + max_length > max_positions, bad sampling
+ * arguments or rules that do not go with the row's mode.  A named slot that is running abandons its utterance. */
+size_t fc_laura_slots_start_many_workspace_bytes(const fc_laura_slots* s, int n, int L, int Cmax);
+int fc_laura_slots_start_many(fc_laura_slots* s, int n, const int32_t* slots, const float* text_outs, const int32_t* text_lens, int L,
+                              const int64_t* continual, const int32_t* cont_lens, int Cmax, const int32_t* max_lengths,
+                              const int32_t* sampling_modes, const int32_t* sampling_ks, const float* sampling_ps, const uint64_t* seeds,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* fc_laura_slots_start_from across two sessions of the SAME fc_laura: slot `dst` of `dst_session` from the prompt that slot `src` of
+ * `src_session` holds.  The sessions may differ in their slot count, in max_positions (hence in the pitch of the key rows) and in whether
+ * they keep log-probabilities or scores.  One device copy (K rows of pad4(P) floats from one pitch to the other, the first P * d floats
+ * of V, the source's prefix logits, the position) and the first sample with `dst`'s own parameters: the slot that fc_laura_slots_start
+ * gives on `dst_session` for the same prompt, bit for bit.  The source row is not disturbed and may be imported any number of times; a
+ * session that is never stepped can so hold prompts, prefilled several per pass by fc_laura_slots_start_many, for the slots of another.
+ * BOTH SESSIONS ARE DRIVEN ON ONE STREAM: the copy is ordered behind the source's prefix pass by `stream` alone.
+ * Refused before any launch, changing nothing, with the slot named: sessions of different engines (or the same session), `dst` or
+ * `src` outside its session, a source that is free, never started or failed, bad sampling arguments, the source's text_len + 2 +
+ * cont_len + max_length > the DESTINATION's max_positions.  A running `dst` is abandoned. */
+int fc_laura_slots_start_from_session(fc_laura_slots* dst_session, int dst, const fc_laura_slots* src_session, int src, int max_length,
+                                      int sampling_mode, int sampling_k, float sampling_p, uint64_t seed, const int64_t* forced,
+                                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,9 @@ SYMBOLS = {
     "fc_laura_slots_start_many": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     # start_from across two sessions of one engine (both driven on one stream)
     "fc_laura_slots_start_from_session": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, _P, _P]),
+    # a session of up to 64 slots (the step's GEMV over column blocks of 16 rows); up to 16 it is the _scored pair
+    "fc_laura_slots_state_bytes_wide": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fc_laura_slots_create_wide": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
 }
 
 _lib = None

@@ -197,7 +197,8 @@ class Text2Audio:
                       step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all", rules=None, prefill: int = 0):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
-        request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.
+        request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.  slots = 17 ..
+        64 opens a wide session (LauraEngine.open_decode(wide=True)): more rows per decoding step, the same calls.
 
         samples = N > 1 draws N candidates per request (consecutive entries in arrival order; seeds [n][N], or drawn per candidate)
         and returns one list of N per request in both return values.  A candidate whose request has another candidate running in
@@ -257,7 +258,9 @@ class Text2Audio:
         if len(seeds) != n * N:
             raise ValueError(f"generate_many: {len(seeds)} seeds for {n} requests")
         outs, lens = [None] * n, [0] * n
-        session = m.open_decode(slots, logp=False, score=True) if best else m.open_decode(slots, logp=False)
+        # more than 16 slots: a wide session (open_decode(wide=True), up to 64); up to 16 the call is the one it always was
+        more = dict(wide=True) if int(slots) > 16 else {}
+        session = m.open_decode(slots, logp=False, score=True, **more) if best else m.open_decode(slots, logp=False, **more)
         held, plan = None, None
         try:
             if P:

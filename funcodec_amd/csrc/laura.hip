@@ -547,6 +547,9 @@ struct StepMem {
     unsigned* error_word() const { return psync + sync_words - 64; }
 };
 
+// rows of the step's token vectors: the GEMV's column blocks are whole
+int step_rows(int B) { return 16 * ((B + 15) / 16); }
+
 StepMem alloc_step_mem(fc_laura* e, Ctx& cx, int B, int Tcap) {
     const Stack& S = e->codec_lm;
     const int D = e->arch.codebook_dim, V = e->vocab(), d = S.s.d_model, ff = S.s.ff, NL = S.s.layers;
@@ -557,15 +560,16 @@ StepMem alloc_step_mem(fc_laura* e, Ctx& cx, int B, int Tcap) {
     m.ctr = cx.alloc<int>(3 * B + 4);
     m.kc = cx.alloc<float>((size_t)NL * B * d * Tcap);
     m.vc = cx.alloc<float>((size_t)NL * B * d * Tcap);
-    m.xs = cx.alloc<float>((size_t)16 * d);
-    m.qb = cx.alloc<float>((size_t)16 * d);
+    const size_t RW = (size_t)step_rows(B);     // whole column blocks of the GEMV: 16 up to 16 rows
+    m.xs = cx.alloc<float>(RW * d);
+    m.qb = cx.alloc<float>(RW * d);
     m.NS = 256 / (B * heads);                   // key ranges per (utterance, head): fill the chip's 256 CUs
     m.NS = m.NS < 1 ? 1 : (m.NS > 8 ? 8 : m.NS);
-    m.apart = cx.alloc<float>((size_t)16 * heads * 8 * (dkh + 2));
-    m.hb = cx.alloc<float>((size_t)16 * ff);
-    m.lg = cx.alloc<float>((size_t)16 * V);
-    m.nemb = cx.alloc<float>((size_t)16 * D);
-    // the decoding step as ONE persistent launch (laura_persist.hip): per-block edge buffers, arrival counters, the launch counter
+    m.apart = cx.alloc<float>(RW * heads * 8 * (dkh + 2));
+    m.hb = cx.alloc<float>(RW * ff);
+    m.lg = cx.alloc<float>(RW * V);
+    m.nemb = cx.alloc<float>(RW * D);
+    // the decoding step as ONE persistent launch (laura_persist.hip, B <= 16 only): per-block edge buffers, arrival counters, the launch counter
     m.KS2 = lk::step_persist_ksplit(d, ff);
     auto pad32 = [](size_t n) { return (n + 31) & ~(size_t)31; };
     m.o_q = 0; m.o_ap = m.o_q + pad32((size_t)16 * d); m.o_xm = m.o_ap + pad32((size_t)16 * heads * 8 * (dkh + 4));
@@ -1235,9 +1239,13 @@ size_t fc_laura_slots_state_bytes(const fc_laura* e, int slots, int max_position
     return fc_laura_slots_state_bytes_scored(e, slots, max_positions, with_logp, 0);
 }
 
-size_t fc_laura_slots_state_bytes_scored(const fc_laura* ce, int slots, int max_positions, int with_logp, int with_score) {
+size_t fc_laura_slots_state_bytes_scored(const fc_laura* e, int slots, int max_positions, int with_logp, int with_score) {
+    return slots > 16 ? 0 : fc_laura_slots_state_bytes_wide(e, slots, max_positions, with_logp, with_score);
+}
+
+size_t fc_laura_slots_state_bytes_wide(const fc_laura* ce, int slots, int max_positions, int with_logp, int with_score) {
     fc_laura* e = const_cast<fc_laura*>(ce);
-    if (!e || slots < 1 || slots > 16 || max_positions < 16 || max_positions > e->R || max_positions % 4) return 0;
+    if (!e || slots < 1 || slots > 64 || max_positions < 16 || max_positions > e->R || max_positions % 4) return 0;
     Ctx cx = make_ctx(slots, nullptr, 0, nullptr);
     fc_laura_slots s;
     slots_layout(e, cx, slots, max_positions, with_logp != 0, with_score != 0, s);
@@ -1250,8 +1258,18 @@ int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_lo
 
 int fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
                                  fc_laura_slots** out) {
+    if (slots < 1 || slots > 16) {
+        if (check_ready(e)) return 1;
+        return fail("a decoding session has 1 .. 16 slots (the step form's 16 MFMA columns), got " + std::to_string(slots));
+    }
+    return fc_laura_slots_create_wide(e, slots, max_positions, with_logp, with_score, state, state_bytes, out);
+}
+
+int fc_laura_slots_create_wide(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
+                               fc_laura_slots** out) {
     if (check_ready(e)) return 1;
-    if (slots < 1 || slots > 16) return fail("a decoding session has 1 .. 16 slots (the step form's 16 MFMA columns), got " + std::to_string(slots));
+    if (slots < 1 || slots > 64)
+        return fail("a wide decoding session has 1 .. 64 slots (4 column blocks of the step form's 16 MFMA columns), got " + std::to_string(slots));
     if (max_positions < 16 || max_positions % 4 || max_positions > e->R)
         return fail("a decoding session's max_positions must be a multiple of 4 in [16, " + std::to_string(e->R) + "] (the engine's), got " +
                     std::to_string(max_positions));
@@ -1269,12 +1287,13 @@ int fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int 
     const int d = S.s.d_model, heads = S.s.heads, dkh = d / heads;
     HIP_TRY(hipMemset(m.pos, 0, (size_t)slots * sizeof(int)));
     HIP_TRY(hipMemset(m.ctr, 0, (size_t)(3 * slots + 4) * sizeof(int)));
-    HIP_TRY(hipMemset(m.xs, 0, (size_t)16 * d * sizeof(float)));
-    HIP_TRY(hipMemset(m.qb, 0, (size_t)16 * d * sizeof(float)));
-    HIP_TRY(hipMemset(m.apart, 0, (size_t)16 * heads * 8 * (dkh + 2) * sizeof(float)));
-    HIP_TRY(hipMemset(m.hb, 0, (size_t)16 * S.s.ff * sizeof(float)));
-    HIP_TRY(hipMemset(m.lg, 0, (size_t)16 * e->vocab() * sizeof(float)));
-    HIP_TRY(hipMemset(m.nemb, 0, (size_t)16 * e->arch.codebook_dim * sizeof(float)));
+    const size_t RW = (size_t)step_rows(slots);
+    HIP_TRY(hipMemset(m.xs, 0, RW * d * sizeof(float)));
+    HIP_TRY(hipMemset(m.qb, 0, RW * d * sizeof(float)));
+    HIP_TRY(hipMemset(m.apart, 0, RW * heads * 8 * (dkh + 2) * sizeof(float)));
+    HIP_TRY(hipMemset(m.hb, 0, RW * S.s.ff * sizeof(float)));
+    HIP_TRY(hipMemset(m.lg, 0, RW * e->vocab() * sizeof(float)));
+    HIP_TRY(hipMemset(m.nemb, 0, RW * e->arch.codebook_dim * sizeof(float)));
     HIP_TRY(hipMemset(m.edge, 0, m.edge_stride * S.s.layers * sizeof(float)));
     HIP_TRY(hipMemset(m.psync, 0, (m.sync_words + 32) * sizeof(unsigned)));
     s->rules.assign(slots, lk::SampleRow{});                // the neutral rules
@@ -1706,7 +1725,7 @@ int fc_laura_linear(fc_laura* e, const char* name, const float* x, int B, int T,
     Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
     if (step_form) {
         if (!L.wf) return fail(std::string(name) + " has no decoding-step form");
-        if (B * T > 16) return fail("step form: at most 16 rows");
+        if (B * T > 64) return fail("step form: at most 64 rows");
         if (step_form < 1 || step_form > 3) return fail("step_form must be 0 .. 3");
         cx.check(step_gemv(L, x, B * T, nullptr, nullptr, 0.f, 0, 0, y, L.cout, cx.st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0,
                            step_form - 1), "GEMV");

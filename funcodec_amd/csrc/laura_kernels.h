@@ -5,8 +5,9 @@
 //   * FULL-SEQUENCE form (text encoder, LM prefix / teacher forcing, fine codec predictor): activations are FEATURE-MAJOR
 //     [B][C][T] (time contiguous), so every Linear is a k = 1 layer of the codec's implicit-GEMM conv kernel (fp32-input MFMA,
 //     conv_kernel.h) and attention reads Q / K / V rows as [d][t] slabs;
-//   * STEP form (autoregressive decoding with a KV cache): B <= 16 new tokens per step, TOKEN-MAJOR vectors [B][C]; every
-//     Linear is a weight-streaming GEMV on 16x16x4 MFMAs (weights in fragment order, one contiguous 1 KiB per wave load),
+//   * STEP form (autoregressive decoding with a KV cache): B <= 64 new tokens per step, TOKEN-MAJOR vectors [B][C]; every
+//     Linear is a weight-streaming GEMV on 16x16x4 MFMAs (weights in fragment order, one contiguous 1 KiB per wave load;
+//     rows beyond 16 as further column blocks of 16 on grid.y, each the 16-column kernel on its own rows),
 //     LayerNorm / activation / residual / cache scatter fused into its prologue / epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,6 +100,8 @@ struct Gemv {
     // test hooks: 1 = one stage whatever the batch allows, 2 = at least two windows
     int stage = 0;
 };
+// 1 <= B <= 64.  The stage form, the waves per workgroup and the window count follow from K alone, as for 16 rows: a row's accumulation
+// order does not depend on B or on the row's column block.
 hipError_t launch_gemv(const Gemv& g, hipStream_t st);
 // rows of x [B][C] in place: [relu](LayerNorm(x)) * post_scale
 hipError_t launch_layernorm_rows(float* x, const float* gamma, const float* beta, float eps, int relu, float post_scale, int B, int C,

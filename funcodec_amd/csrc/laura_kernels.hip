@@ -580,7 +580,7 @@ hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t st) {
 }
 
 // =====================================================================================================================
-// STEP FORM.  Weight-streaming GEMV for B <= 16 new tokens: y[b][n] = f(sum_k W[n][k] g(x)[b][k] + bias[n]).
+// STEP FORM.  Weight-streaming GEMV for B <= 64 new tokens, 16 per column block: y[b][n] = f(sum_k W[n][k] g(x)[b][k] + bias[n]).
 //   workgroup = one 16-row tile of W, KS waves splitting K; W in fragment order [tile][K/16][lane][4]: every wave load is one
 //   contiguous 1 KiB, all loads of a wave's K range issued before its MFMAs; x (optionally LayerNorm'ed) staged in LDS as the
 //   B operand (batch = the 16 MFMA columns, rows >= B read a zero row); partial tiles reduced across the waves in wave order
@@ -601,12 +601,34 @@ struct GemvArgs {
     int W, NW;                      // gemv_win_kernel: x staged in NW windows of W columns (XS = W + 4)
 };
 
+// Rows beyond 16: a workgroup's rows are those of COLUMN BLOCK blockIdx.y, rows 16 j .. min(B, 16 j + 16) - 1, and the kernels below see
+// that block alone: everything indexed by row (x, y, pos, the K / V cache slot of mode 2, the attention partials) starts at the block's
+// first row and B is the block's row count.  The tile stays on blockIdx.x, the fast index.  EXPECTED, from the dispatch order and not
+// measured (no counter run): workgroups go round-robin over the 8 XCDs by linear id, so the blocks of one tile meet on one XCD whenever
+// the tile count is a multiple of 8, and the tile's weight fragments are re-read from that XCD's L2.  Up to 16 rows (grid.y = 1) the
+// launcher takes the instantiations with WIDE = false, which do not have this prologue at all: the kernels of 16 columns.
+__device__ __forceinline__ void gemv_column_block(GemvArgs& a) {
+    const int j = blockIdx.y;
+    if (j == 0) { a.B = a.B < 16 ? a.B : 16; return; }
+    const size_t r0 = (size_t)16 * j;
+    a.B = a.B - 16 * j < 16 ? a.B - 16 * j : 16;
+    if (a.x) a.x += r0 * a.K;
+    a.y += r0 * a.ldy;
+    if (a.mode == 2) {
+        a.pos += r0;
+        a.kc += r0 * a.d * a.Tcap;
+        a.vc += r0 * a.Tcap * a.d;
+    }
+    if (a.apart) a.apart += r0 * a.H * a.NS * (a.DK + 2);
+}
+
 // CPW = 16-wide k chunks per wave as a compile-time constant (2 or 8 for every layer of the recipe): the weight loads are then
 // unconditional straight-line code.  Under a run-time count every load sat behind its own `if`, and hipcc waits for a conditional
 // load right where it is issued (DESIGN.md §5, round-2 finding) -- the "prefetch" was eight serialised round trips.  CPW = 0: generic.
-template <int KS, int CPW>
+template <int KS, int CPW, bool WIDE>
 __global__ __launch_bounds__(64 * KS) void gemv_kernel(GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    if constexpr (WIDE) gemv_column_block(a);
     float* Xs = lds;                                   // [B + 1][XS], row B = zeros
     float* red = lds + (a.B + 1) * a.XS;               // [KS][64][4]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, r16 = lane & 15;
@@ -748,9 +770,10 @@ __global__ __launch_bounds__(64 * KS) void gemv_kernel(GemvArgs a) {
 // barrier (a plain global load survives __syncthreads), and the next window's x requested into registers (a fixed trip count with
 // clamped addresses: unconditional loads) while the current one is multiplied.  CPW = 0: generic, loads per window.
 // x as given (no LayerNorm, no attention partials: both need whole rows); modes 0 and 1.
-template <int KS, int CPW, int NW>
+template <int KS, int CPW, int NW, bool WIDE>
 __global__ __launch_bounds__(64 * KS) void gemv_win_kernel(GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    if constexpr (WIDE) gemv_column_block(a);
     float* Xs = lds;                                   // [B + 1][XS]: the current window, row B = zeros
     float* red = lds + (a.B + 1) * a.XS;               // [KS][64][4]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, r16 = lane & 15;
@@ -857,38 +880,45 @@ hipError_t launch_gemv_windowed(const Gemv& g, GemvArgs a, int KS, dim3 grid, hi
     if (g.gamma || g.apart || g.mode == 2) return hipErrorInvalidValue;       // whole-row prologues / the cache scatter: K <= d
     // the fewest windows of <= 1024 columns that split every wave's chunks evenly (stage 2, test hook: at least two windows)
     const int cpw = g.K / 16 / KS, wmax = g.stage == 2 ? g.K : 1024;
+    const int rows = g.B < 16 ? g.B : 16;                  // of a column block: the LDS stage never holds more
     int nw = 0;
     for (int n = g.stage == 2 ? 2 : 1; n <= cpw && !nw; ++n)
-        if (cpw % n == 0 && g.K / n <= wmax && gemv_lds_bytes(g.B, g.K / n + 4, KS) <= 160 * 1024) nw = n;
+        if (cpw % n == 0 && g.K / n <= wmax && gemv_lds_bytes(rows, g.K / n + 4, KS) <= 160 * 1024) nw = n;
     if (!nw) return hipErrorInvalidValue;
     a.W = g.K / nw; a.NW = nw; a.XS = a.W + 4;
-    const size_t lds = gemv_lds_bytes(g.B, a.XS, KS);
-    static std::atomic<unsigned long long> d_spec, d_gen[5];
+    const size_t lds = gemv_lds_bytes(rows, a.XS, KS);
+    static std::atomic<unsigned long long> d_spec[2], d_gen[5][2];       // per kernel: [0] the 16-column form, [1] over column blocks
+    const bool wide = grid.y > 1;
     hipError_t e;
-    if (KS == 16 && cpw / nw == 4 && nw == 4) {
-        if ((e = big_lds(gemv_win_kernel<16, 4, 4>, d_spec)) != hipSuccess) return e;
-        hipLaunchKernelGGL((gemv_win_kernel<16, 4, 4>), grid, dim3(64 * 16), lds, st, a);
-        return hipGetLastError();
-    }
-#define FC_GEMV_WIN_CASE(ks, i)                                                           \
-    if (KS == ks) {                                                                       \
-        if ((e = big_lds(gemv_win_kernel<ks, 0, 0>, d_gen[i])) != hipSuccess) return e;   \
-        hipLaunchKernelGGL((gemv_win_kernel<ks, 0, 0>), grid, dim3(64 * ks), lds, st, a); \
-        return hipGetLastError();                                                         \
-    }
+#define FC_GEMV_WIN_LAUNCH(ks, cpwc, nwc, flag)                                                              \
+    do {                                                                                                     \
+        if (wide) {                                                                                          \
+            if ((e = big_lds(gemv_win_kernel<ks, cpwc, nwc, true>, flag[1])) != hipSuccess) return e;        \
+            hipLaunchKernelGGL((gemv_win_kernel<ks, cpwc, nwc, true>), grid, dim3(64 * ks), lds, st, a);     \
+        } else {                                                                                             \
+            if ((e = big_lds(gemv_win_kernel<ks, cpwc, nwc, false>, flag[0])) != hipSuccess) return e;       \
+            hipLaunchKernelGGL((gemv_win_kernel<ks, cpwc, nwc, false>), grid, dim3(64 * ks), lds, st, a);    \
+        }                                                                                                    \
+        return hipGetLastError();                                                                            \
+    } while (0)
+    if (KS == 16 && cpw / nw == 4 && nw == 4) FC_GEMV_WIN_LAUNCH(16, 4, 4, d_spec);
+#define FC_GEMV_WIN_CASE(ks, i) \
+    if (KS == ks) FC_GEMV_WIN_LAUNCH(ks, 0, 0, d_gen[i]);
     FC_GEMV_WIN_CASE(16, 0)
     FC_GEMV_WIN_CASE(8, 1)
     FC_GEMV_WIN_CASE(4, 2)
     FC_GEMV_WIN_CASE(2, 3)
     FC_GEMV_WIN_CASE(1, 4)
 #undef FC_GEMV_WIN_CASE
+#undef FC_GEMV_WIN_LAUNCH
     return hipErrorInvalidValue;
 }
 }  // namespace
 
 hipError_t launch_gemv(const Gemv& g, hipStream_t st) {
-    if (g.B < 1 || g.B > 16 || g.K % 16 || g.K < 16) return hipErrorInvalidValue;
+    if (g.B < 1 || g.B > 64 || g.K % 16 || g.K < 16) return hipErrorInvalidValue;
     const int nch = g.K / 16;
+    const int rows = g.B < 16 ? g.B : 16;                  // of a column block (gemv_column_block): what the LDS stage holds
     static const int ks_cap = fc::ab_knob("FC_GEMV_KS", 16);     // tuning aid: waves per workgroup
     int KS = ks_cap >= 1 && ks_cap <= 16 ? ks_cap : 16;
     while (KS > 1 && (nch % KS || nch / KS < 2)) KS >>= 1;     // >= 2 chunks per wave, K split evenly
@@ -897,38 +927,36 @@ hipError_t launch_gemv(const Gemv& g, hipStream_t st) {
                g.apart, g.H, g.DK, g.NS, 0, 0, 0};
     static const int ablate = fc::ab_knob("FC_GEMV_ABLATE", 0);
     a.ablate = ablate;
-    if (g.apart && (g.H * g.DK != g.K || g.NS < 1 || g.NS > 8 || g.B * g.H * 8 > KS * 256)) return hipErrorInvalidValue;
-    const dim3 grid(ceil_div_h(g.N, 16));
+    if (g.apart && (g.H * g.DK != g.K || g.NS < 1 || g.NS > 8 || rows * g.H * 8 > KS * 256)) return hipErrorInvalidValue;
+    const dim3 grid(ceil_div_h(g.N, 16), ceil_div_h(g.B, 16));      // tile x column block
     // one LDS stage whenever it fits at the largest batch (every K <= 2112: the path does not depend on B), windows beyond that
     const bool one_stage = g.stage == 1 || (g.stage == 0 && gemv_lds_bytes(16, g.K + 4, KS) <= 160 * 1024);
     if (!one_stage) return launch_gemv_windowed(g, a, KS, grid, st);
-    const size_t lds = gemv_lds_bytes(g.B, a.XS, KS);
+    const size_t lds = gemv_lds_bytes(rows, a.XS, KS);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static std::atomic<unsigned long long> d16[6], d8[6], d4[6], d2[6], d1[6];
+    static std::atomic<unsigned long long> d16[6][2], d8[6][2], d4[6][2], d2[6][2], d1[6][2];     // [.][1]: over column blocks
+    const bool wide = grid.y > 1;
     hipError_t e;
-#define FC_GEMV_CASE(ks, flag)                                                            \
-    if (KS == ks) {                                                                       \
-        const int cpw = nch / ks;                                                         \
-        if (cpw == 2) {                                                                   \
-            if ((e = big_lds(gemv_kernel<ks, 2>, flag[0])) != hipSuccess) return e;       \
-            hipLaunchKernelGGL((gemv_kernel<ks, 2>), grid, dim3(64 * ks), lds, st, a);    \
-        } else if (cpw == 8) {                                                            \
-            if ((e = big_lds(gemv_kernel<ks, 8>, flag[1])) != hipSuccess) return e;       \
-            hipLaunchKernelGGL((gemv_kernel<ks, 8>), grid, dim3(64 * ks), lds, st, a);    \
-        } else if (cpw == 4) {                                                            \
-            if ((e = big_lds(gemv_kernel<ks, 4>, flag[3])) != hipSuccess) return e;       \
-            hipLaunchKernelGGL((gemv_kernel<ks, 4>), grid, dim3(64 * ks), lds, st, a);    \
-        } else if (cpw == 16) {                                                           \
-            if ((e = big_lds(gemv_kernel<ks, 16>, flag[4])) != hipSuccess) return e;      \
-            hipLaunchKernelGGL((gemv_kernel<ks, 16>), grid, dim3(64 * ks), lds, st, a);   \
-        } else if (cpw == 32) {                                                           \
-            if ((e = big_lds(gemv_kernel<ks, 32>, flag[5])) != hipSuccess) return e;      \
-            hipLaunchKernelGGL((gemv_kernel<ks, 32>), grid, dim3(64 * ks), lds, st, a);   \
-        } else {                                                                          \
-            if ((e = big_lds(gemv_kernel<ks, 0>, flag[2])) != hipSuccess) return e;       \
-            hipLaunchKernelGGL((gemv_kernel<ks, 0>), grid, dim3(64 * ks), lds, st, a);    \
-        }                                                                                 \
-        return hipGetLastError();                                                         \
+#define FC_GEMV_LAUNCH(ks, cpwc, flag)                                                                  \
+    do {                                                                                                \
+        if (wide) {                                                                                     \
+            if ((e = big_lds(gemv_kernel<ks, cpwc, true>, flag[1])) != hipSuccess) return e;            \
+            hipLaunchKernelGGL((gemv_kernel<ks, cpwc, true>), grid, dim3(64 * ks), lds, st, a);         \
+        } else {                                                                                        \
+            if ((e = big_lds(gemv_kernel<ks, cpwc, false>, flag[0])) != hipSuccess) return e;           \
+            hipLaunchKernelGGL((gemv_kernel<ks, cpwc, false>), grid, dim3(64 * ks), lds, st, a);        \
+        }                                                                                               \
+        return hipGetLastError();                                                                       \
+    } while (0)
+#define FC_GEMV_CASE(ks, flag)                                \
+    if (KS == ks) {                                           \
+        const int cpw = nch / ks;                             \
+        if (cpw == 2) FC_GEMV_LAUNCH(ks, 2, flag[0]);         \
+        else if (cpw == 8) FC_GEMV_LAUNCH(ks, 8, flag[1]);    \
+        else if (cpw == 4) FC_GEMV_LAUNCH(ks, 4, flag[3]);    \
+        else if (cpw == 16) FC_GEMV_LAUNCH(ks, 16, flag[4]);  \
+        else if (cpw == 32) FC_GEMV_LAUNCH(ks, 32, flag[5]);  \
+        else FC_GEMV_LAUNCH(ks, 0, flag[2]);                  \
     }
     FC_GEMV_CASE(16, d16)
     FC_GEMV_CASE(8, d8)
@@ -936,6 +964,7 @@ hipError_t launch_gemv(const Gemv& g, hipStream_t st) {
     FC_GEMV_CASE(2, d2)
     FC_GEMV_CASE(1, d1)
 #undef FC_GEMV_CASE
+#undef FC_GEMV_LAUNCH
     return hipErrorInvalidValue;
 }
 

@@ -313,12 +313,15 @@ class LauraEngine:
         lens = [int(v) for v in out_lens]
         return (tokens, lens, logp) if return_logp else (tokens, lens)
 
-    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False) -> "DecodeSlots":
-        """A decoding session of `slots` slots (1 .. 16): prompts join and leave a running batch.  max_positions (default: the engine's)
+    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
+                    wide: bool = False) -> "DecodeSlots":
+        """A decoding session of `slots` slots (1 .. 16, or 1 .. 64 with wide=True): prompts join and leave a running batch.  max_positions (default: the engine's)
         bounds text_len + 2 + prompt tokens + max_length of a slot and sizes the session's state; logp=False leaves out the per-step
         log-probabilities [slots, max_positions, vocab], the largest part of it.  score=True keeps one number per slot and step, the
-        log-probability of the step's picks (DecodeSlots.score): [slots, max_positions] floats."""
-        return DecodeSlots(self, slots, max_positions, logp, score)
+        log-probability of the step's picks (DecodeSlots.score): [slots, max_positions] floats.  wide=True allows 1 .. 64 slots: the
+        step's GEMV runs the rows beyond 16 as further column blocks of 16, each as the 16-row kernel computes it; up to 16 slots it
+        is the session without the flag."""
+        return DecodeSlots(self, slots, max_positions, logp, score, wide)
 
     # -- LauraGenModel.cal_codec_emb on one-hot probabilities (syn_audio) ---------------------------------------------------
     @_on_device
@@ -364,14 +367,21 @@ SLOT_STATES = {1: "running", 2: "done", 3: "failed"}       # fc_laura_slots_step
 
 
 class DecodeSlots:
-    """A decoding session (``LauraEngine.open_decode``): S slots of ``decode_codec``, each holding one utterance at a time.  ``start``
+    """A decoding session (``LauraEngine.open_decode``): S slots (1 .. 16, or 1 .. 64 with ``wide=True``) of ``decode_codec``, each
+    holding one utterance at a time.  ``start``
     puts a prompt into a slot while the others are in the middle of theirs, ``step`` advances every running slot by the same number of
     decoding steps, ``take`` returns what an ended slot generated and frees it.  A slot depends on nothing but its own prompt and
     parameters; a session of one slot is ``decode_codec`` on the prompt alone, bit for bit."""
 
-    def __init__(self, engine: "LauraEngine", slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False):
+    MAX_SLOTS, MAX_SLOTS_WIDE = 16, 64
+
+    def __init__(self, engine: "LauraEngine", slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
+                 wide: bool = False):
         self.engine, self.lib, self.device = engine, engine.lib, engine.device
         self.slots = int(slots)
+        self.wide = bool(wide)
+        if self.wide and not 1 <= self.slots <= self.MAX_SLOTS_WIDE:
+            raise EngineError(f"a wide decoding session has 1 .. {self.MAX_SLOTS_WIDE} slots, got {slots}")
         self.max_positions = int(engine.max_positions if max_positions is None else max_positions)
         self.with_logp = bool(logp)
         self.with_score = bool(score)
@@ -386,7 +396,10 @@ class DecodeSlots:
     @_on_device
     def _open(self):
         eng = self.engine
-        if self.with_score:
+        if self.wide and self.slots > self.MAX_SLOTS:                   # up to 16 slots a wide session is the one below, call for call
+            nbytes = int(self.lib.fc_laura_slots_state_bytes_wide(eng._h, self.slots, self.max_positions, int(self.with_logp),
+                                                                  int(self.with_score)))
+        elif self.with_score:
             nbytes = int(self.lib.fc_laura_slots_state_bytes_scored(eng._h, self.slots, self.max_positions, int(self.with_logp), 1))
         else:                                                            # the session without scores: the call it always was
             nbytes = int(self.lib.fc_laura_slots_state_bytes(eng._h, self.slots, self.max_positions, int(self.with_logp)))
@@ -395,7 +408,10 @@ class DecodeSlots:
         if self.state is not None:
             torch.cuda.current_stream(self.device).synchronize()      # fc_laura_slots_create writes with copies that this stream does not order
         h = C.c_void_p()
-        if self.with_score:
+        if self.wide and self.slots > self.MAX_SLOTS:
+            eng._check(self.lib.fc_laura_slots_create_wide(eng._h, self.slots, self.max_positions, int(self.with_logp), int(self.with_score),
+                                                           _ptr(self.state), nbytes, C.byref(h)))
+        elif self.with_score:
             eng._check(self.lib.fc_laura_slots_create_scored(eng._h, self.slots, self.max_positions, int(self.with_logp), 1, _ptr(self.state),
                                                              nbytes, C.byref(h)))
         else:
@@ -1049,8 +1065,9 @@ class LauraGenMI355X:
         return self.engine.decode_codec(text, text_lengths, max_length, sampling, self._next_seed() if seed is None else seed, continual,
                                         continual_lengths)
 
-    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False) -> DecodeSlots:
-        return self.engine.open_decode(slots, max_positions, logp, score)
+    def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
+                    wide: bool = False) -> DecodeSlots:
+        return self.engine.open_decode(slots, max_positions, logp, score, wide)
 
     @torch.no_grad()
     def cal_codec_emb_batch(self, text, text_lengths, codec, codec_lengths):

@@ -642,7 +642,8 @@ int fc_laura_codec_emb(fc_laura* e, const float* text_outs, const int32_t* text_
 
 /* per-op entry point (tests pin each Linear against torch.nn.functional.linear): `name` = state_dict prefix of a Linear
  * ("codec_lm.encoder.encoders.3.feed_forward.w_1", "text_enc_out_layer", ...; "<block>.self_attn.linear_qkv" = the fused q/k/v).
- * x dev f32 [B][T][in], y dev f32 [B][T][out].  step_form != 0: through the decoding step's GEMV (LM layers only, B*T <= 16);
+ * x dev f32 [B][T][in], y dev f32 [B][T][out].  step_form != 0: through the decoding step's GEMV (LM layers only, B*T <= 64:
+ * rows beyond 16 as further column blocks of 16, each the 16-row call on its own rows, bit for bit);
  * 1 = as the decoding step stages x, 2 = x in one LDS stage, 3 = x in at least two LDS windows (2 and 3 are test hooks). */
 int fc_laura_linear(fc_laura* e, const char* name, const float* x, int B, int T, int step_form, float* y,
                     void* workspace, size_t workspace_bytes, void* stream);
@@ -744,6 +745,17 @@ int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_l
 size_t fc_laura_slots_state_bytes_scored(const fc_laura* e, int slots, int max_positions, int with_logp, int with_score);
 int  fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
                                   fc_laura_slots** out);
+/* A WIDE session: slots 1 .. 64, everything else as the _scored pair (which keeps refusing more than 16).  The step's weight-streaming
+ * GEMV takes 16 rows per workgroup (the MFMA's 16 columns); rows beyond them are further COLUMN BLOCKS of 16, block j = slot / 16, each
+ * computed by the 16-column kernel on its own rows: a slot's bits do not depend on its block or on what the other blocks hold.  Up to
+ * 16 slots a wide session IS the _scored session (state layout, launches, bits).  Above 16 the step runs as the kernel chain (the
+ * persistent launch is built for 16 rows), captured once per session as before, and the key ranges per head follow the same rule
+ * (256 / (slots * heads), 1 .. 8).  Every per-slot call takes every slot; fc_laura_slots_start_many stays at min(16, slots) prompts per
+ * call.  A slot costs its key / value rows (2 * layers * d_model * max_positions floats), its token and forced-token rows, its logits
+ * rows and, with_logp != 0, max_positions * vocab floats of log-probabilities. */
+size_t fc_laura_slots_state_bytes_wide(const fc_laura* e, int slots, int max_positions, int with_logp, int with_score);
+int  fc_laura_slots_create_wide(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
+                                fc_laura_slots** out);
 /* The score row of a slot that holds an utterance (running or ended; the slot keeps it: call this ahead of fc_laura_slots_take):
  *   terms      HOST f32 [cap], cap >= max_positions: the slot's whole row, zeros behind the terms written
  *   count_out  host: terms written as fc_laura_slots_step last reported -- n_gen, plus 1 for a slot that ended on <eos>

@@ -127,9 +127,32 @@ class Text2Audio:
         return ret[0], codecs[0]
 
     # -- the parts generate_batch and generate_many share ---------------------------------------------------------------------------
-    def _prompt_codecs(self, prompt_audios):
-        """First predict_nq code groups of every prompt recording: [T, nq] each (one codec call each: no padding inside an utterance)."""
+    def _refuse_length_aware(self, who: str):
+        """length_aware=True with a codec that has no length-aware calls raises here, before any engine call: nothing falls back."""
+        from ..engine import EngineError, ragged_refusal
+        why = ragged_refusal(self.codec_model.model.arch)
+        if why:
+            raise EngineError(f"{who}(length_aware=True): {why}")
+
+    def _prompt_codecs(self, prompt_audios, length_aware: bool = False):
+        """First predict_nq code groups of every prompt recording: [T, nq] each (one codec call each: no padding inside an utterance).
+        length_aware: the recordings in arrival order, 16 per codec call, zero-padded to the longest of the call and coded by their own
+        lengths (speech_lengths: every row as if it were alone)."""
         per = []
+        if length_aware:
+            frames = self.codec_model.model.engine.frames
+            wavs = [torch.as_tensor(a, dtype=torch.float32) for a in prompt_audios]
+            for i, a in enumerate(wavs):
+                if a.dim() < 2 or a.shape[0] != 1 or tuple(a.shape[1:-1]) != tuple(wavs[0].shape[1:-1]):
+                    raise ValueError(f"prompt recording {i}: one utterance [1, T] (or [1, C, T]) each, got {tuple(a.shape)}")
+            for g in (wavs[i: i + 16] for i in range(0, len(wavs), 16)):
+                ns = [int(a.shape[-1]) for a in g]
+                speech = torch.zeros((len(g),) + tuple(g[0].shape[1:-1]) + (max(ns),), dtype=torch.float32)
+                for b, a in enumerate(g):
+                    speech[b, ..., : ns[b]] = a[0]
+                codes = self.codec_model(speech, run_mod="encode", speech_lengths=torch.tensor(ns, dtype=torch.int64))[0][0]     # [n_q, B, Tf]
+                per += [codes[:, b, : frames(ns[b])].transpose(0, 1)[:, : self.model.predict_nq] for b in range(len(g))]
+            return per
         for a in prompt_audios:
             a = torch.as_tensor(a, dtype=torch.float32)
             codec = self.codec_model(a, run_mod="encode")[0][0].squeeze(1).transpose(0, 1)      # [T, n_q]
@@ -154,9 +177,13 @@ class Text2Audio:
         text_outs, _ = m.encode(text_in, torch.tensor(lens))
         return text_outs, lens
 
-    def _synthesise(self, text_outs, lens, tokens, out_lens, excl):
-        """3. dense embeddings of all codec groups, then the codec decoder, for one batch of finished utterances."""
+    def _synthesise(self, text_outs, lens, tokens, out_lens, excl, length_aware: bool = False):
+        """3. dense embeddings of all codec groups, then the codec decoder, for one batch of finished utterances.
+        length_aware: two codec calls for the batch instead of two per utterance -- row j's frames [excl[j] or 0, out_lens[j]) packed to
+        the front of a padded batch (laura.pack_windows) and decoded by their own count (speech_lengths: every row as if it were alone)."""
         emb = self.model.cal_codec_emb_batch(text_outs, lens, tokens, out_lens)
+        if length_aware:
+            return self._decode_length_aware(emb, tokens, out_lens, excl)
         rets, codecs = [], []
         for i in range(len(lens)):
             dec = tokens[i: i + 1, : out_lens[i]]
@@ -167,19 +194,47 @@ class Text2Audio:
             codecs.append(dec)
         return rets, codecs
 
+    def _decode_length_aware(self, emb, tokens, out_lens, excl):
+        from ..laura import pack_windows
+        n = len(out_lens)
+        lo = [int(e or 0) for e in excl]
+        k = [int(out_lens[j]) - lo[j] for j in range(n)]
+        live = [j for j in range(n) if k[j] > 0]
+        rets = [None] * n
+        if live:
+            rows = slice(None) if len(live) == n else live
+            lo_l, hi_l = [lo[j] for j in live], [int(out_lens[j]) for j in live]
+            ks = torch.tensor([k[j] for j in live], dtype=torch.int64)
+            _, _, only_lm, _ = self.codec_model(pack_windows(tokens[rows], lo_l, hi_l), bit_width=None, run_mod="decode", speech_lengths=ks)
+            _, _, gen, _ = self.codec_model(pack_windows(emb[rows], lo_l, hi_l), run_mod="decode_emb", speech_lengths=ks)
+            samples = self.codec_model.model.engine.decoded_samples
+            for r, j in enumerate(live):
+                ns = samples(k[j])
+                rets[j] = dict(gen=gen[r: r + 1, :, : ns].clone(), gen_only_lm=only_lm[r: r + 1, :, : ns].clone())
+        for j in range(n):
+            if rets[j] is None:       # no frame behind the prompt: the row is in no batch and gets what the one-utterance calls give it
+                dec = tokens[j: j + 1, : out_lens[j]]
+                _, _, only_lm, _ = self.codec_model(dec[:, excl[j]:], bit_width=None, run_mod="decode")
+                _, _, gen, _ = self.codec_model(emb[j: j + 1, : out_lens[j]][:, excl[j]:], run_mod="decode_emb")
+                rets[j] = dict(gen=gen, gen_only_lm=only_lm)
+        return rets, [tokens[j: j + 1, : out_lens[j]] for j in range(n)]
+
     # -- up to 16 prompts per engine call -----------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate_batch(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
-                       prompt_audios: Optional[Sequence[np.ndarray]] = None, seed: Optional[int] = None):
+                       prompt_audios: Optional[Sequence[np.ndarray]] = None, seed: Optional[int] = None, length_aware: bool = False):
         """Returns (list of {"gen": wav [1, 1, T], "gen_only_lm": wav}, list of decoded_codec [1, T, predict_nq]) like calling the
-        reference once per utterance; utterances of one call share the engine passes."""
+        reference once per utterance; utterances of one call share the engine passes.
+        length_aware = True also shares the codec calls (one encode for the prompts, two decodes for the batch; see generate_many)."""
         m, nq = self.model, self.model.predict_nq
         n = len(texts)
+        if length_aware:
+            self._refuse_length_aware("generate_batch")
         continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
         cont, cont_lens = None, None
         if continual_mode:
             texts = [" ".join([p, t]).strip() for p, t in zip(prompt_texts, texts)]
-            per = self._prompt_codecs(prompt_audios)
+            per = self._prompt_codecs(prompt_audios, length_aware)
             cont_lens = [int(c.shape[0]) for c in per]
             cont = torch.zeros((n, max(cont_lens), nq), dtype=torch.int64, device=m.device)
             for i, c in enumerate(per):
@@ -188,13 +243,14 @@ class Text2Audio:
         # 2. first codec groups, autoregressively
         tokens, out_lens = m.decode_codec_batch(text_outs, lens, self.max_length, self.sampling, cont, cont_lens, seed)
         excl = [(cl if self.exclude_prompt else 0) for cl in (cont_lens or [0] * n)] if continual_mode else [None] * n
-        return self._synthesise(text_outs, lens, tokens, out_lens, excl)
+        return self._synthesise(text_outs, lens, tokens, out_lens, excl, length_aware)
 
     # -- any number of prompts through a decoding session ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
-                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all", rules=None, prefill: int = 0):
+                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all", rules=None, prefill: int = 0,
+                      length_aware: bool = False):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
         request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.  slots = 17 ..
@@ -228,8 +284,14 @@ class Text2Audio:
         they sample is never used.  Texts are still encoded one request at a time.  A slot started by the copy is, bit for bit, the
         slot its own prefix pass gives, so the results are token for token and sample for sample those of prefill = 0 (the default:
         today's call) with the same seeds, whatever samples, retries, keep and rules; n requests cost ceil(n / P) prefix passes
-        instead of n.  ``self.last_prefix_passes`` = {"main", "held"} says how many each session of the last call ran."""
-        from ..laura import HeldPrompts, drive_best, drive_retries, drive_samples, retry_seed
+        instead of n.  ``self.last_prefix_passes`` = {"main", "held"} says how many each session of the last call ran.
+
+        length_aware = True runs the codec around the session as length-aware batches (``speech_lengths``: every row as if it were alone)
+        instead of one call per utterance: the prompt recordings 16 per encode call in arrival order; the finished candidates sorted by
+        the frames they decode (laura.tail_groups), 16 per fine-predictor call and per pair of decode calls.  Tokens are those of the
+        default (False: today's call); waveforms are a length-aware row's, within the 1e-4 RMS bar of such a row against its own call.  A
+        codec without length-aware calls (engine.ragged_refusal) raises before anything runs."""
+        from ..laura import HeldPrompts, drive_best, drive_retries, drive_samples, retry_seed, tail_groups
         m, nq = self.model, self.model.predict_nq
         n, N, R = len(texts), int(samples), int(retries)
         if N < 1:
@@ -242,11 +304,13 @@ class Text2Audio:
         if not 0 <= P <= 16:
             raise ValueError(f"generate_many: prefill must be 0 (off) or 1 .. 16 rows, got {prefill}")
         best = keep == "best"
+        if length_aware:
+            self._refuse_length_aware("generate_many")
         continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
         per = None
         if continual_mode:
             texts = [" ".join([p, t]).strip() for p, t in zip(prompt_texts, texts)]
-            per = self._prompt_codecs(prompt_audios)
+            per = self._prompt_codecs(prompt_audios, length_aware)
         if seeds is None:
             seeds = [m._next_seed() for _ in range(n * N)]
         elif N == 1:
@@ -315,19 +379,23 @@ class Text2Audio:
             session.free()
             if held is not None:
                 held.free()
-        rets, codecs = [], []
         cands = sorted(taken) if best else list(range(n * N))          # keep = "best": the winners only
-        for g in (cands[i: i + 16] for i in range(0, len(cands), 16)):      # finished utterances, 16 at a time, through the batch forms
+        first = {c: ((int(per[c // N].shape[0]) if self.exclude_prompt else 0) if continual_mode else None) for c in cands}
+        if length_aware:          # neighbours in decoded length share a call: a length-aware call computes over its group's common width
+            groups = [[cands[p] for p in g] for g in tail_groups([taken[c][1] - (first[c] or 0) for c in cands], 16)]
+        else:
+            groups = [cands[i: i + 16] for i in range(0, len(cands), 16)]
+        done = {}
+        for g in groups:                                                    # finished utterances, 16 at a time, through the batch forms
             L, C = max(lens[c // N] for c in g), max(max(taken[c][1] for c in g), 1)
             text_outs = torch.zeros((len(g), L, outs[g[0] // N].shape[-1]), dtype=torch.float32, device=m.device)
             tokens = torch.zeros((len(g), C, nq), dtype=torch.int64, device=m.device)
             for j, c in enumerate(g):
                 text_outs[j, : lens[c // N]] = outs[c // N]
                 tokens[j, : taken[c][1]] = taken[c][0]
-            excl = [((int(per[c // N].shape[0]) if self.exclude_prompt else 0) if continual_mode else None) for c in g]
-            r, cd = self._synthesise(text_outs, [lens[c // N] for c in g], tokens, [taken[c][1] for c in g], excl)
-            rets += r
-            codecs += cd
+            r, cd = self._synthesise(text_outs, [lens[c // N] for c in g], tokens, [taken[c][1] for c in g], [first[c] for c in g], length_aware)
+            done.update(zip(g, zip(r, cd)))
+        rets, codecs = [done[c][0] for c in cands], [done[c][1] for c in cands]          # request order, however they were grouped
         if best:
             return rets, codecs, choice
         if N == 1:

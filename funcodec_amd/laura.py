@@ -796,6 +796,30 @@ def prefill(need: int, held: Dict[int, int], rows: int, n_requests: int, fresh: 
     return list(zip(free, want))
 
 
+def tail_groups(lengths: Sequence[int], rows: int = 16) -> List[List[int]]:
+    """Which finished candidates go through the fine predictor and the codec decoder together (``generate_many(length_aware=True)``),
+    a plain function of their lengths: the indices sorted by length, ties to the lower index, cut into groups of at most `rows`.  A
+    length-aware call computes over its group's common width, so neighbours in length share a call; results do not depend on it."""
+    if rows < 1:
+        raise ValueError(f"tail_groups: a group has at least one row, got {rows}")
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    return [order[i: i + rows] for i in range(0, len(order), rows)]
+
+
+def pack_windows(x: torch.Tensor, lo: Sequence[int], hi: Sequence[int]) -> torch.Tensor:
+    """x [B, T, ...] -> [B, max(hi - lo), ...] with x[j, lo[j]: hi[j]] at the front of row j and zeros behind: the rows of a
+    length-aware decoder call start at frame 0 (a non-causal decoder run on a window is not a window of the decoder's output)."""
+    if not (len(lo) == len(hi) == x.shape[0]):
+        raise ValueError(f"pack_windows: one window per row ({x.shape[0]}), got {len(lo)} and {len(hi)}")
+    for j, (a, b) in enumerate(zip(lo, hi)):
+        if not 0 <= a <= b <= x.shape[1]:
+            raise ValueError(f"pack_windows: row {j}: window [{a}, {b}) outside 0 .. {x.shape[1]}")
+    out = x.new_zeros((x.shape[0], max((b - a for a, b in zip(lo, hi)), default=0)) + tuple(x.shape[2:]))
+    for j, (a, b) in enumerate(zip(lo, hi)):
+        out[j, : b - a] = x[j, a: b]
+    return out
+
+
 class HeldPrompts:
     """The bookkeeping of ``generate_many(prefill=P)`` around ``prefill``, no device in it: which row of the holding session holds
     which request, and when a row is released -- once all `samples` candidates of its request have started."""

@@ -184,6 +184,14 @@ SYMBOLS = {
     # a session of up to 64 slots (the step's GEMV over column blocks of 16 rows); up to 16 it is the _scored pair
     "fc_laura_slots_state_bytes_wide": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "fc_laura_slots_create_wide": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(_P)]),
+    # a queued session: tickets wait on the device, ended slots retire into a result ring and free slots claim inside the captured step
+    "fc_laura_slots_state_bytes_queued": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fc_laura_slots_create_queued": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, C.POINTER(_P)]),
+    "fc_laura_slots_submit": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_float, C.c_int, C.c_float, C.c_int,
+                                        C.c_int, C.POINTER(C.c_int32), _P]),
+    "fc_laura_slots_queue_status": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), _P]),
+    "fc_laura_slots_collect": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -249,8 +249,8 @@ class Text2Audio:
     @torch.no_grad()
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
-                      step_n: int = 1, samples: int = 1, retries: int = 0, keep: str = "all", rules=None, prefill: int = 0,
-                      length_aware: bool = False):
+                      step_n: Optional[int] = None, samples: int = 1, retries: int = 0, keep: str = "all", rules=None, prefill: int = 0,
+                      length_aware: bool = False, queue: bool = False):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
         request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.  slots = 17 ..
@@ -290,8 +290,18 @@ class Text2Audio:
         instead of one call per utterance: the prompt recordings 16 per encode call in arrival order; the finished candidates sorted by
         the frames they decode (laura.tail_groups), 16 per fine-predictor call and per pair of decode calls.  Tokens are those of the
         default (False: today's call); waveforms are a length-aware row's, within the 1e-4 RMS bar of such a row against its own call.  A
-        codec without length-aware calls (engine.ragged_refusal) raises before anything runs."""
-        from ..laura import HeldPrompts, drive_best, drive_retries, drive_samples, retry_seed, tail_groups
+        codec without length-aware calls (engine.ragged_refusal) raises before anything runs.
+
+        step_n (default 1, with queue 16) is the decoding steps per status read-back (laura.drive_slots).
+
+        queue = True (needs prefill >= 1, retries = 0 -- a rewind is the host's decision) takes the host out of the refill loop: the main
+        session is a QUEUED one (open_decode(queue=, source=the holding session)), every candidate is a ticket, and ended slots are
+        retired and refilled from the waiting tickets on the device inside the captured step, so step_n = 16 no longer lets an ended slot
+        idle.  The host fills held rows in arrival order, submits `samples` tickets per row, refills rows whose tickets are all claimed
+        (laura.queue_rows, laura.drive_queue) and collects results as they finish.  A ticket's slot is the slot
+        start_from(source=held) gives, bit for bit, so the results are token for token those of queue = False (the default: the call
+        as it is) with the same seeds, whatever samples, keep, rules, length_aware and slots."""
+        from ..laura import HeldPrompts, drive_best, drive_queue, drive_retries, drive_samples, pick_best, retry_seed, tail_groups
         m, nq = self.model, self.model.predict_nq
         n, N, R = len(texts), int(samples), int(retries)
         if N < 1:
@@ -304,6 +314,11 @@ class Text2Audio:
         if not 0 <= P <= 16:
             raise ValueError(f"generate_many: prefill must be 0 (off) or 1 .. 16 rows, got {prefill}")
         best = keep == "best"
+        if queue and P < 1:
+            raise ValueError("generate_many: queue=True needs prefill >= 1: tickets name rows of the holding session")
+        if queue and R > 0:
+            raise ValueError(f"generate_many: queue=True goes with retries = 0, got {retries}: a rewind is decided by the host")
+        step_n = (16 if queue else 1) if step_n is None else int(step_n)
         if length_aware:
             self._refuse_length_aware("generate_many")
         continual_mode = self.continual and prompt_texts is not None and prompt_audios is not None
@@ -324,10 +339,19 @@ class Text2Audio:
         outs, lens = [None] * n, [0] * n
         # more than 16 slots: a wide session (open_decode(wide=True), up to 64); up to 16 the call is the one it always was
         more = dict(wide=True) if int(slots) > 16 else {}
-        session = m.open_decode(slots, logp=False, score=True, **more) if best else m.open_decode(slots, logp=False, **more)
-        held, plan = None, None
+        held, plan, session = None, None, None
+        if queue:                   # the holding session first: the queued session is opened on it, with room for every ticket in flight
+            held = m.open_decode(P, logp=False)
+            try:
+                more.update(queue=int(slots) + P * N, source=held)
+                session = m.open_decode(slots, logp=False, score=True, **more) if best else m.open_decode(slots, logp=False, **more)
+            except Exception:
+                held.free()
+                raise
+        else:
+            session = m.open_decode(slots, logp=False, score=True, **more) if best else m.open_decode(slots, logp=False, **more)
         try:
-            if P:
+            if P and not queue:
                 held, plan = m.open_decode(P, logp=False), HeldPrompts(P, n, N)
 
             def encoded(i):
@@ -363,8 +387,24 @@ class Text2Audio:
 
             def rewind(slot, c, keep, attempt):
                 session.rewind(slot, keep, self.max_length, self.sampling, retry_seed(seeds[c], attempt), rules=rules)
+            def fill(batch):
+                for _, q in batch:
+                    encoded(q)
+                held.start_many({row: dict(text_outs=outs[q], text_len=lens[q], max_length=1, sampling=False,
+                                           continual=None if per is None else per[q]) for row, q in batch})
+
+            def submit(row, c):
+                return session.submit(row, self.max_length, self.sampling, seeds[c], rules=rules)
             choice = None
-            if best:
+            if queue:
+                flat = drive_queue(session, P, n, N, fill, submit, step_n)
+                if best:
+                    ks = [pick_best([t[-1] for t in flat[i * N: (i + 1) * N]]) for i in range(n)]
+                    taken = {i * N + k: flat[i * N + k] for i, k in enumerate(ks)}
+                    choice = [(k, taken[i * N + k][-1][0] / taken[i * N + k][-1][1]) for i, k in enumerate(ks)]
+                else:
+                    taken = flat
+            elif best:
                 kept = drive_best(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
                 taken = {i * N + k: t for i, (k, t) in enumerate(kept)}
                 choice = [(k, t[-1][0] / t[-1][1]) for k, t in kept]

@@ -617,9 +617,17 @@ lk::StepPersistArgs step_persist_args(const fc_laura* e, const StepMem& m, unsig
 
 // One decoding step: the newest token of every row through the LM against its KV cache, then the sampler.  Every kernel reads its
 // positions from device memory, so the launch sequence is identical from step to step.  pa null: the kernel chain.
-void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st) {
+// q (a queued session): the refill phase first -- ended slots retire, free slots claim waiting tickets and draw their first sample.
+void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st,
+              const lk::QueuePhase* q = nullptr) {
     const Stack& S = e->codec_lm;
     const int B = m.B, d = S.s.d_model, ff = S.s.ff, NL = S.s.layers, V = e->vocab(), Tcap = m.Tcap, heads = S.s.heads, dkh = d / S.s.heads;
+    if (q) {
+        cx.check(lk::launch_queue_phase(*q, 1, st), "queue phase");
+        lk::Sample first = sm;
+        first.launch_seq = nullptr;        // as slots_prefix: only the full-width launch numbers a persistent step
+        cx.check(lk::launch_sample_claims(first, *q, st), "sampling of the claimed slots");
+    }
     if (pa) {
         cx.check(lk::launch_step_persist(*pa, st), "persistent decoding step");
         cx.check(lk::launch_sample(sm, st), "sampling");
@@ -650,11 +658,12 @@ bool graph_enabled() {
 
 // one step captured on st as an executable graph (62 small launches on the chain: the loop is launch-bound otherwise); null if the
 // stream cannot be captured.  A launch that fails while capturing sets cx.err.
-hipGraphExec_t capture_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st) {
+hipGraphExec_t capture_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st,
+                            const lk::QueuePhase* q = nullptr) {
     hipGraphExec_t gexec = nullptr;
     hipGraph_t graph = nullptr;
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    run_step(e, cx, m, pa, sm, st);
+    run_step(e, cx, m, pa, sm, st, q);
     const hipError_t ec = hipStreamEndCapture(st, &graph);
     if (ec != hipSuccess || cx.err || hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) gexec = nullptr;
     if (graph) (void)hipGraphDestroy(graph);
@@ -785,11 +794,20 @@ struct fc_laura_slots {
     unsigned long long persist_steps = 0;   // persistent launches since the arrival counters were zeroed
     hipStream_t last = nullptr;
     int* status = nullptr;                  // pinned host [2 S + 1]: the read-back of a step (n_gen, done, error word)
+    // a queued session (fc_laura_slots_create_queued); Q = 0: none, and nothing below is used
+    int Q = 0;                              // result entries
+    const fc_laura_slots* from = nullptr;   // the source session: tickets name its rows
+    lk::QueuePhase qp;                      // the refill phase's view of both sessions
+    struct Entry { int state = 0, ticket = -1, n_tok = 0, n_gen = 0, eos = 0, seq = 0; };   // state: 0 free, 1 waiting or running, 2 finished, 3 failed
+    std::vector<Entry> entries;             // host mirror of the result entries, as of the last step's read-back
+    std::vector<int> slot_ticket;           // per slot, the ticket it runs (-1: none), as of the last step's read-back
+    long long submitted = 0, claimed = 0, finished = 0, collected = 0, failed = 0;
+    int queue_words() const { return lk::FC_QUEUE_WORDS + Q * lk::FC_QUEUE_META; }
 };
 
 namespace {
 
-void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, bool with_score, fc_laura_slots& s) {
+void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, bool with_score, fc_laura_slots& s, int Q = 0) {
     const int nq = e->arch.predict_nq, V = e->vocab();
     s.m = alloc_step_mem(e, cx, S, R);
     s.rows = cx.alloc<lk::SampleRow>(S);
@@ -799,6 +817,15 @@ void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, bool with_
     s.logp = with_logp ? cx.alloc<float>((size_t)S * R * V) : nullptr;
     s.lg0 = cx.alloc<float>((size_t)S * V);
     s.score = with_score ? cx.alloc<float>((size_t)S * R) : nullptr;       // behind everything a session without scores has
+    if (Q > 0) {                            // behind everything a session without a queue has
+        lk::QueuePhase& q = s.qp;
+        q.qw = cx.alloc<int>((size_t)lk::FC_QUEUE_WORDS + (size_t)Q * lk::FC_QUEUE_META);
+        q.ring = cx.alloc<lk::QueueTicket>(Q);
+        q.claims = cx.alloc<lk::QueueClaim>(64);
+        q.retires = cx.alloc<lk::QueueRetire>(64);
+        q.ring_tokens = cx.alloc<int64_t>((size_t)Q * R * nq);
+        q.ring_score = with_score ? cx.alloc<float>((size_t)Q * R) : nullptr;
+    }
 }
 
 lk::Sample slots_sampler(const fc_laura_slots* s) {
@@ -981,11 +1008,68 @@ int slots_from_prefix(fc_laura_slots* s, int dst, int src, int max_length, int s
     return 0;
 }
 
+// a queued session is fed by its queue only: the calls that put a prompt into a slot or take one out are refused, changing nothing
+int refuse_queued(const fc_laura_slots* s, const char* call) {
+    if (!s->Q) return 0;
+    return fail(std::string("decoding session: ") + call + ": a queued session is fed by its queue only (fc_laura_slots_submit, fc_laura_slots_collect)");
+}
+
 void slots_report(const fc_laura_slots* s, int32_t* done_out, int32_t* n_gen_out) {
     for (int i = 0; i < s->S; ++i) {
         if (done_out) done_out[i] = s->state[i];
         if (n_gen_out) n_gen_out[i] = s->n_gen[i];
     }
+}
+
+// The host's side of a queued session's step, behind the read-back: the mirrors of the counters, the slots' tickets and the result
+// entries.  A hand-off time-out of the persistent step fails every ticket that ran in this call -- those still in a slot and those the
+// call retired, whose tokens come from steps that cannot be trusted -- and the queue goes on over the kernel chain.
+int queue_after_step(fc_laura_slots* s, Ctx& cx, hipError_t ea, bool persist, int32_t* done_out, int32_t* n_gen_out) {
+    fc_laura* e = s->e;
+    const StepMem& m = s->m;
+    const int S = s->S, Q = s->Q;
+    const int* host = s->status;
+    const int* qw = host + 2 * S + 1;
+    if (ea != hipSuccess) {
+        if (!cx.err) fail(std::string("decoding session: status read-back failed: ") + hipGetErrorString(ea));
+        return 1;
+    }
+    const unsigned perr = (unsigned)host[2 * S];
+    s->claimed = qw[lk::FC_QUEUE_HEAD];
+    for (int en = 0; en < Q; ++en) {
+        const int* meta = qw + lk::FC_QUEUE_WORDS + en * lk::FC_QUEUE_META;
+        fc_laura_slots::Entry& E = s->entries[en];
+        if (E.state != 1 || meta[lk::FC_QMETA_STATE] != 2 || meta[lk::FC_QMETA_TICKET] != E.ticket) continue;
+        if (perr) { E.state = 3; s->failed++; continue; }
+        E.state = 2; E.n_tok = meta[lk::FC_QMETA_NTOK]; E.n_gen = meta[lk::FC_QMETA_NGEN]; E.eos = meta[lk::FC_QMETA_EOS];
+        E.seq = meta[lk::FC_QMETA_SEQ];
+        s->finished++;
+    }
+    for (int i = 0; i < S; ++i) {
+        s->slot_ticket[i] = qw[lk::FC_QUEUE_SLOT_TICKET + i];
+        const bool runs = s->slot_ticket[i] >= 0;
+        s->state[i] = runs ? (host[S + i] ? SLOT_DONE : SLOT_RUNNING) : SLOT_FREE;
+        s->n_gen[i] = runs ? host[i] : 0;
+    }
+    if (perr) {
+        for (int i = 0; i < S; ++i) {
+            if (s->slot_ticket[i] < 0) continue;
+            fc_laura_slots::Entry& E = s->entries[qw[lk::FC_QUEUE_SLOT_ENTRY + i]];
+            if (E.state == 1 && E.ticket == s->slot_ticket[i]) { E.state = 3; s->failed++; }
+            s->slot_ticket[i] = -1;
+            s->state[i] = SLOT_FREE; s->n_gen[i] = 0;
+        }
+        s->chain_only = true;
+        e->persist_fallbacks++;
+        if (s->gexec) { (void)hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
+        cx.check(lk::launch_fill_i32(m.done(), 1, S, cx.st), "done flags");
+        cx.check(lk::launch_fill_i32(s->qp.qw + lk::FC_QUEUE_SLOT_TICKET, -1, 64, cx.st), "slot tickets");
+        slots_reset_sync(s, cx);
+        if (hipStreamSynchronize(cx.st) != hipSuccess || cx.err) return fail("decoding session: reset after a timed-out step failed");
+    }
+    (void)persist;
+    slots_report(s, done_out, n_gen_out);
+    return 0;
 }
 
 int check_ready(fc_laura* e) {
@@ -1265,8 +1349,9 @@ int fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int 
     return fc_laura_slots_create_wide(e, slots, max_positions, with_logp, with_score, state, state_bytes, out);
 }
 
-int fc_laura_slots_create_wide(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
-                               fc_laura_slots** out) {
+// every create: Q = 0 is the session without a queue, call for call what fc_laura_slots_create_wide always did
+static int slots_create(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, int Q, const fc_laura_slots* from,
+                        void* state, size_t state_bytes, fc_laura_slots** out) {
     if (check_ready(e)) return 1;
     if (slots < 1 || slots > 64)
         return fail("a wide decoding session has 1 .. 64 slots (4 column blocks of the step form's 16 MFMA columns), got " + std::to_string(slots));
@@ -1277,7 +1362,7 @@ int fc_laura_slots_create_wide(fc_laura* e, int slots, int max_positions, int wi
     auto s = std::make_unique<fc_laura_slots>();
     s->e = e; s->S = slots; s->R = max_positions; s->with_logp = with_logp != 0; s->with_score = with_score != 0;
     Ctx cx = make_ctx(slots, state, state_bytes, nullptr);
-    slots_layout(e, cx, slots, max_positions, s->with_logp, s->with_score, *s);
+    slots_layout(e, cx, slots, max_positions, s->with_logp, s->with_score, *s, Q);
     if (cx.err) return fail("decoding session: state allocation too small (fc_laura_slots_state_bytes)");
     s->state.assign(slots, SLOT_FREE); s->cont_len.assign(slots, 0); s->max_len.assign(slots, 0); s->n_gen.assign(slots, 0);
     s->text_len.assign(slots, 0); s->prefix.assign(slots, 0); s->forced_on.assign(slots, 0);
@@ -1304,10 +1389,49 @@ int fc_laura_slots_create_wide(fc_laura* e, int slots, int max_positions, int wi
     const unsigned one = 1u;
     HIP_TRY(hipMemcpy(m.done(), ones.data(), (size_t)slots * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m.pseq, &one, sizeof(unsigned), hipMemcpyHostToDevice));
+    if (Q > 0) {
+        // the queue: nothing waits, no slot runs a ticket, every result entry is free
+        s->Q = Q; s->from = from;
+        s->entries.assign(Q, fc_laura_slots::Entry{});
+        s->slot_ticket.assign(slots, -1);
+        lk::QueuePhase& q = s->qp;
+        q.Q = Q; q.S = slots;
+        q.n_gen = m.n_gen(); q.done = m.done(); q.step = m.step(); q.pos = m.pos; q.tok_off = s->tok_off; q.rows = s->rows;
+        q.tokens = s->tokens; q.score = s->score; q.xs = m.xs; q.kc = m.kc; q.vc = m.vc; q.lg = m.lg; q.lg0 = s->lg0;
+        q.R = max_positions; q.nq = e->arch.predict_nq; q.dm = d; q.NL = S.s.layers; q.d = d; q.V = e->vocab();
+        q.kc_src = from->m.kc; q.vc_src = from->m.vc; q.lg0_src = from->lg0; q.tokens_src = from->tokens; q.S_src = from->S; q.R_src = from->R;
+        std::vector<int> words((size_t)s->queue_words(), 0);
+        for (int i = 0; i < 64; ++i) words[lk::FC_QUEUE_SLOT_TICKET + i] = -1;
+        HIP_TRY(hipMemcpy(q.qw, words.data(), words.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipHostMalloc((void**)&s->status, (size_t)(2 * slots + 1) * sizeof(int), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&s->status, (size_t)(2 * slots + 1 + (Q > 0 ? s->queue_words() : 0)) * sizeof(int), hipHostMallocDefault));
     *out = s.release();
     return 0;
+}
+
+int fc_laura_slots_create_wide(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
+                               fc_laura_slots** out) {
+    return slots_create(e, slots, max_positions, with_logp, with_score, 0, nullptr, state, state_bytes, out);
+}
+
+size_t fc_laura_slots_state_bytes_queued(const fc_laura* ce, int slots, int max_positions, int with_score, int queue) {
+    fc_laura* e = const_cast<fc_laura*>(ce);
+    if (!e || slots < 1 || slots > 64 || max_positions < 16 || max_positions > e->R || max_positions % 4 || queue < 1 || queue > 65536) return 0;
+    Ctx cx = make_ctx(slots, nullptr, 0, nullptr);
+    fc_laura_slots s;
+    slots_layout(e, cx, slots, max_positions, false, with_score != 0, s, queue);
+    return cx.off + 4096;
+}
+
+int fc_laura_slots_create_queued(fc_laura* e, int slots, int max_positions, int with_score, int queue, const fc_laura_slots* source,
+                                 void* state, size_t state_bytes, fc_laura_slots** out) {
+    if (check_ready(e)) return 1;
+    if (queue < 1 || queue > 65536) return fail("a queued decoding session has 1 .. 65536 result entries, got " + std::to_string(queue));
+    if (!source) return fail("a queued decoding session needs a source session (its tickets name the source's rows)");
+    if (source->e != e) return fail("a queued decoding session: the source session belongs to another engine (other weights: its prefix is not this engine's)");
+    if (source->Q) return fail("a queued decoding session: the source session is itself queued (it holds no prompts)");
+    return slots_create(e, slots, max_positions, 0, with_score, queue, source, state, state_bytes, out);
 }
 
 void fc_laura_slots_destroy(fc_laura_slots* s) {
@@ -1329,6 +1453,7 @@ int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, in
                          int max_length, int sampling_mode, int sampling_k, float sampling_p, uint64_t seed, const int64_t* forced,
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!s) return fail("null session");
+    if (refuse_queued(s, "start")) return 1;
     if (check_ready(s->e)) return 1;
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
     if (!text_outs || !workspace || text_len < 1 || max_length < 1 || cont_len < 0 || (cont_len > 0 && !continual))
@@ -1360,6 +1485,7 @@ int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, in
 int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_length, int sampling_mode, int sampling_k, float sampling_p,
                               uint64_t seed, const int64_t* forced, void* stream) {
     if (!s) return fail("null session");
+    if (refuse_queued(s, "start_from")) return 1;
     if (check_ready(s->e)) return 1;
     const std::string range = " outside 0 .. " + std::to_string(s->S - 1);
     if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + range);
@@ -1392,6 +1518,7 @@ int fc_laura_slots_start_many(fc_laura_slots* s, int n, const int32_t* slots, co
                               const int32_t* sampling_modes, const int32_t* sampling_ks, const float* sampling_ps, const uint64_t* seeds,
                               void* workspace, size_t workspace_bytes, void* stream) {
     if (!s) return fail("null session");
+    if (refuse_queued(s, "start_many")) return 1;
     if (check_ready(s->e)) return 1;
     if (!slots || !text_outs || !text_lens || !max_lengths || !sampling_modes || !sampling_ks || !sampling_ps || !seeds || !workspace ||
         n < 1 || L < 1 || Cmax < 0 || (continual && !cont_lens))
@@ -1449,6 +1576,7 @@ int fc_laura_slots_start_many(fc_laura_slots* s, int n, const int32_t* slots, co
 int fc_laura_slots_start_from_session(fc_laura_slots* s, int dst, const fc_laura_slots* from, int src, int max_length, int sampling_mode,
                                       int sampling_k, float sampling_p, uint64_t seed, const int64_t* forced, void* stream) {
     if (!s || !from) return fail("null session");
+    if (refuse_queued(s, "start_from_session")) return 1;
     if (check_ready(s->e)) return 1;
     if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + " outside 0 .. " + std::to_string(s->S - 1));
     if (from->e != s->e)
@@ -1503,6 +1631,7 @@ int fc_laura_slots_start_from_session(fc_laura_slots* s, int dst, const fc_laura
 int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_length, int sampling_mode, int sampling_k, float sampling_p,
                         uint64_t seed, void* stream) {
     if (!s) return fail("null session");
+    if (refuse_queued(s, "fork")) return 1;
     if (check_ready(s->e)) return 1;
     const std::string range = " outside 0 .. " + std::to_string(s->S - 1);
     if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + range);
@@ -1583,7 +1712,9 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
     if (n_steps < 1) return fail("decoding session: n_steps must be >= 1");
     bool any = false;
     for (int i = 0; i < s->S; ++i) any = any || s->state[i] == SLOT_RUNNING;
+    if (s->Q) any = s->submitted > s->finished + s->failed;             // a ticket waits or runs
     if (!any) { slots_report(s, done_out, n_gen_out); return 0; }
+    const lk::QueuePhase* qp = s->Q ? &s->qp : nullptr;
     fc_laura* e = s->e;
     const StepMem& m = s->m;
     Ctx cx = make_ctx(s->S, (void*)m.pos, 0, stream);       // launches only: nothing is allocated
@@ -1601,25 +1732,31 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
     }
     for (int i = 0; i < n_steps && !cx.err; ++i) {
         if (!s->warmed[persist]) {                          // the form's first step runs eagerly
-            run_step(e, cx, m, pap, sm, cx.st);
+            run_step(e, cx, m, pap, sm, cx.st, qp);
             s->warmed[persist] = true;
             continue;
         }
         if (!s->gexec && graph_enabled() && cx.st != nullptr) {
-            s->gexec = capture_step(e, cx, m, pap, sm, cx.st);
+            s->gexec = capture_step(e, cx, m, pap, sm, cx.st, qp);
             s->g_persist = persist; s->g_timeout = pa.test_timeout != 0;
             if (cx.err) break;
         }
         if (s->gexec) cx.check(hipGraphLaunch(s->gexec, cx.st), "graph launch");
-        else run_step(e, cx, m, pap, sm, cx.st);
+        else run_step(e, cx, m, pap, sm, cx.st, qp);
     }
     if (persist) s->persist_steps += (unsigned long long)n_steps;
-    // one stream-ordered read-back: n_gen [S], done [S] (adjacent) and the persistent step's error word
+    // a queued session retires what the last step ended before the read-back, so a finished ticket never waits for another call
+    if (qp && !cx.err) cx.check(lk::launch_queue_phase(*qp, 0, cx.st), "queue phase");
+    // one stream-ordered read-back: n_gen [S], done [S] (adjacent) and the persistent step's error word; of a queued session the queue
+    // block as well (counters, the ticket of every slot, the result entries' words), ahead of the same one synchronisation
     int* host = s->status;
     host[2 * s->S] = 0;
     hipError_t ea = cx.err ? hipErrorUnknown : hipMemcpyAsync(host, m.ctr, (size_t)2 * s->S * sizeof(int), hipMemcpyDeviceToHost, cx.st);
     if (ea == hipSuccess && persist) ea = hipMemcpyAsync(host + 2 * s->S, m.error_word(), sizeof(unsigned), hipMemcpyDeviceToHost, cx.st);
+    if (ea == hipSuccess && qp)
+        ea = hipMemcpyAsync(host + 2 * s->S + 1, qp->qw, (size_t)s->queue_words() * sizeof(int), hipMemcpyDeviceToHost, cx.st);
     if (ea == hipSuccess) ea = hipStreamSynchronize(cx.st);
+    if (qp) return queue_after_step(s, cx, ea, persist, done_out, n_gen_out);
     const unsigned perr = (unsigned)host[2 * s->S];
     if (ea != hipSuccess) {
         for (int i = 0; i < s->S; ++i)
@@ -1651,6 +1788,7 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
 
 int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, int32_t* len_out, float* logp_out) {
     if (!s) return fail("null session");
+    if (refuse_queued(s, "take")) return 1;
     if (check_ready(s->e)) return 1;
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
     if (s->state[slot] == SLOT_FAILED) return fail("decoding session: slot " + std::to_string(slot) + " failed (a hand-off of the persistent step timed out); start it again");
@@ -1671,6 +1809,7 @@ int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, i
 
 int fc_laura_slots_score(fc_laura_slots* s, int slot, float* terms, int cap, int32_t* count_out, int32_t* end_out) {
     if (!s) return fail("null session");
+    if (refuse_queued(s, "score")) return 1;
     if (check_ready(s->e)) return 1;
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
     if (!s->score) return fail("decoding session: slot " + std::to_string(slot) + ": the session was opened without scores");
@@ -1684,6 +1823,110 @@ int fc_laura_slots_score(fc_laura_slots* s, int slot, float* terms, int cap, int
     const bool ended = s->state[slot] == SLOT_DONE, eos = ended && s->n_gen[slot] < s->max_len[slot];
     *count_out = s->n_gen[slot] + (eos ? 1 : 0);
     *end_out = eos ? 2 : (ended ? 1 : 0);
+    return 0;
+}
+
+int fc_laura_slots_submit(fc_laura_slots* s, int row, int max_length, int sampling_mode, int sampling_k, float sampling_p, uint64_t seed,
+                          float temperature, int min_length, float top_p, int repeat_window, int repeat_count, int32_t* ticket_out,
+                          void* stream) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (!s->Q) return fail("decoding session: submit: the session was created without a queue (fc_laura_slots_create_queued)");
+    if (!ticket_out) return fail("null argument");
+    const fc_laura_slots* from = s->from;
+    const long long ticket = s->submitted;
+    const std::string who = "decoding session: ticket " + std::to_string(ticket) + " (row " + std::to_string(row) + "): ";
+    if (ticket >= 0x7fffffff) return fail(who + "the session has run out of ticket numbers");
+    if (row < 0 || row >= from->S) return fail(who + "row outside 0 .. " + std::to_string(from->S - 1) + " of the source session");
+    if (from->state[row] != SLOT_RUNNING && from->state[row] != SLOT_DONE)
+        return fail(who + "the row of the source session holds no prompt (" + (from->state[row] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+    if (max_length < 1) return fail(who + "max_length must be >= 1");
+    if (const char* why = sampling_problem(sampling_mode, sampling_k, sampling_p)) return fail(who + why);
+    // the rules, as fc_laura_slots_set_rules and the start that follows it check them
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) return fail(who + "temperature must be finite and > 0");
+    if (min_length < 0) return fail(who + "min_length " + std::to_string(min_length) + " < 0");
+    if (!(top_p >= 0.f && top_p <= 1.f)) return fail(who + "top_p must lie in (0, 1], or be 0 for none");
+    if (repeat_window < 0 || repeat_window > 256) return fail(who + "repeat_window " + std::to_string(repeat_window) + " outside 0 .. 256");
+    if (repeat_window > 0 && (repeat_count < 1 || repeat_count > repeat_window))
+        return fail(who + "repeat_count " + std::to_string(repeat_count) + " outside 1 .. repeat_window " + std::to_string(repeat_window));
+    if (top_p > 0.f && sampling_mode != 2) return fail(who + "top_p applies with top-k sampling (an integer `sampling`) only");
+    if (repeat_window > 0 && sampling_mode == 0) return fail(who + "the repeat rule needs a drawing mode, not greedy");
+    const int P = from->prefix[row], cont_len = from->cont_len[row];
+    if (P + max_length > s->R)
+        return fail(who + "text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) + " exceeds the session's max_positions " +
+                    std::to_string(s->R));
+    if (s->submitted - s->collected >= s->Q)
+        return fail(who + "all " + std::to_string(s->Q) + " result entries are in flight or uncollected (fc_laura_slots_collect frees them)");
+    int entry = -1;
+    for (int i = 0; i < s->Q && entry < 0; ++i)
+        if (s->entries[i].state == 0) entry = i;
+    if (entry < 0) return fail(who + "no free result entry");
+    lk::QueueTicket t;
+    t.row = row; t.P = P; t.cont_len = cont_len; t.entry = entry;
+    t.srow.mode = sampling_mode; t.srow.ki = sampling_k; t.srow.pf = sampling_p; t.srow.max_steps = max_length; t.srow.seed = seed;
+    t.srow.forced_on = 0; t.srow.rng_row = 0u;
+    t.srow.temperature = temperature; t.srow.min_length = min_length; t.srow.top_p = top_p;
+    t.srow.repeat_window = repeat_window; t.srow.repeat_count = repeat_window > 0 ? repeat_count : 1;
+    s->last = (hipStream_t)stream;
+    const hipError_t el = lk::launch_queue_put(s->qp, t, (int)ticket, s->last);
+    if (el != hipSuccess) return fail(who + "queue put: " + hipGetErrorString(el));
+    fc_laura_slots::Entry& E = s->entries[entry];
+    E = fc_laura_slots::Entry{};
+    E.state = 1; E.ticket = (int)ticket;
+    s->submitted++;
+    *ticket_out = (int32_t)ticket;
+    return 0;
+}
+
+int fc_laura_slots_queue_status(const fc_laura_slots* s, int64_t* submitted, int64_t* claimed, int64_t* finished, int64_t* failed,
+                                int64_t* collected, int32_t* slot_tickets) {
+    if (!s) return fail("null session");
+    if (!s->Q) return fail("decoding session: queue_status: the session was created without a queue (fc_laura_slots_create_queued)");
+    if (submitted) *submitted = s->submitted;
+    if (claimed) *claimed = s->claimed;
+    if (finished) *finished = s->finished;
+    if (failed) *failed = s->failed;
+    if (collected) *collected = s->collected;
+    if (slot_tickets)
+        for (int i = 0; i < s->S; ++i) slot_tickets[i] = s->slot_ticket[i];
+    return 0;
+}
+
+int fc_laura_slots_collect(fc_laura_slots* s, int cap, int32_t* tickets, int32_t* states, int32_t* lens, int32_t* n_gens, int32_t* ends,
+                           int64_t* tokens, float* scores, int32_t* n_out) {
+    if (!s) return fail("null session");
+    if (check_ready(s->e)) return 1;
+    if (!s->Q) return fail("decoding session: collect: the session was created without a queue (fc_laura_slots_create_queued)");
+    if (cap < 0 || !n_out || (cap > 0 && (!tickets || !states || !lens || !n_gens || !ends || !tokens))) return fail("null argument");
+    if (scores && !s->score) return fail("decoding session: collect: the session was created without scores");
+    // failed tickets first (in ticket order), then the finished ones in the order they finished
+    std::vector<int> order;
+    for (int i = 0; i < s->Q; ++i)
+        if (s->entries[i].state == 2 || s->entries[i].state == 3) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](int a, int b) {
+        const fc_laura_slots::Entry &A = s->entries[a], &B = s->entries[b];
+        if (A.state != B.state) return A.state > B.state;
+        return A.state == 3 ? A.ticket < B.ticket : A.seq < B.seq;
+    });
+    if ((int)order.size() > cap) order.resize(cap);
+    const int nq = s->e->arch.predict_nq;
+    const size_t tok_row = (size_t)s->R * nq;
+    for (size_t j = 0; j < order.size(); ++j) {
+        const fc_laura_slots::Entry& E = s->entries[order[j]];
+        tickets[j] = E.ticket; states[j] = E.state;
+        lens[j] = E.state == 2 ? E.n_tok : 0; n_gens[j] = E.state == 2 ? E.n_gen : 0; ends[j] = E.state == 2 ? (E.eos ? 2 : 1) : 0;
+        if (E.state != 2) continue;         // a failed ticket has no tokens
+        if (E.n_tok > 0)
+            HIP_TRY(hipMemcpyAsync(tokens + j * tok_row, s->qp.ring_tokens + (size_t)order[j] * tok_row, (size_t)E.n_tok * nq * sizeof(int64_t),
+                                   hipMemcpyDeviceToDevice, s->last));
+        if (scores)
+            HIP_TRY(hipMemcpyAsync(scores + j * s->R, s->qp.ring_score + (size_t)order[j] * s->R, (size_t)s->R * sizeof(float),
+                                   hipMemcpyDeviceToHost, s->last));
+    }
+    if (!order.empty()) HIP_TRY(hipStreamSynchronize(s->last));       // one synchronisation for all of them
+    for (int en : order) s->entries[en] = fc_laura_slots::Entry{};
+    s->collected += (long long)order.size();
+    *n_out = (int32_t)order.size();
     return 0;
 }
 

@@ -239,6 +239,55 @@ hipError_t launch_slot_branch(const SlotBranch& r, hipStream_t st);
 
 hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t st);
 
+// ---- the refill phase of a QUEUED decoding session (fc_laura_slots_create_queued) -------------------------------------------------
+// A ticket waits in a ring of descriptors; at the start of every step the session retires its ended slots into a result ring and
+// claims waiting tickets into its free slots, all from device memory: the launches and their arguments never change, so the phase is
+// part of the captured step.  No kernel of the phase waits on anything; the order comes from the launches.
+struct QueueTicket {                // one waiting ticket, written by queue_put_kernel
+    int row = 0;                    // the row of the source session that holds the prompt
+    int P = 0, cont_len = 0;        // its prefix positions and continual prompt length, as the host knew them at the submit
+    int entry = 0;                  // the result entry the ticket retires into
+    SampleRow srow{};               // the slot's row of the sampling table (mode, seed, max_length, rules)
+};
+struct QueueClaim { int slot, row, P, cont_len; };      // a claim of this step: the ticket's prompt into `slot`
+struct QueueRetire { int slot, entry, n_tok, pad; };    // a slot retired in this step: its first n_tok token rows into `entry`
+
+// words of the queue block (device ints, read back with every step): the counters, then the ticket each slot runs (-1: none) and the
+// result entry that ticket retires into, 64 slots each; behind them FC_QUEUE_META words per result entry
+enum { FC_QUEUE_HEAD = 0, FC_QUEUE_TAIL = 1, FC_QUEUE_FINISHED = 2, FC_QUEUE_NRETIRE = 3, FC_QUEUE_NCLAIM = 4, FC_QUEUE_SLOT_TICKET = 16,
+       FC_QUEUE_SLOT_ENTRY = 80, FC_QUEUE_WORDS = 144 };
+// a result entry's words: state (0 free, 1 waiting or running, 2 finished), ticket, token rows (prompt + generated), generated tokens,
+// ended on <eos>, the order of finishing (0, 1, ...)
+enum { FC_QUEUE_META = 8, FC_QMETA_STATE = 0, FC_QMETA_TICKET = 1, FC_QMETA_NTOK = 2, FC_QMETA_NGEN = 3, FC_QMETA_EOS = 4, FC_QMETA_SEQ = 5 };
+
+struct QueuePhase {
+    int* qw = nullptr;              // the queue block: FC_QUEUE_WORDS + Q * FC_QUEUE_META ints
+    QueueTicket* ring = nullptr;    // [Q]: ticket t waits at t % Q
+    QueueClaim* claims = nullptr;   // [64]
+    QueueRetire* retires = nullptr; // [64]
+    int Q = 0, S = 0;
+    // the queued session: counters, sampling table, rows (R positions per slot), caches
+    int *n_gen = nullptr, *done = nullptr, *step = nullptr, *pos = nullptr, *tok_off = nullptr;
+    SampleRow* rows = nullptr;
+    int64_t* tokens = nullptr;      // [S][R][nq]
+    float* score = nullptr;         // [S][R] or null
+    float* xs = nullptr;            // [S][dm]
+    float *kc = nullptr, *vc = nullptr, *lg = nullptr, *lg0 = nullptr;
+    int R = 0, nq = 0, dm = 0, NL = 0, d = 0, V = 0;
+    int64_t* ring_tokens = nullptr; // [Q][R][nq]
+    float* ring_score = nullptr;    // [Q][R] or null
+    // the source session (never this one): caches, prefix logits, token rows
+    const float *kc_src = nullptr, *vc_src = nullptr, *lg0_src = nullptr;
+    const int64_t* tokens_src = nullptr;
+    int S_src = 0, R_src = 0;
+};
+// ticket number `ticket` into the ring (one thread; the ticket by value in the kernel arguments, like the lengths)
+hipError_t launch_queue_put(const QueuePhase& q, const QueueTicket& t, int ticket, hipStream_t st);
+// the phase: queue_turn_kernel (retire, and with claim != 0 claim), queue_retire_copy_kernel, and with claim != 0 queue_claim_copy_kernel
+hipError_t launch_queue_phase(const QueuePhase& q, int claim, hipStream_t st);
+// launch_sample over the slots claimed in this step: block i samples row claims[i].slot, blocks >= the claim count exit at once
+hipError_t launch_sample_claims(const Sample& s, const QueuePhase& q, hipStream_t st);
+
 // ---- step form as ONE persistent launch (laura_persist.hip) ------------------------------------------------------------------------
 struct StepLayer {          // constant device pointers of one block (fragment-order weights of the step form, biases padded to row tiles)
     const float *wqkv, *bqkv, *wout, *bout, *wff1, *bff1, *wff2, *bff2;

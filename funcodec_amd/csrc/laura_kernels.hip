@@ -1172,6 +1172,9 @@ struct SampleArgs {
     // decoding session: per-row parameters (null: the call's own, above), the row stride of forced / logp_out / score_out, the first row of this launch
     const SampleRow* rows;
     int stride, row0;
+    // a queued session's refill phase (sample_kernel<true>): the claim table and its line count, else null
+    const QueueClaim* claims;
+    const int* nclaims;
 };
 
 #define FC_SAMPLE_MAXV 2048      // candidates per group, padded to a power of two for the bitonic sort (K + 1 <= 2048)
@@ -1373,7 +1376,16 @@ __device__ __forceinline__ int draw_inverse_cdf(const float* val, const int* idx
 // candidates to their nucleus; the repeat rule draws a second time, from the whole group in index order, when the first draw fills the
 // window.  While <eos> is masked it is the last candidate in every order (probability 0, the highest index) and is left out of the
 // candidates, so no rounding of the draw can return it.  The neutral rules skip every one of these statements.
+//
+//
+// CLAIMS: a second instantiation for a queued session's refill phase -- block i takes the row from line i of the claim table and the
+// blocks behind the claim count leave at once.  CLAIMS false is every other launch: the same statements as before the parameter
+// (as gemv_kernel's WIDE), compiled to the same number of instructions, registers (112 VGPRs, no private segment) and LDS bytes.
+template <bool CLAIMS>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
+    if constexpr (CLAIMS) {
+        if ((int)blockIdx.x >= *a.nclaims) return;
+    }
     __shared__ __attribute__((aligned(16))) float val[FC_SAMPLE_MAXV];
     __shared__ __attribute__((aligned(16))) int idx[FC_SAMPLE_MAXV];
     __shared__ float csum[256];
@@ -1387,7 +1399,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __shared__ int cidx[256];
     __shared__ int ccount;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int b = a.row0 + blockIdx.x;
+    const int b = CLAIMS ? a.claims[blockIdx.x].slot : a.row0 + blockIdx.x;
     const int G = a.K + 1, V = a.nq * G;
     // the call's parameters, or the row's own (a decoding session: the table is device memory, so a captured step never changes)
     const SampleRow* row = a.rows ? a.rows + b : nullptr;
@@ -1673,10 +1685,10 @@ hipError_t launch_sample(const Sample& s, hipStream_t st) {
     SampleArgs a{s.logits, s.K, s.nq, s.mode, s.ki, s.pf, s.seed, s.forced, s.max_steps, s.tokens, s.tok_stride, s.tok_off, s.n_gen,
                  s.done, s.n_done, s.pos, s.step, s.logp_out, s.score_out, s.cb, s.D, s.next_emb, s.B,
                  s.emb_wt, s.emb_bias, s.emb_g, s.emb_b, s.dm, s.emb_relu, s.xscale, s.xs, s.launch_seq,
-                 s.rows, s.rows ? s.row_stride : s.max_steps, s.row0};
+                 s.rows, s.rows ? s.row_stride : s.max_steps, s.row0, nullptr, nullptr};
     const int n = s.nrows > 0 ? s.nrows : s.B;
     if (s.row0 < 0 || s.row0 + n > s.B) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sample_kernel, dim3(n), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sample_kernel<false>, dim3(n), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
@@ -1939,6 +1951,188 @@ hipError_t launch_slot_branch(const SlotBranch& r, hipStream_t st) {
     if (r.K + 1 > FC_SAMPLE_MAXV || r.nq > 8 || r.nq < 1 || !r.cb || !r.next_emb) return hipErrorInvalidValue;
     if (r.emb_wt && (r.dm > 1024 || r.dm % 4 || r.D > FC_SAMPLE_MAXV)) return hipErrorInvalidValue;      // as launch_sample
     hipLaunchKernelGGL(slot_branch_kernel, dim3(65), dim3(256), 0, st, r);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The refill phase of a queued decoding session.  Four launches at the head of every step, each a function of device memory only:
+//   queue_turn_kernel        one wave, lane = slot.  A slot that runs a ticket and has ended is RETIRED: its result entry's words (token
+//                            rows, generated count, ended on <eos>, order of finishing), a line of the retire table, no ticket any more.
+//                            Then every free slot, in ascending order, CLAIMS the oldest waiting ticket: a line of the claim table, the
+//                            slot's ticket and entry words, and what slot_reset_kernel's thread 0 and the prefix import's last block
+//                            write -- counters, position = P, prompt length, the slot's row of the sampling table.
+//   queue_retire_copy_kernel the retired slots' token rows [0, n_tok) and score rows into their entries of the result ring.
+//   queue_claim_copy_kernel  per claim what slot_reset_kernel and prefix_import_kernel do: a zero LM input row, the token row = the held
+//                            row's continual prompt with zeros behind, a zero score row, the prefix keys / values (the import's vectors,
+//                            chunks and clamped loads in flight), the prefix logits into the step's and the saved row.
+//   sample_kernel<true>      the claimed slots' first sample.
+// The grids are fixed; the copy kernels stride over (table line x chunk) and read the line count first, so a step that retires or
+// claims nothing costs each block one load.  Every loop is bounded by S, a table's line count or a row size; nothing waits.
+// A queued session keeps no log-probability rows and takes no forced tokens, so those parts of slot_reset_kernel have no counterpart.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void queue_put_kernel(QueuePhase q, QueueTicket t, int ticket) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    q.ring[ticket % q.Q] = t;
+    int* meta = q.qw + FC_QUEUE_WORDS + t.entry * FC_QUEUE_META;
+    meta[FC_QMETA_STATE] = 1; meta[FC_QMETA_TICKET] = ticket; meta[FC_QMETA_NTOK] = 0; meta[FC_QMETA_NGEN] = 0; meta[FC_QMETA_EOS] = 0;
+    meta[FC_QMETA_SEQ] = 0;
+    q.qw[FC_QUEUE_TAIL] = ticket + 1;
+}
+
+__global__ __launch_bounds__(64) void queue_turn_kernel(QueuePhase q, int claim) {
+    const int s = threadIdx.x;
+    const bool valid = s < q.S;
+    const unsigned long long below = (1ull << s) - 1ull;
+    const int head = q.qw[FC_QUEUE_HEAD], tail = q.qw[FC_QUEUE_TAIL], fin = q.qw[FC_QUEUE_FINISHED];
+    const int ticket = valid ? q.qw[FC_QUEUE_SLOT_TICKET + s] : -1;
+    const bool ended = ticket >= 0 && q.done[s] != 0;
+    const unsigned long long ended_mask = __ballot(ended);
+    if (ended) {
+        const int at = __popcll(ended_mask & below), entry = q.qw[FC_QUEUE_SLOT_ENTRY + s];
+        const int gen = q.n_gen[s], n_tok = q.tok_off[s] + gen;
+        q.retires[at] = QueueRetire{s, entry, n_tok, 0};
+        int* meta = q.qw + FC_QUEUE_WORDS + entry * FC_QUEUE_META;
+        meta[FC_QMETA_STATE] = 2; meta[FC_QMETA_TICKET] = ticket; meta[FC_QMETA_NTOK] = n_tok; meta[FC_QMETA_NGEN] = gen;
+        meta[FC_QMETA_EOS] = gen < q.rows[s].max_steps ? 1 : 0;       // ended below its max_length: on <eos>
+        meta[FC_QMETA_SEQ] = fin + at;
+        q.qw[FC_QUEUE_SLOT_TICKET + s] = -1;
+    }
+    const int waiting = claim ? tail - head : 0;
+    const bool is_free = valid && (ticket < 0 || ended);
+    const unsigned long long free_mask = __ballot(is_free);
+    const int at = __popcll(free_mask & below);
+    if (is_free && at < waiting) {
+        const QueueTicket t = q.ring[(head + at) % q.Q];
+        q.claims[at] = QueueClaim{s, t.row, t.P, t.cont_len};
+        q.qw[FC_QUEUE_SLOT_TICKET + s] = head + at;
+        q.qw[FC_QUEUE_SLOT_ENTRY + s] = t.entry;
+        q.n_gen[s] = 0; q.done[s] = 0; q.step[s] = 0; q.pos[s] = t.P; q.tok_off[s] = t.cont_len;
+        q.rows[s] = t.srow;
+    }
+    if (s == 0) {
+        const int n_free = __popcll(free_mask), n_claim = n_free < waiting ? n_free : waiting, n_retire = __popcll(ended_mask);
+        q.qw[FC_QUEUE_HEAD] = head + n_claim;
+        q.qw[FC_QUEUE_FINISHED] = fin + n_retire;
+        q.qw[FC_QUEUE_NRETIRE] = n_retire;
+        q.qw[FC_QUEUE_NCLAIM] = n_claim;
+    }
+}
+
+typedef long long __attribute__((ext_vector_type(2))) i64x2;
+
+__global__ __launch_bounds__(256) void queue_retire_copy_kernel(QueuePhase q) {
+    const int n = q.qw[FC_QUEUE_NRETIRE];
+    const int t0 = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    const size_t tok_row = (size_t)q.R * q.nq;                        // int64 per row: even (R % 4 == 0)
+    for (int r = 0; r < n; ++r) {
+        const QueueRetire rt = q.retires[r];
+        const i64x2* ts = (const i64x2*)(q.tokens + (size_t)rt.slot * tok_row);
+        i64x2* td = (i64x2*)(q.ring_tokens + (size_t)rt.entry * tok_row);
+        const int nv = (rt.n_tok * q.nq + 1) >> 1;                    // <= tok_row / 2
+        for (int i = t0; i < nv; i += nth) td[i] = ts[i];
+        if (q.score) {
+            const f32x4* ss = (const f32x4*)(q.score + (size_t)rt.slot * q.R);
+            f32x4* sd = (f32x4*)(q.ring_score + (size_t)rt.entry * q.R);
+            for (int i = t0; i < (q.R >> 2); i += nth) sd[i] = ss[i];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void queue_claim_copy_kernel(QueuePhase q) {
+    const int n = q.qw[FC_QUEUE_NCLAIM];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.y == q.NL) {                                    // the rows of slot_reset_kernel and the import's logits
+        const int t0 = blockIdx.x * 256 + tid, nth = gridDim.x * 256;
+        const size_t tok_row = (size_t)q.R * q.nq;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < n; ++c) {
+            const QueueClaim cl = q.claims[c];
+            f32x4* xs = (f32x4*)(q.xs + (size_t)cl.slot * q.dm);
+            for (int i = t0; i < (q.dm >> 2); i += nth) xs[i] = zero;
+            const long long nprompt = (long long)cl.cont_len * q.nq;
+            const int64_t* ps = q.tokens_src + (size_t)cl.row * q.R_src * q.nq;
+            i64x2* td = (i64x2*)(q.tokens + (size_t)cl.slot * tok_row);
+            for (int i = t0; i < (int)(tok_row >> 1); i += nth) {
+                i64x2 v = {0, 0};
+                if (2ll * i < nprompt) v.x = ps[2 * i];
+                if (2ll * i + 1 < nprompt) v.y = ps[2 * i + 1];
+                td[i] = v;
+            }
+            if (q.score) {
+                f32x4* sc = (f32x4*)(q.score + (size_t)cl.slot * q.R);
+                for (int i = t0; i < (q.R >> 2); i += nth) sc[i] = zero;
+            }
+            const float* ls = q.lg0_src + (size_t)cl.row * q.V;
+            for (int v = t0; v < q.V; v += nth) {
+                const float x = ls[v];
+                q.lg[(size_t)cl.slot * q.V + v] = x;
+                q.lg0[(size_t)cl.slot * q.V + v] = x;
+            }
+        }
+        return;
+    }
+    const int l = blockIdx.y;
+    const size_t row_s = (size_t)q.d * q.R_src, row_d = (size_t)q.d * q.R;
+    for (int c = 0; c < n; ++c) {
+        const QueueClaim cl = q.claims[c];
+        const int kq = (cl.P + 3) >> 2;
+        const int nK = q.d * kq, nV = (cl.P * q.d) >> 2;
+        const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
+        for (int chunk = blockIdx.x; chunk < bK + bV; chunk += gridDim.x) {       // prefix_import_kernel's block `chunk` of layer l
+            const bool isK = chunk < bK;
+            const int blk = isK ? chunk : chunk - bK;
+            const float* sb = (isK ? q.kc_src : q.vc_src) + ((size_t)l * q.S_src + cl.row) * row_s;
+            float* db = (isK ? q.kc : q.vc) + ((size_t)l * q.S + cl.slot) * row_d;
+            const int nvec = isK ? nK : nV;
+            const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
+            size_t od[FC_PREFIX_VPT];
+            f32x4 v[FC_PREFIX_VPT];
+#pragma unroll
+            for (int u = 0; u < FC_PREFIX_VPT; ++u) {
+                int i = i0 + 256 * u;
+                i = i < nvec ? i : nvec - 1;                          // clamped: unconditional loads, predicated stores
+                const size_t os = isK ? (size_t)(i / kq) * q.R_src + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+                od[u] = isK ? (size_t)(i / kq) * q.R + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+                v[u] = *(const f32x4*)(sb + os);
+            }
+#pragma unroll
+            for (int u = 0; u < FC_PREFIX_VPT; ++u)
+                if (i0 + 256 * u < nvec) *(f32x4*)(db + od[u]) = v[u];
+        }
+    }
+}
+
+static bool queue_phase_ok(const QueuePhase& q) {
+    if (!q.qw || !q.ring || !q.claims || !q.retires || q.Q < 1 || q.S < 1 || q.S > 64) return false;
+    if (q.R < 4 || q.R % 4 || q.R_src < 4 || q.R_src % 4 || q.nq < 1 || q.d < 4 || q.d % 4 || q.dm < 4 || q.dm % 4 || q.NL < 1 || q.V < 1) return false;
+    if ((long long)q.d * q.R > 0x7fffffff || (long long)q.R * q.nq > 0x7fffffff) return false;       // a row's vectors are counted in int
+    return q.S_src >= 1 && q.kc && q.vc && q.kc_src && q.vc_src && q.tokens && q.tokens_src && q.ring_tokens && q.lg && q.lg0 && q.lg0_src &&
+           (q.score == nullptr) == (q.ring_score == nullptr);
+}
+hipError_t launch_queue_put(const QueuePhase& q, const QueueTicket& t, int ticket, hipStream_t st) {
+    if (!queue_phase_ok(q) || ticket < 0 || t.entry < 0 || t.entry >= q.Q || t.row < 0 || t.row >= q.S_src) return hipErrorInvalidValue;
+    // the rows the claim copies: inside both sessions' pitches
+    if (t.P < 1 || ((t.P + 3) & ~3) > q.R || ((t.P + 3) & ~3) > q.R_src || t.cont_len < 0 || t.cont_len > t.P) return hipErrorInvalidValue;
+    if (t.srow.max_steps < 1 || t.P + t.srow.max_steps > q.R) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(queue_put_kernel, dim3(1), dim3(1), 0, st, q, t, ticket);
+    return hipGetLastError();
+}
+hipError_t launch_queue_phase(const QueuePhase& q, int claim, hipStream_t st) {
+    if (!queue_phase_ok(q)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(queue_turn_kernel, dim3(1), dim3(64), 0, st, q, claim);
+    hipLaunchKernelGGL(queue_retire_copy_kernel, dim3(q.S < 16 ? q.S : 16), dim3(256), 0, st, q);
+    if (claim) hipLaunchKernelGGL(queue_claim_copy_kernel, dim3(32, q.NL + 1), dim3(256), 0, st, q);
+    return hipGetLastError();
+}
+hipError_t launch_sample_claims(const Sample& s, const QueuePhase& q, hipStream_t st) {
+    if (s.K + 1 > FC_SAMPLE_MAXV || s.nq > 8 || s.nq < 1 || !s.rows || s.logp_out || s.launch_seq) return hipErrorInvalidValue;
+    if (s.emb_wt && (s.dm > 1024 || s.dm % 4 || s.D > FC_SAMPLE_MAXV)) return hipErrorInvalidValue;      // as launch_sample
+    if (!queue_phase_ok(q) || s.B != q.S) return hipErrorInvalidValue;
+    SampleArgs a{s.logits, s.K, s.nq, s.mode, s.ki, s.pf, s.seed, s.forced, s.max_steps, s.tokens, s.tok_stride, s.tok_off, s.n_gen,
+                 s.done, s.n_done, s.pos, s.step, s.logp_out, s.score_out, s.cb, s.D, s.next_emb, s.B,
+                 s.emb_wt, s.emb_bias, s.emb_g, s.emb_b, s.dm, s.emb_relu, s.xscale, s.xs, s.launch_seq,
+                 s.rows, s.row_stride, 0, q.claims, q.qw + FC_QUEUE_NCLAIM};
+    hipLaunchKernelGGL(sample_kernel<true>, dim3(q.S), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

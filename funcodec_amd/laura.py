@@ -314,14 +314,21 @@ class LauraEngine:
         return (tokens, lens, logp) if return_logp else (tokens, lens)
 
     def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
-                    wide: bool = False) -> "DecodeSlots":
+                    wide: bool = False, queue: Optional[int] = None, source: Optional["DecodeSlots"] = None) -> "DecodeSlots":
         """A decoding session of `slots` slots (1 .. 16, or 1 .. 64 with wide=True): prompts join and leave a running batch.  max_positions (default: the engine's)
         bounds text_len + 2 + prompt tokens + max_length of a slot and sizes the session's state; logp=False leaves out the per-step
         log-probabilities [slots, max_positions, vocab], the largest part of it.  score=True keeps one number per slot and step, the
         log-probability of the step's picks (DecodeSlots.score): [slots, max_positions] floats.  wide=True allows 1 .. 64 slots: the
         step's GEMV runs the rows beyond 16 as further column blocks of 16, each as the 16-row kernel computes it; up to 16 slots it
-        is the session without the flag."""
-        return DecodeSlots(self, slots, max_positions, logp, score, wide)
+        is the session without the flag.
+
+        queue=Q with source=a holding session of this engine opens a QUEUED session (``DecodeSlots.submit`` / ``claimed`` /
+        ``collect``): tickets name a held row and wait on the device; inside every captured step ended slots retire into a result
+        ring of Q entries and free slots claim the oldest tickets, so ``step(n)`` is n steps with the slots full and one read-back.
+        It needs logp=False (no log-probability rows per ticket) and composes with score and wide."""
+        if queue is None and source is None:
+            return DecodeSlots(self, slots, max_positions, logp, score, wide)
+        return DecodeSlots(self, slots, max_positions, logp, score, wide, queue, source)
 
     # -- LauraGenModel.cal_codec_emb on one-hot probabilities (syn_audio) ---------------------------------------------------
     @_on_device
@@ -374,14 +381,38 @@ class DecodeSlots:
     parameters; a session of one slot is ``decode_codec`` on the prompt alone, bit for bit."""
 
     MAX_SLOTS, MAX_SLOTS_WIDE = 16, 64
+    MAX_QUEUE = 65536
+    queue: Optional[int] = None             # a session without a queue, unless __init__ says otherwise
+    source: Optional["DecodeSlots"] = None
 
     def __init__(self, engine: "LauraEngine", slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
-                 wide: bool = False):
+                 wide: bool = False, queue: Optional[int] = None, source: Optional["DecodeSlots"] = None):
         self.engine, self.lib, self.device = engine, engine.lib, engine.device
         self.slots = int(slots)
         self.wide = bool(wide)
         if self.wide and not 1 <= self.slots <= self.MAX_SLOTS_WIDE:
             raise EngineError(f"a wide decoding session has 1 .. {self.MAX_SLOTS_WIDE} slots, got {slots}")
+        #: result entries of a queued session (None: a session without a queue) and the holding session its tickets name rows of
+        self.queue = None if queue is None else int(queue)
+        self.source = source
+        if self.queue is None and source is not None:
+            raise EngineError("open_decode: source= goes with queue= (start_from(source=...) takes a source per call)")
+        if self.queue is not None:
+            if logp:
+                raise EngineError("open_decode: queue= needs logp=False: log-probability rows are not kept per ticket")
+            if not isinstance(source, DecodeSlots):
+                raise EngineError(f"open_decode: queue= needs source=, the holding DecodeSlots its tickets name rows of, got {type(source).__name__}")
+            if source.engine is not engine:
+                raise EngineError("open_decode: queue=: the source session belongs to another engine (other weights: its prefix is not this engine's)")
+            if source.queue is not None:
+                raise EngineError("open_decode: queue=: the source session is itself queued (it holds no prompts)")
+            if not 1 <= self.queue <= self.MAX_QUEUE:
+                raise EngineError(f"open_decode: queue must be 1 .. {self.MAX_QUEUE} result entries, got {queue}")
+            limit = self.MAX_SLOTS_WIDE if self.wide else self.MAX_SLOTS
+            if not 1 <= self.slots <= limit:
+                raise EngineError(f"a {'wide ' if self.wide else ''}decoding session has 1 .. {limit} slots, got {slots}")
+        self._submitted = self._claimed = self._finished = self._failed = self._collected = 0
+        self._ticket_max_length: Dict[int, int] = {}
         self.max_positions = int(engine.max_positions if max_positions is None else max_positions)
         self.with_logp = bool(logp)
         self.with_score = bool(score)
@@ -396,7 +427,9 @@ class DecodeSlots:
     @_on_device
     def _open(self):
         eng = self.engine
-        if self.wide and self.slots > self.MAX_SLOTS:                   # up to 16 slots a wide session is the one below, call for call
+        if self.queue is not None:
+            nbytes = int(self.lib.fc_laura_slots_state_bytes_queued(eng._h, self.slots, self.max_positions, int(self.with_score), self.queue))
+        elif self.wide and self.slots > self.MAX_SLOTS:                 # up to 16 slots a wide session is the one below, call for call
             nbytes = int(self.lib.fc_laura_slots_state_bytes_wide(eng._h, self.slots, self.max_positions, int(self.with_logp),
                                                                   int(self.with_score)))
         elif self.with_score:
@@ -408,7 +441,10 @@ class DecodeSlots:
         if self.state is not None:
             torch.cuda.current_stream(self.device).synchronize()      # fc_laura_slots_create writes with copies that this stream does not order
         h = C.c_void_p()
-        if self.wide and self.slots > self.MAX_SLOTS:
+        if self.queue is not None:
+            eng._check(self.lib.fc_laura_slots_create_queued(eng._h, self.slots, self.max_positions, int(self.with_score), self.queue,
+                                                             self.source._handle(), _ptr(self.state), nbytes, C.byref(h)))
+        elif self.wide and self.slots > self.MAX_SLOTS:
             eng._check(self.lib.fc_laura_slots_create_wide(eng._h, self.slots, self.max_positions, int(self.with_logp), int(self.with_score),
                                                            _ptr(self.state), nbytes, C.byref(h)))
         elif self.with_score:
@@ -449,6 +485,117 @@ class DecodeSlots:
             run.wait_stream(cur)
         return cur, run
 
+    def _refuse_queued(self, call: str) -> None:
+        if self.queue is not None:
+            raise EngineError(f"decoding session: {call}: a queued session is fed by its queue only (submit, collect)")
+
+    def _need_queue(self, call: str) -> None:
+        if self.queue is None:
+            raise EngineError(f"decoding session: {call}: the session was opened without a queue (open_decode(queue=, source=))")
+
+    @_on_device
+    def submit(self, row: int, max_length: int = 30 * 25, sampling: Union[bool, int, float] = True, seed: int = 0,
+               rules: Optional[SamplingRules] = None) -> int:
+        """A ticket into the queue of a queued session: the prompt that row `row` of the source session holds, with the ticket's own
+        max_length, sampling, seed and rules (no forced tokens).  Returns the ticket number, 0, 1, 2, ... in submit order; tickets are
+        claimed in that order, by free slots in ascending order, at the head of every decoding step.  One small launch, no
+        synchronisation.  The slot that claims the ticket is the slot ``start_from(slot, row, source=held, ...)`` gives, bit for bit,
+        so the result is a function of the row and these parameters alone.  Refused, naming the ticket and the row and changing
+        nothing: a row that holds no prompt, prefix + max_length beyond this session's max_positions, sampling and rules that do
+        not agree, and a queue whose `queue` result entries are all waiting, running or uncollected (``collect`` frees them)."""
+        self._need_queue("submit")
+        h = self._handle()
+        row, max_length = int(row), int(max_length)
+        if rules is not None and not isinstance(rules, SamplingRules):
+            raise ValueError(f"decode session submit: ticket {self._submitted} (row {row}): rules must be a SamplingRules or None, "
+                             f"got {type(rules).__name__}")
+        mode, k, p = sampling_args(sampling)
+        t, n, tp, w, r = (rules or SamplingRules()).args()
+        ticket = C.c_int32(-1)
+        cur, run = self._run_stream()
+        try:
+            self.engine._check(self.lib.fc_laura_slots_submit(h, row, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), t, n, tp, w, r,
+                                                              C.byref(ticket), C.c_void_p(run.cuda_stream)))
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+        self._submitted += 1
+        self._ticket_max_length[int(ticket.value)] = max_length
+        return int(ticket.value)
+
+    def _queue_status(self) -> None:
+        v = [C.c_int64(0) for _ in range(5)]
+        self._slot_tickets = (C.c_int32 * max(self.slots, 1))()
+        self.engine._check(self.lib.fc_laura_slots_queue_status(self._handle(), *[C.byref(x) for x in v], self._slot_tickets))
+        self._submitted, self._claimed, self._finished, self._failed, self._collected = (int(x.value) for x in v)
+
+    @property
+    def claimed(self) -> int:
+        """Tickets claimed so far, as the last ``step`` read it back (monotone): every ticket below this number has left the queue, so
+        a held row may be overwritten once ``claimed`` covers all its tickets."""
+        self._need_queue("claimed")
+        return self._claimed
+
+    @property
+    def finished(self) -> int:
+        """Tickets retired into the result ring so far, as the last ``step`` read it back (failed ones not counted)."""
+        self._need_queue("finished")
+        return self._finished
+
+    @property
+    def submitted(self) -> int:
+        self._need_queue("submitted")
+        return self._submitted
+
+    @property
+    def pending(self) -> int:
+        """Tickets waiting or running: ``step`` has work while this is not 0."""
+        self._need_queue("pending")
+        return self._submitted - self._finished - self._failed
+
+    def slot_tickets(self) -> Dict[int, int]:
+        """{slot: the ticket it runs}, as the last ``step`` read it back."""
+        self._need_queue("slot_tickets")
+        t = getattr(self, "_slot_tickets", None)
+        return {} if t is None else {i: int(t[i]) for i in range(self.slots) if int(t[i]) >= 0}
+
+    @_on_device
+    def collect(self, score_rows: bool = False) -> list:
+        """The results the last ``step`` calls retired, out of the ring with one synchronisation for all of them; their entries are
+        free afterwards.  [(ticket, tokens [len, nq] int64 = prompt tokens + generated ones, len, score)], failed tickets first, then
+        in the order of finishing.  score: None for a session without scores, else (sum, count, ended_on_eos) as ``DecodeSlots.score``
+        gives it, or with score_rows (row float32 [max_positions] on the host, count, end) as ``score_row`` does.  A ticket that ran
+        in a step call whose persistent step timed out is failed: (ticket, None, 0, None), never tokens."""
+        self._need_queue("collect")
+        h = self._handle()
+        self._queue_status()
+        cap = self._finished + self._failed - self._collected
+        if cap <= 0:
+            return []
+        nq, R = self.engine.spec.predict_nq, self.max_positions
+        i32 = lambda: (C.c_int32 * cap)()
+        tickets, states, lens, gens, ends = i32(), i32(), i32(), i32(), i32()
+        tokens = torch.zeros((cap, R, nq), dtype=torch.int64, device=self.device)
+        rows = torch.zeros((cap, R), dtype=torch.float32) if self.with_score else None
+        torch.cuda.current_stream(self.device).synchronize()          # the copies run on the session's stream
+        n = C.c_int32(0)
+        self.engine._check(self.lib.fc_laura_slots_collect(h, cap, tickets, states, lens, gens, ends, _ptr(tokens),
+                                                           C.c_void_p(rows.data_ptr()) if rows is not None else None, C.byref(n)))
+        out = []
+        for j in range(int(n.value)):
+            t = int(tickets[j])
+            self._ticket_max_length.pop(t, None)
+            if int(states[j]) != 2:
+                out.append((t, None, 0, None))
+                continue
+            count, end = int(gens[j]) + (1 if int(ends[j]) == 2 else 0), int(ends[j])
+            score = None
+            if rows is not None:
+                score = (rows[j].clone(), count, end) if score_rows else (float(rows[j, :count].double().sum()), count, end == 2)
+            out.append((t, tokens[j, : int(lens[j])].clone(), int(lens[j]), score))
+        self._queue_status()
+        return out
+
     def _set_rules(self, slot: int, rules: Optional[SamplingRules]) -> None:
         """`rules` (None: the neutral ones) as the rules the next start / start_from / fork into `slot` writes: per call, like sampling
         and seed.  Nothing on the device changes here."""
@@ -464,6 +611,7 @@ class DecodeSlots:
         """One prompt into `slot`: text_outs [L, D] or [1, L, D] (rows < text_len are used), continual int64 [C, nq] prompt tokens, forced
         int64 [max_length, nq], rules a ``SamplingRules`` (None: neutral).  A running slot's utterance is abandoned.  A refused call
         changes nothing for any slot."""
+        self._refuse_queued("start")
         eng, nq = self.engine, self.engine.spec.predict_nq
         h = self._handle()
         text_outs = eng._dev(text_outs, torch.float32)
@@ -550,6 +698,7 @@ class DecodeSlots:
         min(16, slots), the slots distinct, in any order.  Every named slot is, bit for bit, the slot ``start`` gives for its prompt and
         parameters -- how a slot was started changes its cost, never its result.  No forced tokens here: ``start`` forces.  A running
         slot's utterance is abandoned.  A refused call names the slot and changes nothing for any slot."""
+        self._refuse_queued("start_many")
         eng, nq = self.engine, self.engine.spec.predict_nq
         h = self._handle()
         rows = self._many_rows(requests)
@@ -614,6 +763,7 @@ class DecodeSlots:
         source's), sampling, seed, rules and forced tokens: a device copy of the source's prefix instead of a prefix pass.  `dst` is, bit for
         bit, the slot that ``start`` gives for the same prompt and parameters; `src` is not disturbed, may be running or ended (not yet
         taken), and may itself come from a start_from.  A running `dst` is abandoned.  A refused call changes nothing for any slot."""
+        self._refuse_queued("start_from")
         eng, nq = self.engine, self.engine.spec.predict_nq
         h = self._handle()
         dst, src = int(dst), int(src)
@@ -659,6 +809,7 @@ class DecodeSlots:
         of ``start`` with its final tokens forced.  `src` is not disturbed, may be running or ended (by <eos> or by length, not yet
         taken) and may itself come from a fork or a start_from; keep = 0 is ``start_from``.  A running `dst` is abandoned.  A refused
         call changes nothing for any slot."""
+        self._refuse_queued("fork")
         h = self._handle()
         dst, src = int(dst), int(src)
         if not 0 <= src < self.slots:
@@ -686,6 +837,7 @@ class DecodeSlots:
         """``fork(slot, slot, keep, ...)``: the slot goes back to its first `keep` generated tokens in place and goes on from there
         with the given sampling, seed, rules and max_length (default: its own).  An ended slot (not yet taken) runs again; one that ended on
         <eos>, rewound to keep = n_gen, draws its ending again."""
+        self._refuse_queued("rewind")
         self.fork(slot, slot, keep, max_length, sampling, seed, rules)
 
     def n_gen(self, slot: int) -> int:
@@ -706,6 +858,8 @@ class DecodeSlots:
         finally:
             if run is not cur:
                 cur.wait_stream(run)
+        if self.queue is not None:                  # the queue's counters and the slots' tickets, out of the same read-back
+            self._queue_status()
         if self.engine.persistent_step_fallbacks != before:
             self.engine._fallbacks_seen = self.engine.persistent_step_fallbacks
             import warnings
@@ -722,6 +876,7 @@ class DecodeSlots:
         written: the tokens generated as the last ``step`` reported (after a fork or rewind: the tokens kept), plus the ending step of
         a slot that ended on <eos>; the row is zero behind them.  end: 0 running, 1 ended by length, 2 ended on <eos>.  Refused, with
         the slot named, for a session opened without score=True."""
+        self._refuse_queued("score_row")
         h = self._handle()
         slot = int(slot)
         if not 0 <= slot < self.slots:
@@ -748,6 +903,7 @@ class DecodeSlots:
         """What an ended slot generated: (tokens [len, nq] int64 = prompt tokens + generated ones, len) and, with return_logp, the
         per-step log-probabilities [max_length, vocab]; with return_score, (sum, count, ended_on_eos) as ``score`` gives it is appended.
         The slot is free afterwards.  Refused for a slot that has not ended."""
+        self._refuse_queued("take")
         h = self._handle()
         slot = int(slot)
         if not 0 <= slot < self.slots:
@@ -794,6 +950,24 @@ def prefill(need: int, held: Dict[int, int], rows: int, n_requests: int, fresh: 
         free = [max(held, key=lambda r: held[r])]
     want = [need] + [q for q in range(max(need + 1, fresh), n_requests) if q not in held.values()]
     return list(zip(free, want))
+
+
+def queue_rows(held: Dict[int, int], claimed: int, rows: int) -> List[int]:
+    """Which rows of the holding session of a QUEUED session may be filled with new prompts, a plain function of (`held` = row -> the
+    number behind the last ticket submitted for the prompt the row holds, `claimed` = DecodeSlots.claimed): in ascending order, the
+    rows that hold nothing and the rows all of whose tickets have been claimed (tickets are claimed in submit order, so tickets
+    < held[row] claimed means claimed >= held[row]).  A claim copies the row's prefix inside the step that claims, so a claimed
+    ticket no longer reads the row; a row with a ticket still waiting is never returned."""
+    if rows < 1:
+        raise ValueError(f"queue_rows: a holding session has at least one row, got {rows}")
+    if claimed < 0:
+        raise ValueError(f"queue_rows: claimed must be >= 0, got {claimed}")
+    for row, end in held.items():
+        if not 0 <= row < rows:
+            raise ValueError(f"queue_rows: row {row} outside 0 .. {rows - 1}")
+        if end < 0:
+            raise ValueError(f"queue_rows: row {row}: ticket bound {end} < 0")
+    return [r for r in range(rows) if r not in held or claimed >= held[r]]
 
 
 def tail_groups(lengths: Sequence[int], rows: int = 16) -> List[List[int]]:
@@ -895,6 +1069,46 @@ def drive_slots(session, slots: int, n_requests: int, start, step_n: int = 1) ->
                     raise EngineError(f"decoding session: request {req} failed again after the session fell back to the kernel chain")
                 failed.append(req)
         pending[:0] = sorted(failed)
+    return results
+
+
+def drive_queue(session, rows: int, n_requests: int, samples: int, fill, submit, step_n: int = 16) -> list:
+    """`samples` candidates of each of n_requests requests through a QUEUED session whose holding session has `rows` rows: the host
+    fills rows and submits tickets, the device refills the slots.  ``fill([(row, request)])`` prefills those rows in one prefix pass
+    (DecodeSlots.start_many on the holding session); ``submit(row, candidate)`` returns the ticket of candidate = request * samples + k;
+    ``session.step`` / ``claimed`` / ``collect`` are a queued DecodeSlots' (or a stand-in's).  Requests go to rows in arrival order; the
+    rows ``queue_rows`` gives are refilled once at least min(requests left, max(1, rows // 2)) of them may be -- a pass per freed row
+    would bring back the serial prefix passes -- and a row never before all its tickets are claimed.  Between two looks the session runs
+    step_n steps; while requests are left to prefill and the slots without a ticket (``session.slots`` - ``session.slot_tickets()``) could
+    take every waiting ticket, it runs ONE, so that a session wider than the holding session fills in a few steps instead of rows per
+    step_n.  Returns the collected (tokens, len[, score]) per candidate, in candidate order.  A failed ticket (a timed-out persistent
+    step) raises: its row may be gone."""
+    total = n_requests * samples
+    held: Dict[int, int] = {}               # row -> the number behind the last ticket of the request it holds
+    owner: Dict[int, int] = {}              # ticket -> candidate
+    results = [None] * total
+    fresh, got, sent = 0, 0, 0
+    while got < total:
+        left = n_requests - fresh
+        free = queue_rows(held, session.claimed, rows)
+        if left and len(free) >= min(left, max(1, rows // 2)):
+            batch = list(zip(free, range(fresh, n_requests)))
+            fill(batch)
+            for row, request in batch:
+                for k in range(samples):
+                    ticket = submit(row, request * samples + k)
+                    owner[ticket] = request * samples + k
+                    held[row] = ticket + 1
+                    sent += 1
+            fresh += len(batch)
+        idle = session.slots - len(session.slot_tickets())
+        session.step(1 if fresh < n_requests and sent - session.claimed <= idle else step_n)
+        for ticket, tokens, n, score in session.collect():
+            if tokens is None:
+                raise EngineError(f"decoding session: ticket {ticket} failed (the persistent decoding step timed out); the session is on the "
+                                  "kernel chain from here on: run the call again")
+            results[owner.pop(ticket)] = (tokens, n) if score is None else (tokens, n, score)
+            got += 1
     return results
 
 
@@ -1090,8 +1304,10 @@ class LauraGenMI355X:
                                         continual_lengths)
 
     def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
-                    wide: bool = False) -> DecodeSlots:
-        return self.engine.open_decode(slots, max_positions, logp, score, wide)
+                    wide: bool = False, queue: Optional[int] = None, source: Optional[DecodeSlots] = None) -> DecodeSlots:
+        if queue is None and source is None:
+            return self.engine.open_decode(slots, max_positions, logp, score, wide)
+        return self.engine.open_decode(slots, max_positions, logp, score, wide, queue, source)
 
     @torch.no_grad()
     def cal_codec_emb_batch(self, text, text_lengths, codec, codec_lengths):

@@ -824,6 +824,50 @@ int fc_laura_slots_start_many(fc_laura_slots* s, int n, const int32_t* slots, co
 int fc_laura_slots_start_from_session(fc_laura_slots* dst_session, int dst, const fc_laura_slots* src_session, int src, int max_length,
                                       int sampling_mode, int sampling_k, float sampling_p, uint64_t seed, const int64_t* forced,
                                       void* stream);
+/* (entry points added without a struct change: FC_ABI_VERSION stays 7)
+ * A QUEUED session: its slots are fed by a queue of TICKETS on the device and by nothing else.  A ticket names a row of `source` -- a
+ * session of the same fc_laura that holds prompts (fc_laura_slots_start_many), fixed here; slot count and max_positions may differ --
+ * and its own max_length, sampling mode, seed and rules.  At the head of EVERY decoding step, inside the captured step and with no word
+ * from the host, (1) every slot whose utterance has ended is retired: its token rows, generated count, <eos> flag and, with_score, its
+ * score row go to the ticket's entry of a result ring in the session state, and the slot is free in the same step; (2) every free slot,
+ * in ascending order, claims the oldest waiting ticket.  Any number up to `slots` claim in one step.  A claimed slot is the slot
+ * fc_laura_slots_start_from_session gives for (row, max_length, mode, seed, rules), BIT FOR BIT -- prefix keys / values and logits,
+ * position, token row (the row's continual prompt, zeros behind), score row, sampling-table row, first sample, random-number stream --
+ * so a ticket's result is a function of its row and parameters only, never of its slot, the step it was claimed at, its neighbours or
+ * the n of fc_laura_slots_step.  The phase is four launches that read everything from device memory (laura_kernels.hip: a one-wave
+ * kernel that retires and claims, two copy kernels, the one-row sampler over the claim table); none waits on anything.
+ *   queue       1 .. 65536 result entries: the tickets that may be waiting, running or uncollected at one time
+ *   with_score  as fc_laura_slots_create_scored.  There are no per-step log-probability rows and no forced tokens per ticket.
+ * slots 1 .. 64; above 16 the session is a wide one.  fc_laura_slots_start, _start_many, _start_from, _start_from_session, _fork, _take
+ * and _score are refused on a queued session, naming the call, and change nothing.  `source` must outlive the session, is driven on
+ * the same stream, and a row of it may be overwritten once every ticket that names it has been claimed. */
+size_t fc_laura_slots_state_bytes_queued(const fc_laura* e, int slots, int max_positions, int with_score, int queue);
+int fc_laura_slots_create_queued(fc_laura* e, int slots, int max_positions, int with_score, int queue, const fc_laura_slots* source,
+                                 void* state, size_t state_bytes, fc_laura_slots** out);
+/* A ticket into the queue: one small stream-ordered launch, no synchronisation.  *ticket_out = 0, 1, 2, ... in submit order, which is the
+ * order of claiming.  The rules are the five of fc_laura_slots_set_rules (1, 0, 0, 0, 1: neutral).  Everything
+ * fc_laura_slots_start_from_session checks is checked here, on the host: the row holds a prompt, its prefix + max_length fits THIS
+ * session's max_positions, the sampling arguments, the rules and that they go with the mode.  Refused as well while `queue` tickets are
+ * waiting, running or uncollected.  A refused submit names the ticket and the row, takes no ticket number and changes nothing. */
+int fc_laura_slots_submit(fc_laura_slots* s, int row, int max_length, int sampling_mode, int sampling_k, float sampling_p, uint64_t seed,
+                          float temperature, int min_length, float top_p, int repeat_window, int repeat_count, int32_t* ticket_out,
+                          void* stream);
+/* The queue as the last fc_laura_slots_step read it back (the same single read-back as the slots' states; no device access here):
+ * tickets submitted (host count), claimed, finished, failed and collected so far -- all monotone -- and slot_tickets host i32 [slots],
+ * the ticket each slot runs or -1.  Any pointer may be NULL.  fc_laura_slots_step on a queued session reports a slot as running or free;
+ * it also retires what its last step ended before it reads back, so a finished ticket never waits for another call. */
+int fc_laura_slots_queue_status(const fc_laura_slots* s, int64_t* submitted, int64_t* claimed, int64_t* finished, int64_t* failed,
+                                int64_t* collected, int32_t* slot_tickets);
+/* Up to `cap` results out of the ring, with ONE synchronisation for all of them, and their entries free: failed tickets first, then the
+ * finished ones in the order they finished.
+ *   tickets / states / lens / n_gens / ends   host i32 [cap]: the ticket; 2 finished, 3 failed; token rows (prompt + generated);
+ *                                             generated tokens; 1 ended by length, 2 on <eos> (the score row then has n_gen + 1 terms)
+ *   tokens      dev i64 [cap][max_positions][predict_nq]: row j's first lens[j] rows are written
+ *   scores      HOST f32 [cap][max_positions] or NULL: the whole score rows (a session created with_score)
+ * A ticket fails when a hand-off of the persistent step timed out in a call it ran in: it has no tokens (lens 0), the session goes on
+ * over the kernel chain and the waiting tickets are claimed as before. */
+int fc_laura_slots_collect(fc_laura_slots* s, int cap, int32_t* tickets, int32_t* states, int32_t* lens, int32_t* n_gens, int32_t* ends,
+                           int64_t* tokens, float* scores, int32_t* n_out);
 
 #ifdef __cplusplus
 }

@@ -192,6 +192,10 @@ SYMBOLS = {
     "fc_laura_slots_queue_status": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                               C.POINTER(C.c_int64), _P]),
     "fc_laura_slots_collect": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
+    # an elastic session: a step as wide as the slots in use; slots moved to other rows in one launch
+    "fc_laura_slots_set_elastic": (C.c_int, [_P, C.c_int]),
+    "fc_laura_slots_step_blocks": (C.c_int, [_P]),
+    "fc_laura_slots_move": (C.c_int, [_P, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -250,7 +250,7 @@ class Text2Audio:
     def generate_many(self, texts: Sequence[str], prompt_texts: Optional[Sequence[str]] = None,
                       prompt_audios: Optional[Sequence[np.ndarray]] = None, slots: int = 16, seeds: Optional[Sequence[int]] = None,
                       step_n: Optional[int] = None, samples: int = 1, retries: int = 0, keep: str = "all", rules=None, prefill: int = 0,
-                      length_aware: bool = False, queue: bool = False):
+                      length_aware: bool = False, queue: bool = False, elastic: bool = False):
         """Any number of prompts through a decoding session of `slots` slots kept full in arrival order (laura.drive_slots): a prompt
         starts as soon as a slot ends, nobody waits for the longest utterance of a batch.  Returns what generate_batch returns, in
         request order; per request the tokens are what a session of `slots` slots gives that prompt alone with its seed.  slots = 17 ..
@@ -300,7 +300,14 @@ class Text2Audio:
         idle.  The host fills held rows in arrival order, submits `samples` tickets per row, refills rows whose tickets are all claimed
         (laura.queue_rows, laura.drive_queue) and collects results as they finish.  A ticket's slot is the slot
         start_from(source=held) gives, bit for bit, so the results are token for token those of queue = False (the default: the call
-        as it is) with the same seeds, whatever samples, keep, rules, length_aware and slots."""
+        as it is) with the same seeds, whatever samples, keep, rules, length_aware and slots.
+
+        elastic = True opens the main session elastic (open_decode(elastic=True)): a decoding step runs the column blocks of 16 rows
+        up to the highest running row, and running rows are moved down when that saves a block, so a session opened for the peak
+        costs what its load needs.  Tokens and waveforms are those of elastic = False (the default: the call as it is) with the same
+        seeds, whatever samples, retries, keep, rules, prefill and length_aware; up to 16 slots there is one block and nothing to
+        save.  Refused with queue = True: a queued session claims its slots on the device and the host cannot know the busy rows.
+        ``self.last_elastic`` = {"moves", "blocks"} of the last such call: rows moved, and {blocks: steps run at that width}."""
         from ..laura import HeldPrompts, drive_best, drive_queue, drive_retries, drive_samples, pick_best, retry_seed, tail_groups
         m, nq = self.model, self.model.predict_nq
         n, N, R = len(texts), int(samples), int(retries)
@@ -318,6 +325,9 @@ class Text2Audio:
             raise ValueError("generate_many: queue=True needs prefill >= 1: tickets name rows of the holding session")
         if queue and R > 0:
             raise ValueError(f"generate_many: queue=True goes with retries = 0, got {retries}: a rewind is decided by the host")
+        if queue and elastic:
+            raise ValueError("generate_many: elastic=True is refused with queue=True: a queued session claims its slots on the device, "
+                             "the host cannot know the busy rows")
         step_n = (16 if queue else 1) if step_n is None else int(step_n)
         if length_aware:
             self._refuse_length_aware("generate_many")
@@ -339,6 +349,8 @@ class Text2Audio:
         outs, lens = [None] * n, [0] * n
         # more than 16 slots: a wide session (open_decode(wide=True), up to 64); up to 16 the call is the one it always was
         more = dict(wide=True) if int(slots) > 16 else {}
+        if elastic:
+            more.update(elastic=True)
         held, plan, session = None, None, None
         if queue:                   # the holding session first: the queued session is opened on it, with room for every ticket in flight
             held = m.open_decode(P, logp=False)
@@ -416,6 +428,8 @@ class Text2Audio:
                 taken = [t for row in rows for t in row]
         finally:
             self.last_prefix_passes = {"main": session.prefix_passes, "held": held.prefix_passes if held is not None else 0}
+            if elastic:
+                self.last_elastic = {"moves": session.moves, "blocks": dict(session.blocks_hist)}
             session.free()
             if held is not None:
                 held.free()

@@ -514,9 +514,9 @@ int do_codec_emb(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* te
 
 hipError_t step_gemv(const Lin& L, const float* x, int B, const float* gamma, const float* beta, float eps, int act, int mode, float* y,
                      int ldy, hipStream_t st, float* kc = nullptr, float* vc = nullptr, const int* pos = nullptr, int d = 0, int Tcap = 0,
-                     const float* apart = nullptr, int H = 0, int DK = 0, int NS = 0, int stage = 0) {
+                     const float* apart = nullptr, int H = 0, int DK = 0, int NS = 0, int stage = 0, int wide = 0) {
     lk::Gemv g;
-    g.stage = stage;
+    g.stage = stage; g.wide = wide;
     g.apart = apart; g.H = H; g.DK = DK; g.NS = NS;
     g.x = x; g.wf = L.wf; g.bias = L.bias; g.gamma = gamma; g.beta = beta; g.eps = eps; g.act = act; g.mode = mode; g.y = y; g.ldy = ldy;
     g.kc = kc; g.vc = vc; g.pos = pos; g.d = d; g.Tcap = Tcap; g.B = B; g.K = L.cin; g.N = L.cout;
@@ -618,10 +618,17 @@ lk::StepPersistArgs step_persist_args(const fc_laura* e, const StepMem& m, unsig
 // One decoding step: the newest token of every row through the LM against its KV cache, then the sampler.  Every kernel reads its
 // positions from device memory, so the launch sequence is identical from step to step.  pa null: the kernel chain.
 // q (a queued session): the refill phase first -- ended slots retire, free slots claim waiting tickets and draw their first sample.
-void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st,
-              const lk::QueuePhase* q = nullptr) {
+// rows > 0 (an elastic session of more than 16 slots, the kernel chain): the step over rows [0, rows) only, rows a multiple of 16 below
+// m.B.  Every launch is the full step's with its row count cut -- the GEMV's grid.y, the attention's grid.y, the sampler's blocks -- and
+// nothing else: the pointers, the layer strides (m.B rows per layer), NS, and the GEMV instantiations over column blocks (Gemv::wide).
+// Every step kernel indexes per-row memory from row 0 and no row reads another's, so rows [0, rows) get the full step's bits.
+void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm0, hipStream_t st,
+              const lk::QueuePhase* q = nullptr, int rows = 0) {
     const Stack& S = e->codec_lm;
-    const int B = m.B, d = S.s.d_model, ff = S.s.ff, NL = S.s.layers, V = e->vocab(), Tcap = m.Tcap, heads = S.s.heads, dkh = d / S.s.heads;
+    const int SB = m.B, B = rows > 0 ? rows : m.B, wide = rows > 0 ? 1 : 0;
+    lk::Sample sm = sm0;
+    if (rows > 0) { sm.row0 = 0; sm.nrows = rows; }
+    const int d = S.s.d_model, ff = S.s.ff, NL = S.s.layers, V = e->vocab(), Tcap = m.Tcap, heads = S.s.heads, dkh = d / S.s.heads;
     if (q) {
         cx.check(lk::launch_queue_phase(*q, 1, st), "queue phase");
         lk::Sample first = sm;
@@ -635,19 +642,22 @@ void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs*
     }
     for (int i = 0; i < NL; ++i) {
         const Block& b = S.blocks[i];
-        float* kc = m.kc + (size_t)i * B * d * Tcap;
-        float* vc = m.vc + (size_t)i * B * d * Tcap;
-        cx.check(step_gemv(b.qkv, m.xs, B, b.n1g, b.n1b, 1e-12f, 0, 2, m.qb, d, st, kc, vc, m.pos, d, Tcap), "QKV GEMV");
+        float* kc = m.kc + (size_t)i * SB * d * Tcap;
+        float* vc = m.vc + (size_t)i * SB * d * Tcap;
+        cx.check(step_gemv(b.qkv, m.xs, B, b.n1g, b.n1b, 1e-12f, 0, 2, m.qb, d, st, kc, vc, m.pos, d, Tcap, nullptr, 0, 0, 0, 0, wide), "QKV GEMV");
         lk::AttnStep a;
         a.q = m.qb; a.kc = kc; a.vc = vc; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.pos = m.pos; a.part = m.apart; a.NS = m.NS;
         a.B = B; a.H = heads; a.DK = dkh; a.Tcap = Tcap; a.R = e->R; a.PR = e->PR;
         cx.check(lk::launch_attn_step(a, st), "step attention");
         // linear_out reads the key-range partials and combines them while staging its input
-        cx.check(step_gemv(b.out, nullptr, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, m.apart, heads, dkh, m.NS), "out GEMV");
-        cx.check(step_gemv(b.ff1, m.xs, B, b.n2g, b.n2b, 1e-12f, S.s.act, 0, m.hb, ff, st), "FFN GEMV 1");
-        cx.check(step_gemv(b.ff2, m.hb, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st), "FFN GEMV 2");
+        cx.check(step_gemv(b.out, nullptr, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, m.apart, heads, dkh, m.NS, 0, wide), "out GEMV");
+        cx.check(step_gemv(b.ff1, m.xs, B, b.n2g, b.n2b, 1e-12f, S.s.act, 0, m.hb, ff, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
+                 "FFN GEMV 1");
+        cx.check(step_gemv(b.ff2, m.hb, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
+                 "FFN GEMV 2");
     }
-    cx.check(step_gemv(e->lm_decoder, m.xs, B, S.ag, S.ab, 1e-12f, 0, 0, m.lg, V, st), "decoder GEMV");
+    cx.check(step_gemv(e->lm_decoder, m.xs, B, S.ag, S.ab, 1e-12f, 0, 0, m.lg, V, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
+             "decoder GEMV");
     cx.check(lk::launch_sample(sm, st), "sampling");
 }
 
@@ -659,11 +669,11 @@ bool graph_enabled() {
 // one step captured on st as an executable graph (62 small launches on the chain: the loop is launch-bound otherwise); null if the
 // stream cannot be captured.  A launch that fails while capturing sets cx.err.
 hipGraphExec_t capture_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs* pa, const lk::Sample& sm, hipStream_t st,
-                            const lk::QueuePhase* q = nullptr) {
+                            const lk::QueuePhase* q = nullptr, int rows = 0) {
     hipGraphExec_t gexec = nullptr;
     hipGraph_t graph = nullptr;
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    run_step(e, cx, m, pa, sm, st, q);
+    run_step(e, cx, m, pa, sm, st, q, rows);
     const hipError_t ec = hipStreamEndCapture(st, &graph);
     if (ec != hipSuccess || cx.err || hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) gexec = nullptr;
     if (graph) (void)hipGraphDestroy(graph);
@@ -788,6 +798,12 @@ struct fc_laura_slots {
     std::vector<int> forced_on;             // the slot's utterance follows forced tokens (rows [0, max_len) of its forced row)
     std::vector<lk::SampleRow> rules;       // per slot, the rule fields only (fc_laura_slots_set_rules): into the slot's row at every start / fork
     hipGraphExec_t gexec = nullptr;         // the captured step, and the form it holds
+    // an elastic session (fc_laura_slots_set_elastic): a call steps the column blocks up to the highest running slot.  Beyond 16 slots one
+    // more captured step per cut width, [nb - 1] = the first nb blocks, captured on first use; the full width is gexec, as ever
+    bool elastic = false;
+    hipGraphExec_t gexec_cut[3] = {nullptr, nullptr, nullptr};
+    int last_blocks = 0;                    // column blocks the last step call launched (0: it launched nothing)
+    int* move_table = nullptr;              // device [lk::FC_SLOT_MOVES_WORDS]: the lines of the last fc_laura_slots_move
     bool g_persist = false, g_timeout = false;
     bool warmed[2] = {false, false};        // one eager step run per form (sets the kernels' LDS attributes, which a capture cannot)
     bool chain_only = false;                // after a hand-off timeout
@@ -826,6 +842,7 @@ void slots_layout(fc_laura* e, Ctx& cx, int S, int R, bool with_logp, bool with_
         q.ring_tokens = cx.alloc<int64_t>((size_t)Q * R * nq);
         q.ring_score = with_score ? cx.alloc<float>((size_t)Q * R) : nullptr;
     }
+    s.move_table = cx.alloc<int>(lk::FC_SLOT_MOVES_WORDS);                 // behind everything else (fc_laura_slots_move)
 }
 
 lk::Sample slots_sampler(const fc_laura_slots* s) {
@@ -1437,6 +1454,8 @@ int fc_laura_slots_create_queued(fc_laura* e, int slots, int max_positions, int 
 void fc_laura_slots_destroy(fc_laura_slots* s) {
     if (!s) return;
     if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
+    for (hipGraphExec_t g : s->gexec_cut)
+        if (g) (void)hipGraphExecDestroy(g);
     if (s->status) (void)hipHostFree(s->status);
     delete s;
 }
@@ -1706,6 +1725,72 @@ int fc_laura_slots_set_rules(fc_laura_slots* s, int slot, float temperature, int
     return 0;
 }
 
+int fc_laura_slots_set_elastic(fc_laura_slots* s, int on) {
+    if (!s) return fail("null session");
+    if (s->Q) return fail("decoding session: set_elastic: a queued session claims its slots on the device, the host cannot know the busy rows");
+    s->elastic = on != 0;
+    return 0;
+}
+
+int fc_laura_slots_step_blocks(const fc_laura_slots* s) { return s ? s->last_blocks : 0; }
+
+int fc_laura_slots_move(fc_laura_slots* s, int n, const int32_t* src, const int32_t* dst, void* stream) {
+    if (!s) return fail("null session");
+    if (refuse_queued(s, "move")) return 1;
+    if (check_ready(s->e)) return 1;
+    const int S = s->S;
+    if (n < 1 || n > S) return fail("decoding session: move: 1 .. " + std::to_string(S) + " moves per call, got " + std::to_string(n));
+    if (!src || !dst) return fail("null argument");
+    // every rule for every line before the first launch: a refused call changes nothing for any slot
+    lk::SlotMoveLines lines;
+    lines.n = n;
+    unsigned long long srcs = 0, dsts = 0;
+    for (int i = 0; i < n; ++i) {
+        const int a = src[i], b = dst[i];
+        const std::string range = " outside 0 .. " + std::to_string(S - 1);
+        if (a < 0 || a >= S) return fail("decoding session: move: source slot " + std::to_string(a) + range);
+        if (b < 0 || b >= S) return fail("decoding session: move: slot " + std::to_string(b) + range);
+        if ((srcs | dsts) >> a & 1ull)
+            return fail("decoding session: move: source slot " + std::to_string(a) + (srcs >> a & 1ull ? " is named twice" : " is also a destination"));
+        if (((srcs | dsts) >> b & 1ull) || a == b)
+            return fail("decoding session: move: slot " + std::to_string(b) + (dsts >> b & 1ull ? " is named twice" : " is also a source"));
+        if (s->state[a] != SLOT_RUNNING && s->state[a] != SLOT_DONE)
+            return fail("decoding session: move: source slot " + std::to_string(a) + " holds no utterance (" +
+                        (s->state[a] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+        srcs |= 1ull << a; dsts |= 1ull << b;
+        lines.src[i] = a; lines.dst[i] = b;
+    }
+    for (int i = 0; i < n; ++i)
+        if (s->state[dst[i]] != SLOT_FREE)
+            return fail("decoding session: move: slot " + std::to_string(dst[i]) + " is not free (" +
+                        (s->state[dst[i]] == SLOT_RUNNING ? "running" : s->state[dst[i]] == SLOT_DONE ? "ended, not taken" : "failed") + ")");
+    fc_laura* e = s->e;
+    const StepMem& m = s->m;
+    lk::SlotMoves mv;
+    mv.table = s->move_table; mv.kc = m.kc; mv.vc = m.vc; mv.n_gen = m.n_gen(); mv.done = m.done(); mv.step = m.step(); mv.pos = m.pos;
+    mv.tok_off = s->tok_off; mv.rows = s->rows; mv.tokens = s->tokens; mv.forced = s->forced; mv.logp = s->logp; mv.score = s->score;
+    mv.lg = m.lg; mv.lg0 = s->lg0; mv.xs = m.xs; mv.nemb = m.nemb;
+    mv.NL = e->codec_lm.s.layers; mv.S = S; mv.d = e->codec_lm.s.d_model; mv.Tcap = m.Tcap; mv.V = e->vocab(); mv.R = s->R;
+    mv.nq = e->arch.predict_nq; mv.D = e->arch.codebook_dim;
+    Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
+    s->last = cx.st;
+    // from here on a failure leaves the named slots failed, as a start that fails half-way
+    cx.check(lk::launch_slot_moves(mv, lines, cx.st), "slot move");
+    if (cx.err) {
+        for (int i = 0; i < n; ++i) s->state[src[i]] = SLOT_FAILED;
+        return 1;
+    }
+    // the host mirror of every moved slot; the rules of the two rows change places
+    for (int i = 0; i < n; ++i) {
+        const int a = src[i], b = dst[i];
+        s->state[b] = s->state[a]; s->cont_len[b] = s->cont_len[a]; s->max_len[b] = s->max_len[a]; s->n_gen[b] = s->n_gen[a];
+        s->text_len[b] = s->text_len[a]; s->prefix[b] = s->prefix[a]; s->forced_on[b] = s->forced_on[a];
+        std::swap(s->rules[a], s->rules[b]);
+        s->state[a] = SLOT_FREE; s->n_gen[a] = 0;
+    }
+    return 0;
+}
+
 int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32_t* n_gen_out, void* stream) {
     if (!s) return fail("null session");
     if (check_ready(s->e)) return 1;
@@ -1713,7 +1798,21 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
     bool any = false;
     for (int i = 0; i < s->S; ++i) any = any || s->state[i] == SLOT_RUNNING;
     if (s->Q) any = s->submitted > s->finished + s->failed;             // a ticket waits or runs
+    s->last_blocks = 0;
     if (!any) { slots_report(s, done_out, n_gen_out); return 0; }
+    // an elastic session: the width of this call, from the host mirror of the slot states.  No slot can start inside the call, so the
+    // width holds for all n_steps.  cut > 0: the first `cut` rows only (whole column blocks, fewer than S; the kernel chain -- S > 16)
+    int cut = 0;
+    s->last_blocks = (s->S + 15) / 16;
+    if (s->elastic && s->S > 16) {
+        int hi = 0;
+        for (int i = 0; i < s->S; ++i)
+            if (s->state[i] == SLOT_RUNNING) hi = i;
+        const int rows = std::min(s->S, 16 * (hi / 16 + 1));
+        s->last_blocks = (rows + 15) / 16;
+        if (rows < s->S) cut = rows;
+    }
+    hipGraphExec_t& gx = cut ? s->gexec_cut[cut / 16 - 1] : s->gexec;
     const lk::QueuePhase* qp = s->Q ? &s->qp : nullptr;
     fc_laura* e = s->e;
     const StepMem& m = s->m;
@@ -1732,17 +1831,17 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
     }
     for (int i = 0; i < n_steps && !cx.err; ++i) {
         if (!s->warmed[persist]) {                          // the form's first step runs eagerly
-            run_step(e, cx, m, pap, sm, cx.st, qp);
+            run_step(e, cx, m, pap, sm, cx.st, qp, cut);
             s->warmed[persist] = true;
             continue;
         }
-        if (!s->gexec && graph_enabled() && cx.st != nullptr) {
-            s->gexec = capture_step(e, cx, m, pap, sm, cx.st, qp);
-            s->g_persist = persist; s->g_timeout = pa.test_timeout != 0;
+        if (!gx && graph_enabled() && cx.st != nullptr) {
+            gx = capture_step(e, cx, m, pap, sm, cx.st, qp, cut);
+            if (!cut) { s->g_persist = persist; s->g_timeout = pa.test_timeout != 0; }
             if (cx.err) break;
         }
-        if (s->gexec) cx.check(hipGraphLaunch(s->gexec, cx.st), "graph launch");
-        else run_step(e, cx, m, pap, sm, cx.st, qp);
+        if (gx) cx.check(hipGraphLaunch(gx, cx.st), "graph launch");
+        else run_step(e, cx, m, pap, sm, cx.st, qp, cut);
     }
     if (persist) s->persist_steps += (unsigned long long)n_steps;
     // a queued session retires what the last step ended before the read-back, so a finished ticket never waits for another call

@@ -99,6 +99,9 @@ struct Gemv {
     // how x is staged in LDS: 0 = one stage when (16 + 1) x (K + 4) floats fit, else windows of <= 1024 columns (x as given, modes 0 / 1);
     // test hooks: 1 = one stage whatever the batch allows, 2 = at least two windows
     int stage = 0;
+    // the instantiations over column blocks (gemv_column_block) also when B <= 16 leaves grid.y = 1: a launch cut to the first blocks of a
+    // wider step (fc_laura_slots_set_elastic) runs the kernels of the full launch, whatever the cut
+    int wide = 0;
 };
 // 1 <= B <= 64.  The stage form, the waves per workgroup and the window count follow from K alone, as for 16 rows: a row's accumulation
 // order does not depend on B or on the row's column block.
@@ -236,6 +239,23 @@ struct SlotBranch {                 // see slot_branch_kernel
     float* xs = nullptr;
 };
 hipError_t launch_slot_branch(const SlotBranch& r, hipStream_t st);
+
+struct SlotMoves {                  // see slot_move_kernel: slots of a decoding session moved to other rows, all in one launch
+    int* table = nullptr;           // device [1 + 2 * 64] ints: the line count n, then n lines (src, dst); written by launch_slot_moves_put
+    float *kc = nullptr, *vc = nullptr;   // the session's caches [NL][S][d][Tcap], [NL][S][Tcap][d]
+    int *n_gen = nullptr, *done = nullptr, *step = nullptr, *pos = nullptr, *tok_off = nullptr;
+    SampleRow* rows = nullptr;
+    int64_t *tokens = nullptr, *forced = nullptr;       // [S][R][nq]
+    float* logp = nullptr;          // [S][R][V] or null
+    float* score = nullptr;         // [S][R] or null
+    float *lg = nullptr, *lg0 = nullptr;                // [S][V]
+    float *xs = nullptr, *nemb = nullptr;               // [S][d], [S][D]
+    int NL = 0, S = 0, d = 0, Tcap = 0, V = 0, R = 0, nq = 0, D = 0;
+};
+enum { FC_SLOT_MOVES_MAX = 64, FC_SLOT_MOVES_WORDS = 1 + 2 * FC_SLOT_MOVES_MAX };
+struct SlotMoveLines { int n = 0; int src[FC_SLOT_MOVES_MAX] = {}, dst[FC_SLOT_MOVES_MAX] = {}; };
+// the lines into the device table (one small launch, the lines by value in the kernel arguments, like a queue ticket), then the copy
+hipError_t launch_slot_moves(const SlotMoves& m, const SlotMoveLines& lines, hipStream_t st);
 
 hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t st);
 

@@ -888,7 +888,7 @@ hipError_t launch_gemv_windowed(const Gemv& g, GemvArgs a, int KS, dim3 grid, hi
     a.W = g.K / nw; a.NW = nw; a.XS = a.W + 4;
     const size_t lds = gemv_lds_bytes(rows, a.XS, KS);
     static std::atomic<unsigned long long> d_spec[2], d_gen[5][2];       // per kernel: [0] the 16-column form, [1] over column blocks
-    const bool wide = grid.y > 1;
+    const bool wide = grid.y > 1 || g.wide;
     hipError_t e;
 #define FC_GEMV_WIN_LAUNCH(ks, cpwc, nwc, flag)                                                              \
     do {                                                                                                     \
@@ -935,7 +935,7 @@ hipError_t launch_gemv(const Gemv& g, hipStream_t st) {
     const size_t lds = gemv_lds_bytes(rows, a.XS, KS);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> d16[6][2], d8[6][2], d4[6][2], d2[6][2], d1[6][2];     // [.][1]: over column blocks
-    const bool wide = grid.y > 1;
+    const bool wide = grid.y > 1 || g.wide;
     hipError_t e;
 #define FC_GEMV_LAUNCH(ks, cpwc, flag)                                                                  \
     do {                                                                                                \
@@ -2133,6 +2133,126 @@ hipError_t launch_sample_claims(const Sample& s, const QueuePhase& q, hipStream_
                  s.emb_wt, s.emb_bias, s.emb_g, s.emb_b, s.dm, s.emb_relu, s.xscale, s.xs, s.launch_seq,
                  s.rows, s.row_stride, 0, q.claims, q.qw + FC_QUEUE_NCLAIM};
     hipLaunchKernelGGL(sample_kernel<true>, dim3(q.S), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Slots of a decoding session moved to other rows (fc_laura_slots_move): after the launch row dst of every table line IS row src, and
+// row src is a free row (done = 1, as a taken one).  Nothing is computed: every word the session keeps per slot is copied.
+//   grid.y = layer l < NL: key / value positions [0, pos[src]] of the layer -- K rows of pad4(pos + 1) floats, the first (pos + 1) * d
+//                          floats of V -- in prefix_copy_kernel's chunks of FC_PREFIX_VPT x 256 16-byte vectors, the loads of a chunk
+//                          in flight together, clamped loads and predicated stores;
+//   grid.y = NL:           the token, forced-token (a slot that follows them), score and log-probability rows (the latter as far as the
+//                          slot's max_steps, what slot_reset_kernel zeroed and a take reads), the step's and the kept prefix logits, the
+//                          pending LM input row and next-embedding row; block 0's thread 0 the counters, the position, the prompt length
+//                          and the row of the sampling table, and done[src] = 1.
+// The grid is fixed and strides over (table line x chunk), like the queue phase's copy kernels.  The sources and the destinations are
+// disjoint sets (checked by the host before the table is written), so no block reads a word another block of the launch writes:
+// pos[src] and rows[src] are only read, done[src] is read and written by the one thread.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void slot_moves_put_kernel(int* table, SlotMoveLines l) {
+    const int i = threadIdx.x;
+    if (i == 0) table[0] = l.n;
+    if (i < l.n && i < FC_SLOT_MOVES_MAX) { table[1 + 2 * i] = l.src[i]; table[2 + 2 * i] = l.dst[i]; }
+}
+
+__global__ __launch_bounds__(256) void slot_move_kernel(SlotMoves m) {
+    int n = m.table[0];
+    n = n < FC_SLOT_MOVES_MAX ? n : FC_SLOT_MOVES_MAX;
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.y == m.NL) {
+        const size_t t0 = (size_t)blockIdx.x * 256 + tid, nth = (size_t)gridDim.x * 256;
+        const size_t tok_row = (size_t)m.R * m.nq;                        // int64 per row: even (R % 4 == 0)
+        for (int c = 0; c < n; ++c) {
+            const int src = m.table[1 + 2 * c], dst = m.table[2 + 2 * c];
+            const SampleRow* sr = m.rows + src;
+            const int max_steps = sr->max_steps < m.R ? sr->max_steps : m.R, forced_on = sr->forced_on;
+            const i64x2* ts = (const i64x2*)(m.tokens + (size_t)src * tok_row);
+            i64x2* td = (i64x2*)(m.tokens + (size_t)dst * tok_row);
+            for (size_t i = t0; i < (tok_row >> 1); i += nth) td[i] = ts[i];
+            if (forced_on) {
+                const i64x2* fs = (const i64x2*)(m.forced + (size_t)src * tok_row);
+                i64x2* fd = (i64x2*)(m.forced + (size_t)dst * tok_row);
+                for (size_t i = t0; i < (tok_row >> 1); i += nth) fd[i] = fs[i];
+            }
+            if (m.score) {
+                const f32x4* ss = (const f32x4*)(m.score + (size_t)src * m.R);
+                f32x4* sd = (f32x4*)(m.score + (size_t)dst * m.R);
+                for (size_t i = t0; i < (size_t)(m.R >> 2); i += nth) sd[i] = ss[i];
+            }
+            if (m.logp) {                                                 // a row starts at slot * R * V floats: 16-byte aligned (R % 4 == 0)
+                const size_t nl = (size_t)(max_steps > 0 ? max_steps : 0) * m.V;
+                const float* ls = m.logp + (size_t)src * m.R * m.V;
+                float* ld = m.logp + (size_t)dst * m.R * m.V;
+                for (size_t i = t0; i < (nl >> 2); i += nth) ((f32x4*)ld)[i] = ((const f32x4*)ls)[i];
+                for (size_t i = (nl & ~(size_t)3) + t0; i < nl; i += nth) ld[i] = ls[i];
+            }
+            for (size_t v = t0; v < (size_t)m.V; v += nth) {              // V need not be a multiple of 4: scalar, 2 x V floats
+                m.lg[(size_t)dst * m.V + v] = m.lg[(size_t)src * m.V + v];
+                m.lg0[(size_t)dst * m.V + v] = m.lg0[(size_t)src * m.V + v];
+            }
+            for (size_t i = t0; i < (size_t)(m.d >> 2); i += nth)
+                ((f32x4*)(m.xs + (size_t)dst * m.d))[i] = ((const f32x4*)(m.xs + (size_t)src * m.d))[i];
+            for (size_t i = t0; i < (size_t)m.D; i += nth) m.nemb[(size_t)dst * m.D + i] = m.nemb[(size_t)src * m.D + i];
+            if (t0 == 0) {
+                m.n_gen[dst] = m.n_gen[src]; m.done[dst] = m.done[src]; m.step[dst] = m.step[src]; m.pos[dst] = m.pos[src];
+                m.tok_off[dst] = m.tok_off[src];
+                m.rows[dst] = *sr;
+                m.done[src] = 1;
+            }
+        }
+        return;
+    }
+    const int l = blockIdx.y;
+    const size_t row = (size_t)m.d * m.Tcap;                             // floats of one slot's row of a layer, K and V alike
+    for (int c = 0; c < n; ++c) {
+        const int src = m.table[1 + 2 * c], dst = m.table[2 + 2 * c];
+        int P = m.pos[src] + 1;                                           // positions [0, pos]
+        P = P < 1 ? 1 : (P > m.Tcap ? m.Tcap : P);
+        const int kq = (P + 3) >> 2;                                      // pad4(P) <= Tcap (Tcap % 4 == 0)
+        const int nK = m.d * kq, nV = (P * m.d) >> 2;
+        const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
+        for (int chunk = blockIdx.x; chunk < bK + bV; chunk += gridDim.x) {
+            const bool isK = chunk < bK;
+            const int blk = isK ? chunk : chunk - bK;
+            float* base = (isK ? m.kc : m.vc) + (size_t)l * m.S * row;
+            const float* sb = base + (size_t)src * row;
+            float* db = base + (size_t)dst * row;
+            const int nvec = isK ? nK : nV;
+            const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
+            size_t off[FC_PREFIX_VPT];
+            f32x4 v[FC_PREFIX_VPT];
+#pragma unroll
+            for (int u = 0; u < FC_PREFIX_VPT; ++u) {
+                int i = i0 + 256 * u;
+                i = i < nvec ? i : nvec - 1;                              // clamped: unconditional loads, predicated stores
+                off[u] = isK ? (size_t)(i / kq) * m.Tcap + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+                v[u] = *(const f32x4*)(sb + off[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < FC_PREFIX_VPT; ++u)
+                if (i0 + 256 * u < nvec) *(f32x4*)(db + off[u]) = v[u];
+        }
+    }
+}
+
+hipError_t launch_slot_moves(const SlotMoves& m, const SlotMoveLines& lines, hipStream_t st) {
+    if (!m.table || !m.kc || !m.vc || !m.n_gen || !m.done || !m.step || !m.pos || !m.tok_off || !m.rows || !m.tokens || !m.forced || !m.lg ||
+        !m.lg0 || !m.xs || !m.nemb)
+        return hipErrorInvalidValue;
+    if (m.NL < 1 || m.S < 2 || m.S > 64 || m.d < 4 || m.d % 4 || m.Tcap < 4 || m.Tcap % 4 || m.R != m.Tcap || m.V < 1 || m.nq < 1 || m.D < 1)
+        return hipErrorInvalidValue;
+    if ((long long)m.d * m.Tcap > 0x7fffffff) return hipErrorInvalidValue;       // a row's vectors are counted in int
+    if (lines.n < 1 || lines.n > FC_SLOT_MOVES_MAX || lines.n > m.S) return hipErrorInvalidValue;
+    unsigned long long srcs = 0, dsts = 0;                                        // distinct rows, disjoint sides
+    for (int i = 0; i < lines.n; ++i) {
+        const int a = lines.src[i], b = lines.dst[i];
+        if (a < 0 || a >= m.S || b < 0 || b >= m.S) return hipErrorInvalidValue;
+        if (((srcs | dsts) >> a & 1ull) || ((srcs | dsts) >> b & 1ull) || a == b) return hipErrorInvalidValue;
+        srcs |= 1ull << a; dsts |= 1ull << b;
+    }
+    hipLaunchKernelGGL(slot_moves_put_kernel, dim3(1), dim3(64), 0, st, m.table, lines);
+    hipLaunchKernelGGL(slot_move_kernel, dim3(64, m.NL + 1), dim3(256), 0, st, m);
     return hipGetLastError();
 }
 

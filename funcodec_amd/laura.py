@@ -314,7 +314,8 @@ class LauraEngine:
         return (tokens, lens, logp) if return_logp else (tokens, lens)
 
     def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
-                    wide: bool = False, queue: Optional[int] = None, source: Optional["DecodeSlots"] = None) -> "DecodeSlots":
+                    wide: bool = False, queue: Optional[int] = None, source: Optional["DecodeSlots"] = None,
+                    elastic: bool = False) -> "DecodeSlots":
         """A decoding session of `slots` slots (1 .. 16, or 1 .. 64 with wide=True): prompts join and leave a running batch.  max_positions (default: the engine's)
         bounds text_len + 2 + prompt tokens + max_length of a slot and sizes the session's state; logp=False leaves out the per-step
         log-probabilities [slots, max_positions, vocab], the largest part of it.  score=True keeps one number per slot and step, the
@@ -325,7 +326,18 @@ class LauraEngine:
         queue=Q with source=a holding session of this engine opens a QUEUED session (``DecodeSlots.submit`` / ``claimed`` /
         ``collect``): tickets name a held row and wait on the device; inside every captured step ended slots retire into a result
         ring of Q entries and free slots claim the oldest tickets, so ``step(n)`` is n steps with the slots full and one read-back.
-        It needs logp=False (no log-probability rows per ticket) and composes with score and wide."""
+        It needs logp=False (no log-probability rows per ticket) and composes with score and wide.
+
+        elastic=True opens an ``ElasticSlots``: a step costs the column blocks in use, not the slots opened.  The caller's slot numbers
+        are logical; a slot that starts takes the lowest free row, ``step`` first moves running rows down when that saves a column
+        block (``compact_plan``, ``DecodeSlots.move``) and the library launches the step over the blocks up to the highest running row.
+        Results do not depend on the row, so nothing but the cost changes.  Up to 16 slots there is one block and the flag is inert;
+        refused with queue= (the slots are claimed on the device, the host cannot know the busy rows)."""
+        if elastic:
+            if queue is not None or source is not None:
+                raise EngineError("open_decode: elastic=True is refused with queue=: a queued session claims its slots on the device, "
+                                  "the host cannot know the busy rows")
+            return ElasticSlots(self, slots, max_positions, logp, score, wide)
         if queue is None and source is None:
             return DecodeSlots(self, slots, max_positions, logp, score, wide)
         return DecodeSlots(self, slots, max_positions, logp, score, wide, queue, source)
@@ -596,6 +608,42 @@ class DecodeSlots:
         self._queue_status()
         return out
 
+    #: rows moved so far (``move``; an elastic session's ``step`` moves rows by itself)
+    moves = 0
+
+    def _phys(self, slot: int) -> int:
+        """The row of the session that slot `slot` lies in: the slot itself (an ``ElasticSlots`` keeps a table)."""
+        return int(slot)
+
+    @property
+    def blocks(self) -> int:
+        """Column blocks of 16 rows the last ``step`` launched (0: it had no running slot and launched nothing)."""
+        return int(self.lib.fc_laura_slots_step_blocks(self._handle()))
+
+    @_on_device
+    def move(self, pairs) -> None:
+        """[(src, dst), ...] rows of the session: after the call row dst IS row src -- a running slot goes on as if it had never moved,
+        an ended one is taken from dst -- and src is free.  Everything the session keeps per slot is copied in one launch; nothing is
+        computed again, so the bits of the moved slot do not change.  Stream-ordered, no synchronisation.  Refused, naming the slot
+        and changing nothing: a row outside the session, named twice or on both sides, a source that holds no utterance, a destination
+        that is not free, a queued session."""
+        self._refuse_queued("move")
+        h = self._handle()
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        if not pairs:
+            raise EngineError("decoding session: move: no moves")
+        cur, run = self._run_stream()
+        try:
+            self.engine._check(self.lib.fc_laura_slots_move(h, len(pairs), _i32([a for a, _ in pairs]), _i32([b for _, b in pairs]),
+                                                            C.c_void_p(run.cuda_stream)))
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+        for a, b in pairs:
+            self._max_length[b], self._n_gen[b], self._status[b] = self._max_length[a], self._n_gen[a], self._status[a]
+            self._n_gen[a], self._status[a] = 0, 0
+        self.moves += len(pairs)
+
     def _set_rules(self, slot: int, rules: Optional[SamplingRules]) -> None:
         """`rules` (None: the neutral ones) as the rules the next start / start_from / fork into `slot` writes: per call, like sampling
         and seed.  Nothing on the device changes here."""
@@ -772,6 +820,7 @@ class DecodeSlots:
         if source is not None and not isinstance(source, DecodeSlots):
             raise EngineError(f"decode session start_from: slot {dst}: source must be a DecodeSlots or None, got {type(source).__name__}")
         held = self if source is None else source
+        src = held._phys(src)
         if max_length is None:
             if not 0 <= src < held.slots:
                 raise EngineError(f"decode session start_from: source slot {src} outside 0 .. {held.slots - 1}")
@@ -814,6 +863,7 @@ class DecodeSlots:
         dst, src = int(dst), int(src)
         if not 0 <= src < self.slots:
             raise EngineError(f"decode session fork: source slot {src} outside 0 .. {self.slots - 1}")
+        src = self._phys(src)
         keep = -1 if keep is None else int(keep)
         if keep < -1:
             raise EngineError(f"decode session fork: slot {dst}: keep {keep} < 0")
@@ -920,6 +970,171 @@ class DecodeSlots:
         self.engine._check(self.lib.fc_laura_slots_take(h, slot, _ptr(tokens), cap, C.byref(n), _ptr(logp)))
         tokens = tokens[: n.value].clone()
         out = (tokens, int(n.value), logp) if return_logp else (tokens, int(n.value))
+        return out + (scored,) if return_score else out
+
+
+def compact_plan(busy_rows: Sequence[int], S: int, held: Sequence[int] = ()) -> List[tuple]:
+    """The compaction rule of an elastic session, a plain function of which rows are busy: the fewest moves [(src, dst), ...], highest
+    busy rows into lowest free rows, that bring the busy (running) rows of a session of S rows into the fewest column blocks of 16.
+    Empty when that does not lower the block count.  `held` rows are occupied but not busy (ended, not taken): they are no
+    destination and do not hold the width up, so they stay where they are."""
+    busy = sorted(set(int(r) for r in busy_rows))
+    kept = set(int(r) for r in held) - set(busy)
+    if not busy:
+        return []
+    if busy[0] < 0 or busy[-1] >= S or any(not 0 <= r < S for r in kept):
+        raise ValueError(f"compact_plan: a row outside 0 .. {S - 1}")
+    now = busy[-1] // 16 + 1
+    for nb in range(1, now):                       # the fewest blocks whose rows, less the held ones, take every busy row
+        top = min(S, 16 * nb)
+        if top - sum(1 for r in kept if r < top) >= len(busy):
+            free = [r for r in range(top) if r not in kept and r not in busy]
+            return list(zip([r for r in reversed(busy) if r >= top], free))
+    return []
+
+
+class RowTable:
+    """Logical slot -> physical row of an elastic session: a slot that starts takes the lowest free row and keeps it until it is
+    taken (``release``) or moved (``moved``)."""
+
+    def __init__(self, S: int):
+        self.S = int(S)
+        self.row: Dict[int, int] = {}
+
+    def free_rows(self) -> List[int]:
+        used = set(self.row.values())
+        return [r for r in range(self.S) if r not in used]
+
+    def place(self, slot: int) -> tuple:
+        """(row, new): the row `slot` holds, else the lowest free one, which it holds from now on."""
+        if slot in self.row:
+            return self.row[slot], False
+        self.row[slot] = self.free_rows()[0]          # S logical slots over S rows: one is free
+        return self.row[slot], True
+
+    def release(self, slot: int) -> None:
+        self.row.pop(slot, None)
+
+    def moved(self, pairs) -> None:
+        at = {r: s for s, r in self.row.items()}
+        for src, dst in pairs:
+            if src in at:
+                self.row[at[src]] = dst
+
+    def slot_of(self) -> Dict[int, int]:
+        return {r: s for s, r in self.row.items()}
+
+
+class ElasticSlots(DecodeSlots):
+    """``open_decode(..., elastic=True)``: a DecodeSlots whose step is as wide as the slots in use.  Slot numbers are the caller's own
+    (logical); the session keeps the table slot -> row.  A slot that starts (``start``, ``start_many``, a ``start_from`` / ``fork``
+    destination) takes the lowest free row, ``take`` frees it, and ``step`` first applies ``compact_plan`` to the running rows
+    (``move``) -- ended rows that are not yet taken stay put and do not hold the width up -- then steps the column blocks up to the
+    highest running row (fc_laura_slots_set_elastic).  A slot's bits depend neither on its row nor on its neighbours, and a cut step
+    is the full step on its rows, so every result is the non-elastic session's, bit for bit.  ``blocks``: the blocks of the last step;
+    ``moves``: rows moved so far; ``rows()``: the table; ``blocks_hist``: {blocks: steps run at that width}."""
+
+    elastic = True
+
+    def __init__(self, engine: "LauraEngine", slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
+                 wide: bool = False):
+        self._table = RowTable(max(int(slots), 0))
+        self._running = set()
+        self.blocks_hist: Dict[int, int] = {}
+        super().__init__(engine, slots, max_positions, logp, score, wide)
+        self.engine._check(self.lib.fc_laura_slots_set_elastic(self._h, 1))
+
+    def rows(self) -> Dict[int, int]:
+        """{slot: row} of every slot that holds a row."""
+        return dict(self._table.row)
+
+    def _logical(self, slot: int) -> int:
+        slot = int(slot)
+        if not 0 <= slot < self.slots:
+            raise EngineError(f"decoding session: slot {slot} outside 0 .. {self.slots - 1}")
+        return slot
+
+    def _phys(self, slot: int) -> int:
+        slot = self._logical(slot)
+        if slot not in self._table.row:
+            raise EngineError(f"decoding session: slot {slot} holds no utterance (free or never started)")
+        return self._table.row[slot]
+
+    def _placed(self, slot: int, call, *args, **kw):
+        slot = self._logical(slot)
+        row, new = self._table.place(slot)
+        try:
+            out = call(row, *args, **kw)
+        except Exception as err:
+            if new:
+                self._table.release(slot)
+            if isinstance(err, EngineError):          # the library names the row: say whose it is
+                raise EngineError(f"slot {slot} (row {row}): {err}") from err
+            raise
+        self._running.add(row)
+        return out
+
+    def start(self, slot: int, *args, **kw) -> None:
+        return self._placed(slot, super().start, *args, **kw)
+
+    def start_many(self, requests) -> None:
+        rows = self._many_rows(requests)              # the checks on the caller's slot numbers, before any row is taken
+        new, phys = [], []
+        for slot, r in rows:
+            row, fresh = self._table.place(slot)
+            phys.append((row, r))
+            if fresh:
+                new.append(slot)
+        try:
+            super().start_many(phys)
+        except Exception as err:
+            for slot in new:
+                self._table.release(slot)
+            if isinstance(err, EngineError):          # the library names the row: say whose it is
+                where = ", ".join(f"slot {slot} in row {row}" for (slot, _), (row, _) in zip(rows, phys))
+                raise EngineError(f"{err} ({where})") from err
+            raise
+        self._running.update(row for row, _ in phys)
+
+    def start_from(self, dst: int, src: int, *args, **kw) -> None:
+        return self._placed(dst, lambda row: super(ElasticSlots, self).start_from(row, src, *args, **kw))
+
+    def fork(self, dst: int, src: int, *args, **kw) -> None:
+        return self._placed(dst, lambda row: super(ElasticSlots, self).fork(row, src, *args, **kw))
+
+    def move(self, pairs) -> None:
+        """``DecodeSlots.move`` on ROWS; the table follows, so every slot keeps its number."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        super().move(pairs)
+        self._table.moved(pairs)
+        at = dict(pairs)
+        self._running = {at.get(r, r) for r in self._running}
+
+    def n_gen(self, slot: int) -> int:
+        return super().n_gen(self._phys(slot))
+
+    def step(self, n: int = 16) -> Dict[int, str]:
+        held = set(self._table.row.values()) - self._running
+        plan = compact_plan(sorted(self._running), self.slots, sorted(held))
+        if plan:
+            self.move(plan)
+        status = super().step(n)
+        nb = self.blocks
+        if nb:
+            self.blocks_hist[nb] = self.blocks_hist.get(nb, 0) + int(n)
+        self._running = {r for r, st in status.items() if st == "running"}
+        at = self._table.slot_of()
+        return {at[r]: st for r, st in status.items() if r in at}
+
+    def score_row(self, slot: int):
+        return super().score_row(self._phys(slot))
+
+    def take(self, slot: int, return_logp: bool = False, return_score: bool = False):
+        row = self._phys(slot)
+        scored = self.score(slot) if return_score else None            # ahead of the take, which frees the row
+        out = super().take(row, return_logp, False)
+        self._table.release(int(slot))
+        self._running.discard(row)
         return out + (scored,) if return_score else out
 
 
@@ -1304,7 +1519,10 @@ class LauraGenMI355X:
                                         continual_lengths)
 
     def open_decode(self, slots: int, max_positions: Optional[int] = None, logp: bool = True, score: bool = False,
-                    wide: bool = False, queue: Optional[int] = None, source: Optional[DecodeSlots] = None) -> DecodeSlots:
+                    wide: bool = False, queue: Optional[int] = None, source: Optional[DecodeSlots] = None,
+                    elastic: bool = False) -> DecodeSlots:
+        if elastic:
+            return self.engine.open_decode(slots, max_positions, logp, score, wide, queue, source, elastic=True)
         if queue is None and source is None:
             return self.engine.open_decode(slots, max_positions, logp, score, wide)
         return self.engine.open_decode(slots, max_positions, logp, score, wide, queue, source)

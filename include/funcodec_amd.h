@@ -868,6 +868,33 @@ int fc_laura_slots_queue_status(const fc_laura_slots* s, int64_t* submitted, int
  * over the kernel chain and the waiting tickets are claimed as before. */
 int fc_laura_slots_collect(fc_laura_slots* s, int cap, int32_t* tickets, int32_t* states, int32_t* lens, int32_t* n_gens, int32_t* ends,
                            int64_t* tokens, float* scores, int32_t* n_out);
+/* (entry points added without a struct change: FC_ABI_VERSION stays 7)
+ * An ELASTIC session steps as wide as the slots in use.  With `on` != 0 every fc_laura_slots_step call takes hi, the highest slot that
+ * is RUNNING at the call, from the library's host mirror of the slot states (free, failed and ended-not-taken slots do not count) and
+ * launches the step over rows = min(slots, 16 * (hi / 16 + 1)): the GEMV's grid.y is the column blocks [0, rows / 16), the step attention
+ * and the sampler run rows [0, rows), and nothing else differs from the full step -- the same kernel instantiations (those over column
+ * blocks, also when one block is left), the same buffers, layer strides and key-range split.  No slot can start inside a call, so the
+ * width holds for all its n_steps.  Every step kernel indexes per-row memory from row 0 and no row reads another's, so the rows stepped
+ * hold the full step's bits; the rows above the cut are not touched (a running slot is never among them).  Up to 16 slots there is one
+ * block and nothing changes, the persistent step included; above 16 the step stays the kernel chain at every width.  One captured graph
+ * per distinct width (at most 4), captured on first use and never again; the first step of a session runs eagerly as ever.
+ * Refused on a queued session: its slots are claimed on the device and the host cannot know the busy rows. */
+int fc_laura_slots_set_elastic(fc_laura_slots* s, int on);
+/* The column blocks the last fc_laura_slots_step call launched (ceil(slots / 16) without set_elastic); 0 when it had no running slot and
+ * launched nothing.  For tests and tools. */
+int fc_laura_slots_step_blocks(const fc_laura_slots* s);
+/* n slots to other rows: after the call slot dst[i] IS slot src[i], and src[i] is free.  Everything the session keeps per slot moves in
+ * ONE launch of a copy kernel driven by a device table of the n lines (written by a one-wave launch ahead of it): key / value positions
+ * [0, pos] of every layer; position, generated count, done flag, sample counter, prompt length; the row of the sampling table; the token
+ * and score rows, the forced-token row of a slot that follows one, the log-probability rows [0, max_length); the step's logits and the
+ * kept prefix logits; the pending LM input row and next-embedding row; and the host mirror of the slot (state, prefix and continual
+ * lengths, max_length, whether it follows forced tokens).  The rules of fc_laura_slots_set_rules belong to the row they were set for and
+ * change places with the destination's.  Nothing is re-derived and no layer runs: a running slot goes on as if it had never moved, an
+ * ended one is taken from dst, a later fc_laura_slots_start_from / _fork from dst is the one from src.  Stream-ordered, no
+ * synchronisation.  Refused before any launch, changing nothing and naming the slot: n outside 1 .. slots, a slot outside
+ * 0 .. slots - 1, a slot named twice or on both sides, a source that holds no utterance (free, never started, failed), a destination
+ * that is not free, a queued session. */
+int fc_laura_slots_move(fc_laura_slots* s, int n, const int32_t* src, const int32_t* dst, void* stream);
 
 #ifdef __cplusplus
 }

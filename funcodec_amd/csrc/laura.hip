@@ -778,6 +778,15 @@ int do_decode(fc_laura* e, Ctx& cx, const float* text_outs, const int32_t* text_
 // ---- decoding session ----------------------------------------------------------------------------------------------------
 enum SlotState { SLOT_FREE = 0, SLOT_RUNNING = 1, SLOT_DONE = 2, SLOT_FAILED = 3 };
 
+// what the host keeps per slot of a decoding session
+struct Slot {
+    int state = SLOT_FREE, n_gen = 0, cont_len = 0, max_len = 0;
+    int text_len = 0, prefix = 0;           // of the prompt the slot holds: text tokens, prefix positions P = text_len + 2 + cont_len
+    int forced_on = 0;                      // the slot's utterance follows forced tokens (rows [0, max_len) of its forced row)
+    lk::SampleRow rules{};                  // the rule fields only (fc_laura_slots_set_rules): into the slot's row at every start / fork
+    bool holds() const { return state == SLOT_RUNNING || state == SLOT_DONE; }     // an utterance, running or ended
+};
+
 }  // namespace
 
 // S slots over ONE StepMem of S rows: a slot is a row of the step.  Everything that survives a call lies in the caller's state allocation,
@@ -793,10 +802,7 @@ struct fc_laura_slots {
     float* logp = nullptr;                  // [S][R][V] or null
     float* score = nullptr;                 // [S][R] or null: the log-probability of every step's picks (sample_kernel)
     float* lg0 = nullptr;                   // [S][V]: the logits every slot's prefix pass ended with (the step overwrites m.lg)
-    std::vector<int> state, cont_len, max_len, n_gen;
-    std::vector<int> text_len, prefix;      // of the prompt a slot holds: text tokens, prefix positions P = text_len + 2 + cont_len
-    std::vector<int> forced_on;             // the slot's utterance follows forced tokens (rows [0, max_len) of its forced row)
-    std::vector<lk::SampleRow> rules;       // per slot, the rule fields only (fc_laura_slots_set_rules): into the slot's row at every start / fork
+    std::vector<Slot> slot;                 // [S]
     hipGraphExec_t gexec = nullptr;         // the captured step, and the form it holds
     // an elastic session (fc_laura_slots_set_elastic): a call steps the column blocks up to the highest running slot.  Beyond 16 slots one
     // more captured step per cut width, [nb - 1] = the first nb blocks, captured on first use; the full width is gexec, as ever
@@ -860,6 +866,46 @@ void slots_reset_sync(fc_laura_slots* s, Ctx& cx) {
     s->persist_steps = 0;
 }
 
+// slot `slot` back to "nothing generated" with `row` in the sampling table: slot_reset_kernel.  continual [cont_len][nq]; forced_src
+// [row.max_steps][nq] or null
+void slot_reset(fc_laura_slots* s, Ctx& cx, int slot, const lk::SampleRow& row, int cont_len, const int64_t* continual, const int64_t* forced_src) {
+    const StepMem& m = s->m;
+    lk::SlotReset r;
+    r.slot = slot; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
+    r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = s->e->codec_lm.s.d_model; r.tokens = s->tokens; r.tok_stride = s->R;
+    r.nq = s->e->arch.predict_nq; r.cont_len = cont_len; r.continual = continual; r.forced = s->forced; r.forced_src = forced_src;
+    r.logp = s->logp; r.V = s->e->vocab(); r.score = s->score;
+    cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+}
+
+// the slot's first sample, from the logits its prefix ended with: the sampler on one row
+void sample_first(const fc_laura_slots* s, Ctx& cx, int slot) {
+    lk::Sample sm = slots_sampler(s);
+    sm.row0 = slot; sm.nrows = 1;
+    sm.launch_seq = nullptr;               // only the full-width launch that precedes a persistent step numbers it
+    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+}
+
+// the first P cache positions and the prefix logits of slot `src` of `from` into slot `dst` of `s` (the same session: dst != src), pos[dst] = P
+void prefix_import(fc_laura_slots* s, Ctx& cx, int dst, const fc_laura_slots* from, int src, int P, const char* what) {
+    const StepMem& m = s->m;
+    lk::PrefixImport c;
+    c.kc_src = from->m.kc; c.vc_src = from->m.vc; c.kc_dst = m.kc; c.vc_dst = m.vc;
+    c.lg0_src = from->lg0; c.lg_dst = m.lg; c.lg0_dst = s->lg0; c.pos_dst = m.pos;
+    c.NL = s->e->codec_lm.s.layers; c.d = s->e->codec_lm.s.d_model; c.V = s->e->vocab();
+    c.S_src = from->S; c.Tcap_src = from->m.Tcap; c.S_dst = s->S; c.Tcap_dst = m.Tcap;
+    c.P = P; c.src = src; c.dst = dst;
+    cx.check(lk::launch_prefix_import(c, cx.st), what);
+}
+
+// From here on the slot's previous utterance is gone (a start on a running slot abandons it): the facts of the new prompt, and failed
+// until its launches are out.  n_gen > 0: a fork that keeps so many tokens.
+void slot_restart(fc_laura_slots* s, int slot, int text_len, int cont_len, int max_length, int forced_on, int n_gen = 0) {
+    Slot& x = s->slot[slot];
+    x.state = SLOT_FAILED; x.n_gen = n_gen; x.cont_len = cont_len; x.max_len = max_length;
+    x.text_len = text_len; x.prefix = text_len + 2 + cont_len; x.forced_on = forced_on;
+}
+
 // the prefix pass of ONE prompt (B = 1) into row `slot`, and the slot's first sample
 int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, int text_len, const int64_t* continual, int cont_len,
                  const lk::SampleRow& row, const int64_t* forced) {
@@ -877,12 +923,7 @@ int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, i
     const StepMem& m = s->m;
     int* pos = m.pos ? m.pos + slot : nullptr;
     if (cx.live()) {
-        lk::SlotReset r;
-        r.slot = slot; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
-        r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
-        r.continual = continual; r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
-        r.score = s->score;
-        cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+        slot_reset(s, cx, slot, row, cont_len, continual, forced);
         cx.check(lk::launch_lm_assemble(tfm, Tt, tl, e->lm_emb, e->cb, K, nq, continual, cl, cont_len, 1, D, T, seq, pos, bidir, cx.st), "LM input");
     }
     KvOut kv;
@@ -895,10 +936,7 @@ int slots_prefix(fc_laura_slots* s, Ctx& cx, int slot, const float* text_outs, i
     // kept for fc_laura_slots_start_from: the step overwrites the slot's row of m.lg
     cx.check(hipMemcpyAsync(s->lg0 + (size_t)slot * V, m.lg + (size_t)slot * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, cx.st),
              "prefix logits");
-    lk::Sample sm = slots_sampler(s);
-    sm.row0 = slot; sm.nrows = 1;
-    sm.launch_seq = nullptr;               // only the full-width launch that precedes a persistent step numbers it
-    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    sample_first(s, cx, slot);
     return cx.err;
 }
 
@@ -924,12 +962,7 @@ int slots_prefix_many(fc_laura_slots* s, Ctx& cx, const lk::RowSlots& rs, const 
     if (cx.live()) {
         for (int b = 0; b < n; ++b) {
             const int cont_len = continual ? cont_lens[b] : 0;
-            lk::SlotReset r;
-            r.slot = rs.slot[b]; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
-            r.rows = s->rows; r.row = rows[b]; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
-            r.continual = cont_len ? continual + (size_t)b * Cmax * nq : nullptr; r.forced = s->forced; r.forced_src = nullptr;
-            r.logp = s->logp; r.V = V; r.score = s->score;
-            cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
+            slot_reset(s, cx, rs.slot[b], rows[b], cont_len, cont_len ? continual + (size_t)b * Cmax * nq : nullptr, nullptr);
         }
         cx.check(lk::launch_lm_assemble(tfm, Tt, tl, e->lm_emb, e->cb, K, nq, continual, cl, Cmax, n, D, T, seq, seq_len, bidir, cx.st), "LM input");
     }
@@ -939,35 +972,50 @@ int slots_prefix_many(fc_laura_slots* s, Ctx& cx, const lk::RowSlots& rs, const 
     float* h = run_stack_full(e, cx, S, seq, T, seq_len, e->arch.bidirectional_inputs ? bidir : nullptr, 1, &kv);
     if (cx.dry || cx.err) return cx.err;
     cx.check(lk::launch_gather_last_slots(h, seq_len, rs, s->S, d, T, m.xs, m.pos, cx.st), "last position");
-    lk::Sample sm = slots_sampler(s);
-    sm.nrows = 1;
-    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
     for (int b = 0; b < n && !cx.err; ++b) {
         const int slot = rs.slot[b];
         cx.check(step_gemv(e->lm_decoder, m.xs + (size_t)slot * d, 1, nullptr, nullptr, 0.f, 0, 0, m.lg + (size_t)slot * V, V, cx.st), "decoder GEMV");
         cx.check(hipMemcpyAsync(s->lg0 + (size_t)slot * V, m.lg + (size_t)slot * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, cx.st),
                  "prefix logits");
-        sm.row0 = slot;
-        cx.check(lk::launch_sample(sm, cx.st), "sampling");
+        sample_first(s, cx, slot);
     }
     return cx.err;
 }
 
-// the slot's rules against the sampling mode of the start / start_from / fork that is about to write them
-int check_rules_mode(const fc_laura_slots* s, int slot, int mode) {
-    const lk::SampleRow& r = s->rules[slot];
-    if (r.top_p > 0.f && mode != 2)
-        return fail("decoding session: slot " + std::to_string(slot) + ": top_p applies with top-k sampling (an integer `sampling`) only");
-    if (r.repeat_window > 0 && mode == 0)
-        return fail("decoding session: slot " + std::to_string(slot) + ": the repeat rule needs a drawing mode, not greedy");
+std::string slot_who(int slot) { return "decoding session: slot " + std::to_string(slot); }
+
+// the rules `r` against the sampling mode of the start / start_from / fork / submit that is about to write them; `who` heads the message
+int check_rules_mode(const lk::SampleRow& r, int mode, const std::string& who) {
+    if (r.top_p > 0.f && mode != 2) return fail(who + "top_p applies with top-k sampling (an integer `sampling`) only");
+    if (r.repeat_window > 0 && mode == 0) return fail(who + "the repeat rule needs a drawing mode, not greedy");
     return 0;
 }
 
-// the slot's rules into a row of the sampling table
-void put_rules(const fc_laura_slots* s, int slot, lk::SampleRow& row) {
-    const lk::SampleRow& r = s->rules[slot];
-    row.temperature = r.temperature; row.min_length = r.min_length; row.top_p = r.top_p;
-    row.repeat_window = r.repeat_window; row.repeat_count = r.repeat_count;
+// what is wrong with a set of rules, as the tail of a message; empty: nothing
+std::string rules_problem(float temperature, int min_length, float top_p, int repeat_window, int repeat_count) {
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) return "temperature must be finite and > 0";
+    if (min_length < 0) return "min_length " + std::to_string(min_length) + " < 0";
+    if (!(top_p >= 0.f && top_p <= 1.f)) return "top_p must lie in (0, 1], or be 0 for none";
+    if (repeat_window < 0 || repeat_window > 256) return "repeat_window " + std::to_string(repeat_window) + " outside 0 .. 256";
+    if (repeat_window > 0 && (repeat_count < 1 || repeat_count > repeat_window))
+        return "repeat_count " + std::to_string(repeat_count) + " outside 1 .. repeat_window " + std::to_string(repeat_window);
+    return "";
+}
+
+// checked rules as a row that holds the rule fields only
+lk::SampleRow rules_row(float temperature, int min_length, float top_p, int repeat_window, int repeat_count) {
+    lk::SampleRow r{};
+    r.temperature = temperature; r.min_length = min_length; r.top_p = top_p;
+    r.repeat_window = repeat_window; r.repeat_count = repeat_window > 0 ? repeat_count : 1;
+    return r;
+}
+
+// a row of the sampling table: `rules` (the rule fields of a slot or a ticket) with the sampling of one utterance
+lk::SampleRow make_row(const lk::SampleRow& rules, int mode, int k, float p, int max_length, uint64_t seed, int forced_on) {
+    lk::SampleRow row = rules;
+    row.mode = mode; row.ki = k; row.pf = p; row.max_steps = max_length; row.seed = seed;
+    row.forced_on = forced_on; row.rng_row = 0u;           // the slot index is NOT in the Philox counter: a slot's draws are its own
+    return row;
 }
 
 const char* sampling_problem(int mode, int k, float p) {
@@ -982,46 +1030,49 @@ int check_sampling(int mode, int k, float p) {
     return why ? fail(why) : 0;
 }
 
-// Slot `dst` from the prompt slot `src` holds: the reset, the copy of the source's prefix, the first sample from the prefix logits.  The
-// caller has checked everything.  dst == src (a rewind to nothing generated) keeps the slot's own prefix and needs no copy.
-int slots_from_prefix(fc_laura_slots* s, int dst, int src, int max_length, int sampling_mode, int sampling_k, float sampling_p, uint64_t seed,
-                      const int64_t* forced, void* stream) {
-    const int P = s->prefix[src], cont_len = s->cont_len[src];
-    fc_laura* e = s->e;
+// Slot `src` of session `from` as the source of a copy: in range, and it holds an utterance.  `who` names it at the head of both messages
+// and `of` follows its range; a submit names the row otherwise in the second message (`holder`) and says a prompt is what it holds.
+int check_source(const fc_laura_slots* from, int src, const std::string& who, const std::string& of = "", std::string holder = "",
+                 const char* holds = " holds no utterance (") {
+    if (src < 0 || src >= from->S) return fail(who + " outside 0 .. " + std::to_string(from->S - 1) + of);
+    if (holder.empty()) holder = who + of;
+    if (!from->slot[src].holds())
+        return fail(holder + holds + (from->slot[src].state == SLOT_FAILED ? "failed" : "free or never started") + ")");
+    return 0;
+}
+
+// a prompt of P prefix positions and max_length steps in a session of R positions per slot
+int check_fits(const std::string& who, int P, int max_length, int R) {
+    if (P + max_length <= R) return 0;
+    return fail(who + "text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) + " exceeds the session's max_positions " +
+                std::to_string(R));
+}
+
+// Slot `dst` of `s` from the prompt slot `src` of `from` holds (the same session or another of the engine): the reset, the copy of the
+// source's prefix, the first sample from the prefix logits.  The caller has checked everything.  The same slot (a rewind to nothing
+// generated) keeps its own prefix and needs no copy.
+int slots_from_prefix(fc_laura_slots* s, int dst, const fc_laura_slots* from, int src, int max_length, int sampling_mode, int sampling_k,
+                      float sampling_p, uint64_t seed, const int64_t* forced, void* stream) {
+    const Slot& held = from->slot[src];
+    const int P = held.prefix, cont_len = held.cont_len;
     const StepMem& m = s->m;
-    const int d = e->codec_lm.s.d_model, V = e->vocab(), nq = e->arch.predict_nq;
-    lk::SampleRow row{};
-    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
-    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;
-    put_rules(s, dst, row);
-    // from here on the destination's previous utterance is gone (as a start on a running slot abandons it)
-    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = 0; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
-    s->text_len[dst] = s->text_len[src]; s->prefix[dst] = P; s->forced_on[dst] = forced ? 1 : 0;
+    const int V = s->e->vocab();
+    const lk::SampleRow row = make_row(s->slot[dst].rules, sampling_mode, sampling_k, sampling_p, max_length, seed, forced ? 1 : 0);
+    slot_restart(s, dst, held.text_len, cont_len, max_length, forced ? 1 : 0);
     Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
     s->last = cx.st;
-    lk::SlotReset r;
-    r.slot = dst; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
-    r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
-    r.continual = s->tokens + (size_t)src * s->R * nq;      // the source's prompt tokens: generation never changes rows [0, cont_len)
-    r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
-    r.score = s->score;
-    cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
-    if (dst != src) {
-        lk::PrefixCopy c;
-        c.kc = m.kc; c.vc = m.vc; c.lg = m.lg; c.lg0 = s->lg0; c.pos = m.pos;
-        c.NL = e->codec_lm.s.layers; c.S = s->S; c.d = d; c.Tcap = m.Tcap; c.V = V; c.P = P; c.src = src; c.n = 1; c.dst[0] = dst;
-        cx.check(lk::launch_prefix_copy(c, cx.st), "prefix copy");
+    // the source's prompt tokens, in its session's token row: generation never changes rows [0, cont_len)
+    slot_reset(s, cx, dst, row, cont_len, from->tokens + (size_t)src * from->R * s->e->arch.predict_nq, forced);
+    if (from != s || dst != src) {
+        prefix_import(s, cx, dst, from, src, P, from != s ? "prefix import" : "prefix copy");
     } else {
         cx.check(hipMemcpyAsync(m.lg + (size_t)dst * V, s->lg0 + (size_t)dst * V, (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, cx.st),
                  "prefix logits");
         cx.check(lk::launch_fill_i32(m.pos + dst, P, 1, cx.st), "position");
     }
-    lk::Sample sm = slots_sampler(s);
-    sm.row0 = dst; sm.nrows = 1;
-    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
-    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    sample_first(s, cx, dst);
     if (cx.err) return 1;
-    s->state[dst] = SLOT_RUNNING;
+    s->slot[dst].state = SLOT_RUNNING;
     return 0;
 }
 
@@ -1033,17 +1084,29 @@ int refuse_queued(const fc_laura_slots* s, const char* call) {
 
 void slots_report(const fc_laura_slots* s, int32_t* done_out, int32_t* n_gen_out) {
     for (int i = 0; i < s->S; ++i) {
-        if (done_out) done_out[i] = s->state[i];
-        if (n_gen_out) n_gen_out[i] = s->n_gen[i];
+        if (done_out) done_out[i] = s->slot[i].state;
+        if (n_gen_out) n_gen_out[i] = s->slot[i].n_gen;
     }
+}
+
+// After a hand-off of the persistent step timed out (the caller has failed what ran): the session stays on the kernel chain, the event
+// is counted, and the device words go back to "nothing runs" -- every slot ended, of a queued session no slot with a ticket, the
+// arrival counters at zero.  Never a silent result.
+int after_timeout(fc_laura_slots* s, Ctx& cx) {
+    s->chain_only = true;
+    s->e->persist_fallbacks++;
+    if (s->gexec) { (void)hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
+    cx.check(lk::launch_fill_i32(s->m.done(), 1, s->S, cx.st), "done flags");
+    if (s->Q) cx.check(lk::launch_fill_i32(s->qp.qw + lk::FC_QUEUE_SLOT_TICKET, -1, 64, cx.st), "slot tickets");
+    slots_reset_sync(s, cx);
+    if (hipStreamSynchronize(cx.st) != hipSuccess || cx.err) return fail("decoding session: reset after a timed-out step failed");
+    return 0;
 }
 
 // The host's side of a queued session's step, behind the read-back: the mirrors of the counters, the slots' tickets and the result
 // entries.  A hand-off time-out of the persistent step fails every ticket that ran in this call -- those still in a slot and those the
 // call retired, whose tokens come from steps that cannot be trusted -- and the queue goes on over the kernel chain.
-int queue_after_step(fc_laura_slots* s, Ctx& cx, hipError_t ea, bool persist, int32_t* done_out, int32_t* n_gen_out) {
-    fc_laura* e = s->e;
-    const StepMem& m = s->m;
+int queue_after_step(fc_laura_slots* s, Ctx& cx, hipError_t ea, int32_t* done_out, int32_t* n_gen_out) {
     const int S = s->S, Q = s->Q;
     const int* host = s->status;
     const int* qw = host + 2 * S + 1;
@@ -1065,8 +1128,8 @@ int queue_after_step(fc_laura_slots* s, Ctx& cx, hipError_t ea, bool persist, in
     for (int i = 0; i < S; ++i) {
         s->slot_ticket[i] = qw[lk::FC_QUEUE_SLOT_TICKET + i];
         const bool runs = s->slot_ticket[i] >= 0;
-        s->state[i] = runs ? (host[S + i] ? SLOT_DONE : SLOT_RUNNING) : SLOT_FREE;
-        s->n_gen[i] = runs ? host[i] : 0;
+        s->slot[i].state = runs ? (host[S + i] ? SLOT_DONE : SLOT_RUNNING) : SLOT_FREE;
+        s->slot[i].n_gen = runs ? host[i] : 0;
     }
     if (perr) {
         for (int i = 0; i < S; ++i) {
@@ -1074,17 +1137,10 @@ int queue_after_step(fc_laura_slots* s, Ctx& cx, hipError_t ea, bool persist, in
             fc_laura_slots::Entry& E = s->entries[qw[lk::FC_QUEUE_SLOT_ENTRY + i]];
             if (E.state == 1 && E.ticket == s->slot_ticket[i]) { E.state = 3; s->failed++; }
             s->slot_ticket[i] = -1;
-            s->state[i] = SLOT_FREE; s->n_gen[i] = 0;
+            s->slot[i].state = SLOT_FREE; s->slot[i].n_gen = 0;
         }
-        s->chain_only = true;
-        e->persist_fallbacks++;
-        if (s->gexec) { (void)hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
-        cx.check(lk::launch_fill_i32(m.done(), 1, S, cx.st), "done flags");
-        cx.check(lk::launch_fill_i32(s->qp.qw + lk::FC_QUEUE_SLOT_TICKET, -1, 64, cx.st), "slot tickets");
-        slots_reset_sync(s, cx);
-        if (hipStreamSynchronize(cx.st) != hipSuccess || cx.err) return fail("decoding session: reset after a timed-out step failed");
+        if (after_timeout(s, cx)) return 1;
     }
-    (void)persist;
     slots_report(s, done_out, n_gen_out);
     return 0;
 }
@@ -1336,53 +1392,61 @@ int fc_laura_decode_codec(fc_laura* e, const float* text_outs, const int32_t* te
 int fc_laura_persistent_step_fallbacks(const fc_laura* e) { return e ? e->persist_fallbacks : -1; }
 
 /* ---- decoding session: S slots that start and end independently in one running batch ---- */
-size_t fc_laura_slots_state_bytes(const fc_laura* e, int slots, int max_positions, int with_logp) {
-    return fc_laura_slots_state_bytes_scored(e, slots, max_positions, with_logp, 0);
+// What is wrong with the sizes of a session, for the create and the state-bytes side alike (e is not null); empty: nothing.  max_slots is
+// 16 for the calls that predate the wide session, and they say so.
+static std::string create_problem(const fc_laura* e, int slots, int max_positions, int max_slots) {
+    if (slots < 1 || slots > max_slots)
+        return (max_slots > 16 ? "a wide decoding session has 1 .. 64 slots (4 column blocks of the step form's 16 MFMA columns), got "
+                               : "a decoding session has 1 .. 16 slots (the step form's 16 MFMA columns), got ") + std::to_string(slots);
+    if (max_positions < 16 || max_positions % 4 || max_positions > e->R)
+        return "a decoding session's max_positions must be a multiple of 4 in [16, " + std::to_string(e->R) + "] (the engine's), got " +
+               std::to_string(max_positions);
+    return "";
+}
+static std::string queue_problem(int queue) {
+    if (queue < 1 || queue > 65536) return "a queued decoding session has 1 .. 65536 result entries, got " + std::to_string(queue);
+    return "";
 }
 
-size_t fc_laura_slots_state_bytes_scored(const fc_laura* e, int slots, int max_positions, int with_logp, int with_score) {
-    return slots > 16 ? 0 : fc_laura_slots_state_bytes_wide(e, slots, max_positions, with_logp, with_score);
-}
-
-size_t fc_laura_slots_state_bytes_wide(const fc_laura* ce, int slots, int max_positions, int with_logp, int with_score) {
+// every byte count: queue = 0 is the session without a queue
+static size_t slots_state_bytes(const fc_laura* ce, int slots, int max_positions, int with_logp, int with_score, int queue, int max_slots) {
     fc_laura* e = const_cast<fc_laura*>(ce);
-    if (!e || slots < 1 || slots > 64 || max_positions < 16 || max_positions > e->R || max_positions % 4) return 0;
+    if (!e || !create_problem(e, slots, max_positions, max_slots).empty()) return 0;
     Ctx cx = make_ctx(slots, nullptr, 0, nullptr);
     fc_laura_slots s;
-    slots_layout(e, cx, slots, max_positions, with_logp != 0, with_score != 0, s);
+    slots_layout(e, cx, slots, max_positions, with_logp != 0, with_score != 0, s, queue);
     return cx.off + 4096;
 }
 
-int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_logp, void* state, size_t state_bytes, fc_laura_slots** out) {
-    return fc_laura_slots_create_scored(e, slots, max_positions, with_logp, 0, state, state_bytes, out);
+size_t fc_laura_slots_state_bytes(const fc_laura* e, int slots, int max_positions, int with_logp) {
+    return slots_state_bytes(e, slots, max_positions, with_logp, 0, 0, 16);
 }
 
-int fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
-                                 fc_laura_slots** out) {
-    if (slots < 1 || slots > 16) {
-        if (check_ready(e)) return 1;
-        return fail("a decoding session has 1 .. 16 slots (the step form's 16 MFMA columns), got " + std::to_string(slots));
-    }
-    return fc_laura_slots_create_wide(e, slots, max_positions, with_logp, with_score, state, state_bytes, out);
+size_t fc_laura_slots_state_bytes_scored(const fc_laura* e, int slots, int max_positions, int with_logp, int with_score) {
+    return slots_state_bytes(e, slots, max_positions, with_logp, with_score, 0, 16);
+}
+
+size_t fc_laura_slots_state_bytes_wide(const fc_laura* e, int slots, int max_positions, int with_logp, int with_score) {
+    return slots_state_bytes(e, slots, max_positions, with_logp, with_score, 0, 64);
+}
+
+size_t fc_laura_slots_state_bytes_queued(const fc_laura* e, int slots, int max_positions, int with_score, int queue) {
+    return queue_problem(queue).empty() ? slots_state_bytes(e, slots, max_positions, 0, with_score, queue, 64) : 0;
 }
 
 // every create: Q = 0 is the session without a queue, call for call what fc_laura_slots_create_wide always did
 static int slots_create(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, int Q, const fc_laura_slots* from,
-                        void* state, size_t state_bytes, fc_laura_slots** out) {
+                        void* state, size_t state_bytes, fc_laura_slots** out, int max_slots = 64) {
     if (check_ready(e)) return 1;
-    if (slots < 1 || slots > 64)
-        return fail("a wide decoding session has 1 .. 64 slots (4 column blocks of the step form's 16 MFMA columns), got " + std::to_string(slots));
-    if (max_positions < 16 || max_positions % 4 || max_positions > e->R)
-        return fail("a decoding session's max_positions must be a multiple of 4 in [16, " + std::to_string(e->R) + "] (the engine's), got " +
-                    std::to_string(max_positions));
+    const std::string why = create_problem(e, slots, max_positions, max_slots);
+    if (!why.empty()) return fail(why);
     if (!state || !out) return fail("null argument");
     auto s = std::make_unique<fc_laura_slots>();
     s->e = e; s->S = slots; s->R = max_positions; s->with_logp = with_logp != 0; s->with_score = with_score != 0;
     Ctx cx = make_ctx(slots, state, state_bytes, nullptr);
     slots_layout(e, cx, slots, max_positions, s->with_logp, s->with_score, *s, Q);
     if (cx.err) return fail("decoding session: state allocation too small (fc_laura_slots_state_bytes)");
-    s->state.assign(slots, SLOT_FREE); s->cont_len.assign(slots, 0); s->max_len.assign(slots, 0); s->n_gen.assign(slots, 0);
-    s->text_len.assign(slots, 0); s->prefix.assign(slots, 0); s->forced_on.assign(slots, 0);
+    s->slot.assign(slots, Slot{});                          // free, the neutral rules
     // a never-started slot: done = 1, pos = 0, a zero xs row -- it goes through every step with finite values and the sampler skips it
     const StepMem& m = s->m;
     const Stack& S = e->codec_lm;
@@ -1398,8 +1462,8 @@ static int slots_create(fc_laura* e, int slots, int max_positions, int with_logp
     HIP_TRY(hipMemset(m.nemb, 0, RW * e->arch.codebook_dim * sizeof(float)));
     HIP_TRY(hipMemset(m.edge, 0, m.edge_stride * S.s.layers * sizeof(float)));
     HIP_TRY(hipMemset(m.psync, 0, (m.sync_words + 32) * sizeof(unsigned)));
-    s->rules.assign(slots, lk::SampleRow{});                // the neutral rules
-    HIP_TRY(hipMemcpy(s->rows, s->rules.data(), (size_t)slots * sizeof(lk::SampleRow), hipMemcpyHostToDevice));
+    const std::vector<lk::SampleRow> neutral(slots, lk::SampleRow{});
+    HIP_TRY(hipMemcpy(s->rows, neutral.data(), (size_t)slots * sizeof(lk::SampleRow), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(s->tok_off, 0, (size_t)slots * sizeof(int)));
     if (s->score) HIP_TRY(hipMemset(s->score, 0, (size_t)slots * max_positions * sizeof(float)));
     std::vector<int> ones(slots, 1);
@@ -1427,24 +1491,25 @@ static int slots_create(fc_laura* e, int slots, int max_positions, int with_logp
     return 0;
 }
 
+int fc_laura_slots_create(fc_laura* e, int slots, int max_positions, int with_logp, void* state, size_t state_bytes, fc_laura_slots** out) {
+    return slots_create(e, slots, max_positions, with_logp, 0, 0, nullptr, state, state_bytes, out, 16);
+}
+
+int fc_laura_slots_create_scored(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
+                                 fc_laura_slots** out) {
+    return slots_create(e, slots, max_positions, with_logp, with_score, 0, nullptr, state, state_bytes, out, 16);
+}
+
 int fc_laura_slots_create_wide(fc_laura* e, int slots, int max_positions, int with_logp, int with_score, void* state, size_t state_bytes,
                                fc_laura_slots** out) {
     return slots_create(e, slots, max_positions, with_logp, with_score, 0, nullptr, state, state_bytes, out);
 }
 
-size_t fc_laura_slots_state_bytes_queued(const fc_laura* ce, int slots, int max_positions, int with_score, int queue) {
-    fc_laura* e = const_cast<fc_laura*>(ce);
-    if (!e || slots < 1 || slots > 64 || max_positions < 16 || max_positions > e->R || max_positions % 4 || queue < 1 || queue > 65536) return 0;
-    Ctx cx = make_ctx(slots, nullptr, 0, nullptr);
-    fc_laura_slots s;
-    slots_layout(e, cx, slots, max_positions, false, with_score != 0, s, queue);
-    return cx.off + 4096;
-}
-
 int fc_laura_slots_create_queued(fc_laura* e, int slots, int max_positions, int with_score, int queue, const fc_laura_slots* source,
                                  void* state, size_t state_bytes, fc_laura_slots** out) {
     if (check_ready(e)) return 1;
-    if (queue < 1 || queue > 65536) return fail("a queued decoding session has 1 .. 65536 result entries, got " + std::to_string(queue));
+    const std::string why = queue_problem(queue);
+    if (!why.empty()) return fail(why);
     if (!source) return fail("a queued decoding session needs a source session (its tickets name the source's rows)");
     if (source->e != e) return fail("a queued decoding session: the source session belongs to another engine (other weights: its prefix is not this engine's)");
     if (source->Q) return fail("a queued decoding session: the source session is itself queued (it holds no prompts)");
@@ -1477,27 +1542,19 @@ int fc_laura_slots_start(fc_laura_slots* s, int slot, const float* text_outs, in
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
     if (!text_outs || !workspace || text_len < 1 || max_length < 1 || cont_len < 0 || (cont_len > 0 && !continual))
         return fail("decoding session: bad argument for slot " + std::to_string(slot));
-    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, slot, sampling_mode)) return 1;
-    const int need = text_len + 2 + cont_len + max_length;
-    if (need > s->R)
-        return fail("decoding session: slot " + std::to_string(slot) + ": text_len + 2 + cont_len + max_length = " + std::to_string(need) +
-                    " exceeds the session's max_positions " + std::to_string(s->R));
-    lk::SampleRow row{};
-    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
-    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;      // the slot index is NOT in the Philox counter: a slot's draws are its own
-    put_rules(s, slot, row);
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s->slot[slot].rules, sampling_mode, slot_who(slot) + ": ")) return 1;
+    if (check_fits(slot_who(slot) + ": ", text_len + 2 + cont_len, max_length, s->R)) return 1;
+    const lk::SampleRow row = make_row(s->slot[slot].rules, sampling_mode, sampling_k, sampling_p, max_length, seed, forced ? 1 : 0);
     {
         Ctx dry = make_ctx(1, nullptr, 0, nullptr);
         slots_prefix(s, dry, slot, nullptr, text_len, nullptr, cont_len, row, nullptr);
         if (dry.off > workspace_bytes) return fail("workspace too small");
     }
-    // from here on the slot's previous utterance is gone (a start on a running slot abandons it)
-    s->state[slot] = SLOT_FAILED; s->n_gen[slot] = 0; s->cont_len[slot] = cont_len; s->max_len[slot] = max_length;
-    s->text_len[slot] = text_len; s->prefix[slot] = text_len + 2 + cont_len; s->forced_on[slot] = forced ? 1 : 0;
+    slot_restart(s, slot, text_len, cont_len, max_length, forced ? 1 : 0);
     s->last = (hipStream_t)stream;
     Ctx cx = make_ctx(1, workspace, workspace_bytes, stream);
     if (slots_prefix(s, cx, slot, text_outs, text_len, cont_len ? continual : nullptr, cont_len, row, forced)) return 1;
-    s->state[slot] = SLOT_RUNNING;
+    s->slot[slot].state = SLOT_RUNNING;
     return 0;
 }
 
@@ -1506,20 +1563,13 @@ int fc_laura_slots_start_from(fc_laura_slots* s, int dst, int src, int max_lengt
     if (!s) return fail("null session");
     if (refuse_queued(s, "start_from")) return 1;
     if (check_ready(s->e)) return 1;
-    const std::string range = " outside 0 .. " + std::to_string(s->S - 1);
-    if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + range);
-    if (src < 0 || src >= s->S) return fail("decoding session: source slot " + std::to_string(src) + range);
-    if (dst == src) return fail("decoding session: slot " + std::to_string(dst) + " cannot be started from itself");
-    if (s->state[src] != SLOT_RUNNING && s->state[src] != SLOT_DONE)
-        return fail("decoding session: source slot " + std::to_string(src) + " holds no utterance (" +
-                    (s->state[src] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+    if (dst < 0 || dst >= s->S) return fail(slot_who(dst) + " outside 0 .. " + std::to_string(s->S - 1));
+    if (dst == src) return fail(slot_who(dst) + " cannot be started from itself");      // dst is in range: so is this src
+    if (check_source(s, src, "decoding session: source slot " + std::to_string(src))) return 1;
     if (max_length < 1) return fail("decoding session: bad argument for slot " + std::to_string(dst));
-    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, dst, sampling_mode)) return 1;
-    const int P = s->prefix[src], cont_len = s->cont_len[src];
-    if (P + max_length > s->R)
-        return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
-                    " exceeds the session's max_positions " + std::to_string(s->R));
-    return slots_from_prefix(s, dst, src, max_length, sampling_mode, sampling_k, sampling_p, seed, forced, stream);
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s->slot[dst].rules, sampling_mode, slot_who(dst) + ": ")) return 1;
+    if (check_fits(slot_who(dst) + ": ", s->slot[src].prefix, max_length, s->R)) return 1;
+    return slots_from_prefix(s, dst, s, src, max_length, sampling_mode, sampling_k, sampling_p, seed, forced, stream);
 }
 
 size_t fc_laura_slots_start_many_workspace_bytes(const fc_laura_slots* cs, int n, int L, int Cmax) {
@@ -1553,7 +1603,7 @@ int fc_laura_slots_start_many(fc_laura_slots* s, int n, const int32_t* slots, co
     int Tmax = 0;
     for (int b = 0; b < n; ++b) {
         const int slot = slots[b];
-        const std::string who = "decoding session: slot " + std::to_string(slot);
+        const std::string who = slot_who(slot);
         if (slot < 0 || slot >= s->S) return fail(who + " outside 0 .. " + std::to_string(s->S - 1));
         for (int j = 0; j < b; ++j)
             if (slots[j] == slot) return fail(who + " is named twice in one start_many");
@@ -1561,34 +1611,23 @@ int fc_laura_slots_start_many(fc_laura_slots* s, int n, const int32_t* slots, co
         if (text_lens[b] < 1 || text_lens[b] > L || max_lengths[b] < 1 || cont_len < 0 || cont_len > Cmax)
             return fail("decoding session: bad argument for slot " + std::to_string(slot));
         if (const char* why = sampling_problem(sampling_modes[b], sampling_ks[b], sampling_ps[b])) return fail(who + ": " + why);
-        if (check_rules_mode(s, slot, sampling_modes[b])) return 1;
-        const int P = text_lens[b] + 2 + cont_len, need = P + max_lengths[b];
-        if (need > s->R)
-            return fail(who + ": text_len + 2 + cont_len + max_length = " + std::to_string(need) + " exceeds the session's max_positions " +
-                        std::to_string(s->R));
+        if (check_rules_mode(s->slot[slot].rules, sampling_modes[b], who + ": ")) return 1;
+        const int P = text_lens[b] + 2 + cont_len;
+        if (check_fits(who + ": ", P, max_lengths[b], s->R)) return 1;
         Tmax = std::max(Tmax, P);
         rs.slot[b] = slot;
-        lk::SampleRow& row = rows[b];
-        row = lk::SampleRow{};
-        row.mode = sampling_modes[b]; row.ki = sampling_ks[b]; row.pf = sampling_ps[b]; row.max_steps = max_lengths[b]; row.seed = seeds[b];
-        row.forced_on = 0; row.rng_row = 0u;
-        put_rules(s, slot, row);
+        rows[b] = make_row(s->slot[slot].rules, sampling_modes[b], sampling_ks[b], sampling_ps[b], max_lengths[b], seeds[b], 0);
     }
     {
         Ctx dry = make_ctx(n, nullptr, 0, nullptr);
         slots_prefix_many(s, dry, rs, nullptr, nullptr, L, nullptr, nullptr, Cmax, nullptr, Tmax);
         if (dry.off > workspace_bytes) return fail("workspace too small");
     }
-    // from here on the named slots' previous utterances are gone (a start on a running slot abandons it)
-    for (int b = 0; b < n; ++b) {
-        const int slot = slots[b], cont_len = continual ? cont_lens[b] : 0;
-        s->state[slot] = SLOT_FAILED; s->n_gen[slot] = 0; s->cont_len[slot] = cont_len; s->max_len[slot] = max_lengths[b];
-        s->text_len[slot] = text_lens[b]; s->prefix[slot] = text_lens[b] + 2 + cont_len; s->forced_on[slot] = 0;
-    }
+    for (int b = 0; b < n; ++b) slot_restart(s, slots[b], text_lens[b], continual ? cont_lens[b] : 0, max_lengths[b], 0);
     s->last = (hipStream_t)stream;
     Ctx cx = make_ctx(n, workspace, workspace_bytes, stream);
     if (slots_prefix_many(s, cx, rs, text_outs, text_lens, L, continual, cont_lens, Cmax, rows, Tmax)) return 1;
-    for (int b = 0; b < n; ++b) s->state[slots[b]] = SLOT_RUNNING;
+    for (int b = 0; b < n; ++b) s->slot[slots[b]].state = SLOT_RUNNING;
     return 0;
 }
 
@@ -1597,54 +1636,15 @@ int fc_laura_slots_start_from_session(fc_laura_slots* s, int dst, const fc_laura
     if (!s || !from) return fail("null session");
     if (refuse_queued(s, "start_from_session")) return 1;
     if (check_ready(s->e)) return 1;
-    if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + " outside 0 .. " + std::to_string(s->S - 1));
+    if (dst < 0 || dst >= s->S) return fail(slot_who(dst) + " outside 0 .. " + std::to_string(s->S - 1));
     if (from->e != s->e)
-        return fail("decoding session: slot " + std::to_string(dst) + ": the source session belongs to another engine (other weights: its prefix is not this engine's)");
-    if (from == s)
-        return fail("decoding session: slot " + std::to_string(dst) + ": the source session is this session (fc_laura_slots_start_from copies inside one)");
-    if (src < 0 || src >= from->S)
-        return fail("decoding session: source slot " + std::to_string(src) + " outside 0 .. " + std::to_string(from->S - 1) + " of the source session");
-    if (from->state[src] != SLOT_RUNNING && from->state[src] != SLOT_DONE)
-        return fail("decoding session: source slot " + std::to_string(src) + " of the source session holds no utterance (" +
-                    (from->state[src] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+        return fail(slot_who(dst) + ": the source session belongs to another engine (other weights: its prefix is not this engine's)");
+    if (from == s) return fail(slot_who(dst) + ": the source session is this session (fc_laura_slots_start_from copies inside one)");
+    if (check_source(from, src, "decoding session: source slot " + std::to_string(src), " of the source session")) return 1;
     if (max_length < 1) return fail("decoding session: bad argument for slot " + std::to_string(dst));
-    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, dst, sampling_mode)) return 1;
-    const int P = from->prefix[src], cont_len = from->cont_len[src];
-    if (P + max_length > s->R)
-        return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
-                    " exceeds the session's max_positions " + std::to_string(s->R));
-    fc_laura* e = s->e;
-    const StepMem& m = s->m;
-    const int d = e->codec_lm.s.d_model, V = e->vocab(), nq = e->arch.predict_nq;
-    lk::SampleRow row{};
-    row.mode = sampling_mode; row.ki = sampling_k; row.pf = sampling_p; row.max_steps = max_length; row.seed = seed;
-    row.forced_on = forced ? 1 : 0; row.rng_row = 0u;
-    put_rules(s, dst, row);
-    // from here on the destination's previous utterance is gone (as a start on a running slot abandons it)
-    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = 0; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
-    s->text_len[dst] = from->text_len[src]; s->prefix[dst] = P; s->forced_on[dst] = forced ? 1 : 0;
-    Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
-    s->last = cx.st;
-    lk::SlotReset r;
-    r.slot = dst; r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off;
-    r.rows = s->rows; r.row = row; r.xs = m.xs; r.dm = d; r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len;
-    r.continual = from->tokens + (size_t)src * from->R * nq;   // the source's prompt tokens, in the source session's token row
-    r.forced = s->forced; r.forced_src = forced; r.logp = s->logp; r.V = V;
-    r.score = s->score;
-    cx.check(lk::launch_slot_reset(r, cx.st), "slot reset");
-    lk::PrefixImport c;
-    c.kc_src = from->m.kc; c.vc_src = from->m.vc; c.kc_dst = m.kc; c.vc_dst = m.vc;
-    c.lg0_src = from->lg0; c.lg_dst = m.lg; c.lg0_dst = s->lg0; c.pos_dst = m.pos;
-    c.NL = e->codec_lm.s.layers; c.d = d; c.V = V; c.S_src = from->S; c.Tcap_src = from->m.Tcap; c.S_dst = s->S; c.Tcap_dst = m.Tcap;
-    c.P = P; c.src = src; c.dst = dst;
-    cx.check(lk::launch_prefix_import(c, cx.st), "prefix import");
-    lk::Sample sm = slots_sampler(s);
-    sm.row0 = dst; sm.nrows = 1;
-    sm.launch_seq = nullptr;               // as slots_prefix: a one-row launch numbers no persistent step
-    cx.check(lk::launch_sample(sm, cx.st), "sampling");
-    if (cx.err) return 1;
-    s->state[dst] = SLOT_RUNNING;
-    return 0;
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s->slot[dst].rules, sampling_mode, slot_who(dst) + ": ")) return 1;
+    if (check_fits(slot_who(dst) + ": ", from->slot[src].prefix, max_length, s->R)) return 1;
+    return slots_from_prefix(s, dst, from, src, max_length, sampling_mode, sampling_k, sampling_p, seed, forced, stream);
 }
 
 int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_length, int sampling_mode, int sampling_k, float sampling_p,
@@ -1652,76 +1652,54 @@ int fc_laura_slots_fork(fc_laura_slots* s, int dst, int src, int keep, int max_l
     if (!s) return fail("null session");
     if (refuse_queued(s, "fork")) return 1;
     if (check_ready(s->e)) return 1;
-    const std::string range = " outside 0 .. " + std::to_string(s->S - 1);
-    if (dst < 0 || dst >= s->S) return fail("decoding session: slot " + std::to_string(dst) + range);
-    if (src < 0 || src >= s->S) return fail("decoding session: source slot " + std::to_string(src) + range);
-    if (s->state[src] != SLOT_RUNNING && s->state[src] != SLOT_DONE)
-        return fail("decoding session: source slot " + std::to_string(src) + " holds no utterance (" +
-                    (s->state[src] == SLOT_FAILED ? "failed" : "free or never started") + ")");
-    const int g = s->n_gen[src];
+    const std::string who = slot_who(dst) + ": ";
+    if (dst < 0 || dst >= s->S) return fail(slot_who(dst) + " outside 0 .. " + std::to_string(s->S - 1));
+    if (check_source(s, src, "decoding session: source slot " + std::to_string(src))) return 1;
+    const Slot& held = s->slot[src];
+    const int g = held.n_gen;
     if (keep < 0) keep = g;
     if (keep > g)
-        return fail("decoding session: slot " + std::to_string(dst) + ": keep " + std::to_string(keep) + " outside 0 .. " + std::to_string(g) +
-                    ", the tokens source slot " + std::to_string(src) + " has generated as last reported");
-    if (max_length < 1) max_length = s->max_len[src];
+        return fail(who + "keep " + std::to_string(keep) + " outside 0 .. " + std::to_string(g) + ", the tokens source slot " +
+                    std::to_string(src) + " has generated as last reported");
+    if (max_length < 1) max_length = held.max_len;
     if (max_length <= keep)
-        return fail("decoding session: slot " + std::to_string(dst) + ": max_length " + std::to_string(max_length) + " leaves nothing to generate after keep " +
-                    std::to_string(keep));
-    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s, dst, sampling_mode)) return 1;
-    const int P = s->prefix[src], cont_len = s->cont_len[src];
-    if (P + max_length > s->R)
-        return fail("decoding session: slot " + std::to_string(dst) + ": text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) +
-                    " exceeds the session's max_positions " + std::to_string(s->R));
-    if (keep == 0) return slots_from_prefix(s, dst, src, max_length, sampling_mode, sampling_k, sampling_p, seed, nullptr, stream);
-    const int forced_on = s->forced_on[src], forced_rows = s->max_len[src];
+        return fail(who + "max_length " + std::to_string(max_length) + " leaves nothing to generate after keep " + std::to_string(keep));
+    if (check_sampling(sampling_mode, sampling_k, sampling_p) || check_rules_mode(s->slot[dst].rules, sampling_mode, who)) return 1;
+    const int P = held.prefix, cont_len = held.cont_len;
+    if (check_fits(who, P, max_length, s->R)) return 1;
+    if (keep == 0) return slots_from_prefix(s, dst, s, src, max_length, sampling_mode, sampling_k, sampling_p, seed, nullptr, stream);
+    const int forced_on = held.forced_on, forced_rows = held.max_len;
     if (forced_on && max_length > forced_rows)
-        return fail("decoding session: slot " + std::to_string(dst) + ": source slot " + std::to_string(src) + " follows " + std::to_string(forced_rows) +
-                    " forced tokens, max_length " + std::to_string(max_length) + " goes past them");
-    fc_laura* e = s->e;
+        return fail(who + "source slot " + std::to_string(src) + " follows " + std::to_string(forced_rows) + " forced tokens, max_length " +
+                    std::to_string(max_length) + " goes past them");
     const StepMem& m = s->m;
-    const int d = e->codec_lm.s.d_model, V = e->vocab(), nq = e->arch.predict_nq;
-    // from here on the destination's previous utterance is gone; in place the slot's own utterance is kept up to token `keep`
-    s->state[dst] = SLOT_FAILED; s->n_gen[dst] = keep; s->cont_len[dst] = cont_len; s->max_len[dst] = max_length;
-    s->text_len[dst] = s->text_len[src]; s->prefix[dst] = P; s->forced_on[dst] = forced_on;
+    // in place the slot's own utterance is kept up to token `keep`
+    slot_restart(s, dst, held.text_len, cont_len, max_length, forced_on, keep);
     Ctx cx = make_ctx(1, (void*)m.pos, 0, stream);          // launches only: nothing is allocated
     s->last = cx.st;
-    if (dst != src) {
-        // positions [0, P + keep - 1): the prefix and kept tokens 0 .. keep - 2; token keep - 1 is the next step's input.  Sets pos[dst].
-        lk::PrefixCopy c;
-        c.kc = m.kc; c.vc = m.vc; c.lg = m.lg; c.lg0 = s->lg0; c.pos = m.pos;
-        c.NL = e->codec_lm.s.layers; c.S = s->S; c.d = d; c.Tcap = m.Tcap; c.V = V; c.P = P + keep - 1; c.src = src; c.n = 1; c.dst[0] = dst;
-        cx.check(lk::launch_prefix_copy(c, cx.st), "cache copy");
-    }
+    // positions [0, P + keep - 1): the prefix and kept tokens 0 .. keep - 2; token keep - 1 is the next step's input.  Sets pos[dst].
+    if (dst != src) prefix_import(s, cx, dst, s, src, P + keep - 1, "cache copy");
     const lk::Sample sm = slots_sampler(s);
     lk::SlotBranch r;
     r.S = s->S; r.dst = dst; r.src = src; r.keep = keep; r.P = P;
     r.n_gen = m.n_gen(); r.done = m.done(); r.step = m.step(); r.pos = m.pos; r.tok_off = s->tok_off; r.rows = s->rows;
-    r.row.mode = sampling_mode; r.row.ki = sampling_k; r.row.pf = sampling_p; r.row.max_steps = max_length; r.row.seed = seed;
-    r.row.forced_on = forced_on; r.row.rng_row = 0u;
-    put_rules(s, dst, r.row);
-    r.tokens = s->tokens; r.tok_stride = s->R; r.nq = nq; r.cont_len = cont_len; r.forced = s->forced; r.forced_rows = forced_rows;
-    r.logp = s->logp; r.V = V; r.score = s->score;
+    r.row = make_row(s->slot[dst].rules, sampling_mode, sampling_k, sampling_p, max_length, seed, forced_on);
+    r.tokens = s->tokens; r.tok_stride = s->R; r.nq = s->e->arch.predict_nq; r.cont_len = cont_len; r.forced = s->forced;
+    r.forced_rows = forced_rows; r.logp = s->logp; r.V = s->e->vocab(); r.score = s->score;
     r.cb = sm.cb; r.K = sm.K; r.D = sm.D; r.next_emb = sm.next_emb; r.emb_wt = sm.emb_wt; r.emb_bias = sm.emb_bias; r.emb_g = sm.emb_g;
     r.emb_b = sm.emb_b; r.dm = sm.dm; r.emb_relu = sm.emb_relu; r.xscale = sm.xscale; r.xs = sm.xs;
     cx.check(lk::launch_slot_branch(r, cx.st), "slot branch");
     if (cx.err) return 1;
-    s->state[dst] = SLOT_RUNNING;
+    s->slot[dst].state = SLOT_RUNNING;
     return 0;
 }
 
 int fc_laura_slots_set_rules(fc_laura_slots* s, int slot, float temperature, int min_length, float top_p, int repeat_window, int repeat_count) {
     if (!s) return fail("null session");
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
-    const std::string who = "decoding session: slot " + std::to_string(slot) + ": ";
-    if (!std::isfinite(temperature) || !(temperature > 0.f)) return fail(who + "temperature must be finite and > 0");
-    if (min_length < 0) return fail(who + "min_length " + std::to_string(min_length) + " < 0");
-    if (!(top_p >= 0.f && top_p <= 1.f)) return fail(who + "top_p must lie in (0, 1], or be 0 for none");
-    if (repeat_window < 0 || repeat_window > 256) return fail(who + "repeat_window " + std::to_string(repeat_window) + " outside 0 .. 256");
-    if (repeat_window > 0 && (repeat_count < 1 || repeat_count > repeat_window))
-        return fail(who + "repeat_count " + std::to_string(repeat_count) + " outside 1 .. repeat_window " + std::to_string(repeat_window));
-    lk::SampleRow& r = s->rules[slot];
-    r.temperature = temperature; r.min_length = min_length; r.top_p = top_p;
-    r.repeat_window = repeat_window; r.repeat_count = repeat_window > 0 ? repeat_count : 1;
+    const std::string why = rules_problem(temperature, min_length, top_p, repeat_window, repeat_count);
+    if (!why.empty()) return fail(slot_who(slot) + ": " + why);
+    s->slot[slot].rules = rules_row(temperature, min_length, top_p, repeat_window, repeat_count);
     return 0;
 }
 
@@ -1754,16 +1732,16 @@ int fc_laura_slots_move(fc_laura_slots* s, int n, const int32_t* src, const int3
             return fail("decoding session: move: source slot " + std::to_string(a) + (srcs >> a & 1ull ? " is named twice" : " is also a destination"));
         if (((srcs | dsts) >> b & 1ull) || a == b)
             return fail("decoding session: move: slot " + std::to_string(b) + (dsts >> b & 1ull ? " is named twice" : " is also a source"));
-        if (s->state[a] != SLOT_RUNNING && s->state[a] != SLOT_DONE)
-            return fail("decoding session: move: source slot " + std::to_string(a) + " holds no utterance (" +
-                        (s->state[a] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+        if (check_source(s, a, "decoding session: move: source slot " + std::to_string(a))) return 1;      // in range: whether it holds one
         srcs |= 1ull << a; dsts |= 1ull << b;
         lines.src[i] = a; lines.dst[i] = b;
     }
-    for (int i = 0; i < n; ++i)
-        if (s->state[dst[i]] != SLOT_FREE)
+    for (int i = 0; i < n; ++i) {
+        const int st = s->slot[dst[i]].state;
+        if (st != SLOT_FREE)
             return fail("decoding session: move: slot " + std::to_string(dst[i]) + " is not free (" +
-                        (s->state[dst[i]] == SLOT_RUNNING ? "running" : s->state[dst[i]] == SLOT_DONE ? "ended, not taken" : "failed") + ")");
+                        (st == SLOT_RUNNING ? "running" : st == SLOT_DONE ? "ended, not taken" : "failed") + ")");
+    }
     fc_laura* e = s->e;
     const StepMem& m = s->m;
     lk::SlotMoves mv;
@@ -1777,16 +1755,16 @@ int fc_laura_slots_move(fc_laura_slots* s, int n, const int32_t* src, const int3
     // from here on a failure leaves the named slots failed, as a start that fails half-way
     cx.check(lk::launch_slot_moves(mv, lines, cx.st), "slot move");
     if (cx.err) {
-        for (int i = 0; i < n; ++i) s->state[src[i]] = SLOT_FAILED;
+        for (int i = 0; i < n; ++i) s->slot[src[i]].state = SLOT_FAILED;
         return 1;
     }
     // the host mirror of every moved slot; the rules of the two rows change places
     for (int i = 0; i < n; ++i) {
-        const int a = src[i], b = dst[i];
-        s->state[b] = s->state[a]; s->cont_len[b] = s->cont_len[a]; s->max_len[b] = s->max_len[a]; s->n_gen[b] = s->n_gen[a];
-        s->text_len[b] = s->text_len[a]; s->prefix[b] = s->prefix[a]; s->forced_on[b] = s->forced_on[a];
-        std::swap(s->rules[a], s->rules[b]);
-        s->state[a] = SLOT_FREE; s->n_gen[a] = 0;
+        Slot &a = s->slot[src[i]], &b = s->slot[dst[i]];
+        const lk::SampleRow rules_b = b.rules;
+        b = a;
+        a.rules = rules_b;
+        a.state = SLOT_FREE; a.n_gen = 0;
     }
     return 0;
 }
@@ -1796,7 +1774,7 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
     if (check_ready(s->e)) return 1;
     if (n_steps < 1) return fail("decoding session: n_steps must be >= 1");
     bool any = false;
-    for (int i = 0; i < s->S; ++i) any = any || s->state[i] == SLOT_RUNNING;
+    for (const Slot& x : s->slot) any = any || x.state == SLOT_RUNNING;
     if (s->Q) any = s->submitted > s->finished + s->failed;             // a ticket waits or runs
     s->last_blocks = 0;
     if (!any) { slots_report(s, done_out, n_gen_out); return 0; }
@@ -1807,7 +1785,7 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
     if (s->elastic && s->S > 16) {
         int hi = 0;
         for (int i = 0; i < s->S; ++i)
-            if (s->state[i] == SLOT_RUNNING) hi = i;
+            if (s->slot[i].state == SLOT_RUNNING) hi = i;
         const int rows = std::min(s->S, 16 * (hi / 16 + 1));
         s->last_blocks = (rows + 15) / 16;
         if (rows < s->S) cut = rows;
@@ -1855,30 +1833,25 @@ int fc_laura_slots_step(fc_laura_slots* s, int n_steps, int32_t* done_out, int32
     if (ea == hipSuccess && qp)
         ea = hipMemcpyAsync(host + 2 * s->S + 1, qp->qw, (size_t)s->queue_words() * sizeof(int), hipMemcpyDeviceToHost, cx.st);
     if (ea == hipSuccess) ea = hipStreamSynchronize(cx.st);
-    if (qp) return queue_after_step(s, cx, ea, persist, done_out, n_gen_out);
+    if (qp) return queue_after_step(s, cx, ea, done_out, n_gen_out);
     const unsigned perr = (unsigned)host[2 * s->S];
     if (ea != hipSuccess) {
-        for (int i = 0; i < s->S; ++i)
-            if (s->state[i] == SLOT_RUNNING) s->state[i] = SLOT_FAILED;
+        for (Slot& x : s->slot)
+            if (x.state == SLOT_RUNNING) x.state = SLOT_FAILED;
         if (!cx.err) fail(std::string("decoding session: status read-back failed: ") + hipGetErrorString(ea));
         return 1;
     }
     if (perr) {
         // A hand-off of the persistent step timed out.  The residual rows are updated in place, so the step cannot be run again: every slot
-        // that was running is failed (start revives it), the session stays on the kernel chain, the event is counted.  Never a silent result.
-        for (int i = 0; i < s->S; ++i)
-            if (s->state[i] == SLOT_RUNNING) s->state[i] = SLOT_FAILED;
-        s->chain_only = true;
-        e->persist_fallbacks++;
-        if (s->gexec) { (void)hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
-        cx.check(lk::launch_fill_i32(m.done(), 1, s->S, cx.st), "done flags");
-        slots_reset_sync(s, cx);
-        if (hipStreamSynchronize(cx.st) != hipSuccess || cx.err) return fail("decoding session: reset after a timed-out step failed");
+        // that was running is failed (start revives it).
+        for (Slot& x : s->slot)
+            if (x.state == SLOT_RUNNING) x.state = SLOT_FAILED;
+        if (after_timeout(s, cx)) return 1;
     } else {
         for (int i = 0; i < s->S; ++i) {
-            if (s->state[i] != SLOT_RUNNING) continue;
-            s->n_gen[i] = host[i];
-            if (host[s->S + i]) s->state[i] = SLOT_DONE;
+            if (s->slot[i].state != SLOT_RUNNING) continue;
+            s->slot[i].n_gen = host[i];
+            if (host[s->S + i]) s->slot[i].state = SLOT_DONE;
         }
     }
     slots_report(s, done_out, n_gen_out);
@@ -1890,19 +1863,19 @@ int fc_laura_slots_take(fc_laura_slots* s, int slot, int64_t* tokens, int cap, i
     if (refuse_queued(s, "take")) return 1;
     if (check_ready(s->e)) return 1;
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
-    if (s->state[slot] == SLOT_FAILED) return fail("decoding session: slot " + std::to_string(slot) + " failed (a hand-off of the persistent step timed out); start it again");
-    if (s->state[slot] != SLOT_DONE) return fail("decoding session: slot " + std::to_string(slot) + " has not ended");
+    if (s->slot[slot].state == SLOT_FAILED) return fail("decoding session: slot " + std::to_string(slot) + " failed (a hand-off of the persistent step timed out); start it again");
+    if (s->slot[slot].state != SLOT_DONE) return fail("decoding session: slot " + std::to_string(slot) + " has not ended");
     if (!tokens || !len_out) return fail("null argument");
     const int nq = s->e->arch.predict_nq, V = s->e->vocab();
-    const int n = s->cont_len[slot] + s->n_gen[slot];
+    const int n = s->slot[slot].cont_len + s->slot[slot].n_gen;
     if (cap < n) return fail("decoding session: slot " + std::to_string(slot) + " holds " + std::to_string(n) + " tokens, room for " + std::to_string(cap));
     if (logp_out && !s->logp) return fail("decoding session: opened without per-step log-probabilities");
     if (n > 0) HIP_TRY(hipMemcpyAsync(tokens, s->tokens + (size_t)slot * s->R * nq, (size_t)n * nq * sizeof(int64_t), hipMemcpyDeviceToDevice, s->last));
     if (logp_out)
-        HIP_TRY(hipMemcpyAsync(logp_out, s->logp + (size_t)slot * s->R * V, (size_t)s->max_len[slot] * V * sizeof(float), hipMemcpyDeviceToDevice, s->last));
+        HIP_TRY(hipMemcpyAsync(logp_out, s->logp + (size_t)slot * s->R * V, (size_t)s->slot[slot].max_len * V * sizeof(float), hipMemcpyDeviceToDevice, s->last));
     HIP_TRY(hipStreamSynchronize(s->last));
     *len_out = n;
-    s->state[slot] = SLOT_FREE;
+    s->slot[slot].state = SLOT_FREE;
     return 0;
 }
 
@@ -1912,15 +1885,16 @@ int fc_laura_slots_score(fc_laura_slots* s, int slot, float* terms, int cap, int
     if (check_ready(s->e)) return 1;
     if (slot < 0 || slot >= s->S) return fail("decoding session: slot " + std::to_string(slot) + " outside 0 .. " + std::to_string(s->S - 1));
     if (!s->score) return fail("decoding session: slot " + std::to_string(slot) + ": the session was opened without scores");
-    if (s->state[slot] == SLOT_FAILED) return fail("decoding session: slot " + std::to_string(slot) + " failed (a hand-off of the persistent step timed out); start it again");
-    if (s->state[slot] != SLOT_DONE && s->state[slot] != SLOT_RUNNING) return fail("decoding session: slot " + std::to_string(slot) + " holds no utterance");
+    const Slot& x = s->slot[slot];
+    if (x.state == SLOT_FAILED) return fail("decoding session: slot " + std::to_string(slot) + " failed (a hand-off of the persistent step timed out); start it again");
+    if (!x.holds()) return fail("decoding session: slot " + std::to_string(slot) + " holds no utterance");
     if (!terms || !count_out || !end_out) return fail("null argument");
     if (cap < s->R) return fail("decoding session: slot " + std::to_string(slot) + ": a score row has " + std::to_string(s->R) + " terms, room for " + std::to_string(cap));
     HIP_TRY(hipMemcpyAsync(terms, s->score + (size_t)slot * s->R, (size_t)s->R * sizeof(float), hipMemcpyDeviceToHost, s->last));
     HIP_TRY(hipStreamSynchronize(s->last));
     // a slot that ended below its max_length ended on <eos>: that step ran and has a term, but no token
-    const bool ended = s->state[slot] == SLOT_DONE, eos = ended && s->n_gen[slot] < s->max_len[slot];
-    *count_out = s->n_gen[slot] + (eos ? 1 : 0);
+    const bool ended = x.state == SLOT_DONE, eos = ended && x.n_gen < x.max_len;
+    *count_out = x.n_gen + (eos ? 1 : 0);
     *end_out = eos ? 2 : (ended ? 1 : 0);
     return 0;
 }
@@ -1936,24 +1910,16 @@ int fc_laura_slots_submit(fc_laura_slots* s, int row, int max_length, int sampli
     const long long ticket = s->submitted;
     const std::string who = "decoding session: ticket " + std::to_string(ticket) + " (row " + std::to_string(row) + "): ";
     if (ticket >= 0x7fffffff) return fail(who + "the session has run out of ticket numbers");
-    if (row < 0 || row >= from->S) return fail(who + "row outside 0 .. " + std::to_string(from->S - 1) + " of the source session");
-    if (from->state[row] != SLOT_RUNNING && from->state[row] != SLOT_DONE)
-        return fail(who + "the row of the source session holds no prompt (" + (from->state[row] == SLOT_FAILED ? "failed" : "free or never started") + ")");
+    if (check_source(from, row, who + "row", " of the source session", who + "the row of the source session", " holds no prompt (")) return 1;
     if (max_length < 1) return fail(who + "max_length must be >= 1");
     if (const char* why = sampling_problem(sampling_mode, sampling_k, sampling_p)) return fail(who + why);
     // the rules, as fc_laura_slots_set_rules and the start that follows it check them
-    if (!std::isfinite(temperature) || !(temperature > 0.f)) return fail(who + "temperature must be finite and > 0");
-    if (min_length < 0) return fail(who + "min_length " + std::to_string(min_length) + " < 0");
-    if (!(top_p >= 0.f && top_p <= 1.f)) return fail(who + "top_p must lie in (0, 1], or be 0 for none");
-    if (repeat_window < 0 || repeat_window > 256) return fail(who + "repeat_window " + std::to_string(repeat_window) + " outside 0 .. 256");
-    if (repeat_window > 0 && (repeat_count < 1 || repeat_count > repeat_window))
-        return fail(who + "repeat_count " + std::to_string(repeat_count) + " outside 1 .. repeat_window " + std::to_string(repeat_window));
-    if (top_p > 0.f && sampling_mode != 2) return fail(who + "top_p applies with top-k sampling (an integer `sampling`) only");
-    if (repeat_window > 0 && sampling_mode == 0) return fail(who + "the repeat rule needs a drawing mode, not greedy");
-    const int P = from->prefix[row], cont_len = from->cont_len[row];
-    if (P + max_length > s->R)
-        return fail(who + "text_len + 2 + cont_len + max_length = " + std::to_string(P + max_length) + " exceeds the session's max_positions " +
-                    std::to_string(s->R));
+    const std::string why = rules_problem(temperature, min_length, top_p, repeat_window, repeat_count);
+    if (!why.empty()) return fail(who + why);
+    const lk::SampleRow rules = rules_row(temperature, min_length, top_p, repeat_window, repeat_count);
+    if (check_rules_mode(rules, sampling_mode, who)) return 1;
+    const int P = from->slot[row].prefix, cont_len = from->slot[row].cont_len;
+    if (check_fits(who, P, max_length, s->R)) return 1;
     if (s->submitted - s->collected >= s->Q)
         return fail(who + "all " + std::to_string(s->Q) + " result entries are in flight or uncollected (fc_laura_slots_collect frees them)");
     int entry = -1;
@@ -1962,10 +1928,7 @@ int fc_laura_slots_submit(fc_laura_slots* s, int row, int max_length, int sampli
     if (entry < 0) return fail(who + "no free result entry");
     lk::QueueTicket t;
     t.row = row; t.P = P; t.cont_len = cont_len; t.entry = entry;
-    t.srow.mode = sampling_mode; t.srow.ki = sampling_k; t.srow.pf = sampling_p; t.srow.max_steps = max_length; t.srow.seed = seed;
-    t.srow.forced_on = 0; t.srow.rng_row = 0u;
-    t.srow.temperature = temperature; t.srow.min_length = min_length; t.srow.top_p = top_p;
-    t.srow.repeat_window = repeat_window; t.srow.repeat_count = repeat_window > 0 ? repeat_count : 1;
+    t.srow = make_row(rules, sampling_mode, sampling_k, sampling_p, max_length, seed, 0);
     s->last = (hipStream_t)stream;
     const hipError_t el = lk::launch_queue_put(s->qp, t, (int)ticket, s->last);
     if (el != hipSuccess) return fail(who + "queue put: " + hipGetErrorString(el));

@@ -190,19 +190,7 @@ struct SlotReset {                  // see slot_reset_kernel
 };
 hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st);
 
-struct PrefixCopy {                 // see prefix_copy_kernel
-    float *kc = nullptr, *vc = nullptr;   // the session's caches [NL][S][d][Tcap], [NL][S][Tcap][d]
-    float* lg = nullptr;            // [S][V] logits of the step
-    float* lg0 = nullptr;           // [S][V] logits every slot's prefix ended with
-    int* pos = nullptr;             // device [S]
-    int NL = 0, S = 0, d = 0, Tcap = 0, V = 0;
-    int P = 0;                      // prefix positions (text_len + 2 + cont_len), known to the host
-    int src = 0, n = 0;             // source slot; destinations dst[0 .. n), 1 <= n <= S - 1, none of them src
-    int dst[15] = {};
-};
-hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st);
-
-struct PrefixImport {               // see prefix_import_kernel: prefix_copy_kernel between two sessions of one engine
+struct PrefixImport {               // see prefix_import_kernel: a slot's prefix into a slot of the same or another session of one engine
     const float *kc_src = nullptr, *vc_src = nullptr;   // the source session's caches [NL][S_src][d][Tcap_src], [NL][S_src][Tcap_src][d]
     float *kc_dst = nullptr, *vc_dst = nullptr;         // the destination session's, with S_dst and Tcap_dst
     const float* lg0_src = nullptr; // [S_src][V] logits every source slot's prefix ended with

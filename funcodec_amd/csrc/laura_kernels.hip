@@ -1725,131 +1725,98 @@ hipError_t launch_slot_reset(const SlotReset& r, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The prefix of slot `src` (its first P cache positions and the logits its prefix pass ended with) into n other slots: what a prefix
-// pass of the same prompt would leave there, bit for bit, for the price of a copy.  grid.y = layer; along x a layer's K vectors, then
-// its V vectors, then one block (layer 0 only) for the logits and the positions.  Every 16-byte source vector is loaded once and stored
-// n times; a block takes FC_PREFIX_VPT x 256 consecutive vectors, its loads in flight together.
-//   K [d][Tcap]: rows of pad4(P) floats (Tcap % 4 == 0: every row start is 16-byte aligned).  Columns [P, pad4(P)) carry whatever the
-//   source holds there (its own later positions).  A destination never reads a column it did not write itself: a step writes K and V at
-//   pos before its attention reads keys 0 .. pos -- on the kernel chain the QKV GEMV's scatter is the launch ahead of attn_step_kernel, in
-//   the persistent step an attention unit waits for the whole QKV phase (wait_phase(ph - 1)) -- and the first step of a destination runs
-//   at pos = P.  (A slot reused by `start` has its previous utterance's columns there in the same way.)
-//   V [Tcap][d]: the first P * d floats, contiguous (d % 4 == 0).
-// ---------------------------------------------------------------------------------------------------------------------
-#define FC_PREFIX_VPT 4
-__global__ __launch_bounds__(256) void prefix_copy_kernel(PrefixCopy c) {
-    const int l = blockIdx.y, tid = threadIdx.x;
-    const int kq = (c.P + 3) >> 2;                                    // vectors per K row: pad4(P) / 4
-    const int nK = c.d * kq, nV = (c.P * c.d) >> 2;
-    const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
-    int blk = blockIdx.x;
-    if (blk >= bK + bV) {                                             // the logits, the saved logits, the position
-        if (l != 0) return;
-        const float* s = c.lg0 + (size_t)c.src * c.V;
-        for (int v = tid; v < c.V; v += 256) {
-            const float x = s[v];
-            for (int i = 0; i < c.n; ++i) {
-                c.lg[(size_t)c.dst[i] * c.V + v] = x;
-                c.lg0[(size_t)c.dst[i] * c.V + v] = x;
-            }
-        }
-        for (int i = 0; i < c.n; ++i)
-            if (tid == i) c.pos[c.dst[i]] = c.P;
-        return;
-    }
-    const bool isK = blk < bK;
-    if (!isK) blk -= bK;
-    const size_t row = (size_t)c.d * c.Tcap;                         // floats of one slot's row of a layer, K and V alike
-    float* base = (isK ? c.kc : c.vc) + (size_t)l * c.S * row;
-    const int nvec = isK ? nK : nV;
-    const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
-    size_t off[FC_PREFIX_VPT];
-    f32x4 v[FC_PREFIX_VPT];
-#pragma unroll
-    for (int u = 0; u < FC_PREFIX_VPT; ++u) {
-        int i = i0 + 256 * u;
-        i = i < nvec ? i : nvec - 1;                                  // clamped: unconditional loads, predicated stores
-        off[u] = isK ? (size_t)(i / kq) * c.Tcap + 4 * (size_t)(i % kq) : 4 * (size_t)i;
-        v[u] = *(const f32x4*)(base + c.src * row + off[u]);
-    }
-    for (int k = 0; k < c.n; ++k) {
-        float* o = base + c.dst[k] * row;
-#pragma unroll
-        for (int u = 0; u < FC_PREFIX_VPT; ++u)
-            if (i0 + 256 * u < nvec) *(f32x4*)(o + off[u]) = v[u];
-    }
-}
-hipError_t launch_prefix_copy(const PrefixCopy& c, hipStream_t st) {
-    if (c.NL < 1 || c.S < 2 || c.n < 1 || c.n > c.S - 1 || c.n > 15 || c.src < 0 || c.src >= c.S) return hipErrorInvalidValue;
-    if (c.d < 4 || c.d % 4 || c.Tcap % 4 || c.P < 1 || ((c.P + 3) & ~3) > c.Tcap || c.V < 1) return hipErrorInvalidValue;
-    for (int i = 0; i < c.n; ++i)
-        if (c.dst[i] < 0 || c.dst[i] >= c.S || c.dst[i] == c.src) return hipErrorInvalidValue;
-    const int per = 256 * FC_PREFIX_VPT;
-    const int kq = ((c.P + 3) & ~3) >> 2;
-    const long long nK = (long long)c.d * kq, nV = ((long long)c.P * c.d) >> 2;
-    if (nK > 0x7fffffff || nV > 0x7fffffff) return hipErrorInvalidValue;
-    const int bK = (int)((nK + per - 1) / per), bV = (int)((nV + per - 1) / per);
-    hipLaunchKernelGGL(prefix_copy_kernel, dim3(bK + bV + 1, c.NL), dim3(256), 0, st, c);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// prefix_copy_kernel between two sessions of one engine: the prefix of slot `src` of the source session into slot `dst` of the
-// destination session, whose slot count and cache pitch may differ.  The same grid (grid.y = layer; along x a layer's K vectors, its V
-// vectors, one block for the logits and the position), the same FC_PREFIX_VPT x 256 16-byte vectors per block with their loads in flight
-// together; one destination.
-//   K: rows of pad4(P) floats from pitch Tcap_src to pitch Tcap_dst (both % 4 == 0).  Columns [P, pad4(P)) carry what the source holds
-//   there; the destination never reads them before it has written them (see prefix_copy_kernel).
-//   V: the first P * d floats of the slot's row, contiguous in both sessions.
+// The prefix of slot `src` of a source session (its first P cache positions and the logits its prefix pass ended with) into slot `dst`
+// of a destination session of the same engine: what a prefix pass of the same prompt would leave there, bit for bit, for the price of a
+// copy.  The two sessions may be one (fc_laura_slots_start_from, fork: dst != src then) or two whose slot counts and cache pitches
+// differ.  grid.y = layer; along x a layer's K vectors, then its V vectors, then one block (layer 0 only) for the logits and the
+// position.  A block takes FC_PREFIX_VPT x 256 consecutive 16-byte vectors, its loads in flight together (kv_chunk_copy).
+//   K [d][Tcap]: rows of pad4(P) floats from pitch Tcap_src to pitch Tcap_dst (both % 4 == 0: every row start is 16-byte aligned).
+//   Columns [P, pad4(P)) carry whatever the source holds there (its own later positions).  A destination never reads a column it did
+//   not write itself: a step writes K and V at pos before its attention reads keys 0 .. pos -- on the kernel chain the QKV GEMV's
+//   scatter is the launch ahead of attn_step_kernel, in the persistent step an attention unit waits for the whole QKV phase
+//   (wait_phase(ph - 1)) -- and the first step of a destination runs at pos = P.  (A slot reused by `start` has its previous
+//   utterance's columns there in the same way.)
+//   V [Tcap][d]: the first P * d floats of the slot's row, contiguous in both sessions (d % 4 == 0).
 //   lg0_src[src] into lg_dst[dst] and lg0_dst[dst]; pos_dst[dst] = P.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void prefix_import_kernel(PrefixImport c) {
-    const int l = blockIdx.y, tid = threadIdx.x;
-    const int kq = (c.P + 3) >> 2;
-    const int nK = c.d * kq, nV = (c.P * c.d) >> 2;
-    const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
-    int blk = blockIdx.x;
-    if (blk >= bK + bV) {
-        if (l != 0) return;
-        const float* s = c.lg0_src + (size_t)c.src * c.V;
-        for (int v = tid; v < c.V; v += 256) {
-            const float x = s[v];
-            c.lg_dst[(size_t)c.dst * c.V + v] = x;
-            c.lg0_dst[(size_t)c.dst * c.V + v] = x;
-        }
-        if (tid == 0) c.pos_dst[c.dst] = c.P;
-        return;
-    }
-    const bool isK = blk < bK;
-    if (!isK) blk -= bK;
-    const size_t row_s = (size_t)c.d * c.Tcap_src, row_d = (size_t)c.d * c.Tcap_dst;
-    const float* sb = (isK ? c.kc_src : c.vc_src) + ((size_t)l * c.S_src + c.src) * row_s;
-    float* db = (isK ? c.kc_dst : c.vc_dst) + ((size_t)l * c.S_dst + c.dst) * row_d;
+#define FC_PREFIX_VPT 4
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+// blocks of FC_PREFIX_VPT x 256 vectors that hold nvec vectors
+__host__ __device__ inline int prefix_blocks(int nvec) { return (nvec + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT); }
+
+// chunks of one layer's first P positions of one slot: its K vectors (d rows of pad4(P) / 4), then its V vectors
+__device__ __forceinline__ int kv_chunks(int d, int P) { return prefix_blocks(d * ((P + 3) >> 2)) + prefix_blocks((P * d) >> 2); }
+
+// Chunk `chunk` < kv_chunks(d, P) of that copy, by the 256 threads of a block: ks / vs and kd / vd are the slot's K and V rows of the
+// layer in the source and the destination, whose pitches are Tcap_s and Tcap_d.
+__device__ __forceinline__ void kv_chunk_copy(const float* ks, const float* vs, float* kd, float* vd, int Tcap_s, int Tcap_d, int d, int P,
+                                              int chunk, int tid) {
+    const int kq = (P + 3) >> 2;                                      // vectors per K row: pad4(P) / 4
+    const int nK = d * kq, nV = (P * d) >> 2, bK = prefix_blocks(nK);
+    const bool isK = chunk < bK;
+    const float* sb = isK ? ks : vs;
+    float* db = isK ? kd : vd;
     const int nvec = isK ? nK : nV;
-    const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
+    const int i0 = (isK ? chunk : chunk - bK) * 256 * FC_PREFIX_VPT + tid;
     size_t od[FC_PREFIX_VPT];
     f32x4 v[FC_PREFIX_VPT];
 #pragma unroll
     for (int u = 0; u < FC_PREFIX_VPT; ++u) {
         int i = i0 + 256 * u;
         i = i < nvec ? i : nvec - 1;                                  // clamped: unconditional loads, predicated stores
-        const size_t os = isK ? (size_t)(i / kq) * c.Tcap_src + 4 * (size_t)(i % kq) : 4 * (size_t)i;
-        od[u] = isK ? (size_t)(i / kq) * c.Tcap_dst + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+        const size_t os = isK ? (size_t)(i / kq) * Tcap_s + 4 * (size_t)(i % kq) : 4 * (size_t)i;
+        od[u] = isK ? (size_t)(i / kq) * Tcap_d + 4 * (size_t)(i % kq) : 4 * (size_t)i;
         v[u] = *(const f32x4*)(sb + os);
     }
 #pragma unroll
     for (int u = 0; u < FC_PREFIX_VPT; ++u)
         if (i0 + 256 * u < nvec) *(f32x4*)(db + od[u]) = v[u];
 }
+
+// a row of V logits into a slot's row of the step's logits and of the saved prefix logits (V need not be a multiple of 4: scalar)
+__device__ __forceinline__ void copy_logits(const float* __restrict__ s, float* lg, float* lg0, int V, int t0, int nth) {
+    for (int v = t0; v < V; v += nth) {
+        const float x = s[v];
+        lg[v] = x;
+        lg0[v] = x;
+    }
+}
+
+// nvec 16-byte vectors of zeros from `row` on (16-byte aligned)
+__device__ __forceinline__ void zero_row(float* row, int nvec, int t0, int nth) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int i = t0; i < nvec; i += nth) ((f32x4*)row)[i] = zero;
+}
+
+__global__ __launch_bounds__(256) void prefix_import_kernel(PrefixImport c) {
+    const int l = blockIdx.y, tid = threadIdx.x, blk = blockIdx.x;
+    if (blk >= kv_chunks(c.d, c.P)) {                                 // the logits, the saved logits, the position
+        if (l != 0) return;
+        copy_logits(c.lg0_src + (size_t)c.src * c.V, c.lg_dst + (size_t)c.dst * c.V, c.lg0_dst + (size_t)c.dst * c.V, c.V, tid, 256);
+        if (tid == 0) c.pos_dst[c.dst] = c.P;
+        return;
+    }
+    const size_t os = ((size_t)l * c.S_src + c.src) * c.d * c.Tcap_src, od = ((size_t)l * c.S_dst + c.dst) * c.d * c.Tcap_dst;
+    kv_chunk_copy(c.kc_src + os, c.vc_src + os, c.kc_dst + od, c.vc_dst + od, c.Tcap_src, c.Tcap_dst, c.d, c.P, blk, tid);
+}
+
+// the grid of that copy along x without its last block: false where the vectors of a layer cannot be counted in int
+static bool prefix_chunks(int d, int P, int* bK, int* bV) {
+    const long long nK = (long long)d * (((P + 3) & ~3) >> 2), nV = ((long long)P * d) >> 2;
+    if (nK > 0x7fffffff || nV > 0x7fffffff) return false;
+    *bK = prefix_blocks((int)nK); *bV = prefix_blocks((int)nV);
+    return true;
+}
+
 hipError_t launch_prefix_import(const PrefixImport& c, hipStream_t st) {
     if (c.NL < 1 || c.S_src < 1 || c.S_dst < 1 || c.src < 0 || c.src >= c.S_src || c.dst < 0 || c.dst >= c.S_dst) return hipErrorInvalidValue;
     if (c.d < 4 || c.d % 4 || c.Tcap_src % 4 || c.Tcap_dst % 4 || c.P < 1 || c.V < 1) return hipErrorInvalidValue;
     if (((c.P + 3) & ~3) > c.Tcap_src || ((c.P + 3) & ~3) > c.Tcap_dst) return hipErrorInvalidValue;
-    const int per = 256 * FC_PREFIX_VPT;
-    const int kq = ((c.P + 3) & ~3) >> 2;
-    const long long nK = (long long)c.d * kq, nV = ((long long)c.P * c.d) >> 2;
-    if (nK > 0x7fffffff || nV > 0x7fffffff) return hipErrorInvalidValue;
-    const int bK = (int)((nK + per - 1) / per), bV = (int)((nV + per - 1) / per);
+    // inside one session the copy must not alias: another slot, and the same pitch and slot count by construction
+    if (c.kc_src == c.kc_dst && (c.dst == c.src || c.S_src != c.S_dst || c.Tcap_src != c.Tcap_dst)) return hipErrorInvalidValue;
+    int bK = 0, bV = 0;
+    if (!prefix_chunks(c.d, c.P, &bK, &bV)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(prefix_import_kernel, dim3(bK + bV + 1, c.NL), dim3(256), 0, st, c);
     return hipGetLastError();
 }
@@ -1859,7 +1826,7 @@ hipError_t launch_prefix_import(const PrefixImport& c, hipStream_t st) {
 // there in place).  What the next step and the sampler's bookkeeping read, and nothing else:
 //   block 0: the LM's next input, next_emb[dst] and xs[dst], from kept token keep - 1 through embed_next -- the sampler's own tail, the
 //   same block shape and LDS -- and, one thread, the counters (n_gen = step = keep, done = 0, tok_off), dst's row of the sampling table.
-//   pos is the copy's (prefix_copy_kernel with P + keep - 1 positions) or, in place, set here.
+//   pos is the copy's (prefix_import_kernel with P + keep - 1 positions) or, in place, set here.
 //   blocks 1 ..: grid-stride over 16-byte vectors of the token row ([0, cont_len + keep) kept, zeros behind), the forced row (the
 //   source's) and the log-probability rows ([0, keep) kept, zeros up to max_steps: take(return_logp) relies on rows never run being
 //   zero) and, in a session with scores, the score row ([0, keep) kept, zeros behind to the row's end, so a branched utterance carries
@@ -1867,8 +1834,6 @@ hipError_t launch_prefix_import(const PrefixImport& c, hipStream_t st) {
 //   row: tok_stride % 4 == 0, so a row's length is a whole number of vectors and its start is 16-byte aligned.
 // A source that is running may be stepped again behind this launch: rows [0, keep) of its tables never change once written.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-
 // A float row of the branch: floats [0, ncopy) of `src` kept, zeros behind them up to vector nvec (16-byte vectors; both rows start
 // 16-byte aligned).  In place (same) the kept floats are not touched: the floats up to the next vector boundary one by one, whole
 // vectors behind.  Thread t0 of nth.
@@ -2018,8 +1983,6 @@ __global__ __launch_bounds__(64) void queue_turn_kernel(QueuePhase q, int claim)
     }
 }
 
-typedef long long __attribute__((ext_vector_type(2))) i64x2;
-
 __global__ __launch_bounds__(256) void queue_retire_copy_kernel(QueuePhase q) {
     const int n = q.qw[FC_QUEUE_NRETIRE];
     const int t0 = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
@@ -2044,11 +2007,9 @@ __global__ __launch_bounds__(256) void queue_claim_copy_kernel(QueuePhase q) {
     if ((int)blockIdx.y == q.NL) {                                    // the rows of slot_reset_kernel and the import's logits
         const int t0 = blockIdx.x * 256 + tid, nth = gridDim.x * 256;
         const size_t tok_row = (size_t)q.R * q.nq;
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         for (int c = 0; c < n; ++c) {
             const QueueClaim cl = q.claims[c];
-            f32x4* xs = (f32x4*)(q.xs + (size_t)cl.slot * q.dm);
-            for (int i = t0; i < (q.dm >> 2); i += nth) xs[i] = zero;
+            zero_row(q.xs + (size_t)cl.slot * q.dm, q.dm >> 2, t0, nth);
             const long long nprompt = (long long)cl.cont_len * q.nq;
             const int64_t* ps = q.tokens_src + (size_t)cl.row * q.R_src * q.nq;
             i64x2* td = (i64x2*)(q.tokens + (size_t)cl.slot * tok_row);
@@ -2058,47 +2019,18 @@ __global__ __launch_bounds__(256) void queue_claim_copy_kernel(QueuePhase q) {
                 if (2ll * i + 1 < nprompt) v.y = ps[2 * i + 1];
                 td[i] = v;
             }
-            if (q.score) {
-                f32x4* sc = (f32x4*)(q.score + (size_t)cl.slot * q.R);
-                for (int i = t0; i < (q.R >> 2); i += nth) sc[i] = zero;
-            }
-            const float* ls = q.lg0_src + (size_t)cl.row * q.V;
-            for (int v = t0; v < q.V; v += nth) {
-                const float x = ls[v];
-                q.lg[(size_t)cl.slot * q.V + v] = x;
-                q.lg0[(size_t)cl.slot * q.V + v] = x;
-            }
+            if (q.score) zero_row(q.score + (size_t)cl.slot * q.R, q.R >> 2, t0, nth);
+            copy_logits(q.lg0_src + (size_t)cl.row * q.V, q.lg + (size_t)cl.slot * q.V, q.lg0 + (size_t)cl.slot * q.V, q.V, t0, nth);
         }
         return;
     }
     const int l = blockIdx.y;
-    const size_t row_s = (size_t)q.d * q.R_src, row_d = (size_t)q.d * q.R;
     for (int c = 0; c < n; ++c) {
         const QueueClaim cl = q.claims[c];
-        const int kq = (cl.P + 3) >> 2;
-        const int nK = q.d * kq, nV = (cl.P * q.d) >> 2;
-        const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
-        for (int chunk = blockIdx.x; chunk < bK + bV; chunk += gridDim.x) {       // prefix_import_kernel's block `chunk` of layer l
-            const bool isK = chunk < bK;
-            const int blk = isK ? chunk : chunk - bK;
-            const float* sb = (isK ? q.kc_src : q.vc_src) + ((size_t)l * q.S_src + cl.row) * row_s;
-            float* db = (isK ? q.kc : q.vc) + ((size_t)l * q.S + cl.slot) * row_d;
-            const int nvec = isK ? nK : nV;
-            const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
-            size_t od[FC_PREFIX_VPT];
-            f32x4 v[FC_PREFIX_VPT];
-#pragma unroll
-            for (int u = 0; u < FC_PREFIX_VPT; ++u) {
-                int i = i0 + 256 * u;
-                i = i < nvec ? i : nvec - 1;                          // clamped: unconditional loads, predicated stores
-                const size_t os = isK ? (size_t)(i / kq) * q.R_src + 4 * (size_t)(i % kq) : 4 * (size_t)i;
-                od[u] = isK ? (size_t)(i / kq) * q.R + 4 * (size_t)(i % kq) : 4 * (size_t)i;
-                v[u] = *(const f32x4*)(sb + os);
-            }
-#pragma unroll
-            for (int u = 0; u < FC_PREFIX_VPT; ++u)
-                if (i0 + 256 * u < nvec) *(f32x4*)(db + od[u]) = v[u];
-        }
+        const size_t os = ((size_t)l * q.S_src + cl.row) * q.d * q.R_src, od = ((size_t)l * q.S + cl.slot) * q.d * q.R;
+        const int nchunk = kv_chunks(q.d, cl.P);
+        for (int chunk = blockIdx.x; chunk < nchunk; chunk += gridDim.x)          // prefix_import_kernel's block `chunk` of layer l
+            kv_chunk_copy(q.kc_src + os, q.vc_src + os, q.kc + od, q.vc + od, q.R_src, q.R, q.d, cl.P, chunk, tid);
     }
 }
 
@@ -2140,7 +2072,7 @@ hipError_t launch_sample_claims(const Sample& s, const QueuePhase& q, hipStream_
 // Slots of a decoding session moved to other rows (fc_laura_slots_move): after the launch row dst of every table line IS row src, and
 // row src is a free row (done = 1, as a taken one).  Nothing is computed: every word the session keeps per slot is copied.
 //   grid.y = layer l < NL: key / value positions [0, pos[src]] of the layer -- K rows of pad4(pos + 1) floats, the first (pos + 1) * d
-//                          floats of V -- in prefix_copy_kernel's chunks of FC_PREFIX_VPT x 256 16-byte vectors, the loads of a chunk
+//                          floats of V -- in kv_chunk_copy's chunks of FC_PREFIX_VPT x 256 16-byte vectors, the loads of a chunk
 //                          in flight together, clamped loads and predicated stores;
 //   grid.y = NL:           the token, forced-token (a slot that follows them), score and log-probability rows (the latter as far as the
 //                          slot's max_steps, what slot_reset_kernel zeroed and a take reads), the step's and the kept prefix logits, the
@@ -2208,31 +2140,11 @@ __global__ __launch_bounds__(256) void slot_move_kernel(SlotMoves m) {
     for (int c = 0; c < n; ++c) {
         const int src = m.table[1 + 2 * c], dst = m.table[2 + 2 * c];
         int P = m.pos[src] + 1;                                           // positions [0, pos]
-        P = P < 1 ? 1 : (P > m.Tcap ? m.Tcap : P);
-        const int kq = (P + 3) >> 2;                                      // pad4(P) <= Tcap (Tcap % 4 == 0)
-        const int nK = m.d * kq, nV = (P * m.d) >> 2;
-        const int bK = (nK + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT), bV = (nV + 256 * FC_PREFIX_VPT - 1) / (256 * FC_PREFIX_VPT);
-        for (int chunk = blockIdx.x; chunk < bK + bV; chunk += gridDim.x) {
-            const bool isK = chunk < bK;
-            const int blk = isK ? chunk : chunk - bK;
-            float* base = (isK ? m.kc : m.vc) + (size_t)l * m.S * row;
-            const float* sb = base + (size_t)src * row;
-            float* db = base + (size_t)dst * row;
-            const int nvec = isK ? nK : nV;
-            const int i0 = blk * 256 * FC_PREFIX_VPT + tid;
-            size_t off[FC_PREFIX_VPT];
-            f32x4 v[FC_PREFIX_VPT];
-#pragma unroll
-            for (int u = 0; u < FC_PREFIX_VPT; ++u) {
-                int i = i0 + 256 * u;
-                i = i < nvec ? i : nvec - 1;                              // clamped: unconditional loads, predicated stores
-                off[u] = isK ? (size_t)(i / kq) * m.Tcap + 4 * (size_t)(i % kq) : 4 * (size_t)i;
-                v[u] = *(const f32x4*)(sb + off[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < FC_PREFIX_VPT; ++u)
-                if (i0 + 256 * u < nvec) *(f32x4*)(db + off[u]) = v[u];
-        }
+        P = P < 1 ? 1 : (P > m.Tcap ? m.Tcap : P);                        // pad4(P) <= Tcap (Tcap % 4 == 0)
+        const size_t os = ((size_t)l * m.S + src) * row, od = ((size_t)l * m.S + dst) * row;
+        const int nchunk = kv_chunks(m.d, P);
+        for (int chunk = blockIdx.x; chunk < nchunk; chunk += gridDim.x)
+            kv_chunk_copy(m.kc + os, m.vc + os, m.kc + od, m.vc + od, m.Tcap, m.Tcap, m.d, P, chunk, tid);
     }
 }
 

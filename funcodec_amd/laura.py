@@ -8,6 +8,7 @@ libfuncodec_amd.so (HIP, gfx950).  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import logging
 from collections.abc import Mapping
@@ -497,6 +498,26 @@ class DecodeSlots:
             run.wait_stream(cur)
         return cur, run
 
+    @contextlib.contextmanager
+    def _launching(self):
+        """The stream a call's launches go to (``_run_stream``); the caller's stream waits for it when the call is out, refused or not."""
+        cur, run = self._run_stream()
+        try:
+            yield C.c_void_p(run.cuda_stream)
+        finally:
+            if run is not cur:
+                cur.wait_stream(run)
+
+    def _token_rows(self, what: str, name: str, t, rows: Optional[int] = None) -> torch.Tensor:
+        """`t` as int64 [n, nq] on the device, a leading 1 squeezed; `rows`: the n the call requires (None: any, "C")."""
+        nq = self.engine.spec.predict_nq
+        t = self.engine._dev(t, torch.int64)
+        if t.dim() == 3 and t.shape[0] == 1:
+            t = t[0]
+        if t.dim() != 2 or t.shape[1] != nq or (rows is not None and t.shape[0] != rows):
+            raise EngineError(f"{what}: {name} must be int64 [{'C' if rows is None else rows}, {nq}], got {tuple(t.shape)}")
+        return t
+
     def _refuse_queued(self, call: str) -> None:
         if self.queue is not None:
             raise EngineError(f"decoding session: {call}: a queued session is fed by its queue only (submit, collect)")
@@ -524,13 +545,9 @@ class DecodeSlots:
         mode, k, p = sampling_args(sampling)
         t, n, tp, w, r = (rules or SamplingRules()).args()
         ticket = C.c_int32(-1)
-        cur, run = self._run_stream()
-        try:
+        with self._launching() as stream:
             self.engine._check(self.lib.fc_laura_slots_submit(h, row, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), t, n, tp, w, r,
-                                                              C.byref(ticket), C.c_void_p(run.cuda_stream)))
-        finally:
-            if run is not cur:
-                cur.wait_stream(run)
+                                                              C.byref(ticket), stream))
         self._submitted += 1
         self._ticket_max_length[int(ticket.value)] = max_length
         return int(ticket.value)
@@ -632,13 +649,8 @@ class DecodeSlots:
         pairs = [(int(a), int(b)) for a, b in pairs]
         if not pairs:
             raise EngineError("decoding session: move: no moves")
-        cur, run = self._run_stream()
-        try:
-            self.engine._check(self.lib.fc_laura_slots_move(h, len(pairs), _i32([a for a, _ in pairs]), _i32([b for _, b in pairs]),
-                                                            C.c_void_p(run.cuda_stream)))
-        finally:
-            if run is not cur:
-                cur.wait_stream(run)
+        with self._launching() as stream:
+            self.engine._check(self.lib.fc_laura_slots_move(h, len(pairs), _i32([a for a, _ in pairs]), _i32([b for _, b in pairs]), stream))
         for a, b in pairs:
             self._max_length[b], self._n_gen[b], self._status[b] = self._max_length[a], self._n_gen[a], self._status[a]
             self._n_gen[a], self._status[a] = 0, 0
@@ -660,7 +672,7 @@ class DecodeSlots:
         int64 [max_length, nq], rules a ``SamplingRules`` (None: neutral).  A running slot's utterance is abandoned.  A refused call
         changes nothing for any slot."""
         self._refuse_queued("start")
-        eng, nq = self.engine, self.engine.spec.predict_nq
+        eng = self.engine
         h = self._handle()
         text_outs = eng._dev(text_outs, torch.float32)
         if text_outs.dim() == 2:
@@ -674,19 +686,11 @@ class DecodeSlots:
         text = text_outs[0, :text_len].contiguous()
         cont_len = 0
         if continual is not None:
-            continual = eng._dev(continual, torch.int64)
-            if continual.dim() == 3 and continual.shape[0] == 1:
-                continual = continual[0]
-            if continual.dim() != 2 or continual.shape[1] != nq:
-                raise EngineError(f"decode session start: slot {slot}: continual must be int64 [C, {nq}], got {tuple(continual.shape)}")
+            continual = self._token_rows(f"decode session start: slot {slot}", "continual", continual)
             cont_len = continual.shape[0]
             continual = continual.contiguous() if cont_len else None
         if forced is not None:
-            forced = eng._dev(forced, torch.int64)
-            if forced.dim() == 3 and forced.shape[0] == 1:
-                forced = forced[0]
-            if tuple(forced.shape) != (max_length, nq):
-                raise EngineError(f"decode session start: slot {slot}: forced must be int64 [{max_length}, {nq}], got {tuple(forced.shape)}")
+            forced = self._token_rows(f"decode session start: slot {slot}", "forced", forced, max_length)
         mode, k, p = sampling_args(sampling)
         self._set_rules(slot, rules)
         need = int(self.lib.fc_laura_slots_workspace_bytes(h, text_len, cont_len))
@@ -694,14 +698,9 @@ class DecodeSlots:
             eng._ws = None
             eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         ws = eng._ws
-        cur, run = self._run_stream()
-        try:
+        with self._launching() as stream:
             eng._check(self.lib.fc_laura_slots_start(h, int(slot), _ptr(text), text_len, _ptr(continual), cont_len, max_length, mode, k, p,
-                                                     int(seed) & (2 ** 64 - 1), _ptr(forced), _ptr(ws), ws.numel(),
-                                                     C.c_void_p(run.cuda_stream)))
-        finally:
-            if run is not cur:
-                cur.wait_stream(run)
+                                                     int(seed) & (2 ** 64 - 1), _ptr(forced), _ptr(ws), ws.numel(), stream))
         self._max_length[int(slot)] = max_length
         self.prefix_passes += 1
 
@@ -763,11 +762,7 @@ class DecodeSlots:
             texts.append(t[:text_len])
             c = r["continual"]
             if c is not None:
-                c = eng._dev(c, torch.int64)
-                if c.dim() == 3 and c.shape[0] == 1:
-                    c = c[0]
-                if c.dim() != 2 or c.shape[1] != nq:
-                    raise EngineError(f"decode session start_many: slot {slot}: continual must be int64 [C, {nq}], got {tuple(c.shape)}")
+                c = self._token_rows(f"decode session start_many: slot {slot}", "continual", c)
             conts.append(c)
         L = max(t.shape[0] for t in texts)
         Cmax = max((c.shape[0] for c in conts if c is not None), default=0)
@@ -792,13 +787,9 @@ class DecodeSlots:
         mode_a, k_a = _i32([m[0] for m in modes]), _i32([m[1] for m in modes])
         p_a = (C.c_float * n)(*[m[2] for m in modes])
         seed_a = (C.c_uint64 * n)(*[int(r["seed"]) & (2 ** 64 - 1) for _, r in rows])
-        cur, run = self._run_stream()
-        try:
+        with self._launching() as stream:
             eng._check(self.lib.fc_laura_slots_start_many(h, n, slots_a, _ptr(text), tl_a, L, _ptr(cont), cl_a, Cmax, ml_a, mode_a, k_a, p_a,
-                                                          seed_a, _ptr(ws), ws.numel(), C.c_void_p(run.cuda_stream)))
-        finally:
-            if run is not cur:
-                cur.wait_stream(run)
+                                                          seed_a, _ptr(ws), ws.numel(), stream))
         for slot, r in rows:
             self._max_length[slot] = int(r["max_length"])
         self.prefix_passes += 1
@@ -812,7 +803,7 @@ class DecodeSlots:
         bit, the slot that ``start`` gives for the same prompt and parameters; `src` is not disturbed, may be running or ended (not yet
         taken), and may itself come from a start_from.  A running `dst` is abandoned.  A refused call changes nothing for any slot."""
         self._refuse_queued("start_from")
-        eng, nq = self.engine, self.engine.spec.predict_nq
+        eng = self.engine
         h = self._handle()
         dst, src = int(dst), int(src)
         if source is self:
@@ -827,24 +818,16 @@ class DecodeSlots:
             max_length = held._max_length[src]
         max_length = int(max_length)
         if forced is not None:
-            forced = eng._dev(forced, torch.int64)
-            if forced.dim() == 3 and forced.shape[0] == 1:
-                forced = forced[0]
-            if tuple(forced.shape) != (max_length, nq):
-                raise EngineError(f"decode session start_from: slot {dst}: forced must be int64 [{max_length}, {nq}], got {tuple(forced.shape)}")
+            forced = self._token_rows(f"decode session start_from: slot {dst}", "forced", forced, max_length)
         mode, k, p = sampling_args(sampling)
         self._set_rules(dst, rules)
-        cur, run = self._run_stream()
-        try:
+        with self._launching() as stream:
             if source is None:
                 eng._check(self.lib.fc_laura_slots_start_from(h, dst, src, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), _ptr(forced),
-                                                              C.c_void_p(run.cuda_stream)))
+                                                              stream))
             else:                           # the prompt lies in another session of this engine; both sessions run on this stream
                 eng._check(self.lib.fc_laura_slots_start_from_session(h, dst, source._handle(), src, max_length, mode, k, p,
-                                                                      int(seed) & (2 ** 64 - 1), _ptr(forced), C.c_void_p(run.cuda_stream)))
-        finally:
-            if run is not cur:
-                cur.wait_stream(run)
+                                                                      int(seed) & (2 ** 64 - 1), _ptr(forced), stream))
         self._max_length[dst] = max_length
 
     @_on_device
@@ -872,13 +855,8 @@ class DecodeSlots:
         max_length = 0 if max_length is None else int(max_length)         # 0: the source's, which the library knows
         mode, k, p = sampling_args(sampling)
         self._set_rules(dst, rules)
-        cur, run = self._run_stream()
-        try:
-            self.engine._check(self.lib.fc_laura_slots_fork(h, dst, src, keep, max_length, mode, k, p, int(seed) & (2 ** 64 - 1),
-                                                            C.c_void_p(run.cuda_stream)))
-        finally:
-            if run is not cur:
-                cur.wait_stream(run)
+        with self._launching() as stream:
+            self.engine._check(self.lib.fc_laura_slots_fork(h, dst, src, keep, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), stream))
         self._max_length[dst] = max_length or self._max_length[src]
         self._n_gen[dst] = self._n_gen[src] if keep < 0 else keep
 
@@ -901,13 +879,9 @@ class DecodeSlots:
     def step(self, n: int = 16) -> Dict[int, str]:
         """n decoding steps for every running slot; {slot: "running" | "done" | "failed"} for every slot that holds an utterance."""
         h = self._handle()
-        cur, run = self._run_stream()
         before = self.engine.persistent_step_fallbacks
-        try:
-            self.engine._check(self.lib.fc_laura_slots_step(h, int(n), self._status, self._n_gen, C.c_void_p(run.cuda_stream)))
-        finally:
-            if run is not cur:
-                cur.wait_stream(run)
+        with self._launching() as stream:
+            self.engine._check(self.lib.fc_laura_slots_step(h, int(n), self._status, self._n_gen, stream))
         if self.queue is not None:                  # the queue's counters and the slots' tickets, out of the same read-back
             self._queue_status()
         if self.engine.persistent_step_fallbacks != before:

@@ -115,19 +115,19 @@ def part_b(name, spec, say):
         for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
             with open(path) as f:
                 for row in csv.DictReader(f):
-                    for k in ("prefix_copy_kernel", "slot_branch_kernel"):
+                    for k in ("prefix_import_kernel", "slot_branch_kernel"):
                         if k in row["Name"]:
                             rows[k] = row
-        if set(rows) != {"prefix_copy_kernel", "slot_branch_kernel"} or any(int(v["Calls"]) != COPY_CALLS for v in rows.values()):
+        if set(rows) != {"prefix_import_kernel", "slot_branch_kernel"} or any(int(v["Calls"]) != COPY_CALLS for v in rows.values()):
             raise RuntimeError(f"no statistics for {COPY_CALLS} launches of both kernels: {rows}")
     finally:
         shutil.rmtree(out, ignore_errors=True)
     s = spec.codec_lm
     pos = P + COPY_KEEP - 1
     nbytes = 2 * s.layers * s.d_model * pos * 4 * 2
-    row = rows["prefix_copy_kernel"]
+    row = rows["prefix_import_kernel"]
     avg = float(row["AverageNs"])
-    say(f"  (b) prefix_copy_kernel, keep = {COPY_KEEP}, {pos} positions: {COPY_CALLS} launches, average {avg / 1e3:.2f} us "
+    say(f"  (b) prefix_import_kernel, keep = {COPY_KEEP}, {pos} positions: {COPY_CALLS} launches, average {avg / 1e3:.2f} us "
         f"(min {int(row['MinNs']) / 1e3:.2f}, max {int(row['MaxNs']) / 1e3:.2f}); {nbytes} bytes from shapes "
         f"(2 * {s.layers} * {s.d_model} * {pos} * 4 * 2) = {nbytes / avg / 1e3:.2f} TB/s (rocprofv3 --kernel-trace --stats, own run)")
     row = rows["slot_branch_kernel"]

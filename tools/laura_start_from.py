@@ -179,16 +179,16 @@ def part_c(name, spec, cont_len, say):
         rows = []
         for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
             with open(path) as f:
-                rows += [row for row in csv.DictReader(f) if "prefix_copy_kernel" in row["Name"]]
+                rows += [row for row in csv.DictReader(f) if "prefix_import_kernel" in row["Name"]]
         if len(rows) != 1 or int(rows[0]["Calls"]) != COPY_CALLS:
-            raise RuntimeError(f"no statistics for {COPY_CALLS} prefix_copy_kernel launches: {rows}")
+            raise RuntimeError(f"no statistics for {COPY_CALLS} prefix_import_kernel launches: {rows}")
     finally:
         shutil.rmtree(out, ignore_errors=True)
     row = rows[0]
     s = spec.codec_lm
     nbytes = 2 * s.layers * s.d_model * P * 4 * (1 + 1)
     avg = float(row["AverageNs"])
-    say(f"  (c) prefix_copy_kernel, P = {P:3d}, n = 1: {COPY_CALLS} launches, average {avg / 1e3:.2f} us "
+    say(f"  (c) prefix_import_kernel, P = {P:3d}, n = 1: {COPY_CALLS} launches, average {avg / 1e3:.2f} us "
         f"(min {int(row['MinNs']) / 1e3:.2f}, max {int(row['MaxNs']) / 1e3:.2f}); {nbytes} bytes from shapes "
         f"(2 * {s.layers} * {s.d_model} * {P} * 4 * 2) = {nbytes / avg:.1f} GB/s (rocprofv3 --kernel-trace --stats, own run)")
 

@@ -82,6 +82,8 @@ SYMBOLS = {
     "fc_encode_decode_ragged": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     # per-row stage counts of the calls that follow (host int32 [B], or None to clear)
     "fc_engine_set_row_nq": (C.c_int, [_P, _P, C.c_int, _P]),
+    "fc_engine_set_rvq_beam": (C.c_int, [_P, C.c_int, _P]),
+    "fc_rvq_encode_beam": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "fc_rvq_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_q0_source_frames": (C.c_int, [C.c_int, _P]),
     "fc_layer_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

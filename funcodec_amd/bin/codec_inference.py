@@ -48,6 +48,7 @@ class Speech2Token:
             sampling_rate: int = 24_000,
             bit_width: int = 24_000,
             check_status: bool = True,
+            rvq_beam: int = 1,
     ):
         if dtype not in ("float16", "float32", "float64"):
             raise ValueError(f"dtype must be float16, float32 or float64, got {dtype!r}")
@@ -70,6 +71,10 @@ class Speech2Token:
         # that check, like the reference raises in line.  check_status=False keeps calls asynchronous (the caller then uses
         # model.engine.check_status() itself).
         self.check_status = check_status
+        # not in the reference: the width of the quantiser's search over its stages in the two encoding modes (1: the reference's greedy
+        # quantiser); a call's own rvq_beam= goes first.  Refused here, before any call, for a model that cannot take it.
+        from ..engine import rvq_beam_width
+        self.rvq_beam = rvq_beam_width(model.arch, rvq_beam)
 
     @torch.no_grad()
     def __call__(
@@ -81,21 +86,27 @@ class Speech2Token:
             use_scale: bool = True,
             run_mod: str = "inference",
             speech_lengths: Optional[Union[torch.Tensor, np.ndarray]] = None,
+            rvq_beam: Optional[int] = None,
     ):
         """Returns (code_indices, code_embeddings, recon_speech, sub_quants) like the reference (:86-134).
 
         speech_lengths [B] (not in the reference; default None = the reference's behaviour): samples per row (frames per row for the
         two decode modes).  With it every row is computed as if it were alone in the batch, cut at its own length, zeros behind
-        (EncodecMI355X.inference)."""
+        (EncodecMI355X.inference).
+
+        rvq_beam (not in the reference; default None = the instance's, whose default 1 is the reference's greedy quantiser): 2, 4 or 8
+        hypotheses per frame through the quantiser's stages in the modes that encode; the two decode modes do not quantise."""
+        rvq_beam = getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam       # (an instance built around a ready model has none)
         if ppg is not None:
             raise NotImplementedError("ppg conditioning (codec_semantic_aug) is outside the hot-path scope")
         if isinstance(speech, np.ndarray):
             speech = torch.from_numpy(speech)
         speech = speech.to(self.model.device)
         if run_mod == "inference":
-            ret = self.model.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, speech_lengths=speech_lengths)
+            ret = self.model.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, speech_lengths=speech_lengths,
+                                       rvq_beam=rvq_beam)
         elif run_mod == "encode":
-            ret = self.model.inference_encoding(speech, need_recon=False, bit_width=bit_width, speech_lengths=speech_lengths)
+            ret = self.model.inference_encoding(speech, need_recon=False, bit_width=bit_width, speech_lengths=speech_lengths, rvq_beam=rvq_beam)
         elif run_mod == "decode_emb":
             ret = self.model.inference_decoding_emb(speech, token_lengths=speech_lengths)
         else:
@@ -119,17 +130,19 @@ class Speech2Token:
         return (ret["code_indices"], ret["code_embeddings"], ret["recon_speech"], ret["sub_quants"])
 
     def open_stream(self, batch: int = 1, n_q: Optional[int] = None, scale=None, max_chunk: Optional[int] = None,
-                    max_frames: Optional[int] = None, graph: bool = False):
+                    max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None):
         """A streaming session of the loaded (causal) model: funcodec_amd.stream.CodecStream.  Not in the reference, whose
         `streaming=` keyword selects a data iterator; that keyword keeps its meaning here (accepted, unused).  graph: replay steady
         pushes as captured HIP graphs (results are then copies)."""
-        return self.model.open_stream(batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames, graph=graph)
+        return self.model.open_stream(batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames, graph=graph,
+                                      rvq_beam=getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam)
 
     def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
-                   graph: bool = False):
+                   graph: bool = False, rvq_beam: Optional[int] = None):
         """A slot session of the loaded (causal) model: funcodec_amd.stream.StreamSlots, independent utterances sharing every push
         (max_frames: the bound a transformer bottleneck needs, as for open_stream; graph: as for open_stream)."""
-        return self.model.open_slots(slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames, graph=graph)
+        return self.model.open_slots(slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames, graph=graph,
+                                     rvq_beam=getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam)
 
     @staticmethod
     def from_pretrained(model_tag: Optional[str] = None, **kwargs: Optional[Any]):
@@ -200,6 +213,7 @@ def inference_modelscope(
     my_model = Speech2Token.from_pretrained(model_tag=model_tag, config_file=config_file, model_file=model_file,
                                             device="cuda", dtype=dtype, streaming=streaming,
                                             sampling_rate=sampling_rate, bit_width=bit_width,
+                                            rvq_beam=int(kwargs.get("rvq_beam") or 1),
                                             check_status=False)      # ONE status check per batch, below (not one per call + one per batch)
 
     def _forward(data_path_and_name_and_type=None, raw_inputs=None, output_dir_v2: Optional[str] = None,
@@ -401,6 +415,9 @@ def get_parser():
     # not in the reference: every utterance of a batch is coded as if it were alone (its own volume scale, normalisation statistics and
     # end padding), so that --batch_size N writes what --batch_size 1 writes
     g.add_argument("--length_aware", type=_str2bool, default=False)
+    # not in the reference: hypotheses per frame through the quantiser's stages (1: the reference's greedy quantiser); same files, no frame
+    # coded worse
+    g.add_argument("--rvq_beam", type=int, choices=[1, 2, 4, 8], default=1)
     return p
 
 

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libfuncodec_amd.so")
 OBJ_DIR = os.path.join(CSRC, "_obj")
-HEADERS = ["kernels.h", "device_common.h", "conv_kernel.h", "laura_kernels.h", "seq_kernels.h", "stream_kernels.h", "ragged_kernels.h", "slots_kernels.h", os.path.join("..", "..", "include", "funcodec_amd.h")]
+HEADERS = ["kernels.h", "device_common.h", "conv_kernel.h", "laura_kernels.h", "seq_kernels.h", "stream_kernels.h", "ragged_kernels.h", "slots_kernels.h", "rvq_beam_kernels.h", os.path.join("..", "..", "include", "funcodec_amd.h")]
 
 
 def sources():
@@ -23,7 +23,7 @@ def sources():
     tiles = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "conv_tile*_*.hip")))
     heavy = [t for t in tiles if t.startswith("conv_tileq_") and "_m" not in t] + [t for t in tiles if t.endswith("_m01.hip")]
     rest = [t for t in tiles if t not in heavy]
-    return heavy + ["kernels.hip", "laura_persist.hip", "laura_kernels.hip", "freq_kernels.hip", "seq_kernels.hip", "seqstream_kernels.hip", "stream_kernels.hip", "ragged_kernels.hip", "slots_kernels.hip", "engine.hip", "laura.hip"] + rest
+    return heavy + ["kernels.hip", "rvq_beam_kernels.hip", "laura_persist.hip", "laura_kernels.hip", "freq_kernels.hip", "seq_kernels.hip", "seqstream_kernels.hip", "stream_kernels.hip", "ragged_kernels.hip", "slots_kernels.hip", "engine.hip", "laura.hip"] + rest
 
 
 def _hipcc() -> str:

@@ -15,6 +15,7 @@
 
 #include "../../include/funcodec_amd.h"
 #include "kernels.h"
+#include "rvq_beam_kernels.h"
 #include "laura_kernels.h"
 #include "ragged_kernels.h"
 #include "seq_kernels.h"
@@ -115,6 +116,7 @@ int ceil_div_i(int a, int b) { return (a + b - 1) / b; }
 const char* kLstmPersistClass = "lstm_persist_kernel<NS> (whole recurrence of one SLSTM block, one launch)";
 const char* kLstmWaveClass = "lstm_wave_kernel<NS> (whole recurrence of one SLSTM block: T + L - 1 launches incl. gaps)";
 const char* kRvqClass = "rvq_encode_kernel<D, RS> (all stages of the residual quantiser)";
+const char* kRvqBeamClass = "rvq_beam_kernel<D, W> (beam search over the stages of the residual quantiser)";
 
 }  // namespace
 
@@ -162,6 +164,7 @@ struct fc_engine {
     std::vector<int32_t> row_nq;
     int* row_nq_dev = nullptr;
     size_t row_nq_cap = 0;
+    int rvq_beam = 1;                        // width of the quantiser's search over the stages for the calls that follow (fc_engine_set_rvq_beam); 1: greedy
     bool lstm_persist_ok = true;             // cleared after a grid-barrier timeout: later calls take the per-step launch path
     int persist_checked_B = -1; bool persist_checked_val = false;
     // optional event timing
@@ -208,9 +211,11 @@ struct Session {
         const void* ws = nullptr; size_t ws_bytes = 0;
         const void* stream = nullptr;
         const void* nq_table = nullptr; int nq_rows = 0;      // per-row stage counts: null / 0 when none are set
+        int rvq_beam = 1;                           // width of the quantiser's search (fc_engine_set_rvq_beam): more launches above 1
         bool operator==(const GraphKey& o) const {
             return form == o.form && width == o.width && parity == o.parity && n_q == o.n_q && use_scale == o.use_scale && ptr == o.ptr && ws == o.ws &&
-                   ws_bytes == o.ws_bytes && stream == o.stream && nq_table == o.nq_table && nq_rows == o.nq_rows;
+                   ws_bytes == o.ws_bytes && stream == o.stream && nq_table == o.nq_table && nq_rows == o.nq_rows &&
+                   rvq_beam == o.rvq_beam;
         }
     };
     struct Graph { GraphKey key; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
@@ -1957,6 +1962,15 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
         return fc::launch_rvq_encode(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, e->cb_frag, e->enorm, codes, quant_c, qbdt_c, sub_quants, Tf, cx.st, q0map,
                                      nq_rows);
     });
+    if (e->rvq_beam > 1) {      // fc_engine_set_rvq_beam: the search over the stages rewrites the greedy codes in place; everything else from the final codes
+        cx.launch("rvq beam", "", [] { return kRvqBeamClass; }, rvq_fl * e->rvq_beam, 0.0, [&] {
+            return fc::launch_rvq_beam(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->rvq_beam, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, Tf,
+                                       cx.st, nq_rows);
+        });
+        cx.launch("rvq beam sum", "", [&] {
+            return fc::launch_rvq_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf, cx.st, nq_rows);
+        });
+    }
     float* qbdt = qbdt_c;
     if (e->q_proj) {       // output_proj (costume_quantizer.py:92-94): decoder input [B][D][Tf] and the returned embeddings [B][Tf][D]
         fc::Src qs; qs.ptr = qbdt_c; qs.used = 1;
@@ -2373,6 +2387,7 @@ Session::GraphKey graph_key(const Session& s, int form, int width, int parity, i
     k.form = form; k.width = width; k.parity = parity & 1; k.n_q = s.n_q; k.use_scale = use_scale ? 1 : 0;
     k.ptr = ptr; k.ws = ws; k.ws_bytes = ws_bytes; k.stream = stream;
     k.nq_table = row_nq_table(s.e); k.nq_rows = (int)s.e->row_nq.size();
+    k.rvq_beam = s.e->rvq_beam;
     return k;
 }
 
@@ -3040,6 +3055,49 @@ int fc_engine_set_row_nq(fc_engine* e, const int32_t* n_q_rows, int B, void* str
         er != hipSuccess) {
         e->row_nq.clear();
         return fail(std::string("fc_engine_set_row_nq: copy of the table: ") + hipGetErrorString(er));
+    }
+    return 0;
+}
+
+namespace {
+// why the quantiser's beam search is refused for this engine and width (before any launch), or 0
+int rvq_beam_check(const fc_engine* e, int width, const char* who) {
+    if (!fc::rvq_beam_width_ok(width) && width != 1)
+        return fail(std::string(who) + ": rvq_beam: a width is one of 1, 2, 4, 8, got " + std::to_string(width));
+    if (width > 1 && e->arch.q0_ds_ratio > 1)
+        return fail(std::string(who) + ": rvq_beam: quantizer_conf.q0_ds_ratio > 1 shares stage 0 between frame pairs, so the frames are not independent; "
+                    "the search over the stages is per frame");
+    return 0;
+}
+}  // namespace
+
+int fc_engine_set_rvq_beam(fc_engine* e, int width, void* stream) {
+    (void)stream;
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (rvq_beam_check(e, width, "fc_engine_set_rvq_beam")) return 1;
+    // outside any capture: a graph-replay session captures the launches only
+    if (width > 1) HIP_TRY(fc::rvq_beam_prepare(e->cdim(), width));
+    e->rvq_beam = width;
+    return 0;
+}
+
+int fc_rvq_encode_beam(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, int64_t* paths, float* errors,
+                       void* stream) {
+    if (check_ready(e)) return 1;
+    if (!x || !codes || N <= 0) return fail("bad argument");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (rvq_beam_check(e, width, "fc_rvq_encode_beam")) return 1;
+    if (width == 1 && (paths || errors)) return fail("fc_rvq_encode_beam: paths and errors are those of a search: rvq_beam above 1");
+    const int B = e->row_nq.empty() ? 1 : (int)e->row_nq.size(), Tf = N / B;
+    if (N % B != 0) return fail("fc_rvq_encode_beam: with per-row stage counts for " + std::to_string(B) + " rows, N must be a multiple of that");
+    if (row_nq_check(e, B, n_q)) return 1;
+    const int Dc = e->cdim(), K = e->arch.codebook_size;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(fc::launch_rvq_encode(x, N, Dc, K, n_q, e->cb, e->cb_frag, e->enorm, codes, quantized, nullptr, nullptr, Tf, st, nullptr, row_nq_table(e)));
+    if (width > 1) {
+        HIP_TRY(fc::launch_rvq_beam(x, N, Dc, K, n_q, width, e->cb, e->cb_frag, e->enorm, codes, paths, errors, Tf, st, row_nq_table(e)));
+        if (quantized) HIP_TRY(fc::launch_rvq_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, st, row_nq_table(e)));
     }
     return 0;
 }

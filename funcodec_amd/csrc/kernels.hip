@@ -1446,20 +1446,7 @@ __device__ __forceinline__ int rvq_stage_counts(int row0, int N, int nq, int Tf,
     }
 }
 
-// |x|^2 of one residual row by four lanes j = 0 .. 3 (consecutive lanes): chain j over d in [j D/4, (j + 1) D/4) with the square rounded
-// separately, the chains combined (p0 + p1) + (p2 + p3); lane j = 0 writes the result
-template <int D>
-__device__ __forceinline__ void rvq_row_norm(const float* row, int j, float* xn_row) {
-    float s = 0.f;
-#pragma unroll 8
-    for (int d = j * (D / 4); d < (j + 1) * (D / 4); ++d) {
-        const float v = row[d];
-        s = __fadd_rn(s, __fmul_rn(v, v));
-    }
-    const float s_pair = __fadd_rn(s, __shfl_xor(s, 1, 64));          // p0+p1 | p2+p3
-    const float s_all = __fadd_rn(s_pair, __shfl_xor(s_pair, 2, 64));  // (p0+p1)+(p2+p3)
-    if (j == 0) *xn_row = s_all;
-}
+// rvq_row_norm (|x|^2 of one residual row by four lanes): device_common.h -- the beam search (rvq_beam_kernels.hip) states its errors with it
 
 // arg-max of a stage, FIRST max wins: every wave's (best, index) registers (row 16 s2 + 4 g + r, the wave's codes spread over the 16 lanes
 // r16) meet by a 16-lane butterfly, the 8 waves' results through LDS; thread `row` then clamps the index into range (all-NaN row: torch

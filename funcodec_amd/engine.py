@@ -7,6 +7,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import logging
+import numbers
 from typing import Dict, Optional
 
 import numpy as np
@@ -60,6 +61,33 @@ def row_nq_refusal(arch) -> Optional[str]:
     if arch.bypass_quantizer:
         return "a bit rate per row is not available with model_conf.bypass_quantizer (the quantiser's result is dropped)"
     return None
+
+
+RVQ_BEAM_WIDTHS = (1, 2, 4, 8)
+
+
+def rvq_beam_refusal(arch) -> Optional[str]:
+    """Why a model of this architecture takes no search over the quantiser's stages (``rvq_beam`` above 1), or None.  The configuration
+    key is named, as ``ragged_refusal`` does."""
+    if arch.bypass_quantizer:
+        return "rvq_beam is not available with model_conf.bypass_quantizer (the quantiser's result is dropped)"
+    if arch.q0_ds_ratio > 1:
+        return ("rvq_beam is not available for quantizer_conf.q0_ds_ratio > 1 (stage 0 is shared by frame pairs, so the frames are "
+                "not independent)")
+    return None
+
+
+def rvq_beam_width(arch, width) -> int:
+    """A checked ``rvq_beam``: None and 1 are the greedy quantiser; raises before any engine call."""
+    if width is None:
+        return 1
+    if isinstance(width, bool) or not isinstance(width, numbers.Integral) or int(width) not in RVQ_BEAM_WIDTHS:
+        raise EngineError(f"rvq_beam: a width is one of {', '.join(map(str, RVQ_BEAM_WIDTHS))}, got {width!r}")
+    if int(width) > 1:
+        why = rvq_beam_refusal(arch)
+        if why:
+            raise EngineError(why)
+    return int(width)
 
 
 def row_nq_list(arch, rows, B: int, cap: Optional[int] = None) -> list:
@@ -293,6 +321,26 @@ class CodecEngine:
         finally:
             self.lib.fc_engine_set_row_nq(self._h, None, 0, None)
 
+    @_on_device
+    def set_rvq_beam(self, width) -> None:
+        """Width of the quantiser's search over the stages (fc_engine_set_rvq_beam) for every call that follows on this engine -- offline,
+        length-aware, session pushes; 1 (or None) clears it: the greedy quantiser, launching exactly what it always did."""
+        width = rvq_beam_width(self.arch, width)
+        self._check(self.lib.fc_engine_set_rvq_beam(self._h, width, self._stream()))
+
+    @contextlib.contextmanager
+    def _rvq_beam(self, width):
+        """set_rvq_beam for the calls made inside; cleared on the way out, whatever happened, as _row_nq does.  width: checked
+        (rvq_beam_width); 1 sets nothing."""
+        if width is None or width == 1:
+            yield
+            return
+        self.set_rvq_beam(width)
+        try:
+            yield
+        finally:
+            self.lib.fc_engine_set_rvq_beam(self._h, 1, None)
+
     # -- hot path ------------------------------------------------------------------------------
     # n_q_rows (encode, encode_decode, decode_codes; optional): a stage count per row, each <= n_q (decode_codes: the tokens' last
     # dimension).  Row b is then what the call with n_q = n_q_rows[b] gives it; codes and sub_quants of its later stages are 0, and a
@@ -463,9 +511,13 @@ class CodecEngine:
 
     # -- per-op entry points (tests) -----------------------------------------------------------
     @_on_device
-    def rvq_encode(self, x: torch.Tensor, n_q: int, n_q_rows=None):
+    def rvq_encode(self, x: torch.Tensor, n_q: int, n_q_rows=None, beam: int = 1, return_paths: bool = False):
         """x [N,D] -> (codes [n_q,N], quantized [N,D]).  n_q_rows (B entries): the N rows are B utterances of N / B frames each, utterance b
-        with n_q_rows[b] stages."""
+        with n_q_rows[b] stages.  beam (2, 4, 8): the search over the stages (fc_rvq_encode_beam) instead of the greedy quantiser;
+        return_paths: also (paths [beam,n_q,N] i64, errors [beam,N]), every slot's final path and its fixed-order residual energy."""
+        beam = rvq_beam_width(self.arch, beam)
+        if return_paths and beam == 1:
+            raise EngineError("rvq_encode: return_paths needs rvq_beam above 1 (the paths are those of a search)")
         if n_q_rows is not None:
             n_q_rows = row_nq_list(self.arch, n_q_rows, len(n_q_rows), n_q)
             if x.shape[0] % len(n_q_rows) != 0:
@@ -476,6 +528,13 @@ class CodecEngine:
             raise EngineError(f"rvq_encode: rows must have {self.arch.codebook_dim} dims, got {D}")
         codes = torch.empty((n_q, N), dtype=torch.int64, device=self.device)
         quant = torch.empty((N, D), dtype=torch.float32, device=self.device)
+        if beam > 1:
+            paths = torch.empty((beam, n_q, N), dtype=torch.int64, device=self.device) if return_paths else None
+            errors = torch.empty((beam, N), dtype=torch.float32, device=self.device) if return_paths else None
+            with self._row_nq(n_q_rows):
+                self._check(self.lib.fc_rvq_encode_beam(self._h, _ptr(x), N, n_q, beam, _ptr(codes), _ptr(quant), _ptr(paths), _ptr(errors),
+                                                        self._stream()))
+            return (codes, quant, paths, errors) if return_paths else (codes, quant)
         ws = torch.empty(N, dtype=torch.int32, device=self.device) if self.arch.q0_ds_ratio > 1 else None     # stage-0 source-row table
         with self._row_nq(n_q_rows):
             self._check(self.lib.fc_rvq_encode(self._h, _ptr(x), N, n_q, _ptr(codes), _ptr(quant), _ptr(ws) if ws is not None else None,

@@ -14,7 +14,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ArchSpec
-from .engine import CodecEngine, EngineError, ragged_refusal, row_nq_list
+from .engine import CodecEngine, EngineError, ragged_refusal, row_nq_list, rvq_beam_width
 
 
 class EncodecMI355X:
@@ -44,26 +44,29 @@ class EncodecMI355X:
         self.engine.load_state_dict(state)
 
     def open_stream(self, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None, max_chunk: Optional[int] = None,
-                    max_frames: Optional[int] = None, graph: bool = False):
+                    max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None):
         """A streaming encode / decode session for `batch` utterances of a causal checkpoint (funcodec_amd/stream.py CodecStream):
         n_q quantisers (default: all; a list of `batch` counts gives every utterance its own, and ``set_n_q`` changes them between
         pushes), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call.  A causal net whose bottleneck is
         a transformer (seq_model: transformer) needs max_frames, the most frames one utterance may hold per side: the size of the
         session's key / value cache.  Any other net is refused with it.  graph=True: steady pushes are replayed as captured HIP graphs
-        from fixed buffers of the session, and what a push returns are copies (CodecStream, "Graph replay"); refused with max_frames."""
+        from fixed buffers of the session, and what a push returns are copies (CodecStream, "Graph replay"); refused with max_frames.
+        rvq_beam (2, 4, 8): the session's encode pushes search over the quantiser's stages (``inference(rvq_beam=)``); a frame's codes
+        equal the offline call's."""
         from .stream import CodecStream
-        return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames, graph=graph)
+        return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames, graph=graph, rvq_beam=rvq_beam)
 
     def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
-                   graph: bool = False):
+                   graph: bool = False, rvq_beam: Optional[int] = None):
         """A slot session of a causal checkpoint (funcodec_amd/stream.py StreamSlots): `slots` independent utterances that start, push
         and end at their own times and share every push of the batch; n_q quantisers at the most (default: all; ``start(slot, n_q=)`` and
         ``set_n_q(slot, n_q)`` give a slot fewer, at any time between pushes), at most max_chunk samples per call.  As for
         ``open_stream``, a net whose bottleneck is a transformer needs max_frames, the most frames one slot's utterance may hold per
         side (every slot has its own key / value cache and its own position in it); any other net is refused with it.  graph=True: pushes
-        are replayed as captured HIP graphs from fixed buffers of the session, and what a push returns are copies (StreamSlots)."""
+        are replayed as captured HIP graphs from fixed buffers of the session, and what a push returns are copies (StreamSlots).
+        rvq_beam: as for ``open_stream``."""
         from .stream import StreamSlots
-        return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames, graph=graph)
+        return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames, graph=graph, rvq_beam=rvq_beam)
 
     # -- helpers -------------------------------------------------------------------------------
     def _as_bct(self, speech: torch.Tensor) -> torch.Tensor:
@@ -139,12 +142,19 @@ class EncodecMI355X:
     # -- Encodec.inference (codec_basic.py:670-718) ------------------------------------------
     @torch.no_grad()
     def inference(self, speech: torch.Tensor, need_recon: bool = True, bit_width: int = None,
-                  use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None) -> Dict[str, torch.Tensor]:
+                  use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None, rvq_beam: int = None) -> Dict[str, torch.Tensor]:
         """bit_width: one value for the batch, as in the reference, or a sequence / 1-D tensor of B: row b is then what this call returns
         for it with ``bit_width[b]``; ``code_indices`` is [max n_q, B, Tf] with zeros at the stages a row does not take (``sub_quants`` too).
         speech_lengths [B] (optional): samples per row.  With it, row b of every output is what this call returns for
         ``speech[b, ..., :speech_lengths[b]]`` alone (its own volume scale, GroupNorm statistics, end padding), zeros behind its
-        ``engine.frames(len)`` frames / ``len`` samples; without it, the call over the whole batch width, as the reference runs it."""
+        ``engine.frames(len)`` frames / ``len`` samples; without it, the call over the whole batch width, as the reference runs it.
+        rvq_beam (2, 4 or 8; optional): the quantiser searches over its stages with that many hypotheses per frame instead of taking the
+        nearest code stage by stage; no frame is coded worse, the outputs keep their shapes and decode like any other.  It is set on the
+        engine around this call only, and combines with ``speech_lengths`` and a per-row ``bit_width``."""
+        with self.engine._rvq_beam(rvq_beam_width(self.arch, rvq_beam)):           # refused before anything reaches the device
+            return self._inference(speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths)
+
+    def _inference(self, speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths):
         speech = self._as_bct(speech)
         bypass = self.arch.bypass_quantizer and not _quantise_always
         n_q, rows = self._bit_widths(bit_width, speech.shape[0])
@@ -183,10 +193,10 @@ class EncodecMI355X:
     # -- Encodec.inference_encoding (codec_basic.py:720-764) ---------------------------------
     @torch.no_grad()
     def inference_encoding(self, speech: torch.Tensor, need_recon: bool = False, bit_width: int = None,
-                           use_scale: bool = True, speech_lengths=None) -> Dict[str, torch.Tensor]:
+                           use_scale: bool = True, speech_lengths=None, rvq_beam: int = None) -> Dict[str, torch.Tensor]:
         # (model_conf.bypass_quantizer does not reach this entry point in the reference: it quantises, :748-750)
         return self.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, _quantise_always=True,
-                              speech_lengths=speech_lengths)
+                              speech_lengths=speech_lengths, rvq_beam=rvq_beam)
 
     # -- Encodec.inference_decoding (codec_basic.py:766-802) ---------------------------------
     @torch.no_grad()

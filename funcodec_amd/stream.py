@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .config import SEQ_FF, SEQ_HEADS
-from .engine import CodecEngine, EngineError, _on_device, _ptr, row_nq_list
+from .engine import CodecEngine, EngineError, _on_device, _ptr, row_nq_list, rvq_beam_width
 
 
 def stream_refusal(arch, max_frames: Optional[int] = None) -> Optional[str]:
@@ -108,10 +108,13 @@ class _Session:
     _cached_family = ""       # the pair that sizes and creates the kind's session with a key / value cache (max_frames)
     _graph_family = ""        # the three calls of the kind's graph replay (set, enabled, counts)
 
-    def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None, graph: bool = False):
+    def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None, graph: bool = False,
+                 rvq_beam: Optional[int] = None):
         why = stream_refusal(model.arch, max_frames)
         if why:
             raise EngineError(why)
+        #: width of the quantiser's search over the stages in this session's encode pushes (1: greedy); set on the engine around each of them
+        self.rvq_beam = rvq_beam_width(model.arch, rvq_beam)
         if graph and max_frames is not None and self._family == "fc_stream":
             raise EngineError(GRAPH_MAX_FRAMES_REFUSAL)
         self.model, self.engine, self.arch = model, model.engine, model.arch
@@ -245,6 +248,10 @@ class _Session:
         """the engine's table around one push; with no counts of its own a push does not touch the engine's table at all"""
         return contextlib.nullcontext() if rows is None else self.engine._row_nq(rows)
 
+    def _engine_rvq_beam(self):
+        """the width of the quantiser's search around one encode push; a session of width 1 does not touch the engine's at all"""
+        return contextlib.nullcontext() if self.rvq_beam == 1 else self.engine._rvq_beam(self.rvq_beam)
+
     def _push_row_nq(self):
         """what a push sets on the engine: the rows' counts, or None when every row runs all n_q stages (the plain kernels)"""
         rows = self._row_nq
@@ -307,13 +314,13 @@ class CodecStream(_Session):
     _graph_family = "fc_graphstream"
 
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
-                 max_chunk: Optional[int] = None, max_frames: Optional[int] = None, graph: bool = False):
+                 max_chunk: Optional[int] = None, max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None):
         self.batch = int(batch)
         rows = None
         if n_q is not None and not isinstance(n_q, numbers.Integral):       # a count per utterance: refused before anything is opened
             rows = row_nq_list(model.arch, n_q, self.batch)
             n_q = max(rows)
-        super().__init__(model, self.batch, n_q, max_chunk, max_frames, graph)
+        super().__init__(model, self.batch, n_q, max_chunk, max_frames, graph, rvq_beam)
         self._row_nq = rows
         self.reset(scale)
 
@@ -341,7 +348,7 @@ class CodecStream(_Session):
         enc = self._buf("enc_out", (B, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
         n = C.c_int(0)
         ws = self._push_ws()
-        with self._push_stream(), self._engine_row_nq(self._push_row_nq()):
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam():
             self.engine._check(self.lib.fc_stream_encode(self._h, _ptr(wav), T, int(final), _ptr(codes), _ptr(quant), _ptr(enc), C.byref(n),
                                                          _ptr(ws), ws.numel(), self.engine._stream()))
         assert n.value == Tf
@@ -486,10 +493,10 @@ class StreamSlots(_Session):
     _graph_family = "fc_graphslots"
 
     def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
-                 graph: bool = False):
+                 graph: bool = False, rvq_beam: Optional[int] = None):
         self.slots = int(slots)
         self.pad_value = 0.0          # what the assembled batch holds behind a row's count and in idle rows (never read; a test aid)
-        super().__init__(model, self.slots, n_q, max_chunk, max_frames, graph)
+        super().__init__(model, self.slots, n_q, max_chunk, max_frames, graph, rvq_beam)
         self._enc = [_Side() for _ in range(self.slots)]
         self._dec = [_Side() for _ in range(self.slots)]
         self._scale = [1.0] * self.slots
@@ -595,7 +602,7 @@ class StreamSlots(_Session):
         quant = self._buf("quantized", (S, Tf, D), torch.float32)
         enc = self._buf("enc_out", (S, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
         ws = self._push_ws()
-        with self._push_stream(), self._engine_row_nq(self._push_row_nq()):
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam():
             self.engine._check(self.lib.fc_slots_encode(self._h, _ptr(wav), Tc, counts, flags, _ptr(scale), _ptr(codes), _ptr(quant), _ptr(enc),
                                                         _ptr(ws), ws.numel(), self.engine._stream()))
         out = {}

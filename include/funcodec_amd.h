@@ -215,6 +215,27 @@ int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengt
  * has neither field -- so only the host wrappers can refuse them, and do. */
 int fc_engine_set_row_nq(fc_engine* e, const int32_t* n_q_rows /* host [B] or NULL */, int B, void* stream);
 
+/* ---- the quantiser's search over the stages (entry points added without a struct change: FC_ABI_VERSION stays) --------------
+ * The reference's residual quantiser is greedy: stage i takes the nearest code to the residual and never looks back.  A width W in
+ * {2, 4, 8} keeps W hypotheses per frame through the stages instead (csrc/rvq_beam_kernels.h states the search); the bit stream, the
+ * decoder and every consumer of codes stay as they are.  Slot 0 is always the greedy path and the pick is by the explicitly recomputed
+ * residual energy, ties to the lowest slot, so a frame is never coded worse than greedy under that formula; the greedy codes themselves
+ * are computed by the same launch as ever.  Everything a call returns besides the codes (quantised embeddings, sub_quants, the
+ * decoder's input, the reconstruction) is made from the final codes: `quantized` is bit for bit fc_decode_codes' emb_out of them.
+ * The search is per frame: nothing is carried between frames, rows, pushes or batch neighbours.
+ * fc_engine_set_rvq_beam sets the width for the calls that follow, as fc_engine_set_row_nq sets stage counts; 1 clears it.  Every call
+ * that quantises honours it: fc_encode, fc_encode_decode, their _ragged siblings, the encode pushes of both session kinds (the width
+ * is part of a captured push's key) and the 2-D (FreqCodec) encode.  With width 1 every call launches exactly what it launched before.
+ * With per-row stage counts a row with count k runs the search over k stages, which is NOT a prefix of the search over more.
+ * Refused before any launch, changing nothing: a width outside {1, 2, 4, 8} (names rvq_beam); quantizer_conf.q0_ds_ratio > 1 with a
+ * width above 1 (stage 0 is shared by frame pairs there).  model_conf.bypass_quantizer is a host-side matter: the host wrappers refuse. */
+int fc_engine_set_rvq_beam(fc_engine* e, int width, void* stream);
+/* The per-op hook: x dev f32 [N,D]; codes dev i64 [n_q,N]; quantized dev f32 [N,D] or NULL; paths dev i64 [width,n_q,N] or NULL and
+ * errors dev f32 [width,N] or NULL: every slot's final path and its fixed-order residual energy (both NULL with width 1).  Honours
+ * fc_engine_set_row_nq as fc_rvq_encode does; ignores the width set on the engine. */
+int fc_rvq_encode_beam(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, int64_t* paths,
+                       float* errors, void* stream);
+
 /* _linear_overlap_add (funcodec/models/codec_basic.py:77-116), the tail of Encodec._decode (:382-396) when
  * model_conf.segment_dur is set: triangle-weighted overlap-add of the decoded segments, products accumulated in
  * frame order and divided once by the summed weights, exactly as the reference orders it.
@@ -376,7 +397,7 @@ int  fc_seqslots_forward(fc_slots* s, int decoder, const float* x, int T, const 
  * Every check of a push runs first, as ever: a refused push changes nothing.  Then the push's KEY is looked up among the session's
  * graphs.  The key holds every host value the enqueued work depends on: the call form (encode, decode_codes, decode_emb), the width
  * (Tc / Tfc), the parity of the side's push count, n_q, use_scale, EVERY POINTER ARGUMENT (inputs, outputs -- NULL for an absent one --,
- * scale, workspace and its size, the stream) and whether per-row stage counts are set (fc_engine_set_row_nq), with the table's
+ * scale, workspace and its size, the stream), the width of the quantiser's search (fc_engine_set_rvq_beam) and whether per-row stage counts are set (fc_engine_set_row_nq), with the table's
  * device address and width.  A hit replays; a miss captures (hipStreamCaptureModeThreadLocal on the caller's stream, which must
  * not be the null stream), instantiates, launches and stores the graph.  So a caller whose pointers repeat from push to push -- fixed
  * input, output and workspace buffers -- replays, two graphs per (side, form, width) in the steady state, one per parity; a caller

@@ -1,7 +1,8 @@
 """Build the gfx950 shared library in-tree (hipcc cross-compiles without a GPU).
 
-The conv kernel template is instantiated in one translation unit per tile shape (csrc/conv_tile_*.hip); all
-translation units compile in parallel and are linked into ONE library, funcodec_amd/libfuncodec_amd.so.
+Every csrc/*.hip is a translation unit.  The templates with many or slow instantiations sit in headers and are instantiated in small
+units of their own (conv_kernel.h in conv_tile*_*.hip, rvq_beam_kernel.h in rvq_beam_w*.hip); all units compile in parallel and are
+linked into ONE library, funcodec_amd/libfuncodec_amd.so.
 """
 from __future__ import annotations
 
@@ -15,15 +16,25 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libfuncodec_amd.so")
 OBJ_DIR = os.path.join(CSRC, "_obj")
-HEADERS = ["kernels.h", "device_common.h", "conv_kernel.h", "laura_kernels.h", "seq_kernels.h", "stream_kernels.h", "ragged_kernels.h", "slots_kernels.h", "rvq_beam_kernels.h", os.path.join("..", "..", "include", "funcodec_amd.h")]
+# every unit depends on every header (a changed header rebuilds all of them)
+HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join("..", "..", "include", "funcodec_amd.h")]
+# the units that compile longest, by name prefix: the pool starts them in this order, then the rest (times: docs/history/translation_units.md)
+START_FIRST = ("rvq_beam_w8", "conv_tile_128x128", "conv_tile_64x256", "kernels", "freq_kernels", "conv_tileq_128x128", "conv_tileq_64x256", "conv_tile", "laura_kernels")
 
 
 def sources():
-    # longest translation units first (the pool starts them in this order): the quad-layout tile units, then the rest
-    tiles = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "conv_tile*_*.hip")))
-    heavy = [t for t in tiles if t.startswith("conv_tileq_") and "_m" not in t] + [t for t in tiles if t.endswith("_m01.hip")]
-    rest = [t for t in tiles if t not in heavy]
-    return heavy + ["kernels.hip", "rvq_beam_kernels.hip", "laura_persist.hip", "laura_kernels.hip", "freq_kernels.hip", "seq_kernels.hip", "seqstream_kernels.hip", "stream_kernels.hip", "ragged_kernels.hip", "slots_kernels.hip", "engine.hip", "laura.hip"] + rest
+    units = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip")))
+
+    def rank(u):
+        return next((i for i, pre in enumerate(START_FIRST) if u.startswith(pre)), len(START_FIRST))
+    return sorted(units, key=rank)
+
+
+def _jobs(units: int) -> int:
+    # MAX_JOBS (a positive integer) caps the compilers started at once: os.cpu_count() is the machine's, not this process's allowance
+    n = min(units, os.cpu_count() or 4)
+    mj = os.environ.get("MAX_JOBS", "")
+    return min(n, int(mj)) if mj.isdigit() and int(mj) > 0 else n
 
 
 def _hipcc() -> str:
@@ -72,7 +83,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return obj
 
     srcs = sources()
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 4)) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=_jobs(len(srcs))) as ex:
         objs = list(ex.map(compile_one, srcs))
     # link next to the target and rename over it: a process dlopen-ing the library concurrently sees the old or the new file, never
     # a half-written one

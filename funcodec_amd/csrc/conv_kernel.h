@@ -15,21 +15,11 @@ namespace fc {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
 
-static inline __host__ __device__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-// Ablation masks (ConvArgs::ablate and friends) exist in tuning builds only (FC_BUILD_DEFINES=FC_AB_KNOBS / FC_TIMELINE): in the shipped
-// library FC_ABL() is the constant 0, so no profiling branch sits around a load, a DMA piece or an MFMA block of the hot loops (a run-time
-// condition around a software-pipelined load is exactly what hipcc turns into exposed latency).
 #ifndef FC_ELEM_NSET
 #define FC_ELEM_NSET 1      // ... of the quad element staging of the prologue modes (plain layers always keep two); 2 measured: slower (below)
 #endif
 #ifndef FC_ROW_NSET
 #define FC_ROW_NSET 1       // register sets of the quad row staging (A / B builds: FC_BUILD_DEFINES="FC_ROW_NSET=2 FC_ELEM_NSET=2")
-#endif
-#ifdef FC_AB_KNOBS
-#define FC_ABL(mask_, bits_) ((mask_) & (bits_))
-#else
-#define FC_ABL(mask_, bits_) (0)
 #endif
 
 // =================================================================================================

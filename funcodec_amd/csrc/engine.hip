@@ -154,7 +154,7 @@ struct fc_engine {
     std::map<std::string, LstmBlock*> lstm_by_prefix;
     // quantiser
     float *cb = nullptr, *enorm = nullptr;   // [nq][K][D], [nq][K]
-    float* cb_frag = nullptr;                // the codebooks in MFMA B-fragment order (kernels.hip rvq_encode_kernel), or null
+    float* cb_frag = nullptr;                // the codebooks in MFMA B-fragment order (rvq_kernels.hip rvq_encode_kernel), or null
     std::vector<void*> dev_allocs;
     // status words written by kernels (host-pinned, device-mapped; kernels.h FC_STATUS_*), read at the next call without a sync
     volatile unsigned* status_host = nullptr;
@@ -1260,7 +1260,7 @@ inline fc::Src src_of(const Act& a) { fc::Src s; s.ptr = a.raw; s.aff = a.aff; s
 // of the earlier pushes instead of starting from a cleared workspace buffer.  h_l(t) sits at parity t & 1 and step 0 reads parity 1, so
 // after an odd number of steps the last hidden state is copied to where the next push looks for it.
 // `steps` (a push of a slot session, with `carried`): row b takes ragged_cols(steps) of the T steps; the masked steps keep every row's
-// hidden state at the common parity (kernels.hip lstm_wave_kernel, MASKED), so the copy after an odd T serves all rows.
+// hidden state at the common parity (lstm_kernels.hip lstm_wave_kernel, MASKED), so the copy after an odd T serves all rows.
 Act run_lstm(fc_engine* e, Ctx& cx, const LstmBlock& lb, const Act& in, int T, float* carried = nullptr, const fc::RagLen* steps = nullptr) {
     const int H = lb.H, B = cx.B, L = (int)lb.layers.size();
     float* xproj = cx.alloc<float>((size_t)T * B * 4 * H);

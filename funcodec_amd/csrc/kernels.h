@@ -1,4 +1,4 @@
-// Launch interface between the engine (engine.hip) and the gfx950 kernels (kernels.hip).
+// Launch interface between the engine (engine.hip) and the gfx950 kernels (kernels.hip, rvq_kernels.hip, lstm_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +23,17 @@ inline int ab_knob(const char* name, int dflt) {
     return dflt;
 #endif
 }
+
+// Ablation masks (ConvArgs::ablate and friends) exist in tuning builds only (FC_BUILD_DEFINES=FC_AB_KNOBS / FC_TIMELINE): in the shipped
+// library FC_ABL() is the constant 0, so no profiling branch sits around a load, a DMA piece or an MFMA block of the hot loops (a run-time
+// condition around a software-pipelined load is exactly what hipcc turns into exposed latency).
+#ifdef FC_AB_KNOBS
+#define FC_ABL(mask_, bits_) ((mask_) & (bits_))
+#else
+#define FC_ABL(mask_, bits_) (0)
+#endif
+
+static inline __host__ __device__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // Deployment switches: the ONLY environment variables the shipped library reads besides the test hooks below.  Every value of each selects a
 // code path whose results are tested against the default's (tests/test_gpu_parity.py::test_staging_scheme_and_workgroup_count_do_not_change_results,
@@ -218,6 +229,11 @@ hipError_t launch_q0_map(int* map /* [B][Tf] */, int B, int Tf, hipStream_t st);
 // nq_rows: per-batch-row stage counts [B] (device) or null; the codes behind a row's count are not read (and never reported)
 hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb,
                              float* emb, float* emb_bdt, unsigned* status, hipStream_t st, const int* nq_rows = nullptr);
+// What the quantiser returns besides codes, from the final codes [nq][N]: quant [N][D] = ((0 + E_0[c0]) + E_1[c1]) + ... (the order of
+// launch_rvq_decode and of the greedy kernel, so bit for bit what decoding those codes gives), quant_bdt [B][D][Tf], subq [nq][B][D][Tf]
+// (E_i[c_i]; 0 behind a row's count).  Each may be null.
+hipError_t launch_rvq_codes_sum(const int64_t* codes, int N, int D, int K, int nq, const float* cb, float* quant, float* quant_bdt, float* subq,
+                                int Tf, hipStream_t st, const int* nq_rows = nullptr);
 
 // engine status words (host-pinned, device-mapped): written by kernels with plain stores, read by the host without a sync
 #define FC_STATUS_LSTM_TIMEOUT 0   // persistent LSTM: the grid barrier timed out (workgroups not co-resident); outputs poisoned
@@ -226,7 +242,7 @@ hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D,
 #define FC_STATUS_WORDS 16
 
 #define FC_LSTM_MAX_LAYERS 4
-// Layer-wavefront step s (see kernels.hip): w[0] = W_hh0 perm [4H][H]; w[l>=1] = [W_ih_l | W_hh_l] perm [4H][2H];
+// Layer-wavefront step s (see lstm_kernels.hip): w[0] = W_hh0 perm [4H][H]; w[l>=1] = [W_ih_l | W_hh_l] perm [4H][2H];
 // bias[l>=1] = perm(b_ih + b_hh); h [L][2][B][H] and c [L][B][H] zero-initialised by the caller.
 // steps (a push of a slot session; null: every row takes all T steps): device [B], row b takes ceil(steps[b] / sdiv) * smul <= T steps;
 // a step beyond that carries the row's h across the parity, leaves its c alone and writes y = 0.

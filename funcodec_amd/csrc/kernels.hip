@@ -1405,928 +1405,6 @@ hipError_t launch_transpose_btd(const float* in, int B, int T, int D, float* out
     return hipGetLastError();
 }
 
-// =================================================================================================
-// 4. Residual vector quantiser: all n_q stages fused, 16 rows per workgroup
-//    (DistributedResidualVectorQuantization.forward ddp_core_vq.py:367-418, eval branch;
-//     EuclideanCodebook.quantize :180-188; dequantize :190-192)
-//
-//    stage i:  dist[row][k] = -(( |x|^2 - (2x).e_k ) + |e_k|^2)     idx = argmax_k, FIRST max wins
-//              q = E_i[idx];  residual -= q;  out += q
-//
-//    Arithmetic order (restated bit-for-bit by oracle/c/rvq_oracle.c):
-//      |x|^2   : 4 partial chains over d in [j*D/4,(j+1)*D/4), s = s + x*x with the square rounded
-//                separately (torch: x.pow(2).sum(1)), combined (p0+p1)+(p2+p3);
-//      (2x).e  : one MFMA accumulator per (row, code): fmaf chain from 0 over d in the order
-//                d = 16q + 4g + j  for q = 0..D/16-1, j = 0..3, g = 0..3 (innermost);
-//      |e|^2   : precomputed at load time (engine.hip), sequential d = 0..D-1, squares rounded separately.
-// =================================================================================================
-// ---- the steps rvq_encode_kernel and rvq_encode_wide_kernel share, stated once (ROWS = rows of the workgroup).  The two tails (the RQ
-//      zeros behind the last stage, the quant / quant_bdt store) are the same lines in both kernels too, but stay in the kernels: as
-//      functions they changed the register allocation of most RQ instantiations (ROCm 7.2 hipcc, kernel-resource-usage remarks).
-
-// RQ: the stages this workgroup runs (the largest count among its rows) and, in krow, every row's own count (0 behind row N; read behind
-// the first barrier of stage 0).  The rows of a workgroup are consecutive frames, so their batch rows are consecutive too: every thread
-// takes the same maximum.  Without RQ: nq, krow untouched.
-template <int ROWS, bool RQ>
-__device__ __forceinline__ int rvq_stage_counts(int row0, int N, int nq, int Tf, const int* nq_rows, int* krow) {
-    if constexpr (!RQ) return nq;
-    else {
-        const int tid = threadIdx.x;
-        const int last = (row0 + ROWS <= N ? row0 + ROWS : N) - 1;
-        int nqw = 0;
-        for (int b = row0 / Tf; b <= last / Tf; ++b) {
-            const int k = nq_rows[b] < nq ? nq_rows[b] : nq;
-            nqw = k > nqw ? k : nqw;
-        }
-        if (tid < ROWS) {
-            const int n = row0 + tid;
-            krow[tid] = n < N ? (nq_rows[n / Tf] < nq ? nq_rows[n / Tf] : nq) : 0;
-        }
-        return nqw;
-    }
-}
-
-// rvq_row_norm (|x|^2 of one residual row by four lanes): device_common.h -- the beam search (rvq_beam_kernels.hip) states its errors with it
-
-// arg-max of a stage, FIRST max wins: every wave's (best, index) registers (row 16 s2 + 4 g + r, the wave's codes spread over the 16 lanes
-// r16) meet by a 16-lane butterfly, the 8 waves' results through LDS; thread `row` then clamps the index into range (all-NaN row: torch
-// would return an index too), leaves it in sel for the gather and stores the row's code -- 0 for a stage the row does not take (RQ; sel
-// keeps the real index).  Holds one barrier; the caller's next barrier publishes sel.  tid, wid, g, r16: the caller's thread coordinates
-// (taken as arguments: recomputed here they cost rvq_encode_kernel<128, 1> two registers).
-template <int RS, bool RQ>
-__device__ __forceinline__ void rvq_argmax_merge(float (&best)[RS][4], int (&bidx)[RS][4], float (*bestv)[16 * RS], int (*besti)[16 * RS],
-                                                 int* sel, const int* krow, int i, int K, int N, int row0, int64_t* codes, int tid, int wid,
-                                                 int g, int r16) {
-#pragma unroll
-    for (int s2 = 0; s2 < RS; ++s2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const float ov = __shfl_xor(best[s2][r], o, 64);
-                const int oi = __shfl_xor(bidx[s2][r], o, 64);
-                if (ov > best[s2][r] || (ov == best[s2][r] && oi < bidx[s2][r])) { best[s2][r] = ov; bidx[s2][r] = oi; }
-            }
-            if (r16 == 0) { bestv[wid][16 * s2 + 4 * g + r] = best[s2][r]; besti[wid][16 * s2 + 4 * g + r] = bidx[s2][r]; }
-        }
-    }
-    __syncthreads();
-    if (tid < 16 * RS) {
-        float bv = bestv[0][tid];
-        int bi = besti[0][tid];
-        for (int w = 1; w < 8; ++w) {
-            const float ov = bestv[w][tid];
-            const int oi = besti[w][tid];
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (bi < 0 || bi >= K) bi = 0;   // all-NaN row: torch would return an index too; stay in range
-        sel[tid] = bi;
-        if constexpr (RQ) { if (i >= krow[tid]) bi = 0; }       // a stage the row does not take: code 0 (sel stays in range for the gather)
-        if (row0 + tid < N) codes[(size_t)i * N + row0 + tid] = (int64_t)bi;
-    }
-}
-
-// RS = row sets of 16 rows per workgroup.  The stage is L2-bandwidth bound when one codebook load feeds only 16 rows
-// (every workgroup streams the whole 512 KiB stage codebook: 250 workgroups x 512 KiB = 128 MiB per stage at config B);
-// with RS = 2 the same registers feed two independent 16-row MFMA accumulators (same arithmetic per row).
-// Q0: the stage-0 source-row table `src0` is honoured (quantizer_conf.q0_ds_ratio > 1); a template parameter so that the benchmark's
-// instantiations keep their register allocation (183 registers, no spill).
-// RQ: the per-batch-row stage counts `nq_rows` [N / Tf] are honoured (frame row n belongs to batch row n / Tf), a template parameter for
-// the same reason.  A residual quantiser is a prefix code, so row r with count k_r runs its stages i < k_r exactly as without the table; for
-// i >= k_r nothing is added to its quantised sum, its code and its sub_quant of that stage are 0, and what the row still computes while
-// its neighbours go on stays in the row (every row has its own residual, MFMA output row and arg-max).  The workgroup ends after the
-// largest count of its rows -- the same for all its threads, so the barriers of a stage stay uniform -- and writes the zeros of the
-// stages it did not run.  nq is the cap: the first dimension of codes / subq, >= every count.
-template <int D, int RS, bool Q0 = false, bool RQ = false>
-__global__ __launch_bounds__(512) void rvq_encode_kernel(const float* __restrict__ x, int N, int K, int nq,
-                                                         const float* __restrict__ cb, const float* __restrict__ cbf,
-                                                         const float* __restrict__ enorm,
-                                                         int64_t* __restrict__ codes, float* __restrict__ quant,
-                                                         float* __restrict__ quant_bdt, float* __restrict__ subq, int Tf,
-                                                         int ablate, const int* __restrict__ src0, const int* __restrict__ nq_rows) {
-    constexpr int NQ4 = D / 16;
-    constexpr int ROWS = 16 * RS;
-    // residual rows, padded by 4 floats: the |x|^2 chains read R[r][32 j + i] from 64 lanes (r, j) at once -- with a row stride of
-    // D every lane hit the same bank (32-way conflict, ~1 us per stage); stride D + 4 spreads the 8 rows of a lane group over 8 banks
-    __shared__ __attribute__((aligned(16))) float R[ROWS][D + 4];
-    constexpr int NEL = (ROWS * D + 511) / 512;                // elements of the row set owned by one thread: e = tid + 512 * it
-    float qreg[NEL];                                    // running sum of the selected code rows (was an LDS array)
-    __shared__ float xn[ROWS];
-    __shared__ float bestv[8][ROWS];
-    __shared__ int besti[8][ROWS];
-    __shared__ int sel[ROWS];
-    __shared__ int krow[RQ ? ROWS : 1];                 // RQ: stages of the workgroup's rows (0 behind row N)
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int g = lane >> 4, r16 = lane & 15;
-    const int row0 = blockIdx.x * ROWS;
-    const int nqw = rvq_stage_counts<ROWS, RQ>(row0, N, nq, Tf, nq_rows, krow);      // stages this workgroup runs
-
-    for (int e = tid; e < ROWS * D; e += 512) {
-        const int r = e / D, d = e - r * D;
-        const int n = row0 + r;
-        // src0 (quantizer_conf.q0_ds_ratio > 1, ddp_core_vq.py:396-404): stage 0 quantises the row its frame copies from the
-        // half-rate sequence; the residual update of that stage starts again from the row itself (below)
-        R[r][d] = n < N ? x[(size_t)(Q0 ? src0[n] : n) * D + d] : 0.f;
-    }
-#pragma unroll
-    for (int it = 0; it < NEL; ++it) qreg[it] = 0.f;
-    const int codes_per_wave = (K >> 3) < 16 ? 16 : (K >> 3);   // 8 waves: two per SIMD hide the codebook-row load latency
-    const bool wactive = wid * codes_per_wave < K;            // small codebooks keep only K/16 waves busy
-
-    constexpr bool DEEP = RS == 1;                                // one row set: codebook tiles two ahead (the two-row-set form has twice the MFMAs per tile)
-    f32x4 b0[NQ4];                                               // first codebook fragment of the stage (requested one stage ahead)
-    f32x4 b1p[DEEP ? NQ4 : 1];                                   // DEEP: the second one
-    for (int i = 0; i < nqw; ++i) {
-        __syncthreads();
-        if (tid < 4 * ROWS) rvq_row_norm<D>(R[tid >> 2], tid & 3, &xn[tid >> 2]);   // |x|^2
-        f32x4 a4[RS][NQ4];
-#pragma unroll
-        for (int s2 = 0; s2 < RS; ++s2)
-#pragma unroll
-            for (int q = 0; q < NQ4; ++q) {
-                const f32x4 v = *(const f32x4*)&R[16 * s2 + r16][16 * q + 4 * g];
-                a4[s2][q] = v + v;   // 2*x, exact
-            }
-        __syncthreads();
-        float best[RS][4];
-        int bidx[RS][4];
-        float xr[RS][4];
-#pragma unroll
-        for (int s2 = 0; s2 < RS; ++s2)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { best[s2][r] = -INFINITY; bidx[s2][r] = 0x7fffffff; xr[s2][r] = xn[16 * s2 + 4 * g + r]; }
-        const float* cbi = cb + (size_t)i * K * D;
-        // One 16-code tile per trip, software pipelined: the codebook fragment of tile n+1 is requested before the 4*NQ4
-        // MFMAs of tile n are issued (two register buffers), so the L2 latency of the stream hides behind the matrix work;
-        // the second wave on the SIMD fills the dependent-MFMA bubbles.  Each (row, code) chain keeps its own d order.
-        const int ntile = wactive ? codes_per_wave >> 4 : 0;
-        const int code0 = wid * codes_per_wave;
-        auto frag_ptr = [&](int stage, int t) __attribute__((always_inline)) {
-            const int code = code0 + 16 * t;
-            return cbf ? cbf + ((size_t)stage * K + code) * D + lane * 4 : cb + ((size_t)stage * K + code + r16) * D + 4 * g;
-        };
-        const int qstep = cbf ? 256 : 16;
-        auto load_tile = [&](int stage, int t, f32x4 (&bq)[NQ4]) __attribute__((always_inline)) {
-            const float* e0 = frag_ptr(stage, t);
-#pragma unroll
-            for (int q = 0; q < NQ4; ++q) bq[q] = FC_ABL(ablate, 2) ? (f32x4){1.f, 1.f, 1.f, 1.f} : *(const f32x4*)(e0 + qstep * q);
-        };
-        auto do_tile = [&](int t, const f32x4 (&bq)[NQ4]) __attribute__((always_inline)) {
-            const int code = code0 + 16 * t + r16;
-            const float en = enorm[(size_t)i * K + code];
-            f32x4 acc[RS];
-#pragma unroll
-            for (int s2 = 0; s2 < RS; ++s2) acc[s2] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (!FC_ABL(ablate, 1)) {
-#pragma unroll
-                for (int q = 0; q < NQ4; ++q)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int s2 = 0; s2 < RS; ++s2)
-                            acc[s2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s2][q][j], bq[q][j], acc[s2], 0, 0, 0);
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < RS; ++s2)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float dist = -__fadd_rn(__fsub_rn(xr[s2][r], acc[s2][r]), en);
-                    if (dist > best[s2][r]) { best[s2][r] = dist; bidx[s2][r] = code; }
-                }
-        };
-        if (ntile > 0) {
-            if constexpr (DEEP) {
-                // Round 5: codebook tiles are requested TWO tiles ahead (three register buffers).  With one tile ahead the L2 round trip of a
-                // fragment (~1 us under this load) is as long as the 2 x 0.43 us of MFMAs of the two waves that share a SIMD.  Measured: 525 -> 517 us
-                // (of the 80 us the codebook loads cost on top of the MFMAs -- tools/ablate_rvq.py -- most is their issue time, not latency)
-                f32x4 b2[NQ4];
-                if (i == 0) { load_tile(0, 0, b0); if (ntile > 1) load_tile(0, 1, b1p); }
-                int t = 0;
-                for (; t + 3 <= ntile; t += 3) {
-                    load_tile(i, t + 2, b2);
-                    do_tile(t, b0);
-                    if (t + 3 < ntile) load_tile(i, t + 3, b0);
-                    do_tile(t + 1, b1p);
-                    if (t + 4 < ntile) load_tile(i, t + 4, b1p);
-                    do_tile(t + 2, b2);
-                }
-                if (t < ntile) do_tile(t, b0);                 // 0, 1 or 2 tiles left: already requested into b0 / b1p
-                if (t + 1 < ntile) do_tile(t + 1, b1p);
-                // the next stage's first fragments do not depend on this stage's result: requested now, the arg-max / residual-update tail
-                // of this stage hides their latency
-                if (i + 1 < nqw) { load_tile(i + 1, 0, b0); if (ntile > 1) load_tile(i + 1, 1, b1p); }
-            } else {
-                f32x4 b1[NQ4];
-                if (i == 0) load_tile(0, 0, b0);
-                int t = 0;
-                for (; t + 2 <= ntile; t += 2) {
-                    load_tile(i, t + 1, b1);
-                    do_tile(t, b0);
-                    if (t + 2 < ntile) load_tile(i, t + 2, b0);
-                    do_tile(t + 1, b1);
-                }
-                if (t < ntile) do_tile(t, b0);
-                // the next stage's first fragment does not depend on this stage's result: request it now, the arg-max /
-                // residual-update tail of this stage hides its latency
-                if (i + 1 < nqw) load_tile(i + 1, 0, b0);
-            }
-        }
-        rvq_argmax_merge<RS, RQ>(best, bidx, bestv, besti, sel, krow, i, K, N, row0, codes, tid, wid, g, r16);
-        __syncthreads();
-        // gather the selected code rows: all loads first (they are independent), then the LDS / register updates
-        float qv[NEL];
-#pragma unroll
-        for (int it = 0; it < NEL; ++it) {
-            const int e = tid + 512 * it, r = e / D, d = e - r * D;
-            qv[it] = 0.f;
-            if (ROWS * D % 512 == 0 || e < ROWS * D) qv[it] = FC_ABL(ablate, 8) ? 0.001f : cbi[(size_t)sel[r] * D + d];
-        }
-#pragma unroll
-        for (int it = 0; it < NEL; ++it) {
-            const int e = tid + 512 * it, r = e / D, d = e - r * D;
-            if (ROWS * D % 512 != 0 && e >= ROWS * D) continue;
-            const int n = row0 + r;
-            float res = R[r][d];
-            if (Q0 && i == 0 && n < N) res = x[(size_t)n * D + d];
-            R[r][d] = res - qv[it];
-            bool keep = true;
-            if constexpr (RQ) keep = i < krow[r];
-            if (keep) qreg[it] = qreg[it] + qv[it];
-            if (subq && n < N && !FC_ABL(ablate, 4)) {
-                const int bb = n / Tf, t = n - bb * Tf;
-                const int Bn = N / Tf;
-                subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = keep ? qv[it] : 0.f;
-            }
-        }
-    }
-    // The two tails; rvq_encode_wide_kernel repeats them line for line (why they are not one function: the note above
-    // rvq_stage_counts).  An edit here is an edit there.
-    if constexpr (RQ) {       // the stages behind the workgroup's last one: codes and sub_quants 0
-        if (tid < ROWS && row0 + tid < N)
-            for (int i = nqw; i < nq; ++i) codes[(size_t)i * N + row0 + tid] = 0;
-        if (subq)
-            for (int i = nqw; i < nq; ++i)
-#pragma unroll
-                for (int it = 0; it < NEL; ++it) {
-                    const int e = tid + 512 * it, r = e / D, d = e - r * D;
-                    const int n = row0 + r;
-                    if (n >= N || (ROWS * D % 512 != 0 && e >= ROWS * D)) continue;
-                    const int bb = n / Tf, t = n - bb * Tf;
-                    const int Bn = N / Tf;
-                    subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = 0.f;
-                }
-    }
-#pragma unroll
-    for (int it = 0; it < NEL; ++it) {
-        const int e = tid + 512 * it, r = e / D, d = e - r * D;
-        const int n = row0 + r;
-        if (n >= N || (ROWS * D % 512 != 0 && e >= ROWS * D)) continue;
-        const float v = qreg[it];
-        if (quant) quant[(size_t)n * D + d] = v;
-        if (quant_bdt) {
-            const int bb = n / Tf, t = n - bb * Tf;
-            quant_bdt[((size_t)bb * D + d) * Tf + t] = v;
-        }
-    }
-}
-
-// Wide codebooks (D = 512, the SoundStream recipe): the shared steps above around its own matrix loop.  A (row, code) chain is fed in
-// chunks of 256 dims -- the 2x fragment of the row (re-read from LDS per chunk) and the two in-flight codebook fragments then fit the
-// register file -- and the residual update fuses each gather with its use.  Q0, RQ: see rvq_encode_kernel.
-template <int D, bool Q0 = false, bool RQ = false>
-__global__ __launch_bounds__(512) void rvq_encode_wide_kernel(const float* __restrict__ x, int N, int K, int nq,
-                                                              const float* __restrict__ cb, const float* __restrict__ cbf,
-                                                              const float* __restrict__ enorm,
-                                                              int64_t* __restrict__ codes, float* __restrict__ quant,
-                                                              float* __restrict__ quant_bdt, float* __restrict__ subq, int Tf,
-                                                              const int* __restrict__ src0, const int* __restrict__ nq_rows) {
-    static_assert(D % 256 == 0, "chunks of 256 dims");
-    constexpr int NC = D / 256, CQ = 16, NEL = 16 * D / 512;
-    __shared__ __attribute__((aligned(16))) float R[16][D];
-    __shared__ float xn[16];
-    __shared__ float bestv[8][16];
-    __shared__ int besti[8][16];
-    __shared__ int sel[16];
-    __shared__ int krow[RQ ? 16 : 1];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int g = lane >> 4, r16 = lane & 15;
-    const int row0 = blockIdx.x * 16;
-    const int nqw = rvq_stage_counts<16, RQ>(row0, N, nq, Tf, nq_rows, krow);
-    float qreg[NEL];                                     // running sum of the selected code rows, element e = tid + 512*i
-#pragma unroll
-    for (int i2 = 0; i2 < NEL; ++i2) {
-        const int e = tid + 512 * i2, r = e / D, d = e - r * D, n = row0 + r;
-        R[r][d] = n < N ? x[(size_t)(Q0 ? src0[n] : n) * D + d] : 0.f;       // Q0 / src0: see rvq_encode_kernel
-        qreg[i2] = 0.f;
-    }
-    const int codes_per_wave = (K >> 3) < 16 ? 16 : (K >> 3);
-    const bool wactive = wid * codes_per_wave < K;
-    const int ntile = wactive ? codes_per_wave >> 4 : 0, nunit = ntile * NC;
-    const int code0 = wid * codes_per_wave;
-    for (int i = 0; i < nqw; ++i) {
-        __syncthreads();
-        if (tid < 64) rvq_row_norm<D>(R[tid >> 2], tid & 3, &xn[tid >> 2]);   // |x|^2
-        __syncthreads();
-        float best[1][4], xr[4];
-        int bidx[1][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { best[0][r] = -INFINITY; bidx[0][r] = 0x7fffffff; xr[r] = xn[4 * g + r]; }
-        const float* cbi = cb + (size_t)i * K * D;
-        auto load_unit = [&](int u, f32x4 (&bq)[CQ]) __attribute__((always_inline)) {
-            const int t = u / NC, c = u - t * NC, code = code0 + 16 * t;
-            const float* e0 = cbf ? cbf + ((size_t)i * K + code) * D + (size_t)c * CQ * 256 + lane * 4
-                                  : cbi + (size_t)(code + r16) * D + 256 * c + 4 * g;
-            const int qstep = cbf ? 256 : 16;
-#pragma unroll
-            for (int q = 0; q < CQ; ++q) bq[q] = *(const f32x4*)(e0 + qstep * q);
-        };
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        auto do_unit = [&](int u, const f32x4 (&bq)[CQ]) __attribute__((always_inline)) {
-            const int t = u / NC, c = u - t * NC, code = code0 + 16 * t + r16;
-            if (c == 0) acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < CQ; ++q) {
-                const f32x4 v = *(const f32x4*)&R[r16][256 * c + 16 * q + 4 * g];
-                const f32x4 a = v + v;                                  // 2*x, exact
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], bq[q][j], acc, 0, 0, 0);
-            }
-            if (c == NC - 1) {
-                const float en = enorm[(size_t)i * K + code];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float dist = -__fadd_rn(__fsub_rn(xr[r], acc[r]), en);
-                    if (dist > best[0][r]) { best[0][r] = dist; bidx[0][r] = code; }
-                }
-            }
-        };
-        if (nunit > 0) {
-            f32x4 b0[CQ], b1[CQ];
-            load_unit(0, b0);
-            int u = 0;
-            for (; u + 2 <= nunit; u += 2) {
-                load_unit(u + 1, b1);
-                do_unit(u, b0);
-                if (u + 2 < nunit) load_unit(u + 2, b0);
-                do_unit(u + 1, b1);
-            }
-            if (u < nunit) do_unit(u, b0);
-        }
-        rvq_argmax_merge<1, RQ>(best, bidx, bestv, besti, sel, krow, i, K, N, row0, codes, tid, wid, g, r16);
-        __syncthreads();
-#pragma unroll
-        for (int i2 = 0; i2 < NEL; ++i2) {
-            const int e = tid + 512 * i2, r = e / D, d = e - r * D, n = row0 + r;
-            const float qv = cbi[(size_t)sel[r] * D + d];
-            float res = R[r][d];
-            if (Q0 && i == 0 && n < N) res = x[(size_t)n * D + d];
-            R[r][d] = res - qv;
-            bool keep = true;
-            if constexpr (RQ) keep = i < krow[r];
-            if (keep) qreg[i2] = qreg[i2] + qv;
-            if (subq && n < N) {
-                const int bb = n / Tf, t = n - bb * Tf, Bn = N / Tf;
-                subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = keep ? qv : 0.f;
-            }
-        }
-    }
-    // The two tails, line for line those of rvq_encode_kernel (why they are not one function: the note above rvq_stage_counts).  An edit
-    // here is an edit there.
-    if constexpr (RQ) {
-        if (tid < 16 && row0 + tid < N)
-            for (int i = nqw; i < nq; ++i) codes[(size_t)i * N + row0 + tid] = 0;
-        if (subq)
-            for (int i = nqw; i < nq; ++i)
-#pragma unroll
-                for (int i2 = 0; i2 < NEL; ++i2) {
-                    const int e = tid + 512 * i2, r = e / D, d = e - r * D, n = row0 + r;
-                    if (n >= N) continue;
-                    const int bb = n / Tf, t = n - bb * Tf, Bn = N / Tf;
-                    subq[(((size_t)i * Bn + bb) * D + d) * Tf + t] = 0.f;
-                }
-    }
-#pragma unroll
-    for (int i2 = 0; i2 < NEL; ++i2) {
-        const int e = tid + 512 * i2, r = e / D, d = e - r * D, n = row0 + r;
-        if (n >= N) continue;
-        if (quant) quant[(size_t)n * D + d] = qreg[i2];
-        if (quant_bdt) {
-            const int bb = n / Tf, t = n - bb * Tf;
-            quant_bdt[((size_t)bb * D + d) * Tf + t] = qreg[i2];
-        }
-    }
-}
-
-// quantizer_conf.q0_ds_ratio > 1 (ddp_core_vq.py:396-404): map[b * Tf + t] = b * Tf + q0_source_frame(t, Tf)   (kernels.h)
-__global__ __launch_bounds__(256) void q0_map_kernel(int* __restrict__ map, int Tf) {
-    const int t = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (t < Tf) map[(size_t)b * Tf + t] = b * Tf + q0_source_frame(t, Tf);
-}
-
-hipError_t launch_q0_map(int* map, int B, int Tf, hipStream_t st) {
-    if (B <= 0 || Tf < 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(q0_map_kernel, dim3(ceil_div(Tf, 256), B), dim3(256), 0, st, map, Tf);
-    return hipGetLastError();
-}
-
-hipError_t launch_rvq_encode(const float* x, int N, int D, int K, int nq, const float* cb, const float* cb_frag,
-                             const float* enorm, int64_t* codes, float* quant, float* quant_bdt, float* subq, int Tf, hipStream_t st,
-                             const int* src0, const int* nq_rows) {
-    if (N <= 0) return hipSuccess;
-    if (K % 16 != 0 || (K > 128 && K % 128 != 0)) return hipErrorInvalidValue;
-    if (nq_rows && (Tf <= 0 || N % Tf != 0)) return hipErrorInvalidValue;      // the table is indexed by n / Tf
-    if (D == 512) {
-#define FC_RVQ_WIDE(Q0_, RQ_)                                                                                                     \
-    hipLaunchKernelGGL((rvq_encode_wide_kernel<512, Q0_, RQ_>), dim3(ceil_div(N, 16)), dim3(512), 0, st, x, N, K, nq, cb, cb_frag, enorm, \
-                       codes, quant, quant_bdt, subq, Tf, src0, nq_rows)
-        if (nq_rows) { if (src0) FC_RVQ_WIDE(true, true); else FC_RVQ_WIDE(false, true); }
-        else if (src0) FC_RVQ_WIDE(true, false);
-        else FC_RVQ_WIDE(false, false);
-#undef FC_RVQ_WIDE
-        return hipGetLastError();
-    }
-    // two row sets per workgroup once there are enough rows to keep ~half the CUs busy that way (L2 traffic halves)
-    static const int ablate = ab_knob("FC_ABLATE_RVQ", 0);
-    // Round 4 (tools/rvq_scaling.py): the kernel's time is linear in the workgroups per CU (one 8-wave workgroup per CU, 183 registers).
-    // Up to 16 rows per CU the 16-row form is the fastest (497 vs 807 us at 4 000 rows); beyond that two row sets per workgroup -- the
-    // codebook fragments of a stage are loaded once for both, 32 rows per MFMA pass -- take 413 us per 32 rows per CU against 2 x 489:
-    // 846 vs 974 us at 8 000 rows, 1 613 vs 1 943 at 16 000.  FC_RVQ_TWO=0 / 1 forces one form (A / B runs).
-    static const int two_env = ab_knob("FC_RVQ_TWO", -1);
-    // CU count of the CURRENT device, looked up per call from a table filled once per device (thread-safe: function-local static of a
-    // type with a constructor; ADVICE r4: the round-4 form cached whichever device was current at the first call, unsynchronised)
-    struct CuTable {
-        int n[64];
-        CuTable() {
-            int nd = 0;
-            if (hipGetDeviceCount(&nd) != hipSuccess) nd = 0;
-            for (int d = 0; d < 64; ++d) {
-                hipDeviceProp_t prop;
-                n[d] = (d < nd && hipGetDeviceProperties(&prop, d) == hipSuccess) ? prop.multiProcessorCount : 256;
-            }
-        }
-    };
-    static const CuTable cu_table;
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    const int n_cus = cu_table.n[cur_dev & 63];
-    const bool two = !src0 && D <= 128 && (two_env >= 0 ? (two_env != 0 && N >= 2048) : N > 16 * n_cus);
-    dim3 grid(ceil_div(N, two ? 32 : 16)), block(512);
-#define FC_RVQ_FORM(DD, RS_, Q0_, RQ_)                                                                             \
-    hipLaunchKernelGGL((rvq_encode_kernel<DD, RS_, Q0_, RQ_>), grid, block, 0, st, x, N, K, nq, cb, cb_frag, enorm, codes, quant, quant_bdt, \
-                       subq, Tf, ablate, src0, nq_rows)
-#define FC_RVQ_CASE(DD)                                                                                            \
-    case DD:                                                                                                       \
-        if (nq_rows) {                                     /* the same choice of form, with the per-row stage counts */ \
-            if (two) FC_RVQ_FORM((DD <= 128 ? DD : 16), 2, false, true);                                           \
-            else if (src0) FC_RVQ_FORM(DD, 1, true, true);                                                         \
-            else FC_RVQ_FORM(DD, 1, false, true);                                                                  \
-        } else if (two) FC_RVQ_FORM((DD <= 128 ? DD : 16), 2, false, false);                                       \
-        else if (src0) FC_RVQ_FORM(DD, 1, true, false);                                                            \
-        else FC_RVQ_FORM(DD, 1, false, false);                                                                     \
-        break;
-    switch (D) {
-        FC_RVQ_CASE(16)
-        FC_RVQ_CASE(32)
-        FC_RVQ_CASE(64)
-        FC_RVQ_CASE(128)
-        FC_RVQ_CASE(256)
-        default: return hipErrorInvalidValue;
-    }
-#undef FC_RVQ_CASE
-#undef FC_RVQ_FORM
-    return hipGetLastError();
-}
-
-// DRVQ.decode (ddp_core_vq.py:442-453): out = ((0 + E_0[i0]) + E_1[i1]) + ...
-// nq_rows (per-batch-row stage counts [B], or null): row n sums its first nq_rows[n / Tf] stages; the codes behind them are not read
-__global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restrict__ codes, int Tf, int nq, int D, int K,
-                                                         const float* __restrict__ cb, float* __restrict__ emb,
-                                                         float* __restrict__ emb_bdt, unsigned* __restrict__ status,
-                                                         const int* __restrict__ nq_rows) {
-    const int n = blockIdx.x;   // row = b*Tf + t
-    const int b = n / Tf, t = n - b * Tf;
-    const int k = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
-    for (int d = threadIdx.x; d < D; d += blockDim.x) {
-        float s = 0.f;
-        for (int i = 0; i < k; ++i) {
-            long long idx = codes[(size_t)n * nq + i];
-            // F.embedding raises on an index outside [0, K) (ddp_core_vq.py:191): never read out of bounds, but make the
-            // corrupt token loud -- the engine status word reports it (fc_engine_status)
-            if (idx < 0 || idx >= K) {
-                if (status && threadIdx.x == 0) *(volatile unsigned*)(status + FC_STATUS_BAD_CODE) = 1u;
-                idx = idx < 0 ? 0 : K - 1;
-            }
-            s = s + cb[((size_t)i * K + idx) * D + d];
-        }
-        if (emb) emb[(size_t)n * D + d] = s;
-        if (emb_bdt) emb_bdt[((size_t)b * D + d) * Tf + t] = s;
-    }
-}
-
-hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb, float* emb,
-                             float* emb_bdt, unsigned* status, hipStream_t st, const int* nq_rows) {
-    if (B * Tf <= 0) return hipSuccess;
-    const int threads = D >= 256 ? 256 : (D >= 128 ? 128 : 64);
-    hipLaunchKernelGGL(rvq_decode_kernel, dim3(B * Tf), dim3(threads), 0, st, codes, Tf, nq, D, K, cb, emb, emb_bdt, status, nq_rows);
-    return hipGetLastError();
-}
-
-// =================================================================================================
-// 5. LSTM (nn.LSTM inside SLSTM, lstm.py:12-28).  Workgroup j owns the 16 gate rows {i,f,g,o} x 4 hidden units (rows
-//    permuted at load time), split-K over its waves, gates + state update fused.
-//    gates = (W_hh h_{t-1}) + xproj_t,  xproj = W_ih x_t + b_ih + b_hh computed for all t at once by the conv kernel (k = 1).
-// =================================================================================================
-// Gate nonlinearities on the hardware exp2 / rcp (1 ulp each): sigmoid(v) = 1 / (1 + 2^(-v log2 e)), tanh(v) = 2 sigmoid(2v) - 1.
-// Absolute error <= ~2e-7 (the libm versions are ~40 and ~60 VALU instructions and sit on the recurrence's critical path);
-// measured end to end: every golden index still bit-exact, LSTM outputs within 1e-5 of torch (tests/test_gpu_parity.py).
-__device__ __forceinline__ float sigmoid_f(float v) {
-    const float e = __builtin_amdgcn_exp2f(-1.44269504088896341f * v);      // +inf for very negative v -> rcp gives 0
-    return __builtin_amdgcn_rcpf(1.f + e);
-}
-__device__ __forceinline__ float tanh_f(float v) {
-    const float e = __builtin_amdgcn_exp2f(-2.88539008177792681f * v);
-    return fmaf(2.f, __builtin_amdgcn_rcpf(1.f + e), -1.f);
-}
-// c' = f * c + i * g with ONE explicit rounding order -- fma(f, c, round(i * g)) -- in every LSTM kernel: left to hipcc's contraction the
-// same expression became v_mul + v_fmac in one kernel and v_pk_mul + v_add in another (one ulp apart; the persistent and the per-step
-// forms are tested for bit equality)
-__device__ __forceinline__ float lstm_cell(float gf, float c, float gi, float gg) { return __fmaf_rn(gf, c, __fmul_rn(gi, gg)); }
-
-// -------------------------------------------------------------------------------------------------
-// Layer-wavefront LSTM step: launch s advances layer l by its timestep t = s - l for ALL layers at once
-// (T + L - 1 launches instead of L*T, and no separate x-projection GEMM for layers >= 1, whose input
-// h_{l-1}(t) is consumed straight from the previous launch):
-//   layer 0 : gates = xproj[t] + W_hh0 . h0(t-1)
-//   layer l : gates = bias_l + [W_ih_l | W_hh_l] . [h_{l-1}(t) ; h_l(t-1)]
-// hidden states ping-pong on the parity of their own timestep: h[l][t & 1].
-// -------------------------------------------------------------------------------------------------
-struct LstmWaveArgs {
-    const float* w[FC_LSTM_MAX_LAYERS];
-    const float* bias[FC_LSTM_MAX_LAYERS];
-    const float* xproj;
-    float* h;
-    float* c;
-    float* y;
-    int B, H, T, L, s, KS;
-    // MASKED form only (a push of a slot session): row b takes ceil(steps[b] / sdiv) * smul of the T steps
-    const int* steps;
-    int sdiv, smul;
-};
-
-// MASKED: a step beyond a row's own count carries h_l across the parity and leaves c alone (y = 0 there), so that after the launch
-// sequence every row's last hidden state sits at the same parity whatever its count.  A live step of a row is computed exactly as in the
-// plain form (rows are independent columns of the MFMA).
-template <int NS, bool MASKED = false>
-__global__ __launch_bounds__(256) void lstm_wave_kernel(const LstmWaveArgs p) {
-    __shared__ f32x4 red[4][64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int g = lane >> 4, r16 = lane & 15;
-    const int H = p.H, B = p.B;
-    const int nblk = H >> 2;
-    const int layer = blockIdx.x / nblk, blk = blockIdx.x - layer * nblk;
-    const int t = p.s - layer;
-    if (t < 0 || t >= p.T) return;
-    const int kslice = H / p.KS;
-    const int nsteps = kslice >> 4;
-    const bool active = wid < p.KS;
-    const int nseg = layer == 0 ? 1 : 2;
-    const int wstride = layer == 0 ? H : 2 * H;
-    const float* wbase = p.w[layer] + ((size_t)blk * 16 + r16) * wstride + (active ? wid : 0) * kslice + 4 * g;
-    const size_t BH = (size_t)B * H;
-    float* hl = p.h + (size_t)layer * 2 * BH;
-    const float* h_own_prev = hl + (size_t)((t + 1) & 1) * BH;                  // h_l(t-1): parity (t-1)&1
-    const float* h_below = layer ? p.h + (size_t)(layer - 1) * 2 * BH + (size_t)(t & 1) * BH : nullptr;   // h_{l-1}(t)
-    float* h_out = hl + (size_t)(t & 1) * BH;
-    float* cl = p.c + (size_t)layer * BH;
-    constexpr int NA = NS > 0 ? NS : 1;
-    const int nbt = (B + 15) >> 4;
-    for (int nb = 0; nb < nbt; ++nb) {
-        const int brow = nb * 16 + r16;
-        const bool bvalid = brow < B;
-        const size_t ci = (size_t)(bvalid ? brow : 0) * H + (size_t)blk * 4 + g;
-        f32x4 xp = {0.f, 0.f, 0.f, 0.f};
-        float cprev = 0.f;
-        if (wid == 0) {
-            if (layer == 0) xp = *(const f32x4*)(p.xproj + ((size_t)t * B + (bvalid ? brow : 0)) * 4 * H + (size_t)blk * 16 + 4 * g);
-            else xp = *(const f32x4*)(p.bias[layer] + (size_t)blk * 16 + 4 * g);
-            cprev = cl[ci];
-        }
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        for (int seg = 0; seg < nseg; ++seg) {
-            const float* wrow = wbase + (nseg == 2 ? seg * H : 0);
-            const float* hsrc = (nseg == 2 && seg == 0) ? h_below : h_own_prev;
-            const float* hrow = hsrc + (size_t)(bvalid ? brow : 0) * H + (active ? wid : 0) * kslice + 4 * g;
-            if (NS > 0) {
-                f32x4 a4[NA], b4[NA];
-#pragma unroll
-                for (int q = 0; q < NA; ++q) {
-                    a4[q] = *(const f32x4*)(wrow + 16 * q);
-                    b4[q] = *(const f32x4*)(hrow + 16 * q);
-                    if (!bvalid) b4[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int q = 0; q < NA; ++q) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (q & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[q][j], b4[q][j], acc1, 0, 0, 0);
-                        else acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[q][j], b4[q][j], acc, 0, 0, 0);
-                    }
-                }
-            } else if (active) {
-                for (int q = 0; q < nsteps; ++q) {
-                    const f32x4 av = *(const f32x4*)(wrow + 16 * q);
-                    f32x4 bv = *(const f32x4*)(hrow + 16 * q);
-                    if (!bvalid) bv = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j], acc, 0, 0, 0);
-                }
-            }
-        }
-        acc = acc + acc1;
-        if (!active) acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        red[wid][lane] = acc;
-        __syncthreads();
-        if (wid == 0) {
-            f32x4 sgate = red[0][lane];
-            for (int w = 1; w < p.KS; ++w) sgate = sgate + red[w][lane];
-            bool masked = false;
-            if (MASKED) masked = bvalid && t >= (p.steps[brow] + p.sdiv - 1) / p.sdiv * p.smul;
-            if (masked) {
-                h_out[ci] = h_own_prev[ci];
-                if (layer == p.L - 1) p.y[ci * p.T + t] = 0.f;
-            } else if (bvalid) {
-                const float gi = sigmoid_f(sgate[0] + xp[0]);
-                const float gf = sigmoid_f(sgate[1] + xp[1]);
-                const float gg = tanh_f(sgate[2] + xp[2]);
-                const float go = sigmoid_f(sgate[3] + xp[3]);
-                const float cn = lstm_cell(gf, cprev, gi, gg);
-                const float hn = go * tanh_f(cn);
-                cl[ci] = cn;
-                h_out[ci] = hn;
-                if (layer == p.L - 1) p.y[ci * p.T + t] = hn;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-hipError_t launch_lstm_wave(const float* const* w, const float* const* bias, const float* xproj, float* h, float* c,
-                            float* y, int B, int H, int T, int L, int s, hipStream_t st, const int* steps, int sdiv, int smul) {
-    if (H % 16 != 0 || L < 1 || L > FC_LSTM_MAX_LAYERS || (steps && (sdiv < 1 || smul < 1))) return hipErrorInvalidValue;
-    LstmWaveArgs a;
-    for (int l = 0; l < FC_LSTM_MAX_LAYERS; ++l) { a.w[l] = l < L ? w[l] : nullptr; a.bias[l] = l < L ? bias[l] : nullptr; }
-    a.xproj = xproj; a.h = h; a.c = c; a.y = y; a.B = B; a.H = H; a.T = T; a.L = L; a.s = s;
-    a.steps = steps; a.sdiv = sdiv; a.smul = smul;
-    int KS = 4;
-    while (KS > 1 && (H % (16 * KS)) != 0) KS >>= 1;
-    a.KS = KS;
-    const int ns = H / (16 * KS);
-    dim3 grid(L * (H / 4)), block(256);
-    if (steps) {
-        switch (ns) {
-            case 1: hipLaunchKernelGGL((lstm_wave_kernel<1, true>), grid, block, 0, st, a); break;
-            case 2: hipLaunchKernelGGL((lstm_wave_kernel<2, true>), grid, block, 0, st, a); break;
-            case 4: hipLaunchKernelGGL((lstm_wave_kernel<4, true>), grid, block, 0, st, a); break;
-            case 8: hipLaunchKernelGGL((lstm_wave_kernel<8, true>), grid, block, 0, st, a); break;
-            case 16: hipLaunchKernelGGL((lstm_wave_kernel<16, true>), grid, block, 0, st, a); break;
-            default: hipLaunchKernelGGL((lstm_wave_kernel<0, true>), grid, block, 0, st, a); break;
-        }
-        return hipGetLastError();
-    }
-    switch (ns) {
-        case 1: hipLaunchKernelGGL(lstm_wave_kernel<1>, grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(lstm_wave_kernel<2>, grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(lstm_wave_kernel<4>, grid, block, 0, st, a); break;
-        case 8: hipLaunchKernelGGL(lstm_wave_kernel<8>, grid, block, 0, st, a); break;
-        case 16: hipLaunchKernelGGL(lstm_wave_kernel<16>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(lstm_wave_kernel<0>, grid, block, 0, st, a); break;
-    }
-    return hipGetLastError();
-}
-
-// -------------------------------------------------------------------------------------------------
-// Persistent 2-layer LSTM: ONE launch for the whole recurrence.  Workgroup j keeps the 16 gate rows of layer 0
-// (W_hh0) and of layer 1 ([W_ih1 | W_hh1]) for its 4 hidden units in REGISTERS for all T steps (192 KiB per CU,
-// one 4-wave workgroup per CU owns the whole 512-register file), cell states stay in registers too.
-//
-// Hidden-state exchange.  Every wavefront step writes h0(s) / h1(s-1) into a HISTORY buffer that is never
-// overwritten inside one launch ([T+1][B][H] per layer, slot 0 = zeros).  Stores are write-through (sc1), so when a
-// wave's vmcnt drains its values are in memory; the consumers read slot s only after the grid barrier of step s-1 and
-// nobody has touched those addresses before in this launch, so no cache on the chip can hold a stale copy of them:
-// the loads are PLAIN loads, the first workgroup of an XCD to touch a line pulls it over the fabric and the other 31
-// hit that XCD's L2 (with double-buffered h and sc1 loads every workgroup fetched all 128 KiB over the fabric every
-// step: 32 MiB per step, the largest term of the step time).
-//
-// Grid barrier: 16 arrival counters on separate cache lines (16 arrivals each instead of 256 atomics serialised on
-// one address), polled by the 16 low lanes of wave 0 with one load each; monotonic targets, bounded spin (on a
-// timeout the error word is set and every workgroup runs to completion instead of hanging).
-// Same arithmetic order per accumulator as lstm_wave_kernel (bit-identical results).
-// -------------------------------------------------------------------------------------------------
-struct LstmPersistArgs {
-    const float *w0, *w1, *bias1, *xproj;
-    float* hist;         // [BH zeros][T x BH: h0(0..T-1)][T x BH: h1(0..T-1)], BH = 16 * tiles * H; one slot = [batch tile][H/4][16 rows][4 units]:
-                         // the 64 lanes of a consumer's B-fragment load read 1 KiB of CONTIGUOUS memory (lane (g, r) = 16 bytes at 16*lane),
-                         // and the 64 producer lanes of a workgroup write one contiguous 256-byte piece.  (Row-major [B][H] put the 16 lanes
-                         // of a fragment row 4 KiB apart -- every lane of a load on its own cache line: 7.2 us per step instead of 5.1.)
-    float* y;
-    unsigned* sync;      // 16 counters at [32*i], error flag at [512]; zeroed by the caller before every launch
-    unsigned* status;    // host-visible engine status words (kernels.h FC_STATUS_*), or null
-    int B, H, T;
-    int ablate;          // FC_ABLATE_LSTM in FC_AB_KNOBS builds: 1 no grid barrier (profiling aid, wrong results).  Ignored (FC_ABL) in the shipped library
-    int test_timeout;    // test hook (FC_ABLATE_LSTM=64, the only value the shipped library honours): behave as if the grid barrier had timed out
-    int tile_base, tiles;   // first 16-row batch tile of this launch / tiles of the whole call (history slot size, barrier word block)
-    int groups;          // independent recurrences in one launch: group j = workgroups [j*H/4, (j+1)*H/4) owns batch rows [16j, 16j+16) with
-                         // its own barrier words (H = 512 fills only half of the chip: two batch tiles then advance side by side)
-};
-
-constexpr int kLstmSyncWords = 1024;
-// profiling builds only (FC_BUILD_DEFINES="FC_LSTM_ABL=<mask>", results are garbage): 1 no critical-path MFMAs, 2 no hidden-state loads,
-// 4 no shadow MFMAs, 8 no y stores, 16 no store drain before the arrival.  Compile time, because a run-time branch around the loads
-// would make hipcc wait for them at the join.
-#ifndef FC_LSTM_ABL
-#define FC_LSTM_ABL 0
-#endif
-
-// split grid barrier: arrive (after this workgroup's stores have drained) ... independent work ... wait
-__device__ __forceinline__ void lstm_barrier_arrive(unsigned* sync, int blk) {
-    if (!(FC_LSTM_ABL & 16)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave drains its own write-through stores
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(sync + 32 * (blk & 15), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void lstm_barrier_wait(unsigned* sync, unsigned target) {
-    if (threadIdx.x < 64) {
-        const unsigned* mine = sync + 32 * (threadIdx.x & 15);
-        unsigned spins = 0;
-        while (true) {
-            const unsigned v = __hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all(v >= target)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 255u) == 0u) {
-                if (__hip_atomic_load(sync + 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-                if (spins > (1u << 21)) { __hip_atomic_store(sync + 512, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-            }
-        }
-    }
-    __syncthreads();
-}
-
-// Wavefront schedule (T + 2 steps): at step s layer 0 produces h0(s) and layer 1 produces h1(s-2).  Layer 1 runs one
-// step later than its data dependence requires so that its input half, P = W_ih1 . h0(s-1), is computed in the SHADOW
-// of the grid barrier of step s (after this workgroup has arrived, before it starts polling) and only the two
-// recurrent products (W_hh0 . h0(s-1), W_hh1 . h1(s-3)) sit on the critical path between two barriers.
-template <int NS>
-__global__ __launch_bounds__(256, 1) void lstm_persist_kernel(const LstmPersistArgs p) {
-    // batch tiles (16 rows) per workgroup and step.  Fixed at one since round 3: a second tile of a call is a second group (H = 512) or a
-    // second launch (H = 1024); the tile loops below are what is left of the two-tiles-per-step form (3.14 vs 2 x 1.26 ms) and fold away.
-    constexpr int NBT = 1;
-    static_assert(NS % 2 == 0, "k slices are issued in pairs");
-    __shared__ f32x4 red[2][4][64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int g = lane >> 4, r16 = lane & 15;
-    const int H = p.H, B = p.B, T = p.T;
-    const int wgs = H >> 2;                          // workgroups of one recurrence
-    const int grp = p.groups > 1 ? blockIdx.x / wgs : 0;
-    const int blk = blockIdx.x - grp * wgs;
-    const int tile0 = p.tile_base + grp;             // first batch tile of this group (groups > 1 run with NBT == 1)
-    const int brow0 = tile0 * 16;                    // its first batch row
-    unsigned* const sync = p.sync + (size_t)tile0 * kLstmSyncWords;
-    const unsigned arrivals = (unsigned)wgs >> 4;    // per counter per step
-    const int kslice = NS * 16;                      // H / 4 waves
-    const size_t BH = (size_t)16 * p.tiles * H;      // floats per history slot (batch padded to whole tiles)
-    // ---- weights -> registers (once)
-    f32x4 a0[NS], a1i[NS], a1h[NS];
-    {
-        const float* w0r = p.w0 + ((size_t)blk * 16 + r16) * H + wid * kslice + 4 * g;
-        const float* w1r = p.w1 + ((size_t)blk * 16 + r16) * 2 * H + wid * kslice + 4 * g;
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            a0[q] = *(const f32x4*)(w0r + 16 * q);
-            a1i[q] = *(const f32x4*)(w1r + 16 * q);
-            a1h[q] = *(const f32x4*)(w1r + H + 16 * q);
-        }
-    }
-    float cst[NBT];                                  // cell state of (batch row, unit): wave 0 -> layer 0, wave 1 -> layer 1
-    f32x4 pa[NBT], pb[NBT];                          // P = W_ih1 . h0 of the NEXT step's layer-1 timestep (even / odd k slices)
-#pragma unroll
-    for (int nb = 0; nb < NBT; ++nb) {
-        cst[nb] = 0.f;
-        pa[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        pb[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const f32x4 bias1 = *(const f32x4*)(p.bias1 + (size_t)blk * 16 + 4 * g);
-    float* const hist0 = p.hist;                     // slot k = h0(k-1), slot 0 = zeros
-    float* const hist1 = p.hist + (size_t)T * BH;    // slot k >= 1 = h1(k-1) (slot 0 is never addressed through this base)
-    f32x4 b0keep[NS];
-
-    for (int s = 0; s <= T + 1; ++s) {
-        const bool act0 = s < T, act1 = s >= 2;
-        const float* h0in = hist0 + (size_t)(s <= T ? s : T) * BH;                   // h0(s-1)
-        const float* h1in = s >= 3 ? hist1 + (size_t)(s - 2) * BH : hist0;           // h1(s-3)
-        float* h0o = hist0 + (size_t)(s + 1) * BH;                                   // h0(s)     (s < T)
-        float* h1o = hist1 + (size_t)(s - 1) * BH;                                   // h1(s-2)   (s >= 2)
-#pragma unroll
-        for (int nb = 0; nb < NBT; ++nb) {
-            const int brow = brow0 + nb * 16 + r16;
-            const bool bvalid = brow < B;
-            // rows >= B of the last tile are never written: their columns compute values nobody stores (MFMA columns are independent)
-            const size_t hoff = (size_t)(tile0 + nb) * 16 * H + (size_t)wid * kslice * 16 + 4 * lane;
-            f32x4 xp = {0.f, 0.f, 0.f, 0.f};
-            if (wid == 0 && act0)
-                xp = *(const f32x4*)(p.xproj + ((size_t)s * B + (bvalid ? brow : 0)) * 4 * H + (size_t)blk * 16 + 4 * g);
-            f32x4 b0l[NBT == 1 ? 1 : NS], b1[NS];
-            f32x4 (&b0)[NS] = *(NBT == 1 ? &b0keep : (f32x4 (*)[NS])&b0l);   // single batch tile: h0(s-1) stays in registers for the shadow phase
-            // All 2*NS loads are issued back to back in the order the MFMAs consume them and NOTHING touches the values before
-            // their MFMA: the k slices then start as they arrive (counted vmcnt) instead of after the last one (round 1 masked
-            // the columns of batch rows >= B right after the loads, which put one vmcnt(0) in front of all 128 MFMAs: 3.3 us
-            // of loads and 2.1 us of MFMAs ran back to back).  Columns of rows >= B read row 0 and compute values nobody stores.
-#pragma unroll
-            for (int q = 0; q < NS; ++q) {
-                if (FC_LSTM_ABL & 2) { b0[q] = (f32x4){0.f, 0.f, 0.f, 0.f}; b1[q] = b0[q]; continue; }
-                b0[q] = *(const f32x4*)(h0in + hoff + 256 * q);
-                b1[q] = *(const f32x4*)(h1in + hoff + 256 * q);
-            }
-            // four accumulators (layer 0 / layer 1 x even / odd k slice); the ISSUE order interleaves them so that two
-            // MFMAs on the same accumulator are never back to back, the order WITHIN each accumulator is that of
-            // lstm_wave_kernel (layer 1: the W_ih1 terms -- already in pa / pb -- then the W_hh1 terms)
-            f32x4 c0a = {0.f, 0.f, 0.f, 0.f}, c0b = {0.f, 0.f, 0.f, 0.f};
-            f32x4 c1a = pa[nb], c1b = pb[nb];
-#pragma unroll
-            for (int q = 0; q < ((FC_LSTM_ABL & 1) ? 0 : NS); q += 2) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    c0a = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[q][j], b0[q][j], c0a, 0, 0, 0);
-                    c1a = __builtin_amdgcn_mfma_f32_16x16x4f32(a1h[q][j], b1[q][j], c1a, 0, 0, 0);
-                    c0b = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[q + 1][j], b0[q + 1][j], c0b, 0, 0, 0);
-                    c1b = __builtin_amdgcn_mfma_f32_16x16x4f32(a1h[q + 1][j], b1[q + 1][j], c1b, 0, 0, 0);
-                }
-            }
-            red[0][wid][lane] = c0a + c0b;
-            red[1][wid][lane] = c1a + c1b;
-            __syncthreads();
-            if (wid < 2) {
-                const int layer = wid;
-                const bool act = layer ? act1 : act0;
-                f32x4 sg = red[layer][0][lane];
-                for (int w = 1; w < 4; ++w) sg = sg + red[layer][w][lane];
-                const f32x4 add = layer ? bias1 : xp;
-                if (act && bvalid) {
-                    const float gi = sigmoid_f(sg[0] + add[0]);
-                    const float gf = sigmoid_f(sg[1] + add[1]);
-                    const float gg = tanh_f(sg[2] + add[2]);
-                    const float go = sigmoid_f(sg[3] + add[3]);
-                    const float cn = lstm_cell(gf, cst[nb], gi, gg);
-                    const float hn = go * tanh_f(cn);
-                    cst[nb] = cn;
-                    const size_t ci = (size_t)brow * H + (size_t)blk * 4 + g;
-                    const size_t hi = (size_t)(tile0 + nb) * 16 * H + ((size_t)blk * 16 + r16) * 4 + g;
-                    if (layer == 0) __hip_atomic_store(&h0o[hi], hn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else { __hip_atomic_store(&h1o[hi], hn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (!(FC_LSTM_ABL & 8)) p.y[ci * T + (s - 2)] = hn; }
-                }
-            }
-            __syncthreads();
-        }
-        if (s > T) break;
-        const bool do_sync = !FC_ABL(p.ablate, 1);
-        if (do_sync) lstm_barrier_arrive(sync, blk);
-        // ---- barrier shadow: P for the next step's layer-1 timestep t = s - 1 (needs h0(s-1), already visible)
-        if (s >= 1) {
-#pragma unroll
-            for (int nb = 0; nb < NBT; ++nb) {
-                const size_t hoff = (size_t)(tile0 + nb) * 16 * H + (size_t)wid * kslice * 16 + 4 * lane;
-                f32x4 b0l[NBT == 1 ? 1 : NS];
-                f32x4 (&b0)[NS] = *(NBT == 1 ? &b0keep : (f32x4 (*)[NS])&b0l);
-                if (NBT > 1) {                        // several batch tiles: re-read (L2 hit) instead of holding NBT x 64 registers
-#pragma unroll
-                    for (int q = 0; q < NS; ++q) b0[q] = *(const f32x4*)(h0in + hoff + 256 * q);
-                }
-                f32x4 c1a = {0.f, 0.f, 0.f, 0.f}, c1b = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int q = 0; q < ((FC_LSTM_ABL & 4) ? 0 : NS); q += 2) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        c1a = __builtin_amdgcn_mfma_f32_16x16x4f32(a1i[q][j], b0[q][j], c1a, 0, 0, 0);
-                        c1b = __builtin_amdgcn_mfma_f32_16x16x4f32(a1i[q + 1][j], b0[q + 1][j], c1b, 0, 0, 0);
-                    }
-                }
-                pa[nb] = c1a; pb[nb] = c1b;
-            }
-        }
-        if (do_sync) lstm_barrier_wait(sync, (unsigned)(s + 1) * arrivals);
-    }
-    // a barrier that timed out (some workgroup was not resident) must not pass for a result: poison this workgroup's
-    // outputs so that the failure is loud downstream (the engine's per-step launch path is the supported fallback)
-    if (__hip_atomic_load(sync + 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || p.test_timeout) {
-        if (p.status && tid == 0) *(volatile unsigned*)(p.status + FC_STATUS_LSTM_TIMEOUT) = 1u;   // read by the host at its next fc_* call
-        for (int i = tid; i < 4 * B * T; i += 256) {
-            const int t = i % T, bu = i / T;
-            p.y[((size_t)(bu / 4) * H + (size_t)blk * 4 + (bu & 3)) * T + t] = __builtin_nanf("");
-        }
-    }
-}
-
-// H = 512 occupies 128 of the 256 CUs: a second batch tile gets its own 128 workgroups (and barrier words) instead of a second pass
-static int lstm_persist_groups(int B, int H) { return (H == 512 && B > 16) ? 2 : 1; }
 // zero fill as a KERNEL of this library (not hipMemsetAsync): under HIP-graph replay the runtime's memset node was observed to run
 // unordered with respect to the neighbouring kernel nodes (tools/graph_probe.py), which resets the barrier words mid-recurrence
 __global__ __launch_bounds__(256) void zero_fill_kernel(float* __restrict__ p, size_t n) {
@@ -2350,70 +1428,7 @@ hipError_t launch_zero_fill(float* p, size_t n, hipStream_t st) {
     return hipGetLastError();
 }
 
-// history slots hold whole 16-row batch tiles (LstmPersistArgs::hist)
-static int lstm_persist_tiles(int B) { return (B + 15) / 16; }
-static size_t lstm_persist_slot_floats(int B, int H) { return (size_t)16 * lstm_persist_tiles(B) * H; }
-size_t lstm_persist_state_floats(int B, int H, int T) { return (size_t)kLstmSyncWords * lstm_persist_tiles(B) + (size_t)(2 * T + 1) * lstm_persist_slot_floats(B, H); }
-size_t lstm_persist_clear_floats(int B, int H) { return (size_t)kLstmSyncWords * lstm_persist_tiles(B) + lstm_persist_slot_floats(B, H); }
-
-// `state`: lstm_persist_state_floats() floats whose first lstm_persist_clear_floats() are zero (barrier words + the
-// all-zero initial hidden state)
-hipError_t launch_lstm_persist(const float* w0, const float* w1, const float* bias1, const float* xproj, float* state, float* y,
-                               int B, int H, int T, unsigned* status, hipStream_t st) {
-    LstmPersistArgs a;
-    const int groups = lstm_persist_groups(B, H);
-    const int tiles = lstm_persist_tiles(B);
-    a.w0 = w0; a.w1 = w1; a.bias1 = bias1; a.xproj = xproj; a.hist = state + (size_t)kLstmSyncWords * tiles; a.y = y;
-    a.sync = (unsigned*)state; a.status = status; a.B = B; a.H = H; a.T = T; a.groups = groups; a.tile_base = 0; a.tiles = tiles;
-    // FC_ABLATE_LSTM: the profiling masks are tuning-build knobs (ab_knob); the shipped library honours exactly one value, 64 = the barrier-timeout
-    // TEST hook of tests/test_gpu_parity.py (every other value is ignored: mask 1 removes the grid barrier and gives wrong results)
-    static const int hook = getenv("FC_ABLATE_LSTM") ? atoi(getenv("FC_ABLATE_LSTM")) : 0;
-#ifdef FC_AB_KNOBS
-    static const int ablate = hook;
-#else
-    static const int ablate = 0;         // (not through ab_knob: the variable is legitimately set by the timeout test, no "ignored" notice)
-#endif
-    a.ablate = ablate & ~64;
-    a.test_timeout = (hook == 64 || (ablate & 64)) ? 1 : 0;
-    // H = 1024 fills the chip with ONE batch tile: a second tile (17 .. 32 utterances) is a second launch of the same kernel on its own
-    // history columns and barrier words (round 3: 2 x 1.26 ms; the two-tiles-per-step instantiation needed 3.14 ms with the new history
-    // layout).  H = 512: two tiles side by side as two groups of 128 workgroups in one launch.
-    dim3 grid(H / 4 * groups), block(256);
-    // FC_LSTM_COOP=1: hipLaunchCooperativeKernel (the runtime validates the grid against the occupancy query at every launch,
-    // +15-19 us of host time per launch); default: plain launch, residency validated once per engine by lstm_persist_supported()
-    static const int coop = ab_knob("FC_LSTM_COOP", 0);
-    void* kargs[] = {(void*)&a};
-#define FC_LP(NS)                                                                                                \
-    do {                                                                                                         \
-        if (coop) { hipError_t ec = hipLaunchCooperativeKernel((const void*)lstm_persist_kernel<NS>, grid, block, kargs, 0, st); \
-                    if (ec != hipSuccess) return ec; }                                                            \
-        else hipLaunchKernelGGL((lstm_persist_kernel<NS>), grid, block, 0, st, a);                                 \
-    } while (0)
-    if (H == 1024) {
-        for (int tb = 0; tb < tiles; ++tb) { a.tile_base = tb; FC_LP(16); }
-    } else if (H == 512 && groups == tiles) FC_LP(8);
-    else return hipErrorInvalidValue;
-#undef FC_LP
-    return hipGetLastError();
-}
-
-// can the persistent kernel be used? (every workgroup must be co-resident: one per CU)
-// The grid barrier needs all H/4 workgroups resident at once.  Checked against the runtime's own occupancy answer for the
-// instantiation that would run (not just the CU count): blocks per CU x CUs >= grid, with the one-block margin the
-// microarchitecture guide asks for near an SGPR edge (the kernel needs exactly ONE block per CU on a 256-CU part, and
-// two fit by registers, so the margin is met by construction).
-bool lstm_persist_supported(int B, int H, int L, int device) {
-    if (L != 2 || (H != 1024 && H != 512) || B > 32) return false;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return false;
-    const int groups = lstm_persist_groups(B, H);
-    int per_cu = 0;
-    hipError_t e = hipErrorInvalidValue;
-    if (H == 1024) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_persist_kernel<16>, 256, 0);
-    else if (H == 512) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_persist_kernel<8>, 256, 0);
-    if (e != hipSuccess || per_cu < 1) return false;
-    return (long long)per_cu * prop.multiProcessorCount >= H / 4 * groups && prop.multiProcessorCount >= H / 4 * groups;
-}
+// 4. Residual vector quantiser: rvq_kernels.hip (the search over the stages: rvq_beam_kernels.hip).  5. LSTM: lstm_kernels.hip.
 
 // =================================================================================================
 // 6. Triangle-weighted overlap-add of decoded segments (_linear_overlap_add, codec_basic.py:77-116)

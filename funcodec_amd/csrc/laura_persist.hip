@@ -21,7 +21,7 @@
 //   no weight loads: it polls, stores and arrives, so its `s_waitcnt vmcnt(0)` drains stores only and its polls do not queue behind a tile.
 // * w_2 (K = ff) is split into k slices of ~d columns (step_persist_ksplit): every GEMV unit contracts over ~d values (short staging and
 //   MFMA chains on the critical path, one LDS tile size); the consumers of a block's output add the slices while staging.
-// * Hand-off = the persistent LSTM's (kernels.hip): results are stored WRITE-THROUGH (relaxed agent-scope atomic stores -> sc1), the storing
+// * Hand-off = the persistent LSTM's (lstm_kernels.hip): results are stored WRITE-THROUGH (relaxed agent-scope atomic stores -> sc1), the storing
 //   wave drains its stores (s_waitcnt vmcnt(0)) and adds 1 to one of the phase's 16 arrival counters (separate cache lines, monotonic
 //   targets = launch number x producers); consumers poll with 16 lanes, then read the edge buffer with PLAIN loads: every edge buffer
 //   is written once per launch and never read before its phase is complete, so no cache can hold a stale copy (copies of the previous

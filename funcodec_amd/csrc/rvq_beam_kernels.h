@@ -1,4 +1,4 @@
-// Residual vector quantiser: a beam search over the stages (rvq_beam_kernels.hip).  The bit stream and the decoder stay as they are; only
+// Residual vector quantiser: a beam search over the stages (launched by rvq_beam_kernels.hip, the kernel: rvq_beam_kernel.h).  The bit stream and the decoder stay as they are; only
 // the choice of codes changes.  The reference has no such search: this header is its specification.
 //
 // Per frame x, stages 0 .. k-1, width W in {2, 4, 8}; slots 0 .. W-1:
@@ -34,11 +34,5 @@ hipError_t rvq_beam_prepare(int D, int W);
 hipError_t launch_rvq_beam(const float* x /* [N][D] */, int N, int D, int K, int nq, int W, const float* cb, const float* cb_frag /* or null */,
                            const float* enorm, int64_t* codes, int64_t* paths, float* errors, int Tf, hipStream_t st,
                            const int* nq_rows /* [N / Tf] or null */ = nullptr);
-
-// What the quantiser returns besides codes, from the final codes [nq][N]: quant [N][D] = ((0 + E_0[c0]) + E_1[c1]) + ... (the order of
-// launch_rvq_decode and of the greedy kernel, so bit for bit what decoding those codes gives), quant_bdt [B][D][Tf], subq [nq][B][D][Tf]
-// (E_i[c_i]; 0 behind a row's count).  Each may be null.
-hipError_t launch_rvq_codes_sum(const int64_t* codes, int N, int D, int K, int nq, const float* cb, float* quant, float* quant_bdt, float* subq,
-                                int Tf, hipStream_t st, const int* nq_rows = nullptr);
 
 }  // namespace fc

@@ -12,7 +12,7 @@
  *
  * The reference evaluates the three terms with ATen kernels whose summation order is unspecified (MKL sgemm,
  * vectorised reductions).  This file fixes ONE explicit fp32 order -- the one the gfx950 kernel uses
- * (funcodec_amd/csrc/kernels.hip, rvq_encode_kernel) -- so that the integer output can be compared
+ * (funcodec_amd/csrc/rvq_kernels.hip, rvq_encode_kernel) -- so that the integer output can be compared
  * BIT-EXACTLY between CPU and GPU at any size, while tests/golden/rvq_*.npz (produced by the real
  * reference) pin that this order reproduces the reference's indices:
  *   |x|^2  : four partial chains over d in [j*D/4,(j+1)*D/4), s = s + fl(x*x) (square rounded separately,

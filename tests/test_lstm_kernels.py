@@ -1,4 +1,4 @@
-"""The SLSTM bottleneck's two HIP kernels (kernels.hip section 5) against a float64 torch.nn.LSTM, at every instantiation the engine
+"""The SLSTM bottleneck's two HIP kernels (lstm_kernels.hip) against a float64 torch.nn.LSTM, at every instantiation the engine
 builds and at full recurrence length:
 
 - lstm_wave_kernel<NS> (one launch per wavefront step): every NS (1, 2, 4, 8, 16 and the generic NS = 0 loop) and every k-slice

@@ -308,7 +308,7 @@ class Text2Audio:
         seeds, whatever samples, retries, keep, rules, prefill and length_aware; up to 16 slots there is one block and nothing to
         save.  Refused with queue = True: a queued session claims its slots on the device and the host cannot know the busy rows.
         ``self.last_elastic`` = {"moves", "blocks"} of the last such call: rows moved, and {blocks: steps run at that width}."""
-        from ..laura import HeldPrompts, drive_best, drive_queue, drive_retries, drive_samples, pick_best, retry_seed, tail_groups
+        from ..laura import CandidateRun, tail_groups
         m, nq = self.model, self.model.predict_nq
         n, N, R = len(texts), int(samples), int(retries)
         if N < 1:
@@ -346,110 +346,40 @@ class Text2Audio:
             seeds = [int(v) for row in seeds for v in row]
         if len(seeds) != n * N:
             raise ValueError(f"generate_many: {len(seeds)} seeds for {n} requests")
-        outs, lens = [None] * n, [0] * n
-        # more than 16 slots: a wide session (open_decode(wide=True), up to 64); up to 16 the call is the one it always was
-        more = dict(wide=True) if int(slots) > 16 else {}
-        if elastic:
-            more.update(elastic=True)
-        held, plan, session = None, None, None
-        if queue:                   # the holding session first: the queued session is opened on it, with room for every ticket in flight
-            held = m.open_decode(P, logp=False)
-            try:
-                more.update(queue=int(slots) + P * N, source=held)
-                session = m.open_decode(slots, logp=False, score=True, **more) if best else m.open_decode(slots, logp=False, **more)
-            except Exception:
-                held.free()
-                raise
-        else:
-            session = m.open_decode(slots, logp=False, score=True, **more) if best else m.open_decode(slots, logp=False, **more)
+
+        def encode(i):
+            text_outs, lens = self._encode_texts([texts[i]])
+            return text_outs[0, : lens[0]], lens[0]
+
+        run = CandidateRun(n, N, seeds, rules, encode, per)
         try:
-            if P and not queue:
-                held, plan = m.open_decode(P, logp=False), HeldPrompts(P, n, N)
-
-            def encoded(i):
-                if outs[i] is None:
-                    to, ln = self._encode_texts([texts[i]])
-                    outs[i], lens[i] = to[0, : ln[0]], ln[0]
-
-            def from_held(slot, c):
-                # every candidate, first or sibling, is a copy from its request's row of the holding session
-                i = c // N
-                todo = plan.need(i)
-                if todo:
-                    for _, q in todo:
-                        encoded(q)
-                    held.start_many({row: dict(text_outs=outs[q], text_len=lens[q], max_length=1, sampling=False,
-                                               continual=None if per is None else per[q]) for row, q in todo})
-                session.start_from(slot, plan.start(i), self.max_length, self.sampling, seeds[c], rules=rules, source=held)
-
-            def start(slot, c):
-                if P:
-                    return from_held(slot, c)
-                # a request's text is encoded when its slot is free, alone: its text_outs are those of a one-utterance call
-                i = c // N
-                if N == 1 or outs[i] is None:
-                    to, ln = self._encode_texts([texts[i]])
-                    outs[i], lens[i] = to[0, : ln[0]], ln[0]
-                session.start(slot, outs[i], lens[i], self.max_length, self.sampling, seeds[c], None if per is None else per[i], rules=rules)
-
-            def start_from(slot, src, c):
-                if P:
-                    return from_held(slot, c)
-                session.start_from(slot, src, self.max_length, self.sampling, seeds[c], rules=rules)
-
-            def rewind(slot, c, keep, attempt):
-                session.rewind(slot, keep, self.max_length, self.sampling, retry_seed(seeds[c], attempt), rules=rules)
-            def fill(batch):
-                for _, q in batch:
-                    encoded(q)
-                held.start_many({row: dict(text_outs=outs[q], text_len=lens[q], max_length=1, sampling=False,
-                                           continual=None if per is None else per[q]) for row, q in batch})
-
-            def submit(row, c):
-                return session.submit(row, self.max_length, self.sampling, seeds[c], rules=rules)
-            choice = None
-            if queue:
-                flat = drive_queue(session, P, n, N, fill, submit, step_n)
-                if best:
-                    ks = [pick_best([t[-1] for t in flat[i * N: (i + 1) * N]]) for i in range(n)]
-                    taken = {i * N + k: flat[i * N + k] for i, k in enumerate(ks)}
-                    choice = [(k, taken[i * N + k][-1][0] / taken[i * N + k][-1][1]) for i, k in enumerate(ks)]
-                else:
-                    taken = flat
-            elif best:
-                kept = drive_best(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
-                taken = {i * N + k: t for i, (k, t) in enumerate(kept)}
-                choice = [(k, t[-1][0] / t[-1][1]) for k, t in kept]
-            else:
-                if R == 0:
-                    rows = drive_samples(session, slots, n, N, start, start_from, step_n)
-                else:
-                    rows = drive_retries(session, slots, n, N, R, self.max_length, start, start_from, rewind, step_n)
-                taken = [t for row in rows for t in row]
+            run.open(m, slots, P, queue, score=best, elastic=elastic)
+            taken, choice = run.drive(self.max_length, self.sampling, R, step_n)
         finally:
-            self.last_prefix_passes = {"main": session.prefix_passes, "held": held.prefix_passes if held is not None else 0}
-            if elastic:
-                self.last_elastic = {"moves": session.moves, "blocks": dict(session.blocks_hist)}
-            session.free()
-            if held is not None:
-                held.free()
-        cands = sorted(taken) if best else list(range(n * N))          # keep = "best": the winners only
-        first = {c: ((int(per[c // N].shape[0]) if self.exclude_prompt else 0) if continual_mode else None) for c in cands}
+            counts = run.close()
+            if counts:
+                self.last_prefix_passes = counts["prefix_passes"]
+                if elastic:
+                    self.last_elastic = counts["elastic"]
+        # taken[j] is a candidate of request j // M: all N of every request, or with keep = "best" the winner only
+        M = 1 if best else N
+        first = [((int(c.shape[0]) if self.exclude_prompt else 0) if continual_mode else None) for c in (per or [None] * n)]
+        ends = [run.encoded(j // M) + (t[0], t[1], first[j // M]) for j, t in enumerate(taken)]   # text_outs, len, tokens, len, first frame kept
         if length_aware:          # neighbours in decoded length share a call: a length-aware call computes over its group's common width
-            groups = [[cands[p] for p in g] for g in tail_groups([taken[c][1] - (first[c] or 0) for c in cands], 16)]
+            groups = tail_groups([e[3] - (e[4] or 0) for e in ends], 16)
         else:
-            groups = [cands[i: i + 16] for i in range(0, len(cands), 16)]
-        done = {}
+            groups = [list(range(i, min(i + 16, len(ends)))) for i in range(0, len(ends), 16)]
+        done = [None] * len(ends)
         for g in groups:                                                    # finished utterances, 16 at a time, through the batch forms
-            L, C = max(lens[c // N] for c in g), max(max(taken[c][1] for c in g), 1)
-            text_outs = torch.zeros((len(g), L, outs[g[0] // N].shape[-1]), dtype=torch.float32, device=m.device)
-            tokens = torch.zeros((len(g), C, nq), dtype=torch.int64, device=m.device)
-            for j, c in enumerate(g):
-                text_outs[j, : lens[c // N]] = outs[c // N]
-                tokens[j, : taken[c][1]] = taken[c][0]
-            r, cd = self._synthesise(text_outs, [lens[c // N] for c in g], tokens, [taken[c][1] for c in g], [first[c] for c in g], length_aware)
-            done.update(zip(g, zip(r, cd)))
-        rets, codecs = [done[c][0] for c in cands], [done[c][1] for c in cands]          # request order, however they were grouped
+            outs, lens, toks, out_lens, excl = (list(col) for col in zip(*(ends[j] for j in g)))
+            text_outs = torch.zeros((len(g), max(lens), outs[0].shape[-1]), dtype=torch.float32, device=m.device)
+            tokens = torch.zeros((len(g), max(max(out_lens), 1), nq), dtype=torch.int64, device=m.device)
+            for b in range(len(g)):
+                text_outs[b, : lens[b]] = outs[b]
+                tokens[b, : out_lens[b]] = toks[b]
+            for j, one in zip(g, zip(*self._synthesise(text_outs, lens, tokens, out_lens, excl, length_aware))):
+                done[j] = one
+        rets, codecs = [d[0] for d in done], [d[1] for d in done]          # candidate order, however they were grouped
         if best:
             return rets, codecs, choice
         if N == 1:

@@ -26,6 +26,10 @@ def _i32(vals: Sequence[int]):
     return (C.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
+def _u64(seed: int) -> int:
+    return int(seed) & (2 ** 64 - 1)
+
+
 def sampling_args(sampling: Union[bool, int, float]):
     """LauraGenModel.sampling_ids' `sampling` argument (laura_model.py:466-499) -> (mode, k, p) of fc_laura_decode_codec."""
     if isinstance(sampling, bool):
@@ -172,6 +176,10 @@ class LauraEngine:
         need = self._ws_need.get(key)
         if need is None:
             need = self._ws_need[key] = int(self.lib.fc_laura_workspace_bytes(self._h, B, L, Cmax, max_length))
+        return self._grown(need)
+
+    def _grown(self, need: int) -> torch.Tensor:
+        """The engine's one scratch buffer, at least `need` bytes of it: it only grows, and the old buffer goes before the new one comes."""
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -301,7 +309,7 @@ class LauraEngine:
             run.wait_stream(cur)
         self._check(self.lib.fc_laura_decode_codec(self._h, _ptr(text_outs), _i32(text_lengths), B, L, _ptr(continual),
                                                    _i32(continual_lengths) if continual is not None else None, Cmax, int(max_length),
-                                                   mode, k, p, int(seed) & (2 ** 64 - 1), _ptr(forced), _ptr(tokens), out_lens, _ptr(logp),
+                                                   mode, k, p, _u64(seed), _ptr(forced), _ptr(tokens), out_lens, _ptr(logp),
                                                    _ptr(ws), ws.numel(), C.c_void_p(run.cuda_stream)))
         if run is not cur:
             cur.wait_stream(run)
@@ -374,10 +382,7 @@ class LauraEngine:
         want = self.expected_tensors()
         cout = want[name + ".weight"][0] if name + ".weight" in want else 3 * cin
         y = torch.empty((B, T, cout), dtype=torch.float32, device=self.device)
-        need = 4 * B * (T + 8) * (cin + cout) * 2 + (1 << 20)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws
+        ws = self._grown(4 * B * (T + 8) * (cin + cout) * 2 + (1 << 20))
         form = {"auto": 1, "single": 2, "windowed": 3}[gemv_stage] if step_form else 0
         self._check(self.lib.fc_laura_linear(self._h, name.encode(), _ptr(x), B, T, form, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y
@@ -546,7 +551,7 @@ class DecodeSlots:
         t, n, tp, w, r = (rules or SamplingRules()).args()
         ticket = C.c_int32(-1)
         with self._launching() as stream:
-            self.engine._check(self.lib.fc_laura_slots_submit(h, row, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), t, n, tp, w, r,
+            self.engine._check(self.lib.fc_laura_slots_submit(h, row, max_length, mode, k, p, _u64(seed), t, n, tp, w, r,
                                                               C.byref(ticket), stream))
         self._submitted += 1
         self._ticket_max_length[int(ticket.value)] = max_length
@@ -693,14 +698,10 @@ class DecodeSlots:
             forced = self._token_rows(f"decode session start: slot {slot}", "forced", forced, max_length)
         mode, k, p = sampling_args(sampling)
         self._set_rules(slot, rules)
-        need = int(self.lib.fc_laura_slots_workspace_bytes(h, text_len, cont_len))
-        if eng._ws is None or eng._ws.numel() < need:
-            eng._ws = None
-            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = eng._ws
+        ws = eng._grown(int(self.lib.fc_laura_slots_workspace_bytes(h, text_len, cont_len)))
         with self._launching() as stream:
             eng._check(self.lib.fc_laura_slots_start(h, int(slot), _ptr(text), text_len, _ptr(continual), cont_len, max_length, mode, k, p,
-                                                     int(seed) & (2 ** 64 - 1), _ptr(forced), _ptr(ws), ws.numel(), stream))
+                                                     _u64(seed), _ptr(forced), _ptr(ws), ws.numel(), stream))
         self._max_length[int(slot)] = max_length
         self.prefix_passes += 1
 
@@ -775,18 +776,14 @@ class DecodeSlots:
         modes = [sampling_args(r["sampling"]) for _, r in rows]
         for slot, r in rows:
             self._set_rules(slot, r["rules"])
-        need = int(self.lib.fc_laura_slots_start_many_workspace_bytes(h, n, L, Cmax))
-        if eng._ws is None or eng._ws.numel() < need:
-            eng._ws = None
-            eng._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = eng._ws
+        ws = eng._grown(int(self.lib.fc_laura_slots_start_many_workspace_bytes(h, n, L, Cmax)))
         slots_a = _i32([slot for slot, _ in rows])
         tl_a = _i32([t.shape[0] for t in texts])
         cl_a = _i32([0 if c is None else c.shape[0] for c in conts]) if cont is not None else None
         ml_a = _i32([int(r["max_length"]) for _, r in rows])
         mode_a, k_a = _i32([m[0] for m in modes]), _i32([m[1] for m in modes])
         p_a = (C.c_float * n)(*[m[2] for m in modes])
-        seed_a = (C.c_uint64 * n)(*[int(r["seed"]) & (2 ** 64 - 1) for _, r in rows])
+        seed_a = (C.c_uint64 * n)(*[_u64(r["seed"]) for _, r in rows])
         with self._launching() as stream:
             eng._check(self.lib.fc_laura_slots_start_many(h, n, slots_a, _ptr(text), tl_a, L, _ptr(cont), cl_a, Cmax, ml_a, mode_a, k_a, p_a,
                                                           seed_a, _ptr(ws), ws.numel(), stream))
@@ -823,11 +820,11 @@ class DecodeSlots:
         self._set_rules(dst, rules)
         with self._launching() as stream:
             if source is None:
-                eng._check(self.lib.fc_laura_slots_start_from(h, dst, src, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), _ptr(forced),
+                eng._check(self.lib.fc_laura_slots_start_from(h, dst, src, max_length, mode, k, p, _u64(seed), _ptr(forced),
                                                               stream))
             else:                           # the prompt lies in another session of this engine; both sessions run on this stream
                 eng._check(self.lib.fc_laura_slots_start_from_session(h, dst, source._handle(), src, max_length, mode, k, p,
-                                                                      int(seed) & (2 ** 64 - 1), _ptr(forced), stream))
+                                                                      _u64(seed), _ptr(forced), stream))
         self._max_length[dst] = max_length
 
     @_on_device
@@ -856,7 +853,7 @@ class DecodeSlots:
         mode, k, p = sampling_args(sampling)
         self._set_rules(dst, rules)
         with self._launching() as stream:
-            self.engine._check(self.lib.fc_laura_slots_fork(h, dst, src, keep, max_length, mode, k, p, int(seed) & (2 ** 64 - 1), stream))
+            self.engine._check(self.lib.fc_laura_slots_fork(h, dst, src, keep, max_length, mode, k, p, _u64(seed), stream))
         self._max_length[dst] = max_length or self._max_length[src]
         self._n_gen[dst] = self._n_gen[src] if keep < 0 else keep
 
@@ -1403,9 +1400,16 @@ def pick_best(scores: Sequence[tuple]) -> int:
     return best
 
 
+def keep_best(flat: Sequence[tuple], samples: int) -> list:
+    """``pick_best`` over each request's `samples` consecutive candidates of `flat` (takes or collected entries in candidate order, the
+    score last): [(k, take of candidate k)], one per request."""
+    rows = (flat[i: i + samples] for i in range(0, len(flat), samples))
+    return [(k, row[k]) for row in rows for k in [pick_best([t[-1] for t in row])]]
+
+
 def drive_best(session, slots: int, n_requests: int, samples: int, retries: int, max_length: int, start, start_from, rewind,
                step_n: int = 1) -> list:
-    """``drive_samples`` (retries = 0) or ``drive_retries`` on a session opened with score=True, every candidate taken with its score
+    """``drive_retries`` (retries = 0: ``drive_samples``) on a session opened with score=True, every candidate taken with its score
     (``session.take(slot, return_score=True)``: the last element of the take), then ``pick_best`` per request.  The drivers, their
     arrival order and which candidates start from a sibling are unchanged; a rewound candidate is ranked by its last attempt, whose
     score is that of its whole final path.  Returns [(k, take of candidate k)], one per request."""
@@ -1420,15 +1424,101 @@ def drive_best(session, slots: int, n_requests: int, samples: int, retries: int,
         def take(self, slot):
             return session.take(slot, return_score=True)
 
-    if retries == 0:
-        rows = drive_samples(_Scored(), slots, n_requests, samples, start, start_from, step_n)
-    else:
-        rows = drive_retries(_Scored(), slots, n_requests, samples, retries, max_length, start, start_from, rewind, step_n)
-    kept = []
-    for row in rows:
-        k = pick_best([t[-1] for t in row])
-        kept.append((k, row[k]))
-    return kept
+    rows = drive_retries(_Scored(), slots, n_requests, samples, retries, max_length, start, start_from, rewind, step_n)
+    return keep_best([t for row in rows for t in row], samples)
+
+
+class CandidateRun:
+    """What ``Text2Audio.generate_many`` runs its candidates on, no device and no Text2Audio in it: the main session, the holding session
+    of prefill = P rows with its bookkeeping, and how candidate c = request * samples + k is started, rewound and submitted, each stated
+    once, so that every option meets the same calls.  ``encode(i)`` gives request i's (text_outs [L, D], L) as a one-utterance call
+    does; `continual` the prompt tokens per request, or None.  ``open``, then ``drive``; ``close`` frees whatever was opened."""
+
+    def __init__(self, n_requests: int, samples: int, seeds: Sequence[int], rules: Optional[SamplingRules], encode, continual=None):
+        self.n, self.N, self.seeds, self.rules, self.encode = int(n_requests), int(samples), seeds, rules, encode
+        self.continual = continual if continual is not None else [None] * self.n
+        self.max_length, self.sampling = None, None          # of every candidate: ``drive`` sets them
+        self.texts: Dict[int, tuple] = {}                     # request -> (text_outs, len)
+        self.session = self.held = self.plan = None
+
+    def open(self, model, slots: int, prefill: int = 0, queue: bool = False, score: bool = False, elastic: bool = False) -> None:
+        """The main session of `slots` slots (wide above 16) and, with prefill = P > 0, the holding session of P rows.  A queued
+        session is opened on the holding session, which therefore comes first, with room for every ticket in flight."""
+        self.slots, self.rows, self.queued, self.scored, self.elastic = slots, int(prefill), bool(queue), bool(score), bool(elastic)
+        more = {key: True for key, on in (("score", score), ("wide", int(slots) > 16), ("elastic", elastic)) if on}
+        hold = lambda: model.open_decode(self.rows, logp=False)
+        if queue:
+            self.held = hold()
+            more.update(queue=int(slots) + self.rows * self.N, source=self.held)
+        self.session = model.open_decode(slots, logp=False, **more)
+        if self.rows and not queue:
+            self.held, self.plan = hold(), HeldPrompts(self.rows, self.n, self.N)
+
+    def close(self) -> Optional[dict]:
+        """Frees the sessions that were opened.  Returns the run's {"prefix_passes": {"main", "held"}, "elastic": {"moves", "blocks"}
+        or None}; None if the main session never opened."""
+        session, held, self.session, self.held = self.session, self.held, None, None
+        counts = None if session is None else dict(
+            prefix_passes={"main": session.prefix_passes, "held": held.prefix_passes if held is not None else 0},
+            elastic={"moves": session.moves, "blocks": dict(session.blocks_hist)} if self.elastic else None)
+        for opened in (session, held):
+            if opened is not None:
+                opened.free()
+        return counts
+
+    def encoded(self, i: int) -> tuple:
+        """Request i's (text_outs, len): encoded when first needed, alone, so its text_outs are those of a one-utterance call."""
+        if i not in self.texts:
+            self.texts[i] = self.encode(i)
+        return self.texts[i]
+
+    def fill(self, batch) -> None:
+        """[(row, request)] into the holding session in one prefix pass; held rows start greedy with max_length 1, what they sample
+        is never used."""
+        requests = {}
+        for row, q in batch:
+            text_outs, text_len = self.encoded(q)
+            requests[row] = dict(text_outs=text_outs, text_len=text_len, max_length=1, sampling=False, continual=self.continual[q])
+        self.held.start_many(requests)
+
+    def start(self, slot: int, c: int, src: Optional[int] = None) -> None:
+        """Candidate c into `slot`, by one of three ways that give the same bits: with prefill EVERY candidate, first or sibling, is a
+        copy from its request's row of the holding session (filled first if the request is not held); else a copy of the sibling
+        running in slot `src`; else its own prefix pass."""
+        i, args = c // self.N, (self.max_length, self.sampling, self.seeds[c])
+        if self.plan is not None:
+            todo = self.plan.need(i)
+            if todo:
+                self.fill(todo)
+            self.session.start_from(slot, self.plan.start(i), *args, rules=self.rules, source=self.held)
+        elif src is not None:
+            self.session.start_from(slot, src, *args, rules=self.rules)
+        else:
+            self.session.start(slot, *self.encoded(i), *args, self.continual[i], rules=self.rules)
+
+    def start_from(self, slot: int, src: int, c: int) -> None:
+        self.start(slot, c, src)
+
+    def rewind(self, slot: int, c: int, keep: int, attempt: int) -> None:
+        self.session.rewind(slot, keep, self.max_length, self.sampling, retry_seed(self.seeds[c], attempt), rules=self.rules)
+
+    def submit(self, row: int, c: int) -> int:
+        return self.session.submit(row, self.max_length, self.sampling, self.seeds[c], rules=self.rules)
+
+    def drive(self, max_length: int, sampling, retries: int = 0, step_n: int = 1) -> tuple:
+        """Every candidate through the driver the options name.  Returns (taken, choice): taken is flat, what ``take`` / ``collect`` gave
+        per candidate in candidate order, and choice None; on a session with scores taken holds each request's winner only and
+        choice[i] = (k, its mean log-probability per step) names it."""
+        self.max_length, self.sampling = max_length, sampling
+        slot_drivers = (self.slots, self.n, self.N, retries, max_length, self.start, self.start_from, self.rewind, step_n)
+        if self.queued:
+            flat = drive_queue(self.session, self.rows, self.n, self.N, self.fill, self.submit, step_n)
+        elif not self.scored:                # retries = 0 rewinds nothing: drive_samples
+            flat = [t for row in drive_retries(self.session, *slot_drivers) for t in row]
+        if not self.scored:
+            return flat, None
+        kept = keep_best(flat, self.N) if self.queued else drive_best(self.session, *slot_drivers)
+        return [t for _, t in kept], [(k, t[-1][0] / t[-1][1]) for k, t in kept]
 
 
 class LauraGenMI355X:
@@ -1470,7 +1560,7 @@ class LauraGenMI355X:
     def _next_seed(self) -> int:
         # the reference draws from torch's global generator; a generation here is a function of (torch seed, call index)
         self._seed_counter += 1
-        return (int(torch.initial_seed()) * 1000003 + self._seed_counter) & (2 ** 64 - 1)
+        return _u64(int(torch.initial_seed()) * 1000003 + self._seed_counter)
 
     @torch.no_grad()
     def decode_codec(self, text: torch.Tensor, text_lengths: torch.Tensor, max_length: int = 30 * 25,

@@ -84,6 +84,9 @@ SYMBOLS = {
     "fc_engine_set_row_nq": (C.c_int, [_P, _P, C.c_int, _P]),
     "fc_engine_set_rvq_beam": (C.c_int, [_P, C.c_int, _P]),
     "fc_rvq_encode_beam": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    # a stage count per row by target SNR: host float64 ratios [B] (None clears), min_nq, device outputs n_q_rows / row_errors / stage_errors
+    "fc_engine_set_rate": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "fc_rvq_encode_rate": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "fc_rvq_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_q0_source_frames": (C.c_int, [C.c_int, _P]),
     "fc_layer_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

@@ -75,6 +75,7 @@ class Speech2Token:
         # quantiser); a call's own rvq_beam= goes first.  Refused here, before any call, for a model that cannot take it.
         from ..engine import rvq_beam_width
         self.rvq_beam = rvq_beam_width(model.arch, rvq_beam)
+        self.last_n_q_rows = self.last_row_snr_db = None          # of the last call made with target_snr_db
 
     @torch.no_grad()
     def __call__(
@@ -87,6 +88,8 @@ class Speech2Token:
             run_mod: str = "inference",
             speech_lengths: Optional[Union[torch.Tensor, np.ndarray]] = None,
             rvq_beam: Optional[int] = None,
+            target_snr_db=None,
+            min_n_q: int = 1,
     ):
         """Returns (code_indices, code_embeddings, recon_speech, sub_quants) like the reference (:86-134).
 
@@ -95,7 +98,15 @@ class Speech2Token:
         (EncodecMI355X.inference).
 
         rvq_beam (not in the reference; default None = the instance's, whose default 1 is the reference's greedy quantiser): 2, 4 or 8
-        hypotheses per frame through the quantiser's stages in the modes that encode; the two decode modes do not quantise."""
+        hypotheses per frame through the quantiser's stages in the modes that encode; the two decode modes do not quantise.
+
+        target_snr_db, min_n_q (not in the reference; default None = off): in the modes that encode, every row takes the fewest stages that
+        reach its target SNR in the quantiser's domain (EncodecMI355X.inference).  The 4-tuple stays; the chosen counts of the last such
+        call stand in ``last_n_q_rows`` (device int32 [B]) and their SNRs in ``last_row_snr_db``; they are None after any other call."""
+        if target_snr_db is not None and run_mod not in ("inference", "encode"):
+            raise ValueError(f"target_snr_db belongs to the modes that encode (inference, encode), not run_mod={run_mod!r}")
+        rate = {} if target_snr_db is None else dict(target_snr_db=target_snr_db, min_n_q=min_n_q)
+        self.last_n_q_rows = self.last_row_snr_db = None
         rvq_beam = getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam       # (an instance built around a ready model has none)
         if ppg is not None:
             raise NotImplementedError("ppg conditioning (codec_semantic_aug) is outside the hot-path scope")
@@ -104,9 +115,10 @@ class Speech2Token:
         speech = speech.to(self.model.device)
         if run_mod == "inference":
             ret = self.model.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, speech_lengths=speech_lengths,
-                                       rvq_beam=rvq_beam)
+                                       rvq_beam=rvq_beam, **rate)
         elif run_mod == "encode":
-            ret = self.model.inference_encoding(speech, need_recon=False, bit_width=bit_width, speech_lengths=speech_lengths, rvq_beam=rvq_beam)
+            ret = self.model.inference_encoding(speech, need_recon=False, bit_width=bit_width, speech_lengths=speech_lengths, rvq_beam=rvq_beam,
+                                                **rate)
         elif run_mod == "decode_emb":
             ret = self.model.inference_decoding_emb(speech, token_lengths=speech_lengths)
         else:
@@ -118,6 +130,7 @@ class Speech2Token:
             speech = speech[:, :, :nq]
             logging.info("use %d quantizers.", speech.shape[-1])
             ret = self.model.inference_decoding(speech, token_lengths=speech_lengths)
+        self.last_n_q_rows, self.last_row_snr_db = ret.get("n_q_rows"), ret.get("row_snr_db")
         if self.check_status:
             self.model.engine.check_status(sync=True)
         if self.dtype != "float32":
@@ -238,7 +251,12 @@ def inference_modelscope(
             os.makedirs(output_path, exist_ok=True)
         file_sr = kwargs.get("file_sampling_rate")
         should_resample = file_sr not in (None, sampling_rate)               # reference :270-273
-        indices_writer, sub_quants_writer = None, None
+        indices_writer, sub_quants_writer, n_q_writer = None, None, None
+        target_snr_db = kwargs.get("target_snr_db")
+        if target_snr_db is not None and output_path is not None:
+            # next to the indices: `key k snr_db` per utterance.  The indices files keep their shape with zeros behind k; a decoder needs k
+            # (a bit_width per row), since code 0 is a valid code
+            n_q_writer = open(os.path.join(output_path, "codec_n_q.txt"), "wt")
         ark_indices = kwargs.get("indices_save_type") == "ark"
         if kwargs.get("need_indices"):
             if ark_indices:
@@ -303,9 +321,11 @@ def inference_modelscope(
             return lines, results
 
         def _drain(job):
-            keys, speech_length, tok_host, sq_host, fut = job
+            keys, speech_length, tok_host, sq_host, fut, nq_host = job
             lines, results = fut.result()
             result_list.extend(results)
+            if nq_host is not None and n_q_writer is not None:
+                n_q_writer.write("".join(f"{key} {int(k)} {float(snr):.4f}\n" for key, k, snr in zip(keys, *nq_host)))
             if lines:
                 indices_writer.write("".join(lines))
             for i, key in enumerate(keys):               # Kaldi ark writers keep file offsets: sequential, in order
@@ -338,7 +358,9 @@ def inference_modelscope(
                     batch["speech_lengths"] = speech_length
                 bw = param_dict["bit_width"] if param_dict is not None and "bit_width" in param_dict else bit_width
                 token_id, token_emb, recon_speech, sub_quants = my_model(**batch, need_recon=True, bit_width=bw,
-                                                                         use_scale=use_scale, run_mod=run_mod)
+                                                                         use_scale=use_scale, run_mod=run_mod,
+                                                                         **({} if target_snr_db is None else dict(
+                                                                             target_snr_db=float(target_snr_db), min_n_q=int(kwargs.get("min_n_q") or 1))))
                 # device-side failures cannot raise in-line like the reference's F.embedding / asserts do: synchronise and ask the
                 # engine before anything of this batch is written (corrupt token files, LSTM barrier timeout)
                 my_model.model.engine.check_status(sync=True)
@@ -347,14 +369,15 @@ def inference_modelscope(
                 recon_host = recon_speech.cpu() if recon_speech is not None else None
                 tok_host = [x.cpu().contiguous() for x in token_id] if (token_id is not None and indices_writer is not None) else None
                 sq_host = [x.cpu() for x in sub_quants] if (sub_quants is not None and sub_quants_writer is not None) else None
-                jobs.append((keys, speech_length, tok_host, sq_host, pool.submit(_write_batch, keys, speech_length, recon_host, tok_host)))
+                nq_host = None if target_snr_db is None else (my_model.last_n_q_rows.tolist(), my_model.last_row_snr_db.tolist())
+                jobs.append((keys, speech_length, tok_host, sq_host, pool.submit(_write_batch, keys, speech_length, recon_host, tok_host), nq_host))
                 while len(jobs) > 3:                                                # bounds the host memory held by queued batches
                     _drain(jobs.pop(0))
             while jobs:
                 _drain(jobs.pop(0))
         finally:
             pool.shutdown(wait=True)
-        for w in (indices_writer, sub_quants_writer):
+        for w in (indices_writer, sub_quants_writer, n_q_writer):
             if w is not None:
                 w.close()
         return result_list
@@ -418,6 +441,10 @@ def get_parser():
     # not in the reference: hypotheses per frame through the quantiser's stages (1: the reference's greedy quantiser); same files, no frame
     # coded worse
     g.add_argument("--rvq_beam", type=int, choices=[1, 2, 4, 8], default=1)
+    # not in the reference: every utterance takes the fewest quantiser stages (at least --min_n_q, at most those of --bit_width) that reach
+    # this SNR in the quantiser's domain; codec_n_q.txt (`key k snr_db`) is written next to the indices, which keep their shape
+    g.add_argument("--target_snr_db", type=float, default=None)
+    g.add_argument("--min_n_q", type=int, default=1)
     return p
 
 

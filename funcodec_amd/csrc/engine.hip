@@ -16,6 +16,7 @@
 #include "../../include/funcodec_amd.h"
 #include "kernels.h"
 #include "rvq_beam_kernels.h"
+#include "rvq_rate_kernels.h"
 #include "laura_kernels.h"
 #include "ragged_kernels.h"
 #include "seq_kernels.h"
@@ -165,6 +166,20 @@ struct fc_engine {
     int* row_nq_dev = nullptr;
     size_t row_nq_cap = 0;
     int rvq_beam = 1;                        // width of the quantiser's search over the stages for the calls that follow (fc_engine_set_rvq_beam); 1: greedy
+    // a stage count per row chosen on the device by a target SNR, for the offline calls that follow (fc_engine_set_rate; csrc/rvq_rate_kernels.h
+    // states the rule): the host copy of the ratios (empty = none set), their device copy and the table of chosen counts -- NOT row_nq_dev,
+    // which still holds the caps the first pass read.  Both tables only grow, like row_nq_dev.  The three outputs are the caller's.
+    struct Rate {
+        std::vector<double> ratio;
+        int min_nq = 1;
+        double* ratio_dev = nullptr;
+        int* k_dev = nullptr;
+        size_t cap = 0;
+        int32_t* n_q_out = nullptr;
+        double* row_err_out = nullptr;
+        float* stage_err_out = nullptr;
+        bool on() const { return !ratio.empty(); }
+    } rate;
     bool lstm_persist_ok = true;             // cleared after a grid-barrier timeout: later calls take the per-step launch path
     int persist_checked_B = -1; bool persist_checked_val = false;
     // optional event timing
@@ -1906,9 +1921,32 @@ int row_nq_check(const fc_engine* e, int rows, int n_q) {
     return 0;
 }
 
+// ---- a stage count per row by target SNR (fc_engine_set_rate) ----------------------------------------
+// The rule of an offline call made while a rate is set, checked BEFORE its first launch: as many rows as the rate has, and the floor no
+// larger than n_q or any row's cap.
+int rate_check(const fc_engine* e, int rows, int n_q) {
+    if (!e->rate.on()) return 0;
+    if ((int)e->rate.ratio.size() != rows)
+        return fail("a rate is set for " + std::to_string(e->rate.ratio.size()) + " rows (fc_engine_set_rate); this call has " + std::to_string(rows) +
+                    " (clear it with NULL ratios)");
+    if (e->rate.min_nq > n_q)
+        return fail("fc_engine_set_rate: min_nq = " + std::to_string(e->rate.min_nq) + " lies above n_q = " + std::to_string(n_q));
+    for (size_t b = 0; b < e->row_nq.size(); ++b)
+        if (e->rate.min_nq > e->row_nq[b])
+            return fail("fc_engine_set_rate: min_nq = " + std::to_string(e->rate.min_nq) + " lies above the cap of row " + std::to_string(b) + " (" +
+                        std::to_string(e->row_nq[b]) + " stages, fc_engine_set_row_nq)");
+    return 0;
+}
+
+// an encode push of a session while a rate is set
+int rate_refuse_session(const fc_engine* e, const char* who) {
+    if (!e->rate.on()) return 0;
+    return fail(std::string(who) + ": a rate is set (fc_engine_set_rate): a stage count per row by target SNR is for offline calls only; clear it with NULL ratios");
+}
+
 // ---- composite paths (each usable in dry mode for workspace sizing / work accounting) ---------------
 int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
-                float** quant_bdt_out);
+                float** quant_bdt_out, const fc::RagLen* offline_rows = nullptr);
 int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* codes, float* quantized,
               float* sub_quants, float* scale, float* enc_out, float** quant_bdt_out, const Pass& p = Pass()) {
     const int B = cx.B, D = e->arch.dimension, Tf = frames_for(e, T);
@@ -1921,12 +1959,16 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
     }
     fc::Src s; s.ptr = wav; s.div = sc; s.used = e->arch.audio_normalize ? 3 : 1;
     Act last = e->arch.model_type == 1 ? run_encoder_2d(e, cx, wav, T, sc) : run_encoder(e, cx, p, s, T);
-    return do_quantize(e, cx, last, Tf, n_q, codes, quantized, sub_quants, enc_out, quant_bdt_out);
+    // an offline call (whole batch width, or a ragged pass with the frames of every row): the one place the rate control applies
+    fc::RagLen rows;
+    if (p.kind == Pass::Ragged) { rows.lens = p.lengths; rows.div = total_hop(e); }
+    return do_quantize(e, cx, last, Tf, n_q, codes, quantized, sub_quants, enc_out, quant_bdt_out, &rows);
 }
 
 // the quantiser behind the encoder's last conv (per frame: the offline call and a streaming push share it)
+// offline_rows (an offline call; null in a session push): the frames of every row, for the rate control (fc_engine_set_rate)
 int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
-                float** quant_bdt_out) {
+                float** quant_bdt_out, const fc::RagLen* offline_rows) {
     const int B = cx.B, D = e->arch.dimension;
     const int Dc = e->cdim();
     const bool ranged = e->arch.codec_range > 0.f;
@@ -1970,6 +2012,28 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
         cx.launch("rvq beam sum", "", [&] {
             return fc::launch_rvq_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf, cx.st, nq_rows);
         });
+    }
+    // fc_engine_set_rate: the errors of every stage from the codes, a count per row, then everything from the first k_b codes.  A dry pass
+    // always counts the two buffers: a workspace is sized before anybody knows whether a rate will be set.
+    if (offline_rows && (cx.dry || e->rate.on())) {
+        float* serr = cx.alloc<float>((size_t)(n_q + 1) * B * Tf);
+        double* rerr = cx.alloc<double>((size_t)B * (n_q + 1));
+        if (e->rate.on()) {
+            if (!cx.dry && (int)e->rate.ratio.size() != B) cx.fail("internal: a rate of another batch width");
+            if (e->rate.stage_err_out) serr = e->rate.stage_err_out;
+            if (e->rate.row_err_out) rerr = e->rate.row_err_out;
+            cx.launch("rvq stage errors", "", [&] {
+                return fc::launch_rvq_stage_errors(xq, codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, serr, Tf, nq_rows, *offline_rows, cx.st);
+            });
+            cx.launch("rvq rate rows", "", [&] {
+                return fc::launch_rvq_rate_rows(serr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.k_dev, e->rate.n_q_out, rerr,
+                                                cx.st);
+            });
+            cx.launch("rvq rate sum", "", [&] {
+                return fc::launch_rvq_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf, cx.st, e->rate.k_dev);
+            });
+            cx.launch("rvq rate zero codes", "", [&] { return fc::launch_rvq_rate_zero_codes(codes, B * Tf, Tf, n_q, e->rate.k_dev, cx.st); });
+        }
     }
     float* qbdt = qbdt_c;
     if (e->q_proj) {       // output_proj (costume_quantizer.py:92-94): decoder input [B][D][Tf] and the returned embeddings [B][Tf][D]
@@ -2928,6 +2992,7 @@ int fc_encode(fc_engine* e, const float* wav, int B, int T, int n_q, int64_t* co
     if (!wav || !codes || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     if (row_nq_check(e, B, n_q)) return 1;
+    if (rate_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return do_encode(e, cx, wav, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr);
 }
@@ -2957,6 +3022,7 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
     if (!wav || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     if (row_nq_check(e, B, n_q)) return 1;
+    if (rate_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     float* sc = scale;
     if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
@@ -2990,6 +3056,7 @@ int fc_encode_ragged(fc_engine* e, const float* wav, const int32_t* lengths, int
     if (!wav || !lengths || !codes || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     if (row_nq_check(e, B, n_q)) return 1;
+    if (rate_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return ragged_encode(e, cx, wav, lengths, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr, nullptr);
 }
@@ -3023,6 +3090,7 @@ int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengt
     if (!wav || !lengths || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     if (row_nq_check(e, B, n_q)) return 1;
+    if (rate_check(e, B, n_q)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     float* sc = scale;
     if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
@@ -3099,6 +3167,67 @@ int fc_rvq_encode_beam(fc_engine* e, const float* x, int N, int n_q, int width, 
         HIP_TRY(fc::launch_rvq_beam(x, N, Dc, K, n_q, width, e->cb, e->cb_frag, e->enorm, codes, paths, errors, Tf, st, row_nq_table(e)));
         if (quantized) HIP_TRY(fc::launch_rvq_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, st, row_nq_table(e)));
     }
+    return 0;
+}
+
+int fc_engine_set_rate(fc_engine* e, const double* ratio_rows, int B, int min_nq, int32_t* n_q_rows_out, double* row_errors_out,
+                       float* stage_errors_out, void* stream) {
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!ratio_rows) { e->rate.ratio.clear(); e->rate.n_q_out = nullptr; e->rate.row_err_out = nullptr; e->rate.stage_err_out = nullptr; return 0; }
+    if (B <= 0) return fail("fc_engine_set_rate: a rate holds at least one row");
+    if (!n_q_rows_out) return fail("fc_engine_set_rate: n_q_rows_out (device int32 [B]) takes the chosen stage counts");
+    if (e->arch.q0_ds_ratio > 1)
+        return fail("fc_engine_set_rate: quantizer_conf.q0_ds_ratio > 1: stage 0 quantises another frame's row, so a frame's residual is not its input "
+                    "minus its codes");
+    if (min_nq < 1 || min_nq > e->arch.num_quantizers)
+        return fail("fc_engine_set_rate: min_nq lies in [1, num_quantizers = " + std::to_string(e->arch.num_quantizers) + "], got " + std::to_string(min_nq));
+    for (int b = 0; b < B; ++b)
+        if (!(ratio_rows[b] >= 0.0))
+            return fail("fc_engine_set_rate: row " + std::to_string(b) + ": a ratio 10^(-target_snr_db / 10) is neither negative nor NaN");
+    if ((size_t)B > e->rate.cap) {      // larger tables; the old ones stay allocated for the launches that may still read them
+        const size_t cap = std::max<size_t>(64, 2 * (size_t)B);
+        void *pr = nullptr, *pk = nullptr;
+        HIP_TRY(hipMalloc(&pr, cap * sizeof(double)));
+        e->dev_allocs.push_back(pr);
+        HIP_TRY(hipMalloc(&pk, cap * sizeof(int)));
+        e->dev_allocs.push_back(pk);
+        e->rate.ratio_dev = (double*)pr; e->rate.k_dev = (int*)pk; e->rate.cap = cap;
+    }
+    // the source of the copy is the engine's own host copy, which lives as long as the engine: the caller's array may go at once
+    e->rate.ratio.assign(ratio_rows, ratio_rows + B);
+    if (hipError_t er = hipMemcpyAsync(e->rate.ratio_dev, e->rate.ratio.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream);
+        er != hipSuccess) {
+        e->rate.ratio.clear();
+        return fail(std::string("fc_engine_set_rate: copy of the ratios: ") + hipGetErrorString(er));
+    }
+    e->rate.min_nq = min_nq;
+    e->rate.n_q_out = n_q_rows_out; e->rate.row_err_out = row_errors_out; e->rate.stage_err_out = stage_errors_out;
+    return 0;
+}
+
+int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, void* stream) {
+    if (check_ready(e)) return 1;
+    if (!x || !codes || N <= 0) return fail("bad argument");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (!e->rate.on()) return fail("fc_rvq_encode_rate: no rate is set (fc_engine_set_rate)");
+    if (!e->rate.row_err_out || !e->rate.stage_err_out)
+        return fail("fc_rvq_encode_rate: the hook has no workspace: fc_engine_set_rate with row_errors_out and stage_errors_out");
+    if (rvq_beam_check(e, width, "fc_rvq_encode_rate")) return 1;
+    const int B = (int)e->rate.ratio.size(), Tf = N / B;
+    if (N % B != 0) return fail("fc_rvq_encode_rate: with a rate for " + std::to_string(B) + " rows, N must be a multiple of that");
+    if (row_nq_check(e, B, n_q)) return 1;
+    if (rate_check(e, B, n_q)) return 1;
+    const int Dc = e->cdim(), K = e->arch.codebook_size;
+    hipStream_t st = (hipStream_t)stream;
+    const fc::RagLen rows;
+    HIP_TRY(fc::launch_rvq_encode(x, N, Dc, K, n_q, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, nullptr, Tf, st, nullptr, row_nq_table(e)));
+    if (width > 1) HIP_TRY(fc::launch_rvq_beam(x, N, Dc, K, n_q, width, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, Tf, st, row_nq_table(e)));
+    HIP_TRY(fc::launch_rvq_stage_errors(x, codes, N, Dc, K, n_q, e->cb, e->rate.stage_err_out, Tf, row_nq_table(e), rows, st));
+    HIP_TRY(fc::launch_rvq_rate_rows(e->rate.stage_err_out, B, Tf, n_q, row_nq_table(e), rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.k_dev,
+                                     e->rate.n_q_out, e->rate.row_err_out, st));
+    if (quantized) HIP_TRY(fc::launch_rvq_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, st, e->rate.k_dev));
+    HIP_TRY(fc::launch_rvq_rate_zero_codes(codes, N, Tf, n_q, e->rate.k_dev, st));
     return 0;
 }
 
@@ -3637,6 +3766,7 @@ int fc_stream_encode(fc_stream* S, const float* wav, int Tc, int final, int64_t*
     const int Tfc = final ? frames_for(e, Tc) : Tc / hop;
     if (frames_fit(S, false, Tfc)) return 1;
     if (row_nq_check(e, S->B, S->n_q)) return 1;
+    if (rate_refuse_session(e, "fc_stream_encode")) return 1;
     // the first push of an utterance (reflection staging) and the final one (extra padding) are one-offs: never cached
     const Session::GraphKey key = graph_key(*S, kFormEncode, Tc, S->enc_pushes, 0, {wav, codes, quantized, enc_out}, workspace, workspace_bytes, stream);
     S->broken = true;                                   // until the whole push is enqueued: a failure in between leaves mixed carries
@@ -3768,6 +3898,7 @@ int fc_slots_encode(fc_slots* Q, const float* wav, int Tc, const int32_t* sample
     if (!wav || !samples || !flags || !codes) return fail("bad argument");
     if (slots_check(Q, false, samples, flags, Tc, Q->max_chunk)) return 1;
     if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
+    if (rate_refuse_session(Q->e, "fc_slots_encode")) return 1;
     const Session::GraphKey key = graph_key(*Q, kFormEncode, Tc, Q->enc_pushes, 0, {wav, codes, quantized, enc_out, scale}, workspace, workspace_bytes, stream);
     const int err = session_push(
         Q, &key, workspace, workspace_bytes, stream, [&](hipStream_t st) { return slots_upload(Q, false, samples, flags, workspace, workspace_bytes, st); },

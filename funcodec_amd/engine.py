@@ -90,6 +90,78 @@ def rvq_beam_width(arch, width) -> int:
     return int(width)
 
 
+def rate_refusal(arch) -> Optional[str]:
+    """Why a model of this architecture takes no stage count per row by target SNR (``target_snr_db``), or None.  The configuration key
+    is named, as ``ragged_refusal`` does."""
+    if arch.segment_length is not None:
+        return "target_snr_db is not available with model_conf.segment_dur (segments are extra batch rows of the engine call)"
+    if arch.bypass_quantizer:
+        return "target_snr_db is not available with model_conf.bypass_quantizer (the quantiser's result is dropped)"
+    if arch.q0_ds_ratio > 1:
+        return ("target_snr_db is not available for quantizer_conf.q0_ds_ratio > 1 (stage 0 quantises another frame's row, so a frame's "
+                "residual is not its input minus its codes)")
+    return None
+
+
+def rate_targets(arch, target, B: int) -> list:
+    """The ratios rho_b = 10^(-target_b / 10) of a ``target_snr_db`` that is one value or B of them, as B Python floats (float64: the
+    device multiplies the same doubles); raises before any engine call.  +inf is "the best k" (rho = 0), -inf is "the floor"."""
+    why = rate_refusal(arch)
+    if why:
+        raise EngineError(why)
+    if isinstance(target, numbers.Real) or (hasattr(target, "ndim") and target.ndim == 0):
+        target = [float(target)] * B
+    elif hasattr(target, "ndim"):
+        if target.ndim != 1:
+            raise EngineError(f"target_snr_db must be one value or a sequence / 1-D tensor of one per row, got shape {tuple(target.shape)}")
+        target = target.tolist()
+    target = list(target)
+    if len(target) != B:
+        raise EngineError(f"target_snr_db must hold one entry per row ({B}), got {len(target)}")
+    out = []
+    for b, v in enumerate(target):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v:
+            raise EngineError(f"row {b}: target_snr_db is a number of dB (not NaN), got {v!r}")
+        v = float(v)
+        out.append(0.0 if v == float("inf") else float("inf") if v == float("-inf") else float(np.float64(10.0) ** np.float64(-v / 10.0)))
+    return out
+
+
+def rate_min_nq(arch, min_n_q, cap: Optional[int] = None, rows=None) -> int:
+    """A checked ``min_n_q``: an integer in [1, cap] (cap: ``num_quantizers`` unless given) and no larger than any per-row cap."""
+    cap = arch.num_quantizers if cap is None else int(cap)
+    if isinstance(min_n_q, bool) or not isinstance(min_n_q, numbers.Integral) or not 1 <= int(min_n_q) <= cap:
+        raise EngineError(f"min_n_q lies in [1, {cap}], got {min_n_q!r}")
+    if rows is not None:
+        for b, k in enumerate(rows):
+            if int(min_n_q) > k:
+                raise EngineError(f"min_n_q = {int(min_n_q)} lies above the cap of row {b} ({k} stages)")
+    return int(min_n_q)
+
+
+def rate_pick(E, ratio: float, min_n_q: int, cap: int) -> int:
+    """The stage count of one row (csrc/rvq_rate_kernels.h, include/funcodec_amd.h), a pure function of its float64 row errors
+    E[0 .. cap] (E[0]: the input energy), its ratio 10^(-target / 10), the floor and the cap:
+      - energies that are not all finite: cap (what the plain call gives the row);
+      - E[0] == 0 (digital silence): min_n_q;
+      - the smallest k in [min_n_q, cap] with E[k] <= E[0] * ratio;
+      - no such k: the k in that range with the smallest E[k], first on ties."""
+    E = [float(v) for v in E[:cap + 1]]
+    lo = min(max(int(min_n_q), 1), cap)
+    if not all(np.isfinite(v) for v in E):
+        return cap
+    if E[0] == 0.0:
+        return lo
+    thr = float(np.float64(E[0]) * np.float64(ratio))
+    best = lo
+    for k in range(lo, cap + 1):
+        if E[k] <= thr:
+            return k
+        if E[k] < E[best]:
+            best = k
+    return best
+
+
 def row_nq_list(arch, rows, B: int, cap: Optional[int] = None) -> list:
     """The per-row stage counts of a call as a list of B ints in [1, cap] (cap: ``num_quantizers`` unless given); raises before any
     engine call -- a bad count or a list of the wrong length refuses the call as a whole."""
@@ -110,6 +182,13 @@ def row_nq_list(arch, rows, B: int, cap: Optional[int] = None) -> list:
             raise EngineError(f"row {b}: a stage count lies in [1, {cap}], got {v!r}")
         out.append(int(v))
     return out
+
+
+class _Ratios(list):
+    """checked ratios 10^(-target / 10) on their way through the micro-batches of a call (CodecEngine._rate_in)"""
+    def __getitem__(self, i):
+        r = super().__getitem__(i)
+        return _Ratios(r) if isinstance(i, slice) else r
 
 
 class CodecEngine:
@@ -321,6 +400,35 @@ class CodecEngine:
         finally:
             self.lib.fc_engine_set_row_nq(self._h, None, 0, None)
 
+    @contextlib.contextmanager
+    def _rate(self, ratios, min_n_q: int, n_q: int, Tf: int, want_stage_errors: bool = False):
+        """The engine's rate (fc_engine_set_rate) for the offline call made inside: a stage count per row chosen on the device; cleared on
+        the way out, whatever happened, as _row_nq does.  ratios: None (nothing is set, None is yielded) or a checked list (rate_targets).
+        Yields dict(n_q_rows [B] i32, row_errors [B, n_q + 1] f64, stage_errors [n_q + 1, B, Tf] f32 | None): device tensors the call
+        fills; nothing is read back."""
+        if ratios is None:
+            yield None
+            return
+        B = len(ratios)
+        out = dict(n_q_rows=torch.empty((B,), dtype=torch.int32, device=self.device),
+                   row_errors=torch.empty((B, n_q + 1), dtype=torch.float64, device=self.device),
+                   stage_errors=torch.empty((n_q + 1, B, Tf), dtype=torch.float32, device=self.device) if want_stage_errors else None)
+        self._check(self.lib.fc_engine_set_rate(self._h, (C.c_double * B)(*ratios), B, int(min_n_q), _ptr(out["n_q_rows"]), _ptr(out["row_errors"]),
+                                                _ptr(out["stage_errors"]), self._stream()))
+        try:
+            yield out
+        finally:
+            self.lib.fc_engine_set_rate(self._h, None, 0, 1, None, None, None, None)
+
+    def _rate_in(self, target_snr_db, min_n_q, B: int, n_q: int, n_q_rows):
+        """(ratios or None, min_n_q) of a call's target_snr_db / min_n_q, checked before anything reaches the device; a list of floats
+        that _rate_in made itself (a micro-batch's slice) passes through."""
+        if target_snr_db is None:
+            return None, 1
+        if isinstance(target_snr_db, _Ratios):
+            return target_snr_db, min_n_q
+        return _Ratios(rate_targets(self.arch, target_snr_db, B)), rate_min_nq(self.arch, min_n_q, n_q, n_q_rows)
+
     @_on_device
     def set_rvq_beam(self, width) -> None:
         """Width of the quantiser's search over the stages (fc_engine_set_rvq_beam) for every call that follows on this engine -- offline,
@@ -356,11 +464,21 @@ class CodecEngine:
             out[k] = None if vals[0] is None else torch.cat(vals, dim)
         return out
 
+    @staticmethod
+    def _rate_dims(ratios):
+        """the batch dimensions of the outputs a rate adds, for _cat"""
+        return {} if ratios is None else dict(n_q_rows=0, row_errors=0, stage_errors=1)
+
     @_on_device
-    def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False, lengths=None, n_q_rows=None):
-        """wav [B,T] (or [B,C,T]) -> dict(codes [n_q,B,Tf] i64, quantized [B,Tf,D], sub_quants [n_q,B,D,Tf], scale [B,1]|None)."""
+    def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False, lengths=None, n_q_rows=None,
+               target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False):
+        """wav [B,T] (or [B,C,T]) -> dict(codes [n_q,B,Tf] i64, quantized [B,Tf,D], sub_quants [n_q,B,D,Tf], scale [B,1]|None).
+        target_snr_db (one value or B; optional): every row takes the smallest stage count in [min_n_q, its cap] whose quantiser-domain SNR
+        reaches its target (rate_pick; the cap: n_q_rows[b], else n_q), chosen on the device inside the call.  The dict then also holds
+        n_q_rows [B] i32, row_errors [B, n_q + 1] f64 and stage_errors [n_q + 1, B, Tf] f32 (None unless want_stage_errors), all on the device."""
         if n_q_rows is not None:                       # refused as a whole before anything reaches the device
             n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
+        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows)
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
         if lengths is not None:
@@ -368,9 +486,10 @@ class CodecEngine:
         if B > self.micro_batch:
             parts = [self.encode(wav[i:i + self.micro_batch], n_q, want_sub_quants, want_enc_out,
                                  None if lengths is None else lengths[i:i + self.micro_batch],
-                                 None if n_q_rows is None else n_q_rows[i:i + self.micro_batch])
+                                 None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
+                                 None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors)
                      for i in range(0, B, self.micro_batch)]
-            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, enc_out=0))
+            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, enc_out=0, **self._rate_dims(ratios)))
         Tf, D = self.frames(T), self.arch.dimension
         dev = self.device
         codes = torch.empty((n_q, B, Tf), dtype=torch.int64, device=dev)
@@ -379,7 +498,7 @@ class CodecEngine:
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         enc = torch.empty((B, Tf, D), dtype=torch.float32, device=dev) if want_enc_out else None
         ws = self._workspace(B, T, lengths is not None)
-        with self._row_nq(n_q_rows):
+        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors) as rate:
             if lengths is not None:
                 self._check(self.lib.fc_encode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq),
                                                       _ptr(scale), _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
@@ -387,12 +506,16 @@ class CodecEngine:
                 self._check(self.lib.fc_encode(self._h, _ptr(wav), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq), _ptr(scale),
                                                _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
         return dict(codes=codes, quantized=quant, sub_quants=subq,
-                    scale=None if scale is None else scale.view(B, 1), enc_out=enc)
+                    scale=None if scale is None else scale.view(B, 1), enc_out=enc, **(rate or {}))
 
     @_on_device
-    def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True, lengths=None, n_q_rows=None):
+    def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True, lengths=None, n_q_rows=None,
+                      target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False):
+        """encode + decode in one enqueue; target_snr_db, min_n_q, want_stage_errors: as for encode (the reconstruction is made from the
+        chosen counts)."""
         if n_q_rows is not None:                       # refused as a whole before anything reaches the device
             n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
+        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows)
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
         if lengths is not None:
@@ -400,9 +523,10 @@ class CodecEngine:
         if B > self.micro_batch:
             parts = [self.encode_decode(wav[i:i + self.micro_batch], n_q, use_scale, want_sub_quants,
                                         None if lengths is None else lengths[i:i + self.micro_batch],
-                                        None if n_q_rows is None else n_q_rows[i:i + self.micro_batch])
+                                        None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
+                                        None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors)
                      for i in range(0, B, self.micro_batch)]
-            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0))
+            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0, **self._rate_dims(ratios)))
         Tf, D = self.frames(T), self.arch.dimension
         dev = self.device
         codes = torch.empty((n_q, B, Tf), dtype=torch.int64, device=dev)
@@ -411,7 +535,7 @@ class CodecEngine:
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         recon = torch.empty((B, self.channels, min(T, self.decoded_samples(Tf))), dtype=torch.float32, device=dev)   # like recon[:, :, :T] of the reference
         ws = self._workspace(B, T, lengths is not None)
-        with self._row_nq(n_q_rows):
+        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors) as rate:
             if lengths is not None:
                 self._check(self.lib.fc_encode_decode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
                                                              _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
@@ -419,7 +543,7 @@ class CodecEngine:
                 self._check(self.lib.fc_encode_decode(self._h, _ptr(wav), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
                                                       _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
         return dict(codes=codes, quantized=quant, sub_quants=subq,
-                    scale=None if scale is None else scale.view(B, 1), recon=recon)
+                    scale=None if scale is None else scale.view(B, 1), recon=recon, **(rate or {}))
 
     @_on_device
     def decode_codes(self, tokens: torch.Tensor, lengths=None, n_q_rows=None):
@@ -511,8 +635,11 @@ class CodecEngine:
 
     # -- per-op entry points (tests) -----------------------------------------------------------
     @_on_device
-    def rvq_encode(self, x: torch.Tensor, n_q: int, n_q_rows=None, beam: int = 1, return_paths: bool = False):
-        """x [N,D] -> (codes [n_q,N], quantized [N,D]).  n_q_rows (B entries): the N rows are B utterances of N / B frames each, utterance b
+    def rvq_encode(self, x: torch.Tensor, n_q: int, n_q_rows=None, beam: int = 1, return_paths: bool = False, target_snr_db=None,
+                   min_n_q: int = 1):
+        """x [N,D] -> (codes [n_q,N], quantized [N,D]).  target_snr_db (a list of B, or with n_q_rows one value or B; fc_rvq_encode_rate):
+        the N rows are B utterances of N / B frames each, every one takes the stage count the rule picks (rate_pick; n_q_rows are the caps)
+        -> (codes, quantized, dict(n_q_rows [B] i32, row_errors [B, n_q + 1] f64, stage_errors [n_q + 1, B, N / B] f32)).  n_q_rows (B entries): the N rows are B utterances of N / B frames each, utterance b
         with n_q_rows[b] stages.  beam (2, 4, 8): the search over the stages (fc_rvq_encode_beam) instead of the greedy quantiser;
         return_paths: also (paths [beam,n_q,N] i64, errors [beam,N]), every slot's final path and its fixed-order residual energy."""
         beam = rvq_beam_width(self.arch, beam)
@@ -522,12 +649,24 @@ class CodecEngine:
             n_q_rows = row_nq_list(self.arch, n_q_rows, len(n_q_rows), n_q)
             if x.shape[0] % len(n_q_rows) != 0:
                 raise EngineError(f"rvq_encode: {x.shape[0]} rows are not {len(n_q_rows)} utterances of equal length")
+        ratios = None
+        if target_snr_db is not None:
+            if return_paths:
+                raise EngineError("rvq_encode: return_paths and target_snr_db are two hooks (fc_rvq_encode_beam, fc_rvq_encode_rate)")
+            rows_b = len(n_q_rows) if n_q_rows is not None else (1 if isinstance(target_snr_db, numbers.Real) else len(target_snr_db))
+            ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, rows_b, n_q, n_q_rows)
+            if x.shape[0] % rows_b != 0:
+                raise EngineError(f"rvq_encode: {x.shape[0]} rows are not {rows_b} utterances of equal length")
         x = self._dev(x, torch.float32)
         N, D = x.shape
         if D != self.arch.codebook_dim:
             raise EngineError(f"rvq_encode: rows must have {self.arch.codebook_dim} dims, got {D}")
         codes = torch.empty((n_q, N), dtype=torch.int64, device=self.device)
         quant = torch.empty((N, D), dtype=torch.float32, device=self.device)
+        if ratios is not None:
+            with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, N // len(ratios), True) as rate:
+                self._check(self.lib.fc_rvq_encode_rate(self._h, _ptr(x), N, n_q, beam, _ptr(codes), _ptr(quant), self._stream()))
+            return codes, quant, rate
         if beam > 1:
             paths = torch.empty((beam, n_q, N), dtype=torch.int64, device=self.device) if return_paths else None
             errors = torch.empty((beam, N), dtype=torch.float32, device=self.device) if return_paths else None

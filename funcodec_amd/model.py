@@ -14,7 +14,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ArchSpec
-from .engine import CodecEngine, EngineError, ragged_refusal, row_nq_list, rvq_beam_width
+from .engine import CodecEngine, EngineError, ragged_refusal, rate_min_nq, rate_targets, row_nq_list, rvq_beam_width
 
 
 class EncodecMI355X:
@@ -142,7 +142,8 @@ class EncodecMI355X:
     # -- Encodec.inference (codec_basic.py:670-718) ------------------------------------------
     @torch.no_grad()
     def inference(self, speech: torch.Tensor, need_recon: bool = True, bit_width: int = None,
-                  use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None, rvq_beam: int = None) -> Dict[str, torch.Tensor]:
+                  use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None, rvq_beam: int = None,
+                  target_snr_db=None, min_n_q: int = 1) -> Dict[str, torch.Tensor]:
         """bit_width: one value for the batch, as in the reference, or a sequence / 1-D tensor of B: row b is then what this call returns
         for it with ``bit_width[b]``; ``code_indices`` is [max n_q, B, Tf] with zeros at the stages a row does not take (``sub_quants`` too).
         speech_lengths [B] (optional): samples per row.  With it, row b of every output is what this call returns for
@@ -150,14 +151,22 @@ class EncodecMI355X:
         ``engine.frames(len)`` frames / ``len`` samples; without it, the call over the whole batch width, as the reference runs it.
         rvq_beam (2, 4 or 8; optional): the quantiser searches over its stages with that many hypotheses per frame instead of taking the
         nearest code stage by stage; no frame is coded worse, the outputs keep their shapes and decode like any other.  It is set on the
-        engine around this call only, and combines with ``speech_lengths`` and a per-row ``bit_width``."""
+        engine around this call only, and combines with ``speech_lengths`` and a per-row ``bit_width``.
+        target_snr_db (one value or B of them, dB; optional): row b takes the smallest number of stages in [min_n_q, its cap] whose
+        quantiser-domain SNR reaches its target (``engine.rate_pick`` states the rule; +inf: the best count), chosen on the device inside
+        this one call; a per-row ``bit_width`` is the per-row cap.  Every output is then what this call returns with the ``bit_width`` of
+        those counts (``rvq_beam``: the first k codes of the full-depth search).  The dict gains ``n_q_rows`` [B] int32 and ``row_snr_db``
+        [B] float64 (10 log10(E[0] / E[k]) of every row at its count), both on the device; a decoder needs the counts, code 0 is a valid code."""
+        if target_snr_db is not None:                  # refused before anything reaches the device
+            rate_targets(self.arch, target_snr_db, speech.shape[0])
         with self.engine._rvq_beam(rvq_beam_width(self.arch, rvq_beam)):           # refused before anything reaches the device
-            return self._inference(speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths)
+            return self._inference(speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db, min_n_q)
 
-    def _inference(self, speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths):
+    def _inference(self, speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db=None, min_n_q=1):
         speech = self._as_bct(speech)
         bypass = self.arch.bypass_quantizer and not _quantise_always
         n_q, rows = self._bit_widths(bit_width, speech.shape[0])
+        rate = {} if target_snr_db is None else dict(target_snr_db=target_snr_db, min_n_q=rate_min_nq(self.arch, min_n_q, n_q, rows))
         wav = speech[:, 0, :] if self.engine.channels == 1 else speech
         if speech_lengths is not None:
             why = ragged_refusal(self.arch)
@@ -166,10 +175,11 @@ class EncodecMI355X:
             if bypass:     # inference() alone: inference_encoding quantises whatever the flag says, the decode calls never see it
                 raise EngineError("Encodec.inference with speech_lengths is not built for model_conf.bypass_quantizer (it would decode the "
                                   "encoder output of every row by its own frames); inference_encoding and the decode calls take lengths")
-            r = (self.engine.encode_decode(wav, n_q, use_scale=use_scale, lengths=speech_lengths, n_q_rows=rows) if need_recon
-                 else self.engine.encode(wav, n_q, lengths=speech_lengths, n_q_rows=rows))
+            r = (self.engine.encode_decode(wav, n_q, use_scale=use_scale, lengths=speech_lengths, n_q_rows=rows, **rate) if need_recon
+                 else self.engine.encode(wav, n_q, lengths=speech_lengths, n_q_rows=rows, **rate))
             return dict(recon_speech=r.get("recon"), code_indices=[r["codes"]],
-                        code_embeddings=[(r["quantized"], r["scale"] if use_scale else None)], sub_quants=[r["sub_quants"]])
+                        code_embeddings=[(r["quantized"], r["scale"] if use_scale else None)], sub_quants=[r["sub_quants"]],
+                        **self._rate_outputs(r))
         if self.arch.segment_length is not None:
             wav = wav.to(self.device, torch.float32)
             return self._inference_segmented(wav, n_q, need_recon, use_scale, bypass)
@@ -181,22 +191,32 @@ class EncodecMI355X:
                 recon = self.engine.decode_emb(r["quantized"], r["scale"] if use_scale else None,
                                                out_len=min(T, self.engine.decoded_samples(r["quantized"].shape[1])))
         elif need_recon:
-            r = self.engine.encode_decode(wav, n_q, use_scale=use_scale, n_q_rows=rows)
+            r = self.engine.encode_decode(wav, n_q, use_scale=use_scale, n_q_rows=rows, **rate)
             recon = r["recon"]
         else:
-            r = self.engine.encode(wav, n_q, n_q_rows=rows)
+            r = self.engine.encode(wav, n_q, n_q_rows=rows, **rate)
             recon = None
         scale = r["scale"] if use_scale else None
         return dict(recon_speech=recon, code_indices=[r["codes"]], code_embeddings=[(r["quantized"], scale)],
-                    sub_quants=[r["sub_quants"]])
+                    sub_quants=[r["sub_quants"]], **self._rate_outputs(r))
+
+    @staticmethod
+    def _rate_outputs(r):
+        """n_q_rows and row_snr_db of an engine call made with a target (device tensors; torch is plumbing here: a gather and a log of B values)"""
+        if "n_q_rows" not in r:
+            return {}
+        E = r["row_errors"]
+        Ek = E.gather(1, r["n_q_rows"].long().unsqueeze(1)).squeeze(1)
+        return dict(n_q_rows=r["n_q_rows"], row_snr_db=10.0 * torch.log10(E[:, 0] / Ek))
 
     # -- Encodec.inference_encoding (codec_basic.py:720-764) ---------------------------------
     @torch.no_grad()
     def inference_encoding(self, speech: torch.Tensor, need_recon: bool = False, bit_width: int = None,
-                           use_scale: bool = True, speech_lengths=None, rvq_beam: int = None) -> Dict[str, torch.Tensor]:
+                           use_scale: bool = True, speech_lengths=None, rvq_beam: int = None, target_snr_db=None,
+                           min_n_q: int = 1) -> Dict[str, torch.Tensor]:
         # (model_conf.bypass_quantizer does not reach this entry point in the reference: it quantises, :748-750)
         return self.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, _quantise_always=True,
-                              speech_lengths=speech_lengths, rvq_beam=rvq_beam)
+                              speech_lengths=speech_lengths, rvq_beam=rvq_beam, target_snr_db=target_snr_db, min_n_q=min_n_q)
 
     # -- Encodec.inference_decoding (codec_basic.py:766-802) ---------------------------------
     @torch.no_grad()

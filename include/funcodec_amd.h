@@ -236,6 +236,43 @@ int fc_engine_set_rvq_beam(fc_engine* e, int width, void* stream);
 int fc_rvq_encode_beam(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, int64_t* paths,
                        float* errors, void* stream);
 
+/* ---- a stage count per row chosen on the device by target SNR (entry points added without a struct change: FC_ABI_VERSION stays) ----
+ * Each row of an offline call takes the smallest number of stages whose quantiser-domain SNR reaches its target, inside the one call:
+ * nothing is read back, the chosen counts are an output on the device.  csrc/rvq_rate_kernels.h states the rule and
+ * funcodec_amd/engine.py::rate_pick restates it on the host.  With x [N = B Tf, Dc] the quantiser's input rows and c [n_q, N] the codes
+ * the call finds at the cap (greedy, or the search of fc_engine_set_rvq_beam at its full depth):
+ *   stage errors [n_q + 1][B][Tf] f32:  r_0 = x[n], r_{i+1} = r_i - E_i[c_i[n]] element-wise in fp32, err[i][n] = |r_i|^2 in one fixed
+ *       order (four chains over Dc / 4, squares rounded separately, (p0 + p1) + (p2 + p3)); err[0] is the input energy.  Made from the
+ *       codes, whoever found them.  0 behind a row's cap and behind a row's frames of a ragged call;
+ *   row errors [B][n_q + 1] f64:  E_b[i] = the sum of err[i][b, t] over the row's frames (a ragged call: its own fc_engine_frames(len_b)
+ *       only), in an order that depends on the row's frame count alone -- never on B, Tmax or the neighbours;
+ *   the pick:  rho_b = 10^(-target_b / 10), computed by the host in double and handed over as a double; the floor min_nq; the cap cap_b
+ *       (the row's entry of fc_engine_set_row_nq if a table is set, else the call's n_q).  k_b = the smallest k in [min_nq, cap_b] with
+ *       E_b[k] <= E_b[0] * rho_b.  If no k reaches the target: the k in that range with the smallest E_b[k], first on ties (the curve is
+ *       not monotone on real codebooks: a missed target never costs more bits for a worse result; rho = 0 therefore means "the best k").
+ *       A row with E_b[0] == 0 (digital silence) takes min_nq.  A row whose energies are not all finite takes cap_b, as the plain call would.
+ * Row b of codes, quantized, sub_quants, the decoder's input and the reconstruction is then what the call with fc_engine_set_row_nq
+ * count k_b returns: zeros in codes[k_b:] and sub_quants[k_b:].  Greedy: bit for bit that call.  With a search: the first k_b codes of
+ * the full-depth path, which is NOT the search over k_b stages; quantized is fc_decode_codes' sum of those codes.  A decoder needs the
+ * count (code 0 is a valid code): hand n_q_rows to fc_engine_set_row_nq for the decode call.
+ *   ratio_rows        HOST f64 [B]; NULL clears the rate (the other arguments are then ignored).  The engine keeps a device copy of its own;
+ *                     the copy is ordered on `stream`, the caller's array may go when the call returns
+ *   n_q_rows_out      dev i32 [B]: the chosen counts (required)
+ *   row_errors_out    dev f64 [B][n_q + 1] or NULL;  stage_errors_out  dev f32 [n_q + 1][B * Tf] or NULL: with n_q and Tf those of the call
+ *                     that follows; the call's workspace holds whichever is NULL (fc_engine_workspace_bytes counts them)
+ * It applies to the calls that follow, like fc_engine_set_row_nq, and is honoured by fc_encode, fc_encode_decode, their _ragged siblings
+ * (the 2-D FreqCodec encode included) and the per-op hook fc_rvq_encode_rate.  With no rate set every call launches exactly what it
+ * launched before.  Refused before the first launch, changing nothing: B other than the call's batch width; min_nq outside
+ * [1, num_quantizers], above the call's n_q or above a row's cap; a ratio that is negative or NaN; quantizer_conf.q0_ds_ratio > 1 (stage 0
+ * quantises another frame's row); any encode push of a stream or slot session while a rate is set (offline calls only).
+ * model_conf.segment_dur and model_conf.bypass_quantizer are host-side matters: the host wrappers refuse. */
+int fc_engine_set_rate(fc_engine* e, const double* ratio_rows /* host [B] or NULL */, int B, int min_nq, int32_t* n_q_rows_out /* dev [B] */,
+                       double* row_errors_out /* dev [B][n_q+1] or NULL */, float* stage_errors_out /* dev [n_q+1][B*Tf] or NULL */, void* stream);
+/* The per-op hook under the rate set on the engine (both optional outputs of fc_engine_set_rate must be given: the hook has no
+ * workspace): x dev f32 [N,D], the N rows being B utterances of N / B frames; width 1 (greedy) or 2, 4, 8 (the search at full depth);
+ * codes dev i64 [n_q,N]; quantized dev f32 [N,D] or NULL.  Honours fc_engine_set_row_nq as the caps. */
+int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, void* stream);
+
 /* _linear_overlap_add (funcodec/models/codec_basic.py:77-116), the tail of Encodec._decode (:382-396) when
  * model_conf.segment_dur is set: triangle-weighted overlap-add of the decoded segments, products accumulated in
  * frame order and divided once by the summed weights, exactly as the reference orders it.

@@ -87,6 +87,11 @@ SYMBOLS = {
     # a stage count per row by target SNR: host float64 ratios [B] (None clears), min_nq, device outputs n_q_rows / row_errors / stage_errors
     "fc_engine_set_rate": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "fc_rvq_encode_rate": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    # the bit stream (csrc/code_pack_kernels.h): pitch and packet length (host arithmetic), pack and unpack on the device; engine-free
+    "fc_code_packet_pitch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "fc_code_packet_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "fc_codes_pack": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "fc_codes_unpack": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "fc_rvq_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_q0_source_frames": (C.c_int, [C.c_int, _P]),
     "fc_layer_forward": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),

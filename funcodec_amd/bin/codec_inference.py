@@ -76,6 +76,7 @@ class Speech2Token:
         from ..engine import rvq_beam_width
         self.rvq_beam = rvq_beam_width(model.arch, rvq_beam)
         self.last_n_q_rows = self.last_row_snr_db = None          # of the last call made with target_snr_db
+        self.last_packets = None                                  # of the last call made with packed=True
 
     @torch.no_grad()
     def __call__(
@@ -90,6 +91,8 @@ class Speech2Token:
             rvq_beam: Optional[int] = None,
             target_snr_db=None,
             min_n_q: int = 1,
+            packed: bool = False,
+            n_q_rows=None,
     ):
         """Returns (code_indices, code_embeddings, recon_speech, sub_quants) like the reference (:86-134).
 
@@ -102,10 +105,23 @@ class Speech2Token:
 
         target_snr_db, min_n_q (not in the reference; default None = off): in the modes that encode, every row takes the fewest stages that
         reach its target SNR in the quantiser's domain (EncodecMI355X.inference).  The 4-tuple stays; the chosen counts of the last such
-        call stand in ``last_n_q_rows`` (device int32 [B]) and their SNRs in ``last_row_snr_db``; they are None after any other call."""
+        call stand in ``last_n_q_rows`` (device int32 [B]) and their SNRs in ``last_row_snr_db``; they are None after any other call.
+
+        packed (not in the reference; default False): in the modes that encode, the call also writes one packet per row (EncodecMI355X.inference,
+        csrc/code_pack_kernels.h).  The 4-tuple stays; the packets (device uint8 [B, pitch]) stand in ``last_packets``, None after any other call.
+
+        n_q_rows (not in the reference; run_mod="decode" only): a stage count per row, as the packets of ``codecs.fcb`` carry it; row b's
+        tokens behind its count are not read."""
+        if packed and run_mod not in ("inference", "encode"):
+            raise ValueError(f"packed belongs to the modes that encode (inference, encode), not run_mod={run_mod!r}")
+        if n_q_rows is not None and run_mod != "decode":
+            raise ValueError(f"n_q_rows belongs to run_mod='decode', not run_mod={run_mod!r}")
+        self.last_packets = None
         if target_snr_db is not None and run_mod not in ("inference", "encode"):
             raise ValueError(f"target_snr_db belongs to the modes that encode (inference, encode), not run_mod={run_mod!r}")
         rate = {} if target_snr_db is None else dict(target_snr_db=target_snr_db, min_n_q=min_n_q)
+        if packed:
+            rate["packed"] = True
         self.last_n_q_rows = self.last_row_snr_db = None
         rvq_beam = getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam       # (an instance built around a ready model has none)
         if ppg is not None:
@@ -129,7 +145,16 @@ class Speech2Token:
                 nq = int(max(bit_width // bit_per_quant, 1))
             speech = speech[:, :, :nq]
             logging.info("use %d quantizers.", speech.shape[-1])
-            ret = self.model.inference_decoding(speech, token_lengths=speech_lengths)
+            if n_q_rows is not None:         # the counts of the rows' packets, no larger than the stages kept
+                rows = [min(int(k), speech.shape[-1]) for k in torch.as_tensor(n_q_rows).reshape(-1).tolist()]
+                recon, emb = self.model.engine.decode_codes(speech, lengths=speech_lengths,
+                                                            n_q_rows=rows if any(k != speech.shape[-1] for k in rows) else None)
+                if self.model.arch.segment_length is not None:
+                    recon = self.model.engine.overlap_add([recon], self.model.arch.segment_stride or 1)
+                ret = dict(recon_speech=recon, code_indices=None, code_embeddings=[(emb, None)], sub_quants=None)
+            else:
+                ret = self.model.inference_decoding(speech, token_lengths=speech_lengths)
+        self.last_packets = ret.get("packets")
         self.last_n_q_rows, self.last_row_snr_db = ret.get("n_q_rows"), ret.get("row_snr_db")
         if self.check_status:
             self.model.engine.check_status(sync=True)
@@ -258,7 +283,23 @@ def inference_modelscope(
             # (a bit_width per row), since code 0 is a valid code
             n_q_writer = open(os.path.join(output_path, "codec_n_q.txt"), "wt")
         ark_indices = kwargs.get("indices_save_type") == "ark"
-        if kwargs.get("need_indices"):
+        packed_indices = bool(kwargs.get("need_indices")) and kwargs.get("indices_save_type") == "packed"
+        run_mod = kwargs.get("run_mod", "inference")
+        fcb_writer = None
+        if packed_indices:
+            # codecs.fcb + codecs.fcb.scp in place of codecs.txt: one packet per utterance with its own frames and stage count
+            # (csrc/code_pack_kernels.h; funcodec_amd.io.FcbWriter)
+            if run_mod not in ("inference", "encode"):
+                raise ValueError(f"--indices_save_type packed belongs to the modes that encode, not --run_mod {run_mod}")
+            from ..engine import EngineError, packed_refusal
+            why = packed_refusal(my_model.model.arch)
+            if why:
+                raise EngineError(why)
+            bw0 = param_dict["bit_width"] if param_dict is not None and "bit_width" in param_dict else bit_width
+            fcb_writer = fio.FcbWriter(os.path.join(output_path, "codecs.fcb"), my_model.model.engine.code_bits,
+                                       my_model.model.arch.num_quantizers_for_bandwidth(bw0), sampling_rate,
+                                       my_model.model.quantizer.encoder_hop_length)
+        elif kwargs.get("need_indices"):
             if ark_indices:
                 indices_writer = fio.KaldiMatrixWriter(os.path.join(output_path, "indices"))
             else:
@@ -267,7 +308,6 @@ def inference_modelscope(
             sub_quants_writer = fio.KaldiMatrixWriter(os.path.join(output_path, "codec_emb"))
 
         result_list = []
-        run_mod = kwargs.get("run_mod", "inference")
         hop = my_model.model.quantizer.encoder_hop_length
 
         # Host pipeline around the engine (the engine does 160 audio-seconds in 17 ms; reading / padding the next batch and writing
@@ -321,9 +361,12 @@ def inference_modelscope(
             return lines, results
 
         def _drain(job):
-            keys, speech_length, tok_host, sq_host, fut, nq_host = job
+            keys, speech_length, tok_host, sq_host, fut, nq_host, packets_host = job
             lines, results = fut.result()
             result_list.extend(results)
+            if packets_host is not None:
+                for key, packet, n in zip(keys, packets_host, speech_length):
+                    fcb_writer(key, packet, int(n))
             if nq_host is not None and n_q_writer is not None:
                 n_q_writer.write("".join(f"{key} {int(k)} {float(snr):.4f}\n" for key, k, snr in zip(keys, *nq_host)))
             if lines:
@@ -352,6 +395,8 @@ def inference_modelscope(
                 if should_resample:                                                 # reference :318-322 (lengths stay in file samples)
                     batch["speech"] = fio.resample(batch["speech"], file_sr, sampling_rate)
                 speech_length = batch.pop("speech_lengths")
+                if "speech_n_q" in batch:                               # a codec_fcb input: every row decodes with the count its packet carries
+                    batch["n_q_rows"] = batch.pop("speech_n_q")
                 if _str2bool(kwargs.get("length_aware", False)):        # opt-in: the lengths go to the model instead of being dropped
                     if should_resample:
                         raise NotImplementedError("length_aware with file_sampling_rate != sampling_rate (the lengths count file samples)")
@@ -370,14 +415,21 @@ def inference_modelscope(
                 tok_host = [x.cpu().contiguous() for x in token_id] if (token_id is not None and indices_writer is not None) else None
                 sq_host = [x.cpu() for x in sub_quants] if (sub_quants is not None and sub_quants_writer is not None) else None
                 nq_host = None if target_snr_db is None else (my_model.last_n_q_rows.tolist(), my_model.last_row_snr_db.tolist())
-                jobs.append((keys, speech_length, tok_host, sq_host, pool.submit(_write_batch, keys, speech_length, recon_host, tok_host), nq_host))
+                packets_host = None
+                if fcb_writer is not None:
+                    # the frames the text form writes for a row (ceil(samples / hop)); the counts of a target go from the device tensor into the packer
+                    eng = my_model.model.engine
+                    frames = [int(math.ceil(int(n) / hop)) for n in speech_length]
+                    packets_host = eng.packets_to_host(eng.pack_codes(token_id[0], frames_rows=frames, n_q_rows=my_model.last_n_q_rows))
+                jobs.append((keys, speech_length, tok_host, sq_host, pool.submit(_write_batch, keys, speech_length, recon_host, tok_host), nq_host,
+                             packets_host))
                 while len(jobs) > 3:                                                # bounds the host memory held by queued batches
                     _drain(jobs.pop(0))
             while jobs:
                 _drain(jobs.pop(0))
         finally:
             pool.shutdown(wait=True)
-        for w in (indices_writer, sub_quants_writer, n_q_writer):
+        for w in (indices_writer, sub_quants_writer, n_q_writer, fcb_writer):
             if w is not None:
                 w.close()
         return result_list
@@ -431,6 +483,8 @@ def get_parser():
     p.add_argument("--bit_width", type=int, default=16_000)
     p.add_argument("--use_scale", type=_str2bool, default=True)
     g.add_argument("--need_indices", type=_str2bool)
+    # text: codecs.txt; ark: a Kaldi float matrix; packed (not in the reference): codecs.fcb + codecs.fcb.scp, the codec's own bit stream --
+    # one packet per utterance with its frames and stage count; --run_mod decode reads it back as input type codec_fcb
     g.add_argument("--indices_save_type", type=str, default="text")
     g.add_argument("--need_sub_quants", type=_str2bool)
     g.add_argument("--run_mod", type=str, choices=["inference", "encode", "decode", "decode_emb"], default="inference")

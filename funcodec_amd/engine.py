@@ -63,6 +63,18 @@ def row_nq_refusal(arch) -> Optional[str]:
     return None
 
 
+def packed_refusal(arch) -> Optional[str]:
+    """Why a model of this architecture writes no packets (``packed=True``; csrc/code_pack_kernels.h states the packet), or None.  The
+    configuration key is named, as ``ragged_refusal`` does."""
+    if arch.segment_length is not None:
+        return "packets are not available with model_conf.segment_dur (a segment's codes are a list of frames, not one row per utterance)"
+    if arch.bypass_quantizer:
+        return "packets are not available with model_conf.bypass_quantizer (the quantiser's result is dropped)"
+    if arch.q0_ds_ratio > 1:
+        return "packets are not available for quantizer_conf.q0_ds_ratio > 1 (stage 0 runs at half the frame rate; its packet form is not built)"
+    return None
+
+
 RVQ_BEAM_WIDTHS = (1, 2, 4, 8)
 
 
@@ -632,6 +644,93 @@ class CodecEngine:
         if sync and torch.cuda.is_available():
             torch.cuda.current_stream(self.device).synchronize()
         self._check(self.lib.fc_engine_status(self._h, None))
+
+    # -- the bit stream (csrc/code_pack_kernels.h states the packet; funcodec_amd/io.py restates it on the host) ----------------
+    @property
+    def code_bits(self) -> int:
+        """bits per code in a packet: ceil(log2(codebook_size))"""
+        from .io import code_bits
+        return code_bits(self.arch.codebook_size)
+
+    def _rows_i32(self, rows, B: int, what: str) -> Optional[torch.Tensor]:
+        """frames or stage counts per row as device int32 [B]; a device tensor stays on the device (nothing is read back: the kernel clamps)"""
+        if rows is None:
+            return None
+        rows = torch.as_tensor(rows).reshape(-1)
+        if rows.numel() != B:
+            raise EngineError(f"{what} must hold one entry per row ({B}), got {rows.numel()}")
+        return self._dev(rows, torch.int32)
+
+    @_on_device
+    def pack_codes(self, codes: torch.Tensor, frames_rows=None, n_q_rows=None) -> torch.Tensor:
+        """codes [n_q,B,Tf] i64 -> packets uint8 [B, pitch] on the device (fc_codes_pack), one packet per row with zeros behind it.
+        frames_rows, n_q_rows [B] (optional; lists, or tensors on any device -- ``n_q_rows`` of a ``target_snr_db`` call goes in as it
+        is): the row's frames and stage count, clamped on the device to [0, Tf] and [1, n_q]; nothing behind them is read."""
+        codes = self._dev(codes, torch.int64)
+        if codes.dim() != 3:
+            raise EngineError(f"pack_codes: codes must be [n_q,B,Tf], got {tuple(codes.shape)}")
+        n_q, B, Tf = codes.shape
+        fr, nq = self._rows_i32(frames_rows, B, "frames_rows"), self._rows_i32(n_q_rows, B, "n_q_rows")
+        bits = self.code_bits
+        pitch = int(self.lib.fc_code_packet_pitch(Tf, n_q, bits))
+        packets = torch.empty((B, pitch), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.fc_codes_pack(_ptr(codes), B, Tf, n_q, bits, _ptr(fr), _ptr(nq), _ptr(packets), pitch, self._stream()))
+        return packets
+
+    @_on_device
+    def unpack_codes(self, packets: torch.Tensor, Tf: int, n_q: Optional[int] = None) -> torch.Tensor:
+        """packets uint8 [B, pitch] -> tokens [B,Tf,n_q] i64 (fc_codes_unpack), the layout the decode calls take: zeros at the stages
+        behind a row's count and the frames behind its frames.  n_q: the tokens' last dimension (default: the model's num_quantizers)."""
+        packets = self._dev(packets, torch.uint8)
+        if packets.dim() != 2:
+            raise EngineError(f"unpack_codes: packets must be [B, pitch], got {tuple(packets.shape)}")
+        n_q = self.arch.num_quantizers if n_q is None else int(n_q)
+        B, pitch = packets.shape
+        tokens = torch.empty((B, int(Tf), n_q), dtype=torch.int64, device=self.device)
+        self._check(self.lib.fc_codes_unpack(_ptr(packets), pitch, B, int(Tf), n_q, self.code_bits, _ptr(tokens), self._stream()))
+        return tokens
+
+    def _parse_packets(self, rows, exact):
+        """(frames, counts) of host packets, every header checked (bits, mode, k <= num_quantizers, length); a bad one raises EngineError
+        naming the row and the field"""
+        from .io import PacketError, parse_packet_header
+        frames, counts = [], []
+        for b, p in enumerate(rows):
+            try:
+                f, k, _, _ = parse_packet_header(p, self.arch.num_quantizers, self.code_bits, exact=exact)
+            except PacketError as err:
+                raise EngineError(f"row {b}: packet field {err}") from None
+            frames.append(f)
+            counts.append(k)
+        return frames, counts
+
+    def packets_to_host(self, packets: torch.Tensor):
+        """packets uint8 [B, pitch] -> list of B bytes: ONE copy to the host, every row cut at its own packet length"""
+        from .io import packet_bytes
+        host = packets.cpu().numpy()
+        rows = [host[b].tobytes() for b in range(host.shape[0])]
+        frames, counts = self._parse_packets(rows, exact=False)
+        return [r[:packet_bytes(f, k, self.code_bits)] for r, f, k in zip(rows, frames, counts)]
+
+    def packets_from_host(self, packets, n_q: Optional[int] = None):
+        """list of B bytes -> (packets uint8 [B, pitch] on the device, Tf, counts): every header is validated first (bits, mode,
+        k <= n_q, and a length of exactly fc_code_packet_bytes); Tf is the largest frame count, the pitch that of (Tf, n_q) with n_q the
+        largest count unless given."""
+        from .io import packet_pitch
+        packets = [bytes(p) for p in packets]
+        if not packets:
+            raise EngineError("packets_from_host: no packets")
+        frames, counts = self._parse_packets(packets, exact=True)
+        if n_q is not None:
+            for b, k in enumerate(counts):
+                if k > n_q:
+                    raise EngineError(f"row {b}: packet field k: {k} stages, more than the {n_q} of this call")
+        Tf = max(max(frames), 1)
+        pitch = packet_pitch(Tf, max(counts) if n_q is None else int(n_q), self.code_bits)
+        host = np.zeros((len(packets), pitch), dtype=np.uint8)
+        for b, p in enumerate(packets):
+            host[b, :len(p)] = np.frombuffer(p, dtype=np.uint8)
+        return torch.from_numpy(host).to(self.device), Tf, counts
 
     # -- per-op entry points (tests) -----------------------------------------------------------
     @_on_device

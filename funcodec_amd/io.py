@@ -6,6 +6,7 @@
 * batches: shorter items are WRAP-padded with ``np.pad(mode="wrap")`` (nets_utils.py:65-98, codec_inference.py:257-261)
 * out:     ``codecs.txt`` jsonl (codec_inference.py:288-299), Kaldi ``ark,scp`` float matrices (:292-294, :301-311),
            PCM16 wav with peak rescale to 0.99 (``save_audio`` :153-161)
+* packets: the codec's own bit stream, ``codecs.fcb`` (not in the reference; csrc/code_pack_kernels.h states the packet)
 """
 from __future__ import annotations
 
@@ -207,6 +208,173 @@ def load_codec_json(json_str: str) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------
+# the bit stream: one packet per utterance (csrc/code_pack_kernels.h states the packet; this is its numpy restatement, so a machine
+# without a GPU reads and writes the format) and the container codecs.fcb
+# ------------------------------------------------------------------------------------------------
+PACKET_HEADER_BYTES = 8
+
+
+class PacketError(ValueError):
+    """a packet that is not one: ``field`` names what is wrong (mode, bits, k, length)"""
+
+    def __init__(self, field: str, msg: str):
+        super().__init__(f"{field}: {msg}")
+        self.field = field
+
+
+def code_bits(codebook_size: int) -> int:
+    """bits = ceil(log2(codebook_size)), at least 1"""
+    return max(1, int(codebook_size - 1).bit_length())
+
+
+def packet_bytes(frames: int, k: int, bits: int) -> int:
+    """8 + ceil(frames k bits / 8) (fc_code_packet_bytes)"""
+    return PACKET_HEADER_BYTES + (int(frames) * int(k) * int(bits) + 7) // 8
+
+
+def packet_pitch(frames: int, n_q: int, bits: int) -> int:
+    """the largest packet rounded up to 16 (fc_code_packet_pitch)"""
+    return (packet_bytes(frames, n_q, bits) + 15) // 16 * 16
+
+
+def parse_packet_header(buf, n_q: Optional[int] = None, bits: Optional[int] = None, exact: Optional[bool] = True) -> Tuple[int, int, int, int]:
+    """(frames, k, bits, packet length) of the packet at the start of ``buf``, every field checked: mode 0, bits in 1..16 (and the
+    expected ``bits`` if given), k in 1..255 (and <= ``n_q`` if given), and a length of exactly (``exact``) or at least the packet's
+    8 + ceil(frames k bits / 8) bytes (``exact=None``: ``buf`` is the header alone).  Raises PacketError naming the field."""
+    buf = buf if isinstance(buf, (bytes, bytearray)) else bytes(buf)
+    if len(buf) < PACKET_HEADER_BYTES:
+        raise PacketError("length", f"a packet begins with an {PACKET_HEADER_BYTES}-byte header, got {len(buf)} bytes")
+    frames, k, b, mode, zero = struct.unpack_from("<IBBBB", buf, 0)
+    if mode != 0:
+        raise PacketError("mode", f"only mode 0 (one stage count per packet) is defined, got {mode}")
+    if not 1 <= b <= 16 or (bits is not None and b != bits):
+        raise PacketError("bits", f"{b} bits per code" + (f", expected {bits}" if bits is not None else " lies outside 1..16"))
+    if k < 1 or (n_q is not None and k > n_q):
+        raise PacketError("k", f"a stage count lies in 1..{255 if n_q is None else n_q}, got {k}")
+    need = packet_bytes(frames, k, b)
+    if exact is not None and ((len(buf) != need) if exact else (len(buf) < need)):
+        raise PacketError("length", f"{frames} frames of {k} stages at {b} bits are {need} bytes, got {len(buf)}")
+    return frames, k, b, need
+
+
+def pack_codes(codes, k: Optional[int] = None, bits: int = 10, frames: Optional[int] = None, layout: str = "qt") -> bytes:
+    """One packet from the codes of one utterance: ``codes`` [n_q, T] (``layout="qt"``, a row of an encode call's codes) or [T, n_q]
+    (``"tq"``, the decode calls' tokens); the first ``k`` stages (default: all) of the first ``frames`` frames (default: all), each code
+    modulo 2^bits."""
+    a = np.asarray(codes)
+    if a.ndim != 2:
+        raise ValueError(f"pack_codes: codes of one utterance are 2-D, got shape {a.shape}")
+    if layout not in ("qt", "tq"):
+        raise ValueError(f"pack_codes: layout is 'qt' ([n_q, T]) or 'tq' ([T, n_q]), got {layout!r}")
+    a = a.T if layout == "qt" else a                         # [T, n_q]
+    k = a.shape[1] if k is None else int(k)
+    frames = a.shape[0] if frames is None else int(frames)
+    if not 1 <= bits <= 16:
+        raise PacketError("bits", f"{bits} bits per code lies outside 1..16")
+    if not 1 <= k <= min(a.shape[1], 255):
+        raise PacketError("k", f"a stage count lies in 1..{min(a.shape[1], 255)}, got {k}")
+    if not 0 <= frames <= a.shape[0]:
+        raise PacketError("frames", f"the codes hold {a.shape[0]} frames, got {frames}")
+    vals = (a[:frames, :k].astype(np.int64).reshape(-1) & ((1 << bits) - 1)).astype(np.uint32)
+    stream = ((vals[:, None] >> np.arange(bits, dtype=np.uint32)[None, :]) & 1).astype(np.uint8).reshape(-1)
+    return struct.pack("<IBBBB", frames, k, bits, 0, 0) + np.packbits(stream, bitorder="little").tobytes()
+
+
+def unpack_packet(packet) -> Tuple[np.ndarray, int, int]:
+    """(tokens [T, k] int64, k, bits) of one packet; the inverse of pack_codes"""
+    packet = bytes(packet)
+    frames, k, bits, _ = parse_packet_header(packet)
+    stream = np.unpackbits(np.frombuffer(packet, dtype=np.uint8, offset=PACKET_HEADER_BYTES), bitorder="little")[:frames * k * bits]
+    vals = (stream.reshape(frames * k, bits).astype(np.int64) << np.arange(bits, dtype=np.int64)[None, :]).sum(1)
+    return vals.reshape(frames, k), k, bits
+
+
+FCB_MAGIC = b"FCB1"
+_FCB_HEADER = struct.Struct("<4sBBHII")      # magic, bits, n_q, 0, sample rate, hop
+_FCB_RECORD = struct.Struct("<II")           # valid samples, packet length (behind: u16 key length, key)
+
+
+class FcbWriter:
+    """``codecs.fcb``: the file header (magic b"FCB1", u8 bits, u8 n_q, u16 0, u32 sample rate, u32 hop), then one record per utterance:
+    u16 key length, key (UTF-8), u32 valid samples, u32 packet length, packet.  ``<path>.scp`` indexes it with lines ``key path:offset``
+    as Kaldi arks are indexed; the offset is that of the record's sample count, behind its key."""
+
+    def __init__(self, path: str, bits: int, n_q: int, sample_rate: int, hop: int):
+        if not 1 <= bits <= 16 or not 1 <= n_q <= 255:
+            raise ValueError(f"FcbWriter: bits in 1..16 and n_q in 1..255, got {bits}, {n_q}")
+        self.path, self.bits, self.n_q = path, int(bits), int(n_q)
+        self._f = open(path, "wb")
+        self._scp = open(path + ".scp", "wt", encoding="utf-8")
+        self._f.write(_FCB_HEADER.pack(FCB_MAGIC, self.bits, self.n_q, 0, int(sample_rate), int(hop)))
+
+    def __call__(self, key: str, packet: bytes, samples: int) -> None:
+        packet = bytes(packet)
+        parse_packet_header(packet, self.n_q, self.bits)
+        kb = key.encode("utf-8")
+        if not 0 < len(kb) < 65536 or any(c.isspace() for c in key):
+            raise ValueError(f"FcbWriter: a key is 1..65535 UTF-8 bytes without white space, got {key!r}")
+        self._f.write(struct.pack("<H", len(kb)) + kb)
+        self._scp.write(f"{key} {self.path}:{self._f.tell()}\n")
+        self._f.write(_FCB_RECORD.pack(int(samples), len(packet)) + packet)
+
+    def close(self) -> None:
+        self._f.close()
+        self._scp.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _fcb_header(f, path: str) -> Dict[str, int]:
+    raw = f.read(_FCB_HEADER.size)
+    if len(raw) != _FCB_HEADER.size or raw[:4] != FCB_MAGIC:
+        raise ValueError(f"{path}: not an FCB1 file")
+    _, bits, n_q, _, sr, hop = _FCB_HEADER.unpack(raw)
+    return dict(bits=bits, n_q=n_q, sample_rate=sr, hop=hop)
+
+
+def read_fcb(path: str):
+    """(header dict(bits, n_q, sample_rate, hop), [(key, samples, packet)] in file order); every packet's header is checked"""
+    out = []
+    with open(path, "rb") as f:
+        head = _fcb_header(f, path)
+        while True:
+            raw = f.read(2)
+            if not raw:
+                break
+            key = f.read(struct.unpack("<H", raw)[0]).decode("utf-8")
+            samples, n = _FCB_RECORD.unpack(f.read(_FCB_RECORD.size))
+            packet = f.read(n)
+            parse_packet_header(packet, head["n_q"], head["bits"])
+            out.append((key, samples, packet))
+    return head, out
+
+
+def load_fcb_record(spec: str):
+    """``<fcb path>:<offset>`` (a line of codecs.fcb.scp) -> (header dict, samples, packet)"""
+    path, _, off = spec.rpartition(":")
+    with open(path, "rb") as f:
+        head = _fcb_header(f, path)
+        f.seek(int(off))
+        samples, n = _FCB_RECORD.unpack(f.read(_FCB_RECORD.size))
+        packet = f.read(n)
+    parse_packet_header(packet, head["n_q"], head["bits"])
+    return head, samples, packet
+
+
+def load_fcb_item(spec: str) -> Tuple[np.ndarray, int]:
+    """``<fcb path>:<offset>`` -> (tokens [T, n_q] int64 with zeros behind the packet's k, k); n_q is the file's"""
+    head, _, packet = load_fcb_record(spec)
+    tok, k, _ = unpack_packet(packet)
+    out = np.zeros((tok.shape[0], head["n_q"]), dtype=np.int64)
+    out[:, :k] = tok
+    return out, k
+
+
+# ------------------------------------------------------------------------------------------------
 # scp-driven batching with the reference's wrap padding
 # ------------------------------------------------------------------------------------------------
 def read_scp(path: str) -> List[Tuple[str, str]]:
@@ -230,6 +398,8 @@ def _load_item(value: str, dtype: str) -> np.ndarray:
         return load_kaldi_mat(value)
     if dtype == "npy":
         return np.load(value)
+    if dtype == "codec_fcb":
+        return load_fcb_item(value)[0]
     raise NotImplementedError(f"data type {dtype!r} is not supported by funcodec_amd.io")
 
 
@@ -258,7 +428,12 @@ def iter_batches(data_path_and_name_and_type: Sequence[Tuple[str, str, str]], ba
         bkeys = keys[i:i + batch_size]
         batch: Dict[str, torch.Tensor] = {}
         for name, dtype, table, _ in tables:
-            items = [_load_item(table[k], dtype) for k in bkeys]
+            if dtype == "codec_fcb":       # the packets carry each row's stage count: it travels next to the lengths
+                pairs = [load_fcb_item(table[k]) for k in bkeys]
+                items = [p[0] for p in pairs]
+                batch[name + "_n_q"] = torch.tensor([p[1] for p in pairs], dtype=torch.long)
+            else:
+                items = [_load_item(table[k], dtype) for k in bkeys]
             batch[name] = pad_list_with_mod(items, 0.0 if items[0].dtype.kind == "f" else 0, "wrap")
             batch[name + "_lengths"] = torch.tensor([it.shape[0] for it in items], dtype=torch.long)
         yield bkeys, batch

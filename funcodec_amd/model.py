@@ -14,7 +14,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ArchSpec
-from .engine import CodecEngine, EngineError, ragged_refusal, rate_min_nq, rate_targets, row_nq_list, rvq_beam_width
+from .engine import CodecEngine, EngineError, packed_refusal, ragged_refusal, rate_min_nq, rate_targets, row_nq_list, rvq_beam_width
 
 
 class EncodecMI355X:
@@ -143,7 +143,7 @@ class EncodecMI355X:
     @torch.no_grad()
     def inference(self, speech: torch.Tensor, need_recon: bool = True, bit_width: int = None,
                   use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None, rvq_beam: int = None,
-                  target_snr_db=None, min_n_q: int = 1) -> Dict[str, torch.Tensor]:
+                  target_snr_db=None, min_n_q: int = 1, packed: bool = False) -> Dict[str, torch.Tensor]:
         """bit_width: one value for the batch, as in the reference, or a sequence / 1-D tensor of B: row b is then what this call returns
         for it with ``bit_width[b]``; ``code_indices`` is [max n_q, B, Tf] with zeros at the stages a row does not take (``sub_quants`` too).
         speech_lengths [B] (optional): samples per row.  With it, row b of every output is what this call returns for
@@ -156,11 +156,34 @@ class EncodecMI355X:
         quantiser-domain SNR reaches its target (``engine.rate_pick`` states the rule; +inf: the best count), chosen on the device inside
         this one call; a per-row ``bit_width`` is the per-row cap.  Every output is then what this call returns with the ``bit_width`` of
         those counts (``rvq_beam``: the first k codes of the full-depth search).  The dict gains ``n_q_rows`` [B] int32 and ``row_snr_db``
-        [B] float64 (10 log10(E[0] / E[k]) of every row at its count), both on the device; a decoder needs the counts, code 0 is a valid code."""
+        [B] float64 (10 log10(E[0] / E[k]) of every row at its count), both on the device; a decoder needs the counts, code 0 is a valid code.
+        packed=True: the dict gains ``packets``, uint8 [B, pitch] on the device: one self-describing packet per row (csrc/code_pack_kernels.h
+        states it) holding the row's own frames (``speech_lengths``) and stage count (a per-row ``bit_width``; with ``target_snr_db`` the
+        counts go from the device tensor into the packer, nothing is read back).  ``engine.packets_to_host`` cuts them into bytes and
+        ``inference_decoding_packed`` decodes them.  Everything else the call returns, and launches, is unchanged."""
+        if packed:                                     # refused before anything reaches the device
+            why = packed_refusal(self.arch)
+            if why:
+                raise EngineError(why)
         if target_snr_db is not None:                  # refused before anything reaches the device
             rate_targets(self.arch, target_snr_db, speech.shape[0])
         with self.engine._rvq_beam(rvq_beam_width(self.arch, rvq_beam)):           # refused before anything reaches the device
-            return self._inference(speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db, min_n_q)
+            ret = self._inference(speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db, min_n_q)
+            if packed:
+                ret["packets"] = self._packets(ret, bit_width, speech_lengths)
+            return ret
+
+    def _packets(self, ret, bit_width, speech_lengths):
+        """the packets of a call's codes: frames per row from the engine's own frames() of speech_lengths, counts from the call's device
+        tensor (target_snr_db), else from a per-row bit_width, else every row has all stages of the call"""
+        codes = ret["code_indices"][0]
+        frames = None
+        if speech_lengths is not None:
+            frames = [self.engine.frames(int(n)) for n in torch.as_tensor(speech_lengths).reshape(-1).tolist()]
+        rows = ret.get("n_q_rows")
+        if rows is None:
+            rows = self._bit_widths(bit_width, codes.shape[1])[1]
+        return self.engine.pack_codes(codes, frames_rows=frames, n_q_rows=rows)
 
     def _inference(self, speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db=None, min_n_q=1):
         speech = self._as_bct(speech)
@@ -213,10 +236,10 @@ class EncodecMI355X:
     @torch.no_grad()
     def inference_encoding(self, speech: torch.Tensor, need_recon: bool = False, bit_width: int = None,
                            use_scale: bool = True, speech_lengths=None, rvq_beam: int = None, target_snr_db=None,
-                           min_n_q: int = 1) -> Dict[str, torch.Tensor]:
+                           min_n_q: int = 1, packed: bool = False) -> Dict[str, torch.Tensor]:
         # (model_conf.bypass_quantizer does not reach this entry point in the reference: it quantises, :748-750)
         return self.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, _quantise_always=True,
-                              speech_lengths=speech_lengths, rvq_beam=rvq_beam, target_snr_db=target_snr_db, min_n_q=min_n_q)
+                              speech_lengths=speech_lengths, rvq_beam=rvq_beam, target_snr_db=target_snr_db, min_n_q=min_n_q, packed=packed)
 
     # -- Encodec.inference_decoding (codec_basic.py:766-802) ---------------------------------
     @torch.no_grad()
@@ -233,6 +256,40 @@ class EncodecMI355X:
             recon = self.engine.overlap_add([recon], self.arch.segment_stride or 1)
         return dict(recon_speech=recon if need_recon else None, code_indices=None,
                     code_embeddings=[(emb, None)], sub_quants=None)
+
+    # -- not in the reference: decoding from the packets of ``inference(..., packed=True)`` ---------------------------------
+    @torch.no_grad()
+    def inference_decoding_packed(self, packets, need_recon: bool = True, use_scale: bool = True) -> Dict[str, torch.Tensor]:
+        """packets: a list of B ``bytes`` (one packet each; every header is validated) or the device buffer uint8 [B, pitch] of a packed
+        call -> what ``inference_decoding`` returns for the codes they hold, every row decoded with the stage count its packet carries:
+        unpack on the device (fc_codes_unpack), the counts of the headers as per-row stage counts, then the decode call there is.  Rows
+        of different frame counts go through ``token_lengths`` where the architecture has length-aware calls; otherwise rows of equal
+        length are required.  The dict also holds ``n_q_rows`` and ``token_lengths`` (lists, from the headers)."""
+        why = packed_refusal(self.arch)
+        if why:
+            raise EngineError(why)
+        eng = self.engine
+        if isinstance(packets, torch.Tensor):
+            if packets.dim() != 2 or packets.dtype != torch.uint8:
+                raise EngineError(f"inference_decoding_packed: a packet buffer is uint8 [B, pitch], got {packets.dtype} {tuple(packets.shape)}")
+            # the host needs the headers (the counts are a host argument of the decode call): 8 bytes per row
+            frames, counts = eng._parse_packets([bytes(h) for h in packets[:, :8].cpu().numpy()], exact=None)
+            buf = packets
+        else:
+            buf, _, counts = eng.packets_from_host(packets)
+            frames = eng._parse_packets(packets, exact=True)[0]
+        Tf, n_q = max(frames), max(counts)
+        lengths = None
+        if any(f != Tf for f in frames):
+            why = ragged_refusal(self.arch)
+            if why:
+                raise EngineError(f"inference_decoding_packed: the packets hold {frames} frames and rows of equal length are required: {why}")
+            lengths = frames
+        tokens = eng.unpack_codes(buf, Tf, n_q)
+        rows = counts if any(k != n_q for k in counts) else None
+        recon, emb = eng.decode_codes(tokens, lengths=lengths, n_q_rows=rows)
+        return dict(recon_speech=recon if need_recon else None, code_indices=None, code_embeddings=[(emb, None)], sub_quants=None,
+                    n_q_rows=counts, token_lengths=frames)
 
     # -- Encodec.inference_decoding_emb (codec_basic.py:804-836) -----------------------------
     @torch.no_grad()

@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .config import SEQ_FF, SEQ_HEADS
-from .engine import CodecEngine, EngineError, _on_device, _ptr, row_nq_list, rvq_beam_width
+from .engine import CodecEngine, EngineError, _on_device, _ptr, packed_refusal, row_nq_list, rvq_beam_width
 
 
 def stream_refusal(arch, max_frames: Optional[int] = None) -> Optional[str]:
@@ -264,6 +264,30 @@ class _Session:
                               f"session's max_frames = {self.max_frames} (the size of its key / value cache); nothing was changed, reset() "
                               "starts the next utterance")
 
+    # -- packets of a push (csrc/code_pack_kernels.h states the packet).  The pack / unpack launch is one more call on the session's
+    # stream, behind / in front of the push and outside any captured graph; a push that asks for no packets launches what it did.
+    def _packed_check(self) -> None:
+        why = packed_refusal(self.arch)
+        if why:
+            raise EngineError(why)
+
+    def _pack_rows(self, codes: torch.Tensor, frames, counts) -> List[bytes]:
+        """codes [n_q,R,Tf] of R rows with their own frames and stage counts -> R packets on the host (one launch, one copy)"""
+        with self._push_stream():
+            packets = self.engine.pack_codes(codes, frames_rows=frames, n_q_rows=counts)
+        return self.engine.packets_to_host(packets)
+
+    def _unpack_rows(self, packets, what: str):
+        """host packets -> (tokens [R,Tf,n_q] on the device, frames, counts), every header validated against the session's n_q"""
+        packets = [bytes(p) for p in packets]
+        buf, Tf, counts = self.engine.packets_from_host(packets, n_q=self.n_q)
+        frames = self.engine._parse_packets(packets, exact=True)[0]
+        if min(frames) < 1:
+            raise EngineError(f"{what}: a packet without frames decodes to nothing; leave it out")
+        with self._push_stream():
+            tokens = self.engine.unpack_codes(buf, Tf, self.n_q)
+        return tokens, frames, counts
+
     def _lstm_scratch(self, x: torch.Tensor) -> torch.Tensor:
         B, H, T = x.shape
         return self._scratch(4 * (T * B * 4 * H + 2 * B * H * T) + (1 << 20))
@@ -275,6 +299,9 @@ class CodecStream(_Session):
     * ``encode(wav, final=False) -> (codes [n_q,B,Tf], quantized [B,Tf,D])``: every push but the final one is a positive
       multiple of ``hop`` samples; the final one has any length >= 1.  A push that breaks the rule raises, it is never padded.
     * ``decode(codes [B,Tf,n_q])`` / ``decode_emb(emb [B,Tf,D]) -> wav [B,C,Tf*hop]``.
+    * ``encode(wav, final, packed=True)`` also returns the push's packets, a list of B ``bytes`` (csrc/code_pack_kernels.h states the
+      packet): this push's frames at every row's current stage count; ``decode_packed(packets, final=False)`` is the inverse and decodes
+      every row with the count its packet carries.  Pack and unpack are one more launch beside the push, outside any captured graph.
     * ``reset(scale=None)`` starts the next utterance.
     * ``set_n_q(rows)``: a stage count per utterance, each in [1, n_q], for the pushes that follow -- in the middle of an utterance
       too (a residual quantiser is a prefix code and carries nothing from frame to frame).  ``open_stream(batch, n_q=[...])`` sets them
@@ -358,8 +385,19 @@ class CodecStream(_Session):
         return codes, quant, enc
 
     @_on_device
-    def encode(self, wav: torch.Tensor, final: bool = False, want_enc_out: bool = False) -> Tuple[torch.Tensor, ...]:
-        """wav [B,T] or [B,C,T] -> (codes [n_q,B,Tf], quantized [B,Tf,D]), plus the encoder output [B,Tf,D] when want_enc_out"""
+    def encode(self, wav: torch.Tensor, final: bool = False, want_enc_out: bool = False, packed: bool = False) -> Tuple[torch.Tensor, ...]:
+        """wav [B,T] or [B,C,T] -> (codes [n_q,B,Tf], quantized [B,Tf,D]), plus the encoder output [B,Tf,D] when want_enc_out, plus, with
+        packed=True, the packets of the push last: a list of B ``bytes`` holding this push's frames at every row's current stage count
+        (self-contained: ``decode_packed`` takes them); an empty list while the start-up is held back."""
+        if packed:
+            self._packed_check()
+        res = self._encode(wav, final, want_enc_out)
+        if not packed:
+            return res
+        codes = res[0]
+        return res + (self._pack_rows(codes, None, self._row_nq) if codes.shape[-1] > 0 else [],)
+
+    def _encode(self, wav: torch.Tensor, final: bool, want_enc_out: bool) -> Tuple[torch.Tensor, ...]:
         wav = self.engine._wav_in(wav)
         if wav.dim() == 2:
             wav = wav.unsqueeze(1)
@@ -422,6 +460,22 @@ class CodecStream(_Session):
             self._h, _ptr(part), part.shape[1], int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(), self.engine._stream()), rows_apply=True)
 
     @_on_device
+    def decode_packed(self, packets, final: bool = False, use_scale: bool = True) -> torch.Tensor:
+        """The inverse of ``encode(..., packed=True)``: a list of B packets (``bytes``) of equal frame count -> wav [B,C,Tf*hop], every row
+        decoded with the stage count its packet carries (the session's own counts are untouched); final as in decode."""
+        self._packed_check()
+        if len(packets) != self.batch:
+            raise EngineError(f"this session streams {self.batch} utterances, got {len(packets)} packets")
+        tokens, frames, counts = self._unpack_rows(packets, "decode_packed")
+        if any(f != frames[0] for f in frames):
+            raise EngineError(f"decode_packed: the utterances of this session advance in lock-step, the packets hold {frames} frames")
+        keep, self._row_nq = self._row_nq, counts
+        try:
+            return self.decode(tokens, use_scale=use_scale, final=final)
+        finally:
+            self._row_nq = keep
+
+    @_on_device
     def decode_emb(self, emb: torch.Tensor, use_scale: bool = True, final: bool = False) -> torch.Tensor:
         """emb [B,Tf,D] -> wav [B,C,Tf*hop]; final as in decode"""
         emb = self.engine._dev(emb, torch.float32)
@@ -459,6 +513,8 @@ class StreamSlots(_Session):
       ``want_enc_out``); ``wav`` is [C,T] or [T]; a bare tensor means ``final=False``.  Every push of a slot but its final one is a
       positive multiple of ``hop`` samples.  Slots that are not named sit idle; slots that emitted nothing are not in the result.
     * ``decode({slot: (codes [Tf,n_q], final)})`` / ``decode_emb({slot: (emb [Tf,D], final)}) -> {slot: wav [C,Tf*hop]}``.
+    * ``encode(pushes, packed=True) -> (results, {slot: bytes})``: one packet per slot that emitted frames, with the slot's own frames and
+      stage count (an idle slot gives none); ``decode_packed({slot: packet | (packet, final)})`` is the inverse.
     * ``start(slot, scale=None, n_q=None)`` begins the next utterance of a slot (a fresh session has every slot started, scale 1); on a
       slot whose utterance is still running it abandons that utterance.  There is no ``end``: the final push ends an utterance.
     * ``set_n_q(slot, n_q)``: the slot's stage count, in [1, the session's n_q], for the pushes that follow -- at any time between
@@ -616,7 +672,25 @@ class StreamSlots(_Session):
         return out
 
     @_on_device
-    def encode(self, pushes, want_enc_out: bool = False) -> Dict[int, Tuple[torch.Tensor, ...]]:
+    def encode(self, pushes, want_enc_out: bool = False, packed: bool = False):
+        """packed=True: returns (results, packets) with packets = {slot: bytes}: one packet per slot that emitted frames in this call,
+        holding the slot's own frames at its own stage count (one pack launch and one copy for the whole push); an idle slot, or one still
+        gathering its start-up, gives no packet."""
+        if packed:
+            self._packed_check()
+        res = self._encode(pushes, want_enc_out)
+        if not packed:
+            return res
+        slots = [slot for slot, r in res.items() if r[0].shape[-1] > 0]
+        if not slots:
+            return res, {}
+        frames = [int(res[slot][0].shape[-1]) for slot in slots]
+        codes = torch.zeros((self.n_q, len(slots), max(frames)), dtype=torch.int64, device=self.device)
+        for j, slot in enumerate(slots):
+            codes[:, j, :frames[j]] = res[slot][0]
+        return res, dict(zip(slots, self._pack_rows(codes, frames, [self._row_nq[slot] for slot in slots])))
+
+    def _encode(self, pushes, want_enc_out: bool = False) -> Dict[int, Tuple[torch.Tensor, ...]]:
         ch = self.engine.channels
 
         def as_ct(item):
@@ -680,6 +754,24 @@ class StreamSlots(_Session):
         """{slot: (codes [Tf,n_q], final)} -> {slot: wav [C,Tf*hop]}.  final=True says the slot's utterance ends here: it changes no sample
         but raises if frames are still held back, and the slot then needs ``start``."""
         return self._decode(pushes, use_scale, False)
+
+    @_on_device
+    def decode_packed(self, pushes, use_scale: bool = True) -> Dict[int, torch.Tensor]:
+        """The inverse of ``encode(..., packed=True)``: {slot: packet | (packet, final)} -> {slot: wav [C,Tf*hop]}, every slot decoded from
+        its own frames with the stage count its packet carries (the slots' own counts are untouched); final as in decode."""
+        self._packed_check()
+        items = {self._slot(slot): (item if isinstance(item, tuple) else (item, False)) for slot, item in pushes.items()}
+        if not items:
+            return {}
+        slots = list(items)
+        tokens, frames, counts = self._unpack_rows([items[slot][0] for slot in slots], "decode_packed")
+        keep = list(self._row_nq)
+        for j, slot in enumerate(slots):
+            self._row_nq[slot] = counts[j]
+        try:
+            return self.decode({slot: (tokens[j, :frames[j]], items[slot][1]) for j, slot in enumerate(slots)}, use_scale=use_scale)
+        finally:
+            self._row_nq = keep
 
     @_on_device
     def decode_emb(self, pushes, use_scale: bool = True) -> Dict[int, torch.Tensor]:

@@ -273,6 +273,34 @@ int fc_engine_set_rate(fc_engine* e, const double* ratio_rows /* host [B] or NUL
  * codes dev i64 [n_q,N]; quantized dev f32 [N,D] or NULL.  Honours fc_engine_set_row_nq as the caps. */
 int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, void* stream);
 
+/* ---- the bit stream: one self-describing packet per row (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
+ * csrc/code_pack_kernels.h states the packet rule (8-byte little-endian header: u32 frames, u8 k, u8 bits, u8 mode = 0, u8 0; payload
+ * value t * k + i = codes[i][b][t] in `bits` bits each, LSB first, pad bits 0) and the device row (pitch = the largest packet rounded up
+ * to 16, zeros behind the packet); funcodec_amd/io.py restates it on the host.  None of the four calls needs an engine.
+ * There is no fused "decode from packets" call: decoding is fc_codes_unpack, then fc_engine_set_row_nq with the counts of the headers
+ * (the host holds the bytes and therefore the headers), then the decode calls.  A call that asks for no packets launches what it did.
+ * Not built: a count per frame (mode 1), entropy coding, packets for quantizer_conf.q0_ds_ratio > 1 and for segmented mode.
+ * Measured 2026-10-21 on the MI355X (tools/code_pack.py, profiles/code_pack.txt; median of 24, every call synchronised): both launches
+ * are bound by their launch -- 17.7 us to pack and 17.0 us to unpack 16 x 250 frames x 32 stages x 10 bits (1.02 MB of int64, 0.16 MB of
+ * packets), 17.9 / 17.6 us for 32 x 1 x 32, 18.5 / 18.3 us for 1 x 7500 x 32; pack plus one copy of the packets 50.9 us against 59.8 us
+ * for a copy of the int64 codes.  Packing does not pay in time: the feature is the bytes. */
+/* By the packet rule of csrc/code_pack_kernels.h: the row pitch of a packet buffer for up to `frames` frames of n_q stages; host
+ * arithmetic, works without a GPU.  0 for arguments outside the format (frames < 0, n_q outside 1..255, bits outside 1..16). */
+size_t fc_code_packet_pitch(int frames, int n_q, int bits);
+/* By the packet rule of csrc/code_pack_kernels.h: 8 + ceil(frames k bits / 8), the length of one packet; 0 as above. */
+size_t fc_code_packet_bytes(int frames, int k, int bits);
+/* By the packet rule of csrc/code_pack_kernels.h: codes dev i64 [n_q][B][Tf] -> packets dev u8 [B][pitch].  frames_rows, n_q_rows: dev
+ * i32 [B] or NULL (all Tf / all n_q); both are read and clamped on the device (frames to [0, Tf], k to [1, n_q]), so n_q_rows_out of
+ * fc_engine_set_rate feeds it directly; nothing behind a row's frames or k is read; a code is taken modulo 2^bits; every byte up to
+ * the pitch is written.  Refused before any launch, naming the argument: bits outside 1..16, n_q outside 1..255, a pitch below
+ * fc_code_packet_pitch(Tf, n_q, bits) (or no multiple of 4), null codes / packets. */
+int fc_codes_pack(const int64_t* codes, int B, int Tf, int n_q, int bits, const int32_t* frames_rows, const int32_t* n_q_rows,
+                  uint8_t* packets, size_t pitch, void* stream);
+/* By the packet rule of csrc/code_pack_kernels.h: packets dev u8 [B][pitch] -> tokens dev i64 [B][Tf][n_q], the layout the decode
+ * calls take, zeros at stages >= k and frames >= frames.  The headers' frames and k are clamped on the device to Tf and n_q; `bits` is
+ * the call's.  Refusals as for fc_codes_pack. */
+int fc_codes_unpack(const uint8_t* packets, size_t pitch, int B, int Tf, int n_q, int bits, int64_t* tokens, void* stream);
+
 /* _linear_overlap_add (funcodec/models/codec_basic.py:77-116), the tail of Encodec._decode (:382-396) when
  * model_conf.segment_dur is set: triangle-weighted overlap-add of the decoded segments, products accumulated in
  * frame order and divided once by the summed weights, exactly as the reference orders it.

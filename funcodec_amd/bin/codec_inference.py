@@ -77,6 +77,7 @@ class Speech2Token:
         self.rvq_beam = rvq_beam_width(model.arch, rvq_beam)
         self.last_n_q_rows = self.last_row_snr_db = None          # of the last call made with target_snr_db
         self.last_packets = None                                  # of the last call made with packed=True
+        self.last_n_q_frames = self.last_n_codes_rows = None      # of the last call made with per_frame=True
 
     @torch.no_grad()
     def __call__(
@@ -93,6 +94,8 @@ class Speech2Token:
             min_n_q: int = 1,
             packed: bool = False,
             n_q_rows=None,
+            per_frame: bool = False,
+            n_q_frames=None,
     ):
         """Returns (code_indices, code_embeddings, recon_speech, sub_quants) like the reference (:86-134).
 
@@ -111,7 +114,19 @@ class Speech2Token:
         csrc/code_pack_kernels.h).  The 4-tuple stays; the packets (device uint8 [B, pitch]) stand in ``last_packets``, None after any other call.
 
         n_q_rows (not in the reference; run_mod="decode" only): a stage count per row, as the packets of ``codecs.fcb`` carry it; row b's
-        tokens behind its count are not read."""
+        tokens behind its count are not read.
+
+        per_frame (not in the reference; with target_snr_db, in the modes that encode): a stage count per FRAME (EncodecMI355X.inference,
+        csrc/rvq_frame_rate_kernels.h); min_n_q may then be 0.  The counts of the last such call stand in ``last_n_q_frames``
+        (device int32 [B, Tf]) and ``last_n_codes_rows``; ``last_n_q_rows`` holds every row's largest, ``last_packets`` packets of mode 1.
+
+        n_q_frames (not in the reference; run_mod="decode" only): a stage count per frame [B, T], as mode-1 packets carry it."""
+        if per_frame and run_mod not in ("inference", "encode"):
+            raise ValueError(f"per_frame belongs to the modes that encode (inference, encode), not run_mod={run_mod!r}")
+        if per_frame and target_snr_db is None:
+            raise ValueError("per_frame chooses a stage count per frame by target_snr_db: give a target")
+        if n_q_frames is not None and run_mod != "decode":
+            raise ValueError(f"n_q_frames belongs to run_mod='decode', not run_mod={run_mod!r}")
         if packed and run_mod not in ("inference", "encode"):
             raise ValueError(f"packed belongs to the modes that encode (inference, encode), not run_mod={run_mod!r}")
         if n_q_rows is not None and run_mod != "decode":
@@ -120,9 +135,11 @@ class Speech2Token:
         if target_snr_db is not None and run_mod not in ("inference", "encode"):
             raise ValueError(f"target_snr_db belongs to the modes that encode (inference, encode), not run_mod={run_mod!r}")
         rate = {} if target_snr_db is None else dict(target_snr_db=target_snr_db, min_n_q=min_n_q)
+        if per_frame:
+            rate["per_frame"] = True
         if packed:
             rate["packed"] = True
-        self.last_n_q_rows = self.last_row_snr_db = None
+        self.last_n_q_rows = self.last_row_snr_db = self.last_n_q_frames = self.last_n_codes_rows = None
         rvq_beam = getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam       # (an instance built around a ready model has none)
         if ppg is not None:
             raise NotImplementedError("ppg conditioning (codec_semantic_aug) is outside the hot-path scope")
@@ -145,7 +162,9 @@ class Speech2Token:
                 nq = int(max(bit_width // bit_per_quant, 1))
             speech = speech[:, :, :nq]
             logging.info("use %d quantizers.", speech.shape[-1])
-            if n_q_rows is not None:         # the counts of the rows' packets, no larger than the stages kept
+            if n_q_frames is not None:       # the counts of mode-1 packets: the device clamps them to the stages kept
+                ret = self.model.inference_decoding(speech, token_lengths=speech_lengths, n_q_frames=n_q_frames)
+            elif n_q_rows is not None:       # the counts of the rows' packets, no larger than the stages kept
                 rows = [min(int(k), speech.shape[-1]) for k in torch.as_tensor(n_q_rows).reshape(-1).tolist()]
                 recon, emb = self.model.engine.decode_codes(speech, lengths=speech_lengths,
                                                             n_q_rows=rows if any(k != speech.shape[-1] for k in rows) else None)
@@ -156,6 +175,7 @@ class Speech2Token:
                 ret = self.model.inference_decoding(speech, token_lengths=speech_lengths)
         self.last_packets = ret.get("packets")
         self.last_n_q_rows, self.last_row_snr_db = ret.get("n_q_rows"), ret.get("row_snr_db")
+        self.last_n_q_frames, self.last_n_codes_rows = ret.get("n_q_frames"), ret.get("n_codes_rows")
         if self.check_status:
             self.model.engine.check_status(sync=True)
         if self.dtype != "float32":
@@ -282,6 +302,15 @@ def inference_modelscope(
             # next to the indices: `key k snr_db` per utterance.  The indices files keep their shape with zeros behind k; a decoder needs k
             # (a bit_width per row), since code 0 is a valid code
             n_q_writer = open(os.path.join(output_path, "codec_n_q.txt"), "wt")
+        per_frame = _str2bool(kwargs.get("per_frame", False))
+        min_n_q_arg = int(kwargs.get("min_n_q") or 1)                        # --min_n_q 0 is a floor of frame mode alone
+        if per_frame and kwargs.get("min_n_q") is not None:
+            min_n_q_arg = int(kwargs.get("min_n_q"))
+        if per_frame and target_snr_db is None:
+            raise ValueError("--per_frame chooses a stage count per frame by --target_snr_db: give a target")
+        if per_frame and kwargs.get("need_indices") and kwargs.get("indices_save_type") != "packed":
+            raise ValueError("--per_frame with --need_indices requires --indices_save_type packed: the text and ark forms have no place for "
+                             f"the counts of the frames, got --indices_save_type {kwargs.get('indices_save_type')}")
         ark_indices = kwargs.get("indices_save_type") == "ark"
         packed_indices = bool(kwargs.get("need_indices")) and kwargs.get("indices_save_type") == "packed"
         run_mod = kwargs.get("run_mod", "inference")
@@ -368,7 +397,10 @@ def inference_modelscope(
                 for key, packet, n in zip(keys, packets_host, speech_length):
                     fcb_writer(key, packet, int(n))
             if nq_host is not None and n_q_writer is not None:
-                n_q_writer.write("".join(f"{key} {int(k)} {float(snr):.4f}\n" for key, k, snr in zip(keys, *nq_host)))
+                if len(nq_host) == 3:      # --per_frame: `key k_max snr_db mean_k` (mean_k over the utterance's own frames)
+                    n_q_writer.write("".join(f"{key} {int(k)} {float(snr):.4f} {float(mk):.4f}\n" for key, k, snr, mk in zip(keys, *nq_host)))
+                else:
+                    n_q_writer.write("".join(f"{key} {int(k)} {float(snr):.4f}\n" for key, k, snr in zip(keys, *nq_host)))
             if lines:
                 indices_writer.write("".join(lines))
             for i, key in enumerate(keys):               # Kaldi ark writers keep file offsets: sequential, in order
@@ -397,6 +429,9 @@ def inference_modelscope(
                 speech_length = batch.pop("speech_lengths")
                 if "speech_n_q" in batch:                               # a codec_fcb input: every row decodes with the count its packet carries
                     batch["n_q_rows"] = batch.pop("speech_n_q")
+                if "speech_n_q_frames" in batch:                        # mode-1 packets in the batch: a count per frame (a mode-0 row: its k in every frame)
+                    batch["n_q_frames"] = batch.pop("speech_n_q_frames")
+                    batch.pop("n_q_rows", None)
                 if _str2bool(kwargs.get("length_aware", False)):        # opt-in: the lengths go to the model instead of being dropped
                     if should_resample:
                         raise NotImplementedError("length_aware with file_sampling_rate != sampling_rate (the lengths count file samples)")
@@ -405,7 +440,8 @@ def inference_modelscope(
                 token_id, token_emb, recon_speech, sub_quants = my_model(**batch, need_recon=True, bit_width=bw,
                                                                          use_scale=use_scale, run_mod=run_mod,
                                                                          **({} if target_snr_db is None else dict(
-                                                                             target_snr_db=float(target_snr_db), min_n_q=int(kwargs.get("min_n_q") or 1))))
+                                                                             target_snr_db=float(target_snr_db), per_frame=per_frame,
+                                                                             min_n_q=min_n_q_arg)))
                 # device-side failures cannot raise in-line like the reference's F.embedding / asserts do: synchronise and ask the
                 # engine before anything of this batch is written (corrupt token files, LSTM barrier timeout)
                 my_model.model.engine.check_status(sync=True)
@@ -415,12 +451,16 @@ def inference_modelscope(
                 tok_host = [x.cpu().contiguous() for x in token_id] if (token_id is not None and indices_writer is not None) else None
                 sq_host = [x.cpu() for x in sub_quants] if (sub_quants is not None and sub_quants_writer is not None) else None
                 nq_host = None if target_snr_db is None else (my_model.last_n_q_rows.tolist(), my_model.last_row_snr_db.tolist())
+                if per_frame:
+                    fr = [max(int(math.ceil(int(n) / hop)), 1) for n in speech_length]
+                    nq_host = ([max(k, 1) for k in nq_host[0]], nq_host[1], [c / f for c, f in zip(my_model.last_n_codes_rows.tolist(), fr)])
                 packets_host = None
                 if fcb_writer is not None:
                     # the frames the text form writes for a row (ceil(samples / hop)); the counts of a target go from the device tensor into the packer
                     eng = my_model.model.engine
                     frames = [int(math.ceil(int(n) / hop)) for n in speech_length]
-                    packets_host = eng.packets_to_host(eng.pack_codes(token_id[0], frames_rows=frames, n_q_rows=my_model.last_n_q_rows))
+                    packets_host = eng.packets_to_host(eng.pack_codes(token_id[0], frames_rows=frames, n_q_rows=my_model.last_n_q_rows,
+                                                                      n_q_frames=my_model.last_n_q_frames))
                 jobs.append((keys, speech_length, tok_host, sq_host, pool.submit(_write_batch, keys, speech_length, recon_host, tok_host), nq_host,
                              packets_host))
                 while len(jobs) > 3:                                                # bounds the host memory held by queued batches
@@ -499,6 +539,10 @@ def get_parser():
     # this SNR in the quantiser's domain; codec_n_q.txt (`key k snr_db`) is written next to the indices, which keep their shape
     g.add_argument("--target_snr_db", type=float, default=None)
     g.add_argument("--min_n_q", type=int, default=1)
+    # not in the reference: with --target_snr_db, a stage count per FRAME (every frame is coded down to the utterance's noise floor; a frame
+    # may take no stage with --min_n_q 0).  With --need_indices it requires --indices_save_type packed (mode-1
+    # packets carry the counts); codec_n_q.txt lines become `key k_max snr_db mean_k`
+    g.add_argument("--per_frame", type=_str2bool, default=False)
     return p
 
 

@@ -16,6 +16,7 @@
 #include "../../include/funcodec_amd.h"
 #include "kernels.h"
 #include "rvq_beam_kernels.h"
+#include "rvq_frame_rate_kernels.h"
 #include "rvq_rate_kernels.h"
 #include "laura_kernels.h"
 #include "ragged_kernels.h"
@@ -178,8 +179,16 @@ struct fc_engine {
         int32_t* n_q_out = nullptr;
         double* row_err_out = nullptr;
         float* stage_err_out = nullptr;
+        // frame mode (fc_engine_set_rate_frames; csrc/rvq_frame_rate_kernels.h states the rule): a count per frame; min_nq may then be 0
+        bool frames = false;
+        int32_t* nq_frames_out = nullptr;
+        int32_t* n_codes_out = nullptr;
+        double* achieved_out = nullptr;
         bool on() const { return !ratio.empty(); }
+        void clear_frames() { frames = false; nq_frames_out = nullptr; n_codes_out = nullptr; achieved_out = nullptr; }
     } rate;
+    // a stage count per frame for the offline decode_codes calls that follow (fc_engine_set_frame_nq): the caller's device table, borrowed
+    struct FrameNq { const int32_t* table = nullptr; int B = 0, Tf = 0; } frame_nq;
     bool lstm_persist_ok = true;             // cleared after a grid-barrier timeout: later calls take the per-step launch path
     int persist_checked_B = -1; bool persist_checked_val = false;
     // optional event timing
@@ -1941,7 +1950,28 @@ int rate_check(const fc_engine* e, int rows, int n_q) {
 // an encode push of a session while a rate is set
 int rate_refuse_session(const fc_engine* e, const char* who) {
     if (!e->rate.on()) return 0;
+    if (e->rate.frames)
+        return fail(std::string(who) + ": frame mode is set (fc_engine_set_rate_frames): a stage count per frame by target SNR is for offline calls only; "
+                    "clear it with NULL ratios (fc_engine_set_rate)");
     return fail(std::string(who) + ": a rate is set (fc_engine_set_rate): a stage count per row by target SNR is for offline calls only; clear it with NULL ratios");
+}
+
+// ---- a stage count per frame for decode calls (fc_engine_set_frame_nq) --------------------------------
+// The rule of an offline decode_codes call made while a frame table is set, checked BEFORE its first launch: the table's B and Tf.
+int frame_nq_check(const fc_engine* e, int B, int Tf) {
+    if (!e->frame_nq.table) return 0;
+    if (!e->row_nq.empty())
+        return fail("a stage count per frame (fc_engine_set_frame_nq) and per-row stage counts (fc_engine_set_row_nq) are both set; clear one of them");
+    if (e->frame_nq.B != B || e->frame_nq.Tf != Tf)
+        return fail("a stage count per frame is set for [" + std::to_string(e->frame_nq.B) + "][" + std::to_string(e->frame_nq.Tf) +
+                    "] frames (fc_engine_set_frame_nq); this call has [" + std::to_string(B) + "][" + std::to_string(Tf) + "] (clear it with a NULL table)");
+    return 0;
+}
+
+// a decode push of a session while a frame table is set
+int frame_nq_refuse_session(const fc_engine* e, const char* who) {
+    if (!e->frame_nq.table) return 0;
+    return fail(std::string(who) + ": a stage count per frame is set (fc_engine_set_frame_nq): it is for offline decode calls only; clear it with a NULL table");
 }
 
 // ---- composite paths (each usable in dry mode for workspace sizing / work accounting) ---------------
@@ -2025,14 +2055,29 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
             cx.launch("rvq stage errors", "", [&] {
                 return fc::launch_rvq_stage_errors(xq, codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, serr, Tf, nq_rows, *offline_rows, cx.st);
             });
-            cx.launch("rvq rate rows", "", [&] {
-                return fc::launch_rvq_rate_rows(serr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.k_dev, e->rate.n_q_out, rerr,
-                                                cx.st);
-            });
-            cx.launch("rvq rate sum", "", [&] {
-                return fc::launch_rvq_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf, cx.st, e->rate.k_dev);
-            });
-            cx.launch("rvq rate zero codes", "", [&] { return fc::launch_rvq_rate_zero_codes(codes, B * Tf, Tf, n_q, e->rate.k_dev, cx.st); });
+            if (e->rate.frames) {       // fc_engine_set_rate_frames: the row sums alone, then a count per frame and everything from the first k_t codes
+                cx.launch("rvq rate rows", "", [&] {
+                    return fc::launch_rvq_rate_rows(serr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, 1, nullptr, nullptr, rerr, cx.st);
+                });
+                cx.launch("rvq rate frames", "", [&] {
+                    return fc::launch_rvq_rate_frames(serr, rerr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.nq_frames_out,
+                                                      e->rate.n_q_out, e->rate.n_codes_out, e->rate.achieved_out, cx.st);
+                });
+                cx.launch("rvq frame sum", "", [&] {
+                    return fc::launch_rvq_frame_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf,
+                                                          e->rate.nq_frames_out, cx.st);
+                });
+                cx.launch("rvq frame zero codes", "", [&] { return fc::launch_rvq_frame_zero_codes(codes, B * Tf, n_q, e->rate.nq_frames_out, cx.st); });
+            } else {
+                cx.launch("rvq rate rows", "", [&] {
+                    return fc::launch_rvq_rate_rows(serr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.k_dev, e->rate.n_q_out,
+                                                    rerr, cx.st);
+                });
+                cx.launch("rvq rate sum", "", [&] {
+                    return fc::launch_rvq_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf, cx.st, e->rate.k_dev);
+                });
+                cx.launch("rvq rate zero codes", "", [&] { return fc::launch_rvq_rate_zero_codes(codes, B * Tf, Tf, n_q, e->rate.k_dev, cx.st); });
+            }
         }
     }
     float* qbdt = qbdt_c;
@@ -2083,7 +2128,9 @@ float* decoder_input_emb(fc_engine* e, Ctx& cx, const float* emb, int Tf) {
 // (optional) gets the embeddings [B][Tf][D].  `rows` (null, or the frames of every row of a ragged call / slot push): the tokens behind a
 // row's frames are the caller's garbage, so a masked copy is looked up (none of them is read, or reported as out of range) and emb_out is
 // masked too.  `either` (workspace sizing): the first buffer as wide as the wider of the two decode calls needs it.
-float* decoder_input_codes(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, int n_q, float* emb_out, const fc::RagLen* rows, bool either = false) {
+// `frame_nq` (an offline call under fc_engine_set_frame_nq, else null): a stage count per frame [B][Tf], by csrc/rvq_frame_rate_kernels.h.
+float* decoder_input_codes(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, int n_q, float* emb_out, const fc::RagLen* rows, bool either = false,
+                           const int32_t* frame_nq = nullptr) {
     const int B = cx.B, D = e->arch.dimension, Dc = e->cdim();
     if (rows) {
         int64_t* masked = cx.alloc<int64_t>((size_t)B * Tf * n_q);
@@ -2095,6 +2142,9 @@ float* decoder_input_codes(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, 
     const int* nq_rows = row_nq_table(e);              // a row's codes behind its count are not read
     if (!cx.dry && nq_rows && (int)e->row_nq.size() != B) cx.fail("internal: per-row stage counts of another batch width");
     cx.launch("rvq decode", "", [&] {
+        if (frame_nq)
+            return fc::launch_rvq_frame_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, frame_nq,
+                                               rows ? *rows : fc::RagLen(), cx.st);
         return fc::launch_rvq_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st,
                                      nq_rows);
     });
@@ -3011,8 +3061,9 @@ int fc_decode_codes(fc_engine* e, const int64_t* codes, int B, int Tf, int n_q, 
     if (!codes || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     if (row_nq_check(e, B, n_q)) return 1;
+    if (frame_nq_check(e, B, Tf)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
-    return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, nullptr), Tf, nullptr, out_len, wav);
+    return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, nullptr, false, e->frame_nq.table), Tf, nullptr, out_len, wav);
 }
 
 int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int use_scale, int64_t* codes, float* quantized,
@@ -3077,11 +3128,12 @@ int fc_decode_codes_ragged(fc_engine* e, const int64_t* codes, const int32_t* le
     if (!codes || !lengths || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     if (row_nq_check(e, B, n_q)) return 1;
+    if (frame_nq_check(e, B, Tf)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     const Pass p = ragged_pass(e, cx, lengths, Tf, 1);
     fc::RagLen f; f.lens = p.lengths;
     fc::RagLen v; v.lens = p.lengths; v.mul = total_hop(e);
-    return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, &f), Tf, nullptr, out_len, wav, p, &v);
+    return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, &f, false, e->frame_nq.table), Tf, nullptr, out_len, wav, p, &v);
 }
 
 int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengths, int B, int T, int n_q, int use_scale, int64_t* codes,
@@ -3174,6 +3226,7 @@ int fc_engine_set_rate(fc_engine* e, const double* ratio_rows, int B, int min_nq
                        float* stage_errors_out, void* stream) {
     if (!e) return fail("null engine");
     if (!e->finalized) return fail("engine not finalized");
+    e->rate.clear_frames();             // frame mode is given after the rate, every time (fc_engine_set_rate_frames)
     if (!ratio_rows) { e->rate.ratio.clear(); e->rate.n_q_out = nullptr; e->rate.row_err_out = nullptr; e->rate.stage_err_out = nullptr; return 0; }
     if (B <= 0) return fail("fc_engine_set_rate: a rate holds at least one row");
     if (!n_q_rows_out) return fail("fc_engine_set_rate: n_q_rows_out (device int32 [B]) takes the chosen stage counts");
@@ -3206,6 +3259,33 @@ int fc_engine_set_rate(fc_engine* e, const double* ratio_rows, int B, int min_nq
     return 0;
 }
 
+int fc_engine_set_rate_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out, int32_t* n_codes_rows_out, double* achieved_out, void* stream) {
+    (void)stream;
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!e->rate.on()) return fail("fc_engine_set_rate_frames: no rate is set: it is given after fc_engine_set_rate");
+    if (!n_q_frames_out) return fail("fc_engine_set_rate_frames: n_q_frames_out (device int32 [B][Tf]) takes the chosen stage counts");
+    if (min_nq < 0 || min_nq > e->arch.num_quantizers)
+        return fail("fc_engine_set_rate_frames: min_nq lies in [0, num_quantizers = " + std::to_string(e->arch.num_quantizers) + "], got " +
+                    std::to_string(min_nq));
+    e->rate.frames = true;
+    e->rate.min_nq = min_nq;
+    e->rate.nq_frames_out = n_q_frames_out; e->rate.n_codes_out = n_codes_rows_out; e->rate.achieved_out = achieved_out;
+    return 0;
+}
+
+int fc_engine_set_frame_nq(fc_engine* e, const int32_t* n_q_frames, int B, int Tf, void* stream) {
+    (void)stream;
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!n_q_frames) { e->frame_nq = fc_engine::FrameNq(); return 0; }
+    if (B <= 0 || Tf <= 0) return fail("fc_engine_set_frame_nq: a table holds at least one row of at least one frame");
+    if (!e->row_nq.empty())
+        return fail("fc_engine_set_frame_nq: per-row stage counts are set (fc_engine_set_row_nq): a call takes a count per row or per frame, not both");
+    e->frame_nq.table = n_q_frames; e->frame_nq.B = B; e->frame_nq.Tf = Tf;
+    return 0;
+}
+
 int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, void* stream) {
     if (check_ready(e)) return 1;
     if (!x || !codes || N <= 0) return fail("bad argument");
@@ -3224,6 +3304,14 @@ int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, 
     HIP_TRY(fc::launch_rvq_encode(x, N, Dc, K, n_q, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, nullptr, Tf, st, nullptr, row_nq_table(e)));
     if (width > 1) HIP_TRY(fc::launch_rvq_beam(x, N, Dc, K, n_q, width, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, Tf, st, row_nq_table(e)));
     HIP_TRY(fc::launch_rvq_stage_errors(x, codes, N, Dc, K, n_q, e->cb, e->rate.stage_err_out, Tf, row_nq_table(e), rows, st));
+    if (e->rate.frames) {       // fc_engine_set_rate_frames: by csrc/rvq_frame_rate_kernels.h
+        HIP_TRY(fc::launch_rvq_rate_rows(e->rate.stage_err_out, B, Tf, n_q, row_nq_table(e), rows, e->rate.ratio_dev, 1, nullptr, nullptr, e->rate.row_err_out, st));
+        HIP_TRY(fc::launch_rvq_rate_frames(e->rate.stage_err_out, e->rate.row_err_out, B, Tf, n_q, row_nq_table(e), rows, e->rate.ratio_dev, e->rate.min_nq,
+                                           e->rate.nq_frames_out, e->rate.n_q_out, e->rate.n_codes_out, e->rate.achieved_out, st));
+        if (quantized) HIP_TRY(fc::launch_rvq_frame_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, e->rate.nq_frames_out, st));
+        HIP_TRY(fc::launch_rvq_frame_zero_codes(codes, N, n_q, e->rate.nq_frames_out, st));
+        return 0;
+    }
     HIP_TRY(fc::launch_rvq_rate_rows(e->rate.stage_err_out, B, Tf, n_q, row_nq_table(e), rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.k_dev,
                                      e->rate.n_q_out, e->rate.row_err_out, st));
     if (quantized) HIP_TRY(fc::launch_rvq_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, st, e->rate.k_dev));
@@ -3794,6 +3882,7 @@ int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_
     if (!codes || !wav) return fail("bad argument");
     if (stream_decode_check(S, Tfc)) return 1;
     if (row_nq_check(S->e, S->B, S->n_q)) return 1;
+    if (frame_nq_refuse_session(S->e, "fc_stream_decode_codes")) return 1;
     return stream_decode_push(S, kFormDecodeCodes, codes, Tfc, use_scale, wav, emb_out, workspace, workspace_bytes, stream);
 }
 
@@ -3929,6 +4018,7 @@ int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int3
     if (!codes || !frames || !flags || !wav) return fail("bad argument");
     if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->max_chunk, total_hop(Q->e)))) return 1;
     if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
+    if (frame_nq_refuse_session(Q->e, "fc_slots_decode_codes")) return 1;
     const Session::GraphKey key = graph_key(*Q, kFormDecodeCodes, Tfc, Q->dec_pushes, use_scale, {codes, wav, emb_out}, workspace, workspace_bytes, stream);
     const int err = session_push(
         Q, &key, workspace, workspace_bytes, stream, [&](hipStream_t st) { return slots_upload(Q, true, frames, flags, workspace, workspace_bytes, st); },

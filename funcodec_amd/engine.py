@@ -174,6 +174,54 @@ def rate_pick(E, ratio: float, min_n_q: int, cap: int) -> int:
     return best
 
 
+def rate_min_nq_frames(arch, min_n_q, cap: Optional[int] = None, rows=None) -> int:
+    """A checked ``min_n_q`` of frame mode (``per_frame=True``): an integer in [0, cap] (cap: ``num_quantizers`` unless given) and no
+    larger than any per-row cap -- a frame may take no stage at all."""
+    cap = arch.num_quantizers if cap is None else int(cap)
+    if isinstance(min_n_q, bool) or not isinstance(min_n_q, numbers.Integral) or not 0 <= int(min_n_q) <= cap:
+        raise EngineError(f"min_n_q lies in [0, {cap}] with per_frame, got {min_n_q!r}")
+    if rows is not None:
+        for b, k in enumerate(rows):
+            if int(min_n_q) > k:
+                raise EngineError(f"min_n_q = {int(min_n_q)} lies above the cap of row {b} ({k} stages)")
+    return int(min_n_q)
+
+
+def rate_pick_frames(err, E, ratio: float, min_n_q: int, cap: int, frames: Optional[int] = None):
+    """The stage counts of one row's frames (csrc/rvq_frame_rate_kernels.h, include/funcodec_amd.h), a pure function of its float32
+    stage errors err[0 .. cap][t] (err[k][t]: frame t's residual energy after k stages), its float64 row errors E[0 .. cap], its ratio
+    10^(-target / 10), the floor in [0, cap], the cap and its own frame count (default: all of err's):
+      - row energies that are not all finite: every frame takes cap;
+      - E[0] == 0 (digital silence): every frame takes the floor;
+      - else frame t takes the smallest k in [floor, cap] with float64(err[k][t]) * float64(frames) <= E[0] * ratio;
+      - no such k: the k in that range with the smallest err[k][t], first on ties;
+      - frames behind the row's frames take 0.
+    Returns int32 [Tf] (Tf = err.shape[1])."""
+    err = np.asarray(err, dtype=np.float32)
+    Tf = err.shape[1]
+    F = Tf if frames is None else min(int(frames), Tf)
+    out = np.zeros((Tf,), dtype=np.int32)
+    Ev = [float(v) for v in np.asarray(E, dtype=np.float64)[:cap + 1]]
+    lo = min(max(int(min_n_q), 0), cap)
+    if not all(np.isfinite(v) for v in Ev):
+        out[:F] = cap
+        return out
+    if Ev[0] == 0.0:
+        out[:F] = lo
+        return out
+    thr = np.float64(Ev[0]) * np.float64(ratio)
+    for t in range(F):
+        best, hit = lo, -1
+        for k in range(lo, cap + 1):
+            if np.float64(err[k, t]) * np.float64(F) <= thr:
+                hit = k
+                break
+            if err[k, t] < err[best, t]:
+                best = k
+        out[t] = hit if hit >= 0 else best
+    return out
+
+
 def row_nq_list(arch, rows, B: int, cap: Optional[int] = None) -> list:
     """The per-row stage counts of a call as a list of B ints in [1, cap] (cap: ``num_quantizers`` unless given); raises before any
     engine call -- a bad count or a list of the wrong length refuses the call as a whole."""
@@ -413,11 +461,12 @@ class CodecEngine:
             self.lib.fc_engine_set_row_nq(self._h, None, 0, None)
 
     @contextlib.contextmanager
-    def _rate(self, ratios, min_n_q: int, n_q: int, Tf: int, want_stage_errors: bool = False):
+    def _rate(self, ratios, min_n_q: int, n_q: int, Tf: int, want_stage_errors: bool = False, per_frame: bool = False):
         """The engine's rate (fc_engine_set_rate) for the offline call made inside: a stage count per row chosen on the device; cleared on
         the way out, whatever happened, as _row_nq does.  ratios: None (nothing is set, None is yielded) or a checked list (rate_targets).
         Yields dict(n_q_rows [B] i32, row_errors [B, n_q + 1] f64, stage_errors [n_q + 1, B, Tf] f32 | None): device tensors the call
-        fills; nothing is read back."""
+        fills; nothing is read back.  per_frame (fc_engine_set_rate_frames; min_n_q may then be 0): also n_q_frames [B, Tf] i32, n_codes_rows
+        [B] i32 and achieved_errors [B] f64; n_q_rows is then every row's largest frame count."""
         if ratios is None:
             yield None
             return
@@ -425,21 +474,49 @@ class CodecEngine:
         out = dict(n_q_rows=torch.empty((B,), dtype=torch.int32, device=self.device),
                    row_errors=torch.empty((B, n_q + 1), dtype=torch.float64, device=self.device),
                    stage_errors=torch.empty((n_q + 1, B, Tf), dtype=torch.float32, device=self.device) if want_stage_errors else None)
-        self._check(self.lib.fc_engine_set_rate(self._h, (C.c_double * B)(*ratios), B, int(min_n_q), _ptr(out["n_q_rows"]), _ptr(out["row_errors"]),
-                                                _ptr(out["stage_errors"]), self._stream()))
+        self._check(self.lib.fc_engine_set_rate(self._h, (C.c_double * B)(*ratios), B, max(int(min_n_q), 1), _ptr(out["n_q_rows"]),
+                                                _ptr(out["row_errors"]), _ptr(out["stage_errors"]), self._stream()))
         try:
+            if per_frame:
+                out.update(n_q_frames=torch.empty((B, Tf), dtype=torch.int32, device=self.device),
+                           n_codes_rows=torch.empty((B,), dtype=torch.int32, device=self.device),
+                           achieved_errors=torch.empty((B,), dtype=torch.float64, device=self.device))
+                self._check(self.lib.fc_engine_set_rate_frames(self._h, int(min_n_q), _ptr(out["n_q_frames"]), _ptr(out["n_codes_rows"]),
+                                                               _ptr(out["achieved_errors"]), self._stream()))
             yield out
         finally:
             self.lib.fc_engine_set_rate(self._h, None, 0, 1, None, None, None, None)
 
-    def _rate_in(self, target_snr_db, min_n_q, B: int, n_q: int, n_q_rows):
+    def _rate_in(self, target_snr_db, min_n_q, B: int, n_q: int, n_q_rows, per_frame: bool = False):
         """(ratios or None, min_n_q) of a call's target_snr_db / min_n_q, checked before anything reaches the device; a list of floats
-        that _rate_in made itself (a micro-batch's slice) passes through."""
+        that _rate_in made itself (a micro-batch's slice) passes through.  per_frame: the floor lies in [0, cap]; without a target it is
+        refused."""
         if target_snr_db is None:
+            if per_frame:
+                raise EngineError("per_frame chooses a stage count per frame by target_snr_db: give a target")
             return None, 1
         if isinstance(target_snr_db, _Ratios):
             return target_snr_db, min_n_q
-        return _Ratios(rate_targets(self.arch, target_snr_db, B)), rate_min_nq(self.arch, min_n_q, n_q, n_q_rows)
+        floor = (rate_min_nq_frames if per_frame else rate_min_nq)(self.arch, min_n_q, n_q, n_q_rows)
+        return _Ratios(rate_targets(self.arch, target_snr_db, B)), floor
+
+    @contextlib.contextmanager
+    def _frame_nq(self, table, B: int, Tf: int):
+        """A stage count per frame (fc_engine_set_frame_nq) for the decode_codes call made inside: a device int32 [B, Tf] the engine
+        borrows; cleared on the way out, whatever happened.  table: None (nothing is set) or anything [B, Tf]; a device tensor stays on
+        the device (the kernel clamps to [0, n_q])."""
+        if table is None:
+            yield
+            return
+        t = torch.as_tensor(table)
+        if tuple(t.shape) != (B, Tf):
+            raise EngineError(f"n_q_frames must be [B, Tf] = [{B}, {Tf}], got {tuple(t.shape)}")
+        t = self._dev(t, torch.int32)
+        self._check(self.lib.fc_engine_set_frame_nq(self._h, _ptr(t), B, Tf, self._stream()))
+        try:
+            yield
+        finally:
+            self.lib.fc_engine_set_frame_nq(self._h, None, 0, 0, None)
 
     @_on_device
     def set_rvq_beam(self, width) -> None:
@@ -477,20 +554,25 @@ class CodecEngine:
         return out
 
     @staticmethod
-    def _rate_dims(ratios):
+    def _rate_dims(ratios, per_frame: bool = False):
         """the batch dimensions of the outputs a rate adds, for _cat"""
-        return {} if ratios is None else dict(n_q_rows=0, row_errors=0, stage_errors=1)
+        if ratios is None:
+            return {}
+        return dict(n_q_rows=0, row_errors=0, stage_errors=1, **(dict(n_q_frames=0, n_codes_rows=0, achieved_errors=0) if per_frame else {}))
 
     @_on_device
     def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False, lengths=None, n_q_rows=None,
-               target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False):
+               target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False, per_frame: bool = False):
         """wav [B,T] (or [B,C,T]) -> dict(codes [n_q,B,Tf] i64, quantized [B,Tf,D], sub_quants [n_q,B,D,Tf], scale [B,1]|None).
         target_snr_db (one value or B; optional): every row takes the smallest stage count in [min_n_q, its cap] whose quantiser-domain SNR
         reaches its target (rate_pick; the cap: n_q_rows[b], else n_q), chosen on the device inside the call.  The dict then also holds
-        n_q_rows [B] i32, row_errors [B, n_q + 1] f64 and stage_errors [n_q + 1, B, Tf] f32 (None unless want_stage_errors), all on the device."""
+        n_q_rows [B] i32, row_errors [B, n_q + 1] f64 and stage_errors [n_q + 1, B, Tf] f32 (None unless want_stage_errors), all on the device.
+        per_frame (with target_snr_db): a count per FRAME (rate_pick_frames; min_n_q in [0, cap]): frame (b, t) is what the call
+        with n_q = n_q_frames[b, t] gives it; the dict also holds n_q_frames [B, Tf] i32, n_codes_rows [B] i32 and achieved_errors [B] f64,
+        and n_q_rows is every row's largest frame count."""
         if n_q_rows is not None:                       # refused as a whole before anything reaches the device
             n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
-        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows)
+        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows, per_frame)
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
         if lengths is not None:
@@ -499,9 +581,9 @@ class CodecEngine:
             parts = [self.encode(wav[i:i + self.micro_batch], n_q, want_sub_quants, want_enc_out,
                                  None if lengths is None else lengths[i:i + self.micro_batch],
                                  None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
-                                 None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors)
+                                 None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors, per_frame)
                      for i in range(0, B, self.micro_batch)]
-            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, enc_out=0, **self._rate_dims(ratios)))
+            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, enc_out=0, **self._rate_dims(ratios, per_frame)))
         Tf, D = self.frames(T), self.arch.dimension
         dev = self.device
         codes = torch.empty((n_q, B, Tf), dtype=torch.int64, device=dev)
@@ -510,7 +592,7 @@ class CodecEngine:
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         enc = torch.empty((B, Tf, D), dtype=torch.float32, device=dev) if want_enc_out else None
         ws = self._workspace(B, T, lengths is not None)
-        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors) as rate:
+        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors, per_frame) as rate:
             if lengths is not None:
                 self._check(self.lib.fc_encode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq),
                                                       _ptr(scale), _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
@@ -522,12 +604,12 @@ class CodecEngine:
 
     @_on_device
     def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True, lengths=None, n_q_rows=None,
-                      target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False):
-        """encode + decode in one enqueue; target_snr_db, min_n_q, want_stage_errors: as for encode (the reconstruction is made from the
-        chosen counts)."""
+                      target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False, per_frame: bool = False):
+        """encode + decode in one enqueue; target_snr_db, min_n_q, want_stage_errors, per_frame: as for encode (the reconstruction is made
+        from the chosen counts)."""
         if n_q_rows is not None:                       # refused as a whole before anything reaches the device
             n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
-        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows)
+        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows, per_frame)
         wav = self._wav_in(wav)
         B, T = wav.shape[0], wav.shape[-1]
         if lengths is not None:
@@ -536,9 +618,9 @@ class CodecEngine:
             parts = [self.encode_decode(wav[i:i + self.micro_batch], n_q, use_scale, want_sub_quants,
                                         None if lengths is None else lengths[i:i + self.micro_batch],
                                         None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
-                                        None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors)
+                                        None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors, per_frame)
                      for i in range(0, B, self.micro_batch)]
-            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0, **self._rate_dims(ratios)))
+            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0, **self._rate_dims(ratios, per_frame)))
         Tf, D = self.frames(T), self.arch.dimension
         dev = self.device
         codes = torch.empty((n_q, B, Tf), dtype=torch.int64, device=dev)
@@ -547,7 +629,7 @@ class CodecEngine:
         scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
         recon = torch.empty((B, self.channels, min(T, self.decoded_samples(Tf))), dtype=torch.float32, device=dev)   # like recon[:, :, :T] of the reference
         ws = self._workspace(B, T, lengths is not None)
-        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors) as rate:
+        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors, per_frame) as rate:
             if lengths is not None:
                 self._check(self.lib.fc_encode_decode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
                                                              _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
@@ -558,8 +640,11 @@ class CodecEngine:
                     scale=None if scale is None else scale.view(B, 1), recon=recon, **(rate or {}))
 
     @_on_device
-    def decode_codes(self, tokens: torch.Tensor, lengths=None, n_q_rows=None):
-        """tokens [B,Tf,n_q] i64 -> (wav [B,1,Tf*hop], emb [B,Tf,D]).  lengths: frames per row."""
+    def decode_codes(self, tokens: torch.Tensor, lengths=None, n_q_rows=None, n_q_frames=None):
+        """tokens [B,Tf,n_q] i64 -> (wav [B,1,Tf*hop], emb [B,Tf,D]).  lengths: frames per row.  n_q_frames [B,Tf] (optional; a device
+        tensor stays there): a stage count per frame, clamped to [0, n_q] on the device; the codes behind it are not read."""
+        if n_q_rows is not None and n_q_frames is not None:
+            raise EngineError("decode_codes: n_q_rows and n_q_frames are a count per row and a count per frame: give one of them")
         if n_q_rows is not None:                       # refused as a whole before anything reaches the device
             n_q_rows = row_nq_list(self.arch, n_q_rows, tokens.shape[0], tokens.shape[-1])
         tokens = self._dev(tokens, torch.int64)
@@ -568,14 +653,15 @@ class CodecEngine:
             lengths = self._lengths_in(lengths, B)
         if B > self.micro_batch:
             parts = [self.decode_codes(tokens[i:i + self.micro_batch], None if lengths is None else lengths[i:i + self.micro_batch],
-                                       None if n_q_rows is None else n_q_rows[i:i + self.micro_batch])
+                                       None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
+                                       None if n_q_frames is None else n_q_frames[i:i + self.micro_batch])
                      for i in range(0, B, self.micro_batch)]
             return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
         L = self.decoded_samples(Tf)
         wav = torch.empty((B, self.channels, L), dtype=torch.float32, device=self.device)
         emb = torch.empty((B, Tf, self.arch.dimension), dtype=torch.float32, device=self.device)
         ws = self._workspace(B, Tf * self.hop_length, lengths is not None)
-        with self._row_nq(n_q_rows):
+        with self._row_nq(n_q_rows), self._frame_nq(n_q_frames, B, Tf):
             if lengths is not None:
                 self._check(self.lib.fc_decode_codes_ragged(self._h, _ptr(tokens), _ptr(lengths), B, Tf, n_q, L, _ptr(wav), _ptr(emb), _ptr(ws),
                                                             ws.numel(), self._stream()))
@@ -662,16 +748,29 @@ class CodecEngine:
         return self._dev(rows, torch.int32)
 
     @_on_device
-    def pack_codes(self, codes: torch.Tensor, frames_rows=None, n_q_rows=None) -> torch.Tensor:
+    def pack_codes(self, codes: torch.Tensor, frames_rows=None, n_q_rows=None, n_q_frames=None) -> torch.Tensor:
         """codes [n_q,B,Tf] i64 -> packets uint8 [B, pitch] on the device (fc_codes_pack), one packet per row with zeros behind it.
         frames_rows, n_q_rows [B] (optional; lists, or tensors on any device -- ``n_q_rows`` of a ``target_snr_db`` call goes in as it
-        is): the row's frames and stage count, clamped on the device to [0, Tf] and [1, n_q]; nothing behind them is read."""
+        is): the row's frames and stage count, clamped on the device to [0, Tf] and [1, n_q]; nothing behind them is read.
+        n_q_frames [B,Tf] (optional; ``n_q_frames`` of a ``per_frame`` call goes in as it is): packets of mode 1, a count per frame
+        (fc_codes_pack_frames), clamped on the device to [0, n_q]; n_q_rows is then not needed (the header's kmax is made on the device)."""
         codes = self._dev(codes, torch.int64)
         if codes.dim() != 3:
             raise EngineError(f"pack_codes: codes must be [n_q,B,Tf], got {tuple(codes.shape)}")
         n_q, B, Tf = codes.shape
         fr, nq = self._rows_i32(frames_rows, B, "frames_rows"), self._rows_i32(n_q_rows, B, "n_q_rows")
         bits = self.code_bits
+        if n_q_frames is not None:
+            kf = torch.as_tensor(n_q_frames)
+            if tuple(kf.shape) != (B, Tf):
+                raise EngineError(f"pack_codes: n_q_frames must be [B, Tf] = [{B}, {Tf}], got {tuple(kf.shape)}")
+            kf = self._dev(kf, torch.int32)
+            pitch = int(self.lib.fc_frame_packet_pitch(Tf, n_q, bits))
+            packets = torch.empty((B, pitch), dtype=torch.uint8, device=self.device)
+            ws = torch.empty((int(self.lib.fc_frame_pack_workspace_bytes(B, Tf)),), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.fc_codes_pack_frames(_ptr(codes), B, Tf, n_q, bits, _ptr(fr), _ptr(kf), _ptr(packets), pitch, _ptr(ws), ws.numel(),
+                                                      self._stream()))
+            return packets
         pitch = int(self.lib.fc_code_packet_pitch(Tf, n_q, bits))
         packets = torch.empty((B, pitch), dtype=torch.uint8, device=self.device)
         self._check(self.lib.fc_codes_pack(_ptr(codes), B, Tf, n_q, bits, _ptr(fr), _ptr(nq), _ptr(packets), pitch, self._stream()))
@@ -690,58 +789,95 @@ class CodecEngine:
         self._check(self.lib.fc_codes_unpack(_ptr(packets), pitch, B, int(Tf), n_q, self.code_bits, _ptr(tokens), self._stream()))
         return tokens
 
-    def _parse_packets(self, rows, exact):
-        """(frames, counts) of host packets, every header checked (bits, mode, k <= num_quantizers, length); a bad one raises EngineError
-        naming the row and the field"""
-        from .io import PacketError, parse_packet_header
-        frames, counts = [], []
+    @_on_device
+    def unpack_frame_codes(self, packets: torch.Tensor, Tf: int, n_q: Optional[int] = None):
+        """packets uint8 [B, pitch], every row of mode 0 or mode 1 -> (tokens [B,Tf,n_q] i64, n_q_frames [B,Tf] i32) on the device
+        (fc_codes_unpack_frames): zeros behind every frame's count and every row's frames; a mode-0 row counts its k in every frame.
+        Both go to decode_codes(tokens, n_q_frames=...) as they are: packets to waveform without a read-back."""
+        packets = self._dev(packets, torch.uint8)
+        if packets.dim() != 2:
+            raise EngineError(f"unpack_frame_codes: packets must be [B, pitch], got {tuple(packets.shape)}")
+        n_q = self.arch.num_quantizers if n_q is None else int(n_q)
+        B, pitch = packets.shape
+        Tf = int(Tf)
+        tokens = torch.empty((B, Tf, n_q), dtype=torch.int64, device=self.device)
+        kf = torch.empty((B, Tf), dtype=torch.int32, device=self.device)
+        ws = torch.empty((int(self.lib.fc_frame_pack_workspace_bytes(B, Tf)),), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.fc_codes_unpack_frames(_ptr(packets), pitch, B, Tf, n_q, self.code_bits, _ptr(tokens), _ptr(kf), _ptr(ws), ws.numel(),
+                                                    self._stream()))
+        return tokens, kf
+
+    def _parse_packets_any(self, rows, exact):
+        """(modes, frames, counts, lengths) of host packets of either mode, every header checked (bits, mode, k <= num_quantizers, a
+        mode-1 packet's counts, length); a bad one raises EngineError naming the row and the field.  counts: k, or a mode-1 packet's
+        largest count.  exact=None: the rows are headers alone (lengths are then None)."""
+        from .io import PacketError, parse_any_packet
+        modes, frames, counts, lengths = [], [], [], []
         for b, p in enumerate(rows):
             try:
-                f, k, _, _ = parse_packet_header(p, self.arch.num_quantizers, self.code_bits, exact=exact)
+                mode, f, k, _, _, need = parse_any_packet(p, self.arch.num_quantizers, self.code_bits, exact=exact)
             except PacketError as err:
                 raise EngineError(f"row {b}: packet field {err}") from None
+            modes.append(mode)
             frames.append(f)
             counts.append(k)
-        return frames, counts
+            lengths.append(need)
+        return modes, frames, counts, lengths
+
+    def _parse_packets(self, rows, exact):
+        """(frames, counts) of host packets, checked as _parse_packets_any checks them"""
+        return self._parse_packets_any(rows, exact)[1:3]
 
     def packets_to_host(self, packets: torch.Tensor):
-        """packets uint8 [B, pitch] -> list of B bytes: ONE copy to the host, every row cut at its own packet length"""
-        from .io import packet_bytes
+        """packets uint8 [B, pitch] -> list of B bytes: ONE copy to the host, every row cut at its own packet length (a mode-1 row's
+        length comes from its counts section, which the host then holds)"""
         host = packets.cpu().numpy()
         rows = [host[b].tobytes() for b in range(host.shape[0])]
-        frames, counts = self._parse_packets(rows, exact=False)
-        return [r[:packet_bytes(f, k, self.code_bits)] for r, f, k in zip(rows, frames, counts)]
+        lengths = self._parse_packets_any(rows, exact=False)[3]
+        return [r[:n] for r, n in zip(rows, lengths)]
 
     def packets_from_host(self, packets, n_q: Optional[int] = None):
         """list of B bytes -> (packets uint8 [B, pitch] on the device, Tf, counts): every header is validated first (bits, mode,
         k <= n_q, and a length of exactly fc_code_packet_bytes); Tf is the largest frame count, the pitch that of (Tf, n_q) with n_q the
-        largest count unless given."""
-        from .io import packet_pitch
+        largest count unless given.  Packets of mode 1 (a count per frame) pass too: counts then holds the packet's largest count, the
+        pitch is the mode-1 pitch, and ``packets_modes(packets)`` tells which unpack call the buffer needs."""
+        from .io import frame_packet_pitch, packet_pitch
         packets = [bytes(p) for p in packets]
         if not packets:
             raise EngineError("packets_from_host: no packets")
-        frames, counts = self._parse_packets(packets, exact=True)
+        modes, frames, counts, _ = self._parse_packets_any(packets, exact=True)
+        pitch_of = frame_packet_pitch if any(modes) else packet_pitch      # a buffer that holds a mode-1 row has the mode-1 pitch
         if n_q is not None:
             for b, k in enumerate(counts):
                 if k > n_q:
                     raise EngineError(f"row {b}: packet field k: {k} stages, more than the {n_q} of this call")
         Tf = max(max(frames), 1)
-        pitch = packet_pitch(Tf, max(counts) if n_q is None else int(n_q), self.code_bits)
+        pitch = pitch_of(Tf, max(counts) if n_q is None else int(n_q), self.code_bits)
         host = np.zeros((len(packets), pitch), dtype=np.uint8)
         for b, p in enumerate(packets):
             host[b, :len(p)] = np.frombuffer(p, dtype=np.uint8)
         return torch.from_numpy(host).to(self.device), Tf, counts
 
+    @staticmethod
+    def packets_modes(packets) -> list:
+        """the mode (0: one count per packet, 1: a count per frame) of every host packet"""
+        from .io import packet_mode
+        return [packet_mode(bytes(p)) for p in packets]
+
     # -- per-op entry points (tests) -----------------------------------------------------------
     @_on_device
     def rvq_encode(self, x: torch.Tensor, n_q: int, n_q_rows=None, beam: int = 1, return_paths: bool = False, target_snr_db=None,
-                   min_n_q: int = 1):
+                   min_n_q: int = 1, per_frame: bool = False):
         """x [N,D] -> (codes [n_q,N], quantized [N,D]).  target_snr_db (a list of B, or with n_q_rows one value or B; fc_rvq_encode_rate):
         the N rows are B utterances of N / B frames each, every one takes the stage count the rule picks (rate_pick; n_q_rows are the caps)
         -> (codes, quantized, dict(n_q_rows [B] i32, row_errors [B, n_q + 1] f64, stage_errors [n_q + 1, B, N / B] f32)).  n_q_rows (B entries): the N rows are B utterances of N / B frames each, utterance b
         with n_q_rows[b] stages.  beam (2, 4, 8): the search over the stages (fc_rvq_encode_beam) instead of the greedy quantiser;
-        return_paths: also (paths [beam,n_q,N] i64, errors [beam,N]), every slot's final path and its fixed-order residual energy."""
+        return_paths: also (paths [beam,n_q,N] i64, errors [beam,N]), every slot's final path and its fixed-order residual energy.
+        per_frame (with target_snr_db): a count per frame (rate_pick_frames; min_n_q in [0, cap]); the dict also holds n_q_frames
+        [B, N / B] i32, n_codes_rows [B] i32 and achieved_errors [B] f64."""
         beam = rvq_beam_width(self.arch, beam)
+        if per_frame and target_snr_db is None:
+            raise EngineError("rvq_encode: per_frame chooses a stage count per frame by target_snr_db: give a target")
         if return_paths and beam == 1:
             raise EngineError("rvq_encode: return_paths needs rvq_beam above 1 (the paths are those of a search)")
         if n_q_rows is not None:
@@ -753,7 +889,7 @@ class CodecEngine:
             if return_paths:
                 raise EngineError("rvq_encode: return_paths and target_snr_db are two hooks (fc_rvq_encode_beam, fc_rvq_encode_rate)")
             rows_b = len(n_q_rows) if n_q_rows is not None else (1 if isinstance(target_snr_db, numbers.Real) else len(target_snr_db))
-            ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, rows_b, n_q, n_q_rows)
+            ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, rows_b, n_q, n_q_rows, per_frame)
             if x.shape[0] % rows_b != 0:
                 raise EngineError(f"rvq_encode: {x.shape[0]} rows are not {rows_b} utterances of equal length")
         x = self._dev(x, torch.float32)
@@ -763,7 +899,7 @@ class CodecEngine:
         codes = torch.empty((n_q, N), dtype=torch.int64, device=self.device)
         quant = torch.empty((N, D), dtype=torch.float32, device=self.device)
         if ratios is not None:
-            with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, N // len(ratios), True) as rate:
+            with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, N // len(ratios), True, per_frame) as rate:
                 self._check(self.lib.fc_rvq_encode_rate(self._h, _ptr(x), N, n_q, beam, _ptr(codes), _ptr(quant), self._stream()))
             return codes, quant, rate
         if beam > 1:

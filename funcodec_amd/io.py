@@ -289,6 +289,140 @@ def unpack_packet(packet) -> Tuple[np.ndarray, int, int]:
     return vals.reshape(frames, k), k, bits
 
 
+# ---- mode 1: a stage count per frame (csrc/code_pack_kernels.h, "MODE 1") ----
+def count_bits(kmax: int) -> int:
+    """cbits: the bit length of kmax (1..8 for kmax in 1..255)"""
+    return int(kmax).bit_length()
+
+
+def frame_packet_bytes(frames: int, kmax: int, n_codes: int, bits: int) -> int:
+    """8 + 4 ceil(frames cbits / 32) + ceil(n_codes bits / 8) (fc_frame_packet_bytes)"""
+    return PACKET_HEADER_BYTES + 4 * ((int(frames) * count_bits(kmax) + 31) // 32) + (int(n_codes) * int(bits) + 7) // 8
+
+
+def frame_packet_pitch(frames: int, n_q: int, bits: int) -> int:
+    """the largest mode-1 packet (kmax = n_q, every count n_q) rounded up to 16 (fc_frame_packet_pitch)"""
+    return (frame_packet_bytes(frames, n_q, int(frames) * int(n_q), bits) + 15) // 16 * 16
+
+
+def packet_mode(buf) -> int:
+    """0 (one count per packet) or 1 (a count per frame) of the packet at the start of ``buf``; anything else raises PacketError("mode")"""
+    buf = buf if isinstance(buf, (bytes, bytearray)) else bytes(buf)
+    if len(buf) < PACKET_HEADER_BYTES:
+        raise PacketError("length", f"a packet begins with an {PACKET_HEADER_BYTES}-byte header, got {len(buf)} bytes")
+    if buf[6] not in (0, 1):
+        raise PacketError("mode", f"modes 0 (one stage count per packet) and 1 (one per frame) are defined, got {buf[6]}")
+    return buf[6]
+
+
+def _bits_lsb(vals: np.ndarray, width: int) -> np.ndarray:
+    """the bit stream of ``vals`` at ``width`` bits each, LSB first, as an array of 0 / 1"""
+    vals = np.asarray(vals, dtype=np.uint32).reshape(-1)
+    return ((vals[:, None] >> np.arange(width, dtype=np.uint32)[None, :]) & 1).astype(np.uint8).reshape(-1)
+
+
+def _vals_lsb(stream: np.ndarray, n: int, width: int) -> np.ndarray:
+    """the first ``n`` values of ``width`` bits of a stream of 0 / 1 (the inverse of _bits_lsb), int64"""
+    return (stream[:n * width].reshape(n, width).astype(np.int64) << np.arange(width, dtype=np.int64)[None, :]).sum(1)
+
+
+def pack_frame_codes(codes, counts, bits: int = 10, frames: Optional[int] = None, layout: str = "qt") -> bytes:
+    """One mode-1 packet from the codes of one utterance: ``codes`` [n_q, T] (``"qt"``) or [T, n_q] (``"tq"``) and ``counts`` [T], the
+    stage count of every frame (0 .. min(n_q, 255)); the first ``frames`` frames (default: all).  Frame t contributes its first
+    counts[t] codes, each modulo 2^bits; nothing behind a count is looked at."""
+    a = np.asarray(codes)
+    if a.ndim != 2:
+        raise ValueError(f"pack_frame_codes: codes of one utterance are 2-D, got shape {a.shape}")
+    if layout not in ("qt", "tq"):
+        raise ValueError(f"pack_frame_codes: layout is 'qt' ([n_q, T]) or 'tq' ([T, n_q]), got {layout!r}")
+    a = a.T if layout == "qt" else a                         # [T, n_q]
+    frames = a.shape[0] if frames is None else int(frames)
+    if not 1 <= bits <= 16:
+        raise PacketError("bits", f"{bits} bits per code lies outside 1..16")
+    if not 0 <= frames <= a.shape[0]:
+        raise PacketError("frames", f"the codes hold {a.shape[0]} frames, got {frames}")
+    k = np.asarray(counts).reshape(-1)
+    if k.shape[0] < frames:
+        raise PacketError("count", f"{frames} frames need {frames} counts, got {k.shape[0]}")
+    k = k[:frames].astype(np.int64)
+    top = min(a.shape[1], 255)
+    bad = np.nonzero((k < 0) | (k > top))[0]
+    if bad.size:
+        raise PacketError("count", f"frame {int(bad[0])}: a stage count lies in 0..{top}, got {int(k[bad[0]])}")
+    kmax = max(int(k.max()) if frames else 0, 1)
+    cbits = count_bits(kmax)
+    cstream = np.zeros(32 * ((frames * cbits + 31) // 32), dtype=np.uint8)
+    cstream[:frames * cbits] = _bits_lsb(k, cbits)
+    keep = np.arange(a.shape[1])[None, :] < k[:, None]       # [frames, n_q], frame-major
+    vals = a[:frames][keep].astype(np.int64) & ((1 << bits) - 1)
+    return (struct.pack("<IBBBB", frames, kmax, bits, 1, 0) + np.packbits(cstream, bitorder="little").tobytes() +
+            np.packbits(_bits_lsb(vals, bits), bitorder="little").tobytes())
+
+
+def parse_frame_packet(buf, n_q: Optional[int] = None, bits: Optional[int] = None, exact: Optional[bool] = True):
+    """(frames, kmax, bits, counts [frames] int64, packet length) of the mode-1 packet at the start of ``buf``, every field checked:
+    mode 1, bits in 1..16 (and the expected ``bits``), kmax in 1..255 (and <= ``n_q``), every count <= kmax and the largest one equal to
+    kmax (1 if all are 0), and a length of exactly (``exact``) or at least (``exact=False``) the packet's (``exact=None``: ``buf`` is the
+    header alone; counts and length are then None).  Raises PacketError naming the field: mode, bits, k, count (with the frame) or length."""
+    buf = buf if isinstance(buf, (bytes, bytearray)) else bytes(buf)
+    if len(buf) < PACKET_HEADER_BYTES:
+        raise PacketError("length", f"a packet begins with an {PACKET_HEADER_BYTES}-byte header, got {len(buf)} bytes")
+    frames, kmax, b, mode, _ = struct.unpack_from("<IBBBB", buf, 0)
+    if mode != 1:
+        raise PacketError("mode", f"a packet with a stage count per frame has mode 1, got {mode}")
+    if not 1 <= b <= 16 or (bits is not None and b != bits):
+        raise PacketError("bits", f"{b} bits per code" + (f", expected {bits}" if bits is not None else " lies outside 1..16"))
+    if kmax < 1 or (n_q is not None and kmax > n_q):
+        raise PacketError("k", f"the largest stage count lies in 1..{255 if n_q is None else n_q}, got {kmax}")
+    if exact is None:                                        # ``buf`` is the header alone: no counts, no length
+        return frames, kmax, b, None, None
+    cbits = count_bits(kmax)
+    cbytes = 4 * ((frames * cbits + 31) // 32)
+    if len(buf) < PACKET_HEADER_BYTES + cbytes:
+        raise PacketError("length", f"{frames} frames at {cbits} count bits need a counts section of {cbytes} bytes, got {len(buf) - PACKET_HEADER_BYTES}")
+    cstream = np.unpackbits(np.frombuffer(buf, dtype=np.uint8, offset=PACKET_HEADER_BYTES, count=cbytes), bitorder="little")
+    counts = _vals_lsb(cstream, frames, cbits)
+    bad = np.nonzero(counts > kmax)[0]
+    if bad.size:
+        raise PacketError("count", f"frame {int(bad[0])}: {int(counts[bad[0]])} stages, more than the packet's largest count {kmax}")
+    if max(int(counts.max()) if frames else 0, 1) != kmax:
+        raise PacketError("k", f"the header's largest count is {kmax}, the counts' is {max(int(counts.max()) if frames else 0, 1)}")
+    need = frame_packet_bytes(frames, kmax, int(counts.sum()), b)
+    if exact is not None and ((len(buf) != need) if exact else (len(buf) < need)):
+        raise PacketError("length", f"{frames} frames with {int(counts.sum())} codes at {b} bits are {need} bytes, got {len(buf)}")
+    return frames, kmax, b, counts, need
+
+
+def unpack_frame_packet(packet) -> Tuple[np.ndarray, np.ndarray, int]:
+    """(tokens [T, kmax] int64 with zeros behind every frame's count, counts [T] int64, bits) of one mode-1 packet; the inverse of
+    pack_frame_codes"""
+    packet = bytes(packet)
+    frames, kmax, bits, counts, _ = parse_frame_packet(packet)
+    off = PACKET_HEADER_BYTES + 4 * ((frames * count_bits(kmax) + 31) // 32)
+    n = int(counts.sum())
+    vals = _vals_lsb(np.unpackbits(np.frombuffer(packet, dtype=np.uint8, offset=off), bitorder="little"), n, bits)
+    tokens = np.zeros((frames, kmax), dtype=np.int64)
+    tokens[np.arange(kmax)[None, :] < counts[:, None]] = vals
+    return tokens, counts, bits
+
+
+def parse_any_packet(buf, n_q: Optional[int] = None, bits: Optional[int] = None, exact: Optional[bool] = True):
+    """(mode, frames, k or kmax, bits, counts [frames] int64, packet length) of a packet of either mode, checked as its own parser checks it"""
+    if packet_mode(buf) == 1:
+        frames, kmax, b, counts, need = parse_frame_packet(buf, n_q, bits, exact)
+        return 1, frames, kmax, b, counts, need
+    frames, k, b, need = parse_packet_header(buf, n_q, bits, exact)
+    return 0, frames, k, b, None if exact is None else np.full((frames,), k, dtype=np.int64), need
+
+
+def unpack_any_packet(packet) -> Tuple[np.ndarray, np.ndarray, int]:
+    """(tokens [T, k or kmax], counts [T], bits) of a packet of either mode"""
+    if packet_mode(packet) == 1:
+        return unpack_frame_packet(packet)
+    tok, k, bits = unpack_packet(packet)
+    return tok, np.full((tok.shape[0],), k, dtype=np.int64), bits
+
+
 FCB_MAGIC = b"FCB1"
 _FCB_HEADER = struct.Struct("<4sBBHII")      # magic, bits, n_q, 0, sample rate, hop
 _FCB_RECORD = struct.Struct("<II")           # valid samples, packet length (behind: u16 key length, key)
@@ -309,7 +443,7 @@ class FcbWriter:
 
     def __call__(self, key: str, packet: bytes, samples: int) -> None:
         packet = bytes(packet)
-        parse_packet_header(packet, self.n_q, self.bits)
+        parse_any_packet(packet, self.n_q, self.bits)       # either mode
         kb = key.encode("utf-8")
         if not 0 < len(kb) < 65536 or any(c.isspace() for c in key):
             raise ValueError(f"FcbWriter: a key is 1..65535 UTF-8 bytes without white space, got {key!r}")
@@ -348,7 +482,7 @@ def read_fcb(path: str):
             key = f.read(struct.unpack("<H", raw)[0]).decode("utf-8")
             samples, n = _FCB_RECORD.unpack(f.read(_FCB_RECORD.size))
             packet = f.read(n)
-            parse_packet_header(packet, head["n_q"], head["bits"])
+            parse_any_packet(packet, head["n_q"], head["bits"])
             out.append((key, samples, packet))
     return head, out
 
@@ -361,17 +495,24 @@ def load_fcb_record(spec: str):
         f.seek(int(off))
         samples, n = _FCB_RECORD.unpack(f.read(_FCB_RECORD.size))
         packet = f.read(n)
-    parse_packet_header(packet, head["n_q"], head["bits"])
+    parse_any_packet(packet, head["n_q"], head["bits"])
     return head, samples, packet
 
 
-def load_fcb_item(spec: str) -> Tuple[np.ndarray, int]:
-    """``<fcb path>:<offset>`` -> (tokens [T, n_q] int64 with zeros behind the packet's k, k); n_q is the file's"""
+def load_fcb_frames(spec: str) -> Tuple[np.ndarray, int, np.ndarray, int]:
+    """``<fcb path>:<offset>`` -> (tokens [T, n_q] int64 with zeros behind every frame's count, the largest count, counts [T] int64,
+    the packet's mode); n_q is the file's.  A mode-0 packet counts its k in every frame."""
     head, _, packet = load_fcb_record(spec)
-    tok, k, _ = unpack_packet(packet)
+    tok, counts, _ = unpack_any_packet(packet)
     out = np.zeros((tok.shape[0], head["n_q"]), dtype=np.int64)
-    out[:, :k] = tok
-    return out, k
+    out[:, :tok.shape[1]] = tok
+    return out, tok.shape[1], counts, packet_mode(packet)
+
+
+def load_fcb_item(spec: str) -> Tuple[np.ndarray, int]:
+    """``<fcb path>:<offset>`` -> (tokens [T, n_q] int64 with zeros behind the packet's k, k); n_q is the file's.  For a mode-1 packet k is
+    its largest count (load_fcb_frames also gives the counts)."""
+    return load_fcb_frames(spec)[:2]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -429,9 +570,14 @@ def iter_batches(data_path_and_name_and_type: Sequence[Tuple[str, str, str]], ba
         batch: Dict[str, torch.Tensor] = {}
         for name, dtype, table, _ in tables:
             if dtype == "codec_fcb":       # the packets carry each row's stage count: it travels next to the lengths
-                pairs = [load_fcb_item(table[k]) for k in bkeys]
+                pairs = [load_fcb_frames(table[k]) for k in bkeys]
                 items = [p[0] for p in pairs]
                 batch[name + "_n_q"] = torch.tensor([p[1] for p in pairs], dtype=torch.long)
+                if any(p[3] == 1 for p in pairs):      # a count per frame somewhere in the batch: [B, T] int32, zeros behind a row's frames
+                    nqf = np.zeros((len(pairs), max(p[2].shape[0] for p in pairs)), dtype=np.int32)
+                    for b, p in enumerate(pairs):
+                        nqf[b, :p[2].shape[0]] = p[2]
+                    batch[name + "_n_q_frames"] = torch.from_numpy(nqf)
             else:
                 items = [_load_item(table[k], dtype) for k in bkeys]
             batch[name] = pad_list_with_mod(items, 0.0 if items[0].dtype.kind == "f" else 0, "wrap")

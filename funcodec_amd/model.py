@@ -14,7 +14,7 @@ from typing import Dict, Optional
 import torch
 
 from .config import ArchSpec
-from .engine import CodecEngine, EngineError, packed_refusal, ragged_refusal, rate_min_nq, rate_targets, row_nq_list, rvq_beam_width
+from .engine import CodecEngine, EngineError, packed_refusal, ragged_refusal, rate_min_nq, rate_min_nq_frames, rate_targets, row_nq_list, rvq_beam_width
 
 
 class EncodecMI355X:
@@ -143,7 +143,7 @@ class EncodecMI355X:
     @torch.no_grad()
     def inference(self, speech: torch.Tensor, need_recon: bool = True, bit_width: int = None,
                   use_scale: bool = True, _quantise_always: bool = False, speech_lengths=None, rvq_beam: int = None,
-                  target_snr_db=None, min_n_q: int = 1, packed: bool = False) -> Dict[str, torch.Tensor]:
+                  target_snr_db=None, min_n_q: int = 1, packed: bool = False, per_frame: bool = False) -> Dict[str, torch.Tensor]:
         """bit_width: one value for the batch, as in the reference, or a sequence / 1-D tensor of B: row b is then what this call returns
         for it with ``bit_width[b]``; ``code_indices`` is [max n_q, B, Tf] with zeros at the stages a row does not take (``sub_quants`` too).
         speech_lengths [B] (optional): samples per row.  With it, row b of every output is what this call returns for
@@ -160,7 +160,16 @@ class EncodecMI355X:
         packed=True: the dict gains ``packets``, uint8 [B, pitch] on the device: one self-describing packet per row (csrc/code_pack_kernels.h
         states it) holding the row's own frames (``speech_lengths``) and stage count (a per-row ``bit_width``; with ``target_snr_db`` the
         counts go from the device tensor into the packer, nothing is read back).  ``engine.packets_to_host`` cuts them into bytes and
-        ``inference_decoding_packed`` decodes them.  Everything else the call returns, and launches, is unchanged."""
+        ``inference_decoding_packed`` decodes them.  Everything else the call returns, and launches, is unchanged.
+        per_frame=True (with ``target_snr_db``): a stage count per FRAME (``engine.rate_pick_frames`` states the rule; csrc/
+        rvq_frame_rate_kernels.h): frame (b, t) takes the fewest stages in [min_n_q, its row's cap] that bring it down to the row's noise
+        floor, min_n_q in [0, cap] (0: a frame may take no stage).  The dict gains ``n_q_frames`` [B, Tf] int32, ``n_q_rows`` (every
+        row's largest frame count), ``n_codes_rows`` [B] int32 (the sum of its frame counts) and ``row_snr_db`` (achieved: 10 log10(E[0] /
+        sum_t err[k_t])); ``packets`` are then of mode 1 and carry the counts.  It composes with ``speech_lengths``, a per-row ``bit_width``
+        (the caps) and ``rvq_beam``; without a target, or with ``segment_dur``, ``bypass_quantizer`` or ``q0_ds_ratio > 1``, it is refused
+        before anything reaches the device."""
+        if per_frame and target_snr_db is None:        # refused before anything reaches the device
+            raise EngineError("per_frame chooses a stage count per frame by target_snr_db: give a target")
         if packed:                                     # refused before anything reaches the device
             why = packed_refusal(self.arch)
             if why:
@@ -168,7 +177,7 @@ class EncodecMI355X:
         if target_snr_db is not None:                  # refused before anything reaches the device
             rate_targets(self.arch, target_snr_db, speech.shape[0])
         with self.engine._rvq_beam(rvq_beam_width(self.arch, rvq_beam)):           # refused before anything reaches the device
-            ret = self._inference(speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db, min_n_q)
+            ret = self._inference(speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db, min_n_q, per_frame)
             if packed:
                 ret["packets"] = self._packets(ret, bit_width, speech_lengths)
             return ret
@@ -180,16 +189,22 @@ class EncodecMI355X:
         frames = None
         if speech_lengths is not None:
             frames = [self.engine.frames(int(n)) for n in torch.as_tensor(speech_lengths).reshape(-1).tolist()]
+        if ret.get("n_q_frames") is not None:          # per_frame: packets of mode 1, the counts from the call's device tensor
+            return self.engine.pack_codes(codes, frames_rows=frames, n_q_frames=ret["n_q_frames"])
         rows = ret.get("n_q_rows")
         if rows is None:
             rows = self._bit_widths(bit_width, codes.shape[1])[1]
         return self.engine.pack_codes(codes, frames_rows=frames, n_q_rows=rows)
 
-    def _inference(self, speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db=None, min_n_q=1):
+    def _inference(self, speech, need_recon, bit_width, use_scale, _quantise_always, speech_lengths, target_snr_db=None, min_n_q=1,
+                   per_frame=False):
         speech = self._as_bct(speech)
         bypass = self.arch.bypass_quantizer and not _quantise_always
         n_q, rows = self._bit_widths(bit_width, speech.shape[0])
-        rate = {} if target_snr_db is None else dict(target_snr_db=target_snr_db, min_n_q=rate_min_nq(self.arch, min_n_q, n_q, rows))
+        rate = {}
+        if target_snr_db is not None:
+            floor = (rate_min_nq_frames if per_frame else rate_min_nq)(self.arch, min_n_q, n_q, rows)
+            rate = dict(target_snr_db=target_snr_db, min_n_q=floor, **(dict(per_frame=True) if per_frame else {}))
         wav = speech[:, 0, :] if self.engine.channels == 1 else speech
         if speech_lengths is not None:
             why = ragged_refusal(self.arch)
@@ -229,6 +244,9 @@ class EncodecMI355X:
         if "n_q_rows" not in r:
             return {}
         E = r["row_errors"]
+        if "n_q_frames" in r:                          # per_frame: the achieved error is the sum over the frames at their own counts
+            return dict(n_q_rows=r["n_q_rows"], n_q_frames=r["n_q_frames"], n_codes_rows=r["n_codes_rows"],
+                        row_snr_db=10.0 * torch.log10(E[:, 0] / r["achieved_errors"]))
         Ek = E.gather(1, r["n_q_rows"].long().unsqueeze(1)).squeeze(1)
         return dict(n_q_rows=r["n_q_rows"], row_snr_db=10.0 * torch.log10(E[:, 0] / Ek))
 
@@ -236,22 +254,25 @@ class EncodecMI355X:
     @torch.no_grad()
     def inference_encoding(self, speech: torch.Tensor, need_recon: bool = False, bit_width: int = None,
                            use_scale: bool = True, speech_lengths=None, rvq_beam: int = None, target_snr_db=None,
-                           min_n_q: int = 1, packed: bool = False) -> Dict[str, torch.Tensor]:
+                           min_n_q: int = 1, packed: bool = False, per_frame: bool = False) -> Dict[str, torch.Tensor]:
         # (model_conf.bypass_quantizer does not reach this entry point in the reference: it quantises, :748-750)
         return self.inference(speech, need_recon=need_recon, bit_width=bit_width, use_scale=use_scale, _quantise_always=True,
-                              speech_lengths=speech_lengths, rvq_beam=rvq_beam, target_snr_db=target_snr_db, min_n_q=min_n_q, packed=packed)
+                              speech_lengths=speech_lengths, rvq_beam=rvq_beam, target_snr_db=target_snr_db, min_n_q=min_n_q, packed=packed,
+                              per_frame=per_frame)
 
     # -- Encodec.inference_decoding (codec_basic.py:766-802) ---------------------------------
     @torch.no_grad()
     def inference_decoding(self, token_idx: torch.Tensor, need_recon: bool = True, bit_width: int = None,
-                           use_scale: bool = True, token_lengths=None) -> Dict[str, torch.Tensor]:
+                           use_scale: bool = True, token_lengths=None, n_q_frames=None) -> Dict[str, torch.Tensor]:
         """token_lengths [B] (optional): frames per row; row b is then decoded from its own frames alone, zeros behind frames * hop.
         bit_width: ignored when it is one value, as in the reference (the tokens' last dimension says how many stages there are); a
-        sequence / 1-D tensor of B gives row b its own count: its tokens behind that are not read."""
+        sequence / 1-D tensor of B gives row b its own count: its tokens behind that are not read.
+        n_q_frames [B, Tf] (optional; ``n_q_frames`` of a ``per_frame`` call as it is): a stage count per frame; a frame's tokens behind
+        its count are not read."""
         rows = None
         if not self._one_bit_width(bit_width):
             rows = self._bit_widths(bit_width, token_idx.shape[0])[1]
-        recon, emb = self.engine.decode_codes(token_idx, lengths=token_lengths, n_q_rows=rows)
+        recon, emb = self.engine.decode_codes(token_idx, lengths=token_lengths, n_q_rows=rows, n_q_frames=n_q_frames)
         if self.arch.segment_length is not None and need_recon:      # _decode: one frame through the overlap-add (codec_basic.py:396)
             recon = self.engine.overlap_add([recon], self.arch.segment_stride or 1)
         return dict(recon_speech=recon if need_recon else None, code_indices=None,
@@ -264,7 +285,9 @@ class EncodecMI355X:
         call -> what ``inference_decoding`` returns for the codes they hold, every row decoded with the stage count its packet carries:
         unpack on the device (fc_codes_unpack), the counts of the headers as per-row stage counts, then the decode call there is.  Rows
         of different frame counts go through ``token_lengths`` where the architecture has length-aware calls; otherwise rows of equal
-        length are required.  The dict also holds ``n_q_rows`` and ``token_lengths`` (lists, from the headers)."""
+        length are required.  The dict also holds ``n_q_rows`` and ``token_lengths`` (lists, from the headers).  Packets of mode 1 (a
+        count per frame), alone or mixed with mode 0: fc_codes_unpack_frames writes the counts of every frame on the device and the decode
+        call takes them from there; the dict then also holds ``n_q_frames`` [B, Tf] int32 (device), and ``n_q_rows`` every row's largest."""
         why = packed_refusal(self.arch)
         if why:
             raise EngineError(why)
@@ -273,11 +296,11 @@ class EncodecMI355X:
             if packets.dim() != 2 or packets.dtype != torch.uint8:
                 raise EngineError(f"inference_decoding_packed: a packet buffer is uint8 [B, pitch], got {packets.dtype} {tuple(packets.shape)}")
             # the host needs the headers (the counts are a host argument of the decode call): 8 bytes per row
-            frames, counts = eng._parse_packets([bytes(h) for h in packets[:, :8].cpu().numpy()], exact=None)
+            modes, frames, counts, _ = eng._parse_packets_any([bytes(h) for h in packets[:, :8].cpu().numpy()], exact=None)
             buf = packets
         else:
             buf, _, counts = eng.packets_from_host(packets)
-            frames = eng._parse_packets(packets, exact=True)[0]
+            modes, frames = eng._parse_packets_any(packets, exact=True)[:2]
         Tf, n_q = max(frames), max(counts)
         lengths = None
         if any(f != Tf for f in frames):
@@ -285,6 +308,11 @@ class EncodecMI355X:
             if why:
                 raise EngineError(f"inference_decoding_packed: the packets hold {frames} frames and rows of equal length are required: {why}")
             lengths = frames
+        if any(modes):
+            tokens, kf = eng.unpack_frame_codes(buf, Tf, n_q)
+            recon, emb = eng.decode_codes(tokens, lengths=lengths, n_q_frames=kf)
+            return dict(recon_speech=recon if need_recon else None, code_indices=None, code_embeddings=[(emb, None)], sub_quants=None,
+                        n_q_rows=counts, token_lengths=frames, n_q_frames=kf)
         tokens = eng.unpack_codes(buf, Tf, n_q)
         rows = counts if any(k != n_q for k in counts) else None
         recon, emb = eng.decode_codes(tokens, lengths=lengths, n_q_rows=rows)

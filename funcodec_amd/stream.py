@@ -280,6 +280,10 @@ class _Session:
     def _unpack_rows(self, packets, what: str):
         """host packets -> (tokens [R,Tf,n_q] on the device, frames, counts), every header validated against the session's n_q"""
         packets = [bytes(p) for p in packets]
+        for b, p in enumerate(packets):
+            if len(p) > 6 and p[6] == 1:
+                raise EngineError(f"{what}: row {b}: packet field mode: a stage count per frame (mode 1) is for offline calls only; "
+                                  "sessions decode packets of mode 0")
         buf, Tf, counts = self.engine.packets_from_host(packets, n_q=self.n_q)
         frames = self.engine._parse_packets(packets, exact=True)[0]
         if min(frames) < 1:

@@ -273,13 +273,39 @@ int fc_engine_set_rate(fc_engine* e, const double* ratio_rows /* host [B] or NUL
  * codes dev i64 [n_q,N]; quantized dev f32 [N,D] or NULL.  Honours fc_engine_set_row_nq as the caps. */
 int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, void* stream);
 
+/* ---- a stage count per FRAME by target SNR (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
+ * csrc/rvq_frame_rate_kernels.h states the rule and funcodec_amd/engine.py::rate_pick_frames restates it on the host: with the stage
+ * errors and the fp64 row sums above, thr_b = E_b[0] * rho_b, and frame t of row b takes the smallest k in [min_nq, cap_b] with
+ * (double)err[k][b,t] * (double)F_b <= thr_b (F_b: the row's own frame count), else the k with the smallest err[k][b,t], first on ties;
+ * a row that is not finite takes cap_b in every frame, a silent row min_nq; frames behind a row's frames take 0.  Every frame is
+ * quantised down to the row's constant noise floor thr_b / F_b (reverse water-filling).  Frame (b,t) of codes, quantized, sub_quants, the
+ * decoder's input and the reconstruction is what the call with n_q = k_t gives that frame (greedy: bit for bit; with a search: the first
+ * k_t codes of the full-depth path); codes[k_t:] and sub_quants[k_t:] of the frame are 0, and a frame with k_t = 0 has quantized 0. */
+/* By the rule of csrc/rvq_frame_rate_kernels.h: given AFTER fc_engine_set_rate, it turns the rate set there into frame mode for the
+ * offline calls that follow (fc_encode, fc_encode_decode, their _ragged siblings, the 2-D FreqCodec encode, fc_rvq_encode_rate); cleared
+ * with the rate (NULL ratios), and by every new fc_engine_set_rate.  min_nq in [0, num_quantizers] replaces the floor given there: a
+ * frame may take no stage.  n_q_rows_out of fc_engine_set_rate then receives every row's LARGEST frame count.
+ *   n_q_frames_out     dev i32 [B][Tf] (required, so no workspace size changes)
+ *   n_codes_rows_out   dev i32 [B] or NULL: the sum of the row's frame counts
+ *   achieved_out       dev f64 [B] or NULL: the sum over the row's frames of err[k_t][b,t], in the order E_b is summed
+ * Refused before anything changes: no rate set, min_nq outside [0, num_quantizers], a null n_q_frames_out.  Every session push is refused
+ * by name while it is set, as for the row rate. */
+int fc_engine_set_rate_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out /* dev [B][Tf] */, int32_t* n_codes_rows_out /* dev [B] or NULL */,
+                              double* achieved_out /* dev [B] or NULL */, void* stream);
+/* By the rule of csrc/rvq_frame_rate_kernels.h (the per-frame decode): a stage count per frame for the fc_decode_codes and
+ * fc_decode_codes_ragged calls that follow; frame (b,t) sums its first n_q_frames[b][t] codes (clamped to [0, n_q]); the codes behind a
+ * frame's count are not read and never raise FC_STATUS_BAD_CODE.  The pointer is BORROWED: it is read by the launches of those calls and
+ * must stay valid until they have run; NULL clears the table.  Refused: together with a row table (fc_engine_set_row_nq); a decode call
+ * of another B or Tf, before its first launch; every decode push of a stream or slot session while a table is set. */
+int fc_engine_set_frame_nq(fc_engine* e, const int32_t* n_q_frames /* DEV i32 [B][Tf] or NULL */, int B, int Tf, void* stream);
+
 /* ---- the bit stream: one self-describing packet per row (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
  * csrc/code_pack_kernels.h states the packet rule (8-byte little-endian header: u32 frames, u8 k, u8 bits, u8 mode = 0, u8 0; payload
  * value t * k + i = codes[i][b][t] in `bits` bits each, LSB first, pad bits 0) and the device row (pitch = the largest packet rounded up
  * to 16, zeros behind the packet); funcodec_amd/io.py restates it on the host.  None of the four calls needs an engine.
  * There is no fused "decode from packets" call: decoding is fc_codes_unpack, then fc_engine_set_row_nq with the counts of the headers
  * (the host holds the bytes and therefore the headers), then the decode calls.  A call that asks for no packets launches what it did.
- * Not built: a count per frame (mode 1), entropy coding, packets for quantizer_conf.q0_ds_ratio > 1 and for segmented mode.
+ * Not built: entropy coding, packets for quantizer_conf.q0_ds_ratio > 1 and for segmented mode (a count per frame, mode 1: below).
  * Measured 2026-10-21 on the MI355X (tools/code_pack.py, profiles/code_pack.txt; median of 24, every call synchronised): both launches
  * are bound by their launch -- 17.7 us to pack and 17.0 us to unpack 16 x 250 frames x 32 stages x 10 bits (1.02 MB of int64, 0.16 MB of
  * packets), 17.9 / 17.6 us for 32 x 1 x 32, 18.5 / 18.3 us for 1 x 7500 x 32; pack plus one copy of the packets 50.9 us against 59.8 us
@@ -300,6 +326,35 @@ int fc_codes_pack(const int64_t* codes, int B, int Tf, int n_q, int bits, const 
  * calls take, zeros at stages >= k and frames >= frames.  The headers' frames and k are clamped on the device to Tf and n_q; `bits` is
  * the call's.  Refusals as for fc_codes_pack. */
 int fc_codes_unpack(const uint8_t* packets, size_t pitch, int B, int Tf, int n_q, int bits, int64_t* tokens, void* stream);
+
+/* ---- the bit stream, mode 1: a stage count per frame (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
+ * csrc/code_pack_kernels.h states mode 1 (header: u32 frames, u8 kmax, u8 bits, u8 mode = 1, u8 0; a counts section of cbits = bit
+ * length of kmax bits per frame, padded to a 32-bit word; a codes section of value S_t + i = codes[i][b][t], frame-major);
+ * funcodec_amd/io.py restates it on the host.  None of the calls needs an engine.  Not built: entropy coding, a fused decode from packets,
+ * frame mode in stream and slot sessions. */
+/* By the packet rule of csrc/code_pack_kernels.h (mode 1): the row pitch for up to `frames` frames of up to n_q stages each: the largest
+ * packet (kmax = n_q, every count n_q) rounded up to 16; 0 for arguments outside the format. */
+size_t fc_frame_packet_pitch(int frames, int n_q, int bits);
+/* By the packet rule of csrc/code_pack_kernels.h (mode 1): 8 + 4 ceil(frames cbits / 32) + ceil(n_codes bits / 8); 0 for arguments
+ * outside the format (n_codes outside 0 .. frames kmax included). */
+size_t fc_frame_packet_bytes(int frames, int kmax, long long n_codes, int bits);
+/* By the packet rule of csrc/code_pack_kernels.h (mode 1): bytes of the workspace both calls below take: one int32 table [B][Tf + 1], the
+ * exclusive scan of the counts. */
+size_t fc_frame_pack_workspace_bytes(int B, int Tf);
+/* By the packet rule of csrc/code_pack_kernels.h (mode 1): codes dev i64 [n_q][B][Tf] and n_q_frames dev i32 [B][Tf] -> packets dev u8
+ * [B][pitch].  frames_rows dev i32 [B] or NULL (all Tf).  Frames and counts are read and clamped on the device (frames to [0, Tf], a
+ * count to [0, n_q], 0 behind the row's frames; kmax is the largest clamped count), so n_q_frames_out of fc_engine_set_rate_frames feeds
+ * it directly; nothing behind a frame's count or a row's frames is read; every byte up to the pitch is written.  Refused before any
+ * launch, naming the argument: as fc_codes_pack (the pitch against fc_frame_packet_pitch), a null n_q_frames, a workspace that is null or
+ * smaller than fc_frame_pack_workspace_bytes, and a Tf * n_q that an int32 scan cannot hold. */
+int fc_codes_pack_frames(const int64_t* codes, int B, int Tf, int n_q, int bits, const int32_t* frames_rows, const int32_t* n_q_frames,
+                         uint8_t* packets, size_t pitch, void* workspace, size_t workspace_bytes, void* stream);
+/* By the packet rule of csrc/code_pack_kernels.h (mode 1): packets dev u8 [B][pitch], every row of mode 1 or mode 0 -> tokens dev i64
+ * [B][Tf][n_q] (zeros behind counts and frames) and n_q_frames dev i32 [B][Tf] (a mode-0 row: its k inside its frames), which
+ * fc_engine_set_frame_nq takes as it is: packets to waveform without a read-back.  Header and counts are clamped on the device and every
+ * read stays inside the row's pitch.  Refusals as for fc_codes_pack_frames, the pitch against fc_code_packet_pitch. */
+int fc_codes_unpack_frames(const uint8_t* packets, size_t pitch, int B, int Tf, int n_q, int bits, int64_t* tokens, int32_t* n_q_frames,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* _linear_overlap_add (funcodec/models/codec_basic.py:77-116), the tail of Encodec._decode (:382-396) when
  * model_conf.segment_dur is set: triangle-weighted overlap-add of the decoded segments, products accumulated in

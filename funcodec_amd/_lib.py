@@ -92,7 +92,7 @@ SYMBOLS = {
     "fc_code_packet_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "fc_codes_pack": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "fc_codes_unpack": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
-    # a stage count per frame (csrc/rvq_frame_rate_kernels.h): frame mode of the rate (min_nq, device outputs n_q_frames / n_codes_rows /
+    # a stage count per frame (csrc/rvq_rate_kernels.h): frame mode of the rate (min_nq, device outputs n_q_frames / n_codes_rows /
     # achieved), and a borrowed device table [B][Tf] for the decode_codes calls
     "fc_engine_set_rate_frames": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "fc_engine_set_frame_nq": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),

@@ -117,7 +117,7 @@ class Speech2Token:
         tokens behind its count are not read.
 
         per_frame (not in the reference; with target_snr_db, in the modes that encode): a stage count per FRAME (EncodecMI355X.inference,
-        csrc/rvq_frame_rate_kernels.h); min_n_q may then be 0.  The counts of the last such call stand in ``last_n_q_frames``
+        csrc/rvq_rate_kernels.h); min_n_q may then be 0.  The counts of the last such call stand in ``last_n_q_frames``
         (device int32 [B, Tf]) and ``last_n_codes_rows``; ``last_n_q_rows`` holds every row's largest, ``last_packets`` packets of mode 1.
 
         n_q_frames (not in the reference; run_mod="decode" only): a stage count per frame [B, T], as mode-1 packets carry it."""

@@ -17,7 +17,7 @@
 // Every byte behind a row's packet, up to the pitch, is written as 0: the buffer is a pure function of its inputs, and one copy of
 // [B][pitch] carries everything a receiver needs.
 //
-// MODE 1, A COUNT PER FRAME (launched by code_pack_frames_kernels.hip; the counts are those of rvq_frame_rate_kernels.h).  Header, 8 bytes:
+// MODE 1, A COUNT PER FRAME (launched by code_pack_frames_kernels.hip; the counts are those of rvq_rate_kernels.h).  Header, 8 bytes:
 //     bytes 0..3   frames (u32)
 //     byte  4      kmax (1 .. n_q): the row's largest frame count, raised to 1 if it is 0
 //     byte  5      bits

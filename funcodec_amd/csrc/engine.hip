@@ -16,7 +16,6 @@
 #include "../../include/funcodec_amd.h"
 #include "kernels.h"
 #include "rvq_beam_kernels.h"
-#include "rvq_frame_rate_kernels.h"
 #include "rvq_rate_kernels.h"
 #include "laura_kernels.h"
 #include "ragged_kernels.h"
@@ -179,7 +178,7 @@ struct fc_engine {
         int32_t* n_q_out = nullptr;
         double* row_err_out = nullptr;
         float* stage_err_out = nullptr;
-        // frame mode (fc_engine_set_rate_frames; csrc/rvq_frame_rate_kernels.h states the rule): a count per frame; min_nq may then be 0
+        // frame mode (fc_engine_set_rate_frames; the frame rule of csrc/rvq_rate_kernels.h): a count per frame; min_nq may then be 0
         bool frames = false;
         int32_t* nq_frames_out = nullptr;
         int32_t* n_codes_out = nullptr;
@@ -1930,13 +1929,20 @@ int row_nq_check(const fc_engine* e, int rows, int n_q) {
     return 0;
 }
 
-// ---- a stage count per row by target SNR (fc_engine_set_rate) ----------------------------------------
-// The rule of an offline call made while a rate is set, checked BEFORE its first launch: as many rows as the rate has, and the floor no
-// larger than n_q or any row's cap.
-int rate_check(const fc_engine* e, int rows, int n_q) {
+// ---- what a call is refused for while counts are set, checked BEFORE its first launch ------------------
+// An encode (`who`: the entry point) under the per-row table (fc_engine_set_row_nq) and the rate (fc_engine_set_rate, _frames).  An
+// offline call: as many rows as the rate has, and the floor no larger than n_q or any row's cap.  A session push takes no rate.
+int counts_check_encode(const fc_engine* e, const char* who, int B, int n_q, bool session) {
+    if (row_nq_check(e, B, n_q)) return 1;
     if (!e->rate.on()) return 0;
-    if ((int)e->rate.ratio.size() != rows)
-        return fail("a rate is set for " + std::to_string(e->rate.ratio.size()) + " rows (fc_engine_set_rate); this call has " + std::to_string(rows) +
+    if (session) {
+        if (e->rate.frames)
+            return fail(std::string(who) + ": frame mode is set (fc_engine_set_rate_frames): a stage count per frame by target SNR is for offline calls only; "
+                        "clear it with NULL ratios (fc_engine_set_rate)");
+        return fail(std::string(who) + ": a rate is set (fc_engine_set_rate): a stage count per row by target SNR is for offline calls only; clear it with NULL ratios");
+    }
+    if ((int)e->rate.ratio.size() != B)
+        return fail("a rate is set for " + std::to_string(e->rate.ratio.size()) + " rows (fc_engine_set_rate); this call has " + std::to_string(B) +
                     " (clear it with NULL ratios)");
     if (e->rate.min_nq > n_q)
         return fail("fc_engine_set_rate: min_nq = " + std::to_string(e->rate.min_nq) + " lies above n_q = " + std::to_string(n_q));
@@ -1947,19 +1953,13 @@ int rate_check(const fc_engine* e, int rows, int n_q) {
     return 0;
 }
 
-// an encode push of a session while a rate is set
-int rate_refuse_session(const fc_engine* e, const char* who) {
-    if (!e->rate.on()) return 0;
-    if (e->rate.frames)
-        return fail(std::string(who) + ": frame mode is set (fc_engine_set_rate_frames): a stage count per frame by target SNR is for offline calls only; "
-                    "clear it with NULL ratios (fc_engine_set_rate)");
-    return fail(std::string(who) + ": a rate is set (fc_engine_set_rate): a stage count per row by target SNR is for offline calls only; clear it with NULL ratios");
-}
-
-// ---- a stage count per frame for decode calls (fc_engine_set_frame_nq) --------------------------------
-// The rule of an offline decode_codes call made while a frame table is set, checked BEFORE its first launch: the table's B and Tf.
-int frame_nq_check(const fc_engine* e, int B, int Tf) {
+// A decode from codes (`who`: the entry point) under the per-row table and the table per frame (fc_engine_set_frame_nq).  An offline call:
+// the frame table's B and Tf, and not both tables.  A session push takes no frame table.
+int counts_check_decode(const fc_engine* e, const char* who, int B, int Tf, int n_q, bool session) {
+    if (row_nq_check(e, B, n_q)) return 1;
     if (!e->frame_nq.table) return 0;
+    if (session)
+        return fail(std::string(who) + ": a stage count per frame is set (fc_engine_set_frame_nq): it is for offline decode calls only; clear it with a NULL table");
     if (!e->row_nq.empty())
         return fail("a stage count per frame (fc_engine_set_frame_nq) and per-row stage counts (fc_engine_set_row_nq) are both set; clear one of them");
     if (e->frame_nq.B != B || e->frame_nq.Tf != Tf)
@@ -1968,10 +1968,56 @@ int frame_nq_check(const fc_engine* e, int B, int Tf) {
     return 0;
 }
 
-// a decode push of a session while a frame table is set
-int frame_nq_refuse_session(const fc_engine* e, const char* who) {
-    if (!e->frame_nq.table) return 0;
-    return fail(std::string(who) + ": a stage count per frame is set (fc_engine_set_frame_nq): it is for offline decode calls only; clear it with a NULL table");
+// ---- everything behind the greedy encode of a quantiser call, stated once ---------------------------------
+// The search over the stages (width > 1), then -- under a rate (fc_engine_set_rate; csrc/rvq_rate_kernels.h) -- the stage errors, the
+// row sums, the pick per row or per frame, the sum from the first k codes and the zeros behind them.
+struct RvqTail {
+    const float* x = nullptr;                   // the quantiser's input rows [B Tf][Dc]
+    int64_t* codes = nullptr;                   // [n_q][B Tf]: the greedy codes, rewritten in place
+    int B = 0, Tf = 0, n_q = 0, width = 1;
+    float *quant = nullptr, *quant_bdt = nullptr, *subq = nullptr;      // what a sum writes; each may be null
+    int64_t* paths = nullptr; float* errors = nullptr;                  // of the search, or null
+    bool beam_sum = true, rate_sum = true;      // the sum behind the search, and behind the pick
+    const fc::RagLen* rate_rows = nullptr;      // the rate applies: the frames of every row (null: it does not)
+    float* serr = nullptr; double* rerr = nullptr;                      // stage errors [n_q + 1][B Tf], row errors [B][n_q + 1]
+};
+// launch(what, flops, enqueue): how the caller makes a launch (flops: booked to the search's kernel class; 0 for every other launch)
+template <typename Launch>
+void rvq_after_greedy(const fc_engine* e, const RvqTail& a, hipStream_t st, Launch&& launch) {
+    const int N = a.B * a.Tf, Dc = e->cdim(), K = e->arch.codebook_size;
+    const int* caps = row_nq_table(e);                 // indexed by batch row (a slot push: by slot)
+    auto sum = [&](const char* what, const fc::StageCounts& k) {
+        launch(what, 0.0, [&] { return fc::launch_rvq_codes_sum(a.codes, N, Dc, K, a.n_q, e->cb, a.quant, a.quant_bdt, a.subq, a.Tf, k, st); });
+    };
+    if (a.width > 1) {      // the search rewrites the greedy codes in place; everything else from the final codes
+        launch("rvq beam", 2.0 * a.B * a.Tf * (double)a.n_q * K * Dc * a.width, [&] {
+            return fc::launch_rvq_beam(a.x, N, Dc, K, a.n_q, a.width, e->cb, e->cb_frag, e->enorm, a.codes, a.paths, a.errors, a.Tf, st, caps);
+        });
+        fc::StageCounts k; k.rows = caps;
+        if (a.beam_sum) sum("rvq beam sum", k);
+    }
+    if (!a.rate_rows) return;
+    const fc_engine::Rate& r = e->rate;
+    launch("rvq stage errors", 0.0, [&] { return fc::launch_rvq_stage_errors(a.x, a.codes, N, Dc, K, a.n_q, e->cb, a.serr, a.Tf, caps, *a.rate_rows, st); });
+    auto row_sums = [&](int min_nq, int* k_table, int32_t* n_q_out) {
+        launch("rvq rate rows", 0.0, [&] {
+            return fc::launch_rvq_rate_rows(a.serr, a.B, a.Tf, a.n_q, caps, *a.rate_rows, r.ratio_dev, min_nq, k_table, n_q_out, a.rerr, st);
+        });
+    };
+    fc::StageCounts k;                                  // the chosen counts
+    if (r.frames) {         // fc_engine_set_rate_frames: the row sums alone, then a count per frame
+        row_sums(1, nullptr, nullptr);
+        launch("rvq rate frames", 0.0, [&] {
+            return fc::launch_rvq_rate_frames(a.serr, a.rerr, a.B, a.Tf, a.n_q, caps, *a.rate_rows, r.ratio_dev, r.min_nq, r.nq_frames_out, r.n_q_out,
+                                              r.n_codes_out, r.achieved_out, st);
+        });
+        k.frames = r.nq_frames_out;
+    } else {                // a count per row, into the engine's own table (NOT row_nq_dev, which holds the caps)
+        row_sums(r.min_nq, r.k_dev, r.n_q_out);
+        k.rows = r.k_dev;
+    }
+    if (a.rate_sum) sum(r.frames ? "rvq frame sum" : "rvq rate sum", k);
+    launch(r.frames ? "rvq frame zero codes" : "rvq rate zero codes", 0.0, [&] { return fc::launch_rvq_rate_zero_codes(a.codes, N, a.Tf, a.n_q, k, st); });
 }
 
 // ---- composite paths (each usable in dry mode for workspace sizing / work accounting) ---------------
@@ -2034,52 +2080,25 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
         return fc::launch_rvq_encode(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, e->cb_frag, e->enorm, codes, quant_c, qbdt_c, sub_quants, Tf, cx.st, q0map,
                                      nq_rows);
     });
-    if (e->rvq_beam > 1) {      // fc_engine_set_rvq_beam: the search over the stages rewrites the greedy codes in place; everything else from the final codes
-        cx.launch("rvq beam", "", [] { return kRvqBeamClass; }, rvq_fl * e->rvq_beam, 0.0, [&] {
-            return fc::launch_rvq_beam(xq, B * Tf, Dc, e->arch.codebook_size, n_q, e->rvq_beam, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, Tf,
-                                       cx.st, nq_rows);
-        });
-        cx.launch("rvq beam sum", "", [&] {
-            return fc::launch_rvq_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf, cx.st, nq_rows);
-        });
-    }
-    // fc_engine_set_rate: the errors of every stage from the codes, a count per row, then everything from the first k_b codes.  A dry pass
-    // always counts the two buffers: a workspace is sized before anybody knows whether a rate will be set.
+    // fc_engine_set_rvq_beam and fc_engine_set_rate: everything behind the greedy codes.  A dry pass always counts the rate's two
+    // buffers: a workspace is sized before anybody knows whether a rate will be set.
+    RvqTail tail;
+    tail.x = xq; tail.codes = codes; tail.B = B; tail.Tf = Tf; tail.n_q = n_q; tail.width = e->rvq_beam;
+    tail.quant = quant_c; tail.quant_bdt = qbdt_c; tail.subq = sub_quants;
     if (offline_rows && (cx.dry || e->rate.on())) {
-        float* serr = cx.alloc<float>((size_t)(n_q + 1) * B * Tf);
-        double* rerr = cx.alloc<double>((size_t)B * (n_q + 1));
+        tail.serr = cx.alloc<float>((size_t)(n_q + 1) * B * Tf);
+        tail.rerr = cx.alloc<double>((size_t)B * (n_q + 1));
         if (e->rate.on()) {
             if (!cx.dry && (int)e->rate.ratio.size() != B) cx.fail("internal: a rate of another batch width");
-            if (e->rate.stage_err_out) serr = e->rate.stage_err_out;
-            if (e->rate.row_err_out) rerr = e->rate.row_err_out;
-            cx.launch("rvq stage errors", "", [&] {
-                return fc::launch_rvq_stage_errors(xq, codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, serr, Tf, nq_rows, *offline_rows, cx.st);
-            });
-            if (e->rate.frames) {       // fc_engine_set_rate_frames: the row sums alone, then a count per frame and everything from the first k_t codes
-                cx.launch("rvq rate rows", "", [&] {
-                    return fc::launch_rvq_rate_rows(serr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, 1, nullptr, nullptr, rerr, cx.st);
-                });
-                cx.launch("rvq rate frames", "", [&] {
-                    return fc::launch_rvq_rate_frames(serr, rerr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.nq_frames_out,
-                                                      e->rate.n_q_out, e->rate.n_codes_out, e->rate.achieved_out, cx.st);
-                });
-                cx.launch("rvq frame sum", "", [&] {
-                    return fc::launch_rvq_frame_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf,
-                                                          e->rate.nq_frames_out, cx.st);
-                });
-                cx.launch("rvq frame zero codes", "", [&] { return fc::launch_rvq_frame_zero_codes(codes, B * Tf, n_q, e->rate.nq_frames_out, cx.st); });
-            } else {
-                cx.launch("rvq rate rows", "", [&] {
-                    return fc::launch_rvq_rate_rows(serr, B, Tf, n_q, nq_rows, *offline_rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.k_dev, e->rate.n_q_out,
-                                                    rerr, cx.st);
-                });
-                cx.launch("rvq rate sum", "", [&] {
-                    return fc::launch_rvq_codes_sum(codes, B * Tf, Dc, e->arch.codebook_size, n_q, e->cb, quant_c, qbdt_c, sub_quants, Tf, cx.st, e->rate.k_dev);
-                });
-                cx.launch("rvq rate zero codes", "", [&] { return fc::launch_rvq_rate_zero_codes(codes, B * Tf, Tf, n_q, e->rate.k_dev, cx.st); });
-            }
+            if (e->rate.stage_err_out) tail.serr = e->rate.stage_err_out;
+            if (e->rate.row_err_out) tail.rerr = e->rate.row_err_out;
+            tail.rate_rows = offline_rows;
         }
     }
+    rvq_after_greedy(e, tail, cx.st, [&](const char* what, double flops, auto&& enqueue) {
+        if (flops > 0.0) cx.launch(what, "", [] { return kRvqBeamClass; }, flops, 0.0, enqueue);
+        else cx.launch(what, "", enqueue);
+    });
     float* qbdt = qbdt_c;
     if (e->q_proj) {       // output_proj (costume_quantizer.py:92-94): decoder input [B][D][Tf] and the returned embeddings [B][Tf][D]
         fc::Src qs; qs.ptr = qbdt_c; qs.used = 1;
@@ -2128,7 +2147,7 @@ float* decoder_input_emb(fc_engine* e, Ctx& cx, const float* emb, int Tf) {
 // (optional) gets the embeddings [B][Tf][D].  `rows` (null, or the frames of every row of a ragged call / slot push): the tokens behind a
 // row's frames are the caller's garbage, so a masked copy is looked up (none of them is read, or reported as out of range) and emb_out is
 // masked too.  `either` (workspace sizing): the first buffer as wide as the wider of the two decode calls needs it.
-// `frame_nq` (an offline call under fc_engine_set_frame_nq, else null): a stage count per frame [B][Tf], by csrc/rvq_frame_rate_kernels.h.
+// `frame_nq` (an offline call under fc_engine_set_frame_nq, else null): a stage count per frame [B][Tf], by csrc/rvq_rate_kernels.h.
 float* decoder_input_codes(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, int n_q, float* emb_out, const fc::RagLen* rows, bool either = false,
                            const int32_t* frame_nq = nullptr) {
     const int B = cx.B, D = e->arch.dimension, Dc = e->cdim();
@@ -2139,14 +2158,12 @@ float* decoder_input_codes(fc_engine* e, Ctx& cx, const int64_t* codes, int Tf, 
         codes = masked;
     }
     float* z = cx.alloc<float>((size_t)B * (either ? std::max(D, Dc) : Dc) * Tf);
-    const int* nq_rows = row_nq_table(e);              // a row's codes behind its count are not read
-    if (!cx.dry && nq_rows && (int)e->row_nq.size() != B) cx.fail("internal: per-row stage counts of another batch width");
-    cx.launch("rvq decode", "", [&] {
-        if (frame_nq)
-            return fc::launch_rvq_frame_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, frame_nq,
-                                               rows ? *rows : fc::RagLen(), cx.st);
-        return fc::launch_rvq_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, cx.st,
-                                     nq_rows);
+    fc::StageCounts k;                                  // a frame's codes behind its count are not read
+    k.rows = row_nq_table(e); k.frames = frame_nq;
+    if (!cx.dry && k.rows && (int)e->row_nq.size() != B) cx.fail("internal: per-row stage counts of another batch width");
+    cx.launch("rvq decode", "", [&] {       // a count per frame also counts 0 behind a row's frames, whatever the caller's table holds there
+        return fc::launch_rvq_decode(codes, B, Tf, n_q, Dc, e->arch.codebook_size, e->cb, e->q_proj ? nullptr : emb_out, z, e->status_dev, k,
+                                     frame_nq && rows ? *rows : fc::RagLen(), cx.st);
     });
     if (e->q_proj) {
         fc::Src qs; qs.ptr = z; qs.used = 1;
@@ -3041,8 +3058,7 @@ int fc_encode(fc_engine* e, const float* wav, int B, int T, int n_q, int64_t* co
     if (check_ready(e)) return 1;
     if (!wav || !codes || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (row_nq_check(e, B, n_q)) return 1;
-    if (rate_check(e, B, n_q)) return 1;
+    if (counts_check_encode(e, "fc_encode", B, n_q, false)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return do_encode(e, cx, wav, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr);
 }
@@ -3060,8 +3076,7 @@ int fc_decode_codes(fc_engine* e, const int64_t* codes, int B, int Tf, int n_q, 
     if (check_ready(e)) return 1;
     if (!codes || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (row_nq_check(e, B, n_q)) return 1;
-    if (frame_nq_check(e, B, Tf)) return 1;
+    if (counts_check_decode(e, "fc_decode_codes", B, Tf, n_q, false)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return do_decode(e, cx, decoder_input_codes(e, cx, codes, Tf, n_q, emb_out, nullptr, false, e->frame_nq.table), Tf, nullptr, out_len, wav);
 }
@@ -3072,8 +3087,7 @@ int fc_encode_decode(fc_engine* e, const float* wav, int B, int T, int n_q, int 
     if (check_ready(e)) return 1;
     if (!wav || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (row_nq_check(e, B, n_q)) return 1;
-    if (rate_check(e, B, n_q)) return 1;
+    if (counts_check_encode(e, "fc_encode_decode", B, n_q, false)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     float* sc = scale;
     if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
@@ -3106,8 +3120,7 @@ int fc_encode_ragged(fc_engine* e, const float* wav, const int32_t* lengths, int
     if (ragged_ready(e)) return 1;
     if (!wav || !lengths || !codes || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (row_nq_check(e, B, n_q)) return 1;
-    if (rate_check(e, B, n_q)) return 1;
+    if (counts_check_encode(e, "fc_encode_ragged", B, n_q, false)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     return ragged_encode(e, cx, wav, lengths, T, n_q, codes, quantized, sub_quants, scale, enc_out, nullptr, nullptr);
 }
@@ -3127,8 +3140,7 @@ int fc_decode_codes_ragged(fc_engine* e, const int64_t* codes, const int32_t* le
     if (ragged_ready(e)) return 1;
     if (!codes || !lengths || !wav || B <= 0 || Tf <= 0 || out_len <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (row_nq_check(e, B, n_q)) return 1;
-    if (frame_nq_check(e, B, Tf)) return 1;
+    if (counts_check_decode(e, "fc_decode_codes_ragged", B, Tf, n_q, false)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     const Pass p = ragged_pass(e, cx, lengths, Tf, 1);
     fc::RagLen f; f.lens = p.lengths;
@@ -3141,8 +3153,7 @@ int fc_encode_decode_ragged(fc_engine* e, const float* wav, const int32_t* lengt
     if (ragged_ready(e)) return 1;
     if (!wav || !lengths || !codes || !recon || B <= 0 || T <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (row_nq_check(e, B, n_q)) return 1;
-    if (rate_check(e, B, n_q)) return 1;
+    if (counts_check_encode(e, "fc_encode_decode_ragged", B, n_q, false)) return 1;
     Ctx cx = make_ctx(e, B, workspace, workspace_bytes, stream);
     float* sc = scale;
     if (e->arch.audio_normalize && !sc) sc = cx.alloc<float>(B);
@@ -3189,6 +3200,42 @@ int rvq_beam_check(const fc_engine* e, int width, const char* who) {
                     "the search over the stages is per frame");
     return 0;
 }
+
+// The prologue of the three fc_rvq_encode* hooks (`who`), before any launch: the arguments; then the N rows as B utterances of Tf = N / B
+// frames each, B from the rate (`rate`: the hook runs under fc_engine_set_rate) or from the per-row table (none set: one utterance).
+int rvq_hook_rows(fc_engine* e, const char* who, const float* x, const int64_t* codes, int N, int n_q, int width, bool search_outputs, bool rate,
+                  int* B, int* Tf) {
+    if (check_ready(e)) return 1;
+    if (!x || !codes || N <= 0) return fail("bad argument");
+    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
+    if (rate && !e->rate.on()) return fail(std::string(who) + ": no rate is set (fc_engine_set_rate)");
+    if (rate && (!e->rate.row_err_out || !e->rate.stage_err_out))
+        return fail(std::string(who) + ": the hook has no workspace: fc_engine_set_rate with row_errors_out and stage_errors_out");
+    if (rvq_beam_check(e, width, who)) return 1;
+    if (width == 1 && search_outputs) return fail(std::string(who) + ": paths and errors are those of a search: rvq_beam above 1");
+    *B = rate ? (int)e->rate.ratio.size() : e->row_nq.empty() ? 1 : (int)e->row_nq.size();
+    *Tf = N / *B;
+    if (N % *B != 0)
+        return fail(std::string(who) + ": with " + (rate ? "a rate for " : "per-row stage counts for ") + std::to_string(*B) +
+                    " rows, N must be a multiple of that");
+    return rate ? counts_check_encode(e, who, *B, n_q, false) : row_nq_check(e, *B, n_q);
+}
+
+// The greedy encode of the search and rate hooks (`quantized`: what it sums, or null) and everything behind it; the first launch that
+// fails ends the sequence and is reported by name.
+int rvq_hook_launch(fc_engine* e, const char* who, const RvqTail& a, float* quantized, hipStream_t st) {
+    hipError_t er = hipSuccess;
+    const char* failed = "";
+    auto launch = [&](const char* what, double, auto&& enqueue) {
+        if (er == hipSuccess && (er = enqueue()) != hipSuccess) failed = what;
+    };
+    launch("rvq", 0.0, [&] {
+        return fc::launch_rvq_encode(a.x, a.B * a.Tf, e->cdim(), e->arch.codebook_size, a.n_q, e->cb, e->cb_frag, e->enorm, a.codes, quantized, nullptr,
+                                     nullptr, a.Tf, st, nullptr, row_nq_table(e));
+    });
+    rvq_after_greedy(e, a, st, launch);
+    return er == hipSuccess ? 0 : fail(std::string(who) + ": " + failed + ": " + hipGetErrorString(er));
+}
 }  // namespace
 
 int fc_engine_set_rvq_beam(fc_engine* e, int width, void* stream) {
@@ -3204,22 +3251,12 @@ int fc_engine_set_rvq_beam(fc_engine* e, int width, void* stream) {
 
 int fc_rvq_encode_beam(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, int64_t* paths, float* errors,
                        void* stream) {
-    if (check_ready(e)) return 1;
-    if (!x || !codes || N <= 0) return fail("bad argument");
-    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (rvq_beam_check(e, width, "fc_rvq_encode_beam")) return 1;
-    if (width == 1 && (paths || errors)) return fail("fc_rvq_encode_beam: paths and errors are those of a search: rvq_beam above 1");
-    const int B = e->row_nq.empty() ? 1 : (int)e->row_nq.size(), Tf = N / B;
-    if (N % B != 0) return fail("fc_rvq_encode_beam: with per-row stage counts for " + std::to_string(B) + " rows, N must be a multiple of that");
-    if (row_nq_check(e, B, n_q)) return 1;
-    const int Dc = e->cdim(), K = e->arch.codebook_size;
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(fc::launch_rvq_encode(x, N, Dc, K, n_q, e->cb, e->cb_frag, e->enorm, codes, quantized, nullptr, nullptr, Tf, st, nullptr, row_nq_table(e)));
-    if (width > 1) {
-        HIP_TRY(fc::launch_rvq_beam(x, N, Dc, K, n_q, width, e->cb, e->cb_frag, e->enorm, codes, paths, errors, Tf, st, row_nq_table(e)));
-        if (quantized) HIP_TRY(fc::launch_rvq_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, st, row_nq_table(e)));
-    }
-    return 0;
+    RvqTail a;
+    if (rvq_hook_rows(e, "fc_rvq_encode_beam", x, codes, N, n_q, width, paths || errors, false, &a.B, &a.Tf)) return 1;
+    a.x = x; a.codes = codes; a.n_q = n_q; a.width = width;
+    a.quant = quantized; a.beam_sum = quantized != nullptr;
+    a.paths = paths; a.errors = errors;
+    return rvq_hook_launch(e, "fc_rvq_encode_beam", a, quantized, (hipStream_t)stream);
 }
 
 int fc_engine_set_rate(fc_engine* e, const double* ratio_rows, int B, int min_nq, int32_t* n_q_rows_out, double* row_errors_out,
@@ -3287,48 +3324,20 @@ int fc_engine_set_frame_nq(fc_engine* e, const int32_t* n_q_frames, int B, int T
 }
 
 int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, void* stream) {
-    if (check_ready(e)) return 1;
-    if (!x || !codes || N <= 0) return fail("bad argument");
-    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (!e->rate.on()) return fail("fc_rvq_encode_rate: no rate is set (fc_engine_set_rate)");
-    if (!e->rate.row_err_out || !e->rate.stage_err_out)
-        return fail("fc_rvq_encode_rate: the hook has no workspace: fc_engine_set_rate with row_errors_out and stage_errors_out");
-    if (rvq_beam_check(e, width, "fc_rvq_encode_rate")) return 1;
-    const int B = (int)e->rate.ratio.size(), Tf = N / B;
-    if (N % B != 0) return fail("fc_rvq_encode_rate: with a rate for " + std::to_string(B) + " rows, N must be a multiple of that");
-    if (row_nq_check(e, B, n_q)) return 1;
-    if (rate_check(e, B, n_q)) return 1;
-    const int Dc = e->cdim(), K = e->arch.codebook_size;
-    hipStream_t st = (hipStream_t)stream;
-    const fc::RagLen rows;
-    HIP_TRY(fc::launch_rvq_encode(x, N, Dc, K, n_q, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, nullptr, Tf, st, nullptr, row_nq_table(e)));
-    if (width > 1) HIP_TRY(fc::launch_rvq_beam(x, N, Dc, K, n_q, width, e->cb, e->cb_frag, e->enorm, codes, nullptr, nullptr, Tf, st, row_nq_table(e)));
-    HIP_TRY(fc::launch_rvq_stage_errors(x, codes, N, Dc, K, n_q, e->cb, e->rate.stage_err_out, Tf, row_nq_table(e), rows, st));
-    if (e->rate.frames) {       // fc_engine_set_rate_frames: by csrc/rvq_frame_rate_kernels.h
-        HIP_TRY(fc::launch_rvq_rate_rows(e->rate.stage_err_out, B, Tf, n_q, row_nq_table(e), rows, e->rate.ratio_dev, 1, nullptr, nullptr, e->rate.row_err_out, st));
-        HIP_TRY(fc::launch_rvq_rate_frames(e->rate.stage_err_out, e->rate.row_err_out, B, Tf, n_q, row_nq_table(e), rows, e->rate.ratio_dev, e->rate.min_nq,
-                                           e->rate.nq_frames_out, e->rate.n_q_out, e->rate.n_codes_out, e->rate.achieved_out, st));
-        if (quantized) HIP_TRY(fc::launch_rvq_frame_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, e->rate.nq_frames_out, st));
-        HIP_TRY(fc::launch_rvq_frame_zero_codes(codes, N, n_q, e->rate.nq_frames_out, st));
-        return 0;
-    }
-    HIP_TRY(fc::launch_rvq_rate_rows(e->rate.stage_err_out, B, Tf, n_q, row_nq_table(e), rows, e->rate.ratio_dev, e->rate.min_nq, e->rate.k_dev,
-                                     e->rate.n_q_out, e->rate.row_err_out, st));
-    if (quantized) HIP_TRY(fc::launch_rvq_codes_sum(codes, N, Dc, K, n_q, e->cb, quantized, nullptr, nullptr, Tf, st, e->rate.k_dev));
-    HIP_TRY(fc::launch_rvq_rate_zero_codes(codes, N, Tf, n_q, e->rate.k_dev, st));
-    return 0;
+    RvqTail a;
+    if (rvq_hook_rows(e, "fc_rvq_encode_rate", x, codes, N, n_q, width, false, true, &a.B, &a.Tf)) return 1;
+    a.x = x; a.codes = codes; a.n_q = n_q; a.width = width;
+    a.quant = quantized; a.beam_sum = false; a.rate_sum = quantized != nullptr;      // one sum, from the chosen counts
+    const fc::RagLen rows;                              // every row has Tf frames
+    a.rate_rows = &rows; a.serr = e->rate.stage_err_out; a.rerr = e->rate.row_err_out;
+    return rvq_hook_launch(e, "fc_rvq_encode_rate", a, nullptr, (hipStream_t)stream);
 }
 
 int fc_rvq_encode(fc_engine* e, const float* x, int N, int n_q, int64_t* codes, float* quantized, void* workspace,
                   size_t workspace_bytes, void* stream) {
-    if (check_ready(e)) return 1;
-    (void)workspace; (void)workspace_bytes;
-    if (!x || !codes || N <= 0) return fail("bad argument");
-    if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
     // with per-row stage counts for B rows (fc_engine_set_row_nq) the N rows are B utterances of N / B frames each
-    const int B = e->row_nq.empty() ? 1 : (int)e->row_nq.size(), Tf = N / B;
-    if (N % B != 0) return fail("fc_rvq_encode: with per-row stage counts for " + std::to_string(B) + " rows, N must be a multiple of that");
-    if (row_nq_check(e, B, n_q)) return 1;
+    int B = 0, Tf = 0;
+    if (rvq_hook_rows(e, "fc_rvq_encode", x, codes, N, n_q, 1, false, false, &B, &Tf)) return 1;
     int* q0map = nullptr;
     if (e->arch.q0_ds_ratio > 1) {      // the rows are ONE utterance of N frames; the stage-0 source-row table lives in the caller's workspace
         if (Tf < 2) return fail("quantizer_conf.q0_ds_ratio > 1 needs at least 2 frames");
@@ -3853,8 +3862,7 @@ int fc_stream_encode(fc_stream* S, const float* wav, int Tc, int final, int64_t*
                     " samples (the offline call's reflected left padding spans them); shorter utterances go through the offline call");
     const int Tfc = final ? frames_for(e, Tc) : Tc / hop;
     if (frames_fit(S, false, Tfc)) return 1;
-    if (row_nq_check(e, S->B, S->n_q)) return 1;
-    if (rate_refuse_session(e, "fc_stream_encode")) return 1;
+    if (counts_check_encode(e, "fc_stream_encode", S->B, S->n_q, true)) return 1;
     // the first push of an utterance (reflection staging) and the final one (extra padding) are one-offs: never cached
     const Session::GraphKey key = graph_key(*S, kFormEncode, Tc, S->enc_pushes, 0, {wav, codes, quantized, enc_out}, workspace, workspace_bytes, stream);
     S->broken = true;                                   // until the whole push is enqueued: a failure in between leaves mixed carries
@@ -3881,8 +3889,7 @@ int fc_stream_decode_codes(fc_stream* S, const int64_t* codes, int Tfc, int use_
     if (stream_ready(S)) return 1;
     if (!codes || !wav) return fail("bad argument");
     if (stream_decode_check(S, Tfc)) return 1;
-    if (row_nq_check(S->e, S->B, S->n_q)) return 1;
-    if (frame_nq_refuse_session(S->e, "fc_stream_decode_codes")) return 1;
+    if (counts_check_decode(S->e, "fc_stream_decode_codes", S->B, Tfc, S->n_q, true)) return 1;
     return stream_decode_push(S, kFormDecodeCodes, codes, Tfc, use_scale, wav, emb_out, workspace, workspace_bytes, stream);
 }
 
@@ -3986,8 +3993,7 @@ int fc_slots_encode(fc_slots* Q, const float* wav, int Tc, const int32_t* sample
     if (slots_ready(Q)) return 1;
     if (!wav || !samples || !flags || !codes) return fail("bad argument");
     if (slots_check(Q, false, samples, flags, Tc, Q->max_chunk)) return 1;
-    if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
-    if (rate_refuse_session(Q->e, "fc_slots_encode")) return 1;
+    if (counts_check_encode(Q->e, "fc_slots_encode", Q->B, Q->n_q, true)) return 1;
     const Session::GraphKey key = graph_key(*Q, kFormEncode, Tc, Q->enc_pushes, 0, {wav, codes, quantized, enc_out, scale}, workspace, workspace_bytes, stream);
     const int err = session_push(
         Q, &key, workspace, workspace_bytes, stream, [&](hipStream_t st) { return slots_upload(Q, false, samples, flags, workspace, workspace_bytes, st); },
@@ -4017,8 +4023,7 @@ int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int3
     if (slots_ready(Q)) return 1;
     if (!codes || !frames || !flags || !wav) return fail("bad argument");
     if (slots_check(Q, true, frames, flags, Tfc, ceil_div_i(Q->max_chunk, total_hop(Q->e)))) return 1;
-    if (row_nq_check(Q->e, Q->B, Q->n_q)) return 1;
-    if (frame_nq_refuse_session(Q->e, "fc_slots_decode_codes")) return 1;
+    if (counts_check_decode(Q->e, "fc_slots_decode_codes", Q->B, Tfc, Q->n_q, true)) return 1;
     const Session::GraphKey key = graph_key(*Q, kFormDecodeCodes, Tfc, Q->dec_pushes, use_scale, {codes, wav, emb_out}, workspace, workspace_bytes, stream);
     const int err = session_push(
         Q, &key, workspace, workspace_bytes, stream, [&](hipStream_t st) { return slots_upload(Q, true, frames, flags, workspace, workspace_bytes, st); },

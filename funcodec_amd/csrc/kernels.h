@@ -224,16 +224,7 @@ __host__ __device__ inline int q0_source_frame(int t, int Tf) {
     return s;
 }
 hipError_t launch_q0_map(int* map /* [B][Tf] */, int B, int Tf, hipStream_t st);
-// codes [B][Tf][nq] (i64) -> emb [B][Tf][D] and/or emb_bdt [B][D][Tf]
-// status: host-visible engine status words (FC_STATUS_*), or null; an index outside [0, K) sets FC_STATUS_BAD_CODE
-// nq_rows: per-batch-row stage counts [B] (device) or null; the codes behind a row's count are not read (and never reported)
-hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb,
-                             float* emb, float* emb_bdt, unsigned* status, hipStream_t st, const int* nq_rows = nullptr);
-// What the quantiser returns besides codes, from the final codes [nq][N]: quant [N][D] = ((0 + E_0[c0]) + E_1[c1]) + ... (the order of
-// launch_rvq_decode and of the greedy kernel, so bit for bit what decoding those codes gives), quant_bdt [B][D][Tf], subq [nq][B][D][Tf]
-// (E_i[c_i]; 0 behind a row's count).  Each may be null.
-hipError_t launch_rvq_codes_sum(const int64_t* codes, int N, int D, int K, int nq, const float* cb, float* quant, float* quant_bdt, float* subq,
-                                int Tf, hipStream_t st, const int* nq_rows = nullptr);
+// launch_rvq_decode and launch_rvq_codes_sum (rvq_kernels.hip) take a count per row or per frame: rvq_rate_kernels.h declares them
 
 // engine status words (host-pinned, device-mapped): written by kernels with plain stores, read by the host without a sync
 #define FC_STATUS_LSTM_TIMEOUT 0   // persistent LSTM: the grid barrier timed out (workgroups not co-resident); outputs poisoned

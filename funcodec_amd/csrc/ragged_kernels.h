@@ -18,6 +18,23 @@ struct RagLen {
     int div = 1, mul = 1, add = 0;
 };
 __host__ __device__ inline int ragged_cols(int len, int div, int mul, int add) { return (len + div - 1) / div * mul + add; }
+// frames of batch row b of a quantiser call: all Tf, or the row's own in a length-aware call
+__device__ __forceinline__ int row_frames(const RagLen& rows, int b, int Tf) {
+    if (!rows.lens) return Tf;
+    const int f = ragged_cols(rows.lens[b], rows.div, rows.mul, rows.add);
+    return f < Tf ? f : Tf;
+}
+
+// ---- how many quantiser stages frame row n = b Tf + t takes, stated once (rvq_rate_kernels.h): a count per batch row, a count per frame,
+// or nq everywhere.  The kernels that sum, decode or zero codes by a count read it through stage_count; the codes behind it are not read.
+struct StageCounts {
+    const int32_t* rows = nullptr;      // device [B], indexed n / Tf
+    const int32_t* frames = nullptr;    // device [B][Tf], indexed n; wins over rows
+};                                      // both null: nq everywhere
+__device__ __forceinline__ int stage_count(const StageCounts& c, int n, int b, int nq) {
+    const int k = c.frames ? c.frames[n] : (c.rows ? c.rows[b] : nq);
+    return k < 0 ? 0 : (k > nq ? nq : k);      // clamped to [0, nq]
+}
 
 // SConv1d's extra_padding for a row of n columns (conv.py:57-64); conv_geom in engine.hip calls it for the whole batch width
 __host__ __device__ inline int ragged_extra(int n, int k, int pt, int stride) {

@@ -2,6 +2,7 @@
 // that restate its order.  The search over the stages is rvq_beam_kernels.hip.  fp32 throughout, 64-lane wavefronts.
 #include "device_common.h"
 #include "kernels.h"
+#include "rvq_rate_kernels.h"
 
 namespace fc {
 
@@ -499,14 +500,15 @@ hipError_t launch_rvq_encode(const float* x, int N, int D, int K, int nq, const 
 }
 
 // DRVQ.decode (ddp_core_vq.py:442-453): out = ((0 + E_0[i0]) + E_1[i1]) + ...
-// nq_rows (per-batch-row stage counts [B], or null): row n sums its first nq_rows[n / Tf] stages; the codes behind them are not read
+// counts (rvq_rate_kernels.h): frame row n sums its first k stages; the codes behind them are not read.  rows (lens given): a frame behind
+// its row's frames sums none
 __global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restrict__ codes, int Tf, int nq, int D, int K,
                                                          const float* __restrict__ cb, float* __restrict__ emb,
                                                          float* __restrict__ emb_bdt, unsigned* __restrict__ status,
-                                                         const int* __restrict__ nq_rows) {
+                                                         StageCounts counts, RagLen rows) {
     const int n = blockIdx.x;   // row = b*Tf + t
     const int b = n / Tf, t = n - b * Tf;
-    const int k = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
+    const int k = t < row_frames(rows, b, Tf) ? stage_count(counts, n, b, nq) : 0;
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         float s = 0.f;
         for (int i = 0; i < k; ++i) {
@@ -524,22 +526,23 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restri
     }
 }
 
-hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb, float* emb,
-                             float* emb_bdt, unsigned* status, hipStream_t st, const int* nq_rows) {
-    if (B * Tf <= 0) return hipSuccess;
+hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb, float* emb, float* emb_bdt,
+                             unsigned* status, const StageCounts& k, const RagLen& rows, hipStream_t st) {
+    if ((long long)B * Tf <= 0) return hipSuccess;
+    if (nq < 1) return hipErrorInvalidValue;
     const int threads = D >= 256 ? 256 : (D >= 128 ? 128 : 64);
-    hipLaunchKernelGGL(rvq_decode_kernel, dim3(B * Tf), dim3(threads), 0, st, codes, Tf, nq, D, K, cb, emb, emb_bdt, status, nq_rows);
+    hipLaunchKernelGGL(rvq_decode_kernel, dim3(B * Tf), dim3(threads), 0, st, codes, Tf, nq, D, K, cb, emb, emb_bdt, status, k, rows);
     return hipGetLastError();
 }
 
-// quant / quant_bdt / subq of the final codes: one workgroup per frame, the sum in stage order from 0 (launch_rvq_decode's order)
+// quant / quant_bdt / subq of the final codes: one workgroup per frame, the sum in stage order from 0 (launch_rvq_decode's order) over the
+// frame's first k codes (counts: rvq_rate_kernels.h)
 __global__ __launch_bounds__(256) void rvq_codes_sum_kernel(const int64_t* __restrict__ codes, int N, int Tf, int nq, int D, int K,
                                                             const float* __restrict__ cb, float* __restrict__ quant,
-                                                            float* __restrict__ quant_bdt, float* __restrict__ subq,
-                                                            const int* __restrict__ nq_rows) {
+                                                            float* __restrict__ quant_bdt, float* __restrict__ subq, StageCounts counts) {
     const int n = blockIdx.x;
     const int b = n / Tf, t = n - b * Tf, Bn = N / Tf;
-    const int k = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
+    const int k = stage_count(counts, n, b, nq);
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         float s = 0.f;
         for (int i = 0; i < nq; ++i) {
@@ -558,11 +561,11 @@ __global__ __launch_bounds__(256) void rvq_codes_sum_kernel(const int64_t* __res
 }
 
 hipError_t launch_rvq_codes_sum(const int64_t* codes, int N, int D, int K, int nq, const float* cb, float* quant, float* quant_bdt, float* subq,
-                                int Tf, hipStream_t st, const int* nq_rows) {
+                                int Tf, const StageCounts& k, hipStream_t st) {
     if (N <= 0) return hipSuccess;
-    if (Tf <= 0 || N % Tf != 0) return hipErrorInvalidValue;
+    if (Tf <= 0 || N % Tf != 0 || nq < 1) return hipErrorInvalidValue;
     const int threads = D >= 256 ? 256 : (D >= 128 ? 128 : 64);
-    hipLaunchKernelGGL(rvq_codes_sum_kernel, dim3(N), dim3(threads), 0, st, codes, N, Tf, nq, D, K, cb, quant, quant_bdt, subq, nq_rows);
+    hipLaunchKernelGGL(rvq_codes_sum_kernel, dim3(N), dim3(threads), 0, st, codes, N, Tf, nq, D, K, cb, quant, quant_bdt, subq, k);
     return hipGetLastError();
 }
 

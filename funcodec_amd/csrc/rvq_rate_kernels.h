@@ -1,8 +1,15 @@
-// Residual vector quantiser: a stage count per row chosen on the device by a target SNR (launched by rvq_rate_kernels.hip).  The
-// reference has no such mode: this header is its specification; funcodec_amd/engine.py::rate_pick restates the pick on the host.
+// Residual vector quantiser: how many stages a piece of audio takes.  A count per row or per frame, given by the caller or chosen on the
+// device by a target SNR (launched by rvq_rate_kernels.hip; the sum and the decode by a count are rvq_kernels.hip).  The reference has no
+// such mode: this header is its specification; funcodec_amd/engine.py::rate_pick and ::rate_pick_frames restate the picks on the host.
 //
-// Input rows x [N = B Tf][D] (what launch_rvq_encode was handed) and the codes c [nq][N] the call found at the cap, whoever found them
-// (the greedy kernel, or the search of rvq_beam_kernels.h at its full depth).
+// THE COUNT (StageCounts, ragged_kernels.h).  Frame row n = b Tf + t takes k stages: frames[n] if a count per frame is given, else
+// rows[n / Tf] if a count per row is, else nq; a count is clamped to [0, nq].  A residual quantiser is a prefix code per frame and nothing
+// is carried from frame to frame, so either count is exact: the frame is what the call with n_q = k gives it.  The kernels that sum
+// (launch_rvq_codes_sum), decode (launch_rvq_decode) or zero (launch_rvq_rate_zero_codes) by a count read it through stage_count; codes
+// behind a count are not read and never raise FC_STATUS_BAD_CODE.
+//
+// THE ROW RULE.  Input rows x [N = B Tf][D] (what launch_rvq_encode was handed) and the codes c [nq][N] the call found at the cap, whoever
+// found them (the greedy kernel, or the search of rvq_beam_kernels.h at its full depth).
 //   * stage errors err [nq + 1][N] fp32:  r_0 = x[n];  r_{i+1} = r_i - E_i[c_i[n]] element-wise in fp32;  err[i][n] = |r_i|^2 in the fixed
 //     order of rvq_row_norm (device_common.h): four chains over D / 4, squares rounded separately, (p0 + p1) + (p2 + p3) -- compiled here
 //     with contraction off, so every multiply and add rounds by itself (the encode kernels' own copy fuses square and add; their
@@ -21,6 +28,25 @@
 // The caller then sums the first k_b code vectors of every row (launch_rvq_codes_sum with the chosen table: stage order from 0, the greedy
 // kernel's running sum) and zeroes codes[k_b:] (launch_rvq_rate_zero_codes).  For greedy codes row b is then bit for bit the call with
 // n_q = k_b.  For the search it is the first k_b codes of the full-depth path, which is NOT the search over k_b stages.
+//
+// THE FRAME RULE, in terms of the row rule.  Inputs: the stage errors err and the fp64 row sums E above, unchanged; rho_b and cap_b as
+// above; the row's own frame count F_b (Tf, or the row's frames in a length-aware call); the floor lo = min_nq clamped to [0, cap_b] -- in
+// frame mode a frame may take no stage at all.
+//   * thr_b = E_b[0] * rho_b: the one IEEE double product of the row rule;
+//   * a row whose E_b[0 .. cap_b] are not all finite: every frame of it takes cap_b (what the plain call gives it);
+//   * a row with E_b[0] == 0 (digital silence): every frame takes lo;
+//   * else frame t takes the smallest k in [lo, cap_b] with (double)err[k][b, t] * (double)F_b <= thr_b -- products only, no division, so
+//     a host restates it operation by operation;
+//   * if no k qualifies: the k in that range with the smallest err[k][b, t], first on ties (the scan of the row rule, on the frame's
+//     fp32 errors);
+//   * frames behind a row's frames get count 0, and nothing of them is read.
+// If every frame of a row meets its threshold then sum_t err[k_t][b, t] <= thr_b up to the rounding of the sum: every frame is quantised
+// down to the same noise floor thr_b / F_b, however loud it is.  A constant noise floor per row is reverse water-filling, the
+// rate-distortion optimum for independent components; the row rule instead spends the loudest frame's stages on a silent one.
+// Outputs, all on the device: n_q_frames [B][Tf] i32; n_q_rows [B] i32, the row's largest frame count; n_codes_rows [B] i32 = sum_t k_t;
+// achieved [B] f64 = sum_t err[k_t][b, t] in the order E_b is summed.
+// The caller then sums and zeroes as above with the counts per frame: for greedy codes frame (b, t) is bit for bit the call with
+// n_q = k_t; for the search it is the first k_t codes of the full-depth path.  A frame with k_t = 0 has quantized exactly 0.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -37,7 +63,25 @@ hipError_t launch_rvq_stage_errors(const float* x /* [N][D] */, const int64_t* c
 hipError_t launch_rvq_rate_rows(const float* err /* [nq + 1][B Tf] */, int B, int Tf, int nq, const int* nq_rows, const RagLen& rows,
                                 const double* ratio /* dev [B] */, int min_nq, int* k_table, int32_t* n_q_out, double* row_err, hipStream_t st);
 
-// codes[i][n] = 0 for every i >= k_table[n / Tf]
-hipError_t launch_rvq_rate_zero_codes(int64_t* codes /* [nq][N] */, int N, int Tf, int nq, const int* k_table, hipStream_t st);
+// One workgroup per batch row.  err [nq + 1][B Tf]; row_err [B][nq + 1] (launch_rvq_rate_rows wrote it on the same stream); nq_rows [B] (caps)
+// or null; rows.lens null: every row has Tf frames.  n_q_frames [B][Tf] never null; the three row outputs may be null.
+hipError_t launch_rvq_rate_frames(const float* err, const double* row_err, int B, int Tf, int nq, const int* nq_rows, const RagLen& rows,
+                                  const double* ratio /* dev [B] */, int min_nq, int32_t* n_q_frames, int32_t* n_q_rows_out, int32_t* n_codes_out,
+                                  double* achieved, hipStream_t st);
+
+// codes[i][n] = 0 for every i >= the count of frame row n (one of k's tables is set)
+hipError_t launch_rvq_rate_zero_codes(int64_t* codes /* [nq][N] */, int N, int Tf, int nq, const StageCounts& k, hipStream_t st);
+
+// ---- rvq_kernels.hip
+// codes [B][Tf][nq] (i64) -> emb [B][Tf][D] and/or emb_bdt [B][D][Tf]: out = ((0 + E_0[i0]) + E_1[i1]) + ... over the frame's first k codes
+// status: host-visible engine status words (FC_STATUS_*), or null; an index outside [0, K) sets FC_STATUS_BAD_CODE
+// rows (lens given): a frame behind its row's frames counts 0 stages whatever the tables hold
+hipError_t launch_rvq_decode(const int64_t* codes, int B, int Tf, int nq, int D, int K, const float* cb, float* emb, float* emb_bdt,
+                             unsigned* status, const StageCounts& k, const RagLen& rows, hipStream_t st);
+// What the quantiser returns besides codes, from the final codes [nq][N]: quant [N][D] = ((0 + E_0[c0]) + E_1[c1]) + ... (the order of
+// launch_rvq_decode and of the greedy kernel, so bit for bit what decoding those codes gives), quant_bdt [B][D][Tf], subq [nq][B][D][Tf]
+// (E_i[c_i]; 0 behind a frame's count).  Each may be null.
+hipError_t launch_rvq_codes_sum(const int64_t* codes, int N, int D, int K, int nq, const float* cb, float* quant, float* quant_bdt, float* subq,
+                                int Tf, const StageCounts& k, hipStream_t st);
 
 }  // namespace fc

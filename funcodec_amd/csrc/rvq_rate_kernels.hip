@@ -1,7 +1,8 @@
 // gfx950 (MI355X / CDNA4) kernels of the quantiser's rate control: the residual energy of every frame after every stage, made from the
-// codes of a call, the fp64 sums per batch row with the pick of a stage count, and the zeros behind it.  rvq_rate_kernels.h states the
-// rule.  fp32 / fp64 throughout, 64-lane wavefronts.  The encode kernels (rvq_kernels.hip, rvq_beam_kernel.h) are not involved: the
-// errors are recomputed from x and the codes, so whoever found the codes is measured by the same formula.
+// codes of a call, the fp64 sums per batch row with the pick of a stage count per row, the pick per frame, and the zeros behind a count.
+// rvq_rate_kernels.h states the rules.  fp32 / fp64 and integers, 64-lane wavefronts.  The encode kernels (rvq_kernels.hip,
+// rvq_beam_kernel.h) are not involved: the errors are recomputed from x and the codes, so whoever found the codes is measured by the
+// same formula.
 #include "device_common.h"
 #include "rvq_rate_kernels.h"
 
@@ -10,11 +11,18 @@ namespace fc {
 namespace {
 constexpr int kRateRows = 16;        // frames per workgroup of rvq_stage_errors_kernel
 
-// frames of batch row b: all Tf, or the row's own in a length-aware call
-__device__ __forceinline__ int rate_frames(const RagLen& rows, int b, int Tf) {
-    if (!rows.lens) return Tf;
-    const int f = ragged_cols(rows.lens[b], rows.div, rows.mul, rows.add);
-    return f < Tf ? f : Tf;
+// The scan of both picks (rvq_rate_kernels.h): the smallest k in [lo, cap] with meets(err(k)), else the k in that range with the smallest
+// err(k), first on ties.  The row rule scans fp64 row sums, the frame rule one frame's fp32 errors.
+template <typename Err, typename Meets>
+__device__ __forceinline__ int rate_pick_scan(int lo, int cap, Err&& err, Meets&& meets) {
+    int best = lo;
+    auto ebest = err(lo);
+    for (int i = lo; i <= cap; ++i) {
+        const auto ei = err(i);
+        if (meets(ei)) return i;
+        if (ei < ebest) { ebest = ei; best = i; }
+    }
+    return best;
 }
 
 // |r|^2 of one residual row by four lanes j = 0 .. 3 (consecutive lanes) in the order rvq_row_norm (device_common.h) states: chain j over
@@ -56,7 +64,7 @@ __global__ __launch_bounds__(256) void rvq_stage_errors_kernel(const float* __re
         int k = -1;
         if (n < N) {
             const int b = n / Tf, t = n - b * Tf;
-            if (t < rate_frames(rows, b, Tf)) k = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
+            if (t < row_frames(rows, b, Tf)) k = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
         }
         krow[tid] = k;
     }
@@ -124,7 +132,7 @@ __global__ __launch_bounds__(256) void rvq_rate_rows_kernel(const float* __restr
     __shared__ double red[256];
     const int tid = threadIdx.x, b = blockIdx.x;
     const size_t N = (size_t)gridDim.x * Tf;
-    const int frames = rate_frames(rows, b, Tf);
+    const int frames = row_frames(rows, b, Tf);
     const int cap = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
     double* E = row_err + (size_t)b * (nq + 1);
     for (int i = 0; i <= nq; ++i) {
@@ -149,12 +157,7 @@ __global__ __launch_bounds__(256) void rvq_rate_rows_kernel(const float* __restr
         if (E[0] == 0.0) k = lo;
         else {
             const double thr = E[0] * ratio[b];
-            int best = lo, hit = 0;
-            for (int i = lo; i <= cap; ++i) {
-                if (E[i] <= thr) { hit = i; break; }
-                if (E[i] < E[best]) best = i;
-            }
-            k = hit ? hit : best;
+            k = rate_pick_scan(lo, cap, [&](int i) { return E[i]; }, [&](double ei) { return ei <= thr; });
         }
     }
     if (k_table) k_table[b] = k;
@@ -169,15 +172,84 @@ hipError_t launch_rvq_rate_rows(const float* err, int B, int Tf, int nq, const i
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void rvq_rate_zero_codes_kernel(int64_t* __restrict__ codes, int N, int Tf, const int* __restrict__ k_table) {
-    const int n = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
-    if (n < N && i >= k_table[n / Tf]) codes[(size_t)i * N + n] = 0;
+// One workgroup per batch row, 256 threads; thread j owns frames t = j, j + 256, ... in rising order (the order of E_b's partial sums).
+// Thread 0 classifies the row (finite / silent / threshold) into LDS; every thread then picks for its frames, keeps its fp64 partial of
+// the achieved error, its count sum and its largest count; the partials meet as a binary tree in LDS (no atomics).
+__global__ __launch_bounds__(256) void rvq_rate_frames_kernel(const float* __restrict__ err, const double* __restrict__ row_err, int Tf, int nq,
+                                                              const int* __restrict__ nq_rows, RagLen rows, const double* __restrict__ ratio,
+                                                              int min_nq, int32_t* __restrict__ n_q_frames, int32_t* __restrict__ n_q_rows_out,
+                                                              int32_t* __restrict__ n_codes_out, double* __restrict__ achieved) {
+    __shared__ double red[256];
+    __shared__ int redk[256], redm[256];
+    __shared__ int row_kind;            // 0: threshold, 1: not finite (cap), 2: silence (floor)
+    __shared__ double row_thr;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const size_t N = (size_t)gridDim.x * Tf;
+    const int frames = row_frames(rows, b, Tf);
+    StageCounts caps; caps.rows = nq_rows;
+    const int cap = stage_count(caps, 0, b, nq);
+    const int lo = min_nq < 0 ? 0 : (min_nq > cap ? cap : min_nq);
+    if (tid == 0) {
+        const double* E = row_err + (size_t)b * (nq + 1);
+        bool finite = true;
+        for (int i = 0; i <= cap; ++i) finite = finite && isfinite(E[i]);
+        row_kind = !finite ? 1 : (E[0] == 0.0 ? 2 : 0);
+        row_thr = finite ? E[0] * ratio[b] : 0.0;
+    }
+    __syncthreads();
+    const int kind = row_kind;
+    const double thr = row_thr, F = (double)frames;
+    double s = 0.0;
+    int ksum = 0, kmax = 0;
+    for (int t = tid; t < Tf; t += 256) {
+        int k = 0;
+        if (t < frames) {
+            const float* e = err + (size_t)b * Tf + t;          // e[i * N]: the frame's error after i stages
+            if (kind == 1) k = cap;
+            else if (kind == 2) k = lo;
+            else k = rate_pick_scan(lo, cap, [&](int i) { return e[(size_t)i * N]; }, [&](float ei) { return (double)ei * F <= thr; });
+            s = s + (double)e[(size_t)k * N];
+            ksum += k;
+            kmax = k > kmax ? k : kmax;
+        }
+        n_q_frames[(size_t)b * Tf + t] = k;
+    }
+    red[tid] = s; redk[tid] = ksum; redm[tid] = kmax;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (tid < o) {
+            red[tid] = red[tid] + red[tid + o];
+            redk[tid] = redk[tid] + redk[tid + o];
+            redm[tid] = redm[tid] > redm[tid + o] ? redm[tid] : redm[tid + o];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    if (n_q_rows_out) n_q_rows_out[b] = redm[0];
+    if (n_codes_out) n_codes_out[b] = redk[0];
+    if (achieved) achieved[b] = red[0];
 }
 
-hipError_t launch_rvq_rate_zero_codes(int64_t* codes, int N, int Tf, int nq, const int* k_table, hipStream_t st) {
+hipError_t launch_rvq_rate_frames(const float* err, const double* row_err, int B, int Tf, int nq, const int* nq_rows, const RagLen& rows,
+                                  const double* ratio, int min_nq, int32_t* n_q_frames, int32_t* n_q_rows_out, int32_t* n_codes_out, double* achieved,
+                                  hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (Tf <= 0 || nq < 1 || !err || !row_err || !ratio || !n_q_frames) return hipErrorInvalidValue;
+    if ((long long)Tf * nq > 0x7fffffffLL) return hipErrorInvalidValue;        // n_codes_rows is an i32
+    hipLaunchKernelGGL(rvq_rate_frames_kernel, dim3(B), dim3(256), 0, st, err, row_err, Tf, nq, nq_rows, rows, ratio, min_nq, n_q_frames, n_q_rows_out,
+                       n_codes_out, achieved);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void rvq_rate_zero_codes_kernel(int64_t* __restrict__ codes, int N, int Tf, StageCounts k) {
+    const int n = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (n < N && i >= stage_count(k, n, n / Tf, gridDim.y)) codes[(size_t)i * N + n] = 0;
+}
+
+hipError_t launch_rvq_rate_zero_codes(int64_t* codes, int N, int Tf, int nq, const StageCounts& k, hipStream_t st) {
     if (N <= 0) return hipSuccess;
-    if (Tf <= 0 || N % Tf != 0 || nq < 1 || !k_table) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rvq_rate_zero_codes_kernel, dim3((N + 255) / 256, nq), dim3(256), 0, st, codes, N, Tf, k_table);
+    if (Tf <= 0 || N % Tf != 0 || nq < 1 || nq > 65535 || !(k.rows || k.frames)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rvq_rate_zero_codes_kernel, dim3((N + 255) / 256, nq), dim3(256), 0, st, codes, N, Tf, k);
     return hipGetLastError();
 }
 

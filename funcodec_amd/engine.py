@@ -139,16 +139,35 @@ def rate_targets(arch, target, B: int) -> list:
     return out
 
 
-def rate_min_nq(arch, min_n_q, cap: Optional[int] = None, rows=None) -> int:
-    """A checked ``min_n_q``: an integer in [1, cap] (cap: ``num_quantizers`` unless given) and no larger than any per-row cap."""
+def rate_min_nq(arch, min_n_q, cap: Optional[int] = None, rows=None, floor: int = 1) -> int:
+    """A checked ``min_n_q``: an integer in [floor, cap] (cap: ``num_quantizers`` unless given) and no larger than any per-row cap.
+    floor: 1 for the row rule; 0 for frame mode (``per_frame=True``), where a frame may take no stage at all."""
     cap = arch.num_quantizers if cap is None else int(cap)
-    if isinstance(min_n_q, bool) or not isinstance(min_n_q, numbers.Integral) or not 1 <= int(min_n_q) <= cap:
-        raise EngineError(f"min_n_q lies in [1, {cap}], got {min_n_q!r}")
+    if isinstance(min_n_q, bool) or not isinstance(min_n_q, numbers.Integral) or not floor <= int(min_n_q) <= cap:
+        raise EngineError(f"min_n_q lies in [{floor}, {cap}]{'' if floor else ' with per_frame'}, got {min_n_q!r}")
     if rows is not None:
         for b, k in enumerate(rows):
             if int(min_n_q) > k:
                 raise EngineError(f"min_n_q = {int(min_n_q)} lies above the cap of row {b} ({k} stages)")
     return int(min_n_q)
+
+
+def rate_min_nq_frames(arch, min_n_q, cap: Optional[int] = None, rows=None) -> int:
+    """A checked ``min_n_q`` of frame mode (``per_frame=True``): an integer in [0, cap] (cap: ``num_quantizers`` unless given) and no
+    larger than any per-row cap -- a frame may take no stage at all."""
+    return rate_min_nq(arch, min_n_q, cap, rows, floor=0)
+
+
+def _pick_scan(e, lo: int, cap: int, meets) -> int:
+    """The scan of both picks: the smallest k in [lo, cap] with meets(e[k]); no such k: the k in that range with the smallest e[k], first
+    on ties."""
+    best = lo
+    for k in range(lo, cap + 1):
+        if meets(e[k]):
+            return k
+        if e[k] < e[best]:
+            best = k
+    return best
 
 
 def rate_pick(E, ratio: float, min_n_q: int, cap: int) -> int:
@@ -165,30 +184,11 @@ def rate_pick(E, ratio: float, min_n_q: int, cap: int) -> int:
     if E[0] == 0.0:
         return lo
     thr = float(np.float64(E[0]) * np.float64(ratio))
-    best = lo
-    for k in range(lo, cap + 1):
-        if E[k] <= thr:
-            return k
-        if E[k] < E[best]:
-            best = k
-    return best
-
-
-def rate_min_nq_frames(arch, min_n_q, cap: Optional[int] = None, rows=None) -> int:
-    """A checked ``min_n_q`` of frame mode (``per_frame=True``): an integer in [0, cap] (cap: ``num_quantizers`` unless given) and no
-    larger than any per-row cap -- a frame may take no stage at all."""
-    cap = arch.num_quantizers if cap is None else int(cap)
-    if isinstance(min_n_q, bool) or not isinstance(min_n_q, numbers.Integral) or not 0 <= int(min_n_q) <= cap:
-        raise EngineError(f"min_n_q lies in [0, {cap}] with per_frame, got {min_n_q!r}")
-    if rows is not None:
-        for b, k in enumerate(rows):
-            if int(min_n_q) > k:
-                raise EngineError(f"min_n_q = {int(min_n_q)} lies above the cap of row {b} ({k} stages)")
-    return int(min_n_q)
+    return _pick_scan(E, lo, cap, lambda v: v <= thr)
 
 
 def rate_pick_frames(err, E, ratio: float, min_n_q: int, cap: int, frames: Optional[int] = None):
-    """The stage counts of one row's frames (csrc/rvq_frame_rate_kernels.h, include/funcodec_amd.h), a pure function of its float32
+    """The stage counts of one row's frames (csrc/rvq_rate_kernels.h, include/funcodec_amd.h), a pure function of its float32
     stage errors err[0 .. cap][t] (err[k][t]: frame t's residual energy after k stages), its float64 row errors E[0 .. cap], its ratio
     10^(-target / 10), the floor in [0, cap], the cap and its own frame count (default: all of err's):
       - row energies that are not all finite: every frame takes cap;
@@ -211,14 +211,7 @@ def rate_pick_frames(err, E, ratio: float, min_n_q: int, cap: int, frames: Optio
         return out
     thr = np.float64(Ev[0]) * np.float64(ratio)
     for t in range(F):
-        best, hit = lo, -1
-        for k in range(lo, cap + 1):
-            if np.float64(err[k, t]) * np.float64(F) <= thr:
-                hit = k
-                break
-            if err[k, t] < err[best, t]:
-                best = k
-        out[t] = hit if hit >= 0 else best
+        out[t] = _pick_scan(err[:, t], lo, cap, lambda v: np.float64(v) * np.float64(F) <= thr)
     return out
 
 
@@ -497,7 +490,7 @@ class CodecEngine:
             return None, 1
         if isinstance(target_snr_db, _Ratios):
             return target_snr_db, min_n_q
-        floor = (rate_min_nq_frames if per_frame else rate_min_nq)(self.arch, min_n_q, n_q, n_q_rows)
+        floor = rate_min_nq(self.arch, min_n_q, n_q, n_q_rows, floor=0 if per_frame else 1)
         return _Ratios(rate_targets(self.arch, target_snr_db, B)), floor
 
     @contextlib.contextmanager
@@ -560,6 +553,43 @@ class CodecEngine:
             return {}
         return dict(n_q_rows=0, row_errors=0, stage_errors=1, **(dict(n_q_frames=0, n_codes_rows=0, achieved_errors=0) if per_frame else {}))
 
+    def _encode(self, decode: bool, wav, n_q, use_scale, want_sub_quants, want_enc_out, lengths, n_q_rows, target_snr_db, min_n_q,
+                want_stage_errors, per_frame):
+        """encode (fc_encode / fc_encode_ragged; the dict holds enc_out) or, with decode, encode_decode (fc_encode_decode / its ragged
+        sibling; the dict holds recon)."""
+        if n_q_rows is not None:                       # refused as a whole before anything reaches the device
+            n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
+        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows, per_frame)
+        wav = self._wav_in(wav)
+        B, T = wav.shape[0], wav.shape[-1]
+        if lengths is not None:
+            lengths = self._lengths_in(lengths, B)
+        last = "recon" if decode else "enc_out"
+        if B > self.micro_batch:
+            parts = [self._encode(decode, wav[i:i + self.micro_batch], n_q, use_scale, want_sub_quants, want_enc_out,
+                                  None if lengths is None else lengths[i:i + self.micro_batch],
+                                  None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
+                                  None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors, per_frame)
+                     for i in range(0, B, self.micro_batch)]
+            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, **{last: 0}, **self._rate_dims(ratios, per_frame)))
+        Tf, D = self.frames(T), self.arch.dimension
+        dev = self.device
+        codes = torch.empty((n_q, B, Tf), dtype=torch.int64, device=dev)
+        quant = torch.empty((B, Tf, D), dtype=torch.float32, device=dev)
+        subq = torch.empty((n_q, B, self.arch.codebook_dim, Tf), dtype=torch.float32, device=dev) if want_sub_quants else None
+        scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
+        if decode:
+            out = torch.empty((B, self.channels, min(T, self.decoded_samples(Tf))), dtype=torch.float32, device=dev)   # like recon[:, :, :T] of the reference
+        else:
+            out = torch.empty((B, Tf, D), dtype=torch.float32, device=dev) if want_enc_out else None
+        ws = self._workspace(B, T, lengths is not None)
+        fn = getattr(self.lib, ("fc_encode_decode" if decode else "fc_encode") + ("_ragged" if lengths is not None else ""))
+        args = [_ptr(wav)] + ([_ptr(lengths)] if lengths is not None else []) + [B, T, n_q] + ([int(use_scale)] if decode else [])
+        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors, per_frame) as rate:
+            self._check(fn(self._h, *args, _ptr(codes), _ptr(quant), _ptr(subq), _ptr(scale), _ptr(out), _ptr(ws), ws.numel(), self._stream()))
+        return dict(codes=codes, quantized=quant, sub_quants=subq, scale=None if scale is None else scale.view(B, 1), **{last: out},
+                    **(rate or {}))
+
     @_on_device
     def encode(self, wav: torch.Tensor, n_q: int, want_sub_quants: bool = True, want_enc_out: bool = False, lengths=None, n_q_rows=None,
                target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False, per_frame: bool = False):
@@ -570,74 +600,16 @@ class CodecEngine:
         per_frame (with target_snr_db): a count per FRAME (rate_pick_frames; min_n_q in [0, cap]): frame (b, t) is what the call
         with n_q = n_q_frames[b, t] gives it; the dict also holds n_q_frames [B, Tf] i32, n_codes_rows [B] i32 and achieved_errors [B] f64,
         and n_q_rows is every row's largest frame count."""
-        if n_q_rows is not None:                       # refused as a whole before anything reaches the device
-            n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
-        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows, per_frame)
-        wav = self._wav_in(wav)
-        B, T = wav.shape[0], wav.shape[-1]
-        if lengths is not None:
-            lengths = self._lengths_in(lengths, B)
-        if B > self.micro_batch:
-            parts = [self.encode(wav[i:i + self.micro_batch], n_q, want_sub_quants, want_enc_out,
-                                 None if lengths is None else lengths[i:i + self.micro_batch],
-                                 None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
-                                 None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors, per_frame)
-                     for i in range(0, B, self.micro_batch)]
-            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, enc_out=0, **self._rate_dims(ratios, per_frame)))
-        Tf, D = self.frames(T), self.arch.dimension
-        dev = self.device
-        codes = torch.empty((n_q, B, Tf), dtype=torch.int64, device=dev)
-        quant = torch.empty((B, Tf, D), dtype=torch.float32, device=dev)
-        subq = torch.empty((n_q, B, self.arch.codebook_dim, Tf), dtype=torch.float32, device=dev) if want_sub_quants else None
-        scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
-        enc = torch.empty((B, Tf, D), dtype=torch.float32, device=dev) if want_enc_out else None
-        ws = self._workspace(B, T, lengths is not None)
-        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors, per_frame) as rate:
-            if lengths is not None:
-                self._check(self.lib.fc_encode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq),
-                                                      _ptr(scale), _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
-            else:
-                self._check(self.lib.fc_encode(self._h, _ptr(wav), B, T, n_q, _ptr(codes), _ptr(quant), _ptr(subq), _ptr(scale),
-                                               _ptr(enc), _ptr(ws), ws.numel(), self._stream()))
-        return dict(codes=codes, quantized=quant, sub_quants=subq,
-                    scale=None if scale is None else scale.view(B, 1), enc_out=enc, **(rate or {}))
+        return self._encode(False, wav, n_q, True, want_sub_quants, want_enc_out, lengths, n_q_rows, target_snr_db, min_n_q, want_stage_errors,
+                            per_frame)
 
     @_on_device
     def encode_decode(self, wav: torch.Tensor, n_q: int, use_scale: bool = True, want_sub_quants: bool = True, lengths=None, n_q_rows=None,
                       target_snr_db=None, min_n_q: int = 1, want_stage_errors: bool = False, per_frame: bool = False):
         """encode + decode in one enqueue; target_snr_db, min_n_q, want_stage_errors, per_frame: as for encode (the reconstruction is made
         from the chosen counts)."""
-        if n_q_rows is not None:                       # refused as a whole before anything reaches the device
-            n_q_rows = row_nq_list(self.arch, n_q_rows, wav.shape[0], n_q)
-        ratios, min_n_q = self._rate_in(target_snr_db, min_n_q, wav.shape[0], n_q, n_q_rows, per_frame)
-        wav = self._wav_in(wav)
-        B, T = wav.shape[0], wav.shape[-1]
-        if lengths is not None:
-            lengths = self._lengths_in(lengths, B)
-        if B > self.micro_batch:
-            parts = [self.encode_decode(wav[i:i + self.micro_batch], n_q, use_scale, want_sub_quants,
-                                        None if lengths is None else lengths[i:i + self.micro_batch],
-                                        None if n_q_rows is None else n_q_rows[i:i + self.micro_batch],
-                                        None if ratios is None else ratios[i:i + self.micro_batch], min_n_q, want_stage_errors, per_frame)
-                     for i in range(0, B, self.micro_batch)]
-            return self._cat(parts, dict(codes=1, quantized=0, sub_quants=1, scale=0, recon=0, **self._rate_dims(ratios, per_frame)))
-        Tf, D = self.frames(T), self.arch.dimension
-        dev = self.device
-        codes = torch.empty((n_q, B, Tf), dtype=torch.int64, device=dev)
-        quant = torch.empty((B, Tf, D), dtype=torch.float32, device=dev)
-        subq = torch.empty((n_q, B, self.arch.codebook_dim, Tf), dtype=torch.float32, device=dev) if want_sub_quants else None
-        scale = torch.empty((B,), dtype=torch.float32, device=dev) if self.arch.audio_normalize else None
-        recon = torch.empty((B, self.channels, min(T, self.decoded_samples(Tf))), dtype=torch.float32, device=dev)   # like recon[:, :, :T] of the reference
-        ws = self._workspace(B, T, lengths is not None)
-        with self._row_nq(n_q_rows), self._rate(ratios, min_n_q, n_q, Tf, want_stage_errors, per_frame) as rate:
-            if lengths is not None:
-                self._check(self.lib.fc_encode_decode_ragged(self._h, _ptr(wav), _ptr(lengths), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
-                                                             _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
-            else:
-                self._check(self.lib.fc_encode_decode(self._h, _ptr(wav), B, T, n_q, int(use_scale), _ptr(codes), _ptr(quant),
-                                                      _ptr(subq), _ptr(scale), _ptr(recon), _ptr(ws), ws.numel(), self._stream()))
-        return dict(codes=codes, quantized=quant, sub_quants=subq,
-                    scale=None if scale is None else scale.view(B, 1), recon=recon, **(rate or {}))
+        return self._encode(True, wav, n_q, use_scale, want_sub_quants, False, lengths, n_q_rows, target_snr_db, min_n_q, want_stage_errors,
+                            per_frame)
 
     @_on_device
     def decode_codes(self, tokens: torch.Tensor, lengths=None, n_q_rows=None, n_q_frames=None):

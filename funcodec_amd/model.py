@@ -162,7 +162,7 @@ class EncodecMI355X:
         counts go from the device tensor into the packer, nothing is read back).  ``engine.packets_to_host`` cuts them into bytes and
         ``inference_decoding_packed`` decodes them.  Everything else the call returns, and launches, is unchanged.
         per_frame=True (with ``target_snr_db``): a stage count per FRAME (``engine.rate_pick_frames`` states the rule; csrc/
-        rvq_frame_rate_kernels.h): frame (b, t) takes the fewest stages in [min_n_q, its row's cap] that bring it down to the row's noise
+        rvq_rate_kernels.h): frame (b, t) takes the fewest stages in [min_n_q, its row's cap] that bring it down to the row's noise
         floor, min_n_q in [0, cap] (0: a frame may take no stage).  The dict gains ``n_q_frames`` [B, Tf] int32, ``n_q_rows`` (every
         row's largest frame count), ``n_codes_rows`` [B] int32 (the sum of its frame counts) and ``row_snr_db`` (achieved: 10 log10(E[0] /
         sum_t err[k_t])); ``packets`` are then of mode 1 and carry the counts.  It composes with ``speech_lengths``, a per-row ``bit_width``

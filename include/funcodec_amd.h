@@ -274,14 +274,14 @@ int fc_engine_set_rate(fc_engine* e, const double* ratio_rows /* host [B] or NUL
 int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, int64_t* codes, float* quantized, void* stream);
 
 /* ---- a stage count per FRAME by target SNR (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
- * csrc/rvq_frame_rate_kernels.h states the rule and funcodec_amd/engine.py::rate_pick_frames restates it on the host: with the stage
+ * csrc/rvq_rate_kernels.h states the frame rule and funcodec_amd/engine.py::rate_pick_frames restates it on the host: with the stage
  * errors and the fp64 row sums above, thr_b = E_b[0] * rho_b, and frame t of row b takes the smallest k in [min_nq, cap_b] with
  * (double)err[k][b,t] * (double)F_b <= thr_b (F_b: the row's own frame count), else the k with the smallest err[k][b,t], first on ties;
  * a row that is not finite takes cap_b in every frame, a silent row min_nq; frames behind a row's frames take 0.  Every frame is
  * quantised down to the row's constant noise floor thr_b / F_b (reverse water-filling).  Frame (b,t) of codes, quantized, sub_quants, the
  * decoder's input and the reconstruction is what the call with n_q = k_t gives that frame (greedy: bit for bit; with a search: the first
  * k_t codes of the full-depth path); codes[k_t:] and sub_quants[k_t:] of the frame are 0, and a frame with k_t = 0 has quantized 0. */
-/* By the rule of csrc/rvq_frame_rate_kernels.h: given AFTER fc_engine_set_rate, it turns the rate set there into frame mode for the
+/* By the frame rule of csrc/rvq_rate_kernels.h: given AFTER fc_engine_set_rate, it turns the rate set there into frame mode for the
  * offline calls that follow (fc_encode, fc_encode_decode, their _ragged siblings, the 2-D FreqCodec encode, fc_rvq_encode_rate); cleared
  * with the rate (NULL ratios), and by every new fc_engine_set_rate.  min_nq in [0, num_quantizers] replaces the floor given there: a
  * frame may take no stage.  n_q_rows_out of fc_engine_set_rate then receives every row's LARGEST frame count.
@@ -292,7 +292,7 @@ int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, 
  * by name while it is set, as for the row rate. */
 int fc_engine_set_rate_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out /* dev [B][Tf] */, int32_t* n_codes_rows_out /* dev [B] or NULL */,
                               double* achieved_out /* dev [B] or NULL */, void* stream);
-/* By the rule of csrc/rvq_frame_rate_kernels.h (the per-frame decode): a stage count per frame for the fc_decode_codes and
+/* By the count of csrc/rvq_rate_kernels.h (a count per frame): a stage count per frame for the fc_decode_codes and
  * fc_decode_codes_ragged calls that follow; frame (b,t) sums its first n_q_frames[b][t] codes (clamped to [0, n_q]); the codes behind a
  * frame's count are not read and never raise FC_STATUS_BAD_CODE.  The pointer is BORROWED: it is read by the launches of those calls and
  * must stay valid until they have run; NULL clears the table.  Refused: together with a row table (fc_engine_set_row_nq); a decode call

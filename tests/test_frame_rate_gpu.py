@@ -1,5 +1,5 @@
 """A stage count per FRAME chosen on the device by a target SNR (fc_engine_set_rate_frames, fc_engine_set_frame_nq; csrc/
-rvq_frame_rate_kernels.h states the rule) on the MI355X: the pick against ``rate_pick_frames`` of the device's own errors, the row
+rvq_rate_kernels.h states the rule) on the MI355X: the pick against ``rate_pick_frames`` of the device's own errors, the row
 outputs against float64 numpy, every frame against today's call with its count, and the decode with a count per frame.  Comparisons
 are exact unless said otherwise."""
 import numpy as np

@@ -113,14 +113,14 @@ def test_symbols_are_exported_declared_and_bound():
     for name, nargs in NEW.items():
         assert hasattr(lib, name) and name in _lib.SYMBOLS and len(_lib.SYMBOLS[name][1]) == nargs, name
         m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int " + name + r"\(", text, re.S)
-        assert m and "csrc/rvq_frame_rate_kernels.h" in m.group(1), name       # each entry states the rule by reference to the kernel header
+        assert m and "csrc/rvq_rate_kernels.h" in m.group(1), name       # each entry states the rule by reference to the kernel header
     assert re.search(r"#define\s+FC_ABI_VERSION\s+7\b", text) and _lib.FC_ABI_VERSION == 7 and lib.fc_abi_version() == 7
-    with open(os.path.join(ROOT, "funcodec_amd", "csrc", "rvq_frame_rate_kernels.h")) as f:
+    with open(os.path.join(ROOT, "funcodec_amd", "csrc", "rvq_rate_kernels.h")) as f:
         rule = f.read()
     for word in ("thr_b = E_b[0] * rho_b", "no division", "first on ties", "reverse water-filling", "clamped to [0, nq]"):
         assert word in rule, word
     from funcodec_amd import build
-    assert "rvq_frame_rate_kernels.hip" in build.sources() and "rvq_frame_rate_kernels.h" in build.HEADERS
+    assert "rvq_rate_kernels.hip" in build.sources() and "rvq_rate_kernels.h" in build.HEADERS
     # a null engine is refused by name, nothing is touched
     assert lib.fc_engine_set_rate_frames(None, 0, None, None, None, None) != 0 and "engine" in _lib.last_error()
     assert lib.fc_engine_set_frame_nq(None, None, 1, 1, None) != 0 and "engine" in _lib.last_error()

@@ -1,4 +1,4 @@
-"""Measurements of the stage count per frame chosen by a target SNR (per_frame=True; csrc/rvq_frame_rate_kernels.h) and of the bit
+"""Measurements of the stage count per frame chosen by a target SNR (per_frame=True; csrc/rvq_rate_kernels.h) and of the bit
 stream's mode 1 (csrc/code_pack_kernels.h), written to profiles/frame_rate.txt:
 
   1. cost of the mode: the headline call (16 x 10 s, ds640, encode + 32 stages + decode) in frame mode against the row-mode target call

@@ -356,6 +356,16 @@ void probe(Ctx& cx, const Stack& S, int what, int layer, const float* src, size_
     cx.check(hipMemcpyAsync(g_probe.dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "probe");
 }
 
+// The attention of block b of stack S over one QKV buffer [B][3 d][T]: what run_stack_full launches, and fc_laura_attention (the per-op
+// test entry) with it.
+lk::AttnFull attn_full_args(const fc_laura* e, const Stack& S, const Block& b, const float* qkv, const int* lens, const int* bidir,
+                            int causal, float* ctx, int B, int T) {
+    lk::AttnFull a;
+    a.qkv = qkv; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.lens = lens; a.bidir = bidir; a.causal = causal; a.ctx = ctx;
+    a.B = B; a.H = S.s.heads; a.DK = S.s.d_model / S.s.heads; a.T = T; a.R = e->R; a.PR = e->PR;
+    return a;
+}
+
 // The stack on feature-major input [B][idim][T]; returns after_norm(x) [B][d][T].
 float* run_stack_full(fc_laura* e, Ctx& cx, const Stack& S, const float* in, int T, const int* lens, const int* bidir, int causal,
                       const KvOut* kv) {
@@ -384,10 +394,7 @@ float* run_stack_full(fc_laura* e, Ctx& cx, const Stack& S, const float* in, int
                                                kv->vc + (size_t)i * kv->layer_stride, cx.st), "kv store");
         else if (kv) cx.check(lk::launch_kv_store(qkv, lens, B, d, T, kv->Tcap, kv->kc + (size_t)i * kv->layer_stride + kv->row_base,
                                              kv->vc + (size_t)i * kv->layer_stride + kv->row_base, cx.st), "kv store");
-        lk::AttnFull a;
-        a.qkv = qkv; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.lens = lens; a.bidir = bidir; a.causal = causal; a.ctx = ctx;
-        a.B = B; a.H = S.s.heads; a.DK = d / S.s.heads; a.T = T; a.R = e->R; a.PR = e->PR;
-        cx.check(lk::launch_attn_full(a, cx.st), "attention");
+        cx.check(lk::launch_attn_full(attn_full_args(e, S, b, qkv, lens, bidir, causal, ctx, B, T), cx.st), "attention");
         probe(cx, S, 3, i, ctx, (size_t)B * d * T);
         cx.check(launch_lin_full(b.out, ctx, B, T, dl, cx.st), "out GEMM");
         cx.check(lk::launch_layernorm_fm(x, dl, x, b.n2g, b.n2b, 1e-12f, 0, 1.f, xn, B, d, T, cx.st), "LayerNorm");
@@ -615,6 +622,30 @@ lk::StepPersistArgs step_persist_args(const fc_laura* e, const StepMem& m, unsig
     return pa;
 }
 
+// One LM block of the kernel chain's decoding step on B rows, in place on xs: what run_step launches per block, and fc_laura_step_block
+// (the per-op test entry) with it.
+struct StepBlockBufs {
+    float *xs, *qb, *apart, *hb;        // [rows][d] residual stream (in / out), [rows][d] q, [rows][H][NS][DK + 2] partials, [rows][ff]
+    float *kc, *vc;                     // this block's caches [rows][d][Tcap], [rows][Tcap][d]
+    const int* pos;                     // device [rows]
+    int NS;
+};
+void run_step_block(fc_laura* e, Ctx& cx, const Block& b, const StepBlockBufs& m, int B, int Tcap, int wide, hipStream_t st) {
+    const Stack& S = e->codec_lm;
+    const int d = S.s.d_model, ff = S.s.ff, heads = S.s.heads, dkh = d / S.s.heads;
+    cx.check(step_gemv(b.qkv, m.xs, B, b.n1g, b.n1b, 1e-12f, 0, 2, m.qb, d, st, m.kc, m.vc, m.pos, d, Tcap, nullptr, 0, 0, 0, 0, wide), "QKV GEMV");
+    lk::AttnStep a;
+    a.q = m.qb; a.kc = m.kc; a.vc = m.vc; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.pos = m.pos; a.part = m.apart; a.NS = m.NS;
+    a.B = B; a.H = heads; a.DK = dkh; a.Tcap = Tcap; a.R = e->R; a.PR = e->PR;
+    cx.check(lk::launch_attn_step(a, st), "step attention");
+    // linear_out reads the key-range partials and combines them while staging its input
+    cx.check(step_gemv(b.out, nullptr, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, m.apart, heads, dkh, m.NS, 0, wide), "out GEMV");
+    cx.check(step_gemv(b.ff1, m.xs, B, b.n2g, b.n2b, 1e-12f, S.s.act, 0, m.hb, ff, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
+             "FFN GEMV 1");
+    cx.check(step_gemv(b.ff2, m.hb, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
+             "FFN GEMV 2");
+}
+
 // One decoding step: the newest token of every row through the LM against its KV cache, then the sampler.  Every kernel reads its
 // positions from device memory, so the launch sequence is identical from step to step.  pa null: the kernel chain.
 // q (a queued session): the refill phase first -- ended slots retire, free slots claim waiting tickets and draw their first sample.
@@ -628,7 +659,7 @@ void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs*
     const int SB = m.B, B = rows > 0 ? rows : m.B, wide = rows > 0 ? 1 : 0;
     lk::Sample sm = sm0;
     if (rows > 0) { sm.row0 = 0; sm.nrows = rows; }
-    const int d = S.s.d_model, ff = S.s.ff, NL = S.s.layers, V = e->vocab(), Tcap = m.Tcap, heads = S.s.heads, dkh = d / S.s.heads;
+    const int d = S.s.d_model, NL = S.s.layers, V = e->vocab(), Tcap = m.Tcap;
     if (q) {
         cx.check(lk::launch_queue_phase(*q, 1, st), "queue phase");
         lk::Sample first = sm;
@@ -640,22 +671,9 @@ void run_step(fc_laura* e, Ctx& cx, const StepMem& m, const lk::StepPersistArgs*
         cx.check(lk::launch_sample(sm, st), "sampling");
         return;
     }
-    for (int i = 0; i < NL; ++i) {
-        const Block& b = S.blocks[i];
-        float* kc = m.kc + (size_t)i * SB * d * Tcap;
-        float* vc = m.vc + (size_t)i * SB * d * Tcap;
-        cx.check(step_gemv(b.qkv, m.xs, B, b.n1g, b.n1b, 1e-12f, 0, 2, m.qb, d, st, kc, vc, m.pos, d, Tcap, nullptr, 0, 0, 0, 0, wide), "QKV GEMV");
-        lk::AttnStep a;
-        a.q = m.qb; a.kc = kc; a.vc = vc; a.ptab = b.ptab; a.bias_u = b.bu; a.bias_v = b.bv; a.pos = m.pos; a.part = m.apart; a.NS = m.NS;
-        a.B = B; a.H = heads; a.DK = dkh; a.Tcap = Tcap; a.R = e->R; a.PR = e->PR;
-        cx.check(lk::launch_attn_step(a, st), "step attention");
-        // linear_out reads the key-range partials and combines them while staging its input
-        cx.check(step_gemv(b.out, nullptr, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, m.apart, heads, dkh, m.NS, 0, wide), "out GEMV");
-        cx.check(step_gemv(b.ff1, m.xs, B, b.n2g, b.n2b, 1e-12f, S.s.act, 0, m.hb, ff, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
-                 "FFN GEMV 1");
-        cx.check(step_gemv(b.ff2, m.hb, B, nullptr, nullptr, 0.f, 0, 1, m.xs, d, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
-                 "FFN GEMV 2");
-    }
+    for (int i = 0; i < NL; ++i)
+        run_step_block(e, cx, S.blocks[i], StepBlockBufs{m.xs, m.qb, m.apart, m.hb, m.kc + (size_t)i * SB * d * Tcap,
+                                                         m.vc + (size_t)i * SB * d * Tcap, m.pos, m.NS}, B, Tcap, wide, st);
     cx.check(step_gemv(e->lm_decoder, m.xs, B, S.ag, S.ab, 1e-12f, 0, 0, m.lg, V, st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, wide),
              "decoder GEMV");
     cx.check(lk::launch_sample(sm, st), "sampling");
@@ -2043,6 +2061,60 @@ int fc_laura_linear(fc_laura* e, const char* name, const float* x, int B, int T,
     cx.check(lk::launch_tm_to_fm(x, nullptr, B, T, L.cin, Tp, in, cx.st), "transpose");
     cx.check(launch_lin_full(L, in, B, Tp, o, cx.st), "GEMM");
     cx.check(lk::launch_fm_to_tm(o, nullptr, B, L.cout, Tp, T, y, cx.st), "transpose");
+    return cx.err;
+}
+
+int fc_laura_attention(fc_laura* e, int stack, int layer, const float* qkv, const int32_t* lens, const int32_t* bidir, int causal, int B,
+                       int T, float* ctx, void* workspace, size_t workspace_bytes, void* stream) {
+    if (check_ready(e)) return 1;
+    if (!qkv || !lens || !ctx || !workspace || B < 1 || T < 1) return fail("bad argument");
+    if (stack < 0 || stack > 2) return fail("stack must be 0 (text_encoder), 1 (codec_lm) or 2 (codec_encoder)");
+    const Stack& S = stack == 0 ? e->text_encoder : stack == 1 ? e->codec_lm : e->codec_encoder;
+    if (layer < 0 || layer >= S.s.layers) return fail("no such block in " + S.prefix);
+    if (T > e->R) return fail("sequence longer than max_positions");
+    if (check_lens(lens, B, 1, T, "lens") || (bidir && check_lens(bidir, B, 0, T, "bidir"))) return 1;
+    const int d = S.s.d_model, Tp = pad4(T);
+    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    int* ld = upload_lens(cx, lens, B);
+    int* bd = bidir ? upload_lens(cx, bidir, B) : nullptr;
+    float* in = cx.alloc<float>((size_t)B * 3 * d * Tp);
+    float* o = cx.alloc<float>((size_t)B * d * Tp);
+    if (!cx.live()) return 1;
+    // no length masking in the transposes: the caller decides every input value, and sees every output value
+    cx.check(lk::launch_tm_to_fm(qkv, nullptr, B, T, 3 * d, Tp, in, cx.st), "transpose");
+    cx.check(lk::launch_attn_full(attn_full_args(e, S, S.blocks[layer], in, ld, bd, causal ? 1 : 0, o, B, Tp), cx.st), "attention");
+    cx.check(lk::launch_fm_to_tm(o, nullptr, B, d, Tp, T, ctx, cx.st), "transpose");
+    return cx.err;
+}
+
+int fc_laura_step_block(fc_laura* e, int layer, float* x, float* k_cache, float* v_cache, const int32_t* pos, int B, int Tcap,
+                        int key_ranges, int wide, float* q_out, float* part_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (check_ready(e)) return 1;
+    if (!x || !k_cache || !v_cache || !pos || !q_out || !part_out || !workspace) return fail("bad argument");
+    const Stack& S = e->codec_lm;
+    if (layer < 0 || layer >= S.s.layers) return fail("no such block in " + S.prefix);
+    if (B < 1 || B > 64) return fail("a decoding step has 1 .. 64 rows");
+    if (wide && B > 16) wide = 0;                 // beyond 16 rows the launches are over column blocks anyway
+    if (Tcap < 4 || Tcap % 4) return fail("the cache capacity must be a multiple of 4");
+    if (check_lens(pos, B, 0, std::min(Tcap, e->R) - 1, "pos")) return 1;
+    const int d = S.s.d_model, heads = S.s.heads, dkh = d / heads;
+    const int NS = key_ranges;
+    if (NS < 1 || NS > 8) return fail("key_ranges must be 1 .. 8");
+    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    const size_t RW = (size_t)step_rows(B);
+    int* pd = upload_lens(cx, pos, B);
+    StepBlockBufs m{};
+    m.xs = cx.alloc<float>(RW * d);
+    m.qb = cx.alloc<float>(RW * d);
+    m.apart = cx.alloc<float>(RW * heads * 8 * (dkh + 2));
+    m.hb = cx.alloc<float>(RW * S.s.ff);
+    m.kc = k_cache; m.vc = v_cache; m.pos = pd; m.NS = NS;
+    if (!cx.live()) return 1;
+    cx.check(hipMemcpyAsync(m.xs, x, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "copy in");
+    run_step_block(e, cx, S.blocks[layer], m, B, Tcap, wide ? 1 : 0, cx.st);
+    cx.check(hipMemcpyAsync(x, m.xs, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "copy out");
+    cx.check(hipMemcpyAsync(q_out, m.qb, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "copy out");
+    cx.check(hipMemcpyAsync(part_out, m.apart, (size_t)B * heads * NS * (dkh + 2) * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "copy out");
     return cx.err;
 }
 

@@ -655,9 +655,10 @@ __global__ __launch_bounds__(64 * KS) void gemv_kernel(GemvArgs a) {
     const int epos = a.mode == 2 ? a.pos[eb] : 0;
     if (a.apart) {
         // x[b][h * DK + dd] = combination of the NS key-range partials of head h (flash-decoding): o_s, running max m_s, sum l_s.
-        // First the B * H * NS normalised weights exp(m_s - M) / L (one thread per (b, h); red[] is free until the reduction)
+        // First the B * H * NS normalised weights exp(m_s - M) / L (one thread per (b, h)), in LDS of their own: B * H * 8 floats do not
+        // fit the reduction scratch at every accepted width (d_model 320 with 10 heads: KS = 4, 1024 floats, 16 rows need 1280)
         const int PS = a.DK + 2;
-        float* wn = red;
+        float* wn = red + KS * 256;                    // [B * H][8], behind the reduction scratch (gemv_lds_bytes)
         // NS <= 8 key ranges; every loop below runs its 8 trips with clamped indices so that the loads are unconditional and
         // independent (a run-time trip count made each partial its own serialised round trip: 11 us instead of 5 for this kernel)
         for (int e = tid; e < B * a.H; e += 64 * KS) {
@@ -696,7 +697,6 @@ __global__ __launch_bounds__(64 * KS) void gemv_kernel(GemvArgs a) {
             Xs[b * XS + k] = o;
         }
         for (int k = tid; k < K; k += 64 * KS) Xs[B * XS + k] = 0.f;
-        __syncthreads();                               // wn (= red) is reused by the reduction below
     } else {
         for (int e = tid * 4; e < (B + 1) * K; e += 64 * KS * 4) {
             const int b = e / K, k = e - b * K;
@@ -874,7 +874,10 @@ __global__ __launch_bounds__(64 * KS) void gemv_win_kernel(GemvArgs a) {
 }
 
 namespace {
-size_t gemv_lds_bytes(int B, int XS, int KS) { return ((size_t)(B + 1) * XS + (size_t)KS * 256) * sizeof(float); }
+// x rows + the zero row, the reduction scratch, and with attention partials (heads > 0) the 8 range weights of every (row, head)
+size_t gemv_lds_bytes(int B, int XS, int KS, int heads = 0) {
+    return ((size_t)(B + 1) * XS + (size_t)KS * 256 + (size_t)B * heads * 8) * sizeof(float);
+}
 
 hipError_t launch_gemv_windowed(const Gemv& g, GemvArgs a, int KS, dim3 grid, hipStream_t st) {
     if (g.gamma || g.apart || g.mode == 2) return hipErrorInvalidValue;       // whole-row prologues / the cache scatter: K <= d
@@ -927,12 +930,13 @@ hipError_t launch_gemv(const Gemv& g, hipStream_t st) {
                g.apart, g.H, g.DK, g.NS, 0, 0, 0};
     static const int ablate = fc::ab_knob("FC_GEMV_ABLATE", 0);
     a.ablate = ablate;
-    if (g.apart && (g.H * g.DK != g.K || g.NS < 1 || g.NS > 8 || rows * g.H * 8 > KS * 256)) return hipErrorInvalidValue;
+    if (g.apart && (g.H * g.DK != g.K || g.NS < 1 || g.NS > 8)) return hipErrorInvalidValue;
+    const int wn_heads = g.apart ? g.H : 0;
     const dim3 grid(ceil_div_h(g.N, 16), ceil_div_h(g.B, 16));      // tile x column block
     // one LDS stage whenever it fits at the largest batch (every K <= 2112: the path does not depend on B), windows beyond that
-    const bool one_stage = g.stage == 1 || (g.stage == 0 && gemv_lds_bytes(16, g.K + 4, KS) <= 160 * 1024);
+    const bool one_stage = g.stage == 1 || (g.stage == 0 && gemv_lds_bytes(16, g.K + 4, KS, wn_heads) <= 160 * 1024);
     if (!one_stage) return launch_gemv_windowed(g, a, KS, grid, st);
-    const size_t lds = gemv_lds_bytes(rows, a.XS, KS);
+    const size_t lds = gemv_lds_bytes(rows, a.XS, KS, wn_heads);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> d16[6][2], d8[6][2], d4[6][2], d2[6][2], d1[6][2];     // [.][1]: over column blocks
     const bool wide = grid.y > 1 || g.wide;

@@ -387,8 +387,69 @@ class LauraEngine:
         self._check(self.lib.fc_laura_linear(self._h, name.encode(), _ptr(x), B, T, form, _ptr(y), _ptr(ws), ws.numel(), self._stream()))
         return y
 
+    STACKS = ("text_encoder", "codec_lm", "codec_encoder")
 
-SLOT_STATES = {1: "running", 2: "done", 3: "failed"}       # fc_laura_slots_step's done_out; 0 = free (not reported)
+    @_on_device
+    def attention(self, stack: str, layer: int, qkv: torch.Tensor, lengths: Sequence[int], causal: bool = False,
+                  bidir: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """The full-sequence rel-pos attention of one block on the caller's q / k / v (per-op test entry): qkv [B, T, 3 d] token-major
+        with q | k | v along the feature axis -> the attention context [B, T, d] before linear_out.  Keys >= lengths[b] are masked;
+        with ``causal``, rows and keys below ``bidir[b]`` see each other.  Nothing is masked on the way in or out: values at
+        positions >= lengths[b] reach the kernel (keep them finite), and rows there come back as the kernel left them."""
+        if stack not in self.STACKS:
+            raise EngineError(f"attention: stack must be one of {self.STACKS}, got {stack!r}")
+        d = getattr(self.spec, stack).d_model
+        qkv = self._dev(qkv, torch.float32)
+        if qkv.dim() != 3 or qkv.shape[-1] != 3 * d:
+            raise EngineError(f"attention: qkv must be [B, T, {3 * d}], got {tuple(qkv.shape)}")
+        B, T = qkv.shape[0], qkv.shape[1]
+        lengths = list(lengths)
+        self._check_batch("attention", B, lengths=lengths, bidir=None if bidir is None else list(bidir))
+        lengths = self._check_lens("attention", "lengths", lengths, T, 1)
+        bd = None if bidir is None else self._check_lens("attention", "bidir", list(bidir), T)
+        ctx = torch.empty((B, T, d), dtype=torch.float32, device=self.device)
+        ws = self._grown(4 * B * (T + 8) * 4 * d + (1 << 20))
+        self._check(self.lib.fc_laura_attention(self._h, self.STACKS.index(stack), int(layer), _ptr(qkv), _i32(lengths),
+                                                None if bd is None else _i32(bd), int(bool(causal)), B, T, _ptr(ctx), _ptr(ws), ws.numel(),
+                                                self._stream()))
+        return ctx
+
+    @_on_device
+    def step_block(self, layer: int, x: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: Sequence[int],
+                   key_ranges: Optional[int] = None, wide: bool = False):
+        """One block of the LM as the kernel chain's decoding step runs it (per-op test entry), on B <= 64 rows: x [B, d], the block's
+        caches k_cache [B, d, Tcap] and v_cache [B, Tcap, d] in the engine's layouts, pos [B] the position of each row's new token
+        (keys 0 .. pos[b]).  ``key_ranges`` 1 .. 8 key ranges per (row, head), None: the engine's rule; ``wide``: the GEMV
+        instantiations over column blocks also at B <= 16.  Returns (new x [B, d], q [B, d], the raw partials
+        [B, heads, key_ranges, dk + 2] -- per range the unnormalised context, the running max, the sum of exponentials --, k_cache
+        and v_cache after the scatter at pos); the arguments are left unchanged."""
+        s = self.spec.codec_lm
+        d, H = s.d_model, s.heads
+        x = self._dev(x, torch.float32).clone()
+        kc = self._dev(k_cache, torch.float32).clone()
+        vc = self._dev(v_cache, torch.float32).clone()
+        if x.dim() != 2 or x.shape[1] != d or not 1 <= x.shape[0] <= 64:
+            raise EngineError(f"step_block: x must be [1 .. 64, {d}], got {tuple(x.shape)}")
+        B = x.shape[0]
+        if kc.dim() != 3 or tuple(kc.shape[:2]) != (B, d) or tuple(vc.shape) != (B, kc.shape[2], d):
+            raise EngineError(f"step_block: caches must be [{B}, {d}, Tcap] and [{B}, Tcap, {d}], got {tuple(kc.shape)} and {tuple(vc.shape)}")
+        Tcap = kc.shape[2]
+        pos = list(pos)
+        self._check_batch("step_block", B, pos=pos)
+        pos = self._check_lens("step_block", "pos", pos, min(Tcap, self.max_positions) - 1)
+        NS = max(1, min(8, 256 // (B * H))) if key_ranges is None else int(key_ranges)      # None: a decoding step's own split (alloc_step_mem)
+        if not 1 <= NS <= 8:
+            raise EngineError(f"step_block: key_ranges must be 1 .. 8, got {key_ranges}")
+        q = torch.empty((B, d), dtype=torch.float32, device=self.device)
+        part = torch.empty((B, H, NS, d // H + 2), dtype=torch.float32, device=self.device)
+        rows = 16 * ((B + 15) // 16)
+        ws = self._grown(4 * rows * (2 * d + H * 8 * (d // H + 2) + s.ff) + (1 << 20))
+        self._check(self.lib.fc_laura_step_block(self._h, int(layer), _ptr(x), _ptr(kc), _ptr(vc), _i32(pos), B, Tcap, NS, int(bool(wide)),
+                                                 _ptr(q), _ptr(part), _ptr(ws), ws.numel(), self._stream()))
+        return x, q, part, kc, vc
+
+
+SLOT_STATES ={1: "running", 2: "done", 3: "failed"}       # fc_laura_slots_step's done_out; 0 = free (not reported)
 
 
 class DecodeSlots:

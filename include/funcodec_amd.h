@@ -789,6 +789,28 @@ int fc_laura_codec_emb(fc_laura* e, const float* text_outs, const int32_t* text_
 int fc_laura_linear(fc_laura* e, const char* name, const float* x, int B, int T, int step_form, float* y,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* per-op entry points of the two attention forms (tests pin them against a float64 restatement); both run the launch code of the path.
+ *
+ * Full-sequence rel-pos attention of block `layer` of a stack (0 text_encoder / 1 codec_lm / 2 codec_encoder) on the caller's q / k / v:
+ *   qkv   dev f32 [B][T][3 d] token-major, q | k | v along the feature axis; transposed to the stack's feature-major layout at T padded
+ *         to 4 with NO length masking (every value reaches the kernel: rows >= lens[b] must be finite)
+ *   lens  host i32 [B] in [1, T]: keys >= lens[b] are masked;  bidir host i32 [B] or NULL: with causal, rows and keys < bidir[b] see each other
+ *   ctx   dev f32 [B][T][d]: the attention context before linear_out (rows >= lens[b]: whatever the kernel leaves, finite) */
+int fc_laura_attention(fc_laura* e, int stack, int layer, const float* qkv, const int32_t* lens, const int32_t* bidir, int causal, int B,
+                       int T, float* ctx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One block of the LM as the kernel chain's decoding step runs it, on 1 <= B <= 64 rows: QKV GEMV (LayerNorm prologue, cache scatter at
+ * pos[b]), step attention over keys 0 .. pos[b], linear_out GEMV (combines the key-range partials while staging) + residual, the two
+ * feed-forward GEMVs + residual.
+ *   x        dev f32 [B][d]: the residual stream, replaced by the block's output
+ *   k_cache  dev f32 [B][d][Tcap], v_cache dev f32 [B][Tcap][d]: this block's caches in the engine's layouts, column pos[b] is written
+ *   pos      host i32 [B] in [0, min(Tcap, max_positions))
+ *   key_ranges 1 .. 8 key ranges per (row, head); a decoding step of B rows takes 256 / (B * heads) clamped to 1 .. 8
+ *   wide     != 0 with B <= 16: the GEMV instantiations over column blocks (what an elastic session's cut launch runs)
+ *   q_out    dev f32 [B][d];  part_out dev f32 [B][heads][key_ranges][dk + 2]: per range the unnormalised context, running max, sum */
+int fc_laura_step_block(fc_laura* e, int layer, float* x, float* k_cache, float* v_cache, const int32_t* pos, int B, int Tcap,
+                        int key_ranges, int wide, float* q_out, float* part_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* debugging aid, not part of the path: the NEXT full-sequence stack runs of this thread copy one intermediate tensor (feature-major
  * [B][rows][T padded to 4]) to dev_dst.  stack 0 text_encoder / 1 codec_lm / 2 codec_encoder (-1 any); what 0 = stream after the input
  * layer, 1 = attention-norm output of block `layer`, 2 = its q/k/v, 3 = its attention context, 5 = residual stream at the entry of

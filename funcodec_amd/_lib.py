@@ -96,6 +96,10 @@ SYMBOLS = {
     # achieved), and a borrowed device table [B][Tf] for the decode_codes calls
     "fc_engine_set_rate_frames": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "fc_engine_set_frame_nq": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    # a stage count per push of a session by a noise floor (the push rule of csrc/rvq_rate_kernels.h): host float64 floors [B] (None
+    # clears), min_nq, the device count table [B]; then the form (chain, device outputs row_errors / stage_errors / sub_quants, host i32 [B] rows off)
+    "fc_engine_set_floor": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "fc_engine_set_floor_form": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     # the bit stream's mode 1 (csrc/code_pack_kernels.h): a count per frame; engine-free
     "fc_frame_packet_pitch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "fc_frame_packet_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_longlong, C.c_int]),

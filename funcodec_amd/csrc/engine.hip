@@ -186,6 +186,22 @@ struct fc_engine {
         bool on() const { return !ratio.empty(); }
         void clear_frames() { frames = false; nq_frames_out = nullptr; n_codes_out = nullptr; achieved_out = nullptr; }
     } rate;
+    // a stage count per row chosen on the device by a noise floor, for the encode pushes of sessions that follow (fc_engine_set_floor; the
+    // push rule of csrc/rvq_rate_kernels.h): the host copy of the floors (empty = none set) and their device copy, which only grows.  The
+    // count table is the caller's.  chain, row_err_out, stage_err_out: fc_engine_set_floor_form.
+    struct Floor {
+        std::vector<double> floor;
+        int min_nq = 1;
+        double* floor_dev = nullptr;
+        size_t cap = 0;
+        int32_t* n_q_out = nullptr;
+        bool chain = false;
+        double* row_err_out = nullptr;
+        float* stage_err_out = nullptr;
+        float* subq_out = nullptr;              // of the hook alone (a push has no sub_quants)
+        bool on() const { return !floor.empty(); }
+        void clear_form() { chain = false; row_err_out = nullptr; stage_err_out = nullptr; subq_out = nullptr; }
+    } floor;
     // a stage count per frame for the offline decode_codes calls that follow (fc_engine_set_frame_nq): the caller's device table, borrowed
     struct FrameNq { const int32_t* table = nullptr; int B = 0, Tf = 0; } frame_nq;
     bool lstm_persist_ok = true;             // cleared after a grid-barrier timeout: later calls take the per-step launch path
@@ -235,10 +251,13 @@ struct Session {
         const void* stream = nullptr;
         const void* nq_table = nullptr; int nq_rows = 0;      // per-row stage counts: null / 0 when none are set
         int rvq_beam = 1;                           // width of the quantiser's search (fc_engine_set_rvq_beam): more launches above 1
+        // the noise floor of an encode push (fc_engine_set_floor): its tables' addresses, min_nq and form; the floors themselves are device data
+        const void* floor_table = nullptr; const void* floor_out = nullptr; int floor_min = 0, floor_chain = 0;
         bool operator==(const GraphKey& o) const {
             return form == o.form && width == o.width && parity == o.parity && n_q == o.n_q && use_scale == o.use_scale && ptr == o.ptr && ws == o.ws &&
                    ws_bytes == o.ws_bytes && stream == o.stream && nq_table == o.nq_table && nq_rows == o.nq_rows &&
-                   rvq_beam == o.rvq_beam;
+                   rvq_beam == o.rvq_beam && floor_table == o.floor_table && floor_out == o.floor_out && floor_min == o.floor_min &&
+                   floor_chain == o.floor_chain;
         }
     };
     struct Graph { GraphKey key; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
@@ -1932,8 +1951,30 @@ int row_nq_check(const fc_engine* e, int rows, int n_q) {
 // ---- what a call is refused for while counts are set, checked BEFORE its first launch ------------------
 // An encode (`who`: the entry point) under the per-row table (fc_engine_set_row_nq) and the rate (fc_engine_set_rate, _frames).  An
 // offline call: as many rows as the rate has, and the floor no larger than n_q or any row's cap.  A session push takes no rate.
-int counts_check_encode(const fc_engine* e, const char* who, int B, int n_q, bool session) {
+// A noise floor (fc_engine_set_floor) is for the pushes (`floor_ok`: a session push, or the per-op hook): as many rows as the floor has, and
+// min_nq no larger than n_q or any row's cap.
+int counts_check_encode(const fc_engine* e, const char* who, int B, int n_q, bool session, bool floor_ok = false) {
     if (row_nq_check(e, B, n_q)) return 1;
+    if (e->floor.on()) {
+        const fc_engine::Floor& f = e->floor;
+        if (!(session || floor_ok))
+            return fail(std::string(who) + ": a noise floor is set (fc_engine_set_floor): a stage count per push by a noise floor is for session pushes only; "
+                        "clear it with NULL floors");
+        if (e->rate.on())
+            return fail(std::string(who) + ": a noise floor (fc_engine_set_floor) and a rate (fc_engine_set_rate) are both set; clear one of them");
+        if ((int)f.floor.size() != B)
+            return fail("a noise floor is set for " + std::to_string(f.floor.size()) + " rows (fc_engine_set_floor); this push has " + std::to_string(B) +
+                        " (clear it with NULL floors)");
+        if (f.min_nq > n_q)
+            return fail("fc_engine_set_floor: min_nq = " + std::to_string(f.min_nq) + " lies above n_q = " + std::to_string(n_q));
+        for (size_t b = 0; b < e->row_nq.size(); ++b)
+            if (f.min_nq > e->row_nq[b])
+                return fail("fc_engine_set_floor: min_nq = " + std::to_string(f.min_nq) + " lies above the cap of row " + std::to_string(b) + " (" +
+                            std::to_string(e->row_nq[b]) + " stages, fc_engine_set_row_nq)");
+        if (floor_ok && !session && (!f.row_err_out || !f.stage_err_out))
+            return fail(std::string(who) + ": the hook has no workspace: fc_engine_set_floor_form with row_errors_out and stage_errors_out");
+        return 0;
+    }
     if (!e->rate.on()) return 0;
     if (session) {
         if (e->rate.frames)
@@ -1979,6 +2020,7 @@ struct RvqTail {
     int64_t* paths = nullptr; float* errors = nullptr;                  // of the search, or null
     bool beam_sum = true, rate_sum = true;      // the sum behind the search, and behind the pick
     const fc::RagLen* rate_rows = nullptr;      // the rate applies: the frames of every row (null: it does not)
+    const fc::RagLen* floor_rows = nullptr;     // the noise floor applies (a session push, the hook): the frames every row has in the push
     float* serr = nullptr; double* rerr = nullptr;                      // stage errors [n_q + 1][B Tf], row errors [B][n_q + 1]
 };
 // launch(what, flops, enqueue): how the caller makes a launch (flops: booked to the search's kernel class; 0 for every other launch)
@@ -1994,7 +2036,25 @@ void rvq_after_greedy(const fc_engine* e, const RvqTail& a, hipStream_t st, Laun
             return fc::launch_rvq_beam(a.x, N, Dc, K, a.n_q, a.width, e->cb, e->cb_frag, e->enorm, a.codes, a.paths, a.errors, a.Tf, st, caps);
         });
         fc::StageCounts k; k.rows = caps;
-        if (a.beam_sum) sum("rvq beam sum", k);
+        if (a.beam_sum && !a.floor_rows) sum("rvq beam sum", k);        // under a floor the pick's sum follows at once
+    }
+    if (a.floor_rows) {     // fc_engine_set_floor (the push rule): one fused launch, or its chain for a push wider than the launch takes
+        const fc_engine::Floor& f = e->floor;
+        if (!f.chain && fc::rvq_push_floor_fits(a.Tf, Dc, a.n_q)) {
+            launch("rvq push floor", 0.0, [&] {
+                return fc::launch_rvq_push_floor(a.x, a.codes, a.B, a.Tf, Dc, K, a.n_q, e->cb, caps, *a.floor_rows, f.floor_dev, f.min_nq, f.n_q_out,
+                                                 a.quant, a.quant_bdt, a.subq, f.row_err_out, f.stage_err_out, st);
+            });
+            return;
+        }
+        launch("rvq stage errors", 0.0, [&] { return fc::launch_rvq_stage_errors(a.x, a.codes, N, Dc, K, a.n_q, e->cb, a.serr, a.Tf, caps, *a.floor_rows, st); });
+        launch("rvq floor rows", 0.0, [&] {
+            return fc::launch_rvq_rate_rows(a.serr, a.B, a.Tf, a.n_q, caps, *a.floor_rows, nullptr, f.min_nq, nullptr, f.n_q_out, a.rerr, st, f.floor_dev);
+        });
+        fc::StageCounts k; k.rows = f.n_q_out;
+        sum("rvq floor sum", k);
+        launch("rvq floor zero codes", 0.0, [&] { return fc::launch_rvq_rate_zero_codes(a.codes, N, a.Tf, a.n_q, k, st); });
+        return;
     }
     if (!a.rate_rows) return;
     const fc_engine::Rate& r = e->rate;
@@ -2022,7 +2082,7 @@ void rvq_after_greedy(const fc_engine* e, const RvqTail& a, hipStream_t st, Laun
 
 // ---- composite paths (each usable in dry mode for workspace sizing / work accounting) ---------------
 int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
-                float** quant_bdt_out, const fc::RagLen* offline_rows = nullptr);
+                float** quant_bdt_out, const fc::RagLen* offline_rows = nullptr, const fc::RagLen* push_rows = nullptr);
 int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* codes, float* quantized,
               float* sub_quants, float* scale, float* enc_out, float** quant_bdt_out, const Pass& p = Pass()) {
     const int B = cx.B, D = e->arch.dimension, Tf = frames_for(e, T);
@@ -2043,8 +2103,9 @@ int do_encode(fc_engine* e, Ctx& cx, const float* wav, int T, int n_q, int64_t* 
 
 // the quantiser behind the encoder's last conv (per frame: the offline call and a streaming push share it)
 // offline_rows (an offline call; null in a session push): the frames of every row, for the rate control (fc_engine_set_rate)
+// push_rows (a session push; null in an offline call): the frames every row has in the push, for the noise floor (fc_engine_set_floor)
 int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t* codes, float* quantized, float* sub_quants, float* enc_out,
-                float** quant_bdt_out, const fc::RagLen* offline_rows) {
+                float** quant_bdt_out, const fc::RagLen* offline_rows, const fc::RagLen* push_rows) {
     const int B = cx.B, D = e->arch.dimension;
     const int Dc = e->cdim();
     const bool ranged = e->arch.codec_range > 0.f;
@@ -2094,6 +2155,16 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
             if (e->rate.row_err_out) tail.rerr = e->rate.row_err_out;
             tail.rate_rows = offline_rows;
         }
+    }
+    // fc_engine_set_floor: a push needs the two buffers in the chain form alone (a push wider than the fused launch takes, or the form
+    // forced); a dry pass counts them for the session's widest push
+    if (push_rows && (cx.dry || e->floor.on())) {
+        if (!cx.dry && (int)e->floor.floor.size() != B) cx.fail("internal: a noise floor of another batch width");
+        if (cx.dry || e->floor.chain || !fc::rvq_push_floor_fits(Tf, Dc, n_q)) {
+            tail.serr = cx.alloc<float>((size_t)(n_q + 1) * B * Tf);
+            tail.rerr = cx.alloc<double>((size_t)B * (n_q + 1));
+        }
+        if (e->floor.on()) tail.floor_rows = push_rows;
     }
     rvq_after_greedy(e, tail, cx.st, [&](const char* what, double flops, auto&& enqueue) {
         if (flops > 0.0) cx.launch(what, "", [] { return kRvqBeamClass; }, flops, 0.0, enqueue);
@@ -2386,7 +2457,8 @@ int stream_encode_pass(const fc_stream* S, Ctx& cx, int n, const float* wav, int
     Act last = run_encoder(e, cx, stream_pass(S, n, final), s, Tc);
     const int Tfc = final ? frames_for(e, Tc) : Tc / total_hop(e);
     if (!cx.dry && last.T != Tfc) cx.fail("internal: frame count of a streaming push");
-    return do_quantize(e, cx, last, Tfc, S->n_q, codes, quantized, nullptr, enc_out, nullptr);
+    const fc::RagLen rows;                                      // lock-step: every row has the push's frames
+    return do_quantize(e, cx, last, Tfc, S->n_q, codes, quantized, nullptr, enc_out, nullptr, nullptr, &rows);
 }
 
 int stream_decode_pass(const fc_stream* S, Ctx& cx, int n, const float* z_bdt, int Tfc, int use_scale, float* wav) {
@@ -2519,6 +2591,10 @@ Session::GraphKey graph_key(const Session& s, int form, int width, int parity, i
     k.ptr = ptr; k.ws = ws; k.ws_bytes = ws_bytes; k.stream = stream;
     k.nq_table = row_nq_table(s.e); k.nq_rows = (int)s.e->row_nq.size();
     k.rvq_beam = s.e->rvq_beam;
+    if (form == kFormEncode && s.e->floor.on()) {
+        const fc_engine::Floor& f = s.e->floor;
+        k.floor_table = f.floor_dev; k.floor_out = f.n_q_out; k.floor_min = f.min_nq; k.floor_chain = f.chain ? 1 : 0;
+    }
     return k;
 }
 
@@ -2736,7 +2812,8 @@ int slots_encode_pass(fc_slots* Q, Ctx& cx, const float* wav, int Tc, const int3
     Act last = run_encoder(e, cx, p, s, Tc);
     const int Tf = frames_for(e, Tc);
     if (!cx.dry && last.T != Tf) cx.fail("internal: frame count of a slot push");
-    if (do_quantize(e, cx, last, Tf, Q->n_q, codes, quantized, nullptr, enc_out, nullptr)) return 1;
+    fc::RagLen rows; rows.lens = p.lengths; rows.div = total_hop(e);      // a slot's frames in this push: ceil(samples / hop), 0 for an idle one
+    if (do_quantize(e, cx, last, Tf, Q->n_q, codes, quantized, nullptr, enc_out, nullptr, nullptr, &rows)) return 1;
     Pass m = p; m.frame_div = total_hop(e);                          // ragged_mask_encoded counts samples
     ragged_mask_encoded(e, cx, m, Tf, Q->n_q, codes, quantized, nullptr, enc_out);
     return cx.err;
@@ -3208,17 +3285,20 @@ int rvq_hook_rows(fc_engine* e, const char* who, const float* x, const int64_t* 
     if (check_ready(e)) return 1;
     if (!x || !codes || N <= 0) return fail("bad argument");
     if (n_q < 1 || n_q > e->arch.num_quantizers) return fail("n_q out of range");
-    if (rate && !e->rate.on()) return fail(std::string(who) + ": no rate is set (fc_engine_set_rate)");
-    if (rate && (!e->rate.row_err_out || !e->rate.stage_err_out))
+    const bool floor = rate && e->floor.on();          // the rate hook under a noise floor (fc_engine_set_floor): the push rule on B rows
+    if (!rate && e->floor.on())
+        return fail(std::string(who) + ": a noise floor is set (fc_engine_set_floor): it is for session pushes only; clear it with NULL floors");
+    if (rate && !floor && !e->rate.on()) return fail(std::string(who) + ": no rate is set (fc_engine_set_rate)");
+    if (rate && !floor && (!e->rate.row_err_out || !e->rate.stage_err_out))
         return fail(std::string(who) + ": the hook has no workspace: fc_engine_set_rate with row_errors_out and stage_errors_out");
     if (rvq_beam_check(e, width, who)) return 1;
     if (width == 1 && search_outputs) return fail(std::string(who) + ": paths and errors are those of a search: rvq_beam above 1");
-    *B = rate ? (int)e->rate.ratio.size() : e->row_nq.empty() ? 1 : (int)e->row_nq.size();
+    *B = floor ? (int)e->floor.floor.size() : rate ? (int)e->rate.ratio.size() : e->row_nq.empty() ? 1 : (int)e->row_nq.size();
     *Tf = N / *B;
     if (N % *B != 0)
         return fail(std::string(who) + ": with " + (rate ? "a rate for " : "per-row stage counts for ") + std::to_string(*B) +
                     " rows, N must be a multiple of that");
-    return rate ? counts_check_encode(e, who, *B, n_q, false) : row_nq_check(e, *B, n_q);
+    return rate ? counts_check_encode(e, who, *B, n_q, false, true) : row_nq_check(e, *B, n_q);
 }
 
 // The greedy encode of the search and rate hooks (`quantized`: what it sums, or null) and everything behind it; the first launch that
@@ -3263,6 +3343,8 @@ int fc_engine_set_rate(fc_engine* e, const double* ratio_rows, int B, int min_nq
                        float* stage_errors_out, void* stream) {
     if (!e) return fail("null engine");
     if (!e->finalized) return fail("engine not finalized");
+    if (ratio_rows && e->floor.on())
+        return fail("fc_engine_set_rate: a noise floor is set (fc_engine_set_floor): a call takes a rate or a floor, not both; clear one of them");
     e->rate.clear_frames();             // frame mode is given after the rate, every time (fc_engine_set_rate_frames)
     if (!ratio_rows) { e->rate.ratio.clear(); e->rate.n_q_out = nullptr; e->rate.row_err_out = nullptr; e->rate.stage_err_out = nullptr; return 0; }
     if (B <= 0) return fail("fc_engine_set_rate: a rate holds at least one row");
@@ -3311,6 +3393,66 @@ int fc_engine_set_rate_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out,
     return 0;
 }
 
+int fc_engine_set_floor(fc_engine* e, const double* floor_rows, int B, int min_nq, int32_t* n_q_rows_out, void* stream) {
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!floor_rows) { e->floor.floor.clear(); e->floor.n_q_out = nullptr; e->floor.clear_form(); return 0; }
+    if (e->rate.on())
+        return fail("fc_engine_set_floor: a rate is set (fc_engine_set_rate): a call takes a rate or a floor, not both; clear one of them");
+    if (B <= 0) return fail("fc_engine_set_floor: a floor holds at least one row");
+    if (!n_q_rows_out) return fail("fc_engine_set_floor: n_q_rows_out (device int32 [B]) takes the chosen stage counts");
+    if (e->arch.q0_ds_ratio > 1)
+        return fail("fc_engine_set_floor: quantizer_conf.q0_ds_ratio > 1: stage 0 quantises another frame's row, so a frame's residual is not its input "
+                    "minus its codes");
+    if (min_nq < 1 || min_nq > e->arch.num_quantizers)
+        return fail("fc_engine_set_floor: min_nq lies in [1, num_quantizers = " + std::to_string(e->arch.num_quantizers) + "], got " + std::to_string(min_nq));
+    for (size_t b = 0; b < e->row_nq.size(); ++b)
+        if (min_nq > e->row_nq[b])
+            return fail("fc_engine_set_floor: min_nq = " + std::to_string(min_nq) + " lies above the cap of row " + std::to_string(b) + " (" +
+                        std::to_string(e->row_nq[b]) + " stages, fc_engine_set_row_nq)");
+    for (int b = 0; b < B; ++b)
+        if (!(floor_rows[b] >= 0.0))
+            return fail("fc_engine_set_floor: row " + std::to_string(b) + ": a floor D * 10^(noise_floor_db / 10) is neither negative nor NaN");
+    if ((size_t)B > e->floor.cap) {     // a larger table; the old one stays allocated for the launches that may still read it
+        const size_t cap = std::max<size_t>(64, 2 * (size_t)B);
+        void* pf = nullptr;
+        HIP_TRY(hipMalloc(&pf, cap * sizeof(double)));
+        e->dev_allocs.push_back(pf);
+        e->floor.floor_dev = (double*)pf; e->floor.cap = cap;
+    }
+    // the source of the copy is the engine's own host copy, which lives as long as the engine: the caller's array may go at once
+    const std::vector<double> keep = e->floor.floor;
+    e->floor.floor.assign(floor_rows, floor_rows + B);
+    if (hipError_t er = hipMemcpyAsync(e->floor.floor_dev, e->floor.floor.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream);
+        er != hipSuccess) {
+        e->floor.floor = keep;
+        return fail(std::string("fc_engine_set_floor: copy of the floors: ") + hipGetErrorString(er));
+    }
+    e->floor.clear_form();              // the form is given after the floor, every time (fc_engine_set_floor_form)
+    e->floor.min_nq = min_nq;
+    e->floor.n_q_out = n_q_rows_out;
+    return 0;
+}
+
+int fc_engine_set_floor_form(fc_engine* e, int chain, double* row_errors_out, float* stage_errors_out, float* sub_quants_out, const int32_t* off_rows,
+                             void* stream) {
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!e->floor.on()) return fail("fc_engine_set_floor_form: no noise floor is set: it is given after fc_engine_set_floor");
+    if (off_rows) {         // a row switched off keeps its cap: on the device its floor reads -1 (the push rule, csrc/rvq_rate_kernels.h)
+        bool any = false;
+        for (size_t b = 0; b < e->floor.floor.size(); ++b)
+            if (off_rows[b]) { e->floor.floor[b] = -1.0; any = true; }
+        if (any)
+            if (hipError_t er = hipMemcpyAsync(e->floor.floor_dev, e->floor.floor.data(), e->floor.floor.size() * sizeof(double), hipMemcpyHostToDevice,
+                                               (hipStream_t)stream);
+                er != hipSuccess)
+                return fail(std::string("fc_engine_set_floor_form: copy of the floors: ") + hipGetErrorString(er));
+    }
+    e->floor.chain = chain != 0; e->floor.row_err_out = row_errors_out; e->floor.stage_err_out = stage_errors_out; e->floor.subq_out = sub_quants_out;
+    return 0;
+}
+
 int fc_engine_set_frame_nq(fc_engine* e, const int32_t* n_q_frames, int B, int Tf, void* stream) {
     (void)stream;
     if (!e) return fail("null engine");
@@ -3329,7 +3471,8 @@ int fc_rvq_encode_rate(fc_engine* e, const float* x, int N, int n_q, int width, 
     a.x = x; a.codes = codes; a.n_q = n_q; a.width = width;
     a.quant = quantized; a.beam_sum = false; a.rate_sum = quantized != nullptr;      // one sum, from the chosen counts
     const fc::RagLen rows;                              // every row has Tf frames
-    a.rate_rows = &rows; a.serr = e->rate.stage_err_out; a.rerr = e->rate.row_err_out;
+    if (e->floor.on()) { a.floor_rows = &rows; a.serr = e->floor.stage_err_out; a.rerr = e->floor.row_err_out; a.subq = e->floor.subq_out; }
+    else { a.rate_rows = &rows; a.serr = e->rate.stage_err_out; a.rerr = e->rate.row_err_out; }
     return rvq_hook_launch(e, "fc_rvq_encode_rate", a, nullptr, (hipStream_t)stream);
 }
 

@@ -47,6 +47,30 @@
 // achieved [B] f64 = sum_t err[k_t][b, t] in the order E_b is summed.
 // The caller then sums and zeroes as above with the counts per frame: for greedy codes frame (b, t) is bit for bit the call with
 // n_q = k_t; for the search it is the first k_t codes of the full-depth path.  A frame with k_t = 0 has quantized exactly 0.
+//
+// THE PUSH RULE, in terms of the row rule: the count of a row of ONE encode push of a session (fc_stream_encode, fc_slots_encode), chosen
+// inside the push by an absolute noise floor (fc_engine_set_floor).  A push sees a few frames of an utterance, so a ratio to the input
+// energy would follow every pause of the speaker; the floor is a level that does not move.  Inputs: the stage errors err and the fp64 sums
+// E_b above, over the F_b frames the row has in THIS push (every row's Tf in a lock-step session; ceil(samples_b / hop) in a slot push),
+// from the codes found at the cap; cap_b as above (the row's or slot's current n_q); lo = min_nq in [1, cap_b] (a mode-0 packet needs
+// k >= 1); and a floor per row, floor_b, a double made by the host: floor_b = D * 10^(noise_floor_db_b / 10), D the quantiser's input
+// width -- the floor reads as "mean-square residual per element, in dB re 1".  It is neither negative nor NaN.
+//   * thr_b = floor_b * (double)F_b: one IEEE double product, no division;
+//   * a row whose E_b[0 .. cap_b] are not all finite takes cap_b (what the plain push gives it);
+//   * a row with E_b[0] <= thr_b takes lo: its input is already at or below the floor -- silence, the discontinuous-transmission case;
+//   * else k_b = the smallest k in [lo, cap_b] with E_b[k] <= thr_b;
+//   * if there is none: the k in that range with the smallest E_b[k], first on ties (the scan of the row rule).  A floor of 0
+//     (noise_floor_db = -inf) therefore means "the best k", a floor of +inf means lo;
+//   * a row that emits no frame in the push (F_b == 0: an idle slot) is neither read nor written: its entry of the count table stays;
+//   * a row switched off (fc_engine_set_floor_form; on the device its floor reads -1, a value no caller can give) takes cap_b: a slot
+//     without a floor beside slots that have one.
+// The rule is stateless: a row's count depends on that row's frames of that push and on nothing else.  The row is then summed and zeroed as
+// for the row rule: for greedy codes row b of the push is bit for bit the push with n_q = k_b and zeros in codes[k_b:]; for the search it is
+// the first k_b codes of the full-depth path.
+// Two forms, bit for bit the same outputs.  The chain: launch_rvq_stage_errors, launch_rvq_rate_rows with `floor`, launch_rvq_codes_sum,
+// launch_rvq_rate_zero_codes -- any width.  The fused form, launch_rvq_push_floor: ONE launch for pushes of at most 256 frames per row
+// (every partial of the fp64 sum then holds at most one term), which runs the same device steps in the same order.  Both read frames,
+// caps and floors from device memory only, so a captured push replays unchanged when a floor changes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -60,8 +84,21 @@ hipError_t launch_rvq_stage_errors(const float* x /* [N][D] */, const int64_t* c
                                    float* err, int Tf, const int* nq_rows, const RagLen& rows, hipStream_t st);
 
 // One workgroup per batch row: row_err [B][nq + 1] (never null), then the pick into k_table [B] and n_q_out [B] (either may be null).
+// floor (dev [B], or null): the absolute threshold of the push rule in place of the ratio, which is then not read; a row without frames
+// writes nothing.
 hipError_t launch_rvq_rate_rows(const float* err /* [nq + 1][B Tf] */, int B, int Tf, int nq, const int* nq_rows, const RagLen& rows,
-                                const double* ratio /* dev [B] */, int min_nq, int* k_table, int32_t* n_q_out, double* row_err, hipStream_t st);
+                                const double* ratio /* dev [B] */, int min_nq, int* k_table, int32_t* n_q_out, double* row_err, hipStream_t st,
+                                const double* floor = nullptr);
+
+// The push rule in one launch: stage errors, row sums, pick, zeros and sum of one push, one workgroup per batch row.  codes [nq][B Tf] are
+// rewritten in place; n_q_out [B] never null; quant [B Tf][D], quant_bdt [B][D][Tf], subq [nq][B][D][Tf], row_err [B][nq + 1] and serr_out
+// [nq + 1][B Tf] may each be null.  rvq_push_floor_fits: whether the launch exists for this shape (Tf <= 256, nq <= 64, its LDS fits);
+// where it does not the caller runs the chain.
+constexpr int kPushFloorMaxFrames = 256, kPushFloorMaxStages = 64;
+bool rvq_push_floor_fits(int Tf, int D, int nq);
+hipError_t launch_rvq_push_floor(const float* x /* [B Tf][D] */, int64_t* codes, int B, int Tf, int D, int K, int nq, const float* cb,
+                                 const int* nq_rows, const RagLen& rows, const double* floor /* dev [B] */, int min_nq, int32_t* n_q_out, float* quant,
+                                 float* quant_bdt, float* subq, double* row_err, float* serr_out, hipStream_t st);
 
 // One workgroup per batch row.  err [nq + 1][B Tf]; row_err [B][nq + 1] (launch_rvq_rate_rows wrote it on the same stream); nq_rows [B] (caps)
 // or null; rows.lens null: every row has Tf frames.  n_q_frames [B][Tf] never null; the three row outputs may be null.

@@ -1,5 +1,6 @@
 // gfx950 (MI355X / CDNA4) kernels of the quantiser's rate control: the residual energy of every frame after every stage, made from the
-// codes of a call, the fp64 sums per batch row with the pick of a stage count per row, the pick per frame, and the zeros behind a count.
+// codes of a call, the fp64 sums per batch row with the pick of a stage count per row, the pick per frame, and the zeros behind a count;
+// and the push rule of a session in one launch (rvq_push_floor_kernel: the same steps, fused per batch row).
 // rvq_rate_kernels.h states the rules.  fp32 / fp64 and integers, 64-lane wavefronts.  The encode kernels (rvq_kernels.hip,
 // rvq_beam_kernel.h) are not involved: the errors are recomputed from x and the codes, so whoever found the codes is measured by the
 // same formula.
@@ -43,31 +44,20 @@ __device__ __forceinline__ float rate_row_norm(const float* row, int j) {
     const float s_pair = s + __shfl_xor(s, 1, 64);          // p0+p1 | p2+p3
     return s_pair + __shfl_xor(s_pair, 2, 64);              // (p0+p1)+(p2+p3)
 }
-}  // namespace
 
-// 16 frames per workgroup, 256 threads.  The residual rows live in LDS (padded by 4 floats like rvq_encode_kernel's: the four chains of
-// a row then start in different banks); the selected code rows come through L2.  Stage i: wave 0 takes |r_i|^2 of the 16 rows (four
-// lanes a row, rate_row_norm) and its 16 lanes j = 0 store 16 consecutive floats of err[i]; then all threads subtract the rows' codes of
-// stage i.  krow: the row's cap, -1 for a row that is not measured (behind N, or behind its batch row's frames).
-template <int D>
-__global__ __launch_bounds__(256) void rvq_stage_errors_kernel(const float* __restrict__ x, const int64_t* __restrict__ codes, int N, int K, int nq,
-                                                               const float* __restrict__ cb, float* __restrict__ err, int Tf,
-                                                               const int* __restrict__ nq_rows, RagLen rows) {
+// The stage errors of 16 consecutive frame rows from row0, by the 256 threads of a workgroup: the one statement of the first bullet of
+// the row rule, shared by rvq_stage_errors_kernel and the fused push kernel.  The residual rows live in LDS (padded by 4 floats like
+// rvq_encode_kernel's: the four chains of a row then start in different banks); the selected code rows come through L2.  Stage i:
+// wave 0 takes |r_i|^2 of the 16 rows (four lanes a row, rate_row_norm) and its 16 lanes j = 0 hand it to store(i, n, value); then all
+// threads subtract the rows' codes of stage i.  cap_of(n): the row's cap, -1 for a row that is not measured (nothing of it is read).
+// Every thread of the workgroup calls it (it holds barriers); the caller puts a barrier between two tiles.
+template <int D, typename Cap, typename Store>
+__device__ __forceinline__ void rvq_stage_errors_tile(float (*R)[D + 4], int* krow, const float* __restrict__ x, const int64_t* __restrict__ codes,
+                                                      int N, int K, int nq, const float* __restrict__ cb, int row0, Cap&& cap_of, Store&& store) {
     constexpr int ROWS = kRateRows, NEL = ROWS * D / 256;
     static_assert(ROWS * D % 256 == 0, "every thread owns NEL elements of the row set");
-    __shared__ __attribute__((aligned(16))) float R[ROWS][D + 4];
-    __shared__ int krow[ROWS];
     const int tid = threadIdx.x;
-    const int row0 = blockIdx.x * ROWS;
-    if (tid < ROWS) {
-        const int n = row0 + tid;
-        int k = -1;
-        if (n < N) {
-            const int b = n / Tf, t = n - b * Tf;
-            if (t < row_frames(rows, b, Tf)) k = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
-        }
-        krow[tid] = k;
-    }
+    if (tid < ROWS) krow[tid] = cap_of(row0 + tid);
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < NEL; ++it) {
@@ -77,9 +67,9 @@ __global__ __launch_bounds__(256) void rvq_stage_errors_kernel(const float* __re
     for (int i = 0; i <= nq; ++i) {
         __syncthreads();
         if (tid < 4 * ROWS) {           // wave 0, all 64 lanes: rate_row_norm exchanges between the four lanes of a row
-            const int r = tid >> 2, n = row0 + r;
+            const int r = tid >> 2;
             const float e2 = rate_row_norm<D>(R[r], tid & 3);
-            if ((tid & 3) == 0 && n < N) err[(size_t)i * N + n] = i <= krow[r] ? e2 : 0.f;
+            if ((tid & 3) == 0) store(i, row0 + r, i <= krow[r] ? e2 : 0.f);
         }
         if (i == nq) break;
         __syncthreads();
@@ -100,6 +90,42 @@ __global__ __launch_bounds__(256) void rvq_stage_errors_kernel(const float* __re
             if (i < krow[r]) R[r][d] = __fsub_rn(R[r][d], qv[it]);
         }
     }
+}
+
+// The pick of one row from its fp64 sums E[0 .. cap] (rvq_rate_kernels.h), by one thread.  floor null: the row rule, thr = E[0] * ratio[b]
+// and E[0] == 0 is silence.  floor given: the push rule, thr = floor[b] * (double)frames and E[0] <= thr is silence.
+__device__ __forceinline__ int rate_pick_row(const double* E, int cap, int min_nq, const double* __restrict__ ratio,
+                                             const double* __restrict__ floor, int b, int frames) {
+    const int lo = min_nq < cap ? (min_nq < 1 ? 1 : min_nq) : cap;
+    if (floor && floor[b] < 0.0) return cap;            // the push rule: a row switched off
+    bool finite = true;
+    for (int i = 0; i <= cap; ++i) finite = finite && isfinite(E[i]);
+    if (!finite) return cap;
+    const double thr = floor ? floor[b] * (double)frames : E[0] * ratio[b];
+    if (floor ? E[0] <= thr : E[0] == 0.0) return lo;
+    return rate_pick_scan(lo, cap, [&](int i) { return E[i]; }, [&](double ei) { return ei <= thr; });
+}
+
+// the cap of batch row b: its entry of the per-row table, else nq
+__device__ __forceinline__ int rate_row_cap(const int* __restrict__ nq_rows, int b, int nq) {
+    return nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
+}
+}  // namespace
+
+// 16 frames per workgroup, 256 threads: one tile of rvq_stage_errors_tile.  A row behind N, or behind its batch row's frames, is not measured.
+template <int D>
+__global__ __launch_bounds__(256) void rvq_stage_errors_kernel(const float* __restrict__ x, const int64_t* __restrict__ codes, int N, int K, int nq,
+                                                               const float* __restrict__ cb, float* __restrict__ err, int Tf,
+                                                               const int* __restrict__ nq_rows, RagLen rows) {
+    __shared__ __attribute__((aligned(16))) float R[kRateRows][D + 4];
+    __shared__ int krow[kRateRows];
+    rvq_stage_errors_tile<D>(R, krow, x, codes, N, K, nq, cb, blockIdx.x * kRateRows,
+        [&](int n) {
+            if (n >= N) return -1;
+            const int b = n / Tf, t = n - b * Tf;
+            return t < row_frames(rows, b, Tf) ? rate_row_cap(nq_rows, b, nq) : -1;
+        },
+        [&](int i, int n, float v) { if (n < N) err[(size_t)i * N + n] = v; });
 }
 
 hipError_t launch_rvq_stage_errors(const float* x, const int64_t* codes, int N, int D, int K, int nq, const float* cb, float* err, int Tf,
@@ -128,12 +154,14 @@ hipError_t launch_rvq_stage_errors(const float* x, const int64_t* codes, int N, 
 // meet as a binary tree in LDS (no atomics): the order depends on the row's frame count alone.  Thread 0 then picks (rvq_rate_kernels.h).
 __global__ __launch_bounds__(256) void rvq_rate_rows_kernel(const float* __restrict__ err, int Tf, int nq, const int* __restrict__ nq_rows,
                                                             RagLen rows, const double* __restrict__ ratio, int min_nq, int* __restrict__ k_table,
-                                                            int32_t* __restrict__ n_q_out, double* __restrict__ row_err) {
+                                                            int32_t* __restrict__ n_q_out, double* __restrict__ row_err,
+                                                            const double* __restrict__ floor) {
     __shared__ double red[256];
     const int tid = threadIdx.x, b = blockIdx.x;
     const size_t N = (size_t)gridDim.x * Tf;
     const int frames = row_frames(rows, b, Tf);
-    const int cap = nq_rows ? (nq_rows[b] < nq ? nq_rows[b] : nq) : nq;
+    if (floor && frames <= 0) return;           // the push rule: a row without a frame in the push is neither read nor written
+    const int cap = rate_row_cap(nq_rows, b, nq);
     double* E = row_err + (size_t)b * (nq + 1);
     for (int i = 0; i <= nq; ++i) {
         double s = 0.0;
@@ -149,26 +177,140 @@ __global__ __launch_bounds__(256) void rvq_rate_rows_kernel(const float* __restr
         __syncthreads();
     }
     if (tid != 0) return;
-    const int lo = min_nq < cap ? (min_nq < 1 ? 1 : min_nq) : cap;
-    int k = cap;
-    bool finite = true;
-    for (int i = 0; i <= cap; ++i) finite = finite && isfinite(E[i]);
-    if (finite) {
-        if (E[0] == 0.0) k = lo;
-        else {
-            const double thr = E[0] * ratio[b];
-            k = rate_pick_scan(lo, cap, [&](int i) { return E[i]; }, [&](double ei) { return ei <= thr; });
-        }
-    }
+    const int k = rate_pick_row(E, cap, min_nq, ratio, floor, b, frames);
     if (k_table) k_table[b] = k;
     if (n_q_out) n_q_out[b] = k;
 }
 
 hipError_t launch_rvq_rate_rows(const float* err, int B, int Tf, int nq, const int* nq_rows, const RagLen& rows, const double* ratio, int min_nq,
-                                int* k_table, int32_t* n_q_out, double* row_err, hipStream_t st) {
+                                int* k_table, int32_t* n_q_out, double* row_err, hipStream_t st, const double* floor) {
     if (B <= 0) return hipSuccess;
-    if (Tf <= 0 || nq < 1 || !err || !ratio || !row_err) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rvq_rate_rows_kernel, dim3(B), dim3(256), 0, st, err, Tf, nq, nq_rows, rows, ratio, min_nq, k_table, n_q_out, row_err);
+    if (Tf <= 0 || nq < 1 || !err || !(ratio || floor) || !row_err) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rvq_rate_rows_kernel, dim3(B), dim3(256), 0, st, err, Tf, nq, nq_rows, rows, ratio, min_nq, k_table, n_q_out, row_err, floor);
+    return hipGetLastError();
+}
+
+// THE PUSH RULE in one launch (rvq_rate_kernels.h): one workgroup per batch row, thread t owns frame t of the push (Tf <= 256).
+//   1. stage errors: the row's frames in tiles of 16 through rvq_stage_errors_tile, into errf [nq + 1][Tf] in LDS (and serr_out);
+//   2. E_b[i]: thread j's partial is its one term (0.0 + err, as rvq_rate_rows_kernel's loop leaves it), the 256 partials meet as that
+//      kernel's binary tree, kTreeStages stages per pass;
+//   3. thread 0 picks (rate_pick_row) and writes k_b;
+//   4. codes[k_b:] of the row's Tf frames are zeroed and the first k_b code vectors summed in stage order from 0, element by element as
+//      rvq_codes_sum_kernel does, into quant / quant_bdt / subq.
+// A row without a frame in the push returns at once.  The zeroed codes lie at stages >= k_b, the summed ones below: no thread reads what
+// another writes in step 4.
+constexpr int kTreeStages = 4;
+template <int D>
+__global__ __launch_bounds__(256) void rvq_push_floor_kernel(const float* __restrict__ x, int64_t* __restrict__ codes, int Tf, int K, int nq,
+                                                             const float* __restrict__ cb, const int* __restrict__ nq_rows, RagLen rows,
+                                                             const double* __restrict__ floor, int min_nq, int32_t* __restrict__ n_q_out,
+                                                             float* __restrict__ quant, float* __restrict__ quant_bdt, float* __restrict__ subq,
+                                                             double* __restrict__ row_err, float* __restrict__ serr_out) {
+    extern __shared__ float errf[];                     // [nq + 1][Tf]
+    __shared__ __attribute__((aligned(16))) float R[kRateRows][D + 4];
+    __shared__ int krow[kRateRows];
+    __shared__ double red[kTreeStages][256];
+    __shared__ double E[kPushFloorMaxStages + 1];
+    __shared__ int k_row;
+    const int tid = threadIdx.x, b = blockIdx.x, Bn = gridDim.x;
+    const int N = Bn * Tf;
+    const int frames = row_frames(rows, b, Tf);
+    if (frames <= 0) return;
+    const int cap = rate_row_cap(nq_rows, b, nq);
+    for (int t0 = 0; t0 < Tf; t0 += kRateRows) {
+        rvq_stage_errors_tile<D>(R, krow, x, codes, N, K, nq, cb, b * Tf + t0,
+            [&](int n) { return n - b * Tf < frames ? cap : -1; },          // also every row of the tile behind Tf: frames <= Tf
+            [&](int i, int n, float v) {
+                const int t = n - b * Tf;
+                if (t >= Tf) return;
+                errf[i * Tf + t] = v;
+                if (serr_out) serr_out[(size_t)i * N + n] = v;
+            });
+        __syncthreads();
+    }
+    for (int i0 = 0; i0 <= nq; i0 += kTreeStages) {
+        const int ni = nq + 1 - i0 < kTreeStages ? nq + 1 - i0 : kTreeStages;
+        for (int j = 0; j < ni; ++j) {
+            double s = 0.0;
+            if (i0 + j <= cap && tid < frames) s = s + (double)errf[(i0 + j) * Tf + tid];
+            red[j][tid] = s;
+        }
+        __syncthreads();
+        for (int o = 128; o >= 1; o >>= 1) {
+            for (int e = tid; e < ni * o; e += 256) {
+                const int j = e / o, c = e - j * o;
+                red[j][c] = red[j][c] + red[j][c + o];
+            }
+            __syncthreads();
+        }
+        if (tid < ni) {
+            E[i0 + tid] = red[tid][0];
+            if (row_err) row_err[(size_t)b * (nq + 1) + i0 + tid] = red[tid][0];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int k = rate_pick_row(E, cap, min_nq, nullptr, floor, b, frames);
+        k_row = k;
+        n_q_out[b] = k;
+    }
+    __syncthreads();
+    const int k = k_row;
+    for (int e = tid; e < (nq - k) * Tf; e += 256) {
+        const int i = k + e / Tf, t = e % Tf;
+        codes[(size_t)i * N + (size_t)b * Tf + t] = 0;
+    }
+    for (int e = tid; e < Tf * D; e += 256) {
+        const int t = e / D, d = e - t * D;
+        const size_t n = (size_t)b * Tf + t;
+        float s = 0.f;
+        for (int i = 0; i < nq; ++i) {
+            float v = 0.f;
+            if (i < k) {
+                long long idx = codes[(size_t)i * N + n];
+                if (idx < 0 || idx >= K) idx = 0;
+                v = cb[((size_t)i * K + idx) * D + d];
+                s = s + v;
+            }
+            if (subq) subq[(((size_t)i * Bn + b) * D + d) * Tf + t] = v;
+        }
+        if (quant) quant[n * D + d] = s;
+        if (quant_bdt) quant_bdt[((size_t)b * D + d) * Tf + t] = s;
+    }
+}
+
+// static LDS of rvq_push_floor_kernel<D> besides errf; the launch is refused (false) where the whole does not fit 64 KiB
+static size_t push_floor_static_lds(int D) {
+    return sizeof(float) * kRateRows * (D + 4) + sizeof(int) * (kRateRows + 1) + sizeof(double) * (kTreeStages * 256 + kPushFloorMaxStages + 1);
+}
+
+bool rvq_push_floor_fits(int Tf, int D, int nq) {
+    if (Tf < 1 || Tf > kPushFloorMaxFrames || nq < 1 || nq > kPushFloorMaxStages) return false;
+    if (D != 16 && D != 32 && D != 64 && D != 128 && D != 256 && D != 512) return false;
+    return push_floor_static_lds(D) + sizeof(float) * (size_t)(nq + 1) * Tf + 256 <= 64 * 1024;
+}
+
+hipError_t launch_rvq_push_floor(const float* x, int64_t* codes, int B, int Tf, int D, int K, int nq, const float* cb, const int* nq_rows,
+                                 const RagLen& rows, const double* floor, int min_nq, int32_t* n_q_out, float* quant, float* quant_bdt, float* subq,
+                                 double* row_err, float* serr_out, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (!rvq_push_floor_fits(Tf, D, nq) || K < 1 || !x || !codes || !floor || !n_q_out) return hipErrorInvalidValue;
+    const size_t dyn = sizeof(float) * (size_t)(nq + 1) * Tf;
+#define FC_FLOOR_CASE(DD)                                                                                                                   \
+    case DD:                                                                                                                                \
+        hipLaunchKernelGGL((rvq_push_floor_kernel<DD>), dim3(B), dim3(256), dyn, st, x, codes, Tf, K, nq, cb, nq_rows, rows, floor, min_nq,    \
+                           n_q_out, quant, quant_bdt, subq, row_err, serr_out);                                                            \
+        break;
+    switch (D) {
+        FC_FLOOR_CASE(16)
+        FC_FLOOR_CASE(32)
+        FC_FLOOR_CASE(64)
+        FC_FLOOR_CASE(128)
+        FC_FLOOR_CASE(256)
+        FC_FLOOR_CASE(512)
+        default: return hipErrorInvalidValue;
+    }
+#undef FC_FLOOR_CASE
     return hipGetLastError();
 }
 

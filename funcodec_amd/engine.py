@@ -187,6 +187,83 @@ def rate_pick(E, ratio: float, min_n_q: int, cap: int) -> int:
     return _pick_scan(E, lo, cap, lambda v: v <= thr)
 
 
+def floor_refusal(arch) -> Optional[str]:
+    """Why a model of this architecture takes no stage count per push by a noise floor (``noise_floor_db``), or None.  The configuration
+    key is named, as ``rate_refusal`` does."""
+    if arch.segment_length is not None:
+        return "noise_floor_db is not available with model_conf.segment_dur (segments are extra batch rows of the engine call)"
+    if arch.bypass_quantizer:
+        return "noise_floor_db is not available with model_conf.bypass_quantizer (the quantiser's result is dropped)"
+    if arch.q0_ds_ratio > 1:
+        return ("noise_floor_db is not available for quantizer_conf.q0_ds_ratio > 1 (stage 0 quantises another frame's row, so a frame's "
+                "residual is not its input minus its codes)")
+    return None
+
+
+def floor_value(arch, db, what: str = "noise_floor_db") -> float:
+    """floor = D * 10^(db / 10) of one ``noise_floor_db`` (D: the quantiser's input width; the floor reads as mean-square residual per
+    element, in dB re 1), as a Python float (float64: the device multiplies the same double); -inf is 0 ("the best k"), +inf is +inf
+    ("always min_n_q"); NaN, or anything that is not a number, raises."""
+    if isinstance(db, bool) or not isinstance(db, numbers.Real) or db != db:
+        raise EngineError(f"{what} is a number of dB (not NaN), got {db!r}")
+    db = float(db)
+    if db == float("-inf"):
+        return 0.0
+    if db == float("inf"):
+        return float("inf")
+    return float(np.float64(arch.codebook_dim) * np.float64(10.0) ** np.float64(db / 10.0))
+
+
+def floor_values(arch, db, B: int) -> list:
+    """The floors of a ``noise_floor_db`` that is one value or B of them, as B Python floats; raises before any engine call."""
+    why = floor_refusal(arch)
+    if why:
+        raise EngineError(why)
+    if isinstance(db, numbers.Real) or (hasattr(db, "ndim") and db.ndim == 0):
+        db = [float(db)] * B
+    elif hasattr(db, "ndim"):
+        if db.ndim != 1:
+            raise EngineError(f"noise_floor_db must be one value or a sequence / 1-D tensor of one per row, got shape {tuple(db.shape)}")
+        db = db.tolist()
+    db = list(db)
+    if len(db) != B:
+        raise EngineError(f"noise_floor_db must hold one entry per row ({B}), got {len(db)}")
+    return [floor_value(arch, v, f"row {b}: noise_floor_db") for b, v in enumerate(db)]
+
+
+def floor_pick(row_err, frames, floor, min_n_q: int, caps):
+    """The push rule (csrc/rvq_rate_kernels.h, include/funcodec_amd.h) in float64 numpy: the stage counts of the B rows of one push, a pure
+    function of their float64 row errors row_err [B, n_q + 1] (row_err[b, 0]: the input energy of the row's frames of the push), the frames
+    every row has in the push (one int or B), the floors D * 10^(noise_floor_db / 10) (one float or B), min_n_q and the caps (one int or B):
+      - a row without frames: -1 (the device leaves its entry alone);
+      - energies E[0 .. cap] that are not all finite: cap;
+      - E[0] <= thr = floor * float64(frames): min_n_q (the input is already at or below the floor);
+      - the smallest k in [min_n_q, cap] with E[k] <= thr;
+      - no such k: the k in that range with the smallest E[k], first on ties.
+    Returns int32 [B]."""
+    row_err = np.asarray(row_err, dtype=np.float64)
+    if row_err.ndim == 1:
+        row_err = row_err[None]
+    B = row_err.shape[0]
+    each = lambda v: list(np.broadcast_to(np.asarray(v), (B,)))
+    out = np.full((B,), -1, dtype=np.int32)
+    for b, (F, fl, cap) in enumerate(zip(each(frames), each(floor), each(caps))):
+        F, cap = int(F), int(cap)
+        if F <= 0:
+            continue
+        if fl is None or fl < 0:        # a row switched off keeps its cap
+            out[b] = cap
+            continue
+        E = [float(v) for v in row_err[b, :cap + 1]]
+        lo = min(max(int(min_n_q), 1), cap)
+        if not all(np.isfinite(v) for v in E):
+            out[b] = cap
+            continue
+        thr = float(np.float64(fl) * np.float64(F))
+        out[b] = lo if E[0] <= thr else _pick_scan(E, lo, cap, lambda v: v <= thr)
+    return out
+
+
 def rate_pick_frames(err, E, ratio: float, min_n_q: int, cap: int, frames: Optional[int] = None):
     """The stage counts of one row's frames (csrc/rvq_rate_kernels.h, include/funcodec_amd.h), a pure function of its float32
     stage errors err[0 .. cap][t] (err[k][t]: frame t's residual energy after k stages), its float64 row errors E[0 .. cap], its ratio
@@ -479,6 +556,29 @@ class CodecEngine:
             yield out
         finally:
             self.lib.fc_engine_set_rate(self._h, None, 0, 1, None, None, None, None)
+
+    @contextlib.contextmanager
+    def _floor(self, floors, min_n_q: int, n_q_out: Optional[torch.Tensor], fused: bool = True, row_errors: Optional[torch.Tensor] = None,
+               stage_errors: Optional[torch.Tensor] = None, sub_quants: Optional[torch.Tensor] = None):
+        # an entry None of floors: the row is switched off (it keeps its cap)
+        """The engine's noise floor (fc_engine_set_floor) for the session push or the per-op hook made inside: a stage count per row chosen
+        on the device from the frames of that push; cleared on the way out, whatever happened, as _row_nq does.  floors: None (nothing is
+        set) or a checked list (floor_values); n_q_out: the device int32 [B] that receives the counts.  fused=False (or outputs given):
+        fc_engine_set_floor_form."""
+        if floors is None:
+            yield
+            return
+        B = len(floors)
+        off = [int(v is None) for v in floors]
+        self._check(self.lib.fc_engine_set_floor(self._h, (C.c_double * B)(*[0.0 if v is None else v for v in floors]), B, int(min_n_q),
+                                                 _ptr(n_q_out), self._stream()))
+        try:
+            if not fused or row_errors is not None or stage_errors is not None or sub_quants is not None or any(off):
+                self._check(self.lib.fc_engine_set_floor_form(self._h, int(not fused), _ptr(row_errors), _ptr(stage_errors), _ptr(sub_quants),
+                                                              (C.c_int32 * B)(*off) if any(off) else None, self._stream()))
+            yield
+        finally:
+            self.lib.fc_engine_set_floor(self._h, None, 0, 1, None, None)
 
     def _rate_in(self, target_snr_db, min_n_q, B: int, n_q: int, n_q_rows, per_frame: bool = False):
         """(ratios or None, min_n_q) of a call's target_snr_db / min_n_q, checked before anything reaches the device; a list of floats
@@ -839,15 +939,45 @@ class CodecEngine:
     # -- per-op entry points (tests) -----------------------------------------------------------
     @_on_device
     def rvq_encode(self, x: torch.Tensor, n_q: int, n_q_rows=None, beam: int = 1, return_paths: bool = False, target_snr_db=None,
-                   min_n_q: int = 1, per_frame: bool = False):
+                   min_n_q: int = 1, per_frame: bool = False, noise_floor_db=None, fused: bool = True):
         """x [N,D] -> (codes [n_q,N], quantized [N,D]).  target_snr_db (a list of B, or with n_q_rows one value or B; fc_rvq_encode_rate):
         the N rows are B utterances of N / B frames each, every one takes the stage count the rule picks (rate_pick; n_q_rows are the caps)
         -> (codes, quantized, dict(n_q_rows [B] i32, row_errors [B, n_q + 1] f64, stage_errors [n_q + 1, B, N / B] f32)).  n_q_rows (B entries): the N rows are B utterances of N / B frames each, utterance b
         with n_q_rows[b] stages.  beam (2, 4, 8): the search over the stages (fc_rvq_encode_beam) instead of the greedy quantiser;
         return_paths: also (paths [beam,n_q,N] i64, errors [beam,N]), every slot's final path and its fixed-order residual energy.
         per_frame (with target_snr_db): a count per frame (rate_pick_frames; min_n_q in [0, cap]); the dict also holds n_q_frames
-        [B, N / B] i32, n_codes_rows [B] i32 and achieved_errors [B] f64."""
+        [B, N / B] i32, n_codes_rows [B] i32 and achieved_errors [B] f64.
+        noise_floor_db (a list of B, or with n_q_rows one value or B): the push rule instead (floor_pick; fc_engine_set_floor): the N rows
+        are ONE push of B rows of N / B frames each -> (codes, quantized, dict(n_q_rows, row_errors, stage_errors)) as for target_snr_db,
+        plus sub_quants [n_q, B, D, N / B] in the dict.
+        fused=False runs the four-launch chain in place of the one fused launch (a push wider than 256 frames always does): same bits."""
         beam = rvq_beam_width(self.arch, beam)
+        if noise_floor_db is not None:
+            if target_snr_db is not None or per_frame:
+                raise EngineError("rvq_encode: noise_floor_db and target_snr_db are two rules (a floor per push, a rate per call): give one")
+            if return_paths:
+                raise EngineError("rvq_encode: return_paths and noise_floor_db are two hooks (fc_rvq_encode_beam, fc_rvq_encode_rate)")
+            rows_b = len(n_q_rows) if n_q_rows is not None else (1 if isinstance(noise_floor_db, numbers.Real) else len(noise_floor_db))
+            floors = floor_values(self.arch, noise_floor_db, rows_b)
+            if n_q_rows is not None:
+                n_q_rows = row_nq_list(self.arch, n_q_rows, rows_b, n_q)
+            min_n_q = rate_min_nq(self.arch, min_n_q, n_q, n_q_rows)
+            x = self._dev(x, torch.float32)
+            N, D = x.shape
+            if D != self.arch.codebook_dim:
+                raise EngineError(f"rvq_encode: rows must have {self.arch.codebook_dim} dims, got {D}")
+            if N % rows_b != 0:
+                raise EngineError(f"rvq_encode: {N} rows are not {rows_b} utterances of equal length")
+            codes = torch.empty((n_q, N), dtype=torch.int64, device=self.device)
+            quant = torch.empty((N, D), dtype=torch.float32, device=self.device)
+            out = dict(n_q_rows=torch.empty((rows_b,), dtype=torch.int32, device=self.device),
+                       row_errors=torch.empty((rows_b, n_q + 1), dtype=torch.float64, device=self.device),
+                       stage_errors=torch.empty((n_q + 1, rows_b, N // rows_b), dtype=torch.float32, device=self.device),
+                       sub_quants=torch.empty((n_q, rows_b, D, N // rows_b), dtype=torch.float32, device=self.device))
+            with self._row_nq(n_q_rows), self._floor(floors, min_n_q, out["n_q_rows"], fused, out["row_errors"], out["stage_errors"],
+                                                     out["sub_quants"]):
+                self._check(self.lib.fc_rvq_encode_rate(self._h, _ptr(x), N, n_q, beam, _ptr(codes), _ptr(quant), self._stream()))
+            return codes, quant, out
         if per_frame and target_snr_db is None:
             raise EngineError("rvq_encode: per_frame chooses a stage count per frame by target_snr_db: give a target")
         if return_paths and beam == 1:

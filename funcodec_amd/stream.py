@@ -15,7 +15,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .config import SEQ_FF, SEQ_HEADS
-from .engine import CodecEngine, EngineError, _on_device, _ptr, packed_refusal, row_nq_list, rvq_beam_width
+from .engine import (CodecEngine, EngineError, _on_device, _ptr, floor_refusal, floor_value, packed_refusal, rate_min_nq, row_nq_list,
+                     rvq_beam_width)
 
 
 def stream_refusal(arch, max_frames: Optional[int] = None) -> Optional[str]:
@@ -109,10 +110,14 @@ class _Session:
     _graph_family = ""        # the three calls of the kind's graph replay (set, enabled, counts)
 
     def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None, graph: bool = False,
-                 rvq_beam: Optional[int] = None):
+                 rvq_beam: Optional[int] = None, min_n_q: int = 1):
         why = stream_refusal(model.arch, max_frames)
         if why:
             raise EngineError(why)
+        #: the noise floor of every row's encode pushes in dB (None: the row has none and runs its fixed count); set on the engine around
+        #: each encode push while any row has one (the push rule of csrc/rvq_rate_kernels.h), min_n_q with it
+        self._floor_db: List[Optional[float]] = [None] * int(rows)
+        self._fused = True            # False: the four-launch chain in place of the fused launch (a measurement aid: same bits)
         #: width of the quantiser's search over the stages in this session's encode pushes (1: greedy); set on the engine around each of them
         self.rvq_beam = rvq_beam_width(model.arch, rvq_beam)
         if graph and max_frames is not None and self._family == "fc_stream":
@@ -131,7 +136,10 @@ class _Session:
         #: True while the library replays this session's steady pushes as captured HIP graphs (False with FC_SESSION_GRAPH=0)
         self.graph = False
         self._g: Optional[_GraphBuffers] = None         # the fixed buffers of a session opened with graph=True; None: nothing of it exists
+        self.min_n_q = rate_min_nq(self.arch, min_n_q, self.n_q)
         self._open(rows, max_chunk)
+        #: the stage counts the last encode push under a noise floor chose, device int32 [rows]: one of the session's fixed buffers
+        self._nq_table = torch.zeros(int(rows), dtype=torch.int32, device=self.device)
         if graph:
             self._graph_open(rows)
 
@@ -252,6 +260,37 @@ class _Session:
         """the width of the quantiser's search around one encode push; a session of width 1 does not touch the engine's at all"""
         return contextlib.nullcontext() if self.rvq_beam == 1 else self.engine._rvq_beam(self.rvq_beam)
 
+    def _checked_floor(self, db) -> Optional[float]:
+        """one row's noise_floor_db (None: no floor), or an EngineError before anything is changed"""
+        if db is None:
+            return None
+        why = floor_refusal(self.arch)
+        if why:
+            raise EngineError(why)
+        floor_value(self.arch, db)
+        return float(db)
+
+    def _push_floor(self):
+        """what an encode push sets on the engine: every row's floor D * 10^(dB / 10) (None: the row is switched off), or None when no
+        row has a floor (the push then does not touch the engine's floor at all)"""
+        if all(v is None for v in self._floor_db):
+            return None
+        return [None if v is None else floor_value(self.arch, v) for v in self._floor_db]
+
+    def _engine_floor(self):
+        """the engine's noise floor around one encode push; min_n_q is checked against the rows' caps before anything is set"""
+        floors = self._push_floor()
+        if floors is None:
+            return contextlib.nullcontext()
+        rate_min_nq(self.arch, self.min_n_q, self.n_q, self._row_nq)
+        return self.engine._floor(floors, self.min_n_q, self._nq_table, self._fused)
+
+    def _one_push(self, pieces, what: str) -> None:
+        """a packet carries ONE count, a push under a noise floor chooses one per push: such a call is one push"""
+        if len(pieces) > 1:
+            raise EngineError(f"{what}: encode(packed=True) under a noise floor takes what fits one push (max_chunk = {self.max_chunk} samples): "
+                              f"this call splits into {len(pieces)} pushes, each with a count of its own; nothing was changed")
+
     def _push_row_nq(self):
         """what a push sets on the engine: the rows' counts, or None when every row runs all n_q stages (the plain kernels)"""
         rows = self._row_nq
@@ -331,6 +370,14 @@ class CodecStream(_Session):
     A call whose frames would pass it raises before anything is pushed and changes nothing; ``reset`` starts the next utterance.  Without
     ``max_frames`` such a net is refused, with it any other net is.
 
+    Noise floor (``noise_floor_db``, ``min_n_q``; ``set_noise_floor``).  With a floor every encode push chooses a stage count per row on
+    the device, inside the push, from the row's frames of that push alone (the push rule of csrc/rvq_rate_kernels.h; ``engine.floor_pick``
+    restates it): the smallest count in [min_n_q, the row's cap] whose residual lies at or below ``D * 10^(dB / 10)`` per frame, min_n_q
+    for a row already below it, the best count where it is missed.  ``set_n_q`` remains the cap.  Row b of a push is what a session with
+    ``set_n_q`` = that count gives it.  ``last_n_q_rows`` is the device table [batch] of the last push's counts (nothing is read back);
+    ``encode(packed=True)`` hands it to the pack launch, so every packet carries its own count and ``decode_packed`` needs nothing else.
+    Such a packed call must fit one push (``max_chunk``): a packet carries one count.  One more launch per push.
+
     Graph replay (``graph=True``, off by default).  The library captures a steady push (neither the first of an utterance nor the
     final one) as a HIP graph and replays it for every later push with the same key: call form, width, parity of the side's push
     count, n_q, use_scale and every pointer.  The session therefore owns fixed device buffers sized for ``max_chunk``, a workspace and a
@@ -345,19 +392,40 @@ class CodecStream(_Session):
     _graph_family = "fc_graphstream"
 
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
-                 max_chunk: Optional[int] = None, max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None):
+                 max_chunk: Optional[int] = None, max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None,
+                 noise_floor_db=None, min_n_q: int = 1):
         self.batch = int(batch)
         rows = None
         if n_q is not None and not isinstance(n_q, numbers.Integral):       # a count per utterance: refused before anything is opened
             rows = row_nq_list(model.arch, n_q, self.batch)
             n_q = max(rows)
-        super().__init__(model, self.batch, n_q, max_chunk, max_frames, graph, rvq_beam)
+        super().__init__(model, self.batch, n_q, max_chunk, max_frames, graph, rvq_beam, min_n_q)
         self._row_nq = rows
+        self.set_noise_floor(noise_floor_db)
         self.reset(scale)
 
     def set_n_q(self, rows) -> None:
         """stage counts [batch], each in [1, n_q], of the pushes that follow; a refused call changes nothing"""
         self._row_nq = self._checked_row_nq(rows, self.batch)
+
+    def set_noise_floor(self, rows) -> None:
+        """noise_floor_db of the encode pushes that follow: one value for every utterance, one per utterance (an entry None: that row keeps
+        its fixed count), or None (no floor: the pushes launch what they always did); between pushes, in the middle of an utterance too.
+        A refused call changes nothing."""
+        if rows is None or isinstance(rows, numbers.Real):
+            rows = [rows] * self.batch
+        elif hasattr(rows, "tolist"):
+            rows = rows.tolist()
+        rows = list(rows)
+        if len(rows) != self.batch:
+            raise EngineError(f"noise_floor_db must hold one entry per row ({self.batch}), got {len(rows)}")
+        self._floor_db = [self._checked_floor(v) for v in rows]
+
+    @property
+    def last_n_q_rows(self) -> torch.Tensor:
+        """device int32 [batch]: the stage counts the last encode push under a noise floor chose (the session's own table: the next such
+        push overwrites it; nothing is read back)"""
+        return self._nq_table
 
     @_on_device
     def reset(self, scale: Optional[torch.Tensor] = None) -> None:
@@ -379,7 +447,7 @@ class CodecStream(_Session):
         enc = self._buf("enc_out", (B, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
         n = C.c_int(0)
         ws = self._push_ws()
-        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam():
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam(), self._engine_floor():
             self.engine._check(self.lib.fc_stream_encode(self._h, _ptr(wav), T, int(final), _ptr(codes), _ptr(quant), _ptr(enc), C.byref(n),
                                                          _ptr(ws), ws.numel(), self.engine._stream()))
         assert n.value == Tf
@@ -395,13 +463,15 @@ class CodecStream(_Session):
         (self-contained: ``decode_packed`` takes them); an empty list while the start-up is held back."""
         if packed:
             self._packed_check()
-        res = self._encode(wav, final, want_enc_out)
+        floor = self._push_floor() is not None
+        res = self._encode(wav, final, want_enc_out, one_push=packed and floor)
         if not packed:
             return res
         codes = res[0]
-        return res + (self._pack_rows(codes, None, self._row_nq) if codes.shape[-1] > 0 else [],)
+        counts = self._nq_table if floor else self._row_nq       # under a floor: the DEVICE counts of the push, every packet carries its k_b
+        return res + (self._pack_rows(codes, None, counts) if codes.shape[-1] > 0 else [],)
 
-    def _encode(self, wav: torch.Tensor, final: bool, want_enc_out: bool) -> Tuple[torch.Tensor, ...]:
+    def _encode(self, wav: torch.Tensor, final: bool, want_enc_out: bool, one_push: bool = False) -> Tuple[torch.Tensor, ...]:
         wav = self.engine._wav_in(wav)
         if wav.dim() == 2:
             wav = wav.unsqueeze(1)
@@ -415,6 +485,8 @@ class CodecStream(_Session):
             f"streaming encode: the first push of an utterance must hold at least {self.min_first_samples} samples (the offline call's "
             "reflected left padding spans them); shorter utterances go through the offline call"))
         frames = sum(self.engine.frames(p.shape[-1]) if f & FC_SLOT_FINAL else p.shape[-1] // self.hop for p, f in pieces)
+        if one_push:
+            self._one_push(pieces, "streaming encode")
         self._fits(self._enc, frames, "encode")
         self._enc.head = head
         if not pieces:
@@ -526,6 +598,11 @@ class StreamSlots(_Session):
       the most any slot may use and the first dimension of every slot's codes: a slot with fewer stages gets zeros at the later ones,
       everything else is what a session with that ``n_q`` gives it, and ``decode`` does not read its codes behind its count.
 
+    * ``open_slots(..., noise_floor_db=, min_n_q=)``, ``start(slot, noise_floor_db=)``, ``set_noise_floor(slot, db | None)``: a noise floor per
+      slot, as for ``CodecStream``: every encode push chooses the slot's stage count on the device from the slot's own frames of that push
+      (a silent caller costs ``min_n_q`` stages); ``set_n_q`` remains the cap; a slot without a floor keeps its fixed count; an idle slot
+      is left alone.  ``last_n_q_rows`` reads the counts back once, {slot: k}; the packets of ``encode(packed=True)`` carry them.
+
     Per slot: pushes are held back until ``min_first_samples`` / ``min_first_frames`` have arrived, then everything held comes
     out at once; an utterance that ends shorter than that raises (the offline call's job); what is longer than ``max_chunk`` is split.
     A call is checked as a whole before anything is pushed: a refused call changes nothing, and neither does a call whose first push
@@ -553,10 +630,17 @@ class StreamSlots(_Session):
     _graph_family = "fc_graphslots"
 
     def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
-                 graph: bool = False, rvq_beam: Optional[int] = None):
+                 graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1):
         self.slots = int(slots)
         self.pad_value = 0.0          # what the assembled batch holds behind a row's count and in idle rows (never read; a test aid)
-        super().__init__(model, self.slots, n_q, max_chunk, max_frames, graph, rvq_beam)
+        super().__init__(model, self.slots, n_q, max_chunk, max_frames, graph, rvq_beam, min_n_q)
+        if noise_floor_db is not None and not isinstance(noise_floor_db, numbers.Real):
+            noise_floor_db = noise_floor_db.tolist() if hasattr(noise_floor_db, "tolist") else list(noise_floor_db)
+            if len(noise_floor_db) != self.slots:
+                raise EngineError(f"noise_floor_db must hold one entry per slot ({self.slots}), got {len(noise_floor_db)}")
+        else:
+            noise_floor_db = [noise_floor_db] * self.slots
+        self._floor_db = [self._checked_floor(v) for v in noise_floor_db]
         self._enc = [_Side() for _ in range(self.slots)]
         self._dec = [_Side() for _ in range(self.slots)]
         self._scale = [1.0] * self.slots
@@ -573,9 +657,25 @@ class StreamSlots(_Session):
         slot = self._slot(slot)
         self._row_nq[slot] = self._checked_row_nq([n_q], 1)[0]
 
-    def start(self, slot: int, scale=None, n_q=None) -> None:
+    def set_noise_floor(self, slot: int, db) -> None:
+        """the slot's noise_floor_db for the encode pushes that follow (None: the slot returns to its fixed n_q); between pushes, in the
+        middle of an utterance too; a refused call changes nothing"""
+        slot = self._slot(slot)
+        self._floor_db[slot] = self._checked_floor(db)
+
+    @property
+    def last_n_q_rows(self) -> Dict[int, int]:
+        """{slot: the stage count the slot's last encode push under a noise floor chose} (0: none yet), by ONE read-back of the session's
+        device table; a slot that was idle in a push keeps its entry"""
+        return dict(enumerate(self._nq_table.tolist()))
+
+    _KEEP = object()
+
+    def start(self, slot: int, scale=None, n_q=None, noise_floor_db=_KEEP) -> None:
         slot = self._slot(slot)
         n_q = self.n_q if n_q is None else self._checked_row_nq([n_q], 1)[0]      # refused before the slot is touched
+        if noise_floor_db is not self._KEEP:                                      # not given: the slot keeps the floor it has
+            self._floor_db[slot] = self._checked_floor(noise_floor_db)
         self._row_nq[slot] = n_q
         self._enc[slot], self._dec[slot] = _Side(), _Side()
         self._scale[slot] = 1.0 if scale is None else float(torch.as_tensor(scale).reshape(()))
@@ -662,7 +762,7 @@ class StreamSlots(_Session):
         quant = self._buf("quantized", (S, Tf, D), torch.float32)
         enc = self._buf("enc_out", (S, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
         ws = self._push_ws()
-        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam():
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam(), self._engine_floor():
             self.engine._check(self.lib.fc_slots_encode(self._h, _ptr(wav), Tc, counts, flags, _ptr(scale), _ptr(codes), _ptr(quant), _ptr(enc),
                                                         _ptr(ws), ws.numel(), self.engine._stream()))
         out = {}
@@ -682,7 +782,8 @@ class StreamSlots(_Session):
         gathering its start-up, gives no packet."""
         if packed:
             self._packed_check()
-        res = self._encode(pushes, want_enc_out)
+        floor = self._push_floor() is not None
+        res = self._encode(pushes, want_enc_out, one_push=packed and floor)
         if not packed:
             return res
         slots = [slot for slot, r in res.items() if r[0].shape[-1] > 0]
@@ -692,9 +793,11 @@ class StreamSlots(_Session):
         codes = torch.zeros((self.n_q, len(slots), max(frames)), dtype=torch.int64, device=self.device)
         for j, slot in enumerate(slots):
             codes[:, j, :frames[j]] = res[slot][0]
-        return res, dict(zip(slots, self._pack_rows(codes, frames, [self._row_nq[slot] for slot in slots])))
+        # under a floor: the DEVICE counts of the push (a slot without a floor had its cap written there), every packet carries its k_b
+        counts = self._nq_table[torch.tensor(slots, device=self.device)] if floor else [self._row_nq[slot] for slot in slots]
+        return res, dict(zip(slots, self._pack_rows(codes, frames, counts)))
 
-    def _encode(self, pushes, want_enc_out: bool = False) -> Dict[int, Tuple[torch.Tensor, ...]]:
+    def _encode(self, pushes, want_enc_out: bool = False, one_push: bool = False) -> Dict[int, Tuple[torch.Tensor, ...]]:
         ch = self.engine.channels
 
         def as_ct(item):
@@ -707,6 +810,9 @@ class StreamSlots(_Session):
             return w, final
         pushes = {slot: as_ct(item) for slot, item in pushes.items()}
         plan = self._plan(self._enc, pushes, -1, self.hop, self.min_first_samples, "samples")
+        if one_push:
+            for slot, v in plan.items():
+                self._one_push(v[0], f"slot {slot}")
         outs = self._run(self._enc, plan, lambda rows: self._encode_call(rows, want_enc_out))
         cat = lambda parts, i, dim: torch.cat([p[i] for p in parts], dim) if len(parts) > 1 else parts[0][i]
         return {slot: (cat(parts, 0, -1), cat(parts, 1, 0)) + ((cat(parts, 2, 0),) if want_enc_out else ()) for slot, parts in outs.items()}

@@ -299,6 +299,35 @@ int fc_engine_set_rate_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out 
  * of another B or Tf, before its first launch; every decode push of a stream or slot session while a table is set. */
 int fc_engine_set_frame_nq(fc_engine* e, const int32_t* n_q_frames /* DEV i32 [B][Tf] or NULL */, int B, int Tf, void* stream);
 
+/* ---- a stage count per PUSH of a session, by a noise floor (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
+ * By the push rule of csrc/rvq_rate_kernels.h ("THE PUSH RULE"): every row of the encode pushes of both session kinds that follow
+ * (fc_stream_encode, fc_slots_encode, sessions made by fc_seqstream_create / fc_seqslots_create included) takes the smallest stage count
+ * in [min_nq, its cap] whose residual energy over the row's frames OF THAT PUSH lies at or below floor_b * frames_b; a row already at or
+ * below its floor takes min_nq; a missed floor takes the best count; a row without a frame in the push (an idle slot) is neither read nor
+ * written.  floor_rows [B] (host, copied): floor_b = D * 10^(noise_floor_db_b / 10), D the quantiser's input width, neither negative nor
+ * NaN; +inf is "always min_nq", 0 "the best count".  The cap of row b is its entry of fc_engine_set_row_nq, else the session's n_q; the
+ * width of fc_engine_set_rvq_beam composes (a row then keeps the first k_b codes of the full-depth path).  The rule is stateless: a
+ * count depends on the row's frames of the push alone.  Row b of codes, quantized and enc_out is what the same push with a row count of
+ * k_b gives (greedy: bit for bit, zeros in codes[k_b:]).  n_q_rows_out [B] (device, the caller's, valid until the floor is cleared)
+ * receives k_b; fc_codes_pack reads it as it is.  A push of at most 256 frames per row adds ONE launch to the push; a wider one runs
+ * four (the same device steps, the same bits).  Every launch reads frames, caps and floors from device memory, so a captured push
+ * (fc_graphstream_set, fc_graphslots_set) replays without a new capture when the floors change.  NULL floors clear it; with no floor
+ * set every call and push launches exactly what it launched before.
+ * It also applies to the per-op hook fc_rvq_encode_rate, on B rows of N / B frames (fc_engine_set_floor_form then gives the hook's outputs).
+ * Refused, before the first launch and changing nothing: an offline encode call while a floor is set (session pushes only); a floor
+ * together with a rate (fc_engine_set_rate), by either setter; a push of another B; min_nq outside [1, num_quantizers], above the
+ * session's n_q or above a row's cap; a NaN or negative floor; quantizer_conf.q0_ds_ratio > 1. */
+int fc_engine_set_floor(fc_engine* e, const double* floor_rows /* host [B] or NULL */, int B, int min_nq, int32_t* n_q_rows_out /* dev [B] */,
+                        void* stream);
+/* Given AFTER fc_engine_set_floor; cleared with it and by every new fc_engine_set_floor.  chain != 0: the four-launch form at every
+ * width (a measurement and test aid: same bits).  row_errors_out (dev f64 [B][n_q + 1]) and stage_errors_out (dev f32 [n_q + 1][B Tf]):
+ * optional outputs of the pushes that follow; the hook fc_rvq_encode_rate needs both (it has no workspace of its own).  sub_quants_out
+ * (dev f32 [n_q][B][D][Tf], optional): E_i[c_i] of every stage, 0 behind a row's count, from the hook alone.  off_rows (host
+ * i32 [B] or NULL): a row with a non-zero entry is switched off -- it takes its cap, as without a floor, and n_q_rows_out receives that
+ * (a slot without a floor beside slots that have one; device data, like the floors). */
+int fc_engine_set_floor_form(fc_engine* e, int chain, double* row_errors_out, float* stage_errors_out, float* sub_quants_out,
+                             const int32_t* off_rows /* host [B] or NULL */, void* stream);
+
 /* ---- the bit stream: one self-describing packet per row (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
  * csrc/code_pack_kernels.h states the packet rule (8-byte little-endian header: u32 frames, u8 k, u8 bits, u8 mode = 0, u8 0; payload
  * value t * k + i = codes[i][b][t] in `bits` bits each, LSB first, pad bits 0) and the device row (pitch = the largest packet rounded up

@@ -55,6 +55,11 @@ class FcLauraArch(C.Structure):
                 ("text_encoder", FcLauraStack), ("codec_lm", FcLauraStack), ("codec_encoder", FcLauraStack)]
 
 
+class FcSlotMeta(C.Structure):
+    """fc_slot_meta: the host part of a slot record (phases: 0 idle, 1 running, 2 ended)"""
+    _fields_ = [("layout", C.c_uint32), ("enc_phase", C.c_int32), ("dec_phase", C.c_int32), ("enc_frames", C.c_int32), ("dec_frames", C.c_int32)]
+
+
 # every symbol include/funcodec_amd.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -166,6 +171,12 @@ SYMBOLS = {
     "fc_graphslots_set": (C.c_int, [_P, C.c_int]),
     "fc_graphslots_enabled": (C.c_int, [_P]),
     "fc_graphslots_counts": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    # the slot record (csrc/slots_kernels.h): export n running calls of a session, import them in another (slots host int32 [n], records
+    # dev f32 [n][pitch], meta host fc_slot_meta [n]); _export_stream: rows of a lock-step session as slot records
+    "fc_slotrec_floats": (C.c_size_t, [_P, C.c_int, C.c_int]),
+    "fc_slotrec_export": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, C.POINTER(FcSlotMeta), _P]),
+    "fc_slotrec_import": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, C.POINTER(FcSlotMeta), _P]),
+    "fc_slotrec_export_stream": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, C.POINTER(FcSlotMeta), _P]),
     # LauraTTS generation (ABI version 5)
     "fc_laura_create": (C.c_int, [C.POINTER(FcLauraArch), C.c_int, C.POINTER(_P)]),
     "fc_laura_destroy": (None, [_P]),

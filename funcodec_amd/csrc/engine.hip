@@ -270,10 +270,29 @@ struct Session {
         for (Graph& g : graphs) (void)hipGraphExecDestroy(g.exec);
         graphs.clear();
     }
+
+    // The slot record (slots_kernels.h states it): the session's segment table, built at create (record_layout) and held in device
+    // memory, with room behind it for the named slots of one export / import call, which travel there in one copy in front of the launch.
+    struct Record {
+        std::vector<fc::SlotSeg> segs;
+        uint32_t layout = 0;                        // the fingerprint of the segment list (fc_slot_meta.layout)
+        size_t fixed = 0;                           // floats of a record without its cache planes
+        int enc_cols = 0, dec_cols = 0;             // cache rows per side: a record holds enc_cols * Fr(enc frames) + dec_cols * Fr(dec frames) more
+        int max_len = 0, max_rows = 0;              // the longest plain segment and the widest cache plane (they size the launch)
+        fc::SlotSeg* segs_dev = nullptr;            // [segs.size()], and behind it
+        fc::SlotRef* refs_dev = nullptr;            // [B]
+        std::vector<fc::SlotRef> refs;              // the host side of the copy
+        size_t floats(int enc_frames, int dec_frames) const {
+            return fixed + (size_t)enc_cols * fc::seq_cache_pitch(enc_frames) + (size_t)dec_cols * fc::seq_cache_pitch(dec_frames);
+        }
+    } rec;
     Session() = default;
     Session(const Session&) = delete;
     Session& operator=(const Session&) = delete;
-    ~Session() { drop_graphs(); }
+    ~Session() {
+        drop_graphs();
+        if (rec.segs_dev) (void)hipFree(rec.segs_dev);
+    }
 };
 
 // One streaming session (fc_stream_*): B utterances in lock-step.  The host side keeps only push counters.
@@ -2356,6 +2375,60 @@ TfCache tf_cache(const Session& s, bool dec, int pos) {
     return c;
 }
 
+// The segment list of the session's slot record, in the order slots_kernels.h states: what stream_layout gave one row, walked again.
+// Called once, at create, behind stream_layout; the table goes to device memory with room for one call's named slots behind it.
+int record_layout(fc_engine* e, Session* S) {
+    Session::Record& R = S->rec;
+    const int B = S->B;
+    uint32_t fp = fc::kSlotRecordLayoutSeed;
+    auto plain = [&](int kind, int side, size_t st_off, size_t half, int len) {
+        fc::SlotSeg g{};
+        g.st_off = (long long)st_off; g.half = (long long)half; g.rec_fixed = (long long)R.fixed;
+        g.slot_stride = len; g.rows = 1; g.len = len; g.st_pitch = len; g.side = side; g.enc_cols = R.enc_cols; g.dec_cols = R.dec_cols;
+        R.segs.push_back(g);
+        R.fixed += (size_t)len;
+        R.max_len = std::max(R.max_len, len);
+        fp = fc::slot_record_layout_step(fp, kind, side, len);
+    };
+    plain(fc::kSegScale, -1, 0, 0, 1);
+    const int F = fc::seq_cache_pitch(S->max_frames);
+    for (int side = 0; side < 2; ++side) {
+        const bool dec = side == 1;
+        for_each_conv(e, [&](const ConvVisit& v) {
+            const int pt = stream_pt(v.L);
+            if (v.dec != dec || !carries_context(v.role) || pt <= 0) return;
+            plain(fc::kSegCarry, side, S->carry.at(&v.L), (size_t)B * v.L.cin * pt, v.L.cin * pt);
+        });
+        const LstmBlock& lb = dec ? e->dec_lstm : e->enc_lstm;
+        const size_t lstm = dec ? S->dec_lstm_off : S->enc_lstm_off, BH = (size_t)B * lb.H, L = (size_t)e->arch.lstm_layers;
+        for (size_t l = 0; lb.H > 0 && l < L; ++l) {        // h [L][2][B][H], the half at parity 1; then c [L][B][H]
+            plain(fc::kSegH, side, lstm + (2 * l + 1) * BH, 0, lb.H);
+            plain(fc::kSegC, side, lstm + (2 * L + l) * BH, 0, lb.H);
+        }
+        if (S->max_frames <= 0) continue;
+        const TfBlock& tb = dec ? e->dec_tf : e->enc_tf;
+        const size_t kv = dec ? S->dec_kv_off : S->enc_kv_off, plane = (size_t)B * tb.C * F;
+        for (size_t p = 0; p < 2 * tb.layers.size(); ++p) {  // per block K then V, [B][C][F] each
+            fc::SlotSeg g{};
+            g.st_off = (long long)(kv + p * plane); g.rec_fixed = (long long)R.fixed;
+            g.slot_stride = tb.C * F; g.rows = tb.C; g.len = 0; g.st_pitch = F; g.side = side; g.enc_cols = R.enc_cols; g.dec_cols = R.dec_cols;
+            R.segs.push_back(g);
+            (dec ? R.dec_cols : R.enc_cols) += tb.C;
+            R.max_rows = std::max(R.max_rows, tb.C);
+            fp = fc::slot_record_layout_step(fp, (p & 1) ? fc::kSegV : fc::kSegK, side, tb.C);
+        }
+    }
+    R.layout = (fp & ~1u) | (S->max_frames > 0 ? 1u : 0u);
+    R.refs.resize(B);
+    const size_t seg_bytes = (R.segs.size() * sizeof(fc::SlotSeg) + 15) & ~(size_t)15;
+    char* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, seg_bytes + (size_t)B * sizeof(fc::SlotRef)));
+    R.segs_dev = (fc::SlotSeg*)dev;
+    R.refs_dev = (fc::SlotRef*)(dev + seg_bytes);
+    HIP_TRY(hipMemcpy(R.segs_dev, R.segs.data(), R.segs.size() * sizeof(fc::SlotSeg), hipMemcpyHostToDevice));
+    return 0;
+}
+
 // The GEMM behind every staging pass (stream_conv, slots_conv, ragged_conv): the layer's own kernel as a conv without padding over the
 // staged buf [B][cin][Tp], which holds T new columns per row behind the left context.  A transposed layer computes `groups` tap pairs
 // (group j = taps (x[j-1], x[j]) = staged columns (j, j + 1)) and drops trimL columns on the left.  With a GroupNorm behind it, which sees
@@ -3908,7 +3981,7 @@ int session_create(Session* s, fc_engine* e, const void* out, int rows, const ch
     if (!state || ((uintptr_t)state & 15) || state_bytes < s->state_floats * sizeof(float)) return fail(state_rule);
     s->state = (float*)state;
     s->ones.assign(rows, 1.f);
-    return 0;
+    return record_layout(e, s);
 }
 
 // The two fc_*_lstm_forward hooks: the SLSTM stage of a push alone (lstm.py:22-28 without the skip) on the session's LSTM state of one
@@ -4093,9 +4166,153 @@ int slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, int max_fr
     *out = Q.release();
     return 0;
 }
+
+// ---- the slot record (slots_kernels.h states it; include/funcodec_amd.h the calls) ----------------------------------------------
+// what the host knows of one row of a session of either kind, as the record sees it
+struct RowView { int enc_phase, dec_phase, enc_frames, dec_frames; };
+
+// the argument rules export and import share, checked before anything else; `who` begins every message
+int record_args(const Session& s, const std::string& who, int n, const int32_t* slots, const void* records, const void* meta) {
+    if (!slots || !records || !meta) return fail(who + ": null argument");
+    if (n < 1 || n > s.B) return fail(who + ": a call names 1 .. " + std::to_string(s.B) + " slots (the session's rows), got n = " + std::to_string(n));
+    std::vector<char> seen(s.B, 0);
+    for (int i = 0; i < n; ++i) {
+        const int b = slots[i];
+        if (b < 0 || b >= s.B) return fail(who + ": slot " + std::to_string(b) + ": out of range, this session has slots 0 .. " + std::to_string(s.B - 1));
+        if (seen[b]) return fail(who + ": slot " + std::to_string(b) + ": named twice in one call");
+        seen[b] = 1;
+    }
+    return 0;
+}
+
+int record_pitch(const Session& s, const std::string& who, int b, int enc_frames, int dec_frames, size_t pitch) {
+    const size_t need = s.rec.floats(enc_frames, dec_frames);
+    if (pitch < need)
+        return fail(who + ": slot " + std::to_string(b) + ": pitch_floats = " + std::to_string(pitch) + " is too small, the slot's record holds " +
+                    std::to_string(need) + " floats (fc_slotrec_floats)");
+    return 0;
+}
+
+// the named slots (s.rec.refs[0 .. n), filled by the caller) in one copy, then the one launch
+int record_launch(Session& s, const std::string& who, bool import, int n, float* records, size_t pitch, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int frames = 0;
+    for (int i = 0; i < n; ++i) frames = std::max(frames, std::max(s.rec.refs[i].enc_frames, s.rec.refs[i].dec_frames));
+    const long long longest = std::max((long long)s.rec.max_len, (long long)s.rec.max_rows * fc::seq_cache_pitch(frames));
+    // pageable memory that the next call overwrites: the runtime stages such a copy before it returns (slots_upload says why that holds)
+    hipError_t er = hipMemcpyAsync(s.rec.refs_dev, s.rec.refs.data(), (size_t)n * sizeof(fc::SlotRef), hipMemcpyHostToDevice, st);
+    if (er == hipSuccess)
+        er = fc::launch_slot_record(import, s.state, s.rec.segs_dev, (int)s.rec.segs.size(), s.rec.refs_dev, n, records, pitch, longest, st);
+    if (er != hipSuccess) return fail(who + ": slot record launch failed: " + hipGetErrorString(er));
+    return 0;
+}
+
+// fc_slotrec_export and fc_slotrec_export_stream: both kinds of session are one Session with one layout; view(b): the row as its kind
+// of session knows it.  The source is only read.
+template <typename View>
+int record_export(Session& s, const std::string& who, int enc_pushes, int dec_pushes, int n, const int32_t* slots, float* records, size_t pitch,
+                  fc_slot_meta* meta, void* stream, View&& view) {
+    if (record_args(s, who, n, slots, records, meta)) return 1;
+    std::vector<fc_slot_meta> out(n);                   // a refused call changes nothing, the caller's meta included
+    for (int i = 0; i < n; ++i) {
+        const int b = slots[i];
+        RowView v = view(b);
+        if (v.enc_phase == fc_slots::Poisoned || v.dec_phase == fc_slots::Poisoned)
+            return fail(who + ": slot " + std::to_string(b) + ": a push of this session failed after it had begun to write carries: the slot's state is "
+                        "invalid and is not exported; START begins its next utterance");
+        const bool enc_live = v.enc_phase == fc_slots::Running, dec_live = v.dec_phase == fc_slots::Running;
+        const bool cached = s.max_frames > 0;
+        fc_slot_meta& m = out[i];
+        m.layout = s.rec.layout; m.enc_phase = v.enc_phase; m.dec_phase = v.dec_phase;
+        m.enc_frames = cached && enc_live ? v.enc_frames : 0;
+        m.dec_frames = cached && dec_live ? v.dec_frames : 0;
+        if (record_pitch(s, who, b, m.enc_frames, m.dec_frames, pitch)) return 1;
+        fc::SlotRef& r = s.rec.refs[i];
+        r.slot = b; r.enc_frames = m.enc_frames; r.dec_frames = m.dec_frames;
+        r.bits = (enc_pushes & 1) | ((dec_pushes & 1) << 1) | (enc_live ? fc::kSlotRecEncLive : 0) | (dec_live ? fc::kSlotRecDecLive : 0);
+    }
+    if (record_launch(s, who, false, n, records, pitch, stream)) return 1;
+    std::copy(out.begin(), out.end(), meta);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
+
+size_t fc_slotrec_floats(const fc_slots* s, int enc_frames, int dec_frames) {
+    if (!s || enc_frames < 0 || dec_frames < 0) return 0;
+    const bool cached = s->max_frames > 0;
+    return s->rec.floats(cached ? enc_frames : 0, cached ? dec_frames : 0);
+}
+
+int fc_slotrec_export(fc_slots* Q, int n, const int32_t* slots, float* records, size_t pitch_floats, fc_slot_meta* meta, void* stream) {
+    if (slots_ready(Q)) return 1;
+    const bool cached = Q->max_frames > 0;
+    return record_export(*Q, "slot export", Q->enc_pushes, Q->dec_pushes, n, slots, records, pitch_floats, meta, stream, [&](int b) {
+        return RowView{Q->enc_phase[b], Q->dec_phase[b], cached ? Q->enc_frames[b] : 0, cached ? Q->dec_frames[b] : 0};
+    });
+}
+
+int fc_slotrec_export_stream(fc_stream* S, int n, const int32_t* rows, float* records, size_t pitch_floats, fc_slot_meta* meta, void* stream) {
+    if (stream_ready(S)) return 1;                      // a broken stream is refused here
+    if (S->enc_pushes < 0) return fail("stream export: fc_stream_reset first");
+    // the common counters as phases: the encoder side runs from its first push to its final one, the decoder side has no final push
+    const int enc_phase = S->enc_pushes == 0 ? fc_slots::Idle : S->enc_done ? fc_slots::Ended : fc_slots::Running;
+    const int dec_phase = S->dec_pushes == 0 ? fc_slots::Idle : fc_slots::Running;
+    return record_export(*S, "stream export", S->enc_pushes, S->dec_pushes, n, rows, records, pitch_floats, meta, stream,
+                         [&](int) { return RowView{enc_phase, dec_phase, S->enc_frames, S->dec_frames}; });
+}
+
+int fc_slotrec_import(fc_slots* Q, int n, const int32_t* slots, const float* records, size_t pitch_floats, const fc_slot_meta* meta, void* stream) {
+    if (slots_ready(Q)) return 1;
+    const std::string who = "slot import";
+    if (record_args(*Q, who, n, slots, records, meta)) return 1;
+    const bool cached = Q->max_frames > 0;
+    for (int i = 0; i < n; ++i) {
+        const fc_slot_meta& m = meta[i];
+        const std::string at = who + ": slot " + std::to_string(slots[i]) + ": ";
+        const bool rec_cached = (m.layout & 1u) != 0;
+        if (rec_cached && !cached)
+            return fail(at + "the record holds a key / value cache and this session has none (fc_seqslots_create opens one, with max_frames); nothing was changed");
+        if (!rec_cached && cached)
+            return fail(at + "the record holds no key / value cache and this session has one (max_frames = " + std::to_string(Q->max_frames) +
+                        "); nothing was changed");
+        if (m.layout != Q->rec.layout)
+            return fail(at + "the record's layout " + std::to_string(m.layout) + " is not this session's " + std::to_string(Q->rec.layout) +
+                        ": it comes from another architecture (the fingerprint of the segments' kinds and lengths); nothing was changed");
+        for (int side = 0; side < 2; ++side) {
+            const int phase = side ? m.dec_phase : m.enc_phase, frames = side ? m.dec_frames : m.enc_frames;
+            const char* name = side ? "decoder" : "encoder";
+            if (phase < fc_slots::Idle || phase > fc_slots::Ended) return fail(at + "the " + name + " phase of the record is none of idle, running, ended");
+            if (frames < 0 || (phase != fc_slots::Running && frames != 0))
+                return fail(at + "the " + name + " frames of the record: a side that is not running holds 0 frames, a running one 0 or more");
+            if (frames > 0 && !cached) return fail(at + "the record holds " + std::to_string(frames) + " frames and this session has no key / value cache");
+            if (frames > Q->max_frames)
+                return fail(at + "this record of " + std::to_string(frames) + " " + name + " frames would take the utterance to " + std::to_string(frames) +
+                            " frames, past the session's max_frames = " + std::to_string(Q->max_frames) +
+                            " (the size of its key / value cache); nothing was changed");
+        }
+        if (record_pitch(*Q, who, slots[i], m.enc_frames, m.dec_frames, pitch_floats)) return 1;
+    }
+    for (int i = 0; i < n; ++i) {
+        const fc_slot_meta& m = meta[i];
+        fc::SlotRef& r = Q->rec.refs[i];
+        r.slot = slots[i]; r.enc_frames = m.enc_frames; r.dec_frames = m.dec_frames;
+        // the halves this session's next pushes read
+        r.bits = (Q->enc_pushes & 1) | ((Q->dec_pushes & 1) << 1) | (m.enc_phase == fc_slots::Running ? fc::kSlotRecEncLive : 0) |
+                 (m.dec_phase == fc_slots::Running ? fc::kSlotRecDecLive : 0);
+    }
+    if (record_launch(*Q, who, true, n, const_cast<float*>(records), pitch_floats, stream)) {
+        for (int i = 0; i < n; ++i) Q->enc_phase[slots[i]] = Q->dec_phase[slots[i]] = (char)fc_slots::Poisoned;      // as a failed push does, for the slots named
+        return 2;                                       // not a refusal: the caller's own books must follow (include/funcodec_amd.h)
+    }
+    for (int i = 0; i < n; ++i) {                       // whatever the slot held is abandoned, as START does
+        const int b = slots[i];
+        Q->enc_phase[b] = (char)meta[i].enc_phase; Q->dec_phase[b] = (char)meta[i].dec_phase;
+        if (cached) { Q->enc_frames[b] = meta[i].enc_frames; Q->dec_frames[b] = meta[i].dec_frames; }
+    }
+    return 0;
+}
 
 int fc_slots_create(fc_engine* e, int S, int max_chunk_samples, int n_q, void* state, size_t state_bytes, fc_slots** out) {
     return slots_create(e, S, max_chunk_samples, n_q, 0, state, state_bytes, "slot state: a 16-byte aligned device buffer of fc_slots_state_bytes() bytes", out);

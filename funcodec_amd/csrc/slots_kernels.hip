@@ -86,7 +86,80 @@ __global__ __launch_bounds__(256) void slots_start_kernel(const int* __restrict_
     if (scale_out && threadIdx.x == 0) scale_out[b] = scale_in ? scale_in[b] : 1.f;
 }
 
+// The slot record (slots_kernels.h states it).  One workgroup = one chunk of kSlotRecChunk record floats of one segment of one named
+// slot; a lane takes four record floats at a time, in groups that begin where the RECORD is 16-byte aligned.  A group that lies whole
+// inside one row (and, for a cache plane, inside the frames in use) moves as one 16-byte load and one 16-byte store: aligned on the
+// record side by construction, and on the state side aligned where the state is 16-byte aligned too, else a dword-aligned vector
+// access (row offsets such as b * cin * pt are generally not multiples of four floats).  The head in front of the first aligned
+// group, the tail, the groups across a row's end and the zero columns move as single floats.  Every float has one writer.
+template <bool IMPORT>
+__global__ __launch_bounds__(256) void slot_record_kernel(float* __restrict__ state, const SlotSeg* __restrict__ segs, const SlotRef* __restrict__ refs,
+                                                          float* __restrict__ records, size_t pitch) {
+    const SlotSeg sg = segs[blockIdx.y];
+    const SlotRef rf = refs[blockIdx.z];
+    const int dec = sg.side == 1;
+    const bool live = sg.side < 0 || (rf.bits & (dec ? kSlotRecDecLive : kSlotRecEncLive));
+    if (IMPORT && !live) return;                                   // a side that is not Running: the destination keeps what it has
+    const int frames = dec ? rf.dec_frames : rf.enc_frames;
+    const int fr_e = (rf.enc_frames + 15) & ~15, fr_d = (rf.dec_frames + 15) & ~15;      // seq_cache_pitch of either side
+    const bool plane = sg.len == 0;
+    const int row = plane ? (dec ? fr_d : fr_e) : sg.len;          // record floats per row
+    const int used = plane ? frames : sg.len;                      // of which the state holds this many
+    const long long total = (long long)sg.rows * row;
+    const long long j_lo = (long long)blockIdx.x * kSlotRecChunk;
+    if (j_lo >= total) return;
+    const long long j_hi = min(total, j_lo + kSlotRecChunk);
+    float* rec = records + (size_t)blockIdx.z * pitch + sg.rec_fixed + (long long)sg.enc_cols * fr_e + (long long)sg.dec_cols * fr_d;
+    const int par = (rf.bits >> dec) & 1;
+    float* st = state + sg.st_off + par * sg.half + (long long)rf.slot * sg.slot_stride;
+    const int st_pitch = plane ? sg.st_pitch : sg.len;
+    const int head = (int)((4 - (((uintptr_t)rec >> 2) & 3)) & 3);  // record floats in front of its first 16-byte boundary
+    auto one = [&](long long j) __attribute__((always_inline)) {
+        const int r = (int)(j / row), f = (int)(j - (long long)r * row);
+        if (IMPORT) {
+            if (f < used) st[(long long)r * st_pitch + f] = rec[j];
+        } else {
+            rec[j] = (live && f < used) ? st[(long long)r * st_pitch + f] : 0.f;
+        }
+    };
+    // groups: g = 0 is the head [0, head), group g >= 1 holds [head + 4 (g - 1), head + 4 g); the chunk's groups are those that BEGIN in it
+    for (long long g = j_lo / 4 + threadIdx.x; ; g += 256) {
+        const long long a = g == 0 ? 0 : head + 4 * (g - 1), b = min(total, head + 4 * g);
+        if (a >= j_hi || a >= total) break;
+        if (a < j_lo) continue;                                    // begins in the chunk in front: its workgroup moves it
+        const int r = (int)(a / row), f = (int)(a - (long long)r * row);
+        if (b - a == 4 && f + 3 < row && (IMPORT ? f + 3 < used : (live && f + 3 < used))) {
+            float* s = st + (long long)r * st_pitch + f;
+            float* d = rec + a;
+            const bool aligned = (((uintptr_t)s) & 15) == 0;
+            if (IMPORT) {
+                const f32x4 v = *(const f32x4*)d;
+                if (aligned) *(f32x4*)s = v; else *(f32x4u*)s = v;
+            } else {
+                const f32x4 v = aligned ? *(const f32x4*)s : (f32x4)(*(const f32x4u*)s);
+                *(f32x4*)d = v;
+            }
+        } else {
+            for (long long j = a; j < b; ++j) one(j);
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_slot_record(bool import, float* state, const SlotSeg* segs, int n_segs, const SlotRef* refs, int n, float* records, size_t pitch,
+                              long long max_floats, hipStream_t st) {
+    if (!state || !segs || !refs || !records || n_segs <= 0 || n_segs > 65535 || n <= 0 || n > 65535 || max_floats <= 0) return hipErrorInvalidValue;
+    if ((uintptr_t)records & 3) return hipErrorInvalidValue;
+    // One grid for all segments, so x is sized by the longest one: beside a full cache plane (some 190 chunks) every short segment --
+    // scale, carry, h, c -- starts workgroups that read their segment's length and return at once, and the zeros of a side that is not
+    // Running go out as single floats.  Both are left as they are: the empty workgroups cost no memory traffic, the zeros are a few KB,
+    // and the large records, the only ones whose time is not the launch's, move at HBM rate (profiles/slot_record.txt).
+    const dim3 grid((unsigned)((max_floats + kSlotRecChunk - 1) / kSlotRecChunk), n_segs, n);      // a group is moved by the chunk it begins in
+    if (import) hipLaunchKernelGGL(slot_record_kernel<true>, grid, dim3(256), 0, st, state, segs, refs, records, pitch);
+    else hipLaunchKernelGGL(slot_record_kernel<false>, grid, dim3(256), 0, st, state, segs, refs, records, pitch);
+    return hipGetLastError();
+}
 
 hipError_t launch_slots_stage(const SlotsStage& s, hipStream_t st) {
     if (s.S <= 0 || s.S > 65535 || s.C <= 0 || s.T <= 0 || s.pt < 0 || s.stride < 1 || !s.len.lens || !s.flags || s.len.add != 0) return hipErrorInvalidValue;

@@ -9,11 +9,14 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import json
 import numbers
+import struct
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from . import _lib
 from .config import SEQ_FF, SEQ_HEADS
 from .engine import (CodecEngine, EngineError, _on_device, _ptr, floor_refusal, floor_value, packed_refusal, rate_min_nq, row_nq_list,
                      rvq_beam_width)
@@ -100,6 +103,19 @@ class _Side:
 
     def __init__(self):
         self.head, self.started, self.ended, self.frames = [], False, False, 0      # frames: pushed so far (read where max_frames bounds them)
+
+    @property
+    def running(self) -> bool:
+        """the library holds state for this side: its first push is taken and its final one is not"""
+        return self.started and not self.ended
+
+    def copy(self, head=None, device=None) -> "_Side":
+        """a copy that shares nothing that changes (the held pieces are never written in place); head: other pieces in place of its own"""
+        sd = _Side()
+        pieces = self.head if head is None else head
+        sd.head = [t if device is None else t.to(device) for t in pieces]
+        sd.started, sd.ended, sd.frames = self.started, self.ended, self.frames
+        return sd
 
 
 class _Session:
@@ -331,6 +347,28 @@ class _Session:
             tokens = self.engine.unpack_codes(buf, Tf, self.n_q)
         return tokens, frames, counts
 
+    # -- the slot record (csrc/slots_kernels.h states it): what both kinds of session share of export
+    def _record_floats(self, enc: _Side, dec: _Side) -> int:
+        """the length of the record of a slot whose sides are `enc` and `dec` (slot_record_floats, its segment list walked once per session)"""
+        shape = getattr(self, "_rec_shape", None)
+        if shape is None:
+            segs = slot_record_segments(self.arch, self.max_frames is not None)
+            cols = lambda side: sum(n for kind, sd, n in segs if kind in "KV" and sd == side)
+            shape = self._rec_shape = (sum(n for kind, _, n in segs if kind not in "KV"), cols("encoder"), cols("decoder"))
+        pitch = lambda sd: (sd.frames + 15) // 16 * 16 if sd.running else 0
+        return shape[0] + shape[1] * pitch(enc) + shape[2] * pitch(dec)
+
+    def _export_rows(self, call, rows: List[int], sides) -> Tuple[torch.Tensor, list]:
+        """the records of `rows` (each with a side Running) by ONE launch: (device floats [n, pitch], [meta tuple]); sides: per row its
+        (_Side, _Side), which size the buffer by the frames in use, never by max_frames"""
+        n = len(rows)
+        pitch = -(-max(self._record_floats(e, d) for e, d in sides) // 4) * 4        # rows of the buffer begin 16-byte aligned
+        buf = torch.empty((n, pitch), dtype=torch.float32, device=self.device)
+        metas = (_lib.FcSlotMeta * n)()
+        with self._push_stream():
+            self.engine._check(call(self._h, n, (C.c_int32 * n)(*rows), _ptr(buf), pitch, metas, self.engine._stream()))
+        return buf, [tuple(int(getattr(m, f)) for f, _ in _lib.FcSlotMeta._fields_) for m in metas]
+
     def _lstm_scratch(self, x: torch.Tensor) -> torch.Tensor:
         B, H, T = x.shape
         return self._scratch(4 * (T * B * 4 * H + 2 * B * H * T) + (1 << 20))
@@ -436,6 +474,23 @@ class CodecStream(_Session):
                 raise EngineError(f"scale must hold one value per utterance ({self.batch}), got {sc.numel()}")
         self.engine._check(self.lib.fc_stream_reset(self._h, _ptr(sc), self.engine._stream()))
         self._enc, self._dec = _Side(), _Side()       # pushes held back until the start-up length has arrived
+        self._scale_rows = sc                         # the utterances' scales as given (None: 1), for export
+
+    @_on_device
+    def export(self, row: int) -> "SlotRecord":
+        """Utterance `row` of this lock-step session as a ``SlotRecord``, which a slot session of a model with the same architecture
+        imports (``StreamSlots.import_slot``) and continues bit for bit; this session is only read and goes on as before."""
+        if not isinstance(row, int) or not 0 <= row < self.batch:
+            raise EngineError(f"this session streams utterances 0 .. {self.batch - 1}, got {row!r}")
+        enc = self._enc.copy([x[row] for x in self._enc.head])
+        dec = self._dec.copy([x[row] for x in self._dec.head])
+        floats = meta = None
+        if enc.running or dec.running:
+            buf, metas = self._export_rows(self.lib.fc_slotrec_export_stream, [row], [(enc, dec)])
+            meta = metas[0]
+            floats = buf[0, :self._record_floats(enc, dec)].clone()
+        scale = 1.0 if self._scale_rows is None else float(self._scale_rows[row])
+        return SlotRecord(floats, meta, enc, dec, self.n_q if self._row_nq is None else self._row_nq[row], self._floor_db[row], scale)
 
     # -- encode --------------------------------------------------------------------------------
     def _encode_call(self, wav: torch.Tensor, final: bool, want_enc_out: bool = False):
@@ -680,6 +735,94 @@ class StreamSlots(_Session):
         self._enc[slot], self._dec[slot] = _Side(), _Side()
         self._scale[slot] = 1.0 if scale is None else float(torch.as_tensor(scale).reshape(()))
         self._poisoned[slot] = False
+
+    # -- the slot record: export a running call, import it in another session (csrc/slots_kernels.h states the record) ------------
+    def _exportable(self, slot) -> int:
+        slot = self._slot(slot)
+        if self._poisoned[slot]:
+            raise EngineError(f"slot {slot}: a push of this session failed inside the library: the slot's state is invalid and is not exported; "
+                              f"start({slot}) begins the next utterance")
+        return slot
+
+    @_on_device
+    def export(self, slot: int) -> "SlotRecord":
+        """Everything the slot's utterance in flight owns, as a ``SlotRecord``: the device floats of the library's record and their meta
+        (none while the slot still gathers its start-up: its record is the held pieces alone), the held-back pieces and counters of both
+        sides, the slot's n_q, noise floor and scale.  The slot is only read and goes on as before, so export + import is also a fork."""
+        slot = self._exportable(slot)
+        enc, dec = self._enc[slot].copy(), self._dec[slot].copy()
+        floats = meta = None
+        if enc.running or dec.running:
+            buf, metas = self._export_rows(self.lib.fc_slotrec_export, [slot], [(enc, dec)])
+            meta = metas[0]
+            floats = buf[0, :self._record_floats(enc, dec)].clone()
+        return SlotRecord(floats, meta, enc, dec, self._row_nq[slot], self._floor_db[slot], self._scale[slot])
+
+    def _importable(self, slot, n_q: int, floor) -> int:
+        """what import_slot and migrate refuse before touching anything"""
+        slot = self._slot(slot)
+        if any(self._poisoned):
+            bad = [b for b, p in enumerate(self._poisoned) if p]
+            raise EngineError(f"slot {slot}: a push of this session failed inside the library (slots {bad} await start()); it takes no record "
+                              "until they are restarted; nothing was changed")
+        if n_q > self.n_q:
+            raise EngineError(f"slot {slot}: the record's n_q = {n_q} exceeds this session's n_q = {self.n_q} (the first dimension of its codes); "
+                              "nothing was changed")
+        self._checked_floor(floor)
+        return slot
+
+    def _adopt(self, slot: int, enc: _Side, dec: _Side, n_q: int, floor, scale: float) -> None:
+        """the wrapper's side of an import: whatever the slot held is abandoned, as start() does"""
+        self._row_nq[slot], self._floor_db[slot], self._scale[slot] = int(n_q), floor, float(scale)
+        self._enc[slot], self._dec[slot] = enc.copy(device=self.device), dec.copy(device=self.device)
+        self._poisoned[slot] = False
+
+    def _import_rows(self, slots: List[int], buf: torch.Tensor, metas) -> None:
+        n = len(slots)
+        arr = (_lib.FcSlotMeta * n)(*[_lib.FcSlotMeta(*m) for m in metas])
+        with self._push_stream():
+            rc = self.lib.fc_slotrec_import(self._h, n, (C.c_int32 * n)(*slots), _ptr(buf), buf.shape[-1], arr, self.engine._stream())
+        if rc not in (0, 1):                            # 1: a refusal, nothing changed.  Anything else: the library has invalidated the slots it named
+            for b in slots:
+                self._poisoned[b] = True
+        self.engine._check(rc)
+
+    @_on_device
+    def import_slot(self, slot: int, rec: "SlotRecord") -> None:
+        """Slot `slot` takes the call that `rec` holds -- from any ``StreamSlots`` (other slots, max_chunk, max_frames, graph=) or
+        ``CodecStream`` of a model with the same architecture -- and abandons what it held, as ``start`` does; the call then goes on bit
+        for bit as if it had never moved.  Refused before anything is touched: a record whose n_q exceeds the session's, a session
+        with invalidated slots, and whatever the library refuses (another layout, frames past max_frames, cache against no cache)."""
+        slot = self._importable(slot, rec.n_q, rec.noise_floor_db)
+        if rec.floats is not None:
+            floats = self.engine._dev(rec.floats, torch.float32).reshape(1, -1)
+            self._import_rows([slot], floats, [rec.meta])
+        self._adopt(slot, rec.enc, rec.dec, rec.n_q, rec.noise_floor_db, rec.scale)
+
+    @_on_device
+    def migrate(self, dst: "StreamSlots", mapping: Dict[int, int]) -> None:
+        """{slot here: slot of dst}: the named calls continue in `dst` -- ONE export launch here, ONE import launch there, the floats
+        never leave the device, the buffer sized by the largest frame count among the named slots.  Frees nothing: the slots here go on
+        as before (``start`` reuses them).  Checked as a whole before anything is touched.  `dst` may be this session (slots copied or
+        exchanged in place): every record is exported before any is imported, and the wrapper's state is taken before any slot adopts."""
+        pairs = [(self._exportable(a), b) for a, b in mapping.items()]
+        seen = set()
+        for a, b in pairs:
+            dst._importable(b, self._row_nq[a], self._floor_db[a])
+            if b in seen:
+                raise EngineError(f"slot {b}: named twice as a destination; nothing was changed")
+            seen.add(b)
+        moving = [(a, b) for a, b in pairs if self._enc[a].running or self._dec[a].running]
+        if moving:
+            buf, metas = self._export_rows(self.lib.fc_slotrec_export, [a for a, _ in moving], [(self._enc[a], self._dec[a]) for a, _ in moving])
+            if buf.device != dst.device:
+                buf = buf.to(dst.device)
+            with torch.cuda.device(dst.device):
+                dst._import_rows([b for _, b in moving], buf, metas)
+        # what the wrapper keeps, taken before any slot adopts: dst may be this session, a destination may be another pair's source
+        held = [(b, self._enc[a].copy(), self._dec[a].copy(), self._row_nq[a], self._floor_db[a], self._scale[a]) for a, b in pairs]
+        for item in held:
+            dst._adopt(*item)
 
     # -- what CodecStream does for its batch, per slot ------------------------------------------------
     def _plan(self, sides, pushes, tdim, unit, min_first, what):
@@ -1021,3 +1164,121 @@ def stage_slot_row(layer, carry, row, start: bool, final: bool, tp: int):
     if extra:
         buf = F.pad(buf[None], (0, extra), "reflect")[0]
     return torch.cat([buf, row.new_zeros(row.shape[0], tp - buf.shape[-1])], -1), new_carry
+
+
+# ---- the slot record, restated in Python (csrc/slots_kernels.h is the specification; tests/test_slot_record_host.py counts it by hand) ----
+def slot_record_segments(arch, cached: bool):
+    """[(kind, side, floats)] of the library's slot record in its order: the scale, then per side (encoder, decoder) every carried conv's
+    cin * carry floats, per LSTM layer h and c, and with a key / value cache per transformer block K and V, whose entry is the floats
+    per cached frame column (C): such a plane holds C * seq_cache_pitch(frames of the side) floats."""
+    segs = [("scale", None, 1)]
+    tf = arch.lstm_layers > 0 and arch.seq_model == "transformer"
+    for side in ("encoder", "decoder"):
+        segs += [("carry", side, L["cin"] * L["carry"]) for L in conv_layers(arch) if L["side"] == side and L["carry"] > 0]
+        for _ in range(0 if tf else arch.lstm_layers):
+            segs += [("h", side, arch.bottleneck_channels), ("c", side, arch.bottleneck_channels)]
+        for _ in range(arch.lstm_layers if tf and cached else 0):
+            segs += [("K", side, arch.bottleneck_channels), ("V", side, arch.bottleneck_channels)]
+    return segs
+
+
+def slot_record_floats(arch, enc_frames: int = 0, dec_frames: int = 0, cached: bool = False) -> int:
+    """the length of a slot record (fc_slotrec_floats): a side that is not running counts 0 frames"""
+    pitch = {"encoder": (int(enc_frames) + 15) // 16 * 16, "decoder": (int(dec_frames) + 15) // 16 * 16}
+    return sum(n * pitch[side] if kind in "KV" else n for kind, side, n in slot_record_segments(arch, cached))
+
+
+SLOT_RECORD_MAGIC = b"FCSLOTRC"
+SLOT_RECORD_VERSION = 1
+#: what a record's tensors may be: the floats and held-back audio or embeddings (float32), held-back codes (int64)
+SLOT_RECORD_DTYPES = {"float32": torch.float32, "int64": torch.int64}
+
+
+class SlotRecord:
+    """One call in flight, taken out of its session (``StreamSlots.export`` / ``CodecStream.export``; ``StreamSlots.import_slot`` puts it
+    into another):
+
+    * ``floats``: the library's slot record on the device (csrc/slots_kernels.h states it), cut to the frames in use, and ``meta``:
+      (layout, enc_phase, dec_phase, enc_frames, dec_frames) of fc_slot_meta; both None for a slot still gathering its start-up, which
+      has no device state yet;
+    * ``enc`` / ``dec``: what the wrapper keeps per side -- the held-back start-up pieces, started, ended, frames;
+    * ``n_q``, ``noise_floor_db``, ``scale``: the slot's stage count, noise floor and volume scale.
+
+    The stage counts the last push chose under a noise floor do not travel.  ``to_bytes`` / ``from_bytes`` take it through host memory.
+    ``meta[0]`` tells architectures apart, not checkpoints: a record continues correctly only under the weights it was made with."""
+
+    def __init__(self, floats, meta, enc: _Side, dec: _Side, n_q: int, noise_floor_db, scale: float):
+        self.floats, self.meta, self.enc, self.dec = floats, (None if meta is None else tuple(int(v) for v in meta)), enc, dec
+        self.n_q, self.noise_floor_db, self.scale = int(n_q), (None if noise_floor_db is None else float(noise_floor_db)), float(scale)
+
+    def _tensors(self):
+        return ([] if self.floats is None else [self.floats]) + self.enc.head + self.dec.head
+
+    def to_bytes(self) -> bytes:
+        """magic, version, a JSON header, then the raw little-endian tensors: the record's floats and the held pieces"""
+        side = lambda sd: {"started": sd.started, "ended": sd.ended, "frames": sd.frames,
+                           "head": [{"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")} for t in sd.head]}
+        header = json.dumps({"meta": self.meta, "floats": None if self.floats is None else int(self.floats.numel()), "n_q": self.n_q,
+                             "noise_floor_db": self.noise_floor_db, "scale": self.scale, "enc": side(self.enc), "dec": side(self.dec)}).encode()
+        body = b"".join(t.detach().cpu().contiguous().numpy().tobytes() for t in self._tensors())
+        return SLOT_RECORD_MAGIC + struct.pack("<II", SLOT_RECORD_VERSION, len(header)) + header + body
+
+    @classmethod
+    def from_bytes(cls, blob: bytes, device=None) -> "SlotRecord":
+        blob = bytes(blob)
+        n = len(SLOT_RECORD_MAGIC)
+        if blob[:n] != SLOT_RECORD_MAGIC:
+            raise EngineError(f"SlotRecord.from_bytes: bad magic {blob[:n]!r}, a slot record begins with {SLOT_RECORD_MAGIC!r}")
+        if len(blob) < n + 8:
+            raise EngineError("SlotRecord.from_bytes: the blob ends inside its header")
+        version, hlen = struct.unpack_from("<II", blob, n)
+        if version != SLOT_RECORD_VERSION:
+            raise EngineError(f"SlotRecord.from_bytes: version {version} is not understood, this library reads version {SLOT_RECORD_VERSION}")
+        pos = n + 8
+        try:
+            h = json.loads(blob[pos:pos + hlen].decode())
+            sides_h = [h["enc"], h["dec"]]
+            pieces = [(list(p["shape"]), p["dtype"]) for sd in sides_h for p in sd["head"]]
+            for sd in sides_h:
+                bool(sd["started"]), bool(sd["ended"]), int(sd["frames"])
+            int(h["n_q"]), float(h["scale"]), h["meta"], h["floats"], h["noise_floor_db"]
+        except (ValueError, KeyError, TypeError) as err:
+            raise EngineError(f"SlotRecord.from_bytes: the header is not a slot record's ({type(err).__name__}: {err})") from None
+        if h["meta"] is not None and not (isinstance(h["meta"], list) and len(h["meta"]) == 5 and all(isinstance(v, int) for v in h["meta"])):
+            raise EngineError(f"SlotRecord.from_bytes: header field meta holds five integers or null, got {h['meta']!r}")
+        if h["floats"] is not None and not (isinstance(h["floats"], int) and h["floats"] >= 0):
+            raise EngineError(f"SlotRecord.from_bytes: header field floats is a count or null, got {h['floats']!r}")
+        if (h["floats"] is None) != (h["meta"] is None):
+            raise EngineError("SlotRecord.from_bytes: header fields floats and meta travel together")
+        if h["noise_floor_db"] is not None and not isinstance(h["noise_floor_db"], (int, float)):
+            raise EngineError(f"SlotRecord.from_bytes: header field noise_floor_db is a number or null, got {h['noise_floor_db']!r}")
+        for shape, dtype in pieces:
+            if dtype not in SLOT_RECORD_DTYPES:
+                raise EngineError(f"SlotRecord.from_bytes: header field dtype of a held piece is one of {sorted(SLOT_RECORD_DTYPES)}, got {dtype!r}")
+            if not all(isinstance(v, int) and v >= 0 for v in shape):
+                raise EngineError(f"SlotRecord.from_bytes: header field shape of a held piece holds counts, got {shape!r}")
+        pos += hlen
+
+        def take(shape, dtype):
+            nonlocal pos
+            dt = SLOT_RECORD_DTYPES[dtype]
+            count = 1
+            for v in shape:
+                count *= int(v)
+            nbytes = count * torch.empty((), dtype=dt).element_size()
+            if pos + nbytes > len(blob):
+                raise EngineError("SlotRecord.from_bytes: the blob is shorter than its header says")
+            t = torch.frombuffer(bytearray(blob[pos:pos + nbytes]), dtype=dt).reshape(shape) if count else torch.empty(shape, dtype=dt)
+            pos += nbytes
+            return t if device is None else t.to(device)
+
+        floats = None if h["floats"] is None else take([h["floats"]], "float32")
+        sides = []
+        for key in ("enc", "dec"):
+            sd = _Side()
+            sd.started, sd.ended, sd.frames = bool(h[key]["started"]), bool(h[key]["ended"]), int(h[key]["frames"])
+            sd.head = [take(p["shape"], p["dtype"]) for p in h[key]["head"]]
+            sides.append(sd)
+        if pos != len(blob):
+            raise EngineError("SlotRecord.from_bytes: the blob is longer than its header says")
+        return cls(floats, h["meta"], sides[0], sides[1], h["n_q"], h["noise_floor_db"], h["scale"])

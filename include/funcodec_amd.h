@@ -572,6 +572,38 @@ int  fc_graphslots_set(fc_slots* s, int on);
 int  fc_graphslots_enabled(const fc_slots* s);
 int  fc_graphslots_counts(const fc_slots* s, int64_t counts[4]);
 
+/* ---- the slot record: export a running call and import it in another session ----------------------------------------------------
+ * (entry points added without a struct change: FC_ABI_VERSION stays 7)
+ * A slot record is a copy of everything one utterance in flight owns: a flat run of floats in a fixed order -- the slot's scale, then
+ * per side the read half of every conv's carry, (h, c) of every LSTM layer and, with a key / value cache, K and V of every block at
+ * the pitch of the frames held.  funcodec_amd/csrc/slots_kernels.h is its specification.  The record is canonical: a pure function of
+ * the utterance's pushes, whatever the session's S, the slot index, max_frames, max_chunk_samples, the parity of its push counters,
+ * graph replay and the other slots.  Any session of the same architecture imports it, and the call goes on bit for bit as if it had
+ * never moved.  fc_slot_meta is the host part: the phases (0 idle, 1 running, 2 ended) and cached frames of both sides, and `layout`,
+ * a fingerprint of the segment list (kinds and lengths): it tells architectures apart, NOT checkpoints.  A side that is not running
+ * contributes zeros and 0 frames.
+ *   fc_slotrec_floats         the record's length for the given frame counts (both 0 in a session without a cache)
+ *   fc_slotrec_export         records[i] = the record of slots[i], meta[i] its host part; the source is only read and goes on as before,
+ *                             so export + import is also a fork of a call.  ONE launch for the n slots, on `stream`, between pushes.
+ *   fc_slotrec_import         the inverse: slots[i] takes records[i] / meta[i].  It abandons whatever the slot held, as START does,
+ *                             writes the DESTINATION's read halves and the destination's cache pitch, sets the slot's phases and frame
+ *                             counts from meta and touches no other slot.  ONE launch.
+ *   fc_slotrec_export_stream  row b of a lock-step session as a slot record (the same code: both kinds are one session layout).
+ * slots, meta: host [n]; records: dev f32 [n][pitch_floats].  Refused before the first launch -- nothing changes, the message names the
+ * slot and the rule: n outside [1, S], a slot out of range or named twice; pitch_floats below a record's length; export of a slot that
+ * a failed push has invalidated or from a broken stream; import of another layout; frames past the destination's max_frames; frames
+ * into a session without a cache, or a record without a cache into a session with one.  A refused call returns 1.  An import that
+ * fails after its launch invalidates the slots it named, as a failed push does, and returns 2, so that a caller who keeps books of
+ * its own tells the two apart without reading the message.
+ * Cost at create: every fc_stream / fc_slots create (the fc_seq* ones included) now builds the segment table, one small hipMalloc
+ * (freed at destroy) and one synchronous copy of a few KB, whether the session ever exports or not. */
+typedef struct { uint32_t layout; int32_t enc_phase, dec_phase, enc_frames, dec_frames; } fc_slot_meta;
+size_t fc_slotrec_floats(const fc_slots* s, int enc_frames, int dec_frames);
+int  fc_slotrec_export(fc_slots* s, int n, const int32_t* slots, float* records /* dev [n][pitch] */, size_t pitch_floats,
+                       fc_slot_meta* meta /* host [n] */, void* stream);
+int  fc_slotrec_import(fc_slots* s, int n, const int32_t* slots, const float* records, size_t pitch_floats, const fc_slot_meta* meta, void* stream);
+int  fc_slotrec_export_stream(fc_stream* s, int n, const int32_t* rows, float* records, size_t pitch_floats, fc_slot_meta* meta, void* stream);
+
 /* Deferred device-side failures.  Kernels cannot return a status, so two conditions are recorded in host-visible
  * status words and reported by the NEXT fc_* compute call on the engine (non-zero return, message in fc_last_error(),
  * condition cleared) or by this call.  *flags (may be NULL) receives the conditions pending at entry:

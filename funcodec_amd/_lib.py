@@ -60,6 +60,23 @@ class FcSlotMeta(C.Structure):
     _fields_ = [("layout", C.c_uint32), ("enc_phase", C.c_int32), ("dec_phase", C.c_int32), ("enc_frames", C.c_int32), ("dec_frames", C.c_int32)]
 
 
+class FcLauraSampleRow(C.Structure):
+    """fc_laura_sample_row: one row of the sampling table of fc_laura_sample's table form"""
+    _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("p", C.c_float), ("max_steps", C.c_int32), ("seed", C.c_uint64),
+                ("forced_on", C.c_int32), ("rng_row", C.c_uint32), ("temperature", C.c_float), ("min_length", C.c_int32),
+                ("top_p", C.c_float), ("repeat_window", C.c_int32), ("repeat_count", C.c_int32)]
+
+
+class FcLauraSampleIo(C.Structure):
+    """fc_laura_sample_io: the buffers and parameters of fc_laura_sample"""
+    _fields_ = [("logits", C.c_void_p), ("step", C.POINTER(C.c_int32)), ("n_gen", C.POINTER(C.c_int32)), ("done", C.POINTER(C.c_int32)),
+                ("pos", C.POINTER(C.c_int32)), ("tok_off", C.POINTER(C.c_int32)), ("n_done", C.POINTER(C.c_int32)),
+                ("tokens", C.c_void_p), ("forced", C.c_void_p), ("logp", C.c_void_p), ("score", C.c_void_p), ("next_emb", C.c_void_p),
+                ("xs", C.c_void_p), ("rows", C.POINTER(FcLauraSampleRow)), ("B", C.c_int32), ("R", C.c_int32), ("mode", C.c_int32),
+                ("k", C.c_int32), ("p", C.c_float), ("seed", C.c_uint64), ("max_steps", C.c_int32), ("row0", C.c_int32),
+                ("nrows", C.c_int32)]
+
+
 # every symbol include/funcodec_amd.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -194,6 +211,7 @@ SYMBOLS = {
     "fc_laura_debug_probe": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "fc_laura_attention": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
     "fc_laura_step_block": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "fc_laura_sample": (C.c_int, [_P, C.POINTER(FcLauraSampleIo), _P, C.c_size_t, _P]),
     "fc_laura_set_persistent_step": (C.c_int, [_P, C.c_int]),
     "fc_laura_persistent_step_fallbacks": (C.c_int, [_P]),
     # decoding session: S slots of decode_codec that start and end independently in one running batch

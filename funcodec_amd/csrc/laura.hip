@@ -595,16 +595,25 @@ bool step_persist_ok(const fc_laura* e, const StepMem& m) {
            lk::step_persist_supported(m.B, s.d_model, s.ff, s.heads, s.d_model / s.heads, e->vocab(), m.NS);
 }
 
-// the sampler of a step over m's rows; the caller adds what is its own (the call's or the rows' parameters, the token buffers)
-lk::Sample step_sampler(const fc_laura* e, const StepMem& m) {
+// the model's side of a sample: the group layout, the codebook table, the LM's fused input layer.  The one statement of these fields, for
+// a step over the engine's own rows (step_sampler) and for fc_laura_sample (the per-op test entry) over the caller's
+lk::Sample model_sampler(const fc_laura* e) {
     const Stack& S = e->codec_lm;
     lk::Sample sm;
-    sm.logits = m.lg; sm.B = m.B; sm.K = e->arch.codebook_size; sm.nq = e->arch.predict_nq;
-    sm.n_gen = m.n_gen(); sm.done = m.done(); sm.n_done = m.n_done(); sm.pos = m.pos; sm.step = m.step();
-    sm.cb = e->cb; sm.D = e->arch.codebook_dim; sm.next_emb = m.nemb;
+    sm.K = e->arch.codebook_size; sm.nq = e->arch.predict_nq;
+    sm.cb = e->cb; sm.D = e->arch.codebook_dim;
     // the sampler also runs the LM's input layer on the new token (Linear + LayerNorm + ReLU + x * sqrt(d)): xs is ready for block 0
     sm.emb_wt = e->lm_embed_wt; sm.emb_bias = S.embed.bias; sm.emb_g = S.eg; sm.emb_b = S.eb; sm.dm = S.s.d_model; sm.emb_relu = S.s.embed_relu;
-    sm.xscale = sqrtf((float)S.s.d_model); sm.xs = m.xs;
+    sm.xscale = sqrtf((float)S.s.d_model);
+    return sm;
+}
+
+// the sampler of a step over m's rows; the caller adds what is its own (the call's or the rows' parameters, the token buffers)
+lk::Sample step_sampler(const fc_laura* e, const StepMem& m) {
+    lk::Sample sm = model_sampler(e);
+    sm.logits = m.lg; sm.B = m.B;
+    sm.n_gen = m.n_gen(); sm.done = m.done(); sm.n_done = m.n_done(); sm.pos = m.pos; sm.step = m.step();
+    sm.next_emb = m.nemb; sm.xs = m.xs;
     sm.launch_seq = m.pseq;                // every sampler launch numbers the persistent step launch that follows it (1, 2, ...)
     return sm;
 }
@@ -2115,6 +2124,75 @@ int fc_laura_step_block(fc_laura* e, int layer, float* x, float* k_cache, float*
     cx.check(hipMemcpyAsync(x, m.xs, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "copy out");
     cx.check(hipMemcpyAsync(q_out, m.qb, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "copy out");
     cx.check(hipMemcpyAsync(part_out, m.apart, (size_t)B * heads * NS * (dkh + 2) * sizeof(float), hipMemcpyDeviceToDevice, cx.st), "copy out");
+    return cx.err;
+}
+
+int fc_laura_sample(fc_laura* e, const fc_laura_sample_io* io, void* workspace, size_t workspace_bytes, void* stream) {
+    if (check_ready(e)) return 1;
+    if (!io || !workspace) return fail("bad argument");
+    if (!io->logits || !io->step || !io->n_gen || !io->done || !io->pos || !io->tok_off || !io->n_done || !io->tokens || !io->next_emb || !io->xs)
+        return fail("sample: null buffer");
+    const int B = io->B, R = io->R, K = e->arch.codebook_size, nq = e->arch.predict_nq;
+    if (B < 1 || B > 64) return fail("sample: 1 .. 64 rows");
+    if (R < 1) return fail("sample: token rows of at least one step");
+    const int n = io->nrows > 0 ? io->nrows : B;
+    if (io->row0 < 0 || io->nrows < 0 || io->row0 + n > B) return fail("sample: row0 / nrows outside the " + std::to_string(B) + " rows");
+    // steps per row of forced / logp / score: the table form's row stride is the token rows' (a session), the call form's is max_steps
+    const int steps = io->rows ? R : io->max_steps;
+    std::vector<lk::SampleRow> table(B);
+    for (int b = 0; b < B; ++b) {
+        const std::string who = "sample: row " + std::to_string(b) + ": ";
+        lk::SampleRow row;
+        if (io->rows) {
+            const fc_laura_sample_row& r = io->rows[b];
+            const std::string why = rules_problem(r.temperature, r.min_length, r.top_p, r.repeat_window, r.repeat_count);
+            if (!why.empty()) return fail(who + why);
+            row = make_row(rules_row(r.temperature, r.min_length, r.top_p, r.repeat_window, r.repeat_count), r.mode, r.k, r.p, r.max_steps,
+                           r.seed, r.forced_on ? 1 : 0);
+            row.rng_row = r.rng_row;
+        } else row = make_row(lk::SampleRow{}, io->mode, io->k, io->p, io->max_steps, io->seed, 1);
+        if (row.mode < 0 || row.mode > 3) return fail(who + "sampling mode must be 0 .. 3");
+        if (row.ki < 0 || !std::isfinite(row.pf)) return fail(who + "bad sampling k / p");
+        if (row.max_steps < 1 || row.max_steps > steps) return fail(who + "max_steps outside 1 .. " + std::to_string(steps));
+        if (io->step[b] < 0 || io->pos[b] < 0 || io->n_gen[b] < 0 || io->tok_off[b] < 0) return fail(who + "negative state");
+        // every token row the kernel can touch lies in the row's R: the write at tok_off + n_gen of a running row, the repeat rule's window behind it
+        if (io->tok_off[b] + io->n_gen[b] > R || io->tok_off[b] + row.max_steps > R)
+            return fail(who + "tok_off + n_gen and tok_off + max_steps must not exceed the " + std::to_string(R) + " token rows");
+        table[b] = row;
+    }
+    if (io->forced) {       // a forced id indexes the codebook table
+        std::vector<int64_t> f((size_t)B * steps * nq);
+        if (hipMemcpy(f.data(), io->forced, f.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return fail("sample: forced read-back failed");
+        for (int64_t v : f)
+            if (v < 0 || v > K) return fail("sample: forced id outside 0 .. " + std::to_string(K));
+    }
+    Ctx cx = make_ctx(B, workspace, workspace_bytes, stream);
+    int* st_d = upload_lens(cx, io->step, B);
+    int* ng_d = upload_lens(cx, io->n_gen, B);
+    int* dn_d = upload_lens(cx, io->done, B);
+    int* ps_d = upload_lens(cx, io->pos, B);
+    int* to_d = upload_lens(cx, io->tok_off, B);
+    int* nd_d = upload_lens(cx, io->n_done, 1);
+    lk::SampleRow* rows_d = cx.alloc<lk::SampleRow>(B);
+    if (!cx.live()) return 1;
+    lk::Sample sm = model_sampler(e);
+    sm.logits = io->logits; sm.B = B;
+    sm.step = st_d; sm.n_gen = ng_d; sm.done = dn_d; sm.pos = ps_d; sm.tok_off = to_d; sm.n_done = nd_d;
+    sm.tokens = io->tokens; sm.tok_stride = R; sm.forced = io->forced; sm.logp_out = io->logp; sm.score_out = io->score;
+    sm.next_emb = io->next_emb; sm.xs = io->xs;
+    sm.row0 = io->row0; sm.nrows = io->nrows;
+    if (io->rows) {
+        cx.check(hipMemcpyAsync(rows_d, table.data(), (size_t)B * sizeof(lk::SampleRow), hipMemcpyHostToDevice, cx.st), "sampling table");
+        sm.rows = rows_d; sm.row_stride = R;
+    } else { sm.mode = io->mode; sm.ki = io->k; sm.pf = io->p; sm.seed = io->seed; sm.max_steps = io->max_steps; }
+    if (cx.err) return 1;
+    cx.check(lk::launch_sample(sm, cx.st), "sampling");
+    cx.check(hipMemcpyAsync(io->step, st_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, cx.st), "state read-back");
+    cx.check(hipMemcpyAsync(io->n_gen, ng_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, cx.st), "state read-back");
+    cx.check(hipMemcpyAsync(io->done, dn_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, cx.st), "state read-back");
+    cx.check(hipMemcpyAsync(io->pos, ps_d, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, cx.st), "state read-back");
+    cx.check(hipMemcpyAsync(io->n_done, nd_d, sizeof(int), hipMemcpyDeviceToHost, cx.st), "state read-back");
+    cx.check(hipStreamSynchronize(cx.st), "sampling");      // the host arrays hold the state, `table` may go
     return cx.err;
 }
 

@@ -1356,6 +1356,9 @@ __device__ __forceinline__ int draw_inverse_cdf(const float* val, const int* idx
             const int iend = (4 * lane + c + 1) * CH < ncand ? (4 * lane + c + 1) * CH : ncand;
             while (i + 1 < iend && run + val[i] <= target) { run += val[i]; ++i; }
             if (i >= ncand) i = ncand - 1;
+            // a walk that rounding carried to the end of a chunk can stand on an entry without mass (an underflowed expf, a masked id):
+            // the CDF does not rise there, the draw belongs to the last entry before it that has some
+            while (i > 0 && !(val[i] > 0.f)) --i;
             if (i < 0) i = 0;
             *sh_pick = idx[i];
         }
@@ -1503,7 +1506,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
                 int nl = 0;
 #pragma unroll
                 for (int i = 0; i < XPT; ++i) {
-                    const unsigned u = __float_as_uint(xr[i]);
+                    unsigned u = __float_as_uint(xr[i]);
+                    if (u == 0x80000000u) u = 0u;       // -0.0 = +0.0 in every float comparison of this kernel: one key for both
                     lk[i] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
                     if (tid + 256 * i < G) nl = i + 1;
                 }

@@ -448,6 +448,99 @@ class LauraEngine:
                                                  _ptr(q), _ptr(part), _ptr(ws), ws.numel(), self._stream()))
         return x, q, part, kc, vc
 
+    SAMPLE_ROW_FIELDS = ("mode", "k", "p", "max_steps", "seed", "forced_on", "rng_row", "temperature", "min_length", "top_p",
+                         "repeat_window", "repeat_count")
+
+    @_on_device
+    def sample(self, logits: torch.Tensor, tokens: torch.Tensor, step: Sequence[int], n_gen: Sequence[int], done: Sequence[int],
+               pos: Sequence[int], tok_off: Sequence[int], *, rows: Optional[Sequence[dict]] = None, mode: int = 0, k: int = 0, p: float = 0.0,
+               seed: int = 0, max_steps: Optional[int] = None, forced: Optional[torch.Tensor] = None, logp: bool = False, score: bool = False,
+               row0: int = 0, nrows: int = 0, n_done: int = 0, fill: float = 0.0) -> dict:
+        """The device sampler on the caller's logits and state (per-op test entry, fc_laura_sample): logits [B, V] float32, B <= 64,
+        tokens [B, R, nq] int64 (the history the repeat rule reads; generated token g of row b is row tok_off[b] + g), the per-row state
+        as integer lists.  Call form (``rows`` None): mode / k / p / seed / max_steps for every row, neutral rules, Philox row word =
+        the batch row; ``forced`` is [B, max_steps, nq] and logp / score hold max_steps steps per row.  Table form: ``rows`` holds a
+        dict per row with SAMPLE_ROW_FIELDS (missing rule fields are neutral, forced_on 1, rng_row 0); ``forced`` is [B, R, nq] and
+        logp / score hold R steps.  ``row0`` / ``nrows``: only those rows (0: all).  The float outputs start filled with ``fill``.
+        Returns a dict: tokens, step, n_gen, done, pos (lists), n_done, logp, score (None unless asked for), next_emb [B, D],
+        xs [B, d_model]; the arguments are left unchanged."""
+        spec = self.spec
+        nq, V, D, dm = spec.predict_nq, spec.lm_vocab, spec.codebook_dim, spec.codec_lm.d_model
+        logits = self._dev(logits, torch.float32)
+        if logits.dim() != 2 or logits.shape[1] != V or not 1 <= logits.shape[0] <= 64:
+            raise EngineError(f"sample: logits must be [1 .. 64, {V}], got {tuple(logits.shape)}")
+        if not bool(torch.isfinite(logits).all()):
+            raise EngineError("sample: logits must be finite")
+        B = logits.shape[0]
+        tokens = self._dev(tokens, torch.int64).clone()
+        if tokens.dim() != 3 or tokens.shape[0] != B or tokens.shape[2] != nq or tokens.shape[1] < 1:
+            raise EngineError(f"sample: tokens must be [{B}, R, {nq}], got {tuple(tokens.shape)}")
+        R = tokens.shape[1]
+        state = {"step": list(step), "n_gen": list(n_gen), "done": list(done), "pos": list(pos), "tok_off": list(tok_off)}
+        self._check_batch("sample", B, **state)
+        if not (0 <= int(row0) and 0 <= int(nrows) and int(row0) + (int(nrows) or B) <= B):
+            raise EngineError(f"sample: row0 = {row0}, nrows = {nrows} outside the {B} rows")
+        io = _lib.FcLauraSampleIo()
+        if rows is None:
+            if max_steps is None:
+                raise EngineError("sample: the call form needs max_steps")
+            steps = int(max_steps)
+            per_row = [int(max_steps)] * B
+            io.rows = None
+            io.mode, io.k, io.p, io.seed, io.max_steps = int(mode), int(k), float(p), _u64(seed), int(max_steps)
+            modes = [int(mode)] * B
+        else:
+            rows = list(rows)
+            if len(rows) != B:
+                raise EngineError(f"sample: {len(rows)} table rows for {B} rows")
+            steps = R
+            table = (_lib.FcLauraSampleRow * B)()
+            neutral = dict(k=0, p=0.0, seed=0, forced_on=1, rng_row=0, temperature=1.0, min_length=0, top_p=0.0, repeat_window=0, repeat_count=1)
+            for b, r in enumerate(rows):
+                extra = set(r) - set(self.SAMPLE_ROW_FIELDS)
+                if extra or "mode" not in r or "max_steps" not in r:
+                    raise EngineError(f"sample: row {b}: fields must be mode, max_steps and any of {self.SAMPLE_ROW_FIELDS}, got {sorted(r)}")
+                full = dict(neutral, **r)
+                SamplingRules(full["temperature"], full["min_length"], full["top_p"] or None, full["repeat_window"], full["repeat_count"])
+                for name in self.SAMPLE_ROW_FIELDS:
+                    v = full[name]
+                    setattr(table[b], name, _u64(v) if name == "seed" else float(v) if name in ("p", "temperature", "top_p") else int(v))
+            io.rows = table
+            per_row = [int(r["max_steps"]) for r in rows]
+            modes = [int(r["mode"]) for r in rows]
+        if any(m not in (0, 1, 2, 3) for m in modes):
+            raise EngineError(f"sample: sampling modes must be 0 .. 3, got {modes}")
+        for b in range(B):
+            if not 1 <= per_row[b] <= steps:
+                raise EngineError(f"sample: row {b}: max_steps {per_row[b]} outside 1 .. {steps}")
+            if min(state[n][b] for n in state) < 0:
+                raise EngineError(f"sample: row {b}: negative state")
+            if state["tok_off"][b] + state["n_gen"][b] > R or state["tok_off"][b] + per_row[b] > R:
+                raise EngineError(f"sample: row {b}: tok_off + n_gen and tok_off + max_steps must not exceed the {R} token rows")
+        if forced is not None:
+            forced = self._dev(forced, torch.int64)
+            if tuple(forced.shape) != (B, steps, nq):
+                raise EngineError(f"sample: forced must be [{B}, {steps}, {nq}], got {tuple(forced.shape)}")
+            if int(forced.min()) < 0 or int(forced.max()) > spec.codebook_size:
+                raise EngineError(f"sample: forced ids must lie in 0 .. {spec.codebook_size}")
+        new = lambda *shape: torch.full(shape, float(fill), dtype=torch.float32, device=self.device)
+        lp = new(B, steps, V) if logp else None
+        sc = new(B, steps) if score else None
+        nemb, xs = new(B, D), new(B, dm)
+        host = {n: _i32(v) for n, v in state.items()}
+        nd = _i32([n_done])
+        io.logits = _ptr(logits)
+        io.step, io.n_gen, io.done, io.pos, io.tok_off, io.n_done = host["step"], host["n_gen"], host["done"], host["pos"], host["tok_off"], nd
+        io.tokens, io.forced = _ptr(tokens), None if forced is None else _ptr(forced)
+        io.logp, io.score = None if lp is None else _ptr(lp), None if sc is None else _ptr(sc)
+        io.next_emb, io.xs = _ptr(nemb), _ptr(xs)
+        io.B, io.R, io.row0, io.nrows = B, R, int(row0), int(nrows)
+        ws = self._grown(1 << 20)
+        self._check(self.lib.fc_laura_sample(self._h, C.byref(io), _ptr(ws), ws.numel(), self._stream()))
+        out = {n: list(host[n]) for n in ("step", "n_gen", "done", "pos")}
+        out.update(tokens=tokens, n_done=int(nd[0]), logp=lp, score=sc, next_emb=nemb, xs=xs)
+        return out
+
 
 SLOT_STATES ={1: "running", 2: "done", 3: "failed"}       # fc_laura_slots_step's done_out; 0 = free (not reported)
 

@@ -872,6 +872,48 @@ int fc_laura_attention(fc_laura* e, int stack, int layer, const float* qkv, cons
 int fc_laura_step_block(fc_laura* e, int layer, float* x, float* k_cache, float* v_cache, const int32_t* pos, int B, int Tcap,
                         int key_ranges, int wide, float* q_out, float* part_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* per-op entry point of the device sampler (tests pin every draw against a float64 restatement and a host Philox): the engine's own
+ * sampler launch on the caller's logits and state, 1 <= B <= 64 rows, with the model's side of the launch (group layout, codebook table,
+ * the LM's fused input layer) stated where a decoding step states it.  Two forms of the sampling parameters, the two the library launches:
+ *   call form   rows == NULL: mode / k / p / seed / max_steps below for every row, neutral rules, Philox row word = the batch row
+ *               (what fc_laura_decode_codec launches); forced / logp / score hold max_steps steps per row
+ *   table form  rows host [B]: a row of the sampling table per row (what a decoding session launches); forced / logp / score hold R
+ *               steps per row
+ * Refused with a message: B, row0 / nrows, a mode, rule or max_steps out of range, state that would reach outside the R token rows
+ * (tok_off + n_gen > R, tok_off + max_steps > R), a forced id outside 0 .. codebook_size.  Logits must be finite.  Synchronises the stream. */
+typedef struct fc_laura_sample_row {
+    int32_t mode, k;            /* 0 greedy, 1 softmax, 2 top-k (k), 3 nucleus (p) */
+    float p;
+    int32_t max_steps;          /* 1 .. R */
+    uint64_t seed;
+    int32_t forced_on;          /* 0: the row samples even when `forced` is given */
+    uint32_t rng_row;           /* second word of the row's Philox counter */
+    float temperature;          /* the five rules of fc_laura_slots_set_rules; 1, 0, 0, 0, 1 are the neutral ones */
+    int32_t min_length;
+    float top_p;
+    int32_t repeat_window, repeat_count;
+} fc_laura_sample_row;
+typedef struct fc_laura_sample_io {
+    const float* logits;        /* dev f32 [B][V], V = predict_nq * (codebook_size + 1) */
+    int32_t *step, *n_gen, *done, *pos;     /* host i32 [B], in and out: samples drawn, tokens generated, ended, cache position */
+    const int32_t* tok_off;     /* host i32 [B]: generated token g of row b is token row tok_off[b] + g */
+    int32_t* n_done;            /* host i32 [1], in and out: the count of ended rows */
+    int64_t* tokens;            /* dev i64 [B][R][predict_nq], in (the repeat rule's history) and out */
+    const int64_t* forced;      /* dev i64 [B][steps][predict_nq] or NULL */
+    float* logp;                /* dev f32 [B][steps][V] or NULL: row n_gen of a running row = log-softmax of its raw logits */
+    float* score;               /* dev f32 [B][steps] or NULL: entry n_gen of a running row = the step's score term */
+    float* next_emb;            /* dev f32 [B][codebook_dim]: written for rows that append a token */
+    float* xs;                  /* dev f32 [B][LM width]: likewise, the LM's fused input layer of next_emb */
+    const fc_laura_sample_row* rows;        /* host [B], or NULL: call form */
+    int32_t B, R;
+    int32_t mode, k;            /* call form */
+    float p;
+    uint64_t seed;
+    int32_t max_steps;
+    int32_t row0, nrows;        /* rows row0 .. row0 + nrows - 1 only (nrows 0: all B); the other rows' state and buffers are untouched */
+} fc_laura_sample_io;
+int fc_laura_sample(fc_laura* e, const fc_laura_sample_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
 /* debugging aid, not part of the path: the NEXT full-sequence stack runs of this thread copy one intermediate tensor (feature-major
  * [B][rows][T padded to 4]) to dev_dst.  stack 0 text_encoder / 1 codec_lm / 2 codec_encoder (-1 any); what 0 = stream after the input
  * layer, 1 = attention-norm output of block `layer`, 2 = its q/k/v, 3 = its attention context, 5 = residual stream at the entry of

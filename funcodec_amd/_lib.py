@@ -122,6 +122,10 @@ SYMBOLS = {
     # clears), min_nq, the device count table [B]; then the form (chain, device outputs row_errors / stage_errors / sub_quants, host i32 [B] rows off)
     "fc_engine_set_floor": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "fc_engine_set_floor_form": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    # the same per frame of a push (the push frame rule): min_nq, the device count table [B][Tf of the push]; and a borrowed device table
+    # [B][Tfc] for the decode_codes pushes of sessions
+    "fc_engine_set_floor_frames": (C.c_int, [_P, C.c_int, _P, _P]),
+    "fc_engine_set_push_frame_nq": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     # the bit stream's mode 1 (csrc/code_pack_kernels.h): a count per frame; engine-free
     "fc_frame_packet_pitch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "fc_frame_packet_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_longlong, C.c_int]),

@@ -188,21 +188,23 @@ class Speech2Token:
         return (ret["code_indices"], ret["code_embeddings"], ret["recon_speech"], ret["sub_quants"])
 
     def open_stream(self, batch: int = 1, n_q: Optional[int] = None, scale=None, max_chunk: Optional[int] = None,
-                    max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1):
+                    max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1,
+                    per_frame: bool = False):
         """A streaming session of the loaded (causal) model: funcodec_amd.stream.CodecStream.  Not in the reference, whose
         `streaming=` keyword selects a data iterator; that keyword keeps its meaning here (accepted, unused).  graph: replay steady
         pushes as captured HIP graphs (results are then copies)."""
         return self.model.open_stream(batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames, graph=graph,
                                       rvq_beam=getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam,
-                                      noise_floor_db=noise_floor_db, min_n_q=min_n_q)
+                                      noise_floor_db=noise_floor_db, min_n_q=min_n_q, per_frame=per_frame)
 
     def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
-                   graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1):
+                   graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1,
+                   per_frame: bool = False):
         """A slot session of the loaded (causal) model: funcodec_amd.stream.StreamSlots, independent utterances sharing every push
         (max_frames: the bound a transformer bottleneck needs, as for open_stream; graph: as for open_stream)."""
         return self.model.open_slots(slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames, graph=graph,
                                      rvq_beam=getattr(self, "rvq_beam", 1) if rvq_beam is None else rvq_beam,
-                                     noise_floor_db=noise_floor_db, min_n_q=min_n_q)
+                                     noise_floor_db=noise_floor_db, min_n_q=min_n_q, per_frame=per_frame)
 
     @staticmethod
     def from_pretrained(model_tag: Optional[str] = None, **kwargs: Optional[Any]):

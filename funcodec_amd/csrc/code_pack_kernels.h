@@ -44,7 +44,8 @@
 //   lie behind the row's pitch is 0.  A hostile packet can index nothing outside its row.
 //
 // Not built: entropy coding, a decode that reads packets directly (decoding is unpack, then the counts per row or frame, then the decode
-// calls there are), a count per frame in stream and slot sessions.
+// calls there are).  Sessions opened per frame write and read mode 1 through these launches (fc_engine_set_floor_frames,
+// fc_engine_set_push_frame_nq); a count per frame by target SNR in sessions is not built.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>

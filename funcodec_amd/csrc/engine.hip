@@ -199,11 +199,16 @@ struct fc_engine {
         double* row_err_out = nullptr;
         float* stage_err_out = nullptr;
         float* subq_out = nullptr;              // of the hook alone (a push has no sub_quants)
+        // a count per frame of the push (fc_engine_set_floor_frames; the push frame rule): the caller's table [B][Tf of the push]; min_nq
+        // may then be 0, and n_q_out is not written
+        int32_t* nq_frames_out = nullptr;
         bool on() const { return !floor.empty(); }
         void clear_form() { chain = false; row_err_out = nullptr; stage_err_out = nullptr; subq_out = nullptr; }
     } floor;
     // a stage count per frame for the offline decode_codes calls that follow (fc_engine_set_frame_nq): the caller's device table, borrowed
     struct FrameNq { const int32_t* table = nullptr; int B = 0, Tf = 0; } frame_nq;
+    // the same for the session decode pushes that follow (fc_engine_set_push_frame_nq): [B][Tfc of the push], borrowed
+    FrameNq push_nq;
     bool lstm_persist_ok = true;             // cleared after a grid-barrier timeout: later calls take the per-step launch path
     int persist_checked_B = -1; bool persist_checked_val = false;
     // optional event timing
@@ -253,11 +258,13 @@ struct Session {
         int rvq_beam = 1;                           // width of the quantiser's search (fc_engine_set_rvq_beam): more launches above 1
         // the noise floor of an encode push (fc_engine_set_floor): its tables' addresses, min_nq and form; the floors themselves are device data
         const void* floor_table = nullptr; const void* floor_out = nullptr; int floor_min = 0, floor_chain = 0;
+        const void* floor_frames = nullptr;         // frame mode (fc_engine_set_floor_frames): the count table per frame, else null
+        const void* push_nq = nullptr;              // a decode push under a count per frame (fc_engine_set_push_frame_nq): its table
         bool operator==(const GraphKey& o) const {
             return form == o.form && width == o.width && parity == o.parity && n_q == o.n_q && use_scale == o.use_scale && ptr == o.ptr && ws == o.ws &&
                    ws_bytes == o.ws_bytes && stream == o.stream && nq_table == o.nq_table && nq_rows == o.nq_rows &&
                    rvq_beam == o.rvq_beam && floor_table == o.floor_table && floor_out == o.floor_out && floor_min == o.floor_min &&
-                   floor_chain == o.floor_chain;
+                   floor_chain == o.floor_chain && floor_frames == o.floor_frames && push_nq == o.push_nq;
         }
     };
     struct Graph { GraphKey key; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
@@ -1990,7 +1997,9 @@ int counts_check_encode(const fc_engine* e, const char* who, int B, int n_q, boo
             if (f.min_nq > e->row_nq[b])
                 return fail("fc_engine_set_floor: min_nq = " + std::to_string(f.min_nq) + " lies above the cap of row " + std::to_string(b) + " (" +
                             std::to_string(e->row_nq[b]) + " stages, fc_engine_set_row_nq)");
-        if (floor_ok && !session && (!f.row_err_out || !f.stage_err_out))
+        if (floor_ok && !session && f.nq_frames_out && !f.stage_err_out)
+            return fail(std::string(who) + ": the hook has no workspace: fc_engine_set_floor_form with stage_errors_out");
+        if (floor_ok && !session && !f.nq_frames_out && (!f.row_err_out || !f.stage_err_out))
             return fail(std::string(who) + ": the hook has no workspace: fc_engine_set_floor_form with row_errors_out and stage_errors_out");
         return 0;
     }
@@ -2017,6 +2026,18 @@ int counts_check_encode(const fc_engine* e, const char* who, int B, int n_q, boo
 // the frame table's B and Tf, and not both tables.  A session push takes no frame table.
 int counts_check_decode(const fc_engine* e, const char* who, int B, int Tf, int n_q, bool session) {
     if (row_nq_check(e, B, n_q)) return 1;
+    if (e->push_nq.table) {     // fc_engine_set_push_frame_nq: the same table for the decode pushes of sessions, and for them alone
+        if (!session)
+            return fail(std::string(who) + ": a stage count per frame of a push is set (fc_engine_set_push_frame_nq): it is for session decode pushes only; "
+                        "clear it with a NULL table");
+        if (!e->row_nq.empty())
+            return fail("a stage count per frame of a push (fc_engine_set_push_frame_nq) and per-row stage counts (fc_engine_set_row_nq) are both set; "
+                        "clear one of them");
+        if (e->push_nq.B != B || e->push_nq.Tf != Tf)
+            return fail("a stage count per frame is set for [" + std::to_string(e->push_nq.B) + "][" + std::to_string(e->push_nq.Tf) +
+                        "] frames (fc_engine_set_push_frame_nq); this push has [" + std::to_string(B) + "][" + std::to_string(Tf) +
+                        "] (clear it with a NULL table)");
+    }
     if (!e->frame_nq.table) return 0;
     if (session)
         return fail(std::string(who) + ": a stage count per frame is set (fc_engine_set_frame_nq): it is for offline decode calls only; clear it with a NULL table");
@@ -2056,6 +2077,24 @@ void rvq_after_greedy(const fc_engine* e, const RvqTail& a, hipStream_t st, Laun
         });
         fc::StageCounts k; k.rows = caps;
         if (a.beam_sum && !a.floor_rows) sum("rvq beam sum", k);        // under a floor the pick's sum follows at once
+    }
+    if (a.floor_rows && e->floor.nq_frames_out) {       // fc_engine_set_floor_frames (the push frame rule): one fused launch of any width, or its chain
+        const fc_engine::Floor& f = e->floor;
+        if (!f.chain) {
+            launch("rvq push floor frames", 0.0, [&] {
+                return fc::launch_rvq_push_floor_frames(a.x, a.codes, a.B, a.Tf, Dc, K, a.n_q, e->cb, caps, *a.floor_rows, f.floor_dev, f.min_nq,
+                                                        f.nq_frames_out, a.quant, a.quant_bdt, a.subq, f.stage_err_out, st);
+            });
+            return;
+        }
+        launch("rvq stage errors", 0.0, [&] { return fc::launch_rvq_stage_errors(a.x, a.codes, N, Dc, K, a.n_q, e->cb, a.serr, a.Tf, caps, *a.floor_rows, st); });
+        launch("rvq floor frames", 0.0, [&] {
+            return fc::launch_rvq_floor_frames(a.serr, a.B, a.Tf, a.n_q, caps, *a.floor_rows, f.floor_dev, f.min_nq, f.nq_frames_out, st);
+        });
+        fc::StageCounts k; k.frames = f.nq_frames_out;
+        sum("rvq floor frame sum", k);
+        launch("rvq floor frame zero codes", 0.0, [&] { return fc::launch_rvq_rate_zero_codes(a.codes, N, a.Tf, a.n_q, k, st); });
+        return;
     }
     if (a.floor_rows) {     // fc_engine_set_floor (the push rule): one fused launch, or its chain for a push wider than the launch takes
         const fc_engine::Floor& f = e->floor;
@@ -2179,7 +2218,7 @@ int do_quantize(fc_engine* e, Ctx& cx, const Act& last, int Tf, int n_q, int64_t
     // forced); a dry pass counts them for the session's widest push
     if (push_rows && (cx.dry || e->floor.on())) {
         if (!cx.dry && (int)e->floor.floor.size() != B) cx.fail("internal: a noise floor of another batch width");
-        if (cx.dry || e->floor.chain || !fc::rvq_push_floor_fits(Tf, Dc, n_q)) {
+        if (cx.dry || e->floor.chain || (!e->floor.nq_frames_out && !fc::rvq_push_floor_fits(Tf, Dc, n_q))) {
             tail.serr = cx.alloc<float>((size_t)(n_q + 1) * B * Tf);
             tail.rerr = cx.alloc<double>((size_t)B * (n_q + 1));
         }
@@ -2667,7 +2706,9 @@ Session::GraphKey graph_key(const Session& s, int form, int width, int parity, i
     if (form == kFormEncode && s.e->floor.on()) {
         const fc_engine::Floor& f = s.e->floor;
         k.floor_table = f.floor_dev; k.floor_out = f.n_q_out; k.floor_min = f.min_nq; k.floor_chain = f.chain ? 1 : 0;
+        k.floor_frames = f.nq_frames_out;
     }
+    if (form == kFormDecodeCodes) k.push_nq = s.e->push_nq.table;
     return k;
 }
 
@@ -2749,7 +2790,7 @@ int session_graph_counts(const Session* s, int64_t* out) {
 int stream_decode_push(fc_stream* S, int form, const void* in, int Tfc, int use_scale, float* wav, float* emb_out, void* ws, size_t ws_bytes, void* stream) {
     const Session::GraphKey key = graph_key(*S, form, Tfc, S->dec_pushes, use_scale, {in, wav, emb_out}, ws, ws_bytes, stream);
     const int rc = session_push(S, S->dec_pushes > 0 ? &key : nullptr, ws, ws_bytes, stream, no_eager_part, [&](Ctx& cx, bool) {
-        const float* z = form == kFormDecodeCodes ? decoder_input_codes(S->e, cx, (const int64_t*)in, Tfc, S->n_q, emb_out, nullptr)      // the lookup is per frame: nothing to carry
+        const float* z = form == kFormDecodeCodes ? decoder_input_codes(S->e, cx, (const int64_t*)in, Tfc, S->n_q, emb_out, nullptr, false, S->e->push_nq.table)      // the lookup is per frame: nothing to carry
                                                   : decoder_input_emb(S->e, cx, (const float*)in, Tfc);
         if (cx.err) return 1;                           // nothing of the state has been written yet
         S->broken = true;
@@ -3469,6 +3510,7 @@ int fc_engine_set_rate_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out,
 int fc_engine_set_floor(fc_engine* e, const double* floor_rows, int B, int min_nq, int32_t* n_q_rows_out, void* stream) {
     if (!e) return fail("null engine");
     if (!e->finalized) return fail("engine not finalized");
+    e->floor.nq_frames_out = nullptr;       // frame mode is given after the floor, every time (fc_engine_set_floor_frames)
     if (!floor_rows) { e->floor.floor.clear(); e->floor.n_q_out = nullptr; e->floor.clear_form(); return 0; }
     if (e->rate.on())
         return fail("fc_engine_set_floor: a rate is set (fc_engine_set_rate): a call takes a rate or a floor, not both; clear one of them");
@@ -3523,6 +3565,36 @@ int fc_engine_set_floor_form(fc_engine* e, int chain, double* row_errors_out, fl
                 return fail(std::string("fc_engine_set_floor_form: copy of the floors: ") + hipGetErrorString(er));
     }
     e->floor.chain = chain != 0; e->floor.row_err_out = row_errors_out; e->floor.stage_err_out = stage_errors_out; e->floor.subq_out = sub_quants_out;
+    return 0;
+}
+
+int fc_engine_set_floor_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out, void* stream) {
+    (void)stream;
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!e->floor.on()) return fail("fc_engine_set_floor_frames: no noise floor is set: it is given after fc_engine_set_floor");
+    if (!n_q_frames_out) return fail("fc_engine_set_floor_frames: n_q_frames_out (device int32 [B][Tf of the push]) takes the chosen stage counts");
+    if (min_nq < 0 || min_nq > e->arch.num_quantizers)
+        return fail("fc_engine_set_floor_frames: min_nq lies in [0, num_quantizers = " + std::to_string(e->arch.num_quantizers) + "], got " +
+                    std::to_string(min_nq));
+    for (size_t b = 0; b < e->row_nq.size(); ++b)
+        if (min_nq > e->row_nq[b])
+            return fail("fc_engine_set_floor_frames: min_nq = " + std::to_string(min_nq) + " lies above the cap of row " + std::to_string(b) + " (" +
+                        std::to_string(e->row_nq[b]) + " stages, fc_engine_set_row_nq)");
+    e->floor.min_nq = min_nq;
+    e->floor.nq_frames_out = n_q_frames_out;
+    return 0;
+}
+
+int fc_engine_set_push_frame_nq(fc_engine* e, const int32_t* n_q_frames, int B, int Tfc, void* stream) {
+    (void)stream;
+    if (!e) return fail("null engine");
+    if (!e->finalized) return fail("engine not finalized");
+    if (!n_q_frames) { e->push_nq = fc_engine::FrameNq(); return 0; }
+    if (B <= 0 || Tfc <= 0) return fail("fc_engine_set_push_frame_nq: a table holds at least one row of at least one frame");
+    if (!e->row_nq.empty())
+        return fail("fc_engine_set_push_frame_nq: per-row stage counts are set (fc_engine_set_row_nq): a push takes a count per row or per frame, not both");
+    e->push_nq.table = n_q_frames; e->push_nq.B = B; e->push_nq.Tf = Tfc;
     return 0;
 }
 
@@ -4390,7 +4462,7 @@ int fc_slots_decode_codes(fc_slots* Q, const int64_t* codes, int Tfc, const int3
         [&](Ctx& cx, bool captured) {
             const Pass p = slots_pass(Q, cx, true, frames, flags, !captured);
             fc::RagLen rows; rows.lens = p.lengths;
-            return slots_decode_pass(Q, cx, p, decoder_input_codes(Q->e, cx, codes, Tfc, Q->n_q, emb_out, &rows), Tfc, use_scale, wav);
+            return slots_decode_pass(Q, cx, p, decoder_input_codes(Q->e, cx, codes, Tfc, Q->n_q, emb_out, &rows, false, Q->e->push_nq.table), Tfc, use_scale, wav);
         });
     slots_commit(Q, true, frames, flags, !err);
     return err ? 1 : 0;

@@ -71,6 +71,27 @@
 // launch_rvq_rate_zero_codes -- any width.  The fused form, launch_rvq_push_floor: ONE launch for pushes of at most 256 frames per row
 // (every partial of the fp64 sum then holds at most one term), which runs the same device steps in the same order.  Both read frames,
 // caps and floors from device memory only, so a captured push replays unchanged when a floor changes.
+//
+// THE PUSH FRAME RULE, in terms of the push rule: a count per FRAME of one encode push of a session, chosen inside the push by the same
+// absolute floor (fc_engine_set_floor, then fc_engine_set_floor_frames).  The push rule takes one count for all frames of a push -- one loud
+// frame buys every stage for 99 silent ones, and the count follows how the caller cuts the audio into pushes.  An absolute floor per frame
+// needs no sum over frames: no fp64 tree, no F_b in the threshold.  Inputs: the fp32 stage errors err[k][b, t] above (same order,
+// contraction off) from the codes found at the cap; cap_b; floor_b = D * 10^(noise_floor_db_b / 10), the host's double; lo = min_nq clamped
+// to [0, cap_b] -- in frame mode a frame may take no stage at all.  For frame t < F_b of a row that has frames in the push:
+//   * a row switched off (its floor reads -1 on the device) takes cap_b in every frame;
+//   * a frame whose err[0 .. cap_b] are not all finite takes cap_b (what the plain push gives it);
+//   * a frame with (double)err[0] <= floor_b takes lo: silence, at frame granularity;
+//   * else the frame takes the smallest k in [lo, cap_b] with (double)err[k] <= floor_b -- comparisons only, no product, no division;
+//   * if there is none: the k in that range with the smallest err[k], first on ties (the scan of the row rule on the frame's fp32 errors).
+// Frames t >= F_b of such a row take 0 and nothing of them is read: their codes are zeroed, their quantized and sub_quants are 0.  A row
+// with F_b == 0 (an idle slot) has its row of the count table left unwritten, as in the push rule.
+// A frame's count is a function of that frame's quantiser input, its row's cap and floor alone: not of the push's width, the row, the slot
+// or the chunking.  For greedy codes frame (b, t) is bit for bit the push with n_q = k_t and zeros in codes[k_t:]; for the search it is the
+// first k_t codes of the full-depth path.
+// For F_b = 1 and min_nq >= 1 this rule IS the push rule: floor_b * 1.0 is floor_b, and the one-term sum 0.0 + (double)err is (double)err.
+// Two forms, bit for bit the same outputs on every row that has frames.  The fused form, launch_rvq_push_floor_frames: ONE launch, a
+// workgroup per tile of 16 frames of a row, any width.  The chain: launch_rvq_stage_errors, launch_rvq_floor_frames, launch_rvq_codes_sum
+// and launch_rvq_rate_zero_codes with the counts per frame.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -99,6 +120,17 @@ bool rvq_push_floor_fits(int Tf, int D, int nq);
 hipError_t launch_rvq_push_floor(const float* x /* [B Tf][D] */, int64_t* codes, int B, int Tf, int D, int K, int nq, const float* cb,
                                  const int* nq_rows, const RagLen& rows, const double* floor /* dev [B] */, int min_nq, int32_t* n_q_out, float* quant,
                                  float* quant_bdt, float* subq, double* row_err, float* serr_out, hipStream_t st);
+
+// The push frame rule in one launch: one workgroup per tile of 16 frames of a batch row, any Tf.  codes [nq][B Tf] are rewritten in place;
+// n_q_frames [B][Tf] never null; quant [B Tf][D], quant_bdt [B][D][Tf], subq [nq][B][D][Tf] and serr_out [nq + 1][B Tf] may each be null.
+// nq <= kPushFloorFramesMaxStages, B <= 65535, D in {16, 32, 64, 128, 256, 512}.
+constexpr int kPushFloorFramesMaxStages = 64;
+hipError_t launch_rvq_push_floor_frames(const float* x /* [B Tf][D] */, int64_t* codes, int B, int Tf, int D, int K, int nq, const float* cb,
+                                        const int* nq_rows, const RagLen& rows, const double* floor /* dev [B] */, int min_nq, int32_t* n_q_frames,
+                                        float* quant, float* quant_bdt, float* subq, float* serr_out, hipStream_t st);
+// The pick of its chain form, one thread per frame: err [nq + 1][B Tf] (launch_rvq_stage_errors wrote it on the same stream) -> n_q_frames [B][Tf].
+hipError_t launch_rvq_floor_frames(const float* err, int B, int Tf, int nq, const int* nq_rows, const RagLen& rows, const double* floor /* dev [B] */,
+                                   int min_nq, int32_t* n_q_frames, hipStream_t st);
 
 // One workgroup per batch row.  err [nq + 1][B Tf]; row_err [B][nq + 1] (launch_rvq_rate_rows wrote it on the same stream); nq_rows [B] (caps)
 // or null; rows.lens null: every row has Tf frames.  n_q_frames [B][Tf] never null; the three row outputs may be null.

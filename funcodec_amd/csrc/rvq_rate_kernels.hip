@@ -314,6 +314,141 @@ hipError_t launch_rvq_push_floor(const float* x, int64_t* codes, int B, int Tf, 
     return hipGetLastError();
 }
 
+namespace {
+// THE PUSH FRAME RULE (rvq_rate_kernels.h): the count of one frame from its fp32 errors err(0 .. cap), by one thread.  fl: the row's floor
+// (-1: the row is switched off).  Comparisons only.
+template <typename Err>
+__device__ __forceinline__ int floor_pick_frame(int cap, int min_nq, double fl, Err&& err) {
+    const int lo = min_nq < 0 ? 0 : (min_nq > cap ? cap : min_nq);
+    if (fl < 0.0) return cap;
+    bool finite = true;
+    for (int i = 0; i <= cap; ++i) finite = finite && isfinite(err(i));
+    if (!finite) return cap;
+    if ((double)err(0) <= fl) return lo;
+    return rate_pick_scan(lo, cap, err, [&](float ei) { return (double)ei <= fl; });
+}
+}  // namespace
+
+// The pick of the chain form: one thread per frame of the push, from the stage errors launch_rvq_stage_errors wrote on the same stream.
+// A frame behind its row's frames takes 0; a row without a frame in the push is not written.
+__global__ __launch_bounds__(256) void rvq_floor_frames_kernel(const float* __restrict__ err, int B, int Tf, int nq, const int* __restrict__ nq_rows,
+                                                               RagLen rows, const double* __restrict__ floor, int min_nq,
+                                                               int32_t* __restrict__ n_q_frames) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int N = B * Tf;
+    if (n >= N) return;
+    const int b = n / Tf, t = n - b * Tf;
+    const int frames = row_frames(rows, b, Tf);
+    if (frames <= 0) return;
+    int k = 0;
+    if (t < frames) {
+        const float* e = err + n;                       // e[i * N]: the frame's error after i stages
+        k = floor_pick_frame(rate_row_cap(nq_rows, b, nq), min_nq, floor[b], [&](int i) { return e[(size_t)i * N]; });
+    }
+    n_q_frames[n] = k;
+}
+
+hipError_t launch_rvq_floor_frames(const float* err, int B, int Tf, int nq, const int* nq_rows, const RagLen& rows, const double* floor, int min_nq,
+                                   int32_t* n_q_frames, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (Tf <= 0 || nq < 1 || !err || !floor || !n_q_frames || (long long)B * Tf > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rvq_floor_frames_kernel, dim3((unsigned)(((long long)B * Tf + 255) / 256)), dim3(256), 0, st, err, B, Tf, nq, nq_rows, rows, floor,
+                       min_nq, n_q_frames);
+    return hipGetLastError();
+}
+
+// THE PUSH FRAME RULE in one launch (rvq_rate_kernels.h): one workgroup per tile of 16 frames of one batch row (blockIdx.x the tile,
+// blockIdx.y the row), any Tf.
+//   1. stage errors of the tile through rvq_stage_errors_tile into errf [nq + 1][16] in LDS (and serr_out);
+//   2. lanes 0 .. 15 pick their frame's count (floor_pick_frame) into kt[] and n_q_frames;
+//   3. codes at stages >= k_t are zeroed and the first k_t code vectors summed in stage order from 0, element by element as
+//      rvq_codes_sum_kernel does, into quant / quant_bdt / subq.
+// A row without a frame in the push returns at once; a tile wholly behind its row's frames writes its zeros and reads nothing of x or the
+// codes (every cap of the tile is -1).  The zeroed codes lie at stages >= k_t, the summed ones below, and a tile's frames are its own: no
+// thread reads a code another thread of the launch writes.  No atomics, no fp64 arithmetic besides the widening of the comparisons.
+template <int D>
+__global__ __launch_bounds__(256) void rvq_push_floor_frames_kernel(const float* __restrict__ x, int64_t* __restrict__ codes, int Tf, int K, int nq,
+                                                                    const float* __restrict__ cb, const int* __restrict__ nq_rows, RagLen rows,
+                                                                    const double* __restrict__ floor, int min_nq, int32_t* __restrict__ n_q_frames,
+                                                                    float* __restrict__ quant, float* __restrict__ quant_bdt,
+                                                                    float* __restrict__ subq, float* __restrict__ serr_out) {
+    extern __shared__ float errf[];                     // [nq + 1][16]
+    __shared__ __attribute__((aligned(16))) float R[kRateRows][D + 4];
+    __shared__ int krow[kRateRows];
+    __shared__ int kt[kRateRows];
+    const int tid = threadIdx.x, b = blockIdx.y, Bn = gridDim.y, t0 = blockIdx.x * kRateRows;
+    const int N = Bn * Tf;
+    const int frames = row_frames(rows, b, Tf);
+    if (frames <= 0) return;
+    const int cap = rate_row_cap(nq_rows, b, nq);
+    const int row0 = b * Tf + t0;
+    rvq_stage_errors_tile<D>(R, krow, x, codes, N, K, nq, cb, row0,
+        [&](int n) { return n - b * Tf < frames ? cap : -1; },              // also every row of the tile behind Tf: frames <= Tf
+        [&](int i, int n, float v) {
+            const int r = n - row0;
+            errf[i * kRateRows + r] = v;
+            if (serr_out && t0 + r < Tf) serr_out[(size_t)i * N + n] = v;
+        });
+    __syncthreads();
+    if (tid < kRateRows) {
+        const int t = t0 + tid;
+        int k = 0;
+        if (t < frames) k = floor_pick_frame(cap, min_nq, floor[b], [&](int i) { return errf[i * kRateRows + tid]; });
+        kt[tid] = k;
+        if (t < Tf) n_q_frames[(size_t)b * Tf + t] = k;
+    }
+    __syncthreads();
+    const int nt = Tf - t0 < kRateRows ? Tf - t0 : kRateRows;             // the tile's frames inside the push
+    for (int e = tid; e < nq * nt; e += 256) {
+        const int i = e / nt, r = e - i * nt;
+        if (i >= kt[r]) codes[(size_t)i * N + row0 + r] = 0;
+    }
+    for (int e = tid; e < nt * D; e += 256) {
+        const int r = e / D, d = e - r * D, t = t0 + r, k = kt[r];
+        const size_t n = (size_t)row0 + r;
+        float s = 0.f;
+        for (int i = 0; i < nq; ++i) {
+            float v = 0.f;
+            if (i < k) {
+                long long idx = codes[(size_t)i * N + n];
+                if (idx < 0 || idx >= K) idx = 0;
+                v = cb[((size_t)i * K + idx) * D + d];
+                s = s + v;
+            }
+            if (subq) subq[(((size_t)i * Bn + b) * D + d) * Tf + t] = v;
+        }
+        if (quant) quant[n * D + d] = s;
+        if (quant_bdt) quant_bdt[((size_t)b * D + d) * Tf + t] = s;
+    }
+}
+
+hipError_t launch_rvq_push_floor_frames(const float* x, int64_t* codes, int B, int Tf, int D, int K, int nq, const float* cb, const int* nq_rows,
+                                        const RagLen& rows, const double* floor, int min_nq, int32_t* n_q_frames, float* quant, float* quant_bdt,
+                                        float* subq, float* serr_out, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (Tf < 1 || nq < 1 || nq > kPushFloorFramesMaxStages || B > 65535 || (long long)B * Tf > 0x7fffffffLL || K < 1 || !x || !codes || !floor ||
+        !n_q_frames)
+        return hipErrorInvalidValue;
+    const size_t dyn = sizeof(float) * (size_t)(nq + 1) * kRateRows;
+    const dim3 grid((Tf + kRateRows - 1) / kRateRows, B);
+#define FC_FLOOR_CASE(DD)                                                                                                                       \
+    case DD:                                                                                                                                    \
+        hipLaunchKernelGGL((rvq_push_floor_frames_kernel<DD>), grid, dim3(256), dyn, st, x, codes, Tf, K, nq, cb, nq_rows, rows, floor, min_nq,     \
+                           n_q_frames, quant, quant_bdt, subq, serr_out);                                                                       \
+        break;
+    switch (D) {
+        FC_FLOOR_CASE(16)
+        FC_FLOOR_CASE(32)
+        FC_FLOOR_CASE(64)
+        FC_FLOOR_CASE(128)
+        FC_FLOOR_CASE(256)
+        FC_FLOOR_CASE(512)
+        default: return hipErrorInvalidValue;
+    }
+#undef FC_FLOOR_CASE
+    return hipGetLastError();
+}
+
 // One workgroup per batch row, 256 threads; thread j owns frames t = j, j + 256, ... in rising order (the order of E_b's partial sums).
 // Thread 0 classifies the row (finite / silent / threshold) into LDS; every thread then picks for its frames, keeps its fp64 partial of
 // the achieved error, its count sum and its largest count; the partials meet as a binary tree in LDS (no atomics).

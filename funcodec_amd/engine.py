@@ -264,6 +264,43 @@ def floor_pick(row_err, frames, floor, min_n_q: int, caps):
     return out
 
 
+def floor_pick_frames(stage_err, frames, floor, min_n_q: int, caps):
+    """The push frame rule (csrc/rvq_rate_kernels.h, include/funcodec_amd.h) in float64 numpy: a stage count per frame of one push, a pure
+    function of the float32 stage errors stage_err [n_q + 1, B, F] (stage_err[k, b, t]: frame t's residual energy after k stages), the
+    frames every row has in the push (one int or B), the floors D * 10^(noise_floor_db / 10) (one float or B; None or negative: the row is
+    switched off), min_n_q (0 allowed) and the caps (one int or B).  Row b, frame t < frames_b:
+      - a row switched off: cap;
+      - errors e[0 .. cap] that are not all finite: cap;
+      - float64(e[0]) <= floor: lo = min_n_q clamped to [0, cap];
+      - the smallest k in [lo, cap] with float64(e[k]) <= floor -- comparisons only;
+      - no such k: the k in that range with the smallest e[k], first on ties.
+    Frames t >= frames_b take 0; a row without frames: -1 in every frame (the device leaves its row alone).  Returns int32 [B, F]."""
+    err = np.asarray(stage_err, dtype=np.float32)
+    if err.ndim == 2:
+        err = err[:, None]
+    _, B, F = err.shape
+    each = lambda v: list(np.broadcast_to(np.asarray(v, dtype=object), (B,)))
+    out = np.zeros((B, F), dtype=np.int32)
+    for b, (Fb, fl, cap) in enumerate(zip(each(frames), each(floor), each(caps))):
+        Fb, cap = int(Fb), int(cap)
+        if Fb <= 0:
+            out[b] = -1
+            continue
+        lo = min(max(int(min_n_q), 0), cap)
+        for t in range(min(Fb, F)):
+            if fl is None or fl < 0:
+                out[b, t] = cap
+                continue
+            e = [float(np.float64(v)) for v in err[:cap + 1, b, t]]
+            if not all(np.isfinite(v) for v in e):
+                out[b, t] = cap
+            elif e[0] <= float(fl):
+                out[b, t] = lo
+            else:
+                out[b, t] = _pick_scan(e, lo, cap, lambda v: v <= float(fl))
+    return out
+
+
 def rate_pick_frames(err, E, ratio: float, min_n_q: int, cap: int, frames: Optional[int] = None):
     """The stage counts of one row's frames (csrc/rvq_rate_kernels.h, include/funcodec_amd.h), a pure function of its float32
     stage errors err[0 .. cap][t] (err[k][t]: frame t's residual energy after k stages), its float64 row errors E[0 .. cap], its ratio
@@ -559,26 +596,45 @@ class CodecEngine:
 
     @contextlib.contextmanager
     def _floor(self, floors, min_n_q: int, n_q_out: Optional[torch.Tensor], fused: bool = True, row_errors: Optional[torch.Tensor] = None,
-               stage_errors: Optional[torch.Tensor] = None, sub_quants: Optional[torch.Tensor] = None):
+               stage_errors: Optional[torch.Tensor] = None, sub_quants: Optional[torch.Tensor] = None,
+               n_q_frames_out: Optional[torch.Tensor] = None):
         # an entry None of floors: the row is switched off (it keeps its cap)
         """The engine's noise floor (fc_engine_set_floor) for the session push or the per-op hook made inside: a stage count per row chosen
         on the device from the frames of that push; cleared on the way out, whatever happened, as _row_nq does.  floors: None (nothing is
         set) or a checked list (floor_values); n_q_out: the device int32 [B] that receives the counts.  fused=False (or outputs given):
-        fc_engine_set_floor_form."""
+        fc_engine_set_floor_form.  n_q_frames_out (device int32 [B][frames of the push], dense): frame mode (fc_engine_set_floor_frames,
+        the push frame rule): a count per frame, min_n_q may be 0, and n_q_out is not written."""
         if floors is None:
             yield
             return
         B = len(floors)
         off = [int(v is None) for v in floors]
-        self._check(self.lib.fc_engine_set_floor(self._h, (C.c_double * B)(*[0.0 if v is None else v for v in floors]), B, int(min_n_q),
-                                                 _ptr(n_q_out), self._stream()))
+        self._check(self.lib.fc_engine_set_floor(self._h, (C.c_double * B)(*[0.0 if v is None else v for v in floors]), B,
+                                                 max(int(min_n_q), 1) if n_q_frames_out is not None else int(min_n_q), _ptr(n_q_out), self._stream()))
         try:
+            if n_q_frames_out is not None:
+                self._check(self.lib.fc_engine_set_floor_frames(self._h, int(min_n_q), _ptr(n_q_frames_out), self._stream()))
             if not fused or row_errors is not None or stage_errors is not None or sub_quants is not None or any(off):
                 self._check(self.lib.fc_engine_set_floor_form(self._h, int(not fused), _ptr(row_errors), _ptr(stage_errors), _ptr(sub_quants),
                                                               (C.c_int32 * B)(*off) if any(off) else None, self._stream()))
             yield
         finally:
             self.lib.fc_engine_set_floor(self._h, None, 0, 1, None, None)
+
+    @contextlib.contextmanager
+    def _push_frame_nq(self, table: Optional[torch.Tensor]):
+        """The engine's stage count per frame (fc_engine_set_push_frame_nq) for the session decode push made inside: table, device int32
+        [B, Tfc], dense and borrowed; cleared on the way out, whatever happened.  None: nothing is set."""
+        if table is None:
+            yield
+            return
+        if table.dtype != torch.int32 or table.dim() != 2 or not table.is_contiguous():
+            raise EngineError(f"a stage count per frame of a push is a dense int32 [B, Tfc] tensor, got {table.dtype} {tuple(table.shape)}")
+        self._check(self.lib.fc_engine_set_push_frame_nq(self._h, _ptr(table), table.shape[0], table.shape[1], self._stream()))
+        try:
+            yield
+        finally:
+            self.lib.fc_engine_set_push_frame_nq(self._h, None, 0, 0, None)
 
     def _rate_in(self, target_snr_db, min_n_q, B: int, n_q: int, n_q_rows, per_frame: bool = False):
         """(ratios or None, min_n_q) of a call's target_snr_db / min_n_q, checked before anything reaches the device; a list of floats
@@ -820,7 +876,7 @@ class CodecEngine:
         return self._dev(rows, torch.int32)
 
     @_on_device
-    def pack_codes(self, codes: torch.Tensor, frames_rows=None, n_q_rows=None, n_q_frames=None) -> torch.Tensor:
+    def pack_codes(self, codes: torch.Tensor, frames_rows=None, n_q_rows=None, n_q_frames=None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
         """codes [n_q,B,Tf] i64 -> packets uint8 [B, pitch] on the device (fc_codes_pack), one packet per row with zeros behind it.
         frames_rows, n_q_rows [B] (optional; lists, or tensors on any device -- ``n_q_rows`` of a ``target_snr_db`` call goes in as it
         is): the row's frames and stage count, clamped on the device to [0, Tf] and [1, n_q]; nothing behind them is read.
@@ -839,7 +895,9 @@ class CodecEngine:
             kf = self._dev(kf, torch.int32)
             pitch = int(self.lib.fc_frame_packet_pitch(Tf, n_q, bits))
             packets = torch.empty((B, pitch), dtype=torch.uint8, device=self.device)
-            ws = torch.empty((int(self.lib.fc_frame_pack_workspace_bytes(B, Tf)),), dtype=torch.uint8, device=self.device)
+            need = int(self.lib.fc_frame_pack_workspace_bytes(B, Tf))     # the scan's workspace: the caller's (a session's fixed buffer), or one made here
+            if ws is None or ws.numel() < need:
+                ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
             self._check(self.lib.fc_codes_pack_frames(_ptr(codes), B, Tf, n_q, bits, _ptr(fr), _ptr(kf), _ptr(packets), pitch, _ptr(ws), ws.numel(),
                                                       self._stream()))
             return packets
@@ -950,10 +1008,12 @@ class CodecEngine:
         noise_floor_db (a list of B, or with n_q_rows one value or B): the push rule instead (floor_pick; fc_engine_set_floor): the N rows
         are ONE push of B rows of N / B frames each -> (codes, quantized, dict(n_q_rows, row_errors, stage_errors)) as for target_snr_db,
         plus sub_quants [n_q, B, D, N / B] in the dict.
-        fused=False runs the four-launch chain in place of the one fused launch (a push wider than 256 frames always does): same bits."""
+        fused=False runs the four-launch chain in place of the one fused launch (a push wider than 256 frames always does): same bits.
+        noise_floor_db with per_frame: the push frame rule (floor_pick_frames; fc_engine_set_floor_frames; min_n_q in [0, cap]): a count
+        per frame -> dict(n_q_frames [B, N / B] i32, stage_errors, sub_quants); one launch at any width, or the chain with fused=False."""
         beam = rvq_beam_width(self.arch, beam)
         if noise_floor_db is not None:
-            if target_snr_db is not None or per_frame:
+            if target_snr_db is not None:
                 raise EngineError("rvq_encode: noise_floor_db and target_snr_db are two rules (a floor per push, a rate per call): give one")
             if return_paths:
                 raise EngineError("rvq_encode: return_paths and noise_floor_db are two hooks (fc_rvq_encode_beam, fc_rvq_encode_rate)")
@@ -961,7 +1021,7 @@ class CodecEngine:
             floors = floor_values(self.arch, noise_floor_db, rows_b)
             if n_q_rows is not None:
                 n_q_rows = row_nq_list(self.arch, n_q_rows, rows_b, n_q)
-            min_n_q = rate_min_nq(self.arch, min_n_q, n_q, n_q_rows)
+            min_n_q = rate_min_nq(self.arch, min_n_q, n_q, n_q_rows, floor=0 if per_frame else 1)
             x = self._dev(x, torch.float32)
             N, D = x.shape
             if D != self.arch.codebook_dim:
@@ -974,9 +1034,14 @@ class CodecEngine:
                        row_errors=torch.empty((rows_b, n_q + 1), dtype=torch.float64, device=self.device),
                        stage_errors=torch.empty((n_q + 1, rows_b, N // rows_b), dtype=torch.float32, device=self.device),
                        sub_quants=torch.empty((n_q, rows_b, D, N // rows_b), dtype=torch.float32, device=self.device))
-            with self._row_nq(n_q_rows), self._floor(floors, min_n_q, out["n_q_rows"], fused, out["row_errors"], out["stage_errors"],
-                                                     out["sub_quants"]):
+            if per_frame:       # the push frame rule: no row sums; n_q_rows is not written
+                out["n_q_frames"] = torch.empty((rows_b, N // rows_b), dtype=torch.int32, device=self.device)
+                del out["row_errors"]
+            with self._row_nq(n_q_rows), self._floor(floors, min_n_q, out["n_q_rows"], fused, out.get("row_errors"), out["stage_errors"],
+                                                     out["sub_quants"], out.get("n_q_frames")):
                 self._check(self.lib.fc_rvq_encode_rate(self._h, _ptr(x), N, n_q, beam, _ptr(codes), _ptr(quant), self._stream()))
+            if per_frame:
+                del out["n_q_rows"]
             return codes, quant, out
         if per_frame and target_snr_db is None:
             raise EngineError("rvq_encode: per_frame chooses a stage count per frame by target_snr_db: give a target")

@@ -44,7 +44,8 @@ class EncodecMI355X:
         self.engine.load_state_dict(state)
 
     def open_stream(self, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None, max_chunk: Optional[int] = None,
-                    max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1):
+                    max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1,
+                    per_frame: bool = False):
         """A streaming encode / decode session for `batch` utterances of a causal checkpoint (funcodec_amd/stream.py CodecStream):
         n_q quantisers (default: all; a list of `batch` counts gives every utterance its own, and ``set_n_q`` changes them between
         pushes), one volume scale per utterance (default 1), pushes of at most max_chunk samples per call.  A causal net whose bottleneck is
@@ -54,13 +55,16 @@ class EncodecMI355X:
         rvq_beam (2, 4, 8): the session's encode pushes search over the quantiser's stages (``inference(rvq_beam=)``); a frame's codes
         equal the offline call's.
         noise_floor_db (one value or one per utterance; optional) and min_n_q: every encode push chooses a stage count per row on the
-        device, inside the push, by an absolute noise floor (CodecStream, "Noise floor"); n_q / ``set_n_q`` are then the caps."""
+        device, inside the push, by an absolute noise floor (CodecStream, "Noise floor"); n_q / ``set_n_q`` are then the caps.
+        per_frame=True (a property of the session): the count is chosen per FRAME of the push (CodecStream, "Noise floor per frame"),
+        min_n_q may be 0, packets are of mode 1 and ``decode_packed`` takes either mode."""
         from .stream import CodecStream
         return CodecStream(self, batch, n_q=n_q, scale=scale, max_chunk=max_chunk, max_frames=max_frames, graph=graph, rvq_beam=rvq_beam,
-                           noise_floor_db=noise_floor_db, min_n_q=min_n_q)
+                           noise_floor_db=noise_floor_db, min_n_q=min_n_q, per_frame=per_frame)
 
     def open_slots(self, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
-                   graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1):
+                   graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1,
+                   per_frame: bool = False):
         """A slot session of a causal checkpoint (funcodec_amd/stream.py StreamSlots): `slots` independent utterances that start, push
         and end at their own times and share every push of the batch; n_q quantisers at the most (default: all; ``start(slot, n_q=)`` and
         ``set_n_q(slot, n_q)`` give a slot fewer, at any time between pushes), at most max_chunk samples per call.  As for
@@ -68,10 +72,10 @@ class EncodecMI355X:
         side (every slot has its own key / value cache and its own position in it); any other net is refused with it.  graph=True: pushes
         are replayed as captured HIP graphs from fixed buffers of the session, and what a push returns are copies (StreamSlots).
         rvq_beam, noise_floor_db, min_n_q: as for ``open_stream`` (noise_floor_db: one value or one per slot; ``start(slot,
-        noise_floor_db=)`` and ``set_noise_floor(slot, db)`` change a slot's)."""
+        noise_floor_db=)`` and ``set_noise_floor(slot, db)`` change a slot's); per_frame: as for ``open_stream``."""
         from .stream import StreamSlots
         return StreamSlots(self, slots, n_q=n_q, max_chunk=max_chunk, max_frames=max_frames, graph=graph, rvq_beam=rvq_beam,
-                           noise_floor_db=noise_floor_db, min_n_q=min_n_q)
+                           noise_floor_db=noise_floor_db, min_n_q=min_n_q, per_frame=per_frame)
 
     # -- helpers -------------------------------------------------------------------------------
     def _as_bct(self, speech: torch.Tensor) -> torch.Tensor:

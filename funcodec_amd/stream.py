@@ -74,6 +74,8 @@ class _GraphBuffers:
         sizes = {"wav_in": (rows * ch * sess.max_chunk, f32), "codes": (n_q * rows * tf_enc, i64), "quantized": (rows * tf_enc * D, f32),
                  "enc_out": (rows * tf_enc * D, f32), "tokens": (rows * tf_dec * n_q, i64), "emb": (rows * tf_dec * D, f32),
                  "wav_out": (rows * ch * tf_dec * sess.hop, f32), "scale": (rows, f32)}
+        if sess.per_frame:      # the decode pushes' stage counts per frame: part of a captured push's key, like every pointer
+            sizes["frame_nq"] = (rows * tf_dec, torch.int32)
         self._flat = {k: torch.zeros(n, dtype=dt, device=dev) for k, (n, dt) in sizes.items()}
         self.ws = torch.empty(sess._ws_bytes, dtype=torch.uint8, device=dev)
         self.stream = torch.cuda.Stream(device=dev)
@@ -126,10 +128,15 @@ class _Session:
     _graph_family = ""        # the three calls of the kind's graph replay (set, enabled, counts)
 
     def __init__(self, model, rows: int, n_q: Optional[int], max_chunk: Optional[int], max_frames: Optional[int] = None, graph: bool = False,
-                 rvq_beam: Optional[int] = None, min_n_q: int = 1):
+                 rvq_beam: Optional[int] = None, min_n_q: int = 1, per_frame: bool = False):
         why = stream_refusal(model.arch, max_frames)
         if why:
             raise EngineError(why)
+        #: a property of the session: a noise floor chooses a stage count per FRAME of a push (the push frame rule of
+        #: csrc/rvq_rate_kernels.h), packets are of mode 1, and every decode push from codes runs under a count per frame
+        self.per_frame = bool(per_frame)
+        if self.per_frame and floor_refusal(model.arch):
+            raise EngineError("per_frame=True: " + floor_refusal(model.arch))
         #: the noise floor of every row's encode pushes in dB (None: the row has none and runs its fixed count); set on the engine around
         #: each encode push while any row has one (the push rule of csrc/rvq_rate_kernels.h), min_n_q with it
         self._floor_db: List[Optional[float]] = [None] * int(rows)
@@ -152,10 +159,19 @@ class _Session:
         #: True while the library replays this session's steady pushes as captured HIP graphs (False with FC_SESSION_GRAPH=0)
         self.graph = False
         self._g: Optional[_GraphBuffers] = None         # the fixed buffers of a session opened with graph=True; None: nothing of it exists
-        self.min_n_q = rate_min_nq(self.arch, min_n_q, self.n_q)
+        self.min_n_q = rate_min_nq(self.arch, min_n_q, self.n_q, floor=0 if self.per_frame else 1)
         self._open(rows, max_chunk)
         #: the stage counts the last encode push under a noise floor chose, device int32 [rows]: one of the session's fixed buffers
         self._nq_table = torch.zeros(int(rows), dtype=torch.int32, device=self.device)
+        #: per_frame: the counts per frame of the last such push, viewed dense [rows][its frames] from the base of a fixed device buffer
+        #: sized for max_chunk, and the fixed workspace of the mode-1 pack launch's scan
+        self._nqf_flat: Optional[torch.Tensor] = None
+        self._nqf: Optional[torch.Tensor] = None
+        self._pack_ws: Optional[torch.Tensor] = None
+        if self.per_frame:
+            tf_enc = self.engine.frames(self.max_chunk)
+            self._nqf_flat = torch.zeros(int(rows) * tf_enc, dtype=torch.int32, device=self.device)
+            self._pack_ws = torch.empty(int(self.lib.fc_frame_pack_workspace_bytes(int(rows), tf_enc)), dtype=torch.uint8, device=self.device)
         if graph:
             self._graph_open(rows)
 
@@ -272,6 +288,10 @@ class _Session:
         """the engine's table around one push; with no counts of its own a push does not touch the engine's table at all"""
         return contextlib.nullcontext() if rows is None else self.engine._row_nq(rows)
 
+    def _engine_push_frame_nq(self, table):
+        """the engine's stage count per frame around one decode push of a per_frame session; any other push does not touch the engine's at all"""
+        return contextlib.nullcontext() if table is None else self.engine._push_frame_nq(table)
+
     def _engine_rvq_beam(self):
         """the width of the quantiser's search around one encode push; a session of width 1 does not touch the engine's at all"""
         return contextlib.nullcontext() if self.rvq_beam == 1 else self.engine._rvq_beam(self.rvq_beam)
@@ -293,13 +313,19 @@ class _Session:
             return None
         return [None if v is None else floor_value(self.arch, v) for v in self._floor_db]
 
-    def _engine_floor(self):
-        """the engine's noise floor around one encode push; min_n_q is checked against the rows' caps before anything is set"""
+    def _engine_floor(self, Tf: int = 0):
+        """the engine's noise floor around one encode push of Tf frames; min_n_q is checked against the rows' caps before anything is set.
+        per_frame: the push writes its counts per frame into the session's table, viewed [rows][Tf] (``_nqf``; None after a push without a floor)"""
         floors = self._push_floor()
+        self._nqf = None
         if floors is None:
             return contextlib.nullcontext()
-        rate_min_nq(self.arch, self.min_n_q, self.n_q, self._row_nq)
-        return self.engine._floor(floors, self.min_n_q, self._nq_table, self._fused)
+        rate_min_nq(self.arch, self.min_n_q, self.n_q, self._row_nq, floor=0 if self.per_frame else 1)
+        if not self.per_frame:
+            return self.engine._floor(floors, self.min_n_q, self._nq_table, self._fused)
+        rows = len(floors)
+        self._nqf = self._nqf_flat[:rows * int(Tf)].view(rows, int(Tf))
+        return self.engine._floor(floors, self.min_n_q, self._nq_table, self._fused, n_q_frames_out=self._nqf)
 
     def _one_push(self, pieces, what: str) -> None:
         """a packet carries ONE count, a push under a noise floor chooses one per push: such a call is one push"""
@@ -326,11 +352,50 @@ class _Session:
         if why:
             raise EngineError(why)
 
-    def _pack_rows(self, codes: torch.Tensor, frames, counts) -> List[bytes]:
-        """codes [n_q,R,Tf] of R rows with their own frames and stage counts -> R packets on the host (one launch, one copy)"""
+    def _pack_rows(self, codes: torch.Tensor, frames, counts, counts_frames: Optional[torch.Tensor] = None) -> List[bytes]:
+        """codes [n_q,R,Tf] of R rows with their own frames and stage counts -> R packets on the host (one launch, one copy).
+        counts_frames (device int32 [R,Tf]; a per_frame session under a floor): packets of mode 1, a count per frame, instead."""
         with self._push_stream():
-            packets = self.engine.pack_codes(codes, frames_rows=frames, n_q_rows=counts)
+            if counts_frames is not None:
+                packets = self.engine.pack_codes(codes, frames_rows=frames, n_q_frames=counts_frames, ws=self._pack_ws)
+            else:
+                packets = self.engine.pack_codes(codes, frames_rows=frames, n_q_rows=counts)
         return self.engine.packets_to_host(packets)
+
+    def _unpack_rows_frames(self, packets, what: str):
+        """a per_frame session: host packets of either mode, mixed -> (tokens [R,Tf,n_q], n_q_frames [R,Tf] i32, both on the device, frames):
+        every header (a mode-1 packet's counts section too) validated on the host against the session's n_q, row and field named"""
+        from .io import frame_packet_pitch
+        packets = [bytes(p) for p in packets]
+        try:
+            _, frames, counts, _ = self.engine._parse_packets_any(packets, exact=True)
+        except EngineError as err:
+            raise EngineError(f"{what}: {err}") from None
+        for b, k in enumerate(counts):
+            if k > self.n_q:
+                raise EngineError(f"{what}: row {b}: packet field k: {k} stages, more than the {self.n_q} of this session")
+        if min(frames) < 1:
+            raise EngineError(f"{what}: a packet without frames decodes to nothing; leave it out")
+        import numpy as np
+        Tf = max(frames)
+        host = np.zeros((len(packets), frame_packet_pitch(Tf, self.n_q, self.engine.code_bits)), dtype=np.uint8)
+        for b, p in enumerate(packets):
+            host[b, :len(p)] = np.frombuffer(p, dtype=np.uint8)
+        with self._push_stream():
+            tokens, kf = self.engine.unpack_frame_codes(torch.from_numpy(host).to(self.device), Tf, self.n_q)
+        return tokens, kf, frames
+
+    def _with_counts(self, codes: torch.Tensor, n_q_frames, count: int, what: str) -> torch.Tensor:
+        """a per_frame session: codes [..., Tf, n_q] with the frames' stage counts as one more column, so that the start-up and splitting
+        rule cuts both alike.  n_q_frames [..., Tf] (any integer tensor), else `count` in every frame."""
+        shape = tuple(codes.shape[:-1])
+        if n_q_frames is None:
+            kf = torch.full(shape, int(count), dtype=torch.int64, device=self.device)
+        else:
+            kf = self.engine._dev(torch.as_tensor(n_q_frames), torch.int64)
+            if tuple(kf.shape) != shape:
+                raise EngineError(f"{what}: n_q_frames must be {list(shape)} (a count per frame of the codes), got {list(kf.shape)}")
+        return torch.cat([codes, kf.unsqueeze(-1)], -1)
 
     def _unpack_rows(self, packets, what: str):
         """host packets -> (tokens [R,Tf,n_q] on the device, frames, counts), every header validated against the session's n_q"""
@@ -416,6 +481,17 @@ class CodecStream(_Session):
     ``encode(packed=True)`` hands it to the pack launch, so every packet carries its own count and ``decode_packed`` needs nothing else.
     Such a packed call must fit one push (``max_chunk``): a packet carries one count.  One more launch per push.
 
+    Noise floor per frame (``per_frame=True``, a property of the session; False by default, and such a session is exactly what it was).
+    Under a floor every FRAME of a push takes its own count (the push frame rule of csrc/rvq_rate_kernels.h; ``engine.floor_pick_frames``
+    restates it): the smallest count in [min_n_q, the row's cap] whose residual of THAT frame lies at or below ``D * 10^(dB / 10)``,
+    min_n_q (which may be 0: a silent frame costs its count bits and nothing else) for a frame already below it, the frame's best count
+    where it is missed.  A frame's count depends on that frame alone, not on how the audio is cut into pushes.  ``last_n_q_frames`` is
+    the device table [batch][frames of the last push].  ``encode(packed=True)`` gives packets of mode 1 (a count per frame) whenever a
+    floor is set -- a row without one packs its cap in every frame -- and of mode 0 without a floor; ``decode_packed`` takes packets of
+    either mode, mixed, and ``decode(codes, n_q_frames=)`` a table of its own.  Every decode push from codes of such a session runs under
+    a count per frame (fc_engine_set_push_frame_nq); ``set_n_q`` still gives the count of the frames without one.  One launch per push at
+    every width.
+
     Graph replay (``graph=True``, off by default).  The library captures a steady push (neither the first of an utterance nor the
     final one) as a HIP graph and replays it for every later push with the same key: call form, width, parity of the side's push
     count, n_q, use_scale and every pointer.  The session therefore owns fixed device buffers sized for ``max_chunk``, a workspace and a
@@ -431,13 +507,13 @@ class CodecStream(_Session):
 
     def __init__(self, model, batch: int, n_q: Optional[int] = None, scale: Optional[torch.Tensor] = None,
                  max_chunk: Optional[int] = None, max_frames: Optional[int] = None, graph: bool = False, rvq_beam: Optional[int] = None,
-                 noise_floor_db=None, min_n_q: int = 1):
+                 noise_floor_db=None, min_n_q: int = 1, per_frame: bool = False):
         self.batch = int(batch)
         rows = None
         if n_q is not None and not isinstance(n_q, numbers.Integral):       # a count per utterance: refused before anything is opened
             rows = row_nq_list(model.arch, n_q, self.batch)
             n_q = max(rows)
-        super().__init__(model, self.batch, n_q, max_chunk, max_frames, graph, rvq_beam, min_n_q)
+        super().__init__(model, self.batch, n_q, max_chunk, max_frames, graph, rvq_beam, min_n_q, per_frame)
         self._row_nq = rows
         self.set_noise_floor(noise_floor_db)
         self.reset(scale)
@@ -464,6 +540,13 @@ class CodecStream(_Session):
         """device int32 [batch]: the stage counts the last encode push under a noise floor chose (the session's own table: the next such
         push overwrites it; nothing is read back)"""
         return self._nq_table
+
+    @property
+    def last_n_q_frames(self) -> Optional[torch.Tensor]:
+        """a per_frame session: device int32 [batch][frames of the last push]: the stage count of every frame of the last encode push
+        under a noise floor (a view of the session's own table: the next such push overwrites it; nothing is read back); None when
+        that push had no floor"""
+        return self._nqf
 
     @_on_device
     def reset(self, scale: Optional[torch.Tensor] = None) -> None:
@@ -502,7 +585,7 @@ class CodecStream(_Session):
         enc = self._buf("enc_out", (B, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
         n = C.c_int(0)
         ws = self._push_ws()
-        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam(), self._engine_floor():
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam(), self._engine_floor(Tf):
             self.engine._check(self.lib.fc_stream_encode(self._h, _ptr(wav), T, int(final), _ptr(codes), _ptr(quant), _ptr(enc), C.byref(n),
                                                          _ptr(ws), ws.numel(), self.engine._stream()))
         assert n.value == Tf
@@ -523,8 +606,12 @@ class CodecStream(_Session):
         if not packed:
             return res
         codes = res[0]
+        if codes.shape[-1] == 0:
+            return res + ([],)
+        if floor and self.per_frame:        # mode 1: the DEVICE counts per frame of the push
+            return res + (self._pack_rows(codes, None, None, self._nqf),)
         counts = self._nq_table if floor else self._row_nq       # under a floor: the DEVICE counts of the push, every packet carries its k_b
-        return res + (self._pack_rows(codes, None, counts) if codes.shape[-1] > 0 else [],)
+        return res + (self._pack_rows(codes, None, counts),)
 
     def _encode(self, wav: torch.Tensor, final: bool, want_enc_out: bool, one_push: bool = False) -> Tuple[torch.Tensor, ...]:
         wav = self.engine._wav_in(wav)
@@ -572,21 +659,34 @@ class CodecStream(_Session):
         self._dec.frames += frames
         outs = []
         for part, _ in pieces:
+            kf = None
+            if name == "tokens" and self.per_frame:     # the last column: the frames' stage counts (_with_counts)
+                kf = self._given("frame_nq", part[..., self.n_q].to(torch.int32).contiguous())
+                part = part[..., :self.n_q]
             part = self._given(name, part.contiguous())
             wav = self._buf("wav_out", (self.batch, self.engine.channels, part.shape[1] * self.hop), torch.float32)
             ws = self._push_ws()
-            with self._push_stream(), self._engine_row_nq(self._push_row_nq() if rows_apply else None):
+            with self._push_stream(), self._engine_row_nq(self._push_row_nq() if rows_apply and kf is None else None), \
+                    self._engine_push_frame_nq(kf):
                 self.engine._check(call(part, wav, ws))
             outs.append(self._out(wav))
         return outs[0] if len(outs) == 1 else torch.cat(outs, -1)
 
     @_on_device
-    def decode(self, codes: torch.Tensor, use_scale: bool = True, final: bool = False) -> torch.Tensor:
+    def decode(self, codes: torch.Tensor, use_scale: bool = True, final: bool = False, n_q_frames=None) -> torch.Tensor:
         """codes [B,Tf,n_q] (the reference's token layout) -> wav [B,C,Tf*hop].  final=True says the utterance ends here: it changes no
-        sample (the decoder has no right padding) but raises if frames are still held back, instead of returning nothing for ever."""
+        sample (the decoder has no right padding) but raises if frames are still held back, instead of returning nothing for ever.
+        n_q_frames [B,Tf] (a per_frame session alone): frame (b, t) sums its first n_q_frames[b, t] codes; without it every frame of a
+        row takes the row's count, as in any session."""
         codes = self.engine._dev(codes, torch.int64)
         if codes.dim() != 3 or codes.shape[2] != self.n_q:
             raise EngineError(f"codes must be [B,Tf,{self.n_q}], got {tuple(codes.shape)}")
+        if n_q_frames is not None and not self.per_frame:
+            raise EngineError("decode: n_q_frames is for a session opened with per_frame=True")
+        if self.per_frame:
+            if n_q_frames is None and self._row_nq is not None and codes.shape[0] == self.batch:
+                n_q_frames = torch.tensor(self._row_nq, dtype=torch.int64).view(-1, 1).expand(codes.shape[0], codes.shape[1])
+            codes = self._with_counts(codes, n_q_frames, self.n_q, "decode")
         return self._decode_pushes(codes, final, lambda part, wav, ws: self.lib.fc_stream_decode_codes(
             self._h, _ptr(part), part.shape[1], int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(), self.engine._stream()), rows_apply=True)
 
@@ -597,6 +697,11 @@ class CodecStream(_Session):
         self._packed_check()
         if len(packets) != self.batch:
             raise EngineError(f"this session streams {self.batch} utterances, got {len(packets)} packets")
+        if self.per_frame:      # packets of either mode, mixed: tokens and a count per frame on the device, nothing of the session changed
+            tokens, kf, frames = self._unpack_rows_frames(packets, "decode_packed")
+            if any(f != frames[0] for f in frames):
+                raise EngineError(f"decode_packed: the utterances of this session advance in lock-step, the packets hold {frames} frames")
+            return self.decode(tokens, use_scale=use_scale, final=final, n_q_frames=kf)
         tokens, frames, counts = self._unpack_rows(packets, "decode_packed")
         if any(f != frames[0] for f in frames):
             raise EngineError(f"decode_packed: the utterances of this session advance in lock-step, the packets hold {frames} frames")
@@ -658,6 +763,10 @@ class StreamSlots(_Session):
       (a silent caller costs ``min_n_q`` stages); ``set_n_q`` remains the cap; a slot without a floor keeps its fixed count; an idle slot
       is left alone.  ``last_n_q_rows`` reads the counts back once, {slot: k}; the packets of ``encode(packed=True)`` carry them.
 
+    * ``open_slots(..., per_frame=True)``: as for ``CodecStream`` ("Noise floor per frame"): under a floor every frame of a slot's push takes
+      its own count (``min_n_q`` may be 0), ``last_n_q_frames`` is {slot: device int32 [its frames of the last push]}, packets are of mode 1
+      and ``decode_packed`` takes either mode, mixed in one push.  ``SlotRecord`` is what it was: ``per_frame`` belongs to the session.
+
     Per slot: pushes are held back until ``min_first_samples`` / ``min_first_frames`` have arrived, then everything held comes
     out at once; an utterance that ends shorter than that raises (the offline call's job); what is longer than ``max_chunk`` is split.
     A call is checked as a whole before anything is pushed: a refused call changes nothing, and neither does a call whose first push
@@ -685,10 +794,11 @@ class StreamSlots(_Session):
     _graph_family = "fc_graphslots"
 
     def __init__(self, model, slots: int, n_q: Optional[int] = None, max_chunk: Optional[int] = None, max_frames: Optional[int] = None,
-                 graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1):
+                 graph: bool = False, rvq_beam: Optional[int] = None, noise_floor_db=None, min_n_q: int = 1, per_frame: bool = False):
         self.slots = int(slots)
         self.pad_value = 0.0          # what the assembled batch holds behind a row's count and in idle rows (never read; a test aid)
-        super().__init__(model, self.slots, n_q, max_chunk, max_frames, graph, rvq_beam, min_n_q)
+        super().__init__(model, self.slots, n_q, max_chunk, max_frames, graph, rvq_beam, min_n_q, per_frame)
+        self._last_nqf: Dict[int, torch.Tensor] = {}       # per_frame: {slot: the counts of its frames of the last encode push under a floor}
         if noise_floor_db is not None and not isinstance(noise_floor_db, numbers.Real):
             noise_floor_db = noise_floor_db.tolist() if hasattr(noise_floor_db, "tolist") else list(noise_floor_db)
             if len(noise_floor_db) != self.slots:
@@ -724,6 +834,13 @@ class StreamSlots(_Session):
         device table; a slot that was idle in a push keeps its entry"""
         return dict(enumerate(self._nq_table.tolist()))
 
+    @property
+    def last_n_q_frames(self) -> Dict[int, torch.Tensor]:
+        """a per_frame session: {slot: device int32 [its frames of the last encode push]} for the slots that emitted frames in the last
+        encode push under a noise floor (a slot without a floor holds its cap in every frame); nothing is read back until the caller
+        asks a tensor for its values"""
+        return dict(self._last_nqf)
+
     _KEEP = object()
 
     def start(self, slot: int, scale=None, n_q=None, noise_floor_db=_KEEP) -> None:
@@ -758,9 +875,12 @@ class StreamSlots(_Session):
             floats = buf[0, :self._record_floats(enc, dec)].clone()
         return SlotRecord(floats, meta, enc, dec, self._row_nq[slot], self._floor_db[slot], self._scale[slot])
 
-    def _importable(self, slot, n_q: int, floor) -> int:
+    def _importable(self, slot, n_q: int, floor, dec: Optional[_Side] = None) -> int:
         """what import_slot and migrate refuse before touching anything"""
         slot = self._slot(slot)
+        if dec is not None and not self.per_frame and any(t.dtype == torch.int64 and t.shape[-1] == self.n_q + 1 for t in dec.head):
+            raise EngineError(f"slot {slot}: the record's held decode frames carry a stage count per frame (a per_frame session's); "
+                              "a session opened with per_frame=True takes it; nothing was changed")
         if any(self._poisoned):
             bad = [b for b, p in enumerate(self._poisoned) if p]
             raise EngineError(f"slot {slot}: a push of this session failed inside the library (slots {bad} await start()); it takes no record "
@@ -775,6 +895,9 @@ class StreamSlots(_Session):
         """the wrapper's side of an import: whatever the slot held is abandoned, as start() does"""
         self._row_nq[slot], self._floor_db[slot], self._scale[slot] = int(n_q), floor, float(scale)
         self._enc[slot], self._dec[slot] = enc.copy(device=self.device), dec.copy(device=self.device)
+        if self.per_frame:      # held decode frames of a session without per_frame: every one with the record's count
+            self._dec[slot].head = [self._with_counts(t, None, int(n_q), f"slot {slot}") if t.dtype == torch.int64 and t.shape[-1] == self.n_q else t
+                                    for t in self._dec[slot].head]
         self._poisoned[slot] = False
 
     def _import_rows(self, slots: List[int], buf: torch.Tensor, metas) -> None:
@@ -793,7 +916,7 @@ class StreamSlots(_Session):
         ``CodecStream`` of a model with the same architecture -- and abandons what it held, as ``start`` does; the call then goes on bit
         for bit as if it had never moved.  Refused before anything is touched: a record whose n_q exceeds the session's, a session
         with invalidated slots, and whatever the library refuses (another layout, frames past max_frames, cache against no cache)."""
-        slot = self._importable(slot, rec.n_q, rec.noise_floor_db)
+        slot = self._importable(slot, rec.n_q, rec.noise_floor_db, rec.dec)
         if rec.floats is not None:
             floats = self.engine._dev(rec.floats, torch.float32).reshape(1, -1)
             self._import_rows([slot], floats, [rec.meta])
@@ -808,7 +931,7 @@ class StreamSlots(_Session):
         pairs = [(self._exportable(a), b) for a, b in mapping.items()]
         seen = set()
         for a, b in pairs:
-            dst._importable(b, self._row_nq[a], self._floor_db[a])
+            dst._importable(b, self._row_nq[a], self._floor_db[a], self._dec[a])
             if b in seen:
                 raise EngineError(f"slot {b}: named twice as a destination; nothing was changed")
             seen.add(b)
@@ -905,12 +1028,16 @@ class StreamSlots(_Session):
         quant = self._buf("quantized", (S, Tf, D), torch.float32)
         enc = self._buf("enc_out", (S, Tf, D), torch.float32) if (self.arch.bypass_quantizer or want_enc_out) else None
         ws = self._push_ws()
-        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam(), self._engine_floor():
+        with self._push_stream(), self._engine_row_nq(self._push_row_nq()), self._engine_rvq_beam(), self._engine_floor(Tf):
             self.engine._check(self.lib.fc_slots_encode(self._h, _ptr(wav), Tc, counts, flags, _ptr(scale), _ptr(codes), _ptr(quant), _ptr(enc),
                                                         _ptr(ws), ws.numel(), self.engine._stream()))
         out = {}
+        self._last_nqf = {}
+        table = None if self._nqf is None else self._nqf.clone()      # the table is the next push's to overwrite: ONE copy, on the device
         for slot, (w, f) in rows.items():
             n = self.engine.frames(w.shape[-1]) if f & FC_SLOT_FINAL else w.shape[-1] // self.hop
+            if table is not None and n > 0:
+                self._last_nqf[slot] = table[slot, :n]
             if self.arch.bypass_quantizer:     # codec_basic.py:700-701: the encoder output in place of the quantised embeddings
                 e = self._out(enc[slot, :n])
                 out[slot] = (torch.zeros((n,), dtype=torch.long, device=self.device), e, e)
@@ -936,6 +1063,11 @@ class StreamSlots(_Session):
         codes = torch.zeros((self.n_q, len(slots), max(frames)), dtype=torch.int64, device=self.device)
         for j, slot in enumerate(slots):
             codes[:, j, :frames[j]] = res[slot][0]
+        if floor and self.per_frame:        # mode 1: the DEVICE counts per frame of the push (a slot without a floor: its cap in every frame)
+            kf = torch.zeros((len(slots), max(frames)), dtype=torch.int32, device=self.device)
+            for j, slot in enumerate(slots):
+                kf[j, :frames[j]] = self._last_nqf[slot]
+            return res, dict(zip(slots, self._pack_rows(codes, frames, None, kf)))
         # under a floor: the DEVICE counts of the push (a slot without a floor had its cap written there), every packet carries its k_b
         counts = self._nq_table[torch.tensor(slots, device=self.device)] if floor else [self._row_nq[slot] for slot in slots]
         return res, dict(zip(slots, self._pack_rows(codes, frames, counts)))
@@ -969,6 +1101,12 @@ class StreamSlots(_Session):
             x = self._buf("emb", (S, Tf, inner), torch.float32).fill_(self.pad_value)
         else:
             x = self._buf("tokens", (S, Tf, inner), torch.int64).zero_()
+        kf = None
+        if not emb and self.per_frame:          # the last column of a slot's rows: its frames' stage counts (_with_counts)
+            kf = self._buf("frame_nq", (S, Tf), torch.int32).zero_()
+            for slot, (t, f) in rows.items():
+                kf[slot, :t.shape[0]] = t[:, inner]
+            rows = {slot: (t[:, :inner], f) for slot, (t, f) in rows.items()}
         for slot, (t, f) in rows.items():
             x[slot, :t.shape[0]] = t
         starts = [slot for slot, (t, f) in rows.items() if f & FC_SLOT_START]
@@ -982,13 +1120,13 @@ class StreamSlots(_Session):
                 rc = self.lib.fc_slots_decode_emb(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), _ptr(ws), ws.numel(),
                                                   self.engine._stream())
             else:
-                with self._engine_row_nq(self._push_row_nq()):
+                with self._engine_row_nq(self._push_row_nq() if kf is None else None), self._engine_push_frame_nq(kf):
                     rc = self.lib.fc_slots_decode_codes(self._h, _ptr(x), Tf, counts, flags, int(use_scale), _ptr(wav), None, _ptr(ws), ws.numel(),
                                                         self.engine._stream())
         self.engine._check(rc)
         return {slot: (self._out(wav[slot, :, :t.shape[0] * self.hop]),) for slot, (t, f) in rows.items()}
 
-    def _decode(self, pushes, use_scale, emb):
+    def _decode(self, pushes, use_scale, emb, n_q_frames=None):
         inner, dtype = (self.arch.dimension, torch.float32) if emb else (self.n_q, torch.int64)
 
         def as_tn(item):
@@ -998,15 +1136,22 @@ class StreamSlots(_Session):
                 raise EngineError(f"a slot's {'emb' if emb else 'codes'} must be [Tf,{inner}], got {tuple(t.shape)}")
             return t, final
         pushes = {slot: as_tn(item) for slot, item in pushes.items()}
+        if n_q_frames is not None and (emb or not self.per_frame):
+            raise EngineError("decode: n_q_frames is for a session opened with per_frame=True")
+        if not emb and self.per_frame:          # every frame with its stage count: the table's, else the slot's own count
+            given = {self._slot(slot): v for slot, v in (n_q_frames or {}).items()}
+            pushes = {slot: (self._with_counts(t, given.get(self._slot(slot)), self._row_nq[self._slot(slot)], f"slot {slot}"), final)
+                      for slot, (t, final) in pushes.items()}
         plan = self._plan(self._dec, pushes, 0, 1, self.min_first_frames, "frames")
         outs = self._run(self._dec, plan, lambda rows: self._decode_call(rows, use_scale, emb))
         return {slot: torch.cat([p[0] for p in parts], -1) if len(parts) > 1 else parts[0][0] for slot, parts in outs.items()}
 
     @_on_device
-    def decode(self, pushes, use_scale: bool = True) -> Dict[int, torch.Tensor]:
+    def decode(self, pushes, use_scale: bool = True, n_q_frames=None) -> Dict[int, torch.Tensor]:
         """{slot: (codes [Tf,n_q], final)} -> {slot: wav [C,Tf*hop]}.  final=True says the slot's utterance ends here: it changes no sample
-        but raises if frames are still held back, and the slot then needs ``start``."""
-        return self._decode(pushes, use_scale, False)
+        but raises if frames are still held back, and the slot then needs ``start``.  n_q_frames {slot: [Tf]} (a per_frame session
+        alone): a stage count per frame of the slot's codes; a slot without an entry takes its own count in every frame."""
+        return self._decode(pushes, use_scale, False, n_q_frames)
 
     @_on_device
     def decode_packed(self, pushes, use_scale: bool = True) -> Dict[int, torch.Tensor]:
@@ -1017,6 +1162,10 @@ class StreamSlots(_Session):
         if not items:
             return {}
         slots = list(items)
+        if self.per_frame:      # packets of either mode, mixed in one push; nothing of the session is changed
+            tokens, kf, frames = self._unpack_rows_frames([items[slot][0] for slot in slots], "decode_packed")
+            return self.decode({slot: (tokens[j, :frames[j]], items[slot][1]) for j, slot in enumerate(slots)}, use_scale=use_scale,
+                               n_q_frames={slot: kf[j, :frames[j]] for j, slot in enumerate(slots)})
         tokens, frames, counts = self._unpack_rows([items[slot][0] for slot in slots], "decode_packed")
         keep = list(self._row_nq)
         for j, slot in enumerate(slots):

@@ -328,6 +328,29 @@ int fc_engine_set_floor(fc_engine* e, const double* floor_rows /* host [B] or NU
 int fc_engine_set_floor_form(fc_engine* e, int chain, double* row_errors_out, float* stage_errors_out, float* sub_quants_out,
                              const int32_t* off_rows /* host [B] or NULL */, void* stream);
 
+/* ---- a stage count per FRAME of a session push, by a noise floor (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
+ * By the push frame rule of csrc/rvq_rate_kernels.h ("THE PUSH FRAME RULE"; funcodec_amd/engine.py::floor_pick_frames restates it on the
+ * host): given AFTER fc_engine_set_floor, it turns the floor set there into frame mode for the encode pushes of both session kinds and
+ * for the per-op hook fc_rvq_encode_rate; cleared with the floor (NULL floors), and by every new fc_engine_set_floor.  Frame t of row b
+ * takes the smallest k in [min_nq, cap_b] with (double)err[k][b,t] <= floor_b -- comparisons only; a frame already at or below the floor
+ * takes min_nq; a missed floor takes the frame's best k, first on ties; a frame that is not finite, and every frame of a row switched
+ * off, takes cap_b; frames behind a row's frames in the push take 0; an idle row's counts are left unwritten.  min_nq in
+ * [0, num_quantizers] replaces the one given to fc_engine_set_floor: a frame may take no stage.  A frame's count depends on that frame's
+ * quantiser input alone, not on how the audio is cut into pushes.  Frame (b,t) of codes and quantized is what the same push with
+ * n_q = k_t gives it (greedy: bit for bit, zeros in codes[k_t:]; with a search: the first k_t codes of the full-depth path).
+ *   n_q_frames_out   dev i32 [B][Tf of the push], dense, required; n_q_rows_out of fc_engine_set_floor is then NOT written
+ * ONE launch at every width (a workgroup per 16 frames of a row), or four with fc_engine_set_floor_form(chain = 1): the same bits on every
+ * row that has frames.  row_errors_out of fc_engine_set_floor_form is not written in frame mode (there are no row sums); the hook needs
+ * stage_errors_out alone.  A captured push is keyed by the table's address, min_nq and the mode, never by a floor.
+ * Refused before anything changes: no floor set, min_nq outside [0, num_quantizers] or above a row's cap, a null n_q_frames_out. */
+int fc_engine_set_floor_frames(fc_engine* e, int min_nq, int32_t* n_q_frames_out /* dev [B][Tf] */, void* stream);
+/* By the count of csrc/rvq_rate_kernels.h (a count per frame): fc_engine_set_frame_nq for the decode pushes of sessions that follow
+ * (fc_stream_decode_codes, fc_slots_decode_codes): frame (b,t) of the push sums its first n_q_frames[b][t] codes (clamped to [0, n_q]; 0
+ * behind a slot's frames in the push).  The pointer is BORROWED; NULL clears the table.  Part of a captured push's key.  Refused:
+ * together with a row table (fc_engine_set_row_nq); a decode push of another B or Tfc, before its first launch; every offline decode
+ * call while it is set. */
+int fc_engine_set_push_frame_nq(fc_engine* e, const int32_t* n_q_frames /* DEV i32 [B][Tfc] or NULL */, int B, int Tfc, void* stream);
+
 /* ---- the bit stream: one self-describing packet per row (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
  * csrc/code_pack_kernels.h states the packet rule (8-byte little-endian header: u32 frames, u8 k, u8 bits, u8 mode = 0, u8 0; payload
  * value t * k + i = codes[i][b][t] in `bits` bits each, LSB first, pad bits 0) and the device row (pitch = the largest packet rounded up
@@ -359,8 +382,9 @@ int fc_codes_unpack(const uint8_t* packets, size_t pitch, int B, int Tf, int n_q
 /* ---- the bit stream, mode 1: a stage count per frame (entry points added without a struct change: FC_ABI_VERSION stays 7) ----
  * csrc/code_pack_kernels.h states mode 1 (header: u32 frames, u8 kmax, u8 bits, u8 mode = 1, u8 0; a counts section of cbits = bit
  * length of kmax bits per frame, padded to a 32-bit word; a codes section of value S_t + i = codes[i][b][t], frame-major);
- * funcodec_amd/io.py restates it on the host.  None of the calls needs an engine.  Not built: entropy coding, a fused decode from packets,
- * frame mode in stream and slot sessions. */
+ * funcodec_amd/io.py restates it on the host.  None of the calls needs an engine.  Sessions opened per frame write and read mode 1
+ * (fc_engine_set_floor_frames, fc_engine_set_push_frame_nq).  Not built: entropy coding, a fused decode from packets, frame mode by target
+ * SNR in stream and slot sessions, a rule with memory over pushes. */
 /* By the packet rule of csrc/code_pack_kernels.h (mode 1): the row pitch for up to `frames` frames of up to n_q stages each: the largest
  * packet (kmax = n_q, every count n_q) rounded up to 16; 0 for arguments outside the format. */
 size_t fc_frame_packet_pitch(int frames, int n_q, int bits);
